@@ -30,10 +30,6 @@ import time
 # the host driver shares device memory between the ranks of a node through dmabuf handles only (RCCL, multi-process runs);
 # must be in the environment before the HIP runtime starts
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-# eight hardware queues: four rollout worker groups (two streams each) run concurrently (trainer.py, rollout_groups: auto);
-# read by the HIP runtime when it starts, like the variable above
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-os.environ.setdefault("ETM_HW_QUEUES_SET_EARLY", "1")   # marker for trainer.py: the line above ran before the HIP runtime started
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(REPO, "episodic-transformer-memory-ppo_amd")
@@ -239,6 +235,34 @@ def worker_processes_run(updates=3, warmup=1):
             "envs_per_process": rec["config"].get("envs_per_process"), "env": "pool 0 (fresh U[0,1) draw per observation), worker processes, own process"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: everything written, in all
+MEMORY_SAMPLE = 1 << 20           # elements of the episode memory bank written (a fixed, seeded sample: the bank is hundreds of MB)
+
+
+def dump_outputs(trainer, stats, out_dir):
+    """What the last timed update handed its caller, as ``out_dir/<name>.npy`` in float32: the rollout's buffer fields (actions,
+    log-probabilities, values, GAE advantages, rewards, done flags), a fixed sample of the episode memories it wrote (flat indices
+    drawn by a generator seeded with 0, stored alongside in float64, which holds them exactly), the loss statistics of every
+    optimiser step, and every parameter after the update.  Returns the file names and the bytes written."""
+    b = trainer.buffer
+    arrays = {f"rollout_{k}": getattr(b, k) for k in ("actions", "log_probs", "values", "advantages")}
+    arrays["rollout_rewards"], arrays["rollout_dones"] = b.rewards_dev, b.dones_dev
+    mem = b.memories
+    idx = torch.randint(0, mem.numel(), (min(MEMORY_SAMPLE, mem.numel()),), generator=torch.Generator().manual_seed(0)).sort().values
+    arrays["memories_sample"] = mem[tuple(torch.as_tensor(np.stack(np.unravel_index(idx.numpy(), tuple(mem.shape)))).to(mem.device))]
+    arrays["train_stats"] = torch.as_tensor(np.asarray(stats, dtype=np.float32))
+    arrays.update({f"param.{n}": p for n, p in trainer.model.named_parameters()})
+    arrays = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in arrays.items()}
+    arrays["memories_sample_index"] = idx.numpy().astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(arrays), total
+
+
 def compact_line(full, full_path):
     """The driver's line: the contract's keys, the roofline / cpu_baseline objects with numbers and one short note each, and
     ONE {kernel: [avg_ms, frac]} summary of the micro-benchmarks.  Everything else (per-kernel tables, models, prose) is in
@@ -332,6 +356,12 @@ def main():
                          "(large BAR; round 6) instead of pinned memory + a copy-engine transfer per worker group and step")
     ap.add_argument("--gen-threads", type=int, default=None,
                     help="pool 0, in-process environments: host threads that draw a step's observation rows (libetm_envgen.so's pool)")
+    ap.add_argument("--tunable-gemm", choices=("on", "off"), default="off",
+                    help="let PyTorch pick each torch GEMM's solution by timing (trainer.py, tunable_gemm).  Off by default: the pick, and so the "
+                         "summation order, can change from run to run, and a changed rounding flips sampled actions, so runs part ways")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rollout buffer, sample of the episode memories, loss "
+                         "statistics, parameters) as DIR/<name>.npy in float32 (rank 0; at most 64 MB)")
     args = ap.parse_args()
     global CONFIG_NAME
     CONFIG_NAME = args.config
@@ -390,6 +420,7 @@ def main():
     cfg["dp_overlap"] = args.dp_overlap == "on"
     cfg["direct_observation_rows"] = args.direct_rows == "on"
     cfg["dp_graph_collective"] = args.dp_graph_collective == "on"
+    cfg["tunable_gemm"] = args.tunable_gemm == "on"
     if args.worker_processes != "config":
         cfg["worker_processes"] = args.worker_processes == "on"
     if args.envs_per_process is not None:
@@ -406,6 +437,8 @@ def main():
     np.random.seed(0)
     trainer = PPOTrainer(cfg, run_id="bench", device=device, dp=dp, first_worker_id=rank * cfg["n_workers"], tensorboard=False)
 
+    last_stats = []
+
     def one_update(i):
         lr, beta, clip = trainer.schedules(i)
         t0 = time.perf_counter()
@@ -415,7 +448,7 @@ def main():
         torch.cuda.synchronize(device)
         t1 = time.perf_counter()
         lib.etm_profile_set_tag(1)
-        trainer._train_epochs(lr, clip, beta)
+        last_stats[:] = trainer._train_epochs(lr, clip, beta)[0]
         torch.cuda.synchronize(device)
         t2 = time.perf_counter()
         return t1 - t0, t2 - t1
@@ -449,6 +482,7 @@ def main():
     prof = etm_lib.profile_collect() if not args.no_profile else {}
     if dp is not None:
         elapsed = dp.max_over_ranks(elapsed)
+    dumped = dump_outputs(trainer, last_stats, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # gradient all-reduce on its own (message = 4 * params bytes, bus bandwidth against the xGMI link rate);
     # measured AFTER the timed region, on every rank, with the trainer's own flat bucket and collective call
@@ -634,7 +668,7 @@ def main():
                        "attention": args.attention, "dp_collective": dp.collective if dp is not None else None,
                        "dp_step": (None if dp is None else "one_graph" if getattr(trainer, "_dp_one_graph", False) else "graph_a+allreduce+graph_b"),
                        "numa_pinned_cpus": len(numa_cpus) if numa_cpus else None,
-                       "rollout_groups": len(getattr(trainer, "_groups", None) or []) or 1, "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+                       "rollout_groups": len(getattr(trainer, "_groups", None) or []) or 1, "tunable_gemm": cfg["tunable_gemm"],
                        "encoder_products": trainer.model.encoder_products + (" (f32 products as 6 bf16 MFMA products of exactly split operands; error vs float64 below the fp32 MFMA kernels')" if trainer.model.encoder_products == "bf16x3" else ""),
                        "observation_rows": ("direct (host writes into device memory" + (", HDP flush register written)" if etm_ops._direct_mode.get(device.index) == 2 else ")")
                                             if getattr(trainer, "_direct_rows", False) else "pinned + upload"),
@@ -648,6 +682,8 @@ def main():
             "kernels_train": kernels,
             "kernels_rollout": rollout_k,
         }
+        if dumped:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped[0], "bytes": dumped[1]}
         if not args.no_rooflines:
             try:
                 import kernel_rooflines

@@ -28,40 +28,11 @@ from collections import deque
 import numpy as np
 import torch
 
-# Four worker groups want four pairs of streams (upload + step graph) running CONCURRENTLY; the HIP runtime maps streams onto
-# GPU_MAX_HW_QUEUES hardware queues (default 4) and reads that variable once, when it starts (the first device query of the
-# process).  With 4 queues four groups serialise (rollout 0.161 s per update instead of 0.087 s; two groups: 0.094 s), so "auto"
-# only trusts a value that is in the environment when this module is imported -- the entry points (bench.py, train.py, the
-# tools) set GPU_MAX_HW_QUEUES=8 as their first statement, before torch is imported; a caller who does not gets two groups.
-def _trusted_hw_queues() -> int:
-    """GPU_MAX_HW_QUEUES as the HIP runtime of this process has read it (or will): the value in os.environ counts only if the runtime
-    has not started yet, or the process was STARTED with it (/proc/self/environ), or one of this package's entry points set it as
-    its first statement (they leave the marker ETM_HW_QUEUES_SET_EARLY).  An application that initialised torch.cuda first and set
-    the variable afterwards runs on the runtime's default four queues whatever os.environ says now: 0."""
-    try:
-        val = int(os.environ.get("GPU_MAX_HW_QUEUES", "0"))
-    except ValueError:
-        return 0
-    if val < 8 or not torch.cuda.is_initialized() or os.environ.get("ETM_HW_QUEUES_SET_EARLY") == "1":
-        return val
-    try:
-        with open("/proc/self/environ", "rb") as f:
-            for item in f.read().split(b"\0"):
-                if item.startswith(b"GPU_MAX_HW_QUEUES=") and int(item.split(b"=", 1)[1]) >= 8:
-                    return val
-    except (OSError, ValueError):
-        pass
-    return 0
-
-
-_HW_QUEUES_AT_IMPORT = _trusted_hw_queues()
-
-
+# Four worker groups want four pairs of streams (upload + step graph) running CONCURRENTLY; the HIP runtime maps streams onto its
+# hardware queues, four by default.  With 4 queues four groups serialise (rollout 0.161 s per update instead of 0.087 s; two
+# groups: 0.094 s), so "auto" forms two groups; four remain available as an explicit ``rollout_groups: 4``.
 def default_rollout_groups(num_workers: int, min_group: int) -> int:
-    """``rollout_groups: auto``: 4 when the runtime has 8 hardware queues (see above) and the groups keep ``min_group`` workers,
-    else 2 (when THEY keep ``min_group`` workers), else 1."""
-    if _HW_QUEUES_AT_IMPORT >= 8 and num_workers % 4 == 0 and num_workers // 4 >= min_group:
-        return 4
+    """``rollout_groups: auto``: 2 when the groups keep ``min_group`` workers, else 1."""
     if num_workers % 2 == 0 and num_workers // 2 >= min_group:
         return 2
     return 1
@@ -155,7 +126,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         self.writer = _make_writer(run_id) if tensorboard else _NullWriter()
 
         # environments (batched front-end over the upstream per-worker protocol)
-        # rollout_groups (default "auto": 4 with 8 hardware queues, else 2): the workers are stepped as that many groups in a software
+        # rollout_groups (default "auto": 2): the workers are stepped as that many groups in a software
         # pipeline -- while the host steps one group's environments the device runs the other groups' forward passes (small step
         # graphs overlap almost perfectly on the GPU: 117 us per round of two, 122 us per round of four vs 112 us each,
         # tools/rollout_profile.py; config 3: rollout 0.094 s per update with two groups, 0.087 s with four).  Needs an environment front-end made
@@ -170,8 +141,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         if n_groups < 1 or self.num_workers % n_groups != 0 or self.num_workers // n_groups < min_group:
             n_groups = 1
         if config.get("rollout_groups", "auto") == "auto" and os.environ.get("ETM_QUIET") != "1":
-            print(f"[etm] rollout worker groups: {n_groups} (rollout_groups: auto; hardware queues the HIP runtime is known to have been "
-                  f"started with: {_HW_QUEUES_AT_IMPORT or 'runtime default (4)'})", file=sys.stderr, flush=True)
+            print(f"[etm] rollout worker groups: {n_groups} (rollout_groups: auto)", file=sys.stderr, flush=True)
         # round 5: the rank's host CPU share (affinity mask, cgroup CPU quota, ranks per node) against the threads a rollout keeps
         # busy -- trainer thread on the action flag, observation-copier helpers, worker processes (etm/hostcpu.py).  With room to
         # spare nothing changes; without it the helpers sleep between jobs, the copier / the worker processes shrink to what fits and

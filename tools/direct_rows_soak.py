@@ -9,8 +9,6 @@ the optimisation phase between rollouts (the staging array's lines are then long
 pattern); train=0 samples back to back (the copy out of the staging array has just read every line)."""
 import os, sys, time
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-os.environ.setdefault("ETM_HW_QUEUES_SET_EARLY", "1")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "episodic-transformer-memory-ppo_amd"))
 import numpy as np, torch

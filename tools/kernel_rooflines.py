@@ -24,8 +24,6 @@ events (etm_profile_*: an event pair on the launch stream around each kernel), a
                 (W x every matrix of the chain + the workers' K | V window columns) / time, and the length of its dependency chain
 """
 import os
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # (as bench.py: the rollout_step target builds a trainer -- rollout_groups: auto)
-os.environ.setdefault("ETM_HW_QUEUES_SET_EARLY", "1")   # marker for trainer.py: the line above ran before the HIP runtime started
 
 import sys
 

@@ -22,8 +22,6 @@ import json
 import os
 import sys
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-os.environ.setdefault("ETM_HW_QUEUES_SET_EARLY", "1")
 os.environ.setdefault("ETM_TUNABLE_GEMM", "0")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (REPO, os.path.join(REPO, "episodic-transformer-memory-ppo_amd"), os.path.join(REPO, "tests", "golden"), os.path.join(REPO, "tests")):

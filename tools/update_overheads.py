@@ -8,8 +8,6 @@ import sys
 import time
 
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-os.environ.setdefault("ETM_HW_QUEUES_SET_EARLY", "1")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(REPO, "episodic-transformer-memory-ppo_amd")
 for p in (REPO, PKG):
