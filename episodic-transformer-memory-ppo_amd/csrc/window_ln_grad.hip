@@ -29,7 +29,12 @@ struct LnGradParams {
   long long vec_hs, vec_ns;                              // u / gz [H, N, D] strides (floats)
   float *partial;                                        // [grid][2 D]
   int N, L, D, H, chunk;                                 // chunk = samples per XCD
+  const float *guard_g, *guard_b;                        // non-NULL: the guarded pass (etm_window_ln_grad_guarded)
+  float tau;
 };
+
+// the columns the from-outputs identity cannot serve: its error in d gain[c] grows as (|g_c| + |b_c|) / |g_c| (see below)
+__device__ __forceinline__ bool ln_gain_small(float g, float b, float tau) { return fabsf(g) < tau * fmaxf(1.f, fabsf(b)); }
 
 // NJ = D / 128: lane owns columns 2 lane + 128 j, + 1 (a float2 per j)
 template <int NJ, int HMAX>
@@ -37,6 +42,11 @@ __global__ __launch_bounds__(WG_T) void window_ln_grad_kernel(const LnGradParams
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int L = p.L, D = p.D, H = p.H;
+  if (p.guard_g) {                                       // guarded pass: nothing to do unless some column's gain is small
+    int small = 0;
+    for (int c = tid; c < D; c += WG_T) small |= ln_gain_small(p.guard_g[c], p.guard_b[c], p.tau);
+    if (!__syncthreads_or(small)) return;                // (the same answer in every workgroup)
+  }
   float *de_s = sm;                 // [H][L]
   float *at_s = de_s + H * L;       // [H][L]
   float *st_s = at_s + H * L;       // [L][2]
@@ -139,8 +149,10 @@ __global__ __launch_bounds__(WG_T) void window_ln_grad_kernel(const LnGradParams
     *reinterpret_cast<float2 *>(&red[wave * 2 * D + D + 2 * lane + 128 * j]) = db[j];
   }
   __syncthreads();
-  for (int c = tid; c < 2 * D; c += WG_T)
+  for (int c = tid; c < 2 * D; c += WG_T) {
+    if (p.guard_g && !(c < D && ln_gain_small(p.guard_g[c], p.guard_b[c], p.tau))) continue;     // guarded: small-gain d gain only
     p.partial[(long long)blockIdx.x * 2 * D + c] = ((red[c] + red[2 * D + c]) + red[4 * D + c]) + red[6 * D + c];
+  }
 }
 
 // ---- Round 6: the same two gradients WITHOUT a pass over the window rows.  With xfull = xhat g + b (what the window passes read):
@@ -152,8 +164,12 @@ __global__ __launch_bounds__(WG_T) void window_ln_grad_kernel(const LnGradParams
 // an elementwise pass over four [H, N, D] tensors (50 MB at config 5) instead of a third read of the gathered window (402 MB).
 // One wave per sample at a time (lane = columns 2 lane + 128 j), per-lane running sums, the workgroup's four waves added in wave
 // order, the division by the gain per workgroup row (distributes over the fixed-order sum of the rows), partial rows as above.
-// The division is the price: a gain of exactly zero has no gradient through this identity (the rows-based kernel above stays for
-// that and as the cross-check of tests/test_gpu_parity.py); LayerNorm gains start at 1 and AdamW moves them by ~lr per step.
+// The division is the price: a gain of exactly zero has no gradient through this identity, and the rounding error of column c grows
+// as (|g_c| + |b_c|) / |g_c| (z - b satt cancels).  So the default path launches the rows kernel above right after this one, in its
+// GUARDED form (etm_window_ln_grad_guarded): every workgroup reads the gain first and leaves at once unless some column has
+// |g_c| < tau max(1, |b_c|); if one has, it rewrites the d gain entries of exactly those columns in every partial row (the sum over
+// the rows of a column is then the rows kernel's; the other columns keep this kernel's bits).  Gains cross zero under weight decay
+// and checkpoints carry any value, so this is not optional (tests/test_gpu_parity.py: the LayerNorm value-edge tests).
 struct LnOutParams {
   const float *u, *gz, *du, *z, *att, *d_e, *ln_g, *ln_b;
   long long vec_hs, vec_ns;
@@ -242,11 +258,10 @@ extern "C" int etm_window_ln_grad_rows(int N) {
 // adds the rows (etm_colsum_reduce_grouped, or any fixed-order sum).  u / gz: the folded vectors [H, N, D] with the given head /
 // sample strides (floats); att, d_e [N, H, L] as etm_window_bwd leaves them; ln_stats [N, L, 2]; pos / pidx as in etm_window_fwd
 // (NULL: the bank rows already contain their positional rows).  D % 128 == 0, D <= 512, H <= 8, L <= 128.
-extern "C" int etm_window_ln_grad(const float *bank, int64_t ep_stride, int64_t row_stride, const int64_t *ep, const int64_t *win,
-                                  const int64_t *pidx, const float *pos, const float *ln_stats, const float *att, const float *d_e,
-                                  const float *u, const float *gz, int64_t vec_head_stride, int64_t vec_sample_stride, float *partial,
-                                  int N, int L, int D, int H, void *stream) {
-  (void)hipGetLastError();
+static int window_ln_grad_launch(const float *bank, int64_t ep_stride, int64_t row_stride, const int64_t *ep, const int64_t *win,
+                                 const int64_t *pidx, const float *pos, const float *ln_stats, const float *att, const float *d_e,
+                                 const float *u, const float *gz, int64_t vec_head_stride, int64_t vec_sample_stride, const float *guard_g,
+                                 const float *guard_b, float tau, float *partial, int N, int L, int D, int H, void *stream) {
   if (!bank || !win || !ln_stats || !att || !d_e || !u || !gz || !partial) return ETM_EINVAL;
   if (N <= 0 || L <= 0 || D <= 0 || H <= 0) return ETM_EINVAL;
   if ((pos != nullptr) != (pidx != nullptr)) return ETM_EINVAL;
@@ -258,6 +273,7 @@ extern "C" int etm_window_ln_grad(const float *bank, int64_t ep_stride, int64_t 
   p.pos = pos; p.ln_stats = ln_stats; p.att = att; p.d_e = d_e; p.u = u; p.gz = gz;
   p.vec_hs = vec_head_stride; p.vec_ns = vec_sample_stride; p.partial = partial;
   p.N = N; p.L = L; p.D = D; p.H = H; p.chunk = (N + 7) / 8;
+  p.guard_g = guard_g; p.guard_b = guard_b; p.tau = tau;
   const int grid = etm_window_ln_grad_rows(N);
   const size_t sm = (size_t)(2 * H * L + 2 * L) * sizeof(float) + (size_t)2 * L * sizeof(long long) + (size_t)WG_WAVES * 2 * D * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
@@ -272,6 +288,30 @@ extern "C" int etm_window_ln_grad(const float *bank, int64_t ep_stride, int64_t 
   }
 #undef LG_LAUNCH
   return etm_launch_status();
+}
+
+extern "C" int etm_window_ln_grad(const float *bank, int64_t ep_stride, int64_t row_stride, const int64_t *ep, const int64_t *win,
+                                  const int64_t *pidx, const float *pos, const float *ln_stats, const float *att, const float *d_e,
+                                  const float *u, const float *gz, int64_t vec_head_stride, int64_t vec_sample_stride, float *partial,
+                                  int N, int L, int D, int H, void *stream) {
+  (void)hipGetLastError();
+  return window_ln_grad_launch(bank, ep_stride, row_stride, ep, win, pidx, pos, ln_stats, att, d_e, u, gz, vec_head_stride,
+                               vec_sample_stride, nullptr, nullptr, 0.f, partial, N, L, D, H, stream);
+}
+
+// The guarded form of etm_window_ln_grad (same arguments, plus norm_kv's ln_g / ln_b [D] and the threshold tau), for the default
+// path right after etm_window_ln_grad_from_outputs on the same `partial` and stream: returns at once in every workgroup unless some
+// column has |ln_g[c]| < tau max(1, |ln_b[c]|); then overwrites partial[r][c] (d gain) of exactly those columns c in every row r with
+// the rows kernel's sums.  The launch exists either way (no host branch: a captured graph replays it as one sequential node).
+extern "C" int etm_window_ln_grad_guarded(const float *bank, int64_t ep_stride, int64_t row_stride, const int64_t *ep, const int64_t *win,
+                                          const int64_t *pidx, const float *pos, const float *ln_stats, const float *att, const float *d_e,
+                                          const float *u, const float *gz, int64_t vec_head_stride, int64_t vec_sample_stride,
+                                          const float *ln_g, const float *ln_b, float tau, float *partial, int N, int L, int D, int H,
+                                          void *stream) {
+  (void)hipGetLastError();
+  if (!ln_g || !ln_b || !(tau >= 0.f)) return ETM_EINVAL;
+  return window_ln_grad_launch(bank, ep_stride, row_stride, ep, win, pidx, pos, ln_stats, att, d_e, u, gz, vec_head_stride,
+                               vec_sample_stride, ln_g, ln_b, tau, partial, N, L, D, H, stream);
 }
 
 // The same partial rows from the window passes' OUTPUTS (see ln_grad_from_outputs_kernel): u / gz / du / z [H, N, D] with one pair of

@@ -305,6 +305,11 @@ class _WindowFn(torch.autograd.Function):
                 rc = lib.etm_window_ln_grad_from_outputs(_ptr(u), _ptr(gz), _ptr(du), _ptr(z_fwd), _ptr(att), _ptr(d_e), _ptr(ln_g), _ptr(ln_b),
                                                          N * D, D, _ptr(partial), N, L, D, H, _stream())
                 _lib.check(rc, "etm_window_ln_grad_from_outputs")
+                # the identity divides by the gain: small-gain columns (zero included) from the window rows, on the same stream
+                rc = lib.etm_window_ln_grad_guarded(spec.block_ptr(block), spec.ep_stride, spec.row_stride, _ptr(spec.ep), _ptr(spec.win),
+                                                    _ptr(pidx), _ptr(pos), _ptr(ln_stats), _ptr(att), _ptr(d_e), _ptr(u), _ptr(gz), N * D, D,
+                                                    _ptr(ln_g), _ptr(ln_b), LN_GRAD_GUARD_TAU, _ptr(partial), N, L, D, H, _stream())
+                _lib.check(rc, "etm_window_ln_grad_guarded")
             col = DeferredDw.active
             params = getattr(ctx, "ln_params", None)
             if col is not None and params is not None and col.offer_colsum(partial, rows, 2 * D, [(0, D, params[0].data_ptr()), (D, D, params[1].data_ptr())]):
@@ -337,6 +342,9 @@ def colsum_rows(partial, P, C):
     return out
 
 
+# "outputs": columns with |gain| < tau max(1, |bias|) get their gain gradient from the rows kernel (etm_window_ln_grad_guarded).  The
+# identity's error in such a column grows as (|g| + |b|) / |g| (tests/test_gpu_parity.py, LayerNorm value edges: measured there).
+LN_GRAD_GUARD_TAU = 0.25
 _ln_grad_kernel = "outputs"      # norm_kv's gain / bias gradients by csrc/window_ln_grad.hip: "outputs" (from the passes' outputs,
 #                                    round 6) or "rows" (a pass over the window rows, round 5); False: the generic dX kernel, etm_window_dx
 

@@ -1295,7 +1295,7 @@ def test_window_ln_grad_and_bank_row_stats_vs_float64():
     """Round 5 (csrc/window_ln_grad.hip): norm_kv's gain / bias gradients of the folded pre-LN attention by the dedicated window pass
     == the float64 contraction sum_{n,l} dY xhat / sum dY with dY = sum_h dE u + att gz, and == the old generic dX kernel
     (etm_window_dx); etm_ln_row_stats == float64 row statistics; the statistics a WindowSpec gathers from per-bank-row statistics
-    equal the ones etm_window_fwd computes per window row (bit for bit: same kernel arithmetic per row)."""
+    equal the ones etm_window_fwd computes per window row (to rounding: the two kernels assign columns to lanes differently)."""
     import ctypes
     from etm import lib as etm_lib
     from etm import ops
@@ -1384,6 +1384,354 @@ def test_window_ln_grad_and_bank_row_stats_vs_float64():
         good = ln_g.abs() > 0.2
         e_good = float(((p_out.double().sum(0)[:D] - want2[:D])[good]).norm() / want2[:D][good].norm())
         assert e_good < 5e-6, e_good
+        # the default path: the same identity followed by its guard (the small-gain columns from the window rows) -> the rows bound
+        etm_lib.check(lib.etm_window_ln_grad_guarded(spec.block_ptr(block), spec.ep_stride, spec.row_stride, ep.data_ptr(), win.data_ptr(), None,
+                                                     None, gathered.data_ptr(), a2.data_ptr(), d_e2.data_ptr(), u.data_ptr(), gz.data_ptr(), N * D, D,
+                                                     ln_g.data_ptr(), ln_b.data_ptr(), ops.LN_GRAD_GUARD_TAU, p_out.data_ptr(), N, L, D, H, st),
+                      "etm_window_ln_grad_guarded")
+        e_def = float((p_out.double().sum(0) - want2).norm() / want2.norm())
+        e_def_g = float((p_out.double().sum(0)[:D] - want2[:D]).norm() / want2[:D].norm())
+        assert e_def < 2e-6 and e_def_g < 2e-6, (N, L, D, H, e_def, e_def_g)
+
+
+# ---- LayerNorm value edges (every LayerNorm kernel against float64 on the same fp32 inputs).  Gains: exact zeros, +-1e-7, +-1e-4,
+# +-1e-2, negative gains near -1, gains just above and just below the guard threshold of norm_kv's default gradient path
+# (etm.ops.LN_GRAD_GUARD_TAU), ordinary gains near 1; and an all-zero gain vector.  Rows: N(0,1) (the control), constant rows (var = 0,
+# rstd = 1 / sqrt(eps)), exactly-zero rows (unwritten memory slots of a fresh episode), rows with |mean| / std ~ 1e3.  The bound of a
+# path is its existing bound or 2 x the error of torch's fp32 CPU evaluation against float64 on the same inputs, whichever is larger:
+# on the large-offset rows the fp32 inputs themselves limit what any fp32 LayerNorm can reach (the mean carries ~1e3 x eps of absolute
+# error into every centred element), and the CPU evaluation measures that limit.
+def _ln_edge_gains(D, g, kind):
+    from etm import ops
+    if kind == "zero":
+        return torch.zeros(D)
+    tau = ops.LN_GRAD_GUARD_TAU
+    w = 1 + 0.1 * torch.randn((D,), generator=g)
+    edges = torch.tensor([0.0, 1e-7, -1e-7, 1e-4, -1e-4, 1e-2, -1e-2, -0.9, -1.05, 1.02 * tau, 0.98 * tau, -1.02 * tau, -0.98 * tau, 0.0])
+    w[torch.randperm(D, generator=g)[:edges.numel()]] = edges
+    return w
+
+
+def _ln_edge_rows(R, D, g):
+    """[R, D] fp32 rows, by row index mod 5: N(0,1), constant, exactly zero, +-1e3 + N(0,1), N(0,1)."""
+    x = torch.randn((R, D), generator=g)
+    k = torch.arange(R) % 5
+    x[k == 1] = torch.randn((int((k == 1).sum()), 1), generator=g).expand(-1, D)
+    x[k == 2] = 0.0
+    off = torch.where(torch.arange(R) % 2 == 0, 1e3, -1e3)[:, None]
+    x[k == 3] = (off + x)[k == 3]
+    return x
+
+
+def _edge_check(got, want64, cpu32, path_rel, name, companion=None):
+    """Finite wherever float64 is; norm-wise error <= max(path bound, 2 x torch fp32 CPU's); per element <= that x the norm.
+    A gradient that VANISHES in float64 (norm < 1e-6 x `companion`'s, a non-vanishing float64 gradient of the same backward pass:
+    keys that are all equal at zero gains make dq = dwk = 0, normalised rows that are all zero make d gain = 0) is measured against
+    the companion's norm instead -- relative to zero, fp32 rounding noise has no scale."""
+    got, want64, cpu32 = got.detach().cpu().double(), want64.detach().cpu().double(), cpu32.detach().cpu().double()
+    fin = torch.isfinite(want64)
+    assert bool(torch.isfinite(got[fin]).all()), f"{name}: {int((~torch.isfinite(got[fin])).sum())} non-finite values where float64 is finite"
+    scale = float(want64.norm())
+    if companion is not None and scale < 1e-6 * float(companion.detach().double().norm()):
+        scale = float(companion.detach().double().norm())
+    scale = max(scale, 1e-300)
+    e_cpu = float((cpu32 - want64).norm()) / scale
+    bound = max(path_rel, 2 * e_cpu)
+    err = float((got - want64).norm()) / scale
+    assert err <= bound, f"{name}: {err:.2e} of the norm from float64 (bound {bound:.2e}; torch fp32 CPU {e_cpu:.2e})"
+    worst = float((got - want64).abs().max())
+    assert worst <= bound * scale, f"{name}: one element {worst:.2e} off, norm {scale:.2e}"
+    return err
+
+
+@pytest.mark.parametrize("fused", [True, "rows", False])
+@pytest.mark.parametrize("gains", ["mixed", "zero"])
+@pytest.mark.parametrize("D,H,L,N,pos", [(384, 4, 128, 9, False), (128, 1, 32, 50, False), (512, 4, 64, 1, False), (64, 1, 32, 7, True),
+                                         (384, 4, 118, 5, True)])
+def test_norm_kv_gradients_at_layernorm_value_edges_vs_float64(D, H, L, N, pos, fused, gains, attn_impl):
+    """ops.mha with norm_kv (pre-LN) at the value edges above, every `fused_ln_grad` setting ("outputs" = True, the default; "rows";
+    False = the generic etm_window_dx), against oracle.ref_model.mha on float64 tensors: context, dq, dwk, dwv, dln_g, dln_b, dpos.
+    Episode 0 of the bank is all zero rows and samples 0 and N - 1 are fully masked (uniform attention over them, Q2).  Rows of the
+    table of test_mha_banked_vs_oracle with ln=True; D = 64 and the learnable positional table take the generic path."""
+    from etm import ops
+    from oracle import ref_model as rm
+    dev = _dev()
+    g = torch.Generator().manual_seed(7 * D + L + N)
+    E, T, nb, blk = 6, L + 9, 3, 1
+    bank = _ln_edge_rows(E * T * nb, D, g).view(E, T, nb, D)
+    bank[0] = 0.0
+    ep = torch.randint(0, E, (N,), generator=g)
+    ep[0] = 0
+    win = (torch.randint(0, T - L + 1, (N,), generator=g)[:, None] + torch.arange(L)[None, :]).long()
+    pidx = (torch.randint(0, T - L + 1, (N,), generator=g)[:, None] + torch.arange(L)[None, :]).long()
+    cnt = torch.randint(0, L + 1, (N,), generator=g)
+    cnt[0] = cnt[-1] = 0
+    mask = torch.arange(L)[None, :] < cnt[:, None]
+    base = dict(table=torch.randn((T, D), generator=g) * 0.5, wk=torch.randn((D, D), generator=g) / D ** 0.5,
+                wv=torch.randn((D, D), generator=g) / D ** 0.5, lg=_ln_edge_gains(D, g, gains), lb=0.1 * torch.randn((D,), generator=g),
+                q=torch.randn((N, D), generator=g))
+    gout = torch.randn((N, D), generator=g)
+
+    def oracle(dt):
+        t = {k: v.to(dt).clone().requires_grad_(True) for k, v in base.items()}
+        x = bank.to(dt)[ep][torch.arange(N)[:, None], win][:, :, blk]
+        if pos:
+            x = x + t["table"][pidx]
+        x = torch.nn.functional.layer_norm(x, (D,), t["lg"], t["lb"], 1e-5)
+        eye = torch.eye(D, dtype=dt)
+        sd = {"a.values.weight": t["wv"], "a.keys.weight": t["wk"], "a.queries.weight": eye, "a.fc_out.weight": eye,
+              "a.fc_out.bias": torch.zeros(D, dtype=dt)}
+        ctx = rm.mha(sd, "a", H, x, x, t["q"].unsqueeze(1), mask)[0][:, 0]
+        (ctx * gout.to(dt)).sum().backward()
+        return dict(ctx=ctx.detach(), dq=t["q"].grad, dwk=t["wk"].grad, dwv=t["wv"].grad, dln_g=t["lg"].grad, dln_b=t["lb"].grad,
+                    dpos=t["table"].grad)
+    ref, cpu = oracle(torch.float64), oracle(torch.float32)
+
+    d = {k: v.to(dev).clone().requires_grad_(True) for k, v in base.items()}
+    spec = ops.WindowSpec.from_bank(bank.to(dev), ep.to(dev), win.to(dev), pidx.to(dev) if pos else None, mask.to(dev))
+    ops.set_ln_grad_kernel(fused)
+    try:
+        out, _ = ops.mha(d["q"], d["wk"], d["wv"], spec, blk, H, d["lg"], d["lb"], d["table"] if pos else None)
+        (out * gout.to(dev)).sum().backward()
+        torch.cuda.synchronize(dev)
+    finally:
+        ops.set_ln_grad_kernel(True)
+    got = dict(ctx=out, dq=d["q"].grad, dwk=d["wk"].grad, dwv=d["wv"].grad, dln_g=d["lg"].grad, dln_b=d["lb"].grad, dpos=d["table"].grad)
+    for name, path_rel in (("ctx", 2e-5), ("dq", 2e-4), ("dwk", 2e-4), ("dwv", 2e-4), ("dln_g", 5e-4), ("dln_b", 5e-4), ("dpos", 5e-4)):
+        if name == "dpos" and not pos:
+            continue
+        companion = {"dq": ref["dwv"], "dwk": ref["dwv"], "dln_g": ref["dln_b"]}.get(name)
+        _edge_check(got[name], ref[name], cpu[name], path_rel, f"{name} (fused_ln_grad={fused}, gains {gains})", companion)
+
+
+@pytest.mark.parametrize("N,H,L,D", [(37, 4, 128, 384), (130, 1, 32, 128), (64, 8, 64, 256), (9, 4, 128, 512)])
+def test_window_passes_ln_grad_and_row_stats_at_value_edges_vs_float64(N, H, L, D):
+    """The C-ABI pieces of pre-LN window attention at the value edges: etm_ln_row_stats (ops.bank_row_stats) on constant / zero /
+    large-offset bank rows vs float64, and WindowSpec.window_stats == etm_window_fwd's own per-window statistics; etm_window_fwd's
+    attention and etm_window_bwd's du vs a float64 evaluation of the same pass (finite at gain 0 too); norm_kv's gain / bias gradients
+    of the DEFAULT path -- etm_window_ln_grad_from_outputs followed by etm_window_ln_grad_guarded on the same partial rows -- and of the
+    rows kernel vs the float64 contraction, 2e-6 norm-wise and per column (relative to the column's sum of |terms|).  Also measures
+    the bare identity per column: columns the guard leaves to it (|g| >= tau max(1, |b|)) must meet the same per-column bound."""
+    from etm import lib as etm_lib
+    from etm import ops
+    from etm.ops import WindowSpec
+    dev = _dev()
+    lib = etm_lib.load()
+    tau = ops.LN_GRAD_GUARD_TAU
+    g = torch.Generator().manual_seed(N + D)
+    E, T, nb, block = 7, L + 11, 2, 1
+    bank_mem = _ln_edge_rows(nb * E * T, D, g).view(nb, E, T, D).to(dev)       # block-major, as buffer.py keeps it
+    bank_mem[:, 0] = 0.0
+    bank = bank_mem.permute(1, 2, 0, 3)
+    ep = torch.randint(0, E, (N,), generator=g).to(dev)
+    ep[0] = 0
+    win = torch.randint(0, T, (N, L), generator=g).to(dev)
+    mask = (torch.rand((N, L), generator=g) < 0.7).to(dev)
+    mask[0] = False                                                           # fully masked over zero rows (Q2)
+    mask[1:, 0] = True
+    ln_g = _ln_edge_gains(D, g, "mixed")
+    ln_b = 0.1 * torch.randn((D,), generator=g)
+    # the bias-aware side of the guard: |g| < tau |b| with |b| > 1 is guarded, |g| just above it is left to the identity
+    ln_g[:4], ln_b[:4] = torch.tensor([2.9 * tau, 3.1 * tau, -2.9 * tau, 3.1 * tau]), torch.tensor([3.0, 3.0, -3.0, -3.0])
+    ln_g, ln_b = ln_g.to(dev), ln_b.to(dev)
+    u, gz = torch.randn((H, N, D), generator=g).to(dev), torch.randn((H, N, D), generator=g).to(dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    # ---- row statistics of the bank rows
+    stats_bank = ops.bank_row_stats(bank, 1e-5)                                 # [nb, E, T, 2]
+    x64 = bank_mem.double()
+    mean64, var64 = x64.mean(-1), x64.var(-1, unbiased=False)
+    xc = bank_mem.cpu()
+    mean32, var32 = xc.mean(-1), xc.var(-1, unbiased=False)
+    assert bool(torch.isfinite(stats_bank).all())
+    scale = mean64.abs().clamp(min=1.0)
+    e_mean, e_mean_cpu = float(((stats_bank[..., 0].double() - mean64).abs() / scale).max()), float(((mean32.double() - mean64.cpu()).abs() / scale.cpu()).max())
+    assert e_mean <= max(1e-6, 2 * e_mean_cpu), (e_mean, e_mean_cpu)
+    rstd64 = 1 / torch.sqrt(var64 + 1e-5)
+    e_rstd = float((stats_bank[..., 1].double() / rstd64 - 1).abs().max())
+    e_rstd_cpu = float(((1 / torch.sqrt(var32 + 1e-5)).double() / rstd64.cpu() - 1).abs().max())
+    assert e_rstd <= max(1e-5, 2 * e_rstd_cpu), (e_rstd, e_rstd_cpu)
+    spec = WindowSpec.from_bank(bank, ep, win, None, mask)
+    spec.row_stats = stats_bank
+    gathered = spec.window_stats(block)
+    # ---- forward: once with its own statistics, once with the gathered ones
+    m8 = mask.contiguous().view(torch.uint8)
+    per_window = torch.empty((N, L, 2), device=dev)
+    z1, a1 = torch.empty((H, N, D), device=dev), torch.empty((N, H, L), device=dev)
+    etm_lib.check(lib.etm_window_fwd(spec.block_ptr(block), spec.ep_stride, spec.row_stride, ep.data_ptr(), win.data_ptr(), None, m8.data_ptr(),
+                                     None, ln_g.data_ptr(), ln_b.data_ptr(), 1e-5, u.data_ptr(), N * D, D, a1.data_ptr(), z1.data_ptr(), N * D, D,
+                                     per_window.data_ptr(), 0, N, L, D, H, st), "etm_window_fwd")
+    # (the two statistics kernels assign columns to lanes differently: equal to rounding, not bit for bit)
+    assert float(((per_window - gathered).abs() / gathered.abs().clamp(min=1.0)).max()) < 2e-6
+    z, att = torch.empty_like(z1), torch.empty_like(a1)
+    etm_lib.check(lib.etm_window_fwd(spec.block_ptr(block), spec.ep_stride, spec.row_stride, ep.data_ptr(), win.data_ptr(), None, m8.data_ptr(),
+                                     None, ln_g.data_ptr(), ln_b.data_ptr(), 1e-5, u.data_ptr(), N * D, D, att.data_ptr(), z.data_ptr(), N * D, D,
+                                     gathered.data_ptr(), 1, N, L, D, H, st), "etm_window_fwd")
+    d_e, du = torch.empty((N, H, L), device=dev), torch.empty((H, N, D), device=dev)
+    etm_lib.check(lib.etm_window_bwd(spec.block_ptr(block), spec.ep_stride, spec.row_stride, ep.data_ptr(), win.data_ptr(), None, m8.data_ptr(),
+                                     None, ln_g.data_ptr(), ln_b.data_ptr(), gathered.data_ptr(), att.data_ptr(), gz.data_ptr(), N * D, D,
+                                     d_e.data_ptr(), du.data_ptr(), N * D, D, N, L, D, H, st), "etm_window_bwd")
+    # float64 window pass: xfull = LN(x) g + b; energy = u . xfull, -1e20 fill before the 1 / sqrt(D) scale (Q1, Q2); z = att . xfull
+    def window_pass(dt, dev_):
+        xw = bank_mem[block].to(dev_, dt)[ep.to(dev_)[:, None], win.to(dev_)]
+        xf = torch.nn.functional.layer_norm(xw, (D,), ln_g.to(dev_, dt), ln_b.to(dev_, dt), 1e-5)
+        uu = u.to(dev_, dt).requires_grad_(True)
+        en = torch.einsum("hnd,nld->nhl", uu, xf).masked_fill(~mask.to(dev_)[:, None, :], -1e20)
+        a = torch.softmax(en / D ** 0.5, dim=-1)
+        zz = torch.einsum("nhl,nld->hnd", a, xf)
+        (zz * gz.to(dev_, dt)).sum().backward()
+        return a.detach(), zz.detach(), uu.grad
+    a64, z64, du64 = window_pass(torch.float64, "cpu")
+    a32, z32, du32 = window_pass(torch.float32, "cpu")
+    _edge_check(att, a64, a32, 2e-6, "att")
+    _edge_check(z, z64, z32, 2e-5, "z")
+    _edge_check(du, du64, du32, 2e-5, "du")
+    # ---- norm_kv's gain / bias gradients: the float64 contraction of the passes' own outputs, with xhat from the statistics the
+    # passes used (checked against float64 above: on the large-offset rows fp32 statistics are ~1e3 eps off, which is not this
+    # contraction's error)
+    xw = bank_mem[block].double()[ep[:, None], win]
+    xhat = (xw - gathered[..., :1].double()) * gathered[..., 1:].double()
+    dY = torch.einsum("nhl,hnd->nld", d_e.double(), u.double()) + torch.einsum("nhl,hnd->nld", att.double(), gz.double())
+    want = torch.cat(((dY * xhat).sum((0, 1)), dY.sum((0, 1))))
+    col_scale = torch.cat(((dY * xhat).abs().sum((0, 1)), dY.abs().sum((0, 1))))      # the column's sum of |terms|
+    rows = lib.etm_window_ln_grad_rows(N)
+    args = (spec.block_ptr(block), spec.ep_stride, spec.row_stride, ep.data_ptr(), win.data_ptr(), None, None, gathered.data_ptr(),
+            att.data_ptr(), d_e.data_ptr(), u.data_ptr(), gz.data_ptr(), N * D, D)
+    p_rows, p_out = torch.full((rows, 2 * D), float("nan"), device=dev), torch.full((rows, 2 * D), float("nan"), device=dev)
+    etm_lib.check(lib.etm_window_ln_grad(*args, p_rows.data_ptr(), N, L, D, H, st), "etm_window_ln_grad")
+    etm_lib.check(lib.etm_window_ln_grad_from_outputs(u.data_ptr(), gz.data_ptr(), du.data_ptr(), z.data_ptr(), att.data_ptr(), d_e.data_ptr(),
+                                                      ln_g.data_ptr(), ln_b.data_ptr(), N * D, D, p_out.data_ptr(), N, L, D, H, st),
+                  "etm_window_ln_grad_from_outputs")
+    bare = p_out.double().sum(0)
+    etm_lib.check(lib.etm_window_ln_grad_guarded(*args, ln_g.data_ptr(), ln_b.data_ptr(), tau, p_out.data_ptr(), N, L, D, H, st),
+                  "etm_window_ln_grad_guarded")
+    guarded = ln_g.abs() < tau * ln_b.abs().clamp(min=1.0)
+    assert bool(guarded.any())
+    for what, part in (("rows kernel", p_rows), ("default path (from outputs + guard)", p_out)):
+        got = part.double().sum(0)
+        assert bool(torch.isfinite(got).all()), (what, int((~torch.isfinite(got)).sum()))
+        e_g = float((got[:D] - want[:D]).norm() / want[:D].norm())
+        e_b = float((got[D:] - want[D:]).norm() / want[D:].norm())
+        e_col = float(((got - want).abs() / col_scale).max())
+        print(f"[norm_kv gradients at value edges N={N} L={L} D={D} H={H}] {what}: gain {e_g:.1e}, bias {e_b:.1e}, worst column {e_col:.1e} of its |terms|")
+        assert e_g < 2e-6 and e_b < 2e-6 and e_col < 2e-6, (what, e_g, e_b, e_col)
+    # columns the guard did not touch keep the identity's bits; the identity alone, per column, against |g| (the measurement behind tau)
+    unguarded = torch.cat((~guarded, torch.ones(D, dtype=torch.bool, device=dev)))
+    assert torch.equal(p_out.double().sum(0)[unguarded], bare[unguarded])
+    e_bare = ((bare[:D] - want[:D]).abs() / col_scale[:D]).nan_to_num(nan=float("inf"))
+    ratio = ln_g.abs() / ln_b.abs().clamp(min=1.0)
+    for lo, hi in ((0, 1e-6), (1e-6, 1e-3), (1e-3, 0.1), (0.1, tau), (tau, 0.5), (0.5, 10)):
+        sel = (ratio >= lo) & (ratio < hi)
+        if bool(sel.any()):
+            print(f"    identity alone, |g| / max(1, |b|) in [{lo:g}, {hi:g}): worst column {float(e_bare[sel].max()):.1e} of its |terms| ({int(sel.sum())} columns)")
+    assert float(e_bare[~guarded].max()) < 2e-6, float(e_bare[~guarded].max())
+
+
+@pytest.mark.parametrize("N,D", [(40, 96), (40, 384), (25, 640)])
+@pytest.mark.parametrize("gains", ["mixed", "zero"])
+def test_fused_layernorm_at_value_edges_vs_float64(N, D, gains):
+    """The training LayerNorm (ops.fused_layernorm: csrc/block_train.hip, ln_train_*) at the value edges: forward, d a, d gamma,
+    d beta against float64 F.layer_norm on the same fp32 inputs; D = 96 and 640 exercise the lane guards (D % 64 != 0, D > 512)."""
+    from etm import ops
+    dev = _dev()
+    g = torch.Generator().manual_seed(N * D + (gains == "zero"))
+    a = _ln_edge_rows(N, D, g)
+    w, b = _ln_edge_gains(D, g, gains), 0.1 * torch.randn((D,), generator=g)
+    go = torch.randn((N, D), generator=g)
+
+    def ref(dt):
+        t = [x.to(dt).requires_grad_(True) for x in (a, w, b)]
+        y = torch.nn.functional.layer_norm(t[0], (D,), t[1], t[2], 1e-5)
+        return [y.detach()] + list(torch.autograd.grad(y, t, go.to(dt)))
+    r64, r32 = ref(torch.float64), ref(torch.float32)
+    norm = torch.nn.LayerNorm(D).to(dev)
+    with torch.no_grad():
+        norm.weight.copy_(w)
+        norm.bias.copy_(b)
+    ad = a.to(dev).requires_grad_(True)
+    y = ops.fused_layernorm(ad, norm)
+    got = [y] + list(torch.autograd.grad(y, [ad, norm.weight, norm.bias], go.to(dev)))
+    for name, gt, w64, w32 in zip(("forward", "d a", "d gamma", "d beta"), got, r64, r32):
+        _edge_check(gt, w64, w32, 2e-5, f"{name} (D={D}, gains {gains})")
+
+
+@pytest.mark.parametrize("mode", ["api", "graph"])
+def test_pre_ln_update_with_zero_and_tiny_norm_kv_gains(golden_dir, mode):
+    """One optimiser update of the cfg5-shaped pre-LN GTrXL trainer whose norm_kv gains hold exact zeros and +-1e-6 entries (weight decay
+    pulls gains to zero; a checkpoint may carry any value): on the default `fused_ln_grad` path the un-clipped gradients, the reported
+    gradient norms, the loss statistics and every updated parameter are finite, and they match the same update with
+    `fused_ln_grad: rows` to the bounds the teacher-forced cfg5/rows_ln_grad case meets (tf_bounds, update 0).  mode "api": the eager
+    upstream-API step; "graph": the captured optimisation step (as test_kink_free_update_vs_reference drives it)."""
+    from trainer import PPOTrainer
+    dev = _dev()
+    z = load(golden_dir, "rollout_cfg5.npz")
+    info = json.loads(str(z["cfg_json"]))
+    keys, shapes = shapes_of(z, "")
+    lr, clip, beta = (float(x) for x in z["u0/hp"])
+    idx = z["kf/s0/idx"]
+    bound = tf_bounds("cfg5", 0)
+    runs = {}
+    for path in (True, "rows"):
+        cfg = {**info["cfg"], "environment": {"type": "Synthetic", **info["env"]}, "fused_ln_grad": path}
+        tr = PPOTrainer(cfg, run_id="lnedge", device=dev, tensorboard=False)
+        load_det(tr.model, "rollout_cfg5", keys, shapes)
+        with torch.no_grad():
+            for n, p in tr.model.named_parameters():
+                if n.endswith("norm_kv.weight"):
+                    p[0::7] = 0.0
+                    p[3::7] = 1e-6
+                    p[5::7] = -1e-6
+        tr._sample_training_data(forced_actions=z["u0/actions"][:, :, 0])
+        tr.buffer.prepare_batch_dict()
+        params = dict(tr.model.named_parameters())
+        init = {k: v.detach().clone() for k, v in params.items()}
+        idx_t = torch.as_tensor(idx, device=dev, dtype=torch.long).sort().values
+        if mode == "graph":
+            assert tr._use_train_graph
+            opt = tr.optimizer
+            arenas = (opt.flat_params, opt.exp_avg, opt.exp_avg_sq, opt.step_dev)
+            snap = [t.clone() for t in arenas]
+            with torch.no_grad():
+                tr._bank_pos, tr._obs_train = tr._bank_with_positions(), tr._observations_channels_last()
+            for _ in range(2):                               # the two eager warm-up steps every capture is preceded by
+                tr._train_step_graph(idx_t, lr, clip, beta, False)
+            with torch.no_grad():
+                for t, s0 in zip(arenas, snap):
+                    t.copy_(s0)
+        grads = tr.minibatch_gradients(idx, clip, beta)
+        if mode == "api":
+            stats = tr._train_mini_batch(tr.buffer.gather(torch.as_tensor(idx, device=dev)), lr, clip, beta)
+            norms = tr._grad_group_norms()
+        else:
+            with torch.no_grad():
+                tr._bank_pos, tr._obs_train = tr._bank_with_positions(), tr._observations_channels_last()
+            stats, norms = tr._train_step_graph(idx_t, lr, clip, beta, True)
+            assert tr._train_graph is not None, "the step must have been a graph replay"
+        torch.cuda.synchronize(dev)
+        runs[path] = dict(grads={k: v.double().cpu() for k, v in grads.items()}, stats=stats.double().cpu(), norms=norms.double().cpu(),
+                          params={k: v.detach().double().cpu() for k, v in params.items()}, init={k: v.double().cpu() for k, v in init.items()})
+        tr.close()
+    for path, r in runs.items():
+        bad = [k for k, v in list(r["grads"].items()) + list(r["params"].items()) if not bool(torch.isfinite(v).all())]
+        assert not bad, f"fused_ln_grad={path}: non-finite {bad[:4]}"
+        assert bool(torch.isfinite(r["stats"]).all()) and bool(torch.isfinite(r["norms"]).all()), (path, r["stats"], r["norms"])
+    d, w = runs[True], runs["rows"]
+    num = den = 0.0
+    for k, gw in w["grads"].items():
+        e = float((d["grads"][k] - gw).norm())
+        num, den = num + e * e, den + float(gw.norm()) ** 2
+        assert e <= bound["grad_tensor"] * max(float(gw.norm()), 1e-30), (k, e / max(float(gw.norm()), 1e-30))
+    assert (num / den) ** 0.5 <= bound["grad_all"], (num / den) ** 0.5
+    st_err = float(((d["stats"] - w["stats"]).abs() / w["stats"].abs().clamp(min=1.0)).max())
+    assert st_err <= bound["stats"], st_err
+    assert float(((d["norms"] - w["norms"]).abs() / w["norms"].abs().clamp(min=1e-30)).max()) <= bound["grad_all"], (d["norms"], w["norms"])
+    num = den = 0.0
+    for k, pw in w["params"].items():
+        mv, e = float((pw - w["init"][k]).norm()), float((d["params"][k] - pw).norm())
+        num, den = num + e * e, den + mv * mv
+        if mv > 0:
+            assert e <= bound["move_tensor"] * mv, (k, e / mv)
+    print(f"[norm_kv zero / tiny gains, cfg5 {mode}] default vs rows: gradient {(num / den) ** 0.5:.2e} movement, loss statistics {st_err:.1e}")
+    assert (num / den) ** 0.5 <= bound["move_all"], (num / den) ** 0.5
 
 
 def test_rollout_glue_riders_and_fused_policy():
