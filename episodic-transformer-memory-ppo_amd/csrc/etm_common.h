@@ -53,6 +53,22 @@ __device__ __forceinline__ float half_sum(float v) {
   return v;
 }
 
+// Inverse-CDF draw from the categorical over the A logits lg with log-normaliser lse (every sampling site: rollout_sample_kernel,
+// rollout_policy_kernel and both step kernels).  The action is the smallest j with u < C_j, C_j = the fp32 running sum of
+// expf(lg[i] - lse) over i <= j.  That total can end below 1, and below the largest fp32 uniform 1 - 2^-24: a draw at or past it
+// takes the LAST action whose term is positive, never one of probability zero (torch.multinomial's contract).
+__device__ __forceinline__ int etm_sample_categorical(const float *lg, int A, float lse, float u) {
+  float c = 0.f;
+  int last = A - 1;
+  for (int j = 0; j < A; ++j) {
+    const float e = expf(lg[j] - lse);
+    c += e;
+    if (e > 0.f) last = j;
+    if (u < c) return j;
+  }
+  return last;
+}
+
 static inline int etm_launch_status() { return (int)hipGetLastError(); }
 
 // ---- optional per-kernel timing with HIP events (see etm_profile_* in include/etm_hip.h); off by default.

@@ -555,14 +555,7 @@ __global__ __launch_bounds__(RF_T) void rollout_trxl_kernel(const RfParams p) {
       for (int j = 0; j < A; ++j) se += expf(lg[j] - mx);
       const float lse = mx + logf(se);
       int a = a_forced;
-      if (a < 0) {
-        float c = 0.f;
-        a = A - 1;
-        for (int j = 0; j < A; ++j) {
-          c += expf(lg[j] - lse);
-          if (u_draw < c) { a = j; break; }
-        }
-      }
+      if (a < 0) a = etm_sample_categorical(lg, A, lse, u_draw);
       p.actions[w] = a;
       if (p.host_actions) p.host_actions[w] = a;
       p.st_actions[t * p.stage_W + w] = a;

@@ -90,13 +90,7 @@ __global__ __launch_bounds__(1024) void rollout_sample_kernel(const float *__res
     const float lse = mx + logf(se);
     int a = forced ? (int)forced[t * W + w] : -1;      // forced: time-major table [S, W]; a negative entry means "sample"
     if (a < 0) {
-      const float u = uniforms[t * W + w];
-      float c = 0.f;
-      a = A - 1;
-      for (int j = 0; j < A; ++j) {
-        c += expf(lg[j] - lse);
-        if (u < c) { a = j; break; }
-      }
+      a = etm_sample_categorical(lg, A, lse, uniforms[t * W + w]);
     }
     actions[w] = a;
     st_actions[t * W + w] = a;
@@ -148,13 +142,7 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel(const float *__rest
     const float lse = mx + logf(se);
     int a = forced ? (int)forced[t * stage_W + w] : -1;   // forced: time-major table [S, stage_W]; negative = "sample"
     if (a < 0) {
-      const float u = uniforms[t * stage_W + w];
-      float c = 0.f;
-      a = A - 1;
-      for (int j = 0; j < A; ++j) {
-        c += expf(lg[j] - lse);
-        if (u < c) { a = j; break; }
-      }
+      a = etm_sample_categorical(lg, A, lse, uniforms[t * stage_W + w]);
     }
     actions[w] = a;
     if (host_actions) host_actions[w] = a;

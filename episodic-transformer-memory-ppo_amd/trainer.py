@@ -393,7 +393,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         g.step_l, g.slot_l = g.ss_latch[0], g.ss_latch[1]
         return g
 
-    def _sample_training_data(self, forced_actions=None) -> list:
+    def _sample_training_data(self, forced_actions=None, uniforms=None) -> list:
         """Runs all workers for ``worker_steps`` steps; fills the buffer; returns finished-episode infos.
 
         The device work of one step (window lookup, model forward, action sampling, staging of the step's buffer rows,
@@ -407,7 +407,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         ``forced_actions`` [W, S] (optional) replays recorded actions instead of sampling (teacher forcing for parity
         tests -- CPU and GPU RNG streams differ) on whichever path the config selects: the sampling
         kernels read them from a fixed-address table, so the captured graphs, the observation streaming and the worker-group
-        pipeline run exactly as they do when sampling."""
+        pipeline run exactly as they do when sampling.
+        ``uniforms`` [W, S] (optional, tests) replaces the rollout's uniform draws: every sampling kernel inverts its CDF at
+        exactly these values."""
         buf, W, S = self.buffer, self.num_workers, self.config["worker_steps"]
         main = torch.cuda.current_stream(self.device)
         use_graph = bool(self.config.get("hip_graph_rollout", True))
@@ -424,7 +426,10 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         groups = self._groups if use_graph else [self._group_all]
         if use_graph and groups[0].graphs is None:
             self._capture_step_graph(groups)
-        self._uniforms.uniform_()                # one draw per (step, worker) for the whole rollout
+        if uniforms is not None:
+            self._uniforms.copy_(torch.as_tensor(np.asarray(uniforms), dtype=torch.float32).reshape(W, S).t())
+        else:
+            self._uniforms.uniform_()            # one draw per (step, worker) for the whole rollout
         for g in groups:
             g.t_dev.zero_()
             g.flag_np[0] = 0
