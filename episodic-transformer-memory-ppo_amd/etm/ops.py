@@ -370,9 +370,54 @@ def set_attention_impl(impl):
     _default_impl = impl
 
 
+_LDS_BYTES = 160 * 1024      # one workgroup's LDS on gfx950
+
+
 def folded_supported(D, L, num_heads):
-    hd = D // num_heads
-    return D % 32 == 0 and hd % 2 == 0 and ((D <= 512 and L <= 128) or (D <= 1024 and L <= 64))
+    """Shapes the folded window pass (etm_window_fwd / etm_window_bwd) runs: check_common's rules, dispatch_rows' row tilings and
+    launch_pass3's LDS budget (H padded window rows of attention weights + the per-wave partial sums)."""
+    H = int(num_heads)
+    if H <= 0 or D % H != 0 or D % 32 != 0 or (D // H) % 2 != 0 or not ((D <= 512 and L <= 128) or (D <= 1024 and L <= 64)):
+        return False
+    nj = {5: 6, 7: 8}.get(-(-D // 128), -(-D // 128))
+    rw, nw = (8, 4) if L <= 32 else ((8, 8) if L <= 64 else (16, 8))
+    return (H * nw * rw + nw * 4 * nj * 128) * 4 <= _LDS_BYTES
+
+
+def _dx_lds_ok(D, H, L):
+    """bwd_dx_kernel (etm_mha_bwd step B3, etm_window_dx): 2HD + 8D + 2HL floats of LDS."""
+    return (2 * H * D + 8 * D + 2 * H * L) * 4 <= _LDS_BYTES
+
+
+def dense_supported(D, L, num_heads, backward=True):
+    """Shapes the dense kernels run: etm_mha_fwd's rules, and with ``backward`` etm_mha_bwd's LDS checks (made for every call)."""
+    H = int(num_heads)
+    if H <= 0 or D % H != 0:
+        return False
+    hd = D // H
+    if D % 32 != 0 or hd % 32 != 0 or hd > 128 or L > 128 or D > 1024:
+        return False
+    return not backward or (_dx_lds_ok(D, H, L) and (D + 3 * H * L) * 4 <= _LDS_BYTES)
+
+
+def _ln_grad_kernel_route(D, H, L, want_ln, want_pos):
+    """_WindowFn.backward: norm_kv's gradients by csrc/window_ln_grad.hip (else by etm_window_dx)."""
+    return bool(_ln_grad_kernel) and want_ln and not want_pos and D % 128 == 0 and D <= 512 and H <= 8 and L <= 128
+
+
+def attention_supported(D, H, L, ln=False, pos_grad=False, backward=True, impl=None):
+    """The kernel family ("folded" / "dense") that ``mha`` runs for this shape, or None if neither can run it.  ``ln``: norm_kv's
+    gain / bias want gradients; ``pos_grad``: a learned positional table does; ``backward``: the backward pass must run too.
+    The folded forward falls back to the dense kernels when it cannot run the shape; its norm_kv / positional gradients go
+    through the dX kernel unless window_ln_grad.hip takes them, and the dense backward needs that same dX kernel's LDS."""
+    impl = _default_impl if impl is None else impl
+    if impl not in ATTENTION_IMPLS:
+        raise ValueError(f"attention impl must be one of {ATTENTION_IMPLS}, got {impl!r}")
+    D, H, L = int(D), int(H), int(L)
+    if impl == "folded" and folded_supported(D, L, H):
+        want_dx = backward and (pos_grad or ln) and not _ln_grad_kernel_route(D, H, L, ln, pos_grad)
+        return "folded" if not want_dx or _dx_lds_ok(D, H, L) else None
+    return "dense" if dense_supported(D, L, H, backward) else None
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -600,7 +645,14 @@ def mha(q, wk, wv, spec, block, num_heads, ln_g=None, ln_b=None, pos=None, ln_ep
         raise ValueError(f"attention impl must be one of {ATTENTION_IMPLS}, got {impl!r}")
     N, D = q.shape
     H = int(num_heads)
-    if impl == "dense" or not folded_supported(D, spec.L, H):
+    grad = lambda t: t is not None and t.requires_grad
+    backward = torch.is_grad_enabled() and any(grad(t) for t in (q, wk, wv, ln_g, ln_b, pos))
+    want_ln, want_pos = backward and (grad(ln_g) or grad(ln_b)), backward and grad(pos)
+    family = attention_supported(D, H, spec.L, want_ln, want_pos, backward, impl)
+    if family is None:
+        raise ValueError(f"window attention D={D} H={H} L={spec.L} (norm_kv gradients: {want_ln}, positional-table gradients: "
+                         f"{want_pos}, backward: {backward}) is outside what the {impl} kernels support (ops.attention_supported)")
+    if family == "dense":
         return _MhaFn.apply(q, wk, wv, ln_g, ln_b, pos, spec, block, num_heads, ln_eps)
     hd = D // H
     # u[h] = q_h Wk_h and ctx_h = z_h Wv_h^T: [N,hd] x [hd,D] per head (library GEMMs; autograd supplies d q, d Wk, d Wv)

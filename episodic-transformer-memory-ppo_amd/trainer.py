@@ -95,6 +95,10 @@ def check_kernel_shapes(tcfg: dict):
         problems.append(f"head_dim={hd} (need 32, 64, 96 or 128)")
     if mem > 128:
         problems.append(f"memory_length={mem} (need <= 128)")
+    if not problems and ops.attention_supported(d, h, mem, ln=tcfg.get("layer_norm") == "pre",
+                                                pos_grad=tcfg.get("positional_encoding") == "learned") is None:
+        problems.append(f"attention backward at embed_dim={d}, num_heads={h}, memory_length={mem}, layer_norm="
+                        f"{tcfg.get('layer_norm')}, positional_encoding={tcfg.get('positional_encoding')} (LDS: see DESIGN.md section 6)")
     if problems:
         raise ValueError("transformer shape not supported by the MI355X kernels: " + "; ".join(problems))
 

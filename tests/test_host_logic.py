@@ -221,6 +221,27 @@ def test_conv_pack_weights_layout_and_attention_dispatch_rules():
     ops.set_attention_impl("dense"); ops.set_attention_impl("folded")
 
 
+def test_attention_supported_predicate_and_trainer_check():
+    """ops.attention_supported: the folded pass's LDS budget at large H, the dX kernel's LDS for norm_kv / positional-table gradients
+    and the dense backward; check_kernel_shapes refuses a config whose attention backward cannot run (pure host logic)."""
+    from etm import ops
+    from trainer import check_kernel_shapes
+    sup = ops.attention_supported
+    assert sup(384, 4, 64, impl="folded") == "folded" and sup(384, 4, 64, impl="dense") == "dense"
+    assert sup(1024, 8, 128, ln=True) == "dense" and sup(1024, 8, 64, ln=True, pos_grad=True) == "folded"
+    # D = 1024, H = 16: the dX kernel needs 168 KB of LDS (2HD + 8D + 2HL floats at L = 64)
+    assert sup(1024, 16, 64) == "folded" and sup(1024, 16, 64, ln=True) is None and sup(1024, 16, 64, pos_grad=True) is None
+    assert sup(1024, 16, 64, impl="dense") is None and sup(1024, 16, 64, backward=False, impl="dense") == "dense"
+    assert sup(1024, 16, 128) is None and sup(1024, 16, 128, backward=False) == "dense"
+    assert ops.folded_supported(512, 128, 128) and not ops.folded_supported(512, 128, 256)      # launch_pass3: H NW RW + 4 NW 128 NJ floats
+    assert sup(512, 256, 128) is None and sup(512, 256, 64) == "folded" and sup(512, 256, 64, ln=True) is None
+    tcfg = dict(embed_dim=1024, num_heads=16, memory_length=64, layer_norm="post", positional_encoding="relative")
+    check_kernel_shapes(tcfg)
+    for bad in (dict(layer_norm="pre"), dict(positional_encoding="learned"), dict(memory_length=128)):
+        with pytest.raises(ValueError, match="attention backward"):
+            check_kernel_shapes({**tcfg, **bad})
+
+
 def test_composite_vec_env_equals_single_front_end():
     """make_vec_env(groups=2) == one front-end over all workers (same per-worker streams), whether it is stepped as a whole or
     part by part (what the pipelined rollout does)."""
