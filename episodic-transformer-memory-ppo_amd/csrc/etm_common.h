@@ -69,6 +69,79 @@ __device__ __forceinline__ int etm_sample_categorical(const float *lg, int A, fl
   return last;
 }
 
+// Action branches of a MultiDiscrete policy (one per nvec entry): branch b owns logit columns [off_b, off_b + size[b]) of the
+// concatenated policy head, off_b = the sum of the sizes before it.  A Discrete policy is n = 1, size[0] = A.  Passed to the
+// kernels by value (no device allocation, graph-capturable).
+constexpr int ETM_MAX_BRANCHES = 16;
+struct EtmBranches {
+  int n;
+  int size[ETM_MAX_BRANCHES];
+};
+
+// Host side: the branch table of (sizes, n) -- sizes == NULL and n <= 1 means one branch of total_a actions.  0 on success;
+// ETM_EINVAL for a bad table, ETM_EUNSUPPORTED for more than ETM_MAX_BRANCHES branches or a sum that is not total_a.
+static inline int etm_branches_make(const int32_t *sizes, int n, int total_a, EtmBranches *out) {
+  if (!sizes && n <= 1) {
+    out->n = 1;
+    out->size[0] = total_a;
+    return total_a > 0 ? 0 : ETM_EINVAL;
+  }
+  if (!sizes || n <= 0) return ETM_EINVAL;
+  if (n > ETM_MAX_BRANCHES) return ETM_EUNSUPPORTED;
+  int s = 0;
+  out->n = n;
+  for (int b = 0; b < n; ++b) {
+    if (sizes[b] <= 0) return ETM_EINVAL;
+    out->size[b] = sizes[b];
+    s += sizes[b];
+  }
+  return s == total_a ? 0 : ETM_EINVAL;
+}
+static inline int etm_branches_total(const int32_t *sizes, int n) {
+  if (!sizes || n <= 0 || n > ETM_MAX_BRANCHES) return 0;
+  int s = 0;
+  for (int b = 0; b < n; ++b) {
+    if (sizes[b] <= 0) return 0;
+    s += sizes[b];
+  }
+  return s;
+}
+
+// One branch's draw: log-sum-exp over its own A logits, then the inverse CDF at its own uniform u -- or the forced action when
+// forced >= 0.  Returns the action (inside the branch) and its log-prob.  With one branch this is exactly the single-branch
+// arithmetic of every sampling site (same operations in the same order).
+__device__ __forceinline__ int etm_sample_branch(const float *lg, int A, float u, int forced, float *logp) {
+  float mx = -INFINITY;
+  for (int j = 0; j < A; ++j) mx = fmaxf(mx, lg[j]);
+  float se = 0.f;
+  for (int j = 0; j < A; ++j) se += expf(lg[j] - mx);
+  const float lse = mx + logf(se);
+  int a = forced;
+  if (a < 0) a = etm_sample_categorical(lg, A, lse, u);
+  *logp = lg[a] - lse;
+  return a;
+}
+
+// Every branch of worker w at step t: row = t * stage_W + w indexes the time-major [S, stage_W, B] uniform / forced / staging
+// tables (B = 1: [S, stage_W]); actions and host_actions are [W, B].  The value (logit column sum(sizes)) is staged by the caller.
+__device__ __forceinline__ void etm_sample_branches(const float *lg, const EtmBranches &br, long long row, int w, const float *uniforms,
+                                                    const long long *forced, long long *actions, long long *host_actions,
+                                                    long long *st_actions, float *st_logp) {
+  const int B = br.n;
+  int off = 0;
+  for (int b = 0; b < B; ++b) {
+    const long long i = row * B + b;
+    const int Ab = br.size[b];
+    float lp;
+    const int a = etm_sample_branch(lg + off, Ab, uniforms[i], forced ? (int)forced[i] : -1, &lp);
+    actions[(long long)w * B + b] = a;
+    if (host_actions) host_actions[(long long)w * B + b] = a;
+    st_actions[i] = a;
+    st_logp[i] = lp;
+    off += Ab;
+  }
+}
+
 static inline int etm_launch_status() { return (int)hipGetLastError(); }
 
 // ---- optional per-kernel timing with HIP events (see etm_profile_* in include/etm_hip.h); off by default.

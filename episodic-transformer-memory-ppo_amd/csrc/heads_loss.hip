@@ -20,7 +20,7 @@
 #include "etm_common.h"
 
 namespace {
-constexpr int HL_MAXA = 8;             // actions of the branch
+constexpr int HL_MAXA = 8;             // actions of the policy (all branches together)
 constexpr int HL_MAXC = 8;             // hidden columns per lane (hid <= 512)
 
 struct HlParams {
@@ -39,9 +39,14 @@ struct HlParams {
   float *logits, *value;               // optional outputs [N, A], [N]
   float *partials;                     // [n_wg][row]: row = (3 + A) * hid floats (sum gm_p | sum gm_v | d wv | d Wb[a] ...) + A + 1 + 5
   int N, A, hid, samples_per_wg;
+  // BR kernels (MultiDiscrete): nbr branches; column j of the A logits belongs to branch col_branch[j], which starts at column
+  // branch_off[col_branch[j]]; actions / old_logp rows hold one entry per branch
+  int nbr;
+  int col_branch[HL_MAXA];
+  int branch_off[HL_MAXA];
 };
 
-template <int HC>
+template <int HC, bool BR>
 __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
   HlParams p = p0;
   if (p.dyn) {
@@ -126,6 +131,8 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
     // ---- loss terms and their gradients: the expressions of ppo_loss_kernel (one sample, evaluated redundantly by every lane)
     const float a_raw = p.adv[n];
     const float a_n = (a_raw - mean) / (stdv + 1e-8f);
+    float dl[HL_MAXA];
+    if constexpr (!BR) {
     float mx = -INFINITY;
 #pragma unroll
     for (int j = 0; j < HL_MAXA; ++j) if (j < A) mx = fmaxf(mx, lg[j]);
@@ -158,7 +165,6 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
     }
     const float cpol = -p.pol_scale * g_ratio * ratio;
     const float cent = -p.beta * p.ent_scale;
-    float dl[HL_MAXA];
 #pragma unroll
     for (int j = 0; j < HL_MAXA; ++j) {
       dl[j] = 0.f;
@@ -168,6 +174,70 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
         const float d_lp = ((j == act) ? 1.f : 0.f) - pj;
         const float d_ent = -pj * (l + ent);
         dl[j] = cpol * d_lp + cent * d_ent;
+      }
+    }
+    } else {
+      // MultiDiscrete (ref_algo.ppo_loss): per branch b a log-softmax over its own columns and a ratio; the sample's normalised
+      // advantage is repeated over the branches; policy term, KL and clip fraction are summed over (sample, branch) and scaled by
+      // pol_scale = 1 / (N B); the entropy is the sum of the branches' entropies (scaled by 1 / N).  Every branch-indexed array
+      // is indexed by unrolled constants only (registers, no scratch).
+      float lse_c[HL_MAXA], ent_c[HL_MAXA], cpol_c[HL_MAXA];
+      int act_col[HL_MAXA];
+#pragma unroll
+      for (int b = 0; b < HL_MAXA; ++b) {
+        act_col[b] = -1;
+        if (b < p.nbr) {
+          float mx = -INFINITY;
+#pragma unroll
+          for (int j = 0; j < HL_MAXA; ++j) if (j < A && p.col_branch[j] == b) mx = fmaxf(mx, lg[j]);
+          float se = 0.f;
+#pragma unroll
+          for (int j = 0; j < HL_MAXA; ++j) if (j < A && p.col_branch[j] == b) se += expf(lg[j] - mx);
+          const float lse = mx + logf(se);
+          const int ac = p.branch_off[b] + (int)p.actions[(long long)n * p.action_stride + b];
+          float lg_act = 0.f, ent = 0.f;
+#pragma unroll
+          for (int j = 0; j < HL_MAXA; ++j) {
+            if (j == ac) lg_act = lg[j];
+            if (j < A && p.col_branch[j] == b) { const float l = lg[j] - lse; ent -= expf(l) * l; }
+          }
+          const float lp = lg_act - lse;
+          const float log_ratio = lp - p.old_logp[(long long)n * p.logp_stride + b];
+          const float ratio = expf(log_ratio);
+          const bool in_range = (ratio >= p.clip_lo) && (ratio <= p.clip_hi);
+          const float s1 = ratio * a_n;
+          const float s2 = fminf(fmaxf(ratio, p.clip_lo), p.clip_hi) * a_n;
+          float g_ratio;
+          if (s1 < s2) g_ratio = a_n;
+          else if (s1 > s2) g_ratio = in_range ? a_n : 0.f;
+          else g_ratio = 0.5f * a_n + (in_range ? 0.5f * a_n : 0.f);
+          if (lane == 0) {
+            acc[0] += fminf(s1, s2);
+            acc[2] += ent;
+            acc[3] += (ratio - 1.0f) - log_ratio;
+            acc[4] += (fabsf(ratio - 1.0f) > p.clip) ? 1.f : 0.f;
+          }
+          act_col[b] = ac;
+          const float cpol = -p.pol_scale * g_ratio * ratio;
+#pragma unroll
+          for (int j = 0; j < HL_MAXA; ++j)
+            if (j < A && p.col_branch[j] == b) { lse_c[j] = lse; ent_c[j] = ent; cpol_c[j] = cpol; }
+        }
+      }
+      const float cent = -p.beta * p.ent_scale;
+#pragma unroll
+      for (int j = 0; j < HL_MAXA; ++j) {
+        dl[j] = 0.f;
+        if (j < A) {
+          bool taken = false;
+#pragma unroll
+          for (int b = 0; b < HL_MAXA; ++b) taken = taken || (act_col[b] == j);
+          const float l = lg[j] - lse_c[j];
+          const float pj = expf(l);
+          const float d_lp = (taken ? 1.f : 0.f) - pj;
+          const float d_ent = -pj * (l + ent_c[j]);
+          dl[j] = cpol_c[j] * d_lp + cent * d_ent;
+        }
       }
     }
     const float vo = p.old_value[n];
@@ -298,12 +368,12 @@ extern "C" int64_t etm_heads_loss_workspace_bytes(int N, int hid, int A) {
 // heads; sums [etm_heads_loss_row_floats] = [d b_lp (hid) | d b_lv (hid) | d wv (hid) | d Wb (A x hid) | d bb (A) | d bv | 5 raw sums];
 // out8 = (policy, value, loss, entropy, kl, clip fraction, 0, 0); logits [N, A] / value [N]: optional (NULL: not written).
 // Scales as in etm_ppo_loss (pol_scale = 1 / N for one branch, ent_scale = val_scale = 1 / N).
-extern "C" int etm_heads_loss(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb, const float *bb,
+static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb, const float *bb,
                               const float *wv, const float *bv, const int64_t *actions, int64_t action_stride, const float *old_logp,
                               int64_t logp_stride, const float *adv, const float *old_value, const float *adv_stats3, double clip, float vf_coef,
                               float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v,
                               float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
-                              int A, void *stream) {
+                              int A, const int32_t *branch_sizes, int n_branches, void *stream) {
   (void)hipGetLastError();
   if (!pre_p || !pre_v || !b_lp || !b_lv || !wb || !bb || !wv || !bv || !actions || !old_logp || !adv || !old_value || !adv_stats3 || !gm_p ||
       !gm_v || !sums || !out8 || !workspace)
@@ -311,6 +381,14 @@ extern "C" int etm_heads_loss(const float *pre_p, const float *pre_v, const floa
   if (!etm_heads_loss_supported(N, hid, A)) return ETM_EUNSUPPORTED;
   if (workspace_bytes < etm_heads_loss_workspace_bytes(N, hid, A)) return ETM_EWORKSPACE;
   HlParams p{};
+  EtmBranches br;
+  if (const int rc = etm_branches_make(branch_sizes, n_branches, A, &br)) return rc;
+  const bool branched = br.n > 1;
+  p.nbr = br.n;
+  for (int b = 0, j = 0; b < br.n; ++b) {
+    p.branch_off[b] = j;
+    for (int k = 0; k < br.size[b]; ++k, ++j) p.col_branch[j] = b;
+  }
   p.pre_p = pre_p; p.pre_v = pre_v; p.b_lp = b_lp; p.b_lv = b_lv; p.wb = wb; p.bb = bb; p.wv = wv; p.bv = bv;
   p.actions = (const long long *)actions; p.action_stride = action_stride; p.old_logp = old_logp; p.logp_stride = logp_stride;
   p.adv = adv; p.old_value = old_value; p.adv_stats3 = adv_stats3;
@@ -325,7 +403,11 @@ extern "C" int etm_heads_loss(const float *pre_p, const float *pre_v, const floa
   {
     EtmProfScope prof(ETM_K_PPO_LOSS, st);
     switch (hid / 64) {
-#define HL_CASE(HC_) case HC_: hipLaunchKernelGGL(heads_loss_kernel<HC_>, dim3((unsigned)n_wg), dim3(256), lds, st, p); break;
+#define HL_CASE(HC_)                                                                                              \
+  case HC_:                                                                                                       \
+    if (branched) hipLaunchKernelGGL((heads_loss_kernel<HC_, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else hipLaunchKernelGGL((heads_loss_kernel<HC_, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p);         \
+    break;
       HL_CASE(1) HL_CASE(2) HL_CASE(3) HL_CASE(4) HL_CASE(5) HL_CASE(6) HL_CASE(7) HL_CASE(8)
 #undef HL_CASE
       default: return ETM_EUNSUPPORTED;
@@ -337,4 +419,35 @@ extern "C" int etm_heads_loss(const float *pre_p, const float *pre_v, const floa
   hipLaunchKernelGGL(heads_reduce_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg, row, A, hid, vf_coef,
                      beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8);
   return etm_launch_status();
+}
+
+extern "C" int etm_heads_loss(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb, const float *bb,
+                              const float *wv, const float *bv, const int64_t *actions, int64_t action_stride, const float *old_logp,
+                              int64_t logp_stride, const float *adv, const float *old_value, const float *adv_stats3, double clip, float vf_coef,
+                              float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v,
+                              float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
+                              int A, void *stream) {
+  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
+                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
+                         workspace_bytes, N, hid, A, nullptr, 1, stream);
+}
+
+// MultiDiscrete: wb / bb = the branches' heads concatenated ([sum(sizes), hid], [sum(sizes)]); actions / old_logp rows carry one entry
+// per branch (action_stride, logp_stride >= n_branches).  pol_scale = 1 / (N B), ent_scale = val_scale = 1 / N for ref_algo.ppo_loss.
+extern "C" int etm_heads_loss_supported_branched(int N, int hid, const int32_t *branch_sizes, int n_branches) {
+  const int A = etm_branches_total(branch_sizes, n_branches);
+  return A > 0 && n_branches <= HL_MAXA && etm_heads_loss_supported(N, hid, A);
+}
+extern "C" int etm_heads_loss_branched(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                       const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
+                                       const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
+                                       const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                                       float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
+                                       float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
+                                       const int32_t *branch_sizes, int n_branches, void *stream) {
+  if (!etm_heads_loss_supported_branched(N, hid, branch_sizes, n_branches)) return ETM_EUNSUPPORTED;
+  if (action_stride < n_branches || logp_stride < n_branches) return ETM_EINVAL;
+  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
+                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
+                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, stream);
 }

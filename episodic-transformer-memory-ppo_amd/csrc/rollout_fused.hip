@@ -82,13 +82,14 @@ __global__ __launch_bounds__(RF_T) void rollout_trxl_kernel(const RfParams p) {
   RF_STAMP(0);
   f32x4 wr[GR];                                                    // the product slice in flight
   gemv_issue<GR>(wr, p.wemb_t + mcol, D, 0, DS, 0, DS, 0);
-  // inputs of the sampling at the very end (thread 0 of member 0)
+  // inputs of the sampling at the very end (thread 0 of member 0 samples; threads b < B fetch branch b's entries now)
   const long long t_now = *p.t_dev;                                 // (uniform) step counter of the rollout
-  int a_forced = -1;
-  float u_draw = 0.f;
-  if (me == 0 && tid == 0) {
-    if (p.forced) a_forced = (int)p.forced[t_now * p.stage_W + w];
-    u_draw = p.uniforms[t_now * p.stage_W + w];
+  __shared__ int forced_s[ETM_MAX_BRANCHES];
+  __shared__ float u_s[ETM_MAX_BRANCHES];
+  if (me == 0 && tid < p.br.n) {
+    const long long i = (t_now * p.stage_W + w) * p.br.n + tid;
+    forced_s[tid] = p.forced ? (int)p.forced[i] : -1;
+    u_s[tid] = p.uniforms[i];
   }
   if (tid < D) {
     float v;
@@ -547,20 +548,20 @@ __global__ __launch_bounds__(RF_T) void rollout_trxl_kernel(const RfParams p) {
   if (tid == 0) {
     if (me == 0) {                                                // sampling + staging + hand-over: as rollout_policy_kernel
       const long long t = t_now;
-      const int A = p.A;
-      const float *lg = out_s;
-      float mx = -INFINITY;
-      for (int j = 0; j < A; ++j) mx = fmaxf(mx, lg[j]);
-      float se = 0.f;
-      for (int j = 0; j < A; ++j) se += expf(lg[j] - mx);
-      const float lse = mx + logf(se);
-      int a = a_forced;
-      if (a < 0) a = etm_sample_categorical(lg, A, lse, u_draw);
-      p.actions[w] = a;
-      if (p.host_actions) p.host_actions[w] = a;
-      p.st_actions[t * p.stage_W + w] = a;
-      p.st_logp[t * p.stage_W + w] = lg[a] - lse;
-      p.st_values[t * p.stage_W + w] = lg[A];
+      const int A = p.A, B = p.br.n;
+      const long long row = t * p.stage_W + w;
+      int off = 0;
+      for (int b = 0; b < B; ++b) {                                 // per branch: its own logit segment, uniform and forced entry
+        const int Ab = p.br.size[b];
+        float lp;
+        const int a = etm_sample_branch(out_s + off, Ab, u_s[b], forced_s[b], &lp);
+        p.actions[(long long)w * B + b] = a;
+        if (p.host_actions) p.host_actions[(long long)w * B + b] = a;
+        p.st_actions[row * B + b] = a;
+        p.st_logp[row * B + b] = lp;
+        off += Ab;
+      }
+      p.st_values[row] = out_s[A];
       RF_STAMP(42);
       // this worker's rows are visible before the arrival below -- system scope when the action went to pinned host memory: the
       // host reads it as soon as it sees the flag that the LAST sampler stores, so every sampler's store must have completed at
@@ -782,7 +783,8 @@ static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, 
                                 const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
                                 int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
                                 int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
-                                int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W, void *stream) {
+                                int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W,
+                                const int32_t *branch_sizes, int n_branches, void *stream) {
   (void)hipGetLastError();
   if (ss && (!mask_table || !index_table || !st_mask || !st_idx || !latch || !mask_t || !win_t || T <= 0)) return ETM_EINVAL;
   if (!ss && (!win || !mask)) return ETM_EINVAL;
@@ -802,6 +804,7 @@ static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, 
     if (scratch_bytes < etm_rollout_trxl_scratch_bytes(W, D, H, nb)) return ETM_EWORKSPACE;
   }
   RfParams p{};
+  if (const int rc = etm_branches_make(branch_sizes, n_branches, A, &p.br)) return rc;
   p.ss = (const long long *)ss; p.mask_table = mask_table; p.index_table = (const long long *)index_table; p.st_mask = st_mask;
   p.st_idx = (long long *)st_idx; p.latch = (long long *)latch; p.t_row = (long long *)t_row; p.mask_t = mask_t; p.win_t = (long long *)win_t;
   p.kv_init = kv_init; p.T = T;
@@ -864,7 +867,7 @@ extern "C" int etm_rollout_trxl(const float *h_in, const float *wemb_t, const fl
   return rollout_trxl_impl(0, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
                           actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
                           slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
-                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, stream);
+                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, nullptr, 1, stream);
 }
 // The group form (csrc/rollout_group.hip): same arguments, other matrix packings (see there) and scratch size
 // (etm_rollout_trxl_group_scratch_bytes); W <= 8 workers, GRU-gated blocks -- etm_rollout_trxl_group_supported.
@@ -881,5 +884,51 @@ extern "C" int etm_rollout_trxl_group(const float *h_in, const float *wemb_t, co
   return rollout_trxl_impl(1, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
                           actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
                           slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
-                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, stream);
+                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, nullptr, 1, stream);
+}
+
+// MultiDiscrete policies: the same two launches with the action branches given by their sizes (wp / bp = the branches' heads
+// concatenated, A = the sum of the sizes); uniforms, forced, st_actions and st_logp are [S, stage_W, B], actions and host_actions [W, B].
+extern "C" int etm_rollout_trxl_branched(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
+                                int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
+                                const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
+                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
+                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
+                                float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
+                                const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
+                                int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
+                                int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
+                                int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int stage_W, const int32_t *branch_sizes,
+                                int n_branches, void *stream) {
+  return rollout_trxl_impl(0, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
+                          actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
+                          slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
+                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, etm_branches_total(branch_sizes, n_branches), stage_W,
+                          branch_sizes, n_branches, stream);
+}
+extern "C" int etm_rollout_trxl_group_branched(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
+                                int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
+                                const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
+                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
+                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
+                                float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
+                                const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
+                                int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
+                                int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
+                                int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int stage_W, const int32_t *branch_sizes,
+                                int n_branches, void *stream) {
+  return rollout_trxl_impl(1, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
+                          actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
+                          slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
+                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, etm_branches_total(branch_sizes, n_branches), stage_W,
+                          branch_sizes, n_branches, stream);
+}
+extern "C" int etm_rollout_trxl_supported_branched(int D, int H, int L, int hid, const int32_t *branch_sizes, int n_branches, int nb) {
+  const int A = etm_branches_total(branch_sizes, n_branches);
+  return A > 0 && etm_rollout_trxl_supported(D, H, L, hid, A, nb);
+}
+extern "C" int etm_rollout_trxl_group_supported_branched(int D, int H, int L, int hid, const int32_t *branch_sizes, int n_branches, int nb,
+                                                         int W, int gtrxl) {
+  const int A = etm_branches_total(branch_sizes, n_branches);
+  return A > 0 && etm_rollout_trxl_group_supported(D, H, L, hid, A, nb, W, gtrxl);
 }

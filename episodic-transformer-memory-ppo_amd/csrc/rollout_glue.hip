@@ -53,8 +53,6 @@ __global__ __launch_bounds__(256) void rollout_window_kernel(const long long *__
   st_idx[t * stage_W * L + i] = idx;
 }
 
-// One thread per worker: log-softmax, inverse-CDF sample with the pre-drawn uniform of (t, w) (or a forced action),
-// log-prob, staging of actions / log_probs / values for step t; finally t += 1.
 // Output heads of the actor-critic for the rollout (model.py:108-110): logits[w, a] = Wp[a,:] . h_pol[w,:] + bp[a] and
 // value[w] = Wv . h_val[w,:] + bv, with h = [h_pol | h_val] rows of length 2*hid.  One wave per (worker, output).
 __global__ __launch_bounds__(256) void rollout_heads_kernel(const float *__restrict__ h, const float *__restrict__ wp, const float *__restrict__ bp,
@@ -75,33 +73,25 @@ __global__ __launch_bounds__(256) void rollout_heads_kernel(const float *__restr
   }
 }
 
+// One thread per worker: per action branch log-softmax over its segment, inverse-CDF sample with the pre-drawn uniform of
+// (t, w, b) (or a forced action), log-prob; staging of actions / log_probs / values for step t; finally t += 1.
 __global__ __launch_bounds__(1024) void rollout_sample_kernel(const float *__restrict__ logits, const float *__restrict__ value,
                                                               const float *__restrict__ uniforms, const long long *__restrict__ forced,
                                                               long long *__restrict__ t_dev, long long *__restrict__ actions,
                                                               long long *__restrict__ st_actions, float *__restrict__ st_logp,
-                                                              float *__restrict__ st_values, int W, int A) {
+                                                              float *__restrict__ st_values, int W, int A, const EtmBranches br) {
   const long long t = *t_dev;
   for (int w = threadIdx.x; w < W; w += 1024) {
-    const float *lg = logits + (long long)w * A;
-    float mx = -INFINITY;
-    for (int j = 0; j < A; ++j) mx = fmaxf(mx, lg[j]);
-    float se = 0.f;
-    for (int j = 0; j < A; ++j) se += expf(lg[j] - mx);
-    const float lse = mx + logf(se);
-    int a = forced ? (int)forced[t * W + w] : -1;      // forced: time-major table [S, W]; a negative entry means "sample"
-    if (a < 0) {
-      a = etm_sample_categorical(lg, A, lse, uniforms[t * W + w]);
-    }
-    actions[w] = a;
-    st_actions[t * W + w] = a;
-    st_logp[t * W + w] = lg[a] - lse;
+    // logits [W, A]: the branches' segments side by side; forced / uniforms / staging time-major [S, W, B] (B = 1: [S, W]), a
+    // negative forced entry means "sample"
+    etm_sample_branches(logits + (long long)w * A, br, t * W + w, w, uniforms, forced, actions, nullptr, st_actions, st_logp);
     st_values[t * W + w] = value[w];
   }
   __syncthreads();
   if (threadIdx.x == 0) *t_dev = t + 1;
 }
 
-// Output heads + sampling of a single-branch policy in ONE launch (rollout_heads_kernel + rollout_sample_kernel): one
+// Output heads + sampling of a policy (every action branch) in ONE launch (rollout_heads_kernel + rollout_sample_kernel): one
 // workgroup per worker, one wave per output (A logits + the value; a single workgroup looping over all W (A + 1) dot products
 // took 19 us, each pass being one global-memory round trip), then lane 0 samples.  The step counter is advanced by the LAST
 // workgroup to finish (every workgroup has read it by then).  Optional hand-over to the host without a copy launch and
@@ -115,8 +105,8 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel(const float *__rest
                                                              long long *__restrict__ actions, long long *__restrict__ st_actions,
                                                              float *__restrict__ st_logp, float *__restrict__ st_values,
                                                              long long *host_actions, long long *host_flag, int *sync_counter,
-                                                             int W, int A, int hid, int stage_W) {
-  extern __shared__ float out_s[];   // [A + 1]: logits, then the value
+                                                             int W, int A, int hid, int stage_W, const EtmBranches br) {
+  extern __shared__ float out_s[];   // [A + 1]: logits (the branches' segments side by side), then the value
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w = blockIdx.x;
   const long long t = *t_dev;
   for (int o = wave; o < A + 1; o += 4) {
@@ -134,21 +124,9 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel(const float *__rest
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float *lg = out_s;
-    float mx = -INFINITY;
-    for (int j = 0; j < A; ++j) mx = fmaxf(mx, lg[j]);
-    float se = 0.f;
-    for (int j = 0; j < A; ++j) se += expf(lg[j] - mx);
-    const float lse = mx + logf(se);
-    int a = forced ? (int)forced[t * stage_W + w] : -1;   // forced: time-major table [S, stage_W]; negative = "sample"
-    if (a < 0) {
-      a = etm_sample_categorical(lg, A, lse, uniforms[t * stage_W + w]);
-    }
-    actions[w] = a;
-    if (host_actions) host_actions[w] = a;
-    st_actions[t * stage_W + w] = a;
-    st_logp[t * stage_W + w] = lg[a] - lse;
-    st_values[t * stage_W + w] = lg[A];
+    // forced / uniforms / staging: time-major [S, stage_W, B] (B = 1: [S, stage_W]); negative forced entry = "sample"
+    etm_sample_branches(out_s, br, t * stage_W + w, w, uniforms, forced, actions, host_actions, st_actions, st_logp);
+    st_values[t * stage_W + w] = out_s[A];
     if (host_actions) __threadfence_system();            // (host memory: see rollout_fused.hip) this worker's rows are visible before
     else __threadfence();                                // the arrival below
     if (atomicAdd(sync_counter, 1) == W - 1) {           // last workgroup of the step
@@ -224,15 +202,51 @@ extern "C" int etm_rollout_window(const int64_t *step, const uint8_t *mask_table
   return etm_launch_status();
 }
 
-extern "C" int etm_rollout_sample(const float *logits, const float *value, const float *uniforms, const int64_t *forced, int64_t *t_dev,
-                                  int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W, int A, void *stream) {
+static int rollout_sample_impl(const float *logits, const float *value, const float *uniforms, const int64_t *forced, int64_t *t_dev,
+                               int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W, int A,
+                               const int32_t *branch_sizes, int n_branches, void *stream) {
   (void)hipGetLastError();
   if (!logits || !value || !uniforms || !t_dev || !actions || !st_actions || !st_logp || !st_values || W <= 0 || A <= 0)
     return ETM_EINVAL;
+  EtmBranches br;
+  if (const int rc = etm_branches_make(branch_sizes, n_branches, A, &br)) return rc;
   hipStream_t st = (hipStream_t)stream;
   EtmProfScope prof(ETM_K_ROLLOUT_SAMPLE, st);
   hipLaunchKernelGGL(rollout_sample_kernel, dim3(1), dim3(1024), 0, st, logits, value, uniforms, (const long long *)forced, (long long *)t_dev,
-                     (long long *)actions, (long long *)st_actions, st_logp, st_values, W, A);
+                     (long long *)actions, (long long *)st_actions, st_logp, st_values, W, A, br);
+  return etm_launch_status();
+}
+
+extern "C" int etm_rollout_sample(const float *logits, const float *value, const float *uniforms, const int64_t *forced, int64_t *t_dev,
+                                  int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W, int A, void *stream) {
+  return rollout_sample_impl(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W, A, nullptr, 1, stream);
+}
+
+extern "C" int etm_rollout_sample_branched(const float *logits, const float *value, const float *uniforms, const int64_t *forced,
+                                           int64_t *t_dev, int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W,
+                                           const int32_t *branch_sizes, int n_branches, void *stream) {
+  return rollout_sample_impl(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W,
+                             etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, stream);
+}
+
+static int rollout_policy_impl(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv, const float *bv,
+                               const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
+                               float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
+                               int W, int A, int hid, int stage_W, const int32_t *branch_sizes, int n_branches, void *stream) {
+  (void)hipGetLastError();
+  if (!h || !wp || !bp || !wv || !bv || !uniforms || !t_dev || !actions || !st_actions || !st_logp || !st_values ||
+      !sync_counter || W <= 0 || A <= 0 || hid <= 0 || stage_W < W)
+    return ETM_EINVAL;
+  if (host_flag && !host_actions) return ETM_EINVAL;
+  EtmBranches br;
+  if (const int rc = etm_branches_make(branch_sizes, n_branches, A, &br)) return rc;
+  const size_t lds = (size_t)(A + 1) * sizeof(float);
+  if (lds > 64 * 1024) return ETM_EUNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  EtmProfScope prof(ETM_K_ROLLOUT_SAMPLE, st);
+  hipLaunchKernelGGL(rollout_policy_kernel, dim3((unsigned)W), dim3(256), lds, st, h, wp, bp, wv, bv, h_bias, uniforms, (const long long *)forced,
+                     (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values, (long long *)host_actions,
+                     (long long *)host_flag, (int *)sync_counter, W, A, hid, stage_W, br);
   return etm_launch_status();
 }
 
@@ -240,19 +254,18 @@ extern "C" int etm_rollout_policy(const float *h, const float *h_bias, const flo
                                   const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
                                   float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
                                   int W, int A, int hid, int stage_W, void *stream) {
-  (void)hipGetLastError();
-  if (!h || !wp || !bp || !wv || !bv || !uniforms || !t_dev || !actions || !st_actions || !st_logp || !st_values ||
-      !sync_counter || W <= 0 || A <= 0 || hid <= 0 || stage_W < W)
-    return ETM_EINVAL;
-  if (host_flag && !host_actions) return ETM_EINVAL;
-  const size_t lds = (size_t)(A + 1) * sizeof(float);
-  if (lds > 64 * 1024) return ETM_EUNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  EtmProfScope prof(ETM_K_ROLLOUT_SAMPLE, st);
-  hipLaunchKernelGGL(rollout_policy_kernel, dim3((unsigned)W), dim3(256), lds, st, h, wp, bp, wv, bv, h_bias, uniforms, (const long long *)forced,
-                     (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values, (long long *)host_actions,
-                     (long long *)host_flag, (int *)sync_counter, W, A, hid, stage_W);
-  return etm_launch_status();
+  return rollout_policy_impl(h, h_bias, wp, bp, wv, bv, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions,
+                             host_flag, sync_counter, W, A, hid, stage_W, nullptr, 1, stream);
+}
+
+extern "C" int etm_rollout_policy_branched(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv,
+                                           const float *bv, const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions,
+                                           int64_t *st_actions, float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag,
+                                           int32_t *sync_counter, int W, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,
+                                           void *stream) {
+  return rollout_policy_impl(h, h_bias, wp, bp, wv, bv, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions,
+                             host_flag, sync_counter, W, etm_branches_total(branch_sizes, n_branches), hid, stage_W, branch_sizes,
+                             n_branches, stream);
 }
 
 extern "C" int etm_rollout_heads(const float *h, const float *wp, const float *bp, const float *wv, const float *bv, float *logits,

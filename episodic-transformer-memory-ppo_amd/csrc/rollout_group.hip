@@ -623,19 +623,8 @@ __global__ __launch_bounds__(RF_T) void rollout_group_kernel(const RfParams p) {
     if (tid < W) {                                                   // sampling + staging + hand-over of worker tid (as rollout_policy_kernel)
       const long long t = t_now;
       const float *lg = out_s + tid * 16;
-      const int a_forced = p.forced ? (int)p.forced[t * p.stage_W + tid] : -1;
-      const float u_draw = p.uniforms[t * p.stage_W + tid];
-      float mx = -INFINITY;
-      for (int j = 0; j < A; ++j) mx = fmaxf(mx, lg[j]);
-      float se = 0.f;
-      for (int j = 0; j < A; ++j) se += expf(lg[j] - mx);
-      const float lse = mx + logf(se);
-      int a = a_forced;
-      if (a < 0) a = etm_sample_categorical(lg, A, lse, u_draw);
-      p.actions[tid] = a;
-      if (p.host_actions) p.host_actions[tid] = a;
-      p.st_actions[t * p.stage_W + tid] = a;
-      p.st_logp[t * p.stage_W + tid] = lg[a] - lse;
+      // per branch: its own logit segment, uniform and forced entry ([S, stage_W, B] tables; B = 1: [S, stage_W])
+      etm_sample_branches(lg, p.br, t * p.stage_W + tid, tid, p.uniforms, p.forced, p.actions, p.host_actions, p.st_actions, p.st_logp);
       p.st_values[t * p.stage_W + tid] = lg[A];
       if (p.host_actions) __threadfence_system();
       else __threadfence();

@@ -45,8 +45,8 @@ struct RfParams {
   const unsigned char *mask;         // [W, L]
   float *items;                      // [nb, W, D] block-major new memory items
   const float *wh_t, *bh;            // [D, 2 hid] transposed [lin_policy ; lin_value], [2 hid]
-  const float *wp, *bp, *wv, *bv;    // output heads [A, hid], [A], [hid], [1]
-  const float *uniforms;
+  const float *wp, *bp, *wv, *bv;    // output heads [A, hid] (the branches' heads concatenated), [A], [hid], [1]
+  const float *uniforms;             // time-major [S, stage_W, B] (B = 1: [S, stage_W]), as forced, st_actions and st_logp
   const long long *forced;
   long long *t_dev, *actions, *st_actions;
   float *st_logp, *st_values;
@@ -65,6 +65,7 @@ struct RfParams {
   float *bank;                       // [slots, T, nb, D]
   long long bank_slot_stride, bank_row_stride, bank_block_stride;   // floats: bank[slot, step, block, :] (block-major bank: block stride = slots * T * D)
   int W, D, H, L, hid, A, stage_W, P;
+  EtmBranches br;                    // action branches: segments of the A = sum(sizes) logit columns (one branch: Discrete)
   int map_mode;                      // block -> (worker, member) placement, see etm_rollout_trxl_set_placement
   float eps, sqrt_d;
 };

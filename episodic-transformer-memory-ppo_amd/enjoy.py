@@ -13,6 +13,7 @@ import pickle
 import numpy as np
 import torch
 
+from environments import action_space_shape
 from model import ActorCriticModel
 from trainer import build_window_tables
 from utils import create_env
@@ -58,7 +59,7 @@ def main():
     with open(args.model, "rb") as f:
         state_dict, config = pickle.load(f)
     env = create_env(config["environment"], render=True)
-    model = ActorCriticModel(config, env.observation_space, (env.action_space.n,), env.max_episode_steps)
+    model = ActorCriticModel(config, env.observation_space, action_space_shape(env.action_space), env.max_episode_steps)
     model.load_state_dict(state_dict)
     model.to(device)
     model.eval()

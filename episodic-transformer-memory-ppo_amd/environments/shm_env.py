@@ -224,12 +224,15 @@ def _probe_env(env_config):
     else:
         from utils import create_env
         e = create_env(env_config)
-    if not hasattr(e.action_space, "n"):
+    from environments import action_space_shape
+    branches = action_space_shape(e.action_space)
+    if len(branches) > 1:
         e.close()
-        raise NotImplementedError("worker_processes supports single-branch (Discrete) action spaces only: the shared segment carries one "
-                                  "action word per environment and the trainer's device-side hand-over writes one; use the in-process "
-                                  "environments (worker_processes: false) for a MultiDiscrete space")
-    res = tuple(e.observation_space.shape), int(e.action_space.n), int(e.max_episode_steps)
+        raise NotImplementedError(f"worker_processes supports single-branch (Discrete) action spaces only, not the {len(branches)} "
+                                  "branches of this MultiDiscrete space: the shared segment carries one action word per environment "
+                                  "and the native rollout driver hands over one; set worker_processes: false (in-process "
+                                  "environments take MultiDiscrete spaces)")
+    res = tuple(e.observation_space.shape), branches[0], int(e.max_episode_steps)
     e.close()
     return res
 
@@ -242,6 +245,7 @@ class _ShmGroup:
         self.num_envs = hi - lo
         self.observation_space_shape = parent.observation_space_shape
         self.num_actions, self.max_episode_steps = parent.num_actions, parent.max_episode_steps
+        self.action_space_shape = parent.action_space_shape
 
     def step(self, actions, out=None, on_rows=None):
         return self.parent._step_groups([self.g], actions, out, on_rows, self.lo)
@@ -262,6 +266,7 @@ class ShmVecEnv:
                  steps_per_rollout: int = 1, num_branches: int = 1, spin: bool = True):
         shape, n_act, T = _probe_env(env_config)
         self.observation_space_shape, self.num_actions, self.max_episode_steps = tuple(shape), int(n_act), int(T)
+        self.action_space_shape = (self.num_actions,)
         W, G = int(num_envs), int(groups)
         if W % G != 0:
             raise ValueError("num_envs must be a multiple of groups")

@@ -11,6 +11,9 @@ Two forms that generate *identical* streams:
   (one call per rollout step for all workers, observations written straight
   into a caller-provided -- normally pinned -- host buffer).
 
+``num_actions``: an int (Discrete) or a list (MultiDiscrete: ``action_space.nvec``, one branch per entry).  Actions do not drive
+the synthetic dynamics: the observation, reward and done streams are the same for every action space.
+
 Workload (BASELINE.md section 3 / SURVEY.md section 8d): observation ~ U[0,1) float32 of
 ``obs_shape`` from ``numpy.random.default_rng(seed + worker_id)``, reward
 Bernoulli(0.05), done when the episode reaches ``max_episode_steps`` or with
@@ -107,13 +110,23 @@ class _WorkerStream:
         return row
 
 
+def _branches(num_actions):
+    """(action_space_shape, nvec or None) of a ``num_actions`` setting: an int is Discrete(n), a list / tuple MultiDiscrete(nvec)."""
+    if isinstance(num_actions, (list, tuple, np.ndarray)):
+        nvec = tuple(int(n) for n in num_actions)
+        if not nvec or min(nvec) <= 0:
+            raise ValueError(f"num_actions {list(nvec)}: every branch needs at least one action")
+        return nvec, nvec
+    return (int(num_actions),), None
+
+
 class SyntheticEnv:
     """Single env, reference env API.  ``worker_id`` selects the RNG stream."""
 
     def __init__(self, obs_shape=(3, 84, 84), num_actions=3, max_episode_steps=96, seed=0, worker_id=0,
                  p_reward=0.05, p_done=0.02, pool=64):
         self._shape = tuple(obs_shape)
-        self._n_act = int(num_actions)
+        self._branches, self._nvec = _branches(num_actions)
         self._T = int(max_episode_steps)
         self._p_r, self._p_d = float(p_reward), float(p_done)
         self._s = _WorkerStream(worker_id, self._shape, seed, pool)
@@ -128,7 +141,9 @@ class SyntheticEnv:
 
     @property
     def action_space(self):
-        return SimpleNamespace(n=self._n_act)
+        if self._nvec is not None:       # (as gym's MultiDiscrete: nvec, shape = (branches,))
+            return SimpleNamespace(nvec=np.array(self._nvec, dtype=np.int64), shape=(len(self._nvec),))
+        return SimpleNamespace(n=self._branches[0])
 
     @property
     def max_episode_steps(self):
@@ -181,7 +196,10 @@ class SyntheticVecEnv:
             self.MIN_CHUNKED_ENVS = int(min_chunked_envs)
         self._row_bytes = int(np.prod(obs_shape)) * 4
         self.observation_space_shape = tuple(obs_shape)
-        self.num_actions = int(num_actions)
+        self.action_space_shape, nvec = _branches(num_actions)     # (actions do not drive the dynamics)
+        self.num_actions = sum(self.action_space_shape)
+        self.action_space = (SimpleNamespace(nvec=np.array(nvec, dtype=np.int64), shape=(len(nvec),)) if nvec is not None
+                             else SimpleNamespace(n=self.num_actions))
         self.max_episode_steps = int(max_episode_steps)
         self._p_r, self._p_d = float(p_reward), float(p_done)
         self._pool = pool

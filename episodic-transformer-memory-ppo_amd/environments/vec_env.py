@@ -1,7 +1,9 @@
 """Vectorised environment front-ends for the trainer.
 
 ``VecEnv`` protocol (what ``PPOTrainer`` steps):
-    num_envs, observation_space_shape, num_actions, max_episode_steps
+    num_envs, observation_space_shape, action_space_shape, num_actions, max_episode_steps
+        action_space_shape: one entry per action branch (environments.action_space_shape: ``nvec`` of a MultiDiscrete space,
+        ``(n,)`` of a Discrete one); num_actions: n of a Discrete space, the sum of ``nvec`` (the policy's logits) otherwise
     reset(out=None) -> obs [W, *obs_shape] float32
     step(actions [W] or [W, B], out=None, on_rows=None) -> (obs, rewards [W] f32, dones [W] bool, infos [W] (dict or None))
         on_rows(lo, hi), optional: called as soon as observation rows [lo, hi) of ``out`` are final, in increasing order and
@@ -14,6 +16,8 @@ is exactly what upstream's loop does by hand (trainer.py:195-201).
 * ``environments.synthetic.SyntheticVecEnv`` implements the protocol natively.
 """
 import numpy as np
+
+from environments import action_space_shape
 
 
 class _VecBase:
@@ -40,7 +44,8 @@ class SerialVecEnv(_VecBase):
         self.num_envs = len(self.envs)
         e = self.envs[0]
         self.observation_space_shape = tuple(e.observation_space.shape)
-        self.num_actions = int(e.action_space.n)
+        self.action_space_shape = action_space_shape(e.action_space)
+        self.num_actions = sum(self.action_space_shape)
         self.max_episode_steps = int(e.max_episode_steps)
 
     def reset(self, out=None):
@@ -57,7 +62,7 @@ class SerialVecEnv(_VecBase):
         infos = [None] * self.num_envs
         sent = 0
         for w, e in enumerate(self.envs):
-            obs, rewards[w], dones[w], info = e.step(actions[w])
+            obs, rewards[w], dones[w], info = e.step(actions[w])      # (one row [B] per environment: one action per branch)
             if info:
                 infos[w] = info
                 obs = e.reset()
@@ -79,7 +84,8 @@ class PipeVecEnv(_VecBase):
         from worker import Worker
         probe = create_env(env_config)
         self.observation_space_shape = tuple(probe.observation_space.shape)
-        self.num_actions = int(probe.action_space.n)
+        self.action_space_shape = action_space_shape(probe.action_space)
+        self.num_actions = sum(self.action_space_shape)
         self.max_episode_steps = int(probe.max_episode_steps)
         probe.close()
         self.num_envs = num_envs
@@ -142,6 +148,7 @@ class CompositeVecEnv(_VecBase):
         self.num_envs = lo
         e = self.parts[0]
         self.observation_space_shape = tuple(e.observation_space_shape)
+        self.action_space_shape = tuple(getattr(e, "action_space_shape", None) or (int(e.num_actions),))
         self.num_actions = int(e.num_actions)
         self.max_episode_steps = int(e.max_episode_steps)
 
@@ -153,7 +160,7 @@ class CompositeVecEnv(_VecBase):
 
     def step(self, actions, out=None, on_rows=None):
         out = self._alloc(out)
-        actions = np.asarray(actions)
+        actions = np.asarray(actions)                          # [W] or [W, B]: the parts take their rows
         rewards = np.zeros(self.num_envs, dtype=np.float32)
         dones = np.zeros(self.num_envs, dtype=bool)
         infos = []

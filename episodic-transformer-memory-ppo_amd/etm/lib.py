@@ -7,7 +7,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: torch ships its ow
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libetm_hip.so")     # (diagnostic tools that load another build assign this before load())
-ABI_VERSION = 47
+ABI_VERSION = 48
 
 _lib = None
 
@@ -36,6 +36,7 @@ SIGNATURES = {
     "etm_reset_rows": (_I, [_P, _P, _P, _I, _L, _P]),
     "etm_rollout_window": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
     "etm_rollout_sample": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "etm_rollout_sample_branched": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
     "etm_add_layernorm": (_I, [_P, _P, _I, _P, _P, _P, _F, _P, _I, _I, _P]),
     "etm_conv_relu": (_I, [_P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "etm_upload": (_I, [_P, _P, _L, _P]),
@@ -50,6 +51,7 @@ SIGNATURES = {
     "etm_allreduce_f32": (_I, [_P, _P, _P, _L, _P]),
     "etm_comm_destroy": (_I, [_P]),
     "etm_rollout_policy": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "etm_rollout_policy_branched": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P]),
     "etm_conv_pack_weights": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "etm_gather_rows": (_I, [_P, _P, _P, _I, _P, _L, _L, _P]),
     "etm_group_norms": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P]),
@@ -71,7 +73,15 @@ SIGNATURES = {
     "etm_rollout_trxl_group": (_I, [_P, _P, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F,
                                     _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I,
                                     _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "etm_rollout_trxl_branched": (_I, [_P, _P, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F,
+                                       _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I,
+                                       _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "etm_rollout_trxl_group_branched": (_I, [_P, _P, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F,
+                                             _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I,
+                                             _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "etm_rollout_trxl_group_supported": (_I, [_I] * 8),
+    "etm_rollout_trxl_supported_branched": (_I, [_I, _I, _I, _I, _P, _I, _I]),
+    "etm_rollout_trxl_group_supported_branched": (_I, [_I, _I, _I, _I, _P, _I, _I, _I, _I]),
     "etm_rollout_trxl_group_grid": (_I, []),
     "etm_rollout_trxl_group_scratch_bytes": (_L, [_I]),
     "etm_window_set_skip_masked": (_I, [_I]),
@@ -126,6 +136,9 @@ SIGNATURES = {
     "etm_heads_loss_workspace_bytes": (_L, [_I, _I, _I]),
     "etm_heads_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _D, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _L,
                             _I, _I, _I, _P]),
+    "etm_heads_loss_supported_branched": (_I, [_I, _I, _P, _I]),
+    "etm_heads_loss_branched": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _D, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P,
+                                     _P, _L, _I, _I, _P, _I, _P]),
     "etm_window_fwd": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _F, _P, _L, _L, _P, _P, _L, _L, _P, _I, _I, _I, _I, _I, _P]),
     "etm_window_ln_grad_rows": (_I, [_I]),
     "etm_window_ln_grad": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _P, _I, _I, _I, _I, _P]),

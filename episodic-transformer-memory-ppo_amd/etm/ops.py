@@ -723,24 +723,49 @@ def rollout_window(step, mask_table, index_table, t_dev, mask_t, win_t, st_mask,
                                       relems, W, L, stage_w, _stream()), "etm_rollout_window")
 
 
-def rollout_sample(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values):
-    """Categorical sampling + staging of one rollout step for a single-branch policy (in place; increments t_dev).
-    ``forced`` (optional): time-major int64 table [S, W]; entries >= 0 replace the sample of that (step, worker)."""
+def _branch_sizes(branches):
+    """Branch sizes of a MultiDiscrete policy as a tuple, or None for a single branch (``branches``: None, an int or a sequence)."""
+    if branches is None or isinstance(branches, int):
+        return None
+    sizes = tuple(int(a) for a in branches)
+    return sizes if len(sizes) > 1 else None
+
+
+def _branch_table(sizes):
+    import ctypes
+    return (ctypes.c_int32 * len(sizes))(*sizes), len(sizes)
+
+
+def rollout_sample(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, branches=None):
+    """Categorical sampling + staging of one rollout step (in place; increments t_dev).  ``forced`` (optional): time-major int64
+    table [S, W]; entries >= 0 replace the sample of that (step, worker).  ``branches`` (optional, MultiDiscrete): the branch sizes;
+    ``logits`` [W, sum] holds the branches' logits side by side, every branch is sampled on its own segment with its own uniform, and
+    ``uniforms`` / ``forced`` / ``st_actions`` / ``st_logp`` are [S, W, B], ``actions`` [W, B] (etm_rollout_sample_branched)."""
     lib = _lib.load()
     W, A = logits.shape
     logits, value = _f32c(logits, "logits"), _f32c(value, "value")
-    _lib.check(lib.etm_rollout_sample(_ptr(logits), _ptr(value), _ptr(uniforms), _ptr(forced), _ptr(t_dev), _ptr(actions),
-                                      _ptr(st_actions), _ptr(st_logp), _ptr(st_values), W, A, _stream()), "etm_rollout_sample")
+    sizes = _branch_sizes(branches)
+    if sizes is None:
+        _lib.check(lib.etm_rollout_sample(_ptr(logits), _ptr(value), _ptr(uniforms), _ptr(forced), _ptr(t_dev), _ptr(actions),
+                                          _ptr(st_actions), _ptr(st_logp), _ptr(st_values), W, A, _stream()), "etm_rollout_sample")
+        return
+    if sum(sizes) != A:
+        raise ValueError(f"rollout_sample: branches {sizes} do not add up to the {A} logit columns")
+    tab, nbr = _branch_table(sizes)
+    _lib.check(lib.etm_rollout_sample_branched(_ptr(logits), _ptr(value), _ptr(uniforms), _ptr(forced), _ptr(t_dev), _ptr(actions),
+                                               _ptr(st_actions), _ptr(st_logp), _ptr(st_values), W, tab, nbr, _stream()),
+               "etm_rollout_sample_branched")
 
 
 _policy_sync = {}
 
 
 def rollout_policy(h2, policy_head, value_head, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values,
-                   host_actions=None, host_flag=None, h_bias=None, w_off=0):
-    """``rollout_heads`` + ``rollout_sample`` in one launch (single-branch policy); ``host_actions`` / ``host_flag``: pinned
-    int64 tensors that receive the actions and then the incremented step counter (the host spins on the flag).  ``forced``
-    (optional): time-major int64 table [S, W_total]; entries >= 0 replace the sample of that (step, worker)."""
+                   host_actions=None, host_flag=None, h_bias=None, w_off=0, branches=None):
+    """``rollout_heads`` + ``rollout_sample`` in one launch; ``host_actions`` / ``host_flag``: pinned int64 tensors that receive
+    the actions and then the incremented step counter (the host spins on the flag).  ``forced`` (optional): time-major int64 table
+    [S, W_total]; entries >= 0 replace the sample of that (step, worker).  ``branches`` (optional, MultiDiscrete): the branch sizes;
+    ``policy_head`` is then the branches' heads concatenated ([sum, hid]) and the tables are as in ``rollout_sample``."""
     lib = _lib.load()
     W, A = h2.shape[0], policy_head.weight.shape[0]
     hid = h2.shape[1] // 2
@@ -751,21 +776,41 @@ def rollout_policy(h2, policy_head, value_head, uniforms, forced, t_dev, actions
     if sync is None:
         sync = _policy_sync[t_dev.data_ptr()] = torch.zeros(1, dtype=torch.int32, device=h2.device)
     # worker groups: h2 / actions / forced / host_actions cover this group's W workers; uniforms and the staging arrays are
-    # [S, W_total(, 1)] and are addressed from the group's first worker ``w_off``
+    # [S, W_total(, B)] and are addressed from the group's first worker ``w_off``
     stage_w = st_values.shape[1]
-    off = lambda t: None if t is None else t.data_ptr() + w_off * t.element_size()
-    _lib.check(lib.etm_rollout_policy(_ptr(h2), _ptr(h_bias), _ptr(policy_head.weight), _ptr(policy_head.bias), _ptr(value_head.weight),
-                                      _ptr(value_head.bias), off(uniforms), off(forced), _ptr(t_dev), _ptr(actions), off(st_actions),
-                                      off(st_logp), off(st_values), ha, hf, _ptr(sync), W, A, hid, stage_w, _stream()),
-               "etm_rollout_policy")
+    sizes = _branch_sizes(branches)
+    nb_ = 1 if sizes is None else len(sizes)
+    off = lambda t: None if t is None else t.data_ptr() + w_off * nb_ * t.element_size()
+    if sizes is None:
+        _lib.check(lib.etm_rollout_policy(_ptr(h2), _ptr(h_bias), _ptr(policy_head.weight), _ptr(policy_head.bias), _ptr(value_head.weight),
+                                          _ptr(value_head.bias), off(uniforms), off(forced), _ptr(t_dev), _ptr(actions), off(st_actions),
+                                          off(st_logp), off(st_values), ha, hf, _ptr(sync), W, A, hid, stage_w, _stream()),
+                   "etm_rollout_policy")
+        return
+    if sum(sizes) != A:
+        raise ValueError(f"rollout_policy: branches {sizes} do not add up to the {A} rows of the policy head")
+    tab, nbr = _branch_table(sizes)
+    _lib.check(lib.etm_rollout_policy_branched(_ptr(h2), _ptr(h_bias), _ptr(policy_head.weight), _ptr(policy_head.bias),
+                                               _ptr(value_head.weight), _ptr(value_head.bias), off(uniforms), off(forced), _ptr(t_dev),
+                                               _ptr(actions), off(st_actions), off(st_logp), st_values.data_ptr() + w_off * st_values.element_size(),
+                                               ha, hf, _ptr(sync), W, hid, stage_w, tab, nbr, _stream()),
+               "etm_rollout_policy_branched")
 
 
 def rollout_trxl_group_ok(fused_group, W, L, hid, A):
     """Does the group form of the step kernel (etm_rollout_trxl_group, csrc/rollout_group.hip) take a worker group of W workers of
-    this model?  ``fused_group``: ``ActorCriticModel._rfg`` (None: the model has no group packings)."""
+    this model?  ``fused_group``: ``ActorCriticModel._rfg`` (None: the model has no group packings).  ``A``: the number of actions,
+    or the branch sizes of a MultiDiscrete policy."""
     if fused_group is None:
         return False
-    return bool(_lib.load().etm_rollout_trxl_group_supported(fused_group["D"], fused_group["H"], L, hid, A, fused_group["nb"], W, fused_group["gtrxl"]))
+    lib = _lib.load()
+    sizes = _branch_sizes(A)
+    if sizes is None:
+        a = A if isinstance(A, int) else int(tuple(A)[0])
+        return bool(lib.etm_rollout_trxl_group_supported(fused_group["D"], fused_group["H"], L, hid, a, fused_group["nb"], W, fused_group["gtrxl"]))
+    tab, nbr = _branch_table(sizes)
+    return bool(lib.etm_rollout_trxl_group_supported_branched(fused_group["D"], fused_group["H"], L, hid, tab, nbr, fused_group["nb"], W,
+                                                              fused_group["gtrxl"]))
 
 
 def rollout_trxl_scratch(W, D, H, nb, device, group=False):
@@ -787,12 +832,18 @@ def rollout_trxl_clear_error(scratch):
 
 
 def rollout_trxl_supported(D, H, L, hid, A, nb):
-    """Does ``rollout_trxl`` handle these shapes (etm_rollout_trxl_supported)?"""
-    return bool(_lib.load().etm_rollout_trxl_supported(D, H, L, hid, A, nb))
+    """Does ``rollout_trxl`` handle these shapes (etm_rollout_trxl_supported)?  ``A``: the number of actions, or the branch sizes
+    of a MultiDiscrete policy (etm_rollout_trxl_supported_branched)."""
+    lib = _lib.load()
+    sizes = _branch_sizes(A)
+    if sizes is None:
+        return bool(lib.etm_rollout_trxl_supported(D, H, L, hid, A if isinstance(A, int) else int(tuple(A)[0]), nb))
+    tab, nbr = _branch_table(sizes)
+    return bool(lib.etm_rollout_trxl_supported_branched(D, H, L, hid, tab, nbr, nb))
 
 
 def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head, uniforms, forced, t_dev, actions, st_actions, st_logp,
-                 st_values, scratch, host_actions=None, host_flag=None, w_off=0, tail=None, h_bias=None, window=None):
+                 st_values, scratch, host_actions=None, host_flag=None, w_off=0, tail=None, h_bias=None, window=None, branches=None):
     """Transformer + hidden / output heads + sampling of one rollout step of a worker group in one launch (etm_rollout_trxl).
     ``fused``: the transposed fixed-address weight copies of ``ActorCriticModel.refresh_rollout_weights`` (dict with the host
     pointer table ``blocks``); ``kv`` the group's K | V cache [W, T, blocks, 2D]; ``scratch`` from ``rollout_trxl_scratch``; the
@@ -800,7 +851,8 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
     the launch does the step's window lookup (and the cache reset of workers at episode step 0) itself -- no ``rollout_window``
     in front of it.  ``tail`` = (wkv [blocks, D, 2D], pos [T, D] or None, step_l [W], slot_l [W],
     bank [slots, T, blocks, D]): after the action hand-over the same launch writes the new memory items into
-    ``bank[slot_l, step_l]`` and their K | V projection into ``kv[w, step_l]``."""
+    ``bank[slot_l, step_l]`` and their K | V projection into ``kv[w, step_l]``.  ``branches`` (optional, MultiDiscrete): as in
+    ``rollout_policy`` (etm_rollout_trxl_branched / etm_rollout_trxl_group_branched)."""
     lib = _lib.load()
     h_in = _f32c(h_in, "h_in")
     h_splits = 0
@@ -831,19 +883,30 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
     if sync is None:
         sync = _policy_sync[t_dev.data_ptr()] = torch.zeros(1, dtype=torch.int32, device=h_in.device)
     stage_w = st_values.shape[1]
-    off = lambda t: None if t is None else t.data_ptr() + w_off * t.element_size()
+    sizes = _branch_sizes(branches)
+    nb_ = 1 if sizes is None else len(sizes)
+    off = lambda t: None if t is None else t.data_ptr() + w_off * nb_ * t.element_size()
     ha = 0 if host_actions is None else host_actions.data_ptr()
     hf = 0 if host_flag is None else host_flag.data_ptr()
+    args = (_ptr(h_in), _ptr(fused["emb_t"]), _ptr(fused["emb_b"]), fused["blocks"], fused["nb"], _ptr(kv), kv.stride(0),
+            kv.stride(1), _ptr(win_t), _ptr(mask_t), _ptr(items), _ptr(fused["heads_t"]), _ptr(fused["heads_b"]),
+            _ptr(policy_head.weight), _ptr(policy_head.bias), _ptr(value_head.weight), _ptr(value_head.bias),
+            off(uniforms), off(forced), _ptr(t_dev), _ptr(actions), off(st_actions), off(st_logp),
+            st_values.data_ptr() + w_off * st_values.element_size(), ha, hf, _ptr(sync), float(fused["eps"]), _ptr(scratch),
+            scratch.numel() * 8, *t_args, 0 if h_bias is None else _ptr(h_bias), h_splits, *w_args, int(fused.get("pre_ln", 0)),
+            int(fused.get("gtrxl", 0)), W, D, fused["H"], L, hid)
     # ``fused`` with the group packings (ActorCriticModel._rfg, "group": True) selects the group form of the kernel: same arguments
-    entry, name = (lib.etm_rollout_trxl_group, "etm_rollout_trxl_group") if fused.get("group") else (lib.etm_rollout_trxl, "etm_rollout_trxl")
-    _lib.check(entry(_ptr(h_in), _ptr(fused["emb_t"]), _ptr(fused["emb_b"]), fused["blocks"], fused["nb"], _ptr(kv), kv.stride(0),
-                                    kv.stride(1), _ptr(win_t), _ptr(mask_t), _ptr(items), _ptr(fused["heads_t"]), _ptr(fused["heads_b"]),
-                                    _ptr(policy_head.weight), _ptr(policy_head.bias), _ptr(value_head.weight), _ptr(value_head.bias),
-                                    off(uniforms), off(forced), _ptr(t_dev), _ptr(actions), off(st_actions), off(st_logp), off(st_values),
-                                    ha, hf, _ptr(sync), float(fused["eps"]), _ptr(scratch), scratch.numel() * 8, *t_args,
-                                    0 if h_bias is None else _ptr(h_bias), h_splits, *w_args, int(fused.get("pre_ln", 0)),
-                                    int(fused.get("gtrxl", 0)), W, D, fused["H"], L, hid, A, stage_w, _stream()),
-               name)
+    group = bool(fused.get("group"))
+    if sizes is None:
+        entry, name = (lib.etm_rollout_trxl_group, "etm_rollout_trxl_group") if group else (lib.etm_rollout_trxl, "etm_rollout_trxl")
+        _lib.check(entry(*args, A, stage_w, _stream()), name)
+        return
+    if sum(sizes) != A:
+        raise ValueError(f"rollout_trxl: branches {sizes} do not add up to the {A} rows of the policy head")
+    tab, nbr = _branch_table(sizes)
+    entry, name = ((lib.etm_rollout_trxl_group_branched, "etm_rollout_trxl_group_branched") if group
+                   else (lib.etm_rollout_trxl_branched, "etm_rollout_trxl_branched"))
+    _lib.check(entry(*args, stage_w, tab, nbr, _stream()), name)
 
 
 def gather_rows(fields, idx):
@@ -1720,7 +1783,8 @@ class _HeadsLossFn(torch.autograd.Function):
     ``g_loss``."""
 
     @staticmethod
-    def forward(ctx, h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn, unit_grad):
+    def forward(ctx, h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn, unit_grad,
+                sizes=None):
         lib = _lib.load()
         _need_dev(h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3)
         h = _f32c(h, "h")
@@ -1735,10 +1799,17 @@ class _HeadsLossFn(torch.autograd.Function):
         ws = workspace(nbytes, dev, "heads_loss")
         actions, old_logp = actions.contiguous(), old_logp.contiguous()
         B = actions.shape[1] if actions.dim() == 2 else 1
-        rc = lib.etm_heads_loss(_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv), _ptr(actions), B,
-                                _ptr(old_logp), B, _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
-                                float(vf_coef), float(beta), 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8),
-                                0, 0, _ptr(ws), nbytes, N, hid, A, _stream())
+        common = (_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv), _ptr(actions), B,
+                  _ptr(old_logp), B, _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
+                  float(vf_coef), float(beta))
+        if sizes is None:
+            rc = lib.etm_heads_loss(*common, 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8),
+                                    0, 0, _ptr(ws), nbytes, N, hid, A, _stream())
+        else:
+            # MultiDiscrete: wb / bb are the branches' heads concatenated; policy term, KL and clip fraction are means over N B
+            tab, nbr = _branch_table(sizes)
+            rc = lib.etm_heads_loss_branched(*common, 1.0 / (N * nbr), 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums),
+                                             _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, tab, nbr, _stream())
         _lib.check(rc, "etm_heads_loss")
         ctx.save_for_backward(h, wlp, wlv, gm_p, gm_v, sums)
         ctx.dims = (hid, A)
@@ -1750,7 +1821,7 @@ class _HeadsLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_stats):
         if g_loss is None:
-            return (None,) * 19
+            return (None,) * 20
         h, wlp, wlv, gm_p, gm_v, sums = ctx.saved_tensors
         hid, A = ctx.dims
         unit = ctx.unit                 # the caller promises loss.backward() on the returned loss itself: g_loss == 1, nothing to scale
@@ -1768,26 +1839,46 @@ class _HeadsLossFn(torch.autograd.Function):
         s = sums if unit else sums * g_loss
         o = (3 + A) * hid
         return (dh, dwlp, s[:hid], dwlv, s[hid:2 * hid], s[3 * hid:o].view(A, hid), s[o:o + A], s[2 * hid:3 * hid].view(1, hid),
-                s[o + A:o + A + 1], None, None, None, None, None, None, None, None, None, None)
+                s[o + A:o + A + 1], None, None, None, None, None, None, None, None, None, None, None)
+
+
+def _branch_list(branch):
+    return list(branch) if isinstance(branch, (list, tuple, torch.nn.ModuleList)) else [branch]
 
 
 def heads_loss_supported(h, lin_policy, branch):
-    return (h.is_cuda and h.dim() == 2 and h.dtype == torch.float32
-            and bool(_lib.load().etm_heads_loss_supported(h.shape[0], lin_policy.weight.shape[0], branch.weight.shape[0])))
+    """Does ``heads_ppo_loss`` take this minibatch?  ``branch``: the policy branch, or the list of branches of a MultiDiscrete
+    policy (etm_heads_loss_supported_branched)."""
+    if not (h.is_cuda and h.dim() == 2 and h.dtype == torch.float32):
+        return False
+    lib = _lib.load()
+    br = _branch_list(branch)
+    if len(br) == 1:
+        return bool(lib.etm_heads_loss_supported(h.shape[0], lin_policy.weight.shape[0], br[0].weight.shape[0]))
+    tab, nbr = _branch_table([b.weight.shape[0] for b in br])
+    return bool(lib.etm_heads_loss_supported_branched(h.shape[0], lin_policy.weight.shape[0], tab, nbr))
 
 
 def heads_ppo_loss(h, lin_policy, lin_value, branch, value_head, actions, old_logp, adv, old_value, clip, vf_coef, beta, stats3=None, dyn=None,
                    unit_grad=False):
-    """model.py:101-110 + the PPO loss of ``ppo_loss`` for a single-branch policy, from the transformer output ``h`` [N, D]:
-    -> (loss scalar with grad, stats[6]).  ``unit_grad=True``: the caller runs ``backward()`` on the returned loss itself (upstream
-    gradient 1): no scaling launches, weight gradients of the hidden heads deferrable.  See _HeadsLossFn."""
+    """model.py:101-110 + the PPO loss of ``ppo_loss``, from the transformer output ``h`` [N, D]: -> (loss scalar with grad, stats[6]).
+    ``branch``: the policy branch, or the list of branches of a MultiDiscrete policy (``actions`` / ``old_logp`` [N, B]; the semantics of
+    ``ppo_loss`` over branches).  ``unit_grad=True``: the caller runs ``backward()`` on the returned loss itself (upstream gradient 1):
+    no scaling launches, weight gradients of the hidden heads deferrable.  See _HeadsLossFn."""
     if stats3 is None:
         stats3 = adv_stats(adv)
     if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
         raise TypeError("heads_ppo_loss: dyn must be a float64 device tensor (clip, beta)")
-    loss, st = _HeadsLossFn.apply(h, lin_policy.weight, lin_policy.bias, lin_value.weight, lin_value.bias, branch.weight, branch.bias,
+    br = _branch_list(branch)
+    if len(br) == 1:
+        wb, bb, sizes = br[0].weight, br[0].bias, None
+    else:
+        # the kernel reads the branches' heads as one [sum A_b, hid] matrix; autograd hands each branch its rows of the gradient
+        wb, bb = torch.cat([b.weight for b in br], dim=0), torch.cat([b.bias for b in br], dim=0)
+        sizes = tuple(int(b.weight.shape[0]) for b in br)
+    loss, st = _HeadsLossFn.apply(h, lin_policy.weight, lin_policy.bias, lin_value.weight, lin_value.bias, wb, bb,
                                   value_head.weight, value_head.bias, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn,
-                                  unit_grad)
+                                  unit_grad, sizes)
     return loss, st[:6]
 
 

@@ -66,6 +66,7 @@ class ActorCriticModel(nn.Module):
         nn.init.orthogonal_(self.lin_policy.weight, math.sqrt(2))
         self.lin_value = nn.Linear(self.memory_layer_size, self.hidden_size)
         nn.init.orthogonal_(self.lin_value.weight, math.sqrt(2))
+        self.action_space_shape = tuple(int(a) for a in action_space_shape)   # one entry per action branch (MultiDiscrete: nvec)
         self.policy_branches = nn.ModuleList()
         for num_actions in action_space_shape:
             branch = nn.Linear(in_features=self.hidden_size, out_features=num_actions)
@@ -118,6 +119,18 @@ class ActorCriticModel(nn.Module):
             else:
                 self._w_heads.copy_(w)
                 self._b_heads.copy_(b)
+            if len(self.policy_branches) > 1:
+                # MultiDiscrete: the branches' heads concatenated [sum A_b, hid] -- the one policy head the rollout kernels read
+                # (branch b owns rows [off_b, off_b + A_b)); fixed address, like the copies above
+                wp = torch.cat([br.weight for br in self.policy_branches], dim=0)
+                bp = torch.cat([br.bias for br in self.policy_branches], dim=0)
+                cat = getattr(self, "_policy_cat", None)
+                if cat is None or cat.weight.device != wp.device:
+                    self._policy_cat = type("PolicyHeads", (), {})()
+                    self._policy_cat.weight, self._policy_cat.bias = wp.contiguous(), bp.contiguous()
+                else:
+                    cat.weight.copy_(wp)
+                    cat.bias.copy_(bp)
         self._refresh_fused_block_weights()
         if not self.visual:
             return
@@ -140,17 +153,25 @@ class ActorCriticModel(nn.Module):
                 self._w3k.copy_(w3k)
             self._wver = (self.conv1.weight._version, self.conv2.weight._version, self.conv3.weight._version)
 
+    def rollout_policy_head(self):
+        """The policy head the rollout kernels read: the branch itself for one branch, else the concatenated fixed-address copy of
+        all branches (built by ``refresh_rollout_weights``)."""
+        return self.policy_branches[0] if len(self.policy_branches) == 1 else getattr(self, "_policy_cat", None)
+
     def rollout_block_fusable(self):
-        """Post-LN blocks without gates, one action branch, shapes inside etm_rollout_trxl's support: the trainer may run the
-        transformer, the heads and the sampling of a rollout step as one kernel."""
+        """Post- or pre-LN blocks, shapes inside etm_rollout_trxl's support (the branches' actions together): the trainer may run
+        the transformer, the heads and the sampling of a rollout step as one kernel."""
         t = self.transformer
         blk = t.transformer_blocks[0]
         d = t.embed_dim
-        if not (self.fused_rollout_block and blk.layer_norm in ("post", "pre") and len(self.policy_branches) == 1
-                and t.linear_embedding.in_features == d):
+        if not (self.fused_rollout_block and blk.layer_norm in ("post", "pre") and t.linear_embedding.in_features == d):
             return False
         return ops.rollout_trxl_supported(d, t.num_heads, t.config["memory_length"], self.hidden_size,
-                                          self.policy_branches[0].out_features, t.num_blocks)
+                                          self._rollout_actions(), t.num_blocks)
+
+    def _rollout_actions(self):
+        """Number of actions (one branch) or the branch sizes (MultiDiscrete): what the kernels' predicates take."""
+        return self.policy_branches[0].out_features if len(self.policy_branches) == 1 else self.action_space_shape
 
     def _refresh_fused_block_weights(self):
         """Transposed ([in, out]) fixed-address copies of the matrices etm_rollout_trxl walks, and the host table of their
@@ -220,7 +241,7 @@ class ActorCriticModel(nn.Module):
         blk0 = t.transformer_blocks[0]
         d = t.embed_dim
         lib = etm_lib.load()
-        A = self.policy_branches[0].out_features
+        A = sum(self.action_space_shape)
         # (the kernel's [W, D] input rows and its D x D embedding slice assume linear_embedding.in_features == embed_dim)
         if not (self.rollout_group_kernel and self._rf is not None and blk0.use_gtrxl and t.linear_embedding.in_features == d
                 and lib.etm_rollout_trxl_group_supported(d, t.num_heads, t.config["memory_length"], self.hidden_size, A, t.num_blocks, 1, 1)
@@ -355,9 +376,10 @@ class ActorCriticModel(nn.Module):
         return [branch(h_policy) for branch in self.policy_branches], value, memory
 
     def rollout_heads_fusable(self):
-        """Single-branch policy with the concatenated hidden heads built: the trainer may run output heads + sampling as one
-        kernel on ``forward_hidden_cached``'s result."""
-        return len(self.policy_branches) == 1 and getattr(self, "_w_heads", None) is not None and not torch.is_grad_enabled()
+        """Concatenated hidden heads (and, with several branches, policy heads) built: the trainer may run output heads + sampling
+        as one kernel on ``forward_hidden_cached``'s result."""
+        return (getattr(self, "_w_heads", None) is not None and self.rollout_policy_head() is not None
+                and not torch.is_grad_enabled())
 
     def forward_hidden_cached(self, obs, kv_spec: WindowSpec, items_out=None, obs_index=None, raw=False, obs_rows=None):
         """Rollout path up to the hidden heads: -> (h2 [N, 2*hidden] = [relu(lin_policy(h)) | relu(lin_value(h))], memory).
@@ -372,11 +394,14 @@ class ActorCriticModel(nn.Module):
         """Rollout path (no grad): like ``forward_logits`` but attention reads the per-worker K/V cache.  With ``items_out``
         [blocks, N, D] the new memory items are written there (block-major) and returned in that layout."""
         h, memory = self.transformer.forward_cached(self._encode(obs, obs_index, obs_rows), kv_spec, items_out)
-        if len(self.policy_branches) == 1 and getattr(self, "_w_heads", None) is not None and not torch.is_grad_enabled():
-            # [lin_policy ; lin_value] as ONE GEMM (+ReLU epilogue), then both output heads in one small kernel
+        if self.rollout_heads_fusable():
+            # [lin_policy ; lin_value] as ONE GEMM (+ReLU epilogue), then both output heads in one small kernel (several branches:
+            # the concatenated policy heads, the logits split into the branches' column views)
             h2 = ops.linear_relu(self._heads_lin, h)
-            logits, value = ops.rollout_heads(h2, self.policy_branches[0], self.value)
-            return [logits], value, memory
+            logits, value = ops.rollout_heads(h2, self.rollout_policy_head(), self.value)
+            if len(self.policy_branches) == 1:
+                return [logits], value, memory
+            return list(logits.split(list(self.action_space_shape), dim=1)), value, memory
         h_policy = ops.linear_relu(self.lin_policy, h)
         h_value = ops.linear_relu(self.lin_value, h)
         value = self.value(h_value).reshape(-1)

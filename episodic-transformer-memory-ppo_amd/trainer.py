@@ -185,7 +185,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         W = self.num_workers
         obs_shape = tuple(self.env.observation_space_shape)
         self.observation_space = type("Space", (), {"shape": obs_shape})()
-        self.action_space_shape = (self.env.num_actions,)  # one branch, like upstream (trainer.py:47)
+        # one branch per action dimension, from the environment (environments.action_space_shape: Discrete(n) -> (n,), MultiDiscrete
+        # -> nvec); Discrete is upstream's single branch (trainer.py:47)
+        self.action_space_shape = tuple(int(a) for a in getattr(self.env, "action_space_shape", None) or (self.env.num_actions,))
         self.max_episode_length = self.env.max_episode_steps
 
         if config.get("tunable_gemm", os.environ.get("ETM_TUNABLE_GEMM", "1") != "0"):
@@ -274,10 +276,11 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         self._mask_t = torch.zeros((W, L), dtype=torch.bool, device=device)
         self._win_t = torch.zeros((W, L), dtype=torch.int64, device=device)
         self._act_dev = torch.zeros((W, B), dtype=torch.int64, device=device)
-        self._uniforms = torch.zeros((S, W), dtype=torch.float32, device=device)
-        # teacher forcing (parity tests): a non-negative entry replaces the sampled action of that (step, worker); the table has
-        # a fixed address, so the captured step graphs read it too -- every rollout path can be driven with recorded actions
-        self._forced_tab = torch.full((S, W), -1, dtype=torch.int64, device=device)
+        # one uniform per (step, worker, branch); a single branch keeps the [S, W] draw (the same bits as ever)
+        self._uniforms = torch.zeros((S, W) if B == 1 else (S, W, B), dtype=torch.float32, device=device)
+        # teacher forcing (parity tests): a non-negative entry replaces the sampled action of that (step, worker, branch); the table
+        # has a fixed address, so the captured step graphs read it too -- every rollout path can be driven with recorded actions
+        self._forced_tab = torch.full((S, W) if B == 1 else (S, W, B), -1, dtype=torch.int64, device=device)
         self._step_graph = None
         self._act_ready = torch.cuda.Event()
         # observation streaming (graph rollout with the fused encoder): rows of the next observation go from pinned memory
@@ -408,12 +411,12 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         streamed from pinned memory into row t+1 of the staging array on a second stream while the environments still step
         (``stream_observations``), together with the workers' (episode step, slot) vector; the actions arrive in pinned host
         memory straight from the sampling kernel.
-        ``forced_actions`` [W, S] (optional) replays recorded actions instead of sampling (teacher forcing for parity
+        ``forced_actions`` [W, S] or [W, S, B] (optional) replays recorded actions instead of sampling (teacher forcing for parity
         tests -- CPU and GPU RNG streams differ) on whichever path the config selects: the sampling
         kernels read them from a fixed-address table, so the captured graphs, the observation streaming and the worker-group
         pipeline run exactly as they do when sampling.
-        ``uniforms`` [W, S] (optional, tests) replaces the rollout's uniform draws: every sampling kernel inverts its CDF at
-        exactly these values."""
+        ``uniforms`` [W, S] or [W, S, B] (optional, tests) replaces the rollout's uniform draws: every sampling kernel inverts its CDF at
+        exactly these values (branch b of a MultiDiscrete policy at its own draw)."""
         buf, W, S = self.buffer, self.num_workers, self.config["worker_steps"]
         main = torch.cuda.current_stream(self.device)
         use_graph = bool(self.config.get("hip_graph_rollout", True))
@@ -424,16 +427,19 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         if self._use_kv_cache:
             self._refresh_kv_cache()
         self.model.refresh_rollout_weights()       # encoder weight copies for the fused rollout convolutions
+        B = len(self.action_space_shape)
         if forced_actions is not None:
-            fa = torch.as_tensor(np.asarray(forced_actions), dtype=torch.int64).reshape(W, S)
-            self._forced_tab.copy_(fa.t().to(self.device))
+            fa = torch.as_tensor(np.asarray(forced_actions), dtype=torch.int64)
+            fa = fa.reshape(W, S).t() if B == 1 else fa.reshape(W, S, B).transpose(0, 1)
+            self._forced_tab.copy_(fa.to(self.device))
         groups = self._groups if use_graph else [self._group_all]
         if use_graph and groups[0].graphs is None:
             self._capture_step_graph(groups)
         if uniforms is not None:
-            self._uniforms.copy_(torch.as_tensor(np.asarray(uniforms), dtype=torch.float32).reshape(W, S).t())
+            u = torch.as_tensor(np.asarray(uniforms), dtype=torch.float32)
+            self._uniforms.copy_(u.reshape(W, S).t() if B == 1 else u.reshape(W, S, B).transpose(0, 1))
         else:
-            self._uniforms.uniform_()            # one draw per (step, worker) for the whole rollout
+            self._uniforms.uniform_()            # one draw per (step, worker, branch) for the whole rollout
         for g in groups:
             g.t_dev.zero_()
             g.flag_np[0] = 0
@@ -652,7 +658,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             g.obs_dev.copy_(g.obs_pin, non_blocking=True)
             obs, obs_index, rows = g.obs_dev, None, None
             g.ss_dev.copy_(g.ss_pin, non_blocking=True)      # (streamed mode: uploaded with the observation rows)
-        single = len(self.action_space_shape) == 1
+        branches = self.action_space_shape       # (one entry: Discrete; the kernels then take their single-branch entries)
+        policy_head = self.model.rollout_policy_head()
         mask_t, win_t = g.mask_t, g.win_t
         # window lookup + staging; the same launch records the staging row of this step for the tail (t_dev is incremented by
         # the sampling kernel) and resets the K/V cache of workers at episode step 0 (they start from the projection of an
@@ -667,10 +674,10 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         # round 5: GRU-gated layouts in groups of <= 8 workers take the GROUP form of the step kernel (weights once per group and
         # step, 32 workgroups per launch; csrc/rollout_group.hip)
         rfg_ = getattr(self.model, "_rfg", None) if rf_ is not None else None
-        g.group_kernel = bool(single and rfg_ is not None and self.config.get("rollout_group_kernel", True)
-                              and ops.rollout_trxl_group_ok(rfg_, g.W, self.memory_length, self.model.hidden_size, self.action_space_shape[0])
+        g.group_kernel = bool(rfg_ is not None and self.config.get("rollout_group_kernel", True)
+                              and ops.rollout_trxl_group_ok(rfg_, g.W, self.memory_length, self.model.hidden_size, self.model._rollout_actions())
                               and n_conc * etm_lib.load().etm_rollout_trxl_group_grid() <= 256)
-        fused_step = (single and rf_ is not None and self.model.rollout_heads_fusable()
+        fused_step = (rf_ is not None and self.model.rollout_heads_fusable()
                       and (g.group_kernel or n_conc * etm_lib.load().etm_rollout_trxl_grid(g.W, rf_["H"]) <= 256))
         # the fused step kernel does the window lookup (and the cache reset of new episodes) itself: one launch fewer in the chain
         if not fused_step:
@@ -720,25 +727,25 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                 if self.config.get("fused_rollout_tail", True) and getattr(self, "_kv_w_blocked", None) is not None:   # (pre-LN: the kernel applies norm_kv)
                     tail = (self._kv_w_blocked, self.model.transformer._pos(), g.step_l, g.slot_l, buf.bank)
                 g.tail_in_kernel = tail is not None
-                ops.rollout_trxl(h_in, rf, g.kv, win_t, mask_t, g.item, self.model.policy_branches[0], self.model.value,
+                ops.rollout_trxl(h_in, rf, g.kv, win_t, mask_t, g.item, policy_head, self.model.value,
                                  self._uniforms, self._forced_tab, g.t_dev, g.act_dev, st["actions"], st["log_probs"], st["values"],
                                  g.rf_scratch, host_actions=g.act_pin, host_flag=g.flag_pin if host_flag else None, w_off=g.lo,
-                                 tail=tail, h_bias=h_bias,
+                                 tail=tail, h_bias=h_bias, branches=branches,
                                  window=(ss_src, self._mask_table, self._index_table, st["memory_mask"], st["memory_indices"],
                                          g.ss_latch, g.t_row, self._kv_init))
                 item = g.item
                 fused_policy = True
-            elif single and self.model.rollout_heads_fusable():
+            elif self.model.rollout_heads_fusable():
                 # hidden heads -> ONE launch for output heads, sampling, staging, t += 1; the kernel stores the actions straight
                 # into the pinned host buffer (no copy launch): they are visible to the host when the step's event (or, with
                 # host_flag_actions, the flag) says the launch is done
                 h2, item = self.model.forward_hidden_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, raw=True,
                                                             obs_rows=rows)
                 flag = host_flag
-                ops.rollout_policy(h2, self.model.policy_branches[0], self.model.value, self._uniforms, self._forced_tab, g.t_dev,
+                ops.rollout_policy(h2, policy_head, self.model.value, self._uniforms, self._forced_tab, g.t_dev,
                                    g.act_dev, st["actions"], st["log_probs"], st["values"],
                                    host_actions=g.act_pin, host_flag=g.flag_pin if flag else None,
-                                   h_bias=self.model._b_heads, w_off=g.lo)
+                                   h_bias=self.model._b_heads, w_off=g.lo, branches=branches)
                 fused_policy = True
             else:
                 logits, value, item = self.model.forward_logits_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index,
@@ -751,28 +758,13 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             pass
         else:
             if not g.full:
-                raise RuntimeError("worker groups need the fused policy path (single-branch policy, K/V cache)")
-            if single:
-                # log-softmax + categorical sample (inverse CDF on pre-drawn uniforms) + log-prob + staging + t += 1: one launch
-                ops.rollout_sample(logits[0], value, self._uniforms, self._forced_tab, g.t_dev, g.act_dev,
-                                   st["actions"], st["log_probs"], st["values"])
-                g.act_pin.copy_(g.act_dev, non_blocking=True)
-            else:
-                row = g.t_row.view(1)
-                acts, logps = [], []
-                forced_t = self._forced_tab.index_select(0, row)[0]       # one recorded action per worker, shared by the branches
-                for lg in logits:
-                    lsm = torch.log_softmax(lg, dim=-1)
-                    a = torch.multinomial(lsm.exp(), 1).squeeze(1)
-                    a = torch.where(forced_t >= 0, forced_t, a)
-                    acts.append(a)
-                    logps.append(lsm.gather(1, a.unsqueeze(1)).squeeze(1))
-                g.act_dev.copy_(torch.stack(acts, dim=1))
-                st["actions"].index_copy_(0, row, g.act_dev.unsqueeze(0))
-                st["log_probs"].index_copy_(0, row, torch.stack(logps, dim=1).unsqueeze(0))
-                st["values"].index_copy_(0, row, value.unsqueeze(0))
-                g.t_dev.add_(1)
-                g.act_pin.copy_(g.act_dev, non_blocking=True)
+                raise RuntimeError("worker groups need the fused policy path (K/V cache)")
+            # log-softmax + categorical sample (inverse CDF on pre-drawn uniforms) + log-prob + staging + t += 1, per action branch:
+            # one launch (several branches: their logits side by side)
+            lg = logits[0] if len(logits) == 1 else torch.cat(logits, dim=1)
+            ops.rollout_sample(lg, value, self._uniforms, self._forced_tab, g.t_dev, g.act_dev,
+                               st["actions"], st["log_probs"], st["values"], branches=branches)
+            g.act_pin.copy_(g.act_dev, non_blocking=True)
         if item.data_ptr() != g.item.data_ptr():
             g.item.copy_(item)
         return g.item
@@ -845,13 +837,13 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         with torch.no_grad():
             self._stream_obs = bool(self.config.get("stream_observations", True) and self._use_kv_cache
                                     and self.model._fused_encoder_ok(self._obs_dev))
-            fusable = self._use_kv_cache and len(self.action_space_shape) == 1 and self.model.rollout_heads_fusable()
+            fusable = self._use_kv_cache and self.model.rollout_heads_fusable()
             # host_flag_actions (default on): the sampling kernel stores the actions and then the step counter into pinned memory
             # and the host spins on the counter -- no event between the action hand-over and the rest of the step, so a step of a
             # group is ONE captured graph (one launch) instead of head + event + tail (measured: 287 -> 279 us per step)
             self._host_flag = bool(self.config.get("host_flag_actions", True) and fusable)
         if len(groups) > 1 and not fusable:
-            raise RuntimeError("rollout_groups > 1 needs a single-branch policy and the K/V cache (set rollout_groups: 1)")
+            raise RuntimeError("rollout_groups > 1 needs the K/V cache (set rollout_groups: 1)")
         so, hf = self._stream_obs, self._host_flag
         # native rollout driver (worker_processes): needs the flag hand-over, streamed observations on the groups' own streams and
         # the (step, slot) block read in place -- then the sampling kernels write the step's sequence number into the SEGMENT's go
@@ -1038,19 +1030,21 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         return stats
 
     def _loss_from(self, obs, spec, mb, clip_range, beta, stats3, dyn="device"):
-        """Model forward + PPO loss of one minibatch (trainer.py:268-304): -> (loss, stats[6]).  Single-branch policies whose hidden size
-        fits take the fused hidden-heads + loss kernel (``fused_heads_loss``, default on); others the separate heads and loss."""
+        """Model forward + PPO loss of one minibatch (trainer.py:268-304): -> (loss, stats[6]).  Policies whose hidden size and actions
+        fit (every branch of a MultiDiscrete policy together) take the fused hidden-heads + loss kernel (``fused_heads_loss``, default
+        on); others the separate heads and the per-branch loss."""
         dyn = getattr(self, "_dyn", None) if dyn == "device" else dyn
         m = self.model
-        if self.config.get("fused_heads_loss", True) and len(m.policy_branches) == 1:
+        if self.config.get("fused_heads_loss", True):
             h, _ = m.forward_state(obs, spec)
-            if ops.heads_loss_supported(h, m.lin_policy, m.policy_branches[0]):
-                return ops.heads_ppo_loss(h, m.lin_policy, m.lin_value, m.policy_branches[0], m.value, mb["actions"], mb["log_probs"],
+            branch = m.policy_branches[0] if len(m.policy_branches) == 1 else list(m.policy_branches)
+            if ops.heads_loss_supported(h, m.lin_policy, branch):
+                return ops.heads_ppo_loss(h, m.lin_policy, m.lin_value, branch, m.value, mb["actions"], mb["log_probs"],
                                           mb["advantages"], mb["values"], clip_range, self.config["value_loss_coefficient"], beta, stats3, dyn=dyn,
                                           unit_grad=True)       # (both callers run loss.backward() on this loss)
             h_policy = ops.linear_relu(m.lin_policy, h)
             h_value = ops.linear_relu(m.lin_value, h)
-            logits, value = [m.policy_branches[0](h_policy)], m.value(h_value).reshape(-1)
+            logits, value = [br(h_policy) for br in m.policy_branches], m.value(h_value).reshape(-1)
         else:
             logits, value, _ = m.forward_logits(obs, spec, want_items=False)
         return ops.ppo_loss(logits, value, mb["actions"], mb["log_probs"], mb["advantages"], mb["values"], clip_range,

@@ -222,6 +222,13 @@ int etm_rollout_window(const int64_t *step, const uint8_t *mask_table, const int
                        int W, int L, int stage_W, void *stream);
 int etm_rollout_sample(const float *logits, const float *value, const float *uniforms, const int64_t *forced, int64_t *t_dev,
                        int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W, int A, void *stream);
+/* MultiDiscrete (ABI 48): logits [W, sum sizes] hold the B = n_branches branches' segments side by side (branch b: columns
+ * [off_b, off_b + sizes[b]), sizes = branch_sizes, a HOST array of B <= 16 entries).  Per branch: log-softmax over its own segment, the
+ * inverse CDF of etm_rollout_sample at its own uniform uniforms[*t_dev, w, b] (or forced[*t_dev, w, b] when >= 0); actions [W, B],
+ * st_actions / st_logp [S, W, B], st_values [S, W].  B = 1 is exactly etm_rollout_sample. */
+int etm_rollout_sample_branched(const float *logits, const float *value, const float *uniforms, const int64_t *forced, int64_t *t_dev,
+                                int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W, const int32_t *branch_sizes,
+                                int n_branches, void *stream);
 int etm_add_layernorm(const float *a, const float *a_bias, int relu, const float *b, const float *gamma, const float *beta, float eps,
                       float *out, int N, int D, void *stream);
 /* Elementwise parts of the GTrXL GRU gate on the rollout path (transformer.py:287-298), around concatenated library GEMMs
@@ -302,6 +309,20 @@ int etm_heads_loss(const float *pre_p, const float *pre_v, const float *b_lp, co
                    float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v,
                    float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
                    int A, void *stream);
+/* MultiDiscrete policies (ABI 48): the same pass over B = n_branches action branches of sizes branch_sizes[B] (HOST array).  wb / bb =
+ * the branches' heads concatenated ([sum sizes, hid], [sum sizes]; branch b owns the rows after those of branches < b); actions /
+ * old_logp rows carry one entry per branch (strides >= B).  Per branch: log-softmax over its own logits and a ratio, the sample's
+ * normalised advantage repeated over the branches; the policy term, KL and clip fraction are summed over (sample, branch) and scaled
+ * by pol_scale (1 / (N B) for ref_algo.ppo_loss), the entropy is the sum over the branches (ent_scale 1 / N).  The sums row is laid
+ * out as in etm_heads_loss with A = sum sizes (d Wb / d bb: the concatenated heads).  Shapes: etm_heads_loss_supported_branched
+ * (sum sizes <= 8, B <= 8, hid as etm_heads_loss). */
+int etm_heads_loss_supported_branched(int N, int hid, const int32_t *branch_sizes, int n_branches);
+int etm_heads_loss_branched(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb, const float *bb,
+                            const float *wv, const float *bv, const int64_t *actions, int64_t action_stride, const float *old_logp,
+                            int64_t logp_stride, const float *adv, const float *old_value, const float *adv_stats3, double clip, float vf_coef,
+                            float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p,
+                            float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes,
+                            int N, int hid, const int32_t *branch_sizes, int n_branches, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Weight gradients of the dense layers of one optimisation step as ONE grouped launch: replaces the `dW = dy^T x` products that
@@ -353,6 +374,12 @@ int etm_rollout_policy(const float *h, const float *h_bias, const float *wp, con
                        const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
                        float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
                        int W, int A, int hid, int stage_W, void *stream);
+/* MultiDiscrete (ABI 48): wp / bp = the branches' heads concatenated ([sum sizes, hid], [sum sizes]); sampling per branch as in
+ * etm_rollout_sample_branched; uniforms / forced / st_actions / st_logp [S, stage_W, B], actions / host_actions [W, B]. */
+int etm_rollout_policy_branched(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv, const float *bv,
+                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
+                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
+                                int W, int hid, int stage_W, const int32_t *branch_sizes, int n_branches, void *stream);
 
 /* The transformer, the hidden / output heads and the sampling of one rollout step of a worker group as ONE launch (post-LN
  * blocks without gates; trainer.py:163-186 -> model.py:96-112 -> transformer.py:222-253), csrc/rollout_fused.hip: a TEAM of
@@ -432,6 +459,36 @@ int etm_rollout_trxl_group(const float *h_in, const float *wemb_t, const float *
                      const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
                      int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
                      int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W, void *stream);
+/* MultiDiscrete forms of the two step kernels (ABI 48): the arguments of etm_rollout_trxl / etm_rollout_trxl_group with A replaced by
+ * the branch table (branch_sizes: HOST array, n_branches <= 16); wp / bp = the branches' heads concatenated; sampling per branch as in
+ * etm_rollout_sample_branched (uniforms / forced / st_actions / st_logp [S, stage_W, B], actions / host_actions [W, B]).  Shapes: the
+ * predicates below = the single-branch ones at A = sum sizes (per-worker kernel: sum sizes + 1 <= 64; group kernel: 8 (sum sizes + 1) + 1
+ * <= 128, the floats of one exchange piece, i.e. sum sizes <= 14). */
+int etm_rollout_trxl_supported_branched(int D, int H, int L, int hid, const int32_t *branch_sizes, int n_branches, int nb);
+int etm_rollout_trxl_group_supported_branched(int D, int H, int L, int hid, const int32_t *branch_sizes, int n_branches, int nb, int W,
+                                              int gtrxl);
+int etm_rollout_trxl_branched(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
+                              int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
+                              const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
+                              const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
+                              float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter, float ln_eps,
+                              void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
+                              const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride,
+                              const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table,
+                              uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,
+                              const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int stage_W,
+                              const int32_t *branch_sizes, int n_branches, void *stream);
+int etm_rollout_trxl_group_branched(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
+                                    int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
+                                    const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
+                                    const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
+                                    float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
+                                    float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
+                                    const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride,
+                                    int64_t bank_block_stride, const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table,
+                                    const int64_t *index_table, uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row,
+                                    uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H,
+                                    int L, int hid, int stage_W, const int32_t *branch_sizes, int n_branches, void *stream);
 /* Window pass (etm_window_*): 0 = load and multiply the window rows of fully masked waves too (A/B diagnostics; the results are
  * bit-identical either way); default 1 = skip them.  Process-wide, read at launch. */
 int etm_window_set_skip_masked(int on);
