@@ -3,6 +3,8 @@
 PyTorch is plumbing here: it owns the device buffers and the stream; the math of the three hot ops runs in the
 hand-written kernels.  Every entry point requires HIP device tensors and raises otherwise -- no CPU/eager fallback.
 """
+import ctypes
+
 import torch
 
 from . import lib as _lib
@@ -287,7 +289,7 @@ class _WindowFn(torch.autograd.Function):
         want_ln = ctx.has_ln and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
         want_pos = ctx.has_pos and ctx.needs_input_grad[3]
         d_ln_g = d_ln_b = d_pos = None
-        if _ln_grad_kernel and want_ln and not want_pos and D % 128 == 0 and D <= 512 and H <= 8 and L <= 128:
+        if _ln_grad_kernel_route(D, H, L, want_ln, want_pos):
             # norm_kv's gain / bias gradients as per-workgroup partial rows (csrc/window_ln_grad.hip), summed by the grouped column-sum
             # reduction of the step, or -- without a collector / once it is full -- by the same kernel launched here.  NOT by torch's
             # column sum: its two-stage reduction (a memset node for its semaphore + the reduce kernel) returns wrong sums in some
@@ -310,12 +312,9 @@ class _WindowFn(torch.autograd.Function):
                                                     _ptr(pidx), _ptr(pos), _ptr(ln_stats), _ptr(att), _ptr(d_e), _ptr(u), _ptr(gz), N * D, D,
                                                     _ptr(ln_g), _ptr(ln_b), LN_GRAD_GUARD_TAU, _ptr(partial), N, L, D, H, _stream())
                 _lib.check(rc, "etm_window_ln_grad_guarded")
-            col = DeferredDw.active
-            params = getattr(ctx, "ln_params", None)
-            if col is not None and params is not None and col.offer_colsum(partial, rows, 2 * D, [(0, D, params[0].data_ptr()), (D, D, params[1].data_ptr())]):
-                return du, None, None, None, None, None, None
-            sums = colsum_rows(partial, rows, 2 * D)
-            return du, sums[:D], sums[D:], None, None, None, None
+            g_param, b_param = ctx.ln_params
+            d_ln_g, d_ln_b = DeferredDw.reduce_colsums(partial, rows, 2 * D, [(0, D, g_param.data_ptr()), (D, D, b_param.data_ptr())])
+            return du, d_ln_g, d_ln_b, None, None, None, None
         if want_ln or want_pos:
             d_ln_g = torch.zeros_like(ln_g) if want_ln else None
             d_ln_b = torch.zeros_like(ln_b) if want_ln else None
@@ -333,12 +332,8 @@ class _WindowFn(torch.autograd.Function):
 def colsum_rows(partial, P, C):
     """Column sums of the first ``C`` columns of ``partial`` [P, ld] by the library's fixed-order reduction (the summation tree of the
     grouped launch a ``DeferredDw`` collector would have used: same bits with and without a collector)."""
-    import ctypes
     out = torch.empty(C, dtype=torch.float32, device=partial.device)
-    one = lambda t, v: (t * 1)(v)
-    _lib.check(_lib.load().etm_colsum_reduce_grouped(one(ctypes.c_void_p, _ptr(partial)), one(ctypes.c_int32, P), one(ctypes.c_int32, C),
-                                                     one(ctypes.c_int32, partial.stride(0)), one(ctypes.c_void_p, _ptr(out)), 1, _stream()),
-               "etm_colsum_reduce_grouped")
+    _colsum_reduce([(partial, 0, P, C, partial.stride(0), out)])
     return out
 
 
@@ -425,8 +420,11 @@ def attention_supported(D, H, L, ln=False, pos_grad=False, backward=True, impl=N
 # (csrc/grouped_dw.hip) straight into the flat gradient arena.  Inactive (no collector) every layer computes its own dW as before.
 class DeferredDw:
     """Context manager around ``loss.backward()``.  ``dest``: {parameter.data_ptr(): gradient view [out, in] in the arena}.
-    Inside, the autograd functions below hand (dy, x, weight) over instead of multiplying; ``flush()`` (called on exit) runs the
-    grouped kernel.  ``written``: data_ptr()s of the parameters whose gradient now sits in its arena view."""
+    Inside, the autograd functions below hand their gradient problems over through the class methods (each of which answers
+    False / None when no collector is active or it refuses); ``flush()`` (called on exit) runs the grouped launches and ``pack()``
+    puts every other gradient into the arena.  ``written``: data_ptr()s of the parameters whose gradient now sits in its arena view
+    -- a parameter's first use only: the grouped launches OVERWRITE their destinations, so a second use of the same rows (tied
+    weights, a layer applied twice) is refused, autograd keeps its gradient and ``pack()`` adds it to the view."""
     active = None
     last_flops = 0.0             # 2 * N * Ma * Nb summed over the problems of the most recent grouped launch (bench.py prices it with this)
 
@@ -466,8 +464,6 @@ class DeferredDw:
         c = view[row0: row0 + ma]
         if view.shape[1] != nb or (_ptr(b) % 16) or (_ptr(c) % 16) or ((_ptr(a) + 4 * a_col0) % 4):
             return False
-        # the grouped kernel OVERWRITES its destination: a parameter used twice in one graph (tied weights, a layer applied twice)
-        # keeps its first use here and the caller multiplies the second one itself (autograd then accumulates it, _train_body_a adds it)
         taken = self.rows.setdefault(weight.data_ptr(), [])
         if any(row0 < r0 + m and r0 < row0 + ma for r0, m in taken):
             return False
@@ -476,6 +472,46 @@ class DeferredDw:
         self.items.append((a, b, c, ma, nb, lda, ldb, ldc, a_col0))
         self.written.add(weight.data_ptr())
         return True
+
+    @classmethod
+    def defer(cls, a, b, weight, **kw):
+        """``offer()`` to the active collector: True when it took the problem."""
+        return cls.active is not None and cls.active.offer(a, b, weight, **kw)
+
+    @classmethod
+    def defer_heads(cls, a, planes, weight):
+        """The rows of head h of ``weight`` [D, D] = a[:, h hd : (h + 1) hd]^T planes[h] (a [N, D], planes [H, N, D]): H problems,
+        taken all together or not at all -- a refusal leaves the collector exactly as it was before the first of them."""
+        col = cls.active
+        if col is None or not (a.is_contiguous() and planes.is_contiguous()):
+            return False
+        H, ptr = planes.shape[0], weight.data_ptr()
+        hd = a.shape[1] // H
+        before = (len(col.items), list(col.rows.get(ptr, ())), ptr in col.written, col.N)
+        if all(col.offer(a, planes[h], weight, row0=h * hd, rows=hd, a_col0=h * hd) for h in range(H)):
+            return True
+        n_items, col.rows[ptr], was_written, col.N = before
+        del col.items[n_items:]
+        if not was_written:
+            col.written.discard(ptr)
+        return False
+
+    @classmethod
+    def claim(cls, ptrs):
+        """The arena views of the parameters ``ptrs`` when the active collector knows every one as a contiguous view and none is
+        written yet; they count as written from now on (the caller fills them, at once or through ``defer_conv_wgrad``).  Else None."""
+        col = cls.active
+        views = None if col is None else [col.dest.get(ptr) for ptr in ptrs]
+        if views is None or any(v is None or not v.is_contiguous() for v in views) or any(ptr in col.written for ptr in ptrs):
+            return None
+        col.written.update(ptrs)
+        return views
+
+    @classmethod
+    def defer_conv_wgrad(cls, slices, count, dw, db, cout, c, kh, kw):
+        """An encoder layer's weight-gradient slices [count, Cout * K + Cout] (kept alive here), reduced into the views ``dw`` / ``db``
+        (from ``claim``) by the ONE slice reduction of ``flush()``."""
+        cls.active.conv_wgrads.append((slices, count, dw, db, cout, c, kh, kw))
 
     def offer_colsum(self, partial, P, ld, parts):
         """Second stage of column-sum gradients (LayerNorm weight / bias, linear bias): ``partial`` [P, ld] per-workgroup partial sums
@@ -494,23 +530,32 @@ class DeferredDw:
             self.written.add(ptr)
         return True
 
+    @classmethod
+    def colsum_workspace(cls, nbytes, P, ld, parts, device, tag):
+        """Workspace of a kernel whose second stage sums its partial rows [P, ld] into the gradients ``parts`` (see ``offer_colsum``).
+        (buffer, True): a private partial buffer the active collector took -- the kernel gets no destination, ``flush()`` reduces it;
+        (buffer, False): the shared ``workspace(nbytes, device, tag)`` -- the kernel reduces into a destination of the caller's."""
+        if cls.active is not None:
+            part = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+            if cls.active.offer_colsum(part, P, ld, parts):
+                return part, True
+        return workspace(nbytes, device, tag), False
+
+    @classmethod
+    def reduce_colsums(cls, partial, P, ld, parts):
+        """The gradients ``parts`` of the partial rows ``partial`` [P, ld]: [None] * len(parts) when the active collector took them
+        (``offer_colsum``), else their column sums, reduced at once by the same fixed-order kernel (``colsum_rows``)."""
+        if cls.active is not None and cls.active.offer_colsum(partial, P, ld, parts):
+            return [None] * len(parts)
+        sums = colsum_rows(partial, P, ld)
+        return [sums[c0: c0 + cols] for c0, cols, _ in parts]
+
     def flush(self):
-        import ctypes
         if self.conv_wgrads:
-            k = len(self.conv_wgrads)
-            vp = lambda j: (ctypes.c_void_p * k)(*[_ptr(it[j]) for it in self.conv_wgrads])
-            ia = lambda j: (ctypes.c_int32 * k)(*[it[j] for it in self.conv_wgrads])
-            _lib.check(_lib.load().etm_conv_wgrad_reduce_grouped(vp(0), ia(1), vp(2), vp(3), ia(4), ia(5), ia(6), ia(7), k, _stream()),
-                       "etm_conv_wgrad_reduce_grouped")
+            _conv_wgrad_reduce(self.conv_wgrads)
             self.conv_wgrads = []
         if self.colsums:
-            k = len(self.colsums)
-            pp = (ctypes.c_void_p * k)(*[_ptr(it[0]) + 4 * it[1] for it in self.colsums])
-            po = (ctypes.c_void_p * k)(*[_ptr(it[5]) for it in self.colsums])
-            iP = (ctypes.c_int32 * k)(*[it[2] for it in self.colsums])
-            iC = (ctypes.c_int32 * k)(*[it[3] for it in self.colsums])
-            iL = (ctypes.c_int32 * k)(*[it[4] for it in self.colsums])
-            _lib.check(_lib.load().etm_colsum_reduce_grouped(pp, iP, iC, iL, po, k, _stream()), "etm_colsum_reduce_grouped")
+            _colsum_reduce(self.colsums)
             self.colsums = []
         if not self.items:
             return
@@ -518,46 +563,49 @@ class DeferredDw:
         cap = lib.etm_grouped_dw_max_problems()          # problems per launch (the kernel-argument table: 84)
         for lo in range(0, len(self.items), cap):
             items = self.items[lo: lo + cap]
-            k = len(items)
-            pa = (ctypes.c_void_p * k)(*[_ptr(it[0]) + 4 * it[8] for it in items])
-            pb = (ctypes.c_void_p * k)(*[_ptr(it[1]) for it in items])
-            pc = (ctypes.c_void_p * k)(*[_ptr(it[2]) for it in items])
-            dims = (ctypes.c_int32 * (5 * k))(*[v for it in items for v in it[3:8]])
-            _lib.check(lib.etm_grouped_dw(pa, pb, pc, dims, k, self.N, _stream()), "etm_grouped_dw")
+            dims = _c_ints([v for it in items for v in it[3:8]])
+            _lib.check(lib.etm_grouped_dw(_c_ptrs([_ptr(it[0]) + 4 * it[8] for it in items]), _c_ptrs([it[1] for it in items]),
+                                          _c_ptrs([it[2] for it in items]), dims, len(items), self.N, _stream()), "etm_grouped_dw")
         DeferredDw.last_flops = float(sum(2.0 * self.N * it[3] * it[4] for it in self.items))
         self.items = []
 
-
-def _offer_dw(a, b, weight, **kw):
-    col = DeferredDw.active
-    return col is not None and col.offer(a, b, weight, **kw)
-
-
-class _LinearNoBiasFn(torch.autograd.Function):
-    """y = x W^T (transformer.py:26-29 queries / fc_out, :115 fc without their epilogues): library GEMMs for y and dx; the weight
-    gradient goes to the grouped launch when a DeferredDw collector is active."""
-
-    @staticmethod
-    def forward(ctx, x, weight):
-        ctx.save_for_backward(x, weight)
-        return x.mm(weight.t())
-
-    @staticmethod
-    def backward(ctx, g):
-        x, weight = ctx.saved_tensors
-        g = g.contiguous()
-        dx = g.mm(weight) if ctx.needs_input_grad[0] else None
-        dw = None
-        if ctx.needs_input_grad[1] and not _offer_dw(g, x, weight):
-            dw = g.t().mm(x)
-        return dx, dw
+    def pack(self, params, views, grads):
+        """After backward: the gradients ``grads`` of ``params`` (their ``.grad`` or torch.autograd.grad's outputs; None: parameter
+        outside the graph) into their arena ``views``.  A parameter in ``written`` is there already -- a refused second use is added
+        to it; every other one is copied by ONE multi-tensor launch."""
+        dst, src = [], []
+        for p, v, g in zip(params, views, grads):
+            if p.data_ptr() in self.written:
+                if g is not None:
+                    v.add_(g)
+                continue
+            dst.append(v)
+            src.append(g if g is not None else torch.zeros_like(v))
+        if dst:
+            torch._foreach_copy_(dst, src)
 
 
-def linear_nobias(x, weight):
-    """F.linear(x, weight) for 2-D fp32 device tensors under autograd, weight gradient deferrable (see DeferredDw)."""
-    if torch.is_grad_enabled() and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous():
-        return _LinearNoBiasFn.apply(x, weight)
-    return torch.nn.functional.linear(x, weight)
+def _c_ptrs(items):
+    """ctypes void* array of the addresses of ``items`` (tensors, or addresses already)."""
+    return (ctypes.c_void_p * len(items))(*[_ptr(t) if torch.is_tensor(t) else t for t in items])
+
+
+def _c_ints(values):
+    return (ctypes.c_int32 * len(values))(*values)
+
+
+def _colsum_reduce(problems):
+    """etm_colsum_reduce_grouped over ``problems`` = [(partial sums, first column, rows P, columns C, row stride, destination)]."""
+    partial, c0, P, C, ld, out = zip(*problems)
+    _lib.check(_lib.load().etm_colsum_reduce_grouped(_c_ptrs([_ptr(p) + 4 * c for p, c in zip(partial, c0)]), _c_ints(P), _c_ints(C),
+                                                     _c_ints(ld), _c_ptrs(out), len(problems), _stream()), "etm_colsum_reduce_grouped")
+
+
+def _conv_wgrad_reduce(problems):
+    """etm_conv_wgrad_reduce_grouped over ``problems`` = [(pixel slices, slice count, dw, db, Cout, C, KH, KW)]."""
+    slices, count, dw, db, cout, c, kh, kw = zip(*problems)
+    _lib.check(_lib.load().etm_conv_wgrad_reduce_grouped(_c_ptrs(slices), _c_ints(count), _c_ptrs(dw), _c_ptrs(db), _c_ints(cout), _c_ints(c),
+                                                         _c_ints(kh), _c_ints(kw), len(problems), _stream()), "etm_conv_wgrad_reduce_grouped")
 
 
 class _HeadFoldFn(torch.autograd.Function):
@@ -583,19 +631,9 @@ class _HeadFoldFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dq = torch.empty_like(q)
             torch.bmm(du, wk.view(H, hd, D).transpose(1, 2), out=dq.view(N, H, hd).transpose(0, 1))
-        if ctx.needs_input_grad[1]:
-            # dWk rows of head h = q_h^T du_h: H problems of the grouped launch (A = the head's columns of q, B = its plane of du)
-            col = DeferredDw.active
-            if col is not None and q.is_contiguous():
-                n0 = len(col.items)
-                ok = all(col.offer(q, du[h], wk, row0=h * hd, rows=hd, a_col0=h * hd) for h in range(H))
-                if not ok:
-                    del col.items[n0:]
-                    col.written.discard(wk.data_ptr())
-            else:
-                ok = False
-            if not ok:
-                dwk = torch.bmm(q.view(N, H, hd).permute(1, 2, 0), du).view(D, D)
+        # dWk rows of head h = q_h^T du_h: H problems of the grouped launch (A = the head's columns of q, B = its plane of du)
+        if ctx.needs_input_grad[1] and not DeferredDw.defer_heads(q, du, wk):
+            dwk = torch.bmm(q.view(N, H, hd).permute(1, 2, 0), du).view(D, D)
         return dq, dwk, None
 
 
@@ -623,18 +661,9 @@ class _HeadUnfoldFn(torch.autograd.Function):
         gh = g.view(N, H, hd).transpose(0, 1)                      # [H, N, hd], strided
         dz = torch.bmm(gh, wv.view(H, hd, D)) if ctx.needs_input_grad[0] else None
         dwv = None
-        if ctx.needs_input_grad[1]:
-            # dWv rows of head h = g_h^T z_h: H problems of the grouped launch
-            col = DeferredDw.active
-            ok = False
-            if col is not None and z.is_contiguous():
-                n0 = len(col.items)
-                ok = all(col.offer(g, z[h], wv, row0=h * hd, rows=hd, a_col0=h * hd) for h in range(H))
-                if not ok:
-                    del col.items[n0:]
-                    col.written.discard(wv.data_ptr())
-            if not ok:
-                dwv = torch.bmm(gh.transpose(1, 2), z).view(D, D)
+        # dWv rows of head h = g_h^T z_h: H problems of the grouped launch
+        if ctx.needs_input_grad[1] and not DeferredDw.defer_heads(g, z, wv):
+            dwv = torch.bmm(gh.transpose(1, 2), z).view(D, D)
         return dz, dwv, None
 
 
@@ -732,7 +761,6 @@ def _branch_sizes(branches):
 
 
 def _branch_table(sizes):
-    import ctypes
     return (ctypes.c_int32 * len(sizes))(*sizes), len(sizes)
 
 
@@ -912,7 +940,6 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
 def gather_rows(fields, idx):
     """``[t.index_select(0, idx) for t in fields]`` in one launch (etm_gather_rows): the per-sample fields of a minibatch.
     Tensors whose rows are not a multiple of 4 bytes (or not contiguous) go through index_select."""
-    import ctypes
     lib = _lib.load()
     n = idx.numel()
     outs = [None] * len(fields)
@@ -1056,21 +1083,17 @@ class _FusedLayerNormFn(torch.autograd.Function):
         da = torch.empty_like(s) if ctx.relu else None
         nbytes = lib.etm_ln_train_bwd_workspace_bytes(N, D)
         d_a = da if ctx.relu else ds
-        col = DeferredDw.active
-        if col is not None:
-            # the three column sums go to the collector's ONE reduction launch, straight into the parameters' arena views
-            g_ptr, b_ptr, bias_ptr = ctx.param_ptrs
-            parts = [(0, D, g_ptr), (D, D, b_ptr)] + ([(2 * D, D, bias_ptr)] if ctx.has_bias else [])
-            part = torch.empty(nbytes // 4, dtype=torch.float32, device=s.device)
-            if col.offer_colsum(part, lib.etm_ln_train_bwd_partial_rows(N), 3 * D, parts):
-                _lib.check(lib.etm_ln_train_bwd(_ptr(dy), _ptr(dy2), _ptr(s), _ptr(stats), _ptr(gamma), _ptr(a), _ptr(bias), 1 if ctx.relu else 0,
-                                                _ptr(ds), _ptr(da), None, _ptr(part), nbytes, N, D, _stream()), "etm_ln_train_bwd")
-                return d_a, None, (ds if ctx.has_res else None), None, None, None, None, None
-        sums = torch.empty((3, D), dtype=torch.float32, device=s.device)
-        ws = workspace(nbytes, s.device, "ln_bwd")
+        # with a collector the three column sums go to its ONE reduction launch, straight into the parameters' arena views
+        g_ptr, b_ptr, bias_ptr = ctx.param_ptrs
+        parts = [(0, D, g_ptr), (D, D, b_ptr)] + ([(2 * D, D, bias_ptr)] if ctx.has_bias else [])
+        ws, deferred = DeferredDw.colsum_workspace(nbytes, lib.etm_ln_train_bwd_partial_rows(N), 3 * D, parts, s.device, "ln_bwd")
+        sums = None if deferred else torch.empty((3, D), dtype=torch.float32, device=s.device)
         _lib.check(lib.etm_ln_train_bwd(_ptr(dy), _ptr(dy2), _ptr(s), _ptr(stats), _ptr(gamma), _ptr(a), _ptr(bias), 1 if ctx.relu else 0, _ptr(ds),
                                         _ptr(da), _ptr(sums), _ptr(ws), nbytes, N, D, _stream()), "etm_ln_train_bwd")
-        return d_a, (sums[2] if ctx.has_bias else None), (ds if ctx.has_res else None), sums[0], sums[1], None, None, None
+        d_res = ds if ctx.has_res else None
+        if deferred:
+            return d_a, None, d_res, None, None, None, None, None
+        return d_a, (sums[2] if ctx.has_bias else None), d_res, sums[0], sums[1], None, None, None
 
 
 def fused_layernorm(a, norm, bias=None, res=None, relu=False, fork=False):
@@ -1129,15 +1152,11 @@ class _GruGateFn(torch.autograd.Function):
         dev = x.device
         dA = torch.empty((N, 3 * D), dtype=torch.float32, device=dev)
         dB = torch.empty((N, 2 * D), dtype=torch.float32, device=dev)
-        dx1, dbg = torch.empty_like(x), None
+        dx1 = torch.empty_like(x)
         nbytes = lib.etm_gate_train_bwd_workspace_bytes(N, D)
-        col = DeferredDw.active
-        part = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if col is not None else None
-        if col is not None and col.offer_colsum(part, lib.etm_gate_train_bwd_partial_rows(N), D, [(0, D, ctx.bg_ptr)]):
-            ws = part                                   # d bg's second stage rides in the collector's one reduction launch
-        else:
-            dbg = torch.empty((D,), dtype=torch.float32, device=dev)
-            ws = workspace(nbytes, dev, "gate_bwd")
+        # (with a collector: d bg's second stage rides in its one reduction launch)
+        ws, deferred = DeferredDw.colsum_workspace(nbytes, lib.etm_gate_train_bwd_partial_rows(N), D, [(0, D, ctx.bg_ptr)], dev, "gate_bwd")
+        dbg = None if deferred else torch.empty((D,), dtype=torch.float32, device=dev)
         _lib.check(lib.etm_gate_train_bwd1(_ptr(dout), _ptr(dout2), _ptr(z), _ptr(hh), _ptr(x), _ptr(dA), _ptr(dB), _ptr(dx1), _ptr(dbg), _ptr(ws), nbytes,
                                            N, D, _stream()), "etm_gate_train_bwd1")
         dC = dA[:, 2 * D:]                              # d pre_h, a strided view (row stride 3D): GEMM operand in place
@@ -1154,8 +1173,9 @@ class _GruGateFn(torch.autograd.Function):
         # the tensor norm against float64 at N = 1,686: the worst tensors of the kink-free parity test were the gate matrices), the
         # grouped kernel in four chains summed pairwise (7e-7).
         wr, ur, wz, uz, wg = ctx.gate_weights
-        took = [_offer_dw(dA, y, wr, a_col0=0), _offer_dw(dB, x, ur, a_col0=0), _offer_dw(dA, y, wz, a_col0=D),
-                _offer_dw(dB, x, uz, a_col0=D), _offer_dw(dA, y, wg, a_col0=2 * D), _offer_dw(dA, rx, ug, a_col0=2 * D)]
+        defer = DeferredDw.defer
+        took = [defer(dA, y, wr, a_col0=0), defer(dB, x, ur, a_col0=0), defer(dA, y, wz, a_col0=D),
+                defer(dB, x, uz, a_col0=D), defer(dA, y, wg, a_col0=2 * D), defer(dA, rx, ug, a_col0=2 * D)]
         dwy = torch.mm(dA.t(), y) if not (took[0] and took[2] and took[4]) else None     # [3D, D] = d [Wr; Wz; Wg]
         dux = torch.mm(dB.t(), x) if not (took[1] and took[3]) else None                 # [2D, D] = d [Ur; Uz]
         pick = lambda t, full, lo: None if t else full[lo: lo + D]
@@ -1273,14 +1293,11 @@ _B3_LAYERS = {(3, 84, 84, 32, 8, 4), (32, 20, 20, 64, 4, 2), (64, 9, 9, 64, 3, 1
 def conv_b3_pack(weights, dgrad, strides):
     """``weights[i]`` [Cout, C, K, K] -> the three bf16 planes of its forward (``dgrad[i]`` 0) or backward-data (1) operand in
     fragment order (etm_conv_b3_pack, one launch for all entries): int16 tensors of 3 * numel."""
-    import ctypes
     lib = _lib.load()
-    n = len(weights)
     outs = [torch.empty(3 * w.numel(), dtype=torch.int16, device=w.device) for w in weights]
-    vp = lambda ts: (ctypes.c_void_p * n)(*[_ptr(t) for t in ts])
-    ia = lambda vs: (ctypes.c_int32 * n)(*vs)
-    _lib.check(lib.etm_conv_b3_pack(vp(weights), vp(outs), ia(dgrad), ia([w.shape[0] for w in weights]), ia([w.shape[1] for w in weights]),
-                                    ia([w.shape[2] for w in weights]), ia(strides), n, _stream()), "etm_conv_b3_pack")
+    _lib.check(lib.etm_conv_b3_pack(_c_ptrs(weights), _c_ptrs(outs), _c_ints(dgrad), _c_ints([w.shape[0] for w in weights]),
+                                    _c_ints([w.shape[1] for w in weights]), _c_ints([w.shape[2] for w in weights]), _c_ints(strides), len(weights),
+                                    _stream()), "etm_conv_b3_pack")
     return outs
 
 
@@ -1303,7 +1320,6 @@ class _EncoderFn(torch.autograd.Function):
         if index is not None:          # batch image i = x[index[i]]: the minibatch gather rides in the first layer's loads
             n = index.numel()
         # both packings of the three layers' weights in ONE launch; the backward-data ones ride in the context
-        import ctypes
         layers = ((w1, b1, strides[0]), (w2, b2, strides[1]), (w3, b3, strides[2]))
         wts = [_f32c(wt.detach(), "conv weight") for wt, _, _ in layers]
         geo, hh, ww = [], h, w
@@ -1317,11 +1333,9 @@ class _EncoderFn(torch.autograd.Function):
         else:
             packs = [torch.empty(wt.numel(), dtype=torch.float32, device=x.device) for wt in wts]
             dgrad_packs = [None] + [torch.empty(wt.numel(), dtype=torch.float32, device=x.device) for wt in wts[1:]]
-            vp = lambda ts: (ctypes.c_void_p * 3)(*[_ptr(t) for t in ts])
-            ia = lambda vs: (ctypes.c_int32 * 3)(*vs)
-            _lib.check(lib.etm_conv_pack_weights_grouped(vp(wts), vp(packs), vp(dgrad_packs), ia([wt.shape[0] for wt in wts]),
-                                                         ia([wt.shape[1] for wt in wts]), ia([wt.shape[2] for wt in wts]),
-                                                         ia([wt.shape[3] for wt in wts]), ia([l[2] for l in layers]), 3, st),
+            _lib.check(lib.etm_conv_pack_weights_grouped(_c_ptrs(wts), _c_ptrs(packs), _c_ptrs(dgrad_packs), _c_ints([wt.shape[0] for wt in wts]),
+                                                         _c_ints([wt.shape[1] for wt in wts]), _c_ints([wt.shape[2] for wt in wts]),
+                                                         _c_ints([wt.shape[3] for wt in wts]), _c_ints([l[2] for l in layers]), 3, st),
                        "etm_conv_pack_weights_grouped")
         ctx.b3 = use_b3
         relu_bits = []      # (b3: the ReLU pattern of every layer's output, one bit per element -- what backward-data needs of it)
@@ -1364,13 +1378,7 @@ class _EncoderFn(torch.autograd.Function):
         inputs = (x0, y1, y2)
         dgrad_packs = (None, pd2, pd3)
         # with a collector that knows the six parameters' arena views the three slice reductions become ONE launch at its flush
-        col = DeferredDw.active
-        dests = None
-        if col is not None:
-            dests = [col.dest.get(ptr) for ptr in ctx.param_ptrs]
-            if any(v is None or not v.is_contiguous() for v in dests) or any(ptr in col.written for ptr in ctx.param_ptrs):
-                dests = None
-        deferred = []
+        dests = DeferredDw.claim(ctx.param_ptrs)
         for i in (2, 1, 0):
             c, h, w, cout, kh, kw, s, ho, wo = ctx.shapes[i]
             K = kh * kw * c
@@ -1383,7 +1391,7 @@ class _EncoderFn(torch.autograd.Function):
             if dests is not None:
                 ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)      # (lives until the collector's flush)
                 buf = None
-                deferred.append((ws, slices, dests[2 * i], dests[2 * i + 1], cout, c, kh, kw))
+                DeferredDw.defer_conv_wgrad(ws, slices, dests[2 * i], dests[2 * i + 1], cout, c, kh, kw)
             else:
                 ws = workspace(nbytes, dev, "conv_wgrad")
                 buf = torch.empty(K * cout + cout, dtype=torch.float32, device=dev)
@@ -1391,12 +1399,7 @@ class _EncoderFn(torch.autograd.Function):
                 _lib.check(lib.etm_conv_b3_wgrad(_ptr(inputs[i]), _ptr(index) if i == 0 else None, _ptr(dy), _ptr(dy_bits), _ptr(ws), nbytes, n, c, h, w,
                                                  cout, kh, kw, s, st), "etm_conv_b3_wgrad")
                 if buf is not None:
-                    import ctypes
-                    one = lambda ct, v: (ct * 1)(v)
-                    _lib.check(lib.etm_conv_wgrad_reduce_grouped(one(ctypes.c_void_p, _ptr(ws)), one(ctypes.c_int32, slices), one(ctypes.c_void_p, _ptr(buf)),
-                                                                 one(ctypes.c_void_p, buf.data_ptr() + K * cout * 4), one(ctypes.c_int32, cout),
-                                                                 one(ctypes.c_int32, c), one(ctypes.c_int32, kh), one(ctypes.c_int32, kw), 1, st),
-                               "etm_conv_wgrad_reduce_grouped")
+                    _conv_wgrad_reduce([(ws, slices, buf, buf[K * cout:], cout, c, kh, kw)])
             else:
                 _lib.check(lib.etm_conv_train_wgrad(_ptr(inputs[i]), _ptr(index) if i == 0 else None, _ptr(dy), _ptr(buf), _ptr(ws), nbytes, n, c, h, w,
                                                     cout, kh, kw, s, st), "etm_conv_train_wgrad")
@@ -1412,9 +1415,6 @@ class _EncoderFn(torch.autograd.Function):
                     _lib.check(lib.etm_conv_train_dgrad(_ptr(dy), _ptr(dgrad_packs[i]), _ptr(inputs[i]), _ptr(dx), n, c, h, w, cout, kh, kw, s, st),
                                "etm_conv_train_dgrad")
                 dy, dy_bits = dx, None      # (the data gradient comes out masked: a pre-activation gradient)
-        if deferred:
-            col.conv_wgrads.extend(deferred)
-            col.written.update(ctx.param_ptrs)
         return (None, *grads, None, None, None)
 
 
@@ -1470,7 +1470,6 @@ def host_view(t):
     """numpy array over the memory of the contiguous float32 device tensor ``t`` at its HOST address (large-BAR systems map the
     device's memory into the process: the pointer is the same) -- WRITE-ONLY use: host reads through the BAR are uncached and
     slow, and the device's caches know nothing of them.  Call ``host_direct_write_ok`` first."""
-    import ctypes
     import numpy as np
     if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
         raise TypeError("host_view: a contiguous float32 device tensor is needed")
@@ -1526,87 +1525,73 @@ def upload(dst, src_pinned, stream):
 _fused_linear_relu = None  # None: untested, True/False after the first call
 
 
-class _LinearReluFn(torch.autograd.Function):
-    """y = relu(x W^T + b) with the element-wise part of the backward in two launches (etm_relu_bwd_colsum: ReLU mask and
-    bias gradient in one pass + the fixed-order column-sum reduction) instead of a mask multiply and a framework reduction."""
+def _addmm_relu(bias, x, wt):
+    """relu(bias + x wt)."""
+    if _fused_linear_relu:        # bias + ReLU in the GEMM's epilogue (one launch; verified against the two-op form by linear_relu)
+        return torch._addmm_activation(bias, x, wt, use_gelu=False)
+    return torch.relu_(torch.addmm(bias, x, wt))
+
+
+def _linear_backward(ctx, g, weight, y):
+    """Backward of y = act(x W^T + b) up to the weight gradient: (dy, dx = dy W, d bias), dy = ``g`` masked by the ReLU of the
+    output ``y`` (None: no ReLU).  The element-wise part is etm_relu_bwd_colsum -- the ReLU mask and the bias gradient in one pass +
+    the fixed-order column-sum reduction, its second stage in the collector's one reduction launch when one is active.  nn.Linear
+    leaves the bias gradient to the framework's column sum instead: two stages with a semaphore, which this runtime does not replay
+    reliably from a captured graph (profiles/r05/graph_reduce_hazard.txt), and two launches."""
+    g = _f32c(g, "grad")
+    db = None
+    if y is not None or (ctx.bias_ptr is not None and ctx.needs_input_grad[2]):
+        lib = _lib.load()
+        n, c = g.shape
+        gm = torch.empty_like(g) if y is not None else None
+        nbytes = lib.etm_relu_bwd_colsum_workspace_bytes(n, c)
+        ws, deferred = DeferredDw.colsum_workspace(nbytes, lib.etm_relu_bwd_colsum_partial_rows(n), c, [(0, c, ctx.bias_ptr)], g.device, "relu_bwd")
+        db = None if deferred else torch.empty(c, dtype=torch.float32, device=g.device)
+        _lib.check(lib.etm_relu_bwd_colsum(_ptr(g), _ptr(y), _ptr(gm), _ptr(db), _ptr(ws), nbytes, n, c, _stream()), "etm_relu_bwd_colsum")
+        g = g if gm is None else gm
+    dx = g.mm(weight) if ctx.needs_input_grad[0] else None
+    return g, dx, db
+
+
+class _LinearFn(torch.autograd.Function):
+    """y = x W^T, x W^T + b or (``relu``) relu(x W^T + b) for 2-D fp32 device tensors: library GEMMs for y and dx, the backward's
+    element-wise part in _linear_backward, the weight gradient to the grouped launch when a DeferredDw collector is active.
+    transformer.py:26-29 queries / fc_out, :115 fc without their epilogues; fc_out with its bias on the pre-LN / gated blocks."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
-        if _fused_linear_relu:        # bias + ReLU in the GEMM's epilogue (one launch; verified against the two-op form by linear_relu)
-            y = torch._addmm_activation(bias, x, weight.t(), use_gelu=False)
-        else:
+    def forward(ctx, x, weight, bias, relu):
+        if relu:
+            y = _addmm_relu(bias, x, weight.t())
+        elif bias is not None:
             y = torch.addmm(bias, x, weight.t())
-            torch.relu_(y)
-        ctx.save_for_backward(x, weight, y)
-        ctx.bias_ptr = bias.data_ptr()
+        else:
+            y = x.mm(weight.t())
+        ctx.save_for_backward(x, weight, y if relu else None)
+        ctx.bias_ptr = None if bias is None else bias.data_ptr()
         return y
 
     @staticmethod
     def backward(ctx, g):
         x, weight, y = ctx.saved_tensors
-        lib = _lib.load()
-        g = _f32c(g, "grad")
-        n, c = g.shape
-        gm = torch.empty_like(g)
-        nbytes = lib.etm_relu_bwd_colsum_workspace_bytes(n, c)
-        col = DeferredDw.active
-        db = None
-        part = torch.empty(nbytes // 4, dtype=torch.float32, device=g.device) if col is not None else None
-        if col is not None and col.offer_colsum(part, lib.etm_relu_bwd_colsum_partial_rows(n), c, [(0, c, ctx.bias_ptr)]):
-            # the bias gradient's second stage rides in the collector's one reduction launch
-            _lib.check(lib.etm_relu_bwd_colsum(_ptr(g), _ptr(y), _ptr(gm), None, _ptr(part), nbytes, n, c, _stream()), "etm_relu_bwd_colsum")
-        else:
-            db = torch.empty(c, dtype=torch.float32, device=g.device)
-            ws = workspace(nbytes, g.device, "relu_bwd")
-            _lib.check(lib.etm_relu_bwd_colsum(_ptr(g), _ptr(y), _ptr(gm), _ptr(db), _ptr(ws), nbytes, n, c, _stream()), "etm_relu_bwd_colsum")
-        dx = gm.mm(weight) if ctx.needs_input_grad[0] else None
+        g, dx, db = _linear_backward(ctx, g, weight, y)
         dw = None
-        if ctx.needs_input_grad[1] and not _offer_dw(gm, x, weight):
-            dw = gm.t().mm(x)
-        return dx, dw, db
-
-
-class _LinearBiasFn(torch.autograd.Function):
-    """y = x W^T + b (transformer.py:29 fc_out on the paths that keep its bias: pre-LN / gated blocks).  nn.Linear's backward leaves
-    the bias gradient to the framework's column sum -- two stages with a semaphore, which this runtime does not replay reliably from a
-    captured graph (profiles/r05/graph_reduce_hazard.txt) and which costs two launches; here it is etm_relu_bwd_colsum without a mask,
-    its second stage in the collector's one reduction launch; the weight gradient goes to the grouped launch."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        ctx.save_for_backward(x, weight)
-        ctx.bias_ptr = bias.data_ptr()
-        return torch.addmm(bias, x, weight.t())
-
-    @staticmethod
-    def backward(ctx, g):
-        x, weight = ctx.saved_tensors
-        lib = _lib.load()
-        g = _f32c(g, "grad")
-        n, c = g.shape
-        db = None
-        if ctx.needs_input_grad[2]:
-            nbytes = lib.etm_relu_bwd_colsum_workspace_bytes(n, c)
-            col = DeferredDw.active
-            part = torch.empty(nbytes // 4, dtype=torch.float32, device=g.device) if col is not None else None
-            if col is not None and col.offer_colsum(part, lib.etm_relu_bwd_colsum_partial_rows(n), c, [(0, c, ctx.bias_ptr)]):
-                _lib.check(lib.etm_relu_bwd_colsum(_ptr(g), None, None, None, _ptr(part), nbytes, n, c, _stream()), "etm_relu_bwd_colsum")
-            else:
-                db = torch.empty(c, dtype=torch.float32, device=g.device)
-                ws = workspace(nbytes, g.device, "relu_bwd")
-                _lib.check(lib.etm_relu_bwd_colsum(_ptr(g), None, None, _ptr(db), _ptr(ws), nbytes, n, c, _stream()), "etm_relu_bwd_colsum")
-        dx = g.mm(weight) if ctx.needs_input_grad[0] else None
-        dw = None
-        if ctx.needs_input_grad[1] and not _offer_dw(g, x, weight):
+        if ctx.needs_input_grad[1] and not DeferredDw.defer(g, x, weight):
             dw = g.t().mm(x)
-        return dx, dw, db
+        return dx, dw, db, None
+
+
+def linear_nobias(x, weight):
+    """F.linear(x, weight) for 2-D fp32 device tensors under autograd, weight gradient deferrable (see DeferredDw)."""
+    if torch.is_grad_enabled() and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous():
+        return _LinearFn.apply(x, weight, None, False)
+    return torch.nn.functional.linear(x, weight)
 
 
 def linear_bias(lin, x):
     """``lin(x)`` (an nn.Linear with bias) for 2-D fp32 device tensors under autograd: library GEMMs for y and dx, the bias gradient by
     the library's column sums, both parameter gradients deferrable (see DeferredDw).  Anything else: ``lin(x)``."""
     if (torch.is_grad_enabled() and lin.bias is not None and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous()):
-        return _LinearBiasFn.apply(x, lin.weight, lin.bias)
+        return _LinearFn.apply(x, lin.weight, lin.bias, False)
     return lin(x)
 
 
@@ -1621,11 +1606,7 @@ class _LinearReluNhwcFn(torch.autograd.Function):
         out, feat = weight.shape
         hw = feat // channels
         wp = weight.detach().view(out, channels, hw).transpose(1, 2).reshape(out, feat)       # [out, (h, w, c)]
-        if _fused_linear_relu:
-            y = torch._addmm_activation(bias, x, wp.t(), use_gelu=False)
-        else:
-            y = torch.addmm(bias, x, wp.t())
-            torch.relu_(y)
+        y = _addmm_relu(bias, x, wp.t())
         ctx.save_for_backward(x, wp, y)
         ctx.bias_ptr, ctx.weight_ptr, ctx.channels = bias.data_ptr(), weight.data_ptr(), channels
         return y
@@ -1633,30 +1614,14 @@ class _LinearReluNhwcFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, wp, y = ctx.saved_tensors
-        lib = _lib.load()
-        g = _f32c(g, "grad")
-        n, c = g.shape
-        out, feat = wp.shape
-        hw = feat // ctx.channels
-        gm = torch.empty_like(g)
-        nbytes = lib.etm_relu_bwd_colsum_workspace_bytes(n, c)
-        col = DeferredDw.active
-        db = None
-        part = torch.empty(nbytes // 4, dtype=torch.float32, device=g.device) if col is not None else None
-        if col is not None and col.offer_colsum(part, lib.etm_relu_bwd_colsum_partial_rows(n), c, [(0, c, ctx.bias_ptr)]):
-            _lib.check(lib.etm_relu_bwd_colsum(_ptr(g), _ptr(y), _ptr(gm), None, _ptr(part), nbytes, n, c, _stream()), "etm_relu_bwd_colsum")
-        else:
-            db = torch.empty(c, dtype=torch.float32, device=g.device)
-            ws = workspace(nbytes, g.device, "relu_bwd")
-            _lib.check(lib.etm_relu_bwd_colsum(_ptr(g), _ptr(y), _ptr(gm), _ptr(db), _ptr(ws), nbytes, n, c, _stream()), "etm_relu_bwd_colsum")
-        dx = gm.mm(wp) if ctx.needs_input_grad[0] else None
+        gm, dx, db = _linear_backward(ctx, g, wp, y)
         dw = None
         if ctx.needs_input_grad[1]:
-            dwp = gm.t().mm(x).view(out, hw, ctx.channels).transpose(1, 2)                # [out, c, hw] view of the (h, w, c) result
-            dest = col.dest.get(ctx.weight_ptr) if col is not None else None
-            if dest is not None and dest.is_contiguous() and ctx.weight_ptr not in col.written:
-                dest.view(out, ctx.channels, hw).copy_(dwp)
-                col.written.add(ctx.weight_ptr)
+            out, feat = wp.shape
+            dwp = gm.t().mm(x).view(out, feat // ctx.channels, ctx.channels).transpose(1, 2)    # [out, c, hw] view of the (h, w, c) result
+            dest = DeferredDw.claim([ctx.weight_ptr])
+            if dest is not None:
+                dest[0].view(dwp.shape).copy_(dwp)
             else:
                 dw = dwp.reshape(out, feat)
         return dx, dw, db, None
@@ -1668,8 +1633,8 @@ def linear_relu_nhwc(x, weight, bias, channels):
 
 
 def linear_relu_train(x, weight, bias):
-    """relu(F.linear(x, weight, bias)) for 2-D fp32 device tensors under autograd (see _LinearReluFn)."""
-    return _LinearReluFn.apply(x, weight, bias)
+    """relu(F.linear(x, weight, bias)) for 2-D fp32 device tensors under autograd (see _LinearFn)."""
+    return _LinearFn.apply(x, weight, bias, True)
 
 
 def linear_relu(lin, x, out=None):
@@ -1681,7 +1646,7 @@ def linear_relu(lin, x, out=None):
     def plain():
         if (torch.is_grad_enabled() and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and lin.bias is not None and out is None
                 and x.is_contiguous()):
-            return _LinearReluFn.apply(x, lin.weight, lin.bias)
+            return _LinearFn.apply(x, lin.weight, lin.bias, True)
         y = torch.relu(torch.nn.functional.linear(x, lin.weight, lin.bias))
         return y if out is None else out.copy_(y)
 
@@ -1832,9 +1797,9 @@ class _HeadsLossFn(torch.autograd.Function):
             if not unit:
                 dh = dh * g_loss
         dwlp = dwlv = None
-        if ctx.needs_input_grad[1] and not (unit and _offer_dw(gm_p, h, wlp)):
+        if ctx.needs_input_grad[1] and not (unit and DeferredDw.defer(gm_p, h, wlp)):
             dwlp = gm_p.t().mm(h) if unit else gm_p.t().mm(h) * g_loss
-        if ctx.needs_input_grad[3] and not (unit and _offer_dw(gm_v, h, wlv)):
+        if ctx.needs_input_grad[3] and not (unit and DeferredDw.defer(gm_v, h, wlv)):
             dwlv = gm_v.t().mm(h) if unit else gm_v.t().mm(h) * g_loss
         s = sums if unit else sums * g_loss
         o = (3 + A) * hid

@@ -1163,15 +1163,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         # during backward and computed by ONE grouped launch straight into their arena views (csrc/grouped_dw.hip)
         with ops.DeferredDw(self._dw_destinations()) as dw:
             loss.backward(self._unit_gradient(loss))
-        views, grads = [], []
-        for p, v in zip(self.params, self._grad_views):
-            if p.data_ptr() in dw.written:
-                if p.grad is not None:               # a second use of the parameter that the collector refused: add it to the arena view
-                    v.add_(p.grad)
-                continue                             # already in the arena
-            views.append(v)
-            grads.append(p.grad if p.grad is not None else torch.zeros_like(v))   # None: parameter outside this graph (unused head)
-        torch._foreach_copy_(views, grads)
+        dw.pack(self.params, self._grad_views, [p.grad for p in self.params])
         for p, v in zip(self.params, self._grad_views):
             p.grad = v
 

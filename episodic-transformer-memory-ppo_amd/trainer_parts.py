@@ -54,18 +54,8 @@ class _DataParallelStep:
             p.grad = None
         with ops.DeferredDw(self._dw_destinations()) as dw:
             got = torch.autograd.grad(loss, [feats] + rest, grad_outputs=self._unit_gradient(loss), allow_unused=True)
-        dfeats, grads_rest = got[0], got[1:]
-        views, grads = [], []
-        for p, v, g in zip(rest, self._grad_views[n_conv:], grads_rest):
-            if p.data_ptr() in dw.written:
-                if g is not None:
-                    v.add_(g)
-                continue
-            views.append(v)
-            grads.append(g if g is not None else torch.zeros_like(v))
-        if views:
-            torch._foreach_copy_(views, grads)
-        return stats, dfeats
+        dw.pack(rest, self._grad_views[n_conv:], got[1:])
+        return stats, got[0]
 
     def _train_body_a2(self, dfeats):
         """The encoder's backward pass from d loss / d features; the convolutions' gradients end up in their arena views."""
@@ -74,16 +64,7 @@ class _DataParallelStep:
         convs = self.params[:n_conv]
         with ops.DeferredDw(self._dw_destinations()) as dw:
             got = torch.autograd.grad(feats, convs, grad_outputs=dfeats, allow_unused=True)
-        views, grads = [], []
-        for p, v, g in zip(convs, self._grad_views[:n_conv], got):
-            if p.data_ptr() in dw.written:
-                if g is not None:
-                    v.add_(g)
-                continue
-            views.append(v)
-            grads.append(g if g is not None else torch.zeros_like(v))
-        if views:
-            torch._foreach_copy_(views, grads)
+        dw.pack(convs, self._grad_views[:n_conv], got)
         for p, v in zip(self.params, self._grad_views):
             p.grad = v
         self.model._encoder_features = None

@@ -2173,6 +2173,39 @@ def test_grouped_weight_gradients_vs_float64(N):
     print(f"[grouped dW N={N}] worst element error / rms element vs float64: {worst:.2e}")
 
 
+@pytest.mark.parametrize("node", ["head_fold", "head_unfold", "linear_nobias"])
+def test_weight_used_twice_under_a_collector_vs_plain_autograd(node):
+    """A weight used twice in one backward pass under a DeferredDw collector: the first use's gradient goes to the grouped launch,
+    the second is refused (its rows are taken) and stays with autograd.  For the per-head nodes the refusal comes at head 0 of the
+    second use, after the first use was accepted; the collector must still count the weight as written.  The gradient is assembled
+    as the trainer does (arena view + w.grad when written, else w.grad) and compared with plain autograd."""
+    from etm import ops
+    dev = _dev()
+    torch.manual_seed(11)
+    N, D, H = 256, 384, 4
+    w = torch.randn((D, D), device=dev).mul_(0.05).requires_grad_(True)
+    apply = {"head_fold": lambda x: ops._HeadFoldFn.apply(x, w, H), "head_unfold": lambda x: ops._HeadUnfoldFn.apply(x, w, H),
+             "linear_nobias": lambda x: ops.linear_nobias(x, w)}[node]
+    shape = (H, N, D) if node == "head_unfold" else (N, D)
+    x1, x2 = torch.randn(shape, device=dev), torch.randn(shape, device=dev)
+    out_shape = apply(x1).shape
+    g1, g2 = torch.randn(out_shape, device=dev), torch.randn(out_shape, device=dev)
+
+    def loss():
+        return (apply(x1) * g1).sum() + (apply(x2) * g2).sum()
+
+    loss().backward()
+    ref = w.grad.clone()
+    w.grad = None
+    view = torch.full((D, D), float("nan"), device=dev)
+    with ops.DeferredDw({w.data_ptr(): view}) as col:
+        loss().backward()
+    assert w.grad is not None            # the second use was refused: autograd holds its gradient
+    got = view + w.grad if w.data_ptr() in col.written else w.grad
+    err = float((got - ref).abs().max())
+    assert err <= 2e-5 * float(ref.abs().max()) + 1e-6, (node, err, float(ref.abs().max()))
+
+
 @pytest.mark.parametrize("N,D", [(2048, 384), (601, 128), (9, 96), (1, 64)])
 def test_grouped_column_sums_bit_identical_to_per_call_reductions(N, D):
     """etm_colsum_reduce_grouped: the LayerNorm weight / bias and linear bias gradients of a backward pass (two fused LayerNorms --
@@ -2581,7 +2614,7 @@ def test_fused_heads_and_loss_vs_composed_ops(N, hid, A, D):
 
 
 def test_linear_relu_backward_kernels_vs_autograd():
-    """_LinearReluFn (mask + bias gradient in one pass, fixed-order column sums) against torch's relu(linear) in float64."""
+    """ops.linear_relu_train (mask + bias gradient in one pass, fixed-order column sums) against torch's relu(linear) in float64."""
     from etm import ops
     dev = _dev()
     torch.manual_seed(41)
