@@ -22,7 +22,7 @@ from etm import ops
 
 class Buffer:
     def __init__(self, config: dict, observation_space, action_space_shape: tuple, max_episode_length: int,
-                 device: torch.device) -> None:
+                 device: torch.device, continuous: bool = False) -> None:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("Buffer is HBM-resident: it needs the MI355X (HIP) device; there is no CPU path in this build")
@@ -35,7 +35,7 @@ class Buffer:
         t = config["transformer"]
         self.memory_length, self.num_blocks, self.embed_dim = t["memory_length"], t["num_blocks"], t["embed_dim"]
         W, S, L, dev = self.n_workers, self.worker_steps, self.memory_length, self.device
-        B = len(action_space_shape)
+        B = action_space_shape[0] if continuous else len(action_space_shape)      # (Box: the A dimensions of one action)
 
         pin = lambda shape, dtype: torch.zeros(shape, dtype=dtype).pin_memory()
         self._rewards_host = pin((W, S), torch.float32)
@@ -47,9 +47,10 @@ class Buffer:
         self.rewards_dev = torch.zeros((W, S), dtype=torch.float32, device=dev)
         self.dones_dev = torch.zeros((W, S), dtype=torch.bool, device=dev)
 
-        self.actions = torch.zeros((W, S, B), dtype=torch.long, device=dev)
+        # (Box: the raw float actions [W, S, A] and one joint log-prob per sample)
+        self.actions = torch.zeros((W, S, B), dtype=torch.float32 if continuous else torch.long, device=dev)
         self.obs = torch.zeros((W, S) + tuple(observation_space.shape), dtype=torch.float32, device=dev)
-        self.log_probs = torch.zeros((W, S, B), dtype=torch.float32, device=dev)
+        self.log_probs = torch.zeros((W, S, 1 if continuous else B), dtype=torch.float32, device=dev)
         self.values = torch.zeros((W, S), dtype=torch.float32, device=dev)
         self.advantages = torch.zeros((W, S), dtype=torch.float32, device=dev)
         self.memory_mask = torch.zeros((W, S, L), dtype=torch.bool, device=dev)

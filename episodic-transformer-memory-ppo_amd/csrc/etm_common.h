@@ -142,6 +142,52 @@ __device__ __forceinline__ void etm_sample_branches(const float *lg, const EtmBr
   }
 }
 
+// Box (continuous) action spaces: a diagonal Gaussian policy over A <= ETM_MAX_BOX dimensions, mean = the A policy-head outputs,
+// sigma_a = exp(log_std[a]) (state-independent).  The environment's bounds travel with the launch by value (no device allocation,
+// graph-capturable); the buffer keeps the raw draw, the host gets it clipped to [lo, hi].
+constexpr int ETM_MAX_BOX = 8;
+struct EtmBox {
+  int A;
+  float lo[ETM_MAX_BOX], hi[ETM_MAX_BOX];
+};
+// Host side: the bound table of A dimensions (lo / hi: HOST arrays; NULL = unbounded).  0, ETM_EINVAL or ETM_EUNSUPPORTED (A > 8).
+static inline int etm_box_make(const float *lo, const float *hi, int A, EtmBox *out) {
+  if (A <= 0) return ETM_EINVAL;
+  if (A > ETM_MAX_BOX) return ETM_EUNSUPPORTED;
+  out->A = A;
+  for (int a = 0; a < ETM_MAX_BOX; ++a) {
+    out->lo[a] = (lo && a < A) ? lo[a] : -INFINITY;
+    out->hi[a] = (hi && a < A) ? hi[a] : INFINITY;
+    if (a < A && !(out->lo[a] <= out->hi[a])) return ETM_EINVAL;
+  }
+  return 0;
+}
+
+// One Gaussian draw of worker w at step t (row = t * stage_W + w of the time-major tables) -- every sampling site of a Box policy:
+// x_a = mu_a + sigma_a eps_a with eps = normals[0 .. A) (or the forced action forced[a] where it is not NaN), the joint log-prob
+// log p(x) = sum_a [-(x_a - mu_a)^2 / (2 sigma_a^2) - log sigma_a - log(2 pi) / 2] of the stored x, staging of x ([S, stage_W, A]),
+// log p and the value ([S, stage_W]); actions / host_actions [W, A] receive clip(x, lo, hi).  normals / forced / log_std: A floats.
+__device__ __forceinline__ void etm_sample_gaussian(const float *mu, const float *log_std, const EtmBox &bx, const float *normals,
+                                                    const float *forced, float value, long long row, int w, float *actions,
+                                                    float *host_actions, float *st_actions, float *st_logp, float *st_values) {
+  const int A = bx.A;
+  float lp = 0.f;
+  for (int a = 0; a < A; ++a) {
+    const float ls = log_std[a];
+    const float sg = expf(ls);
+    float x = forced ? forced[a] : NAN;
+    if (x != x) x = mu[a] + sg * normals[a];
+    const float z = (x - mu[a]) / sg;
+    lp += (-0.5f * z * z - ls) - 0.918938533204672742f;
+    const float c = fminf(fmaxf(x, bx.lo[a]), bx.hi[a]);
+    actions[(long long)w * A + a] = c;
+    if (host_actions) host_actions[(long long)w * A + a] = c;
+    st_actions[row * A + a] = x;
+  }
+  st_logp[row] = lp;
+  st_values[row] = value;
+}
+
 static inline int etm_launch_status() { return (int)hipGetLastError(); }
 
 // ---- optional per-kernel timing with HIP events (see etm_profile_* in include/etm_hip.h); off by default.

@@ -44,9 +44,12 @@ struct HlParams {
   int nbr;
   int col_branch[HL_MAXA];
   int branch_off[HL_MAXA];
+  // GS kernels (Box): the A logits are the means; xact [N, A] (row stride action_stride) the stored raw actions, log_std [A]
+  const float *xact, *log_std;
 };
 
-template <int HC, bool BR>
+// BR: MultiDiscrete branches; GS: diagonal Gaussian (Box; the row gains d log_std [A] behind the five statistic sums)
+template <int HC, bool BR, bool GS = false>
 __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
   HlParams p = p0;
   if (p.dyn) {
@@ -69,6 +72,17 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
   float bbr[HL_MAXA];
 #pragma unroll
   for (int a = 0; a < HL_MAXA; ++a) bbr[a] = (a < A) ? p.bb[a] : 0.f;
+  // GS: log sigma, sigma and the entropy sum_a (1/2 + log(2 pi) / 2 + log sigma_a) (the same for every sample); d log sigma sums
+  float lsr[HL_MAXA], sgr[HL_MAXA], s_ls[HL_MAXA], ent_gs = 0.f;
+  if constexpr (GS) {
+#pragma unroll
+    for (int a = 0; a < HL_MAXA; ++a) {
+      lsr[a] = (a < A) ? p.log_std[a] : 0.f;
+      sgr[a] = expf(lsr[a]);
+      s_ls[a] = 0.f;
+      if (a < A) ent_gs += (0.5f + 0.918938533204672742f) + lsr[a];
+    }
+  }
   const float bvr = p.bv[0];
   const float cnt = p.adv_stats3[0], mean = p.adv_stats3[1], m2 = p.adv_stats3[2];
   const float stdv = sqrtf(m2 / (cnt - 1.0f));                       // torch.std: unbiased
@@ -132,7 +146,47 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
     const float a_raw = p.adv[n];
     const float a_n = (a_raw - mean) / (stdv + 1e-8f);
     float dl[HL_MAXA];
-    if constexpr (!BR) {
+    if constexpr (GS) {
+      // Box (diagonal Gaussian): log p(x) = sum_a [-z_a^2 / 2 - log sigma_a - log(2 pi) / 2], z_a = (x_a - mu_a) / sigma_a, of the
+      // stored raw action x; one ratio per sample, the surrogate's per-sample factor cpol = d loss / d log p as in the other modes;
+      // d log p / d mu_a = z_a / sigma_a, d log p / d log sigma_a = z_a^2 - 1, and the entropy adds cent to every d log sigma_a
+      float zr[HL_MAXA];
+      float lp = 0.f;
+#pragma unroll
+      for (int a = 0; a < HL_MAXA; ++a) {
+        zr[a] = 0.f;
+        if (a < A) {
+          const float x = p.xact[(long long)n * p.action_stride + a];
+          zr[a] = (x - lg[a]) / sgr[a];
+          lp += (-0.5f * zr[a] * zr[a] - lsr[a]) - 0.918938533204672742f;
+        }
+      }
+      const float log_ratio = lp - p.old_logp[(long long)n * p.logp_stride];
+      const float ratio = expf(log_ratio);
+      const bool in_range = (ratio >= p.clip_lo) && (ratio <= p.clip_hi);
+      const float s1 = ratio * a_n;
+      const float s2 = fminf(fmaxf(ratio, p.clip_lo), p.clip_hi) * a_n;
+      float g_ratio;
+      if (s1 < s2) g_ratio = a_n;
+      else if (s1 > s2) g_ratio = in_range ? a_n : 0.f;
+      else g_ratio = 0.5f * a_n + (in_range ? 0.5f * a_n : 0.f);
+      if (lane == 0) {
+        acc[0] += fminf(s1, s2);
+        acc[2] += ent_gs;
+        acc[3] += (ratio - 1.0f) - log_ratio;
+        acc[4] += (fabsf(ratio - 1.0f) > p.clip) ? 1.f : 0.f;
+      }
+      const float cpol = -p.pol_scale * g_ratio * ratio;
+      const float cent = -p.beta * p.ent_scale;
+#pragma unroll
+      for (int a = 0; a < HL_MAXA; ++a) {
+        dl[a] = 0.f;
+        if (a < A) {
+          dl[a] = cpol * (zr[a] / sgr[a]);
+          if (lane == 0) s_ls[a] += cpol * (zr[a] * zr[a] - 1.f) + cent;
+        }
+      }
+    } else if constexpr (!BR) {
     float mx = -INFINITY;
 #pragma unroll
     for (int j = 0; j < HL_MAXA; ++j) if (j < A) mx = fmaxf(mx, lg[j]);
@@ -278,7 +332,8 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
   }
 
   // ---- the four waves' sums -> one partial row per workgroup: [sum gm_p | sum gm_v | d wv | d Wb[0] .. d Wb[A-1] | d bb[A] | d bv | 5 stats]
-  const int row = (3 + A) * hid + A + 1 + 5;
+  //      (GS: then d log_std[A])
+  const int row = (3 + A) * hid + A + 1 + 5 + (GS ? A : 0);
   auto put_row = [&](float *dst, bool add) {
 #pragma unroll
     for (int c = 0; c < HC; ++c) {
@@ -298,6 +353,11 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
       if (add) t[A] += s_bv; else t[A] = s_bv;
 #pragma unroll
       for (int k5 = 0; k5 < 5; ++k5) { if (add) t[A + 1 + k5] += acc[k5]; else t[A + 1 + k5] = acc[k5]; }
+      if constexpr (GS) {
+#pragma unroll
+        for (int a = 0; a < HL_MAXA; ++a)
+          if (a < A) { if (add) t[A + 6 + a] += s_ls[a]; else t[A + 6 + a] = s_ls[a]; }
+      }
     }
   };
   put_row(hl_lds + (long long)wave * row, false);
@@ -306,7 +366,8 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
   for (int e = tid; e < row; e += 256) dst[e] = ((hl_lds[e] + hl_lds[row + e]) + hl_lds[2 * row + e]) + hl_lds[3 * row + e];
 }
 
-// sums the workgroup rows and finishes the loss statistics: out = [row sums ... ], out8.  One workgroup = 64 row elements x 16 row
+// sums the workgroup rows and finishes the loss statistics: out = [row sums ... ], out8 (a Gaussian row's d log_std sums, behind the
+// statistics, are summed like every other element).  One workgroup = 64 row elements x 16 row
 // groups: thread (e, g) adds the rows g, g + 16, ... (all requested at once: the sum is a latency chain otherwise), the 16 group
 // sums are added in group order -- a fixed tree, deterministic.
 __global__ __launch_bounds__(1024) void heads_reduce_kernel(const float *__restrict__ partials, int n_wg, int row, int A, int hid, float vf_coef,
@@ -363,6 +424,12 @@ extern "C" int64_t etm_heads_loss_workspace_bytes(int N, int hid, int A) {
   if (!etm_heads_loss_supported(N, hid, A)) return 0;
   return (int64_t)((N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG) * etm_heads_loss_row_floats(hid, A) * (int64_t)sizeof(float);
 }
+extern "C" int etm_heads_loss_supported_gaussian(int N, int hid, int A) { return A <= ETM_MAX_BOX && etm_heads_loss_supported(N, hid, A); }
+extern "C" int etm_heads_loss_gaussian_row_floats(int hid, int A) { return etm_heads_loss_row_floats(hid, A) + A; }
+extern "C" int64_t etm_heads_loss_gaussian_workspace_bytes(int N, int hid, int A) {
+  if (!etm_heads_loss_supported_gaussian(N, hid, A)) return 0;
+  return (int64_t)((N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG) * etm_heads_loss_gaussian_row_floats(hid, A) * (int64_t)sizeof(float);
+}
 
 // pre_p / pre_v [N, hid] = h Wlp^T / h Wlv^T (no bias).  Outputs: gm_p / gm_v [N, hid] = d loss / d (pre + bias) of the two hidden
 // heads; sums [etm_heads_loss_row_floats] = [d b_lp (hid) | d b_lv (hid) | d wv (hid) | d Wb (A x hid) | d bb (A) | d bv | 5 raw sums];
@@ -373,13 +440,15 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
                               int64_t logp_stride, const float *adv, const float *old_value, const float *adv_stats3, double clip, float vf_coef,
                               float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v,
                               float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
-                              int A, const int32_t *branch_sizes, int n_branches, void *stream) {
+                              int A, const int32_t *branch_sizes, int n_branches, const float *xact, const float *log_std, void *stream) {
   (void)hipGetLastError();
-  if (!pre_p || !pre_v || !b_lp || !b_lv || !wb || !bb || !wv || !bv || !actions || !old_logp || !adv || !old_value || !adv_stats3 || !gm_p ||
-      !gm_v || !sums || !out8 || !workspace)
+  const bool gauss = xact != nullptr;                  // Box: float actions xact and log_std instead of the int64 actions
+  if (!pre_p || !pre_v || !b_lp || !b_lv || !wb || !bb || !wv || !bv || !(gauss ? (const void *)log_std : (const void *)actions) || !old_logp ||
+      !adv || !old_value || !adv_stats3 || !gm_p || !gm_v || !sums || !out8 || !workspace)
     return ETM_EINVAL;
-  if (!etm_heads_loss_supported(N, hid, A)) return ETM_EUNSUPPORTED;
-  if (workspace_bytes < etm_heads_loss_workspace_bytes(N, hid, A)) return ETM_EWORKSPACE;
+  if (!(gauss ? etm_heads_loss_supported_gaussian(N, hid, A) : etm_heads_loss_supported(N, hid, A))) return ETM_EUNSUPPORTED;
+  if (workspace_bytes < (gauss ? etm_heads_loss_gaussian_workspace_bytes(N, hid, A) : etm_heads_loss_workspace_bytes(N, hid, A)))
+    return ETM_EWORKSPACE;
   HlParams p{};
   EtmBranches br;
   if (const int rc = etm_branches_make(branch_sizes, n_branches, A, &br)) return rc;
@@ -396,8 +465,9 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
   p.vf_coef = vf_coef; p.beta = beta; p.pol_scale = pol_scale; p.ent_scale = ent_scale; p.val_scale = val_scale; p.dyn = dyn_clip_beta;
   p.gm_p = gm_p; p.gm_v = gm_v; p.logits = logits; p.value = value; p.partials = (float *)workspace;
   p.N = N; p.A = A; p.hid = hid; p.samples_per_wg = HL_SAMPLES_PER_WG;
+  p.xact = xact; p.log_std = log_std;
   const int n_wg = (N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG;
-  const int row = etm_heads_loss_row_floats(hid, A);
+  const int row = gauss ? etm_heads_loss_gaussian_row_floats(hid, A) : etm_heads_loss_row_floats(hid, A);
   const size_t lds = 4 * (size_t)row * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
   {
@@ -405,7 +475,8 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
     switch (hid / 64) {
 #define HL_CASE(HC_)                                                                                              \
   case HC_:                                                                                                       \
-    if (branched) hipLaunchKernelGGL((heads_loss_kernel<HC_, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    if (gauss) hipLaunchKernelGGL((heads_loss_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (branched) hipLaunchKernelGGL((heads_loss_kernel<HC_, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
     else hipLaunchKernelGGL((heads_loss_kernel<HC_, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p);         \
     break;
       HL_CASE(1) HL_CASE(2) HL_CASE(3) HL_CASE(4) HL_CASE(5) HL_CASE(6) HL_CASE(7) HL_CASE(8)
@@ -429,7 +500,7 @@ extern "C" int etm_heads_loss(const float *pre_p, const float *pre_v, const floa
                               int A, void *stream) {
   return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
                          clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, A, nullptr, 1, stream);
+                         workspace_bytes, N, hid, A, nullptr, 1, nullptr, nullptr, stream);
 }
 
 // MultiDiscrete: wb / bb = the branches' heads concatenated ([sum(sizes), hid], [sum(sizes)]); actions / old_logp rows carry one entry
@@ -449,5 +520,22 @@ extern "C" int etm_heads_loss_branched(const float *pre_p, const float *pre_v, c
   if (action_stride < n_branches || logp_stride < n_branches) return ETM_EINVAL;
   return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
                          clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, stream);
+                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, nullptr, stream);
+}
+
+// Box policies (diagonal Gaussian, A <= 8): wb / bb = the mean head [A, hid], [A]; xact [N, A] (row stride action_stride >= A) the
+// stored raw actions; log_std [A]; old_logp [N] (logp_stride).  sums [etm_heads_loss_gaussian_row_floats] = the etm_heads_loss row
+// followed by d log_std (A); scales as in etm_heads_loss (pol_scale = ent_scale = val_scale = 1 / N).
+extern "C" int etm_heads_loss_gaussian(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                       const float *bb, const float *wv, const float *bv, const float *xact, int64_t action_stride,
+                                       const float *log_std, const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
+                                       const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                                       float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
+                                       float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid, int A,
+                                       void *stream) {
+  if (!xact) return ETM_EINVAL;
+  if (action_stride < A || logp_stride < 1) return ETM_EINVAL;
+  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, nullptr, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
+                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
+                         workspace_bytes, N, hid, A, nullptr, 1, xact, log_std, stream);
 }

@@ -37,7 +37,8 @@ namespace {
 // GR: rows of a product slice in registers per thread; LMAX: window rows the K / V registers are sized for.
 // GEN: the general block layout (pre-LN and / or GRU gates) is compiled in; the post-LN layout without gates (the headline
 // configuration) gets a kernel without that code, which keeps its register allocation free of spills.
-template <int GR, int LMAX, bool GEN>
+// BOX: a Box policy's Gaussian draw at the end (etm_sample_gaussian, float tables p.box) instead of the categorical branches.
+template <int GR, int LMAX, bool GEN, bool BOX>
 __global__ __launch_bounds__(RF_T) void rollout_trxl_kernel(const RfParams p) {
   constexpr int KR = LMAX / RF_WAVES;                             // window rows per wave (energies)
   constexpr int VR = LMAX / 16;                                   // window rows per thread (context): >= 16 row groups (D / P <= 128)
@@ -86,10 +87,20 @@ __global__ __launch_bounds__(RF_T) void rollout_trxl_kernel(const RfParams p) {
   const long long t_now = *p.t_dev;                                 // (uniform) step counter of the rollout
   __shared__ int forced_s[ETM_MAX_BRANCHES];
   __shared__ float u_s[ETM_MAX_BRANCHES];
-  if (me == 0 && tid < p.br.n) {
-    const long long i = (t_now * p.stage_W + w) * p.br.n + tid;
-    forced_s[tid] = p.forced ? (int)p.forced[i] : -1;
-    u_s[tid] = p.uniforms[i];
+  __shared__ float box_s[3 * ETM_MAX_BOX];                         // BOX: normals | forced | log-std of (t, w), dimension a at [a]
+  if constexpr (BOX) {
+    if (me == 0 && tid < p.box.bx.A) {
+      const long long i = (t_now * p.stage_W + w) * p.box.bx.A + tid;
+      box_s[tid] = p.box.normals[i];
+      box_s[ETM_MAX_BOX + tid] = p.box.forced ? p.box.forced[i] : NAN;
+      box_s[2 * ETM_MAX_BOX + tid] = p.box.log_std[tid];
+    }
+  } else {
+    if (me == 0 && tid < p.br.n) {
+      const long long i = (t_now * p.stage_W + w) * p.br.n + tid;
+      forced_s[tid] = p.forced ? (int)p.forced[i] : -1;
+      u_s[tid] = p.uniforms[i];
+    }
   }
   if (tid < D) {
     float v;
@@ -550,23 +561,28 @@ __global__ __launch_bounds__(RF_T) void rollout_trxl_kernel(const RfParams p) {
       const long long t = t_now;
       const int A = p.A, B = p.br.n;
       const long long row = t * p.stage_W + w;
-      int off = 0;
-      for (int b = 0; b < B; ++b) {                                 // per branch: its own logit segment, uniform and forced entry
-        const int Ab = p.br.size[b];
-        float lp;
-        const int a = etm_sample_branch(out_s + off, Ab, u_s[b], forced_s[b], &lp);
-        p.actions[(long long)w * B + b] = a;
-        if (p.host_actions) p.host_actions[(long long)w * B + b] = a;
-        p.st_actions[row * B + b] = a;
-        p.st_logp[row * B + b] = lp;
-        off += Ab;
+      if constexpr (BOX) {                                          // the A means, the step's normals / forced row, clipped hand-over
+        etm_sample_gaussian(out_s, box_s + 2 * ETM_MAX_BOX, p.box.bx, box_s, p.box.forced ? box_s + ETM_MAX_BOX : nullptr, out_s[A], row,
+                            w, p.box.actions, p.box.host_actions, p.box.st_actions, p.st_logp, p.st_values);
+      } else {
+        int off = 0;
+        for (int b = 0; b < B; ++b) {                               // per branch: its own logit segment, uniform and forced entry
+          const int Ab = p.br.size[b];
+          float lp;
+          const int a = etm_sample_branch(out_s + off, Ab, u_s[b], forced_s[b], &lp);
+          p.actions[(long long)w * B + b] = a;
+          if (p.host_actions) p.host_actions[(long long)w * B + b] = a;
+          p.st_actions[row * B + b] = a;
+          p.st_logp[row * B + b] = lp;
+          off += Ab;
+        }
+        p.st_values[row] = out_s[A];
       }
-      p.st_values[row] = out_s[A];
       RF_STAMP(42);
       // this worker's rows are visible before the arrival below -- system scope when the action went to pinned host memory: the
       // host reads it as soon as it sees the flag that the LAST sampler stores, so every sampler's store must have completed at
       // system scope before its arrival (an agent-scope fence does not promise that for host memory)
-      if (p.host_actions) __threadfence_system();
+      if (BOX ? p.box.host_actions != nullptr : p.host_actions != nullptr) __threadfence_system();
       else __threadfence();
       // the last SAMPLER of the step: every team has finished its exchanges, i.e. every workgroup of the launch has read the
       // launch counter and (the samplers) the step counter -- both may move on, and the host may have its actions
@@ -784,15 +800,18 @@ static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, 
                                 int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
                                 int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
                                 int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W,
-                                const int32_t *branch_sizes, int n_branches, void *stream) {
+                                const int32_t *branch_sizes, int n_branches, const RfBox *box, void *stream) {
   (void)hipGetLastError();
   if (ss && (!mask_table || !index_table || !st_mask || !st_idx || !latch || !mask_t || !win_t || T <= 0)) return ETM_EINVAL;
   if (!ss && (!win || !mask)) return ETM_EINVAL;
-  if (!h_in || !wemb_t || !bemb || !blocks || !kv || !items || !wh_t || !bh || !wp || !bp || !wv || !bv || !uniforms ||
-      !t_dev || !actions || !st_actions || !st_logp || !st_values || !sync_counter || !scratch)
+  // (a Box policy's action tables are the float ones of `box`; the int64 ones are unused then)
+  const bool tables = box ? (box->log_std && box->normals && box->actions && box->st_actions) : (uniforms && actions && st_actions);
+  if (!h_in || !wemb_t || !bemb || !blocks || !kv || !items || !wh_t || !bh || !wp || !bp || !wv || !bv || !tables ||
+      !t_dev || !st_logp || !st_values || !sync_counter || !scratch)
     return ETM_EINVAL;
   if (W <= 0 || nb <= 0 || D <= 0 || H <= 0 || L <= 0 || hid <= 0 || A <= 0 || stage_W < W || D % H != 0) return ETM_EINVAL;
-  if (host_flag && !host_actions) return ETM_EINVAL;
+  if (host_flag && !(box ? (const void *)box->host_actions : (const void *)host_actions)) return ETM_EINVAL;
+  if (box && (box->bx.A != A || A > ETM_MAX_BOX)) return ETM_EUNSUPPORTED;
   if (wkv && (!step_l || !slot_l || !bank)) return ETM_EINVAL;
   if (h_splits < 0 || h_splits > RF_MAXSPLIT || (h_splits > 0 && !h_bias)) return ETM_EINVAL;
   const int P = etm_rollout_trxl_team(H);
@@ -805,6 +824,7 @@ static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, 
   }
   RfParams p{};
   if (const int rc = etm_branches_make(branch_sizes, n_branches, A, &p.br)) return rc;
+  if (box) p.box = *box;                               // (RfParams{}: box.bx.A == 0 selects the categorical instantiations)
   p.ss = (const long long *)ss; p.mask_table = mask_table; p.index_table = (const long long *)index_table; p.st_mask = st_mask;
   p.st_idx = (long long *)st_idx; p.latch = (long long *)latch; p.t_row = (long long *)t_row; p.mask_t = mask_t; p.win_t = (long long *)win_t;
   p.kv_init = kv_init; p.T = T;
@@ -837,11 +857,14 @@ static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, 
   const dim3 grid((unsigned)etm_rollout_trxl_grid(W, H)), block(RF_T);
   // rows per thread of the per-block product slices: 20 registers x 4 are enough at D = 384, 32 at D = 512
   const bool small = rf_rows(D, H) == 20;
-  const bool gen = pre_ln || gtrxl;
+  const bool gen = pre_ln || gtrxl, box_k = p.box.bx.A > 0;
 #define RF_LAUNCH(GR_, LM_)                                                                                      \
   do {                                                                                                           \
-    if (gen) hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, true>), grid, block, 0, st, p);                   \
-    else hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, false>), grid, block, 0, st, p);                      \
+    if (box_k) {                                                                                                 \
+      if (gen) hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, true, true>), grid, block, 0, st, p);           \
+      else hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, false, true>), grid, block, 0, st, p);              \
+    } else if (gen) hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, true, false>), grid, block, 0, st, p);     \
+    else hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, false, false>), grid, block, 0, st, p);               \
   } while (0)
   if (L <= 64) {
     if (small) RF_LAUNCH(20, 64);
@@ -867,7 +890,7 @@ extern "C" int etm_rollout_trxl(const float *h_in, const float *wemb_t, const fl
   return rollout_trxl_impl(0, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
                           actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
                           slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
-                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, nullptr, 1, stream);
+                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, nullptr, 1, nullptr, stream);
 }
 // The group form (csrc/rollout_group.hip): same arguments, other matrix packings (see there) and scratch size
 // (etm_rollout_trxl_group_scratch_bytes); W <= 8 workers, GRU-gated blocks -- etm_rollout_trxl_group_supported.
@@ -884,7 +907,7 @@ extern "C" int etm_rollout_trxl_group(const float *h_in, const float *wemb_t, co
   return rollout_trxl_impl(1, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
                           actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
                           slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
-                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, nullptr, 1, stream);
+                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, nullptr, 1, nullptr, stream);
 }
 
 // MultiDiscrete policies: the same two launches with the action branches given by their sizes (wp / bp = the branches' heads
@@ -904,7 +927,7 @@ extern "C" int etm_rollout_trxl_branched(const float *h_in, const float *wemb_t,
                           actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
                           slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
                           latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, etm_branches_total(branch_sizes, n_branches), stage_W,
-                          branch_sizes, n_branches, stream);
+                          branch_sizes, n_branches, nullptr, stream);
 }
 extern "C" int etm_rollout_trxl_group_branched(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
                                 int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
@@ -921,7 +944,7 @@ extern "C" int etm_rollout_trxl_group_branched(const float *h_in, const float *w
                           actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
                           slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
                           latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, etm_branches_total(branch_sizes, n_branches), stage_W,
-                          branch_sizes, n_branches, stream);
+                          branch_sizes, n_branches, nullptr, stream);
 }
 extern "C" int etm_rollout_trxl_supported_branched(int D, int H, int L, int hid, const int32_t *branch_sizes, int n_branches, int nb) {
   const int A = etm_branches_total(branch_sizes, n_branches);
@@ -931,4 +954,56 @@ extern "C" int etm_rollout_trxl_group_supported_branched(int D, int H, int L, in
                                                          int W, int gtrxl) {
   const int A = etm_branches_total(branch_sizes, n_branches);
   return A > 0 && etm_rollout_trxl_group_supported(D, H, L, hid, A, nb, W, gtrxl);
+}
+
+// Box policies (diagonal Gaussian, A <= 8 dimensions): the same two launches with the A means as the policy head (wp [A, hid], bp [A]),
+// the draw of etm_sample_gaussian (normals / forced / st_actions [S, stage_W, A], NaN forced = "sample"; actions / host_actions [W, A]
+// receive the actions clipped to [low, high], HOST arrays of A floats or NULL = unbounded) and log_std [A] on the device.
+static int rollout_trxl_gaussian_impl(int group, const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb,
+                                      float *kv, int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask,
+                                      float *items, const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv,
+                                      const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev,
+                                      float *actions, float *st_actions, float *st_logp, float *st_values, float *host_actions,
+                                      int64_t *host_flag, int32_t *sync_counter, float ln_eps, void *scratch, int64_t scratch_bytes,
+                                      const float *wkv, const float *pos, const int64_t *step_l, const int64_t *slot_l, float *bank,
+                                      int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
+                                      int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table,
+                                      uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,
+                                      const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A,
+                                      int stage_W, const float *low, const float *high, void *stream) {
+  RfBox box{};
+  if (const int rc = etm_box_make(low, high, A, &box.bx)) return rc;
+  box.log_std = log_std; box.normals = normals; box.forced = forced;
+  box.actions = actions; box.st_actions = st_actions; box.host_actions = host_actions;
+  return rollout_trxl_impl(group, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv,
+                           nullptr, nullptr, t_dev, nullptr, nullptr, st_logp, st_values, nullptr, host_flag, sync_counter, ln_eps, scratch,
+                           scratch_bytes, wkv, pos, step_l, slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits,
+                           ss, mask_table, index_table, st_mask, st_idx, latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid,
+                           A, stage_W, nullptr, 1, &box, stream);
+}
+#define RF_GAUSSIAN_ARGS                                                                                                                   \
+  const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv, int64_t kv_worker_stride,      \
+      int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items, const float *wh_t, const float *bh, const float *wp,   \
+      const float *bp, const float *wv, const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev, \
+      float *actions, float *st_actions, float *st_logp, float *st_values, float *host_actions, int64_t *host_flag,                       \
+      int32_t *sync_counter, float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos,                      \
+      const int64_t *step_l, const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride,                       \
+      int64_t bank_block_stride, const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table,                        \
+      const int64_t *index_table, uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,    \
+      const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W, const float *low,     \
+      const float *high, void *stream
+#define RF_GAUSSIAN_PASS                                                                                                                   \
+  h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, log_std, normals,     \
+      forced, t_dev, actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, \
+      pos, step_l, slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table,    \
+      st_mask, st_idx, latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, low, high, stream
+extern "C" int etm_rollout_trxl_gaussian(RF_GAUSSIAN_ARGS) { return rollout_trxl_gaussian_impl(0, RF_GAUSSIAN_PASS); }
+extern "C" int etm_rollout_trxl_group_gaussian(RF_GAUSSIAN_ARGS) { return rollout_trxl_gaussian_impl(1, RF_GAUSSIAN_PASS); }
+#undef RF_GAUSSIAN_ARGS
+#undef RF_GAUSSIAN_PASS
+extern "C" int etm_rollout_trxl_supported_gaussian(int D, int H, int L, int hid, int A, int nb) {
+  return A > 0 && A <= ETM_MAX_BOX && etm_rollout_trxl_supported(D, H, L, hid, A, nb);
+}
+extern "C" int etm_rollout_trxl_group_supported_gaussian(int D, int H, int L, int hid, int A, int nb, int W, int gtrxl) {
+  return A > 0 && A <= ETM_MAX_BOX && etm_rollout_trxl_group_supported(D, H, L, hid, A, nb, W, gtrxl);
 }

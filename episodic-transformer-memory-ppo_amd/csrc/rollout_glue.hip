@@ -91,6 +91,60 @@ __global__ __launch_bounds__(1024) void rollout_sample_kernel(const float *__res
   if (threadIdx.x == 0) *t_dev = t + 1;
 }
 
+// Box policies (etm_sample_gaussian): one thread per worker, the A means of row w of `mean`, its A normals / forced entries of
+// step t (time-major [S, W, A]; NaN forced = "sample"); staging of the raw x, log p(x), the value; actions [W, A] = clip(x); t += 1.
+__global__ __launch_bounds__(1024) void rollout_sample_gaussian_kernel(const float *__restrict__ mean, const float *__restrict__ value,
+                                                                       const float *__restrict__ log_std, const float *__restrict__ normals,
+                                                                       const float *__restrict__ forced, long long *__restrict__ t_dev,
+                                                                       float *__restrict__ actions, float *__restrict__ st_actions,
+                                                                       float *__restrict__ st_logp, float *__restrict__ st_values, int W,
+                                                                       const EtmBox bx) {
+  const long long t = *t_dev;
+  const int A = bx.A;
+  for (int w = threadIdx.x; w < W; w += 1024) {
+    const long long row = t * W + w;
+    etm_sample_gaussian(mean + (long long)w * A, log_std, bx, normals + row * A, forced ? forced + row * A : nullptr, value[w], row, w,
+                        actions, nullptr, st_actions, st_logp, st_values);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) *t_dev = t + 1;
+}
+
+// The A + 1 outputs of the rollout heads of worker w into out_s (logits or means, then the value): one wave per output.
+__device__ __forceinline__ void policy_heads_lds(const float *__restrict__ h, const float *__restrict__ wp, const float *__restrict__ bp,
+                                                 const float *__restrict__ wv, const float *__restrict__ bv, const float *__restrict__ h_bias,
+                                                 float *out_s, int w, int A, int hid) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int o = wave; o < A + 1; o += 4) {
+    const int xo = (o < A ? 0 : hid);
+    const float *x = h + (long long)w * 2 * hid + xo;
+    const float *wt = (o < A) ? wp + (long long)o * hid : wv;
+    float s = 0.f;
+    if (h_bias) {     // h holds the pre-activations of the hidden heads: relu(h + h_bias) on the fly (model.py:106-107)
+      for (int c = lane; c < hid; c += 64) s += fmaxf(x[c] + h_bias[xo + c], 0.f) * wt[c];
+    } else {
+      for (int c = lane; c < hid; c += 64) s += x[c] * wt[c];
+    }
+    s = wave_sum(s);
+    if (lane == 0) out_s[o] = s + (o < A ? bp[o] : bv[0]);
+  }
+}
+
+// After a worker's rows are staged: its arrival; the LAST workgroup of the step advances the step counter and, with host_flag,
+// publishes it to the host after ONE system-scope release.
+__device__ __forceinline__ void policy_arrive(bool to_host, long long t, long long *t_dev, long long *host_flag, int *sync_counter, int W) {
+  if (to_host) __threadfence_system();                 // (host memory: see rollout_fused.hip) this worker's rows are visible before
+  else __threadfence();                                // the arrival below
+  if (atomicAdd(sync_counter, 1) == W - 1) {           // last workgroup of the step
+    *sync_counter = 0;
+    *t_dev = t + 1;
+    if (host_flag) {
+      __threadfence_system();
+      __hip_atomic_store(host_flag, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
 // Output heads + sampling of a policy (every action branch) in ONE launch (rollout_heads_kernel + rollout_sample_kernel): one
 // workgroup per worker, one wave per output (A logits + the value; a single workgroup looping over all W (A + 1) dot products
 // took 19 us, each pass being one global-memory round trip), then lane 0 samples.  The step counter is advanced by the LAST
@@ -107,36 +161,39 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel(const float *__rest
                                                              long long *host_actions, long long *host_flag, int *sync_counter,
                                                              int W, int A, int hid, int stage_W, const EtmBranches br) {
   extern __shared__ float out_s[];   // [A + 1]: logits (the branches' segments side by side), then the value
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w = blockIdx.x;
+  const int w = blockIdx.x;
   const long long t = *t_dev;
-  for (int o = wave; o < A + 1; o += 4) {
-    const int xo = (o < A ? 0 : hid);
-    const float *x = h + (long long)w * 2 * hid + xo;
-    const float *wt = (o < A) ? wp + (long long)o * hid : wv;
-    float s = 0.f;
-    if (h_bias) {     // h holds the pre-activations of the hidden heads: relu(h + h_bias) on the fly (model.py:106-107)
-      for (int c = lane; c < hid; c += 64) s += fmaxf(x[c] + h_bias[xo + c], 0.f) * wt[c];
-    } else {
-      for (int c = lane; c < hid; c += 64) s += x[c] * wt[c];
-    }
-    s = wave_sum(s);
-    if (lane == 0) out_s[o] = s + (o < A ? bp[o] : bv[0]);
-  }
+  policy_heads_lds(h, wp, bp, wv, bv, h_bias, out_s, w, A, hid);
   __syncthreads();
   if (threadIdx.x == 0) {
     // forced / uniforms / staging: time-major [S, stage_W, B] (B = 1: [S, stage_W]); negative forced entry = "sample"
     etm_sample_branches(out_s, br, t * stage_W + w, w, uniforms, forced, actions, host_actions, st_actions, st_logp);
     st_values[t * stage_W + w] = out_s[A];
-    if (host_actions) __threadfence_system();            // (host memory: see rollout_fused.hip) this worker's rows are visible before
-    else __threadfence();                                // the arrival below
-    if (atomicAdd(sync_counter, 1) == W - 1) {           // last workgroup of the step
-      *sync_counter = 0;
-      *t_dev = t + 1;
-      if (host_flag) {
-        __threadfence_system();
-        __hip_atomic_store(host_flag, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
+    policy_arrive(host_actions != nullptr, t, t_dev, host_flag, sync_counter, W);
+  }
+}
+
+// The same launch for a Box policy: the A outputs are the Gaussian's means; the draw of etm_sample_gaussian with the normals /
+// forced rows [S, stage_W, A] of (t, w); host_actions [W, A] (pinned) receives the clipped actions before the flag.
+__global__ __launch_bounds__(256) void rollout_policy_gaussian_kernel(const float *__restrict__ h, const float *__restrict__ wp,
+                                                                      const float *__restrict__ bp, const float *__restrict__ wv,
+                                                                      const float *__restrict__ bv, const float *__restrict__ h_bias,
+                                                                      const float *__restrict__ log_std, const float *__restrict__ normals,
+                                                                      const float *__restrict__ forced, long long *__restrict__ t_dev,
+                                                                      float *__restrict__ actions, float *__restrict__ st_actions,
+                                                                      float *__restrict__ st_logp, float *__restrict__ st_values,
+                                                                      float *host_actions, long long *host_flag, int *sync_counter,
+                                                                      int W, int hid, int stage_W, const EtmBox bx) {
+  __shared__ float out_s[ETM_MAX_BOX + 1];
+  const int w = blockIdx.x, A = bx.A;
+  const long long t = *t_dev;
+  policy_heads_lds(h, wp, bp, wv, bv, h_bias, out_s, w, A, hid);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const long long row = t * stage_W + w;
+    etm_sample_gaussian(out_s, log_std, bx, normals + row * A, forced ? forced + row * A : nullptr, out_s[A], row, w, actions,
+                        host_actions, st_actions, st_logp, st_values);
+    policy_arrive(host_actions != nullptr, t, t_dev, host_flag, sync_counter, W);
   }
 }
 
@@ -266,6 +323,40 @@ extern "C" int etm_rollout_policy_branched(const float *h, const float *h_bias, 
   return rollout_policy_impl(h, h_bias, wp, bp, wv, bv, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions,
                              host_flag, sync_counter, W, etm_branches_total(branch_sizes, n_branches), hid, stage_W, branch_sizes,
                              n_branches, stream);
+}
+
+extern "C" int etm_rollout_sample_gaussian(const float *mean, const float *value, const float *log_std, const float *normals,
+                                           const float *forced, int64_t *t_dev, float *actions, float *st_actions, float *st_logp,
+                                           float *st_values, const float *low, const float *high, int W, int A, void *stream) {
+  (void)hipGetLastError();
+  if (!mean || !value || !log_std || !normals || !t_dev || !actions || !st_actions || !st_logp || !st_values || W <= 0) return ETM_EINVAL;
+  EtmBox bx;
+  if (const int rc = etm_box_make(low, high, A, &bx)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  EtmProfScope prof(ETM_K_ROLLOUT_SAMPLE, st);
+  hipLaunchKernelGGL(rollout_sample_gaussian_kernel, dim3(1), dim3(1024), 0, st, mean, value, log_std, normals, forced, (long long *)t_dev,
+                     actions, st_actions, st_logp, st_values, W, bx);
+  return etm_launch_status();
+}
+
+extern "C" int etm_rollout_policy_gaussian(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv,
+                                           const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev,
+                                           float *actions, float *st_actions, float *st_logp, float *st_values, float *host_actions,
+                                           int64_t *host_flag, int32_t *sync_counter, const float *low, const float *high, int W, int A,
+                                           int hid, int stage_W, void *stream) {
+  (void)hipGetLastError();
+  if (!h || !wp || !bp || !wv || !bv || !log_std || !normals || !t_dev || !actions || !st_actions || !st_logp || !st_values ||
+      !sync_counter || W <= 0 || hid <= 0 || stage_W < W)
+    return ETM_EINVAL;
+  if (host_flag && !host_actions) return ETM_EINVAL;
+  EtmBox bx;
+  if (const int rc = etm_box_make(low, high, A, &bx)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  EtmProfScope prof(ETM_K_ROLLOUT_SAMPLE, st);
+  hipLaunchKernelGGL(rollout_policy_gaussian_kernel, dim3((unsigned)W), dim3(256), 0, st, h, wp, bp, wv, bv, h_bias, log_std, normals, forced,
+                     (long long *)t_dev, actions, st_actions, st_logp, st_values, host_actions, (long long *)host_flag, (int *)sync_counter,
+                     W, hid, stage_W, bx);
+  return etm_launch_status();
 }
 
 extern "C" int etm_rollout_heads(const float *h, const float *wp, const float *bp, const float *wv, const float *bv, float *logits,

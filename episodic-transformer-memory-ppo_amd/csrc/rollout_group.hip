@@ -168,7 +168,8 @@ __device__ __forceinline__ void ln_rows(const float *src_s, float *dst_s, int D,
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // KM = D / 32 (MFMA steps per wave and chunk), LMAX: window rows the K / V registers of a unit are sized for
-template <int KM, int LMAX>
+// BOX: a Box policy's Gaussian draw (etm_sample_gaussian, float tables p.box) instead of the categorical branches.
+template <int KM, int LMAX, bool BOX>
 __global__ __launch_bounds__(RF_T) void rollout_group_kernel(const RfParams p) {
   constexpr int GR = 20;                                          // tail: rows of a K | V projection slice per thread and batch
   constexpr int KR = LMAX / RF_WAVES, VR = LMAX / 16;
@@ -623,10 +624,17 @@ __global__ __launch_bounds__(RF_T) void rollout_group_kernel(const RfParams p) {
     if (tid < W) {                                                   // sampling + staging + hand-over of worker tid (as rollout_policy_kernel)
       const long long t = t_now;
       const float *lg = out_s + tid * 16;
-      // per branch: its own logit segment, uniform and forced entry ([S, stage_W, B] tables; B = 1: [S, stage_W])
-      etm_sample_branches(lg, p.br, t * p.stage_W + tid, tid, p.uniforms, p.forced, p.actions, p.host_actions, p.st_actions, p.st_logp);
-      p.st_values[t * p.stage_W + tid] = lg[A];
-      if (p.host_actions) __threadfence_system();
+      if constexpr (BOX) {
+        // the A means; the normals / forced row [S, stage_W, A] of (t, tid); clipped hand-over
+        const long long row = t * p.stage_W + tid;
+        etm_sample_gaussian(lg, p.box.log_std, p.box.bx, p.box.normals + row * A, p.box.forced ? p.box.forced + row * A : nullptr, lg[A],
+                            row, tid, p.box.actions, p.box.host_actions, p.box.st_actions, p.st_logp, p.st_values);
+      } else {
+        // per branch: its own logit segment, uniform and forced entry ([S, stage_W, B] tables; B = 1: [S, stage_W])
+        etm_sample_branches(lg, p.br, t * p.stage_W + tid, tid, p.uniforms, p.forced, p.actions, p.host_actions, p.st_actions, p.st_logp);
+        p.st_values[t * p.stage_W + tid] = lg[A];
+      }
+      if (BOX ? p.box.host_actions != nullptr : p.host_actions != nullptr) __threadfence_system();
       else __threadfence();
     }
     __syncthreads();                                                 // every sampler's stores are complete (and fenced)
@@ -708,9 +716,10 @@ int etm_rf_launch_group(const RfParams &p, hipStream_t st) {
   const dim3 grid(RG_WG), block(RF_T);
   const size_t lds = rg_lds_bytes(p.D, p.nb);
   if (lds + 8192 > 160 * 1024) return ETM_EUNSUPPORTED;
+  const bool box = p.box.bx.A > 0;
 #define RG_LAUNCH(KM_, LM_)                                                                                                   \
   do {                                                                                                                        \
-    auto kern = rollout_group_kernel<KM_, LM_>;                                                                               \
+    auto kern = box ? rollout_group_kernel<KM_, LM_, true> : rollout_group_kernel<KM_, LM_, false>;                           \
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
     hipLaunchKernelGGL(kern, grid, block, lds, st, p);                                                                        \
   } while (0)

@@ -24,6 +24,16 @@ struct RfBlock {
   const float *nkv_g, *nkv_b;        // pre-LN only: norm_kv of the memory rows (applied by the tail before the K | V projection)
 };
 constexpr int RF_BLOCK_PTRS = 19;
+// The float action tables of a Box policy (the BOX forms of the step kernels; etm_sample_gaussian): A = box.bx.A means are the
+// policy-head outputs; uniforms / forced / actions / st_actions / host_actions of RfParams are unused then.
+struct RfBox {
+  const float *log_std;              // [A]
+  const float *normals, *forced;     // time-major [S, stage_W, A]; forced: NaN = "sample" (optional)
+  float *actions, *st_actions;       // [W, A] clipped, [S, stage_W, A] raw
+  float *host_actions;               // pinned [W, A] (clipped) or nullptr
+  EtmBox bx;
+};
+
 struct RfParams {
   const float *h_in;                 // [W, D] input of the transformer (model.py:96-100 output), or, with h_splits > 0, the
   const float *h_bias;               // [h_splits, W, D] K-slice sums of etm_rollout_hidden_partial: input = relu(sum + h_bias)
@@ -68,6 +78,7 @@ struct RfParams {
   EtmBranches br;                    // action branches: segments of the A = sum(sizes) logit columns (one branch: Discrete)
   int map_mode;                      // block -> (worker, member) placement, see etm_rollout_trxl_set_placement
   float eps, sqrt_d;
+  RfBox box;                         // Box policies only (the BOX instantiations): the float action tables
 };
 
 namespace {

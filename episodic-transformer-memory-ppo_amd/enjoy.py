@@ -13,7 +13,7 @@ import pickle
 import numpy as np
 import torch
 
-from environments import action_space_shape
+from environments import action_space_kind
 from model import ActorCriticModel
 from trainer import build_window_tables
 from utils import create_env
@@ -42,7 +42,11 @@ def run_episode(model, env, config, device, max_steps=None):
             env.render()
         policy, _value, new_memory = model(obs_t, in_memory, mask, indices)
         memory[:, t] = new_memory.detach()
-        action = [branch.sample().item() for branch in policy]
+        if getattr(model, "continuous", False):      # Box: one Gaussian draw of A dimensions, clipped to the space's bounds
+            a = policy[0].sample()[0].cpu().numpy()
+            action = np.clip(a, env.action_space.low, env.action_space.high).astype(np.float32)
+        else:
+            action = [branch.sample().item() for branch in policy]
         obs, reward, done, info = env.step(action)
         rewards.append(reward)
         t += 1
@@ -59,7 +63,8 @@ def main():
     with open(args.model, "rb") as f:
         state_dict, config = pickle.load(f)
     env = create_env(config["environment"], render=True)
-    model = ActorCriticModel(config, env.observation_space, action_space_shape(env.action_space), env.max_episode_steps)
+    kind = action_space_kind(env.action_space)
+    model = ActorCriticModel(config, env.observation_space, kind.shape, env.max_episode_steps, continuous=kind.is_box)
     model.load_state_dict(state_dict)
     model.to(device)
     model.eval()

@@ -11,3 +11,37 @@ def action_space_shape(space):
             raise ValueError(f"MultiDiscrete action space with nvec {list(shape)}: every branch needs at least one action")
         return shape
     return (int(space.n),)
+
+
+class ActionKind:
+    """The kind of an action space: ``kind`` is "discrete", "multidiscrete" or "box"; ``shape`` is ``action_space_shape`` for the
+    first two and ``(A,)`` for a Box; ``low`` / ``high`` (Box only) are float32 arrays of A bounds."""
+
+    def __init__(self, kind, shape, low=None, high=None):
+        self.kind, self.shape, self.low, self.high = kind, tuple(int(a) for a in shape), low, high
+
+    @property
+    def is_box(self):
+        return self.kind == "box"
+
+    def __repr__(self):
+        return f"ActionKind({self.kind!r}, {self.shape})"
+
+
+def action_space_kind(space):
+    """Discrete (``n``), MultiDiscrete (``nvec``) or Box (``low``, ``high`` and a 1-D ``shape``, neither ``n`` nor ``nvec``): an
+    ``ActionKind``.  A Box whose shape is not 1-D raises ValueError."""
+    if getattr(space, "nvec", None) is not None:
+        return ActionKind("multidiscrete", action_space_shape(space))
+    if getattr(space, "n", None) is None and hasattr(space, "low") and hasattr(space, "high") and hasattr(space, "shape"):
+        import numpy as np
+        shape = tuple(int(a) for a in space.shape)
+        if len(shape) != 1 or shape[0] <= 0:
+            raise ValueError(f"Box action space of shape {shape}: only 1-D Box spaces (one vector of A actions) are supported")
+        A = shape[0]
+        low = np.broadcast_to(np.asarray(space.low, dtype=np.float32), (A,)).copy()
+        high = np.broadcast_to(np.asarray(space.high, dtype=np.float32), (A,)).copy()
+        if not np.all(low <= high):
+            raise ValueError(f"Box action space with low {low.tolist()} above high {high.tolist()}")
+        return ActionKind("box", (A,), low, high)
+    return ActionKind("discrete", action_space_shape(space))

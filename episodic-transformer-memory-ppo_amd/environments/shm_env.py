@@ -216,7 +216,7 @@ def _probe_env(env_config):
     """(observation shape, number of actions, max_episode_steps) of the configured environment."""
     if env_config["type"] == "Synthetic":
         from environments.synthetic import SyntheticEnv
-        keys = ("obs_shape", "num_actions", "max_episode_steps")
+        keys = ("obs_shape", "num_actions", "max_episode_steps", "continuous_actions", "action_low", "action_high")
         kw = {k: env_config[k] for k in keys if k in env_config}
         if "obs_shape" in kw:
             kw["obs_shape"] = tuple(kw["obs_shape"])
@@ -224,8 +224,14 @@ def _probe_env(env_config):
     else:
         from utils import create_env
         e = create_env(env_config)
-    from environments import action_space_shape
-    branches = action_space_shape(e.action_space)
+    from environments import action_space_kind
+    kind = action_space_kind(e.action_space)
+    if kind.is_box:
+        e.close()
+        raise NotImplementedError(f"worker_processes supports Discrete action spaces only, not this Box of {kind.shape[0]} continuous "
+                                  "actions: the shared segment carries one integer action word per environment and the native rollout "
+                                  "driver hands over one; set worker_processes: false (in-process environments take Box spaces)")
+    branches = kind.shape
     if len(branches) > 1:
         e.close()
         raise NotImplementedError(f"worker_processes supports single-branch (Discrete) action spaces only, not the {len(branches)} "

@@ -11,7 +11,9 @@ Two forms that generate *identical* streams:
   (one call per rollout step for all workers, observations written straight
   into a caller-provided -- normally pinned -- host buffer).
 
-``num_actions``: an int (Discrete) or a list (MultiDiscrete: ``action_space.nvec``, one branch per entry).  Actions do not drive
+``num_actions``: an int (Discrete) or a list (MultiDiscrete: ``action_space.nvec``, one branch per entry).  ``continuous_actions``:
+an int A (Box of A dimensions, bounds ``action_low`` / ``action_high``: scalars or A-lists, default -1 / 1); ``num_actions`` is not
+used then.  Actions do not drive
 the synthetic dynamics: the observation, reward and done streams are the same for every action space.
 
 Workload (BASELINE.md section 3 / SURVEY.md section 8d): observation ~ U[0,1) float32 of
@@ -120,13 +122,26 @@ def _branches(num_actions):
     return (int(num_actions),), None
 
 
+def _box_space(continuous_actions, action_low, action_high):
+    """The Box action space of a ``continuous_actions`` setting (gym's Box fields: low, high, shape = (A,)), or None."""
+    if continuous_actions is None:
+        return None
+    A = int(continuous_actions)
+    if A <= 0:
+        raise ValueError(f"continuous_actions {continuous_actions}: a Box needs at least one dimension")
+    low = np.broadcast_to(np.asarray(action_low, dtype=np.float32), (A,)).copy()
+    high = np.broadcast_to(np.asarray(action_high, dtype=np.float32), (A,)).copy()
+    return SimpleNamespace(low=low, high=high, shape=(A,), dtype=np.float32)
+
+
 class SyntheticEnv:
     """Single env, reference env API.  ``worker_id`` selects the RNG stream."""
 
     def __init__(self, obs_shape=(3, 84, 84), num_actions=3, max_episode_steps=96, seed=0, worker_id=0,
-                 p_reward=0.05, p_done=0.02, pool=64):
+                 p_reward=0.05, p_done=0.02, pool=64, continuous_actions=None, action_low=-1.0, action_high=1.0):
         self._shape = tuple(obs_shape)
         self._branches, self._nvec = _branches(num_actions)
+        self._box = _box_space(continuous_actions, action_low, action_high)
         self._T = int(max_episode_steps)
         self._p_r, self._p_d = float(p_reward), float(p_done)
         self._s = _WorkerStream(worker_id, self._shape, seed, pool)
@@ -141,6 +156,8 @@ class SyntheticEnv:
 
     @property
     def action_space(self):
+        if self._box is not None:        # (as gym's Box: low, high, shape = (A,))
+            return self._box
         if self._nvec is not None:       # (as gym's MultiDiscrete: nvec, shape = (branches,))
             return SimpleNamespace(nvec=np.array(self._nvec, dtype=np.int64), shape=(len(self._nvec),))
         return SimpleNamespace(n=self._branches[0])
@@ -181,7 +198,7 @@ class SyntheticVecEnv:
 
     def __init__(self, num_envs, obs_shape=(3, 84, 84), num_actions=3, max_episode_steps=96, seed=0,
                  p_reward=0.05, p_done=0.02, pool=64, first_worker_id=0, copy_threads=1, row_chunks=None, step_cost_us=0.0, min_chunked_envs=None,
-                 gen_threads=1):
+                 gen_threads=1, continuous_actions=None, action_low=-1.0, action_high=1.0):
         """``copy_threads`` > 1: the observation rows of a step are written by that many threads (the kernel library's host
         copier; the reference's workers write theirs in n_workers processes) instead of one numpy copy.  ``pool`` = 0: every row is a
         fresh draw of its worker's generator (module docstring); ``gen_threads`` > 1: drawn by that many threads."""
@@ -200,6 +217,13 @@ class SyntheticVecEnv:
         self.num_actions = sum(self.action_space_shape)
         self.action_space = (SimpleNamespace(nvec=np.array(nvec, dtype=np.int64), shape=(len(nvec),)) if nvec is not None
                              else SimpleNamespace(n=self.num_actions))
+        box = _box_space(continuous_actions, action_low, action_high)
+        if box is not None:                                          # Box: float action rows [W, A]
+            self.action_space = box
+            self.action_space_shape = box.shape
+            self.num_actions = box.shape[0]
+        from environments import action_space_kind
+        self.action_kind = action_space_kind(self.action_space)
         self.max_episode_steps = int(max_episode_steps)
         self._p_r, self._p_d = float(p_reward), float(p_done)
         self._pool = pool

@@ -3,7 +3,10 @@
 ``VecEnv`` protocol (what ``PPOTrainer`` steps):
     num_envs, observation_space_shape, action_space_shape, num_actions, max_episode_steps
         action_space_shape: one entry per action branch (environments.action_space_shape: ``nvec`` of a MultiDiscrete space,
-        ``(n,)`` of a Discrete one); num_actions: n of a Discrete space, the sum of ``nvec`` (the policy's logits) otherwise
+        ``(n,)`` of a Discrete one, ``(A,)`` of a Box); num_actions: n of a Discrete space, the sum of ``nvec`` (the policy's
+        logits), A of a Box
+    action_kind (optional; absent = discrete / multidiscrete by action_space_shape): environments.ActionKind, with the bounds of
+        a Box (float action rows [W, A], clipped to them before they arrive)
     reset(out=None) -> obs [W, *obs_shape] float32
     step(actions [W] or [W, B], out=None, on_rows=None) -> (obs, rewards [W] f32, dones [W] bool, infos [W] (dict or None))
         on_rows(lo, hi), optional: called as soon as observation rows [lo, hi) of ``out`` are final, in increasing order and
@@ -17,7 +20,7 @@ is exactly what upstream's loop does by hand (trainer.py:195-201).
 """
 import numpy as np
 
-from environments import action_space_shape
+from environments import action_space_kind
 
 
 class _VecBase:
@@ -44,7 +47,8 @@ class SerialVecEnv(_VecBase):
         self.num_envs = len(self.envs)
         e = self.envs[0]
         self.observation_space_shape = tuple(e.observation_space.shape)
-        self.action_space_shape = action_space_shape(e.action_space)
+        self.action_kind = action_space_kind(e.action_space)
+        self.action_space_shape = self.action_kind.shape
         self.num_actions = sum(self.action_space_shape)
         self.max_episode_steps = int(e.max_episode_steps)
 
@@ -84,7 +88,8 @@ class PipeVecEnv(_VecBase):
         from worker import Worker
         probe = create_env(env_config)
         self.observation_space_shape = tuple(probe.observation_space.shape)
-        self.action_space_shape = action_space_shape(probe.action_space)
+        self.action_kind = action_space_kind(probe.action_space)
+        self.action_space_shape = self.action_kind.shape
         self.num_actions = sum(self.action_space_shape)
         self.max_episode_steps = int(probe.max_episode_steps)
         probe.close()
@@ -149,6 +154,7 @@ class CompositeVecEnv(_VecBase):
         e = self.parts[0]
         self.observation_space_shape = tuple(e.observation_space_shape)
         self.action_space_shape = tuple(getattr(e, "action_space_shape", None) or (int(e.num_actions),))
+        self.action_kind = getattr(e, "action_kind", None) or (action_space_kind(e.action_space) if hasattr(e, "action_space") else None)
         self.num_actions = int(e.num_actions)
         self.max_episode_steps = int(e.max_episode_steps)
 
@@ -183,7 +189,8 @@ def make_vec_env(env_config: dict, num_envs: int, first_worker_id: int = 0, grou
         return CompositeVecEnv([make_vec_env(env_config, per, first_worker_id + g * per) for g in range(groups)])
     if env_config["type"] == "Synthetic":
         from environments.synthetic import SyntheticVecEnv
-        keys = ("obs_shape", "num_actions", "max_episode_steps", "seed", "p_reward", "p_done", "pool", "copy_threads", "row_chunks", "step_cost_us", "gen_threads")
+        keys = ("obs_shape", "num_actions", "max_episode_steps", "seed", "p_reward", "p_done", "pool", "copy_threads", "row_chunks", "step_cost_us", "gen_threads",
+                "continuous_actions", "action_low", "action_high")
         kw = {k: env_config[k] for k in keys if k in env_config}
         if "obs_shape" in kw:
             kw["obs_shape"] = tuple(kw["obs_shape"])

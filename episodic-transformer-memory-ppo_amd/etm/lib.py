@@ -7,7 +7,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: torch ships its ow
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libetm_hip.so")     # (diagnostic tools that load another build assign this before load())
-ABI_VERSION = 48
+ABI_VERSION = 49
 
 _lib = None
 
@@ -37,6 +37,7 @@ SIGNATURES = {
     "etm_rollout_window": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
     "etm_rollout_sample": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "etm_rollout_sample_branched": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
+    "etm_rollout_sample_gaussian": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "etm_add_layernorm": (_I, [_P, _P, _I, _P, _P, _P, _F, _P, _I, _I, _P]),
     "etm_conv_relu": (_I, [_P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "etm_upload": (_I, [_P, _P, _L, _P]),
@@ -52,6 +53,7 @@ SIGNATURES = {
     "etm_comm_destroy": (_I, [_P]),
     "etm_rollout_policy": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "etm_rollout_policy_branched": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P]),
+    "etm_rollout_policy_gaussian": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "etm_conv_pack_weights": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "etm_gather_rows": (_I, [_P, _P, _P, _I, _P, _L, _L, _P]),
     "etm_group_norms": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P]),
@@ -80,7 +82,15 @@ SIGNATURES = {
                                              _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I,
                                              _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "etm_rollout_trxl_group_supported": (_I, [_I] * 8),
+    "etm_rollout_trxl_gaussian": (_I, [_P, _P, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       _P, _F, _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "etm_rollout_trxl_group_gaussian": (_I, [_P, _P, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                             _P, _P, _F, _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                             _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "etm_rollout_trxl_supported_branched": (_I, [_I, _I, _I, _I, _P, _I, _I]),
+    "etm_rollout_trxl_supported_gaussian": (_I, [_I] * 6),
+    "etm_rollout_trxl_group_supported_gaussian": (_I, [_I] * 8),
     "etm_rollout_trxl_group_supported_branched": (_I, [_I, _I, _I, _I, _P, _I, _I, _I, _I]),
     "etm_rollout_trxl_group_grid": (_I, []),
     "etm_rollout_trxl_group_scratch_bytes": (_L, [_I]),
@@ -137,6 +147,11 @@ SIGNATURES = {
     "etm_heads_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _D, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _L,
                             _I, _I, _I, _P]),
     "etm_heads_loss_supported_branched": (_I, [_I, _I, _P, _I]),
+    "etm_heads_loss_supported_gaussian": (_I, [_I, _I, _I]),
+    "etm_heads_loss_gaussian_row_floats": (_I, [_I, _I]),
+    "etm_heads_loss_gaussian_workspace_bytes": (_L, [_I, _I, _I]),
+    "etm_heads_loss_gaussian": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _L, _P, _P, _P, _D, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P,
+                                     _P, _P, _L, _I, _I, _I, _P]),
     "etm_heads_loss_branched": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _D, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P,
                                      _P, _L, _I, _I, _P, _I, _P]),
     "etm_window_fwd": (_I, [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _F, _P, _L, _L, _P, _P, _L, _L, _P, _I, _I, _I, _I, _I, _P]),

@@ -788,6 +788,63 @@ def rollout_sample(logits, value, uniforms, forced, t_dev, actions, st_actions, 
 _policy_sync = {}
 
 
+def _box_bounds(low, high, A):
+    """HOST float arrays of the A bounds of a Box (None: unbounded on that side) for the kernels' launch-time bound table."""
+    import numpy as np
+    arr = lambda b: None if b is None else (ctypes.c_float * A)(*[float(x) for x in np.broadcast_to(np.asarray(b, dtype=np.float32), (A,))])
+    return arr(low), arr(high)
+
+
+def _check_box_tables(A, W, log_std, normals, forced, actions, st_actions):
+    """The float tables of a Box draw must hold A entries per (step, worker): the kernels index them so."""
+    for name, t in (("normals", normals), ("forced", forced), ("st_actions", st_actions)):
+        if t is not None and (t.dim() != 3 or t.shape[2] != A or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"{name}: need a contiguous float32 [S, W, {A}] table, got {tuple(t.shape)} {t.dtype}")
+    if actions.dtype != torch.float32 or tuple(actions.shape) != (W, A) or not actions.is_contiguous():
+        raise ValueError(f"actions: need a contiguous float32 [{W}, {A}] tensor, got {tuple(actions.shape)} {actions.dtype}")
+    if log_std.numel() != A:
+        raise ValueError(f"log_std: need {A} entries, got {log_std.numel()}")
+
+
+def rollout_sample_gaussian(mean, value, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values, low=None, high=None):
+    """Gaussian sampling + staging of one rollout step of a Box policy (in place; increments t_dev), etm_rollout_sample_gaussian:
+    x = mean + exp(log_std) normals[t] (or ``forced[t]`` where it is not NaN), ``st_actions`` [S, W, A] = x, ``st_logp`` [S, W(, 1)]
+    = log p(x), ``actions`` [W, A] = clip(x, low, high)."""
+    lib = _lib.load()
+    W, A = mean.shape
+    mean, value = _f32c(mean, "mean"), _f32c(value, "value")
+    _check_box_tables(A, W, log_std, normals, forced, actions, st_actions)
+    lo, hi = _box_bounds(low, high, A)
+    _lib.check(lib.etm_rollout_sample_gaussian(_ptr(mean), _ptr(value), _ptr(log_std), _ptr(normals), _ptr(forced), _ptr(t_dev), _ptr(actions),
+                                               _ptr(st_actions), _ptr(st_logp), _ptr(st_values), lo, hi, W, A, _stream()),
+               "etm_rollout_sample_gaussian")
+
+
+def rollout_policy_gaussian(h2, mean_head, value_head, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values,
+                            low=None, high=None, host_actions=None, host_flag=None, h_bias=None, w_off=0):
+    """``rollout_policy`` for a Box policy (etm_rollout_policy_gaussian): the heads, the draw of ``rollout_sample_gaussian`` and the
+    hand-over of the clipped float actions (``host_actions``: pinned float32 [W, A]) in one launch."""
+    lib = _lib.load()
+    W, A = h2.shape[0], mean_head.weight.shape[0]
+    hid = h2.shape[1] // 2
+    h2 = _f32c(h2, "h2")
+    ha = 0 if host_actions is None else host_actions.data_ptr()
+    hf = 0 if host_flag is None else host_flag.data_ptr()
+    sync = _policy_sync.get(t_dev.data_ptr())
+    if sync is None:
+        sync = _policy_sync[t_dev.data_ptr()] = torch.zeros(1, dtype=torch.int32, device=h2.device)
+    stage_w = st_values.shape[1]
+    _check_box_tables(A, W, log_std, normals, forced, actions, st_actions)
+    off = lambda t: None if t is None else t.data_ptr() + w_off * A * t.element_size()      # [S, W_total, A] tables
+    lo, hi = _box_bounds(low, high, A)
+    _lib.check(lib.etm_rollout_policy_gaussian(_ptr(h2), _ptr(h_bias), _ptr(mean_head.weight), _ptr(mean_head.bias), _ptr(value_head.weight),
+                                               _ptr(value_head.bias), _ptr(log_std), off(normals), off(forced), _ptr(t_dev), _ptr(actions),
+                                               off(st_actions), st_logp.data_ptr() + w_off * st_logp.element_size(),
+                                               st_values.data_ptr() + w_off * st_values.element_size(), ha, hf, _ptr(sync), lo, hi, W, A,
+                                               hid, stage_w, _stream()),
+               "etm_rollout_policy_gaussian")
+
+
 def rollout_policy(h2, policy_head, value_head, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values,
                    host_actions=None, host_flag=None, h_bias=None, w_off=0, branches=None):
     """``rollout_heads`` + ``rollout_sample`` in one launch; ``host_actions`` / ``host_flag``: pinned int64 tensors that receive
@@ -825,13 +882,16 @@ def rollout_policy(h2, policy_head, value_head, uniforms, forced, t_dev, actions
                "etm_rollout_policy_branched")
 
 
-def rollout_trxl_group_ok(fused_group, W, L, hid, A):
+def rollout_trxl_group_ok(fused_group, W, L, hid, A, gaussian=False):
     """Does the group form of the step kernel (etm_rollout_trxl_group, csrc/rollout_group.hip) take a worker group of W workers of
     this model?  ``fused_group``: ``ActorCriticModel._rfg`` (None: the model has no group packings).  ``A``: the number of actions,
     or the branch sizes of a MultiDiscrete policy."""
     if fused_group is None:
         return False
     lib = _lib.load()
+    if gaussian:               # Box policy of A dimensions (etm_rollout_trxl_group_supported_gaussian)
+        return bool(lib.etm_rollout_trxl_group_supported_gaussian(fused_group["D"], fused_group["H"], L, hid, int(A), fused_group["nb"], W,
+                                                                  fused_group["gtrxl"]))
     sizes = _branch_sizes(A)
     if sizes is None:
         a = A if isinstance(A, int) else int(tuple(A)[0])
@@ -859,10 +919,13 @@ def rollout_trxl_clear_error(scratch):
     scratch[1].zero_()
 
 
-def rollout_trxl_supported(D, H, L, hid, A, nb):
+def rollout_trxl_supported(D, H, L, hid, A, nb, gaussian=False):
     """Does ``rollout_trxl`` handle these shapes (etm_rollout_trxl_supported)?  ``A``: the number of actions, or the branch sizes
-    of a MultiDiscrete policy (etm_rollout_trxl_supported_branched)."""
+    of a MultiDiscrete policy (etm_rollout_trxl_supported_branched); ``gaussian``: A dimensions of a Box policy
+    (etm_rollout_trxl_supported_gaussian)."""
     lib = _lib.load()
+    if gaussian:
+        return bool(lib.etm_rollout_trxl_supported_gaussian(D, H, L, hid, int(A), nb))
     sizes = _branch_sizes(A)
     if sizes is None:
         return bool(lib.etm_rollout_trxl_supported(D, H, L, hid, A if isinstance(A, int) else int(tuple(A)[0]), nb))
@@ -871,7 +934,7 @@ def rollout_trxl_supported(D, H, L, hid, A, nb):
 
 
 def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head, uniforms, forced, t_dev, actions, st_actions, st_logp,
-                 st_values, scratch, host_actions=None, host_flag=None, w_off=0, tail=None, h_bias=None, window=None, branches=None):
+                 st_values, scratch, host_actions=None, host_flag=None, w_off=0, tail=None, h_bias=None, window=None, branches=None, box=None):
     """Transformer + hidden / output heads + sampling of one rollout step of a worker group in one launch (etm_rollout_trxl).
     ``fused``: the transposed fixed-address weight copies of ``ActorCriticModel.refresh_rollout_weights`` (dict with the host
     pointer table ``blocks``); ``kv`` the group's K | V cache [W, T, blocks, 2D]; ``scratch`` from ``rollout_trxl_scratch``; the
@@ -880,7 +943,9 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
     in front of it.  ``tail`` = (wkv [blocks, D, 2D], pos [T, D] or None, step_l [W], slot_l [W],
     bank [slots, T, blocks, D]): after the action hand-over the same launch writes the new memory items into
     ``bank[slot_l, step_l]`` and their K | V projection into ``kv[w, step_l]``.  ``branches`` (optional, MultiDiscrete): as in
-    ``rollout_policy`` (etm_rollout_trxl_branched / etm_rollout_trxl_group_branched)."""
+    ``rollout_policy`` (etm_rollout_trxl_branched / etm_rollout_trxl_group_branched).  ``box`` (optional, Box policy): (log_std, low,
+    high); ``policy_head`` is then the mean head, ``uniforms`` the normals and ``forced`` the NaN-or-action table, both float
+    [S, W_total, A], ``actions`` / ``st_actions`` / ``host_actions`` float (etm_rollout_trxl_gaussian / _group_gaussian)."""
     lib = _lib.load()
     h_in = _f32c(h_in, "h_in")
     h_splits = 0
@@ -925,6 +990,17 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
             int(fused.get("gtrxl", 0)), W, D, fused["H"], L, hid)
     # ``fused`` with the group packings (ActorCriticModel._rfg, "group": True) selects the group form of the kernel: same arguments
     group = bool(fused.get("group"))
+    if box is not None:
+        log_std, low, high = box
+        _check_box_tables(A, W, log_std, uniforms, forced, actions, st_actions)
+        offa = lambda t: None if t is None else t.data_ptr() + w_off * A * t.element_size()      # [S, W_total, A] tables
+        lo, hi = _box_bounds(low, high, A)
+        gargs = args[:17] + (_ptr(log_std), offa(uniforms), offa(forced), _ptr(t_dev), _ptr(actions), offa(st_actions),
+                             st_logp.data_ptr() + w_off * st_logp.element_size()) + args[23:]
+        entry, name = ((lib.etm_rollout_trxl_group_gaussian, "etm_rollout_trxl_group_gaussian") if group
+                       else (lib.etm_rollout_trxl_gaussian, "etm_rollout_trxl_gaussian"))
+        _lib.check(entry(*gargs, A, stage_w, lo, hi, _stream()), name)
+        return
     if sizes is None:
         entry, name = (lib.etm_rollout_trxl_group, "etm_rollout_trxl_group") if group else (lib.etm_rollout_trxl, "etm_rollout_trxl")
         _lib.check(entry(*args, A, stage_w, _stream()), name)
@@ -1749,7 +1825,7 @@ class _HeadsLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn, unit_grad,
-                sizes=None):
+                sizes=None, log_std=None):
         lib = _lib.load()
         _need_dev(h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3)
         h = _f32c(h, "h")
@@ -1757,17 +1833,26 @@ class _HeadsLossFn(torch.autograd.Function):
         dev = h.device
         pre_p, pre_v = h.mm(wlp.t()), h.mm(wlv.t())
         gm_p, gm_v = torch.empty_like(pre_p), torch.empty_like(pre_v)
-        row = lib.etm_heads_loss_row_floats(hid, A)
+        gauss = log_std is not None
+        row = lib.etm_heads_loss_gaussian_row_floats(hid, A) if gauss else lib.etm_heads_loss_row_floats(hid, A)
         sums = torch.empty(row, dtype=torch.float32, device=dev)
         out8 = torch.empty(8, dtype=torch.float32, device=dev)
-        nbytes = lib.etm_heads_loss_workspace_bytes(N, hid, A)
+        nbytes = lib.etm_heads_loss_gaussian_workspace_bytes(N, hid, A) if gauss else lib.etm_heads_loss_workspace_bytes(N, hid, A)
         ws = workspace(nbytes, dev, "heads_loss")
         actions, old_logp = actions.contiguous(), old_logp.contiguous()
         B = actions.shape[1] if actions.dim() == 2 else 1
         common = (_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv), _ptr(actions), B,
                   _ptr(old_logp), B, _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
                   float(vf_coef), float(beta))
-        if sizes is None:
+        if gauss:
+            # Box: wb / bb the mean head, actions [N, A] the stored raw float actions, old_logp [N] (or [N, 1]) the joint log-probs
+            _need_dev(log_std)
+            rc = lib.etm_heads_loss_gaussian(_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv),
+                                             _ptr(_f32c(actions, "actions")), A, _ptr(_f32c(log_std, "log_std")), _ptr(old_logp), 1,
+                                             _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
+                                             float(vf_coef), float(beta), 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
+                                             _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, A, _stream())
+        elif sizes is None:
             rc = lib.etm_heads_loss(*common, 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8),
                                     0, 0, _ptr(ws), nbytes, N, hid, A, _stream())
         else:
@@ -1778,6 +1863,7 @@ class _HeadsLossFn(torch.autograd.Function):
         _lib.check(rc, "etm_heads_loss")
         ctx.save_for_backward(h, wlp, wlv, gm_p, gm_v, sums)
         ctx.dims = (hid, A)
+        ctx.gauss = gauss
         ctx.unit = bool(unit_grad)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(out8)
@@ -1786,7 +1872,7 @@ class _HeadsLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_stats):
         if g_loss is None:
-            return (None,) * 20
+            return (None,) * 21
         h, wlp, wlv, gm_p, gm_v, sums = ctx.saved_tensors
         hid, A = ctx.dims
         unit = ctx.unit                 # the caller promises loss.backward() on the returned loss itself: g_loss == 1, nothing to scale
@@ -1804,7 +1890,8 @@ class _HeadsLossFn(torch.autograd.Function):
         s = sums if unit else sums * g_loss
         o = (3 + A) * hid
         return (dh, dwlp, s[:hid], dwlv, s[hid:2 * hid], s[3 * hid:o].view(A, hid), s[o:o + A], s[2 * hid:3 * hid].view(1, hid),
-                s[o + A:o + A + 1], None, None, None, None, None, None, None, None, None, None, None)
+                s[o + A:o + A + 1], None, None, None, None, None, None, None, None, None, None, None,
+                s[o + A + 6:o + 2 * A + 6] if ctx.gauss else None)
 
 
 def _branch_list(branch):
@@ -1822,6 +1909,30 @@ def heads_loss_supported(h, lin_policy, branch):
         return bool(lib.etm_heads_loss_supported(h.shape[0], lin_policy.weight.shape[0], br[0].weight.shape[0]))
     tab, nbr = _branch_table([b.weight.shape[0] for b in br])
     return bool(lib.etm_heads_loss_supported_branched(h.shape[0], lin_policy.weight.shape[0], tab, nbr))
+
+
+def heads_loss_supported_gaussian(h, lin_policy, mean_head):
+    """Does ``heads_ppo_loss_gaussian`` take this minibatch (etm_heads_loss_supported_gaussian: A <= 8, hid % 64 == 0, hid <= 512)?"""
+    return (h.is_cuda and h.dim() == 2 and h.dtype == torch.float32
+            and bool(_lib.load().etm_heads_loss_supported_gaussian(h.shape[0], lin_policy.weight.shape[0], mean_head.weight.shape[0])))
+
+
+def heads_ppo_loss_gaussian(h, lin_policy, lin_value, mean_head, log_std, value_head, actions, old_logp, adv, old_value, clip, vf_coef, beta,
+                            stats3=None, dyn=None, unit_grad=False):
+    """``heads_ppo_loss`` for a Box policy (diagonal Gaussian, state-independent ``log_std`` [A]): ``mean_head`` gives the means,
+    ``actions`` [N, A] are the stored raw float actions, ``old_logp`` [N] or [N, 1] their joint log-probs.  One ratio per sample;
+    the gradients reach ``log_std`` too (etm_heads_loss_gaussian)."""
+    if stats3 is None:
+        stats3 = adv_stats(adv)
+    if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
+        raise TypeError("heads_ppo_loss_gaussian: dyn must be a float64 device tensor (clip, beta)")
+    A = mean_head.weight.shape[0]
+    if actions.dim() != 2 or actions.shape[1] != A or not actions.is_floating_point():
+        raise ValueError(f"heads_ppo_loss_gaussian: actions must be float [N, {A}]")
+    loss, st = _HeadsLossFn.apply(h, lin_policy.weight, lin_policy.bias, lin_value.weight, lin_value.bias, mean_head.weight, mean_head.bias,
+                                  value_head.weight, value_head.bias, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn,
+                                  unit_grad, None, log_std)
+    return loss, st[:6]
 
 
 def heads_ppo_loss(h, lin_policy, lin_value, branch, value_head, actions, old_logp, adv, old_value, clip, vf_coef, beta, stats3=None, dyn=None,

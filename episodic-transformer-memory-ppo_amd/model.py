@@ -8,7 +8,7 @@ import math
 import numpy as np
 import torch
 from torch import nn
-from torch.distributions import Categorical
+from torch.distributions import Categorical, Normal
 from torch.nn import functional as F
 
 from etm import ops
@@ -26,7 +26,10 @@ class IndexedObservations:
 
 
 class ActorCriticModel(nn.Module):
-    def __init__(self, config, observation_space, action_space_shape, max_episode_length):
+    def __init__(self, config, observation_space, action_space_shape, max_episode_length, continuous=False):
+        """``continuous``: a Box action space of A = action_space_shape[0] dimensions -- a diagonal Gaussian policy whose mean is
+        ``policy_branches[0]`` and whose state-independent log standard deviation is the parameter ``policy_log_std`` [A]
+        (initial value ``action_log_std_init``, default 0)."""
         super().__init__()
         self.hidden_size = config["hidden_layer_size"]
         self.memory_layer_size = config["transformer"]["embed_dim"]
@@ -74,6 +77,18 @@ class ActorCriticModel(nn.Module):
             self.policy_branches.append(branch)
         self.value = nn.Linear(self.hidden_size, 1)
         nn.init.orthogonal_(self.value.weight, 1)
+        self.continuous = bool(continuous)
+        if self.continuous:
+            if len(self.action_space_shape) != 1:
+                raise ValueError("a Box policy has one mean head of A outputs: action_space_shape must be (A,)")
+            self.policy_log_std = nn.Parameter(torch.full((self.action_space_shape[0],), float(config.get("action_log_std_init", 0.0))))
+
+    def arena_parameters(self):
+        """(name, parameter) pairs in the order of the optimiser's flat arena: ``named_parameters()``, except that a Box policy's
+        ``policy_log_std`` -- a parameter of the model itself, which ``named_parameters()`` lists first -- goes last, so that every
+        other parameter keeps the arena offset (and the 16-byte alignment the encoder kernels require) it has without it."""
+        named = [(n, p) for n, p in self.named_parameters() if p.requires_grad]
+        return [x for x in named if x[0] != "policy_log_std"] + [x for x in named if x[0] == "policy_log_std"]
 
     # ------------------------------------------------------------------ forward
     # ------------------------------------------------------------------ rollout encoder (no grad): MFMA conv + bias + ReLU
@@ -167,7 +182,7 @@ class ActorCriticModel(nn.Module):
         if not (self.fused_rollout_block and blk.layer_norm in ("post", "pre") and t.linear_embedding.in_features == d):
             return False
         return ops.rollout_trxl_supported(d, t.num_heads, t.config["memory_length"], self.hidden_size,
-                                          self._rollout_actions(), t.num_blocks)
+                                          self._rollout_actions(), t.num_blocks, gaussian=self.continuous)
 
     def _rollout_actions(self):
         """Number of actions (one branch) or the branch sizes (MultiDiscrete): what the kernels' predicates take."""
@@ -409,6 +424,8 @@ class ActorCriticModel(nn.Module):
 
     def forward_banked(self, obs, spec: WindowSpec):
         logits, value, memory = self.forward_logits(obs, spec)
+        if self.continuous:        # Box: [Normal(mean, exp(policy_log_std))]
+            return [Normal(logits[0], self.policy_log_std.exp().expand_as(logits[0]), validate_args=False)], value, memory
         return [Categorical(logits=l, validate_args=False) for l in logits], value, memory
 
     def forward(self, obs, memory, memory_mask, memory_indices):

@@ -39,6 +39,7 @@ def default_rollout_groups(num_workers: int, min_group: int) -> int:
 
 
 from buffer import Buffer
+from environments import action_space_kind
 from environments.vec_env import make_vec_env
 from etm import lib as etm_lib
 from etm import ops
@@ -103,6 +104,23 @@ def check_kernel_shapes(tcfg: dict):
         raise ValueError("transformer shape not supported by the MI355X kernels: " + "; ".join(problems))
 
 
+def check_box_policy(config: dict, A=None):
+    """Fail early for a Box (continuous) policy the fused kernels do not take: A = ``environment.continuous_actions`` (or the
+    dimension of the environment's Box) must lie in 1..8 and ``hidden_layer_size`` inside the Gaussian heads + loss kernel's
+    predicate (etm_heads_loss_supported_gaussian); there is no torch-autograd fallback.  None when the config is not a Box."""
+    if A is None:
+        A = config.get("environment", {}).get("continuous_actions")
+        if A is None:
+            return None
+    A, hid = int(A), int(config["hidden_layer_size"])
+    if not 1 <= A <= 8:
+        raise ValueError(f"Box action space of {A} dimensions: the fused Gaussian heads + loss kernel takes 1 to 8")
+    if not etm_lib.load().etm_heads_loss_supported_gaussian(1, hid, A):
+        raise ValueError(f"Box action space with hidden_layer_size={hid}: the fused Gaussian heads + loss kernel needs a multiple of 64, "
+                         "at most 512")
+    return A
+
+
 class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
     def __init__(self, config: dict, run_id: str = "run", device: torch.device = None, env=None, dp=None,
                  first_worker_id: int = 0, tensorboard: bool = True) -> None:
@@ -127,6 +145,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         t = config["transformer"]
         self.memory_length, self.num_blocks, self.embed_dim = t["memory_length"], t["num_blocks"], t["embed_dim"]
         check_kernel_shapes(t)
+        check_box_policy(config)
         self.writer = _make_writer(run_id) if tensorboard else _NullWriter()
 
         # environments (batched front-end over the upstream per-worker protocol)
@@ -188,6 +207,14 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         # one branch per action dimension, from the environment (environments.action_space_shape: Discrete(n) -> (n,), MultiDiscrete
         # -> nvec); Discrete is upstream's single branch (trainer.py:47)
         self.action_space_shape = tuple(int(a) for a in getattr(self.env, "action_space_shape", None) or (self.env.num_actions,))
+        # Box (continuous) spaces: a diagonal Gaussian policy over A = action_space_shape[0] dimensions (float action tables, the
+        # environment receives the actions clipped to its bounds); None for Discrete / MultiDiscrete
+        kind = getattr(self.env, "action_kind", None)
+        if kind is None and hasattr(self.env, "action_space"):
+            kind = action_space_kind(self.env.action_space)
+        self.box = kind if kind is not None and kind.is_box else None
+        if self.box is not None:
+            check_box_policy(config, self.box.shape[0])
         self.max_episode_length = self.env.max_episode_steps
 
         if config.get("tunable_gemm", os.environ.get("ETM_TUNABLE_GEMM", "1") != "0"):
@@ -207,13 +234,17 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                 tunable.set_max_tuning_iterations(int(os.environ.get("ETM_TUNABLE_ITERS", 20)))
             except Exception as exc:        # an older / newer torch without this API: run with the default heuristics
                 print(f"[trainer] per-shape GEMM tuning not available ({exc})")
-        self.buffer = Buffer(config, self.observation_space, self.action_space_shape, self.max_episode_length, device)
-        self.model = ActorCriticModel(config, self.observation_space, self.action_space_shape, self.max_episode_length).to(device)
+        box = self.box is not None
+        # entries per worker of the action tables: one per branch, or the A dimensions of a Box
+        self._action_width = self.action_space_shape[0] if box else len(self.action_space_shape)
+        self.buffer = Buffer(config, self.observation_space, self.action_space_shape, self.max_episode_length, device, continuous=box)
+        self.model = ActorCriticModel(config, self.observation_space, self.action_space_shape, self.max_episode_length,
+                                      continuous=box).to(device)
         self.model.train()
         self.model.graph_refresh = bool(config.get("hip_graph_rollout", True))      # (refresh_rollout_weights as a graph replay from its third call on)
         if self.dp is not None:
             self.dp.broadcast_parameters(self.model)
-        self.params = [p for p in self.model.parameters() if p.requires_grad]
+        self.params = [p for _, p in self.model.arena_parameters()]      # (a Box policy's policy_log_std last)
         # The optimisation step of one minibatch (gather, forward, loss, backward, clipping, AdamW) is captured in a HIP graph
         # after two eager warm-up steps and replayed for every other minibatch of the run: the host then issues one launch
         # per minibatch instead of ~280.  lr / clip range / entropy coefficient live on the device so that their schedules
@@ -248,7 +279,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             self._act_pin = torch.from_numpy(self._shm_env.v["act"])
         else:
             self._obs_pin = torch.zeros((W,) + obs_shape, dtype=torch.float32).pin_memory()
-            self._act_pin = torch.zeros((W, len(self.action_space_shape)), dtype=torch.int64).pin_memory()
+            self._act_pin = torch.zeros((W, self._action_width), dtype=torch.float32 if box else torch.int64).pin_memory()
         self.obs = self._obs_pin.numpy()
         # (episode step, episode slot) of every worker: one pinned [2, W] block, uploaded with ONE copy per rollout step
         self._ss_pin = torch.zeros((2, W), dtype=torch.int64).pin_memory()
@@ -262,25 +293,30 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         self.env.reset(out=self.obs)
 
         # fixed-address operands of the rollout step (HIP-graph friendly) and time-major staging of the step outputs
-        S, L, B = config["worker_steps"], self.memory_length, len(self.action_space_shape)
+        S, L, B = config["worker_steps"], self.memory_length, self._action_width
         self._obs_dev = torch.zeros((W,) + obs_shape, dtype=torch.float32, device=device)
         self._t_dev = torch.zeros((), dtype=torch.int64, device=device)
         self._stage = {
             "obs": torch.zeros((S, W) + obs_shape, dtype=torch.float32, device=device),
             "memory_mask": torch.zeros((S, W, L), dtype=torch.bool, device=device),
             "memory_indices": torch.zeros((S, W, L), dtype=torch.int64, device=device),
-            "actions": torch.zeros((S, W, B), dtype=torch.int64, device=device),
-            "log_probs": torch.zeros((S, W, B), dtype=torch.float32, device=device),
+            "actions": torch.zeros((S, W, B), dtype=torch.float32 if box else torch.int64, device=device),
+            "log_probs": torch.zeros((S, W, 1 if box else B), dtype=torch.float32, device=device),      # (Box: one joint log-prob)
             "values": torch.zeros((S, W), dtype=torch.float32, device=device),
         }
         self._mask_t = torch.zeros((W, L), dtype=torch.bool, device=device)
         self._win_t = torch.zeros((W, L), dtype=torch.int64, device=device)
-        self._act_dev = torch.zeros((W, B), dtype=torch.int64, device=device)
+        self._act_dev = torch.zeros((W, B), dtype=torch.float32 if box else torch.int64, device=device)
         # one uniform per (step, worker, branch); a single branch keeps the [S, W] draw (the same bits as ever)
         self._uniforms = torch.zeros((S, W) if B == 1 else (S, W, B), dtype=torch.float32, device=device)
         # teacher forcing (parity tests): a non-negative entry replaces the sampled action of that (step, worker, branch); the table
         # has a fixed address, so the captured step graphs read it too -- every rollout path can be driven with recorded actions
         self._forced_tab = torch.full((S, W) if B == 1 else (S, W, B), -1, dtype=torch.int64, device=device)
+        if box:
+            # Box: one N(0, 1) draw per (step, worker, dimension), fixed address like the uniforms; forced actions are floats, NaN =
+            # "sample" (the [S, W] uniforms stay allocated but are not drawn)
+            self._normals = torch.zeros((S, W, B), dtype=torch.float32, device=device)
+            self._forced_tab = torch.full((S, W, B), float("nan"), dtype=torch.float32, device=device)
         self._step_graph = None
         self._act_ready = torch.cuda.Event()
         # observation streaming (graph rollout with the fused encoder): rows of the next observation go from pinned memory
@@ -369,12 +405,12 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
     def _make_group(self, lo, hi, env, full):
         """Device / pinned state of the workers [lo, hi) for one rollout step (see ``rollout_groups``)."""
         from types import SimpleNamespace
-        dev, Wg, B = self.device, hi - lo, len(self.action_space_shape)
+        dev, Wg, B = self.device, hi - lo, self._action_width
         g = SimpleNamespace(lo=lo, hi=hi, W=Wg, env=env, full=full, graphs=None, rf_scratch=None)
         g.obs_pin, g.act_pin = self._obs_pin[lo:hi], self._act_pin[lo:hi]
         g.obs_np = self.obs[lo:hi]
         acts = g.act_pin.numpy()
-        g.acts_host = acts[:, 0] if B == 1 else acts            # [Wg] for one branch, [Wg, B] for multi-discrete
+        g.acts_host = acts[:, 0] if B == 1 and self.box is None else acts    # [Wg] for one branch, [Wg, B] multi-discrete, [Wg, A] Box
         g.obs_dev, g.mask_t, g.win_t, g.act_dev = self._obs_dev[lo:hi], self._mask_t[lo:hi], self._win_t[lo:hi], self._act_dev[lo:hi]
         g.kv = self._kv_cache[lo:hi]
         if full:
@@ -400,7 +436,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         g.step_l, g.slot_l = g.ss_latch[0], g.ss_latch[1]
         return g
 
-    def _sample_training_data(self, forced_actions=None, uniforms=None) -> list:
+    def _sample_training_data(self, forced_actions=None, uniforms=None, normals=None) -> list:
         """Runs all workers for ``worker_steps`` steps; fills the buffer; returns finished-episode infos.
 
         The device work of one step (window lookup, model forward, action sampling, staging of the step's buffer rows,
@@ -416,7 +452,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         kernels read them from a fixed-address table, so the captured graphs, the observation streaming and the worker-group
         pipeline run exactly as they do when sampling.
         ``uniforms`` [W, S] or [W, S, B] (optional, tests) replaces the rollout's uniform draws: every sampling kernel inverts its CDF at
-        exactly these values (branch b of a MultiDiscrete policy at its own draw)."""
+        exactly these values (branch b of a MultiDiscrete policy at its own draw).
+        Box policies: ``forced_actions`` [W, S, A] floats (NaN = sample), ``normals`` [W, S, A] (optional, tests) replaces the
+        rollout's N(0, 1) draws."""
         buf, W, S = self.buffer, self.num_workers, self.config["worker_steps"]
         main = torch.cuda.current_stream(self.device)
         use_graph = bool(self.config.get("hip_graph_rollout", True))
@@ -427,15 +465,23 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         if self._use_kv_cache:
             self._refresh_kv_cache()
         self.model.refresh_rollout_weights()       # encoder weight copies for the fused rollout convolutions
-        B = len(self.action_space_shape)
-        if forced_actions is not None:
+        B = self._action_width
+        if forced_actions is not None and self.box is not None:
+            fa = torch.as_tensor(np.asarray(forced_actions), dtype=torch.float32)
+            self._forced_tab.copy_(fa.reshape(W, S, B).transpose(0, 1).to(self.device))
+        elif forced_actions is not None:
             fa = torch.as_tensor(np.asarray(forced_actions), dtype=torch.int64)
             fa = fa.reshape(W, S).t() if B == 1 else fa.reshape(W, S, B).transpose(0, 1)
             self._forced_tab.copy_(fa.to(self.device))
         groups = self._groups if use_graph else [self._group_all]
         if use_graph and groups[0].graphs is None:
             self._capture_step_graph(groups)
-        if uniforms is not None:
+        if self.box is not None:
+            if normals is not None:
+                self._normals.copy_(torch.as_tensor(np.asarray(normals), dtype=torch.float32).reshape(W, S, B).transpose(0, 1))
+            else:
+                self._normals.normal_()              # one N(0, 1) draw per (step, worker, dimension) for the whole rollout
+        elif uniforms is not None:
             u = torch.as_tensor(np.asarray(uniforms), dtype=torch.float32)
             self._uniforms.copy_(u.reshape(W, S).t() if B == 1 else u.reshape(W, S, B).transpose(0, 1))
         else:
@@ -625,7 +671,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                 raise RuntimeError("fused rollout step: a team member timed out waiting for its partners; this rollout is void. The "
                                    "trainer has switched to the multi-launch step (fused_rollout_block: false) for the following rollouts")
         if forced_actions is not None:
-            self._forced_tab.fill_(-1)
+            self._forced_tab.fill_(float("nan") if self.box is not None else -1)
         # time-major staging -> the buffer's [W, S, ...] fields (one strided copy per field)
         self._step_dev.copy_(self._step_pin, non_blocking=True)
         self._slot_dev.copy_(self._slot_pin, non_blocking=True)
@@ -660,6 +706,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             g.ss_dev.copy_(g.ss_pin, non_blocking=True)      # (streamed mode: uploaded with the observation rows)
         branches = self.action_space_shape       # (one entry: Discrete; the kernels then take their single-branch entries)
         policy_head = self.model.rollout_policy_head()
+        # Box: the Gaussian forms of the sampling kernels -- normals in place of the uniforms, float forced / action tables
+        box = None if self.box is None else (self.model.policy_log_std, self.box.low, self.box.high)
+        draws = self._uniforms if box is None else self._normals
         mask_t, win_t = g.mask_t, g.win_t
         # window lookup + staging; the same launch records the staging row of this step for the tail (t_dev is incremented by
         # the sampling kernel) and resets the K/V cache of workers at episode step 0 (they start from the projection of an
@@ -675,7 +724,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         # step, 32 workgroups per launch; csrc/rollout_group.hip)
         rfg_ = getattr(self.model, "_rfg", None) if rf_ is not None else None
         g.group_kernel = bool(rfg_ is not None and self.config.get("rollout_group_kernel", True)
-                              and ops.rollout_trxl_group_ok(rfg_, g.W, self.memory_length, self.model.hidden_size, self.model._rollout_actions())
+                              and ops.rollout_trxl_group_ok(rfg_, g.W, self.memory_length, self.model.hidden_size, self.model._rollout_actions(),
+                                                            gaussian=box is not None)
                               and n_conc * etm_lib.load().etm_rollout_trxl_group_grid() <= 256)
         fused_step = (rf_ is not None and self.model.rollout_heads_fusable()
                       and (g.group_kernel or n_conc * etm_lib.load().etm_rollout_trxl_grid(g.W, rf_["H"]) <= 256))
@@ -728,9 +778,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                     tail = (self._kv_w_blocked, self.model.transformer._pos(), g.step_l, g.slot_l, buf.bank)
                 g.tail_in_kernel = tail is not None
                 ops.rollout_trxl(h_in, rf, g.kv, win_t, mask_t, g.item, policy_head, self.model.value,
-                                 self._uniforms, self._forced_tab, g.t_dev, g.act_dev, st["actions"], st["log_probs"], st["values"],
+                                 draws, self._forced_tab, g.t_dev, g.act_dev, st["actions"], st["log_probs"], st["values"],
                                  g.rf_scratch, host_actions=g.act_pin, host_flag=g.flag_pin if host_flag else None, w_off=g.lo,
-                                 tail=tail, h_bias=h_bias, branches=branches,
+                                 tail=tail, h_bias=h_bias, branches=branches, box=box,
                                  window=(ss_src, self._mask_table, self._index_table, st["memory_mask"], st["memory_indices"],
                                          g.ss_latch, g.t_row, self._kv_init))
                 item = g.item
@@ -742,10 +792,16 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                 h2, item = self.model.forward_hidden_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, raw=True,
                                                             obs_rows=rows)
                 flag = host_flag
-                ops.rollout_policy(h2, policy_head, self.model.value, self._uniforms, self._forced_tab, g.t_dev,
-                                   g.act_dev, st["actions"], st["log_probs"], st["values"],
-                                   host_actions=g.act_pin, host_flag=g.flag_pin if flag else None,
-                                   h_bias=self.model._b_heads, w_off=g.lo, branches=branches)
+                if box is not None:
+                    ops.rollout_policy_gaussian(h2, policy_head, self.model.value, box[0], draws, self._forced_tab, g.t_dev, g.act_dev,
+                                                st["actions"], st["log_probs"], st["values"], low=box[1], high=box[2],
+                                                host_actions=g.act_pin, host_flag=g.flag_pin if flag else None,
+                                                h_bias=self.model._b_heads, w_off=g.lo)
+                else:
+                    ops.rollout_policy(h2, policy_head, self.model.value, self._uniforms, self._forced_tab, g.t_dev,
+                                       g.act_dev, st["actions"], st["log_probs"], st["values"],
+                                       host_actions=g.act_pin, host_flag=g.flag_pin if flag else None,
+                                       h_bias=self.model._b_heads, w_off=g.lo, branches=branches)
                 fused_policy = True
             else:
                 logits, value, item = self.model.forward_logits_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index,
@@ -762,8 +818,12 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             # log-softmax + categorical sample (inverse CDF on pre-drawn uniforms) + log-prob + staging + t += 1, per action branch:
             # one launch (several branches: their logits side by side)
             lg = logits[0] if len(logits) == 1 else torch.cat(logits, dim=1)
-            ops.rollout_sample(lg, value, self._uniforms, self._forced_tab, g.t_dev, g.act_dev,
-                               st["actions"], st["log_probs"], st["values"], branches=branches)
+            if box is not None:       # (the means; host actions clipped to the bounds)
+                ops.rollout_sample_gaussian(lg, value, box[0], draws, self._forced_tab, g.t_dev, g.act_dev, st["actions"], st["log_probs"],
+                                            st["values"], low=box[1], high=box[2])
+            else:
+                ops.rollout_sample(lg, value, self._uniforms, self._forced_tab, g.t_dev, g.act_dev,
+                                   st["actions"], st["log_probs"], st["values"], branches=branches)
             g.act_pin.copy_(g.act_dev, non_blocking=True)
         if item.data_ptr() != g.item.data_ptr():
             g.item.copy_(item)
@@ -1035,6 +1095,14 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         on); others the separate heads and the per-branch loss."""
         dyn = getattr(self, "_dyn", None) if dyn == "device" else dyn
         m = self.model
+        if self.box is not None:
+            # Box: the fused Gaussian heads + loss kernel is the only path (check_box_policy made sure it takes the shape)
+            h, _ = m.forward_state(obs, spec)
+            if not ops.heads_loss_supported_gaussian(h, m.lin_policy, m.policy_branches[0]):
+                raise RuntimeError("Box policy: the minibatch is outside the fused Gaussian heads + loss kernel")
+            return ops.heads_ppo_loss_gaussian(h, m.lin_policy, m.lin_value, m.policy_branches[0], m.policy_log_std, m.value, mb["actions"],
+                                               mb["log_probs"], mb["advantages"], mb["values"], clip_range, self.config["value_loss_coefficient"],
+                                               beta, stats3, dyn=dyn, unit_grad=True)
         if self.config.get("fused_heads_loss", True):
             h, _ = m.forward_state(obs, spec)
             branch = m.policy_branches[0] if len(m.policy_branches) == 1 else list(m.policy_branches)

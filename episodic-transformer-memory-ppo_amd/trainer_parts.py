@@ -75,7 +75,7 @@ class _DataParallelStep:
         if self.dp is None or not self.config.get("dp_overlap", False) or self._obs_train is None:
             return False
         if getattr(self, "_n_conv_params", None) is None:
-            names = [n for n, p in self.model.named_parameters() if p.requires_grad]
+            names = [n for n, _ in self.model.arena_parameters()]
             k = 0
             while k < len(names) and names[k].startswith("conv"):
                 k += 1

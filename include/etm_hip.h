@@ -229,6 +229,13 @@ int etm_rollout_sample(const float *logits, const float *value, const float *uni
 int etm_rollout_sample_branched(const float *logits, const float *value, const float *uniforms, const int64_t *forced, int64_t *t_dev,
                                 int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W, const int32_t *branch_sizes,
                                 int n_branches, void *stream);
+/* Box policies (ABI 49): a diagonal Gaussian over A <= 8 dimensions.  mean [W, A] = the policy head's outputs; x = mean + exp(log_std)
+ * normals[*t_dev, w] (log_std [A] on the device; normals / forced / st_actions time-major [S, W, A]; a forced row entry that is not NaN
+ * replaces the draw of its dimension); st_logp[*t_dev, w] = log p(x) = sum_a [-((x_a - mean_a) / sigma_a)^2 / 2 - log sigma_a - log(2 pi) / 2]
+ * of the stored x; st_values [S, W]; actions [W, A] = clip(x, low, high) (low / high: HOST arrays of A floats, NULL = unbounded). */
+int etm_rollout_sample_gaussian(const float *mean, const float *value, const float *log_std, const float *normals, const float *forced,
+                                int64_t *t_dev, float *actions, float *st_actions, float *st_logp, float *st_values, const float *low,
+                                const float *high, int W, int A, void *stream);
 int etm_add_layernorm(const float *a, const float *a_bias, int relu, const float *b, const float *gamma, const float *beta, float eps,
                       float *out, int N, int D, void *stream);
 /* Elementwise parts of the GTrXL GRU gate on the rollout path (transformer.py:287-298), around concatenated library GEMMs
@@ -323,6 +330,21 @@ int etm_heads_loss_branched(const float *pre_p, const float *pre_v, const float 
                             float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p,
                             float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes,
                             int N, int hid, const int32_t *branch_sizes, int n_branches, void *stream);
+/* Box policies (ABI 49): the same pass for a diagonal Gaussian (A <= 8): wb / bb = the mean head; xact [N, A] (row stride
+ * action_stride >= A) the stored raw float actions; log_std [A]; old_logp [N] (logp_stride).  Per sample one ratio of the joint
+ * log-probs; d log p / d mean_a = (x_a - mean_a) / sigma_a^2, d log p / d log sigma_a = ((x_a - mean_a) / sigma_a)^2 - 1, the entropy
+ * sum_a (1/2 + log(2 pi) / 2 + log sigma_a) adds -beta ent_scale per sample to every d log sigma_a.  sums
+ * [etm_heads_loss_gaussian_row_floats = etm_heads_loss_row_floats + A] = the etm_heads_loss row followed by d log_std (A), summed in
+ * the same fixed order (no atomics). */
+int etm_heads_loss_supported_gaussian(int N, int hid, int A);
+int etm_heads_loss_gaussian_row_floats(int hid, int A);
+int64_t etm_heads_loss_gaussian_workspace_bytes(int N, int hid, int A);
+int etm_heads_loss_gaussian(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb, const float *bb,
+                            const float *wv, const float *bv, const float *xact, int64_t action_stride, const float *log_std,
+                            const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value, const float *adv_stats3,
+                            double clip, float vf_coef, float beta, float pol_scale, float ent_scale, float val_scale,
+                            const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8, float *logits, float *value,
+                            void *workspace, int64_t workspace_bytes, int N, int hid, int A, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Weight gradients of the dense layers of one optimisation step as ONE grouped launch: replaces the `dW = dy^T x` products that
@@ -380,6 +402,12 @@ int etm_rollout_policy_branched(const float *h, const float *h_bias, const float
                                 const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
                                 float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
                                 int W, int hid, int stage_W, const int32_t *branch_sizes, int n_branches, void *stream);
+/* Box policies (ABI 49): wp / bp = the mean head [A, hid], [A]; the draw of etm_rollout_sample_gaussian (normals / forced / st_actions
+ * [S, stage_W, A]); actions and host_actions (pinned, optional) [W, A] receive the clipped actions, host_actions before the flag. */
+int etm_rollout_policy_gaussian(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv, const float *bv,
+                                const float *log_std, const float *normals, const float *forced, int64_t *t_dev, float *actions,
+                                float *st_actions, float *st_logp, float *st_values, float *host_actions, int64_t *host_flag,
+                                int32_t *sync_counter, const float *low, const float *high, int W, int A, int hid, int stage_W, void *stream);
 
 /* The transformer, the hidden / output heads and the sampling of one rollout step of a worker group as ONE launch (post-LN
  * blocks without gates; trainer.py:163-186 -> model.py:96-112 -> transformer.py:222-253), csrc/rollout_fused.hip: a TEAM of
@@ -489,6 +517,35 @@ int etm_rollout_trxl_group_branched(const float *h_in, const float *wemb_t, cons
                                     const int64_t *index_table, uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row,
                                     uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H,
                                     int L, int hid, int stage_W, const int32_t *branch_sizes, int n_branches, void *stream);
+/* Box forms of the two step kernels (ABI 49): the arguments of etm_rollout_trxl / etm_rollout_trxl_group with log_std [A] after bv,
+ * float normals / forced / actions / st_actions / host_actions in place of uniforms / forced / actions / st_actions / host_actions (the
+ * layouts of etm_rollout_policy_gaussian) and the HOST bound arrays low / high after stage_W; wp / bp = the mean head.  Shapes: the
+ * predicates below = the Discrete ones at A, and A <= 8. */
+int etm_rollout_trxl_supported_gaussian(int D, int H, int L, int hid, int A, int nb);
+int etm_rollout_trxl_group_supported_gaussian(int D, int H, int L, int hid, int A, int nb, int W, int gtrxl);
+int etm_rollout_trxl_gaussian(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
+                              int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
+                              const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
+                              const float *log_std, const float *normals, const float *forced, int64_t *t_dev, float *actions,
+                              float *st_actions, float *st_logp, float *st_values, float *host_actions, int64_t *host_flag,
+                              int32_t *sync_counter, float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos,
+                              const int64_t *step_l, const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride,
+                              int64_t bank_block_stride, const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table,
+                              const int64_t *index_table, uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row,
+                              uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H,
+                              int L, int hid, int A, int stage_W, const float *low, const float *high, void *stream);
+int etm_rollout_trxl_group_gaussian(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb,
+                                    float *kv, int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask,
+                                    float *items, const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv,
+                                    const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev,
+                                    float *actions, float *st_actions, float *st_logp, float *st_values, float *host_actions,
+                                    int64_t *host_flag, int32_t *sync_counter, float ln_eps, void *scratch, int64_t scratch_bytes,
+                                    const float *wkv, const float *pos, const int64_t *step_l, const int64_t *slot_l, float *bank,
+                                    int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
+                                    int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table,
+                                    uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,
+                                    const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A,
+                                    int stage_W, const float *low, const float *high, void *stream);
 /* Window pass (etm_window_*): 0 = load and multiply the window rows of fully masked waves too (A/B diagnostics; the results are
  * bit-identical either way); default 1 = skip them.  Process-wide, read at launch. */
 int etm_window_set_skip_masked(int on);
