@@ -1326,11 +1326,16 @@ def conv_pack_dgrad_weights(weight, stride):
     return torch.stack(blocks).contiguous()
 
 
-def encoder_train_supported(obs_shape, convs, batch=None):
+def encoder_train_supported(obs_shape, convs, batch=None, bank=None, products=None):
     """Can the hand-written training kernels run this encoder?  (model.py:40-56 geometry with 84 x 84 or similar inputs.)
     ``batch``: images per call -- the kernels index output pixels with 24 bits (N * Ho * Wo < 2^24 per layer, padded to the
-    backward-data kernel's image unit of 1024) and the source with 32-bit element offsets; larger minibatches take the library path."""
+    backward-data kernel's image unit of 1024) and the source with 32-bit element offsets; larger minibatches take the library path.
+    ``bank``: images of the tensor an indexed call gathers from (``encoder_train(bank, index=...)``): the fp32 first layer
+    addresses the whole bank with 32-bit element offsets, so a bank of 2^31 floats or more is refused unless the call runs on the
+    bf16 matrix pipe (``products`` as ``encoder_train`` takes it; those kernels form a 64-bit image base)."""
     c, h, w = obs_shape
+    if bank is not None and bank * h * w * c >= 2 ** 31 and not _encoder_uses_b3(h, w, [cv.weight for cv in convs], [cv.stride[0] for cv in convs], products):
+        return False
     for conv in convs:
         if batch is not None:
             kh, s = conv.kernel_size[0], conv.stride[0]
@@ -1366,6 +1371,19 @@ def set_encoder_products(kind):
 _B3_LAYERS = {(3, 84, 84, 32, 8, 4), (32, 20, 20, 64, 4, 2), (64, 9, 9, 64, 3, 1)}      # (C, H, W, Cout, K, S) of model.py:29-31 on 84 x 84
 
 
+def _encoder_uses_b3(h, w, weights, strides, products):
+    """Does ``encoder_train`` run the three layers (weights [Cout, C, K, K], strides) on h x w images on the bf16 matrix pipe
+    (csrc/conv_b3*.hip)?  Only the exact layers of _B3_LAYERS.  (``_EncoderFn`` and ``encoder_train_supported`` both ask here.)"""
+    if (products or _encoder_products) != "bf16x3":
+        return False
+    for wt, s in zip(weights, strides):
+        cout, cin, kh, kw = wt.shape
+        if kh != kw or (cin, h, w, cout, kh, s) not in _B3_LAYERS:
+            return False
+        h, w = (h - kh) // s + 1, (w - kw) // s + 1
+    return True
+
+
 def conv_b3_pack(weights, dgrad, strides):
     """``weights[i]`` [Cout, C, K, K] -> the three bf16 planes of its forward (``dgrad[i]`` 0) or backward-data (1) operand in
     fragment order (etm_conv_b3_pack, one launch for all entries): int16 tensors of 3 * numel."""
@@ -1398,11 +1416,7 @@ class _EncoderFn(torch.autograd.Function):
         # both packings of the three layers' weights in ONE launch; the backward-data ones ride in the context
         layers = ((w1, b1, strides[0]), (w2, b2, strides[1]), (w3, b3, strides[2]))
         wts = [_f32c(wt.detach(), "conv weight") for wt, _, _ in layers]
-        geo, hh, ww = [], h, w
-        for wt, _, s in layers:
-            geo.append((wt.shape[1], hh, ww, wt.shape[0], wt.shape[2], s))
-            hh, ww = (hh - wt.shape[2]) // s + 1, (ww - wt.shape[3]) // s + 1
-        use_b3 = (products or _encoder_products) == "bf16x3" and all(g in _B3_LAYERS for g in geo) and all(wt.shape[2] == wt.shape[3] for wt in wts)
+        use_b3 = _encoder_uses_b3(h, w, wts, strides, products)
         if use_b3:      # the five operands (three forward, two backward-data) split and packed in ONE launch
             packs = conv_b3_pack(wts + wts[1:], [0, 0, 0, 1, 1], [l[2] for l in layers] + [l[2] for l in layers[1:]])
             dgrad_packs = [None] + packs[3:]

@@ -345,7 +345,8 @@ class ActorCriticModel(nn.Module):
                 if self._train_encoder_ok is None:
                     self._train_encoder_ok = ops.encoder_train_supported(self.observation_space_shape, (self.conv1, self.conv2, self.conv3))
                 if self._train_encoder_ok and ops.encoder_train_supported(self.observation_space_shape, (self.conv1, self.conv2, self.conv3),
-                                                                            batch=int(obs.index.numel())):
+                                                                            batch=int(obs.index.numel()), bank=int(obs.bank.shape[0]),
+                                                                            products=self.encoder_products):
                     feats = ops.encoder_train(obs.bank, self.conv1, self.conv2, self.conv3, index=obs.index, products=self.encoder_products)
                     if getattr(self, "_keep_encoder_features", False):      # data-parallel overlap: the backward pass is cut here
                         self._encoder_features = feats                      # (trainer._train_body_a1; released by _train_body_a2)

@@ -221,6 +221,25 @@ def test_conv_pack_weights_layout_and_attention_dispatch_rules():
     ops.set_attention_impl("dense"); ops.set_attention_impl("folded")
 
 
+def test_encoder_train_supported_minibatch_and_bank_limits():
+    """ops.encoder_train_supported: the 24-bit pixel limit of the minibatch (3 x 84 x 84: N * 20 * 20 < 2^24 up to N = 41,943) and,
+    for an indexed call, the 32-bit element offsets of the fp32 first layer into the whole bank (4 x 84 x 84: 2^31 floats at 76,088
+    images; 3 x 84 x 84 on fp32 products: 101,450) -- the bf16x3 kernels at 3 x 84 x 84 form a 64-bit image base (pure host logic)."""
+    from etm import ops
+    convs = lambda c: (torch.nn.Conv2d(c, 32, 8, 4), torch.nn.Conv2d(32, 64, 4, 2), torch.nn.Conv2d(64, 64, 3, 1))
+    sup = ops.encoder_train_supported
+    assert sup((3, 84, 84), convs(3), batch=41943) and not sup((3, 84, 84), convs(3), batch=41944)
+    assert sup((4, 84, 84), convs(4), batch=2048) and sup((4, 84, 84), convs(4), batch=2048, bank=76087)
+    assert not sup((4, 84, 84), convs(4), batch=2048, bank=76088)
+    for products in (None, "bf16x3", "fp32"):       # (4 x 84 x 84 runs the fp32 kernels whatever the product form)
+        assert not sup((4, 84, 84), convs(4), batch=96, bank=10 ** 6, products=products)
+    assert sup((3, 84, 84), convs(3), batch=2048, bank=101449, products="fp32")
+    assert not sup((3, 84, 84), convs(3), batch=2048, bank=101450, products="fp32")
+    assert sup((3, 84, 84), convs(3), batch=2048, bank=10 ** 6) and sup((3, 84, 84), convs(3), batch=2048, bank=10 ** 6, products="bf16x3")
+    assert not sup((3, 84, 84), convs(3), batch=41944, bank=10 ** 6)          # (the minibatch limit still holds)
+    assert sup((1, 84, 84), convs(1), bank=304348) and not sup((1, 84, 84), convs(1), bank=304349)      # 2^31 / 7056 = 304,348.6
+
+
 def test_attention_supported_predicate_and_trainer_check():
     """ops.attention_supported: the folded pass's LDS budget at large H, the dX kernel's LDS for norm_kv / positional-table gradients
     and the dense backward; check_kernel_shapes refuses a config whose attention backward cannot run (pure host logic)."""
