@@ -16,6 +16,7 @@
 // HBM-bound by construction (3 - 5 tensors of N x D floats per launch); at the minibatch size (N = 2048, D = 384: 3 MB per
 // tensor) they are launch-latency-sized, which is exactly why they are fused: one launch replaces 3 - 10 framework launches.
 #include "etm_common.h"
+#include "tail_jobs.h"
 
 #include <type_traits>
 
@@ -180,26 +181,9 @@ struct ColsumGroup {
   int n;
 };
 __global__ __launch_bounds__(256) void colsum_reduce_grouped_kernel(const ColsumGroup g) {
-  __shared__ float sm[TR_WAVES][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int i = 0;
   while (i + 1 < g.n && (int)blockIdx.x >= g.first_block[i + 1]) ++i;      // uniform
-  const float *__restrict__ partial = g.partial[i];
-  const int P = g.P[i], C = g.C[i], ld = g.ld[i];
-  const int c = ((int)blockIdx.x - g.first_block[i]) * 64 + lane;
-  const int cc = c < C ? c : 0;
-  float acc[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) acc[k] = 0.f;
-  int p = wave;
-  for (; p + 7 * TR_WAVES < P; p += 8 * TR_WAVES) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) acc[k] += partial[(long long)(p + k * TR_WAVES) * ld + cc];
-  }
-  for (; p < P; p += TR_WAVES) acc[0] += partial[(long long)p * ld + cc];
-  sm[wave][lane] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-  __syncthreads();
-  if (wave == 0 && c < C) g.out[i][c] = (sm[0][lane] + sm[1][lane]) + (sm[2][lane] + sm[3][lane]);
+  colsum_reduce_block(g.partial[i], g.P[i], g.C[i], g.ld[i], g.out[i], (int)blockIdx.x - g.first_block[i]);      // (tail_jobs.h)
 }
 
 // ---- backward of relu(x W^T + b) up to the GEMMs (model.py:94-107, transformer.py:232): gm = g * (y > 0) and the column sums of

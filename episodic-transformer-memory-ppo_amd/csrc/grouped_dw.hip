@@ -20,6 +20,7 @@
 // The four waves of a workgroup split the N rows (k-range of N / 4 each: one wave per SIMD, 192 accumulator registers) and are
 // summed in a fixed order through LDS: ((w0 + w2) + (w1 + w3)) -- deterministic, no atomics.
 #include "etm_common.h"
+#include "tail_jobs.h"
 
 namespace {
 constexpr int GD_MT = 3, GD_NT = 4;                 // 32-row tiles along Ma (96) and along Nb (128) per workgroup
@@ -93,12 +94,14 @@ __device__ __forceinline__ void gd_mfma(f32x16 (&acc)[GD_MT][GD_NT], const f32x3
     for (int j = 0; j < GD_NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
 }
 
-__global__ __launch_bounds__(256) void grouped_dw_kernel(const GdParams P) {
+// One 96 x 128 output tile on the 256 threads of workgroup `block` (< P.n_tiles).  PT: GdParams or GdTailParams (the same members).
+template <typename PT>
+__device__ __forceinline__ void gd_tile_block(const PT &P, int block) {
   extern __shared__ __attribute__((aligned(16))) float gd_lds[];      // 2 x 48 KB: the accumulators of two waves
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform: the descriptors below depend on it
   // tile -> problem (uniform; <= GD_MAXP compares on the scalar unit)
-  const int tile = gd_tile_of_block(blockIdx.x, P.n_tiles);
+  const int tile = gd_tile_of_block(block, P.n_tiles);
   int pi = 0;
   for (int q = 1; q < P.n_problems; ++q)
     if (tile >= P.p[q].tile_start) pi = q;
@@ -200,6 +203,38 @@ __global__ __launch_bounds__(256) void grouped_dw_kernel(const GdParams P) {
       *reinterpret_cast<f32x4 *>(crow + (long long)row * pr.ldc) = f32x4{acc[i][0][r], acc[i][1][r], acc[i][2][r], acc[i][3][r]};
     }
 }
+
+__global__ __launch_bounds__(256) void grouped_dw_kernel(const GdParams P) { gd_tile_block(P, (int)blockIdx.x); }
+
+// ---- The tail launch: the tiles above plus, on workgroups numbered AFTER them, the grouped column-sum reduction that ends a backward
+// pass (tail_jobs.h) -- it used to run alone on the chip in front of this launch; here it runs on the CUs the tiles leave idle
+// (216 tiles on 256 CUs at config 3).  (The encoder's slice reduction was tried as a third job and taken out again: 84 MB through the
+// 40 idle CUs at one 256-thread workgroup each stretched the launch from 114 to 167 us, more than the 23 us its own launch costs.)  The tiles come first in the dispatch order and keep their die mapping (gd_tile_of_block looks at
+// the tile count only).  Every extra workgroup reads and writes what its own job names: nothing is handed between workgroups.
+constexpr int GT_MAXP = 52, GT_MAXCS = 64;
+struct GtColsum {                                   // (24 bytes: the table must fit the 4 KB of kernel arguments beside the tiles')
+  const float *partial;
+  float *out;
+  unsigned short P, C, ld, first_block;
+};
+struct GdTailParams {
+  GdProblem p[GT_MAXP];
+  GtColsum cs[GT_MAXCS];
+  int n_problems, n_tiles, N, n_cs;                 // column-sum workgroups: from n_tiles on
+};
+static_assert(sizeof(GdTailParams) <= 4096, "kernel arguments of one launch");
+
+__global__ __launch_bounds__(256) void grouped_dw_tail_kernel(const GdTailParams P) {
+  const int b = (int)blockIdx.x;
+  if (b < P.n_tiles) {
+    gd_tile_block(P, b);
+    return;
+  }
+  const int r = b - P.n_tiles;
+  int i = 0;
+  while (i + 1 < P.n_cs && r >= (int)P.cs[i + 1].first_block) ++i;        // uniform
+  colsum_reduce_block(P.cs[i].partial, P.cs[i].P, P.cs[i].C, P.cs[i].ld, P.cs[i].out, r - (int)P.cs[i].first_block);
+}
 }  // namespace
 
 // 1 when a problem's shape fits the kernel (whole 96 x 128 tiles, 16-byte aligned runs, 32-bit byte offsets).
@@ -239,5 +274,46 @@ extern "C" int etm_grouped_dw(const float *const *A, const float *const *B, floa
   }
   EtmProfScope prof(ETM_K_GROUPED_DW, st);
   hipLaunchKernelGGL(grouped_dw_kernel, dim3((unsigned)tiles), dim3(256), lds, st, P);
+  return etm_launch_status();
+}
+
+extern "C" int etm_grouped_dw_tail_max_problems(void) { return GT_MAXP; }
+
+// etm_grouped_dw (same A / B / C / dims / n_problems / N, n_problems <= etm_grouped_dw_tail_max_problems()) with, in the same launch,
+// etm_colsum_reduce_grouped (cs_*: its arguments; 1 <= n_cs <= 64; P, C and ld below 65536) on extra workgroups.  Every output holds
+// the bits the two separate launches give.
+extern "C" int etm_grouped_dw_tail(const float *const *A, const float *const *B, float *const *C, const int32_t *dims, int n_problems, int N,
+                                   const float *const *cs_partial, const int *cs_P, const int *cs_C, const int *cs_ld, float *const *cs_out,
+                                   int n_cs, void *stream) {
+  (void)hipGetLastError();
+  if (!A || !B || !C || !dims || n_problems <= 0 || N <= 0 || n_cs <= 0 || !cs_partial || !cs_P || !cs_C || !cs_ld || !cs_out) return ETM_EINVAL;
+  if (n_problems > GT_MAXP || n_cs > GT_MAXCS) return ETM_EUNSUPPORTED;
+  GdTailParams P{};
+  int tiles = 0;
+  for (int i = 0; i < n_problems; ++i) {
+    const int Ma = dims[5 * i], Nb = dims[5 * i + 1], lda = dims[5 * i + 2], ldb = dims[5 * i + 3], ldc = dims[5 * i + 4];
+    if (!A[i] || !B[i] || !C[i]) return ETM_EINVAL;
+    if (!etm_grouped_dw_supported(N, Ma, Nb, lda, ldb, ldc)) return ETM_EUNSUPPORTED;
+    if (((uintptr_t)A[i] % 4) || ((uintptr_t)B[i] % 16) || ((uintptr_t)C[i] % 16)) return ETM_EINVAL;
+    P.p[i] = GdProblem{A[i], B[i], C[i], lda, ldb, ldc, Nb / GD_TN, tiles};
+    tiles += (Ma / GD_TM) * (Nb / GD_TN);
+  }
+  int blocks = 0;
+  for (int i = 0; i < n_cs; ++i) {
+    if (!cs_partial[i] || !cs_out[i] || cs_P[i] <= 0 || cs_C[i] <= 0 || cs_ld[i] < cs_C[i]) return ETM_EINVAL;
+    if (cs_P[i] > 65535 || cs_C[i] > 65535 || cs_ld[i] > 65535 || blocks > 65535) return ETM_EUNSUPPORTED;
+    P.cs[i] = GtColsum{cs_partial[i], cs_out[i], (unsigned short)cs_P[i], (unsigned short)cs_C[i], (unsigned short)cs_ld[i], (unsigned short)blocks};
+    blocks += (cs_C[i] + 63) / 64;
+  }
+  P.n_problems = n_problems; P.n_tiles = tiles; P.N = N; P.n_cs = n_cs;
+  hipStream_t st = (hipStream_t)stream;
+  constexpr size_t lds = 2 * (size_t)GD_MT * GD_NT * 16 * 64 * sizeof(float);      // 96 KB (the tiles'; the reduction uses static LDS)
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void *)grouped_dw_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set = true;
+  }
+  EtmProfScope prof(ETM_K_GROUPED_DW, st);
+  hipLaunchKernelGGL(grouped_dw_tail_kernel, dim3((unsigned)(tiles + blocks)), dim3(256), lds, st, P);
   return etm_launch_status();
 }

@@ -91,10 +91,9 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_clip_kernel(float4 *__restr
 // Monitored gradient norms (model.py:128-151: one norm per module group, taken after clipping): partial[s] = sum of squares of
 // segment s (a run of <= 4096 floats inside ONE parameter tensor), then out[g] = sqrt(sum_s member[g][s] * partial[s]) -- two
 // launches whatever the number of tensors and groups, every sum in a fixed order.
-__global__ __launch_bounds__(OPT_THREADS) void segment_sqsum_kernel(const float *__restrict__ g, const long long *__restrict__ seg_start,
-                                                                    const int *__restrict__ seg_len, float *__restrict__ partial) {
+__device__ __forceinline__ void segment_sqsum_block(const float *__restrict__ g, const long long *__restrict__ seg_start,
+                                                    const int *__restrict__ seg_len, float *__restrict__ partial, int s) {
   __shared__ float sm[4];
-  const int s = blockIdx.x;
   const float *src = g + seg_start[s];
   const int len = seg_len[s];
   float v[16];
@@ -109,14 +108,58 @@ __global__ __launch_bounds__(OPT_THREADS) void segment_sqsum_kernel(const float 
   const float t = block_sum_256(acc, sm);
   if (threadIdx.x == 0) partial[s] = t;
 }
-__global__ __launch_bounds__(OPT_THREADS) void group_norm_kernel(const float *__restrict__ member, const float *__restrict__ partial, int n_segs,
-                                                                 float *__restrict__ out) {
+__device__ __forceinline__ float group_norm_block(const float *__restrict__ member, const float *__restrict__ partial, int n_segs, int gidx) {
   __shared__ float sm[4];
-  const int gidx = blockIdx.x;
   float acc = 0.f;
   for (int s = threadIdx.x; s < n_segs; s += OPT_THREADS) acc += member[(long long)gidx * n_segs + s] * partial[s];
-  const float t = block_sum_256(acc, sm);
-  if (threadIdx.x == 0) out[gidx] = sqrtf(t);
+  return sqrtf(block_sum_256(acc, sm));
+}
+__global__ __launch_bounds__(OPT_THREADS) void segment_sqsum_kernel(const float *__restrict__ g, const long long *__restrict__ seg_start,
+                                                                    const int *__restrict__ seg_len, float *__restrict__ partial) {
+  segment_sqsum_block(g, seg_start, seg_len, partial, blockIdx.x);
+}
+__global__ __launch_bounds__(OPT_THREADS) void group_norm_kernel(const float *__restrict__ member, const float *__restrict__ partial, int n_segs,
+                                                                 float *__restrict__ out) {
+  const float t = group_norm_block(member, partial, n_segs, blockIdx.x);
+  if (threadIdx.x == 0) out[blockIdx.x] = t;
+}
+
+// ---- End of a minibatch step that keeps its results on the device (etm_step_end / etm_group_norms_step): the step's statistics and
+// monitored norms go to row `*counter` of result tables and the counter moves on, so that nothing has to be copied out between two
+// replays of the captured step.  One workgroup reads the counter, files the statistics and stores counter + 1 -- a plain store, as
+// grad_sqnorm_kernel advances the optimiser's step count -- in a launch in which no other workgroup looks at the counter; the norm
+// kernel, one launch later, files its row under counter - 1.  Rows beyond the table are clamped to its last row (never out of bounds).
+__device__ __forceinline__ void step_end_block(const float *__restrict__ stats, int n_stats, float *__restrict__ stats_table, int table_rows,
+                                               long long *__restrict__ counter) {
+  const long long c = *counter;
+  const long long row = c < 0 ? 0 : (c >= table_rows ? table_rows - 1 : c);
+  if (stats_table)
+    for (int i = threadIdx.x; i < n_stats; i += OPT_THREADS) stats_table[row * n_stats + i] = stats[i];
+  __syncthreads();
+  if (threadIdx.x == 0) *counter = c + 1;
+}
+__global__ __launch_bounds__(OPT_THREADS) void step_end_kernel(const float *__restrict__ stats, int n_stats, float *__restrict__ stats_table,
+                                                               int table_rows, long long *__restrict__ counter) {
+  step_end_block(stats, n_stats, stats_table, table_rows, counter);
+}
+__global__ __launch_bounds__(OPT_THREADS) void segment_sqsum_end_kernel(const float *__restrict__ g, const long long *__restrict__ seg_start,
+                                                                        const int *__restrict__ seg_len, float *__restrict__ partial, int n_segs,
+                                                                        const float *__restrict__ stats, int n_stats,
+                                                                        float *__restrict__ stats_table, int table_rows,
+                                                                        long long *__restrict__ counter) {
+  if ((int)blockIdx.x < n_segs) segment_sqsum_block(g, seg_start, seg_len, partial, blockIdx.x);
+  else step_end_block(stats, n_stats, stats_table, table_rows, counter);
+}
+__global__ __launch_bounds__(OPT_THREADS) void group_norm_row_kernel(const float *__restrict__ member, const float *__restrict__ partial, int n_segs,
+                                                                     float *__restrict__ out, float *__restrict__ norm_table, int table_rows,
+                                                                     const long long *__restrict__ counter) {
+  const float t = group_norm_block(member, partial, n_segs, blockIdx.x);
+  if (threadIdx.x == 0) {
+    const long long c = *counter - 1;                              // (segment_sqsum_end_kernel has moved the counter on already)
+    const long long row = c < 0 ? 0 : (c >= table_rows ? table_rows - 1 : c);
+    out[blockIdx.x] = t;
+    norm_table[row * gridDim.x + blockIdx.x] = t;
+  }
 }
 }  // namespace
 
@@ -131,6 +174,35 @@ extern "C" int etm_group_norms(const float *flat, const int64_t *seg_start, cons
   int rc = etm_launch_status();
   if (rc) return rc;
   hipLaunchKernelGGL(group_norm_kernel, dim3((unsigned)n_groups), dim3(OPT_THREADS), 0, st, member, partial, n_segs, out);
+  return etm_launch_status();
+}
+
+// etm_group_norms whose two launches also end the minibatch step: row r = *counter of stats_table [table_rows, n_stats] = stats,
+// row r of norm_table [table_rows, n_groups] = out, then *counter = r + 1.  out holds the same bits as etm_group_norms gives.
+extern "C" int etm_group_norms_step(const float *flat, const int64_t *seg_start, const int32_t *seg_len, int n_segs, const float *member,
+                                    int n_groups, float *partial, float *out, float *norm_table, const float *stats, int n_stats,
+                                    float *stats_table, int table_rows, int64_t *counter, void *stream) {
+  (void)hipGetLastError();
+  if (!flat || !seg_start || !seg_len || !member || !partial || !out || n_segs <= 0 || n_groups <= 0) return ETM_EINVAL;
+  if (!norm_table || !stats || !stats_table || !counter || n_stats <= 0 || table_rows <= 0) return ETM_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  EtmProfScope prof(ETM_K_OPTIM, st);
+  hipLaunchKernelGGL(segment_sqsum_end_kernel, dim3((unsigned)n_segs + 1), dim3(OPT_THREADS), 0, st, flat, (const long long *)seg_start, seg_len,
+                     partial, n_segs, stats, n_stats, stats_table, table_rows, (long long *)counter);
+  int rc = etm_launch_status();
+  if (rc) return rc;
+  hipLaunchKernelGGL(group_norm_row_kernel, dim3((unsigned)n_groups), dim3(OPT_THREADS), 0, st, member, partial, n_segs, out, norm_table,
+                     table_rows, (const long long *)counter);
+  return etm_launch_status();
+}
+
+// The end of a step whose gradient norms are not monitored: the statistics row and the counter alone (one workgroup).
+extern "C" int etm_step_end(const float *stats, int n_stats, float *stats_table, int table_rows, int64_t *counter, void *stream) {
+  (void)hipGetLastError();
+  if (!stats || !stats_table || !counter || n_stats <= 0 || table_rows <= 0) return ETM_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  EtmProfScope prof(ETM_K_OPTIM, st);
+  hipLaunchKernelGGL(step_end_kernel, dim3(1), dim3(OPT_THREADS), 0, st, stats, n_stats, stats_table, table_rows, (long long *)counter);
   return etm_launch_status();
 }
 

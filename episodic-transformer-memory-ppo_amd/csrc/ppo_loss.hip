@@ -6,41 +6,12 @@
 // torch.max (gradient split in half) and the inclusive range of torch.clamp's backward are reproduced.
 // HBM traffic: 28 + 8 A bytes per sample.
 #include "etm_common.h"
+#include "adv_stats.h"
 
 namespace {
 
 __global__ __launch_bounds__(1024) void adv_stats_kernel(const float *__restrict__ adv, int N, float *__restrict__ stats3) {
-  __shared__ float red[16];
-  __shared__ float mean_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float s = 0.f;
-  for (int i = tid; i < N; i += 1024) s += adv[i];
-  s = wave_sum(s);
-  if (lane == 0) red[wave] = s;
-  __syncthreads();
-  if (tid == 0) {
-    float t = 0.f;
-    for (int w = 0; w < 16; ++w) t += red[w];
-    mean_s = t / (float)N;
-  }
-  __syncthreads();
-  const float mean = mean_s;
-  float m2 = 0.f;
-  for (int i = tid; i < N; i += 1024) {
-    const float d = adv[i] - mean;
-    m2 += d * d;
-  }
-  m2 = wave_sum(m2);
-  __syncthreads();
-  if (lane == 0) red[wave] = m2;
-  __syncthreads();
-  if (tid == 0) {
-    float t = 0.f;
-    for (int w = 0; w < 16; ++w) t += red[w];
-    stats3[0] = (float)N;
-    stats3[1] = mean;
-    stats3[2] = t;
-  }
+  adv_stats_block_1024(N, stats3, [&](int i) { return adv[i]; });       // (adv_stats.h: shared with the step's head launch)
 }
 
 // Large N (the scaled micro-benchmark, data-parallel epochs at many workers): the one-workgroup kernel above reads at 6 GB/s

@@ -7,7 +7,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: torch ships its ow
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libetm_hip.so")     # (diagnostic tools that load another build assign this before load())
-ABI_VERSION = 49
+ABI_VERSION = 50
 
 _lib = None
 
@@ -57,6 +57,9 @@ SIGNATURES = {
     "etm_conv_pack_weights": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "etm_gather_rows": (_I, [_P, _P, _P, _I, _P, _L, _L, _P]),
     "etm_group_norms": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P]),
+    "etm_step_head": (_I, [_P, _P, _P, _I, _P, _I, _P, _L, _L, _P, _P, _P, _P]),
+    "etm_group_norms_step": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P]),
+    "etm_step_end": (_I, [_P, _I, _P, _I, _P, _P]),
     "etm_relu_bwd_colsum_workspace_bytes": (_L, [_I, _I]),
     "etm_relu_bwd_colsum": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _P]),
     "etm_host_copier_create": (_P, [_I]),
@@ -134,6 +137,8 @@ SIGNATURES = {
     "etm_grouped_dw_supported": (_I, [_I, _I, _I, _I, _I, _I]),
     "etm_grouped_dw_max_problems": (_I, []),
     "etm_grouped_dw": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "etm_grouped_dw_tail_max_problems": (_I, []),
+    "etm_grouped_dw_tail": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "etm_grad_sqnorm": (_I, [_P, _L, _P, _I, _P, _P]),
     "etm_adamw_clip": (_I, [_P, _P, _P, _P, _L, _P, _I, _P, _P, _D, _D, _D, _D, _F, _F, _P, _P]),
     "etm_gae": (_I, [_P, _P, _P, _P, _F, _F, _P, _I, _I, _P]),

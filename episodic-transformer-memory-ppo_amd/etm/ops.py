@@ -428,8 +428,9 @@ class DeferredDw:
     active = None
     last_flops = 0.0             # 2 * N * Ma * Nb summed over the problems of the most recent grouped launch (bench.py prices it with this)
 
-    def __init__(self, dest):
+    def __init__(self, dest, tail=True):
         self.dest = dest
+        self.tail = tail         # the column sums of flush() ride in the grouped launch (etm_grouped_dw_tail); False: a launch of their own
         self.rows = {}           # parameter data_ptr -> [(first row, rows)] already taken (a second use of the same rows is refused)
         self.items = []          # (A, B, C view, Ma, Nb, lda, ldb, ldc)
         self.colsums = []        # (partial sums, first column, rows P, columns C, row stride, destination view)
@@ -551,23 +552,28 @@ class DeferredDw:
         return [sums[c0: c0 + cols] for c0, cols, _ in parts]
 
     def flush(self):
-        if self.conv_wgrads:
-            _conv_wgrad_reduce(self.conv_wgrads)
-            self.conv_wgrads = []
-        if self.colsums:
-            _colsum_reduce(self.colsums)
-            self.colsums = []
-        if not self.items:
-            return
         lib = _lib.load()
         cap = lib.etm_grouped_dw_max_problems()          # problems per launch (the kernel-argument table: 84)
-        for lo in range(0, len(self.items), cap):
-            items = self.items[lo: lo + cap]
+        tail = bool(self.tail and self.items and self.colsums and all(max(c[2], c[3], c[4]) < 65536 for c in self.colsums))
+        if self.conv_wgrads:
+            _conv_wgrad_reduce(self.conv_wgrads)
+        if self.colsums and not tail:
+            _colsum_reduce(self.colsums)
+        lo = 0
+        while lo < len(self.items):
+            # (the tail launch carries the column-sum jobs in its argument table: fewer problems fit beside them)
+            items = self.items[lo: lo + (lib.etm_grouped_dw_tail_max_problems() if tail and lo == 0 else cap)]
             dims = _c_ints([v for it in items for v in it[3:8]])
-            _lib.check(lib.etm_grouped_dw(_c_ptrs([_ptr(it[0]) + 4 * it[8] for it in items]), _c_ptrs([it[1] for it in items]),
-                                          _c_ptrs([it[2] for it in items]), dims, len(items), self.N, _stream()), "etm_grouped_dw")
-        DeferredDw.last_flops = float(sum(2.0 * self.N * it[3] * it[4] for it in self.items))
-        self.items = []
+            args = (_c_ptrs([_ptr(it[0]) + 4 * it[8] for it in items]), _c_ptrs([it[1] for it in items]), _c_ptrs([it[2] for it in items]), dims,
+                    len(items), self.N)
+            if tail and lo == 0:
+                _lib.check(lib.etm_grouped_dw_tail(*args, *_colsum_args(self.colsums), _stream()), "etm_grouped_dw_tail")
+            else:
+                _lib.check(lib.etm_grouped_dw(*args, _stream()), "etm_grouped_dw")
+            lo += len(items)
+        if self.items:
+            DeferredDw.last_flops = float(sum(2.0 * self.N * it[3] * it[4] for it in self.items))
+        self.items, self.colsums, self.conv_wgrads = [], [], []
 
     def pack(self, params, views, grads):
         """After backward: the gradients ``grads`` of ``params`` (their ``.grad`` or torch.autograd.grad's outputs; None: parameter
@@ -594,11 +600,15 @@ def _c_ints(values):
     return (ctypes.c_int32 * len(values))(*values)
 
 
-def _colsum_reduce(problems):
-    """etm_colsum_reduce_grouped over ``problems`` = [(partial sums, first column, rows P, columns C, row stride, destination)]."""
+def _colsum_args(problems):
+    """The arguments of etm_colsum_reduce_grouped for ``problems`` = [(partial sums, first column, rows P, columns C, row stride,
+    destination)]."""
     partial, c0, P, C, ld, out = zip(*problems)
-    _lib.check(_lib.load().etm_colsum_reduce_grouped(_c_ptrs([_ptr(p) + 4 * c for p, c in zip(partial, c0)]), _c_ints(P), _c_ints(C),
-                                                     _c_ints(ld), _c_ptrs(out), len(problems), _stream()), "etm_colsum_reduce_grouped")
+    return (_c_ptrs([_ptr(p) + 4 * c for p, c in zip(partial, c0)]), _c_ints(P), _c_ints(C), _c_ints(ld), _c_ptrs(out), len(problems))
+
+
+def _colsum_reduce(problems):
+    _lib.check(_lib.load().etm_colsum_reduce_grouped(*_colsum_args(problems), _stream()), "etm_colsum_reduce_grouped")
 
 
 def _conv_wgrad_reduce(problems):
@@ -1034,6 +1044,41 @@ def gather_rows(fields, idx):
         rb = (ctypes.c_int64 * m)(*[r for _, r in sel])
         _lib.check(lib.etm_gather_rows(src, dst, rb, m, _ptr(idx), n, fields[sel[0][0]].shape[0], _stream()), "etm_gather_rows")
     return outs
+
+
+def step_head(fields, idx_table, counter, idx_out=None, adv_src=None):
+    """Head of a minibatch step in one launch (etm_step_head).  idx = row ``counter[0] % rows`` of ``idx_table`` [rows, n] (int64;
+    ``counter`` None: row 0).  Returns (``gather_rows(fields, idx)``, ``adv_stats(adv_src[idx])`` or None when ``adv_src`` is None)
+    and writes idx into ``idx_out`` [n] if given.  n must be below the split of ``adv_stats`` when ``adv_src`` is given."""
+    lib = _lib.load()
+    rows, n = idx_table.shape
+    if idx_table.dtype != torch.int64 or not idx_table.is_contiguous() or (counter is not None and counter.dtype != torch.int64):
+        raise TypeError("step_head: the index table and the counter must be contiguous int64 tensors")
+    src_rows = fields[0].shape[0] if fields else adv_src.shape[0]
+    outs, sel = [None] * len(fields), []
+    for k, t in enumerate(fields):          # (the rule of gather_rows: other tensors go through index_select on idx_out below)
+        row = t[0].numel() * t.element_size() if t.shape[0] > 0 else 0
+        if t.is_contiguous() and 0 < row <= 4096 and row % 4 == 0 and t.shape[0] == src_rows and len(sel) < 16:
+            outs[k] = torch.empty((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+            sel.append((k, row))
+        elif idx_out is None:
+            raise ValueError("step_head: a field outside the gather launch needs idx_out")
+    stats = None
+    if adv_src is not None:
+        if adv_src.dtype != torch.float32 or not adv_src.is_contiguous() or adv_src.numel() != src_rows or lib.etm_adv_stats_workspace_bytes(n) > 0:
+            raise ValueError("step_head: advantages outside the one-workgroup statistics kernel")
+        stats = torch.empty(3, dtype=torch.float32, device=adv_src.device)
+    m = len(sel)
+    src = (ctypes.c_void_p * max(m, 1))(*[fields[k].data_ptr() for k, _ in sel])
+    dst = (ctypes.c_void_p * max(m, 1))(*[outs[k].data_ptr() for k, _ in sel])
+    rb = (ctypes.c_int64 * max(m, 1))(*[r for _, r in sel])
+    _lib.check(lib.etm_step_head(src, dst, rb, m, _ptr(idx_table), rows, _ptr(counter) if counter is not None else None, n, src_rows,
+                                 _ptr(idx_out) if idx_out is not None else None, _ptr(adv_src) if adv_src is not None else None,
+                                 _ptr(stats) if stats is not None else None, _stream()), "etm_step_head")
+    for k, t in enumerate(fields):
+        if outs[k] is None:
+            outs[k] = t.index_select(0, idx_out)
+    return outs, stats
 
 
 def rollout_hidden_partial(x, wt, out=None):

@@ -1026,6 +1026,16 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         # their window rows, which the window pass -- every XCD handles a contiguous chunk of the samples -- turns into L2 hits
         # (measured at config 3: 37.9 -> 29.9 us per pass).  One sort per epoch covers all of its minibatches.
         sort_mb = bool(self.config.get("sort_minibatch", True))
+        # step_ends_fused (default on; False: the wiring before it, kept for the bit-for-bit test): the captured step takes its
+        # minibatch from a device-resident table of the epoch's index vectors and files its results in device-resident tables, under a
+        # device-resident step counter -- no copy between two replays (DESIGN section 4 "The ends of the step")
+        n_mb = self.buffer.n_mini_batches
+        tables = bool(self._use_train_graph and self.config.get("step_ends_fused", True) and mbs * n_mb == self.buffer.batch_size
+                      and (perms is None or all(len(p) == self.buffer.batch_size for p in perms)))
+        row = 0
+        if tables:
+            self._step_tables(mbs)
+            self._tg_counter.zero_()
         for epoch in range(self.config["epochs"]):
             if perms is None:
                 perm = torch.randperm(self.buffer.batch_size, device=self.device)
@@ -1034,6 +1044,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             if sort_mb and perm.numel() % mbs == 0:
                 perm = perm.view(-1, mbs).sort(dim=1).values.reshape(-1)
             self._epoch_stats3 = None
+            if tables:
+                self._tg_idx_table.copy_(perm.view(n_mb, mbs))       # the index vectors of the whole epoch: one copy
             if self.dp is not None and self.dp.active and perm.numel() % mbs == 0:
                 # data parallel: the global-minibatch advantage statistics of ALL minibatches of the epoch from one all-gather
                 # (they depend only on the advantages and the permutation, not on the weights)
@@ -1043,6 +1055,10 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             for start in range(0, self.buffer.batch_size, mbs):
                 idx = perm[start: start + mbs]
                 self._mb_stats3 = self._epoch_stats3[start // mbs] if self._epoch_stats3 is not None else None
+                if tables:
+                    self._train_step_graph(idx, learning_rate, clip_range, beta, monitor, row=row)
+                    row += 1
+                    continue
                 if self._use_train_graph and idx.numel() == mbs:
                     st_row, norm_row = self._train_step_graph(idx, learning_rate, clip_range, beta, monitor)
                     stats.append(st_row)
@@ -1053,12 +1069,13 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                 stats.append(self._train_mini_batch(mini_batch, learning_rate, clip_range, beta))
                 if monitor:
                     norms.append(self._grad_group_norms())
-        train_info = torch.stack(stats).cpu().numpy()          # the only host sync of the optimisation phase
+        # the only host sync of the optimisation phase
+        train_info = (self._tg_stats_tab[:row] if tables else torch.stack(stats)).cpu().numpy()
         self._bank_pos = self._row_stats = None
         self._mb_stats3 = self._epoch_stats3 = None
         grad_info = {}
-        if norms:
-            allnorms = torch.stack(norms).cpu().numpy()
+        if norms or (tables and monitor):
+            allnorms = (self._tg_norm_tab[:row] if tables else torch.stack(norms)).cpu().numpy()
             grad_info = {k: allnorms[:, i].tolist() for i, k in enumerate(self._grad_keys)}
         return [row for row in train_info], grad_info
 
@@ -1195,14 +1212,42 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         self._obs_nhwc_buf.copy_(obs.permute(0, 2, 3, 1))
         return self._obs_nhwc_buf
 
-    def _train_body_a(self, idx, clip_range, beta, stats3=None):
+    def _step_tables(self, mbs):
+        """Device-resident state of the table-driven step (allocated with ``_tg_idx``, whose address the captured graph holds too):
+        the step counter, the epoch's index vectors [n_mini_batch, mbs], the statistics and gradient-norm rows of a whole update."""
+        if getattr(self, "_tg_idx", None) is None or self._tg_idx.numel() != mbs:
+            self._tg_idx = torch.empty(mbs, dtype=torch.long, device=self.device)
+            self._tg_stats3 = torch.zeros(3, dtype=torch.float32, device=self.device) if self.dp is not None else None
+            self._tg_idx_table, self._train_graph = None, None        # (a graph captured at another size holds the old addresses)
+        if getattr(self, "_tg_idx_table", None) is None:
+            n_mb, steps = self.buffer.n_mini_batches, self.config["epochs"] * self.buffer.n_mini_batches
+            self._tg_counter = torch.zeros(1, dtype=torch.long, device=self.device)
+            self._tg_idx_table = torch.zeros((n_mb, mbs), dtype=torch.long, device=self.device)
+            self._tg_stats_tab = torch.zeros((steps, 6), dtype=torch.float32, device=self.device)
+            self._tg_norm_tab = torch.zeros((steps, len(self._grad_keys)), dtype=torch.float32, device=self.device)
+
+    def _gather_minibatch(self, keys, idx, stats3, head):
+        """The per-sample fields ``keys`` of the minibatch as a dict, and the advantage statistics.  ``head``: ``idx`` is the step's
+        fixed-address index vector, and ONE launch (etm_step_head) fills it from row ``counter`` of the epoch's index table, gathers
+        the fields through that row and, when ``stats3`` is None, computes the statistics.  Else: ``gather_rows`` on ``idx``."""
+        buf = self.buffer
+        fields = [buf.samples_flat[k] for k in keys]
+        if not head:
+            return dict(zip(keys, ops.gather_rows(fields, idx))), stats3
+        adv = buf.samples_flat["advantages"]
+        own = stats3 is None and etm_lib.load().etm_adv_stats_workspace_bytes(idx.numel()) == 0      # (larger: adv_stats' split form)
+        outs, st3 = ops.step_head(fields, self._tg_idx_table, self._tg_counter, idx_out=idx, adv_src=adv if own else None)
+        return dict(zip(keys, outs)), (st3 if own else stats3)
+
+    def _train_body_a(self, idx, clip_range, beta, stats3=None, head=False):
         """First half of one optimiser step on the minibatch ``idx`` (device int64 [mbs], fixed address): gather, forward,
         loss, backward, gradients packed into the flat bucket.  ``stats3``: (count, mean, M2) of the GLOBAL minibatch's
-        advantages (data-parallel runs merge them over ranks before this graph); None: computed here.  Returns stats[6]."""
+        advantages (data-parallel runs merge them over ranks before this graph); None: computed here.  ``head``: see
+        ``_gather_minibatch``.  Returns stats[6]."""
         buf = self.buffer
         skip = ("obs",) if self._obs_train is not None else ()
         keys = [k for k in buf.samples_flat if k not in skip]
-        mb = dict(zip(keys, ops.gather_rows([buf.samples_flat[k] for k in keys], idx)))    # one launch for the small fields
+        mb, stats3 = self._gather_minibatch(keys, idx, stats3, head)    # one launch for the small fields
         if self._bank_pos is not None:
             spec = WindowSpec.from_bank(self._bank_pos_buf, mb["memory_index"], mb["memory_indices"], None, mb["memory_mask"])
             spec.pos_included = True
@@ -1229,7 +1274,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             p.grad = None
         # the weight gradients of the dense layers (dW = dy^T x, a contraction over the minibatch with a small output) are collected
         # during backward and computed by ONE grouped launch straight into their arena views (csrc/grouped_dw.hip)
-        with ops.DeferredDw(self._dw_destinations()) as dw:
+        with ops.DeferredDw(self._dw_destinations(), tail=bool(self.config.get("step_ends_fused", True))) as dw:
             loss.backward(self._unit_gradient(loss))
         dw.pack(self.params, self._grad_views, [p.grad for p in self.params])
         for p, v in zip(self.params, self._grad_views):
@@ -1256,23 +1301,44 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         self._bank_pos = self._row_stats = None
         return grads
 
-    def _train_body_b(self, monitor):
+    def _train_body_b(self, monitor, stats=None):
         """Second half: global-norm clipping (same rule as torch.nn.utils.clip_grad_norm_, upstream :311) on the flat bucket,
-        fused AdamW, monitored gradient norms."""
+        fused AdamW, monitored gradient norms.  ``stats`` (the table-driven step): the step's statistics; they and the norms are
+        filed under row ``counter`` of the result tables and the counter moves on, inside the norm monitor's two launches."""
         self.optimizer.step(self.config["max_grad_norm"], grad_scale=self._grad_scale())
-        return self._grad_group_norms() if monitor else None
+        if stats is None:
+            return self._grad_group_norms() if monitor else None
+        if stats.numel() != self._tg_stats_tab.shape[1] or stats.dtype != torch.float32 or not stats.is_contiguous():
+            raise RuntimeError("the step's statistics do not fit the rows of the statistics table")
+        if monitor:
+            return self._grad_group_norms(step=(stats, self._tg_stats_tab, self._tg_norm_tab, self._tg_counter))
+        etm_lib.check(etm_lib.load().etm_step_end(stats.data_ptr(), stats.numel(), self._tg_stats_tab.data_ptr(), self._tg_stats_tab.shape[0],
+                                                  self._tg_counter.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream), "etm_step_end")
+        return None
 
-    def _train_step_graph(self, idx, learning_rate, clip_range, beta, monitor):
+    def _train_step_graph(self, idx, learning_rate, clip_range, beta, monitor, row=None):
         """Minibatch step through captured graphs (two eager warm-up steps first).  Single GPU: one graph.  Data parallel: the
         merged advantage statistics are computed eagerly first (one all-gather per epoch), then ONE graph that holds the packed
         gradients' RCCL all-reduce between the backward pass and clip + AdamW (round 6; upstream insertion point trainer.py:310-311)
         when the library collective's captured form passed its self-test on every rank (etm/dist.py: graph_collective_ok) --
-        otherwise graph A, the all-reduce as a host call, graph B.  Returns (stats[6], norms or None)."""
+        otherwise graph A, the all-reduce as a host call, graph B.  Returns (stats[6], norms or None).
+        ``row`` (``_train_epochs``, table-driven step): ``idx`` is row ``row % n_mini_batch`` of the index table already and the
+        device counter stands at ``row``; the results stay in row ``row`` of the result tables and nothing is returned."""
         dp = self.dp
+        tables = bool(self.config.get("step_ends_fused", True))
         if getattr(self, "_tg_idx", None) is None:
-            self._tg_idx = torch.empty_like(idx)
-            self._tg_stats3 = torch.zeros(3, dtype=torch.float32, device=self.device) if dp is not None else None
-        self._tg_idx.copy_(idx)
+            if tables:
+                self._step_tables(idx.numel())
+            else:
+                self._tg_idx = torch.empty_like(idx)
+                self._tg_stats3 = torch.zeros(3, dtype=torch.float32, device=self.device) if dp is not None else None
+                self._tg_idx_table = None
+        tables = self._tg_tables = tables and self._tg_idx_table is not None
+        if not tables:
+            self._tg_idx.copy_(idx)
+        elif row is None:                   # a single step asked for from outside _train_epochs: an "update" of one step
+            self._tg_counter.zero_()
+            self._tg_idx_table[0].copy_(idx)
         self._set_lr(learning_rate)
         if self._sched_host[1] != clip_range or self._sched_host[2] != beta:
             self._dyn.copy_(torch.tensor([clip_range, beta], dtype=torch.float64))
@@ -1281,7 +1347,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             if getattr(self, "_mb_stats3", None) is not None:
                 self._tg_stats3.copy_(self._mb_stats3)
             else:
-                adv = self.buffer.samples_flat["advantages"].index_select(0, self._tg_idx)
+                adv = self.buffer.samples_flat["advantages"].index_select(0, idx if tables else self._tg_idx)
                 self._tg_stats3.copy_(dp.merge_adv_stats(ops.adv_stats(adv)))
         self._mb_counter += 1
         sample_eager = self.profile_sample_every and self._mb_counter % self.profile_sample_every == 0
@@ -1292,15 +1358,17 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         if (self._train_graph is None and self._train_warm < 2) or sample_eager:
             self._train_warm += 1
             if overlap:
-                st, dfe = self._train_body_a1(self._tg_idx, clip_range, beta, self._tg_stats3)
+                st, dfe = self._train_body_a1(self._tg_idx, clip_range, beta, self._tg_stats3, head=tables)
                 self._allreduce_rest_async()
                 self._train_body_a2(dfe)
                 self._allreduce_conv_and_join()
             else:
-                st = self._train_body_a(self._tg_idx, clip_range, beta, self._tg_stats3)
+                st = self._train_body_a(self._tg_idx, clip_range, beta, self._tg_stats3, head=tables)
                 if dp is not None:
                     dp.all_reduce_grads(average=False)
-            nm = self._train_body_b(monitor)
+            nm = self._train_body_b(monitor, st if tables else None)
+            if tables:
+                return self._step_rows(row, monitor)
             return st.clone(), (nm.clone() if nm is not None else None)
         if self._train_graph is None or self._tg_key != key:
             torch.cuda.synchronize(self.device)
@@ -1316,11 +1384,11 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                 pool = torch.cuda.graph_pool_handle() if overlap else None
                 with torch.cuda.graph(ga, pool=pool, capture_error_mode="thread_local"):
                     if overlap:
-                        self._tg_stats, self._tg_dfeats = self._train_body_a1(self._tg_idx, clip_range, beta, self._tg_stats3)
+                        self._tg_stats, self._tg_dfeats = self._train_body_a1(self._tg_idx, clip_range, beta, self._tg_stats3, head=tables)
                     else:
-                        self._tg_stats = self._train_body_a(self._tg_idx, clip_range, beta, self._tg_stats3)
+                        self._tg_stats = self._train_body_a(self._tg_idx, clip_range, beta, self._tg_stats3, head=tables)
                     if dp is None:
-                        self._tg_norms = self._train_body_b(monitor)
+                        self._tg_norms = self._train_body_b(monitor, self._tg_stats if tables else None)
                 if overlap:
                     ga2 = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(ga2, pool=pool, capture_error_mode="thread_local"):
@@ -1328,7 +1396,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                 if dp is not None:
                     gb = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(gb, pool=pool, capture_error_mode="thread_local"):
-                        self._tg_norms = self._train_body_b(monitor)
+                        self._tg_norms = self._train_body_b(monitor, self._tg_stats if tables else None)
             self._train_graph, self._tg_key, self._train_graph_a2 = (ga, gb), key, ga2
             self._dp_one_graph = one_graph
             self.buffer.address_captured = True
@@ -1343,7 +1411,16 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             else:
                 dp.all_reduce_grads(average=False)
             gb.replay()
+        if tables:
+            return self._step_rows(row, monitor)
         return self._tg_stats.clone(), (self._tg_norms.clone() if monitor else None)
+
+    def _step_rows(self, row, monitor):
+        """What a table-driven step hands back: nothing inside ``_train_epochs`` (the rows are read once, after the last step); row 0
+        of the result tables for a single step asked for from outside."""
+        if row is not None:
+            return None, None
+        return self._tg_stats_tab[0].clone(), (self._tg_norm_tab[0].clone() if monitor else None)
 
     def close(self, exit_process: bool = False) -> None:
         """Releases environments and the summary writer (upstream also ``exit(0)``s; opt in with exit_process)."""

@@ -22,13 +22,13 @@ class _DataParallelStep:
     # ---- data-parallel overlap (dp_overlap, SURVEY 8e / upstream insertion point trainer.py:310-311): the backward pass is cut at the
     # encoder output.  Part 1 (heads, transformer, lin_hidden: 98 % of the gradient arena) is summed over the ranks on a side stream
     # while part 2 (the encoder's backward, ~0.5 ms at config 3) runs; the small convolution slice follows on the main stream.
-    def _train_body_a1(self, idx, clip_range, beta, stats3=None):
+    def _train_body_a1(self, idx, clip_range, beta, stats3=None, head=False):
         """Gather, forward, loss, backward DOWN TO the encoder features; every gradient except the convolutions' is in its arena
         view afterwards.  Returns (stats[6], d loss / d features) -- the features themselves stay in ``self.model._encoder_features``."""
         buf = self.buffer
         skip = ("obs",) if self._obs_train is not None else ()
         keys = [k for k in buf.samples_flat if k not in skip]
-        mb = dict(zip(keys, ops.gather_rows([buf.samples_flat[k] for k in keys], idx)))
+        mb, stats3 = self._gather_minibatch(keys, idx, stats3, head)
         if self._bank_pos is not None:
             spec = WindowSpec.from_bank(self._bank_pos_buf, mb["memory_index"], mb["memory_indices"], None, mb["memory_mask"])
             spec.pos_included = True
@@ -52,7 +52,7 @@ class _DataParallelStep:
         rest = self.params[n_conv:]
         for p in self.params:
             p.grad = None
-        with ops.DeferredDw(self._dw_destinations()) as dw:
+        with ops.DeferredDw(self._dw_destinations(), tail=bool(self.config.get("step_ends_fused", True))) as dw:
             got = torch.autograd.grad(loss, [feats] + rest, grad_outputs=self._unit_gradient(loss), allow_unused=True)
         dw.pack(rest, self._grad_views[n_conv:], got[1:])
         return stats, got[0]
@@ -62,7 +62,7 @@ class _DataParallelStep:
         feats = self.model._encoder_features
         n_conv = self._n_conv_params
         convs = self.params[:n_conv]
-        with ops.DeferredDw(self._dw_destinations()) as dw:
+        with ops.DeferredDw(self._dw_destinations(), tail=bool(self.config.get("step_ends_fused", True))) as dw:
             got = torch.autograd.grad(feats, convs, grad_outputs=dfeats, allow_unused=True)
         dw.pack(convs, self._grad_views[:n_conv], got)
         for p, v in zip(self.params, self._grad_views):
@@ -98,14 +98,14 @@ class _DataParallelStep:
         try:
             with torch.cuda.graph(ga, capture_error_mode="thread_local"):
                 if overlap:
-                    self._tg_stats, dfe = self._train_body_a1(self._tg_idx, clip_range, beta, self._tg_stats3)
+                    self._tg_stats, dfe = self._train_body_a1(self._tg_idx, clip_range, beta, self._tg_stats3, head=self._tg_tables)
                     self._allreduce_rest_async()
                     self._train_body_a2(dfe)
                     self._allreduce_conv_and_join()
                 else:
-                    self._tg_stats = self._train_body_a(self._tg_idx, clip_range, beta, self._tg_stats3)
+                    self._tg_stats = self._train_body_a(self._tg_idx, clip_range, beta, self._tg_stats3, head=self._tg_tables)
                     self.dp.all_reduce_grads(average=False)
-                self._tg_norms = self._train_body_b(monitor)
+                self._tg_norms = self._train_body_b(monitor, self._tg_stats if self._tg_tables else None)
             return ga
         except Exception as exc:       # noqa: BLE001
             print(f"[etm] one-graph data-parallel step not captured ({exc!r}); using graph A -> all-reduce -> graph B", file=sys.stderr, flush=True)
@@ -248,8 +248,22 @@ class _RunOutputs:
         self._seg_member = member[:, owner].contiguous().to(self.device)
         self._seg_partial = torch.empty(len(starts), dtype=torch.float32, device=self.device)
 
-    def _grad_group_norms(self):
-        if self.flat_grads.is_cuda and all(p.grad is not None and p.grad.data_ptr() == v.data_ptr() for p, v in zip(self.params[:2], self._grad_views[:2])):
+    def _grad_group_norms(self, step=None):
+        """The monitored norms.  ``step`` = (statistics, statistics table, norm table, counter) of the table-driven step: the same two
+        launches also file the statistics and the norms under row ``counter`` of the tables and advance the counter."""
+        arena = self.flat_grads.is_cuda and all(p.grad is not None and p.grad.data_ptr() == v.data_ptr() for p, v in zip(self.params[:2], self._grad_views[:2]))
+        if step is not None:
+            if not arena:
+                raise RuntimeError("the table-driven step needs the gradients in the flat arena")
+            stats, stats_tab, norm_tab, counter = step
+            out = torch.empty(len(self._grad_keys), dtype=torch.float32, device=self.device)
+            etm_lib.check(etm_lib.load().etm_group_norms_step(self.flat_grads.data_ptr(), self._seg_start.data_ptr(), self._seg_len.data_ptr(),
+                                                              self._seg_start.numel(), self._seg_member.data_ptr(), len(self._grad_keys),
+                                                              self._seg_partial.data_ptr(), out.data_ptr(), norm_tab.data_ptr(), stats.data_ptr(),
+                                                              stats.numel(), stats_tab.data_ptr(), stats_tab.shape[0], counter.data_ptr(),
+                                                              torch.cuda.current_stream(self.device).cuda_stream), "etm_group_norms_step")
+            return out
+        if arena:
             out = torch.empty(len(self._grad_keys), dtype=torch.float32, device=self.device)
             etm_lib.check(etm_lib.load().etm_group_norms(self.flat_grads.data_ptr(), self._seg_start.data_ptr(), self._seg_len.data_ptr(),
                                                          self._seg_start.numel(), self._seg_member.data_ptr(), len(self._grad_keys),

@@ -362,6 +362,18 @@ int etm_grouped_dw_max_problems(void);
 int etm_grouped_dw(const float *const *A, const float *const *B, float *const *C, const int32_t *dims, int n_problems, int N,
                    void *stream);
 
+/* The tail launch (ABI 50; DESIGN section 4 "The ends of the step"): etm_grouped_dw with the grouped column-sum reduction that ends a
+ * backward pass on extra workgroups of the SAME launch, numbered after the tile workgroups -- it runs on the CUs the tiles leave
+ * idle (216 tiles on 256 CUs at config 3) instead of alone on the chip in front of it.
+ *   A .. N: as etm_grouped_dw, n_problems <= etm_grouped_dw_tail_max_problems() (the job table shares the 4 KB of kernel arguments);
+ *   cs_*, n_cs (1 .. 64): the arguments of etm_colsum_reduce_grouped, P / C / ld below 65536.
+ * The reduction runs the device body of that entry point (csrc/tail_jobs.h: 256 threads in both launches, the same code), so every
+ * output holds the bits the two separate launches give.  No workgroup reads what another writes. */
+int etm_grouped_dw_tail_max_problems(void);
+int etm_grouped_dw_tail(const float *const *A, const float *const *B, float *const *C, const int32_t *dims, int n_problems, int N,
+                        const float *const *cs_partial, const int *cs_P, const int *cs_C, const int *cs_ld, float *const *cs_out, int n_cs,
+                        void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Optimiser step on flat fp32 arenas, replaces `clip_grad_norm_(parameters, max_grad_norm)` + `optimizer.step()` of
  * trainer.py:311-312 (torch.optim.AdamW: betas (0.9, 0.999), eps 1e-8, weight_decay 0.01 unless the caller says otherwise).
@@ -586,6 +598,29 @@ int etm_group_norms(const float *flat, const int64_t *seg_start, const int32_t *
  * pointers / byte counts; rows are contiguous, row_bytes % 4 == 0; every src[f] has src_rows rows.  Bit-exact data movement. */
 int etm_gather_rows(const void *const *src, void *const *dst, const int64_t *row_bytes, int n_fields, const int64_t *idx, int64_t n,
                     int64_t src_rows, void *stream);
+
+/* The two ends of the captured optimisation step (ABI 50; DESIGN section 4 "The ends of the step"): a replayed graph walks through the
+ * minibatches of an update by itself, under a device-resident step counter, with no copy in front of or behind a replay.
+ *
+ * etm_step_head: the jobs at the front of the step that depend only on the minibatch indices, in ONE launch, a workgroup range per
+ * job.  idx = row (*counter % table_rows) of idx_table [table_rows, n] int64 (the index vectors of a whole epoch; counter NULL: row 0).
+ *   - etm_gather_rows(src, dst, row_bytes, n_fields, idx, n, src_rows) (same arguments, same limits; n_fields may be 0);
+ *   - idx_out [n] (may be NULL) = idx: the fixed-address index vector that later kernels of the step read;
+ *   - stats3 (may be NULL, then adv_src too) = etm_adv_stats of the vector adv_src[idx[i]], i < n (adv_src: src_rows floats), bit for
+ *     bit: the same workgroup, the same order.  n >= ETM_ADV_STATS_SPLIT_MIN with stats3: ETM_EUNSUPPORTED.
+ * No job reads what another writes.  Out-of-range indices are clamped as etm_gather_rows clamps them. */
+int etm_step_head(const void *const *src, void *const *dst, const int64_t *row_bytes, int n_fields, const int64_t *idx_table, int table_rows,
+                  const int64_t *counter, int64_t n, int64_t src_rows, int64_t *idx_out, const float *adv_src, float *stats3, void *stream);
+
+/* etm_group_norms (same arguments, same bits in `out`) that also ends the minibatch step: with r = *counter,
+ * stats_table [table_rows, n_stats] row r = stats [n_stats], norm_table [table_rows, n_groups] row r = out, *counter = r + 1.  The
+ * counter is advanced with a plain store by the one workgroup of the first launch that reads it; the second launch files its row
+ * under *counter - 1.  r outside the table: its nearest row.  The host resets the counter at the start of an update and reads the
+ * tables after its last step.  etm_step_end: the statistics row and the counter alone (steps without the norm monitor). */
+int etm_group_norms_step(const float *flat, const int64_t *seg_start, const int32_t *seg_len, int n_segs, const float *member, int n_groups,
+                         float *partial, float *out, float *norm_table, const float *stats, int n_stats, float *stats_table, int table_rows,
+                         int64_t *counter, void *stream);
+int etm_step_end(const float *stats, int n_stats, float *stats_table, int table_rows, int64_t *counter, void *stream);
 
 /* Host-side helper of the in-process environment front-ends (no device work): a memcpy split over `threads` threads (the
  * caller + threads - 1 helpers that spin briefly after a job and sleep otherwise).  The reference produces the observations of a
