@@ -99,6 +99,13 @@ class ActorCriticModel(nn.Module):
         h1, w1 = (hh - 8) // 4 + 1, (ww - 8) // 4 + 1
         return ww % 4 == 0 and obs.shape[1] * 1 >= 1 and h1 >= 4 and w1 >= 4 and ((h1 - 4) // 2 + 1) >= 3 and ((w1 - 4) // 2 + 1) >= 3
 
+    def conv2_output_hw(self):
+        """Spatial size of the encoder's activations after conv1 and conv2 (the input of conv3)."""
+        h, w = self.observation_space_shape[-2:]
+        for cv in (self.conv1, self.conv2):
+            h, w = (h - cv.kernel_size[0]) // cv.stride[0] + 1, (w - cv.kernel_size[1]) // cv.stride[1] + 1
+        return h, w
+
     def refresh_rollout_weights(self):
         """(Re)build the weight copies / packings the rollout kernels read.  Buffers keep their address (the captured rollout graph
         reads them); called by the trainer at the start of every rollout and lazily whenever a weight's version counter moved.

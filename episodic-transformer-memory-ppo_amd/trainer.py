@@ -21,9 +21,9 @@ There is no CPU path: constructing the trainer without a HIP device raises.
 """
 import os
 import sys
-import pickle
 import time
 from collections import deque
+from functools import partial
 
 import numpy as np
 import torch
@@ -47,6 +47,7 @@ from etm.ops import WindowSpec
 from etm.optim import FlatAdamW
 from model import ActorCriticModel, IndexedObservations
 from utils import polynomial_decay, process_episode_info
+from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
 from trainer_parts import _DataParallelStep, _NativeRolloutDrive, _RunOutputs
 
 
@@ -121,6 +122,12 @@ def check_box_policy(config: dict, A=None):
     return A
 
 
+def time_major(table, src):
+    """The host table ``src`` [W, S(, B)] in the layout and type of the fixed-address device table ``table`` [S, W(, B)]."""
+    x = torch.as_tensor(np.asarray(src), dtype=table.dtype)
+    return x.reshape((table.shape[1], table.shape[0]) + tuple(table.shape[2:])).transpose(0, 1)
+
+
 class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
     def __init__(self, config: dict, run_id: str = "run", device: torch.device = None, env=None, dp=None,
                  first_worker_id: int = 0, tensorboard: bool = True) -> None:
@@ -130,12 +137,13 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         if device.type != "cuda":
             raise RuntimeError("PPOTrainer needs an MI355X (HIP) device: this build has no CPU training path "
                                "(the CPU restatement under oracle/ is test infrastructure only)")
-        etm_lib.load()  # fail loudly if the kernels are not built
+        self._etm = etm_lib.load()  # fail loudly if the kernels are not built
         # (placement of the step kernel's workgroups: a worker's whole team on one XCD, the library's default; the member-per-XCD map
         # measured equal -- 111.9 vs 112.2 us per step graph -- and is a kernel-level test only since round 6)
-        etm_lib.check(etm_lib.load().etm_rollout_trxl_set_placement(0), "etm_rollout_trxl_set_placement")
+        etm_lib.check(self._etm.etm_rollout_trxl_set_placement(0), "etm_rollout_trxl_set_placement")
         self.config = config
         self.device = device
+        self._dev_index = device.index if device.index is not None else torch.cuda.current_device()
         self.run_id = run_id
         self.dp = dp
         self.num_workers = config["n_workers"]
@@ -295,7 +303,6 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         # fixed-address operands of the rollout step (HIP-graph friendly) and time-major staging of the step outputs
         S, L, B = config["worker_steps"], self.memory_length, self._action_width
         self._obs_dev = torch.zeros((W,) + obs_shape, dtype=torch.float32, device=device)
-        self._t_dev = torch.zeros((), dtype=torch.int64, device=device)
         self._stage = {
             "obs": torch.zeros((S, W) + obs_shape, dtype=torch.float32, device=device),
             "memory_mask": torch.zeros((S, W, L), dtype=torch.bool, device=device),
@@ -317,34 +324,36 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             # "sample" (the [S, W] uniforms stay allocated but are not drawn)
             self._normals = torch.zeros((S, W, B), dtype=torch.float32, device=device)
             self._forced_tab = torch.full((S, W, B), float("nan"), dtype=torch.float32, device=device)
-        self._step_graph = None
-        self._act_ready = torch.cuda.Event()
         # observation streaming (graph rollout with the fused encoder): rows of the next observation go from pinned memory
         # straight into their row of the time-major staging array on a second stream while the environments still step
-        self._flag_pin = torch.zeros((1,), dtype=torch.int64).pin_memory()   # step counter written by the sampling kernel
-        self._flag_np = self._flag_pin.numpy()
-        self._host_flag = False      # decided when the step graph is captured
         self._up_stream = torch.cuda.Stream(device=device)
+        self._step_graph = None      # (head, tail or None) of the first group, once captured
         self._chain_log = None       # tools/rollout_profile.py: per-step host timestamps of the first group
-        self._up_done = torch.cuda.Event()
-        self._stream_obs = False     # decided when the step graph is captured
-        self._t_row = torch.zeros((), dtype=torch.int64, device=device)
-        self._item = torch.zeros((self.num_blocks, W, self.embed_dim), dtype=torch.float32, device=device)   # block-major
+        self._plan = None            # the form of the captured step (rollout_plan.RolloutPlan), decided when it is captured
+        self._stage_host = None      # host view of the staging array (direct observation rows)
+        self._stage_read = torch.cuda.Event()      # (direct rows) the update's copy out of the staging array has run
         # rollout K/V cache (weights are frozen while sampling): per worker [T, blocks, 2D] projections of its episode
         self._use_kv_cache = bool(config.get("kv_cache_rollout", True))
         T, nb, D = self.max_episode_length, self.num_blocks, self.embed_dim
         self._kv_cache = torch.zeros((W, T, nb, 2 * D), dtype=torch.float32, device=device)
         self._kv_init = torch.zeros((T, nb, 2 * D), dtype=torch.float32, device=device)
-        self._kv_weights = None
-        self._worker_ids = torch.arange(W, dtype=torch.int64, device=device)
+        self._kv_weights = self._kv_w_blocked = None
+        # (both replays: ``enabled`` is set before every call -- hip_graph_rollout, and the bank has its final address)
+        self._kv_refresh_replay = ops.ReplayAfterWarmup(self._refresh_kv_cache_now, device, what="_refresh_kv_cache")
+        # get_last_value's forward pass as a replay (``_lv.graph`` once captured), carrying its fixed-address operands
+        self._lv = lv = ops.ReplayAfterWarmup(self._last_value_now, device, what="get_last_value")
+        lv.rows, lv.obs = torch.empty((W, L), dtype=torch.int64, device=device), torch.empty_like(self._obs_dev)
+        lv.out = torch.empty(W, dtype=torch.float32, device=device)
 
         # worker groups: the full-width group (eager path, single-group graph path) aliases the buffers above; the pipelined
-        # groups own what cannot be a contiguous slice of them
-        self._group_all = self._make_group(0, W, self.env, full=True)
+        # groups own what cannot be a contiguous slice of them.  WorkerGroup reads from this object, so all of these exist by now:
+        # device, box, _action_width, num_blocks, embed_dim, num_workers, obs / _obs_pin / _act_pin, _ss_pin / _ss_dev, _obs_dev,
+        # _mask_t, _win_t, _act_dev, _kv_cache, _stage["obs"]
+        self._group_all = WorkerGroup(self, 0, W, self.env, True, self._etm.etm_upload)
         parts = getattr(self.env, "parts", None)
         self._groups = [self._group_all]
         if parts is not None and len(parts) > 1:
-            self._groups = [self._make_group(lo, hi, part, full=False) for part, (lo, hi) in zip(parts, self.env.bounds)]
+            self._groups = [WorkerGroup(self, lo, hi, part, False, self._etm.etm_upload) for part, (lo, hi) in zip(parts, self.env.bounds)]
 
         mask, indices = build_window_tables(self.memory_length, self.max_episode_length)
         self.memory_mask, self.memory_indices = mask, indices                       # host copies (upstream names)
@@ -402,39 +411,12 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         return s(self.lr_schedule), s(self.beta_schedule), s(self.cr_schedule)
 
     # ------------------------------------------------------------------ rollout
-    def _make_group(self, lo, hi, env, full):
-        """Device / pinned state of the workers [lo, hi) for one rollout step (see ``rollout_groups``)."""
-        from types import SimpleNamespace
-        dev, Wg, B = self.device, hi - lo, self._action_width
-        g = SimpleNamespace(lo=lo, hi=hi, W=Wg, env=env, full=full, graphs=None, rf_scratch=None)
-        g.obs_pin, g.act_pin = self._obs_pin[lo:hi], self._act_pin[lo:hi]
-        g.obs_np = self.obs[lo:hi]
-        acts = g.act_pin.numpy()
-        g.acts_host = acts[:, 0] if B == 1 and self.box is None else acts    # [Wg] for one branch, [Wg, B] multi-discrete, [Wg, A] Box
-        g.obs_dev, g.mask_t, g.win_t, g.act_dev = self._obs_dev[lo:hi], self._mask_t[lo:hi], self._win_t[lo:hi], self._act_dev[lo:hi]
-        g.kv = self._kv_cache[lo:hi]
-        if full:
-            g.ss_pin, g.ss_dev, g.item, g.t_dev, g.t_row = self._ss_pin, self._ss_dev, self._item, self._t_dev, self._t_row
-            g.ids, g.flag_pin, g.act_ready, g.up_done, g.stream = self._worker_ids, self._flag_pin, self._act_ready, self._up_done, None
-        else:
-            g.ss_pin = torch.zeros((2, Wg), dtype=torch.int64).pin_memory()
-            g.ss_dev = torch.zeros((2, Wg), dtype=torch.int64, device=dev)
-            g.item = torch.zeros((self.num_blocks, Wg, self.embed_dim), dtype=torch.float32, device=dev)
-            g.t_dev = torch.zeros((), dtype=torch.int64, device=dev)
-            g.t_row = torch.zeros((), dtype=torch.int64, device=dev)
-            g.ids = torch.arange(Wg, dtype=torch.int64, device=dev)
-            g.flag_pin = torch.zeros((1,), dtype=torch.int64).pin_memory()
-            g.act_ready, g.up_done = torch.cuda.Event(), torch.cuda.Event()
-            g.stream = torch.cuda.Stream(device=dev)
-        g.ss_np = g.ss_pin.numpy()
-        g.flag_np = g.flag_pin.numpy()
-        g.step_dev, g.slot_dev = g.ss_dev[0], g.ss_dev[1]
-        # (episode step, slot) as LATCHED by the head of a step for its tail: the host uploads the next step's block on the
-        # upload stream while the tail (bank / cache writes under env.step) may still be running, and only the group's own
-        # stream orders tail t before head t + 1 -- so the tail must not read the uploaded block itself
-        g.ss_latch = torch.zeros((2, Wg), dtype=torch.int64, device=dev)
-        g.step_l, g.slot_l = g.ss_latch[0], g.ss_latch[1]
-        return g
+    # the form of the CAPTURED rollout step, read-only views of its plan (no plan -- before the first capture, after the step kernel's
+    # time-out recovery -- reads False; an eager rollout runs on the all-false plan without replacing a captured one)
+    _stream_obs = property(lambda self: self._plan is not None and self._plan.stream_obs)
+    _host_flag = property(lambda self: self._plan is not None and self._plan.host_flag)
+    _native_rollout = property(lambda self: self._plan is not None and self._plan.native)
+    _direct_rows = property(lambda self: self._plan is not None and self._plan.direct_rows)
 
     def _sample_training_data(self, forced_actions=None, uniforms=None, normals=None) -> list:
         """Runs all workers for ``worker_steps`` steps; fills the buffer; returns finished-episode infos.
@@ -446,7 +428,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         while the device runs the other group's head graph.  With the fused encoder the observation rows of step t+1 are
         streamed from pinned memory into row t+1 of the staging array on a second stream while the environments still step
         (``stream_observations``), together with the workers' (episode step, slot) vector; the actions arrive in pinned host
-        memory straight from the sampling kernel.
+        memory straight from the sampling kernel.  Which of these forms apply is the rollout's plan (rollout_plan.py).
         ``forced_actions`` [W, S] or [W, S, B] (optional) replays recorded actions instead of sampling (teacher forcing for parity
         tests -- CPU and GPU RNG streams differ) on whichever path the config selects: the sampling
         kernels read them from a fixed-address table, so the captured graphs, the observation streaming and the worker-group
@@ -455,248 +437,264 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         exactly these values (branch b of a MultiDiscrete policy at its own draw).
         Box policies: ``forced_actions`` [W, S, A] floats (NaN = sample), ``normals`` [W, S, A] (optional, tests) replaces the
         rollout's N(0, 1) draws."""
-        buf, W, S = self.buffer, self.num_workers, self.config["worker_steps"]
         main = torch.cuda.current_stream(self.device)
-        use_graph = bool(self.config.get("hip_graph_rollout", True))
+        plan, groups = self._begin_rollout(main, forced_actions, uniforms, normals)
+        # the device work of a step of a group goes in flight in ONE of three forms
+        launch = self._launch_graph_exec if plan.direct_launch else self._launch_replay if plan.graph else self._launch_eager
+        for g in groups:
+            launch(g, plan)
         episode_infos = []
-        buf.begin_rollout(self._slot_dev)
-        self.worker_episode_slot[:] = np.arange(W)
+        if plan.native:
+            try:
+                timing = self._drive_rollout_native(groups, episode_infos)
+            finally:
+                self._shm_env.park()          # whatever happened: no worker keeps spinning through the optimisation phase
+        else:
+            timing = self._drive_rollout_host(plan, groups, launch, episode_infos)
+        for g in groups:
+            if g.stream is not None:
+                main.wait_stream(g.stream)
+        self._check_step_kernels(groups)
+        self._finish_rollout(plan, main, forced_actions is not None, timing)
+        return episode_infos
+
+    def _begin_rollout(self, main, forced_actions, uniforms, normals):
+        """Everything before step 0: episode slots, K/V cache and weight copies, the draw tables, the captured graphs (first rollout)
+        and with them the plan, the streams, the rows of observation 0.  -> (plan, the groups that run)."""
+        self.buffer.begin_rollout(self._slot_dev)
+        self.worker_episode_slot[:] = np.arange(self.num_workers)
         self._slot_dev.copy_(self._slot_pin, non_blocking=True)
         if self._use_kv_cache:
             self._refresh_kv_cache()
         self.model.refresh_rollout_weights()       # encoder weight copies for the fused rollout convolutions
-        B = self._action_width
-        if forced_actions is not None and self.box is not None:
-            fa = torch.as_tensor(np.asarray(forced_actions), dtype=torch.float32)
-            self._forced_tab.copy_(fa.reshape(W, S, B).transpose(0, 1).to(self.device))
-        elif forced_actions is not None:
-            fa = torch.as_tensor(np.asarray(forced_actions), dtype=torch.int64)
-            fa = fa.reshape(W, S).t() if B == 1 else fa.reshape(W, S, B).transpose(0, 1)
-            self._forced_tab.copy_(fa.to(self.device))
-        groups = self._groups if use_graph else [self._group_all]
-        if use_graph and groups[0].graphs is None:
-            self._capture_step_graph(groups)
-        if self.box is not None:
-            if normals is not None:
-                self._normals.copy_(torch.as_tensor(np.asarray(normals), dtype=torch.float32).reshape(W, S, B).transpose(0, 1))
-            else:
-                self._normals.normal_()              # one N(0, 1) draw per (step, worker, dimension) for the whole rollout
-        elif uniforms is not None:
-            u = torch.as_tensor(np.asarray(uniforms), dtype=torch.float32)
-            self._uniforms.copy_(u.reshape(W, S).t() if B == 1 else u.reshape(W, S, B).transpose(0, 1))
+        if forced_actions is not None:
+            self._forced_tab.copy_(time_major(self._forced_tab, forced_actions).to(self.device))
+        if self.config.get("hip_graph_rollout", True):
+            groups = self._groups
+            if groups[0].graphs is None:
+                self._capture_step_graph(groups)
+            plan = self._plan
         else:
+            groups, plan = [self._group_all], RolloutPlan(polite_wait=bool(self._host_plan["polite_wait"]))
+        if self.box is None and uniforms is not None:
+            self._uniforms.copy_(time_major(self._uniforms, uniforms))
+        elif self.box is None:
             self._uniforms.uniform_()            # one draw per (step, worker, branch) for the whole rollout
+        elif normals is not None:
+            self._normals.copy_(time_major(self._normals, normals))
+        else:
+            self._normals.normal_()              # one N(0, 1) draw per (step, worker, dimension) for the whole rollout
         for g in groups:
-            g.t_dev.zero_()
-            g.flag_np[0] = 0
-        stream_obs = use_graph and self._stream_obs
-        host_flag = use_graph and self._host_flag
-        lib = etm_lib.load()
-        up = self._up_stream.cuda_stream
-        row_bytes = self._obs_pin[0].numel() * 4
-        src_base, stage_base = self._obs_pin.data_ptr(), self._stage["obs"].data_ptr()
-        ss_global = self._ss_pin.numpy()
-        side_streams = [g.stream for g in groups if g.stream is not None]
-        for st_ in side_streams:
-            st_.wait_stream(main)                  # buffers prepared above on the main stream
-        if stream_obs:
+            g.restart()
+            if g.stream is not None:
+                g.stream.wait_stream(main)         # buffers prepared above on the main stream
+        if plan.stream_obs:
             self._up_stream.wait_stream(main)      # the staging array may still be read by the previous update
-
-        # With a stream per group (the pipelined default) the observation rows of a group go to the device on the GROUP's stream
-        # -- stream order alone puts them before the step that reads them -- and the step's window kernel reads the
-        # (episode step, slot) block straight from pinned host memory: no upload of that block, no event between an upload
-        # stream and the step (each of those was a few us on the critical path of every step).
-        own_stream = stream_obs and all(g.stream is not None for g in groups)
-        # direct observation rows (round 6; in-process environments): the front-end writes the rows of step t + 1 straight into
-        # their row of the staging array in DEVICE memory (large BAR: the hipMalloc pointer is a host address) -- no pinned
-        # intermediate, no copy-engine transfer (677 KB per group and step at 3x84x84: ~20 us of the step's critical path) and no
-        # runtime call; etm_host_store_fence (sfence + the device's HDP flush register) sits between the rows and the launch.
-        # The pinned buffer still receives the observation AFTER the last step (the bootstrap value and the next rollout's
-        # observation 0 read it).  `direct_observation_rows: false`, a device without large BAR or a failed self-test: uploads.
-        direct = bool(own_stream and host_flag and self._shm_env is None and self.config.get("direct_observation_rows", True)
-                      and ops.host_direct_write_ok(self.device))
-        if direct:
-            if getattr(self, "_stage_host", None) is None:
-                self._stage_host = ops.host_view(self._stage["obs"])
-            ev = getattr(self, "_stage_read", None)
-            if ev is not None:
-                ev.synchronize()                   # the previous update's copy out of the staging array has run
-        self._direct_rows = direct
-        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-
-        def obs_stream(g):
-            return g.stream.cuda_stream if own_stream else up
-
-        # (CUDAGraph.raw_cuda_graph_exec exists in torch >= 2.8; without it the framework's replay() is used)
-        direct_launch = bool(host_flag and hasattr(torch.cuda.CUDAGraph, "raw_cuda_graph_exec"))
-        polite = bool(self._host_plan["polite_wait"])
-
-        def upload_state(g):
-            """(episode step, slot) of the group's workers -> where the device finds them, after the host bookkeeping of the step."""
-            if not g.full:
-                g.ss_np[:] = ss_global[:, g.lo:g.hi]
-            if own_stream:
-                return
-            lib.etm_upload(g.ss_dev.data_ptr(), g.ss_pin.data_ptr(), g.ss_pin.numel() * 8, up)
-            g.up_done.record(self._up_stream)
-
-        def launch(g, t):
-            """Device work of step t of group g (graph mode: two replays on the group's stream)."""
-            if use_graph and direct_launch and g.graphs[1] is None and g.stream is not None and (own_stream or not stream_obs):
-                # one captured graph per step on the group's own stream, nothing to wait for: hipGraphLaunch through the library,
-                # without the framework's stream switches around the replay (round 4: ~6 us of every group's step on the host)
-                if not g.full:
-                    g.ss_np[:] = ss_global[:, g.lo:g.hi]
-                if getattr(g, "graph_exec", None) is None:
-                    g.graph_exec = g.graphs[0].raw_cuda_graph_exec()
-                rc = lib.etm_graph_launch(g.graph_exec, g.stream.cuda_stream)
-                if rc != 0:
-                    etm_lib.check(rc, "etm_graph_launch")
-                return
-            if use_graph:
-                if g.stream is not None:
-                    torch.cuda.set_stream(g.stream)
-                cur = g.stream if g.stream is not None else main
-                if stream_obs and not own_stream:
-                    cur.wait_event(g.up_done)        # observation rows and (step, slot) of step t are on the device
-                elif not g.full:
-                    g.ss_np[:] = ss_global[:, g.lo:g.hi]
-                g.graphs[0].replay()
-                if not host_flag:
-                    g.act_ready.record(cur)          # actions are in pinned memory once this event completes
-                if g.graphs[1] is not None:
-                    g.graphs[1].replay()             # tail runs while the host steps the environments
-                if g.stream is not None:
-                    torch.cuda.set_stream(main)
-            else:
-                with torch.no_grad():
-                    carry = self._rollout_step_head(g)
-                    g.act_ready.record(main)
-                    self._rollout_step_tail(g, carry)
-
-        # the native driver runs this rollout iff the captured steps hand over through the segment's go words (_native_rollout, decided
-        # at capture) AND the step is the single flag-hand-over graph on the group's own stream -- ONE predicate for "workers held
-        # spinning", "sequence restarted" and "etm_rollout_drive called" (ADVICE round 4)
-        native = bool(use_graph and getattr(self, "_native_rollout", False) and host_flag and own_stream
-                      and all(g.graphs[1] is None for g in groups))
-        if use_graph and getattr(self, "_native_rollout", False):
+        if plan.direct_rows:
+            # (the pinned buffer still receives the observation AFTER the last step: the bootstrap value and the next rollout's
+            # observation 0 read it)
+            self._stage_read.synchronize()         # the previous update's copy out of the staging array has run
+        if plan.native:
             # the device's step counter restarts at 1: go = 0 on every group, acknowledged by every worker, BEFORE step 0 is launched;
-            # the workers then spin (no self-parking) until the rollout is over (native driver) or park when idle (host loop: the
-            # captured kernels still write the go words, the Python loop below steps the workers through the same sequence numbers)
-            self._shm_env.activate(hold=native)
+            # the workers then spin (no self-parking) until the rollout is over
+            self._shm_env.activate(hold=True)
             self._shm_env.restart_sequence()
-        if stream_obs:
+        if plan.stream_obs:
             for g in groups:                       # observation 0 -> staging row 0
-                lib.etm_upload(stage_base + g.lo * row_bytes, src_base + g.lo * row_bytes, g.W * row_bytes, obs_stream(g))
-                upload_state(g)
-        for g in groups:
-            launch(g, 0)
+                g.upload_rows(0, 0, g.W)
+        return plan, groups
+
+    def _launch_graph_exec(self, g, plan):
+        """One captured graph per step on the group's own stream, nothing to wait for: hipGraphLaunch through the library."""
+        g.take_state()
+        rc = self._etm.etm_graph_launch(g.graph_exec, g.stream.cuda_stream)
+        if rc != 0:
+            etm_lib.check(rc, "etm_graph_launch")
+
+    def _launch_replay(self, g, plan):
+        """Head graph, (event for the host,) tail graph through the framework's replay() on the group's stream."""
+        g.take_state()
+        with torch.cuda.stream(g.stream):        # (no stream of its own: the caller's)
+            cur = g.stream if g.stream is not None else torch.cuda.current_stream(self.device)
+            if plan.stream_obs and not plan.own_stream:
+                # the (step, slot) block follows the observation rows on the shared upload stream; the step waits for both
+                self._etm.etm_upload(g.ss_dev.data_ptr(), g.ss_pin.data_ptr(), g.ss_pin.numel() * 8, self._up_stream.cuda_stream)
+                g.up_done.record(self._up_stream)
+                cur.wait_event(g.up_done)
+            g.graphs[0].replay()
+            if not plan.host_flag:
+                g.act_ready.record(cur)          # actions are in pinned memory once this event completes
+            if g.graphs[1] is not None:
+                g.graphs[1].replay()             # tail runs while the host steps the environments
+
+    def _launch_eager(self, g, plan):
+        with torch.no_grad():
+            carry = self._rollout_step_head(g)
+            g.act_ready.record(torch.cuda.current_stream(self.device))
+            self._rollout_step_tail(g, carry)
+
+    def _drive_rollout_host(self, plan, groups, launch, episode_infos):
+        """Steps 0 .. S - 1 from this thread, step 0 of every group being in flight: per step and group wait for the actions, step
+        the environments, do the episode bookkeeping, launch the next step.  -> seconds in (env.step, waiting, upload + launch)."""
+        # this loop is the rollout's critical path: what the plan fixes is bound to locals here, once
+        buf, S, clock = self.buffer, self.config["worker_steps"], time.perf_counter
+        direct, stream_obs, host_flag, polite = plan.direct_rows, plan.stream_obs, plan.host_flag, plan.polite_wait
+        fence = self._etm.etm_host_store_fence
         t_env = t_wait = t_launch = 0.0
-        if native:
-            try:
-                t_wait, t_launch = self._drive_rollout_native(groups, episode_infos)
-            finally:
-                self._shm_env.park()          # whatever happened: no worker keeps spinning through the optimisation phase
-        for t in (range(S) if not native else ()):
+        for t in range(S):
             for g in groups:
                 lo, hi = g.lo, g.hi
-                tw = time.perf_counter()
+                tw = clock()
                 if host_flag:
-                    # the sampling kernel stored the actions and then step t + 1 into pinned memory: spin on the counter
-                    flag, target, spins, t_wait0 = g.flag_np, t + 1, 0, time.perf_counter()
-                    if polite and flag[0] != target and self._flag_wait_ema > 80e-6:
-                        # not enough CPUs for a spinning trainer thread (etm/hostcpu.py): sleep through most of the wait this flag
-                        # usually takes (an average of the earlier waits), spin for the rest
-                        time.sleep(0.7 * self._flag_wait_ema)
-                    while flag[0] != target:
-                        spins += 1
-                        if spins % 4096 == 0 and time.perf_counter() - t_wait0 > 30.0:
-                            raise RuntimeError("rollout step did not complete within 30 s (device hang?)")
+                    self._await_flag(g.flag_np, t + 1, polite)
                 else:
                     g.act_ready.synchronize()
-                te = time.perf_counter()
+                te = clock()
                 t_wait += te - tw
                 if polite:
                     self._flag_wait_ema += 0.1 * ((te - tw) - self._flag_wait_ema)
+                # the rows of observation t + 1 go straight into their staging row in device memory (the fence sits between them and
+                # the next launch), or into pinned memory and from there, as the environment emits them, into their staging row, or
+                # (unstreamed, and after the last step) into pinned memory alone
                 if direct and t + 1 < S:
                     _, rewards, dones, infos = g.env.step(g.acts_host, out=self._stage_host[t + 1, lo:hi])
-                    lib.etm_host_store_fence(dev_index)
+                    fence(self._dev_index)
                 elif stream_obs and t + 1 < S:
-                    dst_base = stage_base + ((t + 1) * W + lo) * row_bytes
-                    src_g = src_base + lo * row_bytes
-                    up_g = obs_stream(g)
-
-                    def rows_ready(a, b):
-                        lib.etm_upload(dst_base + a * row_bytes, src_g + a * row_bytes, (b - a) * row_bytes, up_g)
-
-                    _, rewards, dones, infos = g.env.step(g.acts_host, out=g.obs_np, on_rows=rows_ready)
+                    _, rewards, dones, infos = g.env.step(g.acts_host, out=g.obs_np, on_rows=partial(g.upload_rows, t + 1))
                 else:
                     _, rewards, dones, infos = g.env.step(g.acts_host, out=g.obs_np)
-                t_env += time.perf_counter() - te
+                t_env += clock() - te
                 self.worker_current_episode_step[lo:hi] += 1
                 if dones.any():
-                    for wl in np.flatnonzero(dones):
-                        w = lo + int(wl)
-                        self.worker_current_episode_step[w] = 0
-                        episode_infos.append(infos[wl])
-                        slot = buf.open_episode()                  # fresh zero memory for the next episode (upstream :208-213)
-                        self.worker_episode_slot[w] = slot
-                        if t < S - 1:
-                            buf.memory_index_host[w, t + 1:] = slot
+                    self._hand_over_episodes(g, t, dones, infos, episode_infos)
                 if t + 1 < S:
-                    tl = time.perf_counter()
-                    if stream_obs:
-                        upload_state(g)              # bookkeeping of this step is final: (step, slot) follow the observation rows
-                    launch(g, t + 1)
-                    t_launch += time.perf_counter() - tl
+                    tl = clock()
+                    launch(g, plan)                  # bookkeeping of this step is final: (step, slot) follow the observation rows
+                    t_launch += clock() - tl
                     if self._chain_log is not None and g is groups[0]:
-                        self._chain_log.append((tw, te, tl, time.perf_counter()))
+                        self._chain_log.append((tw, te, tl, clock()))
                 buf.rewards[lo:hi, t] = rewards    # (after the launch: nothing on the device waits for these)
                 buf.dones[lo:hi, t] = dones
-        for st_ in side_streams:
-            main.wait_stream(st_)
-        t_ = self.model.transformer
-        for g in groups + [self._group_all]:
-            if g.rf_scratch is not None and int(ops.rollout_trxl_error(g.rf_scratch).item()) != 0:
-                # a team member gave up waiting for its partners (not all workgroups were resident): this rollout's data are
-                # unusable.  Leave the trainer in a state that can continue: clear the error word, switch to the multi-launch
-                # step for the rest of the run and drop the captured graphs so that the next rollout re-captures them.
-                for gg in groups + [self._group_all]:
-                    if gg.rf_scratch is not None:
-                        ops.rollout_trxl_clear_error(gg.rf_scratch)
-                    gg.graphs = None
-                self.model.fused_rollout_block = False
-                self.model._rf = self.model._rfg = None
-                self._step_graph = None
-                raise RuntimeError("fused rollout step: a team member timed out waiting for its partners; this rollout is void. The "
-                                   "trainer has switched to the multi-launch step (fused_rollout_block: false) for the following rollouts")
-        if forced_actions is not None:
+        return t_env, t_wait, t_launch
+
+    def _await_flag(self, flag, target, polite):
+        """The sampling kernel stored the actions and then the step's number into the host word ``flag``: spin on it."""
+        spins, t_wait0 = 0, time.perf_counter()
+        if polite and flag[0] != target and self._flag_wait_ema > 80e-6:
+            # not enough CPUs for a spinning trainer thread (etm/hostcpu.py): sleep through most of the wait this flag
+            # usually takes (an average of the earlier waits), spin for the rest
+            time.sleep(0.7 * self._flag_wait_ema)
+        while flag[0] != target:
+            spins += 1
+            if spins % 4096 == 0 and time.perf_counter() - t_wait0 > 30.0:
+                raise RuntimeError("rollout step did not complete within 30 s (device hang?)")
+
+    def _hand_over_episodes(self, g, t, dones, infos, episode_infos):
+        """Workers of group g whose episode ended at step t start the next one in a fresh slot (upstream :195-213)."""
+        buf, S = self.buffer, self.config["worker_steps"]
+        for wl in np.flatnonzero(dones):
+            w = g.lo + int(wl)
+            self.worker_current_episode_step[w] = 0
+            episode_infos.append(infos[wl])
+            slot = buf.open_episode()                  # fresh zero memory for the next episode (upstream :208-213)
+            self.worker_episode_slot[w] = slot
+            if t < S - 1:
+                buf.memory_index_host[w, t + 1:] = slot
+
+    def _check_step_kernels(self, groups):
+        """Raises if a step kernel set its error word during this rollout, after making the trainer fit to continue."""
+        # a team member gave up waiting for its partners (not all workgroups were resident): this rollout's data are
+        # unusable.  Leave the trainer in a state that can continue: clear the error words, switch to the multi-launch
+        # step for the rest of the run and drop the captured graphs and their plan so that the next rollout re-decides and re-captures.
+        every = groups + [self._group_all]
+        if not any(g.rf_scratch is not None and int(ops.rollout_trxl_error(g.rf_scratch).item()) != 0 for g in every):
+            return
+        for g in every:
+            if g.rf_scratch is not None:
+                ops.rollout_trxl_clear_error(g.rf_scratch)
+            g.graphs = g.graph_exec = None
+        self.model.fused_rollout_block = False
+        self.model._rf = self.model._rfg = None
+        self._step_graph = self._plan = None
+        raise RuntimeError("fused rollout step: a team member timed out waiting for its partners; this rollout is void. The "
+                           "trainer has switched to the multi-launch step (fused_rollout_block: false) for the following rollouts")
+
+    def _finish_rollout(self, plan, main, forced, timing):
+        """Time-major staging -> the buffer's [W, S, ...] fields (one strided copy per field), bootstrap value, advantages."""
+        buf = self.buffer
+        if forced:
             self._forced_tab.fill_(float("nan") if self.box is not None else -1)
-        # time-major staging -> the buffer's [W, S, ...] fields (one strided copy per field)
         self._step_dev.copy_(self._step_pin, non_blocking=True)
         self._slot_dev.copy_(self._slot_pin, non_blocking=True)
         for name, stage in self._stage.items():
             getattr(buf, name).copy_(stage.transpose(0, 1))
-        if getattr(self, "_direct_rows", False):
-            if getattr(self, "_stage_read", None) is None:
-                self._stage_read = torch.cuda.Event()
+        if plan.direct_rows:
             self._stage_read.record(main)          # the next rollout's host writes into the staging array wait for this
-        last_value = self.get_last_value()
-        buf.calc_advantages(last_value, self.config["gamma"], self.config["lamda"])
-        self.last_update_timing.update(env_s=t_env, wait_s=t_wait, launch_s=t_launch)
-        return episode_infos
+        buf.calc_advantages(self.get_last_value(), self.config["gamma"], self.config["lamda"])
+        self.last_update_timing.update(env_s=timing[0], wait_s=timing[1], launch_s=timing[2])
 
     def _rollout_step_device(self, g, stream_obs=False, host_flag=False):
         """Device side of one rollout step of group ``g`` (upstream trainer.py:161-186) = head + tail."""
         carry = self._rollout_step_head(g, stream_obs, host_flag)
         self._rollout_step_tail(g, carry, stream_obs)
 
+    def _choose_step_form(self, g, streamed):
+        """Which kernels make up the step of group ``g``: sets ``g.group_kernel`` / ``g.tail_in_kernel`` (and the step kernel's scratch)
+        before anything is launched.  -> (fused_step, the step kernel's weight table, the form of its hidden-layer input)."""
+        # hidden-layer input: "conv3" / "partial" (lin_hidden as K-slice partial sums, with / without the last encoder layer in the same
+        # launch) or "full" (the model's encoder)
+        m, lib = self.model, self._etm
+        rf = getattr(m, "_rf", None) if self._use_kv_cache else None
+        # (every team of the step kernel must be resident at once, and the groups' step kernels run concurrently: the workgroups
+        # of ALL groups together must fit the 256 CUs -- one 512-thread workgroup per CU --, else the multi-launch path)
+        n_conc = len(self._groups) if not g.full else 1
+        # GRU-gated layouts in groups of <= 8 workers take the GROUP form of the step kernel (weights once per group and
+        # step, 32 workgroups per launch; csrc/rollout_group.hip)
+        rfg = getattr(m, "_rfg", None) if rf is not None else None
+        g.group_kernel = bool(rfg is not None and self.config.get("rollout_group_kernel", True)
+                              and ops.rollout_trxl_group_ok(rfg, g.W, self.memory_length, m.hidden_size, m._rollout_actions(),
+                                                            gaussian=self.box is not None)
+                              and n_conc * lib.etm_rollout_trxl_group_grid() <= 256)
+        fused_step = (rf is not None and m.rollout_heads_fusable()
+                      and (g.group_kernel or n_conc * lib.etm_rollout_trxl_grid(g.W, rf["H"]) <= 256))
+        g.tail_in_kernel = bool(fused_step and self.config.get("fused_rollout_tail", True) and self._kv_w_blocked is not None)
+        if not fused_step:
+            return False, None, None
+        rf = rfg if g.group_kernel else rf
+        if g.rf_scratch is None or g.rf_scratch_kind != g.group_kernel:
+            # (the two forms of the kernel lay their scratch out differently: launch counter, tags and slots belong to one form)
+            t_ = m.transformer
+            g.rf_scratch = ops.rollout_trxl_scratch(g.W, t_.embed_dim, t_.num_heads, t_.num_blocks, self.device, group=g.group_kernel)
+            g.rf_scratch_kind = g.group_kernel
+        hidden = "full"
+        if streamed and "hid_t" in rf:
+            conv3 = self.config.get("fused_conv3_hidden", True) and ops.rollout_conv3_hidden_supported(m.conv3, *m.conv2_output_hw(), rf["hid_t"].shape[1])
+            hidden = "conv3" if conv3 else "partial"
+        return True, rf, hidden
+
+    def _hidden_input(self, g, hidden, rf, obs, obs_index, rows):
+        """The step kernel's hidden-layer input in the chosen form -> (h_in, the bias the kernel still has to add or None)."""
+        m = self.model
+        if hidden == "full":
+            return m._encode(obs, obs_index, rows), None
+        # lin_hidden as K-slice partial sums on 12 x 16 workgroups; the step kernel adds slices + bias + ReLU
+        if hidden == "conv3":
+            # the last encoder layer and lin_hidden's partial sums as ONE launch, one workgroup per output pixel
+            # (csrc/conv3_hidden.hip): the step graph is conv1, conv2, this, the step kernel
+            x, partial_sums = m._encode_fused(obs, obs_index, rows, features_only="conv2"), ops.rollout_conv3_hidden
+            args = (m._w3k, m.conv3.bias, rf["hid_t"])
+        else:
+            x, partial_sums = m._encode_fused(obs, obs_index, rows, features_only=True), ops.rollout_hidden_partial
+            args = (rf["hid_t"],)
+        if g.h_part is None:          # (the first call allocates the fixed-address result)
+            g.h_part = partial_sums(x, *args)
+        return partial_sums(x, *args, out=g.h_part), m.lin_hidden.bias
+
     def _rollout_step_head(self, g, stream_obs=False, host_flag=False):
         """Everything the ACTIONS of group ``g`` depend on: (observation / step / slot upload,) window lookup, model forward,
         sampling, staging of the step's rows, action hand-over.  Every operand has a fixed address (HIP-graph capturable).
         Returns what the tail needs (the new memory items, block-major)."""
-        buf = self.buffer
-        st = self._stage
+        buf, st, m = self.buffer, self._stage, self.model
         rows = None if g.full else (g.lo, g.hi)
         if stream_obs:      # the observation of this step is already in row t of the staging array (see _sample_training_data)
             obs, obs_index = st["obs"], g.t_dev
@@ -705,114 +703,59 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             obs, obs_index, rows = g.obs_dev, None, None
             g.ss_dev.copy_(g.ss_pin, non_blocking=True)      # (streamed mode: uploaded with the observation rows)
         branches = self.action_space_shape       # (one entry: Discrete; the kernels then take their single-branch entries)
-        policy_head = self.model.rollout_policy_head()
+        policy_head = m.rollout_policy_head()
         # Box: the Gaussian forms of the sampling kernels -- normals in place of the uniforms, float forced / action tables
-        box = None if self.box is None else (self.model.policy_log_std, self.box.low, self.box.high)
+        box = None if self.box is None else (m.policy_log_std, self.box.low, self.box.high)
         draws = self._uniforms if box is None else self._normals
         mask_t, win_t = g.mask_t, g.win_t
+        # streamed + pipelined mode: the (step, slot) block is read from pinned host memory (see rollout_plan.plan_rollout)
+        ss_src = g.ss_pin if stream_obs and g.stream is not None else g.ss_dev
+        fused_step, rf, hidden = self._choose_step_form(g, obs_index is not None)
+        flag_pin = g.flag_pin if host_flag else None
+        if fused_step:
+            # post-LN blocks without gates: the transformer, the heads and the sampling are ONE launch -- one workgroup per
+            # worker walks the whole chain as matrix-vector products over the L2-resident weights (csrc/rollout_fused.hip);
+            # the step is then encoder (4 launches) + window lookup + this kernel instead of 26 dependent launches
+            # (the kernel does the window lookup and the cache reset of new episodes itself by now: one launch fewer in the chain)
+            h_in, h_bias = self._hidden_input(g, hidden, rf, obs, obs_index, rows)
+            # ... and, after the action hand-over, the memory-bank write and the K | V projection of the new items (the tail;
+            # pre-LN: the kernel applies norm_kv)
+            tail = (self._kv_w_blocked, m.transformer._pos(), g.step_l, g.slot_l, buf.bank) if g.tail_in_kernel else None
+            ops.rollout_trxl(h_in, rf, g.kv, win_t, mask_t, g.item, policy_head, m.value,
+                             draws, self._forced_tab, g.t_dev, g.act_dev, st["actions"], st["log_probs"], st["values"],
+                             g.rf_scratch, host_actions=g.act_pin, host_flag=flag_pin, w_off=g.lo,
+                             tail=tail, h_bias=h_bias, branches=branches, box=box,
+                             window=(ss_src, self._mask_table, self._index_table, st["memory_mask"], st["memory_indices"],
+                                     g.ss_latch, g.t_row, self._kv_init))
+            return g.item
         # window lookup + staging; the same launch records the staging row of this step for the tail (t_dev is incremented by
         # the sampling kernel) and resets the K/V cache of workers at episode step 0 (they start from the projection of an
         # empty memory)
-        # streamed + pipelined mode: the (step, slot) block is read from pinned host memory (see _sample_training_data)
-        zero_copy = stream_obs and g.stream is not None
-        ss_src = g.ss_pin if zero_copy else g.ss_dev
-        rf_ = getattr(self.model, "_rf", None) if self._use_kv_cache else None
-        # (every team of the step kernel must be resident at once, and the groups' step kernels run concurrently: the workgroups
-        # of ALL groups together must fit the 256 CUs -- one 512-thread workgroup per CU --, else the multi-launch path)
-        n_conc = len(self._groups) if not g.full else 1
-        # round 5: GRU-gated layouts in groups of <= 8 workers take the GROUP form of the step kernel (weights once per group and
-        # step, 32 workgroups per launch; csrc/rollout_group.hip)
-        rfg_ = getattr(self.model, "_rfg", None) if rf_ is not None else None
-        g.group_kernel = bool(rfg_ is not None and self.config.get("rollout_group_kernel", True)
-                              and ops.rollout_trxl_group_ok(rfg_, g.W, self.memory_length, self.model.hidden_size, self.model._rollout_actions(),
-                                                            gaussian=box is not None)
-                              and n_conc * etm_lib.load().etm_rollout_trxl_group_grid() <= 256)
-        fused_step = (rf_ is not None and self.model.rollout_heads_fusable()
-                      and (g.group_kernel or n_conc * etm_lib.load().etm_rollout_trxl_grid(g.W, rf_["H"]) <= 256))
-        # the fused step kernel does the window lookup (and the cache reset of new episodes) itself: one launch fewer in the chain
-        if not fused_step:
-            ops.rollout_window(ss_src[0], self._mask_table, self._index_table, g.t_dev, mask_t, win_t,
-                               st["memory_mask"], st["memory_indices"], t_row=g.t_row,
-                               reset=(g.kv, self._kv_init) if self._use_kv_cache else None, w_off=g.lo,
-                               latch=(ss_src, g.ss_latch))
-        fused_policy = False
-        if self._use_kv_cache:
-            kv_spec = WindowSpec.from_bank(g.kv, None, win_t, None, mask_t)
-            if fused_step:
-                # post-LN blocks without gates: the transformer, the heads and the sampling are ONE launch -- one workgroup per
-                # worker walks the whole chain as matrix-vector products over the L2-resident weights (csrc/rollout_fused.hip);
-                # the step is then encoder (4 launches) + window lookup + this kernel instead of 26 dependent launches
-                rf = self.model._rfg if g.group_kernel else self.model._rf
-                h_bias = None
-                if obs_index is not None and "hid_t" in rf:
-                    # lin_hidden as K-slice partial sums on 12 x 16 workgroups; the step kernel adds slices + bias + ReLU
-                    m_ = self.model
-                    hh_, ww_ = m_.observation_space_shape[-2:]
-                    h2_, w2_ = hh_, ww_
-                    for cv in (m_.conv1, m_.conv2):                                                      # spatial size after conv1, conv2
-                        h2_, w2_ = (h2_ - cv.kernel_size[0]) // cv.stride[0] + 1, (w2_ - cv.kernel_size[1]) // cv.stride[1] + 1
-                    if (self.config.get("fused_conv3_hidden", True)
-                            and ops.rollout_conv3_hidden_supported(m_.conv3, h2_, w2_, rf["hid_t"].shape[1])):
-                        # round 4: the last encoder layer and lin_hidden's partial sums as ONE launch, one workgroup per output pixel
-                        # (csrc/conv3_hidden.hip): the step graph is conv1, conv2, this, the step kernel
-                        x2 = m_._encode_fused(obs, obs_index, rows, features_only="conv2")
-                        if getattr(g, "h_part", None) is None:
-                            g.h_part = ops.rollout_conv3_hidden(x2, m_._w3k, m_.conv3.bias, rf["hid_t"])
-                        h_in = ops.rollout_conv3_hidden(x2, m_._w3k, m_.conv3.bias, rf["hid_t"], out=g.h_part)
-                    else:
-                        feats = m_._encode_fused(obs, obs_index, rows, features_only=True)
-                        if getattr(g, "h_part", None) is None:
-                            g.h_part = ops.rollout_hidden_partial(feats, rf["hid_t"])
-                        h_in = ops.rollout_hidden_partial(feats, rf["hid_t"], out=g.h_part)
-                    h_bias = self.model.lin_hidden.bias
-                else:
-                    h_in = self.model._encode(obs, obs_index, rows)
-                if getattr(g, "rf_scratch", None) is None or getattr(g, "rf_scratch_kind", None) != g.group_kernel:
-                    # (the two forms of the kernel lay their scratch out differently: launch counter, tags and slots belong to one form)
-                    t_ = self.model.transformer
-                    g.rf_scratch = ops.rollout_trxl_scratch(g.W, t_.embed_dim, t_.num_heads, t_.num_blocks, self.device, group=g.group_kernel)
-                    g.rf_scratch_kind = g.group_kernel
-                # ... and, after the action hand-over, the memory-bank write and the K | V projection of the new items (the tail)
-                tail = None
-                if self.config.get("fused_rollout_tail", True) and getattr(self, "_kv_w_blocked", None) is not None:   # (pre-LN: the kernel applies norm_kv)
-                    tail = (self._kv_w_blocked, self.model.transformer._pos(), g.step_l, g.slot_l, buf.bank)
-                g.tail_in_kernel = tail is not None
-                ops.rollout_trxl(h_in, rf, g.kv, win_t, mask_t, g.item, policy_head, self.model.value,
-                                 draws, self._forced_tab, g.t_dev, g.act_dev, st["actions"], st["log_probs"], st["values"],
-                                 g.rf_scratch, host_actions=g.act_pin, host_flag=g.flag_pin if host_flag else None, w_off=g.lo,
-                                 tail=tail, h_bias=h_bias, branches=branches, box=box,
-                                 window=(ss_src, self._mask_table, self._index_table, st["memory_mask"], st["memory_indices"],
-                                         g.ss_latch, g.t_row, self._kv_init))
-                item = g.item
-                fused_policy = True
-            elif self.model.rollout_heads_fusable():
-                # hidden heads -> ONE launch for output heads, sampling, staging, t += 1; the kernel stores the actions straight
-                # into the pinned host buffer (no copy launch): they are visible to the host when the step's event (or, with
-                # host_flag_actions, the flag) says the launch is done
-                h2, item = self.model.forward_hidden_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, raw=True,
-                                                            obs_rows=rows)
-                flag = host_flag
-                if box is not None:
-                    ops.rollout_policy_gaussian(h2, policy_head, self.model.value, box[0], draws, self._forced_tab, g.t_dev, g.act_dev,
-                                                st["actions"], st["log_probs"], st["values"], low=box[1], high=box[2],
-                                                host_actions=g.act_pin, host_flag=g.flag_pin if flag else None,
-                                                h_bias=self.model._b_heads, w_off=g.lo)
-                else:
-                    ops.rollout_policy(h2, policy_head, self.model.value, self._uniforms, self._forced_tab, g.t_dev,
-                                       g.act_dev, st["actions"], st["log_probs"], st["values"],
-                                       host_actions=g.act_pin, host_flag=g.flag_pin if flag else None,
-                                       h_bias=self.model._b_heads, w_off=g.lo, branches=branches)
-                fused_policy = True
+        ops.rollout_window(ss_src[0], self._mask_table, self._index_table, g.t_dev, mask_t, win_t,
+                           st["memory_mask"], st["memory_indices"], t_row=g.t_row,
+                           reset=(g.kv, self._kv_init) if self._use_kv_cache else None, w_off=g.lo,
+                           latch=(ss_src, g.ss_latch))
+        kv_spec = WindowSpec.from_bank(g.kv, None, win_t, None, mask_t) if self._use_kv_cache else None
+        if kv_spec is not None and m.rollout_heads_fusable():
+            # hidden heads -> ONE launch for output heads, sampling, staging, t += 1; the kernel stores the actions straight
+            # into the pinned host buffer (no copy launch): they are visible to the host when the step's event (or, with
+            # host_flag_actions, the flag) says the launch is done
+            h2, item = m.forward_hidden_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, raw=True, obs_rows=rows)
+            if box is not None:
+                ops.rollout_policy_gaussian(h2, policy_head, m.value, box[0], draws, self._forced_tab, g.t_dev, g.act_dev,
+                                            st["actions"], st["log_probs"], st["values"], low=box[1], high=box[2],
+                                            host_actions=g.act_pin, host_flag=flag_pin, h_bias=m._b_heads, w_off=g.lo)
             else:
-                logits, value, item = self.model.forward_logits_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index,
-                                                                        obs_rows=rows)
+                ops.rollout_policy(h2, policy_head, m.value, self._uniforms, self._forced_tab, g.t_dev,
+                                   g.act_dev, st["actions"], st["log_probs"], st["values"],
+                                   host_actions=g.act_pin, host_flag=flag_pin, h_bias=m._b_heads, w_off=g.lo, branches=branches)
         else:
-            spec = WindowSpec.from_bank(buf.bank, g.slot_dev, win_t, win_t, mask_t)
-            logits, value, item = self.model.forward_logits(obs, spec)
-            item = item.transpose(0, 1)
-        if fused_policy:
-            pass
-        else:
+            if kv_spec is not None:
+                logits, value, item = m.forward_logits_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, obs_rows=rows)
+            else:
+                spec = WindowSpec.from_bank(buf.bank, g.slot_dev, win_t, win_t, mask_t)
+                logits, value, item = m.forward_logits(obs, spec)
+                item = item.transpose(0, 1)
             if not g.full:
                 raise RuntimeError("worker groups need the fused policy path (K/V cache)")
             # log-softmax + categorical sample (inverse CDF on pre-drawn uniforms) + log-prob + staging + t += 1, per action branch:
@@ -833,17 +776,14 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         """What the host does NOT have to wait for before stepping the environments: memory-bank write (upstream :174),
         K/V projection of the new item into the cache, observation staging.  Runs under the host's env.step()."""
         buf, st = self.buffer, self._stage
-        if getattr(g, "tail_in_kernel", False):      # etm_rollout_trxl has written the bank and cache rows itself
-            if not stream_obs:
-                st["obs"][:, g.lo:g.hi].index_copy_(0, g.t_row.view(1), g.obs_dev.unsqueeze(0))
-            return
-        item = item.transpose(0, 1)                  # block-major staging -> [Wg, blocks, D]
-        buf.bank[g.slot_l, g.step_l] = item           # (step, slot) as latched by this step's head, see _make_group
-        if self._use_kv_cache:
-            tr = self.model.transformer
-            pos = tr._pos()
-            pos_rows = pos.index_select(0, g.step_l) if pos is not None else None
-            g.kv[g.ids, g.step_l] = tr.project_memory(item, pos_rows, self._kv_weights)
+        if not g.tail_in_kernel:                         # (else etm_rollout_trxl has written the bank and cache rows itself)
+            item = item.transpose(0, 1)                  # block-major staging -> [Wg, blocks, D]
+            buf.bank[g.slot_l, g.step_l] = item           # (step, slot) as latched by this step's head, see WorkerGroup
+            if self._use_kv_cache:
+                tr = self.model.transformer
+                pos = tr._pos()
+                pos_rows = pos.index_select(0, g.step_l) if pos is not None else None
+                g.kv[g.ids, g.step_l] = tr.project_memory(item, pos_rows, self._kv_weights)
         if not stream_obs:
             st["obs"][:, g.lo:g.hi].index_copy_(0, g.t_row.view(1), g.obs_dev.unsqueeze(0))
 
@@ -851,11 +791,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         """Start of a rollout: re-project every live episode's memory with the CURRENT weights (they changed in the
         last optimisation phase) into the per-worker K/V cache [W, T, blocks, 2D]; rows that are not written yet hold the
         projection of a zero item, which is also the initial state of every episode that starts during the rollout.
-        (Round 6: a graph replay from its third call on, ops.ReplayAfterWarmup -- with ``hip_graph_rollout``.)"""
-        r = getattr(self, "_kv_refresh_replay", None)
-        if r is None:
-            r = self._kv_refresh_replay = ops.ReplayAfterWarmup(self._refresh_kv_cache_now, self.device, what="_refresh_kv_cache",
-                                                                enabled=bool(self.config.get("hip_graph_rollout", True)))
+        (A graph replay from its third call on, ops.ReplayAfterWarmup -- with ``hip_graph_rollout``.)"""
+        r = self._kv_refresh_replay
         r.enabled = bool(self.config.get("hip_graph_rollout", True)) and self.buffer.address_captured      # (the bank keeps its address from the first captured step on)
         r()
 
@@ -870,19 +807,18 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                 for dst, src in zip(self._kv_weights, fresh):
                     if torch.is_tensor(dst):
                         dst.copy_(src)
-            if self.device.type == "cuda":
-                # the step kernel's tail reads the projection weights member-blocked: [blocks, P, D, 2D / P] (fixed address)
-                team = etm_lib.load().etm_rollout_trxl_team(tr.num_heads)
-                w = self._kv_weights[0]                                    # [blocks, D, 2D] = [Wk^T | Wv^T]
-                if w.shape[2] % (2 * team) == 0:
-                    # member m's block = [its D / P columns of K | its D / P columns of V]: exactly the cache columns it reads in the
-                    # attention phases, so the cache rows a member reads are only ever written by that member
-                    nb_, d_, d2_ = w.shape
-                    wb = w.reshape(nb_, d_, 2, team, d2_ // (2 * team)).permute(0, 3, 1, 2, 4).reshape(nb_, team, d_, d2_ // team)
-                    if getattr(self, "_kv_w_blocked", None) is None:
-                        self._kv_w_blocked = wb.contiguous()
-                    else:
-                        self._kv_w_blocked.copy_(wb)
+            # the step kernel's tail reads the projection weights member-blocked: [blocks, P, D, 2D / P] (fixed address)
+            team = etm_lib.load().etm_rollout_trxl_team(tr.num_heads)
+            w = self._kv_weights[0]                                    # [blocks, D, 2D] = [Wk^T | Wv^T]
+            if w.shape[2] % (2 * team) == 0:
+                # member m's block = [its D / P columns of K | its D / P columns of V]: exactly the cache columns it reads in the
+                # attention phases, so the cache rows a member reads are only ever written by that member
+                nb_, d_, d2_ = w.shape
+                wb = w.reshape(nb_, d_, 2, team, d2_ // (2 * team)).permute(0, 3, 1, 2, 4).reshape(nb_, team, d_, d2_ // team)
+                if self._kv_w_blocked is None:
+                    self._kv_w_blocked = wb.contiguous()
+                else:
+                    self._kv_w_blocked.copy_(wb)
             pos = tr._pos()
             live = self.buffer.bank[:W].reshape(W * T, self.num_blocks, self.embed_dim)
             pos_all = pos.repeat(W, 1) if pos is not None else None
@@ -891,29 +827,26 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             self._kv_init.copy_(tr.project_memory(zeros, pos, self._kv_weights))
 
     def _capture_step_graph(self, groups):
-        """Warm the step of every worker group up on a side stream (library handles, MIOpen find, GEMM tuning, allocator),
-        then capture it as TWO graphs per group: the head (ends with the action hand-over) and the tail (bank / cache /
-        staging writes)."""
-        with torch.no_grad():
-            self._stream_obs = bool(self.config.get("stream_observations", True) and self._use_kv_cache
-                                    and self.model._fused_encoder_ok(self._obs_dev))
-            fusable = self._use_kv_cache and self.model.rollout_heads_fusable()
-            # host_flag_actions (default on): the sampling kernel stores the actions and then the step counter into pinned memory
-            # and the host spins on the counter -- no event between the action hand-over and the rest of the step, so a step of a
-            # group is ONE captured graph (one launch) instead of head + event + tail (measured: 287 -> 279 us per step)
-            self._host_flag = bool(self.config.get("host_flag_actions", True) and fusable)
-        if len(groups) > 1 and not fusable:
-            raise RuntimeError("rollout_groups > 1 needs the K/V cache (set rollout_groups: 1)")
-        so, hf = self._stream_obs, self._host_flag
-        # native rollout driver (worker_processes): needs the flag hand-over, streamed observations on the groups' own streams and
-        # the (step, slot) block read in place -- then the sampling kernels write the step's sequence number into the SEGMENT's go
-        # words (the workers spin on them) instead of a private pinned word (decided here: the address is captured below)
-        self._native_rollout = bool(self._shm_env is not None and so and hf and all(g.stream is not None for g in groups)
-                                    and hasattr(torch.cuda.CUDAGraph, "raw_cuda_graph_exec"))
-        if self._native_rollout:
-            for gi, g in enumerate(groups):
-                g.flag_pin = torch.from_numpy(self._shm_env.v["go"][gi, 0:1])
-                g.flag_np = g.flag_pin.numpy()
+        """Decide the rollout's plan, warm the step of every worker group up on a side stream (library handles, MIOpen find, GEMM
+        tuning, allocator), then capture it as TWO graphs per group: the head (ends with the action hand-over) and the tail (bank /
+        cache / staging writes) -- or, with the flag hand-over, as one."""
+        cfg = self.config
+        with torch.no_grad():       # (both predicates of the model say no while autograd is on)
+            plan = self._plan = plan_rollout(
+                graph=True, stream_observations=bool(cfg.get("stream_observations", True)),
+                host_flag_actions=bool(cfg.get("host_flag_actions", True)), direct_observation_rows=bool(cfg.get("direct_observation_rows", True)),
+                kv_cache=self._use_kv_cache, fused_encoder=self.model._fused_encoder_ok(self._obs_dev),
+                heads_fusable=self.model.rollout_heads_fusable(), several_groups=all(g.stream is not None for g in groups),
+                worker_processes=self._shm_env is not None, raw_graph_exec=hasattr(torch.cuda.CUDAGraph, "raw_cuda_graph_exec"),
+                large_bar=lambda: ops.host_direct_write_ok(self.device), polite_wait=bool(self._host_plan["polite_wait"]))
+        so, hf = plan.stream_obs, plan.host_flag
+        self._stage_host = ops.host_view(self._stage["obs"]) if plan.direct_rows else None
+        for gi, g in enumerate(groups):
+            g.obs_stream = g.stream.cuda_stream if plan.own_stream else self._up_stream.cuda_stream
+            if plan.native:
+                # the sampling kernels write the step's sequence number into the SEGMENT's go words (the workers spin on them) instead
+                # of a private pinned word (decided here: the address is captured below)
+                g.use_flag(self._shm_env.v["go"][gi, 0:1])
         # the warm-up executions below write the CURRENT step's memory item (and its K/V projection) into the bank / cache rows
         # (slot, step) of every worker.  A worker at episode step 0 attends over a fully masked window -- uniform weights over
         # ALL L rows, row 0 included (upstream quirk, transformer.py:66-68 with an all-zero mask row) -- so a row 0 left behind by
@@ -939,24 +872,19 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             pool = torch.cuda.graph_pool_handle()
             head, tail = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             # thread_local: only this thread's calls are checked during capture (RCCL's watchdog thread may query events)
-            if hf:
-                # the host learns about the actions from the flag the sampling kernel writes, not from an event between head and
-                # tail: the whole step is ONE graph (one launch per group and step on the host instead of two)
-                with torch.no_grad(), torch.cuda.graph(head, pool=pool, stream=g.stream, capture_error_mode="thread_local"):
-                    item = self._rollout_step_head(g, so, hf)
+            with torch.no_grad(), torch.cuda.graph(head, pool=pool, stream=g.stream, capture_error_mode="thread_local"):
+                item = self._rollout_step_head(g, so, hf)
+                if hf:
+                    # the host learns about the actions from the flag the sampling kernel writes, not from an event between head and
+                    # tail: the whole step is ONE graph (one launch per group and step on the host instead of two)
                     self._rollout_step_tail(g, item, so)
-                g.graphs = (head, None)
-                g.graph_exec = None
+            if hf or (g.tail_in_kernel and so):
+                tail = None                       # nothing left to launch after the hand-over
             else:
-                with torch.no_grad(), torch.cuda.graph(head, pool=pool, stream=g.stream, capture_error_mode="thread_local"):
-                    self._rollout_step_head(g, so, hf)
-                if getattr(g, "tail_in_kernel", False) and so:
-                    tail = None                       # nothing left to launch after the hand-over
-                else:
-                    with torch.no_grad(), torch.cuda.graph(tail, pool=pool, stream=g.stream, capture_error_mode="thread_local"):
-                        self._rollout_step_tail(g, g.item, so)
-                g.graphs = (head, tail)
-                g.graph_exec = None
+                with torch.no_grad(), torch.cuda.graph(tail, pool=pool, stream=g.stream, capture_error_mode="thread_local"):
+                    self._rollout_step_tail(g, g.item, so)
+            g.graphs = (head, tail)
+            g.graph_exec = head.raw_cuda_graph_exec() if plan.direct_launch else None
             g.t_dev.zero_()
         with torch.no_grad():
             torch.cuda.synchronize(self.device)
@@ -969,46 +897,25 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
     def get_last_value(self):
         """Value of the observation after the last step (bootstrap for GAE), with upstream's window rule:
         rows [clip(step - L, 0), clip(step, L)) and positional indices of the last stored step (trainer.py:230-236)."""
-        L = self.memory_length
+        L, lv = self.memory_length, self._lv
         step = torch.from_numpy(self.worker_current_episode_step.copy())
         start = torch.clamp(step - L, min=0)
-        rows_host = start.unsqueeze(1) + torch.arange(L, dtype=torch.int64).unsqueeze(0)
-        lv = getattr(self, "_lv", None)
-        if lv is None:      # fixed-address operands: the forward pass below is replayed from a captured graph (round 6)
-            from types import SimpleNamespace
-            lv = self._lv = SimpleNamespace(rows=torch.empty((self.num_workers, L), dtype=torch.int64, device=self.device),
-                                            obs=torch.empty_like(self._obs_dev), out=torch.empty(self.num_workers, dtype=torch.float32, device=self.device),
-                                            graph=None, calls=0, failed=False)
-        lv.rows.copy_(rows_host, non_blocking=False)
+        lv.rows.copy_(start.unsqueeze(1) + torch.arange(L, dtype=torch.int64).unsqueeze(0), non_blocking=False)
         lv.obs.copy_(self._obs_pin, non_blocking=True)
+        # ~100 small launches on 32 samples: 1.4 ms eager, once per update; as a graph replay it is the kernels' own time.  The first
+        # two calls run eagerly (library handles, GEMM tuning), any capture failure keeps the eager path for good.
+        lv.enabled = bool(self.config.get("hip_graph_rollout", True)) and self.buffer.address_captured
+        lv()
+        return lv.out
 
-        def body():
+    def _last_value_now(self):
+        """The forward pass of ``get_last_value`` on its fixed-address operands ``_lv.rows`` / ``.obs`` -> ``.out``."""
+        lv, L = self._lv, self.memory_length
+        with torch.no_grad():
             mask = self._mask_table[torch.clamp(self._step_dev, 0, L - 1)]
             spec = WindowSpec.from_bank(self.buffer.bank, self._slot_dev, lv.rows, self.buffer.memory_indices[:, -1], mask)
             _, last_value, _ = self.model.forward_logits(lv.obs, spec, want_items=False)
             lv.out.copy_(last_value)
-
-        # ~100 small launches on 32 samples: 1.4 ms eager, once per update; as a graph replay it is the kernels' own time.  The first
-        # two calls run eagerly (library handles, GEMM tuning), any capture failure keeps the eager path for good.
-        use_graph = bool(self.config.get("hip_graph_rollout", True)) and self.buffer.address_captured and not lv.failed
-        with torch.no_grad():
-            lv.calls += 1
-            if use_graph and lv.graph is None and lv.calls > 2:
-                try:
-                    torch.cuda.synchronize(self.device)
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        body()
-                    lv.graph = g
-                except Exception as exc:       # noqa: BLE001
-                    lv.failed = True
-                    torch.cuda.synchronize(self.device)
-                    print(f"[etm] get_last_value stays eager (capture failed: {exc!r})", file=sys.stderr, flush=True)
-            if lv.graph is not None:
-                lv.graph.replay()
-            else:
-                body()
-        return lv.out
 
     # ------------------------------------------------------------------ optimisation
     def _train_epochs(self, learning_rate: float, clip_range: float, beta: float, perms=None):

@@ -145,18 +145,16 @@ class _NativeRolloutDrive:
         env, lib = self._shm_env, etm_lib.load()
         G = len(groups)
         arr = (etm_lib.RolloutGroup * G)()
-        row_bytes = self._obs_pin[0].numel() * 4
-        stage = self._stage["obs"]
+        row_bytes = groups[0].row_bytes
         for gi, g in enumerate(groups):
             a = arr[gi]
-            a.graph_exec = g.graphs[0].raw_cuda_graph_exec()
+            a.graph_exec = g.graph_exec
             a.stream = g.stream.cuda_stream
             first = gi * env.procs_per_group
             a.ready = env.v["ready"][first:].ctypes.data
             a.n_procs, a.ready_stride = env.procs_per_group, env.v["ready"].shape[1]
             a.lo, a.hi = g.lo, g.hi
-            a.obs_src = self._obs_pin.data_ptr() + g.lo * row_bytes
-            a.stage_dst = stage.data_ptr() + g.lo * row_bytes
+            a.obs_src, a.stage_dst = g.rows_src, g.stage0      # the group's pinned rows and its rows of staging row 0
             a.ss_dst = g.ss_pin.data_ptr()
         if getattr(self, "_drive_events", None) is None:
             self._drive_events = np.zeros((W * S, 3), dtype=np.int64)
@@ -189,7 +187,7 @@ class _NativeRolloutDrive:
                 buf.memory_index_host[w, t + 1:] = slot
         if chain is not None:
             self._chain_log.extend(tuple(r) for r in chain[: S - 1])
-        return float(self._drive_timing[0]), float(self._drive_timing[1])
+        return 0.0, float(self._drive_timing[0]), float(self._drive_timing[1])      # seconds in (env.step, waiting, upload + launch)
 
 
 class _RunOutputs:

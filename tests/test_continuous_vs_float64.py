@@ -137,13 +137,13 @@ def _run_case(c):
         assert tr._use_kv_cache == (path != "sample"), c["name"]
         if path != "sample":
             assert (tr.model._rf is not None) == (path in ("worker", "group")), (c["name"], "fused step kernel")
-        assert all((getattr(g_, "rf_scratch", None) is not None) == (path in ("worker", "group")) for g_ in groups), (c["name"], "step kernel")
+        assert all((g_.rf_scratch is not None) == (path in ("worker", "group")) for g_ in groups), (c["name"], "step kernel")
         if path in ("worker", "group"):
-            assert all(bool(getattr(g_, "group_kernel", False)) == (path == "group") for g_ in groups), (c["name"], "group kernel")
+            assert all(g_.group_kernel == (path == "group") for g_ in groups), (c["name"], "group kernel")
         if "rollout_groups" in c["over"]:
             assert len(tr._groups) == c["over"]["rollout_groups"]
         for g_ in tr._groups + [tr._group_all]:
-            if getattr(g_, "rf_scratch", None) is not None:
+            if g_.rf_scratch is not None:
                 assert int(ops.rollout_trxl_error(g_.rf_scratch).item()) == 0, (c["name"], "step kernel error word")
 
         b = tr.buffer

@@ -1274,7 +1274,7 @@ def test_group_rollout_step_kernel_vs_the_other_rollout_paths():
                     if prm.dim() == 1:
                         prm.add_(0.1 * torch.randn_like(prm))
             tr._sample_training_data()
-            used = [bool(getattr(g, "group_kernel", False)) for g in tr._groups]
+            used = [g.group_kernel for g in tr._groups]
             assert all(used) == (not variant), (D, W, groups, variant, used)
             assert len(tr._groups) == groups
             tr.buffer.prepare_batch_dict()

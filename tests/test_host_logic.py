@@ -727,3 +727,84 @@ def test_native_pcg64_stream_is_numpys():
         for w, g in enumerate(gens):
             assert np.array_equal(out[w], g.random(out.shape[1], dtype=np.float32))
     lib.etm_envgen_pool_destroy(pool)
+
+
+def test_rollout_plan_enumeration_invariants_and_named_rows():
+    """rollout_plan.plan_rollout decides the host-side form of a rollout from plain booleans, on the CPU.  Over every combination
+    of its inputs: exactly the 12 plans of DESIGN.md's table exist; the implications between the fields hold; several groups without
+    the K/V cache or fusable heads raise; and the rows the GPU tests assert for their configurations come out (test_gpu_parity.py:
+    the teacher-forced paths and the path-equivalence test)."""
+    import itertools
+    from rollout_plan import RolloutPlan, plan_rollout
+    names = ("graph", "stream_observations", "host_flag_actions", "direct_observation_rows", "kv_cache", "fused_encoder",
+             "heads_fusable", "several_groups", "worker_processes", "raw_graph_exec", "large_bar", "polite_wait")
+    fields = ("graph", "stream_obs", "host_flag", "own_stream", "direct_rows", "direct_launch", "native")
+    expected = {(0, 0, 0, 0, 0, 0, 0), (1, 0, 0, 0, 0, 0, 0), (1, 0, 1, 0, 0, 0, 0), (1, 0, 1, 0, 0, 1, 0), (1, 1, 0, 0, 0, 0, 0),
+                (1, 1, 0, 1, 0, 0, 0), (1, 1, 1, 0, 0, 0, 0), (1, 1, 1, 1, 0, 0, 0), (1, 1, 1, 1, 0, 1, 0), (1, 1, 1, 1, 0, 1, 1),
+                (1, 1, 1, 1, 1, 0, 0), (1, 1, 1, 1, 1, 1, 0)}
+
+    def plan(**kw):
+        asked = []
+        kw["large_bar"] = (lambda v=kw["large_bar"]: asked.append(1) or v)
+        return plan_rollout(**kw), bool(asked)
+
+    seen = set()
+    for values in itertools.product((False, True), repeat=len(names)):
+        kw = dict(zip(names, values))
+        must_raise = kw["graph"] and kw["several_groups"] and not (kw["kv_cache"] and kw["heads_fusable"])
+        if must_raise:
+            with pytest.raises(RuntimeError, match="rollout_groups > 1 needs the K/V cache"):
+                plan(**kw)
+            continue
+        p, asked = plan(**kw)
+        assert isinstance(p, RolloutPlan) and p.polite_wait == kw["polite_wait"]
+        row = tuple(int(getattr(p, f)) for f in fields)
+        seen.add(row)
+        if p.native:
+            assert p.direct_launch and p.own_stream and p.host_flag and p.stream_obs and kw["worker_processes"], kw
+        if p.direct_rows:
+            assert p.own_stream and p.host_flag and not kw["worker_processes"], kw
+        if p.own_stream:
+            assert p.stream_obs, kw
+        if not p.graph:
+            assert row == (0,) * 7, kw
+        # the device self-test behind large_bar runs only when everything else already says "direct rows"
+        assert asked == (p.graph and p.own_stream and p.host_flag and not kw["worker_processes"] and kw["direct_observation_rows"]), kw
+    assert seen == expected, (sorted(seen - expected), sorted(expected - seen))
+
+    # the default visual config on a large-BAR host with torch >= 2.8: two groups, cache on, everything fusable
+    default = dict(graph=True, stream_observations=True, host_flag_actions=True, direct_observation_rows=True, kv_cache=True,
+                   fused_encoder=True, heads_fusable=True, several_groups=True, worker_processes=False, raw_graph_exec=True,
+                   large_bar=True, polite_wait=False)
+
+    def named(**over):
+        return plan(**dict(default, **over))[0]
+
+    streamed = dict(graph=True, stream_obs=True, host_flag=True, own_stream=True, direct_launch=True)
+    assert named() == RolloutPlan(direct_rows=True, **streamed)
+    assert named(direct_observation_rows=False) == RolloutPlan(**streamed)
+    assert named(large_bar=False) == RolloutPlan(**streamed)
+    assert named(host_flag_actions=False) == RolloutPlan(graph=True, stream_obs=True, own_stream=True)
+    assert named(several_groups=False) == RolloutPlan(graph=True, stream_obs=True, host_flag=True)
+    assert named(stream_observations=False) == RolloutPlan(graph=True, host_flag=True, direct_launch=True)
+    assert named(stream_observations=False, several_groups=False) == RolloutPlan(graph=True, host_flag=True)
+    assert named(graph=False) == RolloutPlan()
+    assert named(worker_processes=True) == RolloutPlan(native=True, **streamed)
+    # vector observations: no fused encoder, hence no streaming -- worker processes are then driven by the host loop
+    assert named(worker_processes=True, fused_encoder=False) == RolloutPlan(graph=True, host_flag=True, direct_launch=True)
+    assert named(worker_processes=True, graph=False) == RolloutPlan()
+
+
+def test_step_form_choice_clears_what_an_earlier_form_left_on_the_group():
+    """PPOTrainer._choose_step_form decides a group's step form anew on every call: when the step kernel is not used (no K/V cache,
+    or no weight table after the step kernel's time-out recovery) ``group_kernel`` and ``tail_in_kernel`` are False whatever an
+    earlier capture left there -- else the multi-launch tail would skip its bank and cache writes -- and nothing is allocated."""
+    from types import SimpleNamespace
+    import trainer
+    for kv_cache in (False, True):
+        model = SimpleNamespace(_rf=None, _rfg=None)
+        tr = SimpleNamespace(model=model, _etm=None, _use_kv_cache=kv_cache, _groups=[None, None], config={}, box=None,
+                             _kv_w_blocked=object())
+        g = SimpleNamespace(full=False, W=8, group_kernel=True, tail_in_kernel=True, rf_scratch=None, rf_scratch_kind=None)
+        assert trainer.PPOTrainer._choose_step_form(tr, g, True) == (False, None, None)
+        assert g.group_kernel is False and g.tail_in_kernel is False and g.rf_scratch is None

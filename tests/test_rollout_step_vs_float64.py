@@ -206,14 +206,14 @@ def _run_case(c):
         assert tr._use_kv_cache == (path != "sample"), (c["name"], "K | V cache")
         if path != "sample":         # (without the cache the trainer never reaches the step kernels, whatever the model packed)
             assert (tr.model._rf is not None) == (path in ("worker", "group")), (c["name"], "fused step kernel")
-        assert all((getattr(g, "rf_scratch", None) is not None) == (path in ("worker", "group")) for g in groups), (c["name"], "step kernel")
+        assert all((g.rf_scratch is not None) == (path in ("worker", "group")) for g in groups), (c["name"], "step kernel")
         if path in ("worker", "group"):
-            assert all(bool(getattr(g, "group_kernel", False)) == (path == "group") for g in groups), (c["name"], "group kernel")
-            assert all(bool(getattr(g, "tail_in_kernel", False)) == cfg.get("fused_rollout_tail", True) for g in groups), (c["name"], "tail")
+            assert all(g.group_kernel == (path == "group") for g in groups), (c["name"], "group kernel")
+            assert all(g.tail_in_kernel == cfg.get("fused_rollout_tail", True) for g in groups), (c["name"], "tail")
         if "rollout_groups" in c["over"]:
             assert len(tr._groups) == c["over"]["rollout_groups"]
         for g in tr._groups + [tr._group_all]:
-            if getattr(g, "rf_scratch", None) is not None:
+            if g.rf_scratch is not None:
                 assert int(ops.rollout_trxl_error(g.rf_scratch).item()) == 0, (c["name"], "step kernel error word")
 
         b = tr.buffer

@@ -374,7 +374,7 @@ def rollout_step(trainer, launches=40):
     res["step_sum_us"] = sum(v[0] * 1e3 * v[1] / launches for v in t.values())
     if "rollout_trxl_kernel" in t:
         feats = trainer.model.lin_hidden.in_features
-        m = rollout_step_model(trainer.config, g.W, feats, group=bool(getattr(g, "group_kernel", False)))
+        m = rollout_step_model(trainer.config, g.W, feats, group=g.group_kernel)
         us = t["rollout_trxl_kernel"][0] * 1e3
         gbs = m["bytes_per_launch"] / (us * 1e-6) / 1e9
         res["rollout_trxl_kernel"] = dict(kernel="rollout_trxl_kernel", bound="latency (dependent chain of matrix-vector products; bytes are L2 / "
