@@ -22,7 +22,9 @@ from etm import ops
 
 class Buffer:
     def __init__(self, config: dict, observation_space, action_space_shape: tuple, max_episode_length: int,
-                 device: torch.device, continuous: bool = False) -> None:
+                 device: torch.device, continuous: bool = False, observation_dtype: torch.dtype = torch.float32) -> None:
+        """``observation_dtype``: ``torch.uint8`` keeps image observations as the bytes the environment emits (byte k stands for
+        float32(k) / float32(255); the encoder's first layer reads them) -- ``obs`` is then a quarter of its float32 size."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("Buffer is HBM-resident: it needs the MI355X (HIP) device; there is no CPU path in this build")
@@ -49,7 +51,9 @@ class Buffer:
 
         # (Box: the raw float actions [W, S, A] and one joint log-prob per sample)
         self.actions = torch.zeros((W, S, B), dtype=torch.float32 if continuous else torch.long, device=dev)
-        self.obs = torch.zeros((W, S) + tuple(observation_space.shape), dtype=torch.float32, device=dev)
+        if observation_dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"observations are float32 or uint8, got {observation_dtype}")
+        self.obs = torch.zeros((W, S) + tuple(observation_space.shape), dtype=observation_dtype, device=dev)
         self.log_probs = torch.zeros((W, S, 1 if continuous else B), dtype=torch.float32, device=dev)
         self.values = torch.zeros((W, S), dtype=torch.float32, device=dev)
         self.advantages = torch.zeros((W, S), dtype=torch.float32, device=dev)

@@ -79,6 +79,7 @@ template <bool DGRAD, int C, int HW, int KS, int S, int COUT, int G_, int BAND =
 struct B3Geo {
   static constexpr int G = G_, WPC = WPC_;
   static constexpr bool SWZ = SWZ_;
+  static constexpr bool U8 = false;                              // (B3GeoBytes: the image in memory is bytes)
   static constexpr int HOUT = (HW - KS) / S + 1;                 // output size of the layer
   static constexpr int T = KS / S;                               // backward-data: taps per dimension and class
   static constexpr int CI = DGRAD ? COUT : C;                    // channels of the LDS-resident image
@@ -133,9 +134,23 @@ struct B3Geo {
   }
 };
 
+// Byte observations (include/etm_hip.h): the layer-1 forward geometry with uint8 images in memory.  p.x is then a byte tensor, a fill
+// load is 16 bytes = 16 elements (all unit sizes are multiples of 16 bytes), each becomes etm_byte_unit and is split as its fp32 twin
+// splits it; the planes and everything after the fill are the fp32 instantiation's code.  The flag travels in the geometry type, so the
+// float instantiations keep their names.
+template <class Base>
+struct B3GeoBytes : Base {
+  static constexpr bool U8 = true;
+};
+
 template <class L, bool DGRAD, int C, int S>
 __global__ __launch_bounds__(256, L::WPC) void conv_b3_kernel(const B3Args p) {
-  constexpr int G = L::G, TPW = L::TPW, NT = L::NT, RP = L::RP, KSTEPS = L::KSTEPS, NQ = L::NQ, PD = 3;
+  constexpr bool U8 = L::U8;
+  static_assert(!U8 || (L::THREE && !DGRAD && L::G == 1 && (L::Q_IMG * 4) % 16 == 0 && (L::Q_UNIT * 4) % 16 == 0 && (L::Q_ROW0 * 4) % 16 == 0),
+                "byte images: layer 1 forward, units of whole 16-byte loads");
+  constexpr int Q16 = L::Q_UNIT / 4;                       // (U8) 16-byte loads per unit
+  constexpr int G = L::G, TPW = L::TPW, NT = L::NT, RP = L::RP, KSTEPS = L::KSTEPS, NQ = U8 ? (Q16 + 255) / 256 : L::NQ, PD = 3;
+  constexpr int LPK = U8 ? (NQ + KSTEPS - 1) / KSTEPS : L::LPK;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];     // three planes of [G] images
   const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -186,6 +201,7 @@ __global__ __launch_bounds__(256, L::WPC) void conv_b3_kernel(const B3Args p) {
   // ---- fill: this thread's float4 u of a group -> LDS byte offset inside a plane
   auto fill_dst = [&](int u) {
     const int q = tid + u * 256;
+    if constexpr (U8) return q * 32;                       // 16 elements x 2 bytes per plane
     const int g = q / L::Q_UNIT, qi = q - g * L::Q_UNIT;
     if (L::THREE) return g * L::IMGB + qi * 8;
     const int pix = qi / (L::CI / 4), c4 = qi - pix * (L::CI / 4), y = pix / L::HI, x = pix - y * L::HI;
@@ -203,7 +219,11 @@ __global__ __launch_bounds__(256, L::WPC) void conv_b3_kernel(const B3Args p) {
     const int n0 = u0 / L::NB, b0 = u0 - n0 * L::NB;
     const long long src = (G == 1 && p.img_index) ? p.img_index[n0] : (long long)n0;
     const int units = exists ? min(G, p.N * L::NB - u0) : 0;
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + src * (L::Q_IMG * 4) + b0 * (L::Q_ROW0 * 4)), 0, units * L::Q_UNIT * 16, 0x00020000);
+    if constexpr (U8)
+      return __builtin_amdgcn_make_buffer_rsrc((void *)(reinterpret_cast<const unsigned char *>(p.x) + src * (L::Q_IMG * 4) + b0 * (L::Q_ROW0 * 4)), 0,
+                                               units * L::Q_UNIT * 4, 0x00020000);
+    else
+      return __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + src * (L::Q_IMG * 4) + b0 * (L::Q_ROW0 * 4)), 0, units * L::Q_UNIT * 16, 0x00020000);
   };
   f32x4 fill[NQ];
   unsigned fbits[DGRAD ? NQ : 1];                          // (backward-data with src_bits: the pattern word of every float4)
@@ -211,6 +231,26 @@ __global__ __launch_bounds__(256, L::WPC) void conv_b3_kernel(const B3Args p) {
 #pragma unroll
   for (int u = 0; u < NQ; ++u) fdst[u] = fill_dst(u);
   auto fill_to_lds = [&]() {
+    if constexpr (U8) {                                    // fill[u] holds 16 bytes: four times the fp32 fill's split and stores
+#pragma unroll
+      for (int u = 0; u < NQ; ++u) {
+        if (tid + u * 256 < Q16) {
+          const u32x4 raw = __builtin_bit_cast(u32x4, fill[u]);
+#pragma unroll
+          for (int w = 0; w < 4; ++w) {
+            const f32x4 v = etm_bytes4_unit(raw[w]);
+            unsigned h0, m0, l0, h1, m1, l1;
+            b3_split_pair(v[0], v[1], h0, m0, l0);
+            b3_split_pair(v[2], v[3], h1, m1, l1);
+            const int d = fdst[u] + w * 8;
+            *reinterpret_cast<u32x2 *>(lds + d) = u32x2{h0, h1};
+            *reinterpret_cast<u32x2 *>(lds + L::PLANE + d) = u32x2{m0, m1};
+            *reinterpret_cast<u32x2 *>(lds + 2 * L::PLANE + d) = u32x2{l0, l1};
+          }
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int u = 0; u < NQ; ++u) {
       if (tid + u * 256 < G * L::Q_UNIT) {
@@ -348,7 +388,7 @@ __global__ __launch_bounds__(256, L::WPC) void conv_b3_kernel(const B3Args p) {
         for (int pl = 0; pl < 3; ++pl) b[s][pl] = w_load(ks + PD, pl);
       }
 #pragma unroll
-      for (int u = ks * L::LPK; u < (ks + 1) * L::LPK; ++u)
+      for (int u = ks * LPK; u < (ks + 1) * LPK; ++u)
         if (u < NQ) fill_load(u, nrx, nrxb);
       __builtin_amdgcn_sched_barrier(0);
     });
@@ -403,9 +443,9 @@ __global__ __launch_bounds__(256, L::WPC) void conv_b3_kernel(const B3Args p) {
   }
 }
 
-template <bool DGRAD, int C, int HW, int KS, int S, int COUT, int G, int BAND = 0, int WPC = 1, bool SWZ = false>
-int launch_b3(const B3Args &p0, hipStream_t st) {
-  using L = B3Geo<DGRAD, C, HW, KS, S, COUT, G, BAND, WPC, SWZ>;
+template <class L, bool DGRAD, int C, int S>
+int launch_b3_geo(const B3Args &p0, hipStream_t st) {
+  constexpr int G = L::G, WPC = L::WPC;
   B3Args p = p0;
   if (G > 1 && p.img_index) return ETM_EUNSUPPORTED;
   if ((long long)p.N * L::HRES * L::HRES * L::CRES * 4 >= 0x7ffffff0ll) return ETM_EUNSUPPORTED;      // 32-bit byte offsets into the result
@@ -418,6 +458,10 @@ int launch_b3(const B3Args &p0, hipStream_t st) {
   const int grid = p.n_groups < 256 * WPC ? p.n_groups : 256 * WPC;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, p);
   return etm_launch_status();
+}
+template <bool DGRAD, int C, int HW, int KS, int S, int COUT, int G, int BAND = 0, int WPC = 1, bool SWZ = false>
+int launch_b3(const B3Args &p, hipStream_t st) {
+  return launch_b3_geo<B3Geo<DGRAD, C, HW, KS, S, COUT, G, BAND, WPC, SWZ>, DGRAD, C, S>(p, st);
 }
 
 // ---- weight split + packing: one thread per (k, output channel) element
@@ -496,6 +540,19 @@ extern "C" int etm_conv_b3_fwd(const float *x, const int64_t *x_index, const uin
   if (C == 32 && H == 20 && KH == 4 && S == 2 && Cout == 64) return launch_b3<false, 32, 20, 4, 2, 64, 2, 0, 1, true>(p, st);      // (one padded image per group: 93.5 us; two swizzled ones: 76)
   if (C == 64 && H == 9 && KH == 3 && S == 1 && Cout == 64) return launch_b3<false, 64, 9, 3, 1, 64, 2, 0, 2>(p, st);
   return ETM_EUNSUPPORTED;
+}
+
+// The first layer on NHWC byte images (include/etm_hip.h): the instantiation above with 16-byte = 16-element fill loads.
+extern "C" int etm_conv_b3_fwd_u8(const uint8_t *x, const int64_t *x_index, const uint16_t *w_b3, const float *bias, float *y, uint32_t *relu_bits,
+                                  int N, int C, int H, int W, int Cout, int KH, int KW, int S, void *stream) {
+  (void)hipGetLastError();
+  if (!x || !w_b3 || !bias || !y || N <= 0) return ETM_EINVAL;
+  if ((uintptr_t)x % 16 || (uintptr_t)y % 16 || (uintptr_t)w_b3 % 16 || (uintptr_t)bias % 16) return ETM_EINVAL;
+  if (!(C == 3 && H == 84 && W == 84 && KH == 8 && KW == 8 && S == 4 && Cout == 32)) return ETM_EUNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  B3Args p{reinterpret_cast<const float *>(x), (const long long *)x_index, w_b3, bias, nullptr, nullptr, nullptr, relu_bits, y, N, 0};
+  EtmProfScope prof(ETM_K_CONV_FWD_L1, st);
+  return launch_b3_geo<B3GeoBytes<B3Geo<false, 3, 84, 8, 4, 32, 1, 10, 2>>, false, 3, 4>(p, st);
 }
 
 // dx = conv_transpose(dy) * (y_below > 0) for layers 2 / 3 (arguments as etm_conv_train_dgrad: C, H, W = the layer INPUT, w_b3 from

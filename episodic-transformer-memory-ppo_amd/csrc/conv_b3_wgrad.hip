@@ -67,6 +67,7 @@ struct W3Geo {
   static constexpr int G = G_, PSPLIT = PSPLIT_, NW = NW_, NTH = NW_ * 64, WPC = WPC_;      // WPC: workgroups per CU
   static constexpr int HOUT = (HW - KS) / S + 1;
   static constexpr bool THREE = C == 3;
+  static constexpr bool U8 = false;                                 // (W3GeoBytes: the layer input in memory is bytes)
   static constexpr int NB = BAND > 0 ? HOUT / BAND : 1;
   static constexpr int OROWS = BAND > 0 ? BAND : HOUT;              // output rows of a unit
   static constexpr int HROWS = (OROWS - 1) * S + KS;                // input rows of a unit
@@ -99,9 +100,21 @@ struct W3Geo {
   }
 };
 
+// Byte observations (include/etm_hip.h): the layer-1 geometry with uint8 input images in memory.  p.x is then a byte tensor, an input
+// fill load is 16 bytes = 16 elements, each becomes etm_byte_unit and is split as its fp32 twin splits it; the planes and everything after
+// the fill are the fp32 instantiation's code.  The flag travels in the geometry type, so the float instantiations keep their names.
+template <class Base>
+struct W3GeoBytes : Base {
+  static constexpr bool U8 = true;
+};
+
 template <class L, int C, int HW, int S, int COUT>
 __global__ __launch_bounds__(L::NTH, L::WPC * L::NW / 4) void conv_b3_wgrad_kernel(const W3Args p) {
-  constexpr int G = L::G, KTW = L::KTW, CTW = L::CTW, STEPS = L::STEPS, NQX = L::NQX, NQD = L::NQD, NTH = L::NTH;
+  constexpr bool U8 = L::U8;
+  static_assert(!U8 || (L::THREE && L::G == 1 && (L::QX_IMG * 4) % 16 == 0 && (L::QX * 4) % 16 == 0 && (L::QX_ROW0 * 4) % 16 == 0),
+                "byte images: layer 1, units of whole 16-byte loads");
+  constexpr int QX16 = L::QX / 4;                          // (U8) 16-byte loads per unit
+  constexpr int G = L::G, KTW = L::KTW, CTW = L::CTW, STEPS = L::STEPS, NQX = U8 ? (QX16 + L::NTH - 1) / L::NTH : L::NQX, NQD = L::NQD, NTH = L::NTH;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];     // input planes [3][G][IMGB], gradient planes [3][MPAD][CPBD]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -156,6 +169,7 @@ __global__ __launch_bounds__(L::NTH, L::WPC * L::NW / 4) void conv_b3_wgrad_kern
   // ---- fills
   auto x_dst = [&](int u) {
     const int q = tid + u * NTH;
+    if constexpr (U8) return q * 32;                       // 16 elements x 2 bytes per plane
     const int g = q / L::QX, qi = q - g * L::QX;
     if (L::THREE) return g * L::IMGB + qi * 8;
     const int pix = qi / (C / 4), c4 = qi - pix * (C / 4), y = pix / HW, x = pix - y * HW;
@@ -173,7 +187,11 @@ __global__ __launch_bounds__(L::NTH, L::WPC * L::NW / 4) void conv_b3_wgrad_kern
     const int units = exists ? min(G, p.N * L::NB - u0) : 0;
     if (grad) return __builtin_amdgcn_make_buffer_rsrc((void *)(p.dy + (long long)n0 * (L::QD_IMG * 4) + b0 * (L::QD * 4)), 0, units * L::QD * 16, 0x00020000);
     const long long src = (G == 1 && p.img_index) ? p.img_index[n0] : (long long)n0;
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + src * (L::QX_IMG * 4) + b0 * (L::QX_ROW0 * 4)), 0, units * L::QX * 16, 0x00020000);
+    if constexpr (U8)
+      return __builtin_amdgcn_make_buffer_rsrc((void *)(reinterpret_cast<const unsigned char *>(p.x) + src * (L::QX_IMG * 4) + b0 * (L::QX_ROW0 * 4)), 0,
+                                               units * L::QX * 4, 0x00020000);
+    else
+      return __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + src * (L::QX_IMG * 4) + b0 * (L::QX_ROW0 * 4)), 0, units * L::QX * 16, 0x00020000);
   };
   f32x4 fx[NQX], fd[NQD];
   unsigned fdb[NQD];                                       // (with dy_bits: the pattern word of every gradient float4)
@@ -215,9 +233,19 @@ __global__ __launch_bounds__(L::NTH, L::WPC * L::NW / 4) void conv_b3_wgrad_kern
         for (int q = 0; q < 4; ++q) bsum[q] += fd[u][q];
         put(fd[u], d_dst(u), L::DPLANE);
       }
+    if constexpr (U8) {                                    // fx[u] holds 16 bytes: four times the fp32 fill's split and stores
 #pragma unroll
-    for (int u = 0; u < NQX; ++u)
-      if (tid + u * NTH < G * L::QX) put(fx[u], x_dst(u), L::XPLANE);
+      for (int u = 0; u < NQX; ++u)
+        if (tid + u * NTH < QX16) {
+          const u32x4 raw = __builtin_bit_cast(u32x4, fx[u]);
+#pragma unroll
+          for (int w = 0; w < 4; ++w) put(etm_bytes4_unit(raw[w]), x_dst(u) + w * 8, L::XPLANE);
+        }
+    } else {
+#pragma unroll
+      for (int u = 0; u < NQX; ++u)
+        if (tid + u * NTH < G * L::QX) put(fx[u], x_dst(u), L::XPLANE);
+    }
   };
 
   // Two accumulators per tile: the leading product x1 d1 alone, the five small products together.  The bf16 MFMA's accumulate step
@@ -358,9 +386,11 @@ __global__ __launch_bounds__(L::NTH, L::WPC * L::NW / 4) void conv_b3_wgrad_kern
   }
 }
 
-template <int C, int HW, int KS, int S, int COUT, int G, int BAND, int PSPLIT, int NW, int WPC = 1>
-struct W3 {
-  using L = W3Geo<C, HW, KS, S, COUT, G, BAND, PSPLIT, NW, WPC>;
+// launcher of one geometry type L (a W3Geo, or W3GeoBytes of one)
+template <class L_, int C, int HW, int S, int COUT>
+struct W3Run {
+  using L = L_;
+  static constexpr int G = L::G, WPC = L::WPC;
   static constexpr int LDS_ALL = L::LDS + L::STEPS * 2 * 64 * 4;      // planes + the address table
   static_assert(LDS_ALL * WPC <= 160 * 1024, "LDS of a CU");
   static int slices(int N) {
@@ -378,10 +408,13 @@ struct W3 {
     return etm_launch_status();
   }
 };
+template <int C, int HW, int KS, int S, int COUT, int G, int BAND, int PSPLIT, int NW, int WPC = 1>
+using W3 = W3Run<W3Geo<C, HW, KS, S, COUT, G, BAND, PSPLIT, NW, WPC>, C, HW, S, COUT>;
 //              C  HW KS S COUT G BAND PSPLIT NW
 using W3L1 = W3<3, 84, 8, 4, 32, 1, 5, 2, 4, 2>;
 using W3L2 = W3<32, 20, 4, 2, 64, 1, 0, 1, 8>;
 using W3L3 = W3<64, 9, 3, 1, 64, 2, 0, 1, 8>;
+using W3L1U8 = W3Run<W3GeoBytes<W3L1::L>, 3, 84, 4, 32>;      // layer 1 on byte images: W3L1 with 16-element fill loads
 
 int w3_layer(int C, int H, int W, int Cout, int KH, int KW, int S) {
   if (H != W || KH != KW) return 0;
@@ -424,4 +457,19 @@ extern "C" int etm_conv_b3_wgrad(const float *x, const int64_t *x_index, const f
     case 2: return W3L2::launch(p, st);
     default: return W3L3::launch(p, st);
   }
+}
+
+// The first layer on NHWC byte images (include/etm_hip.h): slices and workspace layout of etm_conv_b3_wgrad.
+extern "C" int etm_conv_b3_wgrad_u8(const uint8_t *x, const int64_t *x_index, const float *dy, const uint32_t *dy_relu_bits, float *workspace,
+                                    int64_t workspace_bytes, int N, int C, int H, int W, int Cout, int KH, int KW, int S, void *stream) {
+  (void)hipGetLastError();
+  if (!x || !dy || !workspace || N <= 0) return ETM_EINVAL;
+  if ((uintptr_t)x % 16 || (uintptr_t)dy % 16 || (uintptr_t)workspace % 16) return ETM_EINVAL;
+  if (w3_layer(C, H, W, Cout, KH, KW, S) != 1) return ETM_EUNSUPPORTED;
+  const int slices = W3L1U8::slices(N);
+  if (workspace_bytes < (int64_t)slices * ((int64_t)KH * KW * C * Cout + Cout) * (int64_t)sizeof(float)) return ETM_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  W3Args p{reinterpret_cast<const float *>(x), (const long long *)x_index, dy, dy_relu_bits, workspace, N, 0};
+  EtmProfScope prof(ETM_K_CONV_WGRAD_L1, st);
+  return W3L1U8::launch(p, st);
 }

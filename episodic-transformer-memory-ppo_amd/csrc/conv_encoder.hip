@@ -19,7 +19,11 @@ namespace {
 struct ConvParams {
   const long long *in_index;   // optional: input = in + *in_index * in_index_stride (row of a time-major staging array)
   long long in_index_stride;
-  const float *in, *w, *bias;
+  union {
+    const float *in;
+    const unsigned char *in8;  // conv_relu_u8_kernel: the input is bytes
+  };
+  const float *w, *bias;
   float *out;
   int N, C, H, W, Cout, KH, KW, S, Ho, Wo;
   int in_nhwc, out_nchw;
@@ -31,99 +35,29 @@ constexpr int CONV_NW = 8;   // waves per workgroup = K slices
 // GB (template parameter) = 8-wide k-groups per wave and batch: all operands of a batch are requested before its first MFMA;
 // the launcher picks the smallest instantiated GB that covers a wave's share of K in one batch.
 
+// U8 (conv_relu_u8_kernel): the NCHW first layer on byte observations -- p.in is then a byte pointer, offsets and in_index_stride count
+// elements (= bytes), a lane's four window elements are one 4-byte load and become etm_byte_unit of each; everything after the load is the
+// fp32 kernel.  One body for both (conv_relu_body.inc).
 template <int NT, int GB>
 __global__ __launch_bounds__(CONV_NW * 64) void conv_relu_kernel(const ConvParams p) {
-  constexpr int NW = CONV_NW;
-  __shared__ float red[NW * NT * 16 * 64];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, half = lane >> 5;
-  const int M = p.N * p.Ho * p.Wo;
-  const int m = min((int)blockIdx.x * 32 + col, M - 1);
-  const int n = m / (p.Ho * p.Wo);
-  const int rem = m - n * p.Ho * p.Wo;
-  const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-  const float *in_base = p.in + (p.in_index ? *p.in_index * p.in_index_stride : 0);
-  f32x16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-  // weights arrive packed in fragment order (etm_hip.h): the B fragment of (k-group g, tile t) is 64 lanes x 4 floats,
-  // contiguous -- one fully coalesced 1 KB load per wave instead of 64 different cache lines
-  const int t_first = (int)blockIdx.y * NT;
-  const float *wlane = p.w + lane * 4 + (long long)t_first * 256;
-
-  auto a_ptr = [&](int k0) -> const float * {
-    const int seg = k0 / p.seg_len, off = k0 - seg * p.seg_len;
-    long long base;
-    if (p.in_nhwc) {            // seg = ky
-      base = (((long long)n * p.H + oy * p.S + seg) * p.W + ox * p.S) * p.C;
-    } else {                    // seg = c * KH + ky
-      const int c = seg / p.KH, ky = seg - c * p.KH;
-      base = (((long long)n * p.C + c) * p.H + oy * p.S + ky) * p.W + ox * p.S;
-    }
-    return in_base + base + off + half * 4;
-  };
-
-  // Wave w takes k-groups w, w + NW, ... in batches of GB.  Every operand of a batch is requested up front (unconditional
-  // loads, groups past the end clamped to the last one), so a batch exposes ONE global-memory round trip; the three encoder
-  // layers (3 / 8 / 9 groups per wave) are a single batch.  (The first version exposed a round trip per pair of groups, the
-  // second one per four: at 32 images the kernel is pure latency.)
-  f32x4 a_cur[GB], b_cur[GB][NT];
-  const int last = p.groups - 1;
-#define ETM_CONV_LOAD(dst_a, dst_b, g0_)                                                          \
-  _Pragma("unroll") for (int u = 0; u < GB; ++u) {                                                \
-    const int g_ = (g0_) + u * NW;                                                                \
-    const int gc_ = g_ < p.groups ? g_ : last;                                                    \
-    dst_a[u] = *reinterpret_cast<const f32x4 *>(a_ptr(gc_ * 8));                                  \
-    _Pragma("unroll") for (int t = 0; t < NT; ++t) dst_b[u][t] = *reinterpret_cast<const f32x4 *>(wlane + ((long long)gc_ * p.nt_total + t) * 256); \
-  }
-  for (int g0 = wave; g0 < p.groups; g0 += GB * NW) {
-    ETM_CONV_LOAD(a_cur, b_cur, g0)
-#pragma unroll
-    for (int u = 0; u < GB; ++u) {
-      if (g0 + u * NW < p.groups) {     // wave-uniform: groups past the end are skipped
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[u][j], b_cur[u][t][j], acc[t], 0, 0, 0);
-      }
-    }
-  }
-#undef ETM_CONV_LOAD
-
-  // reduce the K-slices of the waves through LDS (lane-contiguous: conflict-free)
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[((wave * NT + t) * 16 + r) * 64 + lane] = acc[t][r];
-  __syncthreads();
-  // each thread finishes (t, r) pairs for its lane: NT*16 pairs over the waves
-  for (int pr = wave; pr < NT * 16; pr += NW) {
-    const int t = pr / 16, r = pr - t * 16;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) v += red[((w * NT + t) * 16 + r) * 64 + lane];
-    const int row = mfma32_row(r, lane);
-    const int mm = (int)blockIdx.x * 32 + row;
-    if (mm < M) {
-      const int co = (t_first + t) * 32 + col;
-      v = fmaxf(v + p.bias[co], 0.f);
-      if (p.out_nchw) {
-        const int nn = mm / (p.Ho * p.Wo);
-        const int rr = mm - nn * p.Ho * p.Wo;
-        p.out[((long long)nn * p.Cout + co) * p.Ho * p.Wo + rr] = v;
-      } else {
-        p.out[(long long)mm * p.Cout + co] = v;
-      }
-    }
-  }
+  constexpr bool U8 = false;
+#include "conv_relu_body.inc"
+}
+template <int NT, int GB>
+__global__ __launch_bounds__(CONV_NW * 64) void conv_relu_u8_kernel(const ConvParams p) {
+  constexpr bool U8 = true;
+#include "conv_relu_body.inc"
 }
 }  // namespace
 
-extern "C" int etm_conv_relu(const float *in, const int64_t *in_index, int64_t in_index_stride, const float *w, const float *bias,
-                             float *out, int N, int C, int H, int W, int Cout, int KH, int KW, int S, int in_nhwc, int out_nchw,
-                             void *stream) {
+namespace {
+// the instantiation (NT, GB) of the float or the byte kernel
+// (the byte form is the first layer: one channel tile, Cout 32 -- etm_conv_relu_u8 refuses every other width)
+#define ETM_CONV_KERNEL(NT_, GB_) (U8 ? conv_relu_u8_kernel<NT_, GB_> : conv_relu_kernel<NT_, GB_>)
+template <bool U8>
+int conv_relu_launch(const float *in, const int64_t *in_index, int64_t in_index_stride, const float *w, const float *bias,
+                     float *out, int N, int C, int H, int W, int Cout, int KH, int KW, int S, int in_nhwc, int out_nchw,
+                     void *stream) {
   (void)hipGetLastError();
   if (!in || !w || !bias || !out || N <= 0 || C <= 0 || H < KH || W < KW || Cout <= 0 || KH <= 0 || KW <= 0 || S <= 0) return ETM_EINVAL;
   ConvParams p;
@@ -145,8 +79,10 @@ extern "C" int etm_conv_relu(const float *in, const int64_t *in_index, int64_t i
   const int gpw = (p.groups + CONV_NW - 1) / CONV_NW;     // k-groups per wave
   const dim3 block(CONV_NW * 64);
   if (Cout == 32) {
-    if (gpw <= 4) hipLaunchKernelGGL((conv_relu_kernel<1, 4>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((conv_relu_kernel<1, 12>), grid, block, 0, st, p);
+    if (gpw <= 4) hipLaunchKernelGGL(ETM_CONV_KERNEL(1, 4), grid, block, 0, st, p);
+    else hipLaunchKernelGGL(ETM_CONV_KERNEL(1, 12), grid, block, 0, st, p);
+  } else if constexpr (U8) {
+    return ETM_EUNSUPPORTED;
   } else if (2 * grid.x <= 256) {
     // few pixel tiles (a worker group of a rollout step): one channel tile per workgroup -- twice the CUs, half the MFMA chain
     // and half the operand requests per wave; the A fragments are fetched twice, which is nothing at this size
@@ -160,4 +96,23 @@ extern "C" int etm_conv_relu(const float *in, const int64_t *in_index, int64_t i
     else hipLaunchKernelGGL((conv_relu_kernel<2, 12>), grid, block, 0, st, p);
   }
   return etm_launch_status();
+}
+#undef ETM_CONV_KERNEL
+}  // namespace
+
+extern "C" int etm_conv_relu(const float *in, const int64_t *in_index, int64_t in_index_stride, const float *w, const float *bias,
+                             float *out, int N, int C, int H, int W, int Cout, int KH, int KW, int S, int in_nhwc, int out_nchw,
+                             void *stream) {
+  return conv_relu_launch<false>(in, in_index, in_index_stride, w, bias, out, N, C, H, W, Cout, KH, KW, S, in_nhwc, out_nchw, stream);
+}
+
+// The NCHW first layer on byte observations (include/etm_hip.h): the fp32 kernel's address arithmetic in elements = bytes, one 4-byte
+// load per lane and k-group (W % 4 == 0, S % 4 == 0, 8-wide groups: 4-byte aligned when the base and the row stride are).
+extern "C" int etm_conv_relu_u8(const uint8_t *in, const int64_t *in_index, int64_t in_index_stride, const float *w, const float *bias,
+                                float *out, int N, int C, int H, int W, int Cout, int KH, int KW, int S, int in_nhwc, int out_nchw,
+                                void *stream) {
+  if (in_nhwc || Cout != 32) return ETM_EUNSUPPORTED;
+  if ((uintptr_t)in % 4 || in_index_stride % 4 || ((int64_t)C * H * W) % 4) return ETM_EINVAL;
+  return conv_relu_launch<true>(reinterpret_cast<const float *>(in), in_index, in_index_stride, w, bias, out, N, C, H, W, Cout, KH, KW, S, 0,
+                                out_nchw, stream);
 }

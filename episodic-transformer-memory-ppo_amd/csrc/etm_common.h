@@ -188,6 +188,23 @@ __device__ __forceinline__ void etm_sample_gaussian(const float *mu, const float
   st_values[row] = value;
 }
 
+// uint8 image observations: byte k stands for float(k) / 255.f CORRECTLY ROUNDED (what `obs.astype(np.float32) / 255.` computes on the
+// host; k * (1 / 255.f) differs from it for 126 of the 256 bytes).  One definition for every kernel that reads bytes: the quotient estimate
+// q = k y (y = the fp32 nearest to 1 / 255) and one residual correction, r = k - 255 q exactly (fma), q + r y rounded once -- the final
+// step of a correctly rounded fp32 division without the scaling and fix-up a general divisor needs (v_cvt_f32_ubyteN + 3 operations; the
+// host test checks this arithmetic against the quotient for all 256 bytes in exact rational arithmetic, the device test on the device).
+__device__ __forceinline__ float etm_byte_unit(unsigned k) {
+  constexpr float y = 1.f / 255.f;
+  const float a = (float)k;
+  const float q = a * y;
+  const float r = __builtin_fmaf(-255.f, q, a);
+  return __builtin_fmaf(r, y, q);
+}
+// the four bytes of a little-endian word (byte 0 = lowest address)
+__device__ __forceinline__ f32x4 etm_bytes4_unit(unsigned w) {
+  return f32x4{etm_byte_unit(w & 0xffu), etm_byte_unit((w >> 8) & 0xffu), etm_byte_unit((w >> 16) & 0xffu), etm_byte_unit(w >> 24)};
+}
+
 static inline int etm_launch_status() { return (int)hipGetLastError(); }
 
 // ---- optional per-kernel timing with HIP events (see etm_profile_* in include/etm_hip.h); off by default.
@@ -199,7 +216,7 @@ enum EtmKernelId {
   ETM_K_CONV_TRAIN_FWD, ETM_K_CONV_TRAIN_DGRAD, ETM_K_CONV_TRAIN_WGRAD, ETM_K_ROLLOUT_FUSED,
   // the encoder passes per layer (kernel size 8 / 4 / 3 = layers 1 / 2 / 3 of model.py:29-31; other geometries keep the ids above)
   ETM_K_CONV_FWD_L1, ETM_K_CONV_FWD_L2, ETM_K_CONV_FWD_L3, ETM_K_CONV_DGRAD_L2, ETM_K_CONV_DGRAD_L3,
-  ETM_K_CONV_WGRAD_L1, ETM_K_CONV_WGRAD_L2, ETM_K_CONV_WGRAD_L3, ETM_K_HIDDEN_PARTIAL, ETM_K_RELU_BWD_COLSUM, ETM_K_GATHER_ROWS, ETM_K_GROUPED_DW,
+  ETM_K_CONV_WGRAD_L1, ETM_K_CONV_WGRAD_L2, ETM_K_CONV_WGRAD_L3, ETM_K_HIDDEN_PARTIAL, ETM_K_RELU_BWD_COLSUM, ETM_K_GATHER_ROWS, ETM_K_GROUPED_DW, ETM_K_BYTES_TO_UNIT,
   ETM_K_COUNT
 };
 // profile id of an encoder pass by layer (kernel size), falling back to the pass's generic id

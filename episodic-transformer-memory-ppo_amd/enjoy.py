@@ -33,8 +33,11 @@ def run_episode(model, env, config, device, max_steps=None):
     memory_length = config["transformer"]["memory_length"]
     rewards, info, done, t = [], None, False, 0
     obs = env.reset()
+    # byte image observations go to the model as they are (byte k stands for k / 255: model._encode), anything else as float32
+    from environments import observation_dtype
+    obs_dtype = torch.uint8 if observation_dtype(env.observation_space) == np.uint8 else torch.float32
     while not done and (max_steps is None or t < max_steps):
-        obs_t = torch.tensor(np.expand_dims(obs, 0), dtype=torch.float32, device=device)
+        obs_t = torch.tensor(np.expand_dims(obs, 0), dtype=obs_dtype, device=device)
         indices = memory_indices[t].unsqueeze(0)
         in_memory = memory[0, indices]                                  # [1, L, blocks, D]
         mask = memory_mask[max(0, min(t, memory_length - 1))].unsqueeze(0)

@@ -13,6 +13,21 @@ def action_space_shape(space):
     return (int(space.n),)
 
 
+def observation_dtype(env_or_space):
+    """The dtype of the observations a front-end (``observation_dtype``) or an environment's ``observation_space`` (``dtype``)
+    declares, as the trainer keeps them: ``numpy.uint8`` for byte images (byte k stands for float32(k) / float32(255); the frame
+    is handed over as it is, nothing divides on the host), ``numpy.float32`` for everything else and where nothing is declared."""
+    import numpy as np
+    dt = getattr(env_or_space, "observation_dtype", None)
+    if dt is None:
+        space = getattr(env_or_space, "observation_space", env_or_space)
+        dt = getattr(space, "dtype", None)
+    try:
+        return np.dtype(np.uint8) if dt is not None and np.dtype(dt) == np.uint8 else np.dtype(np.float32)
+    except TypeError:
+        return np.dtype(np.float32)
+
+
 class ActionKind:
     """The kind of an action space: ``kind`` is "discrete", "multidiscrete" or "box"; ``shape`` is ``action_space_shape`` for the
     first two and ``(A,)`` for a Box; ``low`` / ``high`` (Box only) are float32 arrays of A bounds."""

@@ -238,6 +238,11 @@ def _probe_env(env_config):
                                   "branches of this MultiDiscrete space: the shared segment carries one action word per environment "
                                   "and the native rollout driver hands over one; set worker_processes: false (in-process "
                                   "environments take MultiDiscrete spaces)")
+    from environments import observation_dtype
+    if observation_dtype(e.observation_space) == np.uint8:      # (a real byte environment; the synthetic one is refused from its config)
+        e.close()
+        raise ValueError("worker_processes: true does not carry uint8 observations: the shared segment types its observation rows as "
+                         "float32; set worker_processes: false (in-process environments keep the bytes)")
     res = tuple(e.observation_space.shape), branches[0], int(e.max_episode_steps)
     e.close()
     return res

@@ -37,6 +37,12 @@ Round 6: the fresh draws of the vector form come from ``libetm_envgen.so`` (csrc
 C with the LCG advanced in 32 AVX-512 (or 8 scalar) lanes -- the SAME floats bit for bit (tests/test_host_logic.py), 9 - 12 us per
 3x84x84 observation instead of 30 - 50, the rows of a step drawn side by side by ``gen_threads`` threads of the library's pool.
 Without the library numpy draws them (identical values).
+
+Byte observations: ``observation_levels: 256`` emits every float draw u as ``np.float32(floor(256 u)) / np.float32(255)`` (256 u is
+exact and floor lands in 0 .. 255), ``observation_dtype: uint8`` (which requires the levels) emits the byte ``floor(256 u)`` itself,
+``observation_space.dtype == np.uint8``.  Both derive from the same float stream, so the two forms are twins from the config alone --
+whatever ``pool``, ``copy_threads`` and ``gen_threads`` are -- and the reward / done streams are those of the plain config.  A ring is
+converted once at construction; fresh draws go into a scratch row (the generators keep producing floats) and are converted from there.
 """
 from types import SimpleNamespace
 
@@ -88,13 +94,42 @@ def _copier(threads):
     return _copiers[threads]
 
 
+BYTE_UNIT = np.arange(256, dtype=np.uint8).astype(np.float32) / np.float32(255)     # the float32 value a byte observation stands for
+
+
+def _observation_form(observation_levels, observation_dtype):
+    """Validate the two keys -> None (plain float draws), "levels" (float32 on the 256 byte levels) or "uint8" (the bytes)."""
+    if observation_levels is not None and (isinstance(observation_levels, bool) or observation_levels != 256):
+        raise ValueError(f"observation_levels must be 256 (or absent), got {observation_levels!r}")
+    if observation_dtype not in (None, "float32", "uint8"):
+        raise ValueError(f"observation_dtype must be 'uint8' or 'float32' (or absent), got {observation_dtype!r}")
+    if observation_dtype == "uint8":
+        if observation_levels is None:
+            raise ValueError("observation_dtype: uint8 requires observation_levels: 256")
+        return "uint8"
+    return "levels" if observation_levels is not None else None
+
+
+def _quantize(u, form, out=None):
+    """Float draws u in [0, 1) -> their emitted form: the byte floor(256 u) ("uint8") or float32(byte) / float32(255) ("levels")."""
+    b = (u * np.float32(256)).astype(np.uint8)          # 256 u is exact; the cast truncates = floor, into 0 .. 255
+    if form == "uint8":
+        if out is None:
+            return b
+        out[...] = b
+        return out
+    return np.take(BYTE_UNIT, b, out=out)
+
+
 class _WorkerStream:
     """Per-worker RNG state: frame ring + chunked (reward, done) uniforms."""
 
-    def __init__(self, worker_id, obs_shape, seed, pool):
+    def __init__(self, worker_id, obs_shape, seed, pool, form=None):
         self.rng = np.random.default_rng(seed + worker_id)
         if pool > 0:
             self.frames = self.rng.random((pool,) + tuple(obs_shape), dtype=np.float32)
+            if form is not None:        # the ring in its emitted form, once
+                self.frames = _quantize(self.frames, form)
             self.rng_obs = None
         else:                       # fresh draws: observations from default_rng(seed + worker_id), uniforms from a second stream
             self.frames = None
@@ -138,13 +173,16 @@ class SyntheticEnv:
     """Single env, reference env API.  ``worker_id`` selects the RNG stream."""
 
     def __init__(self, obs_shape=(3, 84, 84), num_actions=3, max_episode_steps=96, seed=0, worker_id=0,
-                 p_reward=0.05, p_done=0.02, pool=64, continuous_actions=None, action_low=-1.0, action_high=1.0):
+                 p_reward=0.05, p_done=0.02, pool=64, continuous_actions=None, action_low=-1.0, action_high=1.0,
+                 observation_levels=None, observation_dtype=None):
+        self._form = _observation_form(observation_levels, observation_dtype)
+        self._dtype = np.dtype(np.uint8 if self._form == "uint8" else np.float32)
         self._shape = tuple(obs_shape)
         self._branches, self._nvec = _branches(num_actions)
         self._box = _box_space(continuous_actions, action_low, action_high)
         self._T = int(max_episode_steps)
         self._p_r, self._p_d = float(p_reward), float(p_done)
-        self._s = _WorkerStream(worker_id, self._shape, seed, pool)
+        self._s = _WorkerStream(worker_id, self._shape, seed, pool, self._form)
         self._pool = pool
         self._cursor = 0
         self._t = 0
@@ -152,6 +190,8 @@ class SyntheticEnv:
 
     @property
     def observation_space(self):
+        if self._form == "uint8":
+            return SimpleNamespace(shape=self._shape, low=0, high=255, dtype=np.uint8)
         return SimpleNamespace(shape=self._shape, low=0.0, high=1.0, dtype=np.float32)
 
     @property
@@ -168,7 +208,8 @@ class SyntheticEnv:
 
     def _emit(self):
         if self._pool == 0:
-            return self._s.rng_obs.random(self._shape, dtype=np.float32)
+            u = self._s.rng_obs.random(self._shape, dtype=np.float32)
+            return u if self._form is None else _quantize(u, self._form)
         frame = self._s.frames[self._cursor % self._pool]
         self._cursor += 1
         return frame
@@ -186,7 +227,7 @@ class SyntheticEnv:
         done = bool(self._t >= self._T or u_d < self._p_d)
         if done:
             # terminal observation is never consumed by the trainer (it resets immediately): no frame is spent
-            return np.zeros(self._shape, dtype=np.float32), reward, True, {"reward": self._ret, "length": self._t}
+            return np.zeros(self._shape, dtype=self._dtype), reward, True, {"reward": self._ret, "length": self._t}
         return self._emit(), reward, False, None
 
     def close(self):
@@ -198,11 +239,13 @@ class SyntheticVecEnv:
 
     def __init__(self, num_envs, obs_shape=(3, 84, 84), num_actions=3, max_episode_steps=96, seed=0,
                  p_reward=0.05, p_done=0.02, pool=64, first_worker_id=0, copy_threads=1, row_chunks=None, step_cost_us=0.0, min_chunked_envs=None,
-                 gen_threads=1, continuous_actions=None, action_low=-1.0, action_high=1.0):
+                 gen_threads=1, continuous_actions=None, action_low=-1.0, action_high=1.0, observation_levels=None, observation_dtype=None):
         """``copy_threads`` > 1: the observation rows of a step are written by that many threads (the kernel library's host
         copier; the reference's workers write theirs in n_workers processes) instead of one numpy copy.  ``pool`` = 0: every row is a
         fresh draw of its worker's generator (module docstring); ``gen_threads`` > 1: drawn by that many threads."""
         self.num_envs = int(num_envs)
+        self._form = _observation_form(observation_levels, observation_dtype)
+        self.observation_dtype = np.dtype(np.uint8 if self._form == "uint8" else np.float32)
         # step_cost_us: a simulated simulator -- every environment of this front-end burns that much CPU time per step, one after
         # the other (what stepping real Python environments in one process costs; worker processes run them side by side)
         self._step_cost_s = float(step_cost_us) * 1e-6
@@ -211,7 +254,9 @@ class SyntheticVecEnv:
             self.ROW_CHUNKS = int(row_chunks)          # instance override of the on_rows granularity
         if min_chunked_envs is not None:
             self.MIN_CHUNKED_ENVS = int(min_chunked_envs)
-        self._row_bytes = int(np.prod(obs_shape)) * 4
+        self._row_elems = int(np.prod(obs_shape))
+        self._row_bytes = self._row_elems * self.observation_dtype.itemsize      # of an emitted row
+        self._scratch = None      # pool 0 with a quantised form: the float draws of a step's rows, converted from here
         self.observation_space_shape = tuple(obs_shape)
         self.action_space_shape, nvec = _branches(num_actions)     # (actions do not drive the dynamics)
         self.num_actions = sum(self.action_space_shape)
@@ -227,7 +272,7 @@ class SyntheticVecEnv:
         self.max_episode_steps = int(max_episode_steps)
         self._p_r, self._p_d = float(p_reward), float(p_done)
         self._pool = pool
-        streams = [_WorkerStream(first_worker_id + w, obs_shape, seed, pool) for w in range(self.num_envs)]
+        streams = [_WorkerStream(first_worker_id + w, obs_shape, seed, pool, self._form) for w in range(self.num_envs)]
         self._rngs = [s.rng for s in streams]
         # [pool, W, *obs]: all cursors advance in lock-step, so the observations of one step are ONE contiguous block
         # (a single memcpy per step / per row chunk instead of W strided ones)
@@ -270,17 +315,22 @@ class SyntheticVecEnv:
     def _emit_fresh(self, out, on_rows):
         """pool = 0: every row of the step is drawn now, by its worker's own generator, into the output row."""
         if out is None:
-            out = np.empty((self.num_envs,) + self.observation_space_shape, dtype=np.float32)
-        if not (out.flags.c_contiguous and out.dtype == np.float32):
-            raise ValueError("fresh observations are drawn in place: a C-contiguous float32 output buffer is needed")
+            out = np.empty((self.num_envs,) + self.observation_space_shape, dtype=self.observation_dtype)
+        if not (out.flags.c_contiguous and out.dtype == self.observation_dtype):
+            raise ValueError(f"fresh observations are drawn in place: a C-contiguous {self.observation_dtype} output buffer is needed")
+        dst = out
+        if self._form is not None:      # the generators produce the floats into a scratch array; the emitted form is made from it
+            if self._scratch is None:
+                self._scratch = np.empty((self.num_envs,) + self.observation_space_shape, dtype=np.float32)
+            out = self._scratch
         chunks = (self.ROW_CHUNKS if self.num_envs >= self.MIN_CHUNKED_ENVS else 1) if on_rows is not None else 1
         step = max(1, -(-self.num_envs // chunks))
-        row_floats = self._row_bytes // 4
+        row_floats = self._row_elems
         for lo in range(0, self.num_envs, step):
             hi = min(lo + step, self.num_envs)
             if self._native is not None:
                 if self._native.etm_pcg64_fill_rows_f32(self._native_pool, self._obs_states[lo:].ctypes.data,
-                                                        out.ctypes.data + lo * self._row_bytes, row_floats, hi - lo) != 0:
+                                                        out.ctypes.data + lo * row_floats * 4, row_floats, hi - lo) != 0:
                     raise RuntimeError("etm_pcg64_fill_rows_f32 failed")
             elif self._gen_pool is not None and hi - lo > 1:
                 k = min(self._gen_threads, hi - lo)
@@ -291,9 +341,11 @@ class SyntheticVecEnv:
                     f.result()
             else:
                 self._draw_rows(out, lo, hi)
+            if self._form is not None:
+                _quantize(out[lo:hi], self._form, out=dst[lo:hi])
             if on_rows is not None:
                 on_rows(lo, hi)
-        return out
+        return dst
 
     def _emit(self, out, on_rows=None):
         if self._pool == 0:
@@ -307,7 +359,7 @@ class SyntheticVecEnv:
             return out
         chunks = self.ROW_CHUNKS if self.num_envs >= self.MIN_CHUNKED_ENVS else 1
         step = max(1, -(-self.num_envs // chunks))
-        if self._copy_threads > 1 and out.flags.c_contiguous and out.dtype == np.float32:
+        if self._copy_threads > 1 and out.flags.c_contiguous and out.dtype == frame.dtype:
             lib, handle = _copier(self._copy_threads)
             dst, src = out.ctypes.data, frame.ctypes.data
             for lo in range(0, self.num_envs, step):

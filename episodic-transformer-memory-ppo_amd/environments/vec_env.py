@@ -2,6 +2,9 @@
 
 ``VecEnv`` protocol (what ``PPOTrainer`` steps):
     num_envs, observation_space_shape, action_space_shape, num_actions, max_episode_steps
+    observation_dtype (optional; absent = float32): numpy.uint8 for byte image observations -- ``out`` and the returned rows
+        are then uint8 and byte k stands for float32(k) / float32(255) (environments.observation_dtype reads it, or else
+        ``observation_space.dtype``)
         action_space_shape: one entry per action branch (environments.action_space_shape: ``nvec`` of a MultiDiscrete space,
         ``(n,)`` of a Discrete one, ``(A,)`` of a Box); num_actions: n of a Discrete space, the sum of ``nvec`` (the policy's
         logits), A of a Box
@@ -20,14 +23,14 @@ is exactly what upstream's loop does by hand (trainer.py:195-201).
 """
 import numpy as np
 
-from environments import action_space_kind
+from environments import action_space_kind, observation_dtype
 
 
 class _VecBase:
     ROW_CHUNKS = 2   # on_rows granularity: W / ROW_CHUNKS workers per notification (each notification costs the trainer ~9 us)
 
     def _alloc(self, out):
-        return out if out is not None else np.zeros((self.num_envs,) + self.observation_space_shape, dtype=np.float32)
+        return out if out is not None else np.zeros((self.num_envs,) + self.observation_space_shape, dtype=getattr(self, "observation_dtype", np.float32))
 
     def _notify(self, on_rows, done_upto, sent_upto):
         """Call on_rows for the complete chunks in [sent_upto, done_upto); returns the new sent_upto."""
@@ -47,6 +50,7 @@ class SerialVecEnv(_VecBase):
         self.num_envs = len(self.envs)
         e = self.envs[0]
         self.observation_space_shape = tuple(e.observation_space.shape)
+        self.observation_dtype = observation_dtype(e.observation_space)
         self.action_kind = action_space_kind(e.action_space)
         self.action_space_shape = self.action_kind.shape
         self.num_actions = sum(self.action_space_shape)
@@ -88,6 +92,7 @@ class PipeVecEnv(_VecBase):
         from worker import Worker
         probe = create_env(env_config)
         self.observation_space_shape = tuple(probe.observation_space.shape)
+        self.observation_dtype = observation_dtype(probe.observation_space)
         self.action_kind = action_space_kind(probe.action_space)
         self.action_space_shape = self.action_kind.shape
         self.num_actions = sum(self.action_space_shape)
@@ -153,6 +158,7 @@ class CompositeVecEnv(_VecBase):
         self.num_envs = lo
         e = self.parts[0]
         self.observation_space_shape = tuple(e.observation_space_shape)
+        self.observation_dtype = observation_dtype(e)
         self.action_space_shape = tuple(getattr(e, "action_space_shape", None) or (int(e.num_actions),))
         self.action_kind = getattr(e, "action_kind", None) or (action_space_kind(e.action_space) if hasattr(e, "action_space") else None)
         self.num_actions = int(e.num_actions)
@@ -190,7 +196,7 @@ def make_vec_env(env_config: dict, num_envs: int, first_worker_id: int = 0, grou
     if env_config["type"] == "Synthetic":
         from environments.synthetic import SyntheticVecEnv
         keys = ("obs_shape", "num_actions", "max_episode_steps", "seed", "p_reward", "p_done", "pool", "copy_threads", "row_chunks", "step_cost_us", "gen_threads",
-                "continuous_actions", "action_low", "action_high")
+                "continuous_actions", "action_low", "action_high", "observation_levels", "observation_dtype")
         kw = {k: env_config[k] for k in keys if k in env_config}
         if "obs_shape" in kw:
             kw["obs_shape"] = tuple(kw["obs_shape"])

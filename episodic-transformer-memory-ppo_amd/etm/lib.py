@@ -7,7 +7,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: torch ships its ow
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libetm_hip.so")     # (diagnostic tools that load another build assign this before load())
-ABI_VERSION = 50
+ABI_VERSION = 51
 
 _lib = None
 
@@ -134,6 +134,10 @@ SIGNATURES = {
     "etm_conv_b3_dgrad": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "etm_conv_b3_wgrad_slices": (_I, [_I] * 8),
     "etm_conv_b3_wgrad": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "etm_bytes_to_unit": (_I, [_P, _P, _P, _L, _L, _P]),
+    "etm_conv_relu_u8": (_I, [_P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "etm_conv_b3_fwd_u8": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "etm_conv_b3_wgrad_u8": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "etm_grouped_dw_supported": (_I, [_I, _I, _I, _I, _I, _I]),
     "etm_grouped_dw_max_problems": (_I, []),
     "etm_grouped_dw": (_I, [_P, _P, _P, _P, _I, _I, _P]),

@@ -35,6 +35,45 @@ def _f32c(t, name):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _obs_c(t, name):
+    """An observation operand: float32, or uint8 where byte k stands for float32(k) / float32(255) (``bytes_to_unit``)."""
+    if t is not None and t.dtype == torch.uint8:
+        return t if t.is_contiguous() else t.contiguous()
+    return _f32c(t, name)
+
+
+def byte_unit_table():
+    """The 256 fp32 values a byte observation stands for: ``np.float32(k) / np.float32(255)``, correctly rounded (numpy, host).
+    The kernels form the same values from the byte (etm_byte_unit, csrc/etm_common.h); k * (1 / 255) is NOT this value."""
+    import numpy as np
+    return np.arange(256, dtype=np.uint8).astype(np.float32) / np.float32(255)
+
+
+def bytes_to_unit(x, index=None, out=None):
+    """uint8 device tensor [R, ...] -> float32 of the same shape with every byte k as float32(k) / 255 (etm_bytes_to_unit); with
+    ``index`` (int64 device tensor [n]) the rows x[index] -> [n, ...].  The fallback in front of every float kernel that has no
+    byte form.  Any row length, any storage offset of ``x``."""
+    lib = _lib.load()
+    _need_dev(x, index, out)
+    if x.dtype != torch.uint8:
+        raise TypeError(f"bytes_to_unit needs uint8, got {x.dtype}")
+    if index is not None and index.dtype != torch.int64:
+        raise TypeError("bytes_to_unit: index must be int64")
+    if x.dim() == 0 or x.numel() == 0:
+        raise ValueError("bytes_to_unit needs a non-empty tensor of at least one dimension")
+    x = x if x.is_contiguous() else x.contiguous()
+    rows = x.shape[0] if index is None else index.numel()
+    row_bytes = x[0].numel()
+    shape = (rows,) + tuple(x.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise TypeError("bytes_to_unit: out must be a contiguous float32 tensor of the result's shape")
+    if rows:
+        _lib.check(lib.etm_bytes_to_unit(_ptr(x), _ptr(index), _ptr(out), rows, row_bytes, _stream()), "etm_bytes_to_unit")
+    return out
+
+
 _frozen = set()
 _retired = []
 
@@ -1327,15 +1366,25 @@ def conv_relu(x, weight2d, bias, C, H, W, KH, KW, S, in_nhwc, out_nchw, index=No
     """relu(conv2d(x) + bias) on the no-grad path (see etm_conv_relu).  ``weight2d``: ``conv_pack_weights`` of the [Cout, K]
     weights in the K order that matches the input layout.  With ``index`` (int64 device scalar) ``x`` is a stack [S, N, ...]
     and the layer reads x[index] -- the row is chosen on the device, so a captured graph can walk a staging array; ``rows =
-    (lo, hi)`` restricts it to images lo..hi-1 of that row (a worker group).
+    (lo, hi)`` restricts it to images lo..hi-1 of that row (a worker group).  ``x`` may be uint8 (byte k = float32(k) / 255): the NCHW
+    first layer then reads the bytes itself (etm_conv_relu_u8), any other layer gets them expanded first (``bytes_to_unit``).
     Returns NHWC [N,Ho,Wo,Cout] or NCHW [N,Cout,Ho,Wo]."""
     lib = _lib.load()
     _need_dev(x, weight2d, bias, index)
-    x = _f32c(x, "x")
+    x = _obs_c(x, "x")
+    u8 = x.dtype == torch.uint8
+    if index is not None and (index.dtype != torch.int64 or index.numel() != 1):
+        raise TypeError("conv_relu: index must be an int64 device scalar")
+    if u8 and (in_nhwc or weight2d.shape[0] != 32 or W % 4 or S % 4 or KW % 8 or x.data_ptr() % 4 or (C * H * W) % 4):
+        # no byte form of this layer: the (selected row of the) input as floats, then the float kernel
+        x = bytes_to_unit(x, index=None if index is None else index.reshape(1))
+        if index is not None:
+            x = x[0, rows[0]:rows[1]] if rows is not None else x[0]
+            index = rows = None
+        u8 = False
+    esize = 1 if u8 else 4
     stride = 0
     if index is not None:
-        if index.dtype != torch.int64 or index.numel() != 1:
-            raise TypeError("conv_relu: index must be an int64 device scalar")
         stride = x[0].numel()
         N = x.shape[1]
     else:
@@ -1345,15 +1394,16 @@ def conv_relu(x, weight2d, bias, C, H, W, KH, KW, S, in_nhwc, out_nchw, index=No
         if index is None:
             raise TypeError("conv_relu: rows needs index (stacked input)")
         lo, hi = rows
-        base += lo * x[0, 0].numel() * 4
+        base += lo * x[0, 0].numel() * esize
         N = hi - lo
     Cout = weight2d.shape[0]
     Ho, Wo = (H - KH) // S + 1, (W - KW) // S + 1
     shape = (N, Cout, Ho, Wo) if out_nchw else (N, Ho, Wo, Cout)
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    rc = lib.etm_conv_relu(base, _ptr(index), stride, _ptr(weight2d), _ptr(bias), _ptr(out), N, C, H, W, Cout, KH, KW, S,
-                           1 if in_nhwc else 0, 1 if out_nchw else 0, _stream())
-    _lib.check(rc, "etm_conv_relu")
+    entry, what = (lib.etm_conv_relu_u8, "etm_conv_relu_u8") if u8 else (lib.etm_conv_relu, "etm_conv_relu")
+    rc = entry(base, _ptr(index), stride, _ptr(weight2d), _ptr(bias), _ptr(out), N, C, H, W, Cout, KH, KW, S,
+               1 if in_nhwc else 0, 1 if out_nchw else 0, _stream())
+    _lib.check(rc, what)
     return out
 
 
@@ -1451,10 +1501,19 @@ class _EncoderFn(torch.autograd.Function):
     def forward(ctx, x_nhwc, w1, b1, w2, b2, w3, b3, strides, index=None, products=None):
         lib = _lib.load()
         _need_dev(x_nhwc, w1, b1, w2, b2, w3, b3)
-        x = _f32c(x_nhwc, "obs")
+        x = _obs_c(x_nhwc, "obs")
         st = _stream()
-        acts, shapes = [x], []
         n, h, w, c = x.shape
+        u8 = x.dtype == torch.uint8
+        if u8 and not (_encoder_uses_b3(h, w, [w1, w2, w3], strides, products) and x.data_ptr() % 16 == 0):
+            # no byte form of this first layer (fp32 products, another geometry): the batch's images as floats, then the float kernels.
+            # The byte tensor is what backward keeps; it expands them again.
+            ctx.u8_fallback = (x, index)
+            x, index, u8 = bytes_to_unit(x, index=index), None, False
+            n = x.shape[0]
+        else:
+            ctx.u8_fallback = None
+        acts, shapes = [x], []
         x_images = n
         if index is not None:          # batch image i = x[index[i]]: the minibatch gather rides in the first layer's loads
             n = index.numel()
@@ -1481,8 +1540,9 @@ class _EncoderFn(torch.autograd.Function):
             if use_b3:
                 bits = torch.empty((n, ho, wo, cout // 32), dtype=torch.int32, device=x.device)
                 relu_bits.append(bits)
-                _lib.check(lib.etm_conv_b3_fwd(_ptr(acts[-1]), _ptr(index) if i == 0 else None, _ptr(packs[i]), _ptr(_f32c(bs.detach(), "bias")),
-                                               _ptr(y), _ptr(bits), n, c, h, w, cout, kh, kw, s, st), "etm_conv_b3_fwd")
+                fwd, what = (lib.etm_conv_b3_fwd_u8, "etm_conv_b3_fwd_u8") if (u8 and i == 0) else (lib.etm_conv_b3_fwd, "etm_conv_b3_fwd")
+                _lib.check(fwd(_ptr(acts[-1]), _ptr(index) if i == 0 else None, _ptr(packs[i]), _ptr(_f32c(bs.detach(), "bias")),
+                               _ptr(y), _ptr(bits), n, c, h, w, cout, kh, kw, s, st), what)
             else:
                 _lib.check(lib.etm_conv_train_fwd(_ptr(acts[-1]), _ptr(index) if i == 0 else None, x_images, _ptr(packs[i]),
                                                   _ptr(_f32c(bs.detach(), "bias")), _ptr(y), n, c, h, w, cout, kh, kw, s, 0, st), "etm_conv_train_fwd")
@@ -1491,6 +1551,9 @@ class _EncoderFn(torch.autograd.Function):
             h, w, c = ho, wo, cout
         ctx.param_ptrs = tuple(t.data_ptr() for t in (w1, b1, w2, b2, w3, b3))
         ctx.shapes = shapes
+        if ctx.u8_fallback is not None:
+            acts[0], index = ctx.u8_fallback      # (the expanded copy is not kept alive between the passes)
+            ctx.u8_fallback = True
         ctx.save_for_backward(acts[0], acts[1], acts[2], acts[3], dgrad_packs[1], dgrad_packs[2], index,
                               *(relu_bits if use_b3 else (None, None, None)))
         return acts[3].view(n, -1)
@@ -1502,6 +1565,9 @@ class _EncoderFn(torch.autograd.Function):
         st = _stream()
         dev = x0.device
         n = y1.shape[0]
+        if ctx.u8_fallback:
+            x0, index = bytes_to_unit(x0, index=index), None
+        u8 = x0.dtype == torch.uint8
         g = _f32c(g, "d_features")
         c3, h3, w3_, cout3, _, _, _, ho3, wo3 = ctx.shapes[2]
         if ctx.b3:      # the last layer's ReLU backward rides in the fills of its two consumers (pattern words of y3 from the forward pass)
@@ -1531,8 +1597,9 @@ class _EncoderFn(torch.autograd.Function):
                 ws = workspace(nbytes, dev, "conv_wgrad")
                 buf = torch.empty(K * cout + cout, dtype=torch.float32, device=dev)
             if ctx.b3:      # the slices on the bf16 matrix pipe (csrc/conv_b3_wgrad.hip); without a collector their reduction follows at once
-                _lib.check(lib.etm_conv_b3_wgrad(_ptr(inputs[i]), _ptr(index) if i == 0 else None, _ptr(dy), _ptr(dy_bits), _ptr(ws), nbytes, n, c, h, w,
-                                                 cout, kh, kw, s, st), "etm_conv_b3_wgrad")
+                wgrad, what = (lib.etm_conv_b3_wgrad_u8, "etm_conv_b3_wgrad_u8") if (u8 and i == 0) else (lib.etm_conv_b3_wgrad, "etm_conv_b3_wgrad")
+                _lib.check(wgrad(_ptr(inputs[i]), _ptr(index) if i == 0 else None, _ptr(dy), _ptr(dy_bits), _ptr(ws), nbytes, n, c, h, w,
+                                 cout, kh, kw, s, st), what)
                 if buf is not None:
                     _conv_wgrad_reduce([(ws, slices, buf, buf[K * cout:], cout, c, kh, kw)])
             else:
@@ -1557,7 +1624,9 @@ def encoder_train(obs_nhwc, conv1, conv2, conv3, index=None, products=None):
     """Differentiable encoder forward on an NHWC observation batch [N, H, W, C] -- or, with ``index`` (int64 [n]), on the images
     ``obs_nhwc[index]`` without gathering them first: features [N, Ho * Wo * Cout], NHWC-flattened
     (``linear_relu_nhwc`` is the following linear layer on that column order).  Gradients flow to the
-    convolution weights and biases (observations need none)."""
+    convolution weights and biases (observations need none).  ``obs_nhwc`` may be uint8 (byte k = float32(k) / 255): on the bf16
+    matrix pipe the first layer's forward and weight-gradient kernels read the bytes; with fp32 products or another geometry the
+    images are expanded (``bytes_to_unit``) in front of the float kernels, in both passes."""
     if products not in (None, "bf16x3", "fp32"):
         raise ValueError(f"products must be 'bf16x3' or 'fp32', got {products!r}")
     return _EncoderFn.apply(obs_nhwc, conv1.weight, conv1.bias, conv2.weight, conv2.bias, conv3.weight, conv3.bias,
@@ -1602,13 +1671,13 @@ class ReplayAfterWarmup:
 
 
 def host_view(t):
-    """numpy array over the memory of the contiguous float32 device tensor ``t`` at its HOST address (large-BAR systems map the
-    device's memory into the process: the pointer is the same) -- WRITE-ONLY use: host reads through the BAR are uncached and
-    slow, and the device's caches know nothing of them.  Call ``host_direct_write_ok`` first."""
+    """numpy array over the memory of the contiguous float32 (or uint8: byte observation rows) device tensor ``t`` at its HOST
+    address (large-BAR systems map the device's memory into the process: the pointer is the same) -- WRITE-ONLY use: host reads
+    through the BAR are uncached and slow, and the device's caches know nothing of them.  Call ``host_direct_write_ok`` first."""
     import numpy as np
-    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise TypeError("host_view: a contiguous float32 device tensor is needed")
-    buf = (ctypes.c_float * t.numel()).from_address(t.data_ptr())
+    if not (t.is_cuda and t.dtype in (torch.float32, torch.uint8) and t.is_contiguous()):
+        raise TypeError("host_view: a contiguous float32 or uint8 device tensor is needed")
+    buf = ((ctypes.c_float if t.dtype == torch.float32 else ctypes.c_uint8) * t.numel()).from_address(t.data_ptr())
     return np.ctypeslib.as_array(buf).reshape(tuple(t.shape))
 
 

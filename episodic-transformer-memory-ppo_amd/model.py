@@ -346,7 +346,19 @@ class ActorCriticModel(nn.Module):
     def _encode(self, obs, obs_index=None, obs_rows=None):
         """Observation encoder.  ``obs_index`` (int64 device scalar, fused rollout encoder only): ``obs`` is a time-major
         stack [S, N, C, H, W] and row obs[obs_index] is encoded (the row is selected on the device).  ``obs`` may be an
-        ``IndexedObservations(bank_nhwc, index)``: the minibatch = bank_nhwc[index], gathered inside the first encoder layer."""
+        ``IndexedObservations(bank_nhwc, index)``: the minibatch = bank_nhwc[index], gathered inside the first encoder layer.
+        Visual observations may be uint8 on every entry: byte k stands for float32(k) / float32(255).  On the device the first
+        layer's kernels read the bytes where they have a byte form (ops.conv_relu, ops.encoder_train) and ``ops.bytes_to_unit``
+        expands them elsewhere; on the CPU it is ``obs.to(torch.float32) / 255``."""
+        raw = obs.bank if isinstance(obs, IndexedObservations) else obs
+        if raw.dtype == torch.uint8:
+            if not self.visual:
+                raise ValueError("uint8 observations are images (byte k = k / 255); a vector observation must be float32")
+            if not raw.is_cuda:      # (IEEE division: the correctly rounded quotient)
+                if isinstance(obs, IndexedObservations):
+                    obs = IndexedObservations(obs.bank.index_select(0, obs.index).to(torch.float32) / 255, torch.arange(obs.index.numel()))
+                else:
+                    obs = obs.to(torch.float32) / 255
         if isinstance(obs, IndexedObservations):
             if self.visual and self.train_encoder and torch.is_grad_enabled():
                 if self._train_encoder_ok is None:
@@ -358,7 +370,10 @@ class ActorCriticModel(nn.Module):
                     if getattr(self, "_keep_encoder_features", False):      # data-parallel overlap: the backward pass is cut here
                         self._encoder_features = feats                      # (trainer._train_body_a1; released by _train_body_a2)
                     return ops.linear_relu_nhwc(feats, self.lin_hidden.weight, self.lin_hidden.bias, self.conv3.out_channels)
-            obs = obs.bank.index_select(0, obs.index).permute(0, 3, 1, 2)      # NCHW view of the gathered NHWC rows
+            if obs.bank.dtype == torch.uint8:      # (device: the gather rides in the expansion)
+                obs = ops.bytes_to_unit(obs.bank, index=obs.index).permute(0, 3, 1, 2)
+            else:
+                obs = obs.bank.index_select(0, obs.index).permute(0, 3, 1, 2)      # NCHW view of the gathered NHWC rows
         if obs_index is not None:
             if not self._fused_encoder_ok(obs[0]):
                 raise RuntimeError("obs_index needs the fused rollout encoder (visual observations, no grad)")
@@ -376,6 +391,9 @@ class ActorCriticModel(nn.Module):
                 feats = ops.encoder_train(obs.permute(0, 2, 3, 1), self.conv1, self.conv2, self.conv3, products=self.encoder_products)      # (h, w, c) flatten order
                 return ops.linear_relu_nhwc(feats, self.lin_hidden.weight, self.lin_hidden.bias, self.conv3.out_channels)
         if self.visual:
+            if h.dtype == torch.uint8:      # library convolutions: the floats first (in the memory order the bytes have)
+                nhwc = h.permute(0, 2, 3, 1)
+                h = ops.bytes_to_unit(nhwc).permute(0, 3, 1, 2) if nhwc.is_contiguous() else ops.bytes_to_unit(h)
             if self.channels_last and h.is_cuda:
                 # NHWC activations: MIOpen's implicit-GEMM kernels run without layout transposes (1.35 vs 2.1 ms for
                 # forward+backward of the three convolutions at N = 2048); weights, logical shapes and state_dict are unchanged

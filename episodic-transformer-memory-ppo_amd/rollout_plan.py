@@ -90,7 +90,7 @@ class WorkerGroup:
         self.ss_latch = torch.zeros((2, Wg), dtype=torch.int64, device=dev)
         self.step_l, self.slot_l = self.ss_latch[0], self.ss_latch[1]
         # observation rows: pinned source of the group's rows, its rows of staging row 0, bytes per row / per staging row
-        self._upload, self.row_bytes = upload, tr._obs_pin[0].numel() * 4
+        self._upload, self.row_bytes = upload, tr._obs_pin[0].numel() * tr._obs_pin.element_size()      # (float32 or uint8 rows)
         self.rows_src = tr._obs_pin.data_ptr() + lo * self.row_bytes
         self.stage0 = tr._stage["obs"].data_ptr() + lo * self.row_bytes
         self._stage_pitch = tr.num_workers * self.row_bytes

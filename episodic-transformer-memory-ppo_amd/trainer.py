@@ -122,6 +122,14 @@ def check_box_policy(config: dict, A=None):
     return A
 
 
+def check_byte_observation_transport(config, env=None):
+    """``worker_processes: true`` with ``observation_dtype: uint8`` is refused, before any environment or process is created: the
+    workers' shared segment types its observation rows as float32 (environments/shm_env.py)."""
+    if env is None and config.get("worker_processes", False) and str(config["environment"].get("observation_dtype", "float32")) == "uint8":
+        raise ValueError("worker_processes: true does not carry uint8 observations (the shared segment's rows are float32): "
+                         "set worker_processes: false (in-process environments keep the bytes), or let the environment emit float32")
+
+
 def time_major(table, src):
     """The host table ``src`` [W, S(, B)] in the layout and type of the fixed-address device table ``table`` [S, W(, B)]."""
     x = torch.as_tensor(np.asarray(src), dtype=table.dtype)
@@ -154,6 +162,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         self.memory_length, self.num_blocks, self.embed_dim = t["memory_length"], t["num_blocks"], t["embed_dim"]
         check_kernel_shapes(t)
         check_box_policy(config)
+        check_byte_observation_transport(config, env)
         self.writer = _make_writer(run_id) if tensorboard else _NullWriter()
 
         # environments (batched front-end over the upstream per-worker protocol)
@@ -212,6 +221,13 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         W = self.num_workers
         obs_shape = tuple(self.env.observation_space_shape)
         self.observation_space = type("Space", (), {"shape": obs_shape})()
+        # uint8 image observations stay bytes from the environment's row to the first encoder layer's loads (byte k stands for
+        # float32(k) / float32(255)): the environment says so (``observation_dtype``, or else ``observation_space.dtype``)
+        from environments import observation_dtype as _observation_dtype
+        self.observation_dtype = torch.uint8 if _observation_dtype(self.env) == np.uint8 else torch.float32
+        if self.observation_dtype == torch.uint8:
+            if len(obs_shape) < 2:
+                raise ValueError("uint8 observations are images (byte k = k / 255); a vector observation must be float32")
         # one branch per action dimension, from the environment (environments.action_space_shape: Discrete(n) -> (n,), MultiDiscrete
         # -> nvec); Discrete is upstream's single branch (trainer.py:47)
         self.action_space_shape = tuple(int(a) for a in getattr(self.env, "action_space_shape", None) or (self.env.num_actions,))
@@ -245,7 +261,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         box = self.box is not None
         # entries per worker of the action tables: one per branch, or the A dimensions of a Box
         self._action_width = self.action_space_shape[0] if box else len(self.action_space_shape)
-        self.buffer = Buffer(config, self.observation_space, self.action_space_shape, self.max_episode_length, device, continuous=box)
+        self.buffer = Buffer(config, self.observation_space, self.action_space_shape, self.max_episode_length, device, continuous=box,
+                             observation_dtype=self.observation_dtype)
         self.model = ActorCriticModel(config, self.observation_space, self.action_space_shape, self.max_episode_length,
                                       continuous=box).to(device)
         self.model.train()
@@ -286,7 +303,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             self._obs_pin = torch.from_numpy(self._shm_env.v["obs"])
             self._act_pin = torch.from_numpy(self._shm_env.v["act"])
         else:
-            self._obs_pin = torch.zeros((W,) + obs_shape, dtype=torch.float32).pin_memory()
+            self._obs_pin = torch.zeros((W,) + obs_shape, dtype=self.observation_dtype).pin_memory()
             self._act_pin = torch.zeros((W, self._action_width), dtype=torch.float32 if box else torch.int64).pin_memory()
         self.obs = self._obs_pin.numpy()
         # (episode step, episode slot) of every worker: one pinned [2, W] block, uploaded with ONE copy per rollout step
@@ -302,9 +319,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
 
         # fixed-address operands of the rollout step (HIP-graph friendly) and time-major staging of the step outputs
         S, L, B = config["worker_steps"], self.memory_length, self._action_width
-        self._obs_dev = torch.zeros((W,) + obs_shape, dtype=torch.float32, device=device)
+        self._obs_dev = torch.zeros((W,) + obs_shape, dtype=self.observation_dtype, device=device)
         self._stage = {
-            "obs": torch.zeros((S, W) + obs_shape, dtype=torch.float32, device=device),
+            "obs": torch.zeros((S, W) + obs_shape, dtype=self.observation_dtype, device=device),
             "memory_mask": torch.zeros((S, W, L), dtype=torch.bool, device=device),
             "memory_indices": torch.zeros((S, W, L), dtype=torch.int64, device=device),
             "actions": torch.zeros((S, W, B), dtype=torch.float32 if box else torch.int64, device=device),
@@ -1115,7 +1132,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             return None
         n, c, h, w = obs.shape
         if getattr(self, "_obs_nhwc_buf", None) is None or self._obs_nhwc_buf.shape != (n, h, w, c):
-            self._obs_nhwc_buf = torch.empty((n, h, w, c), dtype=torch.float32, device=self.device)
+            self._obs_nhwc_buf = torch.empty((n, h, w, c), dtype=obs.dtype, device=self.device)
         self._obs_nhwc_buf.copy_(obs.permute(0, 2, 3, 1))
         return self._obs_nhwc_buf
 

@@ -15,7 +15,7 @@ def create_env(config: dict, render: bool = False, worker_id: int = 0):
     if kind == "Synthetic":
         from environments.synthetic import SyntheticEnv
         keys = ("obs_shape", "num_actions", "max_episode_steps", "seed", "p_reward", "p_done", "pool", "continuous_actions", "action_low",
-                "action_high")
+                "action_high", "observation_levels", "observation_dtype")
         kw = {k: config[k] for k in keys if k in config}
         if "obs_shape" in kw:
             kw["obs_shape"] = tuple(kw["obs_shape"])

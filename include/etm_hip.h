@@ -734,6 +734,30 @@ int etm_conv_b3_wgrad_slices(int N, int C, int H, int W, int Cout, int KH, int K
 int etm_conv_b3_wgrad(const float *x, const int64_t *x_index, const float *dy, const uint32_t *dy_relu_bits, float *workspace,
                       int64_t workspace_bytes, int N, int C, int H, int W, int Cout, int KH, int KW, int S, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * uint8 image observations (byte observations).  A byte k stands for the fp32 value float(k) / 255.f, CORRECTLY ROUNDED -- what
+ * `obs.astype(np.float32) / 255.` of an image wrapper computes on the host (k * (1 / 255.f) is a different value for 126 of the 256
+ * bytes).  Every kernel below forms it at its load with the one conversion helper of csrc/etm_common.h and is otherwise the code of its fp32 twin:
+ * same tiles, same split into bf16 terms, same product and reduction order, hence bit-identical results.
+ *   etm_bytes_to_unit   : dst[r][j] = unit(src[(index ? index[r] : r)][j]) for r < rows, j < row_bytes -- the general fallback in
+ *                         front of every fp32 kernel that has no byte form.  Any row length, any alignment of src; dst dense, 16-byte
+ *                         aligned (16-byte stores); index (optional, device int64 [rows]) gathers source rows.
+ *   etm_conv_relu_u8    : etm_conv_relu on an NCHW byte input (the first layer; in_nhwc must be 0): per 8-wide k-group a lane reads
+ *                         its four consecutive window bytes as one 4-byte load at the fp32 kernel's element offsets.  `in` 4-byte
+ *                         aligned, in_index_stride in elements (= bytes) and a multiple of 4; W % 4 == 0, S % 4 == 0 as before;
+ *                         Cout == 32 (the first layer's width; ETM_EUNSUPPORTED otherwise).
+ *   etm_conv_b3_fwd_u8  : etm_conv_b3_fwd of the FIRST layer (3 x 84 x 84, 8 x 8 / 4, 32 channels) on NHWC byte images: the fill
+ *                         loads 16 bytes = 16 elements per lane.  x 16-byte aligned; x_index as etm_conv_b3_fwd.
+ *   etm_conv_b3_wgrad_u8: etm_conv_b3_wgrad of the first layer on NHWC byte images; slices = etm_conv_b3_wgrad_slices.
+ * ETM_EUNSUPPORTED for every other geometry: the caller expands with etm_bytes_to_unit and runs the fp32 kernels. */
+int etm_bytes_to_unit(const uint8_t *src, const int64_t *index, float *dst, int64_t rows, int64_t row_bytes, void *stream);
+int etm_conv_relu_u8(const uint8_t *in, const int64_t *in_index, int64_t in_index_stride, const float *w, const float *bias, float *out,
+                     int N, int C, int H, int W, int Cout, int KH, int KW, int S, int in_nhwc, int out_nchw, void *stream);
+int etm_conv_b3_fwd_u8(const uint8_t *x, const int64_t *x_index, const uint16_t *w_b3, const float *bias, float *y, uint32_t *relu_bits,
+                       int N, int C, int H, int W, int Cout, int KH, int KW, int S, void *stream);
+int etm_conv_b3_wgrad_u8(const uint8_t *x, const int64_t *x_index, const float *dy, const uint32_t *dy_relu_bits, float *workspace,
+                         int64_t workspace_bytes, int N, int C, int H, int W, int Cout, int KH, int KW, int S, void *stream);
+
 /* hipMemcpyAsync(dst, src, bytes, host-to-device) on `stream`: pinned observation rows are streamed into the time-major
  * staging array while the environments still step (trainer.py:190 of the reference uploads per worker, synchronously). */
 int etm_upload(void *dst, const void *src, int64_t bytes, void *stream);

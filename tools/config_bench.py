@@ -38,5 +38,6 @@ for i in range(n_upd):
 steps = cfg["n_workers"] * cfg["worker_steps"]
 print(f"{name}: {steps * n_upd / (r + t):.0f} env-steps/s  (rollout {r / n_upd:.3f} s, train {t / n_upd:.3f} s per update of {steps} steps; "
       f"D={cfg['transformer']['embed_dim']} L={cfg['transformer']['memory_length']} blocks={cfg['transformer']['num_blocks']} "
-      f"gtrxl={cfg['transformer']['gtrxl']} ln={cfg['transformer']['layer_norm']!r})")
+      f"gtrxl={cfg['transformer']['gtrxl']} ln={cfg['transformer']['layer_norm']!r}; observations {tr.buffer.obs.dtype}, "
+      f"peak device memory {torch.cuda.max_memory_allocated(dev) / 2 ** 20:.0f} MiB allocated / {torch.cuda.max_memory_reserved(dev) / 2 ** 20:.0f} MiB reserved)")
 tr.close()                          # (worker processes: stops them and unlinks the shared segment)
