@@ -107,8 +107,19 @@ static inline int etm_branches_total(const int32_t *sizes, int n) {
   return s;
 }
 
+// The mode of one branch: the smallest index whose logit equals the branch's maximum mx (as computed by etm_sample_branch; the last
+// index when none compares equal, which only NaN logits can cause).
+__device__ __forceinline__ int etm_branch_mode(const float *lg, int A, float mx) {
+  for (int j = 0; j < A - 1; ++j)
+    if (lg[j] == mx) return j;
+  return A - 1;
+}
+
 // One branch's draw: log-sum-exp over its own A logits, then the inverse CDF at its own uniform u -- or the forced action when
-// forced >= 0.  Returns the action (inside the branch) and its log-prob.  With one branch this is exactly the single-branch
+// forced >= 0, or the MODE of the branch (etm_branch_mode: the first maximum) when the uniform is negative: u < 0 is the greedy
+// sentinel of the uniform tables, chosen per (step, worker, branch) entry, so evaluation replays the step graphs captured for
+// training.  A uniform in [0, 1) -- and a NaN one, for which u < 0 is false -- takes the inverse CDF exactly as before.  Returns the
+// action (inside the branch) and its log-prob lg[a] - lse in all three cases.  With one branch this is exactly the single-branch
 // arithmetic of every sampling site (same operations in the same order).
 __device__ __forceinline__ int etm_sample_branch(const float *lg, int A, float u, int forced, float *logp) {
   float mx = -INFINITY;
@@ -117,7 +128,7 @@ __device__ __forceinline__ int etm_sample_branch(const float *lg, int A, float u
   for (int j = 0; j < A; ++j) se += expf(lg[j] - mx);
   const float lse = mx + logf(se);
   int a = forced;
-  if (a < 0) a = etm_sample_categorical(lg, A, lse, u);
+  if (a < 0) a = u < 0.f ? etm_branch_mode(lg, A, mx) : etm_sample_categorical(lg, A, lse, u);
   *logp = lg[a] - lse;
   return a;
 }
@@ -167,6 +178,8 @@ static inline int etm_box_make(const float *lo, const float *hi, int A, EtmBox *
 // x_a = mu_a + sigma_a eps_a with eps = normals[0 .. A) (or the forced action forced[a] where it is not NaN), the joint log-prob
 // log p(x) = sum_a [-(x_a - mu_a)^2 / (2 sigma_a^2) - log sigma_a - log(2 pi) / 2] of the stored x, staging of x ([S, stage_W, A]),
 // log p and the value ([S, stage_W]); actions / host_actions [W, A] receive clip(x, lo, hi).  normals / forced / log_std: A floats.
+// The mode of a Box policy needs no sentinel: a zero in the normals table stores x = mu + sigma * 0 = mu (the deterministic
+// rollouts of the evaluator zero the table), and log p is then sum_a [(-0 - log sigma_a) - log(2 pi) / 2].
 __device__ __forceinline__ void etm_sample_gaussian(const float *mu, const float *log_std, const EtmBox &bx, const float *normals,
                                                     const float *forced, float value, long long row, int w, float *actions,
                                                     float *host_actions, float *st_actions, float *st_logp, float *st_values) {

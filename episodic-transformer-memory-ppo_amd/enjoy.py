@@ -1,7 +1,7 @@
 """Run one episode with a trained checkpoint (upstream enjoy.py: --model flag, ``pickle((state_dict, config))`` format of
 ``PPOTrainer._save_model`` / upstream trainer.py:356-362).
 
-    python enjoy.py --model ./models/run.nn
+    python enjoy.py --model ./models/run.nn [--deterministic]
 
 The model runs on the MI355X (there is no CPU path in this build); the episode loop is upstream's (enjoy.py:62-90): one
 environment, one zero-initialised episodic memory [1, T, blocks, D], per step the window rows of ``memory_indices[t]``,
@@ -27,8 +27,9 @@ def init_transformer_memory(trxl_conf: dict, max_episode_steps: int, device):
     return memory, mask.to(device), indices.to(device)
 
 
-def run_episode(model, env, config, device, max_steps=None):
-    """-> (list of rewards, last info dict).  Sampling uses torch's generator of ``device``."""
+def run_episode(model, env, config, device, max_steps=None, deterministic=False):
+    """-> (list of rewards, last info dict).  Sampling uses torch's generator of ``device``; ``deterministic`` takes the mode of
+    every branch instead: the first maximum of a categorical branch's logits, the mean of a Box policy."""
     memory, memory_mask, memory_indices = init_transformer_memory(config["transformer"], env.max_episode_steps, device)
     memory_length = config["transformer"]["memory_length"]
     rewards, info, done, t = [], None, False, 0
@@ -46,10 +47,11 @@ def run_episode(model, env, config, device, max_steps=None):
         policy, _value, new_memory = model(obs_t, in_memory, mask, indices)
         memory[:, t] = new_memory.detach()
         if getattr(model, "continuous", False):      # Box: one Gaussian draw of A dimensions, clipped to the space's bounds
-            a = policy[0].sample()[0].cpu().numpy()
+            a = (policy[0].mean if deterministic else policy[0].sample())[0].cpu().numpy()
             action = np.clip(a, env.action_space.low, env.action_space.high).astype(np.float32)
         else:
-            action = [branch.sample().item() for branch in policy]
+            # (argmax returns the first of equal maxima)
+            action = [(branch.logits.argmax(dim=-1) if deterministic else branch.sample()).item() for branch in policy]
         obs, reward, done, info = env.step(action)
         rewards.append(reward)
         t += 1
@@ -59,6 +61,7 @@ def run_episode(model, env, config, device, max_steps=None):
 def main():
     ap = argparse.ArgumentParser(description="Run one episode with a trained model on the MI355X")
     ap.add_argument("--model", default="./models/run.nn", help="Path to the trained model")
+    ap.add_argument("--deterministic", action="store_true", help="Take the mode of the policy at every step instead of sampling")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("no HIP device visible: the model runs on the MI355X kernels (there is no CPU fallback)")
@@ -71,7 +74,7 @@ def main():
     model.load_state_dict(state_dict)
     model.to(device)
     model.eval()
-    rewards, info = run_episode(model, env, config, device)
+    rewards, info = run_episode(model, env, config, device, deterministic=args.deterministic)
     if hasattr(env, "render"):
         env.render()
     if info:

@@ -130,6 +130,29 @@ def check_byte_observation_transport(config, env=None):
                          "set worker_processes: false (in-process environments keep the bytes), or let the environment emit float32")
 
 
+def check_evaluation_config(config, world: int = 1):
+    """The optional ``evaluation`` section (interval, episodes_per_worker, n_workers, deterministic, seed, worker_steps) -> a dict with
+    the defaults filled in, or None when the section is absent (never evaluate, allocate nothing).  ``evaluation.interval`` in a
+    data-parallel run (``world`` > 1) is refused, before any environment is built: every rank would have to take part in the same
+    evaluation -- evaluate the checkpoint with evaluate.py instead."""
+    ev = config.get("evaluation")
+    if ev is None:
+        return None
+    known = ("interval", "episodes_per_worker", "n_workers", "deterministic", "seed", "worker_steps")
+    unknown = sorted(set(ev) - set(known))
+    if unknown:
+        raise ValueError(f"evaluation: unknown keys {unknown} (known: {list(known)})")
+    out = dict(interval=int(ev.get("interval", 0) or 0), episodes_per_worker=int(ev.get("episodes_per_worker", 1)),
+               n_workers=int(ev.get("n_workers", config["n_workers"])), deterministic=bool(ev.get("deterministic", True)),
+               seed=int(ev.get("seed", 100000)), worker_steps=ev.get("worker_steps"))
+    if out["interval"] < 0 or out["episodes_per_worker"] < 1 or out["n_workers"] < 1:
+        raise ValueError("evaluation: interval >= 0, episodes_per_worker >= 1 and n_workers >= 1 are required")
+    if out["interval"] > 0 and world > 1:
+        raise ValueError("evaluation.interval in a data-parallel run: periodic evaluation runs on one rank's device only; "
+                         "evaluate the checkpoint with evaluate.py instead")
+    return out
+
+
 def time_major(table, src):
     """The host table ``src`` [W, S(, B)] in the layout and type of the fixed-address device table ``table`` [S, W(, B)]."""
     x = torch.as_tensor(np.asarray(src), dtype=table.dtype)
@@ -163,6 +186,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         check_kernel_shapes(t)
         check_box_policy(config)
         check_byte_observation_transport(config, env)
+        check_evaluation_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         self.writer = _make_writer(run_id) if tensorboard else _NullWriter()
 
         # environments (batched front-end over the upstream per-worker protocol)
@@ -218,6 +242,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                                       spin=self._host_plan["worker_spin"])
             env = self._shm_env
         self.env = env if env is not None else make_vec_env(env_cfg, self.num_workers, first_worker_id, groups=n_groups)
+        self._env_cfg, self._env_groups = env_cfg, n_groups      # (the evaluator rebuilds its environments from these)
+        self._evaluator = None            # evaluation.Evaluator, allocated by the first evaluate()
+        self._draw_generator = None       # the rollout's draws come from torch's generator of the device (None) or from this one
         W = self.num_workers
         obs_shape = tuple(self.env.observation_space_shape)
         self.observation_space = type("Space", (), {"shape": obs_shape})()
@@ -388,6 +415,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
     def run_training(self) -> None:
         print("Step 6: Starting training using " + str(self.device))
         episode_infos = deque(maxlen=100)
+        ev_cfg = check_evaluation_config(self.config, 1 if self.dp is None else int(getattr(self.dp, "world", 1)))
+        ev_every = ev_cfg["interval"] if ev_cfg is not None else 0
         for update in range(self.config["updates"]):
             lr, beta, clip = self.schedules(update)
             t0 = time.perf_counter()
@@ -414,6 +443,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                     training_stats[0], training_stats[1], training_stats[3], training_stats[2], vmean, amean, steps_per_s))
             self._write_gradient_summary(update, grad_info)
             self._write_training_summary(update, training_stats, episode_result, vmean, amean, steps_per_s)
+            if ev_every and ((update + 1) % ev_every == 0 or update + 1 == self.config["updates"]):
+                self._write_evaluation_summary(update, self.evaluate(ev_cfg["episodes_per_worker"], ev_cfg["n_workers"], ev_cfg["deterministic"]))
         if self._is_main:              # replicas are identical: one rank writes the checkpoint
             self._save_model()
         if self.dp is not None:
@@ -435,7 +466,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
     _native_rollout = property(lambda self: self._plan is not None and self._plan.native)
     _direct_rows = property(lambda self: self._plan is not None and self._plan.direct_rows)
 
-    def _sample_training_data(self, forced_actions=None, uniforms=None, normals=None) -> list:
+    def _sample_training_data(self, forced_actions=None, uniforms=None, normals=None, deterministic=False) -> list:
         """Runs all workers for ``worker_steps`` steps; fills the buffer; returns finished-episode infos.
 
         The device work of one step (window lookup, model forward, action sampling, staging of the step's buffer rows,
@@ -453,9 +484,15 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         ``uniforms`` [W, S] or [W, S, B] (optional, tests) replaces the rollout's uniform draws: every sampling kernel inverts its CDF at
         exactly these values (branch b of a MultiDiscrete policy at its own draw).
         Box policies: ``forced_actions`` [W, S, A] floats (NaN = sample), ``normals`` [W, S, A] (optional, tests) replaces the
-        rollout's N(0, 1) draws."""
+        rollout's N(0, 1) draws.
+        ``deterministic``: every action is the MODE of the policy on whichever path the config selects -- a categorical policy's
+        uniform table is filled with the greedy sentinel -1 (etm_sample_branch: the first maximum of each branch's logits), a Box
+        policy's normals table with zeros (the mean).  ``forced_actions`` keep their meaning; ``uniforms`` / ``normals`` together
+        with it is a ValueError (a ``uniforms`` table may itself hold negative entries: greedy per entry)."""
+        if deterministic and (uniforms is not None or normals is not None):
+            raise ValueError("deterministic=True fills the draw tables itself: do not pass uniforms= / normals= with it")
         main = torch.cuda.current_stream(self.device)
-        plan, groups = self._begin_rollout(main, forced_actions, uniforms, normals)
+        plan, groups = self._begin_rollout(main, forced_actions, uniforms, normals, deterministic)
         # the device work of a step of a group goes in flight in ONE of three forms
         launch = self._launch_graph_exec if plan.direct_launch else self._launch_replay if plan.graph else self._launch_eager
         for g in groups:
@@ -475,7 +512,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         self._finish_rollout(plan, main, forced_actions is not None, timing)
         return episode_infos
 
-    def _begin_rollout(self, main, forced_actions, uniforms, normals):
+    def _begin_rollout(self, main, forced_actions, uniforms, normals, deterministic=False):
         """Everything before step 0: episode slots, K/V cache and weight copies, the draw tables, the captured graphs (first rollout)
         and with them the plan, the streams, the rows of observation 0.  -> (plan, the groups that run)."""
         self.buffer.begin_rollout(self._slot_dev)
@@ -493,14 +530,20 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             plan = self._plan
         else:
             groups, plan = [self._group_all], RolloutPlan(polite_wait=bool(self._host_plan["polite_wait"]))
-        if self.box is None and uniforms is not None:
+        if deterministic:
+            # the mode at every entry: the greedy sentinel in the uniforms, zeros in the normals (x = mu + sigma * 0)
+            if self.box is None:
+                self._uniforms.fill_(-1.0)
+            else:
+                self._normals.zero_()
+        elif self.box is None and uniforms is not None:
             self._uniforms.copy_(time_major(self._uniforms, uniforms))
         elif self.box is None:
-            self._uniforms.uniform_()            # one draw per (step, worker, branch) for the whole rollout
+            self._uniforms.uniform_(generator=self._draw_generator)      # one draw per (step, worker, branch) for the whole rollout
         elif normals is not None:
             self._normals.copy_(time_major(self._normals, normals))
         else:
-            self._normals.normal_()              # one N(0, 1) draw per (step, worker, dimension) for the whole rollout
+            self._normals.normal_(generator=self._draw_generator)        # one N(0, 1) draw per (step, worker, dimension) for the whole rollout
         for g in groups:
             g.restart()
             if g.stream is not None:
@@ -1346,8 +1389,26 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             return None, None
         return self._tg_stats_tab[0].clone(), (self._tg_norm_tab[0].clone() if monitor else None)
 
+    def evaluate(self, episodes_per_worker=1, n_workers=None, deterministic=True, seed=None, worker_steps=None) -> dict:
+        """Plays ``episodes_per_worker`` whole episodes in each of ``n_workers`` (None: the config's) held-out environments with the
+        current weights, through the same step kernels and captured step graphs as a training rollout -> {"episodes", "result",
+        "steps", "seconds"} (evaluation.Evaluator).  ``deterministic``: the mode of the policy at every step, else sampled from the
+        evaluator's own generator.  ``seed`` (None: ``evaluation.seed``, or else 100000): the first worker id of the evaluation's
+        environments and the seed of sampled draws.  The evaluator owns its environments and rollout state: training with
+        evaluations interleaved computes the same bits as training without."""
+        from evaluation import Evaluator, evaluation_defaults
+        ev = evaluation_defaults(self.config)
+        if self._evaluator is None:
+            self._evaluator = Evaluator(self.config, self.device, self.run_id, parameters=lambda: self.optimizer.flat_params)
+        return self._evaluator.run(episodes_per_worker=int(episodes_per_worker), n_workers=n_workers, deterministic=bool(deterministic),
+                                   seed=ev["seed"] if seed is None else int(seed),
+                                   worker_steps=ev["worker_steps"] if worker_steps is None else int(worker_steps))
+
     def close(self, exit_process: bool = False) -> None:
         """Releases environments and the summary writer (upstream also ``exit(0)``s; opt in with exit_process)."""
+        if getattr(self, "_evaluator", None) is not None:
+            self._evaluator.close()
+            self._evaluator = None
         if getattr(self, "_shm_registered", None):
             try:
                 torch.cuda.synchronize(self.device)

@@ -207,6 +207,21 @@ class _RunOutputs:
         self.writer.add_scalar("other/clip_fraction", training_stats[5], update)
         self.writer.add_scalar("other/env_steps_per_second", steps_per_s, update)
 
+    def _write_evaluation_summary(self, update, evaluation) -> None:
+        """``evaluation/<key>`` scalars of one periodic evaluation (PPOTrainer.evaluate's dict) and one printed line."""
+        result = evaluation["result"]
+        for key in result:
+            if "std" not in key:
+                self.writer.add_scalar("evaluation/" + key, result[key], update)
+        self.writer.add_scalar("evaluation/env_steps_per_second", evaluation["steps"] / max(evaluation["seconds"], 1e-9), update)
+        if self._is_main:
+            line = "{:4} evaluation episodes={}".format(update, len(evaluation["episodes"]))
+            if "reward_mean" in result and "length_mean" in result:
+                line += " reward={:.2f} std={:.2f} length={:.1f}".format(result["reward_mean"], result["reward_std"], result["length_mean"])
+            if "success_percent" in result:
+                line += " success={:.2f}".format(result["success_percent"])
+            print(line + " steps={} seconds={:.3f}".format(evaluation["steps"], evaluation["seconds"]))
+
     def _write_gradient_summary(self, update, grad_info):
         for key, value in grad_info.items():
             self.writer.add_scalar("gradients/" + key, np.mean(value), update)

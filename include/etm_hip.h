@@ -35,7 +35,8 @@ extern "C" {
 #define ETM_EABORTED (-6)    /* etm_rollout_drive: an environment worker reported an error / the abort word was set */
 #define ETM_ERCCL_BASE 100000 /* ETM_ERCCL_BASE + ncclResult_t: an RCCL call failed */
 
-/* ABI version of this header (bumped on any signature change). */
+/* ABI version of this header (bumped on any signature change, and when the meaning of an argument widens: 52 = the greedy
+ * sentinel of the `uniforms` tables). */
 int etm_abi_version(void);
 
 /* Human-readable name for a negative ETM_E* code or a hipError_t. Static storage. */
@@ -213,6 +214,13 @@ int etm_reset_rows(float *dst, const float *init, const int64_t *step, int W, in
  *                       (forced, optional: time-major int64 table like `uniforms`; a non-negative entry forced[*t_dev, w] is
  *                       taken instead of sampling -- teacher forcing for parity tests -- a negative entry means "sample")
  *                       of st_actions / st_logp / st_values, then *t_dev += 1 (trainer.py:179-186).
+ *                       GREEDY SENTINEL (ABI 52), at every `uniforms` parameter of this header (etm_rollout_sample[_branched],
+ *                       etm_rollout_policy[_branched], etm_rollout_trxl[_branched], the group kernels): an entry u < 0 that is not
+ *                       forced selects the MODE of its branch, the smallest index whose logit equals the branch's fp32 maximum;
+ *                       the log-prob is that action's, as for a draw.  Entries in [0, 1) (and NaN) take the inverse CDF with the
+ *                       operations of ABI 51, bit for bit.  The sentinel is per (step, worker, branch) entry of the fixed-address
+ *                       table, so one captured step graph serves sampled and greedy rollouts.  Box policies (`normals`) have no
+ *                       sentinel: a zero normal stores the mean.
  *   etm_add_layernorm:  out = LayerNorm(act(a + a_bias) + b) (residual + post-LN, transformer.py:145-149 / :166-170), forward only,
  *                       D <= 1024; a_bias [D] (or NULL) and relu fold the bias / ReLU of the linear layer that produced `a`.
  */
