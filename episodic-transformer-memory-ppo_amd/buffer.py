@@ -13,6 +13,9 @@ the storage redesigned for the MI355X path:
   [N, L, blocks, D] gather (trainer.py:271) do not exist.  ``materialize=True`` reproduces upstream's minibatch
   layout for API users that want it.
 * GAE (buffer.py:95-113) is the ``etm_gae`` kernel, bit-identical to the upstream loop.
+* ``bootstrap_truncated: true`` (absent upstream): ``truncated`` [W, S] marks the steps whose episode was only cut at a time limit,
+  ``bootstrap_values`` [W, S] holds the value of the observation after the cut; GAE (``etm_gae_truncated``) takes the next value of
+  such a step from there instead of 0.  Neither is allocated without the key.
 """
 import numpy as np
 import torch
@@ -48,6 +51,14 @@ class Buffer:
         self.memory_index_host = self._memory_index_host.numpy()
         self.rewards_dev = torch.zeros((W, S), dtype=torch.float32, device=dev)
         self.dones_dev = torch.zeros((W, S), dtype=torch.bool, device=dev)
+        # time-limit truncations (bootstrap_truncated: true): flags from the env loop like ``dones``, values from the trainer's
+        # bootstrap pass; None without the key
+        self.truncated = self.truncated_dev = self.bootstrap_values = None
+        if config.get("bootstrap_truncated", False):
+            self._truncated_host = pin((W, S), torch.bool)
+            self.truncated = self._truncated_host.numpy()
+            self.truncated_dev = torch.zeros((W, S), dtype=torch.bool, device=dev)
+            self.bootstrap_values = torch.zeros((W, S), dtype=torch.float32, device=dev)
 
         # (Box: the raw float actions [W, S, A] and one joint log-prob per sample)
         self.actions = torch.zeros((W, S, B), dtype=torch.float32 if continuous else torch.long, device=dev)
@@ -103,6 +114,9 @@ class Buffer:
             self.bank[W: self.num_episodes].zero_()
         self.num_episodes = W
         self.memory_index_host[:] = np.arange(W, dtype=np.int64)[:, None]
+        if self.truncated is not None:
+            self.truncated[:] = False
+            self.bootstrap_values.zero_()
 
     def _mark_host_arrays_uploaded(self):
         if self.device.type == "cuda":
@@ -167,5 +181,11 @@ class Buffer:
         """GAE over the [W, S] buffer on device (upstream buffer.py:95-113)."""
         self.rewards_dev.copy_(self._rewards_host, non_blocking=True)
         self.dones_dev.copy_(self._dones_host, non_blocking=True)
+        if self.truncated is not None:
+            self.truncated_dev.copy_(self._truncated_host, non_blocking=True)
         self._mark_host_arrays_uploaded()
+        if self.truncated is not None:
+            ops.gae(self.rewards_dev, self.dones_dev, self.values, last_value.detach(), gamma, lamda, out=self.advantages,
+                    truncated=self.truncated_dev, boot=self.bootstrap_values)
+            return
         ops.gae(self.rewards_dev, self.dones_dev, self.values, last_value.detach(), gamma, lamda, out=self.advantages)

@@ -13,12 +13,19 @@
 // instructions per wave regardless of the tile shape).  W = 65,536 gives 4,096 single-wave workgroups = 16 waves per CU with
 // ~9 KB in flight each; W = 32 is two waves of 8 tiles each (launch- and latency-bound: ~10 us).
 // HBM traffic: 13 bytes per (worker, step).
+//
+// TRUNC (etm_gae_truncated): where truncated[w,t] is set the next value of step t is boot[w,t] instead of v_{t+1} * (1 - done_t) -- a
+// SELECT in the delta phase, so boot may hold anything (NaN included) where the flag is clear; the chain is untouched (it is cut at
+// every done).  The flag bytes (+1 byte per (worker, step)) are requested ONE TILE AHEAD of the other arrays, so that the fetch of a
+// tile already holds its flags and loads boot only where one is set (16 bytes around it when VEC): both fly under the scan like the
+// rest of the prefetch, and a tile without a truncation moves no byte of boot.
 #include "etm_common.h"
 
 namespace {
-template <int WPW, bool VEC>
+template <int WPW, bool VEC, bool TRUNC>
 __global__ __launch_bounds__(64) void gae_kernel(const float *__restrict__ rewards, const unsigned char *__restrict__ dones,
-                                                 const float *__restrict__ values, const float *__restrict__ last_value,
+                                                 const unsigned char *__restrict__ truncated, const float *__restrict__ values,
+                                                 const float *__restrict__ boot, const float *__restrict__ last_value,
                                                  float gamma, float gamma_lambda, float *__restrict__ adv, int W, int S) {
   constexpr int TT = 1024 / WPW;     // steps per tile
   constexpr int LPR = TT / 4;        // lanes per worker row of a tile (4 steps per lane)
@@ -34,12 +41,35 @@ __global__ __launch_bounds__(64) void gae_kernel(const float *__restrict__ rewar
 
   float pr[NI][4], pv[NI][4], pm[NI][4];      // prefetched tile: rewards, values, 1 - done of this lane's 4 steps per row
   float lastv[NI], carry[NI];                 // bootstrap value of the row; first value of the tile scanned before (= later in time)
+  float pb[NI][4];                            // TRUNC: boot of this lane's 4 steps (0 where it was not loaded)
+  unsigned pt[NI], pt_ahead[NI];              // TRUNC: truncation flags of the 4 steps, one per byte, of the prefetched tile / the one before it
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int w = w0 + i * R + rsub;
     lastv[i] = (w < W) ? last_value[w] : 0.f;
     carry[i] = 0.f;
   }
+  auto fetch_flags = [&](int tile) {           // -> pt_ahead; 0 outside the array
+    const int t = tile * TT + tsub;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int w = w0 + i * R + rsub;
+      if constexpr (VEC) {
+        const bool ok = w < W && t < S;
+        const unsigned f = *reinterpret_cast<const unsigned *>(truncated + (ok ? (long long)w * S + t : 0));
+        pt_ahead[i] = ok ? f : 0u;
+      } else {
+        unsigned f = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool ok = w < W && t + j < S;
+          const unsigned char b = truncated[ok ? (long long)w * S + t + j : 0];
+          f |= (ok && b) ? (1u << (8 * j)) : 0u;
+        }
+        pt_ahead[i] = f;
+      }
+    }
+  };
   auto fetch = [&](int tile) {
     const int t = tile * TT + tsub;
 #pragma unroll
@@ -67,9 +97,31 @@ __global__ __launch_bounds__(64) void gae_kernel(const float *__restrict__ rewar
         }
       }
     }
+    if constexpr (TRUNC) {                    // the flags of this tile arrived with the fetch before: boot only where one is set
+#pragma unroll
+      for (int i = 0; i < NI; ++i) {
+        const int w = w0 + i * R + rsub;
+        pt[i] = pt_ahead[i];
+        pb[i][0] = pb[i][1] = pb[i][2] = pb[i][3] = 0.f;
+        if (pt[i] != 0u) {                    // (a set flag implies w < W and t (+ j) < S)
+          if constexpr (VEC) {
+            const float4 b4 = *reinterpret_cast<const float4 *>(boot + (long long)w * S + t);
+            pb[i][0] = b4.x; pb[i][1] = b4.y; pb[i][2] = b4.z; pb[i][3] = b4.w;
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if ((pt[i] >> (8 * j)) & 0xffu) pb[i][j] = boot[(long long)w * S + t + j];
+          }
+        }
+      }
+    }
   };
 
+  if constexpr (TRUNC) fetch_flags(n_tiles - 1);
   fetch(n_tiles - 1);
+  if constexpr (TRUNC) {
+    if (n_tiles > 1) fetch_flags(n_tiles - 2);
+  }
   float la = 0.f;                              // running advantage of worker w0 + lane (lanes < WPW)
   for (int tile = n_tiles - 1; tile >= 0; --tile) {
     const int t0 = tile * TT;
@@ -84,7 +136,8 @@ __global__ __launch_bounds__(64) void gae_kernel(const float *__restrict__ rewar
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (t + j == S - 1) vn[j] = lastv[i];
-        const float lv = __fmul_rn(vn[j], pm[i][j]);
+        float lv = __fmul_rn(vn[j], pm[i][j]);
+        if constexpr (TRUNC) lv = ((pt[i] >> (8 * j)) & 0xffu) ? pb[i][j] : lv;      // a select: boot elsewhere never enters
         const float delta = __fsub_rn(__fadd_rn(pr[i][j], __fmul_rn(gamma, lv)), pv[i][j]);
         d_s[(i * R + rsub) * LS + tsub + j] = delta;
         m_s[(i * R + rsub) * LS + tsub + j] = pm[i][j];
@@ -93,6 +146,9 @@ __global__ __launch_bounds__(64) void gae_kernel(const float *__restrict__ rewar
     }
     __syncthreads();
     if (tile > 0) fetch(tile - 1);                           // in flight while this tile is scanned and stored
+    if constexpr (TRUNC) {
+      if (tile > 1) fetch_flags(tile - 2);
+    }
     const int t_hi = min(TT, S - t0);
     if (lane < WPW) {
       const int base = lane * LS;
@@ -129,21 +185,42 @@ __global__ __launch_bounds__(64) void gae_kernel(const float *__restrict__ rewar
 }
 }  // namespace
 
-extern "C" int etm_gae(const float *rewards, const uint8_t *dones, const float *values, const float *last_value, float gamma,
-                       float gamma_lambda, float *advantages, int W, int S, void *stream) {
+namespace {
+int launch_gae(const float *rewards, const uint8_t *dones, const uint8_t *truncated, const float *values, const float *boot,
+               const float *last_value, float gamma, float gamma_lambda, float *advantages, int W, int S, void *stream) {
   (void)hipGetLastError();  // drop stale sticky errors of earlier, unrelated runtime calls
-  if (!rewards || !dones || !values || !last_value || !advantages) return ETM_EINVAL;
+  const bool trunc = truncated != nullptr;
+  if (!rewards || !dones || !values || !last_value || !advantages || (trunc && !boot)) return ETM_EINVAL;
   if (W <= 0 || S <= 0) return ETM_EINVAL;
   EtmProfScope prof(ETM_K_GAE, (hipStream_t)stream);
   constexpr int WPW = 16;
   const dim3 grid((unsigned)((W + WPW - 1) / WPW)), block(64);
-  const bool vec = S % 4 == 0 && ((uintptr_t)rewards % 16 == 0) && ((uintptr_t)values % 16 == 0) && ((uintptr_t)advantages % 16 == 0) &&
-                   ((uintptr_t)dones % 4 == 0);
-  if (vec)
-    hipLaunchKernelGGL((gae_kernel<WPW, true>), grid, block, 0, (hipStream_t)stream, rewards, dones, values, last_value, gamma, gamma_lambda,
-                       advantages, W, S);
-  else
-    hipLaunchKernelGGL((gae_kernel<WPW, false>), grid, block, 0, (hipStream_t)stream, rewards, dones, values, last_value, gamma, gamma_lambda,
-                       advantages, W, S);
+  bool vec = S % 4 == 0 && ((uintptr_t)rewards % 16 == 0) && ((uintptr_t)values % 16 == 0) && ((uintptr_t)advantages % 16 == 0) &&
+             ((uintptr_t)dones % 4 == 0);
+  if (trunc) vec = vec && ((uintptr_t)truncated % 4 == 0) && ((uintptr_t)boot % 16 == 0);
+#define ETM_GAE_LAUNCH(V, T)                                                                                                      \
+  hipLaunchKernelGGL((gae_kernel<WPW, V, T>), grid, block, 0, (hipStream_t)stream, rewards, dones, truncated, values, boot, last_value, \
+                     gamma, gamma_lambda, advantages, W, S)
+  if (trunc) {
+    if (vec) ETM_GAE_LAUNCH(true, true);
+    else ETM_GAE_LAUNCH(false, true);
+  } else {
+    if (vec) ETM_GAE_LAUNCH(true, false);
+    else ETM_GAE_LAUNCH(false, false);
+  }
+#undef ETM_GAE_LAUNCH
   return etm_launch_status();
+}
+}  // namespace
+
+extern "C" int etm_gae(const float *rewards, const uint8_t *dones, const float *values, const float *last_value, float gamma,
+                       float gamma_lambda, float *advantages, int W, int S, void *stream) {
+  return launch_gae(rewards, dones, nullptr, values, nullptr, last_value, gamma, gamma_lambda, advantages, W, S, stream);
+}
+
+extern "C" int etm_gae_truncated(const float *rewards, const uint8_t *dones, const uint8_t *truncated, const float *values,
+                                 const float *boot, const float *last_value, float gamma, float gamma_lambda, float *advantages,
+                                 int W, int S, void *stream) {
+  if (!truncated || !boot) return ETM_EINVAL;
+  return launch_gae(rewards, dones, truncated, values, boot, last_value, gamma, gamma_lambda, advantages, W, S, stream);
 }

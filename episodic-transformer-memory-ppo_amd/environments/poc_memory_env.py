@@ -4,6 +4,8 @@ Own implementation of the task described in upstream environments/poc_memory_env
 visible only during the first two steps (while the agent is frozen), afterwards the observation shows only the
 position, so solving it requires memory.  Observation [goal_left, position, goal_right]; actions {0: left, 1: right};
 reward -0.1 per step, +/-(1 + 0.1 * min_steps) at the ends; episodes are cut at ``max_episode_steps``.
+``report_truncation=True``: an episode ended ONLY by that cut (the agent is not at a goal) says so with ``"truncated": True`` in its
+info dict (environments/vec_env.py); off (default) the info dicts are what they always were.
 Uses its own ``numpy.random.Generator`` (seedable) instead of the global numpy RNG.
 """
 from types import SimpleNamespace
@@ -13,8 +15,9 @@ import numpy as np
 
 class PocMemoryEnv:
     def __init__(self, step_size: float = 0.2, glob: bool = False, freeze: bool = False, max_episode_steps: int = -1,
-                 seed=None):
+                 seed=None, report_truncation: bool = False):
         self.freeze = freeze
+        self.report_truncation = bool(report_truncation)
         self._step = step_size
         self.max_episode_steps = max_episode_steps
         self._min_steps = int(1.0 / step_size) + 1
@@ -61,18 +64,20 @@ class PocMemoryEnv:
             return self._obs(True), 0.0, bool(done), None
         self._pos = float(np.round(self._pos + direction * self._step, 2))
         obs = self._obs(showing)
-        reward, success = 0.0, False
+        reward, success, at_goal = 0.0, False, False
         bonus = 1.0 + self._min_steps * self._penalty
         if self._pos == -1.0 or self._pos == 1.0:
             good = self._goals[0 if self._pos == -1.0 else 1] == 1.0
             reward = bonus if good else -bonus
             success = bool(good)
-            done = True
+            done = at_goal = True
         else:
             reward = -self._penalty
         self._rewards.append(reward)
         self._t += 1
         info = {"success": success, "reward": float(sum(self._rewards)), "length": len(self._rewards)} if done else None
+        if done and self.report_truncation and not at_goal:
+            info["truncated"] = True
         return obs, reward, bool(done), info
 
     def close(self):

@@ -16,6 +16,13 @@
         covering [0, W) -- the trainer starts their upload while the remaining environments still step
 with auto-reset: for a finished worker the returned observation is already the first one of the next episode, which
 is exactly what upstream's loop does by hand (trainer.py:195-201).
+    A finished episode's info dict may carry two more keys (the trainer strips both before it averages the infos):
+    "truncated": True -- the episode was only CUT (a time limit); the state after its last step is not terminal.  Absent =
+        terminated.  With ``bootstrap_truncated: true`` GAE then bootstraps from the value of the final observation instead of 0.
+    "final_observation" -- with "truncated" only: the observation ``step`` returned for the episode's last step (the one the auto-reset
+        replaces in the returned rows), a copy in the environment's own dtype (uint8 stays bytes).  ``SerialVecEnv`` and ``PipeVecEnv``
+        add it; ``SyntheticVecEnv`` never reports a truncation (its terminal frame is deliberately not drawn: the key is a no-op there),
+        and the worker processes' shared segment (``worker_processes: true``) has no row for it -- that combination is refused.
 
 * ``SerialVecEnv``  -- wraps in-process single envs with the upstream env API.
 * ``PipeVecEnv``    -- wraps upstream-protocol ``Worker`` subprocesses (worker.py), one pipe round trip per step.
@@ -73,6 +80,8 @@ class SerialVecEnv(_VecBase):
             obs, rewards[w], dones[w], info = e.step(actions[w])      # (one row [B] per environment: one action per branch)
             if info:
                 infos[w] = info
+                if info.get("truncated"):
+                    info["final_observation"] = np.array(obs)      # (a copy, the environment's dtype)
                 obs = e.reset()
             out[w] = obs
             sent = self._notify(on_rows, w + 1, sent)
@@ -122,6 +131,8 @@ class PipeVecEnv(_VecBase):
             obs, rewards[w], dones[w], info = self._recv(wk)
             if info:
                 infos[w] = info
+                if info.get("truncated"):
+                    info["final_observation"] = np.array(obs)      # (a copy, the environment's dtype)
                 wk.child.send(("reset", None))
                 obs = self._recv(wk)
             out[w] = obs

@@ -1871,9 +1871,14 @@ def linear_relu(lin, x, out=None):
     return torch._addmm_activation(lin.bias, x, lin.weight.t(), use_gelu=False)
 
 
-def gae(rewards, dones, values, last_value, gamma, lamda, out=None):
-    """Generalized advantage estimation on device; [W,S] row-major like the reference buffer."""
+def gae(rewards, dones, values, last_value, gamma, lamda, out=None, truncated=None, boot=None):
+    """Generalized advantage estimation on device; [W,S] row-major like the reference buffer.
+    ``truncated`` [W,S] bool / uint8 with ``boot`` [W,S] float32 (both or neither): where the flag is set -- only meaningful at a
+    done -- the step's next value is ``boot`` instead of v_{t+1} * (1 - done) (etm_gae_truncated: a select; ``boot`` elsewhere may
+    hold anything)."""
     lib = _lib.load()
+    if (truncated is None) != (boot is None):
+        raise TypeError("gae: truncated= and boot= come together")
     _need_dev(rewards, dones, values, last_value)
     rewards, values, last_value = _f32c(rewards, "rewards"), _f32c(values, "values"), _f32c(last_value, "last_value")
     d = dones.contiguous()
@@ -1885,6 +1890,17 @@ def gae(rewards, dones, values, last_value, gamma, lamda, out=None):
         raise TypeError("advantages output must be contiguous float32")
     g32 = float(torch.tensor(float(gamma), dtype=torch.float32))
     gl32 = float(torch.tensor(float(gamma) * float(lamda), dtype=torch.float32))  # python-float product, then fp32 (buffer.py:111)
+    if truncated is not None:
+        _need_dev(truncated, boot)
+        if tuple(truncated.shape) != (W, S) or tuple(boot.shape) != (W, S):
+            raise ValueError(f"gae: truncated / boot must be [{W}, {S}], got {tuple(truncated.shape)} / {tuple(boot.shape)}")
+        boot = _f32c(boot, "boot")
+        tr = truncated.contiguous()
+        tr = tr.view(torch.uint8) if tr.dtype == torch.bool else tr.to(torch.uint8)
+        rc = lib.etm_gae_truncated(_ptr(rewards), _ptr(d), _ptr(tr), _ptr(values), _ptr(boot), _ptr(last_value), g32, gl32, _ptr(out),
+                                   W, S, _stream())
+        _lib.check(rc, "etm_gae_truncated")
+        return out
     rc = lib.etm_gae(_ptr(rewards), _ptr(d), _ptr(values), _ptr(last_value), g32, gl32, _ptr(out), W, S, _stream())
     _lib.check(rc, "etm_gae")
     return out

@@ -68,6 +68,7 @@ def evaluation_config(config: dict, n_workers: int, worker_steps: int) -> dict:
     cfg = copy.deepcopy({k: v for k, v in config.items() if k != "evaluation"})
     cfg.update(n_workers=int(n_workers), worker_steps=int(worker_steps), n_mini_batch=1, worker_processes=False)
     cfg.pop("episode_bank_capacity", None)        # (sized for the training batch; the default never fills)
+    cfg.pop("bootstrap_truncated", None)          # (no GAE target is ever used here; the rollout still strips the two info keys)
     if cfg["environment"].get("type") != "Synthetic":
         cfg["environment"]["vectorize"] = "serial"
     return cfg

@@ -17,6 +17,10 @@ for the GPU:
   and gradient clipping (:310-311) -- the division by the world size rides in the clip coefficient -- and merges advantage
   statistics so normalisation is over the global minibatch.
 
+* time-limit truncations (absent upstream; ``bootstrap_truncated: true``): an episode the environment reports as only cut is
+  bootstrapped from the value of its final observation -- records in ``_hand_over_episodes``, one batched pass after the rollout
+  (``_bootstrap_pass``), the select form of the GAE kernel.
+
 There is no CPU path: constructing the trainer without a HIP device raises.
 """
 import os
@@ -130,6 +134,15 @@ def check_byte_observation_transport(config, env=None):
                          "set worker_processes: false (in-process environments keep the bytes), or let the environment emit float32")
 
 
+def check_truncation_transport(config, env=None):
+    """``worker_processes: true`` with ``bootstrap_truncated: true`` is refused, before any environment or process is created: the
+    workers' shared segment has no row for a final observation (environments/shm_env.py; a worker resets in place)."""
+    if env is None and config.get("worker_processes", False) and config.get("bootstrap_truncated", False):
+        raise ValueError("worker_processes: true does not carry bootstrap_truncated: true (the shared segment has no row for a final "
+                         "observation): set worker_processes: false (in-process environments hand it over in their info), or leave "
+                         "bootstrap_truncated off")
+
+
 def check_evaluation_config(config, world: int = 1):
     """The optional ``evaluation`` section (interval, episodes_per_worker, n_workers, deterministic, seed, worker_steps) -> a dict with
     the defaults filled in, or None when the section is absent (never evaluate, allocate nothing).  ``evaluation.interval`` in a
@@ -186,6 +199,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         check_kernel_shapes(t)
         check_box_policy(config)
         check_byte_observation_transport(config, env)
+        check_truncation_transport(config, env)
         check_evaluation_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         self.writer = _make_writer(run_id) if tensorboard else _NullWriter()
 
@@ -388,6 +402,16 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         self._lv = lv = ops.ReplayAfterWarmup(self._last_value_now, device, what="get_last_value")
         lv.rows, lv.obs = torch.empty((W, L), dtype=torch.int64, device=device), torch.empty_like(self._obs_dev)
         lv.out = torch.empty(W, dtype=torch.float32, device=device)
+        # bootstrap_truncated: the value of the observation after every time-limit cut of the rollout (_bootstrap_pass), W records per
+        # replay on fixed-address operands of get_last_value's shape; nothing is allocated without the key
+        self._bootstrap = bool(config.get("bootstrap_truncated", False))
+        self._truncations = []            # (w, t, slot, s, final observation) of the running rollout
+        self.last_truncations = []        # (w, t, slot, s) of the last rollout
+        if self._bootstrap:
+            self._bs = bs = ops.ReplayAfterWarmup(self._bootstrap_chunk_now, device, what="bootstrap pass")
+            bs.obs, bs.rows, bs.pidx = torch.empty_like(self._obs_dev), torch.empty_like(lv.rows), torch.empty_like(lv.rows)
+            bs.slot, bs.s = torch.zeros(W, dtype=torch.int64, device=device), torch.zeros(W, dtype=torch.int64, device=device)
+            bs.out = torch.empty(W, dtype=torch.float32, device=device)
 
         # worker groups: the full-width group (eager path, single-group graph path) aliases the buffers above; the pipelined
         # groups own what cannot be a contiguous slice of them.  WorkerGroup reads from this object, so all of these exist by now:
@@ -516,6 +540,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         """Everything before step 0: episode slots, K/V cache and weight copies, the draw tables, the captured graphs (first rollout)
         and with them the plan, the streams, the rows of observation 0.  -> (plan, the groups that run)."""
         self.buffer.begin_rollout(self._slot_dev)
+        self._truncations = []
         self.worker_episode_slot[:] = np.arange(self.num_workers)
         self._slot_dev.copy_(self._slot_pin, non_blocking=True)
         if self._use_kv_cache:
@@ -654,8 +679,20 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         buf, S = self.buffer, self.config["worker_steps"]
         for wl in np.flatnonzero(dones):
             w = g.lo + int(wl)
+            info = infos[wl]
+            if info is not None and ("truncated" in info or "final_observation" in info):
+                # a time-limit cut (environments/vec_env.py): with bootstrap_truncated remember where it happened -- the episode's
+                # slot and length, before either is replaced -- and the observation after it; key on or off, the episode infos never carry the two keys
+                if self._bootstrap and info.get("truncated"):
+                    if info.get("final_observation") is None:
+                        raise RuntimeError("bootstrap_truncated: a truncated episode's info carries no final_observation "
+                                           "(environments/vec_env.py: the vectorised front-end stores it before it resets)")
+                    self._truncations.append((w, int(t), int(self.worker_episode_slot[w]), int(self.worker_current_episode_step[w]),
+                                              info["final_observation"]))
+                    buf.truncated[w, t] = True
+                info = {k: v for k, v in info.items() if k not in ("truncated", "final_observation")}
             self.worker_current_episode_step[w] = 0
-            episode_infos.append(infos[wl])
+            episode_infos.append(info)
             slot = buf.open_episode()                  # fresh zero memory for the next episode (upstream :208-213)
             self.worker_episode_slot[w] = slot
             if t < S - 1:
@@ -690,6 +727,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             getattr(buf, name).copy_(stage.transpose(0, 1))
         if plan.direct_rows:
             self._stage_read.record(main)          # the next rollout's host writes into the staging array wait for this
+        if self._bootstrap:                        # (after the staging copies: buf.memory_indices is final)
+            self._bootstrap_pass()
         buf.calc_advantages(self.get_last_value(), self.config["gamma"], self.config["lamda"])
         self.last_update_timing.update(env_s=timing[0], wait_s=timing[1], launch_s=timing[2])
 
@@ -976,6 +1015,53 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             spec = WindowSpec.from_bank(self.buffer.bank, self._slot_dev, lv.rows, self.buffer.memory_indices[:, -1], mask)
             _, last_value, _ = self.model.forward_logits(lv.obs, spec, want_items=False)
             lv.out.copy_(last_value)
+
+    def _bootstrap_pass(self):
+        """bootstrap_truncated: the value of the final observation of every episode the rollout saw cut at a time limit -> its
+        element of ``buffer.bootstrap_values``, with get_last_value's window rule applied where the cut happened: rows
+        [clip(s - L, 0), +L) of the episode's slot, mask row clip(s, 0, L - 1), positional indices of the episode's last stored step
+        (s = the episode's length) -- what get_last_value would have returned had the rollout ended there.  No record: no launch."""
+        recs, self._truncations = self._truncations, []
+        self.last_truncations = [r[:4] for r in recs]
+        if not recs:
+            return
+        # W records per execution -- get_last_value's shape: the same kernels and GEMM solutions every update, however many records
+        # there are (one call over all of them meets new GEMM shapes at every new count), and get_last_value's bits
+        W, bs = self.num_workers, self._bs
+        n, w, t, operands = self._bootstrap_operands(recs, W)
+        bs.enabled = bool(self.config.get("hip_graph_rollout", True)) and self.buffer.address_captured
+        with torch.no_grad():
+            values = torch.empty(w.numel(), dtype=torch.float32, device=self.device)
+            for lo in range(0, w.numel(), W):
+                for dst, src in zip((bs.obs, bs.slot, bs.rows, bs.pidx, bs.s), operands):
+                    dst.copy_(src[lo: lo + W])
+                bs()
+                values[lo: lo + W] = bs.out
+            self.buffer.bootstrap_values[w[:n], t[:n]] = values[:n]
+
+    def _bootstrap_operands(self, recs, chunk):
+        """The records as device operands of ``_bootstrap_forward``, filled up to a multiple of ``chunk`` by repeating the last chunk's
+        first record -> (number of records, w, t, (obs, slot, rows, pidx, s))."""
+        L, dev, n = self.memory_length, self.device, len(recs)
+        idx = list(range(n)) + [n - (n % chunk)] * (-n % chunk)
+        meta = torch.tensor([recs[i][:4] for i in idx], dtype=torch.int64).to(dev)      # (w, t, slot, s)
+        obs = torch.from_numpy(np.stack([np.asarray(recs[i][4]) for i in idx])).to(dev)
+        if obs.dtype != self.observation_dtype:
+            obs = obs.to(self.observation_dtype)
+        w, t, slot, s = meta.unbind(1)
+        rows = torch.clamp(s - L, min=0).unsqueeze(1) + torch.arange(L, dtype=torch.int64, device=dev).unsqueeze(0)
+        return n, w, t, (obs, slot, rows, self.buffer.memory_indices[w, t], s)
+
+    def _bootstrap_forward(self, obs, slot, rows, pidx, s):
+        mask = self._mask_table[torch.clamp(s, 0, self.memory_length - 1)]
+        spec = WindowSpec.from_bank(self.buffer.bank, slot, rows, pidx, mask)
+        return self.model.forward_logits(obs, spec, want_items=False)[1]
+
+    def _bootstrap_chunk_now(self):
+        """One chunk of the bootstrap pass on its fixed-address operands ``_bs.obs / .slot / .rows / .pidx / .s`` -> ``.out``."""
+        bs = self._bs
+        with torch.no_grad():
+            bs.out.copy_(self._bootstrap_forward(bs.obs, bs.slot, bs.rows, bs.pidx, bs.s))
 
     # ------------------------------------------------------------------ optimisation
     def _train_epochs(self, learning_rate: float, clip_range: float, beta: float, perms=None):

@@ -25,7 +25,9 @@ def create_env(config: dict, render: bool = False, worker_id: int = 0):
         # ``environment.seed`` (optional): worker w draws from its own stream seed + w, so a run -- and an evaluation, whose
         # workers start at another id -- can be repeated; absent: unseeded, as ever
         seed = int(config["seed"]) + int(worker_id) if config.get("seed") is not None else None
-        return PocMemoryEnv(glob=False, freeze=True, max_episode_steps=32, seed=seed)
+        # ``environment.report_truncation`` (optional): time-limit cuts carry "truncated": True in their info (bootstrap_truncated)
+        return PocMemoryEnv(glob=False, freeze=True, max_episode_steps=32, seed=seed,
+                            report_truncation=bool(config.get("report_truncation", False)))
     raise ImportError(f"environment type {kind!r} needs its simulator package (gym / gym-minigrid / memory-gym), which is "
                       "outside this build; use type 'Synthetic' with the same observation shape for throughput runs")
 

@@ -36,7 +36,7 @@ extern "C" {
 #define ETM_ERCCL_BASE 100000 /* ETM_ERCCL_BASE + ncclResult_t: an RCCL call failed */
 
 /* ABI version of this header (bumped on any signature change, and when the meaning of an argument widens: 52 = the greedy
- * sentinel of the `uniforms` tables). */
+ * sentinel of the `uniforms` tables; 53 = + etm_gae_truncated). */
 int etm_abi_version(void);
 
 /* Human-readable name for a negative ETM_E* code or a hipError_t. Static storage. */
@@ -832,6 +832,16 @@ int etm_rollout_drive(const etm_rollout_group *groups, int G, int t_first, int S
  */
 int etm_gae(const float *rewards, const uint8_t *dones, const float *values, const float *last_value,
             float gamma, float gamma_lambda, float *advantages, int W, int S, void *stream);
+/* Time-limit truncations (ABI 53): the same scan with the next value of a step taken from elsewhere where its episode was only CUT.
+ *   truncated [W,S] one byte each, meaningful only where dones is set; boot [W,S] fp32, both laid out like the other arrays
+ *     next  = truncated[w,t] ? boot[w,t] : v_{t+1} * (1 - done_t)      (v_S = last_value)
+ *     delta = (r_t + gamma * next) - v_t
+ *     la    = delta + gamma_lambda * (la * (1 - done_t))
+ * in etm_gae's operation order without FMA contraction.  A select, not arithmetic on boot: elements of boot whose flag is clear may
+ * hold anything (NaN included) and influence no output; the kernel loads boot only around set flags.  The running advantage is cut
+ * at every done, truncated or not.  With every flag clear the result is etm_gae's, bit for bit. */
+int etm_gae_truncated(const float *rewards, const uint8_t *dones, const uint8_t *truncated, const float *values, const float *boot,
+                      const float *last_value, float gamma, float gamma_lambda, float *advantages, int W, int S, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Kernel #3: PPO clipped-surrogate + clipped value + entropy loss, forward and backward in one pass.
