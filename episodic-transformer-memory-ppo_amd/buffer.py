@@ -16,11 +16,16 @@ the storage redesigned for the MI355X path:
 * ``bootstrap_truncated: true`` (absent upstream): ``truncated`` [W, S] marks the steps whose episode was only cut at a time limit,
   ``bootstrap_values`` [W, S] holds the value of the observation after the cut; GAE (``etm_gae_truncated``) takes the next value of
   such a step from there instead of 0.  Neither is allocated without the key.
+* ``normalize_rewards`` (absent upstream): ``calc_advantages`` scales the uploaded rewards by the running spread of the discounted
+  return (``etm_return_scale``) into ``rewards_scaled`` [W, S], which GAE reads; ``rewards`` keeps the raw values.  The running triple
+  ``ret_stats`` and the per-worker returns ``ret_carry`` are float64 device arrays that live as long as the buffer (trainer state: not
+  in the checkpoint).  Nothing is allocated without the key.
 """
 import numpy as np
 import torch
 
 from etm import ops
+from utils import normalization_section
 
 
 class Buffer:
@@ -59,6 +64,16 @@ class Buffer:
             self.truncated = self._truncated_host.numpy()
             self.truncated_dev = torch.zeros((W, S), dtype=torch.bool, device=dev)
             self.bootstrap_values = torch.zeros((W, S), dtype=torch.float32, device=dev)
+
+        # return-based reward scaling (normalize_rewards): None without the key
+        self.return_norm = normalization_section(config, "normalize_rewards")
+        self.rewards_scaled = self.ret_carry = self.ret_stats = self.return_scale = None
+        if self.return_norm is not None:
+            self.rewards_scaled = torch.zeros((W, S), dtype=torch.float32, device=dev)
+            self.ret_carry = torch.zeros(W, dtype=torch.float64, device=dev)
+            self.ret_stats = torch.zeros(3, dtype=torch.float64, device=dev)
+            self._ret_ws = ops.return_scale_workspace(W, dev)
+            self.return_scale = self._ret_ws[:4].view(torch.float32)       # (the scale of the last call; 0 before the first)
 
         # (Box: the raw float actions [W, S, A] and one joint log-prob per sample)
         self.actions = torch.zeros((W, S, B), dtype=torch.float32 if continuous else torch.long, device=dev)
@@ -184,8 +199,14 @@ class Buffer:
         if self.truncated is not None:
             self.truncated_dev.copy_(self._truncated_host, non_blocking=True)
         self._mark_host_arrays_uploaded()
+        rewards = self.rewards_dev
+        if self.return_norm is not None:
+            # the rollout's returns continue from ret_carry and join the running triple; the rewards GAE reads are scaled with the
+            # triple that already includes this rollout
+            rewards, _ = ops.return_scale(self.rewards_dev, self.dones_dev, self.ret_carry, self.ret_stats, gamma, self.return_norm["epsilon"],
+                                          self.return_norm["clip"], out=self.rewards_scaled, ws=self._ret_ws)
         if self.truncated is not None:
-            ops.gae(self.rewards_dev, self.dones_dev, self.values, last_value.detach(), gamma, lamda, out=self.advantages,
+            ops.gae(rewards, self.dones_dev, self.values, last_value.detach(), gamma, lamda, out=self.advantages,
                     truncated=self.truncated_dev, boot=self.bootstrap_values)
             return
-        ops.gae(self.rewards_dev, self.dones_dev, self.values, last_value.detach(), gamma, lamda, out=self.advantages)
+        ops.gae(rewards, self.dones_dev, self.values, last_value.detach(), gamma, lamda, out=self.advantages)

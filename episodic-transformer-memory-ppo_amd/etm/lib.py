@@ -7,7 +7,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: torch ships its ow
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libetm_hip.so")     # (diagnostic tools that load another build assign this before load())
-ABI_VERSION = 53
+ABI_VERSION = 54
 
 _lib = None
 
@@ -147,6 +147,12 @@ SIGNATURES = {
     "etm_adamw_clip": (_I, [_P, _P, _P, _P, _L, _P, _I, _P, _P, _D, _D, _D, _D, _F, _F, _P, _P]),
     "etm_gae": (_I, [_P, _P, _P, _P, _F, _F, _P, _I, _I, _P]),
     "etm_gae_truncated": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _P, _I, _I, _P]),
+    "etm_obs_stats_supported": (_I, [_I]),
+    "etm_obs_stats_workspace_bytes": (_L, [_I, _I]),
+    "etm_obs_stats_update": (_I, [_P, _I, _I, _P, _P, _P, _D, _P, _L, _P]),
+    "etm_obs_normalize": (_I, [_P, _P, _P, _P, _F, _P, _L, _I, _P]),
+    "etm_return_scale_workspace_bytes": (_L, [_I]),
+    "etm_return_scale": (_I, [_P, _P, _P, _P, _D, _D, _F, _P, _I, _I, _P, _L, _P]),
     "etm_adv_stats": (_I, [_P, _I, _P, _P]),
     "etm_adv_stats_workspace_bytes": (_L, [_I]),
     "etm_adv_stats_ws": (_I, [_P, _I, _P, _P, _L, _P]),

@@ -1906,6 +1906,105 @@ def gae(rewards, dones, values, last_value, gamma, lamda, out=None, truncated=No
     return out
 
 
+def obs_stats_supported(features) -> bool:
+    """Whether ``obs_stats_update`` takes rows of ``features`` floats (etm_obs_stats_supported: 1 to 1024)."""
+    return bool(_lib.load().etm_obs_stats_supported(int(features)))
+
+
+def _f64c(t, name, shape):
+    if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise TypeError(f"{name} must be a contiguous float64 tensor of shape {tuple(shape)}")
+    return t
+
+
+def obs_stats_update(x, stats, mean, rstd, epsilon):
+    """Merge the rows of ``x`` [R, F] float32 into the running per-feature triple ``stats`` [3, F] float64 (count, mean, M2) and
+    refresh the fp32 table ``mean`` [F], ``rstd`` [F] = 1 / sqrt(M2 / count + epsilon) -- all three IN PLACE (etm_obs_stats_update:
+    chunks of 256 rows, merged in chunk order; deterministic)."""
+    lib = _lib.load()
+    _need_dev(x, stats, mean, rstd)
+    x = _f32c(x, "x")
+    if x.dim() != 2 or x.numel() == 0:
+        raise ValueError("obs_stats_update needs a non-empty [R, F] tensor")
+    R, F = x.shape
+    if not lib.etm_obs_stats_supported(F):
+        raise ValueError(f"obs_stats_update: {F} features (the kernel takes 1 to 1024)")
+    _f64c(stats, "stats", (3, F))
+    for t, name in ((mean, "mean"), (rstd, "rstd")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (F,):
+            raise TypeError(f"{name} must be a contiguous float32 tensor of shape ({F},)")
+    ws_bytes = lib.etm_obs_stats_workspace_bytes(R, F)
+    ws = workspace(ws_bytes, x.device, tag="obs_stats")
+    _lib.check(lib.etm_obs_stats_update(_ptr(x), R, F, _ptr(stats), _ptr(mean), _ptr(rstd), float(epsilon), _ptr(ws), ws_bytes, _stream()),
+               "etm_obs_stats_update")
+    return stats
+
+
+def obs_normalize(x, mean, rstd, clip, index=None, out=None):
+    """clamp((x - mean) * rstd, -clip, +clip) in float32, subtraction and product rounded separately (etm_obs_normalize); ``x``
+    [N, F] float32, or with ``index`` (int64 device tensor [n]) the rows x[index] -> [n, F].  One launch, capturable."""
+    lib = _lib.load()
+    _need_dev(x, mean, rstd, index, out)
+    x, mean, rstd = _f32c(x, "x"), _f32c(mean, "mean"), _f32c(rstd, "rstd")
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError("obs_normalize needs a non-empty tensor")
+    F = x.shape[-1]
+    if mean.numel() != F or rstd.numel() != F:
+        raise ValueError(f"obs_normalize: the table has {mean.numel()} / {rstd.numel()} entries, the rows {F}")
+    if index is not None:
+        if index.dtype != torch.int64 or x.dim() != 2:
+            raise TypeError("obs_normalize: index must be int64 and x [N, F]")
+        index = index.contiguous()
+        shape = (index.numel(), F)
+    else:
+        shape = tuple(x.shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise TypeError("obs_normalize: out must be a contiguous float32 tensor of the result's shape")
+    n = out.numel() // F
+    if n:
+        _lib.check(lib.etm_obs_normalize(_ptr(x), _ptr(index), _ptr(mean), _ptr(rstd), float(clip), _ptr(out), n, F, _stream()),
+                   "etm_obs_normalize")
+    return out
+
+
+def return_scale_workspace(W, device):
+    """A workspace of etm_return_scale for ``W`` workers, owned by the caller; its first float is the scale after a call."""
+    return torch.zeros(int(_lib.load().etm_return_scale_workspace_bytes(int(W))), dtype=torch.uint8, device=device)
+
+
+def return_scale(rewards, dones, ret_carry, stats, gamma, epsilon, clip, out=None, ws=None):
+    """Return-based reward scaling of one rollout (etm_return_scale): the per-worker discounted returns R_t = gamma R_{t-1} + r_t
+    (float64; R = 0 after a done) continue from ``ret_carry`` [W] float64 and are merged into the running triple ``stats`` [3] float64,
+    both IN PLACE; -> (scaled [W, S] float32 = clamp(rewards * scale, -clip, +clip), scale: a 1-element float32 view of ``ws``) with
+    scale = 1 / sqrt(M2 / count + epsilon) of the merged triple.  ``ws``: ``return_scale_workspace(W, device)`` (None: a fresh one)."""
+    lib = _lib.load()
+    _need_dev(rewards, dones, ret_carry, stats, out, ws)
+    rewards = _f32c(rewards, "rewards")
+    if rewards.dim() != 2 or rewards.numel() == 0:
+        raise ValueError("return_scale needs non-empty [W, S] rewards")
+    W, S = rewards.shape
+    if tuple(dones.shape) != (W, S):
+        raise ValueError(f"return_scale: dones must be [{W}, {S}], got {tuple(dones.shape)}")
+    d = dones.contiguous()
+    d = d.view(torch.uint8) if d.dtype == torch.bool else d.to(torch.uint8)
+    _f64c(ret_carry, "ret_carry", (W,))
+    _f64c(stats, "stats", (3,))
+    if out is None:
+        out = torch.empty_like(rewards)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (W, S) or not out.is_contiguous():
+        raise TypeError("return_scale: out must be a contiguous float32 tensor [W, S]")
+    ws_bytes = lib.etm_return_scale_workspace_bytes(W)
+    if ws is None:
+        ws = return_scale_workspace(W, rewards.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < ws_bytes:
+        raise TypeError("return_scale: ws must come from return_scale_workspace(W, device)")
+    _lib.check(lib.etm_return_scale(_ptr(rewards), _ptr(d), _ptr(ret_carry), _ptr(stats), float(gamma), float(epsilon), float(clip),
+                                    _ptr(out), W, S, _ptr(ws), ws.numel(), _stream()), "etm_return_scale")
+    return out, ws[:4].view(torch.float32)
+
+
 def adv_stats(adv):
     """(count, mean, M2) of a flat advantage vector as a 3-element device tensor."""
     lib = _lib.load()

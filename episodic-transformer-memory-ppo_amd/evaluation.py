@@ -3,7 +3,8 @@
 The evaluator is a SECOND rollout context next to the training one: a ``PPOTrainer`` built from a copy of the config with the
 evaluation's ``n_workers`` and a short ``worker_steps``, whose environments, episode steps and slots, bank, K|V cache, staging,
 draw tables and captured step graphs are its own.  The only thing it takes from the training context are the parameters: the
-flat parameter arena is copied (read only) before every evaluation.  Its draws come from its own ``torch.Generator`` and its
+flat parameter arena is copied (read only) before every evaluation -- and, with ``normalize_observations``, the model's running
+triple and frozen table, which are buffers outside the arena.  Its draws come from its own ``torch.Generator`` and its
 construction leaves torch's generators as it found them, so training with evaluations interleaved is bit-identical to training
 without them.
 
@@ -69,6 +70,7 @@ def evaluation_config(config: dict, n_workers: int, worker_steps: int) -> dict:
     cfg.update(n_workers=int(n_workers), worker_steps=int(worker_steps), n_mini_batch=1, worker_processes=False)
     cfg.pop("episode_bank_capacity", None)        # (sized for the training batch; the default never fills)
     cfg.pop("bootstrap_truncated", None)          # (no GAE target is ever used here; the rollout still strips the two info keys)
+    cfg.pop("normalize_rewards", None)            # (likewise; normalize_observations stays: the model reads its table)
     if cfg["environment"].get("type") != "Synthetic":
         cfg["environment"]["vectorize"] = "serial"
     return cfg
@@ -118,8 +120,9 @@ class Evaluator:
 
     DEFAULT_WORKER_STEPS = 64         # chunk length when neither the call nor ``evaluation.worker_steps`` gives one (capped by the config's)
 
-    def __init__(self, config: dict, device, run_id: str = "run", parameters=None):
+    def __init__(self, config: dict, device, run_id: str = "run", parameters=None, buffers=None):
         self.config, self.device, self.run_id, self.parameters = config, torch.device(device), run_id, parameters
+        self.buffers = buffers        # with ``parameters``: a callable -> {name: the training model's buffer} (the observation table)
         self.state_dict = None
         self.rollout = None
         self._key = None
@@ -165,6 +168,11 @@ class Evaluator:
                 raise RuntimeError("evaluation: the parameter arenas of the two rollout contexts differ")
             with torch.no_grad():
                 dst.copy_(src)
+                # ... and the model's observation-normalisation buffers (they are no part of the arena), in place
+                named = self.buffers() if self.buffers is not None else {}
+                for name, buf in ro.model.named_buffers():
+                    if name.startswith("obs_norm_"):
+                        buf.copy_(named[name])
         ro.restart(int(seed))
         # sampled evaluation: its own generator, seeded per call (never torch's global one)
         ro._draw_generator = None if deterministic else torch.Generator(device=self.device).manual_seed(int(seed))

@@ -15,11 +15,24 @@ from etm import ops
 from etm import lib as etm_lib
 from etm.ops import WindowSpec
 from transformer import Transformer
+from utils import normalization_section
+
+
+def obs_norm_table(stats, epsilon):
+    """The frozen fp32 table of a running triple ``stats`` [3, F] float64 (count, mean, M2) -> (mean [F], rstd [F]) float32:
+    rstd = 1 / sqrt(M2 / count + epsilon) with the population variance, formed in double and rounded once; the identity (0, 1)
+    where count == 0."""
+    count, mean, m2 = stats.double().unbind(0)
+    seen = count > 0
+    var = torch.where(seen, m2 / torch.where(seen, count, torch.ones_like(count)), torch.zeros_like(m2))
+    rstd = torch.where(seen, 1.0 / torch.sqrt(var + float(epsilon)), torch.ones_like(var))
+    return torch.where(seen, mean, torch.zeros_like(mean)).float(), rstd.float()
 
 
 class IndexedObservations:
     """A minibatch of visual observations as (all observations of the update in NHWC memory order [n, H, W, C], int64 row
-    indices): what ``buffer.samples_flat["obs"][mini_batch_indices]`` (buffer.py:84-91) denotes, without materialising it."""
+    indices): what ``buffer.samples_flat["obs"][mini_batch_indices]`` (buffer.py:84-91) denotes, without materialising it.  With
+    ``normalize_observations`` also vector observations [n, F]: the normalising launch gathers the rows."""
 
     def __init__(self, bank_nhwc, index):
         self.bank, self.index = bank_nhwc, index
@@ -62,6 +75,17 @@ class ActorCriticModel(nn.Module):
             feat = self.conv_out_size
         else:
             feat = self.observation_space_shape[0]
+        # normalize_observations (absent upstream): vector observations are standardised with a FROZEN fp32 table in front of lin_hidden,
+        # derived from a running float64 triple (count, mean, M2) per feature that the trainer merges once per update.  Triple and table
+        # are buffers (they travel in the state dict) and exist only with the key; they are updated in place, never rebound.
+        self.obs_norm = normalization_section(config, "normalize_observations")
+        if self.obs_norm is not None:
+            if self.visual:
+                raise ValueError("normalize_observations is for vector observations: image observations are already in [0, 1] "
+                                 "(remove the key, or flatten the observation)")
+            self.register_buffer("obs_norm_stats", torch.zeros((3, feat), dtype=torch.float64))
+            self.register_buffer("obs_norm_mean", torch.zeros(feat, dtype=torch.float32))
+            self.register_buffer("obs_norm_rstd", torch.ones(feat, dtype=torch.float32))
         self.lin_hidden = nn.Linear(feat, self.memory_layer_size)
         nn.init.orthogonal_(self.lin_hidden.weight, math.sqrt(2))
         self.transformer = Transformer(config["transformer"], self.memory_layer_size, self.max_episode_length)
@@ -351,6 +375,12 @@ class ActorCriticModel(nn.Module):
         layer's kernels read the bytes where they have a byte form (ops.conv_relu, ops.encoder_train) and ``ops.bytes_to_unit``
         expands them elsewhere; on the CPU it is ``obs.to(torch.float32) / 255``."""
         raw = obs.bank if isinstance(obs, IndexedObservations) else obs
+        if self.obs_norm is not None:
+            if raw.dtype != torch.float32:
+                raise ValueError("normalize_observations: a vector observation must be float32")
+            if obs_index is not None:
+                raise RuntimeError("obs_index needs the fused rollout encoder (visual observations, no grad)")
+            return ops.linear_relu(self.lin_hidden, self.normalize_observations(obs))
         if raw.dtype == torch.uint8:
             if not self.visual:
                 raise ValueError("uint8 observations are images (byte k = k / 255); a vector observation must be float32")
@@ -403,6 +433,28 @@ class ActorCriticModel(nn.Module):
             h = F.relu(self.conv3(h))
             h = h.reshape(h.shape[0], -1)
         return ops.linear_relu(self.lin_hidden, h)
+
+    def normalize_observations(self, obs):
+        """clamp((obs - mean) * rstd, -clip, +clip) in fp32 with the frozen table, subtraction and product rounded separately: the one
+        place every pass through the encoder standardises a vector observation (rollout step, get_last_value, the truncation
+        bootstrap, the training forward, evaluation, enjoy.py).  On the device one launch (ops.obs_normalize; the rows of an
+        ``IndexedObservations`` are gathered by it), on a CPU tensor the same expression in torch."""
+        index = None
+        if isinstance(obs, IndexedObservations):
+            obs, index = obs.bank, obs.index
+        clip = self.obs_norm["clip"]
+        if obs.is_cuda:
+            return ops.obs_normalize(obs, self.obs_norm_mean, self.obs_norm_rstd, clip, index=index)
+        if index is not None:
+            obs = obs.index_select(0, index)
+        return torch.clamp((obs - self.obs_norm_mean) * self.obs_norm_rstd, -clip, clip)
+
+    def refresh_obs_norm_table(self):
+        """The table from the triple, in place (after the triple was set by hand or loaded without its table)."""
+        mean, rstd = obs_norm_table(self.obs_norm_stats, self.obs_norm["epsilon"])
+        with torch.no_grad():
+            self.obs_norm_mean.copy_(mean)
+            self.obs_norm_rstd.copy_(rstd)
 
     def forward_state(self, obs, spec: WindowSpec, want_items=False):
         """Encoder + transformer: -> (h [N, D] in front of the hidden heads (model.py:100), new memory items or None)."""

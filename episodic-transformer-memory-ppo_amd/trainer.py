@@ -50,7 +50,7 @@ from etm import ops
 from etm.ops import WindowSpec
 from etm.optim import FlatAdamW
 from model import ActorCriticModel, IndexedObservations
-from utils import polynomial_decay, process_episode_info
+from utils import normalization_section, polynomial_decay, process_episode_info
 from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
 from trainer_parts import _DataParallelStep, _NativeRolloutDrive, _RunOutputs
 
@@ -166,6 +166,28 @@ def check_evaluation_config(config, world: int = 1):
     return out
 
 
+def check_normalization_config(config, world: int = 1, observation_shape=None, observation_dtype=None):
+    """The optional keys ``normalize_observations`` and ``normalize_rewards`` (each ``true`` or {clip, epsilon}) -> {"observations":
+    section or None, "rewards": section or None} with the defaults filled in.  Refused, each before anything is allocated: unknown
+    sub-keys, ``clip <= 0`` or ``epsilon <= 0`` (utils.normalization_section); either key in a data-parallel run (``world`` > 1: the
+    ranks' statistics would have to be merged, which this build does not do); ``normalize_observations`` with image or uint8
+    observations (``observation_shape`` / ``observation_dtype``, once the environment is known) or with more features than the
+    statistics kernel takes."""
+    out = {"observations": normalization_section(config, "normalize_observations"), "rewards": normalization_section(config, "normalize_rewards")}
+    on = [k for k, key in (("normalize_observations", "observations"), ("normalize_rewards", "rewards")) if out[key] is not None]
+    if on and world > 1:
+        raise ValueError(f"{' / '.join(on)} in a data-parallel run: every rank would keep statistics of its own workers only (merging "
+                         "them over the ranks is not built); remove the key(s), or train on one device")
+    if out["observations"] is not None and observation_shape is not None:
+        if len(tuple(observation_shape)) != 1 or observation_dtype == torch.uint8:
+            raise ValueError(f"normalize_observations with image / uint8 observations of shape {tuple(observation_shape)}: they are already "
+                             "in [0, 1] (byte k = k / 255); remove the key -- it is for float32 vector observations")
+        if not ops.obs_stats_supported(int(observation_shape[0])):
+            raise ValueError(f"normalize_observations with {int(observation_shape[0])} features: the statistics kernel takes 1 to 1024; "
+                             "remove the key or reduce the observation")
+    return out
+
+
 def time_major(table, src):
     """The host table ``src`` [W, S(, B)] in the layout and type of the fixed-address device table ``table`` [S, W(, B)]."""
     x = torch.as_tensor(np.asarray(src), dtype=table.dtype)
@@ -201,6 +223,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         check_byte_observation_transport(config, env)
         check_truncation_transport(config, env)
         check_evaluation_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
+        check_normalization_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         self.writer = _make_writer(run_id) if tensorboard else _NullWriter()
 
         # environments (batched front-end over the upstream per-worker protocol)
@@ -269,6 +292,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         if self.observation_dtype == torch.uint8:
             if len(obs_shape) < 2:
                 raise ValueError("uint8 observations are images (byte k = k / 255); a vector observation must be float32")
+        check_normalization_config(config, 1 if dp is None else int(getattr(dp, "world", 1)), obs_shape, self.observation_dtype)
         # one branch per action dimension, from the environment (environments.action_space_shape: Discrete(n) -> (n,), MultiDiscrete
         # -> nvec); Discrete is upstream's single branch (trainer.py:47)
         self.action_space_shape = tuple(int(a) for a in getattr(self.env, "action_space_shape", None) or (self.env.num_actions,))
@@ -434,6 +458,40 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
     def memory(self):
         """[W, T, blocks, D] live episodic memory of every worker (upstream ``self.memory``); a gathered copy."""
         return self.buffer.bank.index_select(0, self._slot_dev)
+
+    @property
+    def obs_norm(self):
+        """``normalize_observations``: a read-only view {"clip", "epsilon", "stats" [3, F] float64 (count, mean, M2), "mean" [F],
+        "rstd" [F]} of the model's running triple and frozen table (the tensors are the model's buffers); None without the key."""
+        m = self.model
+        if m.obs_norm is None:
+            return None
+        return dict(m.obs_norm, stats=m.obs_norm_stats, mean=m.obs_norm_mean, rstd=m.obs_norm_rstd)
+
+    @property
+    def return_norm(self):
+        """``normalize_rewards``: a read-only view {"clip", "epsilon", "stats" [3] float64 (count, mean, M2 of the discounted returns),
+        "carry" [W] float64, "scale" [1] float32 (of the last rollout), "scaled" [W, S] (the rewards GAE read)}; None without the key.
+        Trainer state: it is not stored in the checkpoint (there is no resume of training)."""
+        b = self.buffer
+        if b.return_norm is None:
+            return None
+        return dict(b.return_norm, stats=b.ret_stats, carry=b.ret_carry, scale=b.return_scale, scaled=b.rewards_scaled)
+
+    def _training_observations(self):
+        """What the captured step reads its observations from, when not from the gathered minibatch fields: the NHWC copy of visual
+        observations, or -- ``normalize_observations`` -- the buffer's raw vector rows (the normalising launch gathers them)."""
+        nhwc = self._observations_channels_last()
+        if nhwc is None and self.model.obs_norm is not None:
+            return self.buffer.samples_flat["obs"]
+        return nhwc
+
+    def _update_obs_norm(self):
+        """After the last minibatch of an update: merge the update's W * S raw observations into the running triple and refresh the
+        frozen table, in place (the captured graphs hold the addresses) -- the next rollout and optimisation run on the new table."""
+        m = self.model
+        with torch.no_grad():
+            ops.obs_stats_update(self.buffer.samples_flat["obs"], m.obs_norm_stats, m.obs_norm_mean, m.obs_norm_rstd, m.obs_norm["epsilon"])
 
     # ------------------------------------------------------------------ training loop
     def run_training(self) -> None:
@@ -1072,7 +1130,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         # block, minibatch and epoch inside the kernels (bit-identical sums; halves the kernels' window-row loads)
         with torch.no_grad():
             self._bank_pos = self._bank_with_positions()
-            self._obs_train = self._observations_channels_last()
+            self._obs_train = self._training_observations()
         mbs = self.buffer.batch_size // self.buffer.n_mini_batches
         # sort_minibatch (default on): the samples of a minibatch in ascending flat (worker, step) order.  The minibatch is the
         # same SET (every loss term is a mean over it; only summation order changes), but neighbouring samples then share most of
@@ -1122,6 +1180,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
                 stats.append(self._train_mini_batch(mini_batch, learning_rate, clip_range, beta))
                 if monitor:
                     norms.append(self._grad_group_norms())
+        if self.model.obs_norm is not None:
+            self._update_obs_norm()
         # the only host sync of the optimisation phase
         train_info = (self._tg_stats_tab[:row] if tables else torch.stack(stats)).cpu().numpy()
         self._bank_pos = self._row_stats = None
@@ -1342,7 +1402,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             idx = idx.sort().values
         with torch.no_grad():
             self._bank_pos = self._bank_with_positions()
-            self._obs_train = self._observations_channels_last()
+            self._obs_train = self._training_observations()
         if self._use_train_graph:
             self._dyn.copy_(torch.tensor([clip_range, beta], dtype=torch.float64))
             self._sched_host[1:] = [clip_range, beta]
@@ -1485,7 +1545,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         from evaluation import Evaluator, evaluation_defaults
         ev = evaluation_defaults(self.config)
         if self._evaluator is None:
-            self._evaluator = Evaluator(self.config, self.device, self.run_id, parameters=lambda: self.optimizer.flat_params)
+            self._evaluator = Evaluator(self.config, self.device, self.run_id, parameters=lambda: self.optimizer.flat_params,
+                                        buffers=lambda: dict(self.model.named_buffers()))
         return self._evaluator.run(episodes_per_worker=int(episodes_per_worker), n_workers=n_workers, deterministic=bool(deterministic),
                                    seed=ev["seed"] if seed is None else int(seed),
                                    worker_steps=ev["worker_steps"] if worker_steps is None else int(worker_steps))

@@ -206,6 +206,12 @@ class _RunOutputs:
         self.writer.add_scalar("other/kl", training_stats[4], update)
         self.writer.add_scalar("other/clip_fraction", training_stats[5], update)
         self.writer.add_scalar("other/env_steps_per_second", steps_per_s, update)
+        if self.buffer.return_norm is not None:          # (the scale the last rollout's rewards were multiplied with)
+            self.writer.add_scalar("training/return_scale", float(self.buffer.return_scale.item()), update)
+        if self.model.obs_norm is not None:              # (the spread of the frozen table the next rollout runs on)
+            lo, hi = torch.aminmax(self.model.obs_norm_rstd)
+            self.writer.add_scalar("training/obs_norm_rstd_min", float(lo.item()), update)
+            self.writer.add_scalar("training/obs_norm_rstd_max", float(hi.item()), update)
 
     def _write_evaluation_summary(self, update, evaluation) -> None:
         """``evaluation/<key>`` scalars of one periodic evaluation (PPOTrainer.evaluate's dict) and one printed line."""

@@ -1,5 +1,5 @@
 """Helpers with the upstream names (utils.py): create_env, polynomial_decay, batched_index_select,
-process_episode_info, Module."""
+process_episode_info, Module; normalization_section reads this build's two normalisation keys."""
 import numpy as np
 import torch
 from torch import nn
@@ -63,6 +63,27 @@ def process_episode_info(episode_info: list) -> dict:
         result[key + "_mean"] = np.mean(vals)
         result[key + "_std"] = np.std(vals)
     return result
+
+
+def normalization_section(config: dict, key: str):
+    """The optional section ``key`` (``normalize_observations`` / ``normalize_rewards``) of ``config`` -> {"clip", "epsilon"} with the
+    defaults (10, 1e-8) filled in, or None when the key is absent or false.  ``true`` stands for the defaults."""
+    sec = config.get(key)
+    if sec is None or sec is False:
+        return None
+    if sec is True:
+        sec = {}
+    if not isinstance(sec, dict):
+        raise ValueError(f"{key}: expected true or a section with clip / epsilon, got {sec!r}")
+    unknown = sorted(set(sec) - {"clip", "epsilon"})
+    if unknown:
+        raise ValueError(f"{key}: unknown keys {unknown} (known: ['clip', 'epsilon']); remove them")
+    out = dict(clip=float(sec.get("clip", 10.0)), epsilon=float(sec.get("epsilon", 1.0e-8)))
+    if not out["clip"] > 0 or not np.isfinite(out["clip"]):
+        raise ValueError(f"{key}.clip must be a positive number, got {sec.get('clip')!r}; leave it out for the default 10")
+    if not out["epsilon"] > 0 or not np.isfinite(out["epsilon"]):
+        raise ValueError(f"{key}.epsilon must be a positive number, got {sec.get('epsilon')!r}; leave it out for the default 1e-8")
+    return out
 
 
 class Module(nn.Module):

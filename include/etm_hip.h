@@ -36,7 +36,7 @@ extern "C" {
 #define ETM_ERCCL_BASE 100000 /* ETM_ERCCL_BASE + ncclResult_t: an RCCL call failed */
 
 /* ABI version of this header (bumped on any signature change, and when the meaning of an argument widens: 52 = the greedy
- * sentinel of the `uniforms` tables; 53 = + etm_gae_truncated). */
+ * sentinel of the `uniforms` tables; 53 = + etm_gae_truncated; 54 = + the running-normalisation entries). */
 int etm_abi_version(void);
 
 /* Human-readable name for a negative ETM_E* code or a hipError_t. Static storage. */
@@ -842,6 +842,41 @@ int etm_gae(const float *rewards, const uint8_t *dones, const float *values, con
  * at every done, truncated or not.  With every flag clear the result is etm_gae's, bit for bit. */
 int etm_gae_truncated(const float *rewards, const uint8_t *dones, const uint8_t *truncated, const float *values, const float *boot,
                       const float *last_value, float gamma, float gamma_lambda, float *advantages, int W, int S, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Running normalisation (ABI 54; absent upstream -- the `VecNormalize` pair of PPO libraries: observations standardised with running
+ * per-feature statistics, rewards divided by a running estimate of the spread of the discounted return).  Statistics are
+ * (count, mean, M2 = sum (x - mean)^2) triples in DOUBLE, combined with the pairwise update of Chan et al. in an order fixed by the
+ * algorithm (never by the grid): no floating-point atomics, identical bits from run to run.  Every entry is a sequence of ordinary
+ * launches on `stream`; no workgroup waits for another inside a kernel.
+ *
+ * etm_obs_stats_update: stands for the host-side `RunningMeanStd.update(batch)` over the rows of one update.
+ *   x [R,F] fp32 dense; stats [3,F] doubles (count row, mean row, M2 row) IN/OUT, merged in place with the R rows;
+ *   mean [F], rstd [F] fp32 OUT: the frozen table, mean = fp32(mean), rstd = fp32(1 / sqrt(M2 / count + epsilon)) (population
+ *   variance; formed in double, rounded once).  Rows are cut into chunks of 256 (a property of the algorithm); launch 1 forms one
+ *   triple per (chunk, feature), launch 2 combines them in chunk order, merges into `stats` and writes the table.
+ *   workspace: etm_obs_stats_workspace_bytes(R, F) bytes, 8-byte aligned.  etm_obs_stats_supported(F): 1 <= F <= 1024.
+ * etm_obs_normalize: stands for `np.clip((obs - mean) / sqrt(var + epsilon), -clip, clip)` in front of the encoder.
+ *   out[n][f] = clamp((x[(index ? index[n] : n)][f] - mean[f]) * rstd[f], -clip, +clip), n < N, f < F, in fp32 with the subtraction and
+ *   the product rounded separately (no FMA contraction); NaN stays NaN.  index: optional device int64 [N] row gather (a minibatch
+ *   taken through indices costs no extra pass).  out dense [N,F].  One launch, capturable.
+ * etm_return_scale: stands for the return-based reward scaling of `VecNormalize`, in batch form over one rollout.
+ *   rewards [W,S] fp32, dones [W,S] one byte each (the layout of etm_gae); ret_carry [W] doubles IN/OUT: the running discounted return
+ *   of every worker, R_t = gamma * R_{t-1} + r_t in double (product and sum rounded separately), R = 0 AFTER a step whose done is set;
+ *   stats [3] doubles IN/OUT: all W * S values R_t are merged into it; scale = fp32(1 / sqrt(M2 / count + epsilon)) of the MERGED
+ *   triple; scaled [W,S] fp32 OUT = clamp(r * scale, -clip, +clip) in fp32.  Launch 1: the per-worker scan (the shape of etm_gae's)
+ *   and one partial triple per workgroup of 16 workers; launch 2: the partials in a fixed order, the merge, the scale; launch 3: the
+ *   scaling.  workspace: etm_return_scale_workspace_bytes(W) bytes, 16-byte aligned; its first 4 bytes hold the fp32 scale after the call.
+ */
+int etm_obs_stats_supported(int F);
+int64_t etm_obs_stats_workspace_bytes(int R, int F);
+int etm_obs_stats_update(const float *x, int R, int F, double *stats, float *mean, float *rstd, double epsilon, void *workspace,
+                         int64_t workspace_bytes, void *stream);
+int etm_obs_normalize(const float *x, const int64_t *index, const float *mean, const float *rstd, float clip, float *out, int64_t N,
+                      int F, void *stream);
+int64_t etm_return_scale_workspace_bytes(int W);
+int etm_return_scale(const float *rewards, const uint8_t *dones, double *ret_carry, double *stats, double gamma, double epsilon,
+                     float clip, float *scaled, int W, int S, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Kernel #3: PPO clipped-surrogate + clipped value + entropy loss, forward and backward in one pass.
