@@ -21,6 +21,7 @@
 // summed in a fixed order through LDS: ((w0 + w2) + (w1 + w3)) -- deterministic, no atomics.
 #include "etm_common.h"
 #include "tail_jobs.h"
+#include "grouped_dw_tiles.h"
 
 namespace {
 constexpr int GD_MT = 3, GD_NT = 4;                 // 32-row tiles along Ma (96) and along Nb (128) per workgroup
@@ -42,35 +43,7 @@ struct GdParams {
 
 static_assert(sizeof(GdParams) <= 4096, "kernel arguments of one launch");
 
-// Workgroup b runs on XCD b % 8 (the dispatcher deals consecutive workgroups round the eight dies, each with an L2 of its own), and the
-// 9 - 12 tiles of one problem read the SAME two operands: dealt round the dies as they come, every tile pulls its operand columns
-// through its die's L2 by itself (PMC rounds 5 / 6: 397 MB fetched per launch against 226 MB of operands even without any sharing).  So
-// the tiles are renumbered: die x takes the contiguous run [x T / 8, (x + 1) T / 8) of the launch's tiles -- the tiles of a problem sit on
-// one die (two at a run's ends) and walk the sample rows together through its L2.  A bijection for every T (checked on the host for
-// T <= 2000); the few blocks of a die that has one workgroup more than its run has tiles take the tiles left over on other dies.
-__device__ __forceinline__ int gd_tile_of_block(int b, int n_tiles) {
-  const int x = b & 7, slot = b >> 3;
-  const int lo = (int)(((long long)x * n_tiles) >> 3), hi = (int)(((long long)(x + 1) * n_tiles) >> 3);      // this die's run
-  const int full = n_tiles >> 3;
-  const int wgs = full + (x < (n_tiles & 7) ? 1 : 0);        // workgroups the dispatcher gives die x
-  const int run = hi - lo;
-  if (slot < (run < wgs ? run : wgs)) return lo + slot;
-  int k = 0;                                                 // index of this block among the leftover blocks
-  for (int y = 0; y < x; ++y) {
-    const int wy = full + (y < (n_tiles & 7) ? 1 : 0), ry = (int)(((long long)(y + 1) * n_tiles) >> 3) - (int)(((long long)y * n_tiles) >> 3);
-    if (wy > ry) k += wy - ry;
-  }
-  k += slot - run;
-  for (int y = 0; y < 8; ++y) {
-    const int ly = (int)(((long long)y * n_tiles) >> 3), ry = (int)(((long long)(y + 1) * n_tiles) >> 3) - ly;
-    const int wy = full + (y < (n_tiles & 7) ? 1 : 0);
-    if (ry > wy) {
-      if (k < ry - wy) return ly + wy + k;
-      k -= ry - wy;
-    }
-  }
-  return b;                                                  // (not reached: leftover blocks and leftover tiles are equally many)
-}
+// (the workgroup -> tile map, gd_tile_of_block: grouped_dw_tiles.h -- one body for the kernels and for etm_grouped_dw_tile_map)
 
 typedef float f32x3 __attribute__((ext_vector_type(3)));
 
@@ -242,9 +215,24 @@ extern "C" int etm_grouped_dw_supported(int N, int Ma, int Nb, int lda, int ldb,
   if (N < 2 || Ma <= 0 || Nb <= 0 || Ma % GD_TM != 0 || Nb % GD_TN != 0) return 0;
   if (lda < Ma || ldb < Nb || ldc < Nb || lda % 4 != 0 || ldb % 4 != 0 || ldc % 4 != 0) return 0;
   if ((long long)(N + 2) * lda * 4 >= 0x7fffffffLL || (long long)(N + 2) * ldb * 4 >= 0x7fffffffLL) return 0;
+  // the loads a wave ISSUES reach further than its rows: whole pipeline rounds plus the GD_PD refills of the last one, two rows a
+  // k-step.  Their offsets are 32-bit too -- beyond the descriptor they read zeros, wrapped round they would land inside it again.
+  // (More than N + 2 rows only below N = 22: a bound on strides of tens of millions of floats.  Harm needs 2^32; the limit is 2^31
+  // so that va / vb, which are ints, never overflow.)
+  const int rows_w = ((N + 3) / 4 + 1) & ~1, ksteps = ((rows_w < N ? rows_w : N) + 1) >> 1;
+  const long long span = 2LL * GD_PD * ((ksteps + GD_PD - 1) / GD_PD + 1);
+  if (span * lda * 4 >= 0x7fffffffLL || span * ldb * 4 >= 0x7fffffffLL) return 0;
   return 1;
 }
 extern "C" int etm_grouped_dw_max_problems(void) { return GD_MAXP; }
+
+// out[b] = the tile that workgroup b of a launch with n_tiles tiles computes (gd_tile_of_block, the function the kernels call).  Host
+// only: no GPU call.
+extern "C" int etm_grouped_dw_tile_map(int n_tiles, int32_t *out) {
+  if (n_tiles <= 0 || !out) return ETM_EINVAL;
+  for (int b = 0; b < n_tiles; ++b) out[b] = gd_tile_of_block(b, n_tiles);
+  return 0;
+}
 
 // C[p] = A[p]^T B[p] for n_problems independent problems over the same N rows, one launch.  A / B / C: host arrays of device
 // pointers; dims: host array of 5 ints per problem (Ma, Nb, lda, ldb, ldc).  Every problem must satisfy etm_grouped_dw_supported;

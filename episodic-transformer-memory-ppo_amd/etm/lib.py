@@ -7,7 +7,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: torch ships its ow
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libetm_hip.so")     # (diagnostic tools that load another build assign this before load())
-ABI_VERSION = 54
+ABI_VERSION = 55
 
 _lib = None
 
@@ -141,6 +141,7 @@ SIGNATURES = {
     "etm_grouped_dw_supported": (_I, [_I, _I, _I, _I, _I, _I]),
     "etm_grouped_dw_max_problems": (_I, []),
     "etm_grouped_dw": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "etm_grouped_dw_tile_map": (_I, [_I, _P]),
     "etm_grouped_dw_tail_max_problems": (_I, []),
     "etm_grouped_dw_tail": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "etm_grad_sqnorm": (_I, [_P, _L, _P, _I, _P, _P]),

@@ -36,7 +36,7 @@ extern "C" {
 #define ETM_ERCCL_BASE 100000 /* ETM_ERCCL_BASE + ncclResult_t: an RCCL call failed */
 
 /* ABI version of this header (bumped on any signature change, and when the meaning of an argument widens: 52 = the greedy
- * sentinel of the `uniforms` tables; 53 = + etm_gae_truncated; 54 = + the running-normalisation entries). */
+ * sentinel of the `uniforms` tables; 53 = + etm_gae_truncated; 54 = + the running-normalisation entries; 55 = + etm_grouped_dw_tile_map). */
 int etm_abi_version(void);
 
 /* Human-readable name for a negative ETM_E* code or a hipError_t. Static storage. */
@@ -369,6 +369,12 @@ int etm_grouped_dw_supported(int N, int Ma, int Nb, int lda, int ldb, int ldc);
 int etm_grouped_dw_max_problems(void);
 int etm_grouped_dw(const float *const *A, const float *const *B, float *const *C, const int32_t *dims, int n_problems, int N,
                    void *stream);
+
+/* The workgroup -> tile map of both grouped launches (ABI 55): out[b] = the tile that workgroup b of a launch with n_tiles tiles
+ * computes, b < n_tiles -- die b % 8 takes the contiguous run [x T / 8, (x + 1) T / 8) of the tiles (csrc/grouped_dw_tiles.h).  The
+ * entry evaluates the function the kernels call (one body), on the host: no GPU call, so the map can be checked for every tile count
+ * (tests/test_grouped_dw_host.py).  ETM_EINVAL for n_tiles <= 0 or out == NULL. */
+int etm_grouped_dw_tile_map(int n_tiles, int32_t *out);
 
 /* The tail launch (ABI 50; DESIGN section 4 "The ends of the step"): etm_grouped_dw with the grouped column-sum reduction that ends a
  * backward pass on extra workgroups of the SAME launch, numbered after the tile workgroups -- it runs on the CUs the tiles leave
