@@ -19,7 +19,7 @@ the storage redesigned for the MI355X path:
 * ``normalize_rewards`` (absent upstream): ``calc_advantages`` scales the uploaded rewards by the running spread of the discounted
   return (``etm_return_scale``) into ``rewards_scaled`` [W, S], which GAE reads; ``rewards`` keeps the raw values.  The running triple
   ``ret_stats`` and the per-worker returns ``ret_carry`` are float64 device arrays that live as long as the buffer (trainer state: not
-  in the checkpoint).  Nothing is allocated without the key.
+  in the model file; the training checkpoint of ``PPOTrainer.save_checkpoint`` stores the triple).  Nothing is allocated without the key.
 """
 import numpy as np
 import torch

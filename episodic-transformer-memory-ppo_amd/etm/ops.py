@@ -2020,6 +2020,33 @@ def adv_stats(adv):
     return stats
 
 
+ARENA_DIGEST_PARTIALS = 1024
+
+
+def arena_digest_workspace(device, n_partial=ARENA_DIGEST_PARTIALS):
+    """Scratch of ``arena_digest`` (3 * n_partial 64-bit words), owned by the caller."""
+    return torch.zeros(3 * int(n_partial), dtype=torch.int64, device=device)
+
+
+def arena_digest(x, out=None, partial=None, n_partial=ARENA_DIGEST_PARTIALS):
+    """The four 64-bit words of etm_arena_digest over the contiguous float32 device tensor ``x`` taken as raw bits (fingerprint, number
+    of Inf / NaN words, bit pattern of the largest finite |x|, number of words) -> ``out`` [4] int64 on the device (the words are
+    unsigned: read them through ``.view(np.uint64)`` on the host; checkpoint.digest_numpy computes the same four).  Two launches on the
+    current stream; ``out`` and ``partial`` (``arena_digest_workspace``) are allocated when not given."""
+    lib = _lib.load()
+    _need_dev(x)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise TypeError("arena_digest needs a non-empty contiguous float32 tensor")
+    if out is None:
+        out = torch.zeros(4, dtype=torch.int64, device=x.device)
+    if partial is None:
+        partial = arena_digest_workspace(x.device, n_partial)
+    if partial.dtype != torch.int64 or partial.numel() < 3 * int(n_partial) or out.dtype != torch.int64 or out.numel() != 4:
+        raise TypeError("arena_digest: out is [4] int64, partial at least [3 * n_partial] int64")
+    _lib.check(lib.etm_arena_digest(_ptr(x), x.numel(), _ptr(partial), int(n_partial), _ptr(out), _stream()), "etm_arena_digest")
+    return out
+
+
 class _PpoLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, value, actions, old_logp, adv, old_value, stats3, branch, n_branches, clip, vf_coef, beta,

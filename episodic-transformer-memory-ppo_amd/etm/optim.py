@@ -67,3 +67,36 @@ class FlatAdamW:
                                       self.exp_avg_sq.data_ptr(), n, self.partial.data_ptr(), self.N_PARTIAL, self.lr_dev.data_ptr(),
                                       self.step_dev.data_ptr(), self.betas[0], self.betas[1], self.eps, self.weight_decay,
                                       float(max_grad_norm), float(grad_scale), self.total_norm.data_ptr(), st), "etm_adamw_clip")
+
+    # ------------------------------------------------------------------ checkpointing
+    _HYPER = ("betas", "eps", "weight_decay", "total", "padded")
+
+    def state_dict(self):
+        """Everything that continues the optimiser: both moment arenas as numpy arrays (padded length), the device step counter, the
+        learning rate (the python float ``lr_dev`` was last filled with), and the hyper-parameters and sizes ``load_state_dict`` checks."""
+        return {"exp_avg": self.exp_avg.cpu().numpy(), "exp_avg_sq": self.exp_avg_sq.cpu().numpy(), "step": int(self.step_dev.item()),
+                "lr": self._lr_host, "betas": [self.betas[0], self.betas[1]], "eps": self.eps,
+                "weight_decay": self.weight_decay, "total": int(self.total), "padded": int(self.flat_params.numel())}
+
+    def load_state_dict(self, state):
+        """Copies ``state`` (of ``state_dict``) INTO the existing arenas, ``step_dev`` and ``lr_dev`` -- no tensor is rebound: captured
+        graphs hold these addresses.  A different ``total`` / padded length or different hyper-parameters are refused by name."""
+        mine = {"betas": [self.betas[0], self.betas[1]], "eps": self.eps, "weight_decay": self.weight_decay, "total": int(self.total),
+                "padded": int(self.flat_params.numel())}
+        diff = [f"{k}: saved {state.get(k)!r}, this optimiser {mine[k]!r}" for k in self._HYPER
+                if (list(state[k]) if k == "betas" and k in state else state.get(k)) != mine[k]]
+        if diff:
+            raise ValueError("FlatAdamW.load_state_dict: the saved state does not fit this optimiser (" + "; ".join(diff) + ")")
+        import numpy as np
+        arenas = {}
+        for name in ("exp_avg", "exp_avg_sq"):
+            a = np.ascontiguousarray(state[name])
+            if a.dtype != np.float32 or a.shape != (mine["padded"],):
+                raise ValueError(f"FlatAdamW.load_state_dict: {name} is {a.dtype}{list(a.shape)}, expected float32[{mine['padded']}]")
+            arenas[name] = torch.from_numpy(a)
+        with torch.no_grad():
+            self.exp_avg.copy_(arenas["exp_avg"])
+            self.exp_avg_sq.copy_(arenas["exp_avg_sq"])
+            self.step_dev.fill_(int(state["step"]))
+            self.lr_dev.fill_(float(state["lr"]))
+        self._lr_host = float(state["lr"])              # (set_lr compares against this: it stays in step with lr_dev)

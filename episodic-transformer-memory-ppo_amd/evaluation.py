@@ -90,26 +90,9 @@ class _EvaluationRollout(PPOTrainer):
         super()._hand_over_episodes(g, t, dones, infos, episode_infos)
 
     def restart(self, first_worker_id: int):
-        """Fresh environments from ``first_worker_id`` on, every worker at step 0 of an empty episode in slot w."""
-        from environments.vec_env import make_vec_env
-        W, buf = self.num_workers, self.buffer
-        torch.cuda.synchronize(self.device)
-        self.env.close()
-        self.env = make_vec_env(self._env_cfg, W, first_worker_id, groups=self._env_groups)
-        parts = getattr(self.env, "parts", None)
-        self._group_all.env = self.env
-        if parts is not None and len(parts) == len(self._groups) > 1:
-            for g, part in zip(self._groups, parts):
-                g.env = part
-        ev = getattr(buf, "_host_arrays_uploaded", None)
-        if ev is not None:
-            ev.synchronize()
-        buf.bank[: buf.num_episodes].zero_()
-        buf.num_episodes = W
-        self.worker_current_episode_step[:] = 0
-        self.worker_episode_slot[:] = range(W)
-        self._ss_dev.copy_(self._ss_pin)
-        self.env.reset(out=self.obs)
+        """Fresh environments from ``first_worker_id`` on, every worker at step 0 of an empty episode in slot w (the trainer's
+        ``_restart_workers``, which ``restart_episodes`` runs on in training)."""
+        self._restart_workers(first_worker_id)
 
 
 class Evaluator:

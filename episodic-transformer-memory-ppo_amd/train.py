@@ -1,4 +1,4 @@
-"""Command line entry, same flags as upstream train.py (--config, --run-id, --cpu).
+"""Command line entry, same flags as upstream train.py (--config, --run-id, --cpu) and --resume PATH (continue from a training checkpoint).
 
     python train.py --config ./configs/synthetic_minigrid.yaml --run-id demo
 
@@ -26,6 +26,8 @@ def main():
     ap = argparse.ArgumentParser(description="PPO + TransformerXL episodic memory on MI355X")
     ap.add_argument("--config", default="./configs/poc_memory_env.yaml", help="Path to the yaml config file")
     ap.add_argument("--run-id", default="run", help="Tag for the tensorboard summary and the saved model")
+    ap.add_argument("--resume", default=None, metavar="PATH",
+                    help="Continue training from the checkpoint PATH (models/<run_id>.ckpt, written with checkpoint_interval in the config)")
     ap.add_argument("--cpu", action="store_true", help="(upstream flag) not available in this build: raises")
     args = ap.parse_args()
     config = YamlParser(args.config).get_config()
@@ -45,7 +47,7 @@ def main():
         dp = DataParallel(device)
         first_worker = dp.rank * config["n_workers"]
     trainer = PPOTrainer(config, run_id=args.run_id, device=device, dp=dp, first_worker_id=first_worker,
-                         tensorboard=(dp is None or dp.rank == 0))
+                         tensorboard=(dp is None or dp.rank == 0), resume=args.resume)
     trainer.run_training()
     trainer.close()
     if dp is not None:

@@ -52,7 +52,8 @@ from etm.optim import FlatAdamW
 from model import ActorCriticModel, IndexedObservations
 from utils import normalization_section, polynomial_decay, process_episode_info
 from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
-from trainer_parts import _DataParallelStep, _NativeRolloutDrive, _RunOutputs
+from checkpoint import check_checkpoint_config, segment_first_worker_id
+from trainer_parts import _CheckpointResume, _DataParallelStep, _NativeRolloutDrive, _RunOutputs
 
 
 class _NullWriter:
@@ -194,9 +195,12 @@ def time_major(table, src):
     return x.reshape((table.shape[1], table.shape[0]) + tuple(table.shape[2:])).transpose(0, 1)
 
 
-class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
+class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _CheckpointResume):
     def __init__(self, config: dict, run_id: str = "run", device: torch.device = None, env=None, dp=None,
-                 first_worker_id: int = 0, tensorboard: bool = True) -> None:
+                 first_worker_id: int = 0, tensorboard: bool = True, resume: str = None) -> None:
+        """``resume``: the path of a training checkpoint (``save_checkpoint``) to continue from: the file is read and verified first,
+        the environments are built with the worker ids of the next training segment, and the state is loaded in place once everything
+        exists (``load_checkpoint`` without a second restart) -- also with ``worker_processes: true``."""
         if device is None:
             device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
         device = torch.device(device)
@@ -224,6 +228,16 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         check_truncation_transport(config, env)
         check_evaluation_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_normalization_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
+        check_checkpoint_config(config, 1 if dp is None else int(getattr(dp, "world", 1)), resume=resume is not None)
+        # training state that a checkpoint carries over (trainer_parts._CheckpointResume): completed updates, the training segment (the
+        # number of resumes so far; its environments' worker ids start at segment_first_worker_id), the last episodes' infos
+        self.update_index, self.segment, self._episode_infos = 0, 0, deque(maxlen=100)
+        self._base_worker_id, self._env_supplied = int(first_worker_id), env is not None
+        resumed = None
+        if resume is not None:
+            resumed = self._read_verified(resume)       # (before anything is built: a damaged file costs nothing)
+            self.segment = int(resumed["segment"]) + 1
+            first_worker_id = segment_first_worker_id(first_worker_id, self.segment)
         self.writer = _make_writer(run_id) if tensorboard else _NullWriter()
 
         # environments (batched front-end over the upstream per-worker protocol)
@@ -380,6 +394,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         self._ss_dev = torch.zeros((2, W), dtype=torch.int64, device=device)
         self._ss_dev[1] = torch.arange(W, dtype=torch.int64, device=device)
         self._step_dev, self._slot_dev = self._ss_dev[0], self._ss_dev[1]
+        if resumed is not None and self._env_supplied and hasattr(self.env, "restart"):
+            self.env.restart(first_worker_id)              # (a supplied environment moves to the segment's worker ids itself)
         self.env.reset(out=self.obs)
 
         # fixed-address operands of the rollout step (HIP-graph friendly) and time-major staging of the step outputs
@@ -452,6 +468,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
         self._mask_table = mask.bool().contiguous().to(device)
         self._index_table = indices.contiguous().to(device)
         self.last_update_timing = {}
+        if resumed is not None:
+            self._load_state(resumed, str(resume), restart=False)
 
     # ------------------------------------------------------------------ properties mirroring upstream members
     @property
@@ -472,7 +490,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
     def return_norm(self):
         """``normalize_rewards``: a read-only view {"clip", "epsilon", "stats" [3] float64 (count, mean, M2 of the discounted returns),
         "carry" [W] float64, "scale" [1] float32 (of the last rollout), "scaled" [W, S] (the rewards GAE read)}; None without the key.
-        Trainer state: it is not stored in the checkpoint (there is no resume of training)."""
+        Trainer state: the model file (.nn) does not hold it; the training checkpoint (``save_checkpoint``) stores ``stats``, and a
+        resumed run continues the triple with ``carry`` zero (its episodes start afresh)."""
         b = self.buffer
         if b.return_norm is None:
             return None
@@ -496,10 +515,11 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
     # ------------------------------------------------------------------ training loop
     def run_training(self) -> None:
         print("Step 6: Starting training using " + str(self.device))
-        episode_infos = deque(maxlen=100)
+        episode_infos = self._episode_infos
+        ckpt_every = check_checkpoint_config(self.config, 1 if self.dp is None else int(getattr(self.dp, "world", 1)))
         ev_cfg = check_evaluation_config(self.config, 1 if self.dp is None else int(getattr(self.dp, "world", 1)))
         ev_every = ev_cfg["interval"] if ev_cfg is not None else 0
-        for update in range(self.config["updates"]):
+        for update in range(self.update_index, self.config["updates"]):       # (a resumed run starts at the stored index)
             lr, beta, clip = self.schedules(update)
             t0 = time.perf_counter()
             sampled_episode_info = self._sample_training_data()
@@ -527,7 +547,10 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs):
             self._write_training_summary(update, training_stats, episode_result, vmean, amean, steps_per_s)
             if ev_every and ((update + 1) % ev_every == 0 or update + 1 == self.config["updates"]):
                 self._write_evaluation_summary(update, self.evaluate(ev_cfg["episodes_per_worker"], ev_cfg["n_workers"], ev_cfg["deterministic"]))
-        if self._is_main:              # replicas are identical: one rank writes the checkpoint
+            self.update_index = update + 1
+            if ckpt_every and ((update + 1) % ckpt_every == 0 or update + 1 == self.config["updates"]):
+                self.save_checkpoint()         # (model file + training checkpoint; refused in data-parallel runs, so one rank)
+        if self._is_main and not ckpt_every:   # replicas are identical: one rank writes the model file
             self._save_model()
         if self.dp is not None:
             self.dp.barrier()

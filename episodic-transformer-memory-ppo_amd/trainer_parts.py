@@ -2,7 +2,8 @@
 
 * ``_DataParallelStep``   the overlapped / one-graph forms of the data-parallel minibatch step (insertion point upstream trainer.py:310-311);
 * ``_NativeRolloutDrive`` the rollout loop through the kernel library's driver (worker processes; upstream trainer.py:159-218);
-* ``_RunOutputs``         TensorBoard summaries, the monitored gradient norms and the checkpoint (upstream trainer.py:325-362, model.py:128-151).
+* ``_RunOutputs``         TensorBoard summaries, the monitored gradient norms and the checkpoint (upstream trainer.py:325-362, model.py:128-151);
+* ``_CheckpointResume``   the training checkpoint next to upstream's model file, loading it in place, restarting the episodes.
 
 Every method runs on the trainer's own attributes; nothing here is importable on its own."""
 import os
@@ -293,3 +294,201 @@ class _RunOutputs:
         return torch.sqrt(self._grad_member @ sq)
 
     # ------------------------------------------------------------------ logging / checkpoint
+
+
+class _CheckpointResume:
+    """Checkpoint and resume of training (absent upstream): ``save_checkpoint`` / ``state_digest`` / ``load_checkpoint`` /
+    ``restart_episodes`` and the pieces ``PPOTrainer(..., resume=path)`` runs.  The file format and the host-side checks live in
+    checkpoint.py; nothing here allocates or launches until one of these methods is called."""
+
+    ARENAS = ("params", "exp_avg", "exp_avg_sq")
+
+    def _arenas(self):
+        opt = self.optimizer
+        return {"params": opt.flat_params, "exp_avg": opt.exp_avg, "exp_avg_sq": opt.exp_avg_sq}
+
+    def _arena_digests(self):
+        """{arena: the four words of etm_arena_digest as python ints}: three pairs of launches and one copy of 3 x 32 bytes."""
+        if getattr(self, "_digest_out", None) is None:
+            self._digest_out = torch.zeros((3, 4), dtype=torch.int64, device=self.device)
+            self._digest_partial = ops.arena_digest_workspace(self.device)
+        arenas = self._arenas()
+        for i, name in enumerate(self.ARENAS):
+            ops.arena_digest(arenas[name], out=self._digest_out[i], partial=self._digest_partial)
+        words = self._digest_out.cpu().numpy().view(np.uint64)
+        return {name: tuple(int(w) for w in words[i]) for i, name in enumerate(self.ARENAS)}
+
+    def state_digest(self) -> dict:
+        """{"params", "exp_avg", "exp_avg_sq": (fingerprint, number of Inf / NaN words, largest finite |x|), "step": the optimiser's
+        step count} -- the public way to compare the training state of two runs: equal fingerprints = the same bits at the same
+        places (etm_arena_digest; 32 bytes per arena travel to the host)."""
+        out = {name: (w[0], w[1], float(np.array([w[2]], dtype=np.uint32).view(np.float32)[0])) for name, w in self._arena_digests().items()}
+        out["step"] = int(self.optimizer.step_dev.item())
+        return out
+
+    def _arena_layout(self):
+        return [(name, [int(d) for d in p.shape]) for name, p in self.model.arena_parameters()]
+
+    def _state_buffers(self):
+        """The model's persistent buffers by name (the ``obs_norm_*`` triple and table, when present): state outside the arena."""
+        params = {n for n, _ in self.model.named_parameters()}
+        keep = set(self.model.state_dict().keys()) - params
+        return {n: b for n, b in self.model.named_buffers() if n in keep}
+
+    def _fixed_addresses(self) -> dict:
+        """data_ptr() of everything a load writes into and a captured graph may hold."""
+        opt, buf = self.optimizer, self.buffer
+        out = {"flat_params": opt.flat_params.data_ptr(), "flat_grads": opt.flat_grads.data_ptr(), "exp_avg": opt.exp_avg.data_ptr(),
+               "exp_avg_sq": opt.exp_avg_sq.data_ptr(), "step_dev": opt.step_dev.data_ptr(), "lr_dev": opt.lr_dev.data_ptr()}
+        out.update({"param:" + n: p.data_ptr() for n, p in self.model.named_parameters()})
+        out.update({"buffer:" + n: b.data_ptr() for n, b in self.model.named_buffers()})
+        if buf.ret_stats is not None:
+            out.update(ret_stats=buf.ret_stats.data_ptr(), ret_carry=buf.ret_carry.data_ptr())
+        return out
+
+    def save_checkpoint(self, path=None) -> str:
+        """Writes ./models/<run_id>.nn (the model file of ``_save_model``, unchanged: evaluate.py, enjoy.py and upstream's loader read
+        it) and the training checkpoint ``path`` (default ./models/<run_id>.ckpt; -> the path), which holds what continues the run:
+        completed updates and ``segment``; the config; the arena layout [(parameter name, shape)]; the flat parameter arena; the
+        optimiser state (FlatAdamW.state_dict: both moments, step, lr, hyper-parameters); the model's buffers outside the arena (the
+        ``obs_norm_*`` triple and table); ``buffer.ret_stats``; torch's CPU and device generator states; the last <= 100 episode
+        infos; the digests of the three arenas.
+        Before anything is written etm_arena_digest runs over the three arenas: a non-finite value in any of them raises
+        FloatingPointError (arena, count, update) and leaves both files of the previous save as they are.
+        Episodes in flight are NOT saved (environment state in general cannot be): a resumed run starts every worker on a fresh
+        episode; statistics keep the steps already merged."""
+        digests = self._arena_digests()
+        for name in self.ARENAS:
+            if digests[name][1] > 0:
+                raise FloatingPointError(f"save_checkpoint: {digests[name][1]} non-finite value(s) in the {name} arena after update "
+                                         f"{self.update_index}: nothing written, the previous checkpoint files stay as they are")
+        import checkpoint as ck
+        self._save_model()
+        path = "./models/" + self.run_id + ".ckpt" if path is None else str(path)
+        buf = self.buffer
+        torch.cuda.synchronize(self.device)
+        state = {
+            "update": int(self.update_index), "segment": int(self.segment), "config": self.config, "layout": self._arena_layout(),
+            "params": self.optimizer.flat_params.cpu().numpy(), "optimizer": self.optimizer.state_dict(),
+            "buffers": {n: b.detach().cpu().numpy() for n, b in self._state_buffers().items()},
+            "ret_stats": buf.ret_stats.cpu().numpy() if buf.ret_stats is not None else None,
+            "rng_cpu": torch.get_rng_state().numpy().copy(), "rng_device": torch.cuda.get_rng_state(self.device).numpy().copy(),
+            "episode_infos": list(self._episode_infos), "digests": {n: [int(w) for w in digests[n]] for n in self.ARENAS},
+        }
+        ck.write_checkpoint(path, state)
+        print("Checkpoint saved to " + path)
+        return path
+
+    @staticmethod
+    def _read_verified(path) -> dict:
+        """The checkpoint at ``path`` with every arena checked against its stored digest on the host (checkpoint.digest_numpy)."""
+        import checkpoint as ck
+        state = ck.read_checkpoint(path)
+        arenas = {"params": state["params"], "exp_avg": state["optimizer"]["exp_avg"], "exp_avg_sq": state["optimizer"]["exp_avg_sq"]}
+        for name, a in arenas.items():
+            got, want = ck.digest_numpy(a), tuple(int(w) for w in state["digests"][name])
+            if got != want:
+                raise ValueError(f"{path}: the {name} arena does not match its stored digest (file {got}, stored {want}): the file is damaged")
+        return state
+
+    def load_checkpoint(self, path) -> None:
+        """Continues from the training checkpoint ``path`` IN PLACE, on this live trainer: the file is read and every arena verified
+        against its digest on the host before a byte of the trainer is touched; a different arena layout, or a difference in whether
+        ``normalize_observations`` / ``normalize_rewards`` are set, is refused (any other differing config key is printed on one line;
+        the current config wins); everything is copied into place at fixed addresses (asserted), the device digest must equal the
+        stored one; then the update index and the generator states are set and ``restart_episodes(segment + 1)`` runs.
+        Nothing derived from the weights survives stale, because nothing is rebound and every derived copy is rebuilt from the
+        fixed-address arena before it is read: the rollout weight repackings (``model.refresh_rollout_weights``) and the K | V cache
+        (``_refresh_kv_cache``) at the start of every rollout -- eagerly or as ``ReplayAfterWarmup`` graphs, whose frozen pointer
+        tables stay valid exactly because no parameter moves --, the evaluator's parameter and table copies before every evaluation,
+        the bank-with-positions and the training observations at the start of every optimisation phase.
+        ``worker_processes: true``: refused (live worker processes cannot be restarted on fresh environments): build a new trainer
+        with ``resume=path``."""
+        if self._shm_env is not None:
+            raise ValueError("load_checkpoint on a live trainer with worker_processes: true: the worker processes' environments cannot "
+                             "be restarted in place; build the trainer with PPOTrainer(..., resume=path) (train.py --resume PATH)")
+        import checkpoint as ck
+        ck.check_checkpoint_config(self.config, 1 if self.dp is None else int(getattr(self.dp, "world", 1)), resume=True)
+        self._load_state(self._read_verified(path), str(path), restart=True)
+
+    def _load_state(self, state, what, restart):
+        import checkpoint as ck
+        from utils import normalization_section
+        if [(e[0], tuple(e[1])) for e in state["layout"]] != [(n, tuple(s)) for n, s in self._arena_layout()]:
+            saved, mine = {e[0]: list(e[1]) for e in state["layout"]}, dict(self._arena_layout())
+            diff = sorted(set(saved) ^ set(mine)) + [n for n in saved if n in mine and saved[n] != mine[n]]
+            raise ValueError(f"{what}: the parameter arena of the checkpoint is laid out differently (parameters that differ: "
+                             f"{diff[:8] or 'their order'})")
+        for key in ("normalize_observations", "normalize_rewards"):
+            if (normalization_section(state["config"], key) is None) != (normalization_section(self.config, key) is None):
+                raise ValueError(f"{what}: {key} is {'set' if normalization_section(state['config'], key) is not None else 'not set'} in the "
+                                 "checkpoint and the opposite in this run: the running statistics cannot be continued")
+        buffers, buf, opt = self._state_buffers(), self.buffer, self.optimizer
+        if set(buffers) != set(state["buffers"]) or (buf.ret_stats is None) != (state["ret_stats"] is None):
+            raise ValueError(f"{what}: the state outside the arena differs (checkpoint {sorted(state['buffers'])}, this run {sorted(buffers)})")
+        diff = ck.config_differences(state["config"], self.config)
+        if diff:
+            print(f"[etm] resume: config keys that differ from the checkpoint (the current config wins): {', '.join(diff)}", flush=True)
+        before = self._fixed_addresses()
+        with torch.no_grad():
+            opt.flat_params.copy_(torch.from_numpy(np.ascontiguousarray(state["params"])))
+            opt.load_state_dict(state["optimizer"])
+            for name, b in buffers.items():
+                b.copy_(torch.from_numpy(np.ascontiguousarray(state["buffers"][name])))
+            if buf.ret_stats is not None:
+                buf.ret_stats.copy_(torch.from_numpy(np.ascontiguousarray(state["ret_stats"])))
+        after = self._fixed_addresses()
+        assert after == before, "a load moved " + ", ".join(k for k in before if before[k] != after.get(k))
+        digests = self._arena_digests()
+        for name in self.ARENAS:
+            if digests[name] != tuple(int(w) for w in state["digests"][name]):
+                raise RuntimeError(f"{what}: the {name} arena on the device does not match the checkpoint's digest after the upload "
+                                   f"(device {digests[name]}, stored {tuple(state['digests'][name])})")
+        self.update_index = int(state["update"])
+        self._episode_infos.clear()
+        self._episode_infos.extend(state["episode_infos"])
+        torch.set_rng_state(torch.from_numpy(np.ascontiguousarray(state["rng_cpu"])))
+        torch.cuda.set_rng_state(torch.from_numpy(np.ascontiguousarray(state["rng_device"])), self.device)
+        if restart:
+            self.restart_episodes(int(state["segment"]) + 1)
+
+    def restart_episodes(self, segment: int) -> None:
+        """Every worker at step 0 of an empty episode on fresh environments of training segment ``segment``: worker ids from
+        ``checkpoint.segment_first_worker_id`` on, the running return of every worker (``ret_carry``) zero, pending truncation records
+        dropped.  An environment supplied through ``env=`` gets ``env.restart(first_worker_id)`` if it has that method, else only
+        ``env.reset``.  Episodes in flight are dropped -- a documented deviation of resumed runs."""
+        import checkpoint as ck
+        if self._shm_env is not None:
+            raise ValueError("restart_episodes with worker_processes: true: live worker processes cannot be restarted on fresh "
+                             "environments; build the trainer with PPOTrainer(..., resume=path)")
+        self._restart_workers(ck.segment_first_worker_id(self._base_worker_id, segment))
+        self.segment = int(segment)
+
+    def _restart_workers(self, first_worker_id: int) -> None:
+        """Fresh environments from ``first_worker_id`` on, every worker at step 0 of an empty episode in slot w."""
+        from environments.vec_env import make_vec_env
+        W, buf = self.num_workers, self.buffer
+        torch.cuda.synchronize(self.device)
+        if self._env_supplied:
+            if hasattr(self.env, "restart"):
+                self.env.restart(int(first_worker_id))
+        else:
+            self.env.close()
+            self.env = make_vec_env(self._env_cfg, W, int(first_worker_id), groups=self._env_groups)
+            parts = getattr(self.env, "parts", None)
+            self._group_all.env = self.env
+            if parts is not None and len(parts) == len(self._groups) > 1:
+                for g, part in zip(self._groups, parts):
+                    g.env = part
+        ev = getattr(buf, "_host_arrays_uploaded", None)
+        if ev is not None:
+            ev.synchronize()
+        buf.bank[: buf.num_episodes].zero_()
+        buf.num_episodes = W
+        if buf.ret_carry is not None:
+            buf.ret_carry.zero_()
+        self._truncations = []
+        self.worker_current_episode_step[:] = 0
+        self.worker_episode_slot[:] = range(W)
+        self._ss_dev.copy_(self._ss_pin)
+        self.env.reset(out=self.obs)

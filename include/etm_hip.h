@@ -36,7 +36,8 @@ extern "C" {
 #define ETM_ERCCL_BASE 100000 /* ETM_ERCCL_BASE + ncclResult_t: an RCCL call failed */
 
 /* ABI version of this header (bumped on any signature change, and when the meaning of an argument widens: 52 = the greedy
- * sentinel of the `uniforms` tables; 53 = + etm_gae_truncated; 54 = + the running-normalisation entries; 55 = + etm_grouped_dw_tile_map). */
+ * sentinel of the `uniforms` tables; 53 = + etm_gae_truncated; 54 = + the running-normalisation entries; 55 = + etm_grouped_dw_tile_map;
+ * 56 = + etm_arena_digest). */
 int etm_abi_version(void);
 
 /* Human-readable name for a negative ETM_E* code or a hipError_t. Static storage. */
@@ -405,6 +406,19 @@ int etm_grad_sqnorm(const float *g, int64_t n, float *partial, int n_partial, in
 int etm_adamw_clip(float *p, float *g, float *m, float *v, int64_t n, const float *partial, int n_partial, const float *lr_dev,
                    const int64_t *step, double beta1, double beta2, double eps, double weight_decay, float max_norm, float grad_scale, float *norm_out,
                    void *stream);
+
+/* Digest of a flat fp32 arena taken as raw bits (ABI 56; checkpoints: what is written, what is read back and what two runs compare).
+ * One pass over the n words b_i of x (any n >= 1, any 4-byte-aligned base; 16-byte loads on the aligned middle only) writes
+ *   out4[0] = sum over i of mix(i * 0x9E3779B97F4A7C15 + b_i) mod 2^64, mix(z): z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
+ *             z *= 0x94D049BB133111EB, z ^= z >> 31 -- depends on the position of every word and tells -0 from +0;
+ *   out4[1] = the number of words whose exponent field is all ones (Inf, NaN);
+ *   out4[2] = the bit pattern of the largest |x| among the finite words (0 when there is none);
+ *   out4[3] = n.
+ * Integer sums and one integer maximum: the result does not depend on the order of summation, so neither on n_partial.
+ * partial: 3 * n_partial 64-bit words of scratch (n_partial in 1 .. 4096 workgroups); partial and out4 8-byte aligned.  Two launches
+ * (per-workgroup partial words, then one workgroup adds them), no atomics, nothing allocated: graph-capturable.  ETM_EINVAL for a null
+ * pointer, n <= 0, n_partial outside 1 .. 4096 or a misaligned pointer. */
+int etm_arena_digest(const float *x, int64_t n, uint64_t *partial, int n_partial, uint64_t *out4, void *stream);
 
 /* Output heads on the rollout path (model.py:108-110): h [W, 2*hid] = [relu(lin_policy) | relu(lin_value)] rows;
  * logits [W,A] = h_pol Wp^T + bp, value [W] = h_val . wv + bv.  One launch instead of two small library GEMMs. */
