@@ -30,9 +30,25 @@ __device__ __forceinline__ float block_sum_256(float v, float *sm) {
   return t;
 }
 
-__global__ __launch_bounds__(OPT_THREADS) void grad_sqnorm_kernel(const float4 *__restrict__ g, long long n4, float *__restrict__ partial,
-                                                                  long long *__restrict__ step) {
+// ---- KL early stop (etm_grad_sqnorm_gated / etm_adamw_clip_gated): the step is dropped when an earlier step of this update was
+// dropped or when !(kl <= kl_limit), kl being the step's own statistic (a NaN stops too).  gate: three 64-bit words, [0] stopped (0 / 1),
+// [1] steps applied in this update, [2] the bit pattern of the kl that tripped.  Workgroup 0, thread 0 of the norm launch decides -- no
+// other workgroup of that launch reads gate or step -- and every workgroup of the AdamW launch, one launch later, reads gate[0].  GATED
+// is a compile-time switch on the ONE body of each kernel: the ungated instantiations hold the code they always held.
+template <bool GATED>
+__device__ __forceinline__ void grad_sqnorm_body(const float4 *__restrict__ g, long long n4, float *__restrict__ partial,
+                                                 long long *__restrict__ step, const float *__restrict__ kl, float kl_limit,
+                                                 unsigned long long *__restrict__ gate, unsigned long long *host_word) {
   __shared__ float sm[4];
+  // the deciding thread's three words are asked for first, so that their latency passes under the sum (they were written by earlier
+  // launches of the stream)
+  unsigned long long stopped = 0ull, applied = 0ull;
+  float k = 0.f;
+  if (GATED && blockIdx.x == 0 && threadIdx.x == 0) {
+    stopped = gate[0];
+    applied = gate[1];
+    k = *kl;
+  }
   float acc = 0.f;
   for (long long i = (long long)blockIdx.x * OPT_THREADS + threadIdx.x; i < n4; i += (long long)gridDim.x * OPT_THREADS) {
     const float4 v = g[i];
@@ -41,23 +57,46 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_sqnorm_kernel(const float4 *
   const float t = block_sum_256(acc, sm);
   if (threadIdx.x == 0) {
     partial[blockIdx.x] = t;
-    if (blockIdx.x == 0 && step) *step += 1;
+    if (blockIdx.x == 0) {
+      if (GATED) {
+        bool halted = stopped != 0ull;
+        if (!halted) {
+          if (!(k <= kl_limit)) {
+            halted = true;
+            gate[0] = 1ull;
+            gate[2] = (unsigned long long)__float_as_uint(k);
+            if (host_word) {        // (pinned host memory, as the rollout sampler stores its step number into its host flag)
+              __threadfence_system();
+              __hip_atomic_store(host_word, applied + 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+          }
+        }
+        if (!halted) {
+          if (step) *step += 1;
+          gate[1] = applied + 1ull;
+        }
+      } else if (step) {
+        *step += 1;
+      }
+    }
   }
 }
 
-__global__ __launch_bounds__(OPT_THREADS) void adamw_clip_kernel(float4 *__restrict__ p, float4 *__restrict__ g, float4 *__restrict__ m,
-                                                                 float4 *__restrict__ v, long long n4, const float *__restrict__ partial,
-                                                                 int n_partial, const float *__restrict__ lr_dev,
-                                                                 const long long *__restrict__ step, double beta1, double beta2, double eps,
-                                                                 double weight_decay, float max_norm, float grad_scale,
-                                                                 float *__restrict__ norm_out) {
+template <bool GATED>
+__device__ __forceinline__ void adamw_clip_body(float4 *__restrict__ p, float4 *__restrict__ g, float4 *__restrict__ m,
+                                                float4 *__restrict__ v, long long n4, const float *__restrict__ partial, int n_partial,
+                                                const float *__restrict__ lr_dev, const long long *__restrict__ step, double beta1,
+                                                double beta2, double eps, double weight_decay, float max_norm, float grad_scale,
+                                                float *__restrict__ norm_out, const unsigned long long *__restrict__ gate) {
   __shared__ float sm[4];
+  const bool dropped = GATED && gate[0] != 0ull;      // (asked for first: its latency passes under the sum of the partials)
   float acc = 0.f;
   for (int i = threadIdx.x; i < n_partial; i += OPT_THREADS) acc += partial[i];
   // grad_scale: the arena holds grad_scale^-1 times the gradient (data parallel: the all-reduced SUM, grad_scale = 1 / world) --
   // the division rides in the clip coefficient instead of costing a pass over the arena; 1.0f changes no bit
   const float total = sqrtf(block_sum_256(acc, sm)) * grad_scale;
   if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = total;
+  if (dropped) return;                        // a dropped step: the norm above and nothing else (uniform over the launch)
   float coef = 1.f;
   if (max_norm > 0.f) coef = fminf(max_norm / (total + 1e-6f), 1.f);
   coef *= grad_scale;
@@ -87,6 +126,37 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_clip_kernel(float4 *__restr
     }
     p[i] = pv; g[i] = gv; m[i] = mv; v[i] = vv;
   }
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void grad_sqnorm_kernel(const float4 *__restrict__ g, long long n4, float *__restrict__ partial,
+                                                                  long long *__restrict__ step) {
+  grad_sqnorm_body<false>(g, n4, partial, step, nullptr, 0.f, nullptr, nullptr);
+}
+__global__ __launch_bounds__(OPT_THREADS) void grad_sqnorm_gated_kernel(const float4 *__restrict__ g, long long n4, float *__restrict__ partial,
+                                                                        long long *__restrict__ step, const float *__restrict__ kl,
+                                                                        float kl_limit, unsigned long long *__restrict__ gate,
+                                                                        unsigned long long *host_word) {
+  grad_sqnorm_body<true>(g, n4, partial, step, kl, kl_limit, gate, host_word);
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void adamw_clip_kernel(float4 *__restrict__ p, float4 *__restrict__ g, float4 *__restrict__ m,
+                                                                 float4 *__restrict__ v, long long n4, const float *__restrict__ partial,
+                                                                 int n_partial, const float *__restrict__ lr_dev,
+                                                                 const long long *__restrict__ step, double beta1, double beta2, double eps,
+                                                                 double weight_decay, float max_norm, float grad_scale,
+                                                                 float *__restrict__ norm_out) {
+  adamw_clip_body<false>(p, g, m, v, n4, partial, n_partial, lr_dev, step, beta1, beta2, eps, weight_decay, max_norm, grad_scale, norm_out,
+                         nullptr);
+}
+__global__ __launch_bounds__(OPT_THREADS) void adamw_clip_gated_kernel(float4 *__restrict__ p, float4 *__restrict__ g, float4 *__restrict__ m,
+                                                                       float4 *__restrict__ v, long long n4, const float *__restrict__ partial,
+                                                                       int n_partial, const float *__restrict__ lr_dev,
+                                                                       const long long *__restrict__ step, double beta1, double beta2,
+                                                                       double eps, double weight_decay, float max_norm, float grad_scale,
+                                                                       float *__restrict__ norm_out,
+                                                                       const unsigned long long *__restrict__ gate) {
+  adamw_clip_body<true>(p, g, m, v, n4, partial, n_partial, lr_dev, step, beta1, beta2, eps, weight_decay, max_norm, grad_scale, norm_out,
+                        gate);
 }
 // Monitored gradient norms (model.py:128-151: one norm per module group, taken after clipping): partial[s] = sum of squares of
 // segment s (a run of <= 4096 floats inside ONE parameter tensor), then out[g] = sqrt(sum_s member[g][s] * partial[s]) -- two
@@ -206,30 +276,67 @@ extern "C" int etm_step_end(const float *stats, int n_stats, float *stats_table,
   return etm_launch_status();
 }
 
-extern "C" int etm_grad_sqnorm(const float *g, int64_t n, float *partial, int n_partial, int64_t *step, void *stream) {
+namespace {
+int grad_sqnorm_launch(const float *g, int64_t n, float *partial, int n_partial, int64_t *step, const float *kl, float kl_limit, uint64_t *gate,
+                       uint64_t *host_word, bool gated, void *stream) {
   (void)hipGetLastError();
   if (!g || !partial || n <= 0 || n % 4 != 0 || n_partial <= 0 || n_partial > 4096) return ETM_EINVAL;
   if ((uintptr_t)g % 16 != 0) return ETM_EINVAL;
+  if (gated && (!kl || !gate || (uintptr_t)kl % 4 != 0 || (uintptr_t)gate % 8 != 0 || (uintptr_t)host_word % 8 != 0)) return ETM_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   EtmProfScope prof(ETM_K_OPTIM, st);
-  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)n_partial), dim3(OPT_THREADS), 0, st, (const float4 *)g, (long long)(n / 4), partial,
-                     (long long *)step);
+  if (gated)
+    hipLaunchKernelGGL(grad_sqnorm_gated_kernel, dim3((unsigned)n_partial), dim3(OPT_THREADS), 0, st, (const float4 *)g, (long long)(n / 4),
+                       partial, (long long *)step, kl, kl_limit, (unsigned long long *)gate, (unsigned long long *)host_word);
+  else
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)n_partial), dim3(OPT_THREADS), 0, st, (const float4 *)g, (long long)(n / 4), partial,
+                       (long long *)step);
   return etm_launch_status();
 }
 
-extern "C" int etm_adamw_clip(float *p, float *g, float *m, float *v, int64_t n, const float *partial, int n_partial, const float *lr_dev,
-                              const int64_t *step, double beta1, double beta2, double eps, double weight_decay, float max_norm, float grad_scale,
-                              float *norm_out, void *stream) {
+int adamw_clip_launch(float *p, float *g, float *m, float *v, int64_t n, const float *partial, int n_partial, const float *lr_dev,
+                      const int64_t *step, double beta1, double beta2, double eps, double weight_decay, float max_norm, float grad_scale,
+                      float *norm_out, const uint64_t *gate, bool gated, void *stream) {
   (void)hipGetLastError();
   if (!p || !g || !m || !v || !partial || !lr_dev || !step || n <= 0 || n % 4 != 0 || n_partial <= 0 || n_partial > 4096) return ETM_EINVAL;
   if ((uintptr_t)p % 16 || (uintptr_t)g % 16 || (uintptr_t)m % 16 || (uintptr_t)v % 16 || !(grad_scale > 0.f)) return ETM_EINVAL;
+  if (gated && (!gate || (uintptr_t)gate % 8 != 0)) return ETM_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   EtmProfScope prof(ETM_K_OPTIM, st);
   const long long n4 = n / 4;
   long long blocks = (n4 + OPT_THREADS * 4 - 1) / (OPT_THREADS * 4);
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adamw_clip_kernel, dim3((unsigned)blocks), dim3(OPT_THREADS), 0, st, (float4 *)p, (float4 *)g, (float4 *)m, (float4 *)v, n4,
-                     partial, n_partial, lr_dev, (const long long *)step, beta1, beta2, eps, weight_decay, max_norm, grad_scale, norm_out);
+  if (gated)
+    hipLaunchKernelGGL(adamw_clip_gated_kernel, dim3((unsigned)blocks), dim3(OPT_THREADS), 0, st, (float4 *)p, (float4 *)g, (float4 *)m,
+                       (float4 *)v, n4, partial, n_partial, lr_dev, (const long long *)step, beta1, beta2, eps, weight_decay, max_norm,
+                       grad_scale, norm_out, (const unsigned long long *)gate);
+  else
+    hipLaunchKernelGGL(adamw_clip_kernel, dim3((unsigned)blocks), dim3(OPT_THREADS), 0, st, (float4 *)p, (float4 *)g, (float4 *)m, (float4 *)v, n4,
+                       partial, n_partial, lr_dev, (const long long *)step, beta1, beta2, eps, weight_decay, max_norm, grad_scale, norm_out);
   return etm_launch_status();
+}
+}  // namespace
+
+extern "C" int etm_grad_sqnorm(const float *g, int64_t n, float *partial, int n_partial, int64_t *step, void *stream) {
+  return grad_sqnorm_launch(g, n, partial, n_partial, step, nullptr, 0.f, nullptr, nullptr, false, stream);
+}
+
+extern "C" int etm_grad_sqnorm_gated(const float *g, int64_t n, float *partial, int n_partial, int64_t *step, const float *kl, float kl_limit,
+                                     uint64_t *gate, uint64_t *host_word, void *stream) {
+  return grad_sqnorm_launch(g, n, partial, n_partial, step, kl, kl_limit, gate, host_word, true, stream);
+}
+
+extern "C" int etm_adamw_clip(float *p, float *g, float *m, float *v, int64_t n, const float *partial, int n_partial, const float *lr_dev,
+                              const int64_t *step, double beta1, double beta2, double eps, double weight_decay, float max_norm, float grad_scale,
+                              float *norm_out, void *stream) {
+  return adamw_clip_launch(p, g, m, v, n, partial, n_partial, lr_dev, step, beta1, beta2, eps, weight_decay, max_norm, grad_scale, norm_out,
+                           nullptr, false, stream);
+}
+
+extern "C" int etm_adamw_clip_gated(float *p, float *g, float *m, float *v, int64_t n, const float *partial, int n_partial, const float *lr_dev,
+                                    const int64_t *step, double beta1, double beta2, double eps, double weight_decay, float max_norm,
+                                    float grad_scale, float *norm_out, const uint64_t *gate, void *stream) {
+  return adamw_clip_launch(p, g, m, v, n, partial, n_partial, lr_dev, step, beta1, beta2, eps, weight_decay, max_norm, grad_scale, norm_out,
+                           gate, true, stream);
 }

@@ -6,9 +6,36 @@ step is then two kernel launches (``etm_grad_sqnorm``, ``etm_adamw_clip``; csrc/
 with the learning rate and the step counter on the device so that a captured HIP graph replays it under changing schedules.
 ``state_dict`` keys, shapes and values of the model are untouched (views share storage, nothing is renamed).
 """
+import struct
+
 import torch
 
 from . import lib as _lib
+
+
+class KlGate:
+    """State of the KL early stop of one update (csrc/optim.hip: etm_grad_sqnorm_gated / etm_adamw_clip_gated), handed to
+    ``FlatAdamW.step``: ``limit`` (a float32 value), ``gate`` (device int64[3]: stopped, steps applied in this update, the bits of the
+    kl that tripped), ``host_word`` (pinned int64[1] that receives steps applied + 1 at the first dropped step, or None) and ``kl``, the
+    one-element float32 device tensor the next step compares: the caller points it at the step's own statistic before every step."""
+
+    def __init__(self, limit, device, host_word=True):
+        self.limit = float(limit)
+        self.gate = torch.zeros(3, dtype=torch.int64, device=device)
+        self.host_word = torch.zeros(1, dtype=torch.int64).pin_memory() if host_word else None
+        self.kl = None
+
+    def reset(self):
+        """Start of an update (the previous update's launches have finished: it ended with a read-back)."""
+        self.gate.zero_()
+        if self.host_word is not None:
+            self.host_word.zero_()
+
+    def read(self):
+        """(stopped, steps applied, kl that tripped or None) -- a device read-back."""
+        stopped, applied, bits = (int(x) for x in self.gate.cpu().tolist())
+        kl = struct.unpack("<f", struct.pack("<I", bits & 0xFFFFFFFF))[0] if stopped else None
+        return bool(stopped), applied, kl
 
 
 class FlatAdamW:
@@ -54,13 +81,29 @@ class FlatAdamW:
     def zero_grad(self):
         self.flat_grads.zero_()
 
-    def step(self, max_grad_norm=0.0, grad_scale=1.0):
+    def step(self, max_grad_norm=0.0, grad_scale=1.0, gate=None):
         """Clip the gradient arena to ``max_grad_norm`` (global L2 norm, the rule of ``clip_grad_norm_``; <= 0: no clipping) and
         apply one AdamW update.  Two launches on the current stream.  ``grad_scale``: the arena holds gradient / grad_scale
-        (data parallel: the all-reduced sum, grad_scale = 1 / world); the scale rides in the clip coefficient."""
+        (data parallel: the all-reduced sum, grad_scale = 1 / world); the scale rides in the clip coefficient.  ``gate`` (a ``KlGate``;
+        None: exactly the two ungated calls): the step is dropped -- parameters, moments, gradients and ``step_dev`` keep every bit --
+        when an earlier step under this gate was dropped or when not ``gate.kl <= gate.limit``; still two launches."""
         lib = _lib.load()
         st = torch.cuda.current_stream(self.device).cuda_stream
         n = self.flat_params.numel()
+        if gate is not None:
+            kl = gate.kl
+            if kl is None or not kl.is_cuda or kl.dtype != torch.float32 or kl.numel() != 1:
+                raise ValueError("FlatAdamW.step: gate.kl must be a one-element float32 device tensor (the step's own kl statistic)")
+            word = gate.host_word.data_ptr() if gate.host_word is not None else 0
+            _lib.check(lib.etm_grad_sqnorm_gated(self.flat_grads.data_ptr(), n, self.partial.data_ptr(), self.N_PARTIAL,
+                                                 self.step_dev.data_ptr(), kl.data_ptr(), gate.limit, gate.gate.data_ptr(), word, st),
+                       "etm_grad_sqnorm_gated")
+            _lib.check(lib.etm_adamw_clip_gated(self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.exp_avg.data_ptr(),
+                                                self.exp_avg_sq.data_ptr(), n, self.partial.data_ptr(), self.N_PARTIAL, self.lr_dev.data_ptr(),
+                                                self.step_dev.data_ptr(), self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                                                float(max_grad_norm), float(grad_scale), self.total_norm.data_ptr(), gate.gate.data_ptr(), st),
+                       "etm_adamw_clip_gated")
+            return
         _lib.check(lib.etm_grad_sqnorm(self.flat_grads.data_ptr(), n, self.partial.data_ptr(), self.N_PARTIAL, self.step_dev.data_ptr(), st),
                    "etm_grad_sqnorm")
         _lib.check(lib.etm_adamw_clip(self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.exp_avg.data_ptr(),

@@ -48,9 +48,9 @@ from environments.vec_env import make_vec_env
 from etm import lib as etm_lib
 from etm import ops
 from etm.ops import WindowSpec
-from etm.optim import FlatAdamW
+from etm.optim import FlatAdamW, KlGate
 from model import ActorCriticModel, IndexedObservations
-from utils import normalization_section, polynomial_decay, process_episode_info
+from utils import normalization_section, polynomial_decay, process_episode_info, target_kl_rows, target_kl_section
 from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
 from checkpoint import check_checkpoint_config, segment_first_worker_id
 from trainer_parts import _CheckpointResume, _DataParallelStep, _NativeRolloutDrive, _RunOutputs
@@ -189,6 +189,19 @@ def check_normalization_config(config, world: int = 1, observation_shape=None, o
     return out
 
 
+def check_target_kl_config(config, world: int = 1):
+    """The optional key ``target_kl`` (a number or {value, factor, host_check}; utils.target_kl_section) -> {"value", "factor",
+    "host_check", "limit"} or None when the key is absent (nothing is allocated, no launch is added or exchanged).  Refused, each before
+    anything is allocated: a value or factor that is no finite number > 0, unknown sub-keys, a ``host_check`` other than "epoch" /
+    "none"; the key in a data-parallel run (``world`` > 1): every rank sees the KL of its own minibatch, and agreeing on one is not
+    built."""
+    out = target_kl_section(config)
+    if out is not None and world > 1:
+        raise ValueError("target_kl in a data-parallel run: every rank would stop on the KL of its own minibatch and the replicas would "
+                         "part (agreeing on one KL over the ranks is not built); remove the key, or train on one device")
+    return out
+
+
 def time_major(table, src):
     """The host table ``src`` [W, S(, B)] in the layout and type of the fixed-address device table ``table`` [S, W(, B)]."""
     x = torch.as_tensor(np.asarray(src), dtype=table.dtype)
@@ -229,6 +242,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         check_evaluation_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_normalization_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_checkpoint_config(config, 1 if dp is None else int(getattr(dp, "world", 1)), resume=resume is not None)
+        kl_cfg = check_target_kl_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         # training state that a checkpoint carries over (trainer_parts._CheckpointResume): completed updates, the training segment (the
         # number of resumes so far; its environments' worker ids start at segment_first_worker_id), the last episodes' infos
         self.update_index, self.segment, self._episode_infos = 0, 0, deque(maxlen=100)
@@ -371,6 +385,12 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if self.dp is not None:
             self.dp.flat = self.flat_grads
         self._build_grad_groups()
+        # target_kl: the gate of the KL early stop (etm/optim.py: KlGate), reset at the start of every update; not trainer state, not in
+        # the checkpoint.  ``last_kl_stop``: what the last update's gate said (None without the key: nothing is allocated)
+        self._kl_cfg, self._kl_gate, self.last_kl_stop = kl_cfg, None, None
+        if kl_cfg is not None:
+            self._kl_gate = KlGate(kl_cfg["limit"], device, host_word=kl_cfg["host_check"] == "epoch")
+            self._kl_event = torch.cuda.Event() if kl_cfg["host_check"] == "epoch" else None
 
         # host <-> device staging (pinned)
         if self._shm_env is not None:
@@ -1146,7 +1166,10 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
 
     # ------------------------------------------------------------------ optimisation
     def _train_epochs(self, learning_rate: float, clip_range: float, beta: float, perms=None):
-        """``epochs`` passes over shuffled minibatches.  Returns (list of 6-stat rows, {grad key: [norms]})."""
+        """``epochs`` passes over shuffled minibatches.  Returns (list of 6-stat rows, {grad key: [norms]}).  ``target_kl``: the
+        optimiser steps decide on the device whether they apply (``_step_gate``); a stopped update returns rows 0 ... steps applied
+        (utils.target_kl_rows), and with ``host_check: epoch`` the host looks at the gate's pinned word after every epoch but the last and
+        launches no further epoch once it is set -- they would be no-ops, the results are the same bits."""
         stats, norms = [], []
         monitor = self.config.get("monitor_gradients", True)
         # sinusoidal positions: add them to the (read-only) episode bank once per update instead of once per window row,
@@ -1170,11 +1193,21 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if tables:
             self._step_tables(mbs)
             self._tg_counter.zero_()
+        gate, launched = self._kl_gate, 0
+        if gate is not None:
+            gate.reset()
+        host_stop = False
         for epoch in range(self.config["epochs"]):
+            if gate is not None and gate.host_word is not None and epoch > 0 and not host_stop:
+                self._kl_event.record(torch.cuda.current_stream(self.device))
+                self._kl_event.synchronize()
+                host_stop = int(gate.host_word[0]) != 0
             if perms is None:
                 perm = torch.randperm(self.buffer.batch_size, device=self.device)
             else:
                 perm = torch.as_tensor(perms[epoch], device=self.device, dtype=torch.long)
+            if host_stop:       # the update has stopped: its remaining steps would be no-ops (the generator still moves as ever)
+                continue
             if sort_mb and perm.numel() % mbs == 0:
                 perm = perm.view(-1, mbs).sort(dim=1).values.reshape(-1)
             self._epoch_stats3 = None
@@ -1188,6 +1221,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                 self._epoch_stats3 = self.dp.merge_adv_stats(local)
             for start in range(0, self.buffer.batch_size, mbs):
                 idx = perm[start: start + mbs]
+                launched += 1
                 self._mb_stats3 = self._epoch_stats3[start // mbs] if self._epoch_stats3 is not None else None
                 if tables:
                     self._train_step_graph(idx, learning_rate, clip_range, beta, monitor, row=row)
@@ -1205,13 +1239,18 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                     norms.append(self._grad_group_norms())
         if self.model.obs_norm is not None:
             self._update_obs_norm()
-        # the only host sync of the optimisation phase
-        train_info = (self._tg_stats_tab[:row] if tables else torch.stack(stats)).cpu().numpy()
+        # the only host sync of the optimisation phase (target_kl with host_check: epoch waits for an event between epochs as well)
+        rows = launched
+        if gate is not None:
+            stopped, applied, kl = gate.read()
+            rows = target_kl_rows(stopped, applied, launched)
+            self.last_kl_stop = {"stopped": stopped, "steps_applied": applied, "steps_launched": launched, "kl": kl, "limit": gate.limit}
+        train_info = (self._tg_stats_tab[:rows] if tables else torch.stack(stats[:rows])).cpu().numpy()
         self._bank_pos = self._row_stats = None
         self._mb_stats3 = self._epoch_stats3 = None
         grad_info = {}
         if norms or (tables and monitor):
-            allnorms = (self._tg_norm_tab[:row] if tables else torch.stack(norms)).cpu().numpy()
+            allnorms = (self._tg_norm_tab[:rows] if tables else torch.stack(norms[:rows])).cpu().numpy()
             grad_info = {k: allnorms[:, i].tolist() for i, k in enumerate(self._grad_keys)}
         return [row for row in train_info], grad_info
 
@@ -1239,7 +1278,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if self.dp is not None:
             self.dp.all_reduce_grads(average=False)       # the sum; the 1 / world rides in the clip coefficient below
         # global-norm clipping (the rule of torch.nn.utils.clip_grad_norm_, upstream :311) + AdamW on the flat arenas: 2 launches
-        self.optimizer.step(self.config["max_grad_norm"], grad_scale=self._grad_scale())
+        self.optimizer.step(self.config["max_grad_norm"], grad_scale=self._grad_scale(), gate=self._step_gate(stats))
         return stats
 
     def _loss_from(self, obs, spec, mb, clip_range, beta, stats3, dyn="device"):
@@ -1437,11 +1476,23 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         self._bank_pos = self._row_stats = None
         return grads
 
-    def _train_body_b(self, monitor, stats=None):
+    def _step_gate(self, stats):
+        """``target_kl``: the update's gate with its ``kl`` pointed at element 4 of the step's own statistics (the k3 estimate of the
+        loss on the weights before the step); None without the key."""
+        gate = self._kl_gate
+        if gate is not None:
+            if stats is None or stats.dtype != torch.float32 or stats.dim() != 1 or stats.numel() < 5 or not stats.is_contiguous():
+                raise RuntimeError("target_kl: the step's statistics must be a contiguous float32 vector with the kl at index 4")
+            gate.kl = stats[4:5]
+        return gate
+
+    def _train_body_b(self, monitor, stats=None, kl_stats=None):
         """Second half: global-norm clipping (same rule as torch.nn.utils.clip_grad_norm_, upstream :311) on the flat bucket,
         fused AdamW, monitored gradient norms.  ``stats`` (the table-driven step): the step's statistics; they and the norms are
-        filed under row ``counter`` of the result tables and the counter moves on, inside the norm monitor's two launches."""
-        self.optimizer.step(self.config["max_grad_norm"], grad_scale=self._grad_scale())
+        filed under row ``counter`` of the result tables and the counter moves on, inside the norm monitor's two launches.
+        ``kl_stats`` (``target_kl``): the step's statistics in every form of the step, for the optimiser's gate."""
+        self.optimizer.step(self.config["max_grad_norm"], grad_scale=self._grad_scale(),
+                            gate=self._step_gate(kl_stats) if self._kl_gate is not None else None)
         if stats is None:
             return self._grad_group_norms() if monitor else None
         if stats.numel() != self._tg_stats_tab.shape[1] or stats.dtype != torch.float32 or not stats.is_contiguous():
@@ -1474,6 +1525,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             self._tg_idx.copy_(idx)
         elif row is None:                   # a single step asked for from outside _train_epochs: an "update" of one step
             self._tg_counter.zero_()
+            if self._kl_gate is not None:
+                self._kl_gate.reset()
             self._tg_idx_table[0].copy_(idx)
         self._set_lr(learning_rate)
         if self._sched_host[1] != clip_range or self._sched_host[2] != beta:
@@ -1502,7 +1555,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                 st = self._train_body_a(self._tg_idx, clip_range, beta, self._tg_stats3, head=tables)
                 if dp is not None:
                     dp.all_reduce_grads(average=False)
-            nm = self._train_body_b(monitor, st if tables else None)
+            nm = self._train_body_b(monitor, st if tables else None, kl_stats=st)
             if tables:
                 return self._step_rows(row, monitor)
             return st.clone(), (nm.clone() if nm is not None else None)
@@ -1524,7 +1577,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                     else:
                         self._tg_stats = self._train_body_a(self._tg_idx, clip_range, beta, self._tg_stats3, head=tables)
                     if dp is None:
-                        self._tg_norms = self._train_body_b(monitor, self._tg_stats if tables else None)
+                        self._tg_norms = self._train_body_b(monitor, self._tg_stats if tables else None, kl_stats=self._tg_stats)
                 if overlap:
                     ga2 = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(ga2, pool=pool, capture_error_mode="thread_local"):

@@ -207,6 +207,9 @@ class _RunOutputs:
         self.writer.add_scalar("other/kl", training_stats[4], update)
         self.writer.add_scalar("other/clip_fraction", training_stats[5], update)
         self.writer.add_scalar("other/env_steps_per_second", steps_per_s, update)
+        if self.last_kl_stop is not None:                # (target_kl: did the update stop, and how many optimiser steps it applied)
+            self.writer.add_scalar("other/kl_stopped", float(self.last_kl_stop["stopped"]), update)
+            self.writer.add_scalar("other/optimizer_steps", self.last_kl_stop["steps_applied"], update)
         if self.buffer.return_norm is not None:          # (the scale the last rollout's rewards were multiplied with)
             self.writer.add_scalar("training/return_scale", float(self.buffer.return_scale.item()), update)
         if self.model.obs_norm is not None:              # (the spread of the frozen table the next rollout runs on)

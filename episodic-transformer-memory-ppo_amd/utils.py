@@ -1,5 +1,6 @@
 """Helpers with the upstream names (utils.py): create_env, polynomial_decay, batched_index_select,
-process_episode_info, Module; normalization_section reads this build's two normalisation keys."""
+process_episode_info, Module; normalization_section reads this build's two normalisation keys, target_kl_section its KL early
+stop, target_kl_rows says which rows of an update's result tables a stopped update returns."""
 import numpy as np
 import torch
 from torch import nn
@@ -84,6 +85,43 @@ def normalization_section(config: dict, key: str):
     if not out["epsilon"] > 0 or not np.isfinite(out["epsilon"]):
         raise ValueError(f"{key}.epsilon must be a positive number, got {sec.get('epsilon')!r}; leave it out for the default 1e-8")
     return out
+
+
+def _positive_number(x):
+    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_)) and bool(np.isfinite(x)) and x > 0
+
+
+def target_kl_section(config: dict):
+    """The optional key ``target_kl`` (a number, or {value, factor, host_check}) -> {"value", "factor", "host_check", "limit"} with the
+    defaults (factor 1.5, stable-baselines3's rule; host_check "epoch") filled in, or None when the key is absent.  ``limit`` is
+    float32(factor * value): the product is formed once in double and rounded once."""
+    sec = config.get("target_kl")
+    if sec is None:
+        return None
+    if not isinstance(sec, dict):
+        sec = {"value": sec}
+    known = ("value", "factor", "host_check")
+    unknown = sorted(set(sec) - set(known))
+    if unknown:
+        raise ValueError(f"target_kl: unknown keys {unknown} (known: {list(known)}); remove them")
+    if "value" not in sec:
+        raise ValueError("target_kl: the section needs `value` (the target KL, e.g. 0.02); add it, or remove the key to train without the stop")
+    value, factor, host_check = sec["value"], sec.get("factor", 1.5), sec.get("host_check", "epoch")
+    if not _positive_number(value):
+        raise ValueError(f"target_kl.value must be a finite number > 0, got {value!r}; remove the key to train without the stop")
+    if not _positive_number(factor):
+        raise ValueError(f"target_kl.factor must be a finite number > 0, got {factor!r}; leave it out for the default 1.5")
+    if host_check not in ("epoch", "none"):
+        raise ValueError(f"target_kl.host_check must be 'epoch' or 'none', got {host_check!r}; leave it out for the default 'epoch'")
+    return dict(value=float(value), factor=float(factor), host_check=host_check, limit=float(np.float32(float(factor) * float(value))))
+
+
+def target_kl_rows(stopped: bool, steps_applied: int, steps_launched: int) -> int:
+    """How many leading rows of an update's statistics / norm tables are returned: all launched ones, or -- stopped -- rows
+    0 ... steps_applied, the stopping row included (its loss statistics are real: the loss on the weights the update ends with).
+    Never 0."""
+    rows = min(int(steps_applied) + 1, int(steps_launched)) if stopped else int(steps_launched)
+    return max(rows, 1)
 
 
 class Module(nn.Module):

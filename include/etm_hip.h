@@ -407,6 +407,22 @@ int etm_adamw_clip(float *p, float *g, float *m, float *v, int64_t n, const floa
                    const int64_t *step, double beta1, double beta2, double eps, double weight_decay, float max_norm, float grad_scale, float *norm_out,
                    void *stream);
 
+/* The same pair under a KL early stop (ABI 57): the step is dropped when an earlier step of this update was dropped, or when
+ * !(*kl <= kl_limit) -- *kl is the step's own k3 estimate (out8[4] of the loss entries); a NaN stops too.  gate: three 64-bit words, 8-byte
+ * aligned, zeroed by the caller at the start of every update: gate[0] stopped (0 / 1), gate[1] steps applied in this update, gate[2] the
+ * bit pattern of the kl that tripped.  No launch is added: the decision rides in the two launches.
+ *   etm_grad_sqnorm_gated: partial[] as etm_grad_sqnorm.  Workgroup 0, thread 0 decides (no other workgroup of the launch reads gate or
+ *                    step).  Not halted: *step += 1, gate[1] += 1.  Halted for the first time: gate[0] = 1, gate[2] = bits of *kl and,
+ *                    host_word not NULL, gate[1] + 1 is stored into that pinned host word (system scope, release).
+ *   etm_adamw_clip_gated : every workgroup reads gate[0]; set: norm_out is written and nothing else (p, g, m, v keep every bit);
+ *                    clear: the arithmetic of etm_adamw_clip (one definition in the source, a compile-time switch).
+ * ETM_EINVAL: kl or gate NULL, gate or host_word not 8-byte aligned, and whatever the ungated entries refuse. */
+int etm_grad_sqnorm_gated(const float *g, int64_t n, float *partial, int n_partial, int64_t *step, const float *kl, float kl_limit,
+                          uint64_t *gate, uint64_t *host_word, void *stream);
+int etm_adamw_clip_gated(float *p, float *g, float *m, float *v, int64_t n, const float *partial, int n_partial, const float *lr_dev,
+                         const int64_t *step, double beta1, double beta2, double eps, double weight_decay, float max_norm, float grad_scale,
+                         float *norm_out, const uint64_t *gate, void *stream);
+
 /* Digest of a flat fp32 arena taken as raw bits (ABI 56; checkpoints: what is written, what is read back and what two runs compare).
  * One pass over the n words b_i of x (any n >= 1, any 4-byte-aligned base; 16-byte loads on the aligned middle only) writes
  *   out4[0] = sum over i of mix(i * 0x9E3779B97F4A7C15 + b_i) mod 2^64, mix(z): z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
