@@ -20,6 +20,10 @@ the storage redesigned for the MI355X path:
   return (``etm_return_scale``) into ``rewards_scaled`` [W, S], which GAE reads; ``rewards`` keeps the raw values.  The running triple
   ``ret_stats`` and the per-worker returns ``ret_carry`` are float64 device arrays that live as long as the buffer (trainer state: not
   in the model file; the training checkpoint of ``PPOTrainer.save_checkpoint`` stores the triple).  Nothing is allocated without the key.
+* ``action_masks: true`` (absent upstream): ``action_masks_host`` [W, S] is the pinned array the environment loop writes each step's
+  invalid-action word into (bit j = column j of the concatenated policy head is allowed), ``action_masks`` [W, S] int64 its device
+  copy (uploaded by ``prepare_batch_dict``) and a member of ``samples_flat``, so every minibatch carries its samples' words.  Without
+  the key neither exists and ``samples_flat`` has its usual keys.
 """
 import numpy as np
 import torch
@@ -64,6 +68,13 @@ class Buffer:
             self.truncated = self._truncated_host.numpy()
             self.truncated_dev = torch.zeros((W, S), dtype=torch.bool, device=dev)
             self.bootstrap_values = torch.zeros((W, S), dtype=torch.float32, device=dev)
+
+        # invalid-action words (action_masks: true): written by the env loop like ``memory_index_host``; None without the key
+        self.action_masks = self.action_masks_host = None
+        if config.get("action_masks", False):
+            self._action_masks_host = pin((W, S), torch.int64)
+            self.action_masks_host = self._action_masks_host.numpy()
+            self.action_masks = torch.zeros((W, S), dtype=torch.int64, device=dev)
 
         # return-based reward scaling (normalize_rewards): None without the key
         self.return_norm = normalization_section(config, "normalize_rewards")
@@ -157,12 +168,16 @@ class Buffer:
     def prepare_batch_dict(self) -> None:
         """Upload the host-side bookkeeping and expose the samples flattened to [W*S, ...] (W-major, views)."""
         self.memory_index.copy_(self._memory_index_host, non_blocking=True)
+        if self.action_masks is not None:
+            self.action_masks.copy_(self._action_masks_host, non_blocking=True)
         self._mark_host_arrays_uploaded()
         samples = {
             "actions": self.actions, "values": self.values, "log_probs": self.log_probs, "advantages": self.advantages,
             "obs": self.obs, "memory_mask": self.memory_mask, "memory_index": self.memory_index,
             "memory_indices": self.memory_indices,
         }
+        if self.action_masks is not None:
+            samples["action_masks"] = self.action_masks
         self.samples_flat = {k: v.reshape(v.shape[0] * v.shape[1], *v.shape[2:]) for k, v in samples.items()}
 
     def mini_batch_generator(self, indices: torch.Tensor = None, materialize: bool = False):

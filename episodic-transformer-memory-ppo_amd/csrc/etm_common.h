@@ -53,15 +53,28 @@ __device__ __forceinline__ float half_sum(float v) {
   return v;
 }
 
+// Invalid-action masks (action_masks: true): bit j of a step's 64-bit word says whether column j of the concatenated policy head is
+// allowed; branch b owns bits [off_b, off_b + A_b), handed to the branch functions below shifted down by off_b.  MK = true reads
+// the logit of a masked-out action as -INFINITY in front of the ONE sampling arithmetic below: its exponential is +0 (adds nothing
+// to a sum, and the inverse CDF cannot stop on it), it never equals the branch maximum, and what is left is, operation for
+// operation, the unmasked arithmetic on the branch compacted to its valid actions.  MK = false (the default of every template
+// here) is exactly the code without masks.  A branch with no valid action never reaches the device (the host refuses the word).
+template <bool MK>
+__device__ __forceinline__ float etm_masked_logit(const float *lg, int j, unsigned long long m) {
+  if constexpr (MK) return ((m >> j) & 1ull) ? lg[j] : -INFINITY;
+  else return lg[j];
+}
+
 // Inverse-CDF draw from the categorical over the A logits lg with log-normaliser lse (every sampling site: rollout_sample_kernel,
 // rollout_policy_kernel and both step kernels).  The action is the smallest j with u < C_j, C_j = the fp32 running sum of
 // expf(lg[i] - lse) over i <= j.  That total can end below 1, and below the largest fp32 uniform 1 - 2^-24: a draw at or past it
 // takes the LAST action whose term is positive, never one of probability zero (torch.multinomial's contract).
-__device__ __forceinline__ int etm_sample_categorical(const float *lg, int A, float lse, float u) {
+template <bool MK = false>
+__device__ __forceinline__ int etm_sample_categorical(const float *lg, int A, float lse, float u, unsigned long long m = 0) {
   float c = 0.f;
   int last = A - 1;
   for (int j = 0; j < A; ++j) {
-    const float e = expf(lg[j] - lse);
+    const float e = expf(etm_masked_logit<MK>(lg, j, m) - lse);
     c += e;
     if (e > 0.f) last = j;
     if (u < c) return j;
@@ -97,6 +110,13 @@ static inline int etm_branches_make(const int32_t *sizes, int n, int total_a, Et
   }
   return s == total_a ? 0 : ETM_EINVAL;
 }
+// An optional action-mask word array (int64, one word per worker or sample): NULL = no masks; else 8-byte aligned, and the A
+// columns must fit the 63 usable bits.
+static inline int etm_action_mask_check(const void *mask, int A) {
+  if (!mask) return 0;
+  if (((uintptr_t)mask & 7u) != 0) return ETM_EINVAL;
+  return A <= 63 ? 0 : ETM_EUNSUPPORTED;
+}
 static inline int etm_branches_total(const int32_t *sizes, int n) {
   if (!sizes || n <= 0 || n > ETM_MAX_BRANCHES) return 0;
   int s = 0;
@@ -109,9 +129,10 @@ static inline int etm_branches_total(const int32_t *sizes, int n) {
 
 // The mode of one branch: the smallest index whose logit equals the branch's maximum mx (as computed by etm_sample_branch; the last
 // index when none compares equal, which only NaN logits can cause).
-__device__ __forceinline__ int etm_branch_mode(const float *lg, int A, float mx) {
+template <bool MK = false>
+__device__ __forceinline__ int etm_branch_mode(const float *lg, int A, float mx, unsigned long long m = 0) {
   for (int j = 0; j < A - 1; ++j)
-    if (lg[j] == mx) return j;
+    if (etm_masked_logit<MK>(lg, j, m) == mx) return j;
   return A - 1;
 }
 
@@ -121,30 +142,40 @@ __device__ __forceinline__ int etm_branch_mode(const float *lg, int A, float mx)
 // training.  A uniform in [0, 1) -- and a NaN one, for which u < 0 is false -- takes the inverse CDF exactly as before.  Returns the
 // action (inside the branch) and its log-prob lg[a] - lse in all three cases.  With one branch this is exactly the single-branch
 // arithmetic of every sampling site (same operations in the same order).
-__device__ __forceinline__ int etm_sample_branch(const float *lg, int A, float u, int forced, float *logp) {
+// MK: the branch's bits m of the step's mask word (bit j = action j of THIS branch); a forced action is taken as it is (the host
+// checks it against the stored words after the rollout).
+template <bool MK = false>
+__device__ __forceinline__ int etm_sample_branch(const float *lg, int A, float u, int forced, float *logp, unsigned long long m = 0) {
   float mx = -INFINITY;
-  for (int j = 0; j < A; ++j) mx = fmaxf(mx, lg[j]);
+  for (int j = 0; j < A; ++j) mx = fmaxf(mx, etm_masked_logit<MK>(lg, j, m));
   float se = 0.f;
-  for (int j = 0; j < A; ++j) se += expf(lg[j] - mx);
+  for (int j = 0; j < A; ++j) se += expf(etm_masked_logit<MK>(lg, j, m) - mx);
   const float lse = mx + logf(se);
   int a = forced;
-  if (a < 0) a = u < 0.f ? etm_branch_mode(lg, A, mx) : etm_sample_categorical(lg, A, lse, u);
+  if (a < 0) a = u < 0.f ? etm_branch_mode<MK>(lg, A, mx, m) : etm_sample_categorical<MK>(lg, A, lse, u, m);
   *logp = lg[a] - lse;
   return a;
 }
 
 // Every branch of worker w at step t: row = t * stage_W + w indexes the time-major [S, stage_W, B] uniform / forced / staging
 // tables (B = 1: [S, stage_W]); actions and host_actions are [W, B].  The value (logit column sum(sizes)) is staged by the caller.
+// MK: am points to THIS worker's mask word (any address space); MK = false never reads am.
+template <bool MK = false>
 __device__ __forceinline__ void etm_sample_branches(const float *lg, const EtmBranches &br, long long row, int w, const float *uniforms,
                                                     const long long *forced, long long *actions, long long *host_actions,
-                                                    long long *st_actions, float *st_logp) {
+                                                    long long *st_actions, float *st_logp, const long long *am = nullptr) {
   const int B = br.n;
+  unsigned long long word = 0ull;
+  if constexpr (MK) word = (unsigned long long)*am;
   int off = 0;
   for (int b = 0; b < B; ++b) {
     const long long i = row * B + b;
     const int Ab = br.size[b];
     float lp;
-    const int a = etm_sample_branch(lg + off, Ab, uniforms[i], forced ? (int)forced[i] : -1, &lp);
+    const int fc = forced ? (int)forced[i] : -1;
+    int a;
+    if constexpr (MK) a = etm_sample_branch<true>(lg + off, Ab, uniforms[i], fc, &lp, word >> off);
+    else a = etm_sample_branch(lg + off, Ab, uniforms[i], fc, &lp);
     actions[(long long)w * B + b] = a;
     if (host_actions) host_actions[(long long)w * B + b] = a;
     st_actions[i] = a;

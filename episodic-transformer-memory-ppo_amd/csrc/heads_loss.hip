@@ -46,11 +46,17 @@ struct HlParams {
   int branch_off[HL_MAXA];
   // GS kernels (Box): the A logits are the means; xact [N, A] (row stride action_stride) the stored raw actions, log_std [A]
   const float *xact, *log_std;
+  // MK kernels (invalid-action masks): amask [N] int64, bit j of a sample's word = column j of the A logits was allowed when the
+  // sample was drawn
+  const long long *amask;
 };
 
 // BR: MultiDiscrete branches; GS: diagonal Gaussian (Box; the row gains d log_std [A] behind the five statistic sums)
-template <int HC, bool BR, bool GS = false>
-__global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
+// MK: invalid-action masks (BR or not).  A branch's log-sum-exp, log-probs and entropy run over its VALID columns only (ok(j)); an
+// invalid column has p = 0, is skipped -- not multiplied: 0 * inf -- by the entropy, and its d logit is exactly 0.  The logit dot
+// products and the optional logits output stay raw.  What is left is the unmasked arithmetic on the compacted branch.
+template <int HC, bool BR, bool GS, bool MK>
+__device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
   HlParams p = p0;
   if (p.dyn) {
     const double c = p.dyn[0];
@@ -146,6 +152,9 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
     const float a_raw = p.adv[n];
     const float a_n = (a_raw - mean) / (stdv + 1e-8f);
     float dl[HL_MAXA];
+    unsigned long long am = ~0ull;
+    if constexpr (MK) am = (unsigned long long)p.amask[n];
+    auto ok = [&](int j) { return !MK || ((am >> j) & 1ull) != 0; };
     if constexpr (GS) {
       // Box (diagonal Gaussian): log p(x) = sum_a [-z_a^2 / 2 - log sigma_a - log(2 pi) / 2], z_a = (x_a - mu_a) / sigma_a, of the
       // stored raw action x; one ratio per sample, the surrogate's per-sample factor cpol = d loss / d log p as in the other modes;
@@ -189,10 +198,10 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
     } else if constexpr (!BR) {
     float mx = -INFINITY;
 #pragma unroll
-    for (int j = 0; j < HL_MAXA; ++j) if (j < A) mx = fmaxf(mx, lg[j]);
+    for (int j = 0; j < HL_MAXA; ++j) if (j < A && ok(j)) mx = fmaxf(mx, lg[j]);
     float se = 0.f;
 #pragma unroll
-    for (int j = 0; j < HL_MAXA; ++j) if (j < A) se += expf(lg[j] - mx);
+    for (int j = 0; j < HL_MAXA; ++j) if (j < A && ok(j)) se += expf(lg[j] - mx);
     const float lse = mx + logf(se);
     const int act = (int)p.actions[(long long)n * p.action_stride];
     float lg_act = 0.f;
@@ -201,7 +210,7 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
     const float lp = lg_act - lse;
     float ent = 0.f;
 #pragma unroll
-    for (int j = 0; j < HL_MAXA; ++j) if (j < A) { const float l = lg[j] - lse; ent -= expf(l) * l; }
+    for (int j = 0; j < HL_MAXA; ++j) if (j < A && ok(j)) { const float l = lg[j] - lse; ent -= expf(l) * l; }
     const float log_ratio = lp - p.old_logp[(long long)n * p.logp_stride];
     const float ratio = expf(log_ratio);
     const bool in_range = (ratio >= p.clip_lo) && (ratio <= p.clip_hi);
@@ -222,7 +231,7 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
 #pragma unroll
     for (int j = 0; j < HL_MAXA; ++j) {
       dl[j] = 0.f;
-      if (j < A) {
+      if (j < A && ok(j)) {
         const float l = lg[j] - lse;
         const float pj = expf(l);
         const float d_lp = ((j == act) ? 1.f : 0.f) - pj;
@@ -243,17 +252,17 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
         if (b < p.nbr) {
           float mx = -INFINITY;
 #pragma unroll
-          for (int j = 0; j < HL_MAXA; ++j) if (j < A && p.col_branch[j] == b) mx = fmaxf(mx, lg[j]);
+          for (int j = 0; j < HL_MAXA; ++j) if (j < A && p.col_branch[j] == b && ok(j)) mx = fmaxf(mx, lg[j]);
           float se = 0.f;
 #pragma unroll
-          for (int j = 0; j < HL_MAXA; ++j) if (j < A && p.col_branch[j] == b) se += expf(lg[j] - mx);
+          for (int j = 0; j < HL_MAXA; ++j) if (j < A && p.col_branch[j] == b && ok(j)) se += expf(lg[j] - mx);
           const float lse = mx + logf(se);
           const int ac = p.branch_off[b] + (int)p.actions[(long long)n * p.action_stride + b];
           float lg_act = 0.f, ent = 0.f;
 #pragma unroll
           for (int j = 0; j < HL_MAXA; ++j) {
             if (j == ac) lg_act = lg[j];
-            if (j < A && p.col_branch[j] == b) { const float l = lg[j] - lse; ent -= expf(l) * l; }
+            if (j < A && p.col_branch[j] == b && ok(j)) { const float l = lg[j] - lse; ent -= expf(l) * l; }
           }
           const float lp = lg_act - lse;
           const float log_ratio = lp - p.old_logp[(long long)n * p.logp_stride + b];
@@ -282,7 +291,7 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
 #pragma unroll
       for (int j = 0; j < HL_MAXA; ++j) {
         dl[j] = 0.f;
-        if (j < A) {
+        if (j < A && ok(j)) {
           bool taken = false;
 #pragma unroll
           for (int b = 0; b < HL_MAXA; ++b) taken = taken || (act_col[b] == j);
@@ -366,6 +375,12 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) {
   for (int e = tid; e < row; e += 256) dst[e] = ((hl_lds[e] + hl_lds[row + e]) + hl_lds[2 * row + e]) + hl_lds[3 * row + e];
 }
 
+// The kernels: one body; the instantiations without masks keep their names, the masked ones are kernels of their own.
+template <int HC, bool BR, bool GS = false>
+__global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) { heads_loss_body<HC, BR, GS, false>(p0); }
+template <int HC, bool BR>
+__global__ __launch_bounds__(256) void heads_loss_masked_kernel(const HlParams p0) { heads_loss_body<HC, BR, false, true>(p0); }
+
 // sums the workgroup rows and finishes the loss statistics: out = [row sums ... ], out8 (a Gaussian row's d log_std sums, behind the
 // statistics, are summed like every other element).  One workgroup = 64 row elements x 16 row
 // groups: thread (e, g) adds the rows g, g + 16, ... (all requested at once: the sum is a latency chain otherwise), the 16 group
@@ -440,12 +455,15 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
                               int64_t logp_stride, const float *adv, const float *old_value, const float *adv_stats3, double clip, float vf_coef,
                               float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v,
                               float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
-                              int A, const int32_t *branch_sizes, int n_branches, const float *xact, const float *log_std, void *stream) {
+                              int A, const int32_t *branch_sizes, int n_branches, const float *xact, const float *log_std,
+                              const int64_t *action_mask, void *stream) {
   (void)hipGetLastError();
   const bool gauss = xact != nullptr;                  // Box: float actions xact and log_std instead of the int64 actions
   if (!pre_p || !pre_v || !b_lp || !b_lv || !wb || !bb || !wv || !bv || !(gauss ? (const void *)log_std : (const void *)actions) || !old_logp ||
       !adv || !old_value || !adv_stats3 || !gm_p || !gm_v || !sums || !out8 || !workspace)
     return ETM_EINVAL;
+  if (action_mask && gauss) return ETM_EINVAL;
+  if (const int rc = etm_action_mask_check(action_mask, A)) return rc;
   if (!(gauss ? etm_heads_loss_supported_gaussian(N, hid, A) : etm_heads_loss_supported(N, hid, A))) return ETM_EUNSUPPORTED;
   if (workspace_bytes < (gauss ? etm_heads_loss_gaussian_workspace_bytes(N, hid, A) : etm_heads_loss_workspace_bytes(N, hid, A)))
     return ETM_EWORKSPACE;
@@ -465,7 +483,8 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
   p.vf_coef = vf_coef; p.beta = beta; p.pol_scale = pol_scale; p.ent_scale = ent_scale; p.val_scale = val_scale; p.dyn = dyn_clip_beta;
   p.gm_p = gm_p; p.gm_v = gm_v; p.logits = logits; p.value = value; p.partials = (float *)workspace;
   p.N = N; p.A = A; p.hid = hid; p.samples_per_wg = HL_SAMPLES_PER_WG;
-  p.xact = xact; p.log_std = log_std;
+  p.xact = xact; p.log_std = log_std; p.amask = (const long long *)action_mask;
+  const bool masked = action_mask != nullptr;
   const int n_wg = (N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG;
   const int row = gauss ? etm_heads_loss_gaussian_row_floats(hid, A) : etm_heads_loss_row_floats(hid, A);
   const size_t lds = 4 * (size_t)row * sizeof(float);
@@ -476,6 +495,8 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
 #define HL_CASE(HC_)                                                                                              \
   case HC_:                                                                                                       \
     if (gauss) hipLaunchKernelGGL((heads_loss_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (masked && branched) hipLaunchKernelGGL((heads_loss_masked_kernel<HC_, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (masked) hipLaunchKernelGGL((heads_loss_masked_kernel<HC_, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
     else if (branched) hipLaunchKernelGGL((heads_loss_kernel<HC_, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
     else hipLaunchKernelGGL((heads_loss_kernel<HC_, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p);         \
     break;
@@ -500,7 +521,22 @@ extern "C" int etm_heads_loss(const float *pre_p, const float *pre_v, const floa
                               int A, void *stream) {
   return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
                          clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, A, nullptr, 1, nullptr, nullptr, stream);
+                         workspace_bytes, N, hid, A, nullptr, 1, nullptr, nullptr, nullptr, stream);
+}
+// Invalid-action masks: etm_heads_loss with action_mask [N] int64, the samples' words (bit j = action j was allowed; at least one bit
+// below A set, the taken action among them).  Log-sum-exp, log-prob and entropy run over the valid actions only, and d loss / d logit
+// of an invalid action is exactly 0 -- so are its rows of d Wb and d bb from that sample.  ETM_EINVAL: NULL or misaligned mask.
+extern "C" int etm_heads_loss_masked(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                     const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
+                                     const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
+                                     const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                                     float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
+                                     float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid, int A,
+                                     const int64_t *action_mask, void *stream) {
+  if (!action_mask) return ETM_EINVAL;
+  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
+                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
+                         workspace_bytes, N, hid, A, nullptr, 1, nullptr, nullptr, action_mask, stream);
 }
 
 // MultiDiscrete: wb / bb = the branches' heads concatenated ([sum(sizes), hid], [sum(sizes)]); actions / old_logp rows carry one entry
@@ -520,7 +556,25 @@ extern "C" int etm_heads_loss_branched(const float *pre_p, const float *pre_v, c
   if (action_stride < n_branches || logp_stride < n_branches) return ETM_EINVAL;
   return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
                          clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, nullptr, stream);
+                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, nullptr, nullptr, stream);
+}
+// Invalid-action masks: etm_heads_loss_branched with action_mask [N] int64 (bit j = column j of the concatenated heads; branch b owns
+// bits [off_b, off_b + A_b)), per branch as in etm_heads_loss_masked.
+extern "C" int etm_heads_loss_branched_masked(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                              const float *bb, const float *wv, const float *bv, const int64_t *actions,
+                                              int64_t action_stride, const float *old_logp, int64_t logp_stride, const float *adv,
+                                              const float *old_value, const float *adv_stats3, double clip, float vf_coef, float beta,
+                                              float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p,
+                                              float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace,
+                                              int64_t workspace_bytes, int N, int hid, const int32_t *branch_sizes, int n_branches,
+                                              const int64_t *action_mask, void *stream) {
+  if (!action_mask) return ETM_EINVAL;
+  if (!etm_heads_loss_supported_branched(N, hid, branch_sizes, n_branches)) return ETM_EUNSUPPORTED;
+  if (action_stride < n_branches || logp_stride < n_branches) return ETM_EINVAL;
+  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
+                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
+                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, nullptr,
+                         action_mask, stream);
 }
 
 // Box policies (diagonal Gaussian, A <= 8): wb / bb = the mean head [A, hid], [A]; xact [N, A] (row stride action_stride >= A) the
@@ -537,5 +591,5 @@ extern "C" int etm_heads_loss_gaussian(const float *pre_p, const float *pre_v, c
   if (action_stride < A || logp_stride < 1) return ETM_EINVAL;
   return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, nullptr, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
                          clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, A, nullptr, 1, xact, log_std, stream);
+                         workspace_bytes, N, hid, A, nullptr, 1, xact, log_std, nullptr, stream);
 }

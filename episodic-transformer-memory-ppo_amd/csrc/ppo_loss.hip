@@ -89,14 +89,20 @@ struct LossParams {
   int include_value;
   float *d_logits, *d_value, *partials;
   int N, A;
+  // MK kernels (invalid-action masks): amask [N] int64 words, the branch's A actions at bits [mask_shift, mask_shift + A)
+  const long long *amask;
+  int mask_shift;
 };
 
 // SPT samples per thread.  SPT = 4 (large batches, unit strides, A = 3, N % 4 == 0): the four samples' operands come in as
 // 16-byte loads (logits: three float4 = 12 floats; advantages, values, old log-probs: one float4 each; actions: two 16-byte
 // loads) and the gradients leave the same way -- a quarter of the load / store instructions of the one-sample form, which
 // is what bounds this kernel at large N (28 + 8 A = 52 bytes per sample against ~10 scalar memory instructions).
-template <int SPT>
-__global__ __launch_bounds__(256) void ppo_loss_kernel(const LossParams p0) {
+// MK (SPT = 1 only): invalid-action masks.  Log-sum-exp, log-prob and entropy run over the VALID actions only; an invalid action has
+// p = 0, is skipped -- not multiplied: 0 * inf -- by the entropy, and its d logit is exactly 0.  What is left is the unmasked
+// arithmetic on the compacted branch.
+template <int SPT, bool MK>
+__device__ __forceinline__ void ppo_loss_body(const LossParams &p0) {
   LossParams p = p0;
   if (p.dyn) {   // schedules that change between replays of a captured training step
     const double c = p.dyn[0];
@@ -138,10 +144,13 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossParams p0) {
     float lgl[3];
     if (SPT == 4) { lgl[0] = lgv[s][0]; lgl[1] = lgv[s][SPT == 1 ? 0 : 1]; lgl[2] = lgv[s][SPT == 1 ? 0 : 2]; }
     const float *lg = SPT == 4 ? lgl : p.logits + (long long)n * A;
+    unsigned long long am = ~0ull;
+    if constexpr (MK) am = (unsigned long long)p.amask[n] >> p.mask_shift;
+    auto ok = [&](int j) { return !MK || ((am >> j) & 1ull) != 0; };
     float mx = -INFINITY;
-    for (int j = 0; j < A; ++j) mx = fmaxf(mx, lg[j]);
+    for (int j = 0; j < A; ++j) if (ok(j)) mx = fmaxf(mx, lg[j]);
     float se = 0.f;
-    for (int j = 0; j < A; ++j) se += expf(lg[j] - mx);
+    for (int j = 0; j < A; ++j) if (ok(j)) se += expf(lg[j] - mx);
     const float lse = mx + logf(se);
     const int act = SPT == 4 ? actv[s] : (int)p.actions[(long long)n * p.action_stride];
     float lg_act = lg[0];
@@ -149,6 +158,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossParams p0) {
     const float lp = lg_act - lse;
     float ent = 0.f;
     for (int j = 0; j < A; ++j) {
+      if (!ok(j)) continue;
       const float l = lg[j] - lse;
       ent -= expf(l) * l;
     }
@@ -170,6 +180,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossParams p0) {
     const float cent = -p.beta * p.ent_scale;
     float *dl = p.d_logits + (long long)n * A;
     for (int j = 0; j < A; ++j) {
+      if (!ok(j)) { dl[j] = 0.f; continue; }               // (MK only, i.e. SPT = 1)
       const float l = lg[j] - lse;
       const float pj = expf(l);
       const float d_lp = ((j == act) ? 1.f : 0.f) - pj;   // d log p[act] / d logit_j
@@ -215,6 +226,11 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossParams p0) {
   __syncthreads();
   if (tid < 5) p.partials[(long long)blockIdx.x * 8 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
 }
+
+// The kernels: one body; the instantiations without masks keep their names, the masked one is a kernel of its own.
+template <int SPT>
+__global__ __launch_bounds__(256) void ppo_loss_kernel(const LossParams p0) { ppo_loss_body<SPT, false>(p0); }
+__global__ __launch_bounds__(256) void ppo_loss_masked_kernel(const LossParams p0) { ppo_loss_body<1, true>(p0); }
 
 __global__ __launch_bounds__(64) void ppo_finalize_kernel(const float *__restrict__ partials, int n_blocks, float vf_coef, float beta,
                                                           float pol_scale, float ent_scale, float val_scale, float *__restrict__ out8,
@@ -275,17 +291,20 @@ extern "C" int etm_adv_stats_ws(const float *adv, int N, float *stats3, void *wo
 extern "C" int64_t etm_ppo_loss_workspace_bytes(int N) { return N <= 0 ? 0 : (int64_t)((N + 255) / 256) * 8 * sizeof(float); }
 static bool al16(const void *q) { return ((uintptr_t)q % 16) == 0; }
 
-extern "C" int etm_ppo_loss(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
+static int ppo_loss_impl(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
                             int64_t logp_stride, const float *adv, const float *old_value, const float *value,
                             const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
                             float val_scale, int include_value, float *out8, float *d_logits, float *d_value, void *partials,
-                            int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, void *stream) {
+                            int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, const int64_t *action_mask,
+                            int mask_shift, void *stream) {
   (void)hipGetLastError();  // drop stale sticky errors of earlier, unrelated runtime calls
   if (!logits || !actions || !old_logp || !adv || !adv_stats3 || !out8 || !d_logits || !partials) return ETM_EINVAL;
   if (include_value && (!old_value || !value || !d_value)) return ETM_EINVAL;
   if (N <= 0 || A <= 0) return ETM_EINVAL;
+  if (action_mask && (mask_shift < 0 || mask_shift + A > 63)) return ETM_EUNSUPPORTED;
+  if (const int rc = etm_action_mask_check(action_mask, A)) return rc;
   if (partials_bytes < etm_ppo_loss_workspace_bytes(N)) return ETM_EWORKSPACE;
-  LossParams p;
+  LossParams p{};
   p.logits = logits; p.actions = (const long long *)actions; p.action_stride = action_stride;
   p.old_logp = old_logp; p.logp_stride = logp_stride; p.adv = adv; p.old_value = old_value; p.value = value;
   p.adv_stats3 = adv_stats3;
@@ -293,15 +312,16 @@ extern "C" int etm_ppo_loss(const float *logits, const int64_t *actions, int64_t
   p.vf_coef = vf_coef; p.beta = beta; p.pol_scale = pol_scale; p.ent_scale = ent_scale; p.val_scale = val_scale;
   p.dyn = dyn_clip_beta;
   p.include_value = include_value; p.d_logits = d_logits; p.d_value = d_value; p.partials = (float *)partials;
-  p.N = N; p.A = A;
+  p.N = N; p.A = A; p.amask = (const long long *)action_mask; p.mask_shift = mask_shift;
   // four samples per thread when every operand can move in 16-byte pieces and there are enough samples to fill the chip
-  const bool vec = A == 3 && N % 4 == 0 && N >= (1 << 16) && action_stride == 1 && logp_stride == 1 && al16(logits) && al16(actions) &&
+  const bool vec = !action_mask && A == 3 && N % 4 == 0 && N >= (1 << 16) && action_stride == 1 && logp_stride == 1 && al16(logits) && al16(actions) &&
                    al16(old_logp) && al16(adv) && al16(d_logits) && (!include_value || (al16(value) && al16(old_value) && al16(d_value)));
   const int nb = vec ? (N / 4 + 255) / 256 : (N + 255) / 256;
   hipStream_t st = (hipStream_t)stream;
   {
     EtmProfScope prof(ETM_K_PPO_LOSS, st);
     if (vec) hipLaunchKernelGGL(ppo_loss_kernel<4>, dim3(nb), dim3(256), 0, st, p);
+    else if (action_mask) hipLaunchKernelGGL(ppo_loss_masked_kernel, dim3(nb), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(ppo_loss_kernel<1>, dim3(nb), dim3(256), 0, st, p);
   }
   int rc = etm_launch_status();
@@ -312,4 +332,29 @@ extern "C" int etm_ppo_loss(const float *logits, const int64_t *actions, int64_t
                        val_scale, out8, dyn_clip_beta);
   }
   return etm_launch_status();
+}
+
+extern "C" int etm_ppo_loss(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
+                            int64_t logp_stride, const float *adv, const float *old_value, const float *value,
+                            const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                            float val_scale, int include_value, float *out8, float *d_logits, float *d_value, void *partials,
+                            int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, void *stream) {
+  return ppo_loss_impl(logits, actions, action_stride, old_logp, logp_stride, adv, old_value, value, adv_stats3, clip, vf_coef, beta, pol_scale,
+                       ent_scale, val_scale, include_value, out8, d_logits, d_value, partials, partials_bytes, dyn_clip_beta, N, A, nullptr, 0,
+                       stream);
+}
+// Invalid-action masks: etm_ppo_loss of one action branch with action_mask [N] int64, the samples' words; the branch's A actions are
+// bits [mask_shift, mask_shift + A) (mask_shift = the branch's first column of the concatenated policy head, 0 for Discrete).  At
+// least one of those bits is set per sample, the taken action among them.  Log-sum-exp, log-prob and entropy run over the valid
+// actions only; d_logits of an invalid action is exactly 0.  ETM_EINVAL: NULL or misaligned mask; ETM_EUNSUPPORTED: bits past 62.
+extern "C" int etm_ppo_loss_masked(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
+                                   int64_t logp_stride, const float *adv, const float *old_value, const float *value,
+                                   const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                                   float val_scale, int include_value, float *out8, float *d_logits, float *d_value, void *partials,
+                                   int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, const int64_t *action_mask,
+                                   int mask_shift, void *stream) {
+  if (!action_mask) return ETM_EINVAL;
+  return ppo_loss_impl(logits, actions, action_stride, old_logp, logp_stride, adv, old_value, value, adv_stats3, clip, vf_coef, beta, pol_scale,
+                       ent_scale, val_scale, include_value, out8, d_logits, d_value, partials, partials_bytes, dyn_clip_beta, N, A, action_mask,
+                       mask_shift, stream);
 }

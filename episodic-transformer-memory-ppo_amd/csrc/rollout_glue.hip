@@ -75,20 +75,38 @@ __global__ __launch_bounds__(256) void rollout_heads_kernel(const float *__restr
 
 // One thread per worker: per action branch log-softmax over its segment, inverse-CDF sample with the pre-drawn uniform of
 // (t, w, b) (or a forced action), log-prob; staging of actions / log_probs / values for step t; finally t += 1.
+// MK: am [W] are the workers' action-mask words (one body; the unmasked kernel keeps its name and arguments).
+template <bool MK>
+__device__ __forceinline__ void rollout_sample_body(const float *__restrict__ logits, const float *__restrict__ value,
+                                                    const float *__restrict__ uniforms, const long long *__restrict__ forced,
+                                                    long long *__restrict__ t_dev, long long *__restrict__ actions,
+                                                    long long *__restrict__ st_actions, float *__restrict__ st_logp,
+                                                    float *__restrict__ st_values, int W, int A, const EtmBranches &br,
+                                                    const long long *__restrict__ am) {
+  const long long t = *t_dev;
+  for (int w = threadIdx.x; w < W; w += 1024) {
+    // logits [W, A]: the branches' segments side by side; forced / uniforms / staging time-major [S, W, B] (B = 1: [S, W]), a
+    // negative forced entry means "sample"
+    etm_sample_branches<MK>(logits + (long long)w * A, br, t * W + w, w, uniforms, forced, actions, nullptr, st_actions, st_logp, am + w);
+    st_values[t * W + w] = value[w];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) *t_dev = t + 1;
+}
 __global__ __launch_bounds__(1024) void rollout_sample_kernel(const float *__restrict__ logits, const float *__restrict__ value,
                                                               const float *__restrict__ uniforms, const long long *__restrict__ forced,
                                                               long long *__restrict__ t_dev, long long *__restrict__ actions,
                                                               long long *__restrict__ st_actions, float *__restrict__ st_logp,
                                                               float *__restrict__ st_values, int W, int A, const EtmBranches br) {
-  const long long t = *t_dev;
-  for (int w = threadIdx.x; w < W; w += 1024) {
-    // logits [W, A]: the branches' segments side by side; forced / uniforms / staging time-major [S, W, B] (B = 1: [S, W]), a
-    // negative forced entry means "sample"
-    etm_sample_branches(logits + (long long)w * A, br, t * W + w, w, uniforms, forced, actions, nullptr, st_actions, st_logp);
-    st_values[t * W + w] = value[w];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) *t_dev = t + 1;
+  rollout_sample_body<false>(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W, A, br, nullptr);
+}
+__global__ __launch_bounds__(1024) void rollout_sample_masked_kernel(const float *__restrict__ logits, const float *__restrict__ value,
+                                                                     const float *__restrict__ uniforms, const long long *__restrict__ forced,
+                                                                     long long *__restrict__ t_dev, long long *__restrict__ actions,
+                                                                     long long *__restrict__ st_actions, float *__restrict__ st_logp,
+                                                                     float *__restrict__ st_values, int W, int A, const EtmBranches br,
+                                                                     const long long *__restrict__ am) {
+  rollout_sample_body<true>(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W, A, br, am);
 }
 
 // Box policies (etm_sample_gaussian): one thread per worker, the A means of row w of `mean`, its A normals / forced entries of
@@ -151,26 +169,43 @@ __device__ __forceinline__ void policy_arrive(bool to_host, long long t, long lo
 // workgroup to finish (every workgroup has read it by then).  Optional hand-over to the host without a copy launch and
 // without an event: the actions are also stored straight into pinned host memory, followed (after ONE system-scope release)
 // by the step counter the host spins on.
-__global__ __launch_bounds__(256) void rollout_policy_kernel(const float *__restrict__ h, const float *__restrict__ wp,
-                                                             const float *__restrict__ bp, const float *__restrict__ wv,
-                                                             const float *__restrict__ bv, const float *__restrict__ h_bias,
-                                                             const float *__restrict__ uniforms,
-                                                             const long long *__restrict__ forced, long long *__restrict__ t_dev,
-                                                             long long *__restrict__ actions, long long *__restrict__ st_actions,
-                                                             float *__restrict__ st_logp, float *__restrict__ st_values,
-                                                             long long *host_actions, long long *host_flag, int *sync_counter,
-                                                             int W, int A, int hid, int stage_W, const EtmBranches br) {
+// MK: am [W] are the workers' action-mask words, device or pinned host memory -- requested in front of the dot products (one body;
+// the unmasked kernel keeps its name and arguments).
+template <bool MK>
+__device__ __forceinline__ void rollout_policy_body(const float *__restrict__ h, const float *__restrict__ wp, const float *__restrict__ bp,
+    const float *__restrict__ wv, const float *__restrict__ bv, const float *__restrict__ h_bias, const float *__restrict__ uniforms,
+    const long long *__restrict__ forced, long long *__restrict__ t_dev, long long *__restrict__ actions,
+    long long *__restrict__ st_actions, float *__restrict__ st_logp, float *__restrict__ st_values, long long *host_actions,
+    long long *host_flag, int *sync_counter, int W, int A, int hid, int stage_W, const EtmBranches &br,
+    const long long *__restrict__ am) {
   extern __shared__ float out_s[];   // [A + 1]: logits (the branches' segments side by side), then the value
+  __shared__ long long am_s;
   const int w = blockIdx.x;
   const long long t = *t_dev;
+  if constexpr (MK) { if (threadIdx.x == 0) am_s = am[w]; }
   policy_heads_lds(h, wp, bp, wv, bv, h_bias, out_s, w, A, hid);
   __syncthreads();
   if (threadIdx.x == 0) {
     // forced / uniforms / staging: time-major [S, stage_W, B] (B = 1: [S, stage_W]); negative forced entry = "sample"
-    etm_sample_branches(out_s, br, t * stage_W + w, w, uniforms, forced, actions, host_actions, st_actions, st_logp);
+    etm_sample_branches<MK>(out_s, br, t * stage_W + w, w, uniforms, forced, actions, host_actions, st_actions, st_logp, &am_s);
     st_values[t * stage_W + w] = out_s[A];
     policy_arrive(host_actions != nullptr, t, t_dev, host_flag, sync_counter, W);
   }
+}
+__global__ __launch_bounds__(256) void rollout_policy_kernel(const float *__restrict__ h, const float *__restrict__ wp, const float *__restrict__ bp,
+    const float *__restrict__ wv, const float *__restrict__ bv, const float *__restrict__ h_bias, const float *__restrict__ uniforms,
+    const long long *__restrict__ forced, long long *__restrict__ t_dev, long long *__restrict__ actions,
+    long long *__restrict__ st_actions, float *__restrict__ st_logp, float *__restrict__ st_values, long long *host_actions,
+    long long *host_flag, int *sync_counter, int W, int A, int hid, int stage_W, const EtmBranches br) {
+  rollout_policy_body<false>(h, wp, bp, wv, bv, h_bias, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, W, A, hid, stage_W, br, nullptr);
+}
+__global__ __launch_bounds__(256) void rollout_policy_masked_kernel(const float *__restrict__ h, const float *__restrict__ wp, const float *__restrict__ bp,
+    const float *__restrict__ wv, const float *__restrict__ bv, const float *__restrict__ h_bias, const float *__restrict__ uniforms,
+    const long long *__restrict__ forced, long long *__restrict__ t_dev, long long *__restrict__ actions,
+    long long *__restrict__ st_actions, float *__restrict__ st_logp, float *__restrict__ st_values, long long *host_actions,
+    long long *host_flag, int *sync_counter, int W, int A, int hid, int stage_W, const EtmBranches br,
+    const long long *__restrict__ am) {
+  rollout_policy_body<true>(h, wp, bp, wv, bv, h_bias, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, W, A, hid, stage_W, br, am);
 }
 
 // The same launch for a Box policy: the A outputs are the Gaussian's means; the draw of etm_sample_gaussian with the normals /
@@ -261,35 +296,53 @@ extern "C" int etm_rollout_window(const int64_t *step, const uint8_t *mask_table
 
 static int rollout_sample_impl(const float *logits, const float *value, const float *uniforms, const int64_t *forced, int64_t *t_dev,
                                int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W, int A,
-                               const int32_t *branch_sizes, int n_branches, void *stream) {
+                               const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, void *stream) {
   (void)hipGetLastError();
   if (!logits || !value || !uniforms || !t_dev || !actions || !st_actions || !st_logp || !st_values || W <= 0 || A <= 0)
     return ETM_EINVAL;
   EtmBranches br;
   if (const int rc = etm_branches_make(branch_sizes, n_branches, A, &br)) return rc;
+  if (const int rc = etm_action_mask_check(action_mask, A)) return rc;
   hipStream_t st = (hipStream_t)stream;
   EtmProfScope prof(ETM_K_ROLLOUT_SAMPLE, st);
-  hipLaunchKernelGGL(rollout_sample_kernel, dim3(1), dim3(1024), 0, st, logits, value, uniforms, (const long long *)forced, (long long *)t_dev,
-                     (long long *)actions, (long long *)st_actions, st_logp, st_values, W, A, br);
+  if (action_mask)
+    hipLaunchKernelGGL(rollout_sample_masked_kernel, dim3(1), dim3(1024), 0, st, logits, value, uniforms, (const long long *)forced,
+                       (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values, W, A, br,
+                       (const long long *)action_mask);
+  else
+    hipLaunchKernelGGL(rollout_sample_kernel, dim3(1), dim3(1024), 0, st, logits, value, uniforms, (const long long *)forced, (long long *)t_dev,
+                       (long long *)actions, (long long *)st_actions, st_logp, st_values, W, A, br);
   return etm_launch_status();
 }
 
 extern "C" int etm_rollout_sample(const float *logits, const float *value, const float *uniforms, const int64_t *forced, int64_t *t_dev,
                                   int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W, int A, void *stream) {
-  return rollout_sample_impl(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W, A, nullptr, 1, stream);
+  return rollout_sample_impl(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W, A, nullptr, 1, nullptr, stream);
 }
 
 extern "C" int etm_rollout_sample_branched(const float *logits, const float *value, const float *uniforms, const int64_t *forced,
                                            int64_t *t_dev, int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W,
                                            const int32_t *branch_sizes, int n_branches, void *stream) {
   return rollout_sample_impl(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W,
-                             etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, stream);
+                             etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, stream);
+}
+// Invalid-action masks: etm_rollout_sample_branched (a Discrete policy is one branch, n_branches = 1) with action_mask [W] int64, the
+// workers' words for this step (bit j = column j of the concatenated logits is allowed; every branch has a valid action -- the
+// host's duty).  The draw is the unmasked draw on each branch compacted to its valid actions.  ETM_EINVAL: NULL or misaligned mask.
+extern "C" int etm_rollout_sample_branched_masked(const float *logits, const float *value, const float *uniforms, const int64_t *forced,
+                                                  int64_t *t_dev, int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values,
+                                                  int W, const int32_t *branch_sizes, int n_branches, const int64_t *action_mask,
+                                                  void *stream) {
+  if (!action_mask) return ETM_EINVAL;
+  return rollout_sample_impl(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W,
+                             etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, action_mask, stream);
 }
 
 static int rollout_policy_impl(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv, const float *bv,
                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
-                               int W, int A, int hid, int stage_W, const int32_t *branch_sizes, int n_branches, void *stream) {
+                               int W, int A, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,
+                               const int64_t *action_mask, void *stream) {
   (void)hipGetLastError();
   if (!h || !wp || !bp || !wv || !bv || !uniforms || !t_dev || !actions || !st_actions || !st_logp || !st_values ||
       !sync_counter || W <= 0 || A <= 0 || hid <= 0 || stage_W < W)
@@ -297,13 +350,20 @@ static int rollout_policy_impl(const float *h, const float *h_bias, const float 
   if (host_flag && !host_actions) return ETM_EINVAL;
   EtmBranches br;
   if (const int rc = etm_branches_make(branch_sizes, n_branches, A, &br)) return rc;
+  if (const int rc = etm_action_mask_check(action_mask, A)) return rc;
   const size_t lds = (size_t)(A + 1) * sizeof(float);
   if (lds > 64 * 1024) return ETM_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   EtmProfScope prof(ETM_K_ROLLOUT_SAMPLE, st);
-  hipLaunchKernelGGL(rollout_policy_kernel, dim3((unsigned)W), dim3(256), lds, st, h, wp, bp, wv, bv, h_bias, uniforms, (const long long *)forced,
-                     (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values, (long long *)host_actions,
-                     (long long *)host_flag, (int *)sync_counter, W, A, hid, stage_W, br);
+  if (action_mask)
+    hipLaunchKernelGGL(rollout_policy_masked_kernel, dim3((unsigned)W), dim3(256), lds, st, h, wp, bp, wv, bv, h_bias, uniforms,
+                       (const long long *)forced, (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values,
+                       (long long *)host_actions, (long long *)host_flag, (int *)sync_counter, W, A, hid, stage_W, br,
+                       (const long long *)action_mask);
+  else
+    hipLaunchKernelGGL(rollout_policy_kernel, dim3((unsigned)W), dim3(256), lds, st, h, wp, bp, wv, bv, h_bias, uniforms, (const long long *)forced,
+                       (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values, (long long *)host_actions,
+                       (long long *)host_flag, (int *)sync_counter, W, A, hid, stage_W, br);
   return etm_launch_status();
 }
 
@@ -312,7 +372,7 @@ extern "C" int etm_rollout_policy(const float *h, const float *h_bias, const flo
                                   float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
                                   int W, int A, int hid, int stage_W, void *stream) {
   return rollout_policy_impl(h, h_bias, wp, bp, wv, bv, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions,
-                             host_flag, sync_counter, W, A, hid, stage_W, nullptr, 1, stream);
+                             host_flag, sync_counter, W, A, hid, stage_W, nullptr, 1, nullptr, stream);
 }
 
 extern "C" int etm_rollout_policy_branched(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv,
@@ -322,7 +382,20 @@ extern "C" int etm_rollout_policy_branched(const float *h, const float *h_bias, 
                                            void *stream) {
   return rollout_policy_impl(h, h_bias, wp, bp, wv, bv, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions,
                              host_flag, sync_counter, W, etm_branches_total(branch_sizes, n_branches), hid, stage_W, branch_sizes,
-                             n_branches, stream);
+                             n_branches, nullptr, stream);
+}
+// Invalid-action masks: etm_rollout_policy_branched with action_mask [W] int64 (this group's workers; device or pinned host memory,
+// read in place), as etm_rollout_sample_branched_masked.
+extern "C" int etm_rollout_policy_branched_masked(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv,
+                                                  const float *bv, const float *uniforms, const int64_t *forced, int64_t *t_dev,
+                                                  int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values,
+                                                  int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter, int W, int hid,
+                                                  int stage_W, const int32_t *branch_sizes, int n_branches, const int64_t *action_mask,
+                                                  void *stream) {
+  if (!action_mask) return ETM_EINVAL;
+  return rollout_policy_impl(h, h_bias, wp, bp, wv, bv, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions,
+                             host_flag, sync_counter, W, etm_branches_total(branch_sizes, n_branches), hid, stage_W, branch_sizes,
+                             n_branches, action_mask, stream);
 }
 
 extern "C" int etm_rollout_sample_gaussian(const float *mean, const float *value, const float *log_std, const float *normals,

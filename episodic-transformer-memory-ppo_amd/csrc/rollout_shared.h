@@ -79,6 +79,8 @@ struct RfParams {
   int map_mode;                      // block -> (worker, member) placement, see etm_rollout_trxl_set_placement
   float eps, sqrt_d;
   RfBox box;                         // Box policies only (the BOX instantiations): the float action tables
+  // (last: every member above keeps its place in the kernels' argument block)
+  const long long *am;               // the masked instantiations only: [W] action-mask words of the step (device or pinned host memory)
 };
 
 namespace {

@@ -44,7 +44,12 @@ def run_episode(model, env, config, device, max_steps=None, deterministic=False)
         mask = memory_mask[max(0, min(t, memory_length - 1))].unsqueeze(0)
         if hasattr(env, "render"):
             env.render()
-        policy, _value, new_memory = model(obs_t, in_memory, mask, indices)
+        # an environment that declares its legal actions (``action_masks() -> bool [sum A_b]``, sb3-contrib's protocol) is asked for
+        # the mask of this observation: the policy then puts no probability on an illegal action
+        masked = {}
+        if hasattr(env, "action_masks") and not getattr(model, "continuous", False):
+            masked["action_mask"] = np.asarray(env.action_masks(), dtype=bool).reshape(1, -1)
+        policy, _value, new_memory = model(obs_t, in_memory, mask, indices, **masked)
         memory[:, t] = new_memory.detach()
         if getattr(model, "continuous", False):      # Box: one Gaussian draw of A dimensions, clipped to the space's bounds
             a = (policy[0].mean if deterministic else policy[0].sample())[0].cpu().numpy()

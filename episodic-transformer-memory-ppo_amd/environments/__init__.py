@@ -60,3 +60,53 @@ def action_space_kind(space):
             raise ValueError(f"Box action space with low {low.tolist()} above high {high.tolist()}")
         return ActionKind("box", (A,), low, high)
     return ActionKind("discrete", action_space_shape(space))
+
+
+MAX_MASKED_ACTIONS = 63      # columns of the concatenated policy head that one 64-bit action-mask word describes
+
+
+def pack_action_masks(masks, out=None):
+    """bool [W, sum A_b] (sb3-contrib's flat ``action_masks()`` layout: the branches' actions side by side) -> uint64 [W]: bit j of
+    worker w's word is set when column j is allowed.  The one place that packs; at most 63 columns."""
+    import numpy as np
+    m = np.asarray(masks)
+    if m.ndim == 1:
+        m = m[None, :]
+    if m.ndim != 2 or m.shape[1] < 1 or m.shape[1] > MAX_MASKED_ACTIONS:
+        raise ValueError(f"action masks are bool [W, A] with 1 <= A <= {MAX_MASKED_ACTIONS} (all branches together), got {m.shape}")
+    bits = np.uint64(1) << np.arange(m.shape[1], dtype=np.uint64)
+    words = (m.astype(bool).astype(np.uint64) * bits[None, :]).sum(axis=1, dtype=np.uint64)
+    if out is None:
+        return words
+    out.view(np.uint64)[...] = words
+    return out
+
+
+def branch_bit_masks(branches):
+    """uint64 [B]: the bits [off_b, off_b + A_b) of branch b in a mask word."""
+    import numpy as np
+    out, off = np.zeros(len(branches), dtype=np.uint64), 0
+    for b, a in enumerate(branches):
+        out[b] = ((1 << int(a)) - 1) << off
+        off += int(a)
+    return out
+
+
+def empty_mask_branches(words, branches, bits=None):
+    """bool [W, B]: branch b of worker w has no allowed action in ``words`` (uint64 / int64 [W]) -- one vectorised test over the
+    workers and branches.  ``bits``: ``branch_bit_masks(branches)`` when the caller keeps it."""
+    import numpy as np
+    w = np.asarray(words)
+    w = w.view(np.uint64) if w.dtype == np.int64 else w.astype(np.uint64, copy=False)
+    bits = branch_bit_masks(branches) if bits is None else bits
+    return (w[:, None] & bits[None, :]) == 0
+
+
+def valid_action_share(words, total):
+    """Mean share of set bits among the ``total`` columns over all words (any shape)."""
+    import numpy as np
+    w = np.asarray(words).reshape(-1)
+    w = w.view(np.uint64) if w.dtype == np.int64 else w.astype(np.uint64)
+    w = w & np.uint64((1 << int(total)) - 1)
+    bits = np.unpackbits(w.view(np.uint8)).sum()
+    return float(bits) / float(max(w.size, 1) * int(total))

@@ -43,12 +43,19 @@ exact and floor lands in 0 .. 255), ``observation_dtype: uint8`` (which requires
 ``observation_space.dtype == np.uint8``.  Both derive from the same float stream, so the two forms are twins from the config alone --
 whatever ``pool``, ``copy_threads`` and ``gen_threads`` are -- and the reward / done streams are those of the plain config.  A ring is
 converted once at construction; fresh draws go into a scratch row (the generators keep producing floats) and are converted from there.
+
+Invalid-action masks (vector form): ``action_mask_p: p`` makes every action of every (worker, emitted observation) invalid with
+probability p -- one uniform per action from a generator of its own per worker, ``default_rng((seed + worker_id, 2))``, an action being
+invalid when its draw is below p, except that each branch's LARGEST draw always stays valid (no branch is ever empty).
+``action_masks()`` returns the words of the observations last returned (vec_env protocol).  The observation, reward and done streams
+keep their bits, and without the key nothing is drawn and the front-end has no ``action_masks``.
 """
 from types import SimpleNamespace
 
 import numpy as np
 
 _CHUNK = 4096
+_MASK_CHUNK = 256       # emitted observations per draw of the action-mask uniforms (action_mask_p)
 _copiers = {}   # threads -> (library, copier handle): one pool of helper threads per process, shared by all front-ends
 _copier_spin = None   # None: the library's default (helpers spin ~1 ms between jobs); False: they sleep at once (etm/hostcpu.py)
 
@@ -239,7 +246,8 @@ class SyntheticVecEnv:
 
     def __init__(self, num_envs, obs_shape=(3, 84, 84), num_actions=3, max_episode_steps=96, seed=0,
                  p_reward=0.05, p_done=0.02, pool=64, first_worker_id=0, copy_threads=1, row_chunks=None, step_cost_us=0.0, min_chunked_envs=None,
-                 gen_threads=1, continuous_actions=None, action_low=-1.0, action_high=1.0, observation_levels=None, observation_dtype=None):
+                 gen_threads=1, continuous_actions=None, action_low=-1.0, action_high=1.0, observation_levels=None, observation_dtype=None,
+                 action_mask_p=None):
         """``copy_threads`` > 1: the observation rows of a step are written by that many threads (the kernel library's host
         copier; the reference's workers write theirs in n_workers processes) instead of one numpy copy.  ``pool`` = 0: every row is a
         fresh draw of its worker's generator (module docstring); ``gen_threads`` > 1: drawn by that many threads."""
@@ -304,6 +312,43 @@ class SyntheticVecEnv:
         self._done_c = np.zeros((_CHUNK, self.num_envs), dtype=bool)
         self._any_done = np.zeros(_CHUNK, dtype=bool)
         self._info_c = {}
+        # action_mask_p (module docstring): the words of a chunk of emitted observations at a time, from the workers' own generators
+        self._mask_p = None
+        if action_mask_p is not None:
+            if box is not None:
+                raise ValueError("action_mask_p: a Box action space has no action masks")
+            from environments import MAX_MASKED_ACTIONS
+            if not 0.0 <= float(action_mask_p) < 1.0 or self.num_actions > MAX_MASKED_ACTIONS:
+                raise ValueError(f"action_mask_p is a probability in [0, 1) for at most {MAX_MASKED_ACTIONS} actions (all branches together)")
+            self._mask_p = float(action_mask_p)
+            self._mask_rngs = [np.random.default_rng((seed + first_worker_id + w, 2)) for w in range(self.num_envs)]
+            self._mask_words = np.zeros((_MASK_CHUNK, self.num_envs), dtype=np.uint64)
+            self._mask_pos = _MASK_CHUNK          # position of the NEXT emitted observation's words
+            self._mask_now = np.zeros(self.num_envs, dtype=np.uint64)
+            self.action_masks = self._action_masks
+
+    def _next_masks(self):
+        """The words of the observation being emitted now (``reset`` / ``step``) -> ``_mask_now``."""
+        if self._mask_pos >= _MASK_CHUNK:
+            A = self.num_actions
+            u = np.stack([rng.random((_MASK_CHUNK, A)) for rng in self._mask_rngs], axis=1)        # [chunk, W, A]
+            valid = u >= self._mask_p
+            off = 0
+            for a in self.action_space_shape:          # each branch's largest draw stays valid
+                seg = u[:, :, off:off + a]
+                np.put_along_axis(valid[:, :, off:off + a], seg.argmax(axis=2)[:, :, None], True, axis=2)
+                off += a
+            bits = np.uint64(1) << np.arange(A, dtype=np.uint64)
+            self._mask_words = (valid.astype(np.uint64) * bits).sum(axis=2, dtype=np.uint64)
+            self._mask_pos = 0
+        self._mask_now = self._mask_words[self._mask_pos]
+        self._mask_pos += 1
+
+    def _action_masks(self, out=None):
+        if out is None:
+            return self._mask_now.copy()
+        out.view(np.uint64)[...] = self._mask_now
+        return out
 
     ROW_CHUNKS = 2   # on_rows granularity (vec_env protocol); 2 measured best: every upload call costs ~9 us of host time
     MIN_CHUNKED_ENVS = 16   # fewer environments (a small worker group): one notification for all rows
@@ -379,6 +424,8 @@ class SyntheticVecEnv:
         self._ret[:] = 0.0
         if self._upos < _CHUNK:
             self._plan(self._upos)           # the rest of the current chunk, from fresh episodes
+        if self._mask_p is not None:
+            self._next_masks()
         return self._emit(out)
 
     def _plan(self, p0):
@@ -423,6 +470,8 @@ class SyntheticVecEnv:
             while time.perf_counter() < t_end:
                 pass
         obs = self._emit(out, on_rows)
+        if self._mask_p is not None:
+            self._next_masks()
         if self._upos >= _CHUNK:
             for w, rng in enumerate(self._rngs):
                 self._u[w] = rng.random((_CHUNK, 2))

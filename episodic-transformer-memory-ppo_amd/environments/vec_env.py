@@ -23,6 +23,16 @@ is exactly what upstream's loop does by hand (trainer.py:195-201).
         replaces in the returned rows), a copy in the environment's own dtype (uint8 stays bytes).  ``SerialVecEnv`` and ``PipeVecEnv``
         add it; ``SyntheticVecEnv`` never reports a truncation (its terminal frame is deliberately not drawn: the key is a no-op there),
         and the worker processes' shared segment (``worker_processes: true``) has no row for it -- that combination is refused.
+    action_masks(out=None) -> uint64 [W] (optional; needed by ``action_masks: true``): the invalid-action words of the observations
+        LAST RETURNED by ``reset`` / ``step`` -- after an auto-reset the new episode's.  Bit j of a worker's word is set when column j
+        of the concatenated policy head is allowed: the flat layout of sb3-contrib's ``action_masks()``, branch b of a MultiDiscrete
+        space owning bits [off_b, off_b + A_b); bits past the last column are ignored; at most 63 columns; every branch must keep at
+        least one action (the trainer raises ValueError on a word with an empty branch before it launches the step).  ``out``:
+        an int64 or uint64 [W] array to fill.  A single environment offers ``action_masks() -> bool [sum A_b]`` for its current
+        observation (sb3-contrib's name and layout); ``environments.pack_action_masks`` is the one place that packs.
+        ``SerialVecEnv`` asks its environments, ``PipeVecEnv`` sends the ``("action_masks", None)`` command to every worker and
+        then collects, ``CompositeVecEnv`` fills its parts' slices, ``SyntheticVecEnv`` draws them (``action_mask_p``).  Box spaces
+        have no masks, and the worker processes' shared segment has no row for a word (refused, like ``bootstrap_truncated``).
 
 * ``SerialVecEnv``  -- wraps in-process single envs with the upstream env API.
 * ``PipeVecEnv``    -- wraps upstream-protocol ``Worker`` subprocesses (worker.py), one pipe round trip per step.
@@ -30,7 +40,7 @@ is exactly what upstream's loop does by hand (trainer.py:195-201).
 """
 import numpy as np
 
-from environments import action_space_kind, observation_dtype
+from environments import action_space_kind, observation_dtype, pack_action_masks
 
 
 class _VecBase:
@@ -49,6 +59,9 @@ class _VecBase:
             on_rows(sent_upto, hi)
             sent_upto = hi
         return sent_upto
+
+    def _mask_out(self, out):
+        return out if out is not None else np.zeros(self.num_envs, dtype=np.uint64)
 
 
 class SerialVecEnv(_VecBase):
@@ -87,6 +100,12 @@ class SerialVecEnv(_VecBase):
             sent = self._notify(on_rows, w + 1, sent)
         return out, rewards, dones, infos
 
+    def action_masks(self, out=None):
+        if not all(hasattr(e, "action_masks") for e in self.envs):
+            raise AttributeError("action_masks: an environment of this front-end offers no action_masks()")
+        rows = np.stack([np.asarray(e.action_masks(), dtype=bool).reshape(-1) for e in self.envs])
+        return pack_action_masks(rows, out=self._mask_out(out))
+
     def close(self):
         for e in self.envs:
             e.close()
@@ -106,6 +125,7 @@ class PipeVecEnv(_VecBase):
         self.action_space_shape = self.action_kind.shape
         self.num_actions = sum(self.action_space_shape)
         self.max_episode_steps = int(probe.max_episode_steps)
+        self._has_masks = hasattr(probe, "action_masks")
         probe.close()
         self.num_envs = num_envs
         self.workers = [Worker(env_config, worker_id=first_worker_id + w) for w in range(num_envs)]
@@ -138,6 +158,14 @@ class PipeVecEnv(_VecBase):
             out[w] = obs
             sent = self._notify(on_rows, w + 1, sent)
         return out, rewards, dones, infos
+
+    def action_masks(self, out=None):
+        if not self._has_masks:
+            raise AttributeError("action_masks: the environment of this front-end offers no action_masks()")
+        for wk in self.workers:
+            wk.child.send(("action_masks", None))
+        rows = np.stack([np.asarray(self._recv(wk), dtype=bool).reshape(-1) for wk in self.workers])
+        return pack_action_masks(rows, out=self._mask_out(out))
 
     @staticmethod
     def _recv(wk):
@@ -193,6 +221,12 @@ class CompositeVecEnv(_VecBase):
             infos.extend(inf)
         return out, rewards, dones, infos
 
+    def action_masks(self, out=None):
+        out = self._mask_out(out)
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.action_masks(out=out[lo:hi])
+        return out
+
     def close(self):
         for p in self.parts:
             p.close()
@@ -207,7 +241,7 @@ def make_vec_env(env_config: dict, num_envs: int, first_worker_id: int = 0, grou
     if env_config["type"] == "Synthetic":
         from environments.synthetic import SyntheticVecEnv
         keys = ("obs_shape", "num_actions", "max_episode_steps", "seed", "p_reward", "p_done", "pool", "copy_threads", "row_chunks", "step_cost_us", "gen_threads",
-                "continuous_actions", "action_low", "action_high", "observation_levels", "observation_dtype")
+                "continuous_actions", "action_low", "action_high", "observation_levels", "observation_dtype", "action_mask_p")
         kw = {k: env_config[k] for k in keys if k in env_config}
         if "obs_shape" in kw:
             kw["obs_shape"] = tuple(kw["obs_shape"])

@@ -7,7 +7,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: torch ships its ow
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libetm_hip.so")     # (diagnostic tools that load another build assign this before load())
-ABI_VERSION = 57
+ABI_VERSION = 58
 
 _lib = None
 
@@ -189,6 +189,13 @@ SIGNATURES = {
     "etm_profile_collect": (_I, [_P, _P]),
     "etm_ppo_loss": (_I, [_P, _P, _L, _P, _L, _P, _P, _P, _P, _D, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _L, _P, _I, _I, _P]),
 }
+# invalid-action masks (ABI 58): the masked twins take the arguments of their entry with the mask word array in front of the stream
+for _name, _extra in (("etm_rollout_sample_branched", [_P]), ("etm_rollout_policy_branched", [_P]), ("etm_rollout_trxl_branched", [_P]),
+                      ("etm_rollout_trxl_group_branched", [_P]), ("etm_heads_loss", [_P]), ("etm_heads_loss_branched", [_P]),
+                      ("etm_ppo_loss", [_P, _I])):
+    _res, _args = SIGNATURES[_name]
+    SIGNATURES[_name + "_masked"] = (_res, _args[:-1] + _extra + _args[-1:])
+del _name, _extra, _res, _args
 
 
 def load():

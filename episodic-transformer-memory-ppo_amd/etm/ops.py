@@ -813,14 +813,49 @@ def _branch_table(sizes):
     return (ctypes.c_int32 * len(sizes))(*sizes), len(sizes)
 
 
-def rollout_sample(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, branches=None):
+from environments import MAX_MASKED_ACTIONS      # noqa: E402  (columns of the policy head that a 64-bit action-mask word describes)
+
+
+def _mask_words(action_mask, rows, total, what, device=True):
+    """The int64 word array of an ``action_mask=`` argument ([rows]; bit j = column j of the ``total`` concatenated logits is
+    allowed) for the *_masked entries; ``device``: it must live on the device (else pinned host memory is fine too)."""
+    if action_mask.dtype != torch.int64 or action_mask.dim() != 1 or action_mask.shape[0] != rows or not action_mask.is_contiguous():
+        raise ValueError(f"{what}: action_mask must be a contiguous int64 [{rows}] word array, got {tuple(action_mask.shape)} {action_mask.dtype}")
+    if total > MAX_MASKED_ACTIONS:
+        raise ValueError(f"{what}: action masks describe at most {MAX_MASKED_ACTIONS} actions (all branches together), not {total}")
+    if device:
+        _need_dev(action_mask)
+    elif not (action_mask.is_cuda or action_mask.is_pinned()):
+        raise ValueError(f"{what}: action_mask must be in device or pinned host memory")
+    return action_mask
+
+
+def _sizes_or_single(branches, A):
+    """Branch sizes for the masked entries, which take a Discrete policy as one branch."""
+    sizes = _branch_sizes(branches)
+    return (int(A),) if sizes is None else sizes
+
+
+def rollout_sample(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, branches=None, action_mask=None):
     """Categorical sampling + staging of one rollout step (in place; increments t_dev).  ``forced`` (optional): time-major int64
     table [S, W]; entries >= 0 replace the sample of that (step, worker).  ``branches`` (optional, MultiDiscrete): the branch sizes;
     ``logits`` [W, sum] holds the branches' logits side by side, every branch is sampled on its own segment with its own uniform, and
-    ``uniforms`` / ``forced`` / ``st_actions`` / ``st_logp`` are [S, W, B], ``actions`` [W, B] (etm_rollout_sample_branched)."""
+    ``uniforms`` / ``forced`` / ``st_actions`` / ``st_logp`` are [S, W, B], ``actions`` [W, B] (etm_rollout_sample_branched).
+    ``action_mask`` (optional): int64 [W], the workers' invalid-action words of this step (bit j = logit column j is allowed; no
+    branch empty): every branch is drawn over its valid actions only (etm_rollout_sample_branched_masked)."""
     lib = _lib.load()
     W, A = logits.shape
     logits, value = _f32c(logits, "logits"), _f32c(value, "value")
+    if action_mask is not None:
+        sizes = _sizes_or_single(branches, A)
+        if sum(sizes) != A:
+            raise ValueError(f"rollout_sample: branches {sizes} do not add up to the {A} logit columns")
+        tab, nbr = _branch_table(sizes)
+        am = _mask_words(action_mask, W, A, "rollout_sample", device=False)
+        _lib.check(lib.etm_rollout_sample_branched_masked(_ptr(logits), _ptr(value), _ptr(uniforms), _ptr(forced), _ptr(t_dev), _ptr(actions),
+                                                          _ptr(st_actions), _ptr(st_logp), _ptr(st_values), W, tab, nbr, am.data_ptr(),
+                                                          _stream()), "etm_rollout_sample_branched_masked")
+        return
     sizes = _branch_sizes(branches)
     if sizes is None:
         _lib.check(lib.etm_rollout_sample(_ptr(logits), _ptr(value), _ptr(uniforms), _ptr(forced), _ptr(t_dev), _ptr(actions),
@@ -895,11 +930,13 @@ def rollout_policy_gaussian(h2, mean_head, value_head, log_std, normals, forced,
 
 
 def rollout_policy(h2, policy_head, value_head, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values,
-                   host_actions=None, host_flag=None, h_bias=None, w_off=0, branches=None):
+                   host_actions=None, host_flag=None, h_bias=None, w_off=0, branches=None, action_mask=None):
     """``rollout_heads`` + ``rollout_sample`` in one launch; ``host_actions`` / ``host_flag``: pinned int64 tensors that receive
     the actions and then the incremented step counter (the host spins on the flag).  ``forced`` (optional): time-major int64 table
     [S, W_total]; entries >= 0 replace the sample of that (step, worker).  ``branches`` (optional, MultiDiscrete): the branch sizes;
-    ``policy_head`` is then the branches' heads concatenated ([sum, hid]) and the tables are as in ``rollout_sample``."""
+    ``policy_head`` is then the branches' heads concatenated ([sum, hid]) and the tables are as in ``rollout_sample``.
+    ``action_mask`` (optional): int64 [W] words of THIS group's workers, device or pinned host memory (read in place), as in
+    ``rollout_sample`` (etm_rollout_policy_branched_masked)."""
     lib = _lib.load()
     W, A = h2.shape[0], policy_head.weight.shape[0]
     hid = h2.shape[1] // 2
@@ -915,6 +952,16 @@ def rollout_policy(h2, policy_head, value_head, uniforms, forced, t_dev, actions
     sizes = _branch_sizes(branches)
     nb_ = 1 if sizes is None else len(sizes)
     off = lambda t: None if t is None else t.data_ptr() + w_off * nb_ * t.element_size()
+    if action_mask is not None:
+        tab, nbr = _branch_table(_sizes_or_single(branches, A))
+        am = _mask_words(action_mask, W, A, "rollout_policy", device=False)
+        _lib.check(lib.etm_rollout_policy_branched_masked(_ptr(h2), _ptr(h_bias), _ptr(policy_head.weight), _ptr(policy_head.bias),
+                                                          _ptr(value_head.weight), _ptr(value_head.bias), off(uniforms), off(forced),
+                                                          _ptr(t_dev), _ptr(actions), off(st_actions), off(st_logp),
+                                                          st_values.data_ptr() + w_off * st_values.element_size(), ha, hf, _ptr(sync), W,
+                                                          hid, stage_w, tab, nbr, am.data_ptr(), _stream()),
+                   "etm_rollout_policy_branched_masked")
+        return
     if sizes is None:
         _lib.check(lib.etm_rollout_policy(_ptr(h2), _ptr(h_bias), _ptr(policy_head.weight), _ptr(policy_head.bias), _ptr(value_head.weight),
                                           _ptr(value_head.bias), off(uniforms), off(forced), _ptr(t_dev), _ptr(actions), off(st_actions),
@@ -983,7 +1030,8 @@ def rollout_trxl_supported(D, H, L, hid, A, nb, gaussian=False):
 
 
 def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head, uniforms, forced, t_dev, actions, st_actions, st_logp,
-                 st_values, scratch, host_actions=None, host_flag=None, w_off=0, tail=None, h_bias=None, window=None, branches=None, box=None):
+                 st_values, scratch, host_actions=None, host_flag=None, w_off=0, tail=None, h_bias=None, window=None, branches=None, box=None,
+                 action_mask=None):
     """Transformer + hidden / output heads + sampling of one rollout step of a worker group in one launch (etm_rollout_trxl).
     ``fused``: the transposed fixed-address weight copies of ``ActorCriticModel.refresh_rollout_weights`` (dict with the host
     pointer table ``blocks``); ``kv`` the group's K | V cache [W, T, blocks, 2D]; ``scratch`` from ``rollout_trxl_scratch``; the
@@ -994,7 +1042,9 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
     ``bank[slot_l, step_l]`` and their K | V projection into ``kv[w, step_l]``.  ``branches`` (optional, MultiDiscrete): as in
     ``rollout_policy`` (etm_rollout_trxl_branched / etm_rollout_trxl_group_branched).  ``box`` (optional, Box policy): (log_std, low,
     high); ``policy_head`` is then the mean head, ``uniforms`` the normals and ``forced`` the NaN-or-action table, both float
-    [S, W_total, A], ``actions`` / ``st_actions`` / ``host_actions`` float (etm_rollout_trxl_gaussian / _group_gaussian)."""
+    [S, W_total, A], ``actions`` / ``st_actions`` / ``host_actions`` float (etm_rollout_trxl_gaussian / _group_gaussian).
+    ``action_mask`` (optional, categorical policies): int64 [W] words of this group's workers, device or pinned host memory (read in
+    place at the start of the launch), as in ``rollout_sample`` (etm_rollout_trxl_branched_masked / _group_branched_masked)."""
     lib = _lib.load()
     h_in = _f32c(h_in, "h_in")
     h_splits = 0
@@ -1039,6 +1089,15 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
             int(fused.get("gtrxl", 0)), W, D, fused["H"], L, hid)
     # ``fused`` with the group packings (ActorCriticModel._rfg, "group": True) selects the group form of the kernel: same arguments
     group = bool(fused.get("group"))
+    if action_mask is not None:
+        if box is not None:
+            raise ValueError("rollout_trxl: a Box policy has no action mask")
+        tab, nbr = _branch_table(_sizes_or_single(branches, A))
+        am = _mask_words(action_mask, W, A, "rollout_trxl", device=False)
+        entry, name = ((lib.etm_rollout_trxl_group_branched_masked, "etm_rollout_trxl_group_branched_masked") if group
+                       else (lib.etm_rollout_trxl_branched_masked, "etm_rollout_trxl_branched_masked"))
+        _lib.check(entry(*args, stage_w, tab, nbr, am.data_ptr(), _stream()), name)
+        return
     if box is not None:
         log_std, low, high = box
         _check_box_tables(A, W, log_std, uniforms, forced, actions, st_actions)
@@ -2050,7 +2109,7 @@ def arena_digest(x, out=None, partial=None, n_partial=ARENA_DIGEST_PARTIALS):
 class _PpoLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, value, actions, old_logp, adv, old_value, stats3, branch, n_branches, clip, vf_coef, beta,
-                include_value, dyn=None):
+                include_value, dyn=None, action_mask=None, mask_shift=0):
         lib = _lib.load()
         _need_dev(logits, value, actions, old_logp, adv, old_value, stats3)
         logits = _f32c(logits, "logits")
@@ -2067,10 +2126,15 @@ class _PpoLossFn(torch.autograd.Function):
         d_value = torch.empty_like(value)
         nbytes = lib.etm_ppo_loss_workspace_bytes(N)
         ws = workspace(nbytes, dev, "ppo")
-        rc = lib.etm_ppo_loss(_ptr(logits), actions.data_ptr() + 8 * branch, B, old_logp.data_ptr() + 4 * branch, B, _ptr(adv),
-                              _ptr(old_value), _ptr(value), _ptr(stats3), float(clip), float(vf_coef), float(beta),
-                              1.0 / (N * n_branches), 1.0 / N, 1.0 / N, 1 if include_value else 0, _ptr(out8), _ptr(d_logits),
-                              _ptr(d_value), _ptr(ws), nbytes, _ptr(dyn), N, A, _stream())
+        args = (_ptr(logits), actions.data_ptr() + 8 * branch, B, old_logp.data_ptr() + 4 * branch, B, _ptr(adv),
+                _ptr(old_value), _ptr(value), _ptr(stats3), float(clip), float(vf_coef), float(beta),
+                1.0 / (N * n_branches), 1.0 / N, 1.0 / N, 1 if include_value else 0, _ptr(out8), _ptr(d_logits),
+                _ptr(d_value), _ptr(ws), nbytes, _ptr(dyn), N, A)
+        if action_mask is None:
+            rc = lib.etm_ppo_loss(*args, _stream())
+        else:        # this branch's actions are bits [mask_shift, mask_shift + A) of the samples' words
+            am = _mask_words(action_mask, N, int(mask_shift) + A, "ppo_loss")
+            rc = lib.etm_ppo_loss_masked(*args, am.data_ptr(), int(mask_shift), _stream())
         _lib.check(rc, "etm_ppo_loss")
         ctx.save_for_backward(d_logits, d_value)
         ctx.include_value = include_value
@@ -2081,10 +2145,10 @@ class _PpoLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_stats):
         if g_loss is None:
-            return (None,) * 14
+            return (None,) * 16
         d_logits, d_value = ctx.saved_tensors
         gv = d_value * g_loss if ctx.include_value else None
-        return d_logits * g_loss, gv, None, None, None, None, None, None, None, None, None, None, None, None
+        return (d_logits * g_loss, gv) + (None,) * 14
 
 
 class _HeadsLossFn(torch.autograd.Function):
@@ -2095,7 +2159,7 @@ class _HeadsLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn, unit_grad,
-                sizes=None, log_std=None):
+                sizes=None, log_std=None, action_mask=None):
         lib = _lib.load()
         _need_dev(h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3)
         h = _f32c(h, "h")
@@ -2122,6 +2186,17 @@ class _HeadsLossFn(torch.autograd.Function):
                                              _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
                                              float(vf_coef), float(beta), 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
                                              _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, A, _stream())
+        elif action_mask is not None:
+            # invalid-action masks: the samples' words, Discrete or MultiDiscrete (wb / bb concatenated as below)
+            am = _mask_words(action_mask, N, A, "heads_ppo_loss")
+            if sizes is None:
+                rc = lib.etm_heads_loss_masked(*common, 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8),
+                                               0, 0, _ptr(ws), nbytes, N, hid, A, am.data_ptr(), _stream())
+            else:
+                tab, nbr = _branch_table(sizes)
+                rc = lib.etm_heads_loss_branched_masked(*common, 1.0 / (N * nbr), 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
+                                                        _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, tab, nbr, am.data_ptr(),
+                                                        _stream())
         elif sizes is None:
             rc = lib.etm_heads_loss(*common, 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8),
                                     0, 0, _ptr(ws), nbytes, N, hid, A, _stream())
@@ -2142,7 +2217,7 @@ class _HeadsLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_stats):
         if g_loss is None:
-            return (None,) * 21
+            return (None,) * 22
         h, wlp, wlv, gm_p, gm_v, sums = ctx.saved_tensors
         hid, A = ctx.dims
         unit = ctx.unit                 # the caller promises loss.backward() on the returned loss itself: g_loss == 1, nothing to scale
@@ -2161,7 +2236,7 @@ class _HeadsLossFn(torch.autograd.Function):
         o = (3 + A) * hid
         return (dh, dwlp, s[:hid], dwlv, s[hid:2 * hid], s[3 * hid:o].view(A, hid), s[o:o + A], s[2 * hid:3 * hid].view(1, hid),
                 s[o + A:o + A + 1], None, None, None, None, None, None, None, None, None, None, None,
-                s[o + A + 6:o + 2 * A + 6] if ctx.gauss else None)
+                s[o + A + 6:o + 2 * A + 6] if ctx.gauss else None, None)
 
 
 def _branch_list(branch):
@@ -2206,11 +2281,14 @@ def heads_ppo_loss_gaussian(h, lin_policy, lin_value, mean_head, log_std, value_
 
 
 def heads_ppo_loss(h, lin_policy, lin_value, branch, value_head, actions, old_logp, adv, old_value, clip, vf_coef, beta, stats3=None, dyn=None,
-                   unit_grad=False):
+                   unit_grad=False, action_mask=None):
     """model.py:101-110 + the PPO loss of ``ppo_loss``, from the transformer output ``h`` [N, D]: -> (loss scalar with grad, stats[6]).
     ``branch``: the policy branch, or the list of branches of a MultiDiscrete policy (``actions`` / ``old_logp`` [N, B]; the semantics of
     ``ppo_loss`` over branches).  ``unit_grad=True``: the caller runs ``backward()`` on the returned loss itself (upstream gradient 1):
-    no scaling launches, weight gradients of the hidden heads deferrable.  See _HeadsLossFn."""
+    no scaling launches, weight gradients of the hidden heads deferrable.  See _HeadsLossFn.
+    ``action_mask`` (optional): int64 [N] device words, bit j = column j of the concatenated branch heads was allowed when the sample
+    was drawn: per branch the log-sum-exp, log-prob and entropy run over the valid actions only and the logits of the others get a
+    zero gradient (etm_heads_loss_masked / _branched_masked); None = exactly the calls without masks."""
     if stats3 is None:
         stats3 = adv_stats(adv)
     if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
@@ -2224,25 +2302,35 @@ def heads_ppo_loss(h, lin_policy, lin_value, branch, value_head, actions, old_lo
         sizes = tuple(int(b.weight.shape[0]) for b in br)
     loss, st = _HeadsLossFn.apply(h, lin_policy.weight, lin_policy.bias, lin_value.weight, lin_value.bias, wb, bb,
                                   value_head.weight, value_head.bias, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn,
-                                  unit_grad, sizes)
+                                  unit_grad, sizes, None, action_mask)
     return loss, st[:6]
 
 
-def ppo_loss(logits_list, value, actions, old_logp, adv, old_value, clip, vf_coef, beta, stats3=None, dyn=None):
+def ppo_loss(logits_list, value, actions, old_logp, adv, old_value, clip, vf_coef, beta, stats3=None, dyn=None, action_mask=None):
     """PPO loss over all action branches.  Returns (loss scalar with grad, stats[6] device tensor in trainer.py:318-323 order).
-    ``dyn``: optional float64 device tensor (clip, beta) read by the kernels at run time instead of the two scalars."""
+    ``dyn``: optional float64 device tensor (clip, beta) read by the kernels at run time instead of the two scalars.
+    ``action_mask`` (optional): int64 [N] device words as in ``heads_ppo_loss``; branch b reads its bits at the offset of its logits
+    among the concatenated branches (etm_ppo_loss_masked); None = exactly the calls without masks."""
     if stats3 is None:
         stats3 = adv_stats(adv)
     if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
         raise TypeError("ppo_loss: dyn must be a float64 device tensor (clip, beta)")
     nb = len(logits_list)
-    loss, st = _PpoLossFn.apply(logits_list[0], value, actions, old_logp, adv, old_value, stats3, 0, nb, clip, vf_coef, beta, True, dyn)
+    if action_mask is not None:
+        shifts, total = [], 0
+        for lg in logits_list:
+            shifts.append(total)
+            total += int(lg.shape[1])
+        mk = lambda b: (action_mask, shifts[b])
+    else:
+        mk = lambda b: ()
+    loss, st = _PpoLossFn.apply(logits_list[0], value, actions, old_logp, adv, old_value, stats3, 0, nb, clip, vf_coef, beta, True, dyn, *mk(0))
     if nb == 1:
         return loss, st[:6]
     pol, ent, kl, cf = st[0], st[3], st[4], st[5]
     total = loss
     for b in range(1, nb):
-        l_b, s_b = _PpoLossFn.apply(logits_list[b], value, actions, old_logp, adv, old_value, stats3, b, nb, clip, vf_coef, beta, False, dyn)
+        l_b, s_b = _PpoLossFn.apply(logits_list[b], value, actions, old_logp, adv, old_value, stats3, b, nb, clip, vf_coef, beta, False, dyn, *mk(b))
         total = total + l_b
         pol, ent, kl, cf = pol + s_b[0], ent + s_b[3], kl + s_b[4], cf + s_b[5]
     return total, torch.stack([pol, st[1], total.detach(), ent, kl, cf])

@@ -38,6 +38,25 @@ class IndexedObservations:
         self.bank, self.index = bank_nhwc, index
 
 
+def masked_logits(logits, action_mask):
+    """The branches' logits (a list of [N, A_b] tensors) with -inf at the actions that ``action_mask`` does not allow: bool [N, sum A_b]
+    (the branches' actions side by side) or the packed int64 / uint64 words [N] of ``environments.pack_action_masks`` (bit j = column j)."""
+    total = sum(int(l.shape[1]) for l in logits)
+    dev = logits[0].device
+    m = action_mask.detach().cpu().numpy() if torch.is_tensor(action_mask) else np.asarray(action_mask)
+    if m.dtype != np.bool_:              # packed words, signed or unsigned: the same 64 bits
+        words = torch.from_numpy(np.ascontiguousarray(m.reshape(-1)).astype(np.uint64).view(np.int64)).to(dev).reshape(-1, 1)
+        valid = ((words >> torch.arange(total, device=dev)) & 1).bool()
+    else:
+        valid = torch.from_numpy(np.ascontiguousarray(m)).to(dev).reshape(-1, total)
+    out, off = [], 0
+    for l in logits:
+        a = int(l.shape[1])
+        out.append(l.masked_fill(~valid[:, off:off + a], float("-inf")))
+        off += a
+    return out
+
+
 class ActorCriticModel(nn.Module):
     def __init__(self, config, observation_space, action_space_shape, max_episode_length, continuous=False):
         """``continuous``: a Box action space of A = action_space_shape[0] dimensions -- a diagonal Gaussian policy whose mean is
@@ -500,15 +519,22 @@ class ActorCriticModel(nn.Module):
         value = self.value(h_value).reshape(-1)
         return [branch(h_policy) for branch in self.policy_branches], value, memory
 
-    def forward_banked(self, obs, spec: WindowSpec):
+    def forward_banked(self, obs, spec: WindowSpec, action_mask=None):
+        """``action_mask`` (optional, categorical policies): invalid-action masks of the N samples, bool [N, sum A_b] (the branches'
+        actions side by side, sb3-contrib's ``action_masks()`` layout) or the packed int64 / uint64 words [N]
+        (``environments.pack_action_masks``): the logits of the invalid actions are -inf in the returned distributions."""
+        if self.continuous and action_mask is not None:
+            raise ValueError("a Box policy has no action mask")
         logits, value, memory = self.forward_logits(obs, spec)
         if self.continuous:        # Box: [Normal(mean, exp(policy_log_std))]
             return [Normal(logits[0], self.policy_log_std.exp().expand_as(logits[0]), validate_args=False)], value, memory
+        if action_mask is not None:
+            logits = masked_logits(logits, action_mask)
         return [Categorical(logits=l, validate_args=False) for l in logits], value, memory
 
-    def forward(self, obs, memory, memory_mask, memory_indices):
-        """Upstream signature; memory [N, L, blocks, D] is the pre-gathered window."""
-        return self.forward_banked(obs, WindowSpec.from_windows(memory, memory_indices, memory_mask))
+    def forward(self, obs, memory, memory_mask, memory_indices, action_mask=None):
+        """Upstream signature; memory [N, L, blocks, D] is the pre-gathered window.  ``action_mask``: see ``forward_banked``."""
+        return self.forward_banked(obs, WindowSpec.from_windows(memory, memory_indices, memory_mask), action_mask=action_mask)
 
     def get_conv_output(self, shape) -> int:
         with torch.no_grad():

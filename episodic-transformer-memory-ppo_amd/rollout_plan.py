@@ -73,6 +73,10 @@ class WorkerGroup:
         # (episode step, episode slot) of the workers: the full-width group's block IS the trainer's, the host truth
         self.ss_pin = tr._ss_pin if full else torch.zeros((2, Wg), dtype=torch.int64).pin_memory()
         self.ss_dev = tr._ss_dev if full else torch.zeros((2, Wg), dtype=torch.int64, device=dev)
+        # action_masks: the group's words of the trainer's pinned block, which the sampling kernels read in place, and of its device
+        # twin (measurement only: PPOTrainer._mask_in_place); contiguous slices; None without the key
+        self.am_pin = None if tr._am_pin is None else tr._am_pin[lo:hi]
+        self.am_dev = None if tr._am_dev is None else tr._am_dev[lo:hi]
         self.item = torch.zeros((tr.num_blocks, Wg, tr.embed_dim), dtype=torch.float32, device=dev)      # the step's new memory items, block-major
         self.t_dev = torch.zeros((), dtype=torch.int64, device=dev)      # step counter, incremented by the sampling kernel
         self.t_row = torch.zeros((), dtype=torch.int64, device=dev)      # staging row of the step, for its tail

@@ -43,7 +43,7 @@ def default_rollout_groups(num_workers: int, min_group: int) -> int:
 
 
 from buffer import Buffer
-from environments import action_space_kind
+from environments import action_space_kind, branch_bit_masks, empty_mask_branches, valid_action_share
 from environments.vec_env import make_vec_env
 from etm import lib as etm_lib
 from etm import ops
@@ -144,6 +144,38 @@ def check_truncation_transport(config, env=None):
                          "bootstrap_truncated off")
 
 
+def check_action_mask_config(config, env=None, action_space_shape=None, box=False):
+    """The optional key ``action_masks: true`` (invalid-action masking: one 64-bit word per worker and step, bit j = column j of the
+    concatenated policy head is allowed).  -> whether it is on; absent or false: nothing is allocated, no launch is added or exchanged.
+    Refused, each before anything is built from it: a Box policy (``environment.continuous_actions``, or ``box`` once the environment
+    is known); more than 63 actions over all branches (``action_space_shape``, or a Synthetic environment's ``num_actions``);
+    ``worker_processes: true`` without a supplied ``env`` (the workers' shared segment has no row for a mask word, as for
+    ``bootstrap_truncated``); an environment front-end without ``action_masks`` (``env``, once it exists).  Data-parallel runs need
+    nothing: the masks are per-rank data."""
+    if not config.get("action_masks", False):
+        return False
+    from environments import MAX_MASKED_ACTIONS
+    env_cfg = config.get("environment", {})
+    if box or env_cfg.get("continuous_actions") is not None:
+        raise ValueError("action_masks: true with a Box (continuous) action space: a Gaussian policy has no invalid actions to mask; "
+                         "remove the key (the environment's bounds already clip the actions)")
+    shape = action_space_shape
+    if shape is None and env_cfg.get("type") == "Synthetic" and "num_actions" in env_cfg:
+        n = env_cfg["num_actions"]
+        shape = tuple(n) if isinstance(n, (list, tuple)) else (int(n),)
+    if shape is not None and sum(int(a) for a in shape) > MAX_MASKED_ACTIONS:
+        raise ValueError(f"action_masks: true with {sum(int(a) for a in shape)} actions over all branches: a step's mask is one 64-bit word "
+                         f"per worker and takes at most {MAX_MASKED_ACTIONS}; remove the key, or reduce the action space")
+    if env is None and config.get("worker_processes", False):
+        raise ValueError("worker_processes: true does not carry action_masks: true (the shared segment has no row for a mask word): "
+                         "set worker_processes: false (in-process environments hand the words over each step), or remove the key")
+    if env is not None and not callable(getattr(env, "action_masks", None)):
+        raise ValueError(f"action_masks: true, but the environment front-end {type(env).__name__} has no action_masks(): let the "
+                         "environments offer action_masks() (environments/vec_env.py: the VecEnv protocol; a Synthetic environment needs "
+                         "environment.action_mask_p), or remove the key")
+    return True
+
+
 def check_evaluation_config(config, world: int = 1):
     """The optional ``evaluation`` section (interval, episodes_per_worker, n_workers, deterministic, seed, worker_steps) -> a dict with
     the defaults filled in, or None when the section is absent (never evaluate, allocate nothing).  ``evaluation.interval`` in a
@@ -239,6 +271,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         check_box_policy(config)
         check_byte_observation_transport(config, env)
         check_truncation_transport(config, env)
+        check_action_mask_config(config, env)
         check_evaluation_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_normalization_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_checkpoint_config(config, 1 if dp is None else int(getattr(dp, "world", 1)), resume=resume is not None)
@@ -333,6 +366,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if self.box is not None:
             check_box_policy(config, self.box.shape[0])
         self.max_episode_length = self.env.max_episode_steps
+        # action_masks: the environment's front-end, the width of the policy head and the kind of policy are known now
+        self._masked = check_action_mask_config(config, self.env, self.action_space_shape, self.box is not None)
+        self.last_valid_action_share = None       # mean share of allowed actions in the last rollout's words (None without the key)
 
         if config.get("tunable_gemm", os.environ.get("ETM_TUNABLE_GEMM", "1") != "0"):
             # let PyTorch pick the fastest hipBLASLt / rocBLAS solution per GEMM shape (the small [N, D] x [D, D] products around
@@ -414,9 +450,24 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         self._ss_dev = torch.zeros((2, W), dtype=torch.int64, device=device)
         self._ss_dev[1] = torch.arange(W, dtype=torch.int64, device=device)
         self._step_dev, self._slot_dev = self._ss_dev[0], self._ss_dev[1]
+        # action_masks: the workers' words for the observation they are about to act on -- one pinned int64 [W] block (a group's
+        # words are a contiguous slice, rollout_plan.WorkerGroup) that every sampling kernel reads IN PLACE at its start, in every plan:
+        # the host rewrites a group's words only after it has that step's actions, i.e. after the read.  The device twin, handed over as
+        # the (step, slot) block's twin is (an upload / a copy node per step where the plan does not read that block in place), was
+        # measured against it and lost (``_mask_in_place = False`` selects it: tools/action_masks_measure.py, profiles/r15).  Nothing
+        # is allocated without the key.
+        self._mask_in_place = True
+        self._am_pin = self._am_dev = self._am_np = None
+        if self._masked:
+            self._am_pin = torch.zeros(W, dtype=torch.int64).pin_memory()
+            self._am_np = self._am_pin.numpy()
+            self._branch_bits = branch_bit_masks(self.action_space_shape)
+            self._am_dev = torch.zeros(W, dtype=torch.int64, device=device)
         if resumed is not None and self._env_supplied and hasattr(self.env, "restart"):
             self.env.restart(first_worker_id)              # (a supplied environment moves to the segment's worker ids itself)
         self.env.reset(out=self.obs)
+        if self._masked:
+            self._take_action_masks(self.env, 0, W, "reset")
 
         # fixed-address operands of the rollout step (HIP-graph friendly) and time-major staging of the step outputs
         S, L, B = config["worker_steps"], self.memory_length, self._action_width
@@ -490,6 +541,18 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         self.last_update_timing = {}
         if resumed is not None:
             self._load_state(resumed, str(resume), restart=False)
+
+    def _take_action_masks(self, env, lo, hi, step):
+        """``action_masks: true``: the words of the observations ``env`` (workers [lo, hi)) returned last -> the pinned block the next
+        step launch reads.  A word with an empty branch is an environment bug and raises here, before that launch (``step``: the
+        rollout step whose observation it belongs to, or "reset")."""
+        words = self._am_np[lo:hi]
+        env.action_masks(out=words)
+        empty = empty_mask_branches(words, self.action_space_shape, self._branch_bits)
+        if empty.any():
+            wl, b = (int(x) for x in np.argwhere(empty)[0])
+            raise ValueError(f"action_masks: worker {lo + wl}, step {step}, branch {b} has no valid action (word {int(words[wl]):#x}, branches "
+                             f"{self.action_space_shape}): an environment must leave at least one action of every branch allowed")
 
     # ------------------------------------------------------------------ properties mirroring upstream members
     @property
@@ -649,6 +712,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         self.model.refresh_rollout_weights()       # encoder weight copies for the fused rollout convolutions
         if forced_actions is not None:
             self._forced_tab.copy_(time_major(self._forced_tab, forced_actions).to(self.device))
+        if self._masked:
+            self.buffer.action_masks_host[:, 0] = self._am_np      # (the words of observation 0: taken after the last step / the reset)
         if self.config.get("hip_graph_rollout", True):
             groups = self._groups
             if groups[0].graphs is None:
@@ -705,6 +770,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             if plan.stream_obs and not plan.own_stream:
                 # the (step, slot) block follows the observation rows on the shared upload stream; the step waits for both
                 self._etm.etm_upload(g.ss_dev.data_ptr(), g.ss_pin.data_ptr(), g.ss_pin.numel() * 8, self._up_stream.cuda_stream)
+                if g.am_pin is not None and not self._mask_in_place:         # (the words' device twin travels with the block)
+                    self._etm.etm_upload(g.am_dev.data_ptr(), g.am_pin.data_ptr(), g.am_pin.numel() * 8, self._up_stream.cuda_stream)
                 g.up_done.record(self._up_stream)
                 cur.wait_event(g.up_done)
             g.graphs[0].replay()
@@ -725,6 +792,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # this loop is the rollout's critical path: what the plan fixes is bound to locals here, once
         buf, S, clock = self.buffer, self.config["worker_steps"], time.perf_counter
         direct, stream_obs, host_flag, polite = plan.direct_rows, plan.stream_obs, plan.host_flag, plan.polite_wait
+        masked = self._masked
         fence = self._etm.etm_host_store_fence
         t_env = t_wait = t_launch = 0.0
         for t in range(S):
@@ -753,6 +821,11 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                 self.worker_current_episode_step[lo:hi] += 1
                 if dones.any():
                     self._hand_over_episodes(g, t, dones, infos, episode_infos)
+                if masked:
+                    # the words of observation t + 1 (after an auto-reset: the new episode's) into the pinned block, before the launch
+                    self._take_action_masks(g.env, lo, hi, t + 1)
+                    if t + 1 < S:
+                        buf.action_masks_host[lo:hi, t + 1] = self._am_np[lo:hi]
                 if t + 1 < S:
                     tl = clock()
                     launch(g, plan)                  # bookkeeping of this step is final: (step, slot) follow the observation rows
@@ -820,18 +893,42 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
     def _finish_rollout(self, plan, main, forced, timing):
         """Time-major staging -> the buffer's [W, S, ...] fields (one strided copy per field), bootstrap value, advantages."""
         buf = self.buffer
+        forced_wsb = None
+        if forced and self._masked:          # (which entries were forced, [W, S, B], before the table is cleared)
+            W, S = self.num_workers, self.config["worker_steps"]
+            forced_wsb = self._forced_tab.reshape(S, W, -1).transpose(0, 1).cpu().numpy()
         if forced:
             self._forced_tab.fill_(float("nan") if self.box is not None else -1)
+        if self._masked:
+            self.last_valid_action_share = valid_action_share(buf.action_masks_host, sum(self.action_space_shape))
         self._step_dev.copy_(self._step_pin, non_blocking=True)
         self._slot_dev.copy_(self._slot_pin, non_blocking=True)
         for name, stage in self._stage.items():
             getattr(buf, name).copy_(stage.transpose(0, 1))
         if plan.direct_rows:
             self._stage_read.record(main)          # the next rollout's host writes into the staging array wait for this
+        if forced_wsb is not None:
+            self._check_forced_against_masks(forced_wsb)
         if self._bootstrap:                        # (after the staging copies: buf.memory_indices is final)
             self._bootstrap_pass()
         buf.calc_advantages(self.get_last_value(), self.config["gamma"], self.config["lamda"])
         self.last_update_timing.update(env_s=timing[0], wait_s=timing[1], launch_s=timing[2])
+
+    def _check_forced_against_masks(self, forced):
+        """After a rollout that was given ``forced_actions`` (``forced`` [W, S, B], negative = sampled): a forced action overrides
+        sampling, so it must have been allowed by the word of its step -- raises ValueError naming the first one that was not.  Only
+        the forced entries are looked at: a sampled action is allowed by construction."""
+        words = self.buffer.action_masks_host.view(np.uint64)
+        off = 0
+        for b, a in enumerate(self.action_space_shape):
+            fb = forced[:, :, b]
+            bit = np.where(fb >= 0, fb, 0).astype(np.uint64) + np.uint64(off)
+            bad = (fb >= 0) & (((words >> bit) & np.uint64(1)) == 0)
+            if bad.any():
+                w, t = (int(x) for x in np.argwhere(bad)[0])
+                raise ValueError(f"forced_actions: worker {w}, step {t}, branch {b}: the forced action {int(fb[w, t])} is masked out "
+                                 f"(word {int(words[w, t]):#x})")
+            off += int(a)
 
     def _rollout_step_device(self, g, stream_obs=False, host_flag=False):
         """Device side of one rollout step of group ``g`` (upstream trainer.py:161-186) = head + tail."""
@@ -902,6 +999,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             g.obs_dev.copy_(g.obs_pin, non_blocking=True)
             obs, obs_index, rows = g.obs_dev, None, None
             g.ss_dev.copy_(g.ss_pin, non_blocking=True)      # (streamed mode: uploaded with the observation rows)
+            if g.am_pin is not None and not self._mask_in_place:
+                g.am_dev.copy_(g.am_pin, non_blocking=True)  # (the words' device twin: likewise)
         branches = self.action_space_shape       # (one entry: Discrete; the kernels then take their single-branch entries)
         policy_head = m.rollout_policy_head()
         # Box: the Gaussian forms of the sampling kernels -- normals in place of the uniforms, float forced / action tables
@@ -910,6 +1009,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         mask_t, win_t = g.mask_t, g.win_t
         # streamed + pipelined mode: the (step, slot) block is read from pinned host memory (see rollout_plan.plan_rollout)
         ss_src = g.ss_pin if stream_obs and g.stream is not None else g.ss_dev
+        # action_masks: the words are read in place from pinned memory (or take the block's road); None without the key: the entries without masks
+        am_src = None if g.am_pin is None else (g.am_pin if self._mask_in_place or (stream_obs and g.stream is not None) else g.am_dev)
         fused_step, rf, hidden = self._choose_step_form(g, obs_index is not None)
         flag_pin = g.flag_pin if host_flag else None
         if fused_step:
@@ -926,7 +1027,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                              g.rf_scratch, host_actions=g.act_pin, host_flag=flag_pin, w_off=g.lo,
                              tail=tail, h_bias=h_bias, branches=branches, box=box,
                              window=(ss_src, self._mask_table, self._index_table, st["memory_mask"], st["memory_indices"],
-                                     g.ss_latch, g.t_row, self._kv_init))
+                                     g.ss_latch, g.t_row, self._kv_init), action_mask=am_src)
             return g.item
         # window lookup + staging; the same launch records the staging row of this step for the tail (t_dev is incremented by
         # the sampling kernel) and resets the K/V cache of workers at episode step 0 (they start from the projection of an
@@ -948,7 +1049,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             else:
                 ops.rollout_policy(h2, policy_head, m.value, self._uniforms, self._forced_tab, g.t_dev,
                                    g.act_dev, st["actions"], st["log_probs"], st["values"],
-                                   host_actions=g.act_pin, host_flag=flag_pin, h_bias=m._b_heads, w_off=g.lo, branches=branches)
+                                   host_actions=g.act_pin, host_flag=flag_pin, h_bias=m._b_heads, w_off=g.lo, branches=branches,
+                                   action_mask=am_src)
         else:
             if kv_spec is not None:
                 logits, value, item = m.forward_logits_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, obs_rows=rows)
@@ -966,7 +1068,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                                             st["values"], low=box[1], high=box[2])
             else:
                 ops.rollout_sample(lg, value, self._uniforms, self._forced_tab, g.t_dev, g.act_dev,
-                                   st["actions"], st["log_probs"], st["values"], branches=branches)
+                                   st["actions"], st["log_probs"], st["values"], branches=branches, action_mask=am_src)
             g.act_pin.copy_(g.act_dev, non_blocking=True)
         if item.data_ptr() != g.item.data_ptr():
             g.item.copy_(item)
@@ -1301,14 +1403,14 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             if ops.heads_loss_supported(h, m.lin_policy, branch):
                 return ops.heads_ppo_loss(h, m.lin_policy, m.lin_value, branch, m.value, mb["actions"], mb["log_probs"],
                                           mb["advantages"], mb["values"], clip_range, self.config["value_loss_coefficient"], beta, stats3, dyn=dyn,
-                                          unit_grad=True)       # (both callers run loss.backward() on this loss)
+                                          unit_grad=True, action_mask=mb.get("action_masks"))       # (both callers run loss.backward() on this loss)
             h_policy = ops.linear_relu(m.lin_policy, h)
             h_value = ops.linear_relu(m.lin_value, h)
             logits, value = [br(h_policy) for br in m.policy_branches], m.value(h_value).reshape(-1)
         else:
             logits, value, _ = m.forward_logits(obs, spec, want_items=False)
         return ops.ppo_loss(logits, value, mb["actions"], mb["log_probs"], mb["advantages"], mb["values"], clip_range,
-                            self.config["value_loss_coefficient"], beta, stats3, dyn=dyn)
+                            self.config["value_loss_coefficient"], beta, stats3, dyn=dyn, action_mask=mb.get("action_masks"))
 
     def _dw_destinations(self):
         """{parameter data_ptr: its gradient view in the flat arena}: the [out, in] views of the 2-D parameters for the grouped weight-

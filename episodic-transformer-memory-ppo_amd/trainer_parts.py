@@ -210,6 +210,8 @@ class _RunOutputs:
         if self.last_kl_stop is not None:                # (target_kl: did the update stop, and how many optimiser steps it applied)
             self.writer.add_scalar("other/kl_stopped", float(self.last_kl_stop["stopped"]), update)
             self.writer.add_scalar("other/optimizer_steps", self.last_kl_stop["steps_applied"], update)
+        if self.last_valid_action_share is not None:     # (action_masks: mean share of allowed actions in the rollout's words)
+            self.writer.add_scalar("other/valid_action_share", self.last_valid_action_share, update)
         if self.buffer.return_norm is not None:          # (the scale the last rollout's rewards were multiplied with)
             self.writer.add_scalar("training/return_scale", float(self.buffer.return_scale.item()), update)
         if self.model.obs_norm is not None:              # (the spread of the frozen table the next rollout runs on)
@@ -495,3 +497,5 @@ class _CheckpointResume:
         self.worker_episode_slot[:] = range(W)
         self._ss_dev.copy_(self._ss_pin)
         self.env.reset(out=self.obs)
+        if self._masked:
+            self._take_action_masks(self.env, 0, W, "reset")

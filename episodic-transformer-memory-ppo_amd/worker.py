@@ -1,5 +1,6 @@
 """One environment per subprocess, spoken to over a pipe with upstream's ``(cmd, data)`` messages
-(cmd in {"step", "reset", "close"}; upstream worker.py).  ``Worker(env_config).child`` is the parent's end.
+(cmd in {"step", "reset", "close"}; upstream worker.py; plus "action_masks" -> the environment's ``action_masks()`` for its current
+observation, for ``action_masks: true``).  ``Worker(env_config).child`` is the parent's end.
 
 Environment failures are reported back through the pipe as ``WorkerException`` objects (upstream raises inside the
 child, which leaves the parent's ``recv()`` hanging); ``environments.vec_env.PipeVecEnv`` is the consumer.
@@ -33,6 +34,8 @@ class _EnvServer:
             return self.env.step(data)
         if cmd == "reset":
             return self.env.reset()
+        if cmd == "action_masks":
+            return self.env.action_masks()
         if cmd == "close":
             return self.env.close()
         raise NotImplementedError(f"unknown worker command {cmd!r}")

@@ -37,7 +37,7 @@ extern "C" {
 
 /* ABI version of this header (bumped on any signature change, and when the meaning of an argument widens: 52 = the greedy
  * sentinel of the `uniforms` tables; 53 = + etm_gae_truncated; 54 = + the running-normalisation entries; 55 = + etm_grouped_dw_tile_map;
- * 56 = + etm_arena_digest). */
+ * 56 = + etm_arena_digest; 57 = + the gated optimiser pair; 58 = + the *_masked entries of invalid-action masking). */
 int etm_abi_version(void);
 
 /* Human-readable name for a negative ETM_E* code or a hipError_t. Static storage. */
@@ -238,6 +238,15 @@ int etm_rollout_sample(const float *logits, const float *value, const float *uni
 int etm_rollout_sample_branched(const float *logits, const float *value, const float *uniforms, const int64_t *forced, int64_t *t_dev,
                                 int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W, const int32_t *branch_sizes,
                                 int n_branches, void *stream);
+/* Invalid-action masks (ABI 58): the workers' words for this step, action_mask [W] int64 -- bit j set = column j of the concatenated
+ * logits is allowed; branch b owns bits [off_b, off_b + sizes[b]); bits >= sum sizes are ignored; every branch has a valid action (the
+ * caller's duty: a word with an empty branch must not reach the device).  Per branch the logit of an invalid action reads as -inf in
+ * front of the same sampling arithmetic: the draw (sampled, greedy) is the unmasked draw on the branch compacted to its valid
+ * actions, the staged log-prob is l_a - lse over the valid actions; a forced action is taken as it is.  A Discrete policy is one
+ * branch (n_branches = 1).  sum sizes <= 63 (else ETM_EUNSUPPORTED); ETM_EINVAL for a NULL or misaligned (8 bytes) action_mask. */
+int etm_rollout_sample_branched_masked(const float *logits, const float *value, const float *uniforms, const int64_t *forced,
+                                       int64_t *t_dev, int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W,
+                                       const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, void *stream);
 /* Box policies (ABI 49): a diagonal Gaussian over A <= 8 dimensions.  mean [W, A] = the policy head's outputs; x = mean + exp(log_std)
  * normals[*t_dev, w] (log_std [A] on the device; normals / forced / st_actions time-major [S, W, A]; a forced row entry that is not NaN
  * replaces the draw of its dimension); st_logp[*t_dev, w] = log p(x) = sum_a [-((x_a - mean_a) / sigma_a)^2 / 2 - log sigma_a - log(2 pi) / 2]
@@ -339,6 +348,25 @@ int etm_heads_loss_branched(const float *pre_p, const float *pre_v, const float 
                             float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p,
                             float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes,
                             int N, int hid, const int32_t *branch_sizes, int n_branches, void *stream);
+/* Invalid-action masks (ABI 58): etm_heads_loss / etm_heads_loss_branched with action_mask [N] int64, the samples' words in the layout
+ * of etm_rollout_sample_branched_masked (the word the sample was drawn under; the taken action is among its set bits).  Per branch
+ * with valid set V: lse_V over V only, log p_j = l_j - lse_V on V and p_j = 0 elsewhere, entropy -sum_{j in V} p_j log p_j (invalid
+ * columns are skipped, not multiplied), d loss / d l_j = 0 exactly for j outside V -- so that sample adds nothing to those rows of
+ * d Wb / d bb; a branch with one valid action has log p = 0, entropy 0 and a zero gradient.  Ratio, clipping, KL, clip fraction, value
+ * loss and scales as without masks; the optional logits output stays raw.  ETM_EINVAL for a NULL or misaligned action_mask. */
+int etm_heads_loss_masked(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb, const float *bb,
+                          const float *wv, const float *bv, const int64_t *actions, int64_t action_stride, const float *old_logp,
+                          int64_t logp_stride, const float *adv, const float *old_value, const float *adv_stats3, double clip, float vf_coef,
+                          float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p,
+                          float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes,
+                          int N, int hid, int A, const int64_t *action_mask, void *stream);
+int etm_heads_loss_branched_masked(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                   const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
+                                   const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
+                                   const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                                   float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
+                                   float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
+                                   const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, void *stream);
 /* Box policies (ABI 49): the same pass for a diagonal Gaussian (A <= 8): wb / bb = the mean head; xact [N, A] (row stride
  * action_stride >= A) the stored raw float actions; log_std [A]; old_logp [N] (logp_stride).  Per sample one ratio of the joint
  * log-probs; d log p / d mean_a = (x_a - mean_a) / sigma_a^2, d log p / d log sigma_a = ((x_a - mean_a) / sigma_a)^2 - 1, the entropy
@@ -458,6 +486,13 @@ int etm_rollout_policy_branched(const float *h, const float *h_bias, const float
                                 const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
                                 float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
                                 int W, int hid, int stage_W, const int32_t *branch_sizes, int n_branches, void *stream);
+/* Invalid-action masks (ABI 58): as etm_rollout_sample_branched_masked; action_mask [W] int64 of THIS group's workers, in device or
+ * pinned host memory (each workgroup reads its worker's word in place, in front of the dot products). */
+int etm_rollout_policy_branched_masked(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv,
+                                       const float *bv, const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions,
+                                       int64_t *st_actions, float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag,
+                                       int32_t *sync_counter, int W, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,
+                                       const int64_t *action_mask, void *stream);
 /* Box policies (ABI 49): wp / bp = the mean head [A, hid], [A]; the draw of etm_rollout_sample_gaussian (normals / forced / st_actions
  * [S, stage_W, A]); actions and host_actions (pinned, optional) [W, A] receive the clipped actions, host_actions before the flag. */
 int etm_rollout_policy_gaussian(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv, const float *bv,
@@ -573,6 +608,33 @@ int etm_rollout_trxl_group_branched(const float *h_in, const float *wemb_t, cons
                                     const int64_t *index_table, uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row,
                                     uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H,
                                     int L, int hid, int stage_W, const int32_t *branch_sizes, int n_branches, void *stream);
+/* Invalid-action masks (ABI 58): the two branched step launches with action_mask [W] int64 before the stream, the words of this
+ * group's workers for this step in the layout of etm_rollout_sample_branched_masked (a Discrete policy is one branch).  Device or
+ * pinned host memory: the sampling workgroup reads its words in place at the start of the launch, where the (step, slot) block is
+ * read, so a read over the host link is hidden under the transformer.  Everything else as without masks. */
+int etm_rollout_trxl_branched_masked(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
+                              int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
+                              const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
+                              const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
+                              float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter, float ln_eps,
+                              void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
+                              const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride,
+                              const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table,
+                              uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,
+                              const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int stage_W,
+                              const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, void *stream);
+int etm_rollout_trxl_group_branched_masked(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
+                                    int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
+                                    const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
+                                    const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
+                                    float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
+                                    float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
+                                    const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride,
+                                    int64_t bank_block_stride, const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table,
+                                    const int64_t *index_table, uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row,
+                                    uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H,
+                                    int L, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,
+                                    const int64_t *action_mask, void *stream);
 /* Box forms of the two step kernels (ABI 49): the arguments of etm_rollout_trxl / etm_rollout_trxl_group with log_std [A] after bv,
  * float normals / forced / actions / st_actions / host_actions in place of uniforms / forced / actions / st_actions / host_actions (the
  * layouts of etm_rollout_policy_gaussian) and the HOST bound arrays low / high after stage_W; wp / bp = the mean head.  Shapes: the
@@ -955,6 +1017,15 @@ int etm_ppo_loss(const float *logits, const int64_t *actions, int64_t action_str
                  float *out8, float *d_logits, float *d_value,
                  void *partials, int64_t partials_bytes, const double *dyn_clip_beta,
                  int N, int A, void *stream);
+/* Invalid-action masks (ABI 58): etm_ppo_loss of one branch with action_mask [N] int64 (layout of etm_rollout_sample_branched_masked);
+ * the branch's A actions are bits [mask_shift, mask_shift + A), mask_shift = its first column of the concatenated policy head (0 for
+ * Discrete), mask_shift + A <= 63.  The rule of etm_heads_loss_masked: lse, log-prob and entropy over the valid actions, d_logits = 0
+ * exactly on the invalid ones.  One sample per thread (no 16-byte form).  ETM_EINVAL for a NULL or misaligned action_mask. */
+int etm_ppo_loss_masked(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp, int64_t logp_stride,
+                        const float *adv, const float *old_value, const float *value, const float *adv_stats3, double clip, float vf_coef,
+                        float beta, float pol_scale, float ent_scale, float val_scale, int include_value, float *out8, float *d_logits,
+                        float *d_value, void *partials, int64_t partials_bytes, const double *dyn_clip_beta, int N, int A,
+                        const int64_t *action_mask, int mask_shift, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Gradient exchange of the data-parallel optimiser step (absent upstream -- the call goes between
