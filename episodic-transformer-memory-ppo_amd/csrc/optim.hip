@@ -13,6 +13,9 @@
 //                       p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)   (torch's single-tensor AdamW, fp32, same order)
 // HBM traffic: 4 B read for the norm + 16 B read / 16 B written per parameter = 36 B x 3.94 M = 142 MB at config 3.
 // lr and the step counter are device-resident so a captured HIP graph replays the step under changing schedules.
+//   etm_grad_sqnorm_gated / etm_adamw_clip_gated   the same pair under the KL early stop (`target_kl`)
+//   etm_grad_sqnorm_adaptive                       the norm launch under the KL-adaptive learning rate (`adaptive_lr`): its deciding
+//                     thread moves *lr_dev on the step's own kl before the AdamW launch reads it (with or without the early stop)
 #include "etm_common.h"
 
 #include <math.h>
@@ -35,18 +38,31 @@ __device__ __forceinline__ float block_sum_256(float v, float *sm) {
 // [1] steps applied in this update, [2] the bit pattern of the kl that tripped.  Workgroup 0, thread 0 of the norm launch decides -- no
 // other workgroup of that launch reads gate or step -- and every workgroup of the AdamW launch, one launch later, reads gate[0].  GATED
 // is a compile-time switch on the ONE body of each kernel: the ungated instantiations hold the code they always held.
-template <bool GATED>
+// ---- KL-adaptive learning rate (etm_grad_sqnorm_adaptive): ADAPT is the body's second compile-time switch.  Before the gate's test the
+// deciding thread moves *lr_dev on the step's own kl -- kl > kl_high: lr = max(lr_min, lr / factor); 0 < kl < kl_low: lr = min(lr_max,
+// lr * factor); anything else (a NaN, a kl <= 0, a kl at a limit): nothing -- and counts the decision in lr_state ([0] raises, [1] cuts).
+// The AdamW launch, one launch later, reads the new *lr_dev.  A step behind a stopped gate moves nothing.
+template <bool GATED, bool ADAPT>
 __device__ __forceinline__ void grad_sqnorm_body(const float4 *__restrict__ g, long long n4, float *__restrict__ partial,
                                                  long long *__restrict__ step, const float *__restrict__ kl, float kl_limit,
-                                                 unsigned long long *__restrict__ gate, unsigned long long *host_word) {
+                                                 unsigned long long *__restrict__ gate, unsigned long long *host_word,
+                                                 float *__restrict__ lr_dev, float kl_low, float kl_high, float factor, float lr_min,
+                                                 float lr_max, unsigned long long *__restrict__ lr_state) {
   __shared__ float sm[4];
-  // the deciding thread's three words are asked for first, so that their latency passes under the sum (they were written by earlier
+  // the deciding thread's words are asked for first, so that their latency passes under the sum (they were written by earlier
   // launches of the stream)
-  unsigned long long stopped = 0ull, applied = 0ull;
-  float k = 0.f;
-  if (GATED && blockIdx.x == 0 && threadIdx.x == 0) {
-    stopped = gate[0];
-    applied = gate[1];
+  unsigned long long stopped = 0ull, applied = 0ull, raises = 0ull, cuts = 0ull;
+  float k = 0.f, lr = 0.f;
+  if ((GATED || ADAPT) && blockIdx.x == 0 && threadIdx.x == 0) {
+    if (ADAPT) {
+      lr = *lr_dev;
+      raises = lr_state[0];
+      cuts = lr_state[1];
+    }
+    if (GATED) {
+      stopped = gate[0];
+      applied = gate[1];
+    }
     k = *kl;
   }
   float acc = 0.f;
@@ -58,6 +74,15 @@ __device__ __forceinline__ void grad_sqnorm_body(const float4 *__restrict__ g, l
   if (threadIdx.x == 0) {
     partial[blockIdx.x] = t;
     if (blockIdx.x == 0) {
+      if (ADAPT && !(GATED && stopped != 0ull)) {
+        if (k > kl_high) {
+          *lr_dev = fmaxf(lr_min, __fdiv_rn(lr, factor));
+          lr_state[1] = cuts + 1ull;
+        } else if (k < kl_low && k > 0.f) {
+          *lr_dev = fminf(lr_max, __fmul_rn(lr, factor));
+          lr_state[0] = raises + 1ull;
+        }
+      }
       if (GATED) {
         bool halted = stopped != 0ull;
         if (!halted) {
@@ -130,13 +155,28 @@ __device__ __forceinline__ void adamw_clip_body(float4 *__restrict__ p, float4 *
 
 __global__ __launch_bounds__(OPT_THREADS) void grad_sqnorm_kernel(const float4 *__restrict__ g, long long n4, float *__restrict__ partial,
                                                                   long long *__restrict__ step) {
-  grad_sqnorm_body<false>(g, n4, partial, step, nullptr, 0.f, nullptr, nullptr);
+  grad_sqnorm_body<false, false>(g, n4, partial, step, nullptr, 0.f, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 0.f, nullptr);
 }
 __global__ __launch_bounds__(OPT_THREADS) void grad_sqnorm_gated_kernel(const float4 *__restrict__ g, long long n4, float *__restrict__ partial,
                                                                         long long *__restrict__ step, const float *__restrict__ kl,
                                                                         float kl_limit, unsigned long long *__restrict__ gate,
                                                                         unsigned long long *host_word) {
-  grad_sqnorm_body<true>(g, n4, partial, step, kl, kl_limit, gate, host_word);
+  grad_sqnorm_body<true, false>(g, n4, partial, step, kl, kl_limit, gate, host_word, nullptr, 0.f, 0.f, 0.f, 0.f, 0.f, nullptr);
+}
+__global__ __launch_bounds__(OPT_THREADS) void grad_sqnorm_adaptive_kernel(const float4 *__restrict__ g, long long n4, float *__restrict__ partial,
+                                                                           long long *__restrict__ step, const float *__restrict__ kl,
+                                                                           float *__restrict__ lr_dev, float kl_low, float kl_high, float factor,
+                                                                           float lr_min, float lr_max, unsigned long long *__restrict__ lr_state) {
+  grad_sqnorm_body<false, true>(g, n4, partial, step, kl, 0.f, nullptr, nullptr, lr_dev, kl_low, kl_high, factor, lr_min, lr_max, lr_state);
+}
+__global__ __launch_bounds__(OPT_THREADS) void grad_sqnorm_adaptive_gated_kernel(const float4 *__restrict__ g, long long n4,
+                                                                                 float *__restrict__ partial, long long *__restrict__ step,
+                                                                                 const float *__restrict__ kl, float *__restrict__ lr_dev,
+                                                                                 float kl_low, float kl_high, float factor, float lr_min,
+                                                                                 float lr_max, unsigned long long *__restrict__ lr_state,
+                                                                                 float kl_limit, unsigned long long *__restrict__ gate,
+                                                                                 unsigned long long *host_word) {
+  grad_sqnorm_body<true, true>(g, n4, partial, step, kl, kl_limit, gate, host_word, lr_dev, kl_low, kl_high, factor, lr_min, lr_max, lr_state);
 }
 
 __global__ __launch_bounds__(OPT_THREADS) void adamw_clip_kernel(float4 *__restrict__ p, float4 *__restrict__ g, float4 *__restrict__ m,
@@ -325,6 +365,30 @@ extern "C" int etm_grad_sqnorm(const float *g, int64_t n, float *partial, int n_
 extern "C" int etm_grad_sqnorm_gated(const float *g, int64_t n, float *partial, int n_partial, int64_t *step, const float *kl, float kl_limit,
                                      uint64_t *gate, uint64_t *host_word, void *stream) {
   return grad_sqnorm_launch(g, n, partial, n_partial, step, kl, kl_limit, gate, host_word, true, stream);
+}
+
+// The norm launch under the KL-adaptive learning rate (with gate: and under the KL early stop); the AdamW launch that follows is
+// etm_adamw_clip (gate NULL) or etm_adamw_clip_gated as they are: it reads *lr_dev one launch later.
+extern "C" int etm_grad_sqnorm_adaptive(const float *g, int64_t n, float *partial, int n_partial, int64_t *step, const float *kl, float *lr_dev,
+                                        float kl_low, float kl_high, float factor, float lr_min, float lr_max, uint64_t *lr_state, float kl_limit,
+                                        uint64_t *gate, uint64_t *host_word, void *stream) {
+  (void)hipGetLastError();
+  if (!g || !partial || n <= 0 || n % 4 != 0 || n_partial <= 0 || n_partial > 4096) return ETM_EINVAL;
+  if ((uintptr_t)g % 16 != 0) return ETM_EINVAL;
+  if (!kl || !lr_dev || !lr_state || (uintptr_t)kl % 4 != 0 || (uintptr_t)lr_dev % 4 != 0 || (uintptr_t)lr_state % 8 != 0) return ETM_EINVAL;
+  if ((uintptr_t)gate % 8 != 0 || (uintptr_t)host_word % 8 != 0 || (host_word && !gate)) return ETM_EINVAL;
+  if (!isfinite(kl_low) || !isfinite(kl_high) || !isfinite(factor) || !isfinite(lr_min) || !isfinite(lr_max)) return ETM_EINVAL;
+  if (!(factor > 1.f) || !(kl_low >= 0.f) || !(kl_low < kl_high) || !(lr_min > 0.f) || !(lr_min <= lr_max)) return ETM_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  EtmProfScope prof(ETM_K_OPTIM, st);
+  if (gate)
+    hipLaunchKernelGGL(grad_sqnorm_adaptive_gated_kernel, dim3((unsigned)n_partial), dim3(OPT_THREADS), 0, st, (const float4 *)g,
+                       (long long)(n / 4), partial, (long long *)step, kl, lr_dev, kl_low, kl_high, factor, lr_min, lr_max,
+                       (unsigned long long *)lr_state, kl_limit, (unsigned long long *)gate, (unsigned long long *)host_word);
+  else
+    hipLaunchKernelGGL(grad_sqnorm_adaptive_kernel, dim3((unsigned)n_partial), dim3(OPT_THREADS), 0, st, (const float4 *)g, (long long)(n / 4),
+                       partial, (long long *)step, kl, lr_dev, kl_low, kl_high, factor, lr_min, lr_max, (unsigned long long *)lr_state);
+  return etm_launch_status();
 }
 
 extern "C" int etm_adamw_clip(float *p, float *g, float *m, float *v, int64_t n, const float *partial, int n_partial, const float *lr_dev,

@@ -7,7 +7,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: torch ships its ow
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libetm_hip.so")     # (diagnostic tools that load another build assign this before load())
-ABI_VERSION = 58
+ABI_VERSION = 59
 
 _lib = None
 
@@ -148,6 +148,7 @@ SIGNATURES = {
     "etm_adamw_clip": (_I, [_P, _P, _P, _P, _L, _P, _I, _P, _P, _D, _D, _D, _D, _F, _F, _P, _P]),
     "etm_grad_sqnorm_gated": (_I, [_P, _L, _P, _I, _P, _P, _F, _P, _P, _P]),
     "etm_adamw_clip_gated": (_I, [_P, _P, _P, _P, _L, _P, _I, _P, _P, _D, _D, _D, _D, _F, _F, _P, _P, _P]),
+    "etm_grad_sqnorm_adaptive": (_I, [_P, _L, _P, _I, _P, _P, _P, _F, _F, _F, _F, _F, _P, _F, _P, _P, _P]),
     "etm_arena_digest": (_I, [_P, _L, _P, _I, _P, _P]),
     "etm_gae": (_I, [_P, _P, _P, _P, _F, _F, _P, _I, _I, _P]),
     "etm_gae_truncated": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _P, _I, _I, _P]),

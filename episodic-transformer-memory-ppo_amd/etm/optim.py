@@ -38,6 +38,29 @@ class KlGate:
         return bool(stopped), applied, kl
 
 
+class AdaptiveLr:
+    """The KL-adaptive learning rate (csrc/optim.hip: etm_grad_sqnorm_adaptive), handed to ``FlatAdamW.step``: ``rule``
+    (utils.adaptive_lr_section: float32 values kl_low, kl_high, factor, min, max), ``state`` (device int64[2]: raises and cuts in this
+    update) and ``kl``, the one-element float32 device tensor the next step's rule looks at: the caller points it at the step's own
+    statistic before every step.  The learning rate itself is the optimiser's ``lr_dev``: with a rule attached the device owns it."""
+
+    def __init__(self, rule, device):
+        self.rule = dict(rule)
+        self.kl_low, self.kl_high, self.factor = float(rule["kl_low"]), float(rule["kl_high"]), float(rule["factor"])
+        self.lr_min, self.lr_max = float(rule["min"]), float(rule["max"])
+        self.state = torch.zeros(2, dtype=torch.int64, device=device)
+        self.kl = None
+
+    def reset(self):
+        """Start of an update: the counters are per update (the learning rate is never reset)."""
+        self.state.zero_()
+
+    def read(self):
+        """(raises, cuts) of this update -- a device read-back."""
+        raises, cuts = (int(x) for x in self.state.cpu().tolist())
+        return raises, cuts
+
+
 class FlatAdamW:
     N_PARTIAL = 1024
 
@@ -72,8 +95,16 @@ class FlatAdamW:
         self.partial = torch.zeros(self.N_PARTIAL, dtype=torch.float32, device=dev)
         self.total_norm = torch.zeros((), dtype=torch.float32, device=dev)     # un-clipped gradient norm of the last step
         self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.adaptive = None            # an AdaptiveLr once ``attach_adaptive`` was called: lr_dev then moves on the device
+
+    def attach_adaptive(self, adapt):
+        """From here on ``lr_dev`` belongs to the device (the rule of ``adapt`` moves it inside ``step(adapt=adapt)``): ``state_dict``
+        stores the device value, and ``set_lr`` is refused -- the caller's schedule must not write over what the rule decided."""
+        self.adaptive = adapt
 
     def set_lr(self, lr):
+        if self.adaptive is not None:
+            raise RuntimeError("FlatAdamW.set_lr with an adaptive learning rate attached: the device owns lr_dev; do not call set_lr")
         if float(lr) != self._lr_host:
             self.lr_dev.fill_(float(lr))
             self._lr_host = float(lr)
@@ -81,15 +112,41 @@ class FlatAdamW:
     def zero_grad(self):
         self.flat_grads.zero_()
 
-    def step(self, max_grad_norm=0.0, grad_scale=1.0, gate=None):
+    def step(self, max_grad_norm=0.0, grad_scale=1.0, gate=None, adapt=None):
         """Clip the gradient arena to ``max_grad_norm`` (global L2 norm, the rule of ``clip_grad_norm_``; <= 0: no clipping) and
         apply one AdamW update.  Two launches on the current stream.  ``grad_scale``: the arena holds gradient / grad_scale
         (data parallel: the all-reduced sum, grad_scale = 1 / world); the scale rides in the clip coefficient.  ``gate`` (a ``KlGate``;
         None: exactly the two ungated calls): the step is dropped -- parameters, moments, gradients and ``step_dev`` keep every bit --
-        when an earlier step under this gate was dropped or when not ``gate.kl <= gate.limit``; still two launches."""
+        when an earlier step under this gate was dropped or when not ``gate.kl <= gate.limit``; still two launches.  ``adapt`` (an
+        ``AdaptiveLr``; None: exactly the calls above): the norm launch first moves ``lr_dev`` on ``adapt.kl`` (utils.adaptive_lr_step;
+        not behind a stopped gate), then tests the gate; this step's AdamW launch -- the ungated or the gated one, as they are -- runs
+        with the new rate.  Still two launches."""
         lib = _lib.load()
         st = torch.cuda.current_stream(self.device).cuda_stream
         n = self.flat_params.numel()
+        if adapt is not None:
+            self.adaptive = adapt           # (a step under a rule attaches it: lr_dev is the device's from here on)
+            kls =[adapt.kl] + ([gate.kl] if gate is not None else [])
+            for kl in kls:
+                if kl is None or not kl.is_cuda or kl.dtype != torch.float32 or kl.numel() != 1:
+                    raise ValueError("FlatAdamW.step: adapt.kl (and gate.kl) must be a one-element float32 device tensor (the step's own "
+                                     "kl statistic)")
+            if gate is not None and gate.kl.data_ptr() != adapt.kl.data_ptr():
+                raise ValueError("FlatAdamW.step: adapt.kl and gate.kl must be the same element (the step's own kl statistic)")
+            word = gate.host_word.data_ptr() if gate is not None and gate.host_word is not None else 0
+            _lib.check(lib.etm_grad_sqnorm_adaptive(self.flat_grads.data_ptr(), n, self.partial.data_ptr(), self.N_PARTIAL,
+                                                    self.step_dev.data_ptr(), adapt.kl.data_ptr(), self.lr_dev.data_ptr(), adapt.kl_low,
+                                                    adapt.kl_high, adapt.factor, adapt.lr_min, adapt.lr_max, adapt.state.data_ptr(),
+                                                    gate.limit if gate is not None else 0.0, gate.gate.data_ptr() if gate is not None else 0,
+                                                    word, st), "etm_grad_sqnorm_adaptive")
+            tail = (self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n,
+                    self.partial.data_ptr(), self.N_PARTIAL, self.lr_dev.data_ptr(), self.step_dev.data_ptr(), self.betas[0], self.betas[1],
+                    self.eps, self.weight_decay, float(max_grad_norm), float(grad_scale), self.total_norm.data_ptr())
+            if gate is None:
+                _lib.check(lib.etm_adamw_clip(*tail, st), "etm_adamw_clip")
+            else:
+                _lib.check(lib.etm_adamw_clip_gated(*tail, gate.gate.data_ptr(), st), "etm_adamw_clip_gated")
+            return
         if gate is not None:
             kl = gate.kl
             if kl is None or not kl.is_cuda or kl.dtype != torch.float32 or kl.numel() != 1:
@@ -116,7 +173,10 @@ class FlatAdamW:
 
     def state_dict(self):
         """Everything that continues the optimiser: both moment arenas as numpy arrays (padded length), the device step counter, the
-        learning rate (the python float ``lr_dev`` was last filled with), and the hyper-parameters and sizes ``load_state_dict`` checks."""
+        learning rate (the python float ``lr_dev`` was last filled with; with an adaptive rule attached the device's own value, a float32
+        held exactly), and the hyper-parameters and sizes ``load_state_dict`` checks."""
+        if self.adaptive is not None:
+            self._lr_host = float(self.lr_dev.item())
         return {"exp_avg": self.exp_avg.cpu().numpy(), "exp_avg_sq": self.exp_avg_sq.cpu().numpy(), "step": int(self.step_dev.item()),
                 "lr": self._lr_host, "betas": [self.betas[0], self.betas[1]], "eps": self.eps,
                 "weight_decay": self.weight_decay, "total": int(self.total), "padded": int(self.flat_params.numel())}

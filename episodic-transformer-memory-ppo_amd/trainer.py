@@ -48,9 +48,9 @@ from environments.vec_env import make_vec_env
 from etm import lib as etm_lib
 from etm import ops
 from etm.ops import WindowSpec
-from etm.optim import FlatAdamW, KlGate
+from etm.optim import AdaptiveLr, FlatAdamW, KlGate
 from model import ActorCriticModel, IndexedObservations
-from utils import normalization_section, polynomial_decay, process_episode_info, target_kl_rows, target_kl_section
+from utils import adaptive_lr_section, normalization_section, polynomial_decay, process_episode_info, target_kl_rows, target_kl_section
 from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
 from checkpoint import check_checkpoint_config, segment_first_worker_id
 from trainer_parts import _CheckpointResume, _DataParallelStep, _NativeRolloutDrive, _RunOutputs
@@ -234,6 +234,31 @@ def check_target_kl_config(config, world: int = 1):
     return out
 
 
+def check_adaptive_lr_config(config, world: int = 1):
+    """The optional key ``adaptive_lr`` (a number: the desired KL, or {desired_kl, factor, low, high, min, max};
+    utils.adaptive_lr_section) -> the rule with its float32 constants, or None when the key is absent (nothing is allocated, no launch
+    is added or exchanged).  Refused, each before anything is allocated and each with what to do instead: values outside their ranges
+    and unknown sub-keys (utils.adaptive_lr_section); a start value float32(learning_rate_schedule.initial) outside [min, max]; a
+    ``learning_rate_schedule`` that decays (final != initial): two schedules would compete for one number; the key in a data-parallel
+    run (``world`` > 1): every rank sees the KL of its own minibatch, and agreeing on one is not built."""
+    out = adaptive_lr_section(config)
+    if out is None:
+        return None
+    if world > 1:
+        raise ValueError("adaptive_lr in a data-parallel run: every rank would move its learning rate on the KL of its own minibatch and "
+                         "the replicas would part (agreeing on one KL over the ranks is not built); remove the key, or train on one device")
+    sched = config["learning_rate_schedule"]
+    if sched["final"] != sched["initial"]:
+        raise ValueError(f"adaptive_lr with a decaying learning_rate_schedule (initial {sched['initial']!r}, final {sched['final']!r}): the "
+                         "two schedules compete for one learning rate; set learning_rate_schedule.final to initial (it is the start value "
+                         "only), or remove the key adaptive_lr")
+    start = float(np.float32(sched["initial"]))
+    if not out["min"] <= start <= out["max"]:
+        raise ValueError(f"adaptive_lr: the start value float32(learning_rate_schedule.initial) = {start!r} lies outside [min, max] = "
+                         f"[{out['min']!r}, {out['max']!r}]; move initial into the range, or widen adaptive_lr.min / adaptive_lr.max")
+    return out
+
+
 def time_major(table, src):
     """The host table ``src`` [W, S(, B)] in the layout and type of the fixed-address device table ``table`` [S, W(, B)]."""
     x = torch.as_tensor(np.asarray(src), dtype=table.dtype)
@@ -276,6 +301,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         check_normalization_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_checkpoint_config(config, 1 if dp is None else int(getattr(dp, "world", 1)), resume=resume is not None)
         kl_cfg = check_target_kl_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
+        adapt_cfg = check_adaptive_lr_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         # training state that a checkpoint carries over (trainer_parts._CheckpointResume): completed updates, the training segment (the
         # number of resumes so far; its environments' worker ids start at segment_first_worker_id), the last episodes' infos
         self.update_index, self.segment, self._episode_infos = 0, 0, deque(maxlen=100)
@@ -427,6 +453,14 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if kl_cfg is not None:
             self._kl_gate = KlGate(kl_cfg["limit"], device, host_word=kl_cfg["host_check"] == "epoch")
             self._kl_event = torch.cuda.Event() if kl_cfg["host_check"] == "epoch" else None
+        # adaptive_lr: the rule of the KL-adaptive learning rate (etm/optim.py: AdaptiveLr).  From here on the device owns lr_dev --
+        # learning_rate_schedule.initial was its start value, ``_set_lr`` does nothing, the rate persists across updates and travels in
+        # the optimiser's state; the two counters are per update.  ``last_adaptive_lr``: the rate and the counters after the last update
+        # (None without the key: nothing is allocated)
+        self._adapt, self.last_adaptive_lr = None, None
+        if adapt_cfg is not None:
+            self._adapt = AdaptiveLr(adapt_cfg, device)
+            self.optimizer.attach_adaptive(self._adapt)
 
         # host <-> device staging (pinned)
         if self._shm_env is not None:
@@ -1298,6 +1332,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         gate, launched = self._kl_gate, 0
         if gate is not None:
             gate.reset()
+        if self._adapt is not None:
+            self._adapt.reset()
         host_stop = False
         for epoch in range(self.config["epochs"]):
             if gate is not None and gate.host_word is not None and epoch > 0 and not host_stop:
@@ -1347,6 +1383,10 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             stopped, applied, kl = gate.read()
             rows = target_kl_rows(stopped, applied, launched)
             self.last_kl_stop = {"stopped": stopped, "steps_applied": applied, "steps_launched": launched, "kl": kl, "limit": gate.limit}
+        if self._adapt is not None:
+            (raised, lowered), ad = self._adapt.read(), self._adapt
+            self.last_adaptive_lr = {"lr": float(self.optimizer.lr_dev.item()), "raised": raised, "lowered": lowered,
+                                     "kl_low": ad.kl_low, "kl_high": ad.kl_high}
         train_info = (self._tg_stats_tab[:rows] if tables else torch.stack(stats[:rows])).cpu().numpy()
         self._bank_pos = self._row_stats = None
         self._mb_stats3 = self._epoch_stats3 = None
@@ -1380,7 +1420,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if self.dp is not None:
             self.dp.all_reduce_grads(average=False)       # the sum; the 1 / world rides in the clip coefficient below
         # global-norm clipping (the rule of torch.nn.utils.clip_grad_norm_, upstream :311) + AdamW on the flat arenas: 2 launches
-        self.optimizer.step(self.config["max_grad_norm"], grad_scale=self._grad_scale(), gate=self._step_gate(stats))
+        self.optimizer.step(self.config["max_grad_norm"], grad_scale=self._grad_scale(), **self._step_gate(stats))
         return stats
 
     def _loss_from(self, obs, spec, mb, clip_range, beta, stats3, dyn="device"):
@@ -1434,6 +1474,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         return self.dp.grad_scale if self.dp is not None else 1.0
 
     def _set_lr(self, learning_rate: float):
+        if self._adapt is not None:         # adaptive_lr: the device owns the learning rate (the schedule gave its start value only)
+            return
         self.optimizer.set_lr(learning_rate)
 
     def _bank_with_positions(self):
@@ -1579,22 +1621,28 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         return grads
 
     def _step_gate(self, stats):
-        """``target_kl``: the update's gate with its ``kl`` pointed at element 4 of the step's own statistics (the k3 estimate of the
-        loss on the weights before the step); None without the key."""
-        gate = self._kl_gate
-        if gate is not None:
+        """What the optimiser's step takes besides the clipping: ``gate`` (``target_kl``: the update's gate) and ``adapt``
+        (``adaptive_lr``: the learning-rate rule), each with its ``kl`` pointed at element 4 of the step's own statistics (the k3 estimate
+        of the loss on the weights before the step), each None without its key."""
+        gate, adapt = self._kl_gate, self._adapt
+        if gate is not None or adapt is not None:
             if stats is None or stats.dtype != torch.float32 or stats.dim() != 1 or stats.numel() < 5 or not stats.is_contiguous():
-                raise RuntimeError("target_kl: the step's statistics must be a contiguous float32 vector with the kl at index 4")
-            gate.kl = stats[4:5]
-        return gate
+                raise RuntimeError("target_kl / adaptive_lr: the step's statistics must be a contiguous float32 vector with the kl at index 4")
+            kl = stats[4:5]
+            if gate is not None:
+                gate.kl = kl
+            if adapt is not None:
+                adapt.kl = kl
+        return {"gate": gate, "adapt": adapt}
 
     def _train_body_b(self, monitor, stats=None, kl_stats=None):
         """Second half: global-norm clipping (same rule as torch.nn.utils.clip_grad_norm_, upstream :311) on the flat bucket,
         fused AdamW, monitored gradient norms.  ``stats`` (the table-driven step): the step's statistics; they and the norms are
         filed under row ``counter`` of the result tables and the counter moves on, inside the norm monitor's two launches.
-        ``kl_stats`` (``target_kl``): the step's statistics in every form of the step, for the optimiser's gate."""
+        ``kl_stats`` (``target_kl`` / ``adaptive_lr``): the step's statistics in every form of the step, for the optimiser's gate and
+        learning-rate rule."""
         self.optimizer.step(self.config["max_grad_norm"], grad_scale=self._grad_scale(),
-                            gate=self._step_gate(kl_stats) if self._kl_gate is not None else None)
+                            **(self._step_gate(kl_stats) if self._kl_gate is not None or self._adapt is not None else {}))
         if stats is None:
             return self._grad_group_norms() if monitor else None
         if stats.numel() != self._tg_stats_tab.shape[1] or stats.dtype != torch.float32 or not stats.is_contiguous():
@@ -1629,6 +1677,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             self._tg_counter.zero_()
             if self._kl_gate is not None:
                 self._kl_gate.reset()
+            if self._adapt is not None:
+                self._adapt.reset()
             self._tg_idx_table[0].copy_(idx)
         self._set_lr(learning_rate)
         if self._sched_host[1] != clip_range or self._sched_host[2] != beta:

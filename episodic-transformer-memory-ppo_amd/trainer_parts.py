@@ -210,6 +210,10 @@ class _RunOutputs:
         if self.last_kl_stop is not None:                # (target_kl: did the update stop, and how many optimiser steps it applied)
             self.writer.add_scalar("other/kl_stopped", float(self.last_kl_stop["stopped"]), update)
             self.writer.add_scalar("other/optimizer_steps", self.last_kl_stop["steps_applied"], update)
+        if self.last_adaptive_lr is not None:            # (adaptive_lr: the rate the update ended with, and how often it moved)
+            self.writer.add_scalar("other/learning_rate", self.last_adaptive_lr["lr"], update)
+            self.writer.add_scalar("other/lr_raised", self.last_adaptive_lr["raised"], update)
+            self.writer.add_scalar("other/lr_lowered", self.last_adaptive_lr["lowered"], update)
         if self.last_valid_action_share is not None:     # (action_masks: mean share of allowed actions in the rollout's words)
             self.writer.add_scalar("other/valid_action_share", self.last_valid_action_share, update)
         if self.buffer.return_norm is not None:          # (the scale the last rollout's rewards were multiplied with)

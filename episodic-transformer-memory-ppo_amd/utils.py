@@ -1,6 +1,7 @@
 """Helpers with the upstream names (utils.py): create_env, polynomial_decay, batched_index_select,
 process_episode_info, Module; normalization_section reads this build's two normalisation keys, target_kl_section its KL early
-stop, target_kl_rows says which rows of an update's result tables a stopped update returns."""
+stop, target_kl_rows says which rows of an update's result tables a stopped update returns; adaptive_lr_section reads the
+KL-adaptive learning rate and adaptive_lr_step is its rule, the one host definition of what the norm kernel decides."""
 import numpy as np
 import torch
 from torch import nn
@@ -122,6 +123,81 @@ def target_kl_rows(stopped: bool, steps_applied: int, steps_launched: int) -> in
     Never 0."""
     rows = min(int(steps_applied) + 1, int(steps_launched)) if stopped else int(steps_launched)
     return max(rows, 1)
+
+
+ADAPTIVE_LR_DEFAULTS = dict(factor=1.5, low=0.5, high=2.0, min=1.0e-5, max=1.0e-2)
+
+
+def _finite_number(x):
+    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_)) and bool(np.isfinite(x))
+
+
+def _f32(x):
+    with np.errstate(over="ignore"):            # (a value beyond float32's range becomes inf, and is refused as such)
+        return np.float32(x)
+
+
+def adaptive_lr_section(config: dict):
+    """The optional key ``adaptive_lr`` (a number: the desired KL, or {desired_kl, factor, low, high, min, max}) -> {"desired_kl",
+    "factor", "low", "high", "min", "max", "kl_low", "kl_high"} with the defaults (factor 1.5, low 0.5, high 2.0, the band and the
+    factor of rsl_rl; min 1e-5, max 1e-2) filled in, or None when the key is absent.  ``kl_low`` = float32(desired_kl * low) and
+    ``kl_high`` = float32(desired_kl * high), each product formed once in double and rounded once; ``factor``, ``min`` and ``max`` are
+    each rounded to float32.  Every value returned is a python float that holds a float32 exactly, but ``desired_kl``, ``low`` and
+    ``high``, which stay as given."""
+    sec = config.get("adaptive_lr")
+    if sec is None:
+        return None
+    if not isinstance(sec, dict):
+        sec = {"desired_kl": sec}
+    known = ("desired_kl", "factor", "low", "high", "min", "max")
+    unknown = sorted(set(sec) - set(known))
+    if unknown:
+        raise ValueError(f"adaptive_lr: unknown keys {unknown} (known: {list(known)}); remove them")
+    if "desired_kl" not in sec:
+        raise ValueError("adaptive_lr: the section needs `desired_kl` (the KL the learning rate is steered to, e.g. 0.01); add it, or remove "
+                         "the key to train with learning_rate_schedule alone")
+    desired = sec["desired_kl"]
+    if not _positive_number(desired):
+        raise ValueError(f"adaptive_lr.desired_kl must be a finite number > 0, got {desired!r}; remove the key to train with "
+                         "learning_rate_schedule alone")
+    v = {k: sec.get(k, d) for k, d in ADAPTIVE_LR_DEFAULTS.items()}
+    if not _finite_number(v["factor"]) or not _f32(v["factor"]) > 1 or not np.isfinite(_f32(v["factor"])):
+        raise ValueError(f"adaptive_lr.factor must be a finite number > 1 (also as a float32), got {v['factor']!r}; leave it out for the "
+                         "default 1.5")
+    if not _finite_number(v["low"]) or not v["low"] >= 0:
+        raise ValueError(f"adaptive_lr.low must be a finite number >= 0 (the learning rate rises below low * desired_kl; 0: never), got "
+                         f"{v['low']!r}; leave it out for the default 0.5")
+    if not _positive_number(v["high"]):
+        raise ValueError(f"adaptive_lr.high must be a finite number > 0 (the learning rate falls above high * desired_kl), got "
+                         f"{v['high']!r}; leave it out for the default 2.0")
+    kl_low, kl_high = _f32(float(desired) * float(v["low"])), _f32(float(desired) * float(v["high"]))
+    if not np.isfinite(kl_high) or not kl_low < kl_high:
+        raise ValueError(f"adaptive_lr: float32(desired_kl * low) = {float(kl_low)!r} must lie below float32(desired_kl * high) = "
+                         f"{float(kl_high)!r}, both finite; choose low < high (the defaults are 0.5 and 2.0)")
+    for k in ("min", "max"):
+        if not _positive_number(v[k]) or not _f32(v[k]) > 0 or not np.isfinite(_f32(v[k])):
+            raise ValueError(f"adaptive_lr.{k} must be a finite number > 0 (also as a float32), got {v[k]!r}; leave it out for the default "
+                             f"{ADAPTIVE_LR_DEFAULTS[k]!r}")
+    if not np.float32(v["min"]) <= np.float32(v["max"]):
+        raise ValueError(f"adaptive_lr.min = {v['min']!r} must not exceed adaptive_lr.max = {v['max']!r}; exchange them, or leave them out "
+                         "for the defaults 1e-5 and 1e-2")
+    return dict(desired_kl=float(desired), low=float(v["low"]), high=float(v["high"]), factor=float(np.float32(v["factor"])),
+                min=float(np.float32(v["min"])), max=float(np.float32(v["max"])), kl_low=float(kl_low), kl_high=float(kl_high))
+
+
+def adaptive_lr_step(lr32, kl32, rule):
+    """The rule of ``adaptive_lr`` for one minibatch step, in numpy float32 (the one host definition of what
+    grad_sqnorm_adaptive_kernel decides; csrc/optim.hip): ``lr32`` the learning rate before the step, ``kl32`` the step's own kl,
+    ``rule`` of ``adaptive_lr_section`` -> (the learning rate the step's AdamW launch uses, -1 cut | 0 kept | +1 raised).  A NaN kl or
+    a kl <= 0 changes nothing, +Inf cuts, a kl at a limit changes nothing; the clamps act on a change only.  The direction says what
+    was decided, also where a clamp left the value as it was (a cut at ``min``)."""
+    lr, kl = np.float32(lr32), np.float32(kl32)
+    factor, lo, hi = np.float32(rule["factor"]), np.float32(rule["min"]), np.float32(rule["max"])
+    if kl > np.float32(rule["kl_high"]):
+        return np.maximum(lo, np.float32(lr / factor)), -1          # (float32 / float32: correctly rounded, as __fdiv_rn)
+    if kl < np.float32(rule["kl_low"]) and kl > np.float32(0):
+        return np.minimum(hi, np.float32(lr * factor)), 1
+    return lr, 0
 
 
 class Module(nn.Module):

@@ -451,6 +451,31 @@ int etm_adamw_clip_gated(float *p, float *g, float *m, float *v, int64_t n, cons
                          const int64_t *step, double beta1, double beta2, double eps, double weight_decay, float max_norm, float grad_scale,
                          float *norm_out, const uint64_t *gate, void *stream);
 
+/* The norm launch under a KL-adaptive learning rate (ABI 59; `adaptive_lr`, the `schedule: adaptive` / `desired_kl` of rsl_rl and
+ * rl_games), with or without the KL early stop.  partial[] and *step as etm_grad_sqnorm.  Workgroup 0, thread 0 decides -- it asks for
+ * *lr_dev, *kl, lr_state and the gate words before the sum, and no other workgroup of the launch reads lr_dev, lr_state, gate or step --
+ * in this order:
+ *   1. gate not NULL and gate[0] set (an earlier step of this update was dropped): nothing happens, no lr change, no step.
+ *   2. the rule on k = *kl (the step's own k3 estimate, out8[4] of the loss entries), in fp32:
+ *        k > kl_high           : *lr_dev = fmaxf(lr_min, *lr_dev / factor)   (correctly rounded division), lr_state[1] += 1
+ *        k < kl_low and k > 0  : *lr_dev = fminf(lr_max, *lr_dev * factor),                                lr_state[0] += 1
+ *        otherwise (a NaN, k <= 0, k at a limit): nothing.  +Inf cuts.  The clamps act on a change only: an *lr_dev outside
+ *        [lr_min, lr_max] stays until the rule moves it.  lr_state counts decisions, also those a clamp left without effect.
+ *   3. gate not NULL: the test of etm_grad_sqnorm_gated, !(k <= kl_limit), with its stores (gate[0], gate[2], host_word); the step that
+ *      trips the stop has already cut the lr when k > kl_high.  gate NULL: kl_limit and host_word are not looked at.
+ *   4. not halted: *step += 1 (and gate[1] += 1).
+ * lr_state: two 64-bit words, 8-byte aligned, zeroed by the caller at the start of every update ([0] raises, [1] cuts).  The AdamW launch
+ * that follows -- etm_adamw_clip with gate NULL, etm_adamw_clip_gated otherwise, both as they are -- reads the new *lr_dev: the step that
+ * saw the kl is the first one taken with the new rate.  No launch is added.
+ * ETM_EINVAL, nothing launched: kl, lr_dev or lr_state NULL; kl or lr_dev not 4-byte aligned; lr_state, gate or host_word not 8-byte
+ * aligned; host_word without gate; rule values outside factor > 1, 0 <= kl_low < kl_high, 0 < lr_min <= lr_max, all finite; and
+ * whatever etm_grad_sqnorm refuses. */
+int etm_grad_sqnorm_adaptive(const float *g, int64_t n, float *partial, int n_partial, int64_t *step, const float *kl, float *lr_dev,
+                             float kl_low, float kl_high, float factor, float lr_min, float lr_max,
+                             uint64_t *lr_state,                       /* [0] raises, [1] cuts in this update */
+                             float kl_limit, uint64_t *gate, uint64_t *host_word,   /* gate NULL: no early stop */
+                             void *stream);
+
 /* Digest of a flat fp32 arena taken as raw bits (ABI 56; checkpoints: what is written, what is read back and what two runs compare).
  * One pass over the n words b_i of x (any n >= 1, any 4-byte-aligned base; 16-byte loads on the aligned middle only) writes
  *   out4[0] = sum over i of mix(i * 0x9E3779B97F4A7C15 + b_i) mod 2^64, mix(z): z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
