@@ -310,6 +310,13 @@ int dispatch_nj(int D, F &&f) {
 }
 }  // namespace
 
+// The NJ (column groups of 64 per lane) of the row-kernel instantiation that a launch at width D runs: dispatch_nj itself, evaluated
+// on the host with a functor that launches nothing.  ETM_EUNSUPPORTED beyond 1024, ETM_EINVAL for D <= 0.
+extern "C" int etm_block_row_groups(int D) {
+  if (D <= 0) return ETM_EINVAL;
+  return dispatch_nj(D, [](auto nj) { return (int)decltype(nj)::value; });
+}
+
 extern "C" int etm_ln_train_fwd(const float *a, const float *a_bias, int relu, const float *b, const float *gamma, const float *beta,
                                 float eps, float *y, float *s_out, float *stats, int N, int D, void *stream) {
   (void)hipGetLastError();

@@ -37,7 +37,8 @@ extern "C" {
 
 /* ABI version of this header (bumped on any signature change, and when the meaning of an argument widens: 52 = the greedy
  * sentinel of the `uniforms` tables; 53 = + etm_gae_truncated; 54 = + the running-normalisation entries; 55 = + etm_grouped_dw_tile_map;
- * 56 = + etm_arena_digest; 57 = + the gated optimiser pair; 58 = + the *_masked entries of invalid-action masking). */
+ * 56 = + etm_arena_digest; 57 = + the gated optimiser pair; 58 = + the *_masked entries of invalid-action masking;
+ * 59 = + etm_grad_sqnorm_adaptive; 60 = + etm_block_row_groups). */
 int etm_abi_version(void);
 
 /* Human-readable name for a negative ETM_E* code or a hipError_t. Static storage. */
@@ -290,7 +291,12 @@ int etm_gru_gate_out(const float *a, const float *c, const float *z, const float
  *             dbg == NULL: `workspace` keeps etm_gate_train_bwd_partial_rows(N) rows of D partial sums for etm_colsum_reduce_grouped
  *       bwd2: drx -> dA[:, 0:D] = dB[:, 0:D] = drx x r (1 - r); dx2 = dx1 + drx r
  *             (then dy = dA [Wr;Wz;Wg], dx = dx2 + dB [Ur;Uz], d[Wr;Wz;Wg] = dA^T y, d[Ur;Uz] = dB^T x, dUg = dA[:, 2D:3D]^T rx)
+ *   etm_block_row_groups (ABI 60, host only): the row kernels (ln_train_fwd / ln_train_bwd / gate_train_bwd1) are instantiated for
+ *                     NJ in {1, 2, 4, 6, 8, 12, 16} column groups of 64 per lane; this returns the NJ a launch at width D runs (the
+ *                     smallest member >= ceil(D / 64)), evaluated by the launches' own dispatch.  ETM_EUNSUPPORTED for D > 1024 (as the
+ *                     launches), ETM_EINVAL for D <= 0.  For tests that must reach every instantiation.
  */
+int etm_block_row_groups(int D);
 int etm_ln_train_fwd(const float *a, const float *a_bias, int relu, const float *b, const float *gamma, const float *beta, float eps,
                      float *y, float *s_out, float *stats, int N, int D, void *stream);
 int64_t etm_ln_train_bwd_workspace_bytes(int N, int D);

@@ -2736,7 +2736,8 @@ def _rel(a, b):
                                                    (True, False, False)])
 def test_fused_layernorm_fwd_bwd_vs_torch(N, D, has_bias, relu, has_res):
     """Training-side fused LayerNorm(act(a + bias) + res): forward and every gradient against the framework ops it replaces
-    (transformer.py:131-149, :160-170), on the device in fp32 (tolerance: summation order only)."""
+    (transformer.py:131-149, :160-170), on the device in fp32 (tolerance: summation order only).
+    (Per row and column against float64, at every width instantiation: tests/test_block_kernels_vs_float64.py.)"""
     from etm import ops
     dev = _dev()
     torch.manual_seed(N + D)
@@ -2765,7 +2766,8 @@ def test_fused_layernorm_fwd_bwd_vs_torch(N, D, has_bias, relu, has_res):
 @pytest.mark.parametrize("N,D,bg", [(2048, 384, 0.0), (33, 128, 2.0), (4, 64, 0.0)])
 def test_gru_gate_train_fwd_bwd_vs_torch(N, D, bg):
     """Training-side GTrXL gate (concatenated GEMMs + fused kernels, hand-written backward) against the six-map formulation of
-    transformer.py:287-298 with framework autograd."""
+    transformer.py:287-298 with framework autograd.
+    (The gate kernels alone, without the GEMMs in front, per row against float64: tests/test_block_kernels_vs_float64.py.)"""
     from etm import ops
     from transformer import GRUGate
     dev = _dev()
