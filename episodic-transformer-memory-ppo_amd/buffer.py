@@ -24,12 +24,15 @@ the storage redesigned for the MI355X path:
   invalid-action word into (bit j = column j of the concatenated policy head is allowed), ``action_masks`` [W, S] int64 its device
   copy (uploaded by ``prepare_batch_dict``) and a member of ``samples_flat``, so every minibatch carries its samples' words.  Without
   the key neither exists and ``samples_flat`` has its usual keys.
+* ``kl_estimator: analytic`` (absent upstream; Box policies): ``means`` [W, S, A], the rollout's Gaussian means, a member of
+  ``samples_flat``, and ``old_log_std`` [A], the log-std that drew them, copied once per update by ``prepare_batch_dict``.  They live
+  for one rollout (nothing of them is in a checkpoint).  Without the key neither exists.
 """
 import numpy as np
 import torch
 
 from etm import ops
-from utils import normalization_section
+from utils import kl_estimator_section, normalization_section
 
 
 class Buffer:
@@ -75,6 +78,17 @@ class Buffer:
             self._action_masks_host = pin((W, S), torch.int64)
             self.action_masks_host = self._action_masks_host.numpy()
             self.action_masks = torch.zeros((W, S), dtype=torch.int64, device=dev)
+
+        # the exact Gaussian KL (kl_estimator: analytic, Box policies): the rollout's means [W, S, A] next to ``actions`` (a member of
+        # ``samples_flat``, so every minibatch carries its samples' old means) and a snapshot of the log-std that drew them -- the
+        # parameter moves during the update --, taken by ``prepare_batch_dict`` from ``log_std_source`` (the trainer sets it: the
+        # model's policy_log_std); None without the key
+        self.means = self.old_log_std = self.log_std_source = None
+        if kl_estimator_section(config) == "analytic":
+            if not continuous:
+                raise ValueError("kl_estimator: analytic needs a Box (continuous) policy; remove the key")
+            self.means = torch.zeros((W, S, B), dtype=torch.float32, device=dev)
+            self.old_log_std = torch.zeros(B, dtype=torch.float32, device=dev)
 
         # return-based reward scaling (normalize_rewards): None without the key
         self.return_norm = normalization_section(config, "normalize_rewards")
@@ -170,6 +184,10 @@ class Buffer:
         self.memory_index.copy_(self._memory_index_host, non_blocking=True)
         if self.action_masks is not None:
             self.action_masks.copy_(self._action_masks_host, non_blocking=True)
+        if self.old_log_std is not None:
+            if self.log_std_source is None:
+                raise RuntimeError("kl_estimator: analytic: the buffer has no log_std_source to take the update's snapshot from")
+            self.old_log_std.copy_(self.log_std_source.detach().reshape(-1))       # one device-to-device copy per update
         self._mark_host_arrays_uploaded()
         samples = {
             "actions": self.actions, "values": self.values, "log_probs": self.log_probs, "advantages": self.advantages,
@@ -178,6 +196,8 @@ class Buffer:
         }
         if self.action_masks is not None:
             samples["action_masks"] = self.action_masks
+        if self.means is not None:
+            samples["means"] = self.means
         self.samples_flat = {k: v.reshape(v.shape[0] * v.shape[1], *v.shape[2:]) for k, v in samples.items()}
 
     def mini_batch_generator(self, indices: torch.Tensor = None, materialize: bool = False):

@@ -211,9 +211,13 @@ static inline int etm_box_make(const float *lo, const float *hi, int A, EtmBox *
 // log p and the value ([S, stage_W]); actions / host_actions [W, A] receive clip(x, lo, hi).  normals / forced / log_std: A floats.
 // The mode of a Box policy needs no sentinel: a zero in the normals table stores x = mu + sigma * 0 = mu (the deterministic
 // rollouts of the evaluator zero the table), and log p is then sum_a [(-0 - log sigma_a) - log(2 pi) / 2].
+// MN: the means are staged too, st_means [S, stage_W, A] next to st_actions -- the policy's mu, forced action or not (the exact KL of
+// the update needs the distribution that drew the sample); MN = false never reads st_means.
+template <bool MN = false>
 __device__ __forceinline__ void etm_sample_gaussian(const float *mu, const float *log_std, const EtmBox &bx, const float *normals,
                                                     const float *forced, float value, long long row, int w, float *actions,
-                                                    float *host_actions, float *st_actions, float *st_logp, float *st_values) {
+                                                    float *host_actions, float *st_actions, float *st_logp, float *st_values,
+                                                    float *st_means = nullptr) {
   const int A = bx.A;
   float lp = 0.f;
   for (int a = 0; a < A; ++a) {
@@ -227,6 +231,7 @@ __device__ __forceinline__ void etm_sample_gaussian(const float *mu, const float
     actions[(long long)w * A + a] = c;
     if (host_actions) host_actions[(long long)w * A + a] = c;
     st_actions[row * A + a] = x;
+    if constexpr (MN) st_means[row * A + a] = mu[a];
   }
   st_logp[row] = lp;
   st_values[row] = value;

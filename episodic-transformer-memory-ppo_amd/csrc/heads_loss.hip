@@ -49,13 +49,21 @@ struct HlParams {
   // MK kernels (invalid-action masks): amask [N] int64, bit j of a sample's word = column j of the A logits was allowed when the
   // sample was drawn
   const long long *amask;
+  // KL kernels (Box, the exact KL statistic): old_mean [N, A] (row stride old_mean_stride floats) the means of the policy that drew the
+  // samples, old_log_std [A] its log sigma
+  const float *old_mean, *old_log_std;
+  long long old_mean_stride;
 };
 
 // BR: MultiDiscrete branches; GS: diagonal Gaussian (Box; the row gains d log_std [A] behind the five statistic sums)
 // MK: invalid-action masks (BR or not).  A branch's log-sum-exp, log-probs and entropy run over its VALID columns only (ok(j)); an
 // invalid column has p = 0, is skipped -- not multiplied: 0 * inf -- by the entropy, and its d logit is exactly 0.  The logit dot
 // products and the optional logits output stay raw.  What is left is the unmasked arithmetic on the compacted branch.
-template <int HC, bool BR, bool GS, bool MK>
+// KL (GS only): a sixth running sum, the exact KL(old || new) of the two diagonal Gaussians,
+//   KL_n = sum_a [(expm1(2 d_a) / 2 - d_a) + ((mu_old[n, a] - mu[n, a]) / sigma_a)^2 / 2],  d_a = log sigma_old_a - log sigma_a,
+// written so that nothing cancels (equal policies give exactly 0).  A statistic only: no term of the loss, no gradient; the sum sits
+// behind d log_std at the very end of the row, so every other row offset keeps its value.
+template <int HC, bool BR, bool GS, bool MK, bool KL = false>
 __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
   HlParams p = p0;
   if (p.dyn) {
@@ -88,6 +96,13 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
       s_ls[a] = 0.f;
       if (a < A) ent_gs += (0.5f + 0.918938533204672742f) + lsr[a];
     }
+  }
+  // KL: the part of KL_n that does not depend on the sample, and the sixth sum
+  float kl_ls = 0.f, acc_kl = 0.f;
+  if constexpr (KL) {
+#pragma unroll
+    for (int a = 0; a < HL_MAXA; ++a)
+      if (a < A) { const float d = p.old_log_std[a] - lsr[a]; kl_ls += 0.5f * expm1f(2.f * d) - d; }
   }
   const float bvr = p.bv[0];
   const float cnt = p.adv_stats3[0], mean = p.adv_stats3[1], m2 = p.adv_stats3[2];
@@ -194,6 +209,13 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
           dl[a] = cpol * (zr[a] / sgr[a]);
           if (lane == 0) s_ls[a] += cpol * (zr[a] * zr[a] - 1.f) + cent;
         }
+      }
+      if constexpr (KL) {
+        float kq = 0.f;
+#pragma unroll
+        for (int a = 0; a < HL_MAXA; ++a)
+          if (a < A) { const float q = (p.old_mean[(long long)n * p.old_mean_stride + a] - lg[a]) / sgr[a]; kq += 0.5f * q * q; }
+        if (lane == 0) acc_kl += kl_ls + kq;
       }
     } else if constexpr (!BR) {
     float mx = -INFINITY;
@@ -341,8 +363,8 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
   }
 
   // ---- the four waves' sums -> one partial row per workgroup: [sum gm_p | sum gm_v | d wv | d Wb[0] .. d Wb[A-1] | d bb[A] | d bv | 5 stats]
-  //      (GS: then d log_std[A])
-  const int row = (3 + A) * hid + A + 1 + 5 + (GS ? A : 0);
+  //      (GS: then d log_std[A]; KL: then the KL sum)
+  const int row = (3 + A) * hid + A + 1 + 5 + (GS ? A : 0) + (KL ? 1 : 0);
   auto put_row = [&](float *dst, bool add) {
 #pragma unroll
     for (int c = 0; c < HC; ++c) {
@@ -367,6 +389,7 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
         for (int a = 0; a < HL_MAXA; ++a)
           if (a < A) { if (add) t[A + 6 + a] += s_ls[a]; else t[A + 6 + a] = s_ls[a]; }
       }
+      if constexpr (KL) { if (add) t[A + 6 + A] += acc_kl; else t[A + 6 + A] = acc_kl; }
     }
   };
   put_row(hl_lds + (long long)wave * row, false);
@@ -380,14 +403,18 @@ template <int HC, bool BR, bool GS = false>
 __global__ __launch_bounds__(256) void heads_loss_kernel(const HlParams p0) { heads_loss_body<HC, BR, GS, false>(p0); }
 template <int HC, bool BR>
 __global__ __launch_bounds__(256) void heads_loss_masked_kernel(const HlParams p0) { heads_loss_body<HC, BR, false, true>(p0); }
+template <int HC>
+__global__ __launch_bounds__(256) void heads_loss_gaussian_kl_kernel(const HlParams p0) { heads_loss_body<HC, false, true, false, true>(p0); }
 
 // sums the workgroup rows and finishes the loss statistics: out = [row sums ... ], out8 (a Gaussian row's d log_std sums, behind the
 // statistics, are summed like every other element).  One workgroup = 64 row elements x 16 row
 // groups: thread (e, g) adds the rows g, g + 16, ... (all requested at once: the sum is a latency chain otherwise), the 16 group
 // sums are added in group order -- a fixed tree, deterministic.
-__global__ __launch_bounds__(1024) void heads_reduce_kernel(const float *__restrict__ partials, int n_wg, int row, int A, int hid, float vf_coef,
-                                                            float beta, float pol_scale, float ent_scale, float val_scale,
-                                                            const double *__restrict__ dyn, float *__restrict__ out, float *__restrict__ out8) {
+// KL (the Gaussian row with the KL sum as its last element): out8[4] = that sum * ent_scale (the exact KL), out8[6] = the k3 value.
+template <bool KL>
+__device__ __forceinline__ void heads_reduce_body(const float *__restrict__ partials, int n_wg, int row, int A, int hid, float vf_coef,
+                                                  float beta, float pol_scale, float ent_scale, float val_scale,
+                                                  const double *__restrict__ dyn, float *__restrict__ out, float *__restrict__ out8) {
   __shared__ float sm[16][64];
   const int el = threadIdx.x & 63, g = threadIdx.x >> 6;
   auto group_sum = [&](int e) {
@@ -414,7 +441,8 @@ __global__ __launch_bounds__(1024) void heads_reduce_kernel(const float *__restr
   // the five statistic sums (the last five row elements) once more in this workgroup, then out8
   __syncthreads();
   const int st0 = (3 + A) * hid + A + 1;
-  sm[g][el] = el < 5 ? group_sum(st0 + el) : 0.f;
+  if constexpr (KL) sm[g][el] = el < 5 ? group_sum(st0 + el) : el == 5 ? group_sum(st0 + 5 + A) : 0.f;
+  else sm[g][el] = el < 5 ? group_sum(st0 + el) : 0.f;
   __syncthreads();
   if (threadIdx.x == 0) {
     float acc[5];
@@ -426,8 +454,25 @@ __global__ __launch_bounds__(1024) void heads_reduce_kernel(const float *__restr
     if (dyn) beta = (float)dyn[1];
     const float pol = acc[0] * pol_scale, val = acc[1] * val_scale, ent = acc[2] * ent_scale;
     out8[0] = pol; out8[1] = val; out8[2] = -(pol - vf_coef * val + beta * ent); out8[3] = ent;
-    out8[4] = acc[3] * pol_scale; out8[5] = acc[4] * pol_scale; out8[6] = 0.f; out8[7] = 0.f;
+    if constexpr (KL) {
+      float t = 0.f;
+      for (int k = 0; k < 16; ++k) t += sm[k][5];
+      out8[4] = t * ent_scale; out8[5] = acc[4] * pol_scale; out8[6] = acc[3] * pol_scale; out8[7] = 0.f;
+    } else {
+      out8[4] = acc[3] * pol_scale; out8[5] = acc[4] * pol_scale; out8[6] = 0.f; out8[7] = 0.f;
+    }
   }
+}
+__global__ __launch_bounds__(1024) void heads_reduce_kernel(const float *__restrict__ partials, int n_wg, int row, int A, int hid, float vf_coef,
+                                                            float beta, float pol_scale, float ent_scale, float val_scale,
+                                                            const double *__restrict__ dyn, float *__restrict__ out, float *__restrict__ out8) {
+  heads_reduce_body<false>(partials, n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn, out, out8);
+}
+__global__ __launch_bounds__(1024) void heads_reduce_kl_kernel(const float *__restrict__ partials, int n_wg, int row, int A, int hid,
+                                                               float vf_coef, float beta, float pol_scale, float ent_scale, float val_scale,
+                                                               const double *__restrict__ dyn, float *__restrict__ out,
+                                                               float *__restrict__ out8) {
+  heads_reduce_body<true>(partials, n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn, out, out8);
 }
 static_assert(true, "");
 constexpr int HL_SAMPLES_PER_WG = 8;      // two samples per wave: the pass is a latency chain per sample, so many short waves
@@ -445,6 +490,11 @@ extern "C" int64_t etm_heads_loss_gaussian_workspace_bytes(int N, int hid, int A
   if (!etm_heads_loss_supported_gaussian(N, hid, A)) return 0;
   return (int64_t)((N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG) * etm_heads_loss_gaussian_row_floats(hid, A) * (int64_t)sizeof(float);
 }
+extern "C" int etm_heads_loss_gaussian_kl_row_floats(int hid, int A) { return etm_heads_loss_gaussian_row_floats(hid, A) + 1; }
+extern "C" int64_t etm_heads_loss_gaussian_kl_workspace_bytes(int N, int hid, int A) {
+  if (!etm_heads_loss_supported_gaussian(N, hid, A)) return 0;
+  return (int64_t)((N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG) * etm_heads_loss_gaussian_kl_row_floats(hid, A) * (int64_t)sizeof(float);
+}
 
 // pre_p / pre_v [N, hid] = h Wlp^T / h Wlv^T (no bias).  Outputs: gm_p / gm_v [N, hid] = d loss / d (pre + bias) of the two hidden
 // heads; sums [etm_heads_loss_row_floats] = [d b_lp (hid) | d b_lv (hid) | d wv (hid) | d Wb (A x hid) | d bb (A) | d bv | 5 raw sums];
@@ -456,16 +506,20 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
                               float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v,
                               float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
                               int A, const int32_t *branch_sizes, int n_branches, const float *xact, const float *log_std,
-                              const int64_t *action_mask, void *stream) {
+                              const int64_t *action_mask, void *stream, const float *old_mean = nullptr, int64_t old_mean_stride = 0,
+                              const float *old_log_std = nullptr) {
   (void)hipGetLastError();
   const bool gauss = xact != nullptr;                  // Box: float actions xact and log_std instead of the int64 actions
+  const bool kl = old_mean != nullptr;                 // Box with the exact KL: the row gains the KL sum
   if (!pre_p || !pre_v || !b_lp || !b_lv || !wb || !bb || !wv || !bv || !(gauss ? (const void *)log_std : (const void *)actions) || !old_logp ||
       !adv || !old_value || !adv_stats3 || !gm_p || !gm_v || !sums || !out8 || !workspace)
     return ETM_EINVAL;
   if (action_mask && gauss) return ETM_EINVAL;
   if (const int rc = etm_action_mask_check(action_mask, A)) return rc;
   if (!(gauss ? etm_heads_loss_supported_gaussian(N, hid, A) : etm_heads_loss_supported(N, hid, A))) return ETM_EUNSUPPORTED;
-  if (workspace_bytes < (gauss ? etm_heads_loss_gaussian_workspace_bytes(N, hid, A) : etm_heads_loss_workspace_bytes(N, hid, A)))
+  if (workspace_bytes < (kl      ? etm_heads_loss_gaussian_kl_workspace_bytes(N, hid, A)
+                         : gauss ? etm_heads_loss_gaussian_workspace_bytes(N, hid, A)
+                                 : etm_heads_loss_workspace_bytes(N, hid, A)))
     return ETM_EWORKSPACE;
   HlParams p{};
   EtmBranches br;
@@ -484,9 +538,10 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
   p.gm_p = gm_p; p.gm_v = gm_v; p.logits = logits; p.value = value; p.partials = (float *)workspace;
   p.N = N; p.A = A; p.hid = hid; p.samples_per_wg = HL_SAMPLES_PER_WG;
   p.xact = xact; p.log_std = log_std; p.amask = (const long long *)action_mask;
+  p.old_mean = old_mean; p.old_mean_stride = old_mean_stride; p.old_log_std = old_log_std;
   const bool masked = action_mask != nullptr;
   const int n_wg = (N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG;
-  const int row = gauss ? etm_heads_loss_gaussian_row_floats(hid, A) : etm_heads_loss_row_floats(hid, A);
+  const int row = kl ? etm_heads_loss_gaussian_kl_row_floats(hid, A) : gauss ? etm_heads_loss_gaussian_row_floats(hid, A) : etm_heads_loss_row_floats(hid, A);
   const size_t lds = 4 * (size_t)row * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
   {
@@ -494,7 +549,8 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
     switch (hid / 64) {
 #define HL_CASE(HC_)                                                                                              \
   case HC_:                                                                                                       \
-    if (gauss) hipLaunchKernelGGL((heads_loss_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    if (kl) hipLaunchKernelGGL((heads_loss_gaussian_kl_kernel<HC_>), dim3((unsigned)n_wg), dim3(256), lds, st, p);  \
+    else if (gauss) hipLaunchKernelGGL((heads_loss_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
     else if (masked && branched) hipLaunchKernelGGL((heads_loss_masked_kernel<HC_, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
     else if (masked) hipLaunchKernelGGL((heads_loss_masked_kernel<HC_, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
     else if (branched) hipLaunchKernelGGL((heads_loss_kernel<HC_, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
@@ -508,8 +564,12 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
   int rc = etm_launch_status();
   if (rc) return rc;
   EtmProfScope prof(ETM_K_PPO_FINAL, st);
-  hipLaunchKernelGGL(heads_reduce_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg, row, A, hid, vf_coef,
-                     beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8);
+  if (kl)
+    hipLaunchKernelGGL(heads_reduce_kl_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg, row, A, hid,
+                       vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8);
+  else
+    hipLaunchKernelGGL(heads_reduce_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg, row, A, hid, vf_coef,
+                       beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8);
   return etm_launch_status();
 }
 
@@ -592,4 +652,26 @@ extern "C" int etm_heads_loss_gaussian(const float *pre_p, const float *pre_v, c
   return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, nullptr, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
                          clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
                          workspace_bytes, N, hid, A, nullptr, 1, xact, log_std, nullptr, stream);
+}
+
+// etm_heads_loss_gaussian with the exact KL statistic: old_mean [N, A] (row stride old_mean_stride >= A floats) the means of the policy
+// that drew the samples, old_log_std [A] its log sigma (a snapshot: log_std moves during the update).  sums
+// [etm_heads_loss_gaussian_kl_row_floats] = the etm_heads_loss_gaussian row followed by the raw KL sum; out8[4] = the exact
+// KL(old || new) (mean over the samples, summed over the dimensions), out8[6] = the k3 sample estimate; the loss, every gradient and
+// every other statistic are etm_heads_loss_gaussian's, bit for bit.  ETM_EINVAL: NULL or 4-byte-misaligned old_mean / old_log_std, a
+// stride below A.
+extern "C" int etm_heads_loss_gaussian_kl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                          const float *bb, const float *wv, const float *bv, const float *xact, int64_t action_stride,
+                                          const float *log_std, const float *old_logp, int64_t logp_stride, const float *adv,
+                                          const float *old_value, const float *adv_stats3, double clip, float vf_coef, float beta,
+                                          float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p,
+                                          float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace,
+                                          int64_t workspace_bytes, int N, int hid, int A, const float *old_mean, int64_t old_mean_stride,
+                                          const float *old_log_std, void *stream) {
+  if (!xact || !old_mean || !old_log_std) return ETM_EINVAL;
+  if (((uintptr_t)old_mean | (uintptr_t)old_log_std) & 3u) return ETM_EINVAL;
+  if (action_stride < A || logp_stride < 1 || old_mean_stride < A) return ETM_EINVAL;
+  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, nullptr, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
+                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
+                         workspace_bytes, N, hid, A, nullptr, 1, xact, log_std, nullptr, stream, old_mean, old_mean_stride, old_log_std);
 }

@@ -39,15 +39,20 @@ namespace {
 // configuration) gets a kernel without that code, which keeps its register allocation free of spills.
 // BOX: a Box policy's Gaussian draw at the end (etm_sample_gaussian, float tables p.box) instead of the categorical branches.
 // The body is included text (rollout_fused_body.inc): the kernels without masks are what they were, the masked kernel (categorical
-// policies only) is the same text with MK = true.
+// policies only) is the same text with MK = true, the Box kernel that also stages the means the same text with MN = true.
 template <int GR, int LMAX, bool GEN, bool BOX>
 __global__ __launch_bounds__(RF_T) void rollout_trxl_kernel(const RfParams p) {
-  constexpr bool MK = false;
+  constexpr bool MK = false, MN = false;
 #include "rollout_fused_body.inc"
 }
 template <int GR, int LMAX, bool GEN>
 __global__ __launch_bounds__(RF_T) void rollout_trxl_masked_kernel(const RfParams p) {
-  constexpr bool BOX = false, MK = true;
+  constexpr bool BOX = false, MK = true, MN = false;
+#include "rollout_fused_body.inc"
+}
+template <int GR, int LMAX, bool GEN>
+__global__ __launch_bounds__(RF_T) void rollout_trxl_gaussian_means_kernel(const RfParams p) {
+  constexpr bool BOX = true, MK = false, MN = true;
 #include "rollout_fused_body.inc"
 }
 }  // namespace
@@ -213,8 +218,10 @@ static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, 
                                 int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
                                 int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
                                 int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W,
-                                const int32_t *branch_sizes, int n_branches, const RfBox *box, const int64_t *action_mask, void *stream) {
+                                const int32_t *branch_sizes, int n_branches, const RfBox *box, const int64_t *action_mask, void *stream,
+                                bool means = false, float *st_means = nullptr) {
   (void)hipGetLastError();
+  if (means && (!box || !st_means || ((uintptr_t)st_means & 3u))) return ETM_EINVAL;
   if (ss && (!mask_table || !index_table || !st_mask || !st_idx || !latch || !mask_t || !win_t || T <= 0)) return ETM_EINVAL;
   if (!ss && (!win || !mask)) return ETM_EINVAL;
   // (a Box policy's action tables are the float ones of `box`; the int64 ones are unused then)
@@ -242,7 +249,7 @@ static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, 
   if (box) p.box = *box;                               // (RfParams{}: box.bx.A == 0 selects the categorical instantiations)
   p.ss = (const long long *)ss; p.mask_table = mask_table; p.index_table = (const long long *)index_table; p.st_mask = st_mask;
   p.st_idx = (long long *)st_idx; p.latch = (long long *)latch; p.t_row = (long long *)t_row; p.mask_t = mask_t; p.win_t = (long long *)win_t;
-  p.kv_init = kv_init; p.T = T; p.am = (const long long *)action_mask;
+  p.kv_init = kv_init; p.T = T; p.am = (const long long *)action_mask; p.st_means = means ? st_means : nullptr;
   p.h_in = h_in; p.h_bias = h_bias; p.h_splits = h_splits; p.wemb_t = wemb_t; p.bemb = bemb; p.nb = nb;
   for (int b = 0; b < nb; ++b) {
     const float *const *q = reinterpret_cast<const float *const *>(blocks) + RF_BLOCK_PTRS * b;
@@ -275,7 +282,10 @@ static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, 
   const bool gen = pre_ln || gtrxl, box_k = p.box.bx.A > 0;
 #define RF_LAUNCH(GR_, LM_)                                                                                      \
   do {                                                                                                           \
-    if (box_k) {                                                                                                 \
+    if (box_k && p.st_means) {                                                                                   \
+      if (gen) hipLaunchKernelGGL((rollout_trxl_gaussian_means_kernel<GR_, LM_, true>), grid, block, 0, st, p);  \
+      else hipLaunchKernelGGL((rollout_trxl_gaussian_means_kernel<GR_, LM_, false>), grid, block, 0, st, p);     \
+    } else if (box_k) {                                                                                          \
       if (gen) hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, true, true>), grid, block, 0, st, p);           \
       else hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, false, true>), grid, block, 0, st, p);              \
     } else if (p.am) {                                                                                           \
@@ -428,7 +438,8 @@ static int rollout_trxl_gaussian_impl(int group, const float *h_in, const float 
                                       int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table,
                                       uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,
                                       const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A,
-                                      int stage_W, const float *low, const float *high, void *stream) {
+                                      int stage_W, const float *low, const float *high, void *stream, bool means = false,
+                                      float *st_means = nullptr) {
   RfBox box{};
   if (const int rc = etm_box_make(low, high, A, &box.bx)) return rc;
   box.log_std = log_std; box.normals = normals; box.forced = forced;
@@ -437,9 +448,10 @@ static int rollout_trxl_gaussian_impl(int group, const float *h_in, const float 
                            nullptr, nullptr, t_dev, nullptr, nullptr, st_logp, st_values, nullptr, host_flag, sync_counter, ln_eps, scratch,
                            scratch_bytes, wkv, pos, step_l, slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits,
                            ss, mask_table, index_table, st_mask, st_idx, latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid,
-                           A, stage_W, nullptr, 1, &box, nullptr, stream);
+                           A, stage_W, nullptr, 1, &box, nullptr, stream, means, st_means);
 }
-#define RF_GAUSSIAN_ARGS                                                                                                                   \
+#define RF_GAUSSIAN_ARGS RF_GAUSSIAN_ARGS_HEAD, void *stream
+#define RF_GAUSSIAN_ARGS_HEAD                                                                                                              \
   const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv, int64_t kv_worker_stride,      \
       int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items, const float *wh_t, const float *bh, const float *wp,   \
       const float *bp, const float *wv, const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev, \
@@ -449,7 +461,7 @@ static int rollout_trxl_gaussian_impl(int group, const float *h_in, const float 
       int64_t bank_block_stride, const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table,                        \
       const int64_t *index_table, uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,    \
       const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W, const float *low,     \
-      const float *high, void *stream
+      const float *high
 #define RF_GAUSSIAN_PASS                                                                                                                   \
   h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, log_std, normals,     \
       forced, t_dev, actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, \
@@ -457,6 +469,15 @@ static int rollout_trxl_gaussian_impl(int group, const float *h_in, const float 
       st_mask, st_idx, latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, low, high, stream
 extern "C" int etm_rollout_trxl_gaussian(RF_GAUSSIAN_ARGS) { return rollout_trxl_gaussian_impl(0, RF_GAUSSIAN_PASS); }
 extern "C" int etm_rollout_trxl_group_gaussian(RF_GAUSSIAN_ARGS) { return rollout_trxl_gaussian_impl(1, RF_GAUSSIAN_PASS); }
+// The same two entries with the policy's means staged as well: st_means [S, stage_W, A] next to st_actions (at this group's first
+// worker, as st_actions), forced action or not.  ETM_EINVAL: NULL or 4-byte-misaligned st_means.
+extern "C" int etm_rollout_trxl_gaussian_means(RF_GAUSSIAN_ARGS_HEAD, float *st_means, void *stream) {
+  return rollout_trxl_gaussian_impl(0, RF_GAUSSIAN_PASS, true, st_means);
+}
+extern "C" int etm_rollout_trxl_group_gaussian_means(RF_GAUSSIAN_ARGS_HEAD, float *st_means, void *stream) {
+  return rollout_trxl_gaussian_impl(1, RF_GAUSSIAN_PASS, true, st_means);
+}
+#undef RF_GAUSSIAN_ARGS_HEAD
 #undef RF_GAUSSIAN_ARGS
 #undef RF_GAUSSIAN_PASS
 extern "C" int etm_rollout_trxl_supported_gaussian(int D, int H, int L, int hid, int A, int nb) {

@@ -1,6 +1,7 @@
 // The body of the per-worker step kernels of csrc/rollout_fused.hip (included text, one definition): the including kernel provides the
 // template parameters GR, LMAX, GEN, BOX, the launch parameters `p` and the constant MK (invalid-action masks: the sampler's word is
-// fetched with the step's uniforms and the masked instantiation of the shared sampler draws).
+// fetched with the step's uniforms and the masked instantiation of the shared sampler draws) and the constant MN (BOX only: the
+// Gaussian draw also stages the means into p.st_means).
   constexpr int KR = LMAX / RF_WAVES;                             // window rows per wave (energies)
   constexpr int VR = LMAX / 16;                                   // window rows per thread (context): >= 16 row groups (D / P <= 128)
   __shared__ __attribute__((aligned(16))) float x_s[RF_T];        // current hidden state h_b (full row, every member)
@@ -526,8 +527,8 @@
       const int A = p.A, B = p.br.n;
       const long long row = t * p.stage_W + w;
       if constexpr (BOX) {                                          // the A means, the step's normals / forced row, clipped hand-over
-        etm_sample_gaussian(out_s, box_s + 2 * ETM_MAX_BOX, p.box.bx, box_s, p.box.forced ? box_s + ETM_MAX_BOX : nullptr, out_s[A], row,
-                            w, p.box.actions, p.box.host_actions, p.box.st_actions, p.st_logp, p.st_values);
+        etm_sample_gaussian<MN>(out_s, box_s + 2 * ETM_MAX_BOX, p.box.bx, box_s, p.box.forced ? box_s + ETM_MAX_BOX : nullptr, out_s[A], row,
+                                w, p.box.actions, p.box.host_actions, p.box.st_actions, p.st_logp, p.st_values, MN ? p.st_means : nullptr);
       } else {
         int off = 0;
         for (int b = 0; b < B; ++b) {                               // per branch: its own logit segment, uniform and forced entry

@@ -111,21 +111,27 @@ __global__ __launch_bounds__(1024) void rollout_sample_masked_kernel(const float
 
 // Box policies (etm_sample_gaussian): one thread per worker, the A means of row w of `mean`, its A normals / forced entries of
 // step t (time-major [S, W, A]; NaN forced = "sample"); staging of the raw x, log p(x), the value; actions [W, A] = clip(x); t += 1.
+// The body is included text (rollout_sample_gaussian_body.inc): the kernel without the means is what it was, the one that stages them
+// too (st_means [S, W, A]) is the same text with MN = true.
 __global__ __launch_bounds__(1024) void rollout_sample_gaussian_kernel(const float *__restrict__ mean, const float *__restrict__ value,
                                                                        const float *__restrict__ log_std, const float *__restrict__ normals,
                                                                        const float *__restrict__ forced, long long *__restrict__ t_dev,
                                                                        float *__restrict__ actions, float *__restrict__ st_actions,
                                                                        float *__restrict__ st_logp, float *__restrict__ st_values, int W,
                                                                        const EtmBox bx) {
-  const long long t = *t_dev;
-  const int A = bx.A;
-  for (int w = threadIdx.x; w < W; w += 1024) {
-    const long long row = t * W + w;
-    etm_sample_gaussian(mean + (long long)w * A, log_std, bx, normals + row * A, forced ? forced + row * A : nullptr, value[w], row, w,
-                        actions, nullptr, st_actions, st_logp, st_values);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) *t_dev = t + 1;
+  constexpr bool MN = false;
+  float *const st_means = nullptr;
+#include "rollout_sample_gaussian_body.inc"
+}
+__global__ __launch_bounds__(1024) void rollout_sample_gaussian_means_kernel(const float *__restrict__ mean, const float *__restrict__ value,
+                                                                             const float *__restrict__ log_std,
+                                                                             const float *__restrict__ normals,
+                                                                             const float *__restrict__ forced, long long *__restrict__ t_dev,
+                                                                             float *__restrict__ actions, float *__restrict__ st_actions,
+                                                                             float *__restrict__ st_logp, float *__restrict__ st_values,
+                                                                             int W, const EtmBox bx, float *__restrict__ st_means) {
+  constexpr bool MN = true;
+#include "rollout_sample_gaussian_body.inc"
 }
 
 // The A + 1 outputs of the rollout heads of worker w into out_s (logits or means, then the value): one wave per output.
@@ -210,6 +216,8 @@ __global__ __launch_bounds__(256) void rollout_policy_masked_kernel(const float 
 
 // The same launch for a Box policy: the A outputs are the Gaussian's means; the draw of etm_sample_gaussian with the normals /
 // forced rows [S, stage_W, A] of (t, w); host_actions [W, A] (pinned) receives the clipped actions before the flag.
+// The body is included text (rollout_policy_gaussian_body.inc): the kernel without the means is what it was, the one that stages them
+// too (st_means [S, stage_W, A]) is the same text with MN = true.
 __global__ __launch_bounds__(256) void rollout_policy_gaussian_kernel(const float *__restrict__ h, const float *__restrict__ wp,
                                                                       const float *__restrict__ bp, const float *__restrict__ wv,
                                                                       const float *__restrict__ bv, const float *__restrict__ h_bias,
@@ -219,17 +227,23 @@ __global__ __launch_bounds__(256) void rollout_policy_gaussian_kernel(const floa
                                                                       float *__restrict__ st_logp, float *__restrict__ st_values,
                                                                       float *host_actions, long long *host_flag, int *sync_counter,
                                                                       int W, int hid, int stage_W, const EtmBox bx) {
-  __shared__ float out_s[ETM_MAX_BOX + 1];
-  const int w = blockIdx.x, A = bx.A;
-  const long long t = *t_dev;
-  policy_heads_lds(h, wp, bp, wv, bv, h_bias, out_s, w, A, hid);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const long long row = t * stage_W + w;
-    etm_sample_gaussian(out_s, log_std, bx, normals + row * A, forced ? forced + row * A : nullptr, out_s[A], row, w, actions,
-                        host_actions, st_actions, st_logp, st_values);
-    policy_arrive(host_actions != nullptr, t, t_dev, host_flag, sync_counter, W);
-  }
+  constexpr bool MN = false;
+  float *const st_means = nullptr;
+#include "rollout_policy_gaussian_body.inc"
+}
+__global__ __launch_bounds__(256) void rollout_policy_gaussian_means_kernel(const float *__restrict__ h, const float *__restrict__ wp,
+                                                                            const float *__restrict__ bp, const float *__restrict__ wv,
+                                                                            const float *__restrict__ bv, const float *__restrict__ h_bias,
+                                                                            const float *__restrict__ log_std,
+                                                                            const float *__restrict__ normals,
+                                                                            const float *__restrict__ forced, long long *__restrict__ t_dev,
+                                                                            float *__restrict__ actions, float *__restrict__ st_actions,
+                                                                            float *__restrict__ st_logp, float *__restrict__ st_values,
+                                                                            float *host_actions, long long *host_flag, int *sync_counter,
+                                                                            int W, int hid, int stage_W, const EtmBox bx,
+                                                                            float *__restrict__ st_means) {
+  constexpr bool MN = true;
+#include "rollout_policy_gaussian_body.inc"
 }
 
 // out = LayerNorm(act(a + a_bias) + b) * gamma + beta, one wave per row (post-LN blocks, transformer.py:143-149 / :164-170),
@@ -398,26 +412,49 @@ extern "C" int etm_rollout_policy_branched_masked(const float *h, const float *h
                              n_branches, action_mask, stream);
 }
 
-extern "C" int etm_rollout_sample_gaussian(const float *mean, const float *value, const float *log_std, const float *normals,
-                                           const float *forced, int64_t *t_dev, float *actions, float *st_actions, float *st_logp,
-                                           float *st_values, const float *low, const float *high, int W, int A, void *stream) {
+// (means: the _means entry, which also stages the means into st_means [S, W, A])
+static int rollout_sample_gaussian_impl(const float *mean, const float *value, const float *log_std, const float *normals,
+                                        const float *forced, int64_t *t_dev, float *actions, float *st_actions, float *st_logp,
+                                        float *st_values, const float *low, const float *high, int W, int A, bool means, float *st_means,
+                                        void *stream) {
   (void)hipGetLastError();
   if (!mean || !value || !log_std || !normals || !t_dev || !actions || !st_actions || !st_logp || !st_values || W <= 0) return ETM_EINVAL;
+  if (means && (!st_means || ((uintptr_t)st_means & 3u))) return ETM_EINVAL;
   EtmBox bx;
   if (const int rc = etm_box_make(low, high, A, &bx)) return rc;
   hipStream_t st = (hipStream_t)stream;
   EtmProfScope prof(ETM_K_ROLLOUT_SAMPLE, st);
-  hipLaunchKernelGGL(rollout_sample_gaussian_kernel, dim3(1), dim3(1024), 0, st, mean, value, log_std, normals, forced, (long long *)t_dev,
-                     actions, st_actions, st_logp, st_values, W, bx);
+  if (means)
+    hipLaunchKernelGGL(rollout_sample_gaussian_means_kernel, dim3(1), dim3(1024), 0, st, mean, value, log_std, normals, forced,
+                       (long long *)t_dev, actions, st_actions, st_logp, st_values, W, bx, st_means);
+  else
+    hipLaunchKernelGGL(rollout_sample_gaussian_kernel, dim3(1), dim3(1024), 0, st, mean, value, log_std, normals, forced, (long long *)t_dev,
+                       actions, st_actions, st_logp, st_values, W, bx);
   return etm_launch_status();
 }
+extern "C" int etm_rollout_sample_gaussian(const float *mean, const float *value, const float *log_std, const float *normals,
+                                           const float *forced, int64_t *t_dev, float *actions, float *st_actions, float *st_logp,
+                                           float *st_values, const float *low, const float *high, int W, int A, void *stream) {
+  return rollout_sample_gaussian_impl(mean, value, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values, low, high, W, A,
+                                      false, nullptr, stream);
+}
+// etm_rollout_sample_gaussian that also stages the policy's means: st_means [S, W, A] next to st_actions, forced action or not.
+// ETM_EINVAL: NULL or 4-byte-misaligned st_means.
+extern "C" int etm_rollout_sample_gaussian_means(const float *mean, const float *value, const float *log_std, const float *normals,
+                                                 const float *forced, int64_t *t_dev, float *actions, float *st_actions, float *st_logp,
+                                                 float *st_values, const float *low, const float *high, int W, int A, float *st_means,
+                                                 void *stream) {
+  return rollout_sample_gaussian_impl(mean, value, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values, low, high, W, A,
+                                      true, st_means, stream);
+}
 
-extern "C" int etm_rollout_policy_gaussian(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv,
-                                           const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev,
-                                           float *actions, float *st_actions, float *st_logp, float *st_values, float *host_actions,
-                                           int64_t *host_flag, int32_t *sync_counter, const float *low, const float *high, int W, int A,
-                                           int hid, int stage_W, void *stream) {
+static int rollout_policy_gaussian_impl(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv,
+                                        const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev,
+                                        float *actions, float *st_actions, float *st_logp, float *st_values, float *host_actions,
+                                        int64_t *host_flag, int32_t *sync_counter, const float *low, const float *high, int W, int A,
+                                        int hid, int stage_W, bool means, float *st_means, void *stream) {
   (void)hipGetLastError();
+  if (means && (!st_means || ((uintptr_t)st_means & 3u))) return ETM_EINVAL;
   if (!h || !wp || !bp || !wv || !bv || !log_std || !normals || !t_dev || !actions || !st_actions || !st_logp || !st_values ||
       !sync_counter || W <= 0 || hid <= 0 || stage_W < W)
     return ETM_EINVAL;
@@ -426,10 +463,33 @@ extern "C" int etm_rollout_policy_gaussian(const float *h, const float *h_bias, 
   if (const int rc = etm_box_make(low, high, A, &bx)) return rc;
   hipStream_t st = (hipStream_t)stream;
   EtmProfScope prof(ETM_K_ROLLOUT_SAMPLE, st);
-  hipLaunchKernelGGL(rollout_policy_gaussian_kernel, dim3((unsigned)W), dim3(256), 0, st, h, wp, bp, wv, bv, h_bias, log_std, normals, forced,
-                     (long long *)t_dev, actions, st_actions, st_logp, st_values, host_actions, (long long *)host_flag, (int *)sync_counter,
-                     W, hid, stage_W, bx);
+  if (means)
+    hipLaunchKernelGGL(rollout_policy_gaussian_means_kernel, dim3((unsigned)W), dim3(256), 0, st, h, wp, bp, wv, bv, h_bias, log_std, normals,
+                       forced, (long long *)t_dev, actions, st_actions, st_logp, st_values, host_actions, (long long *)host_flag,
+                       (int *)sync_counter, W, hid, stage_W, bx, st_means);
+  else
+    hipLaunchKernelGGL(rollout_policy_gaussian_kernel, dim3((unsigned)W), dim3(256), 0, st, h, wp, bp, wv, bv, h_bias, log_std, normals, forced,
+                       (long long *)t_dev, actions, st_actions, st_logp, st_values, host_actions, (long long *)host_flag, (int *)sync_counter,
+                       W, hid, stage_W, bx);
   return etm_launch_status();
+}
+extern "C" int etm_rollout_policy_gaussian(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv,
+                                           const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev,
+                                           float *actions, float *st_actions, float *st_logp, float *st_values, float *host_actions,
+                                           int64_t *host_flag, int32_t *sync_counter, const float *low, const float *high, int W, int A,
+                                           int hid, int stage_W, void *stream) {
+  return rollout_policy_gaussian_impl(h, h_bias, wp, bp, wv, bv, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values,
+                                      host_actions, host_flag, sync_counter, low, high, W, A, hid, stage_W, false, nullptr, stream);
+}
+// etm_rollout_policy_gaussian that also stages the policy's means: st_means [S, stage_W, A] next to st_actions (at this group's
+// first worker, as st_actions).  ETM_EINVAL: NULL or 4-byte-misaligned st_means.
+extern "C" int etm_rollout_policy_gaussian_means(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv,
+                                                 const float *bv, const float *log_std, const float *normals, const float *forced,
+                                                 int64_t *t_dev, float *actions, float *st_actions, float *st_logp, float *st_values,
+                                                 float *host_actions, int64_t *host_flag, int32_t *sync_counter, const float *low,
+                                                 const float *high, int W, int A, int hid, int stage_W, float *st_means, void *stream) {
+  return rollout_policy_gaussian_impl(h, h_bias, wp, bp, wv, bv, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values,
+                                      host_actions, host_flag, sync_counter, low, high, W, A, hid, stage_W, true, st_means, stream);
 }
 
 extern "C" int etm_rollout_heads(const float *h, const float *wp, const float *bp, const float *wv, const float *bv, float *logits,

@@ -1,6 +1,7 @@
 // The body of the group step kernels of csrc/rollout_group.hip (included text, one definition): the including kernel provides the
 // template parameters KM, LMAX, BOX, the launch parameters `p` and the constant MK (invalid-action masks: workgroup 0 fetches the
-// workers' words next to the (step, slot) block and the masked instantiation of the shared sampler draws).
+// workers' words next to the (step, slot) block and the masked instantiation of the shared sampler draws) and the constant MN (BOX
+// only: the Gaussian draw also stages the means into p.st_means).
   constexpr int GR = 20;                                          // tail: rows of a K | V projection slice per thread and batch
   constexpr int KR = LMAX / RF_WAVES, VR = LMAX / 16;
   constexpr int NPK = (KM + 3) / 4;                               // packets per thread of a full gather: 32 * 8 CB / 2 / 512 = D / 128
@@ -460,8 +461,9 @@
       if constexpr (BOX) {
         // the A means; the normals / forced row [S, stage_W, A] of (t, tid); clipped hand-over
         const long long row = t * p.stage_W + tid;
-        etm_sample_gaussian(lg, p.box.log_std, p.box.bx, p.box.normals + row * A, p.box.forced ? p.box.forced + row * A : nullptr, lg[A],
-                            row, tid, p.box.actions, p.box.host_actions, p.box.st_actions, p.st_logp, p.st_values);
+        etm_sample_gaussian<MN>(lg, p.box.log_std, p.box.bx, p.box.normals + row * A, p.box.forced ? p.box.forced + row * A : nullptr, lg[A],
+                                row, tid, p.box.actions, p.box.host_actions, p.box.st_actions, p.st_logp, p.st_values,
+                                MN ? p.st_means : nullptr);
       } else {
         // per branch: its own logit segment, uniform and forced entry ([S, stage_W, B] tables; B = 1: [S, stage_W])
         etm_sample_branches<MK>(lg, p.br, t * p.stage_W + tid, tid, p.uniforms, p.forced, p.actions, p.host_actions, p.st_actions,

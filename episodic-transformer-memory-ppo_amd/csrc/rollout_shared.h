@@ -81,6 +81,7 @@ struct RfParams {
   RfBox box;                         // Box policies only (the BOX instantiations): the float action tables
   // (last: every member above keeps its place in the kernels' argument block)
   const long long *am;               // the masked instantiations only: [W] action-mask words of the step (device or pinned host memory)
+  float *st_means;                   // the BOX instantiations that stage the means only (MN): [S, stage_W, A] next to box.st_actions
 };
 
 namespace {

@@ -7,7 +7,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: torch ships its ow
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libetm_hip.so")     # (diagnostic tools that load another build assign this before load())
-ABI_VERSION = 60
+ABI_VERSION = 61
 
 _lib = None
 
@@ -197,6 +197,16 @@ for _name, _extra in (("etm_rollout_sample_branched", [_P]), ("etm_rollout_polic
                       ("etm_ppo_loss", [_P, _I])):
     _res, _args = SIGNATURES[_name]
     SIGNATURES[_name + "_masked"] = (_res, _args[:-1] + _extra + _args[-1:])
+# the exact Gaussian KL (ABI 61): the four Gaussian sampling entries with the means' staging table in front of the stream, and the
+# Gaussian heads + loss pass with old_mean, its row stride and old_log_std there
+for _name, _extra in (("etm_rollout_sample_gaussian", [_P]), ("etm_rollout_policy_gaussian", [_P]), ("etm_rollout_trxl_gaussian", [_P]),
+                      ("etm_rollout_trxl_group_gaussian", [_P])):
+    _res, _args = SIGNATURES[_name]
+    SIGNATURES[_name + "_means"] = (_res, _args[:-1] + _extra + _args[-1:])
+_res, _args = SIGNATURES["etm_heads_loss_gaussian"]
+SIGNATURES["etm_heads_loss_gaussian_kl"] = (_res, _args[:-1] + [_P, _L, _P] + _args[-1:])
+SIGNATURES["etm_heads_loss_gaussian_kl_row_floats"] = (_I, [_I, _I])
+SIGNATURES["etm_heads_loss_gaussian_kl_workspace_bytes"] = (_L, [_I, _I, _I])
 del _name, _extra, _res, _args
 
 

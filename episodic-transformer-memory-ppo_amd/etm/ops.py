@@ -890,24 +890,42 @@ def _check_box_tables(A, W, log_std, normals, forced, actions, st_actions):
         raise ValueError(f"log_std: need {A} entries, got {log_std.numel()}")
 
 
-def rollout_sample_gaussian(mean, value, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values, low=None, high=None):
+def _check_means_table(st_means, st_actions):
+    """The means' staging table of the ``*_gaussian_means`` entries lies next to ``st_actions``: same shape, float32, contiguous."""
+    if (st_means.dtype != torch.float32 or st_means.shape != st_actions.shape or not st_means.is_contiguous()
+            or st_means.device != st_actions.device):
+        raise ValueError(f"st_means: need a contiguous float32 table of st_actions' shape {tuple(st_actions.shape)} on its device, "
+                         f"got {tuple(st_means.shape)} {st_means.dtype}")
+
+
+def rollout_sample_gaussian(mean, value, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values, low=None, high=None,
+                            st_means=None):
     """Gaussian sampling + staging of one rollout step of a Box policy (in place; increments t_dev), etm_rollout_sample_gaussian:
     x = mean + exp(log_std) normals[t] (or ``forced[t]`` where it is not NaN), ``st_actions`` [S, W, A] = x, ``st_logp`` [S, W(, 1)]
-    = log p(x), ``actions`` [W, A] = clip(x, low, high)."""
+    = log p(x), ``actions`` [W, A] = clip(x, low, high).  ``st_means`` (optional, float32 [S, W, A]): the means are staged too,
+    forced action or not (etm_rollout_sample_gaussian_means); None is exactly the call without."""
     lib = _lib.load()
     W, A = mean.shape
     mean, value = _f32c(mean, "mean"), _f32c(value, "value")
     _check_box_tables(A, W, log_std, normals, forced, actions, st_actions)
     lo, hi = _box_bounds(low, high, A)
+    if st_means is not None:
+        _check_means_table(st_means, st_actions)
+        _lib.check(lib.etm_rollout_sample_gaussian_means(_ptr(mean), _ptr(value), _ptr(log_std), _ptr(normals), _ptr(forced), _ptr(t_dev),
+                                                         _ptr(actions), _ptr(st_actions), _ptr(st_logp), _ptr(st_values), lo, hi, W, A,
+                                                         _ptr(st_means), _stream()),
+                   "etm_rollout_sample_gaussian_means")
+        return
     _lib.check(lib.etm_rollout_sample_gaussian(_ptr(mean), _ptr(value), _ptr(log_std), _ptr(normals), _ptr(forced), _ptr(t_dev), _ptr(actions),
                                                _ptr(st_actions), _ptr(st_logp), _ptr(st_values), lo, hi, W, A, _stream()),
                "etm_rollout_sample_gaussian")
 
 
 def rollout_policy_gaussian(h2, mean_head, value_head, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values,
-                            low=None, high=None, host_actions=None, host_flag=None, h_bias=None, w_off=0):
+                            low=None, high=None, host_actions=None, host_flag=None, h_bias=None, w_off=0, st_means=None):
     """``rollout_policy`` for a Box policy (etm_rollout_policy_gaussian): the heads, the draw of ``rollout_sample_gaussian`` and the
-    hand-over of the clipped float actions (``host_actions``: pinned float32 [W, A]) in one launch."""
+    hand-over of the clipped float actions (``host_actions``: pinned float32 [W, A]) in one launch.  ``st_means``: as in
+    ``rollout_sample_gaussian`` ([S, W_total, A], this group's slice taken as for ``st_actions``; etm_rollout_policy_gaussian_means)."""
     lib = _lib.load()
     W, A = h2.shape[0], mean_head.weight.shape[0]
     hid = h2.shape[1] // 2
@@ -921,6 +939,16 @@ def rollout_policy_gaussian(h2, mean_head, value_head, log_std, normals, forced,
     _check_box_tables(A, W, log_std, normals, forced, actions, st_actions)
     off = lambda t: None if t is None else t.data_ptr() + w_off * A * t.element_size()      # [S, W_total, A] tables
     lo, hi = _box_bounds(low, high, A)
+    if st_means is not None:
+        _check_means_table(st_means, st_actions)
+        _lib.check(lib.etm_rollout_policy_gaussian_means(_ptr(h2), _ptr(h_bias), _ptr(mean_head.weight), _ptr(mean_head.bias),
+                                                         _ptr(value_head.weight), _ptr(value_head.bias), _ptr(log_std), off(normals),
+                                                         off(forced), _ptr(t_dev), _ptr(actions), off(st_actions),
+                                                         st_logp.data_ptr() + w_off * st_logp.element_size(),
+                                                         st_values.data_ptr() + w_off * st_values.element_size(), ha, hf, _ptr(sync), lo, hi,
+                                                         W, A, hid, stage_w, off(st_means), _stream()),
+                   "etm_rollout_policy_gaussian_means")
+        return
     _lib.check(lib.etm_rollout_policy_gaussian(_ptr(h2), _ptr(h_bias), _ptr(mean_head.weight), _ptr(mean_head.bias), _ptr(value_head.weight),
                                                _ptr(value_head.bias), _ptr(log_std), off(normals), off(forced), _ptr(t_dev), _ptr(actions),
                                                off(st_actions), st_logp.data_ptr() + w_off * st_logp.element_size(),
@@ -1031,7 +1059,7 @@ def rollout_trxl_supported(D, H, L, hid, A, nb, gaussian=False):
 
 def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head, uniforms, forced, t_dev, actions, st_actions, st_logp,
                  st_values, scratch, host_actions=None, host_flag=None, w_off=0, tail=None, h_bias=None, window=None, branches=None, box=None,
-                 action_mask=None):
+                 action_mask=None, st_means=None):
     """Transformer + hidden / output heads + sampling of one rollout step of a worker group in one launch (etm_rollout_trxl).
     ``fused``: the transposed fixed-address weight copies of ``ActorCriticModel.refresh_rollout_weights`` (dict with the host
     pointer table ``blocks``); ``kv`` the group's K | V cache [W, T, blocks, 2D]; ``scratch`` from ``rollout_trxl_scratch``; the
@@ -1044,8 +1072,12 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
     high); ``policy_head`` is then the mean head, ``uniforms`` the normals and ``forced`` the NaN-or-action table, both float
     [S, W_total, A], ``actions`` / ``st_actions`` / ``host_actions`` float (etm_rollout_trxl_gaussian / _group_gaussian).
     ``action_mask`` (optional, categorical policies): int64 [W] words of this group's workers, device or pinned host memory (read in
-    place at the start of the launch), as in ``rollout_sample`` (etm_rollout_trxl_branched_masked / _group_branched_masked)."""
+    place at the start of the launch), as in ``rollout_sample`` (etm_rollout_trxl_branched_masked / _group_branched_masked).
+    ``st_means`` (optional, Box policy only): the means' staging table as in ``rollout_policy_gaussian``
+    (etm_rollout_trxl_gaussian_means / _group_gaussian_means)."""
     lib = _lib.load()
+    if st_means is not None and box is None:
+        raise ValueError("rollout_trxl: st_means belongs to a Box policy")
     h_in = _f32c(h_in, "h_in")
     h_splits = 0
     if h_bias is not None:        # h_in = [splits, W, D] slice sums of rollout_hidden_partial
@@ -1105,6 +1137,12 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
         lo, hi = _box_bounds(low, high, A)
         gargs = args[:17] + (_ptr(log_std), offa(uniforms), offa(forced), _ptr(t_dev), _ptr(actions), offa(st_actions),
                              st_logp.data_ptr() + w_off * st_logp.element_size()) + args[23:]
+        if st_means is not None:
+            _check_means_table(st_means, st_actions)
+            entry, name = ((lib.etm_rollout_trxl_group_gaussian_means, "etm_rollout_trxl_group_gaussian_means") if group
+                           else (lib.etm_rollout_trxl_gaussian_means, "etm_rollout_trxl_gaussian_means"))
+            _lib.check(entry(*gargs, A, stage_w, lo, hi, offa(st_means), _stream()), name)
+            return
         entry, name = ((lib.etm_rollout_trxl_group_gaussian, "etm_rollout_trxl_group_gaussian") if group
                        else (lib.etm_rollout_trxl_gaussian, "etm_rollout_trxl_gaussian"))
         _lib.check(entry(*gargs, A, stage_w, lo, hi, _stream()), name)
@@ -2159,7 +2197,7 @@ class _HeadsLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn, unit_grad,
-                sizes=None, log_std=None, action_mask=None):
+                sizes=None, log_std=None, action_mask=None, old_mean=None, old_log_std=None):
         lib = _lib.load()
         _need_dev(h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3)
         h = _f32c(h, "h")
@@ -2168,17 +2206,35 @@ class _HeadsLossFn(torch.autograd.Function):
         pre_p, pre_v = h.mm(wlp.t()), h.mm(wlv.t())
         gm_p, gm_v = torch.empty_like(pre_p), torch.empty_like(pre_v)
         gauss = log_std is not None
-        row = lib.etm_heads_loss_gaussian_row_floats(hid, A) if gauss else lib.etm_heads_loss_row_floats(hid, A)
+        kl = old_mean is not None           # Box with the exact KL statistic: the row carries the KL sum behind d log_std
+        if kl:
+            row, nbytes = lib.etm_heads_loss_gaussian_kl_row_floats(hid, A), lib.etm_heads_loss_gaussian_kl_workspace_bytes(N, hid, A)
+        elif gauss:
+            row, nbytes = lib.etm_heads_loss_gaussian_row_floats(hid, A), lib.etm_heads_loss_gaussian_workspace_bytes(N, hid, A)
+        else:
+            row, nbytes = lib.etm_heads_loss_row_floats(hid, A), lib.etm_heads_loss_workspace_bytes(N, hid, A)
         sums = torch.empty(row, dtype=torch.float32, device=dev)
         out8 = torch.empty(8, dtype=torch.float32, device=dev)
-        nbytes = lib.etm_heads_loss_gaussian_workspace_bytes(N, hid, A) if gauss else lib.etm_heads_loss_workspace_bytes(N, hid, A)
         ws = workspace(nbytes, dev, "heads_loss")
         actions, old_logp = actions.contiguous(), old_logp.contiguous()
         B = actions.shape[1] if actions.dim() == 2 else 1
         common = (_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv), _ptr(actions), B,
                   _ptr(old_logp), B, _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
                   float(vf_coef), float(beta))
-        if gauss:
+        if kl:
+            # Box with the exact KL: old_mean [N, A] the rollout's means (rows of any stride), old_log_std [A] its log sigma
+            _need_dev(log_std, old_mean, old_log_std)
+            if (old_mean.dtype != torch.float32 or old_mean.dim() != 2 or tuple(old_mean.shape) != (N, A) or old_mean.stride(1) != 1
+                    or old_log_std.dtype != torch.float32 or old_log_std.numel() != A or not old_log_std.is_contiguous()):
+                raise ValueError(f"heads_ppo_loss_gaussian: old_mean must be float32 [{N}, {A}] with contiguous rows and old_log_std "
+                                 f"float32 [{A}], got {tuple(old_mean.shape)} {old_mean.dtype} / {tuple(old_log_std.shape)} {old_log_std.dtype}")
+            rc = lib.etm_heads_loss_gaussian_kl(_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv),
+                                                _ptr(_f32c(actions, "actions")), A, _ptr(_f32c(log_std, "log_std")), _ptr(old_logp), 1,
+                                                _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
+                                                float(vf_coef), float(beta), 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
+                                                _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, A, old_mean.data_ptr(),
+                                                old_mean.stride(0) if N > 1 else A, old_log_std.data_ptr(), _stream())
+        elif gauss:
             # Box: wb / bb the mean head, actions [N, A] the stored raw float actions, old_logp [N] (or [N, 1]) the joint log-probs
             _need_dev(log_std)
             rc = lib.etm_heads_loss_gaussian(_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv),
@@ -2217,7 +2273,7 @@ class _HeadsLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_stats):
         if g_loss is None:
-            return (None,) * 22
+            return (None,) * 24
         h, wlp, wlv, gm_p, gm_v, sums = ctx.saved_tensors
         hid, A = ctx.dims
         unit = ctx.unit                 # the caller promises loss.backward() on the returned loss itself: g_loss == 1, nothing to scale
@@ -2236,7 +2292,7 @@ class _HeadsLossFn(torch.autograd.Function):
         o = (3 + A) * hid
         return (dh, dwlp, s[:hid], dwlv, s[hid:2 * hid], s[3 * hid:o].view(A, hid), s[o:o + A], s[2 * hid:3 * hid].view(1, hid),
                 s[o + A:o + A + 1], None, None, None, None, None, None, None, None, None, None, None,
-                s[o + A + 6:o + 2 * A + 6] if ctx.gauss else None, None)
+                s[o + A + 6:o + 2 * A + 6] if ctx.gauss else None, None, None, None)
 
 
 def _branch_list(branch):
@@ -2263,10 +2319,15 @@ def heads_loss_supported_gaussian(h, lin_policy, mean_head):
 
 
 def heads_ppo_loss_gaussian(h, lin_policy, lin_value, mean_head, log_std, value_head, actions, old_logp, adv, old_value, clip, vf_coef, beta,
-                            stats3=None, dyn=None, unit_grad=False):
+                            stats3=None, dyn=None, unit_grad=False, old_mean=None, old_log_std=None):
     """``heads_ppo_loss`` for a Box policy (diagonal Gaussian, state-independent ``log_std`` [A]): ``mean_head`` gives the means,
     ``actions`` [N, A] are the stored raw float actions, ``old_logp`` [N] or [N, 1] their joint log-probs.  One ratio per sample;
-    the gradients reach ``log_std`` too (etm_heads_loss_gaussian)."""
+    the gradients reach ``log_std`` too (etm_heads_loss_gaussian).
+    ``old_mean`` [N, A] / ``old_log_std`` [A] (optional, together): the means and log sigma of the policy that drew the samples;
+    stats[4] is then the exact KL(old || new) of the two Gaussians instead of the k3 sample estimate, in the same launch and with
+    every other output unchanged in its bits (etm_heads_loss_gaussian_kl); None = exactly the call without."""
+    if (old_mean is None) != (old_log_std is None):
+        raise ValueError("heads_ppo_loss_gaussian: old_mean and old_log_std come together (the exact KL needs both)")
     if stats3 is None:
         stats3 = adv_stats(adv)
     if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
@@ -2276,7 +2337,7 @@ def heads_ppo_loss_gaussian(h, lin_policy, lin_value, mean_head, log_std, value_
         raise ValueError(f"heads_ppo_loss_gaussian: actions must be float [N, {A}]")
     loss, st = _HeadsLossFn.apply(h, lin_policy.weight, lin_policy.bias, lin_value.weight, lin_value.bias, mean_head.weight, mean_head.bias,
                                   value_head.weight, value_head.bias, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn,
-                                  unit_grad, None, log_std)
+                                  unit_grad, None, log_std, None, old_mean, old_log_std)
     return loss, st[:6]
 
 

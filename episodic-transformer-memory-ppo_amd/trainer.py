@@ -50,7 +50,8 @@ from etm import ops
 from etm.ops import WindowSpec
 from etm.optim import AdaptiveLr, FlatAdamW, KlGate
 from model import ActorCriticModel, IndexedObservations
-from utils import adaptive_lr_section, normalization_section, polynomial_decay, process_episode_info, target_kl_rows, target_kl_section
+from utils import (adaptive_lr_section, kl_estimator_section, normalization_section, polynomial_decay, process_episode_info, target_kl_rows,
+                   target_kl_section)
 from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
 from checkpoint import check_checkpoint_config, segment_first_worker_id
 from trainer_parts import _CheckpointResume, _DataParallelStep, _NativeRolloutDrive, _RunOutputs
@@ -259,6 +260,26 @@ def check_adaptive_lr_config(config, world: int = 1):
     return out
 
 
+def check_kl_estimator_config(config, box: bool = False, world: int = 1):
+    """The optional key ``kl_estimator`` (utils.kl_estimator_section) -> "k3" (absent: nothing is allocated, no launch is added or
+    exchanged) or "analytic": the statistic ``kl`` -- what ``other/kl`` shows and what ``target_kl`` and ``adaptive_lr`` decide on -- is
+    the exact KL of the rollout's and the current Gaussian of a Box policy instead of the sample estimate.  Refused, each before
+    anything is built and each with what to do instead: a value other than ``k3`` / ``analytic``; ``analytic`` without a Box policy
+    (``box``: a categorical policy's exact KL would need every old logit stored); ``analytic`` in a data-parallel run (``world`` > 1),
+    as for the other KL keys."""
+    kind = kl_estimator_section(config)
+    if kind != "analytic":
+        return kind
+    if not box:
+        raise ValueError("kl_estimator: analytic without a Box (continuous) action space: the exact KL is built for diagonal Gaussian "
+                         "policies only (a categorical policy's would need every old logit stored); categorical policies keep k3: "
+                         "remove the key")
+    if world > 1:
+        raise ValueError("kl_estimator: analytic in a data-parallel run: every rank would see the KL of its own minibatch (agreeing on one "
+                         "KL over the ranks is not built); remove the key, or train on one device")
+    return kind
+
+
 def time_major(table, src):
     """The host table ``src`` [W, S(, B)] in the layout and type of the fixed-address device table ``table`` [S, W(, B)]."""
     x = torch.as_tensor(np.asarray(src), dtype=table.dtype)
@@ -302,6 +323,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         check_checkpoint_config(config, 1 if dp is None else int(getattr(dp, "world", 1)), resume=resume is not None)
         kl_cfg = check_target_kl_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         adapt_cfg = check_adaptive_lr_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
+        # (a supplied environment says what the policy is once it is looked at, below; else the config does, before anything is built)
+        check_kl_estimator_config(config, env is not None or check_box_policy(config) is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
         # training state that a checkpoint carries over (trainer_parts._CheckpointResume): completed updates, the training segment (the
         # number of resumes so far; its environments' worker ids start at segment_first_worker_id), the last episodes' infos
         self.update_index, self.segment, self._episode_infos = 0, 0, deque(maxlen=100)
@@ -395,6 +418,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # action_masks: the environment's front-end, the width of the policy head and the kind of policy are known now
         self._masked = check_action_mask_config(config, self.env, self.action_space_shape, self.box is not None)
         self.last_valid_action_share = None       # mean share of allowed actions in the last rollout's words (None without the key)
+        # kl_estimator: the kind of policy is known now.  "analytic": the four Gaussian sampling sites stage the means, the buffer
+        # carries them and a snapshot of the log-std, the Gaussian heads + loss kernel reduces the exact KL into stats[4]
+        self._kl_analytic = check_kl_estimator_config(config, self.box is not None, 1 if dp is None else int(getattr(dp, "world", 1))) == "analytic"
 
         if config.get("tunable_gemm", os.environ.get("ETM_TUNABLE_GEMM", "1") != "0"):
             # let PyTorch pick the fastest hipBLASLt / rocBLAS solution per GEMM shape (the small [N, D] x [D, D] products around
@@ -425,6 +451,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if self.dp is not None:
             self.dp.broadcast_parameters(self.model)
         self.params = [p for _, p in self.model.arena_parameters()]      # (a Box policy's policy_log_std last)
+        if self._kl_analytic:
+            self.buffer.log_std_source = self.model.policy_log_std       # (prepare_batch_dict snapshots it once per update)
         # The optimisation step of one minibatch (gather, forward, loss, backward, clipping, AdamW) is captured in a HIP graph
         # after two eager warm-up steps and replayed for every other minibatch of the run: the host then issues one launch
         # per minibatch instead of ~280.  lr / clip range / entropy coefficient live on the device so that their schedules
@@ -514,6 +542,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             "log_probs": torch.zeros((S, W, 1 if box else B), dtype=torch.float32, device=device),      # (Box: one joint log-prob)
             "values": torch.zeros((S, W), dtype=torch.float32, device=device),
         }
+        if self._kl_analytic:       # (the means next to the actions; _finish_rollout moves every staging table into the buffer's field)
+            self._stage["means"] = torch.zeros((S, W, B), dtype=torch.float32, device=device)
         self._mask_t = torch.zeros((W, L), dtype=torch.bool, device=device)
         self._win_t = torch.zeros((W, L), dtype=torch.int64, device=device)
         self._act_dev = torch.zeros((W, B), dtype=torch.float32 if box else torch.int64, device=device)
@@ -1040,6 +1070,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # Box: the Gaussian forms of the sampling kernels -- normals in place of the uniforms, float forced / action tables
         box = None if self.box is None else (m.policy_log_std, self.box.low, self.box.high)
         draws = self._uniforms if box is None else self._normals
+        means = {"st_means": st["means"]} if self._kl_analytic else {}      # (kl_estimator: analytic; else exactly the calls of ever)
         mask_t, win_t = g.mask_t, g.win_t
         # streamed + pipelined mode: the (step, slot) block is read from pinned host memory (see rollout_plan.plan_rollout)
         ss_src = g.ss_pin if stream_obs and g.stream is not None else g.ss_dev
@@ -1061,7 +1092,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                              g.rf_scratch, host_actions=g.act_pin, host_flag=flag_pin, w_off=g.lo,
                              tail=tail, h_bias=h_bias, branches=branches, box=box,
                              window=(ss_src, self._mask_table, self._index_table, st["memory_mask"], st["memory_indices"],
-                                     g.ss_latch, g.t_row, self._kv_init), action_mask=am_src)
+                                     g.ss_latch, g.t_row, self._kv_init), action_mask=am_src, **means)
             return g.item
         # window lookup + staging; the same launch records the staging row of this step for the tail (t_dev is incremented by
         # the sampling kernel) and resets the K/V cache of workers at episode step 0 (they start from the projection of an
@@ -1079,7 +1110,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             if box is not None:
                 ops.rollout_policy_gaussian(h2, policy_head, m.value, box[0], draws, self._forced_tab, g.t_dev, g.act_dev,
                                             st["actions"], st["log_probs"], st["values"], low=box[1], high=box[2],
-                                            host_actions=g.act_pin, host_flag=flag_pin, h_bias=m._b_heads, w_off=g.lo)
+                                            host_actions=g.act_pin, host_flag=flag_pin, h_bias=m._b_heads, w_off=g.lo, **means)
             else:
                 ops.rollout_policy(h2, policy_head, m.value, self._uniforms, self._forced_tab, g.t_dev,
                                    g.act_dev, st["actions"], st["log_probs"], st["values"],
@@ -1099,7 +1130,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             lg = logits[0] if len(logits) == 1 else torch.cat(logits, dim=1)
             if box is not None:       # (the means; host actions clipped to the bounds)
                 ops.rollout_sample_gaussian(lg, value, box[0], draws, self._forced_tab, g.t_dev, g.act_dev, st["actions"], st["log_probs"],
-                                            st["values"], low=box[1], high=box[2])
+                                            st["values"], low=box[1], high=box[2], **means)
             else:
                 ops.rollout_sample(lg, value, self._uniforms, self._forced_tab, g.t_dev, g.act_dev,
                                    st["actions"], st["log_probs"], st["values"], branches=branches, action_mask=am_src)
@@ -1434,9 +1465,11 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             h, _ = m.forward_state(obs, spec)
             if not ops.heads_loss_supported_gaussian(h, m.lin_policy, m.policy_branches[0]):
                 raise RuntimeError("Box policy: the minibatch is outside the fused Gaussian heads + loss kernel")
+            # kl_estimator: analytic: the minibatch's old means and the update's log-std snapshot; stats[4] is then the exact KL
+            old = dict(old_mean=mb["means"], old_log_std=self.buffer.old_log_std) if self._kl_analytic else {}
             return ops.heads_ppo_loss_gaussian(h, m.lin_policy, m.lin_value, m.policy_branches[0], m.policy_log_std, m.value, mb["actions"],
                                                mb["log_probs"], mb["advantages"], mb["values"], clip_range, self.config["value_loss_coefficient"],
-                                               beta, stats3, dyn=dyn, unit_grad=True)
+                                               beta, stats3, dyn=dyn, unit_grad=True, **old)
         if self.config.get("fused_heads_loss", True):
             h, _ = m.forward_state(obs, spec)
             branch = m.policy_branches[0] if len(m.policy_branches) == 1 else list(m.policy_branches)

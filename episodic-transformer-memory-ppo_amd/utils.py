@@ -1,7 +1,9 @@
 """Helpers with the upstream names (utils.py): create_env, polynomial_decay, batched_index_select,
 process_episode_info, Module; normalization_section reads this build's two normalisation keys, target_kl_section its KL early
 stop, target_kl_rows says which rows of an update's result tables a stopped update returns; adaptive_lr_section reads the
-KL-adaptive learning rate and adaptive_lr_step is its rule, the one host definition of what the norm kernel decides."""
+KL-adaptive learning rate and adaptive_lr_step is its rule, the one host definition of what the norm kernel decides;
+kl_estimator_section reads which KL both rules see and gaussian_kl is the exact KL of a Box policy's Gaussians, the one host
+definition of what the Gaussian heads + loss kernel reduces."""
 import numpy as np
 import torch
 from torch import nn
@@ -198,6 +200,38 @@ def adaptive_lr_step(lr32, kl32, rule):
     if kl < np.float32(rule["kl_low"]) and kl > np.float32(0):
         return np.minimum(hi, np.float32(lr * factor)), 1
     return lr, 0
+
+
+KL_ESTIMATORS = ("k3", "analytic")
+
+
+def kl_estimator_section(config: dict) -> str:
+    """The optional key ``kl_estimator`` -> "k3" (absent: the sample estimate mean((ratio - 1) - log ratio) of every policy kind) or
+    "analytic" (the exact KL of the two diagonal Gaussians of a Box policy, ``gaussian_kl``).  Any other value is refused."""
+    value = config.get("kl_estimator", "k3")
+    if not isinstance(value, str) or value not in KL_ESTIMATORS:
+        raise ValueError(f"kl_estimator must be one of {list(KL_ESTIMATORS)}, got {value!r}; write `k3` (or remove the key) for the sample "
+                         "estimate, `analytic` for the exact KL of a Box policy's Gaussians")
+    return value
+
+
+def gaussian_kl(old_mean, old_log_std, mean, log_std, dtype=np.float64):
+    """KL(old || new) of two diagonal Gaussians, the mean over the N samples of the sum over the A dimensions, in numpy ``dtype`` (the
+    one host definition of what heads_loss_gaussian_kl_kernel reduces; csrc/heads_loss.hip): ``old_mean`` / ``mean`` [N, A],
+    ``old_log_std`` / ``log_std`` [A].
+        KL_n = sum_a [(expm1(2 d_a) / 2 - d_a) + ((old_mean_na - mean_na) / sigma_a)^2 / 2],  d_a = old_log_std_a - log_std_a
+    -- rsl_rl's log(sigma / sigma_old) + (sigma_old^2 + (mu_old - mu)^2) / (2 sigma^2) - 1/2 written so that nothing cancels (and
+    without its 1e-5): equal policies give exactly 0, equal log-stds exactly mean_n sum_a ((mu_old - mu) / sigma)^2 / 2."""
+    dt = np.dtype(dtype).type
+    mo, mu = np.asarray(old_mean, dtype=dt), np.asarray(mean, dtype=dt)
+    lo, ls = np.asarray(old_log_std, dtype=dt).reshape(-1), np.asarray(log_std, dtype=dt).reshape(-1)
+    if mo.ndim != 2 or mo.shape != mu.shape or lo.shape != (mo.shape[1],) or ls.shape != lo.shape:
+        raise ValueError(f"gaussian_kl: means [N, A] and log-stds [A] expected, got {mo.shape}, {lo.shape}, {mu.shape}, {ls.shape}")
+    d = lo - ls
+    const = (dt(0.5) * np.expm1(dt(2) * d) - d).sum(dtype=dt)
+    q = (mo - mu) / np.exp(ls)
+    per_sample = const + (dt(0.5) * q * q).sum(axis=1, dtype=dt)
+    return dt(per_sample.sum(dtype=dt) / dt(mo.shape[0]))
 
 
 class Module(nn.Module):

@@ -38,7 +38,8 @@ extern "C" {
 /* ABI version of this header (bumped on any signature change, and when the meaning of an argument widens: 52 = the greedy
  * sentinel of the `uniforms` tables; 53 = + etm_gae_truncated; 54 = + the running-normalisation entries; 55 = + etm_grouped_dw_tile_map;
  * 56 = + etm_arena_digest; 57 = + the gated optimiser pair; 58 = + the *_masked entries of invalid-action masking;
- * 59 = + etm_grad_sqnorm_adaptive; 60 = + etm_block_row_groups). */
+ * 59 = + etm_grad_sqnorm_adaptive; 60 = + etm_block_row_groups; 61 = + the *_gaussian_means sampling entries and
+ * etm_heads_loss_gaussian_kl of the exact Gaussian KL). */
 int etm_abi_version(void);
 
 /* Human-readable name for a negative ETM_E* code or a hipError_t. Static storage. */
@@ -255,6 +256,13 @@ int etm_rollout_sample_branched_masked(const float *logits, const float *value, 
 int etm_rollout_sample_gaussian(const float *mean, const float *value, const float *log_std, const float *normals, const float *forced,
                                 int64_t *t_dev, float *actions, float *st_actions, float *st_logp, float *st_values, const float *low,
                                 const float *high, int W, int A, void *stream);
+/* The exact Gaussian KL (ABI 61; `kl_estimator: analytic`): the *_gaussian_means form of each of the four Gaussian sampling entries
+ * takes its twin's arguments and st_means before the stream -- [S, W, A] (or [S, stage_W, A] at this group's first worker) next to
+ * st_actions -- and stores the policy's mean of every dimension there as well, forced action or not; every other output is the twin's,
+ * bit for bit.  ETM_EINVAL: NULL or 4-byte-misaligned st_means. */
+int etm_rollout_sample_gaussian_means(const float *mean, const float *value, const float *log_std, const float *normals, const float *forced,
+                                      int64_t *t_dev, float *actions, float *st_actions, float *st_logp, float *st_values, const float *low,
+                                      const float *high, int W, int A, float *st_means, void *stream);
 int etm_add_layernorm(const float *a, const float *a_bias, int relu, const float *b, const float *gamma, const float *beta, float eps,
                       float *out, int N, int D, void *stream);
 /* Elementwise parts of the GTrXL GRU gate on the rollout path (transformer.py:287-298), around concatenated library GEMMs
@@ -388,6 +396,23 @@ int etm_heads_loss_gaussian(const float *pre_p, const float *pre_v, const float 
                             double clip, float vf_coef, float beta, float pol_scale, float ent_scale, float val_scale,
                             const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8, float *logits, float *value,
                             void *workspace, int64_t workspace_bytes, int N, int hid, int A, void *stream);
+/* The exact Gaussian KL (ABI 61): etm_heads_loss_gaussian with old_mean [N, A] (row stride old_mean_stride >= A floats), the means of
+ * the policy that drew the samples (the *_gaussian_means sampling entries), and old_log_std [A], a snapshot of its log sigma.  The
+ * same launch also reduces KL(old || new) = mean_n sum_a [(expm1(2 d_a) / 2 - d_a) + ((old_mean_na - mean_na) / sigma_a)^2 / 2],
+ * d_a = old_log_std_a - log_std_a (nothing cancels: equal policies give exactly 0): out8[4] = that KL, out8[6] = the k3 sample
+ * estimate that etm_heads_loss_gaussian puts into out8[4].  A statistic only: the loss, gm_p, gm_v, out8[0..3], out8[5] and the
+ * etm_heads_loss_gaussian row are that entry's bit for bit; sums [etm_heads_loss_gaussian_kl_row_floats =
+ * etm_heads_loss_gaussian_row_floats + 1] carries the raw KL sum as its last element.  Shapes: etm_heads_loss_supported_gaussian.
+ * ETM_EINVAL: NULL or 4-byte-misaligned old_mean / old_log_std, old_mean_stride < A. */
+int etm_heads_loss_gaussian_kl_row_floats(int hid, int A);
+int64_t etm_heads_loss_gaussian_kl_workspace_bytes(int N, int hid, int A);
+int etm_heads_loss_gaussian_kl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                               const float *bb, const float *wv, const float *bv, const float *xact, int64_t action_stride,
+                               const float *log_std, const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
+                               const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                               float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
+                               float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid, int A,
+                               const float *old_mean, int64_t old_mean_stride, const float *old_log_std, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Weight gradients of the dense layers of one optimisation step as ONE grouped launch: replaces the `dW = dy^T x` products that
@@ -530,6 +555,12 @@ int etm_rollout_policy_gaussian(const float *h, const float *h_bias, const float
                                 const float *log_std, const float *normals, const float *forced, int64_t *t_dev, float *actions,
                                 float *st_actions, float *st_logp, float *st_values, float *host_actions, int64_t *host_flag,
                                 int32_t *sync_counter, const float *low, const float *high, int W, int A, int hid, int stage_W, void *stream);
+/* (ABI 61) with the means staged, see etm_rollout_sample_gaussian_means */
+int etm_rollout_policy_gaussian_means(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv, const float *bv,
+                                      const float *log_std, const float *normals, const float *forced, int64_t *t_dev, float *actions,
+                                      float *st_actions, float *st_logp, float *st_values, float *host_actions, int64_t *host_flag,
+                                      int32_t *sync_counter, const float *low, const float *high, int W, int A, int hid, int stage_W,
+                                      float *st_means, void *stream);
 
 /* The transformer, the hidden / output heads and the sampling of one rollout step of a worker group as ONE launch (post-LN
  * blocks without gates; trainer.py:163-186 -> model.py:96-112 -> transformer.py:222-253), csrc/rollout_fused.hip: a TEAM of
@@ -695,6 +726,31 @@ int etm_rollout_trxl_group_gaussian(const float *h_in, const float *wemb_t, cons
                                     uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,
                                     const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A,
                                     int stage_W, const float *low, const float *high, void *stream);
+/* (ABI 61) with the means staged, see etm_rollout_sample_gaussian_means; the shapes of the predicates above */
+int etm_rollout_trxl_gaussian_means(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb,
+                                    float *kv, int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask,
+                                    float *items, const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv,
+                                    const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev,
+                                    float *actions, float *st_actions, float *st_logp, float *st_values, float *host_actions,
+                                    int64_t *host_flag, int32_t *sync_counter, float ln_eps, void *scratch, int64_t scratch_bytes,
+                                    const float *wkv, const float *pos, const int64_t *step_l, const int64_t *slot_l, float *bank,
+                                    int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
+                                    int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table,
+                                    uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,
+                                    const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A,
+                                    int stage_W, const float *low, const float *high, float *st_means, void *stream);
+int etm_rollout_trxl_group_gaussian_means(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb,
+                                    float *kv, int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask,
+                                    float *items, const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv,
+                                    const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev,
+                                    float *actions, float *st_actions, float *st_logp, float *st_values, float *host_actions,
+                                    int64_t *host_flag, int32_t *sync_counter, float ln_eps, void *scratch, int64_t scratch_bytes,
+                                    const float *wkv, const float *pos, const int64_t *step_l, const int64_t *slot_l, float *bank,
+                                    int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
+                                    int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table,
+                                    uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,
+                                    const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A,
+                                    int stage_W, const float *low, const float *high, float *st_means, void *stream);
 /* Window pass (etm_window_*): 0 = load and multiply the window rows of fully masked waves too (A/B diagnostics; the results are
  * bit-identical either way); default 1 = skip them.  Process-wide, read at launch. */
 int etm_window_set_skip_masked(int on);
