@@ -27,12 +27,15 @@ the storage redesigned for the MI355X path:
 * ``kl_estimator: analytic`` (absent upstream; Box policies): ``means`` [W, S, A], the rollout's Gaussian means, a member of
   ``samples_flat``, and ``old_log_std`` [A], the log-std that drew them, copied once per update by ``prepare_batch_dict``.  They live
   for one rollout (nothing of them is in a checkpoint).  Without the key neither exists.
+* ``exact_kl: true`` (absent upstream): on a Box policy exactly the two fields above; on a Discrete / MultiDiscrete policy (masked or
+  not) ``old_logps`` [W, S, sum A_b], the rollout's log-probs of every column of every branch (-inf where a column was masked out), a
+  member of ``samples_flat``.  The rows live for one rollout (nothing of them is in a checkpoint).  Without the key it does not exist.
 """
 import numpy as np
 import torch
 
 from etm import ops
-from utils import kl_estimator_section, normalization_section
+from utils import exact_kl_section, kl_estimator_section, normalization_section
 
 
 class Buffer:
@@ -84,11 +87,17 @@ class Buffer:
         # parameter moves during the update --, taken by ``prepare_batch_dict`` from ``log_std_source`` (the trainer sets it: the
         # model's policy_log_std); None without the key
         self.means = self.old_log_std = self.log_std_source = None
-        if kl_estimator_section(config) == "analytic":
+        exact = exact_kl_section(config)      # (exact_kl: true on a Box policy is exactly kl_estimator: analytic)
+        if kl_estimator_section(config) == "analytic" or (exact and continuous):
             if not continuous:
                 raise ValueError("kl_estimator: analytic needs a Box (continuous) policy; remove the key")
             self.means = torch.zeros((W, S, B), dtype=torch.float32, device=dev)
             self.old_log_std = torch.zeros(B, dtype=torch.float32, device=dev)
+        # the exact categorical KL (exact_kl: true, Discrete / MultiDiscrete policies, masked or not): the rollout's log-probs of every
+        # column of every branch [W, S, sum A_b] next to ``actions``, a member of ``samples_flat``; None without the key
+        self.old_logps = None
+        if exact and not continuous:
+            self.old_logps = torch.zeros((W, S, sum(int(a) for a in action_space_shape)), dtype=torch.float32, device=dev)
 
         # return-based reward scaling (normalize_rewards): None without the key
         self.return_norm = normalization_section(config, "normalize_rewards")
@@ -198,6 +207,8 @@ class Buffer:
             samples["action_masks"] = self.action_masks
         if self.means is not None:
             samples["means"] = self.means
+        if self.old_logps is not None:
+            samples["old_logps"] = self.old_logps
         self.samples_flat = {k: v.reshape(v.shape[0] * v.shape[1], *v.shape[2:]) for k, v in samples.items()}
 
     def mini_batch_generator(self, indices: torch.Tensor = None, materialize: bool = False):

@@ -144,8 +144,13 @@ __device__ __forceinline__ int etm_branch_mode(const float *lg, int A, float mx,
 // arithmetic of every sampling site (same operations in the same order).
 // MK: the branch's bits m of the step's mask word (bit j = action j of THIS branch); a forced action is taken as it is (the host
 // checks it against the stored words after the rollout).
-template <bool MK = false>
-__device__ __forceinline__ int etm_sample_branch(const float *lg, int A, float u, int forced, float *logp, unsigned long long m = 0) {
+// LP (the exact KL of the update needs the distribution that drew the sample, taken, greedy or forced action alike): logps [A], when
+// given, receives every column's log-prob lg[j] - lse (-inf for a masked-out column; at the taken action the returned log-prob's
+// expression with the same lse, so its bits); lse_out, when given, the branch's lse for a caller that stores the columns itself,
+// behind its hand-over.  LP = false reads neither.
+template <bool MK = false, bool LP = false>
+__device__ __forceinline__ int etm_sample_branch(const float *lg, int A, float u, int forced, float *logp, unsigned long long m = 0,
+                                                 float *logps = nullptr, float *lse_out = nullptr) {
   float mx = -INFINITY;
   for (int j = 0; j < A; ++j) mx = fmaxf(mx, etm_masked_logit<MK>(lg, j, m));
   float se = 0.f;
@@ -154,16 +159,25 @@ __device__ __forceinline__ int etm_sample_branch(const float *lg, int A, float u
   int a = forced;
   if (a < 0) a = u < 0.f ? etm_branch_mode<MK>(lg, A, mx, m) : etm_sample_categorical<MK>(lg, A, lse, u, m);
   *logp = lg[a] - lse;
+  if constexpr (LP) {
+    if (logps)
+      for (int j = 0; j < A; ++j) logps[j] = etm_masked_logit<MK>(lg, j, m) - lse;
+    if (lse_out) *lse_out = lse;
+  }
   return a;
 }
 
 // Every branch of worker w at step t: row = t * stage_W + w indexes the time-major [S, stage_W, B] uniform / forced / staging
 // tables (B = 1: [S, stage_W]); actions and host_actions are [W, B].  The value (logit column sum(sizes)) is staged by the caller.
 // MK: am points to THIS worker's mask word (any address space); MK = false never reads am.
-template <bool MK = false>
+// LP: st_logps [S, stage_W, total_a] next to st_actions receives the row's log-probs of every column of every branch (MK or not);
+// or, for a caller that stores the columns itself behind its hand-over (st_logps == NULL), lse_out [B] receives the branches' lse.
+// LP = false reads neither.
+template <bool MK = false, bool LP = false>
 __device__ __forceinline__ void etm_sample_branches(const float *lg, const EtmBranches &br, long long row, int w, const float *uniforms,
                                                     const long long *forced, long long *actions, long long *host_actions,
-                                                    long long *st_actions, float *st_logp, const long long *am = nullptr) {
+                                                    long long *st_actions, float *st_logp, const long long *am = nullptr,
+                                                    float *st_logps = nullptr, int total_a = 0, float *lse_out = nullptr) {
   const int B = br.n;
   unsigned long long word = 0ull;
   if constexpr (MK) word = (unsigned long long)*am;
@@ -174,7 +188,10 @@ __device__ __forceinline__ void etm_sample_branches(const float *lg, const EtmBr
     float lp;
     const int fc = forced ? (int)forced[i] : -1;
     int a;
-    if constexpr (MK) a = etm_sample_branch<true>(lg + off, Ab, uniforms[i], fc, &lp, word >> off);
+    if constexpr (LP)
+      a = etm_sample_branch<MK, true>(lg + off, Ab, uniforms[i], fc, &lp, word >> off, st_logps ? st_logps + row * total_a + off : nullptr,
+                                      lse_out ? lse_out + b : nullptr);
+    else if constexpr (MK) a = etm_sample_branch<true>(lg + off, Ab, uniforms[i], fc, &lp, word >> off);
     else a = etm_sample_branch(lg + off, Ab, uniforms[i], fc, &lp);
     actions[(long long)w * B + b] = a;
     if (host_actions) host_actions[(long long)w * B + b] = a;
@@ -182,6 +199,16 @@ __device__ __forceinline__ void etm_sample_branches(const float *lg, const EtmBr
     st_logp[i] = lp;
     off += Ab;
   }
+}
+
+// One column's term of the exact categorical KL(old || new) (utils.categorical_kl is the host definition; the loss kernels sum it over
+// a branch's valid columns): lo / l the column's old and current log-prob, pj = exp(l), d = lo - l.
+// p_old (expm1(-d) + d) = p_old (lo - l) + (p - p_old): never negative beyond the rounding of the one expm1 + d, exactly 0 at d = 0,
+// and no term of size 1 cancels (the added p - p_old sums to zero over a branch).  Below d = -60 (p_old -> 0, lo = -inf included) the
+// limit p: the dropped part is under e^-60 |d|, and the case keeps inf * denormal out of the sum.
+__device__ __forceinline__ float etm_categorical_kl_term(float lo, float l, float pj) {
+  const float d = lo - l;
+  return d >= -60.f ? expf(lo) * (expm1f(-d) + d) : pj;
 }
 
 // Box (continuous) action spaces: a diagonal Gaussian policy over A <= ETM_MAX_BOX dimensions, mean = the A policy-head outputs,

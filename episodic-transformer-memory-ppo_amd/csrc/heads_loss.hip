@@ -53,6 +53,10 @@ struct HlParams {
   // samples, old_log_std [A] its log sigma
   const float *old_mean, *old_log_std;
   long long old_mean_stride;
+  // KL kernels (categorical, the exact KL statistic): old_logps [N, A] (row stride old_logps_stride floats) every column's log-prob
+  // under the policy that drew the samples (-inf at a column that was masked out)
+  const float *old_logps;
+  long long old_logps_stride;
 };
 
 // BR: MultiDiscrete branches; GS: diagonal Gaussian (Box; the row gains d log_std [A] behind the five statistic sums)
@@ -63,6 +67,9 @@ struct HlParams {
 //   KL_n = sum_a [(expm1(2 d_a) / 2 - d_a) + ((mu_old[n, a] - mu[n, a]) / sigma_a)^2 / 2],  d_a = log sigma_old_a - log sigma_a,
 // written so that nothing cancels (equal policies give exactly 0).  A statistic only: no term of the loss, no gradient; the sum sits
 // behind d log_std at the very end of the row, so every other row offset keeps its value.
+// KL (categorical, BR and MK or not): the sixth running sum is the exact KL of the two categoricals, per branch the sum over its VALID
+// columns of etm_categorical_kl_term(old_logps[n, j], l_j, p_j), formed where l_j and p_j already are; it sits behind the five statistic
+// sums at the very end of the row.  Again a statistic only.
 template <int HC, bool BR, bool GS, bool MK, bool KL = false>
 __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
   HlParams p = p0;
@@ -97,9 +104,9 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
       if (a < A) ent_gs += (0.5f + 0.918938533204672742f) + lsr[a];
     }
   }
-  // KL: the part of KL_n that does not depend on the sample, and the sixth sum
+  // KL: the part of KL_n that does not depend on the sample (GS), and the sixth sum
   float kl_ls = 0.f, acc_kl = 0.f;
-  if constexpr (KL) {
+  if constexpr (KL && GS) {
 #pragma unroll
     for (int a = 0; a < HL_MAXA; ++a)
       if (a < A) { const float d = p.old_log_std[a] - lsr[a]; kl_ls += 0.5f * expm1f(2.f * d) - d; }
@@ -250,6 +257,7 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
     }
     const float cpol = -p.pol_scale * g_ratio * ratio;
     const float cent = -p.beta * p.ent_scale;
+    float kl_n = 0.f;
 #pragma unroll
     for (int j = 0; j < HL_MAXA; ++j) {
       dl[j] = 0.f;
@@ -259,8 +267,10 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
         const float d_lp = ((j == act) ? 1.f : 0.f) - pj;
         const float d_ent = -pj * (l + ent);
         dl[j] = cpol * d_lp + cent * d_ent;
+        if constexpr (KL) kl_n += etm_categorical_kl_term(p.old_logps[(long long)n * p.old_logps_stride + j], l, pj);
       }
     }
+    if constexpr (KL) { if (lane == 0) acc_kl += kl_n; }
     } else {
       // MultiDiscrete (ref_algo.ppo_loss): per branch b a log-softmax over its own columns and a ratio; the sample's normalised
       // advantage is repeated over the branches; policy term, KL and clip fraction are summed over (sample, branch) and scaled by
@@ -310,6 +320,7 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
         }
       }
       const float cent = -p.beta * p.ent_scale;
+      float kl_n = 0.f;                                               // (KL: the branches' KLs of this sample, column order)
 #pragma unroll
       for (int j = 0; j < HL_MAXA; ++j) {
         dl[j] = 0.f;
@@ -322,8 +333,10 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
           const float d_lp = (taken ? 1.f : 0.f) - pj;
           const float d_ent = -pj * (l + ent_c[j]);
           dl[j] = cpol_c[j] * d_lp + cent * d_ent;
+          if constexpr (KL) kl_n += etm_categorical_kl_term(p.old_logps[(long long)n * p.old_logps_stride + j], l, pj);
         }
       }
+      if constexpr (KL) { if (lane == 0) acc_kl += kl_n; }
     }
     const float vo = p.old_value[n];
     const float ret = vo + a_raw;
@@ -389,7 +402,7 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
         for (int a = 0; a < HL_MAXA; ++a)
           if (a < A) { if (add) t[A + 6 + a] += s_ls[a]; else t[A + 6 + a] = s_ls[a]; }
       }
-      if constexpr (KL) { if (add) t[A + 6 + A] += acc_kl; else t[A + 6 + A] = acc_kl; }
+      if constexpr (KL) { const int k = A + 6 + (GS ? A : 0); if (add) t[k] += acc_kl; else t[k] = acc_kl; }
     }
   };
   put_row(hl_lds + (long long)wave * row, false);
@@ -405,13 +418,17 @@ template <int HC, bool BR>
 __global__ __launch_bounds__(256) void heads_loss_masked_kernel(const HlParams p0) { heads_loss_body<HC, BR, false, true>(p0); }
 template <int HC>
 __global__ __launch_bounds__(256) void heads_loss_gaussian_kl_kernel(const HlParams p0) { heads_loss_body<HC, false, true, false, true>(p0); }
+template <int HC, bool BR, bool MK>
+__global__ __launch_bounds__(256) void heads_loss_kl_kernel(const HlParams p0) { heads_loss_body<HC, BR, false, MK, true>(p0); }
 
 // sums the workgroup rows and finishes the loss statistics: out = [row sums ... ], out8 (a Gaussian row's d log_std sums, behind the
 // statistics, are summed like every other element).  One workgroup = 64 row elements x 16 row
 // groups: thread (e, g) adds the rows g, g + 16, ... (all requested at once: the sum is a latency chain otherwise), the 16 group
 // sums are added in group order -- a fixed tree, deterministic.
-// KL (the Gaussian row with the KL sum as its last element): out8[4] = that sum * ent_scale (the exact KL), out8[6] = the k3 value.
-template <bool KL>
+// KL = 1 (the Gaussian row with the KL sum as its last element): out8[4] = that sum * ent_scale (the exact KL), out8[6] = the k3 value.
+// KL = 2 (the categorical row with the KL sum as its last element, right behind the five statistic sums): out8[4] = that sum *
+// pol_scale -- the mean over samples AND branches, the convention of the k3 value, which goes to out8[6].
+template <int KL>
 __device__ __forceinline__ void heads_reduce_body(const float *__restrict__ partials, int n_wg, int row, int A, int hid, float vf_coef,
                                                   float beta, float pol_scale, float ent_scale, float val_scale,
                                                   const double *__restrict__ dyn, float *__restrict__ out, float *__restrict__ out8) {
@@ -441,7 +458,7 @@ __device__ __forceinline__ void heads_reduce_body(const float *__restrict__ part
   // the five statistic sums (the last five row elements) once more in this workgroup, then out8
   __syncthreads();
   const int st0 = (3 + A) * hid + A + 1;
-  if constexpr (KL) sm[g][el] = el < 5 ? group_sum(st0 + el) : el == 5 ? group_sum(st0 + 5 + A) : 0.f;
+  if constexpr (KL != 0) sm[g][el] = el < 5 ? group_sum(st0 + el) : el == 5 ? group_sum(st0 + 5 + (KL == 1 ? A : 0)) : 0.f;
   else sm[g][el] = el < 5 ? group_sum(st0 + el) : 0.f;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -454,10 +471,10 @@ __device__ __forceinline__ void heads_reduce_body(const float *__restrict__ part
     if (dyn) beta = (float)dyn[1];
     const float pol = acc[0] * pol_scale, val = acc[1] * val_scale, ent = acc[2] * ent_scale;
     out8[0] = pol; out8[1] = val; out8[2] = -(pol - vf_coef * val + beta * ent); out8[3] = ent;
-    if constexpr (KL) {
+    if constexpr (KL != 0) {
       float t = 0.f;
       for (int k = 0; k < 16; ++k) t += sm[k][5];
-      out8[4] = t * ent_scale; out8[5] = acc[4] * pol_scale; out8[6] = acc[3] * pol_scale; out8[7] = 0.f;
+      out8[4] = t * (KL == 1 ? ent_scale : pol_scale); out8[5] = acc[4] * pol_scale; out8[6] = acc[3] * pol_scale; out8[7] = 0.f;
     } else {
       out8[4] = acc[3] * pol_scale; out8[5] = acc[4] * pol_scale; out8[6] = 0.f; out8[7] = 0.f;
     }
@@ -466,13 +483,19 @@ __device__ __forceinline__ void heads_reduce_body(const float *__restrict__ part
 __global__ __launch_bounds__(1024) void heads_reduce_kernel(const float *__restrict__ partials, int n_wg, int row, int A, int hid, float vf_coef,
                                                             float beta, float pol_scale, float ent_scale, float val_scale,
                                                             const double *__restrict__ dyn, float *__restrict__ out, float *__restrict__ out8) {
-  heads_reduce_body<false>(partials, n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn, out, out8);
+  heads_reduce_body<0>(partials, n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn, out, out8);
 }
 __global__ __launch_bounds__(1024) void heads_reduce_kl_kernel(const float *__restrict__ partials, int n_wg, int row, int A, int hid,
                                                                float vf_coef, float beta, float pol_scale, float ent_scale, float val_scale,
                                                                const double *__restrict__ dyn, float *__restrict__ out,
                                                                float *__restrict__ out8) {
-  heads_reduce_body<true>(partials, n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn, out, out8);
+  heads_reduce_body<1>(partials, n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn, out, out8);
+}
+__global__ __launch_bounds__(1024) void heads_reduce_categorical_kl_kernel(const float *__restrict__ partials, int n_wg, int row, int A, int hid,
+                                                                           float vf_coef, float beta, float pol_scale, float ent_scale,
+                                                                           float val_scale, const double *__restrict__ dyn,
+                                                                           float *__restrict__ out, float *__restrict__ out8) {
+  heads_reduce_body<2>(partials, n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn, out, out8);
 }
 static_assert(true, "");
 constexpr int HL_SAMPLES_PER_WG = 8;      // two samples per wave: the pass is a latency chain per sample, so many short waves
@@ -483,6 +506,12 @@ extern "C" int etm_heads_loss_row_floats(int hid, int A) { return (3 + A) * hid 
 extern "C" int64_t etm_heads_loss_workspace_bytes(int N, int hid, int A) {
   if (!etm_heads_loss_supported(N, hid, A)) return 0;
   return (int64_t)((N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG) * etm_heads_loss_row_floats(hid, A) * (int64_t)sizeof(float);
+}
+// (the exact categorical KL: the etm_heads_loss row followed by the raw KL sum)
+extern "C" int etm_heads_loss_kl_row_floats(int hid, int A) { return etm_heads_loss_row_floats(hid, A) + 1; }
+extern "C" int64_t etm_heads_loss_kl_workspace_bytes(int N, int hid, int A) {
+  if (!etm_heads_loss_supported(N, hid, A)) return 0;
+  return (int64_t)((N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG) * etm_heads_loss_kl_row_floats(hid, A) * (int64_t)sizeof(float);
 }
 extern "C" int etm_heads_loss_supported_gaussian(int N, int hid, int A) { return A <= ETM_MAX_BOX && etm_heads_loss_supported(N, hid, A); }
 extern "C" int etm_heads_loss_gaussian_row_floats(int hid, int A) { return etm_heads_loss_row_floats(hid, A) + A; }
@@ -507,10 +536,12 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
                               float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
                               int A, const int32_t *branch_sizes, int n_branches, const float *xact, const float *log_std,
                               const int64_t *action_mask, void *stream, const float *old_mean = nullptr, int64_t old_mean_stride = 0,
-                              const float *old_log_std = nullptr) {
+                              const float *old_log_std = nullptr, const float *old_logps = nullptr, int64_t old_logps_stride = 0) {
   (void)hipGetLastError();
   const bool gauss = xact != nullptr;                  // Box: float actions xact and log_std instead of the int64 actions
   const bool kl = old_mean != nullptr;                 // Box with the exact KL: the row gains the KL sum
+  const bool ckl = old_logps != nullptr;               // categorical with the exact KL: likewise
+  if (ckl && gauss) return ETM_EINVAL;
   if (!pre_p || !pre_v || !b_lp || !b_lv || !wb || !bb || !wv || !bv || !(gauss ? (const void *)log_std : (const void *)actions) || !old_logp ||
       !adv || !old_value || !adv_stats3 || !gm_p || !gm_v || !sums || !out8 || !workspace)
     return ETM_EINVAL;
@@ -518,6 +549,7 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
   if (const int rc = etm_action_mask_check(action_mask, A)) return rc;
   if (!(gauss ? etm_heads_loss_supported_gaussian(N, hid, A) : etm_heads_loss_supported(N, hid, A))) return ETM_EUNSUPPORTED;
   if (workspace_bytes < (kl      ? etm_heads_loss_gaussian_kl_workspace_bytes(N, hid, A)
+                         : ckl   ? etm_heads_loss_kl_workspace_bytes(N, hid, A)
                          : gauss ? etm_heads_loss_gaussian_workspace_bytes(N, hid, A)
                                  : etm_heads_loss_workspace_bytes(N, hid, A)))
     return ETM_EWORKSPACE;
@@ -539,9 +571,11 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
   p.N = N; p.A = A; p.hid = hid; p.samples_per_wg = HL_SAMPLES_PER_WG;
   p.xact = xact; p.log_std = log_std; p.amask = (const long long *)action_mask;
   p.old_mean = old_mean; p.old_mean_stride = old_mean_stride; p.old_log_std = old_log_std;
+  p.old_logps = old_logps; p.old_logps_stride = old_logps_stride;
   const bool masked = action_mask != nullptr;
   const int n_wg = (N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG;
-  const int row = kl ? etm_heads_loss_gaussian_kl_row_floats(hid, A) : gauss ? etm_heads_loss_gaussian_row_floats(hid, A) : etm_heads_loss_row_floats(hid, A);
+  const int row = kl ? etm_heads_loss_gaussian_kl_row_floats(hid, A) : ckl ? etm_heads_loss_kl_row_floats(hid, A)
+                  : gauss ? etm_heads_loss_gaussian_row_floats(hid, A) : etm_heads_loss_row_floats(hid, A);
   const size_t lds = 4 * (size_t)row * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
   {
@@ -551,6 +585,10 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
   case HC_:                                                                                                       \
     if (kl) hipLaunchKernelGGL((heads_loss_gaussian_kl_kernel<HC_>), dim3((unsigned)n_wg), dim3(256), lds, st, p);  \
     else if (gauss) hipLaunchKernelGGL((heads_loss_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (ckl && masked && branched) hipLaunchKernelGGL((heads_loss_kl_kernel<HC_, true, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (ckl && masked) hipLaunchKernelGGL((heads_loss_kl_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (ckl && branched) hipLaunchKernelGGL((heads_loss_kl_kernel<HC_, true, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (ckl) hipLaunchKernelGGL((heads_loss_kl_kernel<HC_, false, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
     else if (masked && branched) hipLaunchKernelGGL((heads_loss_masked_kernel<HC_, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
     else if (masked) hipLaunchKernelGGL((heads_loss_masked_kernel<HC_, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
     else if (branched) hipLaunchKernelGGL((heads_loss_kernel<HC_, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
@@ -567,6 +605,9 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
   if (kl)
     hipLaunchKernelGGL(heads_reduce_kl_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg, row, A, hid,
                        vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8);
+  else if (ckl)
+    hipLaunchKernelGGL(heads_reduce_categorical_kl_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg,
+                       row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8);
   else
     hipLaunchKernelGGL(heads_reduce_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg, row, A, hid, vf_coef,
                        beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8);
@@ -635,6 +676,45 @@ extern "C" int etm_heads_loss_branched_masked(const float *pre_p, const float *p
                          clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
                          workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, nullptr,
                          action_mask, stream);
+}
+
+// The exact categorical KL (`exact_kl: true`): etm_heads_loss_masked / etm_heads_loss_branched_masked with action_mask optional (NULL:
+// no masks) and old_logps [N, A] (row stride old_logps_stride >= A floats; A = sum(sizes)), every column's log-prob under the policy
+// that drew the samples (the *_logps sampling entries; -inf where the column was masked out).  The same launch also reduces
+// sum_n sum_b KL_nb, KL_nb = the sum over the branch's valid columns of etm_categorical_kl_term: out8[4] = that sum * pol_scale (the
+// mean over samples and branches, the k3 value's convention), out8[6] = the k3 value the twin puts into out8[4].  A statistic only:
+// the loss, gm_p, gm_v, out8[0..3], out8[5] and the twin's row are the twin's bit for bit; sums [etm_heads_loss_kl_row_floats =
+// etm_heads_loss_row_floats + 1] carries the raw KL sum as its last element.  ETM_EINVAL: NULL or 4-byte-misaligned old_logps, a
+// stride below A; otherwise the twin's refusals.
+extern "C" int etm_heads_loss_kl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                 const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
+                                 const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
+                                 const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                                 float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
+                                 float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid, int A,
+                                 const int64_t *action_mask, const float *old_logps, int64_t old_logps_stride, void *stream) {
+  if (!old_logps || ((uintptr_t)old_logps & 3u) || old_logps_stride < A) return ETM_EINVAL;
+  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
+                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
+                         workspace_bytes, N, hid, A, nullptr, 1, nullptr, nullptr, action_mask, stream, nullptr, 0, nullptr, old_logps,
+                         old_logps_stride);
+}
+extern "C" int etm_heads_loss_branched_kl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                          const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
+                                          const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
+                                          const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale,
+                                          float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v,
+                                          float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes,
+                                          int N, int hid, const int32_t *branch_sizes, int n_branches, const int64_t *action_mask,
+                                          const float *old_logps, int64_t old_logps_stride, void *stream) {
+  if (!old_logps || ((uintptr_t)old_logps & 3u)) return ETM_EINVAL;
+  if (!etm_heads_loss_supported_branched(N, hid, branch_sizes, n_branches)) return ETM_EUNSUPPORTED;
+  if (action_stride < n_branches || logp_stride < n_branches || old_logps_stride < etm_branches_total(branch_sizes, n_branches))
+    return ETM_EINVAL;
+  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
+                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
+                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, nullptr,
+                         action_mask, stream, nullptr, 0, nullptr, old_logps, old_logps_stride);
 }
 
 // Box policies (diagonal Gaussian, A <= 8): wb / bb = the mean head [A, hid], [A]; xact [N, A] (row stride action_stride >= A) the

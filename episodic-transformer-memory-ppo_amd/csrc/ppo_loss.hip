@@ -92,6 +92,11 @@ struct LossParams {
   // MK kernels (invalid-action masks): amask [N] int64 words, the branch's A actions at bits [mask_shift, mask_shift + A)
   const long long *amask;
   int mask_shift;
+  // KL kernels (the exact categorical KL statistic): old_logps [N, row stride old_logps_stride], every column's log-prob under the policy
+  // that drew the samples; the branch's A columns start at column logps_off of a row
+  const float *old_logps;
+  long long old_logps_stride;
+  int logps_off;
 };
 
 // SPT samples per thread.  SPT = 4 (large batches, unit strides, A = 3, N % 4 == 0): the four samples' operands come in as
@@ -101,7 +106,9 @@ struct LossParams {
 // MK (SPT = 1 only): invalid-action masks.  Log-sum-exp, log-prob and entropy run over the VALID actions only; an invalid action has
 // p = 0, is skipped -- not multiplied: 0 * inf -- by the entropy, and its d logit is exactly 0.  What is left is the unmasked
 // arithmetic on the compacted branch.
-template <int SPT, bool MK>
+// KL (SPT = 1 only, MK or not): a sixth sum, the branch's exact KL(old || new) -- etm_categorical_kl_term over its valid columns, formed
+// where l and pj already are -- into slot 5 of the workgroup's 8 partial floats.  A statistic only: no term of the loss, no gradient.
+template <int SPT, bool MK, bool KL = false>
 __device__ __forceinline__ void ppo_loss_body(const LossParams &p0) {
   LossParams p = p0;
   if (p.dyn) {   // schedules that change between replays of a captured training step
@@ -109,10 +116,11 @@ __device__ __forceinline__ void ppo_loss_body(const LossParams &p0) {
     p.clip = (float)c; p.clip_lo = (float)(1.0 - c); p.clip_hi = (float)(1.0 + c);
     p.beta = (float)p.dyn[1];
   }
-  __shared__ float red[4][5];
+  constexpr int NK = KL ? 6 : 5;
+  __shared__ float red[4][NK];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n0 = (blockIdx.x * 256 + tid) * SPT;
-  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  // policy, value, entropy, kl, clip fraction
+  float acc[NK] = {0.f, 0.f, 0.f, 0.f, 0.f};  // policy, value, entropy, kl, clip fraction (KL: then the exact KL)
   // operands of this thread's samples
   float lgv[SPT][SPT == 1 ? 1 : 3], advv[SPT], oldlp[SPT], vv[SPT], vov[SPT], dlv[SPT][SPT == 1 ? 1 : 3], dvv[SPT];
   int actv[SPT];
@@ -187,6 +195,7 @@ __device__ __forceinline__ void ppo_loss_body(const LossParams &p0) {
       const float d_ent = -pj * (l + ent);                // d entropy / d logit_j
       const float g = cpol * d_lp + cent * d_ent;
       if (SPT == 4) dlv[s][SPT == 1 ? 0 : j] = g; else dl[j] = g;
+      if constexpr (KL) acc[NK - 1] += etm_categorical_kl_term(p.old_logps[(long long)n * p.old_logps_stride + p.logps_off + j], l, pj);
     }
     if (p.include_value) {
       const float v = SPT == 4 ? vv[s] : p.value[n], vo = SPT == 4 ? vov[s] : p.old_value[n];
@@ -219,41 +228,57 @@ __device__ __forceinline__ void ppo_loss_body(const LossParams &p0) {
     if (p.include_value) *reinterpret_cast<f32x4 *>(p.d_value + n0) = f32x4{dvv[0], dvv[SPT == 1 ? 0 : 1], dvv[SPT == 1 ? 0 : 2], dvv[SPT == 1 ? 0 : 3]};
   }
 #pragma unroll
-  for (int k = 0; k < 5; ++k) {
+  for (int k = 0; k < NK; ++k) {
     const float s = wave_sum(acc[k]);
     if (lane == 0) red[wave][k] = s;
   }
   __syncthreads();
-  if (tid < 5) p.partials[(long long)blockIdx.x * 8 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+  if (tid < NK) p.partials[(long long)blockIdx.x * 8 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
 }
 
-// The kernels: one body; the instantiations without masks keep their names, the masked one is a kernel of its own.
+// The kernels: one body; the instantiations without masks keep their names, the masked one and the ones with the exact KL are kernels
+// of their own.
 template <int SPT>
 __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossParams p0) { ppo_loss_body<SPT, false>(p0); }
 __global__ __launch_bounds__(256) void ppo_loss_masked_kernel(const LossParams p0) { ppo_loss_body<1, true>(p0); }
+template <bool MK>
+__global__ __launch_bounds__(256) void ppo_loss_kl_kernel(const LossParams p0) { ppo_loss_body<1, MK, true>(p0); }
 
-__global__ __launch_bounds__(64) void ppo_finalize_kernel(const float *__restrict__ partials, int n_blocks, float vf_coef, float beta,
-                                                          float pol_scale, float ent_scale, float val_scale, float *__restrict__ out8,
-                                                          const double *__restrict__ dyn) {
+// KL: the sixth partial is the exact KL sum -> out8[4] (scaled as the k3 value, which goes to out8[6])
+template <bool KL>
+__device__ __forceinline__ void ppo_finalize_body(const float *__restrict__ partials, int n_blocks, float vf_coef, float beta,
+                                                  float pol_scale, float ent_scale, float val_scale, float *__restrict__ out8,
+                                                  const double *__restrict__ dyn) {
+  constexpr int NK = KL ? 6 : 5;
   const int lane = threadIdx.x;
   if (dyn) beta = (float)dyn[1];
-  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  float acc[NK] = {0.f, 0.f, 0.f, 0.f, 0.f};
   for (int b = lane; b < n_blocks; b += 64)
 #pragma unroll
-    for (int k = 0; k < 5; ++k) acc[k] += partials[(long long)b * 8 + k];
+    for (int k = 0; k < NK; ++k) acc[k] += partials[(long long)b * 8 + k];
 #pragma unroll
-  for (int k = 0; k < 5; ++k) acc[k] = wave_sum(acc[k]);
+  for (int k = 0; k < NK; ++k) acc[k] = wave_sum(acc[k]);
   if (lane == 0) {
     const float pol = acc[0] * pol_scale, val = acc[1] * val_scale, ent = acc[2] * ent_scale;
     out8[0] = pol;
     out8[1] = val;
     out8[2] = -(pol - vf_coef * val + beta * ent);
     out8[3] = ent;
-    out8[4] = acc[3] * pol_scale;
+    out8[4] = acc[KL ? 5 : 3] * pol_scale;
     out8[5] = acc[4] * pol_scale;
-    out8[6] = 0.f;
+    out8[6] = KL ? acc[3] * pol_scale : 0.f;
     out8[7] = 0.f;
   }
+}
+__global__ __launch_bounds__(64) void ppo_finalize_kernel(const float *__restrict__ partials, int n_blocks, float vf_coef, float beta,
+                                                          float pol_scale, float ent_scale, float val_scale, float *__restrict__ out8,
+                                                          const double *__restrict__ dyn) {
+  ppo_finalize_body<false>(partials, n_blocks, vf_coef, beta, pol_scale, ent_scale, val_scale, out8, dyn);
+}
+__global__ __launch_bounds__(64) void ppo_finalize_kl_kernel(const float *__restrict__ partials, int n_blocks, float vf_coef, float beta,
+                                                             float pol_scale, float ent_scale, float val_scale, float *__restrict__ out8,
+                                                             const double *__restrict__ dyn) {
+  ppo_finalize_body<true>(partials, n_blocks, vf_coef, beta, pol_scale, ent_scale, val_scale, out8, dyn);
 }
 }  // namespace
 
@@ -296,7 +321,8 @@ static int ppo_loss_impl(const float *logits, const int64_t *actions, int64_t ac
                             const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
                             float val_scale, int include_value, float *out8, float *d_logits, float *d_value, void *partials,
                             int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, const int64_t *action_mask,
-                            int mask_shift, void *stream) {
+                            int mask_shift, void *stream, const float *old_logps = nullptr, int64_t old_logps_stride = 0,
+                            int logps_off = 0) {
   (void)hipGetLastError();  // drop stale sticky errors of earlier, unrelated runtime calls
   if (!logits || !actions || !old_logp || !adv || !adv_stats3 || !out8 || !d_logits || !partials) return ETM_EINVAL;
   if (include_value && (!old_value || !value || !d_value)) return ETM_EINVAL;
@@ -313,14 +339,18 @@ static int ppo_loss_impl(const float *logits, const int64_t *actions, int64_t ac
   p.dyn = dyn_clip_beta;
   p.include_value = include_value; p.d_logits = d_logits; p.d_value = d_value; p.partials = (float *)partials;
   p.N = N; p.A = A; p.amask = (const long long *)action_mask; p.mask_shift = mask_shift;
+  p.old_logps = old_logps; p.old_logps_stride = old_logps_stride; p.logps_off = logps_off;
+  const bool kl = old_logps != nullptr;                // the exact KL: always the one-sample form
   // four samples per thread when every operand can move in 16-byte pieces and there are enough samples to fill the chip
-  const bool vec = !action_mask && A == 3 && N % 4 == 0 && N >= (1 << 16) && action_stride == 1 && logp_stride == 1 && al16(logits) && al16(actions) &&
+  const bool vec = !kl && !action_mask && A == 3 && N % 4 == 0 && N >= (1 << 16) && action_stride == 1 && logp_stride == 1 && al16(logits) && al16(actions) &&
                    al16(old_logp) && al16(adv) && al16(d_logits) && (!include_value || (al16(value) && al16(old_value) && al16(d_value)));
   const int nb = vec ? (N / 4 + 255) / 256 : (N + 255) / 256;
   hipStream_t st = (hipStream_t)stream;
   {
     EtmProfScope prof(ETM_K_PPO_LOSS, st);
     if (vec) hipLaunchKernelGGL(ppo_loss_kernel<4>, dim3(nb), dim3(256), 0, st, p);
+    else if (kl && action_mask) hipLaunchKernelGGL(ppo_loss_kl_kernel<true>, dim3(nb), dim3(256), 0, st, p);
+    else if (kl) hipLaunchKernelGGL(ppo_loss_kl_kernel<false>, dim3(nb), dim3(256), 0, st, p);
     else if (action_mask) hipLaunchKernelGGL(ppo_loss_masked_kernel, dim3(nb), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(ppo_loss_kernel<1>, dim3(nb), dim3(256), 0, st, p);
   }
@@ -328,8 +358,12 @@ static int ppo_loss_impl(const float *logits, const int64_t *actions, int64_t ac
   if (rc) return rc;
   {
     EtmProfScope prof(ETM_K_PPO_FINAL, st);
-    hipLaunchKernelGGL(ppo_finalize_kernel, dim3(1), dim3(64), 0, st, (const float *)partials, nb, vf_coef, beta, pol_scale, ent_scale,
-                       val_scale, out8, dyn_clip_beta);
+    if (kl)
+      hipLaunchKernelGGL(ppo_finalize_kl_kernel, dim3(1), dim3(64), 0, st, (const float *)partials, nb, vf_coef, beta, pol_scale, ent_scale,
+                         val_scale, out8, dyn_clip_beta);
+    else
+      hipLaunchKernelGGL(ppo_finalize_kernel, dim3(1), dim3(64), 0, st, (const float *)partials, nb, vf_coef, beta, pol_scale, ent_scale,
+                         val_scale, out8, dyn_clip_beta);
   }
   return etm_launch_status();
 }
@@ -357,4 +391,22 @@ extern "C" int etm_ppo_loss_masked(const float *logits, const int64_t *actions, 
   return ppo_loss_impl(logits, actions, action_stride, old_logp, logp_stride, adv, old_value, value, adv_stats3, clip, vf_coef, beta, pol_scale,
                        ent_scale, val_scale, include_value, out8, d_logits, d_value, partials, partials_bytes, dyn_clip_beta, N, A, action_mask,
                        mask_shift, stream);
+}
+// The exact categorical KL (`exact_kl: true`) of one action branch: etm_ppo_loss_masked with action_mask optional (NULL: no masks;
+// mask_shift is then ignored) and old_logps [N, rows of old_logps_stride floats], every column's log-prob under the policy that drew
+// the samples (the *_logps sampling entries), the branch's A columns starting at column logps_off of a row.  out8[4] = pol_scale *
+// sum_n KL_n, KL_n = the sum over the branch's valid columns of etm_categorical_kl_term; out8[6] = the k3 value that the twin puts into
+// out8[4]; the loss, d_logits, d_value, out8[0..3], out8[5] and partial slots 0..4 are the twin's one-sample-per-thread form's, bit
+// for bit (slot 5 carries the raw KL sum).  ETM_EINVAL: NULL or 4-byte-misaligned old_logps, logps_off < 0, a stride below
+// logps_off + A; otherwise the twin's refusals.
+extern "C" int etm_ppo_loss_kl(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
+                               int64_t logp_stride, const float *adv, const float *old_value, const float *value,
+                               const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                               float val_scale, int include_value, float *out8, float *d_logits, float *d_value, void *partials,
+                               int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, const int64_t *action_mask,
+                               int mask_shift, const float *old_logps, int64_t old_logps_stride, int logps_off, void *stream) {
+  if (!old_logps || ((uintptr_t)old_logps & 3u) || logps_off < 0 || old_logps_stride < (int64_t)logps_off + A) return ETM_EINVAL;
+  return ppo_loss_impl(logits, actions, action_stride, old_logp, logp_stride, adv, old_value, value, adv_stats3, clip, vf_coef, beta, pol_scale,
+                       ent_scale, val_scale, include_value, out8, d_logits, d_value, partials, partials_bytes, dyn_clip_beta, N, A, action_mask,
+                       action_mask ? mask_shift : 0, stream, old_logps, old_logps_stride, logps_off);
 }

@@ -39,20 +39,26 @@ namespace {
 // configuration) gets a kernel without that code, which keeps its register allocation free of spills.
 // BOX: a Box policy's Gaussian draw at the end (etm_sample_gaussian, float tables p.box) instead of the categorical branches.
 // The body is included text (rollout_fused_body.inc): the kernels without masks are what they were, the masked kernel (categorical
-// policies only) is the same text with MK = true, the Box kernel that also stages the means the same text with MN = true.
+// policies only) is the same text with MK = true, the Box kernel that also stages the means the same text with MN = true, the
+// categorical kernels that also stage every column's log-prob (masks or not) the same text with LP = true.
 template <int GR, int LMAX, bool GEN, bool BOX>
 __global__ __launch_bounds__(RF_T) void rollout_trxl_kernel(const RfParams p) {
-  constexpr bool MK = false, MN = false;
+  constexpr bool MK = false, MN = false, LP = false;
 #include "rollout_fused_body.inc"
 }
 template <int GR, int LMAX, bool GEN>
 __global__ __launch_bounds__(RF_T) void rollout_trxl_masked_kernel(const RfParams p) {
-  constexpr bool BOX = false, MK = true, MN = false;
+  constexpr bool BOX = false, MK = true, MN = false, LP = false;
 #include "rollout_fused_body.inc"
 }
 template <int GR, int LMAX, bool GEN>
 __global__ __launch_bounds__(RF_T) void rollout_trxl_gaussian_means_kernel(const RfParams p) {
-  constexpr bool BOX = true, MK = false, MN = true;
+  constexpr bool BOX = true, MK = false, MN = true, LP = false;
+#include "rollout_fused_body.inc"
+}
+template <int GR, int LMAX, bool GEN, bool MK>
+__global__ __launch_bounds__(RF_T) void rollout_trxl_logps_kernel(const RfParams p) {
+  constexpr bool BOX = false, MN = false, LP = true;
 #include "rollout_fused_body.inc"
 }
 }  // namespace
@@ -219,9 +225,10 @@ static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, 
                                 int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
                                 int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W,
                                 const int32_t *branch_sizes, int n_branches, const RfBox *box, const int64_t *action_mask, void *stream,
-                                bool means = false, float *st_means = nullptr) {
+                                bool means = false, float *st_means = nullptr, bool logps = false, float *st_logps = nullptr) {
   (void)hipGetLastError();
   if (means && (!box || !st_means || ((uintptr_t)st_means & 3u))) return ETM_EINVAL;
+  if (logps && (box || !st_logps || ((uintptr_t)st_logps & 3u))) return ETM_EINVAL;
   if (ss && (!mask_table || !index_table || !st_mask || !st_idx || !latch || !mask_t || !win_t || T <= 0)) return ETM_EINVAL;
   if (!ss && (!win || !mask)) return ETM_EINVAL;
   // (a Box policy's action tables are the float ones of `box`; the int64 ones are unused then)
@@ -250,6 +257,7 @@ static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, 
   p.ss = (const long long *)ss; p.mask_table = mask_table; p.index_table = (const long long *)index_table; p.st_mask = st_mask;
   p.st_idx = (long long *)st_idx; p.latch = (long long *)latch; p.t_row = (long long *)t_row; p.mask_t = mask_t; p.win_t = (long long *)win_t;
   p.kv_init = kv_init; p.T = T; p.am = (const long long *)action_mask; p.st_means = means ? st_means : nullptr;
+  p.st_logps = logps ? st_logps : nullptr;
   p.h_in = h_in; p.h_bias = h_bias; p.h_splits = h_splits; p.wemb_t = wemb_t; p.bemb = bemb; p.nb = nb;
   for (int b = 0; b < nb; ++b) {
     const float *const *q = reinterpret_cast<const float *const *>(blocks) + RF_BLOCK_PTRS * b;
@@ -288,6 +296,12 @@ static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, 
     } else if (box_k) {                                                                                          \
       if (gen) hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, true, true>), grid, block, 0, st, p);           \
       else hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, false, true>), grid, block, 0, st, p);              \
+    } else if (p.st_logps && p.am) {                                                                             \
+      if (gen) hipLaunchKernelGGL((rollout_trxl_logps_kernel<GR_, LM_, true, true>), grid, block, 0, st, p);     \
+      else hipLaunchKernelGGL((rollout_trxl_logps_kernel<GR_, LM_, false, true>), grid, block, 0, st, p);        \
+    } else if (p.st_logps) {                                                                                     \
+      if (gen) hipLaunchKernelGGL((rollout_trxl_logps_kernel<GR_, LM_, true, false>), grid, block, 0, st, p);    \
+      else hipLaunchKernelGGL((rollout_trxl_logps_kernel<GR_, LM_, false, false>), grid, block, 0, st, p);       \
     } else if (p.am) {                                                                                           \
       if (gen) hipLaunchKernelGGL((rollout_trxl_masked_kernel<GR_, LM_, true>), grid, block, 0, st, p);          \
       else hipLaunchKernelGGL((rollout_trxl_masked_kernel<GR_, LM_, false>), grid, block, 0, st, p);             \
@@ -414,6 +428,31 @@ extern "C" int etm_rollout_trxl_group_branched_masked(const float *h_in, const f
                           latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, etm_branches_total(branch_sizes, n_branches), stage_W,
                           branch_sizes, n_branches, nullptr, action_mask, stream);
 }
+// The exact categorical KL (`exact_kl: true`): the two masked launches with action_mask optional (NULL: no masks) and st_logps
+// [S, stage_W, sum(sizes)] (at this group's first worker, as st_actions) before the stream: every column's log-prob lg[j] - lse of
+// the row -- sampled, greedy or forced action alike; -inf for a masked-out column; the st_logp entry's bits at the taken action --,
+// stored by the sampling thread as it draws.  Every other output is the twin's, bit for bit.  ETM_EINVAL: NULL or 4-byte-misaligned st_logps.
+#define RF_LOGPS_ARGS                                                                                                                       \
+  const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv, int64_t kv_worker_stride,       \
+      int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items, const float *wh_t, const float *bh, const float *wp,    \
+      const float *bp, const float *wv, const float *bv, const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions,   \
+      int64_t *st_actions, float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,             \
+      float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,                       \
+      const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride,                    \
+      const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,       \
+      int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T, int pre_ln,           \
+      int gtrxl, int W, int D, int H, int L, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,                            \
+      const int64_t *action_mask, float *st_logps, void *stream
+#define RF_LOGPS_PASS                                                                                                                       \
+  h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced,      \
+      t_dev, actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos,     \
+      step_l, slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask,  \
+      st_idx, latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, etm_branches_total(branch_sizes, n_branches),       \
+      stage_W, branch_sizes, n_branches, nullptr, action_mask, stream, false, nullptr, true, st_logps
+extern "C" int etm_rollout_trxl_branched_logps(RF_LOGPS_ARGS) { return rollout_trxl_impl(0, RF_LOGPS_PASS); }
+extern "C" int etm_rollout_trxl_group_branched_logps(RF_LOGPS_ARGS) { return rollout_trxl_impl(1, RF_LOGPS_PASS); }
+#undef RF_LOGPS_ARGS
+#undef RF_LOGPS_PASS
 extern "C" int etm_rollout_trxl_supported_branched(int D, int H, int L, int hid, const int32_t *branch_sizes, int n_branches, int nb) {
   const int A = etm_branches_total(branch_sizes, n_branches);
   return A > 0 && etm_rollout_trxl_supported(D, H, L, hid, A, nb);

@@ -1,7 +1,8 @@
 // The body of the per-worker step kernels of csrc/rollout_fused.hip (included text, one definition): the including kernel provides the
 // template parameters GR, LMAX, GEN, BOX, the launch parameters `p` and the constant MK (invalid-action masks: the sampler's word is
 // fetched with the step's uniforms and the masked instantiation of the shared sampler draws) and the constant MN (BOX only: the
-// Gaussian draw also stages the means into p.st_means).
+// Gaussian draw also stages the means into p.st_means) and the constant LP (categorical only, MK or not: every column's log-prob of
+// the row goes to p.st_logps, stored by the sampling thread as it draws).
   constexpr int KR = LMAX / RF_WAVES;                             // window rows per wave (energies)
   constexpr int VR = LMAX / 16;                                   // window rows per thread (context): >= 16 row groups (D / P <= 128)
   __shared__ __attribute__((aligned(16))) float x_s[RF_T];        // current hidden state h_b (full row, every member)
@@ -535,7 +536,16 @@
           const int Ab = p.br.size[b];
           float lp;
           int a;
-          if constexpr (MK) a = etm_sample_branch<true>(out_s + off, Ab, u_s[b], forced_s[b], &lp, (unsigned long long)am_s >> off);
+          if constexpr (LP) {
+            unsigned long long mb = 0ull;
+            if constexpr (MK) mb = (unsigned long long)am_s >> off;
+#ifndef ETM_LOGPS_TAIL          // the columns are stored by the sampling thread as it draws (the measured faster of the two placements)
+            a = etm_sample_branch<MK, true>(out_s + off, Ab, u_s[b], forced_s[b], &lp, mb, p.st_logps + row * A + off);
+#else                           // (diagnostic build: stored behind the hand-over; the branch's lse takes the place of its uniform)
+            a = etm_sample_branch<MK, true>(out_s + off, Ab, u_s[b], forced_s[b], &lp, mb, nullptr, u_s + b);
+#endif
+          }
+          else if constexpr (MK) a = etm_sample_branch<true>(out_s + off, Ab, u_s[b], forced_s[b], &lp, (unsigned long long)am_s >> off);
           else a = etm_sample_branch(out_s + off, Ab, u_s[b], forced_s[b], &lp);
           p.actions[(long long)w * B + b] = a;
           if (p.host_actions) p.host_actions[(long long)w * B + b] = a;
@@ -564,6 +574,24 @@
       }
     }
   }
+#ifdef ETM_LOGPS_TAIL
+  // (diagnostic build, the other store placement: measured slower on the replayed step graph, profiles/r18/exact_kl.txt)
+  // LP: every column's log-prob of this worker's row, behind the hand-over (they need only be there when the launch ends): one column
+  // per thread from the logits still in out_s and the branch's lse that the sampler left in u_s -- at the taken action the expression
+  // and the operands of the staged log-prob, so its bits; a masked-out column is -inf
+  if constexpr (LP) {
+    if (me == 0) {                                                  // (uniform per workgroup)
+      rf_sync();
+      if (tid < p.A) {
+        int b = 0, off = p.br.size[0];
+        while (tid >= off) off += p.br.size[++b];
+        float l = out_s[tid];
+        if constexpr (MK) { if (!(((unsigned long long)am_s >> tid) & 1ull)) l = -INFINITY; }
+        p.st_logps[(t_now * p.stage_W + w) * p.A + tid] = l - u_s[b];
+      }
+    }
+  }
+#endif
   // ---- tail, after the hand-over (the host is stepping the environments now): bank[slot, step, b] = item_b (member 0) and
   // cache[w, step, b] = (item_b + pos[step]) [Wk ; Wv]^T, the D / P columns of K and of V that I read (transformer.py:236-237 applied to one new row;
   // the rows of this step are not part of any window of this launch that is still being read: a member gets here only after

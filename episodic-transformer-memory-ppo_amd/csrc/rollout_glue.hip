@@ -76,18 +76,20 @@ __global__ __launch_bounds__(256) void rollout_heads_kernel(const float *__restr
 // One thread per worker: per action branch log-softmax over its segment, inverse-CDF sample with the pre-drawn uniform of
 // (t, w, b) (or a forced action), log-prob; staging of actions / log_probs / values for step t; finally t += 1.
 // MK: am [W] are the workers' action-mask words (one body; the unmasked kernel keeps its name and arguments).
-template <bool MK>
+// LP: st_logps [S, W, A] receives every column's log-prob of the row (the exact categorical KL; kernels of their own, MK or not).
+template <bool MK, bool LP = false>
 __device__ __forceinline__ void rollout_sample_body(const float *__restrict__ logits, const float *__restrict__ value,
                                                     const float *__restrict__ uniforms, const long long *__restrict__ forced,
                                                     long long *__restrict__ t_dev, long long *__restrict__ actions,
                                                     long long *__restrict__ st_actions, float *__restrict__ st_logp,
                                                     float *__restrict__ st_values, int W, int A, const EtmBranches &br,
-                                                    const long long *__restrict__ am) {
+                                                    const long long *__restrict__ am, float *__restrict__ st_logps = nullptr) {
   const long long t = *t_dev;
   for (int w = threadIdx.x; w < W; w += 1024) {
     // logits [W, A]: the branches' segments side by side; forced / uniforms / staging time-major [S, W, B] (B = 1: [S, W]), a
     // negative forced entry means "sample"
-    etm_sample_branches<MK>(logits + (long long)w * A, br, t * W + w, w, uniforms, forced, actions, nullptr, st_actions, st_logp, am + w);
+    etm_sample_branches<MK, LP>(logits + (long long)w * A, br, t * W + w, w, uniforms, forced, actions, nullptr, st_actions, st_logp, am + w,
+                                st_logps, A);
     st_values[t * W + w] = value[w];
   }
   __syncthreads();
@@ -107,6 +109,16 @@ __global__ __launch_bounds__(1024) void rollout_sample_masked_kernel(const float
                                                                      float *__restrict__ st_values, int W, int A, const EtmBranches br,
                                                                      const long long *__restrict__ am) {
   rollout_sample_body<true>(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W, A, br, am);
+}
+// the same body with every column's log-prob staged too (st_logps [S, W, A]); MK: with the workers' mask words
+template <bool MK>
+__global__ __launch_bounds__(1024) void rollout_sample_logps_kernel(const float *__restrict__ logits, const float *__restrict__ value,
+                                                                    const float *__restrict__ uniforms, const long long *__restrict__ forced,
+                                                                    long long *__restrict__ t_dev, long long *__restrict__ actions,
+                                                                    long long *__restrict__ st_actions, float *__restrict__ st_logp,
+                                                                    float *__restrict__ st_values, int W, int A, const EtmBranches br,
+                                                                    const long long *__restrict__ am, float *__restrict__ st_logps) {
+  rollout_sample_body<MK, true>(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W, A, br, am, st_logps);
 }
 
 // Box policies (etm_sample_gaussian): one thread per worker, the A means of row w of `mean`, its A normals / forced entries of
@@ -177,13 +189,14 @@ __device__ __forceinline__ void policy_arrive(bool to_host, long long t, long lo
 // by the step counter the host spins on.
 // MK: am [W] are the workers' action-mask words, device or pinned host memory -- requested in front of the dot products (one body;
 // the unmasked kernel keeps its name and arguments).
-template <bool MK>
+// LP: st_logps [S, stage_W, A] receives every column's log-prob of the row (kernels of their own, MK or not).
+template <bool MK, bool LP = false>
 __device__ __forceinline__ void rollout_policy_body(const float *__restrict__ h, const float *__restrict__ wp, const float *__restrict__ bp,
     const float *__restrict__ wv, const float *__restrict__ bv, const float *__restrict__ h_bias, const float *__restrict__ uniforms,
     const long long *__restrict__ forced, long long *__restrict__ t_dev, long long *__restrict__ actions,
     long long *__restrict__ st_actions, float *__restrict__ st_logp, float *__restrict__ st_values, long long *host_actions,
     long long *host_flag, int *sync_counter, int W, int A, int hid, int stage_W, const EtmBranches &br,
-    const long long *__restrict__ am) {
+    const long long *__restrict__ am, float *__restrict__ st_logps = nullptr) {
   extern __shared__ float out_s[];   // [A + 1]: logits (the branches' segments side by side), then the value
   __shared__ long long am_s;
   const int w = blockIdx.x;
@@ -193,7 +206,7 @@ __device__ __forceinline__ void rollout_policy_body(const float *__restrict__ h,
   __syncthreads();
   if (threadIdx.x == 0) {
     // forced / uniforms / staging: time-major [S, stage_W, B] (B = 1: [S, stage_W]); negative forced entry = "sample"
-    etm_sample_branches<MK>(out_s, br, t * stage_W + w, w, uniforms, forced, actions, host_actions, st_actions, st_logp, &am_s);
+    etm_sample_branches<MK, LP>(out_s, br, t * stage_W + w, w, uniforms, forced, actions, host_actions, st_actions, st_logp, &am_s, st_logps, A);
     st_values[t * stage_W + w] = out_s[A];
     policy_arrive(host_actions != nullptr, t, t_dev, host_flag, sync_counter, W);
   }
@@ -212,6 +225,16 @@ __global__ __launch_bounds__(256) void rollout_policy_masked_kernel(const float 
     long long *host_flag, int *sync_counter, int W, int A, int hid, int stage_W, const EtmBranches br,
     const long long *__restrict__ am) {
   rollout_policy_body<true>(h, wp, bp, wv, bv, h_bias, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, W, A, hid, stage_W, br, am);
+}
+// the same body with every column's log-prob staged too (st_logps [S, stage_W, A]); MK: with the workers' mask words
+template <bool MK>
+__global__ __launch_bounds__(256) void rollout_policy_logps_kernel(const float *__restrict__ h, const float *__restrict__ wp, const float *__restrict__ bp,
+    const float *__restrict__ wv, const float *__restrict__ bv, const float *__restrict__ h_bias, const float *__restrict__ uniforms,
+    const long long *__restrict__ forced, long long *__restrict__ t_dev, long long *__restrict__ actions,
+    long long *__restrict__ st_actions, float *__restrict__ st_logp, float *__restrict__ st_values, long long *host_actions,
+    long long *host_flag, int *sync_counter, int W, int A, int hid, int stage_W, const EtmBranches br,
+    const long long *__restrict__ am, float *__restrict__ st_logps) {
+  rollout_policy_body<MK, true>(h, wp, bp, wv, bv, h_bias, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, W, A, hid, stage_W, br, am, st_logps);
 }
 
 // The same launch for a Box policy: the A outputs are the Gaussian's means; the draw of etm_sample_gaussian with the normals /
@@ -310,8 +333,10 @@ extern "C" int etm_rollout_window(const int64_t *step, const uint8_t *mask_table
 
 static int rollout_sample_impl(const float *logits, const float *value, const float *uniforms, const int64_t *forced, int64_t *t_dev,
                                int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W, int A,
-                               const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, void *stream) {
+                               const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, void *stream,
+                               bool logps = false, float *st_logps = nullptr) {
   (void)hipGetLastError();
+  if (logps && (!st_logps || ((uintptr_t)st_logps & 3u))) return ETM_EINVAL;
   if (!logits || !value || !uniforms || !t_dev || !actions || !st_actions || !st_logp || !st_values || W <= 0 || A <= 0)
     return ETM_EINVAL;
   EtmBranches br;
@@ -319,7 +344,15 @@ static int rollout_sample_impl(const float *logits, const float *value, const fl
   if (const int rc = etm_action_mask_check(action_mask, A)) return rc;
   hipStream_t st = (hipStream_t)stream;
   EtmProfScope prof(ETM_K_ROLLOUT_SAMPLE, st);
-  if (action_mask)
+  if (logps && action_mask)
+    hipLaunchKernelGGL(rollout_sample_logps_kernel<true>, dim3(1), dim3(1024), 0, st, logits, value, uniforms, (const long long *)forced,
+                       (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values, W, A, br,
+                       (const long long *)action_mask, st_logps);
+  else if (logps)
+    hipLaunchKernelGGL(rollout_sample_logps_kernel<false>, dim3(1), dim3(1024), 0, st, logits, value, uniforms, (const long long *)forced,
+                       (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values, W, A, br,
+                       (const long long *)nullptr, st_logps);
+  else if (action_mask)
     hipLaunchKernelGGL(rollout_sample_masked_kernel, dim3(1), dim3(1024), 0, st, logits, value, uniforms, (const long long *)forced,
                        (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values, W, A, br,
                        (const long long *)action_mask);
@@ -351,13 +384,25 @@ extern "C" int etm_rollout_sample_branched_masked(const float *logits, const flo
   return rollout_sample_impl(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W,
                              etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, action_mask, stream);
 }
+// The exact categorical KL (`exact_kl: true`): etm_rollout_sample_branched_masked with action_mask optional (NULL: no masks) and
+// st_logps [S, W, sum(sizes)] next to st_actions, which receives lg[j] - lse of every column of every branch -- the policy's
+// distribution whether the action was sampled, taken greedily or forced; -inf for a masked-out column; at the taken action the
+// st_logp entry's bits.  Every other output is the twin's, bit for bit.  ETM_EINVAL: NULL or 4-byte-misaligned st_logps.
+extern "C" int etm_rollout_sample_branched_logps(const float *logits, const float *value, const float *uniforms, const int64_t *forced,
+                                                 int64_t *t_dev, int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values,
+                                                 int W, const int32_t *branch_sizes, int n_branches, const int64_t *action_mask,
+                                                 float *st_logps, void *stream) {
+  return rollout_sample_impl(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, W,
+                             etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, action_mask, stream, true, st_logps);
+}
 
 static int rollout_policy_impl(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv, const float *bv,
                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
                                int W, int A, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,
-                               const int64_t *action_mask, void *stream) {
+                               const int64_t *action_mask, void *stream, bool logps = false, float *st_logps = nullptr) {
   (void)hipGetLastError();
+  if (logps && (!st_logps || ((uintptr_t)st_logps & 3u))) return ETM_EINVAL;
   if (!h || !wp || !bp || !wv || !bv || !uniforms || !t_dev || !actions || !st_actions || !st_logp || !st_values ||
       !sync_counter || W <= 0 || A <= 0 || hid <= 0 || stage_W < W)
     return ETM_EINVAL;
@@ -369,7 +414,17 @@ static int rollout_policy_impl(const float *h, const float *h_bias, const float 
   if (lds > 64 * 1024) return ETM_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   EtmProfScope prof(ETM_K_ROLLOUT_SAMPLE, st);
-  if (action_mask)
+  if (logps && action_mask)
+    hipLaunchKernelGGL(rollout_policy_logps_kernel<true>, dim3((unsigned)W), dim3(256), lds, st, h, wp, bp, wv, bv, h_bias, uniforms,
+                       (const long long *)forced, (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values,
+                       (long long *)host_actions, (long long *)host_flag, (int *)sync_counter, W, A, hid, stage_W, br,
+                       (const long long *)action_mask, st_logps);
+  else if (logps)
+    hipLaunchKernelGGL(rollout_policy_logps_kernel<false>, dim3((unsigned)W), dim3(256), lds, st, h, wp, bp, wv, bv, h_bias, uniforms,
+                       (const long long *)forced, (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values,
+                       (long long *)host_actions, (long long *)host_flag, (int *)sync_counter, W, A, hid, stage_W, br,
+                       (const long long *)nullptr, st_logps);
+  else if (action_mask)
     hipLaunchKernelGGL(rollout_policy_masked_kernel, dim3((unsigned)W), dim3(256), lds, st, h, wp, bp, wv, bv, h_bias, uniforms,
                        (const long long *)forced, (long long *)t_dev, (long long *)actions, (long long *)st_actions, st_logp, st_values,
                        (long long *)host_actions, (long long *)host_flag, (int *)sync_counter, W, A, hid, stage_W, br,
@@ -410,6 +465,18 @@ extern "C" int etm_rollout_policy_branched_masked(const float *h, const float *h
   return rollout_policy_impl(h, h_bias, wp, bp, wv, bv, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions,
                              host_flag, sync_counter, W, etm_branches_total(branch_sizes, n_branches), hid, stage_W, branch_sizes,
                              n_branches, action_mask, stream);
+}
+// (the exact categorical KL) etm_rollout_policy_branched_masked with action_mask optional (NULL: no masks) and st_logps
+// [S, stage_W, sum(sizes)] at this group's first worker, as etm_rollout_sample_branched_logps.
+extern "C" int etm_rollout_policy_branched_logps(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv,
+                                                 const float *bv, const float *uniforms, const int64_t *forced, int64_t *t_dev,
+                                                 int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values,
+                                                 int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter, int W, int hid,
+                                                 int stage_W, const int32_t *branch_sizes, int n_branches, const int64_t *action_mask,
+                                                 float *st_logps, void *stream) {
+  return rollout_policy_impl(h, h_bias, wp, bp, wv, bv, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, host_actions,
+                             host_flag, sync_counter, W, etm_branches_total(branch_sizes, n_branches), hid, stage_W, branch_sizes,
+                             n_branches, action_mask, stream, true, st_logps);
 }
 
 // (means: the _means entry, which also stages the means into st_means [S, W, A])

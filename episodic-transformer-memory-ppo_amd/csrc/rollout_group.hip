@@ -170,20 +170,26 @@ __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf
 // KM = D / 32 (MFMA steps per wave and chunk), LMAX: window rows the K / V registers of a unit are sized for
 // BOX: a Box policy's Gaussian draw (etm_sample_gaussian, float tables p.box) instead of the categorical branches.
 // The body is included text (rollout_group_body.inc): the kernels without masks are what they were, the masked kernel (categorical
-// policies only) is the same text with MK = true, the Box kernel that also stages the means the same text with MN = true.
+// policies only) is the same text with MK = true, the Box kernel that also stages the means the same text with MN = true, the
+// categorical kernels that also stage every column's log-prob (masks or not) the same text with LP = true.
 template <int KM, int LMAX, bool BOX>
 __global__ __launch_bounds__(RF_T) void rollout_group_kernel(const RfParams p) {
-  constexpr bool MK = false, MN = false;
+  constexpr bool MK = false, MN = false, LP = false;
 #include "rollout_group_body.inc"
 }
 template <int KM, int LMAX>
 __global__ __launch_bounds__(RF_T) void rollout_group_masked_kernel(const RfParams p) {
-  constexpr bool BOX = false, MK = true, MN = false;
+  constexpr bool BOX = false, MK = true, MN = false, LP = false;
 #include "rollout_group_body.inc"
 }
 template <int KM, int LMAX>
 __global__ __launch_bounds__(RF_T) void rollout_group_gaussian_means_kernel(const RfParams p) {
-  constexpr bool BOX = true, MK = false, MN = true;
+  constexpr bool BOX = true, MK = false, MN = true, LP = false;
+#include "rollout_group_body.inc"
+}
+template <int KM, int LMAX, bool MK>
+__global__ __launch_bounds__(RF_T) void rollout_group_logps_kernel(const RfParams p) {
+  constexpr bool BOX = false, MN = false, LP = true;
 #include "rollout_group_body.inc"
 }
 
@@ -220,6 +226,7 @@ int etm_rf_launch_group(const RfParams &p, hipStream_t st) {
 #define RG_LAUNCH(KM_, LM_)                                                                                                   \
   do {                                                                                                                        \
     auto kern = box ? (p.st_means ? rollout_group_gaussian_means_kernel<KM_, LM_> : rollout_group_kernel<KM_, LM_, true>)     \
+                    : p.st_logps ? (p.am ? rollout_group_logps_kernel<KM_, LM_, true> : rollout_group_logps_kernel<KM_, LM_, false>) \
                     : p.am ? rollout_group_masked_kernel<KM_, LM_> : rollout_group_kernel<KM_, LM_, false>;                   \
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
     hipLaunchKernelGGL(kern, grid, block, lds, st, p);                                                                        \

@@ -1,7 +1,8 @@
 // The body of the group step kernels of csrc/rollout_group.hip (included text, one definition): the including kernel provides the
 // template parameters KM, LMAX, BOX, the launch parameters `p` and the constant MK (invalid-action masks: workgroup 0 fetches the
 // workers' words next to the (step, slot) block and the masked instantiation of the shared sampler draws) and the constant MN (BOX
-// only: the Gaussian draw also stages the means into p.st_means).
+// only: the Gaussian draw also stages the means into p.st_means) and the constant LP (categorical only, MK or not: every column's
+// log-prob of every worker's row goes to p.st_logps, stored by the sampling thread as it draws).
   constexpr int GR = 20;                                          // tail: rows of a K | V projection slice per thread and batch
   constexpr int KR = LMAX / RF_WAVES, VR = LMAX / 16;
   constexpr int NPK = (KM + 3) / 4;                               // packets per thread of a full gather: 32 * 8 CB / 2 / 512 = D / 128
@@ -466,8 +467,13 @@
                                 MN ? p.st_means : nullptr);
       } else {
         // per branch: its own logit segment, uniform and forced entry ([S, stage_W, B] tables; B = 1: [S, stage_W])
-        etm_sample_branches<MK>(lg, p.br, t * p.stage_W + tid, tid, p.uniforms, p.forced, p.actions, p.host_actions, p.st_actions,
-                                p.st_logp, am_s + tid);
+#ifndef ETM_LOGPS_TAIL          // LP: the columns are stored by the sampling thread as it draws (the measured faster of the two placements)
+        etm_sample_branches<MK, LP>(lg, p.br, t * p.stage_W + tid, tid, p.uniforms, p.forced, p.actions, p.host_actions, p.st_actions,
+                                    p.st_logp, am_s + tid, LP ? p.st_logps : nullptr, A);
+#else                           // (diagnostic build) LP: the branches' lse go to the dead hidden-head rows (h2_s [worker][16]) for the stores behind the hand-over
+        etm_sample_branches<MK, LP>(lg, p.br, t * p.stage_W + tid, tid, p.uniforms, p.forced, p.actions, p.host_actions, p.st_actions,
+                                    p.st_logp, am_s + tid, nullptr, A, LP ? h2_s + tid * 16 : nullptr);
+#endif
         p.st_values[t * p.stage_W + tid] = lg[A];
       }
       if (BOX ? p.box.host_actions != nullptr : p.host_actions != nullptr) __threadfence_system();
@@ -483,6 +489,22 @@
         __hip_atomic_store(p.host_flag, t_now + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
+#ifdef ETM_LOGPS_TAIL
+    // (diagnostic build, the other store placement: not faster on the replayed step graph, profiles/r18/exact_kl.txt)
+    // LP: every column's log-prob of every worker's row, behind the hand-over (they need only be there when the launch ends): one
+    // (worker, column) per thread from the logits still in out_s and the branch's lse the sampler left in h2_s -- at the taken
+    // action the expression and the operands of the staged log-prob, so its bits; a masked-out column is -inf
+    if constexpr (LP) {
+      if (tid < W * A) {
+        const int gw = tid / A, j = tid - gw * A;
+        int b = 0, off = p.br.size[0];
+        while (j >= off) off += p.br.size[++b];
+        float l = out_s[gw * 16 + j];
+        if constexpr (MK) { if (!(((unsigned long long)am_s[gw] >> j) & 1ull)) l = -INFINITY; }
+        p.st_logps[(t_now * p.stage_W + gw) * A + j] = l - h2_s[gw * 16 + b];
+      }
+    }
+#endif
   }
   ++ex;
   // ---- tail (units): bank[slot, step, b] = item_b (head 0's workgroup) and my head's K | V columns of the new cache row

@@ -82,6 +82,7 @@ struct RfParams {
   // (last: every member above keeps its place in the kernels' argument block)
   const long long *am;               // the masked instantiations only: [W] action-mask words of the step (device or pinned host memory)
   float *st_means;                   // the BOX instantiations that stage the means only (MN): [S, stage_W, A] next to box.st_actions
+  float *st_logps;                   // the categorical instantiations that stage every column's log-prob only (LP): [S, stage_W, A]
 };
 
 namespace {

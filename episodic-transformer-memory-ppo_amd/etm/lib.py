@@ -207,6 +207,21 @@ _res, _args = SIGNATURES["etm_heads_loss_gaussian"]
 SIGNATURES["etm_heads_loss_gaussian_kl"] = (_res, _args[:-1] + [_P, _L, _P] + _args[-1:])
 SIGNATURES["etm_heads_loss_gaussian_kl_row_floats"] = (_I, [_I, _I])
 SIGNATURES["etm_heads_loss_gaussian_kl_workspace_bytes"] = (_L, [_I, _I, _I])
+# the exact categorical KL (`exact_kl: true`; added with the ABI left at 61 -- no signature above changes): the four categorical sampling
+# entries' *_logps forms take their masked twin's arguments (the mask optional) and the log-probs' staging table in front of the stream;
+# the loss entries their masked twin's (the mask optional) and old_logps, its row stride (etm_ppo_loss_kl: and the branch's first
+# column) there
+for _name in ("etm_rollout_sample_branched", "etm_rollout_policy_branched", "etm_rollout_trxl_branched", "etm_rollout_trxl_group_branched"):
+    _res, _args = SIGNATURES[_name + "_masked"]
+    SIGNATURES[_name + "_logps"] = (_res, _args[:-1] + [_P] + _args[-1:])
+for _name, _twin, _extra in (("etm_heads_loss_kl", "etm_heads_loss_masked", [_P, _L]),
+                             ("etm_heads_loss_branched_kl", "etm_heads_loss_branched_masked", [_P, _L]),
+                             ("etm_ppo_loss_kl", "etm_ppo_loss_masked", [_P, _L, _I])):
+    _res, _args = SIGNATURES[_twin]
+    SIGNATURES[_name] = (_res, _args[:-1] + _extra + _args[-1:])
+SIGNATURES["etm_heads_loss_kl_row_floats"] = (_I, [_I, _I])
+SIGNATURES["etm_heads_loss_kl_workspace_bytes"] = (_L, [_I, _I, _I])
+del _twin
 del _name, _extra, _res, _args
 
 

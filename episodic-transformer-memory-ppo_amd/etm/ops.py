@@ -836,16 +836,40 @@ def _sizes_or_single(branches, A):
     return (int(A),) if sizes is None else sizes
 
 
-def rollout_sample(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, branches=None, action_mask=None):
+def _check_logps_table(st_logps, st_values, A):
+    """The log-probs' staging table of the ``*_logps`` entries lies next to the other staging tables: float32 [S, W_total, A] (A = all
+    branches' columns together), contiguous, on their device."""
+    if (st_logps.dtype != torch.float32 or tuple(st_logps.shape) != (*st_values.shape[:2], A) or not st_logps.is_contiguous()
+            or st_logps.device != st_values.device):
+        raise ValueError(f"st_logps: need a contiguous float32 [{st_values.shape[0]}, {st_values.shape[1]}, {A}] table on the staging "
+                         f"tables' device, got {tuple(st_logps.shape)} {st_logps.dtype}")
+
+
+def rollout_sample(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, branches=None, action_mask=None,
+                   st_logps=None):
     """Categorical sampling + staging of one rollout step (in place; increments t_dev).  ``forced`` (optional): time-major int64
     table [S, W]; entries >= 0 replace the sample of that (step, worker).  ``branches`` (optional, MultiDiscrete): the branch sizes;
     ``logits`` [W, sum] holds the branches' logits side by side, every branch is sampled on its own segment with its own uniform, and
     ``uniforms`` / ``forced`` / ``st_actions`` / ``st_logp`` are [S, W, B], ``actions`` [W, B] (etm_rollout_sample_branched).
     ``action_mask`` (optional): int64 [W], the workers' invalid-action words of this step (bit j = logit column j is allowed; no
-    branch empty): every branch is drawn over its valid actions only (etm_rollout_sample_branched_masked)."""
+    branch empty): every branch is drawn over its valid actions only (etm_rollout_sample_branched_masked).
+    ``st_logps`` (optional, float32 [S, W, sum]): every column's log-prob of the row is staged too -- the policy's distribution,
+    sampled, greedy or forced action alike; -inf at a masked-out column (etm_rollout_sample_branched_logps, masks or not); None is
+    exactly the call without."""
     lib = _lib.load()
     W, A = logits.shape
     logits, value = _f32c(logits, "logits"), _f32c(value, "value")
+    if st_logps is not None:
+        sizes = _sizes_or_single(branches, A)
+        if sum(sizes) != A:
+            raise ValueError(f"rollout_sample: branches {sizes} do not add up to the {A} logit columns")
+        tab, nbr = _branch_table(sizes)
+        _check_logps_table(st_logps, st_values, A)
+        am = 0 if action_mask is None else _mask_words(action_mask, W, A, "rollout_sample", device=False).data_ptr()
+        _lib.check(lib.etm_rollout_sample_branched_logps(_ptr(logits), _ptr(value), _ptr(uniforms), _ptr(forced), _ptr(t_dev), _ptr(actions),
+                                                         _ptr(st_actions), _ptr(st_logp), _ptr(st_values), W, tab, nbr, am,
+                                                         _ptr(st_logps), _stream()), "etm_rollout_sample_branched_logps")
+        return
     if action_mask is not None:
         sizes = _sizes_or_single(branches, A)
         if sum(sizes) != A:
@@ -958,8 +982,9 @@ def rollout_policy_gaussian(h2, mean_head, value_head, log_std, normals, forced,
 
 
 def rollout_policy(h2, policy_head, value_head, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values,
-                   host_actions=None, host_flag=None, h_bias=None, w_off=0, branches=None, action_mask=None):
-    """``rollout_heads`` + ``rollout_sample`` in one launch; ``host_actions`` / ``host_flag``: pinned int64 tensors that receive
+                   host_actions=None, host_flag=None, h_bias=None, w_off=0, branches=None, action_mask=None, st_logps=None):
+    """``rollout_heads`` + ``rollout_sample`` in one launch; ``st_logps``: as in ``rollout_sample`` ([S, W_total, sum], this group's
+    slice taken as for ``st_actions``; etm_rollout_policy_branched_logps); ``host_actions`` / ``host_flag``: pinned int64 tensors that receive
     the actions and then the incremented step counter (the host spins on the flag).  ``forced`` (optional): time-major int64 table
     [S, W_total]; entries >= 0 replace the sample of that (step, worker).  ``branches`` (optional, MultiDiscrete): the branch sizes;
     ``policy_head`` is then the branches' heads concatenated ([sum, hid]) and the tables are as in ``rollout_sample``.
@@ -980,6 +1005,21 @@ def rollout_policy(h2, policy_head, value_head, uniforms, forced, t_dev, actions
     sizes = _branch_sizes(branches)
     nb_ = 1 if sizes is None else len(sizes)
     off = lambda t: None if t is None else t.data_ptr() + w_off * nb_ * t.element_size()
+    if st_logps is not None:
+        sizes1 = _sizes_or_single(branches, A)
+        if sum(sizes1) != A:
+            raise ValueError(f"rollout_policy: branches {sizes1} do not add up to the {A} rows of the policy head")
+        tab, nbr = _branch_table(sizes1)
+        _check_logps_table(st_logps, st_values, A)
+        am = 0 if action_mask is None else _mask_words(action_mask, W, A, "rollout_policy", device=False).data_ptr()
+        _lib.check(lib.etm_rollout_policy_branched_logps(_ptr(h2), _ptr(h_bias), _ptr(policy_head.weight), _ptr(policy_head.bias),
+                                                         _ptr(value_head.weight), _ptr(value_head.bias), off(uniforms), off(forced),
+                                                         _ptr(t_dev), _ptr(actions), off(st_actions), off(st_logp),
+                                                         st_values.data_ptr() + w_off * st_values.element_size(), ha, hf, _ptr(sync), W,
+                                                         hid, stage_w, tab, nbr, am,
+                                                         st_logps.data_ptr() + w_off * A * st_logps.element_size(), _stream()),
+                   "etm_rollout_policy_branched_logps")
+        return
     if action_mask is not None:
         tab, nbr = _branch_table(_sizes_or_single(branches, A))
         am = _mask_words(action_mask, W, A, "rollout_policy", device=False)
@@ -1059,7 +1099,7 @@ def rollout_trxl_supported(D, H, L, hid, A, nb, gaussian=False):
 
 def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head, uniforms, forced, t_dev, actions, st_actions, st_logp,
                  st_values, scratch, host_actions=None, host_flag=None, w_off=0, tail=None, h_bias=None, window=None, branches=None, box=None,
-                 action_mask=None, st_means=None):
+                 action_mask=None, st_means=None, st_logps=None):
     """Transformer + hidden / output heads + sampling of one rollout step of a worker group in one launch (etm_rollout_trxl).
     ``fused``: the transposed fixed-address weight copies of ``ActorCriticModel.refresh_rollout_weights`` (dict with the host
     pointer table ``blocks``); ``kv`` the group's K | V cache [W, T, blocks, 2D]; ``scratch`` from ``rollout_trxl_scratch``; the
@@ -1074,10 +1114,14 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
     ``action_mask`` (optional, categorical policies): int64 [W] words of this group's workers, device or pinned host memory (read in
     place at the start of the launch), as in ``rollout_sample`` (etm_rollout_trxl_branched_masked / _group_branched_masked).
     ``st_means`` (optional, Box policy only): the means' staging table as in ``rollout_policy_gaussian``
-    (etm_rollout_trxl_gaussian_means / _group_gaussian_means)."""
+    (etm_rollout_trxl_gaussian_means / _group_gaussian_means).
+    ``st_logps`` (optional, categorical policies only): the log-probs' staging table as in ``rollout_policy``
+    (etm_rollout_trxl_branched_logps / _group_branched_logps, masks or not)."""
     lib = _lib.load()
     if st_means is not None and box is None:
         raise ValueError("rollout_trxl: st_means belongs to a Box policy")
+    if st_logps is not None and box is not None:
+        raise ValueError("rollout_trxl: st_logps belongs to a categorical policy")
     h_in = _f32c(h_in, "h_in")
     h_splits = 0
     if h_bias is not None:        # h_in = [splits, W, D] slice sums of rollout_hidden_partial
@@ -1121,6 +1165,17 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
             int(fused.get("gtrxl", 0)), W, D, fused["H"], L, hid)
     # ``fused`` with the group packings (ActorCriticModel._rfg, "group": True) selects the group form of the kernel: same arguments
     group = bool(fused.get("group"))
+    if st_logps is not None:
+        sizes1 = _sizes_or_single(branches, A)
+        if sum(sizes1) != A:
+            raise ValueError(f"rollout_trxl: branches {sizes1} do not add up to the {A} rows of the policy head")
+        tab, nbr = _branch_table(sizes1)
+        _check_logps_table(st_logps, st_values, A)
+        am = 0 if action_mask is None else _mask_words(action_mask, W, A, "rollout_trxl", device=False).data_ptr()
+        entry, name = ((lib.etm_rollout_trxl_group_branched_logps, "etm_rollout_trxl_group_branched_logps") if group
+                       else (lib.etm_rollout_trxl_branched_logps, "etm_rollout_trxl_branched_logps"))
+        _lib.check(entry(*args, stage_w, tab, nbr, am, st_logps.data_ptr() + w_off * A * st_logps.element_size(), _stream()), name)
+        return
     if action_mask is not None:
         if box is not None:
             raise ValueError("rollout_trxl: a Box policy has no action mask")
@@ -2144,10 +2199,19 @@ def arena_digest(x, out=None, partial=None, n_partial=ARENA_DIGEST_PARTIALS):
     return out
 
 
+def _check_old_logps(old_logps, N, cols, what):
+    """The ``old_logps=`` argument of the loss ops: the minibatch's rows of the rollout's log-prob table, float32 [N, >= cols] on the
+    device with contiguous rows (any row stride)."""
+    _need_dev(old_logps)
+    if (old_logps.dtype != torch.float32 or old_logps.dim() != 2 or old_logps.shape[0] != N or old_logps.shape[1] < cols
+            or old_logps.stride(1) != 1):
+        raise ValueError(f"{what}: old_logps must be float32 [{N}, {cols}] with contiguous rows, got {tuple(old_logps.shape)} {old_logps.dtype}")
+
+
 class _PpoLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, value, actions, old_logp, adv, old_value, stats3, branch, n_branches, clip, vf_coef, beta,
-                include_value, dyn=None, action_mask=None, mask_shift=0):
+                include_value, dyn=None, action_mask=None, mask_shift=0, old_logps=None, logps_off=0):
         lib = _lib.load()
         _need_dev(logits, value, actions, old_logp, adv, old_value, stats3)
         logits = _f32c(logits, "logits")
@@ -2168,7 +2232,14 @@ class _PpoLossFn(torch.autograd.Function):
                 _ptr(old_value), _ptr(value), _ptr(stats3), float(clip), float(vf_coef), float(beta),
                 1.0 / (N * n_branches), 1.0 / N, 1.0 / N, 1 if include_value else 0, _ptr(out8), _ptr(d_logits),
                 _ptr(d_value), _ptr(ws), nbytes, _ptr(dyn), N, A)
-        if action_mask is None:
+        if old_logps is not None:
+            # the exact KL: this branch's columns [logps_off, logps_off + A) of the rollout's log-prob rows; stats[4] is then the
+            # branch's exact KL (masks or not)
+            _check_old_logps(old_logps, N, int(logps_off) + A, "ppo_loss")
+            am = 0 if action_mask is None else _mask_words(action_mask, N, int(mask_shift) + A, "ppo_loss").data_ptr()
+            rc = lib.etm_ppo_loss_kl(*args, am, int(mask_shift), old_logps.data_ptr(), old_logps.stride(0) if N > 1 else old_logps.shape[1],
+                                     int(logps_off), _stream())
+        elif action_mask is None:
             rc = lib.etm_ppo_loss(*args, _stream())
         else:        # this branch's actions are bits [mask_shift, mask_shift + A) of the samples' words
             am = _mask_words(action_mask, N, int(mask_shift) + A, "ppo_loss")
@@ -2183,10 +2254,10 @@ class _PpoLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_stats):
         if g_loss is None:
-            return (None,) * 16
+            return (None,) * 18
         d_logits, d_value = ctx.saved_tensors
         gv = d_value * g_loss if ctx.include_value else None
-        return (d_logits * g_loss, gv) + (None,) * 14
+        return (d_logits * g_loss, gv) + (None,) * 16
 
 
 class _HeadsLossFn(torch.autograd.Function):
@@ -2197,7 +2268,7 @@ class _HeadsLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn, unit_grad,
-                sizes=None, log_std=None, action_mask=None, old_mean=None, old_log_std=None):
+                sizes=None, log_std=None, action_mask=None, old_mean=None, old_log_std=None, old_logps=None):
         lib = _lib.load()
         _need_dev(h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3)
         h = _f32c(h, "h")
@@ -2207,8 +2278,13 @@ class _HeadsLossFn(torch.autograd.Function):
         gm_p, gm_v = torch.empty_like(pre_p), torch.empty_like(pre_v)
         gauss = log_std is not None
         kl = old_mean is not None           # Box with the exact KL statistic: the row carries the KL sum behind d log_std
+        ckl = old_logps is not None         # categorical with the exact KL statistic: the row carries the KL sum at its very end
+        if ckl and gauss:
+            raise ValueError("heads_ppo_loss: old_logps belongs to a categorical policy")
         if kl:
             row, nbytes = lib.etm_heads_loss_gaussian_kl_row_floats(hid, A), lib.etm_heads_loss_gaussian_kl_workspace_bytes(N, hid, A)
+        elif ckl:
+            row, nbytes = lib.etm_heads_loss_kl_row_floats(hid, A), lib.etm_heads_loss_kl_workspace_bytes(N, hid, A)
         elif gauss:
             row, nbytes = lib.etm_heads_loss_gaussian_row_floats(hid, A), lib.etm_heads_loss_gaussian_workspace_bytes(N, hid, A)
         else:
@@ -2242,6 +2318,18 @@ class _HeadsLossFn(torch.autograd.Function):
                                              _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
                                              float(vf_coef), float(beta), 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
                                              _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, A, _stream())
+        elif ckl:
+            # the exact categorical KL: the minibatch's rows of the rollout's log-prob table (rows of any stride), masks or not
+            _check_old_logps(old_logps, N, A, "heads_ppo_loss")
+            am = 0 if action_mask is None else _mask_words(action_mask, N, A, "heads_ppo_loss").data_ptr()
+            lp_args = (am, old_logps.data_ptr(), old_logps.stride(0) if N > 1 else old_logps.shape[1], _stream())
+            if sizes is None:
+                rc = lib.etm_heads_loss_kl(*common, 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8),
+                                           0, 0, _ptr(ws), nbytes, N, hid, A, *lp_args)
+            else:
+                tab, nbr = _branch_table(sizes)
+                rc = lib.etm_heads_loss_branched_kl(*common, 1.0 / (N * nbr), 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
+                                                    _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, tab, nbr, *lp_args)
         elif action_mask is not None:
             # invalid-action masks: the samples' words, Discrete or MultiDiscrete (wb / bb concatenated as below)
             am = _mask_words(action_mask, N, A, "heads_ppo_loss")
@@ -2273,7 +2361,7 @@ class _HeadsLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_stats):
         if g_loss is None:
-            return (None,) * 24
+            return (None,) * 25
         h, wlp, wlv, gm_p, gm_v, sums = ctx.saved_tensors
         hid, A = ctx.dims
         unit = ctx.unit                 # the caller promises loss.backward() on the returned loss itself: g_loss == 1, nothing to scale
@@ -2292,7 +2380,7 @@ class _HeadsLossFn(torch.autograd.Function):
         o = (3 + A) * hid
         return (dh, dwlp, s[:hid], dwlv, s[hid:2 * hid], s[3 * hid:o].view(A, hid), s[o:o + A], s[2 * hid:3 * hid].view(1, hid),
                 s[o + A:o + A + 1], None, None, None, None, None, None, None, None, None, None, None,
-                s[o + A + 6:o + 2 * A + 6] if ctx.gauss else None, None, None, None)
+                s[o + A + 6:o + 2 * A + 6] if ctx.gauss else None, None, None, None, None)
 
 
 def _branch_list(branch):
@@ -2342,14 +2430,18 @@ def heads_ppo_loss_gaussian(h, lin_policy, lin_value, mean_head, log_std, value_
 
 
 def heads_ppo_loss(h, lin_policy, lin_value, branch, value_head, actions, old_logp, adv, old_value, clip, vf_coef, beta, stats3=None, dyn=None,
-                   unit_grad=False, action_mask=None):
+                   unit_grad=False, action_mask=None, old_logps=None):
     """model.py:101-110 + the PPO loss of ``ppo_loss``, from the transformer output ``h`` [N, D]: -> (loss scalar with grad, stats[6]).
     ``branch``: the policy branch, or the list of branches of a MultiDiscrete policy (``actions`` / ``old_logp`` [N, B]; the semantics of
     ``ppo_loss`` over branches).  ``unit_grad=True``: the caller runs ``backward()`` on the returned loss itself (upstream gradient 1):
     no scaling launches, weight gradients of the hidden heads deferrable.  See _HeadsLossFn.
     ``action_mask`` (optional): int64 [N] device words, bit j = column j of the concatenated branch heads was allowed when the sample
     was drawn: per branch the log-sum-exp, log-prob and entropy run over the valid actions only and the logits of the others get a
-    zero gradient (etm_heads_loss_masked / _branched_masked); None = exactly the calls without masks."""
+    zero gradient (etm_heads_loss_masked / _branched_masked); None = exactly the calls without masks.
+    ``old_logps`` (optional): float32 [N, sum A_b], every column's log-prob under the policy that drew the samples (the rollout's
+    ``st_logps`` rows of the minibatch); stats[4] is then the exact KL(old || new) of the categoricals, the mean over samples and
+    branches, instead of the k3 sample estimate, in the same launch and with every other output unchanged in its bits
+    (etm_heads_loss_kl / _branched_kl, masks or not); None = exactly the call without."""
     if stats3 is None:
         stats3 = adv_stats(adv)
     if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
@@ -2363,26 +2455,33 @@ def heads_ppo_loss(h, lin_policy, lin_value, branch, value_head, actions, old_lo
         sizes = tuple(int(b.weight.shape[0]) for b in br)
     loss, st = _HeadsLossFn.apply(h, lin_policy.weight, lin_policy.bias, lin_value.weight, lin_value.bias, wb, bb,
                                   value_head.weight, value_head.bias, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn,
-                                  unit_grad, sizes, None, action_mask)
+                                  unit_grad, sizes, None, action_mask, None, None, old_logps)
     return loss, st[:6]
 
 
-def ppo_loss(logits_list, value, actions, old_logp, adv, old_value, clip, vf_coef, beta, stats3=None, dyn=None, action_mask=None):
+def ppo_loss(logits_list, value, actions, old_logp, adv, old_value, clip, vf_coef, beta, stats3=None, dyn=None, action_mask=None,
+             old_logps=None):
     """PPO loss over all action branches.  Returns (loss scalar with grad, stats[6] device tensor in trainer.py:318-323 order).
     ``dyn``: optional float64 device tensor (clip, beta) read by the kernels at run time instead of the two scalars.
     ``action_mask`` (optional): int64 [N] device words as in ``heads_ppo_loss``; branch b reads its bits at the offset of its logits
-    among the concatenated branches (etm_ppo_loss_masked); None = exactly the calls without masks."""
+    among the concatenated branches (etm_ppo_loss_masked); None = exactly the calls without masks.
+    ``old_logps`` (optional): float32 [N, sum A_b], every column's log-prob under the policy that drew the samples; branch b reads its
+    columns at the same offset, and stats[4] is the exact KL(old || new), the mean over samples and branches, instead of the k3
+    sample estimate -- every other output unchanged in its bits (etm_ppo_loss_kl, masks or not); None = exactly the calls without."""
     if stats3 is None:
         stats3 = adv_stats(adv)
     if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
         raise TypeError("ppo_loss: dyn must be a float64 device tensor (clip, beta)")
     nb = len(logits_list)
-    if action_mask is not None:
+    if action_mask is not None or old_logps is not None:
         shifts, total = [], 0
         for lg in logits_list:
             shifts.append(total)
             total += int(lg.shape[1])
-        mk = lambda b: (action_mask, shifts[b])
+        if old_logps is not None:      # (the mask shift and the column offset of a branch are the same number)
+            mk = lambda b: (action_mask, shifts[b] if action_mask is not None else 0, old_logps, shifts[b])
+        else:
+            mk = lambda b: (action_mask, shifts[b])
     else:
         mk = lambda b: ()
     loss, st = _PpoLossFn.apply(logits_list[0], value, actions, old_logp, adv, old_value, stats3, 0, nb, clip, vf_coef, beta, True, dyn, *mk(0))

@@ -50,7 +50,7 @@ from etm import ops
 from etm.ops import WindowSpec
 from etm.optim import AdaptiveLr, FlatAdamW, KlGate
 from model import ActorCriticModel, IndexedObservations
-from utils import (adaptive_lr_section, kl_estimator_section, normalization_section, polynomial_decay, process_episode_info, target_kl_rows,
+from utils import (adaptive_lr_section, exact_kl_section, kl_estimator_section, normalization_section, polynomial_decay, process_episode_info, target_kl_rows,
                    target_kl_section)
 from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
 from checkpoint import check_checkpoint_config, segment_first_worker_id
@@ -273,11 +273,31 @@ def check_kl_estimator_config(config, box: bool = False, world: int = 1):
     if not box:
         raise ValueError("kl_estimator: analytic without a Box (continuous) action space: the exact KL is built for diagonal Gaussian "
                          "policies only (a categorical policy's would need every old logit stored); categorical policies keep k3: "
-                         "remove the key")
+                         "remove the key, or replace it with `exact_kl: true` (the exact KL of every policy kind)")
     if world > 1:
         raise ValueError("kl_estimator: analytic in a data-parallel run: every rank would see the KL of its own minibatch (agreeing on one "
                          "KL over the ranks is not built); remove the key, or train on one device")
     return kind
+
+
+def check_exact_kl_config(config, box: bool = False, world: int = 1) -> bool:
+    """The optional key ``exact_kl`` (utils.exact_kl_section) -> False (absent or ``false``: nothing is allocated, no launch is added
+    or exchanged) or True: the statistic ``kl`` -- what ``other/kl`` shows and what ``target_kl`` and ``adaptive_lr`` decide on -- is the
+    exact KL(old || new) of the rollout's and the current policy for EVERY policy kind.  For a Box policy (``box``) that is exactly
+    ``kl_estimator: analytic``; for Discrete and MultiDiscrete policies, masked or not, the four categorical sampling sites stage
+    every column's log-prob and the loss kernels reduce ``utils.categorical_kl``.  Refused, each before anything is built and each
+    with what to do instead: a value that is no bool; ``exact_kl: true`` next to an explicit ``kl_estimator: k3`` (they contradict
+    each other); the key in a data-parallel run (``world`` > 1), as for the other KL keys."""
+    on = exact_kl_section(config)
+    if not on:
+        return False
+    if "kl_estimator" in config and kl_estimator_section(config) == "k3":
+        raise ValueError("exact_kl: true next to kl_estimator: k3: the two keys contradict each other (k3 is the sample estimate); "
+                         "remove kl_estimator for the exact KL, or remove exact_kl to keep the sample estimate")
+    if world > 1:
+        raise ValueError("exact_kl: true in a data-parallel run: every rank would see the KL of its own minibatch (agreeing on one "
+                         "KL over the ranks is not built); remove the key, or train on one device")
+    return True
 
 
 def time_major(table, src):
@@ -325,6 +345,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         adapt_cfg = check_adaptive_lr_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         # (a supplied environment says what the policy is once it is looked at, below; else the config does, before anything is built)
         check_kl_estimator_config(config, env is not None or check_box_policy(config) is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
+        check_exact_kl_config(config, check_box_policy(config) is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
         # training state that a checkpoint carries over (trainer_parts._CheckpointResume): completed updates, the training segment (the
         # number of resumes so far; its environments' worker ids start at segment_first_worker_id), the last episodes' infos
         self.update_index, self.segment, self._episode_infos = 0, 0, deque(maxlen=100)
@@ -421,6 +442,11 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # kl_estimator: the kind of policy is known now.  "analytic": the four Gaussian sampling sites stage the means, the buffer
         # carries them and a snapshot of the log-std, the Gaussian heads + loss kernel reduces the exact KL into stats[4]
         self._kl_analytic = check_kl_estimator_config(config, self.box is not None, 1 if dp is None else int(getattr(dp, "world", 1))) == "analytic"
+        # exact_kl: a Box policy takes exactly that path; a categorical one (masked or not) stages every column's log-prob at the four
+        # categorical sampling sites, the buffer carries the rows, the categorical loss kernels reduce the exact KL into stats[4]
+        exact = check_exact_kl_config(config, self.box is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
+        self._kl_analytic = self._kl_analytic or (exact and self.box is not None)
+        self._kl_exact_cat = exact and self.box is None
 
         if config.get("tunable_gemm", os.environ.get("ETM_TUNABLE_GEMM", "1") != "0"):
             # let PyTorch pick the fastest hipBLASLt / rocBLAS solution per GEMM shape (the small [N, D] x [D, D] products around
@@ -544,6 +570,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         }
         if self._kl_analytic:       # (the means next to the actions; _finish_rollout moves every staging table into the buffer's field)
             self._stage["means"] = torch.zeros((S, W, B), dtype=torch.float32, device=device)
+        if self._kl_exact_cat:      # (every column's log-prob of every branch next to the actions; into the buffer's old_logps likewise)
+            self._stage["logps"] = torch.zeros((S, W, sum(self.action_space_shape)), dtype=torch.float32, device=device)
         self._mask_t = torch.zeros((W, L), dtype=torch.bool, device=device)
         self._win_t = torch.zeros((W, L), dtype=torch.int64, device=device)
         self._act_dev = torch.zeros((W, B), dtype=torch.float32 if box else torch.int64, device=device)
@@ -967,8 +995,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             self.last_valid_action_share = valid_action_share(buf.action_masks_host, sum(self.action_space_shape))
         self._step_dev.copy_(self._step_pin, non_blocking=True)
         self._slot_dev.copy_(self._slot_pin, non_blocking=True)
-        for name, stage in self._stage.items():
-            getattr(buf, name).copy_(stage.transpose(0, 1))
+        for name, stage in self._stage.items():      # (the buffer's field has the table's name; the log-prob rows are its old_logps)
+            getattr(buf, "old_logps" if name == "logps" else name).copy_(stage.transpose(0, 1))
         if plan.direct_rows:
             self._stage_read.record(main)          # the next rollout's host writes into the staging array wait for this
         if forced_wsb is not None:
@@ -1071,6 +1099,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         box = None if self.box is None else (m.policy_log_std, self.box.low, self.box.high)
         draws = self._uniforms if box is None else self._normals
         means = {"st_means": st["means"]} if self._kl_analytic else {}      # (kl_estimator: analytic; else exactly the calls of ever)
+        logps = {"st_logps": st["logps"]} if self._kl_exact_cat else {}     # (exact_kl, categorical; likewise)
         mask_t, win_t = g.mask_t, g.win_t
         # streamed + pipelined mode: the (step, slot) block is read from pinned host memory (see rollout_plan.plan_rollout)
         ss_src = g.ss_pin if stream_obs and g.stream is not None else g.ss_dev
@@ -1092,7 +1121,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                              g.rf_scratch, host_actions=g.act_pin, host_flag=flag_pin, w_off=g.lo,
                              tail=tail, h_bias=h_bias, branches=branches, box=box,
                              window=(ss_src, self._mask_table, self._index_table, st["memory_mask"], st["memory_indices"],
-                                     g.ss_latch, g.t_row, self._kv_init), action_mask=am_src, **means)
+                                     g.ss_latch, g.t_row, self._kv_init), action_mask=am_src, **means, **logps)
             return g.item
         # window lookup + staging; the same launch records the staging row of this step for the tail (t_dev is incremented by
         # the sampling kernel) and resets the K/V cache of workers at episode step 0 (they start from the projection of an
@@ -1115,7 +1144,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                 ops.rollout_policy(h2, policy_head, m.value, self._uniforms, self._forced_tab, g.t_dev,
                                    g.act_dev, st["actions"], st["log_probs"], st["values"],
                                    host_actions=g.act_pin, host_flag=flag_pin, h_bias=m._b_heads, w_off=g.lo, branches=branches,
-                                   action_mask=am_src)
+                                   action_mask=am_src, **logps)
         else:
             if kv_spec is not None:
                 logits, value, item = m.forward_logits_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, obs_rows=rows)
@@ -1133,7 +1162,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                                             st["values"], low=box[1], high=box[2], **means)
             else:
                 ops.rollout_sample(lg, value, self._uniforms, self._forced_tab, g.t_dev, g.act_dev,
-                                   st["actions"], st["log_probs"], st["values"], branches=branches, action_mask=am_src)
+                                   st["actions"], st["log_probs"], st["values"], branches=branches, action_mask=am_src, **logps)
             g.act_pin.copy_(g.act_dev, non_blocking=True)
         if item.data_ptr() != g.item.data_ptr():
             g.item.copy_(item)
@@ -1470,20 +1499,22 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             return ops.heads_ppo_loss_gaussian(h, m.lin_policy, m.lin_value, m.policy_branches[0], m.policy_log_std, m.value, mb["actions"],
                                                mb["log_probs"], mb["advantages"], mb["values"], clip_range, self.config["value_loss_coefficient"],
                                                beta, stats3, dyn=dyn, unit_grad=True, **old)
+        # exact_kl (categorical): the minibatch's rows of the rollout's log-probs; stats[4] is then the exact KL on all three routes
+        old = dict(old_logps=mb["old_logps"]) if self._kl_exact_cat else {}
         if self.config.get("fused_heads_loss", True):
             h, _ = m.forward_state(obs, spec)
             branch = m.policy_branches[0] if len(m.policy_branches) == 1 else list(m.policy_branches)
             if ops.heads_loss_supported(h, m.lin_policy, branch):
                 return ops.heads_ppo_loss(h, m.lin_policy, m.lin_value, branch, m.value, mb["actions"], mb["log_probs"],
                                           mb["advantages"], mb["values"], clip_range, self.config["value_loss_coefficient"], beta, stats3, dyn=dyn,
-                                          unit_grad=True, action_mask=mb.get("action_masks"))       # (both callers run loss.backward() on this loss)
+                                          unit_grad=True, action_mask=mb.get("action_masks"), **old)       # (both callers run loss.backward() on this loss)
             h_policy = ops.linear_relu(m.lin_policy, h)
             h_value = ops.linear_relu(m.lin_value, h)
             logits, value = [br(h_policy) for br in m.policy_branches], m.value(h_value).reshape(-1)
         else:
             logits, value, _ = m.forward_logits(obs, spec, want_items=False)
         return ops.ppo_loss(logits, value, mb["actions"], mb["log_probs"], mb["advantages"], mb["values"], clip_range,
-                            self.config["value_loss_coefficient"], beta, stats3, dyn=dyn, action_mask=mb.get("action_masks"))
+                            self.config["value_loss_coefficient"], beta, stats3, dyn=dyn, action_mask=mb.get("action_masks"), **old)
 
     def _dw_destinations(self):
         """{parameter data_ptr: its gradient view in the flat arena}: the [out, in] views of the 2-D parameters for the grouped weight-

@@ -3,7 +3,9 @@ process_episode_info, Module; normalization_section reads this build's two norma
 stop, target_kl_rows says which rows of an update's result tables a stopped update returns; adaptive_lr_section reads the
 KL-adaptive learning rate and adaptive_lr_step is its rule, the one host definition of what the norm kernel decides;
 kl_estimator_section reads which KL both rules see and gaussian_kl is the exact KL of a Box policy's Gaussians, the one host
-definition of what the Gaussian heads + loss kernel reduces."""
+definition of what the Gaussian heads + loss kernel reduces; exact_kl_section reads the key that switches the exact KL on for every
+policy kind and categorical_kl is the exact KL of Discrete / MultiDiscrete policies, the one host definition of what the categorical
+loss kernels reduce."""
 import numpy as np
 import torch
 from torch import nn
@@ -232,6 +234,60 @@ def gaussian_kl(old_mean, old_log_std, mean, log_std, dtype=np.float64):
     q = (mo - mu) / np.exp(ls)
     per_sample = const + (dt(0.5) * q * q).sum(axis=1, dtype=dt)
     return dt(per_sample.sum(dtype=dt) / dt(mo.shape[0]))
+
+
+def exact_kl_section(config: dict) -> bool:
+    """The optional key ``exact_kl`` -> False (absent or ``false``: the KL statistic is what ``kl_estimator`` says, the k3 sample
+    estimate by default) or True (the exact KL(old || new) of every policy kind: ``gaussian_kl`` for a Box policy, ``categorical_kl``
+    for Discrete and MultiDiscrete ones, masked or not).  A value that is no bool is refused."""
+    value = config.get("exact_kl", False)
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"exact_kl must be true or false, got {value!r}; write `exact_kl: true` for the exact KL of the rollout's and "
+                         "the current policy, or remove the key for the sample estimate")
+    return bool(value)
+
+
+def categorical_kl(old_logps, logits, sizes, mask_words=None, dtype=np.float64):
+    """Exact KL(old || new) of categorical policies, the mean over the N samples AND the B branches (the convention of the k3 column it
+    replaces; the joint KL of a sample's branches is B times it), in numpy ``dtype`` -- the one host definition of what the categorical
+    loss kernels reduce (etm_categorical_kl_term; csrc/heads_loss.hip, csrc/ppo_loss.hip).  ``old_logps`` [N, sum(sizes)]: every
+    column's log-prob under the policy that drew the samples (-inf where the column was masked out); ``logits`` [N, sum(sizes)]: the
+    current raw logits, the branches' segments side by side; ``mask_words`` (optional) [N] int64: bit j = column j was allowed.
+    Per sample n and branch b with valid columns V (all of them without masks), with l_j = logit_j - lse_V, d_j = old_j - l_j:
+        KL_nb = sum_{j in V} t_j,   t_j = exp(old_j) (expm1(-d_j) + d_j)  for d_j >= -60,   t_j = exp(l_j)  for d_j < -60
+    -- sum p_old (old - l) with the vanishing sum (p - p_old) added: every term is >= 0 and no term of size 1 cancels, equal policies
+    give exactly 0; below d = -60 the limit p_old -> 0 (the dropped part is under e^-60 |d|, and inf * denormal stays out of the
+    sum).  Columns outside V are skipped, not multiplied (0 * inf); a branch with one valid action contributes 0."""
+    dt = np.dtype(dtype).type
+    lo, lg = np.asarray(old_logps, dtype=dt), np.asarray(logits, dtype=dt)
+    sizes = tuple(int(a) for a in sizes)
+    if lg.ndim != 2 or lo.shape != lg.shape or not sizes or min(sizes) <= 0 or sum(sizes) != lg.shape[1]:
+        raise ValueError(f"categorical_kl: old_logps and logits [N, {sum(sizes)}] for branches {sizes} expected, got {lo.shape}, {lg.shape}")
+    N, A = lg.shape
+    if mask_words is None:
+        valid = np.ones((N, A), dtype=bool)
+    else:
+        if A > 63:
+            raise ValueError(f"categorical_kl: a mask word describes at most 63 columns, not {A}")
+        words = np.asarray(mask_words).astype(np.int64).reshape(-1)
+        if words.shape != (N,):
+            raise ValueError(f"categorical_kl: mask_words [{N}] expected, got {words.shape}")
+        valid = ((words[:, None] >> np.arange(A, dtype=np.int64)[None, :]) & 1).astype(bool)
+    total, off = dt(0), 0
+    with np.errstate(all="ignore"):
+        for size in sizes:
+            v = valid[:, off:off + size]
+            if not v.any(axis=1).all():
+                raise ValueError("categorical_kl: a branch without a valid action")
+            l = np.where(v, lg[:, off:off + size], dt(-np.inf))
+            mx = l.max(axis=1, keepdims=True)
+            logp = l - (mx + np.log(np.exp(l - mx).sum(axis=1, keepdims=True, dtype=dt)))
+            old = lo[:, off:off + size]
+            d = old - logp
+            t = np.where(d >= dt(-60), np.exp(old) * (np.expm1(-d) + d), np.exp(logp))
+            total = dt(total + np.where(v, t, dt(0)).sum(dtype=dt))
+            off += size
+    return dt(total / dt(N * len(sizes)))
 
 
 class Module(nn.Module):

@@ -39,7 +39,8 @@ extern "C" {
  * sentinel of the `uniforms` tables; 53 = + etm_gae_truncated; 54 = + the running-normalisation entries; 55 = + etm_grouped_dw_tile_map;
  * 56 = + etm_arena_digest; 57 = + the gated optimiser pair; 58 = + the *_masked entries of invalid-action masking;
  * 59 = + etm_grad_sqnorm_adaptive; 60 = + etm_block_row_groups; 61 = + the *_gaussian_means sampling entries and
- * etm_heads_loss_gaussian_kl of the exact Gaussian KL). */
+ * etm_heads_loss_gaussian_kl of the exact Gaussian KL; still 61, added without a change to any signature above: the *_logps sampling
+ * entries, etm_heads_loss_kl / etm_heads_loss_branched_kl and etm_ppo_loss_kl of the exact categorical KL). */
 int etm_abi_version(void);
 
 /* Human-readable name for a negative ETM_E* code or a hipError_t. Static storage. */
@@ -249,6 +250,17 @@ int etm_rollout_sample_branched(const float *logits, const float *value, const f
 int etm_rollout_sample_branched_masked(const float *logits, const float *value, const float *uniforms, const int64_t *forced,
                                        int64_t *t_dev, int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W,
                                        const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, void *stream);
+/* The exact categorical KL (`exact_kl: true`; added at ABI 61): the *_logps form of each of the four categorical sampling entries takes
+ * its *_branched_masked twin's arguments with action_mask OPTIONAL (NULL: no masks -- then the unmasked twin's refusals hold) and
+ * st_logps before the stream: [S, W, sum sizes] (or [S, stage_W, sum sizes] at this group's first worker) next to st_actions.  It
+ * receives l_j - lse of every column of every branch of the row -- the policy's distribution whether the action was sampled, taken
+ * greedily (u < 0) or forced; exactly -inf for a masked-out column; at the taken action the st_logp entry's bits (the same expression
+ * with the same lse).  Every other output is the twin's, bit for bit.  A Discrete policy is one branch.  ETM_EINVAL: NULL or
+ * 4-byte-misaligned st_logps. */
+int etm_rollout_sample_branched_logps(const float *logits, const float *value, const float *uniforms, const int64_t *forced,
+                                      int64_t *t_dev, int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W,
+                                      const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, float *st_logps,
+                                      void *stream);
 /* Box policies (ABI 49): a diagonal Gaussian over A <= 8 dimensions.  mean [W, A] = the policy head's outputs; x = mean + exp(log_std)
  * normals[*t_dev, w] (log_std [A] on the device; normals / forced / st_actions time-major [S, W, A]; a forced row entry that is not NaN
  * replaces the draw of its dimension); st_logp[*t_dev, w] = log p(x) = sum_a [-((x_a - mean_a) / sigma_a)^2 / 2 - log sigma_a - log(2 pi) / 2]
@@ -381,6 +393,33 @@ int etm_heads_loss_branched_masked(const float *pre_p, const float *pre_v, const
                                    float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
                                    float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
                                    const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, void *stream);
+/* The exact categorical KL (added at ABI 61): etm_heads_loss_masked / etm_heads_loss_branched_masked with action_mask OPTIONAL (NULL:
+ * no masks) and old_logps [N, A] (row stride old_logps_stride >= A floats; A = sum sizes), every column's log-prob under the policy
+ * that drew the samples (the *_logps sampling entries).  The same launch also reduces KL(old || new): per sample n and branch b with
+ * valid columns V, KL_nb = sum_{j in V} t_j, t_j = p_old_j (expm1(-d_j) + d_j) for d_j = old_logp_j - logp_j >= -60, t_j = p_j below
+ * (the limit p_old_j -> 0); every term >= 0, no term of size 1 cancels, equal policies give exactly 0, a masked-out column is skipped,
+ * a branch with one valid action contributes 0.  out8[4] = pol_scale sum_n sum_b KL_nb (pol_scale = 1 / (N B): the mean over samples
+ * AND branches, the convention of the k3 value; the joint KL is B times it), out8[6] = the k3 value that the twin puts into out8[4].
+ * A statistic only: the loss, gm_p, gm_v, out8[0..3], out8[5] and the twin's row are the twin's bit for bit; sums
+ * [etm_heads_loss_kl_row_floats = etm_heads_loss_row_floats + 1] carries the raw KL sum as its last element.  ETM_EINVAL: NULL or
+ * 4-byte-misaligned old_logps, old_logps_stride < A; ETM_EUNSUPPORTED exactly where the twin returns it. */
+int etm_heads_loss_kl_row_floats(int hid, int A);
+int64_t etm_heads_loss_kl_workspace_bytes(int N, int hid, int A);
+int etm_heads_loss_kl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb, const float *bb,
+                      const float *wv, const float *bv, const int64_t *actions, int64_t action_stride, const float *old_logp,
+                      int64_t logp_stride, const float *adv, const float *old_value, const float *adv_stats3, double clip, float vf_coef,
+                      float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p,
+                      float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes,
+                      int N, int hid, int A, const int64_t *action_mask, const float *old_logps, int64_t old_logps_stride,
+                      void *stream);
+int etm_heads_loss_branched_kl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                               const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
+                               const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
+                               const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                               float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
+                               float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
+                               const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, const float *old_logps,
+                               int64_t old_logps_stride, void *stream);
 /* Box policies (ABI 49): the same pass for a diagonal Gaussian (A <= 8): wb / bb = the mean head; xact [N, A] (row stride
  * action_stride >= A) the stored raw float actions; log_std [A]; old_logp [N] (logp_stride).  Per sample one ratio of the joint
  * log-probs; d log p / d mean_a = (x_a - mean_a) / sigma_a^2, d log p / d log sigma_a = ((x_a - mean_a) / sigma_a)^2 - 1, the entropy
@@ -549,6 +588,12 @@ int etm_rollout_policy_branched_masked(const float *h, const float *h_bias, cons
                                        int64_t *st_actions, float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag,
                                        int32_t *sync_counter, int W, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,
                                        const int64_t *action_mask, void *stream);
+/* (added at ABI 61) with every column's log-prob staged, see etm_rollout_sample_branched_logps */
+int etm_rollout_policy_branched_logps(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv,
+                                      const float *bv, const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions,
+                                      int64_t *st_actions, float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag,
+                                      int32_t *sync_counter, int W, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,
+                                      const int64_t *action_mask, float *st_logps, void *stream);
 /* Box policies (ABI 49): wp / bp = the mean head [A, hid], [A]; the draw of etm_rollout_sample_gaussian (normals / forced / st_actions
  * [S, stage_W, A]); actions and host_actions (pinned, optional) [W, A] receive the clipped actions, host_actions before the flag. */
 int etm_rollout_policy_gaussian(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv, const float *bv,
@@ -697,6 +742,32 @@ int etm_rollout_trxl_group_branched_masked(const float *h_in, const float *wemb_
                                     uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H,
                                     int L, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,
                                     const int64_t *action_mask, void *stream);
+/* (added at ABI 61) with every column's log-prob staged, see etm_rollout_sample_branched_logps: the sampling thread stores the columns
+ * as it draws (measured against storing them behind the action's hand-over, which was not faster); the shapes of the predicates above */
+int etm_rollout_trxl_branched_logps(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
+                                    int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
+                                    const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
+                                    const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
+                                    float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
+                                    float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
+                                    const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride,
+                                    int64_t bank_block_stride, const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table,
+                                    const int64_t *index_table, uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row,
+                                    uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H,
+                                    int L, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,
+                                    const int64_t *action_mask, float *st_logps, void *stream);
+int etm_rollout_trxl_group_branched_logps(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
+                                    int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
+                                    const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
+                                    const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
+                                    float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
+                                    float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
+                                    const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride,
+                                    int64_t bank_block_stride, const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table,
+                                    const int64_t *index_table, uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row,
+                                    uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H,
+                                    int L, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,
+                                    const int64_t *action_mask, float *st_logps, void *stream);
 /* Box forms of the two step kernels (ABI 49): the arguments of etm_rollout_trxl / etm_rollout_trxl_group with log_std [A] after bv,
  * float normals / forced / actions / st_actions / host_actions in place of uniforms / forced / actions / st_actions / host_actions (the
  * layouts of etm_rollout_policy_gaussian) and the HOST bound arrays low / high after stage_W; wp / bp = the mean head.  Shapes: the
@@ -1113,6 +1184,18 @@ int etm_ppo_loss_masked(const float *logits, const int64_t *actions, int64_t act
                         float beta, float pol_scale, float ent_scale, float val_scale, int include_value, float *out8, float *d_logits,
                         float *d_value, void *partials, int64_t partials_bytes, const double *dyn_clip_beta, int N, int A,
                         const int64_t *action_mask, int mask_shift, void *stream);
+/* The exact categorical KL (added at ABI 61) of one branch: etm_ppo_loss_masked with action_mask OPTIONAL (NULL: no masks, mask_shift
+ * ignored) and old_logps [N, rows of old_logps_stride floats] (the *_logps sampling entries' rows), the branch's A columns starting at
+ * column logps_off.  out8[4] = pol_scale sum_n KL_n (the rule of etm_heads_loss_kl), out8[6] = the k3 value; the loss, d_logits,
+ * d_value, out8[0..3], out8[5] and partial slots 0..4 are those of the twin's one-sample-per-thread form, bit for bit; slot 5 of a
+ * workgroup's 8 partial floats carries its raw KL sum.  ETM_EINVAL: NULL or 4-byte-misaligned old_logps, logps_off < 0,
+ * old_logps_stride < logps_off + A; otherwise the twin's refusals. */
+int etm_ppo_loss_kl(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp, int64_t logp_stride,
+                    const float *adv, const float *old_value, const float *value, const float *adv_stats3, double clip, float vf_coef,
+                    float beta, float pol_scale, float ent_scale, float val_scale, int include_value, float *out8, float *d_logits,
+                    float *d_value, void *partials, int64_t partials_bytes, const double *dyn_clip_beta, int N, int A,
+                    const int64_t *action_mask, int mask_shift, const float *old_logps, int64_t old_logps_stride, int logps_off,
+                    void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Gradient exchange of the data-parallel optimiser step (absent upstream -- the call goes between
