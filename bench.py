@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Throughput bench of the MI355X PPO + TransformerXL path (driver contract: see the repo prompt / DESIGN.md).
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1             # the headline figure and nothing else
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full      # + everything listed under --full below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,12 +11,19 @@ environment steps per GPU on synthetic 3x84x84 observations, GAE, and epochs x n
 on minibatches of 2048 samples (configs/synthetic_minigrid.yaml).  Weak scaling: every rank owns its own 32
 environments; gradients are all-reduced with RCCL.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: the headline (metric, value, unit,
+ms_per_step, ...), config, phase_s_per_step and, from the HIP events that the timed region records anyway:
   roofline     the dominant kernel's achieved rate from HIP events recorded around its launches inside the timed
                region (libetm_hip.so's etm_profile_* facility): the folded window-attention pass against the HBM peak,
                bytes_per_launch = N * L * D * 4 -- or, with --attention dense, the fp32-MFMA
-               contraction against the fp32 MFMA peak of gfx950;
-  rooflines    kernel micro-benchmarks run AFTER the timed region (tools/kernel_rooflines.py): window pass with every byte
+               contraction against the fp32 MFMA peak of gfx950.  (= roofline_train, the optimisation phase's dominant kernel.)
+
+Whatever takes a run of its own is measured with --full only, after the timed region (EXTRAS below):
+  rollout_step the kernels of one rollout step timed eagerly; `roofline` is then picked over ALL modelled kernels, the
+               rollout step kernel among them;
+  allreduce    the gradient all-reduce timed on its own (N > 1 only);
+  value_worker_processes  the same update with the environments in worker processes, a second run of this script (N == 1 only);
+  rooflines   kernel micro-benchmarks run AFTER the timed region (tools/kernel_rooflines.py): window pass with every byte
                from HBM and with the training access pattern, the dense north-star attention kernels against the fp32
                MFMA peak at config 3 and config 5 dims, GAE and PPO loss against the HBM peak at config and scaled sizes;
   cpu_baseline the CPU oracle (oracle/ref_algo.OracleTrainer, a validated restatement of the reference trainer)
@@ -172,6 +180,16 @@ def cpu_baseline(cfg, seed=0):
                       f"{dt:.1f} s (rollout {split['rollout_s']:.1f} s on {roll_threads} torch threads, train {split['train_s']:.1f} s on "
                       f"{threads}) of {cores} host cores"}
 
+# What only a --full run measures, each a run of its own after the timed region: name -> the switch that takes it out of a --full run
+EXTRAS = {"rollout_step": "no_profile", "allreduce": None, "rooflines": "no_rooflines", "worker_processes_run": "no_worker_processes_run",
+          "cpu_baseline": "no_cpu_baseline"}
+
+
+def extras_of(args):
+    """The EXTRAS this run measures: none of them without --full, with it all but the ones switched off."""
+    return {name for name, off in EXTRAS.items() if args.full and not (off and getattr(args, off))}
+
+
 LINE_LIMIT = 8000      # bytes of the ONE stdout line (the driver's parser dropped round 5's 20,013-character line); the full record goes to --full-json
 
 
@@ -301,20 +319,19 @@ def compact_line(full, full_path):
     return text
 
 
-def main():
-    # the contract is ONE JSON line on stdout: whatever the libraries / the trainer print on the way goes to stderr
-    # (at the descriptor level: RCCL / gloo / the HIP runtime print from C)
-    sys.stdout.flush()
-    json_out = os.fdopen(os.dup(1), "w")
-    os.dup2(2, 1)
-    sys.stdout = sys.stderr
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed region")
-    ap.add_argument("--no-rooflines", action="store_true", help="skip the kernel micro-benchmarks after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, after the timed region: the rollout step's kernels timed eagerly "
+                         "(and `roofline` picked over all kernels), the kernel micro-benchmarks, the worker-process run, the CPU baseline, "
+                         "with N > 1 the all-reduce on its own.  Off: the run ends with the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed region (nor, with --full, "
+                                                              "time the rollout step's kernels after it)")
+    ap.add_argument("--no-rooflines", action="store_true", help="--full without the kernel micro-benchmarks after the timed region")
     ap.add_argument("--dist-backend", default=None, help="testing only: torch.distributed backend instead of nccl (= RCCL), e.g. gloo")
     ap.add_argument("--dp-collective", choices=("torch", "etm"), default=None,
                     help="gradient all-reduce through the library's own RCCL communicator (etm, the default: created and self-tested "
@@ -349,7 +366,7 @@ def main():
                     help="side file for the FULL record (per-kernel tables, roofline models, micro-benchmark trees, prose): the stdout line "
                          "is a < 8 KB summary of it")
     ap.add_argument("--no-worker-processes-run", "--no-fresh-obs", dest="no_worker_processes_run", action="store_true",
-                    help="skip the second measurement after the timed region (N == 1 only): the same update with the environments in worker "
+                    help="--full without the second measurement after the timed region (N == 1 only): the same update with the environments in worker "
                          "processes over shared memory (the reference's form), reported as value_worker_processes")
     ap.add_argument("--direct-rows", choices=("on", "off"), default="on",
                     help="in-process environments write the observation rows of a step straight into the staging array in device memory "
@@ -362,7 +379,18 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rollout buffer, sample of the episode memories, loss "
                          "statistics, parameters) as DIR/<name>.npy in float32 (rank 0; at most 64 MB)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    # the contract is ONE JSON line on stdout: whatever the libraries / the trainer print on the way goes to stderr
+    # (at the descriptor level: RCCL / gloo / the HIP runtime print from C)
+    sys.stdout.flush()
+    json_out = os.fdopen(os.dup(1), "w")
+    os.dup2(2, 1)
+    sys.stdout = sys.stderr
+    args = make_parser().parse_args()
+    extras = extras_of(args)
     global CONFIG_NAME
     CONFIG_NAME = args.config
 
@@ -487,7 +515,7 @@ def main():
     # gradient all-reduce on its own (message = 4 * params bytes, bus bandwidth against the xGMI link rate);
     # measured AFTER the timed region, on every rank, with the trainer's own flat bucket and collective call
     allreduce = None
-    if dp is not None:
+    if dp is not None and "allreduce" in extras:
         try:
             bucket = trainer.flat_grads
             for _ in range(3):
@@ -546,7 +574,7 @@ def main():
         # ---- the kernels of a rollout step, timed eagerly AFTER the timed region (inside it they run from captured graphs, which
         # take no per-kernel events): average launch time x the launches the timed region made = their share of GPU time
         rollout_step = None
-        if not args.no_profile and trainer is not None:
+        if "rollout_step" in extras and trainer is not None:
             try:
                 import kernel_rooflines
                 rollout_step = kernel_rooflines.rollout_step(trainer)
@@ -684,7 +712,7 @@ def main():
         }
         if dumped:
             out["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped[0], "bytes": dumped[1]}
-        if not args.no_rooflines:
+        if "rooflines" in extras:
             try:
                 import kernel_rooflines
                 trainer.close()
@@ -695,7 +723,7 @@ def main():
             except Exception as exc:       # reporting only: never lose the throughput line over it
                 out["rooflines"] = {"error": repr(exc)}
             trainer = None
-        if world == 1 and not args.no_worker_processes_run and CONFIG_NAME == "synthetic_minigrid" and not cfg.get("worker_processes", False):
+        if world == 1 and "worker_processes_run" in extras and CONFIG_NAME == "synthetic_minigrid" and not cfg.get("worker_processes", False):
             # the other environment form, after the timed region: the same fresh-draw environments stepped in worker processes
             try:
                 if trainer is not None:
@@ -706,7 +734,7 @@ def main():
                 out["value_worker_processes"] = out["worker_processes_run"]["value"]
             except Exception as exc:       # reporting only: never lose the throughput line over it
                 out["worker_processes_run"] = {"error": repr(exc)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and "cpu_baseline" in extras:
             out["cpu_baseline"] = cpu_baseline(cfg)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         full_path = args.full_json

@@ -3078,14 +3078,14 @@ def test_poc_memory_env_learns():
 
 
 def test_bench_prints_one_json_line(tmp_path):
-    """bench.py's contract with the driver, on the DRIVER'S command shape (--gpus 1, micro-benchmarks, fresh-observation run and CPU
-    baseline all ON): rank 0 prints ONE strict-JSON line on stdout, shorter than 8 KB (round 5's 20,013-character line was dropped by
-    the driver's parser), carrying the headline, `roofline`, `cpu_baseline` and `config.workload`; the full record is the side file."""
+    """bench.py's contract with the driver, on the DRIVER'S --full command shape (--gpus 1 --full: micro-benchmarks, fresh-observation run
+    and CPU baseline all ON): rank 0 prints ONE strict-JSON line on stdout, shorter than 8 KB (round 5's 20,013-character line was dropped
+    by the driver's parser), carrying the headline, `roofline`, `cpu_baseline` and `config.workload`; the full record is the side file."""
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     full = tmp_path / "full.json"
-    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full-json", str(full)],
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--full-json", str(full)],
                          capture_output=True, text=True, timeout=1500, cwd=repo)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -3105,3 +3105,30 @@ def test_bench_prints_one_json_line(tmp_path):
     assert rec["value_worker_processes"] > 0 and rec["config"]["env_pool"] == 0          # the default environment draws every observation fresh
     side = json.loads(full.read_text())
     assert side["value"] == pytest.approx(rec["value"], rel=1e-5) and "kernels_train" in side and "rooflines" in side
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """The driver's plain command shape (--gpus 1 --steps N --warmup W, no --full) measures the headline and nothing that takes a run of
+    its own: ONE strict-JSON line with the contract's keys and the roofline of the timed region's own HIP events; no CPU baseline, no
+    micro-benchmarks, no worker-process run, no eager rollout-step timing, on the line or in the side file; --dump-outputs still writes."""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    full, dump = tmp_path / "full.json", tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--full-json", str(full),
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=300, cwd=repo)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[:2000]
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "env-steps/sec (whole node) MinigridMemory 3x84x84" and rec["unit"] == "env-steps/s" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f32" and rec["n_gpus"] == 1 and rec["steps"] == 1 and rec["warmup"] == 1 and rec["value"] > 0
+    assert abs(rec["ms_per_step"] * 1e-3 * rec["value"] - 32 * 512) < 0.01 * 32 * 512
+    assert 0 < rec["roofline"]["frac"] < 1.5 and rec["roofline"]["kernel"] == rec["roofline_train"]["kernel"]
+    side = json.loads(full.read_text())
+    for rec_ in (rec, side):
+        for key in ("cpu_baseline", "speedup_vs_cpu_baseline", "rooflines", "worker_processes_run", "value_worker_processes"):
+            assert key not in rec_, key
+    assert side["rollout_step"] is None and side["allreduce"] is None and side["kernels_train"]
+    assert rec["config"]["env_pool"] == 0
+    assert sorted(f[:-4] for f in os.listdir(dump)) == side["dump_outputs"]["files"] and "rollout_actions" in side["dump_outputs"]["files"]

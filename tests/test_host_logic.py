@@ -684,6 +684,32 @@ def test_bench_line_summary_is_short_strict_json():
     assert len(text.encode()) < 8000 and "rooflines" not in strict(text) and strict(text)["value"] > 0
 
 
+def test_bench_plain_run_measures_no_extras():
+    """bench.py measures what the headline figure does not need (the rollout step's kernels timed eagerly, the all-reduce on its own,
+    the kernel micro-benchmarks, the worker-process run, the CPU baseline) with --full only: a plain run plans none of them whatever
+    else is on the command line, a --full run all of them less the ones its --no-... switches take out; the options that shape the
+    timed steps read the same with and without --full."""
+    import importlib.util
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    every = {"rollout_step", "allreduce", "rooflines", "worker_processes_run", "cpu_baseline"}
+    assert set(bench.EXTRAS) == every
+    parse = bench.make_parser().parse_args
+    plain = ["--gpus", "1", "--steps", "3", "--warmup", "1"]
+    assert parse(plain).full is False
+    assert bench.extras_of(parse(plain)) == set()
+    assert bench.extras_of(parse(plain + ["--dump-outputs", "d", "--full-json", "f.json"])) == set()
+    assert bench.extras_of(parse(plain + ["--no-rooflines", "--no-cpu-baseline", "--no-worker-processes-run", "--no-profile"])) == set()
+    assert bench.extras_of(parse(plain + ["--full"])) == every
+    for switch, gone in (("--no-rooflines", "rooflines"), ("--no-cpu-baseline", "cpu_baseline"), ("--no-worker-processes-run", "worker_processes_run"),
+                         ("--no-fresh-obs", "worker_processes_run"), ("--no-profile", "rollout_step")):
+        assert bench.extras_of(parse(plain + ["--full", switch])) == every - {gone}, switch
+    a, b = vars(parse(plain + ["--dump-outputs", "d"])), vars(parse(plain + ["--dump-outputs", "d", "--full"]))
+    assert a.pop("full") is False and b.pop("full") is True and a == b
+
+
 def test_native_pcg64_stream_is_numpys():
     """libetm_envgen.so (csrc/envgen.cc, include/etm_envgen.h): every symbol the header declares is exported, and the fill is numpy's
     ``default_rng(seed).random(n, dtype=float32)`` bit for bit -- floats AND the generator state afterwards -- in the AVX-512 form (where

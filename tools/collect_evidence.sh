@@ -11,7 +11,7 @@ if [ "${SUITE:-0}" = 1 ]; then
   echo "== pytest -m gpu"; rm -f $OUT/tf_measured.jsonl; (cd $ROOT && ETM_QUIET=1 ETM_TF_MEASURE_LOG=$OUT/tf_measured.jsonl timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" | tail -3 | tee $OUT/gpu_suite.txt)
 fi
 cd /tmp && export TMPDIR=/tmp
-echo "== bench (the driver's command shape)"; timeout 900 python $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full-json $OUT/bench_full.json > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.err; wc -c $OUT/bench.json
+echo "== bench (the driver's command shape)"; timeout 900 python $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full --full-json $OUT/bench_full.json > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.err; wc -c $OUT/bench.json
 echo "== rocprofv3 --kernel-trace --stats of the bench command"
 rm -rf /tmp/prof_stats; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o b -- python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-rooflines > /tmp/prof_stats.log 2>&1
 cp $(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv 2>/dev/null; head -8 $OUT/bench_kernel_stats.csv | cut -c1-160
