@@ -7,7 +7,10 @@
 //   etm_grad_sqnorm   per-workgroup partial sums of g^2 (fixed chunking => deterministic), and step += 1
 //   etm_adamw_clip    every workgroup adds the partial sums in the same order -> total norm -> clip coefficient
 //                     min(1, max_norm / (norm + 1e-6)) (the rule of clip_grad_norm_; data parallel: x 1 / world, the averaging of
-//                     the all-reduced sum), then for its elements:
+//                     the all-reduced sum).  A non-finite norm poisons the step as upstream's does: a NaN gradient makes the norm and
+//                     the coefficient NaN, so every gradient, parameter and moment becomes NaN; a +-Inf makes the coefficient 0, so that
+//                     element becomes NaN and every other gradient 0.  max_norm <= 0: no clipping, a NaN stays in its element.
+//                     Then for its elements:
 //                       g *= coef (written back: the monitored gradient norms of model.py:128-151 are taken after clipping)
 //                       p *= 1 - lr wd;  m = lerp(m, g, 1 - b1);  v = b2 v + (1 - b2) g g
 //                       p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)   (torch's single-tensor AdamW, fp32, same order)
@@ -123,7 +126,11 @@ __device__ __forceinline__ void adamw_clip_body(float4 *__restrict__ p, float4 *
   if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = total;
   if (dropped) return;                        // a dropped step: the norm above and nothing else (uniform over the launch)
   float coef = 1.f;
-  if (max_norm > 0.f) coef = fminf(max_norm / (total + 1e-6f), 1.f);
+  if (max_norm > 0.f) {
+    // torch.clamp(q, max = 1): a NaN norm gives a NaN coefficient (fminf would hand back the 1); every other q keeps fminf's bits
+    const float q = max_norm / (total + 1e-6f);
+    coef = !(q >= 1.f) ? q : 1.f;
+  }
   coef *= grad_scale;
   // scalars as torch.optim.AdamW forms them (python floats = doubles), then the fp32 tensor arithmetic of its single-tensor
   // path in the same order: p.mul_(1 - lr wd); m.lerp_(g, 1 - b1); v.mul_(b2).addcmul_(g, g, value = 1 - b2);

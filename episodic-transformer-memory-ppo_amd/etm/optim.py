@@ -115,7 +115,9 @@ class FlatAdamW:
     def step(self, max_grad_norm=0.0, grad_scale=1.0, gate=None, adapt=None):
         """Clip the gradient arena to ``max_grad_norm`` (global L2 norm, the rule of ``clip_grad_norm_``; <= 0: no clipping) and
         apply one AdamW update.  Two launches on the current stream.  ``grad_scale``: the arena holds gradient / grad_scale
-        (data parallel: the all-reduced sum, grad_scale = 1 / world); the scale rides in the clip coefficient.  ``gate`` (a ``KlGate``;
+        (data parallel: the all-reduced sum, grad_scale = 1 / world); the scale rides in the clip coefficient.  A non-finite norm
+        poisons the step as upstream's does (``max_grad_norm`` > 0): one NaN gradient makes every gradient, parameter and moment NaN, one
+        Inf makes that element NaN and every other gradient 0; without clipping a NaN stays in its element.  ``gate`` (a ``KlGate``;
         None: exactly the two ungated calls): the step is dropped -- parameters, moments, gradients and ``step_dev`` keep every bit --
         when an earlier step under this gate was dropped or when not ``gate.kl <= gate.limit``; still two launches.  ``adapt`` (an
         ``AdaptiveLr``; None: exactly the calls above): the norm launch first moves ``lr_dev`` on ``adapt.kl`` (utils.adaptive_lr_step;
