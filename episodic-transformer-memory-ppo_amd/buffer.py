@@ -30,12 +30,13 @@ the storage redesigned for the MI355X path:
 * ``exact_kl: true`` (absent upstream): on a Box policy exactly the two fields above; on a Discrete / MultiDiscrete policy (masked or
   not) ``old_logps`` [W, S, sum A_b], the rollout's log-probs of every column of every branch (-inf where a column was masked out), a
   member of ``samples_flat``.  The rows live for one rollout (nothing of them is in a checkpoint).  Without the key it does not exist.
+* ``kl_penalty`` (absent upstream) implies ``exact_kl: true``: the same fields, for either policy kind (the penalty is a term in that KL).
 """
 import numpy as np
 import torch
 
 from etm import ops
-from utils import exact_kl_section, kl_estimator_section, normalization_section
+from utils import exact_kl_section, kl_estimator_section, kl_penalty_section, normalization_section
 
 
 class Buffer:
@@ -88,6 +89,7 @@ class Buffer:
         # model's policy_log_std); None without the key
         self.means = self.old_log_std = self.log_std_source = None
         exact = exact_kl_section(config)      # (exact_kl: true on a Box policy is exactly kl_estimator: analytic)
+        exact = exact or kl_penalty_section(config) is not None      # (kl_penalty implies the exact KL's fields, for every policy kind)
         if kl_estimator_section(config) == "analytic" or (exact and continuous):
             if not continuous:
                 raise ValueError("kl_estimator: analytic needs a Box (continuous) policy; remove the key")

@@ -57,6 +57,8 @@ struct HlParams {
   // under the policy that drew the samples (-inf at a column that was masked out)
   const float *old_logps;
   long long old_logps_stride;
+  // PEN kernels (`kl_penalty`): one device float32, the coefficient of the KL term of the loss, read in place by every launch
+  const float *kl_coef;
 };
 
 // BR: MultiDiscrete branches; GS: diagonal Gaussian (Box; the row gains d log_std [A] behind the five statistic sums)
@@ -65,13 +67,20 @@ struct HlParams {
 // products and the optional logits output stay raw.  What is left is the unmasked arithmetic on the compacted branch.
 // KL (GS only): a sixth running sum, the exact KL(old || new) of the two diagonal Gaussians,
 //   KL_n = sum_a [(expm1(2 d_a) / 2 - d_a) + ((mu_old[n, a] - mu[n, a]) / sigma_a)^2 / 2],  d_a = log sigma_old_a - log sigma_a,
-// written so that nothing cancels (equal policies give exactly 0).  A statistic only: no term of the loss, no gradient; the sum sits
-// behind d log_std at the very end of the row, so every other row offset keeps its value.
+// written so that nothing cancels (equal policies give exactly 0).  A statistic only: no term of the loss, no gradient, unless
+// `kl_penalty` (PEN, below); the sum sits behind d log_std at the very end of the row, so every other row offset keeps its value.
 // KL (categorical, BR and MK or not): the sixth running sum is the exact KL of the two categoricals, per branch the sum over its VALID
 // columns of etm_categorical_kl_term(old_logps[n, j], l_j, p_j), formed where l_j and p_j already are; it sits behind the five statistic
-// sums at the very end of the row.  Again a statistic only.
-template <int HC, bool BR, bool GS, bool MK, bool KL = false>
+// sums at the very end of the row.  Again a statistic only, unless `kl_penalty`.
+// PEN (KL only; `kl_penalty`): the loss gains coef * K, K the exact KL as out8[4] holds it, coef = *kl_coef read in place.  Its gradient
+// joins d logits where l_j, p_j, mu_a, sigma_a already are (utils.categorical_kl_grad / gaussian_kl_grad are the host definitions):
+//   categorical   dl[j] += coef pol_scale (p_j - p_old_j) inside the ok(j) guard (an invalid column's d logit stays exactly 0)
+//   Box           dl[a] += coef ent_scale (-q / sigma_a), q = (mu_old - mu) / sigma_a; lane 0 adds coef ent_scale (-expm1(2 d_a) - q^2)
+//                 to d log_std[a], the expm1 part formed once per lane, where kl_ls is
+// Equal policies add exactly 0 to every gradient; the row layout is the KL kernels'.
+template <int HC, bool BR, bool GS, bool MK, bool KL = false, bool PEN = false>
 __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
+  static_assert(!PEN || KL, "the KL penalty needs the exact KL's operands");
   HlParams p = p0;
   if (p.dyn) {
     const double c = p.dyn[0];
@@ -110,6 +119,16 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
 #pragma unroll
     for (int a = 0; a < HL_MAXA; ++a)
       if (a < A) { const float d = p.old_log_std[a] - lsr[a]; kl_ls += 0.5f * expm1f(2.f * d) - d; }
+  }
+  // PEN: the coefficient times the scale of K, and (GS) the part of d K / d log sigma_a that does not depend on the sample
+  float pen_pol = 0.f, pen_ent = 0.f, pen_ls[HL_MAXA];
+  if constexpr (PEN) {
+    const float coef = p.kl_coef[0];
+    pen_pol = coef * p.pol_scale; pen_ent = coef * p.ent_scale;
+    if constexpr (GS) {
+#pragma unroll
+      for (int a = 0; a < HL_MAXA; ++a) pen_ls[a] = (a < A) ? pen_ent * -expm1f(2.f * (p.old_log_std[a] - lsr[a])) : 0.f;
+    }
   }
   const float bvr = p.bv[0];
   const float cnt = p.adv_stats3[0], mean = p.adv_stats3[1], m2 = p.adv_stats3[2];
@@ -221,7 +240,14 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
         float kq = 0.f;
 #pragma unroll
         for (int a = 0; a < HL_MAXA; ++a)
-          if (a < A) { const float q = (p.old_mean[(long long)n * p.old_mean_stride + a] - lg[a]) / sgr[a]; kq += 0.5f * q * q; }
+          if (a < A) {
+            const float q = (p.old_mean[(long long)n * p.old_mean_stride + a] - lg[a]) / sgr[a];
+            kq += 0.5f * q * q;
+            if constexpr (PEN) {
+              dl[a] += pen_ent * (-q / sgr[a]);
+              if (lane == 0) s_ls[a] += pen_ls[a] - pen_ent * (q * q);
+            }
+          }
         if (lane == 0) acc_kl += kl_ls + kq;
       }
     } else if constexpr (!BR) {
@@ -267,7 +293,11 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
         const float d_lp = ((j == act) ? 1.f : 0.f) - pj;
         const float d_ent = -pj * (l + ent);
         dl[j] = cpol * d_lp + cent * d_ent;
-        if constexpr (KL) kl_n += etm_categorical_kl_term(p.old_logps[(long long)n * p.old_logps_stride + j], l, pj);
+        if constexpr (KL) {
+          const float lo = p.old_logps[(long long)n * p.old_logps_stride + j];
+          kl_n += etm_categorical_kl_term(lo, l, pj);
+          if constexpr (PEN) dl[j] += pen_pol * (pj - expf(lo));
+        }
       }
     }
     if constexpr (KL) { if (lane == 0) acc_kl += kl_n; }
@@ -333,7 +363,11 @@ __device__ __forceinline__ void heads_loss_body(const HlParams &p0) {
           const float d_lp = (taken ? 1.f : 0.f) - pj;
           const float d_ent = -pj * (l + ent_c[j]);
           dl[j] = cpol_c[j] * d_lp + cent * d_ent;
-          if constexpr (KL) kl_n += etm_categorical_kl_term(p.old_logps[(long long)n * p.old_logps_stride + j], l, pj);
+          if constexpr (KL) {
+          const float lo = p.old_logps[(long long)n * p.old_logps_stride + j];
+          kl_n += etm_categorical_kl_term(lo, l, pj);
+          if constexpr (PEN) dl[j] += pen_pol * (pj - expf(lo));
+        }
         }
       }
       if constexpr (KL) { if (lane == 0) acc_kl += kl_n; }
@@ -420,6 +454,10 @@ template <int HC>
 __global__ __launch_bounds__(256) void heads_loss_gaussian_kl_kernel(const HlParams p0) { heads_loss_body<HC, false, true, false, true>(p0); }
 template <int HC, bool BR, bool MK>
 __global__ __launch_bounds__(256) void heads_loss_kl_kernel(const HlParams p0) { heads_loss_body<HC, BR, false, MK, true>(p0); }
+template <int HC>
+__global__ __launch_bounds__(256) void heads_loss_gaussian_kl_penalty_kernel(const HlParams p0) { heads_loss_body<HC, false, true, false, true, true>(p0); }
+template <int HC, bool BR, bool MK>
+__global__ __launch_bounds__(256) void heads_loss_kl_penalty_kernel(const HlParams p0) { heads_loss_body<HC, BR, false, MK, true, true>(p0); }
 
 // sums the workgroup rows and finishes the loss statistics: out = [row sums ... ], out8 (a Gaussian row's d log_std sums, behind the
 // statistics, are summed like every other element).  One workgroup = 64 row elements x 16 row
@@ -428,10 +466,13 @@ __global__ __launch_bounds__(256) void heads_loss_kl_kernel(const HlParams p0) {
 // KL = 1 (the Gaussian row with the KL sum as its last element): out8[4] = that sum * ent_scale (the exact KL), out8[6] = the k3 value.
 // KL = 2 (the categorical row with the KL sum as its last element, right behind the five statistic sums): out8[4] = that sum *
 // pol_scale -- the mean over samples AND branches, the convention of the k3 value, which goes to out8[6].
-template <int KL>
+// PEN (`kl_penalty`, KL != 0): out8[2] gains coef * out8[4], out8[7] = coef = *kl_coef.
+template <int KL, bool PEN = false>
 __device__ __forceinline__ void heads_reduce_body(const float *__restrict__ partials, int n_wg, int row, int A, int hid, float vf_coef,
                                                   float beta, float pol_scale, float ent_scale, float val_scale,
-                                                  const double *__restrict__ dyn, float *__restrict__ out, float *__restrict__ out8) {
+                                                  const double *__restrict__ dyn, float *__restrict__ out, float *__restrict__ out8,
+                                                  const float *__restrict__ kl_coef = nullptr) {
+  static_assert(!PEN || KL != 0, "the KL penalty needs the exact KL");
   __shared__ float sm[16][64];
   const int el = threadIdx.x & 63, g = threadIdx.x >> 6;
   auto group_sum = [&](int e) {
@@ -474,7 +515,9 @@ __device__ __forceinline__ void heads_reduce_body(const float *__restrict__ part
     if constexpr (KL != 0) {
       float t = 0.f;
       for (int k = 0; k < 16; ++k) t += sm[k][5];
-      out8[4] = t * (KL == 1 ? ent_scale : pol_scale); out8[5] = acc[4] * pol_scale; out8[6] = acc[3] * pol_scale; out8[7] = 0.f;
+      const float k = t * (KL == 1 ? ent_scale : pol_scale);
+      out8[4] = k; out8[5] = acc[4] * pol_scale; out8[6] = acc[3] * pol_scale; out8[7] = 0.f;
+      if constexpr (PEN) { const float coef = kl_coef[0]; out8[2] = -(pol - vf_coef * val + beta * ent) + coef * k; out8[7] = coef; }
     } else {
       out8[4] = acc[3] * pol_scale; out8[5] = acc[4] * pol_scale; out8[6] = 0.f; out8[7] = 0.f;
     }
@@ -496,6 +539,19 @@ __global__ __launch_bounds__(1024) void heads_reduce_categorical_kl_kernel(const
                                                                            float val_scale, const double *__restrict__ dyn,
                                                                            float *__restrict__ out, float *__restrict__ out8) {
   heads_reduce_body<2>(partials, n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn, out, out8);
+}
+__global__ __launch_bounds__(1024) void heads_reduce_kl_penalty_kernel(const float *__restrict__ partials, int n_wg, int row, int A, int hid,
+                                                                       float vf_coef, float beta, float pol_scale, float ent_scale,
+                                                                       float val_scale, const double *__restrict__ dyn, float *__restrict__ out,
+                                                                       float *__restrict__ out8, const float *__restrict__ kl_coef) {
+  heads_reduce_body<1, true>(partials, n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn, out, out8, kl_coef);
+}
+__global__ __launch_bounds__(1024) void heads_reduce_categorical_kl_penalty_kernel(const float *__restrict__ partials, int n_wg, int row, int A,
+                                                                                   int hid, float vf_coef, float beta, float pol_scale,
+                                                                                   float ent_scale, float val_scale,
+                                                                                   const double *__restrict__ dyn, float *__restrict__ out,
+                                                                                   float *__restrict__ out8, const float *__restrict__ kl_coef) {
+  heads_reduce_body<2, true>(partials, n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn, out, out8, kl_coef);
 }
 static_assert(true, "");
 constexpr int HL_SAMPLES_PER_WG = 8;      // two samples per wave: the pass is a latency chain per sample, so many short waves
@@ -536,12 +592,15 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
                               float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
                               int A, const int32_t *branch_sizes, int n_branches, const float *xact, const float *log_std,
                               const int64_t *action_mask, void *stream, const float *old_mean = nullptr, int64_t old_mean_stride = 0,
-                              const float *old_log_std = nullptr, const float *old_logps = nullptr, int64_t old_logps_stride = 0) {
+                              const float *old_log_std = nullptr, const float *old_logps = nullptr, int64_t old_logps_stride = 0,
+                              const float *kl_coef = nullptr) {
   (void)hipGetLastError();
   const bool gauss = xact != nullptr;                  // Box: float actions xact and log_std instead of the int64 actions
   const bool kl = old_mean != nullptr;                 // Box with the exact KL: the row gains the KL sum
   const bool ckl = old_logps != nullptr;               // categorical with the exact KL: likewise
   if (ckl && gauss) return ETM_EINVAL;
+  const bool pen = kl_coef != nullptr;                 // `kl_penalty`: the KL kernels with the term's gradient
+  if (pen && !kl && !ckl) return ETM_EINVAL;
   if (!pre_p || !pre_v || !b_lp || !b_lv || !wb || !bb || !wv || !bv || !(gauss ? (const void *)log_std : (const void *)actions) || !old_logp ||
       !adv || !old_value || !adv_stats3 || !gm_p || !gm_v || !sums || !out8 || !workspace)
     return ETM_EINVAL;
@@ -571,7 +630,7 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
   p.N = N; p.A = A; p.hid = hid; p.samples_per_wg = HL_SAMPLES_PER_WG;
   p.xact = xact; p.log_std = log_std; p.amask = (const long long *)action_mask;
   p.old_mean = old_mean; p.old_mean_stride = old_mean_stride; p.old_log_std = old_log_std;
-  p.old_logps = old_logps; p.old_logps_stride = old_logps_stride;
+  p.old_logps = old_logps; p.old_logps_stride = old_logps_stride; p.kl_coef = kl_coef;
   const bool masked = action_mask != nullptr;
   const int n_wg = (N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG;
   const int row = kl ? etm_heads_loss_gaussian_kl_row_floats(hid, A) : ckl ? etm_heads_loss_kl_row_floats(hid, A)
@@ -583,7 +642,12 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
     switch (hid / 64) {
 #define HL_CASE(HC_)                                                                                              \
   case HC_:                                                                                                       \
-    if (kl) hipLaunchKernelGGL((heads_loss_gaussian_kl_kernel<HC_>), dim3((unsigned)n_wg), dim3(256), lds, st, p);  \
+    if (pen && kl) hipLaunchKernelGGL((heads_loss_gaussian_kl_penalty_kernel<HC_>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (pen && masked && branched) hipLaunchKernelGGL((heads_loss_kl_penalty_kernel<HC_, true, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (pen && masked) hipLaunchKernelGGL((heads_loss_kl_penalty_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (pen && branched) hipLaunchKernelGGL((heads_loss_kl_penalty_kernel<HC_, true, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (pen) hipLaunchKernelGGL((heads_loss_kl_penalty_kernel<HC_, false, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
+    else if (kl) hipLaunchKernelGGL((heads_loss_gaussian_kl_kernel<HC_>), dim3((unsigned)n_wg), dim3(256), lds, st, p);  \
     else if (gauss) hipLaunchKernelGGL((heads_loss_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
     else if (ckl && masked && branched) hipLaunchKernelGGL((heads_loss_kl_kernel<HC_, true, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
     else if (ckl && masked) hipLaunchKernelGGL((heads_loss_kl_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
@@ -602,7 +666,13 @@ static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *
   int rc = etm_launch_status();
   if (rc) return rc;
   EtmProfScope prof(ETM_K_PPO_FINAL, st);
-  if (kl)
+  if (pen && kl)
+    hipLaunchKernelGGL(heads_reduce_kl_penalty_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg, row, A,
+                       hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8, kl_coef);
+  else if (pen)
+    hipLaunchKernelGGL(heads_reduce_categorical_kl_penalty_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace,
+                       n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8, kl_coef);
+  else if (kl)
     hipLaunchKernelGGL(heads_reduce_kl_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg, row, A, hid,
                        vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8);
   else if (ckl)
@@ -754,4 +824,62 @@ extern "C" int etm_heads_loss_gaussian_kl(const float *pre_p, const float *pre_v
   return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, nullptr, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
                          clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
                          workspace_bytes, N, hid, A, nullptr, 1, xact, log_std, nullptr, stream, old_mean, old_mean_stride, old_log_std);
+}
+
+// `kl_penalty`: the three exact-KL entries with the loss L + coef * K, K = out8[4] (the exact KL as the twin reports it), coef = *kl_coef,
+// ONE device float32 that the kernels read in place (eager launches and captured graphs alike; the host rewrites it between updates).
+// The gradient outputs (gm_p, gm_v, every gradient element of sums) are those of L + coef * K; out8[2] includes coef * K, out8[7] = coef;
+// out8[0, 1, 3, 4, 5, 6], logits, value, the statistic sums and the row layout are the twin's.  ETM_EINVAL with nothing launched: a NULL
+// or 4-byte-misaligned kl_coef; otherwise exactly the twin's refusals.
+extern "C" int etm_heads_loss_kl_penalty(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                         const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
+                                         const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
+                                         const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                                         float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
+                                         float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid, int A,
+                                         const int64_t *action_mask, const float *old_logps, int64_t old_logps_stride, const float *kl_coef,
+                                         void *stream) {
+  if (!kl_coef || ((uintptr_t)kl_coef & 3u)) return ETM_EINVAL;
+  if (!old_logps || ((uintptr_t)old_logps & 3u) || old_logps_stride < A) return ETM_EINVAL;
+  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
+                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
+                         workspace_bytes, N, hid, A, nullptr, 1, nullptr, nullptr, action_mask, stream, nullptr, 0, nullptr, old_logps,
+                         old_logps_stride, kl_coef);
+}
+extern "C" int etm_heads_loss_branched_kl_penalty(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                                  const float *bb, const float *wv, const float *bv, const int64_t *actions,
+                                                  int64_t action_stride, const float *old_logp, int64_t logp_stride, const float *adv,
+                                                  const float *old_value, const float *adv_stats3, double clip, float vf_coef, float beta,
+                                                  float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p,
+                                                  float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace,
+                                                  int64_t workspace_bytes, int N, int hid, const int32_t *branch_sizes, int n_branches,
+                                                  const int64_t *action_mask, const float *old_logps, int64_t old_logps_stride,
+                                                  const float *kl_coef, void *stream) {
+  if (!kl_coef || ((uintptr_t)kl_coef & 3u)) return ETM_EINVAL;
+  if (!old_logps || ((uintptr_t)old_logps & 3u)) return ETM_EINVAL;
+  if (!etm_heads_loss_supported_branched(N, hid, branch_sizes, n_branches)) return ETM_EUNSUPPORTED;
+  if (action_stride < n_branches || logp_stride < n_branches || old_logps_stride < etm_branches_total(branch_sizes, n_branches))
+    return ETM_EINVAL;
+  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
+                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
+                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, nullptr,
+                         action_mask, stream, nullptr, 0, nullptr, old_logps, old_logps_stride, kl_coef);
+}
+// (Box: d log_std, the A row elements behind the statistic sums, carries the term's gradient too)
+extern "C" int etm_heads_loss_gaussian_kl_penalty(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                                  const float *bb, const float *wv, const float *bv, const float *xact, int64_t action_stride,
+                                                  const float *log_std, const float *old_logp, int64_t logp_stride, const float *adv,
+                                                  const float *old_value, const float *adv_stats3, double clip, float vf_coef, float beta,
+                                                  float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p,
+                                                  float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace,
+                                                  int64_t workspace_bytes, int N, int hid, int A, const float *old_mean,
+                                                  int64_t old_mean_stride, const float *old_log_std, const float *kl_coef, void *stream) {
+  if (!kl_coef || ((uintptr_t)kl_coef & 3u)) return ETM_EINVAL;
+  if (!xact || !old_mean || !old_log_std) return ETM_EINVAL;
+  if (((uintptr_t)old_mean | (uintptr_t)old_log_std) & 3u) return ETM_EINVAL;
+  if (action_stride < A || logp_stride < 1 || old_mean_stride < A) return ETM_EINVAL;
+  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, nullptr, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
+                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
+                         workspace_bytes, N, hid, A, nullptr, 1, xact, log_std, nullptr, stream, old_mean, old_mean_stride, old_log_std,
+                         nullptr, 0, kl_coef);
 }

@@ -97,6 +97,8 @@ struct LossParams {
   const float *old_logps;
   long long old_logps_stride;
   int logps_off;
+  // PEN kernels (`kl_penalty`): one device float32, the coefficient of the KL term of the loss, read in place
+  const float *kl_coef;
 };
 
 // SPT samples per thread.  SPT = 4 (large batches, unit strides, A = 3, N % 4 == 0): the four samples' operands come in as
@@ -107,9 +109,17 @@ struct LossParams {
 // p = 0, is skipped -- not multiplied: 0 * inf -- by the entropy, and its d logit is exactly 0.  What is left is the unmasked
 // arithmetic on the compacted branch.
 // KL (SPT = 1 only, MK or not): a sixth sum, the branch's exact KL(old || new) -- etm_categorical_kl_term over its valid columns, formed
-// where l and pj already are -- into slot 5 of the workgroup's 8 partial floats.  A statistic only: no term of the loss, no gradient.
-template <int SPT, bool MK, bool KL = false>
+// where l and pj already are -- into slot 5 of the workgroup's 8 partial floats.  A statistic only: no term of the loss, no gradient,
+// unless `kl_penalty`.
+// PEN (KL only; `kl_penalty`): the loss gains coef * K, K the exact KL as out8[4] holds it, coef = *kl_coef; a valid column's d logit
+// gains coef pol_scale (p_j - p_old_j) (utils.categorical_kl_grad), an invalid one's stays exactly 0.  The term's p_j is
+// exp((logit_j - max) - log(sum)), not the exp(logit_j - lse) of the other terms: logit_j - lse carries half a spacing of lse (2.4e-7 at
+// lse = 4.3) into every p_j, which coef multiplies (a d logit of size 0.16 was off by 9.6e-7 at coef 7); the form here is exact at the
+// largest column, as a float32 log-softmax is.  One more expf per column, in these kernels only.  With the sampler's rows of equal
+// logits the term is therefore of rounding size, |p_j - p_old_j| <= p_j (a spacing of lse), not exactly 0 as in the fused kernels.
+template <int SPT, bool MK, bool KL = false, bool PEN = false>
 __device__ __forceinline__ void ppo_loss_body(const LossParams &p0) {
+  static_assert(!PEN || (KL && SPT == 1), "the KL penalty needs the exact KL's operands");
   LossParams p = p0;
   if (p.dyn) {   // schedules that change between replays of a captured training step
     const double c = p.dyn[0];
@@ -121,6 +131,8 @@ __device__ __forceinline__ void ppo_loss_body(const LossParams &p0) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n0 = (blockIdx.x * 256 + tid) * SPT;
   float acc[NK] = {0.f, 0.f, 0.f, 0.f, 0.f};  // policy, value, entropy, kl, clip fraction (KL: then the exact KL)
+  float pen_pol = 0.f;
+  if constexpr (PEN) pen_pol = p.kl_coef[0] * p.pol_scale;
   // operands of this thread's samples
   float lgv[SPT][SPT == 1 ? 1 : 3], advv[SPT], oldlp[SPT], vv[SPT], vov[SPT], dlv[SPT][SPT == 1 ? 1 : 3], dvv[SPT];
   int actv[SPT];
@@ -160,6 +172,8 @@ __device__ __forceinline__ void ppo_loss_body(const LossParams &p0) {
     float se = 0.f;
     for (int j = 0; j < A; ++j) if (ok(j)) se += expf(lg[j] - mx);
     const float lse = mx + logf(se);
+    float log_se = 0.f;                                     // (PEN: the penalty's own log-probs, see above)
+    if constexpr (PEN) log_se = logf(se);
     const int act = SPT == 4 ? actv[s] : (int)p.actions[(long long)n * p.action_stride];
     float lg_act = lg[0];
     if (SPT == 4) { lg_act = act == 1 ? lgl[1] : (act == 2 ? lgl[2] : lgl[0]); } else { lg_act = lg[act]; }
@@ -193,7 +207,8 @@ __device__ __forceinline__ void ppo_loss_body(const LossParams &p0) {
       const float pj = expf(l);
       const float d_lp = ((j == act) ? 1.f : 0.f) - pj;   // d log p[act] / d logit_j
       const float d_ent = -pj * (l + ent);                // d entropy / d logit_j
-      const float g = cpol * d_lp + cent * d_ent;
+      float g = cpol * d_lp + cent * d_ent;
+      if constexpr (PEN) g += pen_pol * (expf((lg[j] - mx) - log_se) - expf(p.old_logps[(long long)n * p.old_logps_stride + p.logps_off + j]));
       if (SPT == 4) dlv[s][SPT == 1 ? 0 : j] = g; else dl[j] = g;
       if constexpr (KL) acc[NK - 1] += etm_categorical_kl_term(p.old_logps[(long long)n * p.old_logps_stride + p.logps_off + j], l, pj);
     }
@@ -243,12 +258,16 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossParams p0) { pp
 __global__ __launch_bounds__(256) void ppo_loss_masked_kernel(const LossParams p0) { ppo_loss_body<1, true>(p0); }
 template <bool MK>
 __global__ __launch_bounds__(256) void ppo_loss_kl_kernel(const LossParams p0) { ppo_loss_body<1, MK, true>(p0); }
+template <bool MK>
+__global__ __launch_bounds__(256) void ppo_loss_kl_penalty_kernel(const LossParams p0) { ppo_loss_body<1, MK, true, true>(p0); }
 
 // KL: the sixth partial is the exact KL sum -> out8[4] (scaled as the k3 value, which goes to out8[6])
-template <bool KL>
+// PEN (`kl_penalty`, KL only): out8[2] gains coef * out8[4], out8[7] = coef = *kl_coef
+template <bool KL, bool PEN = false>
 __device__ __forceinline__ void ppo_finalize_body(const float *__restrict__ partials, int n_blocks, float vf_coef, float beta,
                                                   float pol_scale, float ent_scale, float val_scale, float *__restrict__ out8,
-                                                  const double *__restrict__ dyn) {
+                                                  const double *__restrict__ dyn, const float *__restrict__ kl_coef = nullptr) {
+  static_assert(!PEN || KL, "the KL penalty needs the exact KL");
   constexpr int NK = KL ? 6 : 5;
   const int lane = threadIdx.x;
   if (dyn) beta = (float)dyn[1];
@@ -268,6 +287,11 @@ __device__ __forceinline__ void ppo_finalize_body(const float *__restrict__ part
     out8[5] = acc[4] * pol_scale;
     out8[6] = KL ? acc[3] * pol_scale : 0.f;
     out8[7] = 0.f;
+    if constexpr (PEN) {
+      const float coef = kl_coef[0];
+      out8[2] = -(pol - vf_coef * val + beta * ent) + coef * (acc[NK - 1] * pol_scale);
+      out8[7] = coef;
+    }
   }
 }
 __global__ __launch_bounds__(64) void ppo_finalize_kernel(const float *__restrict__ partials, int n_blocks, float vf_coef, float beta,
@@ -279,6 +303,12 @@ __global__ __launch_bounds__(64) void ppo_finalize_kl_kernel(const float *__rest
                                                              float pol_scale, float ent_scale, float val_scale, float *__restrict__ out8,
                                                              const double *__restrict__ dyn) {
   ppo_finalize_body<true>(partials, n_blocks, vf_coef, beta, pol_scale, ent_scale, val_scale, out8, dyn);
+}
+__global__ __launch_bounds__(64) void ppo_finalize_kl_penalty_kernel(const float *__restrict__ partials, int n_blocks, float vf_coef, float beta,
+                                                                     float pol_scale, float ent_scale, float val_scale,
+                                                                     float *__restrict__ out8, const double *__restrict__ dyn,
+                                                                     const float *__restrict__ kl_coef) {
+  ppo_finalize_body<true, true>(partials, n_blocks, vf_coef, beta, pol_scale, ent_scale, val_scale, out8, dyn, kl_coef);
 }
 }  // namespace
 
@@ -322,7 +352,7 @@ static int ppo_loss_impl(const float *logits, const int64_t *actions, int64_t ac
                             float val_scale, int include_value, float *out8, float *d_logits, float *d_value, void *partials,
                             int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, const int64_t *action_mask,
                             int mask_shift, void *stream, const float *old_logps = nullptr, int64_t old_logps_stride = 0,
-                            int logps_off = 0) {
+                            int logps_off = 0, const float *kl_coef = nullptr) {
   (void)hipGetLastError();  // drop stale sticky errors of earlier, unrelated runtime calls
   if (!logits || !actions || !old_logp || !adv || !adv_stats3 || !out8 || !d_logits || !partials) return ETM_EINVAL;
   if (include_value && (!old_value || !value || !d_value)) return ETM_EINVAL;
@@ -339,8 +369,10 @@ static int ppo_loss_impl(const float *logits, const int64_t *actions, int64_t ac
   p.dyn = dyn_clip_beta;
   p.include_value = include_value; p.d_logits = d_logits; p.d_value = d_value; p.partials = (float *)partials;
   p.N = N; p.A = A; p.amask = (const long long *)action_mask; p.mask_shift = mask_shift;
-  p.old_logps = old_logps; p.old_logps_stride = old_logps_stride; p.logps_off = logps_off;
+  p.old_logps = old_logps; p.old_logps_stride = old_logps_stride; p.logps_off = logps_off; p.kl_coef = kl_coef;
   const bool kl = old_logps != nullptr;                // the exact KL: always the one-sample form
+  const bool pen = kl_coef != nullptr;                 // `kl_penalty`: the KL kernels with the term's gradient
+  if (pen && !kl) return ETM_EINVAL;
   // four samples per thread when every operand can move in 16-byte pieces and there are enough samples to fill the chip
   const bool vec = !kl && !action_mask && A == 3 && N % 4 == 0 && N >= (1 << 16) && action_stride == 1 && logp_stride == 1 && al16(logits) && al16(actions) &&
                    al16(old_logp) && al16(adv) && al16(d_logits) && (!include_value || (al16(value) && al16(old_value) && al16(d_value)));
@@ -349,6 +381,8 @@ static int ppo_loss_impl(const float *logits, const int64_t *actions, int64_t ac
   {
     EtmProfScope prof(ETM_K_PPO_LOSS, st);
     if (vec) hipLaunchKernelGGL(ppo_loss_kernel<4>, dim3(nb), dim3(256), 0, st, p);
+    else if (pen && action_mask) hipLaunchKernelGGL(ppo_loss_kl_penalty_kernel<true>, dim3(nb), dim3(256), 0, st, p);
+    else if (pen) hipLaunchKernelGGL(ppo_loss_kl_penalty_kernel<false>, dim3(nb), dim3(256), 0, st, p);
     else if (kl && action_mask) hipLaunchKernelGGL(ppo_loss_kl_kernel<true>, dim3(nb), dim3(256), 0, st, p);
     else if (kl) hipLaunchKernelGGL(ppo_loss_kl_kernel<false>, dim3(nb), dim3(256), 0, st, p);
     else if (action_mask) hipLaunchKernelGGL(ppo_loss_masked_kernel, dim3(nb), dim3(256), 0, st, p);
@@ -358,7 +392,10 @@ static int ppo_loss_impl(const float *logits, const int64_t *actions, int64_t ac
   if (rc) return rc;
   {
     EtmProfScope prof(ETM_K_PPO_FINAL, st);
-    if (kl)
+    if (pen)
+      hipLaunchKernelGGL(ppo_finalize_kl_penalty_kernel, dim3(1), dim3(64), 0, st, (const float *)partials, nb, vf_coef, beta, pol_scale,
+                         ent_scale, val_scale, out8, dyn_clip_beta, kl_coef);
+    else if (kl)
       hipLaunchKernelGGL(ppo_finalize_kl_kernel, dim3(1), dim3(64), 0, st, (const float *)partials, nb, vf_coef, beta, pol_scale, ent_scale,
                          val_scale, out8, dyn_clip_beta);
     else
@@ -409,4 +446,20 @@ extern "C" int etm_ppo_loss_kl(const float *logits, const int64_t *actions, int6
   return ppo_loss_impl(logits, actions, action_stride, old_logp, logp_stride, adv, old_value, value, adv_stats3, clip, vf_coef, beta, pol_scale,
                        ent_scale, val_scale, include_value, out8, d_logits, d_value, partials, partials_bytes, dyn_clip_beta, N, A, action_mask,
                        action_mask ? mask_shift : 0, stream, old_logps, old_logps_stride, logps_off);
+}
+// `kl_penalty`: etm_ppo_loss_kl with the loss L + coef * K of the branch, K = out8[4], coef = *kl_coef, ONE device float32 read in place.
+// d_logits is the gradient of L + coef * K; out8[2] includes coef * K, out8[7] = coef; d_value, out8[0, 1, 3, 4, 5, 6] and the partial
+// slots are the twin's.  ETM_EINVAL with nothing launched: a NULL or 4-byte-misaligned kl_coef; otherwise exactly the twin's refusals.
+extern "C" int etm_ppo_loss_kl_penalty(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
+                                       int64_t logp_stride, const float *adv, const float *old_value, const float *value,
+                                       const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                                       float val_scale, int include_value, float *out8, float *d_logits, float *d_value, void *partials,
+                                       int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, const int64_t *action_mask,
+                                       int mask_shift, const float *old_logps, int64_t old_logps_stride, int logps_off, const float *kl_coef,
+                                       void *stream) {
+  if (!kl_coef || ((uintptr_t)kl_coef & 3u)) return ETM_EINVAL;
+  if (!old_logps || ((uintptr_t)old_logps & 3u) || logps_off < 0 || old_logps_stride < (int64_t)logps_off + A) return ETM_EINVAL;
+  return ppo_loss_impl(logits, actions, action_stride, old_logp, logp_stride, adv, old_value, value, adv_stats3, clip, vf_coef, beta, pol_scale,
+                       ent_scale, val_scale, include_value, out8, d_logits, d_value, partials, partials_bytes, dyn_clip_beta, N, A, action_mask,
+                       action_mask ? mask_shift : 0, stream, old_logps, old_logps_stride, logps_off, kl_coef);
 }

@@ -221,6 +221,11 @@ for _name, _twin, _extra in (("etm_heads_loss_kl", "etm_heads_loss_masked", [_P,
     SIGNATURES[_name] = (_res, _args[:-1] + _extra + _args[-1:])
 SIGNATURES["etm_heads_loss_kl_row_floats"] = (_I, [_I, _I])
 SIGNATURES["etm_heads_loss_kl_workspace_bytes"] = (_L, [_I, _I, _I])
+# the KL penalty (`kl_penalty`; the ABI stays at 61 -- no signature above changes): each loss entry is its *_kl twin's argument list with
+# kl_coef, one device float32, in front of the stream
+for _name in ("etm_heads_loss_kl", "etm_heads_loss_branched_kl", "etm_heads_loss_gaussian_kl", "etm_ppo_loss_kl"):
+    _res, _args = SIGNATURES[_name]
+    SIGNATURES[_name + "_penalty"] = (_res, _args[:-1] + [_P] + _args[-1:])
 del _twin
 del _name, _extra, _res, _args
 

@@ -2208,10 +2208,18 @@ def _check_old_logps(old_logps, N, cols, what):
         raise ValueError(f"{what}: old_logps must be float32 [{N}, {cols}] with contiguous rows, got {tuple(old_logps.shape)} {old_logps.dtype}")
 
 
+def _check_kl_coef(kl_coef, what):
+    """The ``kl_coef=`` argument of the loss ops (`kl_penalty`): ONE float32 on the device, read in place by the kernels."""
+    _need_dev(kl_coef)
+    if kl_coef.dtype != torch.float32 or kl_coef.numel() != 1:
+        raise ValueError(f"{what}: kl_coef must be a device tensor of one float32, got {tuple(kl_coef.shape)} {kl_coef.dtype}")
+    return kl_coef.data_ptr()
+
+
 class _PpoLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, value, actions, old_logp, adv, old_value, stats3, branch, n_branches, clip, vf_coef, beta,
-                include_value, dyn=None, action_mask=None, mask_shift=0, old_logps=None, logps_off=0):
+                include_value, dyn=None, action_mask=None, mask_shift=0, old_logps=None, logps_off=0, kl_coef=None):
         lib = _lib.load()
         _need_dev(logits, value, actions, old_logp, adv, old_value, stats3)
         logits = _f32c(logits, "logits")
@@ -2237,8 +2245,11 @@ class _PpoLossFn(torch.autograd.Function):
             # branch's exact KL (masks or not)
             _check_old_logps(old_logps, N, int(logps_off) + A, "ppo_loss")
             am = 0 if action_mask is None else _mask_words(action_mask, N, int(mask_shift) + A, "ppo_loss").data_ptr()
-            rc = lib.etm_ppo_loss_kl(*args, am, int(mask_shift), old_logps.data_ptr(), old_logps.stride(0) if N > 1 else old_logps.shape[1],
-                                     int(logps_off), _stream())
+            lp_args = (am, int(mask_shift), old_logps.data_ptr(), old_logps.stride(0) if N > 1 else old_logps.shape[1], int(logps_off))
+            if kl_coef is not None:      # `kl_penalty`: the loss and d_logits carry coef * KL, the coefficient read in place
+                rc = lib.etm_ppo_loss_kl_penalty(*args, *lp_args, _check_kl_coef(kl_coef, "ppo_loss"), _stream())
+            else:
+                rc = lib.etm_ppo_loss_kl(*args, *lp_args, _stream())
         elif action_mask is None:
             rc = lib.etm_ppo_loss(*args, _stream())
         else:        # this branch's actions are bits [mask_shift, mask_shift + A) of the samples' words
@@ -2254,10 +2265,10 @@ class _PpoLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_stats):
         if g_loss is None:
-            return (None,) * 18
+            return (None,) * 19
         d_logits, d_value = ctx.saved_tensors
         gv = d_value * g_loss if ctx.include_value else None
-        return (d_logits * g_loss, gv) + (None,) * 16
+        return (d_logits * g_loss, gv) + (None,) * 17
 
 
 class _HeadsLossFn(torch.autograd.Function):
@@ -2268,7 +2279,7 @@ class _HeadsLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn, unit_grad,
-                sizes=None, log_std=None, action_mask=None, old_mean=None, old_log_std=None, old_logps=None):
+                sizes=None, log_std=None, action_mask=None, old_mean=None, old_log_std=None, old_logps=None, kl_coef=None):
         lib = _lib.load()
         _need_dev(h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3)
         h = _f32c(h, "h")
@@ -2281,6 +2292,7 @@ class _HeadsLossFn(torch.autograd.Function):
         ckl = old_logps is not None         # categorical with the exact KL statistic: the row carries the KL sum at its very end
         if ckl and gauss:
             raise ValueError("heads_ppo_loss: old_logps belongs to a categorical policy")
+        pen = () if kl_coef is None else (_check_kl_coef(kl_coef, "heads_ppo_loss"),)      # (`kl_penalty`: the *_kl_penalty entries)
         if kl:
             row, nbytes = lib.etm_heads_loss_gaussian_kl_row_floats(hid, A), lib.etm_heads_loss_gaussian_kl_workspace_bytes(N, hid, A)
         elif ckl:
@@ -2304,12 +2316,13 @@ class _HeadsLossFn(torch.autograd.Function):
                     or old_log_std.dtype != torch.float32 or old_log_std.numel() != A or not old_log_std.is_contiguous()):
                 raise ValueError(f"heads_ppo_loss_gaussian: old_mean must be float32 [{N}, {A}] with contiguous rows and old_log_std "
                                  f"float32 [{A}], got {tuple(old_mean.shape)} {old_mean.dtype} / {tuple(old_log_std.shape)} {old_log_std.dtype}")
-            rc = lib.etm_heads_loss_gaussian_kl(_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv),
-                                                _ptr(_f32c(actions, "actions")), A, _ptr(_f32c(log_std, "log_std")), _ptr(old_logp), 1,
-                                                _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
-                                                float(vf_coef), float(beta), 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
-                                                _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, A, old_mean.data_ptr(),
-                                                old_mean.stride(0) if N > 1 else A, old_log_std.data_ptr(), _stream())
+            entry = lib.etm_heads_loss_gaussian_kl_penalty if pen else lib.etm_heads_loss_gaussian_kl
+            rc = entry(_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv),
+                       _ptr(_f32c(actions, "actions")), A, _ptr(_f32c(log_std, "log_std")), _ptr(old_logp), 1,
+                       _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
+                       float(vf_coef), float(beta), 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
+                       _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, A, old_mean.data_ptr(),
+                       old_mean.stride(0) if N > 1 else A, old_log_std.data_ptr(), *pen, _stream())
         elif gauss:
             # Box: wb / bb the mean head, actions [N, A] the stored raw float actions, old_logp [N] (or [N, 1]) the joint log-probs
             _need_dev(log_std)
@@ -2322,14 +2335,15 @@ class _HeadsLossFn(torch.autograd.Function):
             # the exact categorical KL: the minibatch's rows of the rollout's log-prob table (rows of any stride), masks or not
             _check_old_logps(old_logps, N, A, "heads_ppo_loss")
             am = 0 if action_mask is None else _mask_words(action_mask, N, A, "heads_ppo_loss").data_ptr()
-            lp_args = (am, old_logps.data_ptr(), old_logps.stride(0) if N > 1 else old_logps.shape[1], _stream())
+            lp_args = (am, old_logps.data_ptr(), old_logps.stride(0) if N > 1 else old_logps.shape[1], *pen, _stream())
             if sizes is None:
-                rc = lib.etm_heads_loss_kl(*common, 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8),
+                rc = (lib.etm_heads_loss_kl_penalty if pen else lib.etm_heads_loss_kl)(*common, 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8),
                                            0, 0, _ptr(ws), nbytes, N, hid, A, *lp_args)
             else:
                 tab, nbr = _branch_table(sizes)
-                rc = lib.etm_heads_loss_branched_kl(*common, 1.0 / (N * nbr), 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
-                                                    _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, tab, nbr, *lp_args)
+                entry = lib.etm_heads_loss_branched_kl_penalty if pen else lib.etm_heads_loss_branched_kl
+                rc = entry(*common, 1.0 / (N * nbr), 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
+                           _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, tab, nbr, *lp_args)
         elif action_mask is not None:
             # invalid-action masks: the samples' words, Discrete or MultiDiscrete (wb / bb concatenated as below)
             am = _mask_words(action_mask, N, A, "heads_ppo_loss")
@@ -2361,7 +2375,7 @@ class _HeadsLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_stats):
         if g_loss is None:
-            return (None,) * 25
+            return (None,) * 26
         h, wlp, wlv, gm_p, gm_v, sums = ctx.saved_tensors
         hid, A = ctx.dims
         unit = ctx.unit                 # the caller promises loss.backward() on the returned loss itself: g_loss == 1, nothing to scale
@@ -2380,7 +2394,7 @@ class _HeadsLossFn(torch.autograd.Function):
         o = (3 + A) * hid
         return (dh, dwlp, s[:hid], dwlv, s[hid:2 * hid], s[3 * hid:o].view(A, hid), s[o:o + A], s[2 * hid:3 * hid].view(1, hid),
                 s[o + A:o + A + 1], None, None, None, None, None, None, None, None, None, None, None,
-                s[o + A + 6:o + 2 * A + 6] if ctx.gauss else None, None, None, None, None)
+                s[o + A + 6:o + 2 * A + 6] if ctx.gauss else None, None, None, None, None, None)
 
 
 def _branch_list(branch):
@@ -2407,15 +2421,20 @@ def heads_loss_supported_gaussian(h, lin_policy, mean_head):
 
 
 def heads_ppo_loss_gaussian(h, lin_policy, lin_value, mean_head, log_std, value_head, actions, old_logp, adv, old_value, clip, vf_coef, beta,
-                            stats3=None, dyn=None, unit_grad=False, old_mean=None, old_log_std=None):
+                            stats3=None, dyn=None, unit_grad=False, old_mean=None, old_log_std=None, kl_coef=None):
     """``heads_ppo_loss`` for a Box policy (diagonal Gaussian, state-independent ``log_std`` [A]): ``mean_head`` gives the means,
     ``actions`` [N, A] are the stored raw float actions, ``old_logp`` [N] or [N, 1] their joint log-probs.  One ratio per sample;
     the gradients reach ``log_std`` too (etm_heads_loss_gaussian).
     ``old_mean`` [N, A] / ``old_log_std`` [A] (optional, together): the means and log sigma of the policy that drew the samples;
     stats[4] is then the exact KL(old || new) of the two Gaussians instead of the k3 sample estimate, in the same launch and with
-    every other output unchanged in its bits (etm_heads_loss_gaussian_kl); None = exactly the call without."""
+    every other output unchanged in its bits (etm_heads_loss_gaussian_kl); None = exactly the call without.
+    ``kl_coef`` (optional, `kl_penalty`; needs ``old_mean``): a device tensor of one float32 that the kernels read in place; the loss is
+    then loss + coef * stats[4] and every gradient (``log_std``'s too) is that sum's (etm_heads_loss_gaussian_kl_penalty); None =
+    exactly the call without."""
     if (old_mean is None) != (old_log_std is None):
         raise ValueError("heads_ppo_loss_gaussian: old_mean and old_log_std come together (the exact KL needs both)")
+    if kl_coef is not None and old_mean is None:
+        raise ValueError("heads_ppo_loss_gaussian: kl_coef without old_mean / old_log_std (the KL penalty is a term in the exact KL); pass both")
     if stats3 is None:
         stats3 = adv_stats(adv)
     if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
@@ -2425,12 +2444,12 @@ def heads_ppo_loss_gaussian(h, lin_policy, lin_value, mean_head, log_std, value_
         raise ValueError(f"heads_ppo_loss_gaussian: actions must be float [N, {A}]")
     loss, st = _HeadsLossFn.apply(h, lin_policy.weight, lin_policy.bias, lin_value.weight, lin_value.bias, mean_head.weight, mean_head.bias,
                                   value_head.weight, value_head.bias, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn,
-                                  unit_grad, None, log_std, None, old_mean, old_log_std)
+                                  unit_grad, None, log_std, None, old_mean, old_log_std, None, kl_coef)
     return loss, st[:6]
 
 
 def heads_ppo_loss(h, lin_policy, lin_value, branch, value_head, actions, old_logp, adv, old_value, clip, vf_coef, beta, stats3=None, dyn=None,
-                   unit_grad=False, action_mask=None, old_logps=None):
+                   unit_grad=False, action_mask=None, old_logps=None, kl_coef=None):
     """model.py:101-110 + the PPO loss of ``ppo_loss``, from the transformer output ``h`` [N, D]: -> (loss scalar with grad, stats[6]).
     ``branch``: the policy branch, or the list of branches of a MultiDiscrete policy (``actions`` / ``old_logp`` [N, B]; the semantics of
     ``ppo_loss`` over branches).  ``unit_grad=True``: the caller runs ``backward()`` on the returned loss itself (upstream gradient 1):
@@ -2441,7 +2460,12 @@ def heads_ppo_loss(h, lin_policy, lin_value, branch, value_head, actions, old_lo
     ``old_logps`` (optional): float32 [N, sum A_b], every column's log-prob under the policy that drew the samples (the rollout's
     ``st_logps`` rows of the minibatch); stats[4] is then the exact KL(old || new) of the categoricals, the mean over samples and
     branches, instead of the k3 sample estimate, in the same launch and with every other output unchanged in its bits
-    (etm_heads_loss_kl / _branched_kl, masks or not); None = exactly the call without."""
+    (etm_heads_loss_kl / _branched_kl, masks or not); None = exactly the call without.
+    ``kl_coef`` (optional, `kl_penalty`; needs ``old_logps``): a device tensor of one float32 that the kernels read in place; the loss
+    is then loss + coef * stats[4] and every gradient is that sum's (etm_heads_loss_kl_penalty / _branched_kl_penalty); None = exactly
+    the call without."""
+    if kl_coef is not None and old_logps is None:
+        raise ValueError("heads_ppo_loss: kl_coef without old_logps (the KL penalty is a term in the exact KL); pass the rollout's log-prob rows")
     if stats3 is None:
         stats3 = adv_stats(adv)
     if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
@@ -2455,19 +2479,23 @@ def heads_ppo_loss(h, lin_policy, lin_value, branch, value_head, actions, old_lo
         sizes = tuple(int(b.weight.shape[0]) for b in br)
     loss, st = _HeadsLossFn.apply(h, lin_policy.weight, lin_policy.bias, lin_value.weight, lin_value.bias, wb, bb,
                                   value_head.weight, value_head.bias, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn,
-                                  unit_grad, sizes, None, action_mask, None, None, old_logps)
+                                  unit_grad, sizes, None, action_mask, None, None, old_logps, kl_coef)
     return loss, st[:6]
 
 
 def ppo_loss(logits_list, value, actions, old_logp, adv, old_value, clip, vf_coef, beta, stats3=None, dyn=None, action_mask=None,
-             old_logps=None):
+             old_logps=None, kl_coef=None):
     """PPO loss over all action branches.  Returns (loss scalar with grad, stats[6] device tensor in trainer.py:318-323 order).
     ``dyn``: optional float64 device tensor (clip, beta) read by the kernels at run time instead of the two scalars.
     ``action_mask`` (optional): int64 [N] device words as in ``heads_ppo_loss``; branch b reads its bits at the offset of its logits
     among the concatenated branches (etm_ppo_loss_masked); None = exactly the calls without masks.
     ``old_logps`` (optional): float32 [N, sum A_b], every column's log-prob under the policy that drew the samples; branch b reads its
     columns at the same offset, and stats[4] is the exact KL(old || new), the mean over samples and branches, instead of the k3
-    sample estimate -- every other output unchanged in its bits (etm_ppo_loss_kl, masks or not); None = exactly the calls without."""
+    sample estimate -- every other output unchanged in its bits (etm_ppo_loss_kl, masks or not); None = exactly the calls without.
+    ``kl_coef`` (optional, `kl_penalty`; needs ``old_logps``): a device tensor of one float32 read in place; every branch's loss is then
+    its loss + coef * its share of stats[4], with that sum's gradient (etm_ppo_loss_kl_penalty); None = exactly the calls without."""
+    if kl_coef is not None and old_logps is None:
+        raise ValueError("ppo_loss: kl_coef without old_logps (the KL penalty is a term in the exact KL); pass the rollout's log-prob rows")
     if stats3 is None:
         stats3 = adv_stats(adv)
     if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
@@ -2479,7 +2507,7 @@ def ppo_loss(logits_list, value, actions, old_logp, adv, old_value, clip, vf_coe
             shifts.append(total)
             total += int(lg.shape[1])
         if old_logps is not None:      # (the mask shift and the column offset of a branch are the same number)
-            mk = lambda b: (action_mask, shifts[b] if action_mask is not None else 0, old_logps, shifts[b])
+            mk = lambda b: (action_mask, shifts[b] if action_mask is not None else 0, old_logps, shifts[b], kl_coef)
         else:
             mk = lambda b: (action_mask, shifts[b])
     else:

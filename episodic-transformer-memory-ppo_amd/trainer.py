@@ -50,7 +50,7 @@ from etm import ops
 from etm.ops import WindowSpec
 from etm.optim import AdaptiveLr, FlatAdamW, KlGate
 from model import ActorCriticModel, IndexedObservations
-from utils import (adaptive_lr_section, exact_kl_section, kl_estimator_section, normalization_section, polynomial_decay, process_episode_info, target_kl_rows,
+from utils import (adaptive_lr_section, exact_kl_section, kl_estimator_section, kl_penalty_section, kl_penalty_step, normalization_section, polynomial_decay, process_episode_info, target_kl_rows,
                    target_kl_section)
 from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
 from checkpoint import check_checkpoint_config, segment_first_worker_id
@@ -300,6 +300,29 @@ def check_exact_kl_config(config, box: bool = False, world: int = 1) -> bool:
     return True
 
 
+def check_kl_penalty_config(config, world: int = 1):
+    """The optional key ``kl_penalty`` (a number: a fixed coefficient, or {coef, target, high, low, up, down, min, max};
+    utils.kl_penalty_section) -> the section with its float32 constants, or None when the key is absent (nothing is allocated, no launch
+    is added or exchanged).  With the key the loss is L + coef * KL(old || new), the exact KL that ``exact_kl: true`` reports -- the key
+    implies that plumbing for every policy kind -- and with ``target`` the coefficient adapts once per update (utils.kl_penalty_step).
+    Refused, each before anything is built and each with what to do instead: what utils.kl_penalty_section refuses; an explicit
+    ``exact_kl: false`` or ``kl_estimator: k3`` next to the key (they contradict it); the key in a data-parallel run (``world`` > 1),
+    as for the other KL keys."""
+    out = kl_penalty_section(config)
+    if out is None:
+        return None
+    if "exact_kl" in config and not exact_kl_section(config):
+        raise ValueError("kl_penalty next to exact_kl: false: the two keys contradict each other (the penalty is a term in the exact KL "
+                         "and switches its plumbing on); remove exact_kl, or remove kl_penalty to train without the penalty")
+    if "kl_estimator" in config and kl_estimator_section(config) == "k3":
+        raise ValueError("kl_penalty next to kl_estimator: k3: the two keys contradict each other (the penalty is a term in the exact KL, "
+                         "k3 is the sample estimate); remove kl_estimator, or remove kl_penalty to train without the penalty")
+    if world > 1:
+        raise ValueError("kl_penalty in a data-parallel run: every rank would penalise and adapt on the KL of its own minibatches "
+                         "(agreeing on one KL over the ranks is not built); remove the key, or train on one device")
+    return out
+
+
 def time_major(table, src):
     """The host table ``src`` [W, S(, B)] in the layout and type of the fixed-address device table ``table`` [S, W(, B)]."""
     x = torch.as_tensor(np.asarray(src), dtype=table.dtype)
@@ -346,6 +369,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # (a supplied environment says what the policy is once it is looked at, below; else the config does, before anything is built)
         check_kl_estimator_config(config, env is not None or check_box_policy(config) is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_exact_kl_config(config, check_box_policy(config) is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
+        pen_cfg = check_kl_penalty_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         # training state that a checkpoint carries over (trainer_parts._CheckpointResume): completed updates, the training segment (the
         # number of resumes so far; its environments' worker ids start at segment_first_worker_id), the last episodes' infos
         self.update_index, self.segment, self._episode_infos = 0, 0, deque(maxlen=100)
@@ -445,6 +469,14 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # exact_kl: a Box policy takes exactly that path; a categorical one (masked or not) stages every column's log-prob at the four
         # categorical sampling sites, the buffer carries the rows, the categorical loss kernels reduce the exact KL into stats[4]
         exact = check_exact_kl_config(config, self.box is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
+        # kl_penalty implies the exact KL's plumbing (the penalty is coef times the very number that column 4 then holds).  The
+        # coefficient lives in ONE device float32 at a fixed address: the loss kernels read it in place, in eager steps and in captured
+        # graphs alike; the host writes it between updates only (_adapt_kl_penalty).  ``last_kl_penalty``: what the last update used and
+        # decided (None without the key: nothing is allocated)
+        exact = exact or pen_cfg is not None
+        self._kl_pen, self._kl_coef, self.last_kl_penalty = pen_cfg, None, None
+        if pen_cfg is not None:
+            self._kl_coef = torch.full((1,), pen_cfg["coef"], dtype=torch.float32, device=device)
         self._kl_analytic = self._kl_analytic or (exact and self.box is not None)
         self._kl_exact_cat = exact and self.box is None
 
@@ -1448,6 +1480,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             self.last_adaptive_lr = {"lr": float(self.optimizer.lr_dev.item()), "raised": raised, "lowered": lowered,
                                      "kl_low": ad.kl_low, "kl_high": ad.kl_high}
         train_info = (self._tg_stats_tab[:rows] if tables else torch.stack(stats[:rows])).cpu().numpy()
+        if self._kl_pen is not None:
+            self._adapt_kl_penalty(train_info)
         self._bank_pos = self._row_stats = None
         self._mb_stats3 = self._epoch_stats3 = None
         grad_info = {}
@@ -1455,6 +1489,19 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             allnorms = (self._tg_norm_tab[:rows] if tables else torch.stack(norms[:rows])).cpu().numpy()
             grad_info = {k: allnorms[:, i].tolist() for i, k in enumerate(self._grad_keys)}
         return [row for row in train_info], grad_info
+
+    def _adapt_kl_penalty(self, train_info):
+        """kl_penalty, once per update, behind the optimisation phase's one read-back and outside every graph: kl = float32(the mean of
+        column 4 over the returned rows, accumulated in double and rounded once); with ``target`` the next update's coefficient is
+        utils.kl_penalty_step's, written into the device word the loss kernels read in place."""
+        coef = np.float32(self._kl_coef.item())
+        kl = np.float32(np.asarray(train_info)[:, 4].astype(np.float64).mean())
+        nxt, moved = (coef, 0)
+        if self._kl_pen["adaptive"]:
+            nxt, moved = kl_penalty_step(coef, kl, self._kl_pen)
+            if np.float32(nxt) != coef:
+                self._kl_coef.fill_(float(nxt))
+        self.last_kl_penalty = {"coef": float(coef), "next_coef": float(np.float32(nxt)), "kl": float(kl), "moved": int(moved)}
 
     def _train_mini_batch(self, samples: dict, learning_rate: float, clip_range: float, beta: float):
         """One optimiser step on one minibatch.  Returns a device tensor [policy, value, loss, entropy, kl, clip_frac]."""
@@ -1496,11 +1543,15 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                 raise RuntimeError("Box policy: the minibatch is outside the fused Gaussian heads + loss kernel")
             # kl_estimator: analytic: the minibatch's old means and the update's log-std snapshot; stats[4] is then the exact KL
             old = dict(old_mean=mb["means"], old_log_std=self.buffer.old_log_std) if self._kl_analytic else {}
+            if self._kl_coef is not None:      # (kl_penalty: the coefficient's device word, read in place)
+                old["kl_coef"] = self._kl_coef
             return ops.heads_ppo_loss_gaussian(h, m.lin_policy, m.lin_value, m.policy_branches[0], m.policy_log_std, m.value, mb["actions"],
                                                mb["log_probs"], mb["advantages"], mb["values"], clip_range, self.config["value_loss_coefficient"],
                                                beta, stats3, dyn=dyn, unit_grad=True, **old)
         # exact_kl (categorical): the minibatch's rows of the rollout's log-probs; stats[4] is then the exact KL on all three routes
         old = dict(old_logps=mb["old_logps"]) if self._kl_exact_cat else {}
+        if self._kl_coef is not None:          # (kl_penalty: the coefficient's device word, read in place on all three routes)
+            old["kl_coef"] = self._kl_coef
         if self.config.get("fused_heads_loss", True):
             h, _ = m.forward_state(obs, spec)
             branch = m.policy_branches[0] if len(m.policy_branches) == 1 else list(m.policy_branches)

@@ -214,6 +214,8 @@ class _RunOutputs:
             self.writer.add_scalar("other/learning_rate", self.last_adaptive_lr["lr"], update)
             self.writer.add_scalar("other/lr_raised", self.last_adaptive_lr["raised"], update)
             self.writer.add_scalar("other/lr_lowered", self.last_adaptive_lr["lowered"], update)
+        if self.last_kl_penalty is not None:             # (kl_penalty: the coefficient the update's steps used)
+            self.writer.add_scalar("other/kl_coef", self.last_kl_penalty["coef"], update)
         if self.last_valid_action_share is not None:     # (action_masks: mean share of allowed actions in the rollout's words)
             self.writer.add_scalar("other/valid_action_share", self.last_valid_action_share, update)
         if self.buffer.return_norm is not None:          # (the scale the last rollout's rewards were multiplied with)
@@ -349,6 +351,8 @@ class _CheckpointResume:
         opt, buf = self.optimizer, self.buffer
         out = {"flat_params": opt.flat_params.data_ptr(), "flat_grads": opt.flat_grads.data_ptr(), "exp_avg": opt.exp_avg.data_ptr(),
                "exp_avg_sq": opt.exp_avg_sq.data_ptr(), "step_dev": opt.step_dev.data_ptr(), "lr_dev": opt.lr_dev.data_ptr()}
+        if self._kl_coef is not None:
+            out["kl_coef"] = self._kl_coef.data_ptr()
         out.update({"param:" + n: p.data_ptr() for n, p in self.model.named_parameters()})
         out.update({"buffer:" + n: b.data_ptr() for n, b in self.model.named_buffers()})
         if buf.ret_stats is not None:
@@ -361,7 +365,8 @@ class _CheckpointResume:
         completed updates and ``segment``; the config; the arena layout [(parameter name, shape)]; the flat parameter arena; the
         optimiser state (FlatAdamW.state_dict: both moments, step, lr, hyper-parameters); the model's buffers outside the arena (the
         ``obs_norm_*`` triple and table); ``buffer.ret_stats``; torch's CPU and device generator states; the last <= 100 episode
-        infos; the digests of the three arenas.
+        infos; the digests of the three arenas; with ``kl_penalty`` one more entry, ``kl_coef``, the float32 coefficient of the next
+        update (absent without the key).
         Before anything is written etm_arena_digest runs over the three arenas: a non-finite value in any of them raises
         FloatingPointError (arena, count, update) and leaves both files of the previous save as they are.
         Episodes in flight are NOT saved (environment state in general cannot be): a resumed run starts every worker on a fresh
@@ -384,6 +389,8 @@ class _CheckpointResume:
             "rng_cpu": torch.get_rng_state().numpy().copy(), "rng_device": torch.cuda.get_rng_state(self.device).numpy().copy(),
             "episode_infos": list(self._episode_infos), "digests": {n: [int(w) for w in digests[n]] for n in self.ARENAS},
         }
+        if self._kl_coef is not None:       # (kl_penalty: the coefficient is trainer state; no entry without the key)
+            state["kl_coef"] = np.float32(self._kl_coef.item())
         ck.write_checkpoint(path, state)
         print("Checkpoint saved to " + path)
         return path
@@ -446,6 +453,14 @@ class _CheckpointResume:
                 b.copy_(torch.from_numpy(np.ascontiguousarray(state["buffers"][name])))
             if buf.ret_stats is not None:
                 buf.ret_stats.copy_(torch.from_numpy(np.ascontiguousarray(state["ret_stats"])))
+            if self._kl_coef is not None:
+                # kl_penalty: the current config wins (as for adaptive_lr) -- a fixed coefficient is the config's, an adaptive one
+                # continues from the checkpoint's; a checkpoint without the entry starts at the config's coef
+                start = self._kl_pen["coef"]
+                if self._kl_pen["adaptive"] and state.get("kl_coef") is not None:
+                    start = float(np.float32(state["kl_coef"]))
+                self._kl_coef.fill_(start)
+                self.last_kl_penalty = None
         after = self._fixed_addresses()
         assert after == before, "a load moved " + ", ".join(k for k in before if before[k] != after.get(k))
         digests = self._arena_digests()

@@ -5,7 +5,9 @@ KL-adaptive learning rate and adaptive_lr_step is its rule, the one host definit
 kl_estimator_section reads which KL both rules see and gaussian_kl is the exact KL of a Box policy's Gaussians, the one host
 definition of what the Gaussian heads + loss kernel reduces; exact_kl_section reads the key that switches the exact KL on for every
 policy kind and categorical_kl is the exact KL of Discrete / MultiDiscrete policies, the one host definition of what the categorical
-loss kernels reduce."""
+loss kernels reduce; kl_penalty_section reads the KL penalty of the loss, kl_penalty_step is the rule that adapts its coefficient once
+per update, and categorical_kl_grad / gaussian_kl_grad are the gradients of the two exact KLs, the one host definition of what the
+penalty kernels add to d logits."""
 import numpy as np
 import torch
 from torch import nn
@@ -288,6 +290,142 @@ def categorical_kl(old_logps, logits, sizes, mask_words=None, dtype=np.float64):
             total = dt(total + np.where(v, t, dt(0)).sum(dtype=dt))
             off += size
     return dt(total / dt(N * len(sizes)))
+
+
+def _valid_columns(mask_words, N, A, what):
+    if mask_words is None:
+        return np.ones((N, A), dtype=bool)
+    if A > 63:
+        raise ValueError(f"{what}: a mask word describes at most 63 columns, not {A}")
+    words = np.asarray(mask_words).astype(np.int64).reshape(-1)
+    if words.shape != (N,):
+        raise ValueError(f"{what}: mask_words [{N}] expected, got {words.shape}")
+    return ((words[:, None] >> np.arange(A, dtype=np.int64)[None, :]) & 1).astype(bool)
+
+
+def categorical_kl_grad(old_logps, logits, sizes, mask_words=None, dtype=np.float64):
+    """d (sum_n sum_b KL_nb) / d logits, [N, sum(sizes)] in numpy ``dtype``, KL_nb as in ``categorical_kl`` (whose operands these are;
+    that function returns the sum divided by N B) -- the one host definition of what the penalty kernels add to d logits (PEN;
+    csrc/heads_loss.hip, csrc/ppo_loss.hip).  Per sample and branch with valid columns V, p_j = exp(l_j), p_old_j = exp(old_j) (+0 at
+    -inf):
+        d KL_nb / d logit_k = p_k - p_old_k  for k in V,   exactly 0 for k outside V
+    -- from sum_{j in V} p_old_j (old_j - l_j) with d l_j / d logit_k = delta_jk - p_k and sum_V p_old = 1.  No case at d < -60: there
+    p_old -> 0 and the term's derivative is p_k.  Equal policies give exactly 0, and so does a branch with one valid action (1 - 1)."""
+    dt = np.dtype(dtype).type
+    lo, lg = np.asarray(old_logps, dtype=dt), np.asarray(logits, dtype=dt)
+    sizes = tuple(int(a) for a in sizes)
+    if lg.ndim != 2 or lo.shape != lg.shape or not sizes or min(sizes) <= 0 or sum(sizes) != lg.shape[1]:
+        raise ValueError(f"categorical_kl_grad: old_logps and logits [N, {sum(sizes)}] for branches {sizes} expected, got {lo.shape}, {lg.shape}")
+    N, A = lg.shape
+    valid = _valid_columns(mask_words, N, A, "categorical_kl_grad")
+    out, off = np.zeros((N, A), dtype=dt), 0
+    with np.errstate(all="ignore"):
+        for size in sizes:
+            v = valid[:, off:off + size]
+            if not v.any(axis=1).all():
+                raise ValueError("categorical_kl_grad: a branch without a valid action")
+            l = np.where(v, lg[:, off:off + size], dt(-np.inf))
+            mx = l.max(axis=1, keepdims=True)
+            logp = l - (mx + np.log(np.exp(l - mx).sum(axis=1, keepdims=True, dtype=dt)))
+            out[:, off:off + size] = np.where(v, np.exp(logp) - np.exp(lo[:, off:off + size]), dt(0))
+            off += size
+    return out
+
+
+def gaussian_kl_grad(old_mean, old_log_std, mean, log_std, dtype=np.float64):
+    """(d / d mean [N, A], d / d log_std [A]) of sum_n KL_n, KL_n as in ``gaussian_kl`` (which returns the sum divided by N), in numpy
+    ``dtype`` -- the one host definition of what heads_loss_gaussian_kl_penalty_kernel adds.  With d_a = old_log_std_a - log_std_a and
+    q_na = (old_mean_na - mean_na) / sigma_a:
+        d KL_n / d mean_na = -q_na / sigma_a,    d KL_n / d log_std_a = -expm1(2 d_a) - q_na^2
+    -- the second is 1 - (sigma_old^2 + (mu_old - mu)^2) / sigma^2, written so that equal policies give exactly 0."""
+    dt = np.dtype(dtype).type
+    mo, mu = np.asarray(old_mean, dtype=dt), np.asarray(mean, dtype=dt)
+    lo, ls = np.asarray(old_log_std, dtype=dt).reshape(-1), np.asarray(log_std, dtype=dt).reshape(-1)
+    if mo.ndim != 2 or mo.shape != mu.shape or lo.shape != (mo.shape[1],) or ls.shape != lo.shape:
+        raise ValueError(f"gaussian_kl_grad: means [N, A] and log-stds [A] expected, got {mo.shape}, {lo.shape}, {mu.shape}, {ls.shape}")
+    sigma = np.exp(ls)
+    q = (mo - mu) / sigma
+    d_mean = -q / sigma
+    d_ls = (-np.expm1(dt(2) * (lo - ls))[None, :] - q * q).sum(axis=0, dtype=dt)
+    return d_mean.astype(dt), d_ls.astype(dt)
+
+
+KL_PENALTY_DEFAULTS = dict(high=2.0, low=0.5, up=1.5, down=0.5, min=1.0e-4, max=100.0)
+
+
+def kl_penalty_section(config: dict):
+    """The optional key ``kl_penalty`` (a number: a fixed coefficient, or {coef, target, high, low, up, down, min, max}) -> {"coef",
+    "adaptive", "target", "high", "low", "up", "down", "min", "max", "kl_high", "kl_low"}, or None when the key is absent.  ``coef`` alone
+    is a fixed coefficient (0 allowed); with ``target`` the coefficient adapts once per update (``kl_penalty_step``) and the other
+    sub-keys default to RLlib's thresholds and factors (high 2.0, low 0.5, up 1.5, down 0.5) and this build's clamps (min 1e-4, max
+    100).  ``kl_high`` = float32(high * target) and ``kl_low`` = float32(low * target), each product formed once in double and rounded
+    once; ``coef``, ``up``, ``down``, ``min`` and ``max`` are each rounded to float32 (python floats that hold a float32 exactly).
+    Without ``target`` the rule's entries are None."""
+    sec = config.get("kl_penalty")
+    if sec is None:
+        return None
+    if not isinstance(sec, dict):
+        sec = {"coef": sec}
+    known = ("coef", "target") + tuple(KL_PENALTY_DEFAULTS)
+    unknown = sorted(set(sec) - set(known))
+    if unknown:
+        raise ValueError(f"kl_penalty: unknown keys {unknown} (known: {list(known)}); remove them")
+    if "coef" not in sec:
+        raise ValueError("kl_penalty: the section needs `coef` (the coefficient of the KL term, e.g. 0.2); add it, or remove the key to "
+                         "train without the penalty")
+    coef = sec["coef"]
+    if not _finite_number(coef) or not coef >= 0 or not np.isfinite(_f32(coef)):
+        raise ValueError(f"kl_penalty.coef must be a finite number >= 0 (also as a float32), got {coef!r}; remove the key to train without "
+                         "the penalty")
+    coef32 = float(np.float32(coef))
+    if "target" not in sec:
+        extra = sorted(set(sec) - {"coef"})
+        if extra:
+            raise ValueError(f"kl_penalty: {extra} belong to the adaptive coefficient and need `target` (the KL the coefficient is steered "
+                             "to, e.g. 0.01); add it, or remove them for a fixed coefficient")
+        return dict(coef=coef32, adaptive=False, target=None, kl_high=None, kl_low=None, **{k: None for k in KL_PENALTY_DEFAULTS})
+    v = {k: sec.get(k, d) for k, d in KL_PENALTY_DEFAULTS.items()}
+    v["target"] = sec["target"]
+    for k in ("target",) + tuple(KL_PENALTY_DEFAULTS):
+        if not _positive_number(v[k]) or not _f32(v[k]) > 0 or not np.isfinite(_f32(v[k])):
+            hint = "remove it for a fixed coefficient" if k == "target" else f"leave it out for the default {KL_PENALTY_DEFAULTS[k]!r}"
+            raise ValueError(f"kl_penalty.{k} must be a finite number > 0 (also as a float32), got {v[k]!r}; {hint}")
+    if coef32 == 0:
+        raise ValueError("kl_penalty: coef 0 with `target`: a multiplication never leaves 0, the coefficient could not adapt; start at a "
+                         "positive coef (e.g. 0.2), or remove target for a fixed coefficient of 0")
+    kl_low, kl_high = _f32(float(v["target"]) * float(v["low"])), _f32(float(v["target"]) * float(v["high"]))
+    if not np.isfinite(kl_high) or not kl_low < kl_high:
+        raise ValueError(f"kl_penalty: float32(low * target) = {float(kl_low)!r} must lie below float32(high * target) = {float(kl_high)!r}, "
+                         "both finite; choose low < high (the defaults are 0.5 and 2.0)")
+    if not np.float32(v["up"]) > 1:
+        raise ValueError(f"kl_penalty.up must be > 1 (also as a float32; the coefficient rises by it above high * target), got {v['up']!r}; "
+                         "leave it out for the default 1.5")
+    if not np.float32(v["down"]) < 1:
+        raise ValueError(f"kl_penalty.down must be < 1 (also as a float32; the coefficient falls by it below low * target), got "
+                         f"{v['down']!r}; leave it out for the default 0.5")
+    if not np.float32(v["min"]) <= np.float32(v["max"]):
+        raise ValueError(f"kl_penalty.min = {v['min']!r} must not exceed kl_penalty.max = {v['max']!r}; exchange them, or leave them out "
+                         "for the defaults 1e-4 and 100")
+    if not np.float32(v["min"]) <= np.float32(coef32) <= np.float32(v["max"]):
+        raise ValueError(f"kl_penalty: the start value float32(coef) = {coef32!r} lies outside [min, max] = [{float(np.float32(v['min']))!r}, "
+                         f"{float(np.float32(v['max']))!r}]; move coef into the range, or widen kl_penalty.min / kl_penalty.max")
+    return dict(coef=coef32, adaptive=True, target=float(v["target"]), high=float(v["high"]), low=float(v["low"]),
+                up=float(np.float32(v["up"])), down=float(np.float32(v["down"])), min=float(np.float32(v["min"])),
+                max=float(np.float32(v["max"])), kl_high=float(kl_high), kl_low=float(kl_low))
+
+
+def kl_penalty_step(coef32, kl32, rule):
+    """The rule of an adaptive ``kl_penalty`` for one update, in numpy float32 (PPO paper section 4; RLlib's thresholds, with clamps):
+    ``coef32`` the coefficient the update used, ``kl32`` float32(the mean of the update's returned kl column), ``rule`` of
+    ``kl_penalty_section`` -> (the next update's coefficient, -1 cut | 0 kept | +1 raised).  kl > kl_high: min(max, coef * up);
+    kl < kl_low: max(min, coef * down); a kl at a limit and a NaN change nothing.  The direction says what was decided, also where a
+    clamp left the value as it was."""
+    coef, kl = np.float32(coef32), np.float32(kl32)
+    if kl > np.float32(rule["kl_high"]):
+        return np.minimum(np.float32(rule["max"]), np.float32(coef * np.float32(rule["up"]))), 1
+    if kl < np.float32(rule["kl_low"]):
+        return np.maximum(np.float32(rule["min"]), np.float32(coef * np.float32(rule["down"]))), -1
+    return coef, 0
 
 
 class Module(nn.Module):

@@ -400,7 +400,8 @@ int etm_heads_loss_branched_masked(const float *pre_p, const float *pre_v, const
  * (the limit p_old_j -> 0); every term >= 0, no term of size 1 cancels, equal policies give exactly 0, a masked-out column is skipped,
  * a branch with one valid action contributes 0.  out8[4] = pol_scale sum_n sum_b KL_nb (pol_scale = 1 / (N B): the mean over samples
  * AND branches, the convention of the k3 value; the joint KL is B times it), out8[6] = the k3 value that the twin puts into out8[4].
- * A statistic only: the loss, gm_p, gm_v, out8[0..3], out8[5] and the twin's row are the twin's bit for bit; sums
+ * A statistic only (unless `kl_penalty`, the *_kl_penalty entries): the loss, gm_p, gm_v, out8[0..3], out8[5] and the twin's row are
+ * the twin's bit for bit; sums
  * [etm_heads_loss_kl_row_floats = etm_heads_loss_row_floats + 1] carries the raw KL sum as its last element.  ETM_EINVAL: NULL or
  * 4-byte-misaligned old_logps, old_logps_stride < A; ETM_EUNSUPPORTED exactly where the twin returns it. */
 int etm_heads_loss_kl_row_floats(int hid, int A);
@@ -439,7 +440,7 @@ int etm_heads_loss_gaussian(const float *pre_p, const float *pre_v, const float 
  * the policy that drew the samples (the *_gaussian_means sampling entries), and old_log_std [A], a snapshot of its log sigma.  The
  * same launch also reduces KL(old || new) = mean_n sum_a [(expm1(2 d_a) / 2 - d_a) + ((old_mean_na - mean_na) / sigma_a)^2 / 2],
  * d_a = old_log_std_a - log_std_a (nothing cancels: equal policies give exactly 0): out8[4] = that KL, out8[6] = the k3 sample
- * estimate that etm_heads_loss_gaussian puts into out8[4].  A statistic only: the loss, gm_p, gm_v, out8[0..3], out8[5] and the
+ * estimate that etm_heads_loss_gaussian puts into out8[4].  A statistic only (unless `kl_penalty`): the loss, gm_p, gm_v, out8[0..3], out8[5] and the
  * etm_heads_loss_gaussian row are that entry's bit for bit; sums [etm_heads_loss_gaussian_kl_row_floats =
  * etm_heads_loss_gaussian_row_floats + 1] carries the raw KL sum as its last element.  Shapes: etm_heads_loss_supported_gaussian.
  * ETM_EINVAL: NULL or 4-byte-misaligned old_mean / old_log_std, old_mean_stride < A. */
@@ -452,6 +453,40 @@ int etm_heads_loss_gaussian_kl(const float *pre_p, const float *pre_v, const flo
                                float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
                                float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid, int A,
                                const float *old_mean, int64_t old_mean_stride, const float *old_log_std, void *stream);
+/* The KL penalty (`kl_penalty`; added with the ABI left at 61 -- no signature above changes): each entry is its *_kl twin's argument
+ * list with kl_coef in front of the stream, ONE device float32 (4-byte aligned) that the kernels read in place, in eager launches and
+ * captured graphs alike.  The loss is L + coef K, K = out8[4], the exact KL exactly as the twin reports it, coef = *kl_coef:
+ *   categorical  d K / d logit_k = pol_scale (p_k - p_old_k) on a branch's valid columns, exactly 0 on the others
+ *   Box          d K / d mean_na = ent_scale (-q_na / sigma_a), d K / d log_std_a = ent_scale sum_n (-expm1(2 d_a) - q_na^2),
+ *                q_na = (old_mean_na - mean_na) / sigma_a, d_a = old_log_std_a - log_std_a
+ * join d logits before the heads' backward: gm_p, gm_v and every gradient element of sums (Box: d log_std too) are those of L + coef K;
+ * equal policies add exactly 0.  out8[2] = the twin's loss + coef K, out8[7] = coef (0 elsewhere); logits, value, out8[0, 1, 3, 4, 5,
+ * 6], the statistic sums, the row layout and the workspace are the twin's.  No launch is added.  ETM_EINVAL with nothing launched: a
+ * NULL or 4-byte-misaligned kl_coef; otherwise exactly the twin's refusals. */
+int etm_heads_loss_kl_penalty(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                              const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
+                              const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
+                              const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
+                              float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
+                              float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid, int A,
+                              const int64_t *action_mask, const float *old_logps, int64_t old_logps_stride, const float *kl_coef,
+                              void *stream);
+int etm_heads_loss_branched_kl_penalty(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                       const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
+                                       const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
+                                       const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale,
+                                       float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v,
+                                       float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes,
+                                       int N, int hid, const int32_t *branch_sizes, int n_branches, const int64_t *action_mask,
+                                       const float *old_logps, int64_t old_logps_stride, const float *kl_coef, void *stream);
+int etm_heads_loss_gaussian_kl_penalty(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
+                                       const float *bb, const float *wv, const float *bv, const float *xact, int64_t action_stride,
+                                       const float *log_std, const float *old_logp, int64_t logp_stride, const float *adv,
+                                       const float *old_value, const float *adv_stats3, double clip, float vf_coef, float beta,
+                                       float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p,
+                                       float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace,
+                                       int64_t workspace_bytes, int N, int hid, int A, const float *old_mean, int64_t old_mean_stride,
+                                       const float *old_log_std, const float *kl_coef, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Weight gradients of the dense layers of one optimisation step as ONE grouped launch: replaces the `dW = dy^T x` products that
@@ -1196,6 +1231,17 @@ int etm_ppo_loss_kl(const float *logits, const int64_t *actions, int64_t action_
                     float *d_value, void *partials, int64_t partials_bytes, const double *dyn_clip_beta, int N, int A,
                     const int64_t *action_mask, int mask_shift, const float *old_logps, int64_t old_logps_stride, int logps_off,
                     void *stream);
+/* The KL penalty (`kl_penalty`) of one branch: etm_ppo_loss_kl with kl_coef in front of the stream (etm_heads_loss_kl_penalty: ONE
+ * device float32 read in place).  d_logits is the gradient of L + coef K (a valid column gains coef pol_scale (p_j - p_old_j), an
+ * invalid one stays exactly 0), out8[2] = the twin's loss + coef out8[4], out8[7] = coef; d_value, out8[0, 1, 3, 4, 5, 6] and the
+ * partial slots are the twin's.  The term's p_j is exp((logit_j - max) - log(sum)), exact at the largest column (logit_j - lse would
+ * carry half a spacing of lse, times coef): equal policies add a term of rounding size here, exactly 0 in the fused entries.  ETM_EINVAL with nothing launched: a NULL or 4-byte-misaligned kl_coef; otherwise the twin's refusals. */
+int etm_ppo_loss_kl_penalty(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
+                            int64_t logp_stride, const float *adv, const float *old_value, const float *value, const float *adv_stats3,
+                            double clip, float vf_coef, float beta, float pol_scale, float ent_scale, float val_scale, int include_value,
+                            float *out8, float *d_logits, float *d_value, void *partials, int64_t partials_bytes,
+                            const double *dyn_clip_beta, int N, int A, const int64_t *action_mask, int mask_shift, const float *old_logps,
+                            int64_t old_logps_stride, int logps_off, const float *kl_coef, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Gradient exchange of the data-parallel optimiser step (absent upstream -- the call goes between
