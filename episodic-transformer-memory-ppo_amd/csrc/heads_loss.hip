@@ -558,145 +558,158 @@ constexpr int HL_SAMPLES_PER_WG = 8;      // two samples per wave: the pass is a
 }  // namespace
 
 extern "C" int etm_heads_loss_supported(int N, int hid, int A) { return N > 0 && hid > 0 && hid % 64 == 0 && hid / 64 <= HL_MAXC && A > 0 && A <= HL_MAXA; }
-extern "C" int etm_heads_loss_row_floats(int hid, int A) { return (3 + A) * hid + A + 1 + 5; }
-extern "C" int64_t etm_heads_loss_workspace_bytes(int N, int hid, int A) {
-  if (!etm_heads_loss_supported(N, hid, A)) return 0;
-  return (int64_t)((N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG) * etm_heads_loss_row_floats(hid, A) * (int64_t)sizeof(float);
-}
-// (the exact categorical KL: the etm_heads_loss row followed by the raw KL sum)
-extern "C" int etm_heads_loss_kl_row_floats(int hid, int A) { return etm_heads_loss_row_floats(hid, A) + 1; }
-extern "C" int64_t etm_heads_loss_kl_workspace_bytes(int N, int hid, int A) {
-  if (!etm_heads_loss_supported(N, hid, A)) return 0;
-  return (int64_t)((N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG) * etm_heads_loss_kl_row_floats(hid, A) * (int64_t)sizeof(float);
-}
 extern "C" int etm_heads_loss_supported_gaussian(int N, int hid, int A) { return A <= ETM_MAX_BOX && etm_heads_loss_supported(N, hid, A); }
-extern "C" int etm_heads_loss_gaussian_row_floats(int hid, int A) { return etm_heads_loss_row_floats(hid, A) + A; }
-extern "C" int64_t etm_heads_loss_gaussian_workspace_bytes(int N, int hid, int A) {
-  if (!etm_heads_loss_supported_gaussian(N, hid, A)) return 0;
-  return (int64_t)((N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG) * etm_heads_loss_gaussian_row_floats(hid, A) * (int64_t)sizeof(float);
-}
-extern "C" int etm_heads_loss_gaussian_kl_row_floats(int hid, int A) { return etm_heads_loss_gaussian_row_floats(hid, A) + 1; }
-extern "C" int64_t etm_heads_loss_gaussian_kl_workspace_bytes(int N, int hid, int A) {
-  if (!etm_heads_loss_supported_gaussian(N, hid, A)) return 0;
-  return (int64_t)((N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG) * etm_heads_loss_gaussian_kl_row_floats(hid, A) * (int64_t)sizeof(float);
+extern "C" int etm_heads_loss_supported_branched(int N, int hid, const int32_t *branch_sizes, int n_branches) {
+  const int A = etm_branches_total(branch_sizes, n_branches);
+  return A > 0 && n_branches <= HL_MAXA && etm_heads_loss_supported(N, hid, A);
 }
 
-// pre_p / pre_v [N, hid] = h Wlp^T / h Wlv^T (no bias).  Outputs: gm_p / gm_v [N, hid] = d loss / d (pre + bias) of the two hidden
-// heads; sums [etm_heads_loss_row_floats] = [d b_lp (hid) | d b_lv (hid) | d wv (hid) | d Wb (A x hid) | d bb (A) | d bv | 5 raw sums];
-// out8 = (policy, value, loss, entropy, kl, clip fraction, 0, 0); logits [N, A] / value [N]: optional (NULL: not written).
-// Scales as in etm_ppo_loss (pol_scale = 1 / N for one branch, ent_scale = val_scale = 1 / N).
-static int heads_loss_impl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb, const float *bb,
-                              const float *wv, const float *bv, const int64_t *actions, int64_t action_stride, const float *old_logp,
-                              int64_t logp_stride, const float *adv, const float *old_value, const float *adv_stats3, double clip, float vf_coef,
-                              float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v,
-                              float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
-                              int A, const int32_t *branch_sizes, int n_branches, const float *xact, const float *log_std,
-                              const int64_t *action_mask, void *stream, const float *old_mean = nullptr, int64_t old_mean_stride = 0,
-                              const float *old_log_std = nullptr, const float *old_logps = nullptr, int64_t old_logps_stride = 0,
-                              const float *kl_coef = nullptr) {
-  (void)hipGetLastError();
-  const bool gauss = xact != nullptr;                  // Box: float actions xact and log_std instead of the int64 actions
-  const bool kl = old_mean != nullptr;                 // Box with the exact KL: the row gains the KL sum
-  const bool ckl = old_logps != nullptr;               // categorical with the exact KL: likewise
-  if (ckl && gauss) return ETM_EINVAL;
-  const bool pen = kl_coef != nullptr;                 // `kl_penalty`: the KL kernels with the term's gradient
-  if (pen && !kl && !ckl) return ETM_EINVAL;
-  if (!pre_p || !pre_v || !b_lp || !b_lv || !wb || !bb || !wv || !bv || !(gauss ? (const void *)log_std : (const void *)actions) || !old_logp ||
-      !adv || !old_value || !adv_stats3 || !gm_p || !gm_v || !sums || !out8 || !workspace)
+namespace {
+// The row of sums: [d b_lp (hid) | d b_lv (hid) | d wv (hid) | d Wb (A x hid) | d bb (A) | d bv | 5 raw sums], then d log_std (A) for a Box
+// policy, then the raw KL sum with the exact KL.  The workspace holds one row per workgroup.
+int hl_row_floats(int hid, int A, bool gauss, bool kl) { return (3 + A) * hid + A + 1 + 5 + (gauss ? A : 0) + (kl ? 1 : 0); }
+int64_t hl_workspace_bytes(int N, int hid, int A, bool gauss, bool kl) {
+  if (!(gauss ? etm_heads_loss_supported_gaussian(N, hid, A) : etm_heads_loss_supported(N, hid, A))) return 0;
+  return (int64_t)((N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG) * hl_row_floats(hid, A, gauss, kl) * (int64_t)sizeof(float);
+}
+}  // namespace
+extern "C" int etm_heads_loss_row_floats(int hid, int A) { return hl_row_floats(hid, A, false, false); }
+extern "C" int etm_heads_loss_kl_row_floats(int hid, int A) { return hl_row_floats(hid, A, false, true); }
+extern "C" int etm_heads_loss_gaussian_row_floats(int hid, int A) { return hl_row_floats(hid, A, true, false); }
+extern "C" int etm_heads_loss_gaussian_kl_row_floats(int hid, int A) { return hl_row_floats(hid, A, true, true); }
+extern "C" int64_t etm_heads_loss_workspace_bytes(int N, int hid, int A) { return hl_workspace_bytes(N, hid, A, false, false); }
+extern "C" int64_t etm_heads_loss_kl_workspace_bytes(int N, int hid, int A) { return hl_workspace_bytes(N, hid, A, false, true); }
+extern "C" int64_t etm_heads_loss_gaussian_workspace_bytes(int N, int hid, int A) { return hl_workspace_bytes(N, hid, A, true, false); }
+extern "C" int64_t etm_heads_loss_gaussian_kl_workspace_bytes(int N, int hid, int A) { return hl_workspace_bytes(N, hid, A, true, true); }
+
+namespace {
+// One call of any of the eleven entries: the operands by name (what an entry does not take stays NULL / 0) and what the entry requires.
+struct HlCall {
+  HlParams p{};                           // the kernels' operands, filled by name (partials = the workspace; clip: by the launcher)
+  double clip = 0;
+  float *sums = nullptr, *out8 = nullptr;
+  int64_t workspace_bytes = 0;
+  const int32_t *branch_sizes = nullptr;  // with `branched`; p.A is then sum(sizes), set by the validator
+  int n_branches = 1;
+  void *stream = nullptr;
+  // what the calling entry takes: Box (xact, log_std) | branch_sizes, n_branches instead of A | a mandatory action_mask (the exact-KL
+  // entries take one or NULL) | the old policy (old_logps, or old_mean / old_log_std of a Box policy) | kl_coef
+  bool gauss = false, branched = false, need_mask = false, kl = false, pen = false;
+};
+// a record `c` with the arguments that all eleven entries name alike
+#define HL_CALL(c)                                                                                                                        \
+  HlCall c;                                                                                                                               \
+  c.p.pre_p = pre_p; c.p.pre_v = pre_v; c.p.b_lp = b_lp; c.p.b_lv = b_lv; c.p.wb = wb; c.p.bb = bb; c.p.wv = wv; c.p.bv = bv;            \
+  c.p.action_stride = action_stride; c.p.old_logp = old_logp; c.p.logp_stride = logp_stride; c.p.adv = adv; c.p.old_value = old_value;    \
+  c.p.adv_stats3 = adv_stats3; c.clip = clip; c.p.vf_coef = vf_coef; c.p.beta = beta; c.p.pol_scale = pol_scale;                         \
+  c.p.ent_scale = ent_scale; c.p.val_scale = val_scale; c.p.dyn = dyn_clip_beta; c.p.gm_p = gm_p; c.p.gm_v = gm_v; c.sums = sums;        \
+  c.out8 = out8; c.p.logits = logits; c.p.value = value; c.p.partials = (float *)workspace; c.workspace_bytes = workspace_bytes;         \
+  c.p.N = N; c.p.hid = hid; c.stream = stream
+
+bool hl_misaligned4(const void *q) { return ((uintptr_t)q & 3u) != 0; }
+
+// Every refusal of every entry, in the one order that include/etm_hip.h states ("Refusals of the loss entries").
+int hl_validate(HlCall &c) {
+  HlParams &p = c.p;
+  if (c.pen && (!p.kl_coef || hl_misaligned4(p.kl_coef))) return ETM_EINVAL;
+  if (c.kl && !c.gauss && (!p.old_logps || hl_misaligned4(p.old_logps) || (!c.branched && p.old_logps_stride < p.A))) return ETM_EINVAL;
+  if (c.gauss && !p.xact) return ETM_EINVAL;
+  if (c.kl && c.gauss && (!p.old_mean || !p.old_log_std || hl_misaligned4(p.old_mean) || hl_misaligned4(p.old_log_std))) return ETM_EINVAL;
+  if (c.need_mask && !p.amask) return ETM_EINVAL;
+  if (c.branched) {
+    if (!etm_heads_loss_supported_branched(p.N, p.hid, c.branch_sizes, c.n_branches)) return ETM_EUNSUPPORTED;
+    p.A = etm_branches_total(c.branch_sizes, c.n_branches);
+    if (p.action_stride < c.n_branches || p.logp_stride < c.n_branches || (c.kl && p.old_logps_stride < p.A)) return ETM_EINVAL;
+  }
+  if (c.gauss && (p.action_stride < p.A || p.logp_stride < 1 || (c.kl && p.old_mean_stride < p.A))) return ETM_EINVAL;
+  if (!p.pre_p || !p.pre_v || !p.b_lp || !p.b_lv || !p.wb || !p.bb || !p.wv || !p.bv || !(c.gauss ? (const void *)p.log_std : (const void *)p.actions) ||
+      !p.old_logp || !p.adv || !p.old_value || !p.adv_stats3 || !p.gm_p || !p.gm_v || !c.sums || !c.out8 || !p.partials)
     return ETM_EINVAL;
-  if (action_mask && gauss) return ETM_EINVAL;
-  if (const int rc = etm_action_mask_check(action_mask, A)) return rc;
-  if (!(gauss ? etm_heads_loss_supported_gaussian(N, hid, A) : etm_heads_loss_supported(N, hid, A))) return ETM_EUNSUPPORTED;
-  if (workspace_bytes < (kl      ? etm_heads_loss_gaussian_kl_workspace_bytes(N, hid, A)
-                         : ckl   ? etm_heads_loss_kl_workspace_bytes(N, hid, A)
-                         : gauss ? etm_heads_loss_gaussian_workspace_bytes(N, hid, A)
-                                 : etm_heads_loss_workspace_bytes(N, hid, A)))
-    return ETM_EWORKSPACE;
-  HlParams p{};
+  if ((p.old_logps && c.gauss) || (c.pen && !c.kl)) return ETM_EINVAL;      // (no entry fills the record like this)
+  if (p.amask && c.gauss) return ETM_EINVAL;
+  if (const int rc = etm_action_mask_check(p.amask, p.A)) return rc;
+  if (!(c.gauss ? etm_heads_loss_supported_gaussian(p.N, p.hid, p.A) : etm_heads_loss_supported(p.N, p.hid, p.A))) return ETM_EUNSUPPORTED;
+  if (c.workspace_bytes < hl_workspace_bytes(p.N, p.hid, p.A, c.gauss, c.kl)) return ETM_EWORKSPACE;
+  return 0;
+}
+
+// The kernel of a variant: Box (plain, exact KL, penalty), or categorical [plain, exact KL, penalty][branched][masked].
+using HlKernel = void (*)(const HlParams);
+template <int HC>
+HlKernel hl_kernel(bool gauss, int level, bool branched, bool masked) {
+  static constexpr HlKernel box[3] = {heads_loss_kernel<HC, false, true>, heads_loss_gaussian_kl_kernel<HC>, heads_loss_gaussian_kl_penalty_kernel<HC>};
+  static constexpr HlKernel cat[3][2][2] = {
+      {{heads_loss_kernel<HC, false>, heads_loss_masked_kernel<HC, false>}, {heads_loss_kernel<HC, true>, heads_loss_masked_kernel<HC, true>}},
+      {{heads_loss_kl_kernel<HC, false, false>, heads_loss_kl_kernel<HC, false, true>},
+       {heads_loss_kl_kernel<HC, true, false>, heads_loss_kl_kernel<HC, true, true>}},
+      {{heads_loss_kl_penalty_kernel<HC, false, false>, heads_loss_kl_penalty_kernel<HC, false, true>},
+       {heads_loss_kl_penalty_kernel<HC, true, false>, heads_loss_kl_penalty_kernel<HC, true, true>}}};
+  return gauss ? box[level] : cat[level][branched][masked];
+}
+
+// The one launcher: validate, fill HlParams, the pass, the reduction.
+int hl_launch(HlCall &c) {
+  (void)hipGetLastError();
+  if (const int rc = hl_validate(c)) return rc;
+  HlParams &p = c.p;
   EtmBranches br;
-  if (const int rc = etm_branches_make(branch_sizes, n_branches, A, &br)) return rc;
-  const bool branched = br.n > 1;
+  if (const int rc = etm_branches_make(c.branch_sizes, c.n_branches, p.A, &br)) return rc;
   p.nbr = br.n;
   for (int b = 0, j = 0; b < br.n; ++b) {
     p.branch_off[b] = j;
     for (int k = 0; k < br.size[b]; ++k, ++j) p.col_branch[j] = b;
   }
-  p.pre_p = pre_p; p.pre_v = pre_v; p.b_lp = b_lp; p.b_lv = b_lv; p.wb = wb; p.bb = bb; p.wv = wv; p.bv = bv;
-  p.actions = (const long long *)actions; p.action_stride = action_stride; p.old_logp = old_logp; p.logp_stride = logp_stride;
-  p.adv = adv; p.old_value = old_value; p.adv_stats3 = adv_stats3;
-  p.clip = (float)clip; p.clip_lo = (float)(1.0 - clip); p.clip_hi = (float)(1.0 + clip);
-  p.vf_coef = vf_coef; p.beta = beta; p.pol_scale = pol_scale; p.ent_scale = ent_scale; p.val_scale = val_scale; p.dyn = dyn_clip_beta;
-  p.gm_p = gm_p; p.gm_v = gm_v; p.logits = logits; p.value = value; p.partials = (float *)workspace;
-  p.N = N; p.A = A; p.hid = hid; p.samples_per_wg = HL_SAMPLES_PER_WG;
-  p.xact = xact; p.log_std = log_std; p.amask = (const long long *)action_mask;
-  p.old_mean = old_mean; p.old_mean_stride = old_mean_stride; p.old_log_std = old_log_std;
-  p.old_logps = old_logps; p.old_logps_stride = old_logps_stride; p.kl_coef = kl_coef;
-  const bool masked = action_mask != nullptr;
-  const int n_wg = (N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG;
-  const int row = kl ? etm_heads_loss_gaussian_kl_row_floats(hid, A) : ckl ? etm_heads_loss_kl_row_floats(hid, A)
-                  : gauss ? etm_heads_loss_gaussian_row_floats(hid, A) : etm_heads_loss_row_floats(hid, A);
+  p.clip = (float)c.clip; p.clip_lo = (float)(1.0 - c.clip); p.clip_hi = (float)(1.0 + c.clip);
+  p.samples_per_wg = HL_SAMPLES_PER_WG;
+  const int level = c.pen ? 2 : c.kl ? 1 : 0;
+  const bool branched = br.n > 1, masked = p.amask != nullptr;
+  HlKernel pass = nullptr;
+  switch (p.hid / 64) {
+    case 1: pass = hl_kernel<1>(c.gauss, level, branched, masked); break;
+    case 2: pass = hl_kernel<2>(c.gauss, level, branched, masked); break;
+    case 3: pass = hl_kernel<3>(c.gauss, level, branched, masked); break;
+    case 4: pass = hl_kernel<4>(c.gauss, level, branched, masked); break;
+    case 5: pass = hl_kernel<5>(c.gauss, level, branched, masked); break;
+    case 6: pass = hl_kernel<6>(c.gauss, level, branched, masked); break;
+    case 7: pass = hl_kernel<7>(c.gauss, level, branched, masked); break;
+    case 8: pass = hl_kernel<8>(c.gauss, level, branched, masked); break;
+    default: return ETM_EUNSUPPORTED;
+  }
+  const int n_wg = (p.N + HL_SAMPLES_PER_WG - 1) / HL_SAMPLES_PER_WG;
+  const int row = hl_row_floats(p.hid, p.A, c.gauss, c.kl);
   const size_t lds = 4 * (size_t)row * sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)c.stream;
   {
     EtmProfScope prof(ETM_K_PPO_LOSS, st);
-    switch (hid / 64) {
-#define HL_CASE(HC_)                                                                                              \
-  case HC_:                                                                                                       \
-    if (pen && kl) hipLaunchKernelGGL((heads_loss_gaussian_kl_penalty_kernel<HC_>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (pen && masked && branched) hipLaunchKernelGGL((heads_loss_kl_penalty_kernel<HC_, true, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (pen && masked) hipLaunchKernelGGL((heads_loss_kl_penalty_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (pen && branched) hipLaunchKernelGGL((heads_loss_kl_penalty_kernel<HC_, true, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (pen) hipLaunchKernelGGL((heads_loss_kl_penalty_kernel<HC_, false, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (kl) hipLaunchKernelGGL((heads_loss_gaussian_kl_kernel<HC_>), dim3((unsigned)n_wg), dim3(256), lds, st, p);  \
-    else if (gauss) hipLaunchKernelGGL((heads_loss_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (ckl && masked && branched) hipLaunchKernelGGL((heads_loss_kl_kernel<HC_, true, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (ckl && masked) hipLaunchKernelGGL((heads_loss_kl_kernel<HC_, false, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (ckl && branched) hipLaunchKernelGGL((heads_loss_kl_kernel<HC_, true, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (ckl) hipLaunchKernelGGL((heads_loss_kl_kernel<HC_, false, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (masked && branched) hipLaunchKernelGGL((heads_loss_masked_kernel<HC_, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (masked) hipLaunchKernelGGL((heads_loss_masked_kernel<HC_, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else if (branched) hipLaunchKernelGGL((heads_loss_kernel<HC_, true>), dim3((unsigned)n_wg), dim3(256), lds, st, p); \
-    else hipLaunchKernelGGL((heads_loss_kernel<HC_, false>), dim3((unsigned)n_wg), dim3(256), lds, st, p);         \
-    break;
-      HL_CASE(1) HL_CASE(2) HL_CASE(3) HL_CASE(4) HL_CASE(5) HL_CASE(6) HL_CASE(7) HL_CASE(8)
-#undef HL_CASE
-      default: return ETM_EUNSUPPORTED;
-    }
+    hipLaunchKernelGGL(pass, dim3((unsigned)n_wg), dim3(256), lds, st, p);
   }
-  int rc = etm_launch_status();
-  if (rc) return rc;
+  if (const int rc = etm_launch_status()) return rc;
   EtmProfScope prof(ETM_K_PPO_FINAL, st);
-  if (pen && kl)
-    hipLaunchKernelGGL(heads_reduce_kl_penalty_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg, row, A,
-                       hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8, kl_coef);
-  else if (pen)
-    hipLaunchKernelGGL(heads_reduce_categorical_kl_penalty_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace,
-                       n_wg, row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8, kl_coef);
-  else if (kl)
-    hipLaunchKernelGGL(heads_reduce_kl_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg, row, A, hid,
-                       vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8);
-  else if (ckl)
-    hipLaunchKernelGGL(heads_reduce_categorical_kl_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg,
-                       row, A, hid, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8);
-  else
-    hipLaunchKernelGGL(heads_reduce_kernel, dim3((unsigned)((row + 63) / 64)), dim3(1024), 0, st, (const float *)workspace, n_wg, row, A, hid, vf_coef,
-                       beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, sums, out8);
+  const dim3 grid((unsigned)((row + 63) / 64));
+  if (c.pen) {
+    const auto reduce = c.gauss ? heads_reduce_kl_penalty_kernel : heads_reduce_categorical_kl_penalty_kernel;
+    hipLaunchKernelGGL(reduce, grid, dim3(1024), 0, st, (const float *)p.partials, n_wg, row, p.A, p.hid, p.vf_coef, p.beta, p.pol_scale,
+                       p.ent_scale, p.val_scale, p.dyn, c.sums, c.out8, p.kl_coef);
+  } else {
+    const auto reduce = !c.kl ? heads_reduce_kernel : c.gauss ? heads_reduce_kl_kernel : heads_reduce_categorical_kl_kernel;
+    hipLaunchKernelGGL(reduce, grid, dim3(1024), 0, st, (const float *)p.partials, n_wg, row, p.A, p.hid, p.vf_coef, p.beta, p.pol_scale,
+                       p.ent_scale, p.val_scale, p.dyn, c.sums, c.out8);
+  }
   return etm_launch_status();
 }
+}  // namespace
 
+// The entries (include/etm_hip.h documents each): fill the record by name, say what the entry takes, launch.
 extern "C" int etm_heads_loss(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb, const float *bb,
                               const float *wv, const float *bv, const int64_t *actions, int64_t action_stride, const float *old_logp,
                               int64_t logp_stride, const float *adv, const float *old_value, const float *adv_stats3, double clip, float vf_coef,
                               float beta, float pol_scale, float ent_scale, float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v,
                               float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
                               int A, void *stream) {
-  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
-                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, A, nullptr, 1, nullptr, nullptr, nullptr, stream);
+  HL_CALL(c);
+  c.p.actions = (const long long *)actions; c.p.A = A;
+  return hl_launch(c);
 }
-// Invalid-action masks: etm_heads_loss with action_mask [N] int64, the samples' words (bit j = action j was allowed; at least one bit
-// below A set, the taken action among them).  Log-sum-exp, log-prob and entropy run over the valid actions only, and d loss / d logit
-// of an invalid action is exactly 0 -- so are its rows of d Wb and d bb from that sample.  ETM_EINVAL: NULL or misaligned mask.
 extern "C" int etm_heads_loss_masked(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
                                      const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
                                      const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
@@ -704,18 +717,11 @@ extern "C" int etm_heads_loss_masked(const float *pre_p, const float *pre_v, con
                                      float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
                                      float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid, int A,
                                      const int64_t *action_mask, void *stream) {
-  if (!action_mask) return ETM_EINVAL;
-  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
-                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, A, nullptr, 1, nullptr, nullptr, action_mask, stream);
+  HL_CALL(c);
+  c.p.actions = (const long long *)actions; c.p.A = A; c.p.amask = (const long long *)action_mask; c.need_mask = true;
+  return hl_launch(c);
 }
-
-// MultiDiscrete: wb / bb = the branches' heads concatenated ([sum(sizes), hid], [sum(sizes)]); actions / old_logp rows carry one entry
-// per branch (action_stride, logp_stride >= n_branches).  pol_scale = 1 / (N B), ent_scale = val_scale = 1 / N for ref_algo.ppo_loss.
-extern "C" int etm_heads_loss_supported_branched(int N, int hid, const int32_t *branch_sizes, int n_branches) {
-  const int A = etm_branches_total(branch_sizes, n_branches);
-  return A > 0 && n_branches <= HL_MAXA && etm_heads_loss_supported(N, hid, A);
-}
+// MultiDiscrete: wb / bb = the branches' heads concatenated; actions / old_logp rows carry one entry per branch
 extern "C" int etm_heads_loss_branched(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
                                        const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
                                        const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
@@ -723,14 +729,10 @@ extern "C" int etm_heads_loss_branched(const float *pre_p, const float *pre_v, c
                                        float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
                                        float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid,
                                        const int32_t *branch_sizes, int n_branches, void *stream) {
-  if (!etm_heads_loss_supported_branched(N, hid, branch_sizes, n_branches)) return ETM_EUNSUPPORTED;
-  if (action_stride < n_branches || logp_stride < n_branches) return ETM_EINVAL;
-  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
-                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, nullptr, nullptr, stream);
+  HL_CALL(c);
+  c.p.actions = (const long long *)actions; c.branch_sizes = branch_sizes; c.n_branches = n_branches; c.branched = true;
+  return hl_launch(c);
 }
-// Invalid-action masks: etm_heads_loss_branched with action_mask [N] int64 (bit j = column j of the concatenated heads; branch b owns
-// bits [off_b, off_b + A_b)), per branch as in etm_heads_loss_masked.
 extern "C" int etm_heads_loss_branched_masked(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
                                               const float *bb, const float *wv, const float *bv, const int64_t *actions,
                                               int64_t action_stride, const float *old_logp, int64_t logp_stride, const float *adv,
@@ -739,23 +741,12 @@ extern "C" int etm_heads_loss_branched_masked(const float *pre_p, const float *p
                                               float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace,
                                               int64_t workspace_bytes, int N, int hid, const int32_t *branch_sizes, int n_branches,
                                               const int64_t *action_mask, void *stream) {
-  if (!action_mask) return ETM_EINVAL;
-  if (!etm_heads_loss_supported_branched(N, hid, branch_sizes, n_branches)) return ETM_EUNSUPPORTED;
-  if (action_stride < n_branches || logp_stride < n_branches) return ETM_EINVAL;
-  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
-                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, nullptr,
-                         action_mask, stream);
+  HL_CALL(c);
+  c.p.actions = (const long long *)actions; c.branch_sizes = branch_sizes; c.n_branches = n_branches; c.branched = true;
+  c.p.amask = (const long long *)action_mask; c.need_mask = true;
+  return hl_launch(c);
 }
-
-// The exact categorical KL (`exact_kl: true`): etm_heads_loss_masked / etm_heads_loss_branched_masked with action_mask optional (NULL:
-// no masks) and old_logps [N, A] (row stride old_logps_stride >= A floats; A = sum(sizes)), every column's log-prob under the policy
-// that drew the samples (the *_logps sampling entries; -inf where the column was masked out).  The same launch also reduces
-// sum_n sum_b KL_nb, KL_nb = the sum over the branch's valid columns of etm_categorical_kl_term: out8[4] = that sum * pol_scale (the
-// mean over samples and branches, the k3 value's convention), out8[6] = the k3 value the twin puts into out8[4].  A statistic only:
-// the loss, gm_p, gm_v, out8[0..3], out8[5] and the twin's row are the twin's bit for bit; sums [etm_heads_loss_kl_row_floats =
-// etm_heads_loss_row_floats + 1] carries the raw KL sum as its last element.  ETM_EINVAL: NULL or 4-byte-misaligned old_logps, a
-// stride below A; otherwise the twin's refusals.
+// The exact categorical KL (`exact_kl: true`): the masked entries with action_mask optional (NULL: no masks) and old_logps [N, A]
 extern "C" int etm_heads_loss_kl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
                                  const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
                                  const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
@@ -763,11 +754,10 @@ extern "C" int etm_heads_loss_kl(const float *pre_p, const float *pre_v, const f
                                  float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
                                  float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid, int A,
                                  const int64_t *action_mask, const float *old_logps, int64_t old_logps_stride, void *stream) {
-  if (!old_logps || ((uintptr_t)old_logps & 3u) || old_logps_stride < A) return ETM_EINVAL;
-  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
-                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, A, nullptr, 1, nullptr, nullptr, action_mask, stream, nullptr, 0, nullptr, old_logps,
-                         old_logps_stride);
+  HL_CALL(c);
+  c.p.actions = (const long long *)actions; c.p.A = A; c.p.amask = (const long long *)action_mask;
+  c.p.old_logps = old_logps; c.p.old_logps_stride = old_logps_stride; c.kl = true;
+  return hl_launch(c);
 }
 extern "C" int etm_heads_loss_branched_kl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
                                           const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
@@ -777,19 +767,12 @@ extern "C" int etm_heads_loss_branched_kl(const float *pre_p, const float *pre_v
                                           float *sums, float *out8, float *logits, float *value, void *workspace, int64_t workspace_bytes,
                                           int N, int hid, const int32_t *branch_sizes, int n_branches, const int64_t *action_mask,
                                           const float *old_logps, int64_t old_logps_stride, void *stream) {
-  if (!old_logps || ((uintptr_t)old_logps & 3u)) return ETM_EINVAL;
-  if (!etm_heads_loss_supported_branched(N, hid, branch_sizes, n_branches)) return ETM_EUNSUPPORTED;
-  if (action_stride < n_branches || logp_stride < n_branches || old_logps_stride < etm_branches_total(branch_sizes, n_branches))
-    return ETM_EINVAL;
-  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
-                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, nullptr,
-                         action_mask, stream, nullptr, 0, nullptr, old_logps, old_logps_stride);
+  HL_CALL(c);
+  c.p.actions = (const long long *)actions; c.branch_sizes = branch_sizes; c.n_branches = n_branches; c.branched = true; c.p.amask = (const long long *)action_mask;
+  c.p.old_logps = old_logps; c.p.old_logps_stride = old_logps_stride; c.kl = true;
+  return hl_launch(c);
 }
-
-// Box policies (diagonal Gaussian, A <= 8): wb / bb = the mean head [A, hid], [A]; xact [N, A] (row stride action_stride >= A) the
-// stored raw actions; log_std [A]; old_logp [N] (logp_stride).  sums [etm_heads_loss_gaussian_row_floats] = the etm_heads_loss row
-// followed by d log_std (A); scales as in etm_heads_loss (pol_scale = ent_scale = val_scale = 1 / N).
+// Box policies (diagonal Gaussian, A <= 8): wb / bb = the mean head; xact [N, A] the stored raw actions; old_logp [N] the joint log-probs
 extern "C" int etm_heads_loss_gaussian(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
                                        const float *bb, const float *wv, const float *bv, const float *xact, int64_t action_stride,
                                        const float *log_std, const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
@@ -797,19 +780,11 @@ extern "C" int etm_heads_loss_gaussian(const float *pre_p, const float *pre_v, c
                                        float val_scale, const double *dyn_clip_beta, float *gm_p, float *gm_v, float *sums, float *out8,
                                        float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid, int A,
                                        void *stream) {
-  if (!xact) return ETM_EINVAL;
-  if (action_stride < A || logp_stride < 1) return ETM_EINVAL;
-  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, nullptr, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
-                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, A, nullptr, 1, xact, log_std, nullptr, stream);
+  HL_CALL(c);
+  c.p.xact = xact; c.p.log_std = log_std; c.p.A = A; c.gauss = true;
+  return hl_launch(c);
 }
-
-// etm_heads_loss_gaussian with the exact KL statistic: old_mean [N, A] (row stride old_mean_stride >= A floats) the means of the policy
-// that drew the samples, old_log_std [A] its log sigma (a snapshot: log_std moves during the update).  sums
-// [etm_heads_loss_gaussian_kl_row_floats] = the etm_heads_loss_gaussian row followed by the raw KL sum; out8[4] = the exact
-// KL(old || new) (mean over the samples, summed over the dimensions), out8[6] = the k3 sample estimate; the loss, every gradient and
-// every other statistic are etm_heads_loss_gaussian's, bit for bit.  ETM_EINVAL: NULL or 4-byte-misaligned old_mean / old_log_std, a
-// stride below A.
+// ... with the exact KL: old_mean [N, A] the means of the policy that drew the samples, old_log_std [A] a snapshot of its log sigma
 extern "C" int etm_heads_loss_gaussian_kl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
                                           const float *bb, const float *wv, const float *bv, const float *xact, int64_t action_stride,
                                           const float *log_std, const float *old_logp, int64_t logp_stride, const float *adv,
@@ -818,19 +793,12 @@ extern "C" int etm_heads_loss_gaussian_kl(const float *pre_p, const float *pre_v
                                           float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace,
                                           int64_t workspace_bytes, int N, int hid, int A, const float *old_mean, int64_t old_mean_stride,
                                           const float *old_log_std, void *stream) {
-  if (!xact || !old_mean || !old_log_std) return ETM_EINVAL;
-  if (((uintptr_t)old_mean | (uintptr_t)old_log_std) & 3u) return ETM_EINVAL;
-  if (action_stride < A || logp_stride < 1 || old_mean_stride < A) return ETM_EINVAL;
-  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, nullptr, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
-                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, A, nullptr, 1, xact, log_std, nullptr, stream, old_mean, old_mean_stride, old_log_std);
+  HL_CALL(c);
+  c.p.xact = xact; c.p.log_std = log_std; c.p.A = A; c.gauss = true;
+  c.p.old_mean = old_mean; c.p.old_mean_stride = old_mean_stride; c.p.old_log_std = old_log_std; c.kl = true;
+  return hl_launch(c);
 }
-
-// `kl_penalty`: the three exact-KL entries with the loss L + coef * K, K = out8[4] (the exact KL as the twin reports it), coef = *kl_coef,
-// ONE device float32 that the kernels read in place (eager launches and captured graphs alike; the host rewrites it between updates).
-// The gradient outputs (gm_p, gm_v, every gradient element of sums) are those of L + coef * K; out8[2] includes coef * K, out8[7] = coef;
-// out8[0, 1, 3, 4, 5, 6], logits, value, the statistic sums and the row layout are the twin's.  ETM_EINVAL with nothing launched: a NULL
-// or 4-byte-misaligned kl_coef; otherwise exactly the twin's refusals.
+// `kl_penalty`: the three exact-KL entries with the loss L + coef * K, K = out8[4], coef = *kl_coef, ONE device float32 read in place
 extern "C" int etm_heads_loss_kl_penalty(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
                                          const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
                                          const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
@@ -839,12 +807,10 @@ extern "C" int etm_heads_loss_kl_penalty(const float *pre_p, const float *pre_v,
                                          float *logits, float *value, void *workspace, int64_t workspace_bytes, int N, int hid, int A,
                                          const int64_t *action_mask, const float *old_logps, int64_t old_logps_stride, const float *kl_coef,
                                          void *stream) {
-  if (!kl_coef || ((uintptr_t)kl_coef & 3u)) return ETM_EINVAL;
-  if (!old_logps || ((uintptr_t)old_logps & 3u) || old_logps_stride < A) return ETM_EINVAL;
-  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
-                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, A, nullptr, 1, nullptr, nullptr, action_mask, stream, nullptr, 0, nullptr, old_logps,
-                         old_logps_stride, kl_coef);
+  HL_CALL(c);
+  c.p.actions = (const long long *)actions; c.p.A = A; c.p.amask = (const long long *)action_mask;
+  c.p.old_logps = old_logps; c.p.old_logps_stride = old_logps_stride; c.kl = true; c.p.kl_coef = kl_coef; c.pen = true;
+  return hl_launch(c);
 }
 extern "C" int etm_heads_loss_branched_kl_penalty(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
                                                   const float *bb, const float *wv, const float *bv, const int64_t *actions,
@@ -855,17 +821,11 @@ extern "C" int etm_heads_loss_branched_kl_penalty(const float *pre_p, const floa
                                                   int64_t workspace_bytes, int N, int hid, const int32_t *branch_sizes, int n_branches,
                                                   const int64_t *action_mask, const float *old_logps, int64_t old_logps_stride,
                                                   const float *kl_coef, void *stream) {
-  if (!kl_coef || ((uintptr_t)kl_coef & 3u)) return ETM_EINVAL;
-  if (!old_logps || ((uintptr_t)old_logps & 3u)) return ETM_EINVAL;
-  if (!etm_heads_loss_supported_branched(N, hid, branch_sizes, n_branches)) return ETM_EUNSUPPORTED;
-  if (action_stride < n_branches || logp_stride < n_branches || old_logps_stride < etm_branches_total(branch_sizes, n_branches))
-    return ETM_EINVAL;
-  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, actions, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
-                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, etm_branches_total(branch_sizes, n_branches), branch_sizes, n_branches, nullptr, nullptr,
-                         action_mask, stream, nullptr, 0, nullptr, old_logps, old_logps_stride, kl_coef);
+  HL_CALL(c);
+  c.p.actions = (const long long *)actions; c.branch_sizes = branch_sizes; c.n_branches = n_branches; c.branched = true; c.p.amask = (const long long *)action_mask;
+  c.p.old_logps = old_logps; c.p.old_logps_stride = old_logps_stride; c.kl = true; c.p.kl_coef = kl_coef; c.pen = true;
+  return hl_launch(c);
 }
-// (Box: d log_std, the A row elements behind the statistic sums, carries the term's gradient too)
 extern "C" int etm_heads_loss_gaussian_kl_penalty(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
                                                   const float *bb, const float *wv, const float *bv, const float *xact, int64_t action_stride,
                                                   const float *log_std, const float *old_logp, int64_t logp_stride, const float *adv,
@@ -874,12 +834,9 @@ extern "C" int etm_heads_loss_gaussian_kl_penalty(const float *pre_p, const floa
                                                   float *gm_v, float *sums, float *out8, float *logits, float *value, void *workspace,
                                                   int64_t workspace_bytes, int N, int hid, int A, const float *old_mean,
                                                   int64_t old_mean_stride, const float *old_log_std, const float *kl_coef, void *stream) {
-  if (!kl_coef || ((uintptr_t)kl_coef & 3u)) return ETM_EINVAL;
-  if (!xact || !old_mean || !old_log_std) return ETM_EINVAL;
-  if (((uintptr_t)old_mean | (uintptr_t)old_log_std) & 3u) return ETM_EINVAL;
-  if (action_stride < A || logp_stride < 1 || old_mean_stride < A) return ETM_EINVAL;
-  return heads_loss_impl(pre_p, pre_v, b_lp, b_lv, wb, bb, wv, bv, nullptr, action_stride, old_logp, logp_stride, adv, old_value, adv_stats3,
-                         clip, vf_coef, beta, pol_scale, ent_scale, val_scale, dyn_clip_beta, gm_p, gm_v, sums, out8, logits, value, workspace,
-                         workspace_bytes, N, hid, A, nullptr, 1, xact, log_std, nullptr, stream, old_mean, old_mean_stride, old_log_std,
-                         nullptr, 0, kl_coef);
+  HL_CALL(c);
+  c.p.xact = xact; c.p.log_std = log_std; c.p.A = A; c.gauss = true;
+  c.p.old_mean = old_mean; c.p.old_mean_stride = old_mean_stride; c.p.old_log_std = old_log_std; c.kl = true; c.p.kl_coef = kl_coef; c.pen = true;
+  return hl_launch(c);
 }
+#undef HL_CALL

@@ -345,111 +345,107 @@ extern "C" int etm_adv_stats_ws(const float *adv, int N, float *stats3, void *wo
 
 extern "C" int64_t etm_ppo_loss_workspace_bytes(int N) { return N <= 0 ? 0 : (int64_t)((N + 255) / 256) * 8 * sizeof(float); }
 static bool al16(const void *q) { return ((uintptr_t)q % 16) == 0; }
-
-static int ppo_loss_impl(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
-                            int64_t logp_stride, const float *adv, const float *old_value, const float *value,
-                            const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
-                            float val_scale, int include_value, float *out8, float *d_logits, float *d_value, void *partials,
-                            int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, const int64_t *action_mask,
-                            int mask_shift, void *stream, const float *old_logps = nullptr, int64_t old_logps_stride = 0,
-                            int logps_off = 0, const float *kl_coef = nullptr) {
-  (void)hipGetLastError();  // drop stale sticky errors of earlier, unrelated runtime calls
-  if (!logits || !actions || !old_logp || !adv || !adv_stats3 || !out8 || !d_logits || !partials) return ETM_EINVAL;
-  if (include_value && (!old_value || !value || !d_value)) return ETM_EINVAL;
-  if (N <= 0 || A <= 0) return ETM_EINVAL;
-  if (action_mask && (mask_shift < 0 || mask_shift + A > 63)) return ETM_EUNSUPPORTED;
-  if (const int rc = etm_action_mask_check(action_mask, A)) return rc;
-  if (partials_bytes < etm_ppo_loss_workspace_bytes(N)) return ETM_EWORKSPACE;
+namespace {
+// One call of any of the four entries: the kernels' operands by name (what an entry does not take stays NULL / 0), what only the host needs,
+// and what the entry takes: a mandatory action_mask (the exact-KL entries take one or NULL) | old_logps, its stride and offset | kl_coef
+struct PlCall {
   LossParams p{};
-  p.logits = logits; p.actions = (const long long *)actions; p.action_stride = action_stride;
-  p.old_logp = old_logp; p.logp_stride = logp_stride; p.adv = adv; p.old_value = old_value; p.value = value;
-  p.adv_stats3 = adv_stats3;
-  p.clip = (float)clip; p.clip_lo = (float)(1.0 - clip); p.clip_hi = (float)(1.0 + clip);
-  p.vf_coef = vf_coef; p.beta = beta; p.pol_scale = pol_scale; p.ent_scale = ent_scale; p.val_scale = val_scale;
-  p.dyn = dyn_clip_beta;
-  p.include_value = include_value; p.d_logits = d_logits; p.d_value = d_value; p.partials = (float *)partials;
-  p.N = N; p.A = A; p.amask = (const long long *)action_mask; p.mask_shift = mask_shift;
-  p.old_logps = old_logps; p.old_logps_stride = old_logps_stride; p.logps_off = logps_off; p.kl_coef = kl_coef;
-  const bool kl = old_logps != nullptr;                // the exact KL: always the one-sample form
-  const bool pen = kl_coef != nullptr;                 // `kl_penalty`: the KL kernels with the term's gradient
-  if (pen && !kl) return ETM_EINVAL;
-  // four samples per thread when every operand can move in 16-byte pieces and there are enough samples to fill the chip
-  const bool vec = !kl && !action_mask && A == 3 && N % 4 == 0 && N >= (1 << 16) && action_stride == 1 && logp_stride == 1 && al16(logits) && al16(actions) &&
-                   al16(old_logp) && al16(adv) && al16(d_logits) && (!include_value || (al16(value) && al16(old_value) && al16(d_value)));
-  const int nb = vec ? (N / 4 + 255) / 256 : (N + 255) / 256;
-  hipStream_t st = (hipStream_t)stream;
+  double clip = 0;
+  float *out8 = nullptr;
+  int64_t partials_bytes = 0;
+  void *stream = nullptr;
+  bool need_mask = false, kl = false, pen = false;
+};
+// a record `c` with the arguments that all four entries name alike
+#define PL_CALL(c)                                                                                                                         \
+  PlCall c;                                                                                                                                \
+  c.p.logits = logits; c.p.actions = (const long long *)actions; c.p.action_stride = action_stride; c.p.old_logp = old_logp;              \
+  c.p.logp_stride = logp_stride; c.p.adv = adv; c.p.old_value = old_value; c.p.value = value; c.p.adv_stats3 = adv_stats3; c.clip = clip; \
+  c.p.vf_coef = vf_coef; c.p.beta = beta; c.p.pol_scale = pol_scale; c.p.ent_scale = ent_scale; c.p.val_scale = val_scale;                \
+  c.p.include_value = include_value; c.out8 = out8; c.p.d_logits = d_logits; c.p.d_value = d_value; c.p.partials = (float *)partials;     \
+  c.partials_bytes = partials_bytes; c.p.dyn = dyn_clip_beta; c.p.N = N; c.p.A = A; c.stream = stream
+// Every refusal of every entry, in the one order that include/etm_hip.h states ("Refusals of the loss entries").
+int pl_validate(const PlCall &c) {
+  const LossParams &p = c.p;
+  if (c.pen && (!p.kl_coef || ((uintptr_t)p.kl_coef & 3u))) return ETM_EINVAL;
+  if (c.kl && (!p.old_logps || ((uintptr_t)p.old_logps & 3u) || p.logps_off < 0 || p.old_logps_stride < (int64_t)p.logps_off + p.A)) return ETM_EINVAL;
+  if (c.need_mask && !p.amask) return ETM_EINVAL;
+  if (!p.logits || !p.actions || !p.old_logp || !p.adv || !p.adv_stats3 || !c.out8 || !p.d_logits || !p.partials) return ETM_EINVAL;
+  if (p.include_value && (!p.old_value || !p.value || !p.d_value)) return ETM_EINVAL;
+  if (p.N <= 0 || p.A <= 0) return ETM_EINVAL;
+  if (p.amask && (p.mask_shift < 0 || p.mask_shift + p.A > 63)) return ETM_EUNSUPPORTED;
+  if (const int rc = etm_action_mask_check(p.amask, p.A)) return rc;
+  if (c.partials_bytes < etm_ppo_loss_workspace_bytes(p.N)) return ETM_EWORKSPACE;
+  return c.pen && !c.kl ? ETM_EINVAL : 0;      // (no entry fills the record like this)
+}
+// The one launcher: validate, the pass, the finalisation.
+int pl_launch(PlCall &c) {
+  (void)hipGetLastError();  // drop stale sticky errors of earlier, unrelated runtime calls
+  if (const int rc = pl_validate(c)) return rc;
+  LossParams &p = c.p;
+  p.clip = (float)c.clip; p.clip_lo = (float)(1.0 - c.clip); p.clip_hi = (float)(1.0 + c.clip);
+  const bool masked = p.amask != nullptr;
+  // four samples per thread when every operand can move in 16-byte pieces and there are enough samples to fill the chip (the exact KL:
+  // always the one-sample form)
+  const bool vec = !c.kl && !masked && p.A == 3 && p.N % 4 == 0 && p.N >= (1 << 16) && p.action_stride == 1 && p.logp_stride == 1 &&
+                   al16(p.logits) && al16(p.actions) && al16(p.old_logp) && al16(p.adv) && al16(p.d_logits) &&
+                   (!p.include_value || (al16(p.value) && al16(p.old_value) && al16(p.d_value)));
+  const int nb = vec ? (p.N / 4 + 255) / 256 : (p.N + 255) / 256;
+  // [plain, exact KL, penalty][masked]; the four-sample form is the plain kernel's only
+  static constexpr void (*pass[3][2])(const LossParams) = {{ppo_loss_kernel<1>, ppo_loss_masked_kernel},
+                                                           {ppo_loss_kl_kernel<false>, ppo_loss_kl_kernel<true>},
+                                                           {ppo_loss_kl_penalty_kernel<false>, ppo_loss_kl_penalty_kernel<true>}};
+  const auto kernel = vec ? ppo_loss_kernel<4> : pass[c.pen ? 2 : c.kl ? 1 : 0][masked];
+  hipStream_t st = (hipStream_t)c.stream;
   {
     EtmProfScope prof(ETM_K_PPO_LOSS, st);
-    if (vec) hipLaunchKernelGGL(ppo_loss_kernel<4>, dim3(nb), dim3(256), 0, st, p);
-    else if (pen && action_mask) hipLaunchKernelGGL(ppo_loss_kl_penalty_kernel<true>, dim3(nb), dim3(256), 0, st, p);
-    else if (pen) hipLaunchKernelGGL(ppo_loss_kl_penalty_kernel<false>, dim3(nb), dim3(256), 0, st, p);
-    else if (kl && action_mask) hipLaunchKernelGGL(ppo_loss_kl_kernel<true>, dim3(nb), dim3(256), 0, st, p);
-    else if (kl) hipLaunchKernelGGL(ppo_loss_kl_kernel<false>, dim3(nb), dim3(256), 0, st, p);
-    else if (action_mask) hipLaunchKernelGGL(ppo_loss_masked_kernel, dim3(nb), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(ppo_loss_kernel<1>, dim3(nb), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, st, p);
   }
-  int rc = etm_launch_status();
-  if (rc) return rc;
-  {
-    EtmProfScope prof(ETM_K_PPO_FINAL, st);
-    if (pen)
-      hipLaunchKernelGGL(ppo_finalize_kl_penalty_kernel, dim3(1), dim3(64), 0, st, (const float *)partials, nb, vf_coef, beta, pol_scale,
-                         ent_scale, val_scale, out8, dyn_clip_beta, kl_coef);
-    else if (kl)
-      hipLaunchKernelGGL(ppo_finalize_kl_kernel, dim3(1), dim3(64), 0, st, (const float *)partials, nb, vf_coef, beta, pol_scale, ent_scale,
-                         val_scale, out8, dyn_clip_beta);
-    else
-      hipLaunchKernelGGL(ppo_finalize_kernel, dim3(1), dim3(64), 0, st, (const float *)partials, nb, vf_coef, beta, pol_scale, ent_scale,
-                         val_scale, out8, dyn_clip_beta);
-  }
+  if (const int rc = etm_launch_status()) return rc;
+  EtmProfScope prof(ETM_K_PPO_FINAL, st);
+  const auto finalize = c.kl ? ppo_finalize_kl_kernel : ppo_finalize_kernel;
+  if (c.pen)
+    hipLaunchKernelGGL(ppo_finalize_kl_penalty_kernel, dim3(1), dim3(64), 0, st, (const float *)p.partials, nb, p.vf_coef, p.beta, p.pol_scale,
+                       p.ent_scale, p.val_scale, c.out8, p.dyn, p.kl_coef);
+  else
+    hipLaunchKernelGGL(finalize, dim3(1), dim3(64), 0, st, (const float *)p.partials, nb, p.vf_coef, p.beta, p.pol_scale, p.ent_scale,
+                       p.val_scale, c.out8, p.dyn);
   return etm_launch_status();
 }
-
+}  // namespace
+// The entries (include/etm_hip.h documents each): fill the record by name, say what the entry takes, launch.
 extern "C" int etm_ppo_loss(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
                             int64_t logp_stride, const float *adv, const float *old_value, const float *value,
                             const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
                             float val_scale, int include_value, float *out8, float *d_logits, float *d_value, void *partials,
                             int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, void *stream) {
-  return ppo_loss_impl(logits, actions, action_stride, old_logp, logp_stride, adv, old_value, value, adv_stats3, clip, vf_coef, beta, pol_scale,
-                       ent_scale, val_scale, include_value, out8, d_logits, d_value, partials, partials_bytes, dyn_clip_beta, N, A, nullptr, 0,
-                       stream);
+  PL_CALL(c);
+  return pl_launch(c);
 }
-// Invalid-action masks: etm_ppo_loss of one action branch with action_mask [N] int64, the samples' words; the branch's A actions are
-// bits [mask_shift, mask_shift + A) (mask_shift = the branch's first column of the concatenated policy head, 0 for Discrete).  At
-// least one of those bits is set per sample, the taken action among them.  Log-sum-exp, log-prob and entropy run over the valid
-// actions only; d_logits of an invalid action is exactly 0.  ETM_EINVAL: NULL or misaligned mask; ETM_EUNSUPPORTED: bits past 62.
+// Invalid-action masks: the branch's A actions are bits [mask_shift, mask_shift + A) of the samples' words action_mask [N]
 extern "C" int etm_ppo_loss_masked(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
                                    int64_t logp_stride, const float *adv, const float *old_value, const float *value,
                                    const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
                                    float val_scale, int include_value, float *out8, float *d_logits, float *d_value, void *partials,
                                    int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, const int64_t *action_mask,
                                    int mask_shift, void *stream) {
-  if (!action_mask) return ETM_EINVAL;
-  return ppo_loss_impl(logits, actions, action_stride, old_logp, logp_stride, adv, old_value, value, adv_stats3, clip, vf_coef, beta, pol_scale,
-                       ent_scale, val_scale, include_value, out8, d_logits, d_value, partials, partials_bytes, dyn_clip_beta, N, A, action_mask,
-                       mask_shift, stream);
+  PL_CALL(c);
+  c.p.amask = (const long long *)action_mask; c.p.mask_shift = mask_shift; c.need_mask = true;
+  return pl_launch(c);
 }
-// The exact categorical KL (`exact_kl: true`) of one action branch: etm_ppo_loss_masked with action_mask optional (NULL: no masks;
-// mask_shift is then ignored) and old_logps [N, rows of old_logps_stride floats], every column's log-prob under the policy that drew
-// the samples (the *_logps sampling entries), the branch's A columns starting at column logps_off of a row.  out8[4] = pol_scale *
-// sum_n KL_n, KL_n = the sum over the branch's valid columns of etm_categorical_kl_term; out8[6] = the k3 value that the twin puts into
-// out8[4]; the loss, d_logits, d_value, out8[0..3], out8[5] and partial slots 0..4 are the twin's one-sample-per-thread form's, bit
-// for bit (slot 5 carries the raw KL sum).  ETM_EINVAL: NULL or 4-byte-misaligned old_logps, logps_off < 0, a stride below
-// logps_off + A; otherwise the twin's refusals.
+// The exact categorical KL: action_mask optional (NULL: mask_shift is ignored) and old_logps, the branch's A columns from logps_off on
 extern "C" int etm_ppo_loss_kl(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
                                int64_t logp_stride, const float *adv, const float *old_value, const float *value,
                                const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
                                float val_scale, int include_value, float *out8, float *d_logits, float *d_value, void *partials,
                                int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, const int64_t *action_mask,
                                int mask_shift, const float *old_logps, int64_t old_logps_stride, int logps_off, void *stream) {
-  if (!old_logps || ((uintptr_t)old_logps & 3u) || logps_off < 0 || old_logps_stride < (int64_t)logps_off + A) return ETM_EINVAL;
-  return ppo_loss_impl(logits, actions, action_stride, old_logp, logp_stride, adv, old_value, value, adv_stats3, clip, vf_coef, beta, pol_scale,
-                       ent_scale, val_scale, include_value, out8, d_logits, d_value, partials, partials_bytes, dyn_clip_beta, N, A, action_mask,
-                       action_mask ? mask_shift : 0, stream, old_logps, old_logps_stride, logps_off);
+  PL_CALL(c);
+  c.p.amask = (const long long *)action_mask; c.p.mask_shift = action_mask ? mask_shift : 0;
+  c.p.old_logps = old_logps; c.p.old_logps_stride = old_logps_stride; c.p.logps_off = logps_off; c.kl = true;
+  return pl_launch(c);
 }
-// `kl_penalty`: etm_ppo_loss_kl with the loss L + coef * K of the branch, K = out8[4], coef = *kl_coef, ONE device float32 read in place.
-// d_logits is the gradient of L + coef * K; out8[2] includes coef * K, out8[7] = coef; d_value, out8[0, 1, 3, 4, 5, 6] and the partial
-// slots are the twin's.  ETM_EINVAL with nothing launched: a NULL or 4-byte-misaligned kl_coef; otherwise exactly the twin's refusals.
+// `kl_penalty`: etm_ppo_loss_kl with the loss L + coef * K of the branch, K = out8[4], coef = *kl_coef, ONE device float32 read in place
 extern "C" int etm_ppo_loss_kl_penalty(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
                                        int64_t logp_stride, const float *adv, const float *old_value, const float *value,
                                        const float *adv_stats3, double clip, float vf_coef, float beta, float pol_scale, float ent_scale,
@@ -457,9 +453,9 @@ extern "C" int etm_ppo_loss_kl_penalty(const float *logits, const int64_t *actio
                                        int64_t partials_bytes, const double *dyn_clip_beta, int N, int A, const int64_t *action_mask,
                                        int mask_shift, const float *old_logps, int64_t old_logps_stride, int logps_off, const float *kl_coef,
                                        void *stream) {
-  if (!kl_coef || ((uintptr_t)kl_coef & 3u)) return ETM_EINVAL;
-  if (!old_logps || ((uintptr_t)old_logps & 3u) || logps_off < 0 || old_logps_stride < (int64_t)logps_off + A) return ETM_EINVAL;
-  return ppo_loss_impl(logits, actions, action_stride, old_logp, logp_stride, adv, old_value, value, adv_stats3, clip, vf_coef, beta, pol_scale,
-                       ent_scale, val_scale, include_value, out8, d_logits, d_value, partials, partials_bytes, dyn_clip_beta, N, A, action_mask,
-                       action_mask ? mask_shift : 0, stream, old_logps, old_logps_stride, logps_off, kl_coef);
+  PL_CALL(c);
+  c.p.amask = (const long long *)action_mask; c.p.mask_shift = action_mask ? mask_shift : 0;
+  c.p.old_logps = old_logps; c.p.old_logps_stride = old_logps_stride; c.p.logps_off = logps_off; c.kl = true; c.p.kl_coef = kl_coef; c.pen = true;
+  return pl_launch(c);
 }
+#undef PL_CALL

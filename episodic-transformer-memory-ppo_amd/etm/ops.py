@@ -4,6 +4,8 @@ PyTorch is plumbing here: it owns the device buffers and the stream; the math of
 hand-written kernels.  Every entry point requires HIP device tensors and raises otherwise -- no CPU/eager fallback.
 """
 import ctypes
+import dataclasses
+import itertools
 
 import torch
 
@@ -2213,15 +2215,86 @@ def _check_kl_coef(kl_coef, what):
     _need_dev(kl_coef)
     if kl_coef.dtype != torch.float32 or kl_coef.numel() != 1:
         raise ValueError(f"{what}: kl_coef must be a device tensor of one float32, got {tuple(kl_coef.shape)} {kl_coef.dtype}")
-    return kl_coef.data_ptr()
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class _LossCall:
+    """What a loss call knows beyond the tensors that autograd sees; ``_loss_call`` makes it and validates it once.  The variant of
+    the C entry follows from what is set: ``action_mask`` alone -> *_masked; the old policy (``old_logps``, or ``old_mean`` /
+    ``old_log_std`` of a Box policy) -> *_kl, the mask then optional; ``kl_coef`` on top -> *_kl_penalty."""
+    stats3: torch.Tensor
+    clip: float
+    vf_coef: float
+    beta: float
+    dyn: torch.Tensor = None            # float64 device (clip, beta), read by the kernels instead of the two scalars
+    unit_grad: bool = False
+    sizes: tuple = None                 # heads + loss: the branch sizes of a MultiDiscrete policy
+    action_mask: torch.Tensor = None
+    old_logps: torch.Tensor = None
+    old_mean: torch.Tensor = None
+    old_log_std: torch.Tensor = None
+    kl_coef: torch.Tensor = None
+
+    @property
+    def kl(self):
+        return self.old_logps is not None or self.old_mean is not None
+
+    @property
+    def suffix(self):
+        """Behind etm_heads_loss[_gaussian | _branched] / etm_ppo_loss -- the scheme lib.py derives the signatures by."""
+        return ("_kl" if self.kl else "_masked" if self.action_mask is not None else "") + ("_penalty" if self.kl_coef is not None else "")
+
+    def tail(self, N, shift=None):
+        """The arguments behind the unmasked entry's, in the order of ``suffix``.  ``shift`` (PPO loss entries): the branch's first
+        column among the concatenated branches -- its mask bits and its log-prob columns start there."""
+        t = []
+        if self.action_mask is not None or self.old_logps is not None:
+            t += [_ptr(self.action_mask)] + ([] if shift is None else [shift if self.action_mask is not None else 0])
+        for rows in (self.old_logps, self.old_mean):      # rows of any stride
+            if rows is not None:
+                t += [rows.data_ptr(), rows.stride(0) if N > 1 else rows.shape[1]]
+        if self.old_logps is not None and shift is not None:
+            t.append(shift)
+        if self.old_log_std is not None:
+            t.append(self.old_log_std.data_ptr())
+        return t + ([] if self.kl_coef is None else [self.kl_coef.data_ptr()])
+
+
+def _loss_call(what, N, cols, adv, stats3, dyn, clip, vf_coef, beta, **policy):
+    """The record of one call of the loss op ``what`` over ``N`` samples, its operands checked.  ``cols``: the policy head's columns --
+    for ``ppo_loss`` the column at which each branch ends, every one checked as that branch's launch needs it."""
+    c = _LossCall(adv_stats(adv) if stats3 is None else stats3, float(clip), float(vf_coef), float(beta), dyn, **policy)
+    gauss = what == "heads_ppo_loss_gaussian"
+    if (c.old_mean is None) != (c.old_log_std is None):
+        raise ValueError(f"{what}: old_mean and old_log_std come together (the exact KL needs both)")
+    if c.kl_coef is not None and not c.kl:
+        raise ValueError(f"{what}: kl_coef without " + ("old_mean / old_log_std (the KL penalty is a term in the exact KL); pass both" if gauss
+                                                        else "old_logps (the KL penalty is a term in the exact KL); pass the rollout's log-prob rows"))
+    if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
+        raise TypeError(f"{what}: dyn must be a float64 device tensor (clip, beta)")
+    if c.kl_coef is not None:
+        _check_kl_coef(c.kl_coef, what.replace("_gaussian", ""))
+    if c.old_mean is not None:
+        # Box with the exact KL: old_mean [N, A] the rollout's means (rows of any stride), old_log_std [A] its log sigma
+        _need_dev(c.old_mean, c.old_log_std)
+        old_mean, old_log_std, A = c.old_mean, c.old_log_std, cols
+        if (old_mean.dtype != torch.float32 or old_mean.dim() != 2 or tuple(old_mean.shape) != (N, A) or old_mean.stride(1) != 1
+                or old_log_std.dtype != torch.float32 or old_log_std.numel() != A or not old_log_std.is_contiguous()):
+            raise ValueError(f"{what}: old_mean must be float32 [{N}, {A}] with contiguous rows and old_log_std "
+                             f"float32 [{A}], got {tuple(old_mean.shape)} {old_mean.dtype} / {tuple(old_log_std.shape)} {old_log_std.dtype}")
+    for end in (cols if what == "ppo_loss" else (cols,)):
+        if c.old_logps is not None:
+            _check_old_logps(c.old_logps, N, end, what)
+        if c.action_mask is not None:
+            _mask_words(c.action_mask, N, end, what)
+    return c
 
 
 class _PpoLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, value, actions, old_logp, adv, old_value, stats3, branch, n_branches, clip, vf_coef, beta,
-                include_value, dyn=None, action_mask=None, mask_shift=0, old_logps=None, logps_off=0, kl_coef=None):
+    def forward(ctx, logits, value, actions, old_logp, adv, old_value, call, branch, n_branches, shift, include_value):
         lib = _lib.load()
-        _need_dev(logits, value, actions, old_logp, adv, old_value, stats3)
+        _need_dev(logits, value, actions, old_logp, adv, old_value, call.stats3)
         logits = _f32c(logits, "logits")
         value = _f32c(value, "value")
         adv, old_value = _f32c(adv, "adv"), _f32c(old_value, "old_value")
@@ -2236,25 +2309,11 @@ class _PpoLossFn(torch.autograd.Function):
         d_value = torch.empty_like(value)
         nbytes = lib.etm_ppo_loss_workspace_bytes(N)
         ws = workspace(nbytes, dev, "ppo")
-        args = (_ptr(logits), actions.data_ptr() + 8 * branch, B, old_logp.data_ptr() + 4 * branch, B, _ptr(adv),
-                _ptr(old_value), _ptr(value), _ptr(stats3), float(clip), float(vf_coef), float(beta),
-                1.0 / (N * n_branches), 1.0 / N, 1.0 / N, 1 if include_value else 0, _ptr(out8), _ptr(d_logits),
-                _ptr(d_value), _ptr(ws), nbytes, _ptr(dyn), N, A)
-        if old_logps is not None:
-            # the exact KL: this branch's columns [logps_off, logps_off + A) of the rollout's log-prob rows; stats[4] is then the
-            # branch's exact KL (masks or not)
-            _check_old_logps(old_logps, N, int(logps_off) + A, "ppo_loss")
-            am = 0 if action_mask is None else _mask_words(action_mask, N, int(mask_shift) + A, "ppo_loss").data_ptr()
-            lp_args = (am, int(mask_shift), old_logps.data_ptr(), old_logps.stride(0) if N > 1 else old_logps.shape[1], int(logps_off))
-            if kl_coef is not None:      # `kl_penalty`: the loss and d_logits carry coef * KL, the coefficient read in place
-                rc = lib.etm_ppo_loss_kl_penalty(*args, *lp_args, _check_kl_coef(kl_coef, "ppo_loss"), _stream())
-            else:
-                rc = lib.etm_ppo_loss_kl(*args, *lp_args, _stream())
-        elif action_mask is None:
-            rc = lib.etm_ppo_loss(*args, _stream())
-        else:        # this branch's actions are bits [mask_shift, mask_shift + A) of the samples' words
-            am = _mask_words(action_mask, N, int(mask_shift) + A, "ppo_loss")
-            rc = lib.etm_ppo_loss_masked(*args, am.data_ptr(), int(mask_shift), _stream())
+        # this branch's actions are bits [shift, shift + A) of the samples' words and columns [shift, shift + A) of the log-prob rows
+        rc = getattr(lib, "etm_ppo_loss" + call.suffix)(
+            _ptr(logits), actions.data_ptr() + 8 * branch, B, old_logp.data_ptr() + 4 * branch, B, _ptr(adv), _ptr(old_value), _ptr(value),
+            _ptr(call.stats3), call.clip, call.vf_coef, call.beta, 1.0 / (N * n_branches), 1.0 / N, 1.0 / N, 1 if include_value else 0,
+            _ptr(out8), _ptr(d_logits), _ptr(d_value), _ptr(ws), nbytes, _ptr(call.dyn), N, A, *call.tail(N, shift), _stream())
         _lib.check(rc, "etm_ppo_loss")
         ctx.save_for_backward(d_logits, d_value)
         ctx.include_value = include_value
@@ -2265,109 +2324,56 @@ class _PpoLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_stats):
         if g_loss is None:
-            return (None,) * 19
+            return (None,) * len(ctx.needs_input_grad)
         d_logits, d_value = ctx.saved_tensors
-        gv = d_value * g_loss if ctx.include_value else None
-        return (d_logits * g_loss, gv) + (None,) * 17
+        grads = (d_logits * g_loss, d_value * g_loss if ctx.include_value else None)
+        return grads + (None,) * (len(ctx.needs_input_grad) - len(grads))
 
 
 class _HeadsLossFn(torch.autograd.Function):
     """Hidden heads (bias + ReLU), policy branch, value head, PPO loss and the backward pass down to the hidden heads' pre-activations
     as one kernel pass (csrc/heads_loss.hip); the two hidden GEMMs h W^T (forward) and gm W (backward) stay library GEMMs, the hidden
     heads' weight gradients go to the grouped launch.  Gradients are those of ``loss`` itself (unit upstream gradient) times
-    ``g_loss``."""
+    ``g_loss``.  The inputs that receive gradients come first (``log_std``: a Box policy's, else None), then the other tensors, then
+    the ``_LossCall``."""
 
     @staticmethod
-    def forward(ctx, h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn, unit_grad,
-                sizes=None, log_std=None, action_mask=None, old_mean=None, old_log_std=None, old_logps=None, kl_coef=None):
+    def forward(ctx, h, wlp, blp, wlv, blv, wb, bb, wv, bv, log_std, actions, old_logp, adv, old_value, call):
         lib = _lib.load()
-        _need_dev(h, wlp, blp, wlv, blv, wb, bb, wv, bv, actions, old_logp, adv, old_value, stats3)
+        _need_dev(h, wlp, blp, wlv, blv, wb, bb, wv, bv, log_std, actions, old_logp, adv, old_value, call.stats3)
         h = _f32c(h, "h")
         N, hid, A = h.shape[0], wlp.shape[0], wb.shape[0]
         dev = h.device
         pre_p, pre_v = h.mm(wlp.t()), h.mm(wlv.t())
         gm_p, gm_v = torch.empty_like(pre_p), torch.empty_like(pre_v)
         gauss = log_std is not None
-        kl = old_mean is not None           # Box with the exact KL statistic: the row carries the KL sum behind d log_std
-        ckl = old_logps is not None         # categorical with the exact KL statistic: the row carries the KL sum at its very end
-        if ckl and gauss:
-            raise ValueError("heads_ppo_loss: old_logps belongs to a categorical policy")
-        pen = () if kl_coef is None else (_check_kl_coef(kl_coef, "heads_ppo_loss"),)      # (`kl_penalty`: the *_kl_penalty entries)
-        if kl:
-            row, nbytes = lib.etm_heads_loss_gaussian_kl_row_floats(hid, A), lib.etm_heads_loss_gaussian_kl_workspace_bytes(N, hid, A)
-        elif ckl:
-            row, nbytes = lib.etm_heads_loss_kl_row_floats(hid, A), lib.etm_heads_loss_kl_workspace_bytes(N, hid, A)
-        elif gauss:
-            row, nbytes = lib.etm_heads_loss_gaussian_row_floats(hid, A), lib.etm_heads_loss_gaussian_workspace_bytes(N, hid, A)
-        else:
-            row, nbytes = lib.etm_heads_loss_row_floats(hid, A), lib.etm_heads_loss_workspace_bytes(N, hid, A)
+        # the row of sums: a Box policy's carries d log_std behind the statistics, the exact KL's the KL sum at its very end
+        kind = ("gaussian_" if gauss else "") + ("kl_" if call.kl else "")
+        row = getattr(lib, f"etm_heads_loss_{kind}row_floats")(hid, A)
+        nbytes = getattr(lib, f"etm_heads_loss_{kind}workspace_bytes")(N, hid, A)
         sums = torch.empty(row, dtype=torch.float32, device=dev)
         out8 = torch.empty(8, dtype=torch.float32, device=dev)
         ws = workspace(nbytes, dev, "heads_loss")
         actions, old_logp = actions.contiguous(), old_logp.contiguous()
-        B = actions.shape[1] if actions.dim() == 2 else 1
-        common = (_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv), _ptr(actions), B,
-                  _ptr(old_logp), B, _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
-                  float(vf_coef), float(beta))
-        if kl:
-            # Box with the exact KL: old_mean [N, A] the rollout's means (rows of any stride), old_log_std [A] its log sigma
-            _need_dev(log_std, old_mean, old_log_std)
-            if (old_mean.dtype != torch.float32 or old_mean.dim() != 2 or tuple(old_mean.shape) != (N, A) or old_mean.stride(1) != 1
-                    or old_log_std.dtype != torch.float32 or old_log_std.numel() != A or not old_log_std.is_contiguous()):
-                raise ValueError(f"heads_ppo_loss_gaussian: old_mean must be float32 [{N}, {A}] with contiguous rows and old_log_std "
-                                 f"float32 [{A}], got {tuple(old_mean.shape)} {old_mean.dtype} / {tuple(old_log_std.shape)} {old_log_std.dtype}")
-            entry = lib.etm_heads_loss_gaussian_kl_penalty if pen else lib.etm_heads_loss_gaussian_kl
-            rc = entry(_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv),
-                       _ptr(_f32c(actions, "actions")), A, _ptr(_f32c(log_std, "log_std")), _ptr(old_logp), 1,
-                       _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
-                       float(vf_coef), float(beta), 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
-                       _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, A, old_mean.data_ptr(),
-                       old_mean.stride(0) if N > 1 else A, old_log_std.data_ptr(), *pen, _stream())
-        elif gauss:
+        if gauss:
             # Box: wb / bb the mean head, actions [N, A] the stored raw float actions, old_logp [N] (or [N, 1]) the joint log-probs
-            _need_dev(log_std)
-            rc = lib.etm_heads_loss_gaussian(_ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv),
-                                             _ptr(_f32c(actions, "actions")), A, _ptr(_f32c(log_std, "log_std")), _ptr(old_logp), 1,
-                                             _ptr(_f32c(adv, "adv")), _ptr(_f32c(old_value, "old_value")), _ptr(stats3), float(clip),
-                                             float(vf_coef), float(beta), 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
-                                             _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, A, _stream())
-        elif ckl:
-            # the exact categorical KL: the minibatch's rows of the rollout's log-prob table (rows of any stride), masks or not
-            _check_old_logps(old_logps, N, A, "heads_ppo_loss")
-            am = 0 if action_mask is None else _mask_words(action_mask, N, A, "heads_ppo_loss").data_ptr()
-            lp_args = (am, old_logps.data_ptr(), old_logps.stride(0) if N > 1 else old_logps.shape[1], *pen, _stream())
-            if sizes is None:
-                rc = (lib.etm_heads_loss_kl_penalty if pen else lib.etm_heads_loss_kl)(*common, 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8),
-                                           0, 0, _ptr(ws), nbytes, N, hid, A, *lp_args)
-            else:
-                tab, nbr = _branch_table(sizes)
-                entry = lib.etm_heads_loss_branched_kl_penalty if pen else lib.etm_heads_loss_branched_kl
-                rc = entry(*common, 1.0 / (N * nbr), 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
-                           _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, tab, nbr, *lp_args)
-        elif action_mask is not None:
-            # invalid-action masks: the samples' words, Discrete or MultiDiscrete (wb / bb concatenated as below)
-            am = _mask_words(action_mask, N, A, "heads_ppo_loss")
-            if sizes is None:
-                rc = lib.etm_heads_loss_masked(*common, 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8),
-                                               0, 0, _ptr(ws), nbytes, N, hid, A, am.data_ptr(), _stream())
-            else:
-                tab, nbr = _branch_table(sizes)
-                rc = lib.etm_heads_loss_branched_masked(*common, 1.0 / (N * nbr), 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v),
-                                                        _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, tab, nbr, am.data_ptr(),
-                                                        _stream())
-        elif sizes is None:
-            rc = lib.etm_heads_loss(*common, 1.0 / N, 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8),
-                                    0, 0, _ptr(ws), nbytes, N, hid, A, _stream())
+            taken = (_ptr(_f32c(actions, "actions")), A, _ptr(_f32c(log_std, "log_std")), _ptr(old_logp), 1)
         else:
-            # MultiDiscrete: wb / bb are the branches' heads concatenated; policy term, KL and clip fraction are means over N B
-            tab, nbr = _branch_table(sizes)
-            rc = lib.etm_heads_loss_branched(*common, 1.0 / (N * nbr), 1.0 / N, 1.0 / N, _ptr(dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums),
-                                             _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, tab, nbr, _stream())
+            B = actions.shape[1] if actions.dim() == 2 else 1
+            taken = (_ptr(actions), B, _ptr(old_logp), B)
+        # MultiDiscrete: wb / bb are the branches' heads concatenated; policy term, KL and clip fraction are means over N B
+        nbr = 1 if call.sizes is None else len(call.sizes)
+        shape = (A,) if call.sizes is None else _branch_table(call.sizes)
+        entry = "etm_heads_loss" + ("_gaussian" if gauss else "_branched" if call.sizes is not None else "") + call.suffix
+        rc = getattr(lib, entry)(
+            _ptr(pre_p), _ptr(pre_v), _ptr(blp), _ptr(blv), _ptr(wb), _ptr(bb), _ptr(wv), _ptr(bv), *taken, _ptr(_f32c(adv, "adv")),
+            _ptr(_f32c(old_value, "old_value")), _ptr(call.stats3), call.clip, call.vf_coef, call.beta, 1.0 / (N * nbr), 1.0 / N, 1.0 / N,
+            _ptr(call.dyn), _ptr(gm_p), _ptr(gm_v), _ptr(sums), _ptr(out8), 0, 0, _ptr(ws), nbytes, N, hid, *shape, *call.tail(N), _stream())
         _lib.check(rc, "etm_heads_loss")
         ctx.save_for_backward(h, wlp, wlv, gm_p, gm_v, sums)
         ctx.dims = (hid, A)
         ctx.gauss = gauss
-        ctx.unit = bool(unit_grad)
+        ctx.unit = call.unit_grad
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(out8)
         return out8[2].clone(), out8
@@ -2375,7 +2381,7 @@ class _HeadsLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_stats):
         if g_loss is None:
-            return (None,) * 26
+            return (None,) * len(ctx.needs_input_grad)
         h, wlp, wlv, gm_p, gm_v, sums = ctx.saved_tensors
         hid, A = ctx.dims
         unit = ctx.unit                 # the caller promises loss.backward() on the returned loss itself: g_loss == 1, nothing to scale
@@ -2392,9 +2398,9 @@ class _HeadsLossFn(torch.autograd.Function):
             dwlv = gm_v.t().mm(h) if unit else gm_v.t().mm(h) * g_loss
         s = sums if unit else sums * g_loss
         o = (3 + A) * hid
-        return (dh, dwlp, s[:hid], dwlv, s[hid:2 * hid], s[3 * hid:o].view(A, hid), s[o:o + A], s[2 * hid:3 * hid].view(1, hid),
-                s[o + A:o + A + 1], None, None, None, None, None, None, None, None, None, None, None,
-                s[o + A + 6:o + 2 * A + 6] if ctx.gauss else None, None, None, None, None, None)
+        grads = (dh, dwlp, s[:hid], dwlv, s[hid:2 * hid], s[3 * hid:o].view(A, hid), s[o:o + A], s[2 * hid:3 * hid].view(1, hid),
+                 s[o + A:o + A + 1], s[o + A + 6:o + 2 * A + 6] if ctx.gauss else None)
+        return grads + (None,) * (len(ctx.needs_input_grad) - len(grads))
 
 
 def _branch_list(branch):
@@ -2431,20 +2437,13 @@ def heads_ppo_loss_gaussian(h, lin_policy, lin_value, mean_head, log_std, value_
     ``kl_coef`` (optional, `kl_penalty`; needs ``old_mean``): a device tensor of one float32 that the kernels read in place; the loss is
     then loss + coef * stats[4] and every gradient (``log_std``'s too) is that sum's (etm_heads_loss_gaussian_kl_penalty); None =
     exactly the call without."""
-    if (old_mean is None) != (old_log_std is None):
-        raise ValueError("heads_ppo_loss_gaussian: old_mean and old_log_std come together (the exact KL needs both)")
-    if kl_coef is not None and old_mean is None:
-        raise ValueError("heads_ppo_loss_gaussian: kl_coef without old_mean / old_log_std (the KL penalty is a term in the exact KL); pass both")
-    if stats3 is None:
-        stats3 = adv_stats(adv)
-    if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
-        raise TypeError("heads_ppo_loss_gaussian: dyn must be a float64 device tensor (clip, beta)")
     A = mean_head.weight.shape[0]
+    call = _loss_call("heads_ppo_loss_gaussian", h.shape[0], A, adv, stats3, dyn, clip, vf_coef, beta, unit_grad=bool(unit_grad),
+                      old_mean=old_mean, old_log_std=old_log_std, kl_coef=kl_coef)
     if actions.dim() != 2 or actions.shape[1] != A or not actions.is_floating_point():
         raise ValueError(f"heads_ppo_loss_gaussian: actions must be float [N, {A}]")
     loss, st = _HeadsLossFn.apply(h, lin_policy.weight, lin_policy.bias, lin_value.weight, lin_value.bias, mean_head.weight, mean_head.bias,
-                                  value_head.weight, value_head.bias, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn,
-                                  unit_grad, None, log_std, None, old_mean, old_log_std, None, kl_coef)
+                                  value_head.weight, value_head.bias, log_std, actions, old_logp, adv, old_value, call)
     return loss, st[:6]
 
 
@@ -2464,12 +2463,6 @@ def heads_ppo_loss(h, lin_policy, lin_value, branch, value_head, actions, old_lo
     ``kl_coef`` (optional, `kl_penalty`; needs ``old_logps``): a device tensor of one float32 that the kernels read in place; the loss
     is then loss + coef * stats[4] and every gradient is that sum's (etm_heads_loss_kl_penalty / _branched_kl_penalty); None = exactly
     the call without."""
-    if kl_coef is not None and old_logps is None:
-        raise ValueError("heads_ppo_loss: kl_coef without old_logps (the KL penalty is a term in the exact KL); pass the rollout's log-prob rows")
-    if stats3 is None:
-        stats3 = adv_stats(adv)
-    if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
-        raise TypeError("heads_ppo_loss: dyn must be a float64 device tensor (clip, beta)")
     br = _branch_list(branch)
     if len(br) == 1:
         wb, bb, sizes = br[0].weight, br[0].bias, None
@@ -2477,9 +2470,10 @@ def heads_ppo_loss(h, lin_policy, lin_value, branch, value_head, actions, old_lo
         # the kernel reads the branches' heads as one [sum A_b, hid] matrix; autograd hands each branch its rows of the gradient
         wb, bb = torch.cat([b.weight for b in br], dim=0), torch.cat([b.bias for b in br], dim=0)
         sizes = tuple(int(b.weight.shape[0]) for b in br)
+    call = _loss_call("heads_ppo_loss", h.shape[0], wb.shape[0], adv, stats3, dyn, clip, vf_coef, beta, unit_grad=bool(unit_grad), sizes=sizes,
+                      action_mask=action_mask, old_logps=old_logps, kl_coef=kl_coef)
     loss, st = _HeadsLossFn.apply(h, lin_policy.weight, lin_policy.bias, lin_value.weight, lin_value.bias, wb, bb,
-                                  value_head.weight, value_head.bias, actions, old_logp, adv, old_value, stats3, clip, vf_coef, beta, dyn,
-                                  unit_grad, sizes, None, action_mask, None, None, old_logps, kl_coef)
+                                  value_head.weight, value_head.bias, None, actions, old_logp, adv, old_value, call)
     return loss, st[:6]
 
 
@@ -2494,31 +2488,18 @@ def ppo_loss(logits_list, value, actions, old_logp, adv, old_value, clip, vf_coe
     sample estimate -- every other output unchanged in its bits (etm_ppo_loss_kl, masks or not); None = exactly the calls without.
     ``kl_coef`` (optional, `kl_penalty`; needs ``old_logps``): a device tensor of one float32 read in place; every branch's loss is then
     its loss + coef * its share of stats[4], with that sum's gradient (etm_ppo_loss_kl_penalty); None = exactly the calls without."""
-    if kl_coef is not None and old_logps is None:
-        raise ValueError("ppo_loss: kl_coef without old_logps (the KL penalty is a term in the exact KL); pass the rollout's log-prob rows")
-    if stats3 is None:
-        stats3 = adv_stats(adv)
-    if dyn is not None and (dyn.dtype != torch.float64 or dyn.numel() != 2 or not dyn.is_cuda):
-        raise TypeError("ppo_loss: dyn must be a float64 device tensor (clip, beta)")
     nb = len(logits_list)
-    if action_mask is not None or old_logps is not None:
-        shifts, total = [], 0
-        for lg in logits_list:
-            shifts.append(total)
-            total += int(lg.shape[1])
-        if old_logps is not None:      # (the mask shift and the column offset of a branch are the same number)
-            mk = lambda b: (action_mask, shifts[b] if action_mask is not None else 0, old_logps, shifts[b], kl_coef)
-        else:
-            mk = lambda b: (action_mask, shifts[b])
-    else:
-        mk = lambda b: ()
-    loss, st = _PpoLossFn.apply(logits_list[0], value, actions, old_logp, adv, old_value, stats3, 0, nb, clip, vf_coef, beta, True, dyn, *mk(0))
+    ends = list(itertools.accumulate(int(lg.shape[1]) for lg in logits_list))
+    shifts = [0] + ends[:-1]      # (the mask shift and the column offset of a branch are the same number)
+    call = _loss_call("ppo_loss", logits_list[0].shape[0], ends, adv, stats3, dyn, clip, vf_coef, beta, action_mask=action_mask,
+                      old_logps=old_logps, kl_coef=kl_coef)
+    loss, st = _PpoLossFn.apply(logits_list[0], value, actions, old_logp, adv, old_value, call, 0, nb, shifts[0], True)
     if nb == 1:
         return loss, st[:6]
     pol, ent, kl, cf = st[0], st[3], st[4], st[5]
     total = loss
     for b in range(1, nb):
-        l_b, s_b = _PpoLossFn.apply(logits_list[b], value, actions, old_logp, adv, old_value, stats3, b, nb, clip, vf_coef, beta, False, dyn, *mk(b))
+        l_b, s_b = _PpoLossFn.apply(logits_list[b], value, actions, old_logp, adv, old_value, call, b, nb, shifts[b], False)
         total = total + l_b
         pol, ent, kl, cf = pol + s_b[0], ent + s_b[3], kl + s_b[4], cf + s_b[5]
     return total, torch.stack([pol, st[1], total.detach(), ent, kl, cf])

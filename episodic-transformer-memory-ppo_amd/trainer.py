@@ -1534,38 +1534,35 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         """Model forward + PPO loss of one minibatch (trainer.py:268-304): -> (loss, stats[6]).  Policies whose hidden size and actions
         fit (every branch of a MultiDiscrete policy together) take the fused hidden-heads + loss kernel (``fused_heads_loss``, default
         on); others the separate heads and the per-branch loss."""
-        dyn = getattr(self, "_dyn", None) if dyn == "device" else dyn
         m = self.model
+        # what every route takes behind its own operands, the old policy of the exact KL rules among it: a Box policy's means and log-std
+        # snapshot (kl_estimator: analytic), a categorical policy's log-prob rows (exact_kl), masks or not; stats[4] is then the exact KL.
+        # kl_penalty: the coefficient's device word on top, read in place
+        if self.box is not None:
+            kw = dict(old_mean=mb["means"], old_log_std=self.buffer.old_log_std) if self._kl_analytic else {}
+        else:
+            kw = dict(action_mask=mb.get("action_masks"), **(dict(old_logps=mb["old_logps"]) if self._kl_exact_cat else {}))
+        if self._kl_coef is not None:
+            kw["kl_coef"] = self._kl_coef
+        rest = (mb["actions"], mb["log_probs"], mb["advantages"], mb["values"], clip_range, self.config["value_loss_coefficient"], beta, stats3)
+        kw["dyn"] = getattr(self, "_dyn", None) if dyn == "device" else dyn
         if self.box is not None:
             # Box: the fused Gaussian heads + loss kernel is the only path (check_box_policy made sure it takes the shape)
             h, _ = m.forward_state(obs, spec)
             if not ops.heads_loss_supported_gaussian(h, m.lin_policy, m.policy_branches[0]):
                 raise RuntimeError("Box policy: the minibatch is outside the fused Gaussian heads + loss kernel")
-            # kl_estimator: analytic: the minibatch's old means and the update's log-std snapshot; stats[4] is then the exact KL
-            old = dict(old_mean=mb["means"], old_log_std=self.buffer.old_log_std) if self._kl_analytic else {}
-            if self._kl_coef is not None:      # (kl_penalty: the coefficient's device word, read in place)
-                old["kl_coef"] = self._kl_coef
-            return ops.heads_ppo_loss_gaussian(h, m.lin_policy, m.lin_value, m.policy_branches[0], m.policy_log_std, m.value, mb["actions"],
-                                               mb["log_probs"], mb["advantages"], mb["values"], clip_range, self.config["value_loss_coefficient"],
-                                               beta, stats3, dyn=dyn, unit_grad=True, **old)
-        # exact_kl (categorical): the minibatch's rows of the rollout's log-probs; stats[4] is then the exact KL on all three routes
-        old = dict(old_logps=mb["old_logps"]) if self._kl_exact_cat else {}
-        if self._kl_coef is not None:          # (kl_penalty: the coefficient's device word, read in place on all three routes)
-            old["kl_coef"] = self._kl_coef
+            return ops.heads_ppo_loss_gaussian(h, m.lin_policy, m.lin_value, m.policy_branches[0], m.policy_log_std, m.value, *rest, unit_grad=True, **kw)
         if self.config.get("fused_heads_loss", True):
             h, _ = m.forward_state(obs, spec)
             branch = m.policy_branches[0] if len(m.policy_branches) == 1 else list(m.policy_branches)
-            if ops.heads_loss_supported(h, m.lin_policy, branch):
-                return ops.heads_ppo_loss(h, m.lin_policy, m.lin_value, branch, m.value, mb["actions"], mb["log_probs"],
-                                          mb["advantages"], mb["values"], clip_range, self.config["value_loss_coefficient"], beta, stats3, dyn=dyn,
-                                          unit_grad=True, action_mask=mb.get("action_masks"), **old)       # (both callers run loss.backward() on this loss)
+            if ops.heads_loss_supported(h, m.lin_policy, branch):      # (both callers run loss.backward() on this loss)
+                return ops.heads_ppo_loss(h, m.lin_policy, m.lin_value, branch, m.value, *rest, unit_grad=True, **kw)
             h_policy = ops.linear_relu(m.lin_policy, h)
             h_value = ops.linear_relu(m.lin_value, h)
             logits, value = [br(h_policy) for br in m.policy_branches], m.value(h_value).reshape(-1)
         else:
             logits, value, _ = m.forward_logits(obs, spec, want_items=False)
-        return ops.ppo_loss(logits, value, mb["actions"], mb["log_probs"], mb["advantages"], mb["values"], clip_range,
-                            self.config["value_loss_coefficient"], beta, stats3, dyn=dyn, action_mask=mb.get("action_masks"), **old)
+        return ops.ppo_loss(logits, value, *rest, **kw)
 
     def _dw_destinations(self):
         """{parameter data_ptr: its gradient view in the flat arena}: the [out, in] views of the 2-D parameters for the grouped weight-

@@ -350,7 +350,23 @@ int etm_gate_train_bwd2(const float *drx, const float *x, const float *r, const 
  *   d Wlp = gm_p^T h ...); sums [etm_heads_loss_row_floats(hid, A)] = [d b_lp (hid) | d b_lv (hid) | d wv (hid) | d Wb (A x hid) |
  *   d bb (A) | d bv | 5 raw statistic sums]; out8 as etm_ppo_loss; logits [N, A] / value [N] optional (NULL: not written).
  *   workspace: etm_heads_loss_workspace_bytes(N, hid, A) bytes (one partial row per 8 samples, summed in row order: deterministic).
- * Shapes: etm_heads_loss_supported(N, hid, A) == 1 (hid % 64 == 0, hid <= 512, A <= 8). */
+ * Shapes: etm_heads_loss_supported(N, hid, A) == 1 (hid % 64 == 0, hid <= 512, A <= 8).
+ *
+ * Refusals of the loss entries.  Every etm_heads_loss* entry refuses a defective call with nothing launched and nothing written; of
+ * two defects the one earlier in this list decides the code.  Each step applies to the entries that take the operand it names:
+ *   1. kl_coef NULL or not 4-byte aligned                                                              -> ETM_EINVAL
+ *   2. old_logps NULL or not 4-byte aligned; etm_heads_loss_kl[_penalty]: old_logps_stride < A; xact, old_mean or old_log_std
+ *      NULL, old_mean / old_log_std not 4-byte aligned; the action_mask of the *_masked entries NULL        -> ETM_EINVAL
+ *   3. *_branched*: etm_heads_loss_supported_branched(...) == 0 (a NULL or non-positive size table too)     -> ETM_EUNSUPPORTED
+ *   4. *_branched*: action_stride or logp_stride < n_branches, old_logps_stride < sum sizes; *_gaussian*: action_stride < A,
+ *      logp_stride < 1, old_mean_stride < A                                                                -> ETM_EINVAL
+ *   5. a NULL among the other pointers (logits, value and dyn_clip_beta may be NULL)                        -> ETM_EINVAL
+ *   6. action_mask not 8-byte aligned -> ETM_EINVAL (more than 63 columns under a mask: ETM_EUNSUPPORTED)
+ *   7. etm_heads_loss_supported / _supported_gaussian(N, hid, A) == 0                                       -> ETM_EUNSUPPORTED
+ *   8. workspace_bytes below the entry's *_workspace_bytes(N, hid, A)                                       -> ETM_EWORKSPACE
+ * The etm_ppo_loss* entries follow the same list without the steps on shapes of the heads: 1; 2 with logps_off < 0 and
+ * old_logps_stride < logps_off + A; 5 with value, old_value and d_value required when include_value != 0, then N <= 0 or A <= 0
+ * -> ETM_EINVAL; a mask with mask_shift < 0 or mask_shift + A > 63 -> ETM_EUNSUPPORTED; 6; 8. */
 int etm_heads_loss_supported(int N, int hid, int A);
 int etm_heads_loss_row_floats(int hid, int A);
 int64_t etm_heads_loss_workspace_bytes(int N, int hid, int A);
@@ -379,7 +395,7 @@ int etm_heads_loss_branched(const float *pre_p, const float *pre_v, const float 
  * with valid set V: lse_V over V only, log p_j = l_j - lse_V on V and p_j = 0 elsewhere, entropy -sum_{j in V} p_j log p_j (invalid
  * columns are skipped, not multiplied), d loss / d l_j = 0 exactly for j outside V -- so that sample adds nothing to those rows of
  * d Wb / d bb; a branch with one valid action has log p = 0, entropy 0 and a zero gradient.  Ratio, clipping, KL, clip fraction, value
- * loss and scales as without masks; the optional logits output stays raw.  ETM_EINVAL for a NULL or misaligned action_mask. */
+ * loss and scales as without masks; the optional logits output stays raw.  Refusals: the list above. */
 int etm_heads_loss_masked(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb, const float *bb,
                           const float *wv, const float *bv, const int64_t *actions, int64_t action_stride, const float *old_logp,
                           int64_t logp_stride, const float *adv, const float *old_value, const float *adv_stats3, double clip, float vf_coef,
@@ -402,8 +418,8 @@ int etm_heads_loss_branched_masked(const float *pre_p, const float *pre_v, const
  * AND branches, the convention of the k3 value; the joint KL is B times it), out8[6] = the k3 value that the twin puts into out8[4].
  * A statistic only (unless `kl_penalty`, the *_kl_penalty entries): the loss, gm_p, gm_v, out8[0..3], out8[5] and the twin's row are
  * the twin's bit for bit; sums
- * [etm_heads_loss_kl_row_floats = etm_heads_loss_row_floats + 1] carries the raw KL sum as its last element.  ETM_EINVAL: NULL or
- * 4-byte-misaligned old_logps, old_logps_stride < A; ETM_EUNSUPPORTED exactly where the twin returns it. */
+ * [etm_heads_loss_kl_row_floats = etm_heads_loss_row_floats + 1] carries the raw KL sum as its last element.  Refusals: the list
+ * above. */
 int etm_heads_loss_kl_row_floats(int hid, int A);
 int64_t etm_heads_loss_kl_workspace_bytes(int N, int hid, int A);
 int etm_heads_loss_kl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb, const float *bb,
@@ -443,7 +459,7 @@ int etm_heads_loss_gaussian(const float *pre_p, const float *pre_v, const float 
  * estimate that etm_heads_loss_gaussian puts into out8[4].  A statistic only (unless `kl_penalty`): the loss, gm_p, gm_v, out8[0..3], out8[5] and the
  * etm_heads_loss_gaussian row are that entry's bit for bit; sums [etm_heads_loss_gaussian_kl_row_floats =
  * etm_heads_loss_gaussian_row_floats + 1] carries the raw KL sum as its last element.  Shapes: etm_heads_loss_supported_gaussian.
- * ETM_EINVAL: NULL or 4-byte-misaligned old_mean / old_log_std, old_mean_stride < A. */
+ * Refusals: the list above. */
 int etm_heads_loss_gaussian_kl_row_floats(int hid, int A);
 int64_t etm_heads_loss_gaussian_kl_workspace_bytes(int N, int hid, int A);
 int etm_heads_loss_gaussian_kl(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
@@ -461,8 +477,7 @@ int etm_heads_loss_gaussian_kl(const float *pre_p, const float *pre_v, const flo
  *                q_na = (old_mean_na - mean_na) / sigma_a, d_a = old_log_std_a - log_std_a
  * join d logits before the heads' backward: gm_p, gm_v and every gradient element of sums (Box: d log_std too) are those of L + coef K;
  * equal policies add exactly 0.  out8[2] = the twin's loss + coef K, out8[7] = coef (0 elsewhere); logits, value, out8[0, 1, 3, 4, 5,
- * 6], the statistic sums, the row layout and the workspace are the twin's.  No launch is added.  ETM_EINVAL with nothing launched: a
- * NULL or 4-byte-misaligned kl_coef; otherwise exactly the twin's refusals. */
+ * 6], the statistic sums, the row layout and the workspace are the twin's.  No launch is added.  Refusals: the list above. */
 int etm_heads_loss_kl_penalty(const float *pre_p, const float *pre_v, const float *b_lp, const float *b_lv, const float *wb,
                               const float *bb, const float *wv, const float *bv, const int64_t *actions, int64_t action_stride,
                               const float *old_logp, int64_t logp_stride, const float *adv, const float *old_value,
@@ -1213,7 +1228,7 @@ int etm_ppo_loss(const float *logits, const int64_t *actions, int64_t action_str
 /* Invalid-action masks (ABI 58): etm_ppo_loss of one branch with action_mask [N] int64 (layout of etm_rollout_sample_branched_masked);
  * the branch's A actions are bits [mask_shift, mask_shift + A), mask_shift = its first column of the concatenated policy head (0 for
  * Discrete), mask_shift + A <= 63.  The rule of etm_heads_loss_masked: lse, log-prob and entropy over the valid actions, d_logits = 0
- * exactly on the invalid ones.  One sample per thread (no 16-byte form).  ETM_EINVAL for a NULL or misaligned action_mask. */
+ * exactly on the invalid ones.  One sample per thread (no 16-byte form).  Refusals: "Refusals of the loss entries" (etm_heads_loss). */
 int etm_ppo_loss_masked(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp, int64_t logp_stride,
                         const float *adv, const float *old_value, const float *value, const float *adv_stats3, double clip, float vf_coef,
                         float beta, float pol_scale, float ent_scale, float val_scale, int include_value, float *out8, float *d_logits,
@@ -1223,8 +1238,7 @@ int etm_ppo_loss_masked(const float *logits, const int64_t *actions, int64_t act
  * ignored) and old_logps [N, rows of old_logps_stride floats] (the *_logps sampling entries' rows), the branch's A columns starting at
  * column logps_off.  out8[4] = pol_scale sum_n KL_n (the rule of etm_heads_loss_kl), out8[6] = the k3 value; the loss, d_logits,
  * d_value, out8[0..3], out8[5] and partial slots 0..4 are those of the twin's one-sample-per-thread form, bit for bit; slot 5 of a
- * workgroup's 8 partial floats carries its raw KL sum.  ETM_EINVAL: NULL or 4-byte-misaligned old_logps, logps_off < 0,
- * old_logps_stride < logps_off + A; otherwise the twin's refusals. */
+ * workgroup's 8 partial floats carries its raw KL sum.  Refusals: "Refusals of the loss entries" (etm_heads_loss). */
 int etm_ppo_loss_kl(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp, int64_t logp_stride,
                     const float *adv, const float *old_value, const float *value, const float *adv_stats3, double clip, float vf_coef,
                     float beta, float pol_scale, float ent_scale, float val_scale, int include_value, float *out8, float *d_logits,
@@ -1235,7 +1249,8 @@ int etm_ppo_loss_kl(const float *logits, const int64_t *actions, int64_t action_
  * device float32 read in place).  d_logits is the gradient of L + coef K (a valid column gains coef pol_scale (p_j - p_old_j), an
  * invalid one stays exactly 0), out8[2] = the twin's loss + coef out8[4], out8[7] = coef; d_value, out8[0, 1, 3, 4, 5, 6] and the
  * partial slots are the twin's.  The term's p_j is exp((logit_j - max) - log(sum)), exact at the largest column (logit_j - lse would
- * carry half a spacing of lse, times coef): equal policies add a term of rounding size here, exactly 0 in the fused entries.  ETM_EINVAL with nothing launched: a NULL or 4-byte-misaligned kl_coef; otherwise the twin's refusals. */
+ * carry half a spacing of lse, times coef): equal policies add a term of rounding size here, exactly 0 in the fused entries.
+ * Refusals: "Refusals of the loss entries" (etm_heads_loss). */
 int etm_ppo_loss_kl_penalty(const float *logits, const int64_t *actions, int64_t action_stride, const float *old_logp,
                             int64_t logp_stride, const float *adv, const float *old_value, const float *value, const float *adv_stats3,
                             double clip, float vf_coef, float beta, float pol_scale, float ent_scale, float val_scale, int include_value,
