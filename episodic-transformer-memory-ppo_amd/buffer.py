@@ -31,12 +31,16 @@ the storage redesigned for the MI355X path:
   not) ``old_logps`` [W, S, sum A_b], the rollout's log-probs of every column of every branch (-inf where a column was masked out), a
   member of ``samples_flat``.  The rows live for one rollout (nothing of them is in a checkpoint).  Without the key it does not exist.
 * ``kl_penalty`` (absent upstream) implies ``exact_kl: true``: the same fields, for either policy kind (the penalty is a term in that KL).
+* ``previous_step_input`` (absent upstream): ``prev_actions`` [W, S, B] int64 (-1 at an episode's first step) and, with the reward,
+  ``prev_rewards`` [W, S] float32 (the raw reward, 0 there), members of ``samples_flat``; built on the device after the rollout by
+  ``build_previous_step`` (utils.previous_step_fields is the rule) with a per-worker carry across rollouts that a restart clears
+  (nothing of them is in a checkpoint).  Without the key neither exists.
 """
 import numpy as np
 import torch
 
 from etm import ops
-from utils import exact_kl_section, kl_estimator_section, kl_penalty_section, normalization_section
+from utils import exact_kl_section, kl_estimator_section, kl_penalty_section, normalization_section, previous_step_input_section
 
 
 class Buffer:
@@ -100,6 +104,20 @@ class Buffer:
         self.old_logps = None
         if exact and not continuous:
             self.old_logps = torch.zeros((W, S, sum(int(a) for a in action_space_shape)), dtype=torch.float32, device=dev)
+
+        # previous_step_input (absent upstream): what the model is fed of step t - 1 at every sample -- ``prev_actions`` [W, S, B] int64
+        # (-1 in every branch at an episode's first step) and, with the reward, ``prev_rewards`` [W, S] float32 (the RAW reward, 0 there);
+        # members of ``samples_flat``.  Built on the device after the rollout (``build_previous_step``; utils.previous_step_fields is the
+        # rule) from ``actions``, the raw rewards, the done flags and the carry of the rollout before: the last step's action and reward
+        # per worker and whether its episode goes on (``prev_live``; all False at the start and after a restart).  None without the key
+        self.prev_actions = self.prev_rewards = self.prev_live = None
+        prev_cfg = None if continuous else previous_step_input_section(config)
+        if prev_cfg is not None:
+            self.prev_actions = torch.full((W, S, B), -1, dtype=torch.int64, device=dev)
+            self.prev_rewards = torch.zeros((W, S), dtype=torch.float32, device=dev) if prev_cfg["reward"] else None
+            self._prev_carry_a = torch.full((W, B), -1, dtype=torch.int64, device=dev)
+            self._prev_carry_r = torch.zeros(W, dtype=torch.float32, device=dev)
+            self.prev_live = torch.zeros(W, dtype=torch.bool, device=dev)
 
         # return-based reward scaling (normalize_rewards): None without the key
         self.return_norm = normalization_section(config, "normalize_rewards")
@@ -211,6 +229,10 @@ class Buffer:
             samples["means"] = self.means
         if self.old_logps is not None:
             samples["old_logps"] = self.old_logps
+        if self.prev_actions is not None:
+            samples["prev_actions"] = self.prev_actions
+        if self.prev_rewards is not None:
+            samples["prev_rewards"] = self.prev_rewards
         self.samples_flat = {k: v.reshape(v.shape[0] * v.shape[1], *v.shape[2:]) for k, v in samples.items()}
 
     def mini_batch_generator(self, indices: torch.Tensor = None, materialize: bool = False):
@@ -239,6 +261,20 @@ class Buffer:
         mini_batch = {k: v.index_select(0, idx) for k, v in self.samples_flat.items()}
         mini_batch["memories"] = self.memories[mini_batch.pop("memory_index")] if materialize else self.memories
         return mini_batch
+
+    def build_previous_step(self) -> None:
+        """previous_step_input: ``prev_actions`` / ``prev_rewards`` of the rollout just staged, on the device, and the carry for the next
+        one (utils.previous_step_fields).  After ``calc_advantages``: ``rewards_dev`` (raw) and ``dones_dev`` are this rollout's."""
+        a, r, d = self.actions, self.rewards_dev, self.dones_dev
+        live = self.prev_live
+        self.prev_actions[:, 0] = torch.where(live.unsqueeze(1), self._prev_carry_a, torch.full_like(self._prev_carry_a, -1))
+        self.prev_actions[:, 1:] = torch.where(d[:, :-1].unsqueeze(2), torch.full_like(a[:, :-1], -1), a[:, :-1])
+        if self.prev_rewards is not None:
+            self.prev_rewards[:, 0] = torch.where(live, self._prev_carry_r, torch.zeros_like(self._prev_carry_r))
+            self.prev_rewards[:, 1:] = torch.where(d[:, :-1], torch.zeros_like(r[:, :-1]), r[:, :-1])
+        self._prev_carry_a.copy_(a[:, -1])
+        self._prev_carry_r.copy_(r[:, -1])
+        self.prev_live.copy_(~d[:, -1])
 
     def calc_advantages(self, last_value: torch.Tensor, gamma: float, lamda: float) -> None:
         """GAE over the [W, S] buffer on device (upstream buffer.py:95-113)."""

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from environments import action_space_kind
-from model import ActorCriticModel
+from model import ActorCriticModel, PreviousStep
 from trainer import build_window_tables
 from utils import create_env
 
@@ -33,6 +33,7 @@ def run_episode(model, env, config, device, max_steps=None, deterministic=False)
     memory, memory_mask, memory_indices = init_transformer_memory(config["transformer"], env.max_episode_steps, device)
     memory_length = config["transformer"]["memory_length"]
     rewards, info, done, t = [], None, False, 0
+    prev_action, prev_reward = [0] * len(getattr(model, "action_space_shape", (0,))), 0.0
     obs = env.reset()
     # byte image observations go to the model as they are (byte k stands for k / 255: model._encode), anything else as float32
     from environments import observation_dtype
@@ -49,6 +50,11 @@ def run_episode(model, env, config, device, max_steps=None, deterministic=False)
         masked = {}
         if hasattr(env, "action_masks") and not getattr(model, "continuous", False):
             masked["action_mask"] = np.asarray(env.action_masks(), dtype=bool).reshape(1, -1)
+        if getattr(model, "prev_input", None) is not None:
+            # previous_step_input: the action and the raw reward of the step before (none at the episode's first step)
+            masked["prev"] = PreviousStep(torch.tensor([prev_action], dtype=torch.int64, device=device),
+                                          torch.tensor([prev_reward], dtype=torch.float32, device=device),
+                                          torch.tensor([t], dtype=torch.int64, device=device))
         policy, _value, new_memory = model(obs_t, in_memory, mask, indices, **masked)
         memory[:, t] = new_memory.detach()
         if getattr(model, "continuous", False):      # Box: one Gaussian draw of A dimensions, clipped to the space's bounds
@@ -59,6 +65,8 @@ def run_episode(model, env, config, device, max_steps=None, deterministic=False)
             action = [(branch.logits.argmax(dim=-1) if deterministic else branch.sample()).item() for branch in policy]
         obs, reward, done, info = env.step(action)
         rewards.append(reward)
+        if not getattr(model, "continuous", False):
+            prev_action, prev_reward = [int(a) for a in action], float(reward)
         t += 1
     return rewards, info
 

@@ -226,6 +226,14 @@ SIGNATURES["etm_heads_loss_kl_workspace_bytes"] = (_L, [_I, _I, _I])
 for _name in ("etm_heads_loss_kl", "etm_heads_loss_branched_kl", "etm_heads_loss_gaussian_kl", "etm_ppo_loss_kl"):
     _res, _args = SIGNATURES[_name]
     SIGNATURES[_name + "_penalty"] = (_res, _args[:-1] + [_P] + _args[-1:])
+# previous_step_input (csrc/prev_input.hip; the ABI stays at 61 -- no signature above changes): the table's rows as an addend of
+# lin_hidden's pre-activation, and the table's gradient
+SIGNATURES["etm_prev_input_supported"] = (_I, [_I, _I])
+SIGNATURES["etm_prev_input_rows"] = (_I, [_P, _I, _I, _P, _L, _P, _I, _P, _P, _P, _P, _L, _L, _P])
+SIGNATURES["etm_prev_input_grad_chunk"] = (_I, [])
+SIGNATURES["etm_prev_input_grad_partial_rows"] = (_I, [_L])
+SIGNATURES["etm_prev_input_grad_workspace_bytes"] = (_L, [_L, _I, _I])
+SIGNATURES["etm_prev_input_grad"] = (_I, [_P, _L, _P, _L, _P, _I, _P, _P, _I, _I, _L, _P, _L, _P])
 del _twin
 del _name, _extra, _res, _args
 

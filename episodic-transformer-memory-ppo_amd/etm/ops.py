@@ -1911,14 +1911,117 @@ def _linear_backward(ctx, g, weight, y):
     return g, dx, db
 
 
+def _prev_input_args(table, actions, sizes, rewards, N=None):
+    """Checked (R, D, N, actions pointer, row stride, branch table, branch count, rewards) of the two etm_prev_input_* entries."""
+    _need_dev(table, actions)
+    if rewards is not None and not (rewards.is_cuda or rewards.is_pinned()):       # (the rollout reads its pinned block in place)
+        raise RuntimeError("prev_input: rewards must be in device or pinned host memory")
+    if table.dim() != 2 or table.dtype != torch.float32 or not table.is_contiguous():
+        raise TypeError("prev_input: the table must be a contiguous float32 [R, D] tensor")
+    R, D = table.shape
+    sizes = tuple(int(a) for a in sizes)
+    if not _lib.load().etm_prev_input_supported(R, D):
+        raise RuntimeError(f"prev_input: a table of {R} rows x {D} columns is outside the kernels (1 .. 64 rows)")
+    if sizes:
+        if actions is None or actions.dtype != torch.int64 or actions.dim() != 2 or actions.shape[1] != len(sizes) or actions.stride(1) != 1:
+            raise TypeError(f"prev_input: actions must be int64 [N, {len(sizes)}] with unit column stride")
+        N = actions.shape[0]
+    if rewards is not None:
+        if rewards.dtype != torch.float32 or rewards.dim() != 1 or not rewards.is_contiguous() or (sizes and rewards.shape[0] != N):
+            raise TypeError("prev_input: rewards must be a contiguous float32 [N] tensor")
+        N = rewards.shape[0]
+    if N is None or sum(sizes) + (rewards is not None) > R or not (sizes or rewards is not None):
+        raise ValueError(f"prev_input: branches {sizes}{' + the reward row' if rewards is not None else ''} do not fit a table of {R} rows")
+    return (R, D, N, _ptr(actions) if sizes else None, actions.stride(0) if sizes else 0, _c_ints(sizes) if sizes else None, len(sizes),
+            _ptr(rewards))
+
+
+def prev_input_rows(table, actions, sizes, rewards=None, ep_step=None, bias=None, out=None):
+    """The addend of ``previous_step_input`` (etm_prev_input_rows; utils.previous_step_rows is the rule, bit for bit): [N, D] =
+    sum_b table[off_b + actions[:, b]] + rewards[:, None] * table[-1] (+ ``bias``), +0 (+ bias) where a sample has no previous step --
+    ``ep_step`` [N] int64 (device or pinned host memory; the rollout form): where its word is 0; without it (the training form): where
+    actions[:, 0] < 0.  ``actions`` [N, B] int64 (any row stride), ``sizes`` the B branch sizes (empty: the action rows are not fed
+    back).  ``out``: a float32 [N, D] destination with unit column stride."""
+    lib = _lib.load()
+    _need_dev(bias, out)
+    R, D, N, a_ptr, a_ld, c_sizes, B, r_ptr = _prev_input_args(table, actions, sizes, rewards)
+    if ep_step is not None and (ep_step.dtype != torch.int64 or ep_step.dim() != 1 or ep_step.shape[0] != N or not ep_step.is_contiguous()
+                                or not (ep_step.is_cuda or ep_step.is_pinned())):
+        raise TypeError("prev_input_rows: ep_step must be a contiguous int64 [N] tensor in device or pinned host memory")
+    if bias is not None and (bias.dtype != torch.float32 or bias.shape != (D,) or not bias.is_contiguous()):
+        raise TypeError("prev_input_rows: bias must be a contiguous float32 [D] tensor")
+    if out is None:
+        out = torch.empty((N, D), dtype=torch.float32, device=table.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (N, D) or out.stride(1) != 1:
+        raise TypeError("prev_input_rows: out must be a float32 [N, D] tensor with unit column stride")
+    _lib.check(lib.etm_prev_input_rows(_ptr(table), R, D, a_ptr, a_ld, c_sizes, B, r_ptr, _ptr(ep_step), _ptr(bias), _ptr(out), out.stride(0), N,
+                                       _stream()), "etm_prev_input_rows")
+    return out
+
+
+def prev_input_grad(gm, table_like, actions, sizes, rewards=None, out=None):
+    """The table's gradient (etm_prev_input_grad; utils.previous_step_table_grad is the rule): [R, D] = sum_n c_n^T gm[n] over the
+    samples that have a previous step (actions[:, 0] >= 0), fixed summation order, no atomics.  ``gm`` [N, D] float32 with unit column
+    stride; ``table_like``: the table (its shape is what is read); ``out``: a contiguous [R, D] destination."""
+    lib = _lib.load()
+    _need_dev(gm, out)
+    R, D, N, a_ptr, a_ld, c_sizes, B, r_ptr = _prev_input_args(table_like, actions, sizes, rewards)
+    if gm.dtype != torch.float32 or tuple(gm.shape) != (N, D) or gm.stride(1) != 1:
+        raise TypeError(f"prev_input_grad: gm must be a float32 [{N}, {D}] tensor with unit column stride")
+    if out is None:
+        out = torch.empty((R, D), dtype=torch.float32, device=gm.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (R, D) or not out.is_contiguous():
+        raise TypeError("prev_input_grad: out must be a contiguous float32 [R, D] tensor")
+    nbytes = lib.etm_prev_input_grad_workspace_bytes(N, R, D)
+    ws = workspace(nbytes, gm.device, "prev_input_grad")          # (fixed address once a graph has captured it: freeze_workspaces)
+    _lib.check(lib.etm_prev_input_grad(_ptr(gm), gm.stride(0), a_ptr, a_ld, c_sizes, B, r_ptr, _ptr(out), R, D, N, _ptr(ws), nbytes, _stream()),
+               "etm_prev_input_grad")
+    return out
+
+
+class _PrevInputFn(torch.autograd.Function):
+    """The addend of ``previous_step_input`` under autograd, over the two kernels: forward ``prev_input_rows`` in its training form
+    (with lin_hidden's bias folded in, so the layer's forward needs no pass of its own for it), backward ``prev_input_grad`` of the
+    incoming gradient -- which, from _LinearFn / _LinearReluNhwcFn, is gm = g * (y > 0).  The table's gradient goes straight into the
+    parameter's arena view when a DeferredDw collector knows it.  The bias gets its gradient from the linear node (column sums of gm)."""
+
+    @staticmethod
+    def forward(ctx, table, actions, rewards, sizes, bias):
+        ctx.actions, ctx.rewards, ctx.sizes, ctx.table_ptr = actions, rewards, tuple(sizes), table.data_ptr()
+        ctx.save_for_backward(table)
+        return prev_input_rows(table.detach(), actions, sizes, rewards, bias=None if bias is None else bias.detach())
+
+    @staticmethod
+    def backward(ctx, g):
+        (table,) = ctx.saved_tensors
+        g = g if g.dtype == torch.float32 and g.stride(1) == 1 else _f32c(g, "grad")
+        dest = DeferredDw.claim([ctx.table_ptr])
+        if dest is not None and tuple(dest[0].shape) == tuple(table.shape):
+            prev_input_grad(g, table, ctx.actions, ctx.sizes, ctx.rewards, out=dest[0])
+            return None, None, None, None, None
+        return prev_input_grad(g, table, ctx.actions, ctx.sizes, ctx.rewards), None, None, None, None
+
+
+def prev_input_addend(table, actions, sizes, rewards=None, bias=None):
+    """``previous_step_input``'s addend [N, D] (+ ``bias``) as an autograd node over the two kernels (see _PrevInputFn); the operand
+    ``addend`` of ``linear_relu_train`` / ``linear_relu_nhwc``."""
+    return _PrevInputFn.apply(table, actions, rewards, tuple(sizes), bias)
+
+
 class _LinearFn(torch.autograd.Function):
     """y = x W^T, x W^T + b or (``relu``) relu(x W^T + b) for 2-D fp32 device tensors: library GEMMs for y and dx, the backward's
     element-wise part in _linear_backward, the weight gradient to the grouped launch when a DeferredDw collector is active.
-    transformer.py:26-29 queries / fc_out, :115 fc without their epilogues; fc_out with its bias on the pre-LN / gated blocks."""
+    transformer.py:26-29 queries / fc_out, :115 fc without their epilogues; fc_out with its bias on the pre-LN / gated blocks.
+    ``addend`` (relu form only; previous_step_input): [N, out] that already holds e + b, so y = relu(x W^T + addend); its gradient is
+    gm.  None: exactly the calls without it."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu):
-        if relu:
+    def forward(ctx, x, weight, bias, relu, addend=None):
+        if addend is not None:
+            if not relu:
+                raise ValueError("_LinearFn: an addend belongs to the relu form")
+            y = torch.relu_(torch.addmm(addend, x, weight.t()))
+        elif relu:
             y = _addmm_relu(bias, x, weight.t())
         elif bias is not None:
             y = torch.addmm(bias, x, weight.t())
@@ -1926,6 +2029,7 @@ class _LinearFn(torch.autograd.Function):
             y = x.mm(weight.t())
         ctx.save_for_backward(x, weight, y if relu else None)
         ctx.bias_ptr = None if bias is None else bias.data_ptr()
+        ctx.has_addend = addend is not None
         return y
 
     @staticmethod
@@ -1935,6 +2039,8 @@ class _LinearFn(torch.autograd.Function):
         dw = None
         if ctx.needs_input_grad[1] and not DeferredDw.defer(g, x, weight):
             dw = g.t().mm(x)
+        if ctx.has_addend:
+            return dx, dw, db, None, g
         return dx, dw, db, None
 
 
@@ -1957,16 +2063,19 @@ class _LinearReluNhwcFn(torch.autograd.Function):
     """relu(x Wp^T + b) for NHWC-flattened features x [N, HW * C] and a weight kept in upstream's (c, h, w) column order
     (model.py:94): Wp = the weight with its columns in (h, w, c) order.  The permutation lives INSIDE the node: one permuting copy
     of the weight forward, and backward the weight gradient is permuted straight into the parameter's arena view when a DeferredDw
-    collector knows it (one permuting copy instead of a permute-back copy plus the gradient packing copy)."""
+    collector knows it (one permuting copy instead of a permute-back copy plus the gradient packing copy).
+    ``addend`` (previous_step_input): [N, out] that already holds e + b, so y = relu(x Wp^T + addend); its gradient is gm.  None:
+    exactly the calls without it."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, channels):
+    def forward(ctx, x, weight, bias, channels, addend=None):
         out, feat = weight.shape
         hw = feat // channels
         wp = weight.detach().view(out, channels, hw).transpose(1, 2).reshape(out, feat)       # [out, (h, w, c)]
-        y = _addmm_relu(bias, x, wp.t())
+        y = _addmm_relu(bias, x, wp.t()) if addend is None else torch.relu_(torch.addmm(addend, x, wp.t()))
         ctx.save_for_backward(x, wp, y)
         ctx.bias_ptr, ctx.weight_ptr, ctx.channels = bias.data_ptr(), weight.data_ptr(), channels
+        ctx.has_addend = addend is not None
         return y
 
     @staticmethod
@@ -1982,17 +2091,25 @@ class _LinearReluNhwcFn(torch.autograd.Function):
                 dest[0].view(dwp.shape).copy_(dwp)
             else:
                 dw = dwp.reshape(out, feat)
+        if ctx.has_addend:
+            return dx, dw, db, None, gm
         return dx, dw, db, None
 
 
-def linear_relu_nhwc(x, weight, bias, channels):
-    """relu(F.linear(x, nhwc_columns(weight, channels), bias)) as one autograd node (see _LinearReluNhwcFn)."""
-    return _LinearReluNhwcFn.apply(x, weight, bias, channels)
+def linear_relu_nhwc(x, weight, bias, channels, addend=None):
+    """relu(F.linear(x, nhwc_columns(weight, channels), bias)) as one autograd node (see _LinearReluNhwcFn); with ``addend`` (of
+    ``prev_input_addend`` WITH this bias) relu(F.linear(x, nhwc_columns(weight, channels)) + addend)."""
+    if addend is None:
+        return _LinearReluNhwcFn.apply(x, weight, bias, channels)
+    return _LinearReluNhwcFn.apply(x, weight, bias, channels, addend)
 
 
-def linear_relu_train(x, weight, bias):
-    """relu(F.linear(x, weight, bias)) for 2-D fp32 device tensors under autograd (see _LinearFn)."""
-    return _LinearFn.apply(x, weight, bias, True)
+def linear_relu_train(x, weight, bias, addend=None):
+    """relu(F.linear(x, weight, bias)) for 2-D fp32 device tensors under autograd (see _LinearFn); with ``addend`` (of
+    ``prev_input_addend`` WITH this bias) relu(F.linear(x, weight) + addend)."""
+    if addend is None:
+        return _LinearFn.apply(x, weight, bias, True)
+    return _LinearFn.apply(x, weight, bias, True, addend)
 
 
 def linear_relu(lin, x, out=None):

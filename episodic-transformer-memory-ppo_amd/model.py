@@ -15,7 +15,17 @@ from etm import ops
 from etm import lib as etm_lib
 from etm.ops import WindowSpec
 from transformer import Transformer
-from utils import normalization_section
+from utils import normalization_section, previous_step_input_section, previous_step_table_rows
+
+
+class PreviousStep:
+    """What ``previous_step_input`` feeds back for N samples: ``actions`` [N, B] int64 (the previous step's action of every branch),
+    ``rewards`` [N] float32 (its raw reward; None where the key leaves the reward out), and which samples have a previous step at all
+    -- ``ep_step`` [N] int64 (the rollout's form: the episode step, 0 at an episode's first step; the actions of such a row are stale
+    and not read), or, without it (the buffer's form), a negative entry in column 0 of ``actions``."""
+
+    def __init__(self, actions, rewards=None, ep_step=None):
+        self.actions, self.rewards, self.ep_step = actions, rewards, ep_step
 
 
 def obs_norm_table(stats, epsilon):
@@ -125,6 +135,15 @@ class ActorCriticModel(nn.Module):
             if len(self.action_space_shape) != 1:
                 raise ValueError("a Box policy has one mean head of A outputs: action_space_shape must be (A,)")
             self.policy_log_std = nn.Parameter(torch.full((self.action_space_shape[0],), float(config.get("action_log_std_init", 0.0))))
+        # previous_step_input (absent upstream): the previous step's action(s) and raw reward enter lin_hidden's pre-activation through
+        # a learned table [R, lin_hidden.out_features] -- branch b owns rows off_b .. off_b + A_b - 1, the reward row is the last
+        # (utils.previous_step_rows is the rule).  Zeros at the start: the run begins as the function without the key.  Registered last,
+        # so every other parameter keeps its place in the arena; the parameter exists only with the key.
+        self.prev_cfg = previous_step_input_section(config, self.action_space_shape, box=self.continuous)
+        self.prev_input = None
+        if self.prev_cfg is not None:
+            self.prev_input = nn.Embedding(previous_step_table_rows(self.action_space_shape, self.prev_cfg["reward"]), self.memory_layer_size)
+            nn.init.zeros_(self.prev_input.weight)
 
     def arena_parameters(self):
         """(name, parameter) pairs in the order of the optimiser's flat arena: ``named_parameters()``, except that a Box policy's
@@ -367,7 +386,70 @@ class ActorCriticModel(nn.Module):
             if "hid_t" in self._rf:
                 self._rfg["hid_t"] = self._rf["hid_t"]
 
-    def _encode_fused(self, obs, obs_index=None, obs_rows=None, features_only=False):
+    def _prev_addend(self, prev):
+        """``previous_step_input``: e + lin_hidden.bias [N, D] for the samples of ``prev`` (a PreviousStep) -- on the device the rows
+        kernel (under autograd: the node over the rows and the gradient kernel), on a CPU tensor the same expression in torch."""
+        if prev is None:
+            raise ValueError("previous_step_input: this model was built with the key and needs the previous step on every pass "
+                             "(prev=PreviousStep(actions, rewards, ep_step)); there is no pass without it")
+        table, bias = self.prev_input.weight, self.lin_hidden.bias
+        sizes = self.action_space_shape if self.prev_cfg["action"] else ()
+        rewards = prev.rewards if self.prev_cfg["reward"] else None
+        if self.prev_cfg["reward"] and rewards is None:
+            raise ValueError("previous_step_input: reward: true needs PreviousStep.rewards")
+        actions = prev.actions if prev.actions is None or prev.actions.dim() == 2 else prev.actions.reshape(prev.actions.shape[0], -1)
+        if table.is_cuda:
+            if torch.is_grad_enabled():
+                if prev.ep_step is not None:      # (the rollout's form under autograd: rewritten into the buffer's form)
+                    has = prev.ep_step != 0
+                    actions = None if actions is None else torch.where(has.unsqueeze(1), actions, torch.full_like(actions, -1))
+                    rewards = None if rewards is None else torch.where(has, rewards, torch.zeros_like(rewards))
+                return ops.prev_input_addend(table, actions, sizes, rewards, bias=bias)
+            return ops.prev_input_rows(table, actions, sizes, rewards, ep_step=prev.ep_step, bias=bias)
+        n = actions.shape[0] if sizes else rewards.shape[0]
+        has = torch.ones(n, dtype=torch.bool) if not sizes else actions[:, 0] >= 0
+        if prev.ep_step is not None:
+            has = prev.ep_step != 0
+        e, off = torch.zeros((n, table.shape[1]), dtype=table.dtype), 0
+        for b, size in enumerate(sizes):
+            e = e + table[off + actions[:, b].clamp(0, size - 1)]
+            off += size
+        if rewards is not None:
+            e = e + rewards.to(table.dtype).unsqueeze(1) * table[-1]
+        return torch.where(has.unsqueeze(1), e, torch.zeros_like(e)) + bias
+
+    def _hidden(self, x, prev=None):
+        """lin_hidden on the encoder's features ``x`` [N, F]: relu(x W^T + b), or, with ``previous_step_input``, relu(x W^T + e + b)."""
+        if self.prev_input is None:
+            if prev is not None:
+                raise ValueError("a previous step was handed to a model built without previous_step_input")
+            return ops.linear_relu(self.lin_hidden, x)
+        addend = self._prev_addend(prev)
+        if x.is_cuda and torch.is_grad_enabled() and x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous():
+            return ops.linear_relu_train(x, self.lin_hidden.weight, self.lin_hidden.bias, addend=addend)
+        return torch.relu(torch.addmm(addend, x, self.lin_hidden.weight.t()))
+
+    def rollout_features(self, obs, obs_index=None, obs_rows=None):
+        """What lin_hidden reads in a no-grad rollout step, [N, F] float32 -- the (normalised) vector observation, or the fused
+        encoder's features -- for a caller that forms x W^T itself (the step kernel's two-slice input with ``previous_step_input``);
+        None where only ``_encode``'s road builds them (library convolutions)."""
+        if self.obs_norm is not None:
+            return self.normalize_observations(obs)
+        if not self.visual:
+            return obs if obs.dtype == torch.float32 and obs.dim() == 2 else None
+        if obs_index is not None or self._fused_encoder_ok(obs):
+            return self._encode_fused(obs, obs_index, obs_rows, features_only=True)
+        return None
+
+    def _hidden_nhwc(self, feats, prev=None):
+        """``_hidden`` for the NHWC-flattened features of the training encoder (ops.linear_relu_nhwc)."""
+        if self.prev_input is None:
+            if prev is not None:
+                raise ValueError("a previous step was handed to a model built without previous_step_input")
+            return ops.linear_relu_nhwc(feats, self.lin_hidden.weight, self.lin_hidden.bias, self.conv3.out_channels)
+        return ops.linear_relu_nhwc(feats, self.lin_hidden.weight, self.lin_hidden.bias, self.conv3.out_channels, addend=self._prev_addend(prev))
+
+    def _encode_fused(self, obs, obs_index=None, obs_rows=None, features_only=False, prev=None):
         if getattr(self, "_w2p", None) is None or (not torch.cuda.is_current_stream_capturing()
                                                      and self._wver != (self.conv1.weight._version, self.conv2.weight._version,
                                                                         self.conv3.weight._version)):
@@ -384,9 +466,9 @@ class ActorCriticModel(nn.Module):
         x = ops.conv_relu(x, self._w3p, self.conv3.bias, 64, h2, w2, 3, 3, 1, True, True)                                # -> NCHW
         if features_only:
             return x.reshape(n, -1)
-        return ops.linear_relu(self.lin_hidden, x.reshape(n, -1))
+        return self._hidden(x.reshape(n, -1), prev)
 
-    def _encode(self, obs, obs_index=None, obs_rows=None):
+    def _encode(self, obs, obs_index=None, obs_rows=None, prev=None):
         """Observation encoder.  ``obs_index`` (int64 device scalar, fused rollout encoder only): ``obs`` is a time-major
         stack [S, N, C, H, W] and row obs[obs_index] is encoded (the row is selected on the device).  ``obs`` may be an
         ``IndexedObservations(bank_nhwc, index)``: the minibatch = bank_nhwc[index], gathered inside the first encoder layer.
@@ -399,7 +481,7 @@ class ActorCriticModel(nn.Module):
                 raise ValueError("normalize_observations: a vector observation must be float32")
             if obs_index is not None:
                 raise RuntimeError("obs_index needs the fused rollout encoder (visual observations, no grad)")
-            return ops.linear_relu(self.lin_hidden, self.normalize_observations(obs))
+            return self._hidden(self.normalize_observations(obs), prev)
         if raw.dtype == torch.uint8:
             if not self.visual:
                 raise ValueError("uint8 observations are images (byte k = k / 255); a vector observation must be float32")
@@ -418,7 +500,7 @@ class ActorCriticModel(nn.Module):
                     feats = ops.encoder_train(obs.bank, self.conv1, self.conv2, self.conv3, index=obs.index, products=self.encoder_products)
                     if getattr(self, "_keep_encoder_features", False):      # data-parallel overlap: the backward pass is cut here
                         self._encoder_features = feats                      # (trainer._train_body_a1; released by _train_body_a2)
-                    return ops.linear_relu_nhwc(feats, self.lin_hidden.weight, self.lin_hidden.bias, self.conv3.out_channels)
+                    return self._hidden_nhwc(feats, prev)
             if obs.bank.dtype == torch.uint8:      # (device: the gather rides in the expansion)
                 obs = ops.bytes_to_unit(obs.bank, index=obs.index).permute(0, 3, 1, 2)
             else:
@@ -426,10 +508,10 @@ class ActorCriticModel(nn.Module):
         if obs_index is not None:
             if not self._fused_encoder_ok(obs[0]):
                 raise RuntimeError("obs_index needs the fused rollout encoder (visual observations, no grad)")
-            return self._encode_fused(obs, obs_index, obs_rows)
+            return self._encode_fused(obs, obs_index, obs_rows, prev=prev)
         h = obs
         if self._fused_encoder_ok(obs):
-            return self._encode_fused(obs)
+            return self._encode_fused(obs, prev=prev)
         if self.visual and self.train_encoder and obs.is_cuda and torch.is_grad_enabled() and obs.dim() == 4:
             if self._train_encoder_ok is None:
                 self._train_encoder_ok = ops.encoder_train_supported(self.observation_space_shape, (self.conv1, self.conv2, self.conv3))
@@ -438,7 +520,7 @@ class ActorCriticModel(nn.Module):
                 # optimisation phase: the three relu(conv2d) layers forward and backward on the hand-written MFMA kernels
                 # (NHWC activations; the trainer hands over an NCHW view of NHWC memory, which permutes back for free)
                 feats = ops.encoder_train(obs.permute(0, 2, 3, 1), self.conv1, self.conv2, self.conv3, products=self.encoder_products)      # (h, w, c) flatten order
-                return ops.linear_relu_nhwc(feats, self.lin_hidden.weight, self.lin_hidden.bias, self.conv3.out_channels)
+                return self._hidden_nhwc(feats, prev)
         if self.visual:
             if h.dtype == torch.uint8:      # library convolutions: the floats first (in the memory order the bytes have)
                 nhwc = h.permute(0, 2, 3, 1)
@@ -451,7 +533,7 @@ class ActorCriticModel(nn.Module):
             h = F.relu(self.conv2(h))
             h = F.relu(self.conv3(h))
             h = h.reshape(h.shape[0], -1)
-        return ops.linear_relu(self.lin_hidden, h)
+        return self._hidden(h, prev)
 
     def normalize_observations(self, obs):
         """clamp((obs - mean) * rstd, -clip, +clip) in fp32 with the frozen table, subtraction and product rounded separately: the one
@@ -475,13 +557,14 @@ class ActorCriticModel(nn.Module):
             self.obs_norm_mean.copy_(mean)
             self.obs_norm_rstd.copy_(rstd)
 
-    def forward_state(self, obs, spec: WindowSpec, want_items=False):
+    def forward_state(self, obs, spec: WindowSpec, want_items=False, prev=None):
         """Encoder + transformer: -> (h [N, D] in front of the hidden heads (model.py:100), new memory items or None)."""
-        return self.transformer.forward_window(self._encode(obs), spec, want_items)
+        return self.transformer.forward_window(self._encode(obs, prev=prev), spec, want_items)
 
-    def forward_logits(self, obs, spec: WindowSpec, want_items=True):
-        """-> (list of raw logits per branch, value [N], new memory items [N, blocks, D] or None)."""
-        h, memory = self.transformer.forward_window(self._encode(obs), spec, want_items)
+    def forward_logits(self, obs, spec: WindowSpec, want_items=True, prev=None):
+        """-> (list of raw logits per branch, value [N], new memory items [N, blocks, D] or None).  ``prev``: the samples'
+        PreviousStep, with ``previous_step_input`` (every entry below takes it and hands it to the encoder)."""
+        h, memory = self.transformer.forward_window(self._encode(obs, prev=prev), spec, want_items)
         h_policy = ops.linear_relu(self.lin_policy, h)
         h_value = ops.linear_relu(self.lin_value, h)
         value = self.value(h_value).reshape(-1)
@@ -493,19 +576,19 @@ class ActorCriticModel(nn.Module):
         return (getattr(self, "_w_heads", None) is not None and self.rollout_policy_head() is not None
                 and not torch.is_grad_enabled())
 
-    def forward_hidden_cached(self, obs, kv_spec: WindowSpec, items_out=None, obs_index=None, raw=False, obs_rows=None):
+    def forward_hidden_cached(self, obs, kv_spec: WindowSpec, items_out=None, obs_index=None, raw=False, obs_rows=None, prev=None):
         """Rollout path up to the hidden heads: -> (h2 [N, 2*hidden] = [relu(lin_policy(h)) | relu(lin_value(h))], memory).
         ``raw=True``: h2 are the PRE-activations (plain GEMM without epilogue); the caller applies relu(h2 + self._b_heads)
         (``ops.rollout_policy(h_bias=...)`` does it on the fly)."""
-        h, memory = self.transformer.forward_cached(self._encode(obs, obs_index, obs_rows), kv_spec, items_out)
+        h, memory = self.transformer.forward_cached(self._encode(obs, obs_index, obs_rows, prev=prev), kv_spec, items_out)
         if raw:
             return F.linear(h, self._w_heads), memory
         return ops.linear_relu(self._heads_lin, h), memory
 
-    def forward_logits_cached(self, obs, kv_spec: WindowSpec, items_out=None, obs_index=None, obs_rows=None):
+    def forward_logits_cached(self, obs, kv_spec: WindowSpec, items_out=None, obs_index=None, obs_rows=None, prev=None):
         """Rollout path (no grad): like ``forward_logits`` but attention reads the per-worker K/V cache.  With ``items_out``
         [blocks, N, D] the new memory items are written there (block-major) and returned in that layout."""
-        h, memory = self.transformer.forward_cached(self._encode(obs, obs_index, obs_rows), kv_spec, items_out)
+        h, memory = self.transformer.forward_cached(self._encode(obs, obs_index, obs_rows, prev=prev), kv_spec, items_out)
         if self.rollout_heads_fusable():
             # [lin_policy ; lin_value] as ONE GEMM (+ReLU epilogue), then both output heads in one small kernel (several branches:
             # the concatenated policy heads, the logits split into the branches' column views)
@@ -519,22 +602,22 @@ class ActorCriticModel(nn.Module):
         value = self.value(h_value).reshape(-1)
         return [branch(h_policy) for branch in self.policy_branches], value, memory
 
-    def forward_banked(self, obs, spec: WindowSpec, action_mask=None):
+    def forward_banked(self, obs, spec: WindowSpec, action_mask=None, prev=None):
         """``action_mask`` (optional, categorical policies): invalid-action masks of the N samples, bool [N, sum A_b] (the branches'
         actions side by side, sb3-contrib's ``action_masks()`` layout) or the packed int64 / uint64 words [N]
         (``environments.pack_action_masks``): the logits of the invalid actions are -inf in the returned distributions."""
         if self.continuous and action_mask is not None:
             raise ValueError("a Box policy has no action mask")
-        logits, value, memory = self.forward_logits(obs, spec)
+        logits, value, memory = self.forward_logits(obs, spec, prev=prev)
         if self.continuous:        # Box: [Normal(mean, exp(policy_log_std))]
             return [Normal(logits[0], self.policy_log_std.exp().expand_as(logits[0]), validate_args=False)], value, memory
         if action_mask is not None:
             logits = masked_logits(logits, action_mask)
         return [Categorical(logits=l, validate_args=False) for l in logits], value, memory
 
-    def forward(self, obs, memory, memory_mask, memory_indices, action_mask=None):
+    def forward(self, obs, memory, memory_mask, memory_indices, action_mask=None, prev=None):
         """Upstream signature; memory [N, L, blocks, D] is the pre-gathered window.  ``action_mask``: see ``forward_banked``."""
-        return self.forward_banked(obs, WindowSpec.from_windows(memory, memory_indices, memory_mask), action_mask=action_mask)
+        return self.forward_banked(obs, WindowSpec.from_windows(memory, memory_indices, memory_mask), action_mask=action_mask, prev=prev)
 
     def get_conv_output(self, shape) -> int:
         with torch.no_grad():
@@ -546,7 +629,7 @@ class ActorCriticModel(nn.Module):
         groups = {}
         if self.visual:
             groups["encoder"] = [self.conv1, self.conv2, self.conv3]
-        groups["linear_layer"] = [self.lin_hidden]
+        groups["linear_layer"] = [self.lin_hidden] if self.prev_input is None else [self.lin_hidden, self.prev_input]
         for i, block in enumerate(self.transformer.transformer_blocks):
             groups["transformer_block_" + str(i)] = [block]
         for i, head in enumerate(self.policy_branches):

@@ -77,6 +77,9 @@ class WorkerGroup:
         # twin (measurement only: PPOTrainer._mask_in_place); contiguous slices; None without the key
         self.am_pin = None if tr._am_pin is None else tr._am_pin[lo:hi]
         self.am_dev = None if tr._am_dev is None else tr._am_dev[lo:hi]
+        # previous_step_input: the group's entries of the trainer's pinned block of last rewards (read in place by the rows kernel in
+        # front of the step; a contiguous slice); None without the key or its reward
+        self.rw_pin = None if tr._rw_pin is None else tr._rw_pin[lo:hi]
         self.item = torch.zeros((tr.num_blocks, Wg, tr.embed_dim), dtype=torch.float32, device=dev)      # the step's new memory items, block-major
         self.t_dev = torch.zeros((), dtype=torch.int64, device=dev)      # step counter, incremented by the sampling kernel
         self.t_row = torch.zeros((), dtype=torch.int64, device=dev)      # staging row of the step, for its tail

@@ -49,9 +49,9 @@ from etm import lib as etm_lib
 from etm import ops
 from etm.ops import WindowSpec
 from etm.optim import AdaptiveLr, FlatAdamW, KlGate
-from model import ActorCriticModel, IndexedObservations
+from model import ActorCriticModel, IndexedObservations, PreviousStep
 from utils import (adaptive_lr_section, exact_kl_section, kl_estimator_section, kl_penalty_section, kl_penalty_step, normalization_section, polynomial_decay, process_episode_info, target_kl_rows,
-                   target_kl_section)
+                   target_kl_section, previous_step_input_section)
 from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
 from checkpoint import check_checkpoint_config, segment_first_worker_id
 from trainer_parts import _CheckpointResume, _DataParallelStep, _NativeRolloutDrive, _RunOutputs
@@ -361,6 +361,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         check_byte_observation_transport(config, env)
         check_truncation_transport(config, env)
         check_action_mask_config(config, env)
+        # previous_step_input: the value itself and the transport, before any environment or process is created (the shared segment of
+        # the worker processes has no row for the last reward); the action space is looked at below
+        previous_step_input_section(config, worker_processes=bool(env is None and config.get("worker_processes", False)))
         check_evaluation_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_normalization_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_checkpoint_config(config, 1 if dp is None else int(getattr(dp, "world", 1)), resume=resume is not None)
@@ -463,6 +466,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # action_masks: the environment's front-end, the width of the policy head and the kind of policy are known now
         self._masked = check_action_mask_config(config, self.env, self.action_space_shape, self.box is not None)
         self.last_valid_action_share = None       # mean share of allowed actions in the last rollout's words (None without the key)
+        # previous_step_input: {"action", "reward"} or None (the kind of policy and the table's rows are known now)
+        self._prev_cfg = previous_step_input_section(config, self.action_space_shape, box=self.box is not None)
         # kl_estimator: the kind of policy is known now.  "analytic": the four Gaussian sampling sites stage the means, the buffer
         # carries them and a snapshot of the log-std, the Gaussian heads + loss kernel reduces the exact KL into stats[4]
         self._kl_analytic = check_kl_estimator_config(config, self.box is not None, 1 if dp is None else int(getattr(dp, "world", 1))) == "analytic"
@@ -583,6 +588,14 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             self._am_np = self._am_pin.numpy()
             self._branch_bits = branch_bit_masks(self.action_space_shape)
             self._am_dev = torch.zeros(W, dtype=torch.int64, device=device)
+        # previous_step_input with the reward: the workers' last raw rewards, one pinned float32 [W] block that the rows kernel in front
+        # of a step reads IN PLACE -- the discipline of the mask words: the host writes a group's entries where it writes
+        # buffer.rewards[w, t], after env.step and before the next launch, i.e. after that step's actions are back.  Nothing is
+        # allocated without the key.
+        self._rw_pin = self._rw_np = None
+        if self._prev_cfg is not None and self._prev_cfg["reward"]:
+            self._rw_pin = torch.zeros(W, dtype=torch.float32).pin_memory()
+            self._rw_np = self._rw_pin.numpy()
         if resumed is not None and self._env_supplied and hasattr(self.env, "restart"):
             self.env.restart(first_worker_id)              # (a supplied environment moves to the segment's worker ids itself)
         self.env.reset(out=self.obs)
@@ -647,6 +660,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             bs.obs, bs.rows, bs.pidx = torch.empty_like(self._obs_dev), torch.empty_like(lv.rows), torch.empty_like(lv.rows)
             bs.slot, bs.s = torch.zeros(W, dtype=torch.int64, device=device), torch.zeros(W, dtype=torch.int64, device=device)
             bs.out = torch.empty(W, dtype=torch.float32, device=device)
+            if self._prev_cfg is not None:
+                bs.pa, bs.pr = torch.zeros((W, B), dtype=torch.int64, device=device), torch.zeros(W, dtype=torch.float32, device=device)
 
         # worker groups: the full-width group (eager path, single-group graph path) aliases the buffers above; the pipelined
         # groups own what cannot be a contiguous slice of them.  WorkerGroup reads from this object, so all of these exist by now:
@@ -916,7 +931,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # this loop is the rollout's critical path: what the plan fixes is bound to locals here, once
         buf, S, clock = self.buffer, self.config["worker_steps"], time.perf_counter
         direct, stream_obs, host_flag, polite = plan.direct_rows, plan.stream_obs, plan.host_flag, plan.polite_wait
-        masked = self._masked
+        masked, rw = self._masked, self._rw_np
         fence = self._etm.etm_host_store_fence
         t_env = t_wait = t_launch = 0.0
         for t in range(S):
@@ -950,6 +965,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                     self._take_action_masks(g.env, lo, hi, t + 1)
                     if t + 1 < S:
                         buf.action_masks_host[lo:hi, t + 1] = self._am_np[lo:hi]
+                if rw is not None:
+                    rw[lo:hi] = rewards              # (previous_step_input: the raw rewards the next step's rows kernel reads in place)
                 if t + 1 < S:
                     tl = clock()
                     launch(g, plan)                  # bookkeeping of this step is final: (step, slot) follow the observation rows
@@ -1036,6 +1053,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if self._bootstrap:                        # (after the staging copies: buf.memory_indices is final)
             self._bootstrap_pass()
         buf.calc_advantages(self.get_last_value(), self.config["gamma"], self.config["lamda"])
+        if self._prev_cfg is not None:       # (after the uploads of the raw rewards and the done flags)
+            buf.build_previous_step()
         self.last_update_timing.update(env_s=timing[0], wait_s=timing[1], launch_s=timing[2])
 
     def _check_forced_against_masks(self, forced):
@@ -1090,14 +1109,32 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         hidden = "full"
         if streamed and "hid_t" in rf:
             conv3 = self.config.get("fused_conv3_hidden", True) and ops.rollout_conv3_hidden_supported(m.conv3, *m.conv2_output_hw(), rf["hid_t"].shape[1])
+            if conv3 and self._prev_cfg is not None:
+                # previous_step_input adds one slice: one per output pixel + 1 must fit the step kernel's 64 slices, else `partial`
+                h2, w2 = m.conv2_output_hw()
+                conv3 = (h2 - 2) * (w2 - 2) + 1 <= 64
             hidden = "conv3" if conv3 else "partial"
         return True, rf, hidden
 
-    def _hidden_input(self, g, hidden, rf, obs, obs_index, rows):
+    def _hidden_input(self, g, hidden, rf, obs, obs_index, rows, ss_src=None):
         """The step kernel's hidden-layer input in the chosen form -> (h_in, the bias the kernel still has to add or None)."""
         m = self.model
+        prev = self._rollout_prev(g, ss_src)
         if hidden == "full":
-            return m._encode(obs, obs_index, rows), None
+            if prev is None:
+                return m._encode(obs, obs_index, rows), None
+            # previous_step_input: a TWO-SLICE input -- x W^T into slice 0, the term into slice 1, lin_hidden's bias as the kernel's
+            # bias: the step kernel's slices + bias + ReLU path.  (Where only the model's encoder builds the features -- library
+            # convolutions -- its own road: the rows kernel with the bias, then relu(x W^T + that).)
+            feats = m.rollout_features(obs, obs_index, rows)
+            if feats is None:
+                return m._encode(obs, obs_index, rows, prev=prev), None
+            if g.h_part is None:
+                g.h_part = torch.empty((2, feats.shape[0], m.lin_hidden.out_features), dtype=torch.float32, device=feats.device)
+            torch.mm(feats, m.lin_hidden.weight.t(), out=g.h_part[0])
+            sizes = self.action_space_shape if self._prev_cfg["action"] else ()
+            ops.prev_input_rows(m.prev_input.weight, prev.actions, sizes, prev.rewards, ep_step=prev.ep_step, out=g.h_part[1])
+            return g.h_part, m.lin_hidden.bias
         # lin_hidden as K-slice partial sums on 12 x 16 workgroups; the step kernel adds slices + bias + ReLU
         if hidden == "conv3":
             # the last encoder layer and lin_hidden's partial sums as ONE launch, one workgroup per output pixel
@@ -1107,9 +1144,28 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         else:
             x, partial_sums = m._encode_fused(obs, obs_index, rows, features_only=True), ops.rollout_hidden_partial
             args = (rf["hid_t"],)
+        if prev is not None:
+            # previous_step_input rides in as ONE MORE SLICE: the producer writes the first `splits` slices of the fixed-address block,
+            # the rows kernel the last one, the step kernel adds the slices in slice order, then the bias, then the ReLU
+            if g.h_part is None:
+                first = partial_sums(x, *args)
+                g.h_part = torch.empty((first.shape[0] + 1,) + tuple(first.shape[1:]), dtype=first.dtype, device=first.device)
+            splits = g.h_part.shape[0] - 1
+            partial_sums(x, *args, out=g.h_part[:splits])
+            sizes = self.action_space_shape if self._prev_cfg["action"] else ()
+            ops.prev_input_rows(m.prev_input.weight, prev.actions, sizes, prev.rewards, ep_step=prev.ep_step, out=g.h_part[splits])
+            return g.h_part, m.lin_hidden.bias
         if g.h_part is None:          # (the first call allocates the fixed-address result)
             g.h_part = partial_sums(x, *args)
         return partial_sums(x, *args, out=g.h_part), m.lin_hidden.bias
+
+    def _rollout_prev(self, g, ss_src):
+        """previous_step_input: the previous step of group ``g``'s workers in the rollout's form, or None without the key -- the
+        group's ``act_dev`` (the actions of step t - 1, which the sampling of step t has not yet overwritten), its entries of the pinned
+        block of last rewards, and row 0 of the (episode step, slot) block the step reads (0 = no previous step)."""
+        if self._prev_cfg is None:
+            return None
+        return PreviousStep(g.act_dev, g.rw_pin, ss_src[0])
 
     def _rollout_step_head(self, g, stream_obs=False, host_flag=False):
         """Everything the ACTIONS of group ``g`` depend on: (observation / step / slot upload,) window lookup, model forward,
@@ -1144,7 +1200,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             # worker walks the whole chain as matrix-vector products over the L2-resident weights (csrc/rollout_fused.hip);
             # the step is then encoder (4 launches) + window lookup + this kernel instead of 26 dependent launches
             # (the kernel does the window lookup and the cache reset of new episodes itself by now: one launch fewer in the chain)
-            h_in, h_bias = self._hidden_input(g, hidden, rf, obs, obs_index, rows)
+            h_in, h_bias = self._hidden_input(g, hidden, rf, obs, obs_index, rows, ss_src)
             # ... and, after the action hand-over, the memory-bank write and the K | V projection of the new items (the tail;
             # pre-LN: the kernel applies norm_kv)
             tail = (self._kv_w_blocked, m.transformer._pos(), g.step_l, g.slot_l, buf.bank) if g.tail_in_kernel else None
@@ -1163,11 +1219,13 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                            reset=(g.kv, self._kv_init) if self._use_kv_cache else None, w_off=g.lo,
                            latch=(ss_src, g.ss_latch))
         kv_spec = WindowSpec.from_bank(g.kv, None, win_t, None, mask_t) if self._use_kv_cache else None
+        # previous_step_input on the unfused roads: the encoder takes the previous step (nothing is passed without the key)
+        pk = {} if self._prev_cfg is None else {"prev": self._rollout_prev(g, ss_src)}
         if kv_spec is not None and m.rollout_heads_fusable():
             # hidden heads -> ONE launch for output heads, sampling, staging, t += 1; the kernel stores the actions straight
             # into the pinned host buffer (no copy launch): they are visible to the host when the step's event (or, with
             # host_flag_actions, the flag) says the launch is done
-            h2, item = m.forward_hidden_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, raw=True, obs_rows=rows)
+            h2, item = m.forward_hidden_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, raw=True, obs_rows=rows, **pk)
             if box is not None:
                 ops.rollout_policy_gaussian(h2, policy_head, m.value, box[0], draws, self._forced_tab, g.t_dev, g.act_dev,
                                             st["actions"], st["log_probs"], st["values"], low=box[1], high=box[2],
@@ -1179,10 +1237,10 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                                    action_mask=am_src, **logps)
         else:
             if kv_spec is not None:
-                logits, value, item = m.forward_logits_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, obs_rows=rows)
+                logits, value, item = m.forward_logits_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, obs_rows=rows, **pk)
             else:
                 spec = WindowSpec.from_bank(buf.bank, g.slot_dev, win_t, win_t, mask_t)
-                logits, value, item = m.forward_logits(obs, spec)
+                logits, value, item = m.forward_logits(obs, spec, **pk)
                 item = item.transpose(0, 1)
             if not g.full:
                 raise RuntimeError("worker groups need the fused policy path (K/V cache)")
@@ -1284,6 +1342,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             all_ids = torch.arange(self.num_workers, device=self.device)
             saved_bank = self.buffer.bank[ss[1], ss[0]].clone()
             saved_kv = self._kv_cache[all_ids, ss[0]].clone()
+            # (previous_step_input reads the last actions from act_dev, which the warm-up steps overwrite: kept likewise)
+            saved_act = self._act_dev.clone() if self._prev_cfg is not None else None
         for g in groups:
             g.t_dev.zero_()
             # warm-up and capture run on the stream the group's graphs are replayed on: the BLAS workspace of the library
@@ -1318,6 +1378,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             torch.cuda.synchronize(self.device)
             self.buffer.bank[ss[1], ss[0]] = saved_bank
             self._kv_cache[all_ids, ss[0]] = saved_kv
+            if saved_act is not None:
+                self._act_dev.copy_(saved_act)
         self.buffer.address_captured = True
         ops.freeze_workspaces(self.device)
         self._step_graph = groups[0].graphs
@@ -1342,7 +1404,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         with torch.no_grad():
             mask = self._mask_table[torch.clamp(self._step_dev, 0, L - 1)]
             spec = WindowSpec.from_bank(self.buffer.bank, self._slot_dev, lv.rows, self.buffer.memory_indices[:, -1], mask)
-            _, last_value, _ = self.model.forward_logits(lv.obs, spec, want_items=False)
+            # previous_step_input: every worker's last action and raw reward (act_dev, the pinned block), none where its episode just ended
+            pk = {} if self._prev_cfg is None else {"prev": PreviousStep(self._act_dev, self._rw_pin, self._step_dev)}
+            _, last_value, _ = self.model.forward_logits(lv.obs, spec, want_items=False, **pk)
             lv.out.copy_(last_value)
 
     def _bootstrap_pass(self):
@@ -1362,7 +1426,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         with torch.no_grad():
             values = torch.empty(w.numel(), dtype=torch.float32, device=self.device)
             for lo in range(0, w.numel(), W):
-                for dst, src in zip((bs.obs, bs.slot, bs.rows, bs.pidx, bs.s), operands):
+                for dst, src in zip((bs.obs, bs.slot, bs.rows, bs.pidx, bs.s) + ((bs.pa, bs.pr) if self._prev_cfg is not None else ()), operands):
                     dst.copy_(src[lo: lo + W])
                 bs()
                 values[lo: lo + W] = bs.out
@@ -1379,18 +1443,26 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             obs = obs.to(self.observation_dtype)
         w, t, slot, s = meta.unbind(1)
         rows = torch.clamp(s - L, min=0).unsqueeze(1) + torch.arange(L, dtype=torch.int64, device=dev).unsqueeze(0)
-        return n, w, t, (obs, slot, rows, self.buffer.memory_indices[w, t], s)
+        operands = (obs, slot, rows, self.buffer.memory_indices[w, t], s)
+        if self._prev_cfg is not None:      # previous_step_input: the action and the raw reward of the recorded (worker, step)
+            wt = meta[:, :2].cpu().numpy()
+            operands += (self.buffer.actions[w, t], torch.from_numpy(self.buffer.rewards[wt[:, 0], wt[:, 1]].astype(np.float32)).to(dev))
+        return n, w, t, operands
 
-    def _bootstrap_forward(self, obs, slot, rows, pidx, s):
+    def _bootstrap_forward(self, obs, slot, rows, pidx, s, prev=None):
         mask = self._mask_table[torch.clamp(s, 0, self.memory_length - 1)]
         spec = WindowSpec.from_bank(self.buffer.bank, slot, rows, pidx, mask)
-        return self.model.forward_logits(obs, spec, want_items=False)[1]
+        if prev is None:
+            return self.model.forward_logits(obs, spec, want_items=False)[1]
+        return self.model.forward_logits(obs, spec, want_items=False, prev=prev)[1]
 
     def _bootstrap_chunk_now(self):
         """One chunk of the bootstrap pass on its fixed-address operands ``_bs.obs / .slot / .rows / .pidx / .s`` -> ``.out``."""
         bs = self._bs
         with torch.no_grad():
-            bs.out.copy_(self._bootstrap_forward(bs.obs, bs.slot, bs.rows, bs.pidx, bs.s))
+            # (previous_step_input: the episode's length s >= 1 is the step word -- the final observation always has a previous step)
+            prev = None if self._prev_cfg is None else PreviousStep(bs.pa, bs.pr if self._prev_cfg["reward"] else None, bs.s)
+            bs.out.copy_(self._bootstrap_forward(bs.obs, bs.slot, bs.rows, bs.pidx, bs.s, prev))
 
     # ------------------------------------------------------------------ optimisation
     def _train_epochs(self, learning_rate: float, clip_range: float, beta: float, perms=None):
@@ -1546,14 +1618,16 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             kw["kl_coef"] = self._kl_coef
         rest = (mb["actions"], mb["log_probs"], mb["advantages"], mb["values"], clip_range, self.config["value_loss_coefficient"], beta, stats3)
         kw["dyn"] = getattr(self, "_dyn", None) if dyn == "device" else dyn
+        # previous_step_input: the minibatch's rows of the buffer's fields (a negative action = no previous step); {} without the key
+        pk = {} if self._prev_cfg is None else {"prev": PreviousStep(mb.get("prev_actions"), mb.get("prev_rewards"))}
         if self.box is not None:
             # Box: the fused Gaussian heads + loss kernel is the only path (check_box_policy made sure it takes the shape)
-            h, _ = m.forward_state(obs, spec)
+            h, _ = m.forward_state(obs, spec, **pk)
             if not ops.heads_loss_supported_gaussian(h, m.lin_policy, m.policy_branches[0]):
                 raise RuntimeError("Box policy: the minibatch is outside the fused Gaussian heads + loss kernel")
             return ops.heads_ppo_loss_gaussian(h, m.lin_policy, m.lin_value, m.policy_branches[0], m.policy_log_std, m.value, *rest, unit_grad=True, **kw)
         if self.config.get("fused_heads_loss", True):
-            h, _ = m.forward_state(obs, spec)
+            h, _ = m.forward_state(obs, spec, **pk)
             branch = m.policy_branches[0] if len(m.policy_branches) == 1 else list(m.policy_branches)
             if ops.heads_loss_supported(h, m.lin_policy, branch):      # (both callers run loss.backward() on this loss)
                 return ops.heads_ppo_loss(h, m.lin_policy, m.lin_value, branch, m.value, *rest, unit_grad=True, **kw)
@@ -1561,7 +1635,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             h_value = ops.linear_relu(m.lin_value, h)
             logits, value = [br(h_policy) for br in m.policy_branches], m.value(h_value).reshape(-1)
         else:
-            logits, value, _ = m.forward_logits(obs, spec, want_items=False)
+            logits, value, _ = m.forward_logits(obs, spec, want_items=False, **pk)
         return ops.ppo_loss(logits, value, *rest, **kw)
 
     def _dw_destinations(self):

@@ -511,6 +511,8 @@ class _CheckpointResume:
         buf.num_episodes = W
         if buf.ret_carry is not None:
             buf.ret_carry.zero_()
+        if buf.prev_actions is not None:      # previous_step_input: every worker starts an episode, nothing is carried over
+            buf.prev_live.zero_()
         self._truncations = []
         self.worker_current_episode_step[:] = 0
         self.worker_episode_slot[:] = range(W)

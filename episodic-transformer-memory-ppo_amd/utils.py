@@ -36,6 +36,10 @@ def create_env(config: dict, render: bool = False, worker_id: int = 0):
         # ``environment.report_truncation`` (optional): time-limit cuts carry "truncated": True in their info (bootstrap_truncated)
         return PocMemoryEnv(glob=False, freeze=True, max_episode_steps=32, seed=seed,
                             report_truncation=bool(config.get("report_truncation", False)))
+    if kind == "HiddenArm":
+        from environments.hidden_arm_env import HiddenArmEnv
+        seed = int(config["seed"]) + int(worker_id) if config.get("seed") is not None else None
+        return HiddenArmEnv(arms=int(config.get("arms", 2)), max_episode_steps=int(config.get("max_episode_steps", 16)), seed=seed)
     raise ImportError(f"environment type {kind!r} needs its simulator package (gym / gym-minigrid / memory-gym), which is "
                       "outside this build; use type 'Synthetic' with the same observation shape for throughput runs")
 
@@ -426,6 +430,179 @@ def kl_penalty_step(coef32, kl32, rule):
     if kl < np.float32(rule["kl_low"]):
         return np.maximum(np.float32(rule["min"]), np.float32(coef * np.float32(rule["down"]))), -1
     return coef, 0
+
+
+PREVIOUS_STEP_MAX_ROWS = 64          # rows of the table the kernels carry (csrc/prev_input.hip PI_MAXR; RF_MAXSPLIT of the step kernel)
+
+
+def previous_step_input_section(config: dict, action_space_shape=None, box=False, worker_processes=False):
+    """The optional key ``previous_step_input`` (``true``: both, or {action, reward} with at least one true) -> {"action", "reward"},
+    or None when the key is absent or ``false``.  Refused, each with what to do instead: a value that is neither a bool nor a dict of
+    the two bools, unknown sub-keys, both sub-keys false; a Box policy (``box``); ``worker_processes: true``; a table of more than 64
+    rows (``action_space_shape``, when given: sum A_b, + 1 with ``reward``)."""
+    value = config.get("previous_step_input")
+    if value is None:
+        return None
+    if isinstance(value, (bool, np.bool_)):
+        if not value:
+            return None
+        sec = dict(action=True, reward=True)
+    elif isinstance(value, dict):
+        known = ("action", "reward")
+        unknown = sorted(str(k) for k in set(value) - set(known))
+        if unknown:
+            raise ValueError(f"previous_step_input: unknown keys {unknown} (known: {list(known)}); remove them")
+        sec = {}
+        for k in known:
+            v = value.get(k, False)
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"previous_step_input.{k} must be true or false, got {v!r}")
+            sec[k] = bool(v)
+        if not sec["action"] and not sec["reward"]:
+            raise ValueError("previous_step_input: both `action` and `reward` are false, so nothing would be fed back; set at least one "
+                             "of them true, or remove the key")
+    else:
+        raise ValueError(f"previous_step_input must be true or {{action: bool, reward: bool}}, got {value!r}; write "
+                         "`previous_step_input: true` for both the previous action and the previous reward, or remove the key")
+    if box:
+        raise ValueError("previous_step_input does not carry a Box policy (the table has one row per discrete action): use a Discrete or "
+                         "MultiDiscrete action space, append the previous action to the observation in a wrapper, or remove the key")
+    if worker_processes:
+        raise ValueError("worker_processes: true does not carry previous_step_input (the shared segment has no row for the last reward): "
+                         "set worker_processes: false (in-process environments hand the reward over each step), or remove the key")
+    if action_space_shape is not None:
+        rows = previous_step_table_rows(action_space_shape, sec["reward"])
+        if rows > PREVIOUS_STEP_MAX_ROWS:
+            raise ValueError(f"previous_step_input: the table would have {rows} rows (sum of the action space {tuple(action_space_shape)}"
+                             f"{' + the reward row' if sec['reward'] else ''}), the kernels carry {PREVIOUS_STEP_MAX_ROWS}: use a smaller "
+                             "action space, or remove the key")
+    return sec
+
+
+def previous_step_table_rows(sizes, reward: bool) -> int:
+    """R of the table ``prev_input.weight`` [R, D]: branch b owns rows off_b .. off_b + A_b - 1 (the flat layout of the action masks),
+    the reward row, with ``reward`` only, is the last one."""
+    sizes = tuple(int(a) for a in sizes)
+    if not sizes or min(sizes) <= 0:
+        raise ValueError(f"previous_step_table_rows: positive branch sizes expected, got {sizes}")
+    return sum(sizes) + (1 if reward else 0)
+
+
+def _previous_step_operands(table, prev_actions, prev_rewards, sizes, dt):
+    T = np.asarray(table, dtype=dt)
+    sizes = tuple(int(a) for a in sizes)
+    reward = prev_rewards is not None
+    if T.ndim != 2 or (sizes and min(sizes) <= 0) or T.shape[0] < sum(sizes) + (1 if reward else 0) or not (sizes or reward):
+        raise ValueError(f"previous step rule: a table [R >= {sum(sizes) + (1 if reward else 0)}, D] for branches {sizes} expected, got {T.shape}")
+    if sizes:
+        a = np.asarray(prev_actions).astype(np.int64)
+        a = a.reshape(a.shape[0], -1)
+        if a.shape[1] != len(sizes):
+            raise ValueError(f"previous step rule: prev_actions [N, {len(sizes)}] expected, got {a.shape}")
+        if (a >= np.asarray(sizes, dtype=np.int64)[None, :]).any():
+            raise ValueError("previous step rule: an action outside its branch")
+        n = a.shape[0]
+    else:
+        a = None
+        n = np.asarray(prev_rewards).reshape(-1).shape[0]
+    r = None
+    if reward:
+        r = np.asarray(prev_rewards, dtype=dt).reshape(-1)
+        if r.shape != (n,):
+            raise ValueError(f"previous step rule: prev_rewards [{n}] expected, got {r.shape}")
+    return T, a, r, sizes, n
+
+
+def previous_step_rows(table, prev_actions, prev_rewards, sizes, bias=None, dtype=np.float64):
+    """The addend of ``previous_step_input`` in numpy ``dtype`` -- the one host definition of what etm_prev_input_rows writes
+    (csrc/prev_input.hip; bit for bit in float32).  ``table`` T [R, D]; ``prev_actions`` [N, B] int64, one column per entry of ``sizes``
+    (empty ``sizes``: the action rows are not fed back and ``prev_actions`` is not read), a NEGATIVE entry in column 0 = the sample has
+    no previous step; ``prev_rewards`` [N] (None: no reward term), the raw reward.
+        e_n = sum_b T[off_b + a_nb, :] + r_n T[R - 1, :]
+    started at +0, the branches in ascending b, the reward term last, every product and sum rounded on its own; a sample without a
+    previous step is exactly +0 in every column.  ``bias`` [D] (optional) is added last, to every row."""
+    dt = np.dtype(dtype).type
+    T, a, r, sizes, n = _previous_step_operands(table, prev_actions, prev_rewards, sizes, dt)
+    out = np.zeros((n, T.shape[1]), dtype=dt)
+    has = np.ones(n, dtype=bool) if a is None else a[:, 0] >= 0
+    off = 0
+    for b, size in enumerate(sizes):
+        idx = np.where(has, a[:, b], 0)
+        if (idx < 0).any():
+            raise ValueError("previous step rule: a negative action behind column 0 of a sample that has a previous step")
+        out = np.where(has[:, None], (out + T[off + idx]).astype(dt), out)
+        off += size
+    if r is not None:
+        out = np.where(has[:, None], (out + (r[:, None] * T[-1][None, :]).astype(dt)).astype(dt), out)
+    if bias is not None:
+        out = (out + np.asarray(bias, dtype=dt).reshape(1, -1)).astype(dt)
+    return out
+
+
+def previous_step_coefficients(prev_actions, prev_rewards, sizes, rows, dtype=np.float64):
+    """c [N, R] of the rule above as a matrix: e = c T.  c_nk = 1 at the rows of the sample's previous actions, r_n at the reward row
+    (the last), 0 elsewhere, and 0 everywhere for a sample without a previous step."""
+    dt = np.dtype(dtype).type
+    _, a, r, sizes, n = _previous_step_operands(np.zeros((rows, 1), dtype=dt), prev_actions, prev_rewards, sizes, dt)
+    c = np.zeros((n, rows), dtype=dt)
+    has = np.ones(n, dtype=bool) if a is None else a[:, 0] >= 0
+    off = 0
+    for b, size in enumerate(sizes):
+        c[np.nonzero(has)[0], off + a[has, b]] += dt(1)
+        off += size
+    if r is not None:
+        c[has, rows - 1] = r[has]
+    return c
+
+
+def previous_step_table_grad(gm, prev_actions, prev_rewards, sizes, rows, dtype=np.float64):
+    """d L / d T [R, D] in numpy ``dtype`` -- the host definition of what etm_prev_input_grad sums: dT[k, :] = sum_n c_nk gm[n, :] with
+    ``previous_step_coefficients``, ``gm`` [N, D] the gradient at lin_hidden's pre-activation.  The samples are added in ascending n;
+    a row that no sample touched is exactly 0."""
+    dt = np.dtype(dtype).type
+    g = np.asarray(gm, dtype=dt)
+    _, a, r, sizes, n = _previous_step_operands(np.zeros((rows, 1), dtype=dt), prev_actions, prev_rewards, sizes, dt)
+    if g.ndim != 2 or g.shape[0] != n:
+        raise ValueError(f"previous_step_table_grad: gm [{n}, D] expected, got {g.shape}")
+    out = np.zeros((rows, g.shape[1]), dtype=dt)
+    for i in range(n):
+        if a is not None and a[i, 0] < 0:
+            continue
+        off = 0
+        for b, size in enumerate(sizes):
+            out[off + a[i, b]] = out[off + a[i, b]] + g[i]
+            off += size
+        if r is not None:
+            out[rows - 1] = out[rows - 1] + (r[i] * g[i]).astype(dt)
+    return out
+
+
+def previous_step_fields(actions, rewards, dones, carry_actions=None, carry_rewards=None, carry_live=None):
+    """The buffer fields of ``previous_step_input`` for one rollout -- the host definition of what the trainer builds on the device.
+    ``actions`` [W, S, B] int, ``rewards`` [W, S] (raw, as the environment returned them), ``dones`` [W, S] bool (step t ended its
+    episode); the carry of the rollout before: ``carry_actions`` [W, B], ``carry_rewards`` [W], ``carry_live`` [W] bool (False or
+    None: the worker starts an episode at step 0 -- the first rollout, a resume, or a done at the last step before).
+    -> (prev_actions [W, S, B] int64, prev_rewards [W, S] float32, (carry_actions, carry_rewards, carry_live) for the next rollout).
+    At an episode's first step prev_actions is -1 in every branch and prev_rewards is 0; elsewhere they are step t - 1's."""
+    a = np.asarray(actions).astype(np.int64)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    r = np.asarray(rewards, dtype=np.float32)
+    d = np.asarray(dones).astype(bool)
+    W, S, B = a.shape
+    if r.shape != (W, S) or d.shape != (W, S):
+        raise ValueError(f"previous_step_fields: rewards and dones [{W}, {S}] expected, got {r.shape}, {d.shape}")
+    live = np.zeros(W, dtype=bool) if carry_live is None else np.asarray(carry_live).astype(bool).reshape(W)
+    ca = np.full((W, B), -1, dtype=np.int64) if carry_actions is None else np.asarray(carry_actions).astype(np.int64).reshape(W, B)
+    cr = np.zeros(W, dtype=np.float32) if carry_rewards is None else np.asarray(carry_rewards, dtype=np.float32).reshape(W)
+    pa = np.empty((W, S, B), dtype=np.int64)
+    pr = np.empty((W, S), dtype=np.float32)
+    pa[:, 0] = np.where(live[:, None], ca, -1)
+    pr[:, 0] = np.where(live, cr, np.float32(0))
+    first = d[:, :-1]                                  # step t + 1 starts an episode where step t ended one
+    pa[:, 1:] = np.where(first[:, :, None], -1, a[:, :-1])
+    pr[:, 1:] = np.where(first, np.float32(0), r[:, :-1])
+    return pa, pr, (a[:, -1].copy(), r[:, -1].copy(), ~d[:, -1])
 
 
 class Module(nn.Module):

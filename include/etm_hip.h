@@ -900,6 +900,43 @@ int etm_relu_bwd_colsum_partial_rows(int N);
 int etm_relu_bwd_colsum(const float *g, const float *y, float *gm, float *db, float *workspace, int64_t workspace_bytes, int N, int C,
                         void *stream);
 
+/* previous_step_input (csrc/prev_input.hip; added without a change to any signature above, the ABI version stays): the previous
+ * step's action(s) and raw reward as an addend of lin_hidden's pre-activation, from a learned table T [R, D] -- branch b owns rows
+ * off_b .. off_b + sizes[b] - 1, the reward row (rewards non-NULL) is row R - 1; sum(sizes) + (rewards ? 1 : 0) <= R <= 64.
+ * utils.previous_step_rows / previous_step_table_grad are the host definitions.
+ *   etm_prev_input_supported: 1 for 1 <= R <= 64 and 1 <= D <= 65536, else 0.
+ *   etm_prev_input_rows: out[n, :] (row stride out_stride >= D floats) = sum_b T[off_b + actions[n, b], :] + rewards[n] T[R - 1, :]
+ *       (+ bias [D] when not NULL), started at +0, branches in ascending b, the reward term last, every product and sum rounded on
+ *       its own; +0 (+ bias) for a sample without a previous step.  actions [N, n_branches] int64 with row stride act_stride (in
+ *       elements; NULL with n_branches == 0: no action rows are fed back, rewards is then required).  Which samples have a previous
+ *       step: ep_step non-NULL (rollout form; [N] int64, device or pinned host memory, read in place -- row 0 of the step kernels'
+ *       (episode step, slot) block): those whose word is not 0; ep_step NULL (training form): those with actions[n, 0] >= 0 (all,
+ *       with n_branches == 0).  One launch; bit for bit the host rule in float32.
+ *   etm_prev_input_grad: d_table [R, D] = sum_n c_n^T gm[n, :] (gm row stride gm_stride >= D), c_n the coefficients of sample n in
+ *       the rule above (training form).  No float atomics: workgroups own chunks of etm_prev_input_grad_chunk() samples, added in
+ *       ascending order, and the chunks' partial tables are added in chunk order by a second launch (none for a single chunk).
+ *       Rows no sample touched are exactly 0; two calls give the same bits.  workspace: etm_prev_input_grad_workspace_bytes(N, R, D)
+ *       bytes, always required.  d_table NULL: the second launch is left out -- `workspace` then holds
+ *       etm_prev_input_grad_partial_rows(N) rows of R D partial sums for etm_colsum_reduce_grouped.
+ * Valid input only: an action outside its branch (>= sizes[b], or negative in a sample that has a previous step -- in the training
+ * form only column 0 decides that) is the caller's error; it is clamped into the branch's rows so that nothing outside the table is
+ * read or written, where the host rule raises.  The bit-for-bit statement holds on what the host rule accepts.
+ * Profiling (etm_profile_*): the rows kernel is booked under the gather_rows slot, the gradient kernel and its reduction under the
+ * colsum slot -- the slot table lives in a source file this addition leaves untouched; with the key on, those two rows of the
+ * per-kernel profile include these launches.
+ * ETM_EINVAL, with nothing launched: a NULL or misaligned pointer, a stride below n_branches / D, R outside 1 .. 64, sizes that do not
+ * fit R, N <= 0; ETM_EWORKSPACE: a workspace below the stated size. */
+int etm_prev_input_supported(int R, int D);
+int etm_prev_input_rows(const float *table, int R, int D, const int64_t *actions, int64_t act_stride, const int32_t *sizes, int n_branches,
+                        const float *rewards, const int64_t *ep_step, const float *bias, float *out, int64_t out_stride, int64_t N,
+                        void *stream);
+int etm_prev_input_grad_chunk(void);
+int etm_prev_input_grad_partial_rows(int64_t N);
+int64_t etm_prev_input_grad_workspace_bytes(int64_t N, int R, int D);
+int etm_prev_input_grad(const float *gm, int64_t gm_stride, const int64_t *actions, int64_t act_stride, const int32_t *sizes, int n_branches,
+                        const float *rewards, float *d_table, int R, int D, int64_t N, float *workspace, int64_t workspace_bytes,
+                        void *stream);
+
 /* Monitored gradient norms of the module groups (model.py:128-151) from the flat gradient arena in two launches:
  * out[g] = sqrt(sum_s member[g][s] * ||flat[seg_start[s] .. seg_start[s] + seg_len[s])||^2).  Segments: runs of <= 4096 floats, each
  * inside one parameter tensor (device arrays seg_start int64 [n_segs], seg_len int32 [n_segs]); member [n_groups, n_segs] float
