@@ -234,6 +234,12 @@ SIGNATURES["etm_prev_input_grad_chunk"] = (_I, [])
 SIGNATURES["etm_prev_input_grad_partial_rows"] = (_I, [_L])
 SIGNATURES["etm_prev_input_grad_workspace_bytes"] = (_L, [_L, _I, _I])
 SIGNATURES["etm_prev_input_grad"] = (_I, [_P, _L, _P, _L, _P, _I, _P, _P, _I, _I, _L, _P, _L, _P])
+# obs_reconstruction (csrc/obs_recon.hip; the ABI stays at 61): the decoder's last layer fused with the sigmoid cross-entropy and its
+# gradient, and that layer's data gradient (its weight gradient is etm_conv_train_wgrad with the roles exchanged)
+SIGNATURES["etm_obs_recon_supported"] = (_I, [_I, _I, _I])
+SIGNATURES["etm_obs_recon_workspace_bytes"] = (_L, [_L, _I, _I, _I])
+SIGNATURES["etm_obs_recon_fwd_loss"] = (_I, [_P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P])
+SIGNATURES["etm_obs_recon_dgrad"] = (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P])
 del _twin
 del _name, _extra, _res, _args
 

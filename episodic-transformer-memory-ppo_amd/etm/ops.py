@@ -2620,3 +2620,196 @@ def ppo_loss(logits_list, value, actions, old_logp, adv, old_value, clip, vf_coe
         total = total + l_b
         pol, ent, kl, cf = pol + s_b[0], ent + s_b[3], kl + s_b[4], cf + s_b[5]
     return total, torch.stack([pol, st[1], total.detach(), ent, kl, cf])
+
+
+# ---------------------------------------------------------------------------------------------------------------- obs_reconstruction
+class _BiasReluRowsFn(torch.autograd.Function):
+    """relu(x + b) over the rows of x [n, c] (an NHWC activation seen as pixels x channels): the forward is two library element-wise
+    ops, the backward is etm_relu_bwd_colsum -- the ReLU mask and the bias gradient in one pass with a fixed-order column sum, its
+    second stage in the collector's one reduction launch when one is active (the library's own column sum is the reduction
+    ``_linear_backward`` speaks of)."""
+
+    @staticmethod
+    def forward(ctx, x, bias):
+        y = torch.relu_(x + bias)
+        ctx.save_for_backward(y)
+        ctx.bias_ptr = bias.data_ptr()
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (y,) = ctx.saved_tensors
+        lib = _lib.load()
+        g = _f32c(g, "grad")
+        n, c = g.shape
+        gm = torch.empty_like(g)
+        nbytes = lib.etm_relu_bwd_colsum_workspace_bytes(n, c)
+        ws, deferred = DeferredDw.colsum_workspace(nbytes, lib.etm_relu_bwd_colsum_partial_rows(n), c, [(0, c, ctx.bias_ptr)], g.device, "relu_bwd")
+        db = None if deferred else torch.empty(c, dtype=torch.float32, device=g.device)
+        _lib.check(lib.etm_relu_bwd_colsum(_ptr(g), _ptr(y), _ptr(gm), _ptr(db), _ptr(ws), nbytes, n, c, _stream()), "etm_relu_bwd_colsum")
+        return gm, db
+
+
+def conv_transpose_wgrad(g, x, K, S):
+    """dW [Cin, Cout, K, K] of y = ConvTranspose2d(Cin, Cout, K, S)(x) from g = dL/dy NHWC [N, Ho, Wo, Cout] and x NHWC [N, Hi, Wi, Cin]:
+    dW[ci][co][ky][kx] = sum x[n, iy, ix, ci] g[n, S iy + ky, S ix + kx, co] is the weight gradient of the convolution (Cout -> Cin, K, S)
+    with the roles exchanged, etm_conv_train_wgrad(x := g, dy := x) -- in the transposed layer's own parameter layout, summed in a fixed
+    order (the library's weight gradient of these layers adds with atomics: its bits change from call to call).  That entry's trailing
+    "bias gradient", the column sums of x, is discarded."""
+    lib = _lib.load()
+    _need_dev(g, x)
+    g, x = _f32c(g, "grad"), _f32c(x, "x")
+    N, Ho, Wo, C = g.shape
+    cin = x.shape[3]
+    if tuple(x.shape[:3]) != (N, (Ho - K) // S + 1, (Wo - K) // S + 1):
+        raise ValueError(f"conv_transpose_wgrad: the gradient {tuple(g.shape)} and the input {tuple(x.shape)} do not belong to one layer")
+    args = (N, C, Ho, Wo, cin, K, K, S)
+    nbytes = lib.etm_conv_train_wgrad_workspace_bytes(*args)
+    ws = workspace(nbytes, g.device, "conv_wgrad")
+    buf = torch.empty(K * K * C * cin + cin, dtype=torch.float32, device=g.device)
+    _lib.check(lib.etm_conv_train_wgrad(_ptr(g), None, _ptr(x), _ptr(buf), _ptr(ws), nbytes, *args, _stream()), "etm_conv_train_wgrad")
+    return buf[: K * K * C * cin].view(cin, C, K, K)
+
+
+class _ConvTransposeFn(torch.autograd.Function):
+    """y = conv_transpose2d(x, w, stride) without bias on channels_last activations: the library's transposed convolution forward, the
+    library's convolution for dx, and ``conv_transpose_wgrad`` for dW (fixed summation order: two runs give the same bits)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride):
+        ctx.save_for_backward(x, weight)
+        ctx.stride = int(stride)
+        return torch.nn.functional.conv_transpose2d(x, weight, None, stride)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        g = g.contiguous(memory_format=torch.channels_last)
+        dx = torch.nn.functional.conv2d(g, weight, None, ctx.stride) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw = conv_transpose_wgrad(g.permute(0, 2, 3, 1), x.permute(0, 2, 3, 1), weight.shape[2], ctx.stride)
+        return dx, dw, None
+
+
+def conv_transpose_relu(deconv, x):
+    """relu(deconv(x)) for an nn.ConvTranspose2d on an NCHW-shaped tensor in channels_last memory (the decoder's two middle layers):
+    the library's transposed convolution without its bias (``_ConvTransposeFn``), then bias + ReLU over the pixels' rows
+    (``_BiasReluRowsFn``).  A CPU tensor, or no grad: the same expression in torch."""
+    if not (x.is_cuda and torch.is_grad_enabled() and x.dtype == torch.float32):
+        return torch.relu(deconv(x))
+    y = _ConvTransposeFn.apply(x.contiguous(memory_format=torch.channels_last), deconv.weight, deconv.stride[0])
+    n, c, h, w = y.shape
+    rows = y.permute(0, 2, 3, 1).contiguous().view(n * h * w, c)
+    return _BiasReluRowsFn.apply(rows, deconv.bias).view(n, h, w, c).permute(0, 3, 1, 2)
+
+
+def obs_recon_supported(C, Hi, Wi):
+    return bool(_lib.load().etm_obs_recon_supported(int(C), int(Hi), int(Wi)))
+
+
+def _obs_recon_operands(a2, w, b, obs, index, coef_word, what):
+    """Checked operands of etm_obs_recon_fwd_loss: (a2, w, b, x, N, C, Hi, Wi)."""
+    _need_dev(a2, w, b, obs, index, coef_word)
+    a2, w, b, x = _f32c(a2, "a2"), _f32c(w, "weight"), _f32c(b, "bias"), _obs_c(obs, "obs")
+    if a2.dim() != 4 or w.dim() != 4 or tuple(w.shape[2:]) != (8, 8) or w.shape[0] != a2.shape[3] or a2.shape[3] != 32 or tuple(b.shape) != (w.shape[1],):
+        raise ValueError(f"{what}: a2 NHWC [N, Hi, Wi, 32], weight [32, C, 8, 8] and bias [C] expected, got {tuple(a2.shape)}, "
+                         f"{tuple(w.shape)}, {tuple(b.shape)}")
+    N, Hi, Wi, _ = a2.shape
+    C = w.shape[1]
+    if N < 1 or not obs_recon_supported(C, Hi, Wi):
+        raise ValueError(f"{what}: outside the kernel's support (1 <= C <= 4, 1 <= Hi, Wi <= 4096, N >= 1): N {N}, C {C}, Hi {Hi}, Wi {Wi}")
+    if x.dim() != 4 or tuple(x.shape[1:]) != (4 * Hi + 4, 4 * Wi + 4, C):
+        raise ValueError(f"{what}: the observation must be NHWC [n, {4 * Hi + 4}, {4 * Wi + 4}, {C}] (the decoder's output size), got {tuple(x.shape)}")
+    if index is not None and (index.dtype != torch.int64 or index.dim() != 1 or index.numel() != N or not index.is_contiguous()):
+        raise ValueError(f"{what}: the index must be a contiguous int64 vector of {N} entries")
+    if index is None and x.shape[0] != N:
+        raise ValueError(f"{what}: {x.shape[0]} observations for {N} samples (pass an IndexedObservations to gather)")
+    if coef_word.dtype != torch.float32 or coef_word.numel() != 1:
+        raise ValueError(f"{what}: the coefficient must be a device tensor of one float32, got {tuple(coef_word.shape)} {coef_word.dtype}")
+    return a2, w, b, x, N, C, Hi, Wi
+
+
+def obs_recon_fwd_loss(a2, w, b, obs, coef_word, index=None):
+    """etm_obs_recon_fwd_loss on checked operands -> (dz [N, Ho, Wo, C], out [4] = (loss, coef, coef * loss, 0), db [C])."""
+    lib = _lib.load()
+    a2, w, b, x, N, C, Hi, Wi = _obs_recon_operands(a2, w, b, obs, index, coef_word, "obs_recon_fwd_loss")
+    dev = a2.device
+    dz = torch.empty((N, 4 * Hi + 4, 4 * Wi + 4, C), dtype=torch.float32, device=dev)
+    out, db = torch.empty(4, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
+    nbytes = lib.etm_obs_recon_workspace_bytes(N, C, Hi, Wi)
+    ws = workspace(nbytes, dev, "obs_recon")
+    _lib.check(lib.etm_obs_recon_fwd_loss(_ptr(a2), _ptr(w), _ptr(b), _ptr(x), int(x.dtype == torch.uint8), _ptr(index), x.shape[0], _ptr(coef_word),
+                                          _ptr(dz), _ptr(out), _ptr(db), _ptr(ws), nbytes, N, C, Hi, Wi, _stream()), "etm_obs_recon_fwd_loss")
+    return dz, out, db
+
+
+def obs_recon_dgrad(dz, w, a2):
+    """etm_obs_recon_dgrad: da2 [N, Hi, Wi, 32] = (a2 > 0) * (the 8 x 8 / 4 convolution of dz with w read as [32, C, 8, 8])."""
+    lib = _lib.load()
+    _need_dev(dz, w, a2)
+    dz, w, a2 = _f32c(dz, "dz"), _f32c(w, "weight"), _f32c(a2, "a2")
+    N, Hi, Wi, _ = a2.shape
+    C = w.shape[1]
+    if tuple(dz.shape) != (N, 4 * Hi + 4, 4 * Wi + 4, C) or a2.shape[3] != 32 or tuple(w.shape) != (32, C, 8, 8):
+        raise ValueError(f"obs_recon_dgrad: dz {tuple(dz.shape)}, weight {tuple(w.shape)}, a2 {tuple(a2.shape)} do not belong together")
+    da2 = torch.empty_like(a2)
+    _lib.check(lib.etm_obs_recon_dgrad(_ptr(dz), _ptr(w), _ptr(a2), _ptr(da2), N, C, Hi, Wi, _stream()), "etm_obs_recon_dgrad")
+    return da2
+
+
+def obs_recon_wgrad(dz, a2):
+    """dW [32, C, 8, 8] of the decoder's last layer = the first encoder layer's weight gradient with the roles exchanged:
+    etm_conv_train_wgrad(x := dz, dy := a2) (include/etm_hip.h states the identity).  That entry's trailing "bias gradient" -- the
+    column sums of a2 -- is discarded."""
+    return conv_transpose_wgrad(dz, a2, 8, 4)
+
+
+class _ObsReconFn(torch.autograd.Function):
+    """The decoder's last layer + sigmoid cross-entropy as one node over etm_obs_recon_fwd_loss (forward: the loss AND the gradient
+    image dz = coef * dloss / dlogits), etm_obs_recon_dgrad and the reused etm_conv_train_wgrad (backward).  Returns (coef * loss, out
+    [4]).  ``unit``: the caller runs backward() on a sum this term enters with weight 1, nothing is scaled."""
+
+    @staticmethod
+    def forward(ctx, a2, w, b, obs, index, coef_word, unit):
+        dz, out, db = obs_recon_fwd_loss(a2.detach(), w.detach(), b.detach(), obs, coef_word, index)
+        ctx.save_for_backward(a2.detach(), w.detach(), dz, db)
+        ctx.unit = bool(unit)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(out)
+        return out[2].clone(), out
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_out):
+        if g_loss is None:
+            return (None,) * 7
+        a2, w, dz, db = ctx.saved_tensors
+        if not ctx.unit:
+            dz, db = dz * g_loss, db * g_loss
+        da2 = obs_recon_dgrad(dz, w, a2) if ctx.needs_input_grad[0] else None
+        dw = obs_recon_wgrad(dz, a2) if ctx.needs_input_grad[1] else None
+        return da2, dw, (db if ctx.needs_input_grad[2] else None), None, None, None, None
+
+
+def obs_reconstruction_loss(a2, dec_conv1, obs, coef_word, unit_grad=False, with_out=False):
+    """``coef * loss`` of the observation reconstruction: the decoder's last layer ``dec_conv1`` (an nn.ConvTranspose2d(32, C, 8, 4)) on
+    ``a2`` NHWC [N, Hi, Wi, 32], the sigmoid cross-entropy of its logits against ``obs`` -- an NHWC tensor [N, Ho, Wo, C], float32 in
+    [0, 1] or uint8 (byte k = float32(k) / 255), or an ``IndexedObservations``-like object (``.bank`` NHWC, ``.index`` int64 [N]) whose
+    rows the kernel gathers -- times the one float32 of ``coef_word``, read in place (utils.obs_reconstruction_loss is the rule).
+    ``unit_grad=True``: the caller runs ``backward()`` on a loss this term enters with weight 1 (the contract of the loss entries).
+    ``with_out``: also the node's ``out`` [4] = (loss, coef, coef * loss, 0).  On CPU tensors the same expression in torch."""
+    bank, index = (obs.bank, obs.index) if hasattr(obs, "bank") else (obs, None)
+    w, b = dec_conv1.weight, dec_conv1.bias
+    if a2.is_cuda:
+        scaled, out = _ObsReconFn.apply(a2, w, b, bank, index, coef_word, bool(unit_grad))
+        return (scaled, out) if with_out else scaled
+    t = bank if index is None else bank.index_select(0, index)
+    t = t.to(torch.float32) / 255 if t.dtype == torch.uint8 else t
+    z = torch.nn.functional.conv_transpose2d(a2.permute(0, 3, 1, 2), w, b, stride=4).permute(0, 2, 3, 1)
+    t = t.to(z.dtype)
+    loss = (z.clamp_min(0) - z * t + torch.log1p(torch.exp(-z.abs()))).mean()
+    coef = coef_word.reshape(()).to(z.dtype)
+    scaled = coef * loss
+    if with_out:
+        return scaled, torch.stack([loss.detach(), coef, scaled.detach(), torch.zeros_like(coef)])
+    return scaled

@@ -15,7 +15,7 @@ from etm import ops
 from etm import lib as etm_lib
 from etm.ops import WindowSpec
 from transformer import Transformer
-from utils import normalization_section, previous_step_input_section, previous_step_table_rows
+from utils import normalization_section, obs_reconstruction_section, previous_step_input_section, previous_step_table_rows
 
 
 class PreviousStep:
@@ -144,6 +144,33 @@ class ActorCriticModel(nn.Module):
         if self.prev_cfg is not None:
             self.prev_input = nn.Embedding(previous_step_table_rows(self.action_space_shape, self.prev_cfg["reward"]), self.memory_layer_size)
             nn.init.zeros_(self.prev_input.weight)
+        # obs_reconstruction (absent upstream's model.py; the auxiliary loss of its author's Memory Gym runs): a decoder that mirrors the
+        # encoder reads h [N, D], the transformer's output, and has to reproduce the current frame (``reconstruct`` + the fused last
+        # layer and loss, ops.obs_reconstruction_loss).  Optimisation phase only.  Registered last, behind prev_input, so every other
+        # parameter keeps its place in the arena; the four modules exist only with the key.
+        self.recon_cfg = obs_reconstruction_section(config, self.observation_space_shape)
+        if self.recon_cfg is not None:
+            hh, ww = self.observation_space_shape[-2:]
+            self._dec_hw3 = (((hh - 8) // 4 + 1 - 4) // 2 + 1 - 2, ((ww - 8) // 4 + 1 - 4) // 2 + 1 - 2)      # the encoder's last feature map
+            self.dec_hidden = nn.Linear(self.memory_layer_size, self.conv_out_size)
+            self.dec_conv3 = nn.ConvTranspose2d(64, 64, 3, 1)
+            self.dec_conv2 = nn.ConvTranspose2d(64, 32, 4, 2)
+            self.dec_conv1 = nn.ConvTranspose2d(32, self.observation_space_shape[0], 8, 4)
+            for mod in (self.dec_hidden, self.dec_conv3, self.dec_conv2, self.dec_conv1):      # (as the encoder is initialised)
+                nn.init.orthogonal_(mod.weight, math.sqrt(2))
+
+    def reconstruct(self, h):
+        """``obs_reconstruction``: the decoder up to its last layer's input, h [N, D] (what ``forward_state`` returns) -> a2 NHWC
+        [N, h1, w1, 32] (h1, w1: the first encoder layer's output size): dec_hidden + ReLU through the linear node, viewed as the
+        encoder's last feature map (NHWC), then the two middle transposed layers on channels_last activations (library convolutions;
+        bias + ReLU and their backward by ``ops.conv_transpose_relu``)."""
+        if self.recon_cfg is None:
+            raise ValueError("reconstruct: this model was built without obs_reconstruction")
+        h3, w3 = self._dec_hw3
+        x = ops.linear_relu(self.dec_hidden, h).view(h.shape[0], h3, w3, 64).permute(0, 3, 1, 2)
+        x = ops.conv_transpose_relu(self.dec_conv3, x)
+        x = ops.conv_transpose_relu(self.dec_conv2, x)
+        return x.permute(0, 2, 3, 1).contiguous()
 
     def arena_parameters(self):
         """(name, parameter) pairs in the order of the optimiser's flat arena: ``named_parameters()``, except that a Box policy's
@@ -636,6 +663,8 @@ class ActorCriticModel(nn.Module):
             groups["policy_head_" + str(i)] = [head]
         groups["lin_policy"] = [self.lin_policy]
         groups["value"] = [self.lin_value, self.value]
+        if self.recon_cfg is not None:
+            groups["decoder"] = [self.dec_hidden, self.dec_conv3, self.dec_conv2, self.dec_conv1]
         groups["model"] = [self, self.value]
         return groups
 

@@ -50,7 +50,8 @@ from etm import ops
 from etm.ops import WindowSpec
 from etm.optim import AdaptiveLr, FlatAdamW, KlGate
 from model import ActorCriticModel, IndexedObservations, PreviousStep
-from utils import (adaptive_lr_section, exact_kl_section, kl_estimator_section, kl_penalty_section, kl_penalty_step, normalization_section, polynomial_decay, process_episode_info, target_kl_rows,
+from utils import (adaptive_lr_section, exact_kl_section, kl_estimator_section, kl_penalty_section, kl_penalty_step, normalization_section,
+                   obs_reconstruction_coef, obs_reconstruction_section, polynomial_decay, process_episode_info, target_kl_rows,
                    target_kl_section, previous_step_input_section)
 from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
 from checkpoint import check_checkpoint_config, segment_first_worker_id
@@ -373,6 +374,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         check_kl_estimator_config(config, env is not None or check_box_policy(config) is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_exact_kl_config(config, check_box_policy(config) is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
         pen_cfg = check_kl_penalty_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
+        obs_reconstruction_section(config, world=1 if dp is None else int(getattr(dp, "world", 1)))      # (the value; the observation's shape below)
         # training state that a checkpoint carries over (trainer_parts._CheckpointResume): completed updates, the training segment (the
         # number of resumes so far; its environments' worker ids start at segment_first_worker_id), the last episodes' infos
         self.update_index, self.segment, self._episode_infos = 0, 0, deque(maxlen=100)
@@ -484,6 +486,18 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             self._kl_coef = torch.full((1,), pen_cfg["coef"], dtype=torch.float32, device=device)
         self._kl_analytic = self._kl_analytic or (exact and self.box is not None)
         self._kl_exact_cat = exact and self.box is None
+        # obs_reconstruction: the schedule of the auxiliary loss's coefficient, or None.  The coefficient lives in ONE device float32 at a
+        # fixed address that the fused last layer + loss kernel reads in place, in eager steps and captured graphs alike; the host writes
+        # it once per update, outside every graph (_train_epochs).  Every step files its (unscaled) reconstruction loss in a device table
+        # of its own under a device counter; the eight statistics columns are untouched.  ``last_obs_reconstruction``: {"loss", "coef"} of
+        # the last update (None without the key: nothing is allocated)
+        self._recon = obs_reconstruction_section(config, obs_shape, 1 if dp is None else int(getattr(dp, "world", 1)))
+        self._recon_coef = self._recon_tab = self._recon_row = self.last_obs_reconstruction = None
+        if self._recon is not None:
+            self._recon_coef_host = obs_reconstruction_coef(self._recon, 0)
+            self._recon_coef = torch.full((1,), self._recon_coef_host, dtype=torch.float32, device=device)
+            self._recon_tab = torch.zeros(max(1, int(config["epochs"]) * int(config["n_mini_batch"])), dtype=torch.float32, device=device)
+            self._recon_row = torch.zeros(1, dtype=torch.long, device=device)
 
         if config.get("tunable_gemm", os.environ.get("ETM_TUNABLE_GEMM", "1") != "0"):
             # let PyTorch pick the fastest hipBLASLt / rocBLAS solution per GEMM shape (the small [N, D] x [D, D] products around
@@ -1493,6 +1507,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if tables:
             self._step_tables(mbs)
             self._tg_counter.zero_()
+        if self._recon is not None:
+            self._begin_reconstruction()
         gate, launched = self._kl_gate, 0
         if gate is not None:
             gate.reset()
@@ -1554,6 +1570,10 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         train_info = (self._tg_stats_tab[:rows] if tables else torch.stack(stats[:rows])).cpu().numpy()
         if self._kl_pen is not None:
             self._adapt_kl_penalty(train_info)
+        if self._recon is not None:
+            # (behind the phase's read-back: the table is complete, the copy waits for nothing) the float32 of the float64 mean
+            losses = self._recon_tab[:min(rows, self._recon_tab.numel())].cpu().numpy()
+            self.last_obs_reconstruction = {"loss": float(np.float32(losses.astype(np.float64).mean())), "coef": float(self._recon_coef_host)}
         self._bank_pos = self._row_stats = None
         self._mb_stats3 = self._epoch_stats3 = None
         grad_info = {}
@@ -1574,6 +1594,29 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             if np.float32(nxt) != coef:
                 self._kl_coef.fill_(float(nxt))
         self.last_kl_penalty = {"coef": float(coef), "next_coef": float(np.float32(nxt)), "kl": float(kl), "moved": int(moved)}
+
+    def _begin_reconstruction(self):
+        """obs_reconstruction, once per update and outside every graph: the update's coefficient into the device word (written only
+        when it moved) and the steps' loss table back to row 0."""
+        coef = obs_reconstruction_coef(self._recon, self.update_index)
+        if coef != self._recon_coef_host:
+            self._recon_coef.fill_(coef)
+            self._recon_coef_host = coef
+        self._recon_row.zero_()
+
+    def _add_reconstruction(self, loss, h, obs):
+        """``loss`` + coef * (the reconstruction loss of the minibatch), one loss for ``_backward_into_arena``: the decoder on ``h``
+        [N, D] up to its last layer's input, then the fused last layer + sigmoid cross-entropy against ``obs`` (the minibatch's
+        observations: an ``IndexedObservations`` over the NHWC copy, or the gathered NCHW rows of the eager step).  The step's unscaled
+        loss goes into row ``_recon_row`` of the table of its own and the counter moves on (round the table: a step asked for from
+        outside an update never leaves it)."""
+        target = obs if isinstance(obs, IndexedObservations) else obs.permute(0, 2, 3, 1)
+        term, out = ops.obs_reconstruction_loss(self.model.reconstruct(h), self.model.dec_conv1, target, self._recon_coef, unit_grad=True,
+                                                with_out=True)
+        with torch.no_grad():
+            self._recon_tab.index_copy_(0, self._recon_row, out[0:1])
+            self._recon_row.add_(1).remainder_(self._recon_tab.numel())
+        return loss + term
 
     def _train_mini_batch(self, samples: dict, learning_rate: float, clip_range: float, beta: float):
         """One optimiser step on one minibatch.  Returns a device tensor [policy, value, loss, entropy, kl, clip_frac]."""
@@ -1625,18 +1668,22 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             h, _ = m.forward_state(obs, spec, **pk)
             if not ops.heads_loss_supported_gaussian(h, m.lin_policy, m.policy_branches[0]):
                 raise RuntimeError("Box policy: the minibatch is outside the fused Gaussian heads + loss kernel")
-            return ops.heads_ppo_loss_gaussian(h, m.lin_policy, m.lin_value, m.policy_branches[0], m.policy_log_std, m.value, *rest, unit_grad=True, **kw)
-        if self.config.get("fused_heads_loss", True):
+            loss, stats = ops.heads_ppo_loss_gaussian(h, m.lin_policy, m.lin_value, m.policy_branches[0], m.policy_log_std, m.value, *rest, unit_grad=True, **kw)
+            return (loss, stats) if self._recon is None else (self._add_reconstruction(loss, h, obs), stats)
+        if self.config.get("fused_heads_loss", True) or self._recon is not None:      # (obs_reconstruction reads h on every route)
             h, _ = m.forward_state(obs, spec, **pk)
             branch = m.policy_branches[0] if len(m.policy_branches) == 1 else list(m.policy_branches)
-            if ops.heads_loss_supported(h, m.lin_policy, branch):      # (both callers run loss.backward() on this loss)
-                return ops.heads_ppo_loss(h, m.lin_policy, m.lin_value, branch, m.value, *rest, unit_grad=True, **kw)
+            if self.config.get("fused_heads_loss", True) and ops.heads_loss_supported(h, m.lin_policy, branch):      # (both callers run loss.backward() on this loss)
+                loss, stats = ops.heads_ppo_loss(h, m.lin_policy, m.lin_value, branch, m.value, *rest, unit_grad=True, **kw)
+                return (loss, stats) if self._recon is None else (self._add_reconstruction(loss, h, obs), stats)
             h_policy = ops.linear_relu(m.lin_policy, h)
             h_value = ops.linear_relu(m.lin_value, h)
             logits, value = [br(h_policy) for br in m.policy_branches], m.value(h_value).reshape(-1)
         else:
+            h = None
             logits, value, _ = m.forward_logits(obs, spec, want_items=False, **pk)
-        return ops.ppo_loss(logits, value, *rest, **kw)
+        loss, stats = ops.ppo_loss(logits, value, *rest, **kw)
+        return (loss, stats) if self._recon is None else (self._add_reconstruction(loss, h, obs), stats)
 
     def _dw_destinations(self):
         """{parameter data_ptr: its gradient view in the flat arena}: the [out, in] views of the 2-D parameters for the grouped weight-
@@ -1795,6 +1842,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         with torch.no_grad():
             self._bank_pos = self._bank_with_positions()
             self._obs_train = self._training_observations()
+        if self._recon is not None:
+            self._begin_reconstruction()
         if self._use_train_graph:
             self._dyn.copy_(torch.tensor([clip_range, beta], dtype=torch.float64))
             self._sched_host[1:] = [clip_range, beta]

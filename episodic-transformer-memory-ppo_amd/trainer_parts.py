@@ -216,6 +216,9 @@ class _RunOutputs:
             self.writer.add_scalar("other/lr_lowered", self.last_adaptive_lr["lowered"], update)
         if self.last_kl_penalty is not None:             # (kl_penalty: the coefficient the update's steps used)
             self.writer.add_scalar("other/kl_coef", self.last_kl_penalty["coef"], update)
+        if self.last_obs_reconstruction is not None:     # (obs_reconstruction: the mean of the steps' loss, and the coefficient they used)
+            self.writer.add_scalar("losses/obs_reconstruction", self.last_obs_reconstruction["loss"], update)
+            self.writer.add_scalar("other/obs_reconstruction_coef", self.last_obs_reconstruction["coef"], update)
         if self.last_valid_action_share is not None:     # (action_masks: mean share of allowed actions in the rollout's words)
             self.writer.add_scalar("other/valid_action_share", self.last_valid_action_share, update)
         if self.buffer.return_norm is not None:          # (the scale the last rollout's rewards were multiplied with)
@@ -353,6 +356,8 @@ class _CheckpointResume:
                "exp_avg_sq": opt.exp_avg_sq.data_ptr(), "step_dev": opt.step_dev.data_ptr(), "lr_dev": opt.lr_dev.data_ptr()}
         if self._kl_coef is not None:
             out["kl_coef"] = self._kl_coef.data_ptr()
+        if self._recon_coef is not None:
+            out["obs_reconstruction_coef"] = self._recon_coef.data_ptr()
         out.update({"param:" + n: p.data_ptr() for n, p in self.model.named_parameters()})
         out.update({"buffer:" + n: b.data_ptr() for n, b in self.model.named_buffers()})
         if buf.ret_stats is not None:

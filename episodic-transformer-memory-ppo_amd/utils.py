@@ -7,7 +7,8 @@ definition of what the Gaussian heads + loss kernel reduces; exact_kl_section re
 policy kind and categorical_kl is the exact KL of Discrete / MultiDiscrete policies, the one host definition of what the categorical
 loss kernels reduce; kl_penalty_section reads the KL penalty of the loss, kl_penalty_step is the rule that adapts its coefficient once
 per update, and categorical_kl_grad / gaussian_kl_grad are the gradients of the two exact KLs, the one host definition of what the
-penalty kernels add to d logits."""
+penalty kernels add to d logits; obs_reconstruction_section reads the observation reconstruction loss, obs_reconstruction_loss and
+transposed_conv_last are the one host definition of what the fused last decoder layer + loss kernel computes."""
 import numpy as np
 import torch
 from torch import nn
@@ -430,6 +431,125 @@ def kl_penalty_step(coef32, kl32, rule):
     if kl < np.float32(rule["kl_low"]):
         return np.maximum(np.float32(rule["min"]), np.float32(coef * np.float32(rule["down"]))), -1
     return coef, 0
+
+
+OBS_RECONSTRUCTION_KEYS = ("initial", "final", "power", "max_decay_steps")
+
+
+def obs_reconstruction_sizes(limit: int = 200):
+    """The image sizes (one side) the decoder maps back onto themselves, up to ``limit``: the three encoder layers must consume the
+    side without a remainder -- (H - 8) % 4 == 0, then (h1 - 4) % 2 == 0, then h2 >= 3 -- because the transposed layers produce exactly
+    (h - 1) * stride + kernel.  84 -> 20 -> 9 -> 7 -> 9 -> 20 -> 84 is one of them."""
+    return [h for h in range(8, limit + 1) if obs_reconstruction_maps_back(h)]
+
+
+def obs_reconstruction_maps_back(side: int) -> bool:
+    h = int(side)
+    for k, s in ((8, 4), (4, 2), (3, 1)):
+        if h < k or (h - k) % s:
+            return False
+        h = (h - k) // s + 1
+    return True
+
+
+def obs_reconstruction_section(config: dict, observation_shape=None, world: int = 1):
+    """The optional key ``obs_reconstruction`` (a number > 0: a fixed coefficient, or the four keys of the other schedules {initial, final,
+    power, max_decay_steps}) -> that schedule as a dict of floats (``polynomial_decay`` gives the coefficient of an update), or None when
+    the key is absent.  The training loss is then L_ppo + coef * (the mean sigmoid cross-entropy of the decoder's logits against the
+    observation, ``obs_reconstruction_loss``).  Refused, each with what to do instead: a value that is neither a number > 0 nor a dict
+    of exactly the four keys with finite values >= 0 and initial > 0; vector observations and image sizes the decoder does not map back
+    onto themselves (``observation_shape``, when given); a data-parallel run (``world`` > 1)."""
+    value = config.get("obs_reconstruction")
+    if value is None:
+        return None
+    if isinstance(value, dict):
+        unknown, missing = sorted(str(k) for k in set(value) - set(OBS_RECONSTRUCTION_KEYS)), [k for k in OBS_RECONSTRUCTION_KEYS if k not in value]
+        if unknown or missing:
+            raise ValueError(f"obs_reconstruction: a schedule has exactly the keys {list(OBS_RECONSTRUCTION_KEYS)} (unknown: {unknown}, "
+                             f"missing: {missing}); write all four, or a single number for a fixed coefficient")
+        for k in OBS_RECONSTRUCTION_KEYS:
+            if not _finite_number(value[k]) or not value[k] >= 0 or not np.isfinite(_f32(value[k])):
+                raise ValueError(f"obs_reconstruction.{k} must be a finite number >= 0, got {value[k]!r}")
+        if not value["initial"] > 0 or not _f32(value["initial"]) > 0:
+            raise ValueError(f"obs_reconstruction.initial must be > 0 (the coefficient the run starts with), got {value['initial']!r}; "
+                             "remove the key to train without the reconstruction loss")
+        sec = {k: float(value[k]) for k in OBS_RECONSTRUCTION_KEYS}
+    elif _positive_number(value) and np.isfinite(_f32(value)) and _f32(value) > 0:
+        sec = dict(initial=float(value), final=float(value), power=1.0, max_decay_steps=0.0)
+    else:
+        raise ValueError(f"obs_reconstruction must be a number > 0 (a fixed coefficient, e.g. 0.1) or a schedule {{initial, final, power, "
+                         f"max_decay_steps}}, got {value!r}; remove the key to train without the reconstruction loss")
+    if observation_shape is not None:
+        shape = tuple(int(s) for s in observation_shape)
+        if len(shape) != 3:
+            raise ValueError(f"obs_reconstruction is for image observations [C, H, W] (the decoder mirrors the convolutional encoder), got "
+                             f"the observation shape {shape}; remove the key")
+        if shape[0] > 4:
+            raise ValueError(f"obs_reconstruction: the last decoder layer's kernel carries at most 4 image channels, got {shape[0]}; "
+                             "remove the key")
+        bad = [s for s in shape[1:] if not obs_reconstruction_maps_back(s)]
+        if bad:
+            raise ValueError(f"obs_reconstruction: the decoder does not map a side of {bad[0]} pixels back onto itself (the encoder's "
+                             f"layers must consume it without a remainder: (H - 8) % 4 == 0 for the first, and so on); sides that work: "
+                             f"{obs_reconstruction_sizes(132)} ...; resize the observation, or remove the key")
+    if world > 1:
+        raise ValueError("obs_reconstruction in a data-parallel run: every rank would report the reconstruction loss of its own "
+                         "minibatches (agreeing on one loss over the ranks is not built); remove the key, or train on one device")
+    return sec
+
+
+def obs_reconstruction_coef(section: dict, update: int) -> float:
+    """The coefficient of update ``update`` as the float32 the device word holds (a decay of 0 steps: ``initial`` at update 0, then
+    ``final``)."""
+    if section["max_decay_steps"] <= 0:
+        return float(np.float32(section["initial"] if update <= 0 else section["final"]))
+    return float(np.float32(polynomial_decay(section["initial"], section["final"], section["max_decay_steps"], section["power"], update)))
+
+
+def obs_reconstruction_target(target, dtype=np.float64):
+    """The observation as the loss's target in [0, 1]: a byte k stands for float32(k) / float32(255) (the one conversion of
+    csrc/etm_common.h), then ``dtype``; a float array is taken as it is."""
+    t = np.asarray(target)
+    if t.dtype == np.uint8:
+        t = t.astype(np.float32) / np.float32(255)
+    return t.astype(dtype)
+
+
+def obs_reconstruction_loss(logits, target, dtype=np.float64):
+    """(loss, dlogits) of the sigmoid cross-entropy on the logit, in numpy ``dtype`` -- the one host definition of what
+    etm_obs_recon_fwd_loss computes.  Per element l = max(z, 0) - z t + log1p(exp(-|z|)) (no sigmoid followed by a log: finite for every
+    finite z); loss = the mean of l over all elements; dlogits = (sigma(z) - t) / (number of elements), sigma formed from exp(-|z|) so
+    that neither tail overflows.  ``target`` as ``obs_reconstruction_target`` takes it, in the shape of ``logits``."""
+    dt = np.dtype(dtype).type
+    z = np.asarray(logits, dtype=dt)
+    t = obs_reconstruction_target(target, dt)
+    if z.shape != t.shape or z.size == 0:
+        raise ValueError(f"obs_reconstruction_loss: logits and target of one non-empty shape expected, got {z.shape} and {t.shape}")
+    e = np.exp(-np.abs(z))
+    l = np.maximum(z, dt(0)) - z * t + np.log1p(e)
+    r = dt(1) / (dt(1) + e)
+    sigma = np.where(z >= 0, r, e * r)
+    count = dt(z.size)
+    return dt(l.sum(dtype=dt) / count), ((sigma - t) / count).astype(dt)
+
+
+def transposed_conv_last(a, w, b, dtype=np.float64):
+    """The decoder's last layer in plain numpy ``dtype``: ConvTranspose2d(Cin, C, 8, 4) on ``a`` NHWC [N, Hi, Wi, Cin] with ``w``
+    [Cin, C, 8, 8] and ``b`` [C] (the parameters' own layouts) -> the logits NHWC [N, 4 (Hi - 1) + 8, 4 (Wi - 1) + 8, C].  Output pixel
+    (Y, X) sums over the at most 2 x 2 input pixels with 0 <= Y - 4 iy < 8, 0 <= X - 4 ix < 8 and over the channels, in ascending
+    (iy, ix, ci), the bias last -- the kernel's order."""
+    dt = np.dtype(dtype).type
+    a, w, b = np.asarray(a, dtype=dt), np.asarray(w, dtype=dt), np.asarray(b, dtype=dt)
+    if a.ndim != 4 or w.ndim != 4 or w.shape[0] != a.shape[3] or w.shape[2:] != (8, 8) or b.shape != (w.shape[1],):
+        raise ValueError(f"transposed_conv_last: a [N, Hi, Wi, Cin], w [Cin, C, 8, 8], b [C] expected, got {a.shape}, {w.shape}, {b.shape}")
+    n, hi, wi, cin = a.shape
+    c = w.shape[1]
+    z = np.zeros((n, 4 * hi + 4, 4 * wi + 4, c), dtype=dt)
+    for iy in range(hi):
+        for ix in range(wi):
+            for ci in range(cin):       # z[n, 4 iy + ky, 4 ix + kx, c] += a[n, iy, ix, ci] w[ci, c, ky, kx]
+                z[:, 4 * iy:4 * iy + 8, 4 * ix:4 * ix + 8, :] += a[:, iy, ix, ci][:, None, None, None] * w[ci].transpose(1, 2, 0)[None]
+    return z + b
 
 
 PREVIOUS_STEP_MAX_ROWS = 64          # rows of the table the kernels carry (csrc/prev_input.hip PI_MAXR; RF_MAXSPLIT of the step kernel)

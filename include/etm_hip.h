@@ -937,6 +937,43 @@ int etm_prev_input_grad(const float *gm, int64_t gm_stride, const int64_t *actio
                         const float *rewards, float *d_table, int R, int D, int64_t N, float *workspace, int64_t workspace_bytes,
                         void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * obs_reconstruction (csrc/obs_recon.hip; absent upstream's model.py, the auxiliary loss of its author's Memory Gym runs): the
+ * decoder's last layer z = ConvTranspose2d(32, C, 8, 4)(a2) + bias fused with the sigmoid cross-entropy against the observation.
+ * a2 NHWC [N, Hi, Wi, 32]; w [32, C, 8, 8] and bias [C] in the parameters' own layouts; Ho = 4 (Hi - 1) + 8, Wo likewise; 1 <= C <= 4.
+ * utils.transposed_conv_last / utils.obs_reconstruction_loss are the host definitions.
+ *   etm_obs_recon_supported: 1 for 1 <= C <= 4 and 1 <= Hi, Wi <= 4096, else 0.
+ *   etm_obs_recon_fwd_loss: the target is taken as the first encoder layer takes its input: x NHWC [N or x_images, Ho, Wo, C], float32
+ *       (x_is_u8 == 0) or bytes (byte k = float(k) / 255.f correctly rounded), x_index (device int64 [N] or NULL): image n is image
+ *       x_index[n] of x, which then holds x_images images.  z[n, Y, X, c] sums a2[n, iy, ix, ci] w[ci][c][Y - 4 iy][X - 4 ix] over the
+ *       at most 2 x 2 input pixels with 0 <= Y - 4 iy < 8, 0 <= X - 4 ix < 8 and the 32 channels, in ascending (iy, ix, ci), bias last.
+ *       Per element l = max(z, 0) - z t + log1p(exp(-|z|)); sigma(z) is formed from exp(-|z|).  Written:
+ *         dz [N, Ho, Wo, C] = ((sigma(z) - t) / (N Ho Wo C)) * *coef   (float32, the layout of an NHWC image; the difference, the
+ *                             quotient and the product in double, rounded once; coef: one device float read in place --
+ *                             doubling it doubles dz bit for bit, 0 gives zeros)
+ *         out [4]: out[0] = mean of l (NOT scaled by coef), out[1] = *coef, out[2] = out[1] * out[0] (the term of the training
+ *                             loss), out[3] = 0;  db [C] = the sums of dz over (n, Y, X).
+ *       z is never stored; it is accumulated in double.  Three launches: a copy of w as doubles into the workspace, the pass, and the
+ *       sum of the pass's per-workgroup partial sums (doubles, in `workspace`, at least
+ *       etm_obs_recon_workspace_bytes(N, C, Hi, Wi) bytes, 8-byte aligned) in a fixed order.  No float atomics: two calls give the
+ *       same bits.
+ *   etm_obs_recon_dgrad: da2[n, iy, ix, ci] = (a2 > 0) sum_{ky, kx, c} dz[n, 4 iy + ky, 4 ix + kx, c] w[ci][c][ky][kx] -- the first
+ *       encoder layer's forward on the gradient image without bias, masked by the ReLU pattern of a2.  One launch.
+ *   The weight gradient needs no entry of its own: dW[ci][c][ky][kx] = sum a2[n, iy, ix, ci] dz[n, 4 iy + ky, 4 ix + kx, c] is the
+ *       first encoder layer's weight gradient with the roles exchanged -- etm_conv_train_wgrad(x := dz, x_index NULL, dy := a2, ...,
+ *       N, C, H = Ho, W = Wo, Cout = 32, KH = KW = 8, S = 4) returns it as [32, C, 8, 8], the decoder parameter's layout.  The 32
+ *       trailing floats (that entry's "bias gradient") are the column sums of a2: discard them, db comes from etm_obs_recon_fwd_loss.
+ * ETM_EINVAL, with nothing launched: a NULL pointer (x_index may be NULL), a NULL coef, a misaligned pointer (a2, dz, da2 and a float
+ * x: 16 bytes; a byte x: 4; workspace and x_index: 8; the others: 4), N < 1, C outside 1 .. 4, an x_index with x_images < 1.
+ * ETM_EUNSUPPORTED: Hi / Wi outside etm_obs_recon_supported; ETM_EWORKSPACE: a workspace below the stated size.
+ * Profiling (etm_profile_*): booked under the conv_train_fwd / colsum / conv_train_dgrad slots. */
+int etm_obs_recon_supported(int C, int Hi, int Wi);
+int64_t etm_obs_recon_workspace_bytes(int64_t N, int C, int Hi, int Wi);
+int etm_obs_recon_fwd_loss(const float *a2, const float *w, const float *bias, const void *x, int x_is_u8, const int64_t *x_index,
+                           int64_t x_images, const float *coef, float *dz, float *out, float *db, void *workspace, int64_t workspace_bytes,
+                           int64_t N, int C, int Hi, int Wi, void *stream);
+int etm_obs_recon_dgrad(const float *dz, const float *w, const float *a2, float *da2, int64_t N, int C, int Hi, int Wi, void *stream);
+
 /* Monitored gradient norms of the module groups (model.py:128-151) from the flat gradient arena in two launches:
  * out[g] = sqrt(sum_s member[g][s] * ||flat[seg_start[s] .. seg_start[s] + seg_len[s])||^2).  Segments: runs of <= 4096 floats, each
  * inside one parameter tensor (device arrays seg_start int64 [n_segs], seg_len int32 [n_segs]); member [n_groups, n_segs] float
