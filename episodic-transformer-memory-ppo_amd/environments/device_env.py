@@ -1,0 +1,148 @@
+"""Device-resident vectorised environments: ``CueRoomDeviceVecEnv`` serves CueRoom (environments/cue_room_env.py is the one
+definition of the rule) from device memory -- step, auto-reset and rendering of all its workers are ONE HIP kernel per call
+(csrc/device_env.hip), bit for bit the host rule.
+
+Two ways of stepping, over the same state:
+
+* the ``VecEnv`` protocol (``reset`` / ``step`` / ``action_masks``, vec_env.py): ``step(actions, out)`` uploads the host actions, runs
+  the kernel into a device frame block and copies the frames into ``out`` -- every existing consumer works unchanged;
+* ``device_resident = True`` and ``step_device(actions_dev, rows_dev, stream)``: the kernel reads the actions where the sampling
+  kernel left them and writes the frames where the next step's encoder reads them; no observation byte crosses the bus.  The trainer
+  takes this form in the plans that stream observations (trainer._drive_rollout_host).
+
+Both return the step's rewards, dones and infos from result words the kernel writes into pinned host memory.  The host waits for them
+on an EVENT recorded behind the launch, not on a completion word: the step's workgroups have no arrival counter (it would be the
+kernel's only atomic), so a word needs a second launch behind the step (the C entry offers it), and the event behind one launch was
+the shorter chain.
+"""
+import numpy as np
+import torch
+
+from etm import lib as etm_lib
+
+
+class CueRoomDeviceVecEnv:
+    device_resident = True
+    observation_dtype = np.uint8
+
+    def __init__(self, num_envs, grid=7, cell=12, cue_steps=2, max_episode_steps=32, seed=0, first_worker_id=0, device=None):
+        from environments import ActionKind
+        from environments.cue_room_env import cue_room_section
+        sec = cue_room_section(dict(grid=grid, cell=cell, cue_steps=cue_steps, max_episode_steps=max_episode_steps, seed=seed))
+        if int(num_envs) < 1:
+            raise ValueError("CueRoomDeviceVecEnv needs at least one environment")
+        if not torch.cuda.is_available():
+            raise RuntimeError("environment.device: true needs the MI355X (the environments live in device memory): set device: false "
+                               "for the host twin")
+        self._etm = etm_lib.load()
+        self.grid, self.cell, self.cue_steps = sec["grid"], sec["cell"], sec["cue_steps"]
+        if not self._etm.etm_cue_room_supported(self.grid, self.cell):
+            raise ValueError(f"CueRoom: the kernel does not take grid {self.grid} with cell {self.cell}")
+        self.num_envs = W = int(num_envs)
+        self.max_episode_steps = sec["max_episode_steps"]
+        side = self.grid * self.cell
+        self.observation_space_shape = (3, side, side)
+        self.action_kind = ActionKind("discrete", (4,))
+        self.action_space_shape = (4,)
+        self.num_actions = 4
+        self.stream0 = (sec["seed"] + int(first_worker_id)) & ((1 << 64) - 1)
+        if self.stream0 >= 1 << 63:
+            self.stream0 -= 1 << 64          # (the C entry takes the 64-bit word as int64)
+        self.device = dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.frame_bytes = 3 * side * side
+        self._state = torch.zeros(int(self._etm.etm_cue_room_state_bytes(W)) // 8, dtype=torch.int64, device=dev)
+        self._frames = torch.zeros((W,) + self.observation_space_shape, dtype=torch.uint8, device=dev)
+        self._act_dev = torch.zeros(W, dtype=torch.int64, device=dev)
+        self._act_pin = torch.zeros(W, dtype=torch.int64).pin_memory()
+        # the result words, in pinned host memory: the kernel writes them in place
+        self._rewards = torch.zeros(W, dtype=torch.float32).pin_memory()
+        self._flags = torch.zeros(W, dtype=torch.uint8).pin_memory()
+        self._returns = torch.zeros(W, dtype=torch.float32).pin_memory()
+        self._lengths = torch.zeros(W, dtype=torch.int32).pin_memory()
+        self._masks = torch.zeros(W, dtype=torch.int64).pin_memory()
+        self._rewards_np, self._flags_np, self._returns_np = self._rewards.numpy(), self._flags.numpy(), self._returns.numpy()
+        self._lengths_np, self._masks_np = self._lengths.numpy(), self._masks.numpy()
+        self._words = tuple(t.data_ptr() for t in (self._rewards, self._flags, self._returns, self._lengths, self._masks))
+        self._rule = (W, self.grid, self.cell, self.cue_steps, self.max_episode_steps, self.stream0)
+        self._done_event = torch.cuda.Event()
+        self.device_steps = 0          # calls of step_device (the trainer's fast path), for tests and tools
+        self.protocol_steps = 0        # calls of step
+
+    # ---------------------------------------------------------------- launches
+    def _run(self, actions_ptr, act_stride, frames_ptr, stream):
+        """One launch on ``stream`` (a torch stream), then the host waits for its result words."""
+        args = self._words + (None, 0) + self._rule + (stream.cuda_stream,)
+        if actions_ptr is None:
+            rc = self._etm.etm_cue_room_reset(self._state.data_ptr(), frames_ptr, self.frame_bytes, *args)
+        else:
+            rc = self._etm.etm_cue_room_step(self._state.data_ptr(), actions_ptr, act_stride, frames_ptr, self.frame_bytes, *args)
+        if rc != 0:
+            etm_lib.check(rc, "etm_cue_room_reset" if actions_ptr is None else "etm_cue_room_step")
+        self._done_event.record(stream)
+        self._done_event.synchronize()
+
+    def _results(self):
+        """(rewards, dones, infos) of the last step from the pinned words (copies: the next launch rewrites the words)."""
+        flags = self._flags_np
+        dones = (flags & 1) != 0
+        infos = [None] * self.num_envs
+        for w in np.flatnonzero(dones):
+            info = {"reward": float(self._returns_np[w]), "length": int(self._lengths_np[w]), "success": int(flags[w] >> 2 & 1)}
+            if flags[w] & 2:
+                info["truncated"] = True
+            infos[w] = info
+        return self._rewards_np.copy(), dones, infos
+
+    def _frames_to(self, out):
+        if out is None:
+            return self._frames.cpu().numpy()
+        if isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype == np.uint8:
+            torch.from_numpy(out).copy_(self._frames)
+        else:
+            out[...] = self._frames.cpu().numpy()
+        return out
+
+    # ---------------------------------------------------------------- the VecEnv protocol
+    def reset(self, out=None):
+        self._run(None, 0, self._frames.data_ptr(), torch.cuda.current_stream(self.device))
+        return self._frames_to(out)
+
+    def step(self, actions, out=None, on_rows=None):
+        a = np.asarray(actions).reshape(self.num_envs, -1)[:, 0]
+        if a.min() < 0 or a.max() > 3:
+            raise ValueError(f"CueRoom: action {int(a[(a < 0) | (a > 3)][0])} is outside Discrete(4)")
+        self._act_pin.numpy()[:] = a
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(stream):
+            self._act_dev.copy_(self._act_pin, non_blocking=True)
+        self._run(self._act_dev.data_ptr(), 1, self._frames.data_ptr(), stream)
+        self.protocol_steps += 1
+        out = self._frames_to(out)
+        if on_rows is not None:
+            on_rows(0, self.num_envs)
+        rewards, dones, infos = self._results()
+        return out, rewards, dones, infos
+
+    def action_masks(self, out=None):
+        """The words of the frames last written (by ``reset``, ``step`` or ``step_device``)."""
+        if out is None:
+            return self._masks_np.view(np.uint64).copy()
+        out.view(np.uint64)[...] = self._masks_np.view(np.uint64)
+        return out
+
+    # ---------------------------------------------------------------- the device-resident form
+    def step_device(self, actions_dev, rows_dev, stream=None):
+        """``actions_dev``: device int64 [W] or [W, 1] (a row stride is honoured), the rows the sampling kernel wrote; ``rows_dev``: a
+        device uint8 tensor [W, 3, S, S] (contiguous) or the address of W contiguous frames -- rows [lo, hi) of a staging row;
+        ``stream``: the torch stream the launch is enqueued on (None: the current one).  -> (rewards, dones, infos)."""
+        if actions_dev.dtype != torch.int64 or actions_dev.shape[0] != self.num_envs:
+            raise ValueError("step_device: actions_dev is the device int64 [W] / [W, 1] table of the sampling kernels")
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        rows = rows_dev.data_ptr() if hasattr(rows_dev, "data_ptr") else int(rows_dev)
+        self._run(actions_dev.data_ptr(), actions_dev.stride(0), rows, stream)
+        self.device_steps += 1
+        return self._results()
+
+    def close(self):
+        return None

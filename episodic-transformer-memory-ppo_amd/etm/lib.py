@@ -240,6 +240,11 @@ SIGNATURES["etm_obs_recon_supported"] = (_I, [_I, _I, _I])
 SIGNATURES["etm_obs_recon_workspace_bytes"] = (_L, [_L, _I, _I, _I])
 SIGNATURES["etm_obs_recon_fwd_loss"] = (_I, [_P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P])
 SIGNATURES["etm_obs_recon_dgrad"] = (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P])
+# device-resident environments (csrc/device_env.hip; the ABI stays at 61): CueRoom stepped, auto-reset and rendered by one launch
+SIGNATURES["etm_cue_room_supported"] = (_I, [_I, _I])
+SIGNATURES["etm_cue_room_state_bytes"] = (_L, [_I])
+SIGNATURES["etm_cue_room_reset"] = (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P])
+SIGNATURES["etm_cue_room_step"] = (_I, [_P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P])
 del _twin
 del _name, _extra, _res, _args
 

@@ -44,6 +44,7 @@ def default_rollout_groups(num_workers: int, min_group: int) -> int:
 
 from buffer import Buffer
 from environments import action_space_kind, branch_bit_masks, empty_mask_branches, valid_action_share
+from environments.cue_room_env import check_device_env_config
 from environments.vec_env import make_vec_env
 from etm import lib as etm_lib
 from etm import ops
@@ -132,7 +133,9 @@ def check_box_policy(config: dict, A=None):
 def check_byte_observation_transport(config, env=None):
     """``worker_processes: true`` with ``observation_dtype: uint8`` is refused, before any environment or process is created: the
     workers' shared segment types its observation rows as float32 (environments/shm_env.py)."""
-    if env is None and config.get("worker_processes", False) and str(config["environment"].get("observation_dtype", "float32")) == "uint8":
+    env_cfg = config["environment"]
+    as_bytes = str(env_cfg.get("observation_dtype", "float32")) == "uint8" or env_cfg.get("type") == "CueRoom"      # (CueRoom has no float form)
+    if env is None and config.get("worker_processes", False) and as_bytes:
         raise ValueError("worker_processes: true does not carry uint8 observations (the shared segment's rows are float32): "
                          "set worker_processes: false (in-process environments keep the bytes), or let the environment emit float32")
 
@@ -361,6 +364,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         check_box_policy(config)
         check_byte_observation_transport(config, env)
         check_truncation_transport(config, env)
+        if env is None:       # environment.device: true (CueRoom on the device) against the transports and the world size
+            check_device_env_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_action_mask_config(config, env)
         # previous_step_input: the value itself and the transport, before any environment or process is created (the shared segment of
         # the worker processes has no row for the last reward); the action space is looked at below
@@ -948,8 +953,13 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         masked, rw = self._masked, self._rw_np
         fence = self._etm.etm_host_store_fence
         t_env = t_wait = t_launch = 0.0
+        # a device-resident front-end (environments/device_env.py) in a plan that streams observations: its kernel reads the actions in
+        # g.act_dev and writes the frames of step t + 1 into the group's rows of staging row t + 1, on the group's stream -- behind the
+        # step's sampling, in front of the next step's encoder; nothing is uploaded.  Every other front-end takes the branches of ever.
+        resident = [stream_obs and bool(getattr(g.env, "device_resident", False)) for g in groups]
+        main = torch.cuda.current_stream(self.device)
         for t in range(S):
-            for g in groups:
+            for g, on_device in zip(groups, resident):
                 lo, hi = g.lo, g.hi
                 tw = clock()
                 if host_flag:
@@ -963,7 +973,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                 # the rows of observation t + 1 go straight into their staging row in device memory (the fence sits between them and
                 # the next launch), or into pinned memory and from there, as the environment emits them, into their staging row, or
                 # (unstreamed, and after the last step) into pinned memory alone
-                if direct and t + 1 < S:
+                if on_device and t + 1 < S:
+                    rewards, dones, infos = g.env.step_device(g.act_dev, g.stage0 + (t + 1) * g._stage_pitch, g.stream if g.stream is not None else main)
+                elif direct and t + 1 < S:
                     _, rewards, dones, infos = g.env.step(g.acts_host, out=self._stage_host[t + 1, lo:hi])
                     fence(self._dev_index)
                 elif stream_obs and t + 1 < S:

@@ -974,6 +974,35 @@ int etm_obs_recon_fwd_loss(const float *a2, const float *w, const float *bias, c
                            int64_t N, int C, int Hi, int Wi, void *stream);
 int etm_obs_recon_dgrad(const float *dz, const float *w, const float *a2, float *da2, int64_t N, int C, int Hi, int Wi, void *stream);
 
+/* Device-resident environments (csrc/device_env.hip; added with the ABI left at 61 -- no signature above changes): CueRoom, the image
+ * memory task whose one host definition is environments/cue_room_env.py, stepped, auto-reset and rendered by ONE launch per call, one
+ * workgroup per environment.  G x G cells (G odd) of P x P pixels (P % 4 == 0); a frame is [3, G P, G P] bytes, CHW.
+ *   etm_cue_room_supported: 1 for odd 3 <= G <= 31 and P % 4 == 0, 4 <= P <= 64, else 0.
+ *   etm_cue_room_state_bytes: bytes of device memory the caller owns for W environments (32 each; 0 for W < 1), 8-byte aligned.
+ *   etm_cue_room_reset: every environment w < W starts episode 0 of the stream stream0 + w (stream0 = seed + first worker id, taken
+ *       mod 2^64) and writes the outputs below with rewards, flags, returns and lengths zero.
+ *   etm_cue_room_step: environment w reads actions[w * act_stride] (the int64 rows the sampling kernels write; a value outside 0 .. 3
+ *       is clamped -- the host rule raises), advances its state exactly once, decides reward, done, truncated and success, starts the
+ *       next episode where done, then renders the NEW state.  Bit for bit the host rule on valid actions.
+ * Outputs (every pointer may be pinned host memory): frames -- environment w's frame at frames + w * frame_pitch bytes, written
+ * with 4-byte stores, nothing outside [w * frame_pitch, w * frame_pitch + 3 G P G P) is touched; rewards [W] float32 (1.0 for the
+ * target, else 0.0); flags [W] bytes (bit 0 done, bit 1 truncated, bit 2 success); returns [W] float32 and lengths [W] int32 of the
+ * episode that ended (0 where none did); masks [W] int64 of the frame written (bit a set when move a stays on the grid).
+ * done_word (optional, 8-byte aligned, host-visible): receives done_value after every result, by a one-thread launch behind the step
+ * on the same stream (one system-scope fence, then a system-scope release store: the sampling kernels' hand-over).
+ * Integer arithmetic only, no atomics: two calls from equal state give equal bytes.
+ * ETM_EINVAL, with nothing launched: a NULL pointer (done_word may be NULL), a misaligned pointer (state, actions, masks, done_word:
+ * 8 bytes; frames, rewards, returns, lengths: 4), W < 1, act_stride < 1, frame_pitch below 3 G P G P or no multiple of 4, cue_steps
+ * or max_steps < 1, (G, P) outside etm_cue_room_supported. */
+int etm_cue_room_supported(int G, int P);
+int64_t etm_cue_room_state_bytes(int W);
+int etm_cue_room_reset(void *state, uint8_t *frames, int64_t frame_pitch, float *rewards, uint8_t *flags, float *returns, int32_t *lengths,
+                       int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P, int cue_steps, int max_steps,
+                       int64_t stream0, void *stream);
+int etm_cue_room_step(void *state, const int64_t *actions, int64_t act_stride, uint8_t *frames, int64_t frame_pitch, float *rewards,
+                      uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W,
+                      int G, int P, int cue_steps, int max_steps, int64_t stream0, void *stream);
+
 /* Monitored gradient norms of the module groups (model.py:128-151) from the flat gradient arena in two launches:
  * out[g] = sqrt(sum_s member[g][s] * ||flat[seg_start[s] .. seg_start[s] + seg_len[s])||^2).  Segments: runs of <= 4096 floats, each
  * inside one parameter tensor (device arrays seg_start int64 [n_segs], seg_len int32 [n_segs]); member [n_groups, n_segs] float
