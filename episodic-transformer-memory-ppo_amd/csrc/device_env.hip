@@ -11,6 +11,8 @@
 // The completion word (optional) is a second, one-thread launch behind the step on the same stream: the workgroups of the step have
 // no arrival counter (that would be an atomic), so "everything is written" is the stream's order; the store itself is the sampling
 // kernels' hand-over (one system-scope fence, then a system-scope release store).
+// CommandRoom (environments/command_room_env.py), further down, is the second task of the same shape; the two share splitmix64, the
+// output record (EnvOut), the argument validation (env_check) and the publish launch (env_publish).
 #include "etm_common.h"
 
 namespace {
@@ -28,7 +30,7 @@ struct CueRule {
   unsigned long long stream0;          // seed + first worker id; environment w draws from stream0 + w
 };
 
-struct CueOut {
+struct EnvOut {                        // the output record of every task here
   unsigned char *frames;               // environment w's frame at frames + w * pitch: [3, G P, G P] bytes
   long long pitch;
   float *rewards;                      // [W]
@@ -72,7 +74,7 @@ __device__ __forceinline__ int cr_corner(int r, int c, int G) {
 
 template <bool RESET>
 __global__ __launch_bounds__(CR_THREADS) void cue_room_kernel(CueState *__restrict__ state, const long long *__restrict__ actions,
-                                                              long long act_ld, const CueRule rule, const CueOut out) {
+                                                              long long act_ld, const CueRule rule, const EnvOut out) {
   __shared__ int pic[4];               // agent row, agent column, target, cue visible
   const int w = blockIdx.x, G = rule.G;
   if (threadIdx.x == 0) {
@@ -139,27 +141,188 @@ __global__ __launch_bounds__(CR_THREADS) void cue_room_kernel(CueState *__restri
   }
 }
 
-__global__ void cue_room_publish_kernel(long long *word, long long value) {
+// ---------------------------------------------------------------------------------------------------------------- CommandRoom
+// environments/command_room_env.py is the ONE host definition of the rule: K commands shown one after the other (observation t of
+// the episode shows command t / L while t % L < show_steps, L = show_steps + gap_steps), then executed from memory, one per step.
+// Same shape as above: thread 0 advances the 32-byte state once and leaves three cell indices (mark, pointer, agent; -1: not drawn)
+// in LDS, after one barrier all threads fill the frame.  The one float operation is the episode's return, float(n) * 0.1f.
+constexpr int CMD_MAX_COMMANDS = 16;
+
+struct CmdState {                      // 32 bytes per environment (etm_command_room_state_bytes)
+  unsigned long long episode;
+  unsigned long long commands;         // command j in bits [3 j, 3 j + 3)
+  int row, col, t, n;
+};
+static_assert(sizeof(CmdState) == 32, "CmdState is 32 bytes");
+
+struct CmdRule {
+  int G, P, K, show_steps, L;
+  unsigned long long stream0;
+};
+
+// flat colours of floor, mark, pointer, agent (command_room_env.PALETTE)
+__device__ __constant__ unsigned cmd_palette[4][3] = {{20u * 0x01010101u, 24u * 0x01010101u, 40u * 0x01010101u},
+                                                      {208u * 0x01010101u, 208u * 0x01010101u, 216u * 0x01010101u},
+                                                      {48u * 0x01010101u, 176u * 0x01010101u, 232u * 0x01010101u},
+                                                      {232u * 0x01010101u, 96u * 0x01010101u, 32u * 0x01010101u}};
+
+__device__ __forceinline__ int cmd_dr(int a) { return a == 0 ? -1 : (a == 2 ? 1 : 0); }
+__device__ __forceinline__ int cmd_dc(int a) { return a == 1 ? 1 : (a == 3 ? -1 : 0); }
+
+// bit a set when move a (up, right, down, left, stay) keeps (r, c) on the grid
+__device__ __forceinline__ unsigned cmd_valid(int r, int c, int G) {
+  return (r > 0 ? 1u : 0u) | (c < G - 1 ? 2u : 0u) | (r < G - 1 ? 4u : 0u) | (c > 0 ? 8u : 0u) | 16u;
+}
+
+// (x >> 16) mod n for n = 3, 4 or 5 without a 64-bit division (a long software loop on one lane, K times per draw, while 255 threads
+// wait at the barrier): the 48-bit value is hi 2^24 + lo with 24-bit halves, 2^24 = 1 mod 3 and mod 5 and 0 mod 4, so it is congruent
+// to hi + lo (below 2^25) resp. lo, and the three divisors are constants.
+__device__ __forceinline__ int cmd_pick(unsigned long long x, unsigned n) {
+  const unsigned hi = (unsigned)(x >> 40), lo = (unsigned)(x >> 16) & 0xffffffu;
+  return (int)(n == 3u ? (hi + lo) % 3u : (n == 4u ? lo & 3u : (hi + lo) % 5u));
+}
+
+__device__ __forceinline__ void cmd_draw(CmdState &s, unsigned long long stream, int G, int K) {
+  const unsigned long long h = cr_splitmix64(cr_splitmix64(stream) + s.episode);
+  const int start = (int)((h >> 8) % (unsigned long long)(G * G));
+  s.row = start / G;
+  s.col = start % G;
+  s.t = 0;
+  s.n = 0;
+  int r = s.row, c = s.col;
+  unsigned long long x = h, word = 0;
+  for (int j = 0; j < K; ++j) {
+    x = cr_splitmix64(x);
+    const unsigned valid = cmd_valid(r, c, G);
+    int pick = cmd_pick(x, (unsigned)__popc(valid));                      // the pick-th set bit of valid, from bit 0
+    int a = 0;
+    for (int b = 0; b < 5; ++b) {
+      if (valid >> b & 1u) {
+        if (pick == 0) a = b;
+        --pick;
+      }
+    }
+    word |= (unsigned long long)a << (3 * j);
+    r += cmd_dr(a);
+    c += cmd_dc(a);
+  }
+  s.commands = word;
+}
+
+template <bool RESET>
+__global__ __launch_bounds__(CR_THREADS) void command_room_kernel(CmdState *__restrict__ state, const long long *__restrict__ actions,
+                                                                  long long act_ld, const CmdRule rule, const EnvOut out) {
+  __shared__ int pic[3];               // cell index (row-major) of the mark, the pointer and the agent; -1: not drawn
+  const int w = blockIdx.x, G = rule.G, K = rule.K;
+  const int show_len = K * rule.L;     // the first execute observation
+  if (threadIdx.x == 0) {
+    CmdState s;
+    float reward = 0.f, ep_ret = 0.f;
+    unsigned flag = 0;
+    int ep_len = 0;
+    if (RESET) {
+      s.episode = 0;
+      cmd_draw(s, rule.stream0 + (unsigned long long)w, G, K);
+    } else {
+      s = state[w];
+      long long a = actions[(long long)w * act_ld];
+      a = a < 0 ? 0 : (a > 4 ? 4 : a);                                 // (the host rule raises; the kernel never leaves the table)
+      const int e = s.t - show_len;
+      if (e >= 0) {                                                    // execute; an action on a show or gap observation is ignored
+        const int cmd = e < K ? (int)(s.commands >> (3 * e) & 7ull) : -1;
+        if ((int)a == cmd) {
+          reward = 0.1f;
+          s.row += cmd_dr(cmd);
+          s.col += cmd_dc(cmd);
+          s.n += 1;
+          if (e == K - 1) flag = 1u | 4u;
+        } else {
+          flag = 1u;
+        }
+      }
+      s.t += 1;
+      if (flag) {
+        ep_ret = (float)s.n * 0.1f;
+        ep_len = s.t;
+        s.episode += 1;                                                // auto-reset: the frame below is the next episode's first
+        cmd_draw(s, rule.stream0 + (unsigned long long)w, G, K);
+      }
+    }
+    state[w] = s;
+    out.rewards[w] = reward;
+    out.flags[w] = (unsigned char)flag;
+    out.returns[w] = ep_ret;
+    out.lengths[w] = ep_len;
+    int mark = -1, pointer = -1, agent = -1;
+    unsigned mask = 31u;
+    if (s.t < show_len) {
+      if (s.t % rule.L < rule.show_steps) {
+        const int cmd = (int)(s.commands >> (3 * (s.t / rule.L)) & 7ull), mid = G >> 1;
+        mark = mid * G + mid;
+        if (cmd != 4) pointer = (mid + cmd_dr(cmd)) * G + mid + cmd_dc(cmd);
+      }
+    } else {
+      agent = s.row * G + s.col;
+      mask = cmd_valid(s.row, s.col, G);
+    }
+    out.masks[w] = (long long)mask;
+    pic[0] = mark;
+    pic[1] = pointer;
+    pic[2] = agent;
+  }
+  __syncthreads();
+  const int mark = pic[0], pointer = pic[1], agent = pic[2];
+  const int P = rule.P, side = G * P, row_words = side >> 2, plane_words = side * row_words;
+  unsigned *dst = reinterpret_cast<unsigned *>(out.frames + (long long)w * out.pitch);
+  for (int i = threadIdx.x; i < 3 * plane_words; i += CR_THREADS) {
+    const int ch = i / plane_words, rem = i - ch * plane_words;
+    const int y = rem / row_words, xw = rem - y * row_words;
+    const int cell = (y / P) * G + (xw << 2) / P;
+    const int colour = cell == agent ? 3 : (cell == pointer ? 2 : (cell == mark ? 1 : 0));
+    dst[i] = cmd_palette[colour][ch];
+  }
+}
+
+__global__ void env_publish_kernel(long long *word, long long value) {
   __threadfence_system();
   __hip_atomic_store(word, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 inline bool cr_al(const void *p, unsigned a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
-int cr_launch(bool reset, void *state, const int64_t *actions, int64_t act_stride, uint8_t *frames, int64_t frame_pitch, float *rewards,
-              uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P,
-              int cue_steps, int max_steps, int64_t stream0, void *stream) {
-  (void)hipGetLastError();
+// What the tasks' entries validate alike, before anything is launched: pointers and their alignment, W, the geometry's frame
+// size against the pitch.  -> 0 or ETM_EINVAL.
+int env_check(bool reset, const void *state, const int64_t *actions, int64_t act_stride, const uint8_t *frames, int64_t frame_pitch,
+              const float *rewards, const uint8_t *flags, const float *returns, const int32_t *lengths, const int64_t *masks,
+              const int64_t *done_word, int W, int G, int P) {
   if (!state || !frames || !rewards || !flags || !returns || !lengths || !masks || W < 1) return ETM_EINVAL;
   if (!reset && (!actions || act_stride < 1 || !cr_al(actions, 8))) return ETM_EINVAL;
-  if (!etm_cue_room_supported(G, P) || cue_steps < 1 || max_steps < 1) return ETM_EINVAL;
+  if (!etm_cue_room_supported(G, P)) return ETM_EINVAL;
   if (!cr_al(state, 8) || !cr_al(frames, 4) || !cr_al(rewards, 4) || !cr_al(returns, 4) || !cr_al(lengths, 4) || !cr_al(masks, 8) ||
       !cr_al(done_word, 8))
     return ETM_EINVAL;
   const int64_t frame_bytes = 3ll * G * P * G * P;
   if (frame_pitch < frame_bytes || (frame_pitch & 3) != 0) return ETM_EINVAL;
+  return 0;
+}
+
+// Behind a step's launch: its status, then (optionally) the completion word by a one-thread launch on the same stream.
+int env_publish(int64_t *done_word, int64_t done_value, hipStream_t st) {
+  int rc = etm_launch_status();
+  if (rc || !done_word) return rc;
+  hipLaunchKernelGGL(env_publish_kernel, dim3(1), dim3(1), 0, st, (long long *)done_word, (long long)done_value);
+  return etm_launch_status();
+}
+
+int cr_launch(bool reset, void *state, const int64_t *actions, int64_t act_stride, uint8_t *frames, int64_t frame_pitch, float *rewards,
+              uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P,
+              int cue_steps, int max_steps, int64_t stream0, void *stream) {
+  (void)hipGetLastError();
+  if (env_check(reset, state, actions, act_stride, frames, frame_pitch, rewards, flags, returns, lengths, masks, done_word, W, G, P) ||
+      cue_steps < 1 || max_steps < 1)
+    return ETM_EINVAL;
   const CueRule rule{G, P, cue_steps, max_steps, (unsigned long long)stream0};
-  const CueOut out{frames, (long long)frame_pitch, rewards, flags, returns, lengths, (long long *)masks};
+  const EnvOut out{frames, (long long)frame_pitch, rewards, flags, returns, lengths, (long long *)masks};
   hipStream_t st = (hipStream_t)stream;
   if (reset)
     hipLaunchKernelGGL(cue_room_kernel<true>, dim3((unsigned)W), dim3(CR_THREADS), 0, st, (CueState *)state, (const long long *)nullptr, 0ll,
@@ -167,15 +330,53 @@ int cr_launch(bool reset, void *state, const int64_t *actions, int64_t act_strid
   else
     hipLaunchKernelGGL(cue_room_kernel<false>, dim3((unsigned)W), dim3(CR_THREADS), 0, st, (CueState *)state, (const long long *)actions,
                        (long long)act_stride, rule, out);
-  int rc = etm_launch_status();
-  if (rc || !done_word) return rc;
-  hipLaunchKernelGGL(cue_room_publish_kernel, dim3(1), dim3(1), 0, st, (long long *)done_word, (long long)done_value);
-  return etm_launch_status();
+  return env_publish(done_word, done_value, st);
+}
+
+int cmd_launch(bool reset, void *state, const int64_t *actions, int64_t act_stride, uint8_t *frames, int64_t frame_pitch, float *rewards,
+               uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P,
+               int K, int show_steps, int gap_steps, int64_t stream0, void *stream) {
+  (void)hipGetLastError();
+  if (env_check(reset, state, actions, act_stride, frames, frame_pitch, rewards, flags, returns, lengths, masks, done_word, W, G, P) ||
+      !etm_command_room_supported(G, P, K) || show_steps < 1 || gap_steps < 0 ||
+      (long long)K * ((long long)show_steps + gap_steps) + K > 0x7fffffffll)
+    return ETM_EINVAL;
+  const CmdRule rule{G, P, K, show_steps, show_steps + gap_steps, (unsigned long long)stream0};
+  const EnvOut out{frames, (long long)frame_pitch, rewards, flags, returns, lengths, (long long *)masks};
+  hipStream_t st = (hipStream_t)stream;
+  if (reset)
+    hipLaunchKernelGGL(command_room_kernel<true>, dim3((unsigned)W), dim3(CR_THREADS), 0, st, (CmdState *)state, (const long long *)nullptr,
+                       0ll, rule, out);
+  else
+    hipLaunchKernelGGL(command_room_kernel<false>, dim3((unsigned)W), dim3(CR_THREADS), 0, st, (CmdState *)state,
+                       (const long long *)actions, (long long)act_stride, rule, out);
+  return env_publish(done_word, done_value, st);
 }
 }  // namespace
 
 extern "C" int etm_cue_room_supported(int G, int P) {
   return G >= 3 && G <= CR_MAX_GRID && (G & 1) == 1 && P >= 4 && P <= CR_MAX_CELL && (P & 3) == 0 ? 1 : 0;
+}
+
+extern "C" int etm_command_room_supported(int G, int P, int K) {
+  return etm_cue_room_supported(G, P) && K >= 1 && K <= CMD_MAX_COMMANDS ? 1 : 0;
+}
+
+extern "C" int64_t etm_command_room_state_bytes(int W) { return W < 1 ? 0 : (int64_t)W * (int64_t)sizeof(CmdState); }
+
+extern "C" int etm_command_room_reset(void *state, uint8_t *frames, int64_t frame_pitch, float *rewards, uint8_t *flags, float *returns,
+                                      int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P,
+                                      int K, int show_steps, int gap_steps, int64_t stream0, void *stream) {
+  return cmd_launch(true, state, nullptr, 0, frames, frame_pitch, rewards, flags, returns, lengths, masks, done_word, done_value, W, G, P,
+                    K, show_steps, gap_steps, stream0, stream);
+}
+
+extern "C" int etm_command_room_step(void *state, const int64_t *actions, int64_t act_stride, uint8_t *frames, int64_t frame_pitch,
+                                     float *rewards, uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks,
+                                     int64_t *done_word, int64_t done_value, int W, int G, int P, int K, int show_steps, int gap_steps,
+                                     int64_t stream0, void *stream) {
+  return cmd_launch(false, state, actions, act_stride, frames, frame_pitch, rewards, flags, returns, lengths, masks, done_word,
+                    done_value, W, G, P, K, show_steps, gap_steps, stream0, stream);
 }
 
 extern "C" int64_t etm_cue_room_state_bytes(int W) { return W < 1 ? 0 : (int64_t)W * (int64_t)sizeof(CueState); }

@@ -102,9 +102,11 @@ def cue_room_section(env_config: dict) -> dict:
 def check_device_env_config(config: dict, world: int = 1) -> bool:
     """``environment.device: true`` against the rest of the config, before anything is built -> whether the key is on.  Refused:
     ``worker_processes: true`` (the environments live on the device, no process steps them), ``bootstrap_truncated: true`` (the
-    front-end keeps no final observation) and a data-parallel run (``world`` > 1: not built, not measured)."""
-    env_config = config.get("environment", {})
-    if env_config.get("type") != "CueRoom" or not cue_room_section(env_config)["device"]:
+    front-end keeps no final observation) and a data-parallel run (``world`` > 1: not built, not measured).  Every type of
+    environments/device_types.py is covered alike."""
+    from environments.device_types import device_env_section
+    sec = device_env_section(config.get("environment", {}))
+    if sec is None or not sec["device"]:
         return False
     if config.get("worker_processes", False):
         raise ValueError("environment.device: true keeps the environments on the device, worker_processes: true in host processes: set "

@@ -1,6 +1,6 @@
 """Device-resident vectorised environments: ``CueRoomDeviceVecEnv`` serves CueRoom (environments/cue_room_env.py is the one
-definition of the rule) from device memory -- step, auto-reset and rendering of all its workers are ONE HIP kernel per call
-(csrc/device_env.hip), bit for bit the host rule.
+definition of the rule) and ``CommandRoomDeviceVecEnv`` serves CommandRoom (environments/command_room_env.py) from device memory --
+step, auto-reset and rendering of all workers are ONE HIP kernel per call (csrc/device_env.hip), bit for bit the host rule.
 
 Two ways of stepping, over the same state:
 
@@ -14,6 +14,10 @@ Both return the step's rewards, dones and infos from result words the kernel wri
 on an EVENT recorded behind the launch, not on a completion word: the step's workgroups have no arrival counter (it would be the
 kernel's only atomic), so a word needs a second launch behind the step (the C entry offers it), and the event behind one launch was
 the shorter chain.
+
+``DeviceVecEnv`` holds everything that is not one task's: the buffers, the pinned result words, the event wait, both ways of stepping
+and the counters.  A task's class reads its section, names its action count and hands over its two C entries with the rule words
+they take behind ``W`` (``_bind``).
 """
 import numpy as np
 import torch
@@ -21,36 +25,31 @@ import torch
 from etm import lib as etm_lib
 
 
-class CueRoomDeviceVecEnv:
+class DeviceVecEnv:
     device_resident = True
     observation_dtype = np.uint8
+    TASK = None        # the environment type, for messages
 
-    def __init__(self, num_envs, grid=7, cell=12, cue_steps=2, max_episode_steps=32, seed=0, first_worker_id=0, device=None):
+    def _bind(self, num_envs, grid, cell, num_actions, max_episode_steps, seed, first_worker_id, device, entries, state_bytes, rule):
+        """Everything behind the task's own checks.  ``entries``: the names of the reset and the step entry; ``state_bytes``: the
+        name of the entry that sizes the state; ``rule``: the integers both entries take between ``W`` and the stream word."""
         from environments import ActionKind
-        from environments.cue_room_env import cue_room_section
-        sec = cue_room_section(dict(grid=grid, cell=cell, cue_steps=cue_steps, max_episode_steps=max_episode_steps, seed=seed))
-        if int(num_envs) < 1:
-            raise ValueError("CueRoomDeviceVecEnv needs at least one environment")
-        if not torch.cuda.is_available():
-            raise RuntimeError("environment.device: true needs the MI355X (the environments live in device memory): set device: false "
-                               "for the host twin")
-        self._etm = etm_lib.load()
-        self.grid, self.cell, self.cue_steps = sec["grid"], sec["cell"], sec["cue_steps"]
-        if not self._etm.etm_cue_room_supported(self.grid, self.cell):
-            raise ValueError(f"CueRoom: the kernel does not take grid {self.grid} with cell {self.cell}")
         self.num_envs = W = int(num_envs)
-        self.max_episode_steps = sec["max_episode_steps"]
-        side = self.grid * self.cell
+        self.grid, self.cell = grid, cell
+        self.max_episode_steps = int(max_episode_steps)
+        side = grid * cell
         self.observation_space_shape = (3, side, side)
-        self.action_kind = ActionKind("discrete", (4,))
-        self.action_space_shape = (4,)
-        self.num_actions = 4
-        self.stream0 = (sec["seed"] + int(first_worker_id)) & ((1 << 64) - 1)
+        self.action_kind = ActionKind("discrete", (num_actions,))
+        self.action_space_shape = (num_actions,)
+        self.num_actions = num_actions
+        self.stream0 = (seed + int(first_worker_id)) & ((1 << 64) - 1)
         if self.stream0 >= 1 << 63:
             self.stream0 -= 1 << 64          # (the C entry takes the 64-bit word as int64)
         self.device = dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.frame_bytes = 3 * side * side
-        self._state = torch.zeros(int(self._etm.etm_cue_room_state_bytes(W)) // 8, dtype=torch.int64, device=dev)
+        self._entry_names = tuple(entries)
+        self._reset_entry, self._step_entry = (getattr(self._etm, name) for name in entries)
+        self._state = torch.zeros(int(getattr(self._etm, state_bytes)(W)) // 8, dtype=torch.int64, device=dev)
         self._frames = torch.zeros((W,) + self.observation_space_shape, dtype=torch.uint8, device=dev)
         self._act_dev = torch.zeros(W, dtype=torch.int64, device=dev)
         self._act_pin = torch.zeros(W, dtype=torch.int64).pin_memory()
@@ -63,21 +62,30 @@ class CueRoomDeviceVecEnv:
         self._rewards_np, self._flags_np, self._returns_np = self._rewards.numpy(), self._flags.numpy(), self._returns.numpy()
         self._lengths_np, self._masks_np = self._lengths.numpy(), self._masks.numpy()
         self._words = tuple(t.data_ptr() for t in (self._rewards, self._flags, self._returns, self._lengths, self._masks))
-        self._rule = (W, self.grid, self.cell, self.cue_steps, self.max_episode_steps, self.stream0)
+        self._rule = (W,) + tuple(rule) + (self.stream0,)
         self._done_event = torch.cuda.Event()
         self.device_steps = 0          # calls of step_device (the trainer's fast path), for tests and tools
         self.protocol_steps = 0        # calls of step
+
+    @classmethod
+    def _load(cls, num_envs):
+        if int(num_envs) < 1:
+            raise ValueError(f"{cls.__name__} needs at least one environment")
+        if not torch.cuda.is_available():
+            raise RuntimeError("environment.device: true needs the MI355X (the environments live in device memory): set device: false "
+                               "for the host twin")
+        return etm_lib.load()
 
     # ---------------------------------------------------------------- launches
     def _run(self, actions_ptr, act_stride, frames_ptr, stream):
         """One launch on ``stream`` (a torch stream), then the host waits for its result words."""
         args = self._words + (None, 0) + self._rule + (stream.cuda_stream,)
         if actions_ptr is None:
-            rc = self._etm.etm_cue_room_reset(self._state.data_ptr(), frames_ptr, self.frame_bytes, *args)
+            rc = self._reset_entry(self._state.data_ptr(), frames_ptr, self.frame_bytes, *args)
         else:
-            rc = self._etm.etm_cue_room_step(self._state.data_ptr(), actions_ptr, act_stride, frames_ptr, self.frame_bytes, *args)
+            rc = self._step_entry(self._state.data_ptr(), actions_ptr, act_stride, frames_ptr, self.frame_bytes, *args)
         if rc != 0:
-            etm_lib.check(rc, "etm_cue_room_reset" if actions_ptr is None else "etm_cue_room_step")
+            etm_lib.check(rc, self._entry_names[0 if actions_ptr is None else 1])
         self._done_event.record(stream)
         self._done_event.synchronize()
 
@@ -109,8 +117,9 @@ class CueRoomDeviceVecEnv:
 
     def step(self, actions, out=None, on_rows=None):
         a = np.asarray(actions).reshape(self.num_envs, -1)[:, 0]
-        if a.min() < 0 or a.max() > 3:
-            raise ValueError(f"CueRoom: action {int(a[(a < 0) | (a > 3)][0])} is outside Discrete(4)")
+        top = self.num_actions - 1
+        if a.min() < 0 or a.max() > top:
+            raise ValueError(f"{self.TASK}: action {int(a[(a < 0) | (a > top)][0])} is outside Discrete({self.num_actions})")
         self._act_pin.numpy()[:] = a
         stream = torch.cuda.current_stream(self.device)
         with torch.cuda.stream(stream):
@@ -146,3 +155,36 @@ class CueRoomDeviceVecEnv:
 
     def close(self):
         return None
+
+
+class CueRoomDeviceVecEnv(DeviceVecEnv):
+    TASK = "CueRoom"
+
+    def __init__(self, num_envs, grid=7, cell=12, cue_steps=2, max_episode_steps=32, seed=0, first_worker_id=0, device=None):
+        from environments.cue_room_env import cue_room_section
+        sec = cue_room_section(dict(grid=grid, cell=cell, cue_steps=cue_steps, max_episode_steps=max_episode_steps, seed=seed))
+        self._etm = self._load(num_envs)
+        self.cue_steps = sec["cue_steps"]
+        if not self._etm.etm_cue_room_supported(sec["grid"], sec["cell"]):
+            raise ValueError(f"CueRoom: the kernel does not take grid {sec['grid']} with cell {sec['cell']}")
+        self._bind(num_envs, sec["grid"], sec["cell"], 4, sec["max_episode_steps"], sec["seed"], first_worker_id, device,
+                   ("etm_cue_room_reset", "etm_cue_room_step"), "etm_cue_room_state_bytes",
+                   (sec["grid"], sec["cell"], sec["cue_steps"], sec["max_episode_steps"]))
+
+
+class CommandRoomDeviceVecEnv(DeviceVecEnv):
+    TASK = "CommandRoom"
+
+    def __init__(self, num_envs, grid=7, cell=12, command_count=8, show_steps=1, gap_steps=1, seed=0, first_worker_id=0, device=None):
+        from environments.command_room_env import command_room_section
+        sec = command_room_section(dict(grid=grid, cell=cell, command_count=command_count, show_steps=show_steps, gap_steps=gap_steps,
+                                        seed=seed))
+        self._etm = self._load(num_envs)
+        self.command_count, self.show_steps, self.gap_steps = sec["command_count"], sec["show_steps"], sec["gap_steps"]
+        if not self._etm.etm_command_room_supported(sec["grid"], sec["cell"], self.command_count):
+            raise ValueError(f"CommandRoom: the kernel does not take grid {sec['grid']} with cell {sec['cell']} and "
+                             f"{self.command_count} commands")
+        K, L = self.command_count, self.show_steps + self.gap_steps
+        self._bind(num_envs, sec["grid"], sec["cell"], 5, K * L + K, sec["seed"], first_worker_id, device,
+                   ("etm_command_room_reset", "etm_command_room_step"), "etm_command_room_state_bytes",
+                   (sec["grid"], sec["cell"], K, self.show_steps, self.gap_steps))

@@ -1,0 +1,50 @@
+"""The environment types that have a device-resident front-end, as ONE table: what ``utils.create_env``, ``vec_env.make_vec_env``,
+``cue_room_env.check_device_env_config`` and ``trainer.check_byte_observation_transport`` ask about a ``type`` is looked up here, so
+no type is spelled in their code.  All of these types emit uint8 frames only (no float form) and take ``device: true``.
+
+An entry names the rule's module (under ``environments``), its section reader, its host class and its front-end class (in
+``environments/device_env.py``); everything is imported on use, so reading the table needs neither torch nor the native library.
+The host class and the front-end take the section's keys (without ``device``) as keyword arguments.
+"""
+import importlib
+from collections import namedtuple
+
+DeviceEnvType = namedtuple("DeviceEnvType", "module section host_class front_end")
+
+DEVICE_ENV_TYPES = {
+    "CueRoom": DeviceEnvType("environments.cue_room_env", "cue_room_section", "CueRoomEnv", "CueRoomDeviceVecEnv"),
+    "CommandRoom": DeviceEnvType("environments.command_room_env", "command_room_section", "CommandRoomEnv", "CommandRoomDeviceVecEnv"),
+}
+
+
+def is_byte_only(kind) -> bool:
+    """Whether environments of this ``type`` emit uint8 observations whatever ``observation_dtype`` says (they have no float form)."""
+    return kind in DEVICE_ENV_TYPES
+
+
+def device_env_section(env_config: dict):
+    """The checked section of a config whose type is in the table (the type's own reader: defaults filled, refusals raised) -> dict
+    with ``device`` among its keys; None for every other type."""
+    entry = DEVICE_ENV_TYPES.get(env_config.get("type"))
+    if entry is None:
+        return None
+    return getattr(importlib.import_module(entry.module), entry.section)(env_config)
+
+
+def _arguments(sec: dict) -> dict:
+    return {k: v for k, v in sec.items() if k != "device"}
+
+
+def make_host_env(env_config: dict, worker_id: int = 0):
+    """The host twin (one environment) of a type in the table; ``device`` means nothing to a single environment."""
+    entry = DEVICE_ENV_TYPES[env_config["type"]]
+    sec = device_env_section(env_config)
+    return getattr(importlib.import_module(entry.module), entry.host_class)(worker_id=worker_id, **_arguments(sec))
+
+
+def make_device_vec_env(env_config: dict, num_envs: int, first_worker_id: int = 0):
+    """The device-resident front-end of a type in the table (``device: true`` was asked for)."""
+    entry = DEVICE_ENV_TYPES[env_config["type"]]
+    sec = device_env_section(env_config)
+    cls = getattr(importlib.import_module("environments.device_env"), entry.front_end)
+    return cls(num_envs, first_worker_id=first_worker_id, **_arguments(sec))

@@ -37,8 +37,8 @@ is exactly what upstream's loop does by hand (trainer.py:195-201).
 * ``SerialVecEnv``  -- wraps in-process single envs with the upstream env API.
 * ``PipeVecEnv``    -- wraps upstream-protocol ``Worker`` subprocesses (worker.py), one pipe round trip per step.
 * ``environments.synthetic.SyntheticVecEnv`` implements the protocol natively.
-* ``environments.device_env.CueRoomDeviceVecEnv`` (``type: CueRoom`` with ``device: true``) implements it over environments that live in
-  device memory, and declares ``device_resident = True``: ``step_device(actions_dev, rows_dev, stream) -> (rewards, dones, infos)`` steps
+* ``environments.device_env.CueRoomDeviceVecEnv`` / ``CommandRoomDeviceVecEnv`` (the types of environments/device_types.py with
+  ``device: true``) implement it over environments that live in device memory, and declare ``device_resident = True``: ``step_device(actions_dev, rows_dev, stream) -> (rewards, dones, infos)`` steps
   them from the device's action table straight into the given device rows (the trainer's streamed plans use it).
 """
 import numpy as np
@@ -249,12 +249,10 @@ def make_vec_env(env_config: dict, num_envs: int, first_worker_id: int = 0, grou
         if "obs_shape" in kw:
             kw["obs_shape"] = tuple(kw["obs_shape"])
         return SyntheticVecEnv(num_envs, first_worker_id=first_worker_id, **kw)
-    if env_config["type"] == "CueRoom":
-        from environments.cue_room_env import cue_room_section
-        sec = cue_room_section(env_config)
-        if sec["device"]:       # the device-resident front-end: the rule as one HIP kernel per step (environments/device_env.py)
-            from environments.device_env import CueRoomDeviceVecEnv
-            return CueRoomDeviceVecEnv(num_envs, first_worker_id=first_worker_id, **{k: v for k, v in sec.items() if k != "device"})
+    from environments.device_types import device_env_section, make_device_vec_env
+    sec = device_env_section(env_config)        # (None unless the type has a device-resident front-end: CueRoom, CommandRoom)
+    if sec is not None and sec["device"]:       # the rule as one HIP kernel per step (environments/device_env.py)
+        return make_device_vec_env(env_config, num_envs, first_worker_id)
     if env_config.get("vectorize", "pipe") == "serial":
         from utils import create_env
         return SerialVecEnv([create_env(env_config, worker_id=first_worker_id + w) for w in range(num_envs)])

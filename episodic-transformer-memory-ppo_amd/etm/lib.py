@@ -245,6 +245,11 @@ SIGNATURES["etm_cue_room_supported"] = (_I, [_I, _I])
 SIGNATURES["etm_cue_room_state_bytes"] = (_L, [_I])
 SIGNATURES["etm_cue_room_reset"] = (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P])
 SIGNATURES["etm_cue_room_step"] = (_I, [_P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P])
+# CommandRoom, the second device-resident task (same file, same shape of entry; one more rule word: K, show_steps, gap_steps)
+SIGNATURES["etm_command_room_supported"] = (_I, [_I, _I, _I])
+SIGNATURES["etm_command_room_state_bytes"] = (_L, [_I])
+SIGNATURES["etm_command_room_reset"] = (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _L, _P])
+SIGNATURES["etm_command_room_step"] = (_I, [_P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _L, _P])
 del _twin
 del _name, _extra, _res, _args
 

@@ -45,6 +45,7 @@ def default_rollout_groups(num_workers: int, min_group: int) -> int:
 from buffer import Buffer
 from environments import action_space_kind, branch_bit_masks, empty_mask_branches, valid_action_share
 from environments.cue_room_env import check_device_env_config
+from environments.device_types import is_byte_only
 from environments.vec_env import make_vec_env
 from etm import lib as etm_lib
 from etm import ops
@@ -134,7 +135,7 @@ def check_byte_observation_transport(config, env=None):
     """``worker_processes: true`` with ``observation_dtype: uint8`` is refused, before any environment or process is created: the
     workers' shared segment types its observation rows as float32 (environments/shm_env.py)."""
     env_cfg = config["environment"]
-    as_bytes = str(env_cfg.get("observation_dtype", "float32")) == "uint8" or env_cfg.get("type") == "CueRoom"      # (CueRoom has no float form)
+    as_bytes = str(env_cfg.get("observation_dtype", "float32")) == "uint8" or is_byte_only(env_cfg.get("type"))      # (types with no float form)
     if env is None and config.get("worker_processes", False) and as_bytes:
         raise ValueError("worker_processes: true does not carry uint8 observations (the shared segment's rows are float32): "
                          "set worker_processes: false (in-process environments keep the bytes), or let the environment emit float32")
@@ -364,7 +365,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         check_box_policy(config)
         check_byte_observation_transport(config, env)
         check_truncation_transport(config, env)
-        if env is None:       # environment.device: true (CueRoom on the device) against the transports and the world size
+        if env is None:       # environment.device: true (a device-resident type) against the transports and the world size
             check_device_env_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         check_action_mask_config(config, env)
         # previous_step_input: the value itself and the transport, before any environment or process is created (the shared segment of

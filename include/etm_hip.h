@@ -1003,6 +1003,28 @@ int etm_cue_room_step(void *state, const int64_t *actions, int64_t act_stride, u
                       uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W,
                       int G, int P, int cue_steps, int max_steps, int64_t stream0, void *stream);
 
+/* CommandRoom (same file, added with the ABI left at 61): the command-sequence memory task whose one host definition is
+ * environments/command_room_env.py -- K commands (up, right, down, left, stay) are shown one after the other, show_steps observations
+ * each with gap_steps floor-only observations between, then executed from memory, one per step.  Same launch shape, outputs, order of
+ * outputs, completion word and alignment rules as etm_cue_room_*; the state is 32 bytes per environment (episode u64, packed commands
+ * u64 with 3 bits each, row, col, observation index t, commands completed n).
+ *   etm_command_room_supported: 1 where etm_cue_room_supported(G, P) and 1 <= K <= 16, else 0.
+ *   etm_command_room_step: actions outside 0 .. 4 are clamped (the host rule raises).  rewards: 0.1f for the correct command in the
+ *       execute phase, else 0; flags: bit 0 done, bit 2 success (all K commands executed), bit 1 never set (no time limit); returns:
+ *       float(n) * 0.1f of the episode that ended, one multiply; lengths: its steps; masks: all five bits while commands are shown,
+ *       else bit a set when move a stays on the grid and bit 4 (stay).
+ * Integer arithmetic apart from the reward constant and that multiply, no atomics: two calls from equal state give equal bytes.
+ * ETM_EINVAL, with nothing launched: the classes of etm_cue_room_*, (G, P, K) outside etm_command_room_supported, show_steps < 1,
+ * gap_steps < 0. */
+int etm_command_room_supported(int G, int P, int K);
+int64_t etm_command_room_state_bytes(int W);
+int etm_command_room_reset(void *state, uint8_t *frames, int64_t frame_pitch, float *rewards, uint8_t *flags, float *returns,
+                           int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P, int K,
+                           int show_steps, int gap_steps, int64_t stream0, void *stream);
+int etm_command_room_step(void *state, const int64_t *actions, int64_t act_stride, uint8_t *frames, int64_t frame_pitch, float *rewards,
+                          uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W,
+                          int G, int P, int K, int show_steps, int gap_steps, int64_t stream0, void *stream);
+
 /* Monitored gradient norms of the module groups (model.py:128-151) from the flat gradient arena in two launches:
  * out[g] = sqrt(sum_s member[g][s] * ||flat[seg_start[s] .. seg_start[s] + seg_len[s])||^2).  Segments: runs of <= 4096 floats, each
  * inside one parameter tensor (device arrays seg_start int64 [n_segs], seg_len int32 [n_segs]); member [n_groups, n_segs] float

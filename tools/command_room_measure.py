@@ -1,0 +1,171 @@
+"""Measurements behind the README section on CommandRoom (profiles/r23/command_room.txt).  Needs the MI355X.
+
+  python tools/command_room_measure.py kernel [--steps 500] [--rounds 3]
+      etm_command_room_step next to etm_cue_room_step (the yardstick) in one process, at 84 x 84 (grid 7, cell 12) and W in
+      {16, 64, 1024}: device time per step between two events around ``steps`` back-to-back launches on one stream (frames to device
+      memory, result words to pinned host memory), after a warm-up; ``rounds`` alternated rounds, every round printed.
+  python tools/command_room_measure.py rollout [--pairs 5] [--rollouts 3]
+      the rollout phase of configs/command_room_device.yaml against configs/command_room.yaml (the host twin stepped serially) and
+      against the ``Synthetic`` uint8 config of equal shape and action count, the floor a host environment that costs nothing
+      reaches.  All trainers alive in one process, one warm-up rollout each (it captures the step graphs), then ``pairs`` alternated
+      rounds of ``rollouts`` rollouts: seconds per rollout and environment steps per second, range and median, with the trainer's
+      own split (env.step, waiting for the actions, upload + launch).
+  python tools/command_room_measure.py behaviour [--updates 200]
+      configs/command_room_device.yaml for ``updates`` updates, then once more with ``memory_length`` cut to ``command_count``:
+      success rate and mean commands completed of the episodes that ended in the first and the last tenth of the run, beside what a
+      uniformly random policy reaches (no assertion).
+"""
+import argparse
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "episodic-transformer-memory-ppo_amd")
+sys.path[:0] = [REPO, PKG]
+os.environ.setdefault("ETM_QUIET", "1")
+
+import numpy as np      # noqa: E402
+import torch            # noqa: E402
+
+
+def _config(name, **env_over):
+    from yaml_parser import YamlParser
+    cfg = YamlParser(os.path.join(PKG, "configs", name + ".yaml")).get_config()
+    cfg["environment"].update(env_over)
+    cfg["tunable_gemm"] = False
+    return cfg
+
+
+def _trainer(cfg, run_id):
+    from trainer import PPOTrainer
+    torch.manual_seed(0)
+    return PPOTrainer(cfg, run_id=run_id, device=torch.device("cuda", 0), tensorboard=False)
+
+
+def kernel(args):
+    from etm import lib as etm_lib
+    lib = etm_lib.load()
+    G, P, dev = 7, 12, torch.device("cuda", 0)
+    fb = 3 * (G * P) ** 2
+    # (name, reset entry, step entry, state bytes, rule words behind W, actions): CueRoom's kernel is the yardstick
+    tasks = [("etm_cue_room_step", lib.etm_cue_room_reset, lib.etm_cue_room_step, lib.etm_cue_room_state_bytes, (G, P, 2, 32, 0), 4),
+             ("etm_command_room_step", lib.etm_command_room_reset, lib.etm_command_room_step, lib.etm_command_room_state_bytes,
+              (G, P, 8, 1, 1, 0), 5)]
+    for W in (16, 64, 1024):
+        frames = torch.zeros((W, fb), dtype=torch.uint8, device=dev)
+        words = [torch.zeros(W, dtype=dt).pin_memory() for dt in (torch.float32, torch.uint8, torch.float32, torch.int32, torch.int64)]
+        ptrs = [t.data_ptr() for t in words]
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        runs = []
+        for name, reset, step, state_bytes, rule, n_act in tasks:
+            state = torch.zeros(int(state_bytes(W)) // 8, dtype=torch.int64, device=dev)
+            actions = torch.from_numpy(np.random.default_rng(0).integers(0, n_act, size=(8, W))).to(dev)
+            etm_lib.check(reset(state.data_ptr(), frames.data_ptr(), fb, *ptrs, None, 0, W, *rule, stream), name + " (reset)")
+
+            def run(n, step=step, state=state, actions=actions, rule=rule, name=name):
+                for i in range(n):
+                    rc = step(state.data_ptr(), actions[i % 8].data_ptr(), 1, frames.data_ptr(), fb, *ptrs, None, 0, W, *rule, stream)
+                    if rc != 0:
+                        etm_lib.check(rc, name)
+            run(50)
+            torch.cuda.synchronize()
+            runs.append((name, run, []))
+        for _ in range(args.rounds):
+            for name, run, us in runs:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                run(args.steps)
+                b.record()
+                torch.cuda.synchronize()
+                us.append(a.elapsed_time(b) * 1000.0 / args.steps)
+        for name, _, us in runs:
+            med = float(np.median(us))
+            print(f"{name} 84x84 W={W}: {' / '.join(f'{u:.2f}' for u in us)} us per step over {args.steps} back-to-back launches (events, "
+                  f"{args.rounds} alternated rounds), median {med:.2f} us = {W * fb / med / 1e3:.1f} GB/s of frame bytes written", flush=True)
+
+
+def rollout(args):
+    base = _config("command_room")
+    W, S = base["n_workers"], base["worker_steps"]
+    env = base["environment"]
+    longest = env["command_count"] * (env["show_steps"] + env["gap_steps"] + 1)
+    synthetic = dict(type="Synthetic", obs_shape=[3, env["grid"] * env["cell"], env["grid"] * env["cell"]], num_actions=5,
+                     max_episode_steps=longest, seed=0, p_reward=0.05, p_done=0.05, pool=64, observation_levels=256,
+                     observation_dtype="uint8")
+    floor = dict(base, environment=synthetic)
+    runs = [("device", _config("command_room_device")), ("host serial", _config("command_room", vectorize="serial")),
+            ("Synthetic uint8 floor", floor)]
+    trainers = [(name, _trainer(cfg, "measure_" + name.split()[0])) for name, cfg in runs]
+    times = {name: [] for name, _ in trainers}
+    split = {name: [] for name, _ in trainers}
+    try:
+        for name, tr in trainers:
+            tr._sample_training_data()
+            torch.cuda.synchronize()
+            print(f"{name}: plan {tr._plan}", flush=True)
+        for _ in range(args.pairs):
+            for name, tr in trainers:
+                for _ in range(args.rollouts):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    tr._sample_training_data()
+                    torch.cuda.synchronize()
+                    times[name].append(time.perf_counter() - t0)
+                    t = tr.last_update_timing
+                    split[name].append((t["env_s"], t["wait_s"], t["launch_s"]))
+    finally:
+        for _, tr in trainers:
+            tr.close()
+    print(f"rollout phase, W = {W}, S = {S}, {args.pairs} alternated rounds of {args.rollouts} rollouts each:")
+    for name, _ in trainers:
+        x, sp = np.asarray(times[name]), np.median(np.asarray(split[name]), axis=0)
+        print(f"  {name:24s} {1e3 * x.min():7.1f} .. {1e3 * x.max():7.1f} ms per rollout, median {1e3 * np.median(x):7.1f} ms = "
+              f"{W * S / np.median(x):9.0f} env-steps/s; medians of env.step / wait / launch: {1e3 * sp[0]:.1f} / {1e3 * sp[1]:.1f} / "
+              f"{1e3 * sp[2]:.1f} ms", flush=True)
+
+
+def behaviour(args):
+    K = _config("command_room_device")["environment"]["command_count"]
+    # a policy uniform over the five actions answers command e correctly with probability 1 / 5, whatever the command
+    chance_n, chance_success = sum(0.2 ** k for k in range(1, K + 1)), 0.2 ** K
+    for window in (None, K):
+        cfg = _config("command_room_device")
+        if window is not None:
+            cfg["transformer"]["memory_length"] = window
+        tr = _trainer(cfg, "command_room_behaviour")
+        ended = []
+        t0 = time.perf_counter()
+        for update in range(args.updates):
+            lr, beta, clip = tr.schedules(update)
+            infos = tr._sample_training_data()
+            tr.buffer.prepare_batch_dict()
+            tr._train_epochs(lr, clip, beta)
+            tr.update_index += 1
+            ended.append((sum(i["success"] for i in infos), len(infos), sum(round(i["reward"] * 10) for i in infos)))
+        torch.cuda.synchronize()
+        e = np.asarray(ended, dtype=np.float64)
+        k = max(1, args.updates // 10)
+        first, last = e[:k].sum(axis=0), e[-k:].sum(axis=0)
+        print(f"command_room_device memory_length={cfg['transformer']['memory_length']}: {args.updates} updates in "
+              f"{time.perf_counter() - t0:.0f} s; first {k} updates: success {100 * first[0] / first[1]:.2f} %, "
+              f"{first[2] / first[1]:.2f} of {K} commands completed on average ({int(first[1])} episodes); last {k} updates: success "
+              f"{100 * last[0] / last[1]:.2f} %, {last[2] / last[1]:.2f} commands ({int(last[1])} episodes); a uniformly random policy: "
+              f"success {100 * chance_success:.4f} %, {chance_n:.2f} commands", flush=True)
+        tr.close()
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    sub = ap.add_subparsers(dest="what", required=True)
+    k = sub.add_parser("kernel")
+    k.add_argument("--steps", type=int, default=500)
+    k.add_argument("--rounds", type=int, default=3)
+    r = sub.add_parser("rollout")
+    r.add_argument("--pairs", type=int, default=5)
+    r.add_argument("--rollouts", type=int, default=3)
+    b = sub.add_parser("behaviour")
+    b.add_argument("--updates", type=int, default=200)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the MI355X"
+    {"kernel": kernel, "rollout": rollout, "behaviour": behaviour}[args.what](args)
