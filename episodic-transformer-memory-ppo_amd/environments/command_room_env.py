@@ -29,7 +29,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from environments.cue_room_env import MAX_CELL, MAX_GRID, encoder_takes, splitmix64
+from environments.grid_room import check_encoder_side, episode_hash, paint, read_device, read_integers, splitmix64
 
 # flat colours (R, G, B) by what a cell shows
 FLOOR, MARK, POINTER, AGENT = 0, 1, 2, 3
@@ -39,13 +39,13 @@ MOVES = ((-1, 0), (0, 1), (1, 0), (0, -1), (0, 0))
 MAX_COMMANDS = 16                  # what the kernel admits (etm_command_room_supported): 3 bits each in one 64-bit word
 REWARD = np.float32(0.1)
 
-KEYS = ("type", "grid", "cell", "command_count", "show_steps", "gap_steps", "seed", "device", "vectorize")
-_MASK64 = (1 << 64) - 1
+DEFAULTS = dict(grid=7, cell=12, command_count=8, show_steps=1, gap_steps=1, seed=0)
+KEYS = ("type", *DEFAULTS, "device", "vectorize")
 
 
 def episode_draw(stream: int, episode: int, G: int, K: int):
     """(start row, start column, the K commands) of episode ``episode`` of the worker stream ``stream`` (= seed + worker_id)."""
-    h = splitmix64((splitmix64(int(stream) & _MASK64) + int(episode)) & _MASK64)
+    h = episode_hash(stream, episode)
     start = (h >> 8) % (G * G)
     row, col = start // G, start % G
     r, c, x, commands = row, col, h, []
@@ -71,23 +71,9 @@ def command_room_section(env_config: dict) -> dict:
     "seed", "device"} with the defaults (7, 12, 8, 1, 1, 0, False) filled in.  Refused, each with what to do instead: unknown
     sub-keys, non-integers, an even grid or one outside 3 .. 31, a cell that is no multiple of 4 in 4 .. 64, a side grid * cell the
     encoder cannot take, command_count outside 1 .. 16, show_steps < 1, gap_steps < 0, a ``device`` that is no bool."""
-    unknown = sorted(set(env_config) - set(KEYS))
-    if unknown:
-        raise ValueError(f"environment (CommandRoom): unknown keys {unknown} (known: {sorted(KEYS)}); remove them")
-    G, P, K = env_config.get("grid", 7), env_config.get("cell", 12), env_config.get("command_count", 8)
-    show, gap, seed = env_config.get("show_steps", 1), env_config.get("gap_steps", 1), env_config.get("seed", 0)
-    for name, v in (("grid", G), ("cell", P), ("command_count", K), ("show_steps", show), ("gap_steps", gap), ("seed", seed)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"environment.{name} (CommandRoom) must be an integer, got {v!r}")
-    if G < 3 or G % 2 == 0 or G > MAX_GRID:
-        raise ValueError(f"environment.grid must be odd and between 3 and {MAX_GRID} (the commands are shown around a centre cell), got "
-                         f"{G}: use {max(3, min(MAX_GRID, G + 1 - G % 2 if G >= 3 else 3))}")
-    if P < 4 or P % 4 != 0 or P > MAX_CELL:
-        raise ValueError(f"environment.cell must be a multiple of 4 between 4 and {MAX_CELL} (frames are written in 4-byte words that "
-                         f"never straddle two cells), got {P}: use {max(4, min(MAX_CELL, (P + 3) // 4 * 4))}")
-    if not encoder_takes(G * P):
-        raise ValueError(f"environment: a {G * P} x {G * P} frame (grid {G} x cell {P}) is too small for the image encoder (8x8/4, 4x4/2, "
-                         "3x3/1 need a side of at least 36): raise grid or cell")
+    sec = read_integers("CommandRoom", env_config, KEYS, DEFAULTS, "the commands are shown around a centre cell")
+    check_encoder_side(sec["grid"], sec["cell"])
+    K, show, gap = sec["command_count"], sec["show_steps"], sec["gap_steps"]
     if K < 1 or K > MAX_COMMANDS:
         raise ValueError(f"environment.command_count must be between 1 and {MAX_COMMANDS} (the sequence is one 64-bit word, 3 bits per "
                          f"command), got {K}: use {max(1, min(MAX_COMMANDS, K))}")
@@ -96,10 +82,7 @@ def command_room_section(env_config: dict) -> dict:
                          "use 1")
     if gap < 0:
         raise ValueError(f"environment.gap_steps must be at least 0, got {gap}: use 0 for commands shown back to back")
-    dev = env_config.get("device", False)
-    if not isinstance(dev, bool):
-        raise ValueError(f"environment.device must be true or false, got {dev!r}")
-    return dict(grid=int(G), cell=int(P), command_count=int(K), show_steps=int(show), gap_steps=int(gap), seed=int(seed), device=dev)
+    return dict(sec, device=read_device(env_config))
 
 
 def shown(t: int, K: int, show_steps: int, gap_steps: int):
@@ -121,11 +104,7 @@ def render(G: int, P: int, phase: str, command: int, row: int, col: int, out=Non
             cells[mid + MOVES[command][0], mid + MOVES[command][1]] = POINTER
     elif phase == "execute":
         cells[row, col] = AGENT
-    frame = PALETTE[cells].transpose(2, 0, 1).repeat(P, axis=1).repeat(P, axis=2)      # [G, G, 3] -> [3, G P, G P]
-    if out is None:
-        return np.ascontiguousarray(frame)
-    out[...] = frame
-    return out
+    return paint(PALETTE, cells, P, out)
 
 
 class CommandRoomEnv:

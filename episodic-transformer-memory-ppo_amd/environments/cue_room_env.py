@@ -22,23 +22,19 @@ from types import SimpleNamespace
 
 import numpy as np
 
+# (importable from here as before, defined where they belong: the mixer with the rooms' shared code, the check beside the type table)
+from environments.device_types import check_device_env_config  # noqa: F401
+from environments.grid_room import splitmix64  # noqa: F401
+from environments.grid_room import check_encoder_side, episode_hash, paint, read_device, read_integers
+
 # flat colours (R, G, B) by what a cell shows; the agent is drawn last
 FLOOR, GOAL, CUE, AGENT = 0, 1, 2, 3
 PALETTE = np.array([[24, 24, 32], [64, 160, 64], [240, 208, 32], [224, 48, 48]], dtype=np.uint8)
 # (row, column) steps of the four moves: up, right, down, left
 MOVES = ((-1, 0), (0, 1), (1, 0), (0, -1))
-MAX_GRID, MAX_CELL = 31, 64        # what the kernel admits (etm_cue_room_supported)
 
-KEYS = ("type", "grid", "cell", "cue_steps", "max_episode_steps", "seed", "device", "vectorize")
-_MASK64 = (1 << 64) - 1
-
-
-def splitmix64(x: int) -> int:
-    """One step of splitmix64 on a 64-bit word (Python integers reduced mod 2^64: what uint64 arithmetic does)."""
-    z = (int(x) + 0x9E3779B97F4A7C15) & _MASK64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
-    return z ^ (z >> 31)
+DEFAULTS = dict(grid=7, cell=12, cue_steps=2, max_episode_steps=32, seed=0)
+KEYS = ("type", *DEFAULTS, "device", "vectorize")
 
 
 def corner_cells(G: int):
@@ -50,7 +46,7 @@ def episode_draw(stream: int, episode: int, G: int):
     """(target corner, start row, start column) of episode ``episode`` of the worker stream ``stream`` (= seed + worker_id).
     h = splitmix64(splitmix64(stream) + episode); target = h & 3; the start is non-corner cell (h >> 8) mod (G G - 4) in row-major
     order with the corners left out."""
-    h = splitmix64((splitmix64(int(stream) & _MASK64) + int(episode)) & _MASK64)
+    h = episode_hash(stream, episode)
     target = h & 3
     c = (h >> 8) % (G * G - 4) + 1        # row-major index with the corners skipped: past (0, 0) ...
     if c >= G - 1:                        # ... past (0, G - 1) ...
@@ -60,64 +56,19 @@ def episode_draw(stream: int, episode: int, G: int):
     return int(target), int(c // G), int(c % G)
 
 
-def encoder_takes(side: int) -> bool:
-    """The model's image encoder (8x8 stride 4, 4x4 stride 2, 3x3 stride 1, no padding) leaves at least one position."""
-    o1 = (side - 8) // 4 + 1 if side >= 8 else 0
-    o2 = (o1 - 4) // 2 + 1 if o1 >= 4 else 0
-    return o2 - 2 >= 1
-
-
 def cue_room_section(env_config: dict) -> dict:
     """The ``environment`` section of a ``type: CueRoom`` config -> {"grid", "cell", "cue_steps", "max_episode_steps", "seed",
     "device"} with the defaults (7, 12, 2, 32, 0, False) filled in.  Refused, each with what to do instead: unknown sub-keys, an even
     grid or one below 3 (or above what the kernel admits), a cell that is no multiple of 4, cue_steps < 1, max_episode_steps < 1, a
     side grid * cell the encoder cannot take."""
-    unknown = sorted(set(env_config) - set(KEYS))
-    if unknown:
-        raise ValueError(f"environment (CueRoom): unknown keys {unknown} (known: {sorted(KEYS)}); remove them")
-    G, P = env_config.get("grid", 7), env_config.get("cell", 12)
-    cue, T = env_config.get("cue_steps", 2), env_config.get("max_episode_steps", 32)
-    for name, v in (("grid", G), ("cell", P), ("cue_steps", cue), ("max_episode_steps", T), ("seed", env_config.get("seed", 0))):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"environment.{name} (CueRoom) must be an integer, got {v!r}")
-    if G < 3 or G % 2 == 0 or G > MAX_GRID:
-        raise ValueError(f"environment.grid must be odd and between 3 and {MAX_GRID} (the corners and a centre need it), got {G}: "
-                         f"use {max(3, min(MAX_GRID, G + 1 - G % 2 if G >= 3 else 3))}")
-    if P < 4 or P % 4 != 0 or P > MAX_CELL:
-        raise ValueError(f"environment.cell must be a multiple of 4 between 4 and {MAX_CELL} (frames are written in 4-byte words that "
-                         f"never straddle two cells), got {P}: use {max(4, min(MAX_CELL, (P + 3) // 4 * 4))}")
-    if cue < 1:
-        raise ValueError(f"environment.cue_steps must be at least 1 (observation 0 is the only one that can show the cue then), got {cue}")
-    if T < 1:
-        raise ValueError(f"environment.max_episode_steps must be at least 1, got {T}")
-    if not encoder_takes(G * P):
-        raise ValueError(f"environment: a {G * P} x {G * P} frame (grid {G} x cell {P}) is too small for the image encoder (8x8/4, 4x4/2, "
-                         "3x3/1 need a side of at least 36): raise grid or cell")
-    dev = env_config.get("device", False)
-    if not isinstance(dev, bool):
-        raise ValueError(f"environment.device must be true or false, got {dev!r}")
-    return dict(grid=int(G), cell=int(P), cue_steps=int(cue), max_episode_steps=int(T), seed=int(env_config.get("seed", 0)), device=dev)
-
-
-def check_device_env_config(config: dict, world: int = 1) -> bool:
-    """``environment.device: true`` against the rest of the config, before anything is built -> whether the key is on.  Refused:
-    ``worker_processes: true`` (the environments live on the device, no process steps them), ``bootstrap_truncated: true`` (the
-    front-end keeps no final observation) and a data-parallel run (``world`` > 1: not built, not measured).  Every type of
-    environments/device_types.py is covered alike."""
-    from environments.device_types import device_env_section
-    sec = device_env_section(config.get("environment", {}))
-    if sec is None or not sec["device"]:
-        return False
-    if config.get("worker_processes", False):
-        raise ValueError("environment.device: true keeps the environments on the device, worker_processes: true in host processes: set "
-                         "worker_processes: false, or device: false to step the host twin in the worker processes")
-    if config.get("bootstrap_truncated", False):
-        raise ValueError("environment.device: true does not carry bootstrap_truncated: true (the device front-end keeps no final "
-                         "observation): set device: false (the host twin hands it over in its info), or leave bootstrap_truncated off")
-    if int(world) > 1:
-        raise ValueError("environment.device: true is not built for data-parallel runs (every rank would need its own worker streams and "
-                         "nothing here has run more than one rank): run one rank, or set device: false")
-    return True
+    sec = read_integers("CueRoom", env_config, KEYS, DEFAULTS, "the corners and a centre need it")
+    if sec["cue_steps"] < 1:
+        raise ValueError("environment.cue_steps must be at least 1 (observation 0 is the only one that can show the cue then), got "
+                         f"{sec['cue_steps']}")
+    if sec["max_episode_steps"] < 1:
+        raise ValueError(f"environment.max_episode_steps must be at least 1, got {sec['max_episode_steps']}")
+    check_encoder_side(sec["grid"], sec["cell"])
+    return dict(sec, device=read_device(env_config))
 
 
 def render(G: int, P: int, row: int, col: int, target: int, cue_visible: bool, out=None):
@@ -126,11 +77,7 @@ def render(G: int, P: int, row: int, col: int, target: int, cue_visible: bool, o
     for k, (r, c) in enumerate(corner_cells(G)):
         cells[r, c] = CUE if cue_visible and k == target else GOAL
     cells[row, col] = AGENT
-    frame = PALETTE[cells].transpose(2, 0, 1).repeat(P, axis=1).repeat(P, axis=2)      # [G, G, 3] -> [3, G P, G P]
-    if out is None:
-        return np.ascontiguousarray(frame)
-    out[...] = frame
-    return out
+    return paint(PALETTE, cells, P, out)
 
 
 class CueRoomEnv:

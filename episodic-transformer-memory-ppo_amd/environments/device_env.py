@@ -16,40 +16,59 @@ kernel's only atomic), so a word needs a second launch behind the step (the C en
 the shorter chain.
 
 ``DeviceVecEnv`` holds everything that is not one task's: the buffers, the pinned result words, the event wait, both ways of stepping
-and the counters.  A task's class reads its section, names its action count and hands over its two C entries with the rule words
-they take behind ``W`` (``_bind``).
+and the counters, and opens them (``_open``: section, library, the kernel's own refusal, buffers).  A task's class is four attributes
+-- its name, its action count, the prefix of its C entries, its section reader -- a constructor with its keys, and ``_rule_of``.
 """
 import numpy as np
 import torch
 
+from environments.command_room_env import command_room_section
+from environments.cue_room_env import cue_room_section
 from etm import lib as etm_lib
 
 
 class DeviceVecEnv:
     device_resident = True
     observation_dtype = np.uint8
-    TASK = None        # the environment type, for messages
+    TASK = None            # the environment type, for messages
+    NUM_ACTIONS = None     # Discrete(n)
+    ENTRY = None           # the C entries are ENTRY + "_supported", "_state_bytes", "_reset", "_step"
+    SECTION = None         # the type's section reader (a staticmethod)
 
-    def _bind(self, num_envs, grid, cell, num_actions, max_episode_steps, seed, first_worker_id, device, entries, state_bytes, rule):
-        """Everything behind the task's own checks.  ``entries``: the names of the reset and the step entry; ``state_bytes``: the
-        name of the entry that sizes the state; ``rule``: the integers both entries take between ``W`` and the stream word."""
+    def _rule_of(self, sec):
+        """The checked section -> (the integers both entries take between ``W`` and the stream word, the arguments of the
+        ``_supported`` entry, max_episode_steps); keeps the task's own keys as attributes."""
+        raise NotImplementedError
+
+    def _open(self, num_envs, first_worker_id, device, **keys):
+        """Everything behind a task's constructor: the checked section, the library, the kernel's own refusal, the buffers."""
         from environments import ActionKind
+        sec = self.SECTION(keys)
+        if int(num_envs) < 1:
+            raise ValueError(f"{type(self).__name__} needs at least one environment")
+        if not torch.cuda.is_available():
+            raise RuntimeError("environment.device: true needs the MI355X (the environments live in device memory): set device: false "
+                               "for the host twin")
+        self._etm = etm_lib.load()
+        rule, supported, max_episode_steps = self._rule_of(sec)
+        if not getattr(self._etm, self.ENTRY + "_supported")(*supported):
+            raise ValueError(f"{self.TASK}: the kernel does not take {self.ENTRY}_supported{tuple(supported)}")
         self.num_envs = W = int(num_envs)
-        self.grid, self.cell = grid, cell
+        self.grid, self.cell = sec["grid"], sec["cell"]
         self.max_episode_steps = int(max_episode_steps)
-        side = grid * cell
+        side = self.grid * self.cell
         self.observation_space_shape = (3, side, side)
+        self.num_actions = num_actions = self.NUM_ACTIONS
         self.action_kind = ActionKind("discrete", (num_actions,))
         self.action_space_shape = (num_actions,)
-        self.num_actions = num_actions
-        self.stream0 = (seed + int(first_worker_id)) & ((1 << 64) - 1)
+        self.stream0 = (sec["seed"] + int(first_worker_id)) & ((1 << 64) - 1)
         if self.stream0 >= 1 << 63:
             self.stream0 -= 1 << 64          # (the C entry takes the 64-bit word as int64)
         self.device = dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.frame_bytes = 3 * side * side
-        self._entry_names = tuple(entries)
-        self._reset_entry, self._step_entry = (getattr(self._etm, name) for name in entries)
-        self._state = torch.zeros(int(getattr(self._etm, state_bytes)(W)) // 8, dtype=torch.int64, device=dev)
+        self._entry_names = (self.ENTRY + "_reset", self.ENTRY + "_step")
+        self._reset_entry, self._step_entry = (getattr(self._etm, name) for name in self._entry_names)
+        self._state = torch.zeros(int(getattr(self._etm, self.ENTRY + "_state_bytes")(W)) // 8, dtype=torch.int64, device=dev)
         self._frames = torch.zeros((W,) + self.observation_space_shape, dtype=torch.uint8, device=dev)
         self._act_dev = torch.zeros(W, dtype=torch.int64, device=dev)
         self._act_pin = torch.zeros(W, dtype=torch.int64).pin_memory()
@@ -66,15 +85,6 @@ class DeviceVecEnv:
         self._done_event = torch.cuda.Event()
         self.device_steps = 0          # calls of step_device (the trainer's fast path), for tests and tools
         self.protocol_steps = 0        # calls of step
-
-    @classmethod
-    def _load(cls, num_envs):
-        if int(num_envs) < 1:
-            raise ValueError(f"{cls.__name__} needs at least one environment")
-        if not torch.cuda.is_available():
-            raise RuntimeError("environment.device: true needs the MI355X (the environments live in device memory): set device: false "
-                               "for the host twin")
-        return etm_lib.load()
 
     # ---------------------------------------------------------------- launches
     def _run(self, actions_ptr, act_stride, frames_ptr, stream):
@@ -158,33 +168,24 @@ class DeviceVecEnv:
 
 
 class CueRoomDeviceVecEnv(DeviceVecEnv):
-    TASK = "CueRoom"
+    TASK, NUM_ACTIONS, ENTRY, SECTION = "CueRoom", 4, "etm_cue_room", staticmethod(cue_room_section)
 
     def __init__(self, num_envs, grid=7, cell=12, cue_steps=2, max_episode_steps=32, seed=0, first_worker_id=0, device=None):
-        from environments.cue_room_env import cue_room_section
-        sec = cue_room_section(dict(grid=grid, cell=cell, cue_steps=cue_steps, max_episode_steps=max_episode_steps, seed=seed))
-        self._etm = self._load(num_envs)
+        self._open(num_envs, first_worker_id, device, grid=grid, cell=cell, cue_steps=cue_steps, max_episode_steps=max_episode_steps,
+                   seed=seed)
+
+    def _rule_of(self, sec):
         self.cue_steps = sec["cue_steps"]
-        if not self._etm.etm_cue_room_supported(sec["grid"], sec["cell"]):
-            raise ValueError(f"CueRoom: the kernel does not take grid {sec['grid']} with cell {sec['cell']}")
-        self._bind(num_envs, sec["grid"], sec["cell"], 4, sec["max_episode_steps"], sec["seed"], first_worker_id, device,
-                   ("etm_cue_room_reset", "etm_cue_room_step"), "etm_cue_room_state_bytes",
-                   (sec["grid"], sec["cell"], sec["cue_steps"], sec["max_episode_steps"]))
+        return (sec["grid"], sec["cell"], sec["cue_steps"], sec["max_episode_steps"]), (sec["grid"], sec["cell"]), sec["max_episode_steps"]
 
 
 class CommandRoomDeviceVecEnv(DeviceVecEnv):
-    TASK = "CommandRoom"
+    TASK, NUM_ACTIONS, ENTRY, SECTION = "CommandRoom", 5, "etm_command_room", staticmethod(command_room_section)
 
     def __init__(self, num_envs, grid=7, cell=12, command_count=8, show_steps=1, gap_steps=1, seed=0, first_worker_id=0, device=None):
-        from environments.command_room_env import command_room_section
-        sec = command_room_section(dict(grid=grid, cell=cell, command_count=command_count, show_steps=show_steps, gap_steps=gap_steps,
-                                        seed=seed))
-        self._etm = self._load(num_envs)
-        self.command_count, self.show_steps, self.gap_steps = sec["command_count"], sec["show_steps"], sec["gap_steps"]
-        if not self._etm.etm_command_room_supported(sec["grid"], sec["cell"], self.command_count):
-            raise ValueError(f"CommandRoom: the kernel does not take grid {sec['grid']} with cell {sec['cell']} and "
-                             f"{self.command_count} commands")
-        K, L = self.command_count, self.show_steps + self.gap_steps
-        self._bind(num_envs, sec["grid"], sec["cell"], 5, K * L + K, sec["seed"], first_worker_id, device,
-                   ("etm_command_room_reset", "etm_command_room_step"), "etm_command_room_state_bytes",
-                   (sec["grid"], sec["cell"], K, self.show_steps, self.gap_steps))
+        self._open(num_envs, first_worker_id, device, grid=grid, cell=cell, command_count=command_count, show_steps=show_steps,
+                   gap_steps=gap_steps, seed=seed)
+
+    def _rule_of(self, sec):
+        self.command_count, self.show_steps, self.gap_steps = K, show, gap = sec["command_count"], sec["show_steps"], sec["gap_steps"]
+        return (sec["grid"], sec["cell"], K, show, gap), (sec["grid"], sec["cell"], K), K * (show + gap) + K

@@ -1,5 +1,5 @@
 """The environment types that have a device-resident front-end, as ONE table: what ``utils.create_env``, ``vec_env.make_vec_env``,
-``cue_room_env.check_device_env_config`` and ``trainer.check_byte_observation_transport`` ask about a ``type`` is looked up here, so
+``check_device_env_config`` (below) and ``trainer.check_byte_observation_transport`` ask about a ``type`` is looked up here, so
 no type is spelled in their code.  All of these types emit uint8 frames only (no float form) and take ``device: true``.
 
 An entry names the rule's module (under ``environments``), its section reader, its host class and its front-end class (in
@@ -29,6 +29,26 @@ def device_env_section(env_config: dict):
     if entry is None:
         return None
     return getattr(importlib.import_module(entry.module), entry.section)(env_config)
+
+
+def check_device_env_config(config: dict, world: int = 1) -> bool:
+    """``environment.device: true`` against the rest of the config, before anything is built -> whether the key is on.  Refused:
+    ``worker_processes: true`` (the environments live on the device, no process steps them), ``bootstrap_truncated: true`` (the
+    front-end keeps no final observation) and a data-parallel run (``world`` > 1: not built, not measured).  Every type of the table
+    is covered alike."""
+    sec = device_env_section(config.get("environment", {}))
+    if sec is None or not sec["device"]:
+        return False
+    if config.get("worker_processes", False):
+        raise ValueError("environment.device: true keeps the environments on the device, worker_processes: true in host processes: set "
+                         "worker_processes: false, or device: false to step the host twin in the worker processes")
+    if config.get("bootstrap_truncated", False):
+        raise ValueError("environment.device: true does not carry bootstrap_truncated: true (the device front-end keeps no final "
+                         "observation): set device: false (the host twin hands it over in its info), or leave bootstrap_truncated off")
+    if int(world) > 1:
+        raise ValueError("environment.device: true is not built for data-parallel runs (every rank would need its own worker streams and "
+                         "nothing here has run more than one rank): run one rank, or set device: false")
+    return True
 
 
 def _arguments(sec: dict) -> dict:

@@ -44,8 +44,7 @@ def default_rollout_groups(num_workers: int, min_group: int) -> int:
 
 from buffer import Buffer
 from environments import action_space_kind, branch_bit_masks, empty_mask_branches, valid_action_share
-from environments.cue_room_env import check_device_env_config
-from environments.device_types import is_byte_only
+from environments.device_types import check_device_env_config, is_byte_only
 from environments.vec_env import make_vec_env
 from etm import lib as etm_lib
 from etm import ops

@@ -7,7 +7,7 @@ import pytest
 import command_room_reference as ref
 from environments import observation_dtype, pack_action_masks
 from environments.command_room_env import (MOVES, PALETTE, CommandRoomEnv, command_room_section, episode_draw, pack_commands, shown)
-from environments.cue_room_env import check_device_env_config
+from environments.device_types import check_device_env_config
 from environments.vec_env import PipeVecEnv, SerialVecEnv, make_vec_env
 from utils import create_env, process_episode_info
 

@@ -5,8 +5,8 @@ import pytest
 
 import cue_room_reference as ref
 from environments import observation_dtype, pack_action_masks
-from environments.cue_room_env import (CueRoomEnv, PALETTE, check_device_env_config, corner_cells, cue_room_section, episode_draw,
-                                       splitmix64)
+from environments.cue_room_env import CueRoomEnv, PALETTE, corner_cells, cue_room_section, episode_draw, splitmix64
+from environments.device_types import check_device_env_config
 from environments.vec_env import PipeVecEnv, SerialVecEnv, make_vec_env
 from utils import create_env, process_episode_info
 

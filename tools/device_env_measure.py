@@ -1,17 +1,22 @@
-"""Measurements behind the README section on device-resident environments (profiles/r22/device_env.txt).  Needs the MI355X.
+"""Measurements behind the README sections on the device-resident environments (profiles/r22/device_env.txt, profiles/r23/command_room.txt,
+profiles/r24/device_env_refactor.txt).  Needs the MI355X.  ``ETM_DIAG_LIB=<path>`` measures another build of the library.
 
-  python tools/device_env_measure.py kernel [--steps 500]
-      etm_cue_room_step at 84 x 84 (grid 7, cell 12) and W in {16, 64, 1024}: device time per step between two events around
-      ``steps`` back-to-back launches on one stream (frames to device memory, result words to pinned host memory), after a warm-up.
-  python tools/device_env_measure.py rollout [--pairs 5] [--rollouts 3]
-      the rollout phase of configs/cue_room_device.yaml against configs/cue_room.yaml -- the host twin stepped serially and through
-      worker processes (``vectorize: pipe``) -- and against the ``Synthetic`` uint8 config of equal shape, the floor a host environment
-      that costs nothing reaches.  All trainers alive in one process, one warm-up rollout each (it captures the step graphs), then
-      ``pairs`` alternated rounds of ``rollouts`` rollouts: seconds per rollout and environment steps per second, range and median,
-      with the trainer's own split (env.step, waiting for the actions, upload + launch).
-  python tools/device_env_measure.py behaviour [--updates 200]
-      configs/cue_room_device.yaml for ``updates`` updates with and without ``obs_reconstruction``: success rate of the episodes that
-      ended in the first and the last tenth of the run (no assertion; always walking to one corner earns 25 %).
+  python tools/device_env_measure.py kernel [--steps 500] [--rounds 3]
+      etm_cue_room_step and etm_command_room_step side by side in one process, at 84 x 84 (grid 7, cell 12) and W in {16, 64, 1024}:
+      device time per step between two events around ``steps`` back-to-back launches on one stream (frames to device memory, result
+      words to pinned host memory), after a warm-up; ``rounds`` alternated rounds, every round printed.
+  python tools/device_env_measure.py rollout [--type CueRoom|CommandRoom] [--pairs 5] [--rollouts 3]
+      the rollout phase of the type's device config (configs/cue_room_device.yaml, command_room_device.yaml) against its host config
+      -- the host twin stepped serially and, for CueRoom, through worker processes (``vectorize: pipe``) -- and against the
+      ``Synthetic`` uint8 config of equal shape and action count, the floor a host environment that costs nothing reaches.  All
+      trainers alive in one process, one warm-up rollout each (it captures the step graphs), then ``pairs`` alternated rounds of
+      ``rollouts`` rollouts: seconds per rollout and environment steps per second, range and median, with the trainer's own split
+      (env.step, waiting for the actions, upload + launch).
+  python tools/device_env_measure.py behaviour [--type CueRoom|CommandRoom] [--updates 200]
+      the type's device config for ``updates`` updates, twice (no assertion).  CueRoom: with and without ``obs_reconstruction``;
+      success rate of the episodes that ended in the first and the last tenth of the run (always walking to one corner earns 25 %).
+      CommandRoom: as configured and with ``memory_length`` cut to ``command_count``; success rate and mean commands completed,
+      beside what a uniformly random policy reaches.
 """
 import argparse
 import os
@@ -25,6 +30,10 @@ os.environ.setdefault("ETM_QUIET", "1")
 
 import numpy as np      # noqa: E402
 import torch            # noqa: E402
+
+if os.environ.get("ETM_DIAG_LIB"):
+    from etm import lib as etm_lib      # noqa: E402
+    etm_lib.LIB_PATH = os.environ["ETM_DIAG_LIB"]
 
 
 def _config(name, **env_over):
@@ -46,43 +55,64 @@ def kernel(args):
     lib = etm_lib.load()
     G, P, dev = 7, 12, torch.device("cuda", 0)
     fb = 3 * (G * P) ** 2
+    # (name, reset entry, step entry, state bytes, rule words behind W, actions)
+    tasks = [("etm_cue_room_step", lib.etm_cue_room_reset, lib.etm_cue_room_step, lib.etm_cue_room_state_bytes, (G, P, 2, 32, 0), 4),
+             ("etm_command_room_step", lib.etm_command_room_reset, lib.etm_command_room_step, lib.etm_command_room_state_bytes,
+              (G, P, 8, 1, 1, 0), 5)]
     for W in (16, 64, 1024):
-        state = torch.zeros(int(lib.etm_cue_room_state_bytes(W)) // 8, dtype=torch.int64, device=dev)
         frames = torch.zeros((W, fb), dtype=torch.uint8, device=dev)
-        actions = torch.from_numpy(np.random.default_rng(0).integers(0, 4, size=(8, W))).to(dev)
         words = [torch.zeros(W, dtype=dt).pin_memory() for dt in (torch.float32, torch.uint8, torch.float32, torch.int32, torch.int64)]
         ptrs = [t.data_ptr() for t in words]
         stream = torch.cuda.current_stream(dev).cuda_stream
-        etm_lib.check(lib.etm_cue_room_reset(state.data_ptr(), frames.data_ptr(), fb, *ptrs, None, 0, W, G, P, 2, 32, 0, stream), "reset")
+        runs = []
+        for name, reset, step, state_bytes, rule, n_act in tasks:
+            state = torch.zeros(int(state_bytes(W)) // 8, dtype=torch.int64, device=dev)
+            actions = torch.from_numpy(np.random.default_rng(0).integers(0, n_act, size=(8, W))).to(dev)
+            etm_lib.check(reset(state.data_ptr(), frames.data_ptr(), fb, *ptrs, None, 0, W, *rule, stream), name + " (reset)")
 
-        def run(n):
-            for i in range(n):
-                rc = lib.etm_cue_room_step(state.data_ptr(), actions[i % 8].data_ptr(), 1, frames.data_ptr(), fb, *ptrs, None, 0, W, G, P,
-                                           2, 32, 0, stream)
-                if rc != 0:
-                    etm_lib.check(rc, "etm_cue_room_step")
-        run(50)
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        run(args.steps)
-        b.record()
-        torch.cuda.synchronize()
-        us = a.elapsed_time(b) * 1000.0 / args.steps
-        print(f"etm_cue_room_step 84x84 W={W}: {us:.2f} us per step over {args.steps} back-to-back launches (events), "
-              f"{W * fb / us / 1e3:.1f} GB/s of frame bytes written", flush=True)
+            def run(n, step=step, state=state, actions=actions, rule=rule, name=name):
+                for i in range(n):
+                    rc = step(state.data_ptr(), actions[i % 8].data_ptr(), 1, frames.data_ptr(), fb, *ptrs, None, 0, W, *rule, stream)
+                    if rc != 0:
+                        etm_lib.check(rc, name)
+            run(50)
+            torch.cuda.synchronize()
+            runs.append((name, run, []))
+        for _ in range(args.rounds):
+            for name, run, us in runs:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                run(args.steps)
+                b.record()
+                torch.cuda.synchronize()
+                us.append(a.elapsed_time(b) * 1000.0 / args.steps)
+        for name, _, us in runs:
+            med = float(np.median(us))
+            print(f"{name} 84x84 W={W}: {' / '.join(f'{u:.2f}' for u in us)} us per step over {args.steps} back-to-back launches (events, "
+                  f"{args.rounds} alternated rounds), median {med:.2f} us = {W * fb / med / 1e3:.1f} GB/s of frame bytes written", flush=True)
+
+
+# per type: the config names' stem, the action count, and whether the worker-process front-end is among the rollout's runs
+TYPES = {"CueRoom": ("cue_room", 4, True), "CommandRoom": ("command_room", 5, False)}
 
 
 def rollout(args):
-    base = _config("cue_room")
+    stem, n_act, with_pipe = TYPES[args.type]
+    base = _config(stem)
     W, S = base["n_workers"], base["worker_steps"]
     env = base["environment"]
-    synthetic = dict(type="Synthetic", obs_shape=[3, env["grid"] * env["cell"], env["grid"] * env["cell"]], num_actions=4,
-                     max_episode_steps=env["max_episode_steps"], seed=0, p_reward=0.05, p_done=0.05, pool=64, observation_levels=256,
+    if args.type == "CueRoom":
+        longest = env["max_episode_steps"]
+    else:
+        longest = env["command_count"] * (env["show_steps"] + env["gap_steps"] + 1)
+    synthetic = dict(type="Synthetic", obs_shape=[3, env["grid"] * env["cell"], env["grid"] * env["cell"]], num_actions=n_act,
+                     max_episode_steps=longest, seed=0, p_reward=0.05, p_done=0.05, pool=64, observation_levels=256,
                      observation_dtype="uint8")
     floor = dict(base, environment=synthetic)
-    runs = [("device", _config("cue_room_device")), ("host serial", _config("cue_room", vectorize="serial")),
-            ("host worker processes", _config("cue_room", vectorize="pipe")), ("Synthetic uint8 floor", floor)]
+    runs = [("device", _config(stem + "_device")), ("host serial", _config(stem, vectorize="serial"))]
+    if with_pipe:
+        runs.append(("host worker processes", _config(stem, vectorize="pipe")))
+    runs.append(("Synthetic uint8 floor", floor))
     trainers = [(name, _trainer(cfg, "measure_" + name.split()[0])) for name, cfg in runs]
     times = {name: [] for name, _ in trainers}
     split = {name: [] for name, _ in trainers}
@@ -112,31 +142,60 @@ def rollout(args):
               f"{1e3 * sp[2]:.1f} ms", flush=True)
 
 
-def behaviour(args):
+def _train(cfg, run_id, updates, count):
+    """``updates`` updates of ``cfg`` -> (the trainer, still open; ``count(infos)`` summed over the first tenth of the updates and
+    over the last, as float arrays; how many updates a tenth is; seconds)."""
+    tr = _trainer(cfg, run_id)
+    ended = []
+    t0 = time.perf_counter()
+    for update in range(updates):
+        lr, beta, clip = tr.schedules(update)
+        infos = tr._sample_training_data()
+        tr.buffer.prepare_batch_dict()
+        tr._train_epochs(lr, clip, beta)
+        tr.update_index += 1
+        ended.append(count(infos))
+    torch.cuda.synchronize()
+    e = np.asarray(ended, dtype=np.float64)
+    k = max(1, updates // 10)
+    return tr, e[:k].sum(axis=0), e[-k:].sum(axis=0), k, time.perf_counter() - t0
+
+
+def _behaviour_cue_room(args):
     for recon in (None, 0.1):
         cfg = _config("cue_room_device")
         if recon is not None:
             cfg["obs_reconstruction"] = recon
-        tr = _trainer(cfg, "cue_room_behaviour")
-        ended = []
-        t0 = time.perf_counter()
-        for update in range(args.updates):
-            lr, beta, clip = tr.schedules(update)
-            infos = tr._sample_training_data()
-            tr.buffer.prepare_batch_dict()
-            tr._train_epochs(lr, clip, beta)
-            tr.update_index += 1
-            ended.append((sum(i["success"] for i in infos), len(infos), sum(i["length"] for i in infos)))
-        torch.cuda.synchronize()
-        e = np.asarray(ended, dtype=np.float64)
-        k = max(1, args.updates // 10)
-        first, last = e[:k].sum(axis=0), e[-k:].sum(axis=0)
+        tr, first, last, k, seconds = _train(cfg, "cue_room_behaviour", args.updates, lambda infos: (
+            sum(i["success"] for i in infos), len(infos), sum(i["length"] for i in infos)))
         extra = "" if tr.last_obs_reconstruction is None else f"; last reconstruction loss {tr.last_obs_reconstruction['loss']:.4f}"
-        print(f"cue_room_device obs_reconstruction={recon}: {args.updates} updates in {time.perf_counter() - t0:.0f} s; success rate of the "
+        print(f"cue_room_device obs_reconstruction={recon}: {args.updates} updates in {seconds:.0f} s; success rate of the "
               f"first {k} updates {100 * first[0] / first[1]:.1f} % ({int(first[1])} episodes, mean length {first[2] / first[1]:.1f}), of the "
               f"last {k} updates {100 * last[0] / last[1]:.1f} % ({int(last[1])} episodes, mean length {last[2] / last[1]:.1f}); "
               f"one fixed corner earns 25 %{extra}", flush=True)
         tr.close()
+
+
+def _behaviour_command_room(args):
+    K = _config("command_room_device")["environment"]["command_count"]
+    # a policy uniform over the five actions answers command e correctly with probability 1 / 5, whatever the command
+    chance_n, chance_success = sum(0.2 ** k for k in range(1, K + 1)), 0.2 ** K
+    for window in (None, K):
+        cfg = _config("command_room_device")
+        if window is not None:
+            cfg["transformer"]["memory_length"] = window
+        tr, first, last, k, seconds = _train(cfg, "command_room_behaviour", args.updates, lambda infos: (
+            sum(i["success"] for i in infos), len(infos), sum(round(i["reward"] * 10) for i in infos)))
+        print(f"command_room_device memory_length={cfg['transformer']['memory_length']}: {args.updates} updates in "
+              f"{seconds:.0f} s; first {k} updates: success {100 * first[0] / first[1]:.2f} %, "
+              f"{first[2] / first[1]:.2f} of {K} commands completed on average ({int(first[1])} episodes); last {k} updates: success "
+              f"{100 * last[0] / last[1]:.2f} %, {last[2] / last[1]:.2f} commands ({int(last[1])} episodes); a uniformly random policy: "
+              f"success {100 * chance_success:.4f} %, {chance_n:.2f} commands", flush=True)
+        tr.close()
+
+
+def behaviour(args):
+    {"CueRoom": _behaviour_cue_room, "CommandRoom": _behaviour_command_room}[args.type](args)
 
 
 if __name__ == "__main__":
@@ -144,10 +203,13 @@ if __name__ == "__main__":
     sub = ap.add_subparsers(dest="what", required=True)
     k = sub.add_parser("kernel")
     k.add_argument("--steps", type=int, default=500)
+    k.add_argument("--rounds", type=int, default=3)
     r = sub.add_parser("rollout")
+    r.add_argument("--type", choices=list(TYPES), default="CueRoom")
     r.add_argument("--pairs", type=int, default=5)
     r.add_argument("--rollouts", type=int, default=3)
     b = sub.add_parser("behaviour")
+    b.add_argument("--type", choices=list(TYPES), default="CueRoom")
     b.add_argument("--updates", type=int, default=200)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
