@@ -1,7 +1,7 @@
 // Device-resident environments: grid-room tasks stepped, auto-reset and rendered by one launch per worker group and step.  ONE kernel
 // skeleton (env_kernel) and one launcher (env_launch) serve every task; a task is a stateless struct of static functions that says
-// what is its own -- state, rule words, draw, advance, picture, colour (CueRoom and CommandRoom below; the ONE host definition of
-// each rule is environments/cue_room_env.py resp. command_room_env.py).
+// what is its own -- state, rule words, draw, advance, picture, colour (CueRoom, CommandRoom and PathRoom below; the ONE host definition
+// of each rule is environments/cue_room_env.py, command_room_env.py resp. path_room_env.py).
 // What the skeleton keeps, whatever the task:
 //   * one workgroup of 256 threads per environment, grid = W; no dependence on launch geometry, no atomics, no inline assembly: two
 //     calls from equal state give equal bytes;
@@ -247,6 +247,120 @@ struct CommandRoom {
   }
 };
 
+// ---------------------------------------------------------------------------------------------------------------- PathRoom
+// An invisible path of at most M moves (up, right, down) from an origin in column 0; a move onto a path cell pays the progress beyond
+// the best index reached, the goal 10 tenths more, a move onto any other cell is a fall back to the origin (the cell is the mark of
+// the next observation only).  Whether a cell is on the path, and its index, is a walk over the packed moves: integer adds.
+constexpr int PATH_MAX_MOVES = 32;
+
+// flat colours of floor, goal, mark, agent (path_room_env.PALETTE)
+__device__ __constant__ unsigned path_palette[4][3] = {{28u * 0x01010101u, 28u * 0x01010101u, 36u * 0x01010101u},
+                                                       {64u * 0x01010101u, 192u * 0x01010101u, 96u * 0x01010101u},
+                                                       {232u * 0x01010101u, 64u * 0x01010101u, 200u * 0x01010101u},
+                                                       {240u * 0x01010101u, 200u * 0x01010101u, 48u * 0x01010101u}};
+
+struct PathRoom {
+  struct State {                       // 32 bytes per environment (etm_path_room_state_bytes)
+    unsigned long long episode;
+    unsigned long long path;           // move j (0 up, 1 right, 2 down) in bits [2 j, 2 j + 2)
+    int agent, t, best;                // a cell is row << 5 | column here (G <= 31): no division by G in the step
+    unsigned places;                   // origin row in bits [0, 5), n in [5, 11), the goal cell in [11, 21), the mark cell + 1 in [21, 32)
+  };
+  struct Rule {
+    int G, P, M, max_steps;
+    unsigned long long stream0;
+  };
+  static constexpr int ACTIONS = 4;
+  static constexpr int PIC = 3;        // cell index (row-major) of the goal, the mark and the agent; -1: not drawn
+
+  static bool rule_ok(const Rule &rule) { return rule.M >= 1 && rule.M <= PATH_MAX_MOVES && rule.max_steps >= 1; }
+
+  static __device__ __forceinline__ int origin_of(const State &s) { return (int)(s.places & 31u); }
+  static __device__ __forceinline__ int moves_of(const State &s) { return (int)(s.places >> 5 & 63u); }
+  static __device__ __forceinline__ int goal_of(const State &s) { return (int)(s.places >> 11 & 1023u); }
+
+  // (x >> 16) mod n for n = 1, 2 or 3 without a 64-bit division, as CommandRoom::pick_of: 2^24 = 1 mod 3, and mod 2 is a bit
+  static __device__ __forceinline__ int pick_of(unsigned long long x, int n) {
+    const unsigned hi = (unsigned)(x >> 40), lo = (unsigned)(x >> 16) & 0xffffffu;
+    return (int)(n == 3 ? (hi + lo) % 3u : (n == 2 ? lo & 1u : 0u));
+  }
+
+  static __device__ __forceinline__ void draw(State &s, unsigned long long stream, const Rule &rule) {
+    const int G = rule.G;
+    const unsigned long long h = env_hash(stream, s.episode);
+    const int origin = (int)((h >> 8) % (unsigned long long)G);
+    int r = origin, c = 0, previous = -1, n = 0;
+    unsigned long long x = h, word = 0;
+    for (int j = 0; j < rule.M && c < G - 1; ++j) {
+      x = env_splitmix64(x);
+      const int up = (r > 0 && previous != 2) ? 1 : 0, down = (r < G - 1 && previous != 0) ? 1 : 0;
+      // the candidates (up, right, down) with up and / or down left out: entry pick is move pick, or pick + 1 where up is left out
+      const int a = pick_of(x, 1 + up + down) + 1 - up;
+      word |= (unsigned long long)a << (2 * j);
+      r += env_dr(a);
+      c += env_dc(a);
+      previous = a;
+      n = j + 1;
+    }
+    s.path = word;
+    s.agent = origin << 5;
+    s.best = 0;
+    s.places = (unsigned)origin | (unsigned)n << 5 | (unsigned)(r << 5 | c) << 11;        // no mark
+  }
+
+  static __device__ __forceinline__ void advance(State &s, int a, const Rule &rule, float &reward, unsigned &flag) {
+    const int G = rule.G, origin = origin_of(s), n = moves_of(s);
+    const int r = (s.agent >> 5) + env_dr(a), c = (s.agent & 31) + env_dc(a);
+    int k = 0;
+    s.places &= 0x1fffffu;                                                 // the mark lasts one observation
+    if (r >= 0 && r < G && c >= 0 && c < G) {
+      const int target = r << 5 | c;
+      int cell = origin << 5, index = cell == target ? 0 : -1;           // the path visits no cell twice: at most one match
+      unsigned long long word = s.path;
+      for (int j = 1; j <= n; ++j) {
+        const int m = (int)(word & 3ull);
+        word >>= 2;
+        cell += env_dr(m) * 32 + env_dc(m);
+        if (cell == target) index = j;
+      }
+      if (index >= 0) {
+        s.agent = target;
+        k = index > s.best ? index - s.best : 0;
+        if (index > s.best) s.best = index;
+        if (index == n) {
+          k += 10;
+          flag = 1u | 4u;
+        }
+      } else {                                                             // a fall: back to the origin, the cell marked
+        s.agent = origin << 5;
+        s.places |= (unsigned)(target + 1) << 21;
+      }
+    }
+    if (!flag && s.t + 1 >= rule.max_steps) flag = 1u | 2u;
+    reward = (float)k * 0.1f;
+  }
+
+  // (the agent stands on the goal only in the step that ends the episode there)
+  static __device__ __forceinline__ float episode_return(const State &s) {
+    return (float)(s.best + (s.agent == goal_of(s) ? 10 : 0)) * 0.1f;
+  }
+
+  static __device__ __forceinline__ int index_of(int cell, int G) { return (cell >> 5) * G + (cell & 31); }
+
+  static __device__ __forceinline__ void picture(const State &s, const Rule &rule, int *pic, unsigned &mask) {
+    const int G = rule.G, mark = (int)(s.places >> 21);
+    mask = env_on_grid(s.agent >> 5, s.agent & 31, G);
+    pic[0] = index_of(goal_of(s), G);
+    pic[1] = mark ? index_of(mark - 1, G) : -1;
+    pic[2] = index_of(s.agent, G);
+  }
+
+  static __device__ __forceinline__ unsigned colour(int r, int c, const int *pic, int G, int ch) {
+    const int cell = r * G + c;
+    return path_palette[cell == pic[2] ? 3 : (cell == pic[1] ? 2 : (cell == pic[0] ? 1 : 0))][ch];
+  }
+};
+
 // ---------------------------------------------------------------------------------------------------------------- the skeleton
 template <class Task, bool RESET>
 __global__ __launch_bounds__(ENV_THREADS) void env_kernel(typename Task::State *__restrict__ state, const long long *__restrict__ actions,
@@ -349,9 +463,13 @@ extern "C" int etm_cue_room_supported(int G, int P) { return env_grid_ok(G, P) ?
 
 extern "C" int etm_command_room_supported(int G, int P, int K) { return env_grid_ok(G, P) && K >= 1 && K <= CMD_MAX_COMMANDS ? 1 : 0; }
 
+extern "C" int etm_path_room_supported(int G, int P, int M) { return env_grid_ok(G, P) && M >= 1 && M <= PATH_MAX_MOVES ? 1 : 0; }
+
 extern "C" int64_t etm_cue_room_state_bytes(int W) { return W < 1 ? 0 : (int64_t)W * (int64_t)sizeof(CueRoom::State); }
 
 extern "C" int64_t etm_command_room_state_bytes(int W) { return W < 1 ? 0 : (int64_t)W * (int64_t)sizeof(CommandRoom::State); }
+
+extern "C" int64_t etm_path_room_state_bytes(int W) { return W < 1 ? 0 : (int64_t)W * (int64_t)sizeof(PathRoom::State); }
 
 extern "C" int etm_cue_room_reset(void *state, uint8_t *frames, int64_t frame_pitch, float *rewards, uint8_t *flags, float *returns,
                                   int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P,
@@ -384,4 +502,20 @@ extern "C" int etm_command_room_step(void *state, const int64_t *actions, int64_
   const EnvOut out{frames, (long long)frame_pitch, rewards, flags, returns, lengths, (long long *)masks};
   return env_launch<CommandRoom>(false, state, actions, act_stride, out, done_word, done_value, W,
                                  CommandRoom::Rule{G, P, K, show_steps, gap_steps, (unsigned long long)stream0}, stream);
+}
+
+extern "C" int etm_path_room_reset(void *state, uint8_t *frames, int64_t frame_pitch, float *rewards, uint8_t *flags, float *returns,
+                                   int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P, int M,
+                                   int max_steps, int64_t stream0, void *stream) {
+  const EnvOut out{frames, (long long)frame_pitch, rewards, flags, returns, lengths, (long long *)masks};
+  return env_launch<PathRoom>(true, state, nullptr, 0, out, done_word, done_value, W,
+                              PathRoom::Rule{G, P, M, max_steps, (unsigned long long)stream0}, stream);
+}
+
+extern "C" int etm_path_room_step(void *state, const int64_t *actions, int64_t act_stride, uint8_t *frames, int64_t frame_pitch,
+                                  float *rewards, uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word,
+                                  int64_t done_value, int W, int G, int P, int M, int max_steps, int64_t stream0, void *stream) {
+  const EnvOut out{frames, (long long)frame_pitch, rewards, flags, returns, lengths, (long long *)masks};
+  return env_launch<PathRoom>(false, state, actions, act_stride, out, done_word, done_value, W,
+                              PathRoom::Rule{G, P, M, max_steps, (unsigned long long)stream0}, stream);
 }

@@ -1,6 +1,7 @@
 """Device-resident vectorised environments: ``CueRoomDeviceVecEnv`` serves CueRoom (environments/cue_room_env.py is the one
-definition of the rule) and ``CommandRoomDeviceVecEnv`` serves CommandRoom (environments/command_room_env.py) from device memory --
-step, auto-reset and rendering of all workers are ONE HIP kernel per call (csrc/device_env.hip), bit for bit the host rule.
+definition of the rule), ``CommandRoomDeviceVecEnv`` serves CommandRoom (environments/command_room_env.py) and
+``PathRoomDeviceVecEnv`` serves PathRoom (environments/path_room_env.py) from device memory -- step, auto-reset and rendering
+of all workers are ONE HIP kernel per call (csrc/device_env.hip), bit for bit the host rule.
 
 Two ways of stepping, over the same state:
 
@@ -24,6 +25,7 @@ import torch
 
 from environments.command_room_env import command_room_section
 from environments.cue_room_env import cue_room_section
+from environments.path_room_env import path_room_section
 from etm import lib as etm_lib
 
 
@@ -189,3 +191,15 @@ class CommandRoomDeviceVecEnv(DeviceVecEnv):
     def _rule_of(self, sec):
         self.command_count, self.show_steps, self.gap_steps = K, show, gap = sec["command_count"], sec["show_steps"], sec["gap_steps"]
         return (sec["grid"], sec["cell"], K, show, gap), (sec["grid"], sec["cell"], K), K * (show + gap) + K
+
+
+class PathRoomDeviceVecEnv(DeviceVecEnv):
+    TASK, NUM_ACTIONS, ENTRY, SECTION = "PathRoom", 4, "etm_path_room", staticmethod(path_room_section)
+
+    def __init__(self, num_envs, grid=7, cell=12, path_moves=16, max_episode_steps=64, seed=0, first_worker_id=0, device=None):
+        self._open(num_envs, first_worker_id, device, grid=grid, cell=cell, path_moves=path_moves, max_episode_steps=max_episode_steps,
+                   seed=seed)
+
+    def _rule_of(self, sec):
+        self.path_moves = M = sec["path_moves"]
+        return (sec["grid"], sec["cell"], M, sec["max_episode_steps"]), (sec["grid"], sec["cell"], M), sec["max_episode_steps"]

@@ -14,6 +14,7 @@ DeviceEnvType = namedtuple("DeviceEnvType", "module section host_class front_end
 DEVICE_ENV_TYPES = {
     "CueRoom": DeviceEnvType("environments.cue_room_env", "cue_room_section", "CueRoomEnv", "CueRoomDeviceVecEnv"),
     "CommandRoom": DeviceEnvType("environments.command_room_env", "command_room_section", "CommandRoomEnv", "CommandRoomDeviceVecEnv"),
+    "PathRoom": DeviceEnvType("environments.path_room_env", "path_room_section", "PathRoomEnv", "PathRoomDeviceVecEnv"),
 }
 
 

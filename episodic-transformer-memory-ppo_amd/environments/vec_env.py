@@ -37,7 +37,7 @@ is exactly what upstream's loop does by hand (trainer.py:195-201).
 * ``SerialVecEnv``  -- wraps in-process single envs with the upstream env API.
 * ``PipeVecEnv``    -- wraps upstream-protocol ``Worker`` subprocesses (worker.py), one pipe round trip per step.
 * ``environments.synthetic.SyntheticVecEnv`` implements the protocol natively.
-* ``environments.device_env.CueRoomDeviceVecEnv`` / ``CommandRoomDeviceVecEnv`` (the types of environments/device_types.py with
+* ``environments.device_env.CueRoomDeviceVecEnv`` / ``CommandRoomDeviceVecEnv`` / ``PathRoomDeviceVecEnv`` (the types of environments/device_types.py with
   ``device: true``) implement it over environments that live in device memory, and declare ``device_resident = True``: ``step_device(actions_dev, rows_dev, stream) -> (rewards, dones, infos)`` steps
   them from the device's action table straight into the given device rows (the trainer's streamed plans use it).
 """
@@ -250,7 +250,7 @@ def make_vec_env(env_config: dict, num_envs: int, first_worker_id: int = 0, grou
             kw["obs_shape"] = tuple(kw["obs_shape"])
         return SyntheticVecEnv(num_envs, first_worker_id=first_worker_id, **kw)
     from environments.device_types import device_env_section, make_device_vec_env
-    sec = device_env_section(env_config)        # (None unless the type has a device-resident front-end: CueRoom, CommandRoom)
+    sec = device_env_section(env_config)        # (None unless the type has a device-resident front-end: environments/device_types.py)
     if sec is not None and sec["device"]:       # the rule as one HIP kernel per step (environments/device_env.py)
         return make_device_vec_env(env_config, num_envs, first_worker_id)
     if env_config.get("vectorize", "pipe") == "serial":

@@ -250,6 +250,11 @@ SIGNATURES["etm_command_room_supported"] = (_I, [_I, _I, _I])
 SIGNATURES["etm_command_room_state_bytes"] = (_L, [_I])
 SIGNATURES["etm_command_room_reset"] = (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _L, _P])
 SIGNATURES["etm_command_room_step"] = (_I, [_P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _L, _P])
+# PathRoom, the third (same file, same shape of entry; the rule words are G, P, M, max_steps)
+SIGNATURES["etm_path_room_supported"] = (_I, [_I, _I, _I])
+SIGNATURES["etm_path_room_state_bytes"] = (_L, [_I])
+SIGNATURES["etm_path_room_reset"] = (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P])
+SIGNATURES["etm_path_room_step"] = (_I, [_P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P])
 del _twin
 del _name, _extra, _res, _args
 

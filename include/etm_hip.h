@@ -1025,6 +1025,28 @@ int etm_command_room_step(void *state, const int64_t *actions, int64_t act_strid
                           uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W,
                           int G, int P, int K, int show_steps, int gap_steps, int64_t stream0, void *stream);
 
+/* PathRoom (same file, added with the ABI left at 61): the hidden-path memory task whose one host definition is
+ * environments/path_room_env.py -- an invisible path of at most M moves (up, right, down) leads from an origin in column 0 to a goal;
+ * a move onto a path cell pays the progress beyond the best index reached, a move onto any other cell is a fall back to the origin.
+ * Same launch shape, outputs, order of outputs, completion word and alignment rules as etm_cue_room_*; the state is 32 bytes per
+ * environment (episode u64, packed moves u64 with 2 bits each, agent cell, observation index t, best index, and one word that packs
+ * the origin row, the number of moves n, the goal cell and the mark cell + 1; a cell is row << 5 | column there).
+ *   etm_path_room_supported: 1 where etm_cue_room_supported(G, P) and 1 <= M <= 32, else 0.
+ *   etm_path_room_step: actions outside 0 .. 3 are clamped (the host rule raises).  rewards: float(k) * 0.1f, one multiply, k the
+ *       tenths earned (progress, plus 10 on the goal); flags: bit 0 done, bit 1 truncated (t + 1 >= max_steps without the goal), bit 2
+ *       success; returns: float(best + 10 success) * 0.1f of the episode that ended, one multiply; lengths: its steps; masks: bit a
+ *       set when move a stays on the grid.
+ * Integer arithmetic apart from those two multiplies, no atomics: two calls from equal state give equal bytes.
+ * ETM_EINVAL, with nothing launched: the classes of etm_cue_room_*, (G, P, M) outside etm_path_room_supported, max_steps < 1. */
+int etm_path_room_supported(int G, int P, int M);
+int64_t etm_path_room_state_bytes(int W);
+int etm_path_room_reset(void *state, uint8_t *frames, int64_t frame_pitch, float *rewards, uint8_t *flags, float *returns, int32_t *lengths,
+                        int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P, int M, int max_steps,
+                        int64_t stream0, void *stream);
+int etm_path_room_step(void *state, const int64_t *actions, int64_t act_stride, uint8_t *frames, int64_t frame_pitch, float *rewards,
+                       uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W,
+                       int G, int P, int M, int max_steps, int64_t stream0, void *stream);
+
 /* Monitored gradient norms of the module groups (model.py:128-151) from the flat gradient arena in two launches:
  * out[g] = sqrt(sum_s member[g][s] * ||flat[seg_start[s] .. seg_start[s] + seg_len[s])||^2).  Segments: runs of <= 4096 floats, each
  * inside one parameter tensor (device arrays seg_start int64 [n_segs], seg_len int32 [n_segs]); member [n_groups, n_segs] float

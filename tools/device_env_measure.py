@@ -1,22 +1,23 @@
 """Measurements behind the README sections on the device-resident environments (profiles/r22/device_env.txt, profiles/r23/command_room.txt,
-profiles/r24/device_env_refactor.txt).  Needs the MI355X.  ``ETM_DIAG_LIB=<path>`` measures another build of the library.
+profiles/r24/device_env_refactor.txt, profiles/r25/path_room.txt).  Needs the MI355X.  ``ETM_DIAG_LIB=<path>`` measures another build of the library.
 
   python tools/device_env_measure.py kernel [--steps 500] [--rounds 3]
-      etm_cue_room_step and etm_command_room_step side by side in one process, at 84 x 84 (grid 7, cell 12) and W in {16, 64, 1024}:
+      etm_cue_room_step, etm_command_room_step and etm_path_room_step side by side in one process, at 84 x 84 (grid 7, cell 12) and W in {16, 64, 1024}:
       device time per step between two events around ``steps`` back-to-back launches on one stream (frames to device memory, result
       words to pinned host memory), after a warm-up; ``rounds`` alternated rounds, every round printed.
-  python tools/device_env_measure.py rollout [--type CueRoom|CommandRoom] [--pairs 5] [--rollouts 3]
-      the rollout phase of the type's device config (configs/cue_room_device.yaml, command_room_device.yaml) against its host config
+  python tools/device_env_measure.py rollout [--type CueRoom|CommandRoom|PathRoom] [--pairs 5] [--rollouts 3]
+      the rollout phase of the type's device config (configs/cue_room_device.yaml, command_room_device.yaml, path_room_device.yaml) against its host config
       -- the host twin stepped serially and, for CueRoom, through worker processes (``vectorize: pipe``) -- and against the
       ``Synthetic`` uint8 config of equal shape and action count, the floor a host environment that costs nothing reaches.  All
       trainers alive in one process, one warm-up rollout each (it captures the step graphs), then ``pairs`` alternated rounds of
       ``rollouts`` rollouts: seconds per rollout and environment steps per second, range and median, with the trainer's own split
       (env.step, waiting for the actions, upload + launch).
-  python tools/device_env_measure.py behaviour [--type CueRoom|CommandRoom] [--updates 200]
+  python tools/device_env_measure.py behaviour [--type CueRoom|CommandRoom|PathRoom] [--updates 200]
       the type's device config for ``updates`` updates, twice (no assertion).  CueRoom: with and without ``obs_reconstruction``;
       success rate of the episodes that ended in the first and the last tenth of the run (always walking to one corner earns 25 %).
       CommandRoom: as configured and with ``memory_length`` cut to ``command_count``; success rate and mean commands completed,
-      beside what a uniformly random policy reaches.
+      beside what a uniformly random policy reaches.  PathRoom: as configured and with ``memory_length`` cut to 8; mean best / n (the
+      share of the path reached), success rate and falls per episode, beside a uniformly random policy stepped on the host twin.
 """
 import argparse
 import os
@@ -58,7 +59,8 @@ def kernel(args):
     # (name, reset entry, step entry, state bytes, rule words behind W, actions)
     tasks = [("etm_cue_room_step", lib.etm_cue_room_reset, lib.etm_cue_room_step, lib.etm_cue_room_state_bytes, (G, P, 2, 32, 0), 4),
              ("etm_command_room_step", lib.etm_command_room_reset, lib.etm_command_room_step, lib.etm_command_room_state_bytes,
-              (G, P, 8, 1, 1, 0), 5)]
+              (G, P, 8, 1, 1, 0), 5),
+             ("etm_path_room_step", lib.etm_path_room_reset, lib.etm_path_room_step, lib.etm_path_room_state_bytes, (G, P, 16, 64, 0), 4)]
     for W in (16, 64, 1024):
         frames = torch.zeros((W, fb), dtype=torch.uint8, device=dev)
         words = [torch.zeros(W, dtype=dt).pin_memory() for dt in (torch.float32, torch.uint8, torch.float32, torch.int32, torch.int64)]
@@ -93,7 +95,7 @@ def kernel(args):
 
 
 # per type: the config names' stem, the action count, and whether the worker-process front-end is among the rollout's runs
-TYPES = {"CueRoom": ("cue_room", 4, True), "CommandRoom": ("command_room", 5, False)}
+TYPES = {"CueRoom": ("cue_room", 4, True), "CommandRoom": ("command_room", 5, False), "PathRoom": ("path_room", 4, False)}
 
 
 def rollout(args):
@@ -101,7 +103,7 @@ def rollout(args):
     base = _config(stem)
     W, S = base["n_workers"], base["worker_steps"]
     env = base["environment"]
-    if args.type == "CueRoom":
+    if "max_episode_steps" in env:
         longest = env["max_episode_steps"]
     else:
         longest = env["command_count"] * (env["show_steps"] + env["gap_steps"] + 1)
@@ -142,10 +144,10 @@ def rollout(args):
               f"{1e3 * sp[2]:.1f} ms", flush=True)
 
 
-def _train(cfg, run_id, updates, count):
-    """``updates`` updates of ``cfg`` -> (the trainer, still open; ``count(infos)`` summed over the first tenth of the updates and
-    over the last, as float arrays; how many updates a tenth is; seconds)."""
-    tr = _trainer(cfg, run_id)
+def _train(cfg, run_id, updates, count, tr=None):
+    """``updates`` updates of ``cfg`` (on the trainer ``tr`` where one is given) -> (the trainer, still open; ``count(infos)`` summed
+    over the first tenth of the updates and over the last, as float arrays; how many updates a tenth is; seconds)."""
+    tr = _trainer(cfg, run_id) if tr is None else tr
     ended = []
     t0 = time.perf_counter()
     for update in range(updates):
@@ -194,8 +196,82 @@ def _behaviour_command_room(args):
         tr.close()
 
 
+class _PathRoomRecorder:
+    """What PathRoom's infos do not carry, per finished episode: n (from the episode draw: every worker's episodes follow one
+    another from 0) and the falls (the mark bits of the state words, read back after every step; a fall in the step that ends an
+    episode is not seen, the state is the next episode's by then)."""
+
+    def __init__(self, front_ends):
+        self.total = np.zeros(4)                  # sum of best / n, successes, episodes, falls of the episodes that ended
+        for env in front_ends:
+            self._wrap(env)
+
+    def _wrap(self, env):
+        from environments.path_room_env import episode_draw
+        results = env._results
+        W, G, M = env.num_envs, env.grid, env.path_moves
+        episode, falls = np.zeros(W, dtype=np.int64), np.zeros(W, dtype=np.int64)
+
+        def recorded():
+            rewards, dones, infos = results()
+            falls[:] += ((env._state.view(W, 4)[:, 3].cpu().numpy() >> 53) & 0x7ff) != 0
+            for w in np.flatnonzero(dones):
+                n = len(episode_draw(env.stream0 + int(w), int(episode[w]), G, M)[1])
+                best = round(infos[w]["reward"] * 10) - 10 * infos[w]["success"]
+                self.total += (best / n, infos[w]["success"], 1, falls[w])
+                episode[w] += 1
+                falls[w] = 0
+            return rewards, dones, infos
+        env._results = recorded
+
+    def take(self, infos):
+        total, self.total = self.total, np.zeros(4)
+        return tuple(total)
+
+
+def _path_room_random_policy(env, episodes=1000):
+    """(mean best / n, success rate, falls per episode) of a policy uniform over the four actions, on the host twin."""
+    from environments.path_room_env import PathRoomEnv
+    e = PathRoomEnv(**{k: v for k, v in env.items() if k in ("grid", "cell", "path_moves", "max_episode_steps", "seed")})
+    rng = np.random.default_rng(0)
+    share = success = falls = 0.0
+    for _ in range(episodes):
+        e.reset()
+        while True:
+            _, _, done, info = e.step(int(rng.integers(0, 4)))
+            falls += e.mark is not None and not done      # (as the recorder counts: not in the step that ends the episode)
+            if done:
+                share += e.best / len(e.moves)
+                success += info["success"]
+                break
+    return share / episodes, success / episodes, falls / episodes
+
+
+def _behaviour_path_room(args):
+    chance = _path_room_random_policy(_config("path_room_device")["environment"])
+    for window in (None, 8):
+        cfg = _config("path_room_device")
+        if window is not None:
+            cfg["transformer"]["memory_length"] = window
+        recorder = []
+
+        def count(infos):
+            return recorder[0].take(infos)
+        tr = _trainer(cfg, "path_room_behaviour")
+        recorder.append(_PathRoomRecorder(list(getattr(tr.env, "parts", None) or [tr.env])))
+        tr, first, last, k, seconds = _train(cfg, "path_room_behaviour", args.updates, count, tr)
+
+        def line(x):
+            return (f"best / n {x[0] / x[2]:.3f}, success {100 * x[1] / x[2]:.2f} %, {x[3] / x[2]:.2f} falls per episode "
+                    f"({int(x[2])} episodes)")
+        print(f"path_room_device memory_length={cfg['transformer']['memory_length']}: {args.updates} updates in {seconds:.0f} s; "
+              f"first {k} updates: {line(first)}; last {k} updates: {line(last)}; a uniformly random policy (1000 episodes of the "
+              f"host twin): best / n {chance[0]:.3f}, success {100 * chance[1]:.2f} %, {chance[2]:.2f} falls per episode", flush=True)
+        tr.close()
+
+
 def behaviour(args):
-    {"CueRoom": _behaviour_cue_room, "CommandRoom": _behaviour_command_room}[args.type](args)
+    {"CueRoom": _behaviour_cue_room, "CommandRoom": _behaviour_command_room, "PathRoom": _behaviour_path_room}[args.type](args)
 
 
 if __name__ == "__main__":
