@@ -1,7 +1,7 @@
 // Device-resident environments: grid-room tasks stepped, auto-reset and rendered by one launch per worker group and step.  ONE kernel
 // skeleton (env_kernel) and one launcher (env_launch) serve every task; a task is a stateless struct of static functions that says
-// what is its own -- state, rule words, draw, advance, picture, colour (CueRoom, CommandRoom and PathRoom below; the ONE host definition
-// of each rule is environments/cue_room_env.py, command_room_env.py resp. path_room_env.py).
+// what is its own -- state, rule words, draw, advance, picture, colour (CueRoom, CommandRoom, PathRoom and SpotRoom below; the ONE host
+// definition of each rule is environments/cue_room_env.py, command_room_env.py, path_room_env.py resp. spot_room_env.py).
 // What the skeleton keeps, whatever the task:
 //   * one workgroup of 256 threads per environment, grid = W; no dependence on launch geometry, no atomics, no inline assembly: two
 //     calls from equal state give equal bytes;
@@ -361,6 +361,170 @@ struct PathRoom {
   }
 };
 
+// ---------------------------------------------------------------------------------------------------------------- SpotRoom
+// A coin, then an exit, in a room that is dark from observation light_steps on; N <= 4 spotlights sweep a lane each as a triangle
+// wave and light the 3 x 3 block around their centre.  The agent is drawn only where a spotlight is on it, and that costs health.
+// The picture depends on time: the state carries the wave's common offset (step, wave) counted up, so the step divides by nothing.
+constexpr int SPOT_MAX_LIGHTS = 4, SPOT_MAX_HEALTH = 15;
+constexpr int SPOT_COIN_TENTHS = 5, SPOT_EXIT_TENTHS = 10;
+constexpr unsigned SPOT_NOT_DRAWN = 1023u, SPOT_NO_CENTRE = 0x6464u;      // (row 100, column 100: no cell is within 1 of it)
+
+// flat colours of dark floor, lit floor, coin, exit, agent (spot_room_env.PALETTE)
+__device__ __constant__ unsigned spot_palette[5][3] = {{12u * 0x01010101u, 12u * 0x01010101u, 20u * 0x01010101u},
+                                                       {96u * 0x01010101u, 92u * 0x01010101u, 72u * 0x01010101u},
+                                                       {248u * 0x01010101u, 208u * 0x01010101u, 40u * 0x01010101u},
+                                                       {56u * 0x01010101u, 176u * 0x01010101u, 112u * 0x01010101u},
+                                                       {224u * 0x01010101u, 64u * 0x01010101u, 200u * 0x01010101u}};
+
+struct SpotRoom {
+  struct State {                       // 32 bytes per environment (etm_spot_room_state_bytes)
+    unsigned long long episode;
+    unsigned long long spots;          // spotlight i in bits [12 i, 12 i + 12): axis 1, lane 5, phase 6
+    int agent, t;                      // a cell is row << 5 | column here (G <= 31)
+    unsigned places;                   // the coin cell in bits [0, 10), the exit cell in [10, 20), health LOST in [20, 24), coin taken in
+                                       // bit 24, wave = ((t - light_steps) div spot_period) mod (2 G - 2) in [25, 31) (0 while t < light_steps)
+    int rest;                          // (t - light_steps) mod spot_period: the steps the spotlights have rested (0 while t < light_steps)
+  };
+  struct Rule {
+    int G, P, N, light_steps, spot_period, health, max_steps;
+    unsigned long long stream0;
+  };
+  static constexpr int ACTIONS = 5;
+  static constexpr int PIC = 3;        // [0]: agent, coin, exit cell in 10 bits each (1023: not drawn), bit 30: all floor lit;
+                                       // [1], [2]: the four centres, row | column << 8 in 16 bits each (SPOT_NO_CENTRE: none)
+
+  static bool rule_ok(const Rule &rule) {
+    return rule.N >= 0 && rule.N <= SPOT_MAX_LIGHTS && rule.light_steps >= 1 && rule.spot_period >= 1 && rule.health >= 1 &&
+           rule.health <= SPOT_MAX_HEALTH && rule.max_steps >= 1;
+  }
+
+  static __device__ __forceinline__ int coin_of(const State &s) { return (int)(s.places & 1023u); }
+  static __device__ __forceinline__ int exit_of(const State &s) { return (int)(s.places >> 10 & 1023u); }
+  static __device__ __forceinline__ int lost_of(const State &s) { return (int)(s.places >> 20 & 15u); }
+  static __device__ __forceinline__ bool taken_of(const State &s) { return (s.places >> 24 & 1u) != 0; }
+  static __device__ __forceinline__ int wave_of(const State &s) { return (int)(s.places >> 25 & 63u); }
+
+  static __device__ __forceinline__ int cell_of(unsigned index, unsigned G) {      // row-major index -> row << 5 | column
+    const unsigned r = index / G;
+    return (int)(r << 5 | (index - r * G));
+  }
+
+  // the start, the coin and the exit are three remainders of 24-bit fields by G^2, G^2 - 1, G^2 - 2, a spotlight's lane and phase two
+  // of 16-bit fields: 32-bit divisions all, and only where an episode starts
+  static __device__ __forceinline__ void draw(State &s, unsigned long long stream, const Rule &rule) {
+    const unsigned G = (unsigned)rule.G, cells = G * G;
+    const unsigned long long h = env_hash(stream, s.episode);
+    const unsigned start = ((unsigned)(h >> 8) & 0xffffffu) % cells;
+    unsigned long long x = env_splitmix64(h);
+    unsigned coin = ((unsigned)(x >> 16) & 0xffffffu) % (cells - 1u);    // entry of the cells without the start
+    if (coin >= start) ++coin;
+    x = env_splitmix64(x);
+    unsigned leave = ((unsigned)(x >> 16) & 0xffffffu) % (cells - 2u);   // entry of the cells without the start and the coin
+    const unsigned lo = start < coin ? start : coin, hi = start < coin ? coin : start;
+    if (leave >= lo) ++leave;
+    if (leave >= hi) ++leave;
+    unsigned long long word = 0;
+    for (int i = 0; i < rule.N; ++i) {
+      x = env_splitmix64(x);
+      const unsigned axis = (unsigned)(x >> 16) & 1u, lane = ((unsigned)(x >> 20) & 0xffffu) % G;
+      const unsigned phase = ((unsigned)(x >> 40) & 0xffffu) % (2u * G - 2u);
+      word |= (unsigned long long)(axis | lane << 1 | phase << 6) << (12 * i);
+    }
+    s.spots = word;
+    s.agent = cell_of(start, G);
+    s.places = (unsigned)cell_of(coin, G) | (unsigned)cell_of(leave, G) << 10;      // nothing lost, coin not taken, wave 0
+    s.rest = 0;
+  }
+
+  // centre of spotlight i, row | column << 8, with the wave's common offset
+  static __device__ __forceinline__ unsigned centre(unsigned long long spots, int i, int wave, int G) {
+    const unsigned bits = (unsigned)(spots >> (12 * i)) & 0xfffu;
+    int q = (int)(bits >> 6) + wave;                                       // both below 2 G - 2
+    if (q >= 2 * G - 2) q -= 2 * G - 2;
+    const unsigned pos = (unsigned)(q < G ? q : 2 * G - 2 - q), lane = bits >> 1 & 31u;
+    return (bits & 1u) ? (pos | lane << 8) : (lane | pos << 8);
+  }
+
+  static __device__ __forceinline__ bool in_box(int r, int c, unsigned centre16) {
+    return (unsigned)(r - (int)(centre16 & 255u) + 1) <= 2u && (unsigned)(c - (int)(centre16 >> 8 & 255u) + 1) <= 2u;
+  }
+
+  // whether a spotlight is on ``cell`` with the wave at ``wave`` (the caller knows that the spotlights are active)
+  static __device__ __forceinline__ bool lit(const State &s, int cell, int wave, const Rule &rule) {
+    bool on = false;
+    for (int i = 0; i < rule.N; ++i) on = on || in_box(cell >> 5, cell & 31, centre(s.spots, i, wave, rule.G));
+    return on;
+  }
+
+  // (the skeleton counts s.t up behind this: s.t + 1 is the observation this action leads to)
+  static __device__ __forceinline__ void advance(State &s, int a, const Rule &rule, float &reward, unsigned &flag) {
+    const int G = rule.G, r = (s.agent >> 5) + env_dr(a), c = (s.agent & 31) + env_dc(a);
+    int k = 0;
+    if (r >= 0 && r < G && c >= 0 && c < G) s.agent = r << 5 | c;
+    if (s.agent == coin_of(s) && !taken_of(s)) {
+      s.places |= 1u << 24;
+      k += SPOT_COIN_TENTHS;
+    }
+    // the spotlights of observation t + 1: they rest spot_period observations on a cell, from observation light_steps on
+    int wave = wave_of(s);
+    if (s.t >= rule.light_steps) {
+      s.rest += 1;
+      if (s.rest >= rule.spot_period) {
+        s.rest = 0;
+        wave = wave + 1 >= 2 * G - 2 ? 0 : wave + 1;
+        s.places = (s.places & ~(63u << 25)) | (unsigned)wave << 25;
+      }
+    }
+    if (s.agent == exit_of(s) && taken_of(s)) {
+      k += SPOT_EXIT_TENTHS;
+      flag = 1u | 4u;
+    } else if (s.t + 1 >= rule.light_steps && lit(s, s.agent, wave, rule)) {
+      s.places += 1u << 20;
+      k -= 1;
+      if (lost_of(s) >= rule.health) flag = 1u;
+    }
+    if (!flag && s.t + 1 >= rule.max_steps) flag = 1u | 2u;
+    reward = (float)k * 0.1f;
+  }
+
+  // (the agent stands on the exit with the coin taken only in the step that ends the episode there)
+  static __device__ __forceinline__ float episode_return(const State &s) {
+    const int taken = taken_of(s) ? 1 : 0;
+    return (float)(SPOT_COIN_TENTHS * taken + (taken && s.agent == exit_of(s) ? SPOT_EXIT_TENTHS : 0) - lost_of(s)) * 0.1f;
+  }
+
+  static __device__ __forceinline__ void picture(const State &s, const Rule &rule, int *pic, unsigned &mask) {
+    const int G = rule.G, wave = wave_of(s);
+    const bool light = s.t < rule.light_steps;
+    mask = env_on_grid(s.agent >> 5, s.agent & 31, G) | 16u;
+    unsigned centres[SPOT_MAX_LIGHTS];
+    for (int i = 0; i < SPOT_MAX_LIGHTS; ++i) centres[i] = (!light && i < rule.N) ? centre(s.spots, i, wave, G) : SPOT_NO_CENTRE;
+    bool seen = light;
+    for (int i = 0; i < SPOT_MAX_LIGHTS; ++i) seen = seen || in_box(s.agent >> 5, s.agent & 31, centres[i]);
+    pic[0] = (int)((seen ? (unsigned)s.agent : SPOT_NOT_DRAWN) | (taken_of(s) ? SPOT_NOT_DRAWN : (unsigned)coin_of(s)) << 10 |
+                   (unsigned)exit_of(s) << 20 | (light ? 1u << 30 : 0u));
+    pic[1] = (int)(centres[0] | centres[1] << 16);
+    pic[2] = (int)(centres[2] | centres[3] << 16);
+  }
+
+  // bits x .. x + 2 of a word whose bit k + 1 stands for row (column) k: the three rows (columns) around x; none for no centre
+  static __device__ __forceinline__ unsigned span(unsigned x) { return x < 31u ? 7u << x : 0u; }
+
+  // (the spans depend on the picture alone: the frame loop keeps them in registers, and a word costs two shifts and an AND per box)
+  static __device__ __forceinline__ unsigned colour(int r, int c, const int *pic, int, int ch) {
+    const unsigned places = (unsigned)pic[0], first = (unsigned)pic[1], second = (unsigned)pic[2], cell = (unsigned)(r << 5 | c);
+    const unsigned on = (places >> 30 | ((span(first & 255u) >> (r + 1)) & (span(first >> 8 & 255u) >> (c + 1))) |
+                         ((span(first >> 16 & 255u) >> (r + 1)) & (span(first >> 24) >> (c + 1))) |
+                         ((span(second & 255u) >> (r + 1)) & (span(second >> 8 & 255u) >> (c + 1))) |
+                         ((span(second >> 16 & 255u) >> (r + 1)) & (span(second >> 24) >> (c + 1)))) & 1u;
+    int colour = (int)on;
+    if (cell == (places >> 10 & 1023u)) colour = 2;
+    if (cell == (places >> 20 & 1023u)) colour = 3;
+    if (cell == (places & 1023u)) colour = 4;
+    return spot_palette[colour][ch];
+  }
+};
+
 // ---------------------------------------------------------------------------------------------------------------- the skeleton
 template <class Task, bool RESET>
 __global__ __launch_bounds__(ENV_THREADS) void env_kernel(typename Task::State *__restrict__ state, const long long *__restrict__ actions,
@@ -465,11 +629,17 @@ extern "C" int etm_command_room_supported(int G, int P, int K) { return env_grid
 
 extern "C" int etm_path_room_supported(int G, int P, int M) { return env_grid_ok(G, P) && M >= 1 && M <= PATH_MAX_MOVES ? 1 : 0; }
 
+extern "C" int etm_spot_room_supported(int G, int P, int N, int H) {
+  return env_grid_ok(G, P) && N >= 0 && N <= SPOT_MAX_LIGHTS && H >= 1 && H <= SPOT_MAX_HEALTH ? 1 : 0;
+}
+
 extern "C" int64_t etm_cue_room_state_bytes(int W) { return W < 1 ? 0 : (int64_t)W * (int64_t)sizeof(CueRoom::State); }
 
 extern "C" int64_t etm_command_room_state_bytes(int W) { return W < 1 ? 0 : (int64_t)W * (int64_t)sizeof(CommandRoom::State); }
 
 extern "C" int64_t etm_path_room_state_bytes(int W) { return W < 1 ? 0 : (int64_t)W * (int64_t)sizeof(PathRoom::State); }
+
+extern "C" int64_t etm_spot_room_state_bytes(int W) { return W < 1 ? 0 : (int64_t)W * (int64_t)sizeof(SpotRoom::State); }
 
 extern "C" int etm_cue_room_reset(void *state, uint8_t *frames, int64_t frame_pitch, float *rewards, uint8_t *flags, float *returns,
                                   int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P,
@@ -518,4 +688,21 @@ extern "C" int etm_path_room_step(void *state, const int64_t *actions, int64_t a
   const EnvOut out{frames, (long long)frame_pitch, rewards, flags, returns, lengths, (long long *)masks};
   return env_launch<PathRoom>(false, state, actions, act_stride, out, done_word, done_value, W,
                               PathRoom::Rule{G, P, M, max_steps, (unsigned long long)stream0}, stream);
+}
+
+extern "C" int etm_spot_room_reset(void *state, uint8_t *frames, int64_t frame_pitch, float *rewards, uint8_t *flags, float *returns,
+                                   int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P, int N,
+                                   int light_steps, int spot_period, int health, int max_steps, int64_t stream0, void *stream) {
+  const EnvOut out{frames, (long long)frame_pitch, rewards, flags, returns, lengths, (long long *)masks};
+  return env_launch<SpotRoom>(true, state, nullptr, 0, out, done_word, done_value, W,
+                              SpotRoom::Rule{G, P, N, light_steps, spot_period, health, max_steps, (unsigned long long)stream0}, stream);
+}
+
+extern "C" int etm_spot_room_step(void *state, const int64_t *actions, int64_t act_stride, uint8_t *frames, int64_t frame_pitch,
+                                  float *rewards, uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word,
+                                  int64_t done_value, int W, int G, int P, int N, int light_steps, int spot_period, int health,
+                                  int max_steps, int64_t stream0, void *stream) {
+  const EnvOut out{frames, (long long)frame_pitch, rewards, flags, returns, lengths, (long long *)masks};
+  return env_launch<SpotRoom>(false, state, actions, act_stride, out, done_word, done_value, W,
+                              SpotRoom::Rule{G, P, N, light_steps, spot_period, health, max_steps, (unsigned long long)stream0}, stream);
 }

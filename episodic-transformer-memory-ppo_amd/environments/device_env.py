@@ -1,6 +1,7 @@
 """Device-resident vectorised environments: ``CueRoomDeviceVecEnv`` serves CueRoom (environments/cue_room_env.py is the one
-definition of the rule), ``CommandRoomDeviceVecEnv`` serves CommandRoom (environments/command_room_env.py) and
-``PathRoomDeviceVecEnv`` serves PathRoom (environments/path_room_env.py) from device memory -- step, auto-reset and rendering
+definition of the rule), ``CommandRoomDeviceVecEnv`` serves CommandRoom (environments/command_room_env.py),
+``PathRoomDeviceVecEnv`` serves PathRoom (environments/path_room_env.py) and ``SpotRoomDeviceVecEnv`` serves SpotRoom
+(environments/spot_room_env.py) from device memory -- step, auto-reset and rendering
 of all workers are ONE HIP kernel per call (csrc/device_env.hip), bit for bit the host rule.
 
 Two ways of stepping, over the same state:
@@ -26,6 +27,7 @@ import torch
 from environments.command_room_env import command_room_section
 from environments.cue_room_env import cue_room_section
 from environments.path_room_env import path_room_section
+from environments.spot_room_env import spot_room_section
 from etm import lib as etm_lib
 
 
@@ -203,3 +205,18 @@ class PathRoomDeviceVecEnv(DeviceVecEnv):
     def _rule_of(self, sec):
         self.path_moves = M = sec["path_moves"]
         return (sec["grid"], sec["cell"], M, sec["max_episode_steps"]), (sec["grid"], sec["cell"], M), sec["max_episode_steps"]
+
+
+class SpotRoomDeviceVecEnv(DeviceVecEnv):
+    TASK, NUM_ACTIONS, ENTRY, SECTION = "SpotRoom", 5, "etm_spot_room", staticmethod(spot_room_section)
+
+    def __init__(self, num_envs, grid=7, cell=12, spotlights=2, light_steps=2, spot_period=2, health=5, max_episode_steps=64, seed=0,
+                 first_worker_id=0, device=None):
+        self._open(num_envs, first_worker_id, device, grid=grid, cell=cell, spotlights=spotlights, light_steps=light_steps,
+                   spot_period=spot_period, health=health, max_episode_steps=max_episode_steps, seed=seed)
+
+    def _rule_of(self, sec):
+        self.spotlights, self.light_steps, self.spot_period, self.health = N, light, period, H = (
+            sec["spotlights"], sec["light_steps"], sec["spot_period"], sec["health"])
+        G, P, limit = sec["grid"], sec["cell"], sec["max_episode_steps"]
+        return (G, P, N, light, period, H, limit), (G, P, N, H), limit

@@ -15,6 +15,7 @@ DEVICE_ENV_TYPES = {
     "CueRoom": DeviceEnvType("environments.cue_room_env", "cue_room_section", "CueRoomEnv", "CueRoomDeviceVecEnv"),
     "CommandRoom": DeviceEnvType("environments.command_room_env", "command_room_section", "CommandRoomEnv", "CommandRoomDeviceVecEnv"),
     "PathRoom": DeviceEnvType("environments.path_room_env", "path_room_section", "PathRoomEnv", "PathRoomDeviceVecEnv"),
+    "SpotRoom": DeviceEnvType("environments.spot_room_env", "spot_room_section", "SpotRoomEnv", "SpotRoomDeviceVecEnv"),
 }
 
 

@@ -1,6 +1,6 @@
-"""What the grid-room image tasks (CueRoom, CommandRoom, PathRoom) share on the host: the 64-bit mixer and the episode hash every
+"""What the grid-room image tasks (CueRoom, CommandRoom, PathRoom, SpotRoom) share on the host: the 64-bit mixer and the episode hash every
 draw starts from, the geometry the kernel admits, the shared part of a section reader and the painter that turns a table of cell
-colours into the frame.  A task's module (cue_room_env.py, command_room_env.py, path_room_env.py) holds what is its own -- the rule,
+colours into the frame.  A task's module (cue_room_env.py, command_room_env.py, path_room_env.py, spot_room_env.py) holds what is its own -- the rule,
 the palette, the draw, its keys and their checks -- and imports from here, never from another task.  csrc/device_env.hip is laid out
 the same way.
 """

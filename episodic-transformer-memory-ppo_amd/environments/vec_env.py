@@ -37,7 +37,7 @@ is exactly what upstream's loop does by hand (trainer.py:195-201).
 * ``SerialVecEnv``  -- wraps in-process single envs with the upstream env API.
 * ``PipeVecEnv``    -- wraps upstream-protocol ``Worker`` subprocesses (worker.py), one pipe round trip per step.
 * ``environments.synthetic.SyntheticVecEnv`` implements the protocol natively.
-* ``environments.device_env.CueRoomDeviceVecEnv`` / ``CommandRoomDeviceVecEnv`` / ``PathRoomDeviceVecEnv`` (the types of environments/device_types.py with
+* ``environments.device_env.CueRoomDeviceVecEnv`` / ``CommandRoomDeviceVecEnv`` / ``PathRoomDeviceVecEnv`` / ``SpotRoomDeviceVecEnv`` (the types of environments/device_types.py with
   ``device: true``) implement it over environments that live in device memory, and declare ``device_resident = True``: ``step_device(actions_dev, rows_dev, stream) -> (rewards, dones, infos)`` steps
   them from the device's action table straight into the given device rows (the trainer's streamed plans use it).
 """

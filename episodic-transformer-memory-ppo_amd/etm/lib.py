@@ -255,6 +255,11 @@ SIGNATURES["etm_path_room_supported"] = (_I, [_I, _I, _I])
 SIGNATURES["etm_path_room_state_bytes"] = (_L, [_I])
 SIGNATURES["etm_path_room_reset"] = (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P])
 SIGNATURES["etm_path_room_step"] = (_I, [_P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P])
+# SpotRoom, the fourth (the rule words are G, P, N, light_steps, spot_period, health, max_steps)
+SIGNATURES["etm_spot_room_supported"] = (_I, [_I, _I, _I, _I])
+SIGNATURES["etm_spot_room_state_bytes"] = (_L, [_I])
+SIGNATURES["etm_spot_room_reset"] = (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P])
+SIGNATURES["etm_spot_room_step"] = (_I, [_P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P])
 del _twin
 del _name, _extra, _res, _args
 

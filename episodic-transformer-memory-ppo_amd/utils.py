@@ -43,8 +43,8 @@ def create_env(config: dict, render: bool = False, worker_id: int = 0):
         return HiddenArmEnv(arms=int(config.get("arms", 2)), max_episode_steps=int(config.get("max_episode_steps", 16)), seed=seed)
     from environments.device_types import DEVICE_ENV_TYPES, make_host_env
     if kind in DEVICE_ENV_TYPES:
-        # the host twin of an image memory task (environments/cue_room_env.py, command_room_env.py, path_room_env.py); ``device: true``
-        # is the vectorised front-end's key (environments/device_env.py) and means nothing to a single environment
+        # the host twin of an image memory task (environments/cue_room_env.py, command_room_env.py, path_room_env.py, spot_room_env.py);
+        # ``device: true`` is the vectorised front-end's key (environments/device_env.py) and means nothing to a single environment
         return make_host_env(config, worker_id=worker_id)
     raise ImportError(f"environment type {kind!r} needs its simulator package (gym / gym-minigrid / memory-gym), which is "
                       "outside this build; use type 'Synthetic' with the same observation shape for throughput runs")

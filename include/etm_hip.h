@@ -1047,6 +1047,31 @@ int etm_path_room_step(void *state, const int64_t *actions, int64_t act_stride, 
                        uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W,
                        int G, int P, int M, int max_steps, int64_t stream0, void *stream);
 
+/* SpotRoom (same file, added with the ABI left at 61): the dark-room task with moving spotlights whose one host definition is
+ * environments/spot_room_env.py -- the agent takes a coin, then leaves through an exit; from observation light_steps on the room is
+ * dark, N spotlights sweep a lane each as a triangle wave (one cell every spot_period observations) and light the 3 x 3 block around
+ * their centre; the agent is drawn only where a spotlight is on it, and every such observation costs one of its `health` points.
+ * Same launch shape, outputs, order of outputs, completion word and alignment rules as etm_cue_room_*; the state is 32 bytes per
+ * environment (episode u64, the spotlights u64 with 12 bits each -- axis 1, lane 5, phase 6 --, agent cell, observation index t, one
+ * word that packs the coin cell, the exit cell, the health lost, coin-taken and the wave's common offset, and the observations the
+ * spotlights have rested; a cell is row << 5 | column there).
+ *   etm_spot_room_supported: 1 where etm_cue_room_supported(G, P), 0 <= N <= 4 and 1 <= H <= 15, else 0.
+ *   etm_spot_room_step: actions outside 0 .. 4 are clamped (the host rule raises).  rewards: float(k) * 0.1f, one multiply, k the
+ *       signed tenths earned (+5 the coin, +10 the exit with the coin, -1 a lit observation); flags: bit 0 done, bit 1 truncated
+ *       (t + 1 >= max_steps, neither left nor dead), bit 2 success; returns: float(5 coin + 10 success - health lost) * 0.1f of the
+ *       episode that ended, one multiply; lengths: its steps; masks: bit a < 4 set when move a stays on the grid, bit 4 (stay) set.
+ * Integer arithmetic apart from those two multiplies, no atomics: two calls from equal state give equal bytes.
+ * ETM_EINVAL, with nothing launched: the classes of etm_cue_room_*, (G, P, N, health) outside etm_spot_room_supported, light_steps < 1,
+ * spot_period < 1, max_steps < 1. */
+int etm_spot_room_supported(int G, int P, int N, int H);
+int64_t etm_spot_room_state_bytes(int W);
+int etm_spot_room_reset(void *state, uint8_t *frames, int64_t frame_pitch, float *rewards, uint8_t *flags, float *returns, int32_t *lengths,
+                        int64_t *masks, int64_t *done_word, int64_t done_value, int W, int G, int P, int N, int light_steps,
+                        int spot_period, int health, int max_steps, int64_t stream0, void *stream);
+int etm_spot_room_step(void *state, const int64_t *actions, int64_t act_stride, uint8_t *frames, int64_t frame_pitch, float *rewards,
+                       uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W,
+                       int G, int P, int N, int light_steps, int spot_period, int health, int max_steps, int64_t stream0, void *stream);
+
 /* Monitored gradient norms of the module groups (model.py:128-151) from the flat gradient arena in two launches:
  * out[g] = sqrt(sum_s member[g][s] * ||flat[seg_start[s] .. seg_start[s] + seg_len[s])||^2).  Segments: runs of <= 4096 floats, each
  * inside one parameter tensor (device arrays seg_start int64 [n_segs], seg_len int32 [n_segs]); member [n_groups, n_segs] float

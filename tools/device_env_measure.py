@@ -1,23 +1,26 @@
 """Measurements behind the README sections on the device-resident environments (profiles/r22/device_env.txt, profiles/r23/command_room.txt,
-profiles/r24/device_env_refactor.txt, profiles/r25/path_room.txt).  Needs the MI355X.  ``ETM_DIAG_LIB=<path>`` measures another build of the library.
+profiles/r24/device_env_refactor.txt, profiles/r25/path_room.txt, profiles/r26/spot_room.txt).  Needs the MI355X.  ``ETM_DIAG_LIB=<path>`` measures another build of the library.
 
   python tools/device_env_measure.py kernel [--steps 500] [--rounds 3]
-      etm_cue_room_step, etm_command_room_step and etm_path_room_step side by side in one process, at 84 x 84 (grid 7, cell 12) and W in {16, 64, 1024}:
+      etm_cue_room_step, etm_command_room_step, etm_path_room_step and etm_spot_room_step side by side in one process, at 84 x 84 (grid 7, cell 12) and W in {16, 64, 1024}:
       device time per step between two events around ``steps`` back-to-back launches on one stream (frames to device memory, result
       words to pinned host memory), after a warm-up; ``rounds`` alternated rounds, every round printed.
-  python tools/device_env_measure.py rollout [--type CueRoom|CommandRoom|PathRoom] [--pairs 5] [--rollouts 3]
-      the rollout phase of the type's device config (configs/cue_room_device.yaml, command_room_device.yaml, path_room_device.yaml) against its host config
+  python tools/device_env_measure.py rollout [--type CueRoom|CommandRoom|PathRoom|SpotRoom] [--pairs 5] [--rollouts 3]
+      the rollout phase of the type's device config (configs/cue_room_device.yaml, command_room_device.yaml, path_room_device.yaml, spot_room_device.yaml) against its host config
       -- the host twin stepped serially and, for CueRoom, through worker processes (``vectorize: pipe``) -- and against the
       ``Synthetic`` uint8 config of equal shape and action count, the floor a host environment that costs nothing reaches.  All
       trainers alive in one process, one warm-up rollout each (it captures the step graphs), then ``pairs`` alternated rounds of
       ``rollouts`` rollouts: seconds per rollout and environment steps per second, range and median, with the trainer's own split
       (env.step, waiting for the actions, upload + launch).
-  python tools/device_env_measure.py behaviour [--type CueRoom|CommandRoom|PathRoom] [--updates 200]
+  python tools/device_env_measure.py behaviour [--type CueRoom|CommandRoom|PathRoom|SpotRoom] [--updates 200]
       the type's device config for ``updates`` updates, twice (no assertion).  CueRoom: with and without ``obs_reconstruction``;
       success rate of the episodes that ended in the first and the last tenth of the run (always walking to one corner earns 25 %).
       CommandRoom: as configured and with ``memory_length`` cut to ``command_count``; success rate and mean commands completed,
       beside what a uniformly random policy reaches.  PathRoom: as configured and with ``memory_length`` cut to 8; mean best / n (the
       share of the path reached), success rate and falls per episode, beside a uniformly random policy stepped on the host twin.
+      SpotRoom: as configured, with ``previous_step_input: false`` and with ``memory_length`` cut to 8; mean return, success rate,
+      share of deaths, coins and damage per episode of the episodes that ended in the first and the last tenth, beside a uniformly
+      random policy stepped on the host twin.
 """
 import argparse
 import os
@@ -60,7 +63,9 @@ def kernel(args):
     tasks = [("etm_cue_room_step", lib.etm_cue_room_reset, lib.etm_cue_room_step, lib.etm_cue_room_state_bytes, (G, P, 2, 32, 0), 4),
              ("etm_command_room_step", lib.etm_command_room_reset, lib.etm_command_room_step, lib.etm_command_room_state_bytes,
               (G, P, 8, 1, 1, 0), 5),
-             ("etm_path_room_step", lib.etm_path_room_reset, lib.etm_path_room_step, lib.etm_path_room_state_bytes, (G, P, 16, 64, 0), 4)]
+             ("etm_path_room_step", lib.etm_path_room_reset, lib.etm_path_room_step, lib.etm_path_room_state_bytes, (G, P, 16, 64, 0), 4),
+             ("etm_spot_room_step", lib.etm_spot_room_reset, lib.etm_spot_room_step, lib.etm_spot_room_state_bytes,
+              (G, P, 2, 2, 2, 5, 64, 0), 5)]
     for W in (16, 64, 1024):
         frames = torch.zeros((W, fb), dtype=torch.uint8, device=dev)
         words = [torch.zeros(W, dtype=dt).pin_memory() for dt in (torch.float32, torch.uint8, torch.float32, torch.int32, torch.int64)]
@@ -95,7 +100,8 @@ def kernel(args):
 
 
 # per type: the config names' stem, the action count, and whether the worker-process front-end is among the rollout's runs
-TYPES = {"CueRoom": ("cue_room", 4, True), "CommandRoom": ("command_room", 5, False), "PathRoom": ("path_room", 4, False)}
+TYPES = {"CueRoom": ("cue_room", 4, True), "CommandRoom": ("command_room", 5, False), "PathRoom": ("path_room", 4, False),
+         "SpotRoom": ("spot_room", 5, False)}
 
 
 def rollout(args):
@@ -270,8 +276,59 @@ def _behaviour_path_room(args):
         tr.close()
 
 
+def _spot_room_episodes(infos, health):
+    """(sum of returns, successes, deaths, coins, damage, episodes) of finished SpotRoom episodes, from their infos alone: the return
+    is 5 coin + 10 success - damage tenths; an ending that is neither a success nor a cut is a death and has lost all ``health``
+    points, every other episode has lost fewer, so with ``health`` <= 5 (asserted) the sign of 5 coin - damage tells the coin."""
+    assert health <= 5, "the coin and the damage are read apart only while the damage stays below the coin's 5 tenths"
+    total = np.zeros(6)
+    for i in infos:
+        tenths = round(i["reward"] * 10) - 10 * i["success"]
+        death = not i["success"] and not i.get("truncated", False)
+        damage = health if death else (5 - tenths if tenths > 0 else -tenths)
+        total += (i["reward"], i["success"], death, (tenths + damage) // 5, damage, 1)
+    return tuple(total)
+
+
+def _spot_room_line(x):
+    return (f"return {x[0] / x[5]:.3f}, success {100 * x[1] / x[5]:.2f} %, deaths {100 * x[2] / x[5]:.2f} %, coins {100 * x[3] / x[5]:.2f} %, "
+            f"damage {x[4] / x[5]:.2f} per episode ({int(x[5])} episodes)")
+
+
+def _spot_room_random_policy(env, episodes=1000):
+    """``_spot_room_episodes`` of a policy uniform over the five actions, on the host twin."""
+    from environments.spot_room_env import SpotRoomEnv
+    e = SpotRoomEnv(**{k: v for k, v in env.items() if k not in ("type", "device", "vectorize")})
+    rng = np.random.default_rng(0)
+    infos = []
+    for _ in range(episodes):
+        e.reset()
+        done = False
+        while not done:
+            _, _, done, info = e.step(int(rng.integers(0, 5)))
+        infos.append(info)
+    return _spot_room_episodes(infos, env["health"])
+
+
+def _behaviour_spot_room(args):
+    env = _config("spot_room_device")["environment"]
+    print(f"spot_room: a uniformly random policy (1000 episodes of the host twin): {_spot_room_line(_spot_room_random_policy(env))}", flush=True)
+    for name, change in (("as configured", {}), ("previous_step_input=false", {"previous_step_input": False}),
+                         ("memory_length=8", {"memory_length": 8})):
+        cfg = _config("spot_room_device")
+        if "previous_step_input" in change:
+            cfg["previous_step_input"] = False
+        if "memory_length" in change:
+            cfg["transformer"]["memory_length"] = change["memory_length"]
+        tr, first, last, k, seconds = _train(cfg, "spot_room_behaviour", args.updates, lambda infos: _spot_room_episodes(infos, env["health"]))
+        print(f"spot_room_device {name}: {args.updates} updates in {seconds:.0f} s; first {k} updates: {_spot_room_line(first)}; "
+              f"last {k} updates: {_spot_room_line(last)}", flush=True)
+        tr.close()
+
+
 def behaviour(args):
-    {"CueRoom": _behaviour_cue_room, "CommandRoom": _behaviour_command_room, "PathRoom": _behaviour_path_room}[args.type](args)
+    {"CueRoom": _behaviour_cue_room, "CommandRoom": _behaviour_command_room, "PathRoom": _behaviour_path_room,
+     "SpotRoom": _behaviour_spot_room}[args.type](args)
 
 
 if __name__ == "__main__":
