@@ -214,245 +214,182 @@ extern "C" int etm_rollout_hidden_partial(const float *x, const float *wt, float
 // their K | V projection (items + pos[step_l[w]]) wkv[b] into kv[w, step_l[w]] -- what the multi-launch path does with five more
 // launches while the host steps the environments.
 // h_splits > 0: h_in is the [h_splits, W, D] output of etm_rollout_hidden_partial and the transformer input is relu(sum + h_bias).
-static int rollout_trxl_impl(int group, const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
-                                int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
-                                const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
-                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
-                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
-                                float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
-                                const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
-                                int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
-                                int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
-                                int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W,
-                                const int32_t *branch_sizes, int n_branches, const RfBox *box, const int64_t *action_mask, void *stream,
-                                bool means = false, float *st_means = nullptr, bool logps = false, float *st_logps = nullptr) {
+//
+// The 12 launch entries (worker and group form of: one branch, MultiDiscrete, with masks, with every column's log-prob, Box, Box with
+// the means) share one call record: an entry fills it by field name and hands it to rollout_trxl_run, which validates -- in the
+// order written there, the order in which refusals win -- and launches.  The entries hold no checks of their own.
+namespace {
+struct RfCall {
+  RfParams p;                        // the kernels' parameters as the entry's arguments give them; the rest is derived by the validator
+  int group;                         // 0: a team of workgroups per worker (this file); 1: the group form (csrc/rollout_group.hip)
+  void *scratch;
+  int64_t scratch_bytes;
+  const void *const *blocks;         // the raw block table: p.nb x RF_BLOCK_PTRS device pointers
+  const int32_t *branch_sizes;       // categorical policies: HOST array, or NULL with n_branches = 1 for one branch of p.A actions
+  int n_branches;
+  bool box;                          // a Box policy: p.box holds the action tables, low / high (HOST arrays or NULL) its bounds
+  const float *low, *high;
+  bool need_mask, need_means, need_logps;   // the optional tables p.am / p.st_means / p.st_logps that this entry makes mandatory
+  hipStream_t stream;
+};
+
+// The worker form's kernel of (register rows 20 / 32, window rows 64 / 128, general block layout, variant)
+using RfKernel = void (*)(const RfParams);
+enum { RF_PLAIN, RF_MASKED, RF_LOGPS, RF_LOGPS_MASKED, RF_BOX, RF_BOX_MEANS, RF_VARIANTS };
+#define RF_VARIANT_ROW(GR, LM, GEN)                                                                                                   \
+  { rollout_trxl_kernel<GR, LM, GEN, false>, rollout_trxl_masked_kernel<GR, LM, GEN>, rollout_trxl_logps_kernel<GR, LM, GEN, false>, \
+    rollout_trxl_logps_kernel<GR, LM, GEN, true>, rollout_trxl_kernel<GR, LM, GEN, true>, rollout_trxl_gaussian_means_kernel<GR, LM, GEN> }
+#define RF_LAYOUT_ROWS(GR, LM) { RF_VARIANT_ROW(GR, LM, false), RF_VARIANT_ROW(GR, LM, true) }
+const RfKernel rf_kernels[2][2][2][RF_VARIANTS] = {{RF_LAYOUT_ROWS(20, 64), RF_LAYOUT_ROWS(20, 128)},
+                                                   {RF_LAYOUT_ROWS(32, 64), RF_LAYOUT_ROWS(32, 128)}};
+#undef RF_LAYOUT_ROWS
+#undef RF_VARIANT_ROW
+
+int rollout_trxl_run(RfCall &c) {
+  RfParams &p = c.p;
   (void)hipGetLastError();
-  if (means && (!box || !st_means || ((uintptr_t)st_means & 3u))) return ETM_EINVAL;
-  if (logps && (box || !st_logps || ((uintptr_t)st_logps & 3u))) return ETM_EINVAL;
-  if (ss && (!mask_table || !index_table || !st_mask || !st_idx || !latch || !mask_t || !win_t || T <= 0)) return ETM_EINVAL;
-  if (!ss && (!win || !mask)) return ETM_EINVAL;
-  // (a Box policy's action tables are the float ones of `box`; the int64 ones are unused then)
-  const bool tables = box ? (box->log_std && box->normals && box->actions && box->st_actions) : (uniforms && actions && st_actions);
-  if (!h_in || !wemb_t || !bemb || !blocks || !kv || !items || !wh_t || !bh || !wp || !bp || !wv || !bv || !tables ||
-      !t_dev || !st_logp || !st_values || !sync_counter || !scratch)
+  if (c.need_mask && !p.am) return ETM_EINVAL;
+  if (c.box)
+    if (const int rc = etm_box_make(c.low, c.high, p.A, &p.box.bx)) return rc;
+  if (c.need_means && (!p.st_means || ((uintptr_t)p.st_means & 3u))) return ETM_EINVAL;
+  if (c.need_logps && (!p.st_logps || ((uintptr_t)p.st_logps & 3u))) return ETM_EINVAL;
+  if (p.ss && (!p.mask_table || !p.index_table || !p.st_mask || !p.st_idx || !p.latch || !p.mask_t || !p.win_t || p.T <= 0)) return ETM_EINVAL;
+  if (!p.ss && (!p.win || !p.mask)) return ETM_EINVAL;
+  // (a Box policy's action tables are the float ones of p.box; the int64 ones are unused then)
+  const bool tables = c.box ? (p.box.log_std && p.box.normals && p.box.actions && p.box.st_actions) : (p.uniforms && p.actions && p.st_actions);
+  if (!p.h_in || !p.wemb_t || !p.bemb || !c.blocks || !p.kv || !p.items || !p.wh_t || !p.bh || !p.wp || !p.bp || !p.wv || !p.bv || !tables ||
+      !p.t_dev || !p.st_logp || !p.st_values || !p.sync_counter || !c.scratch)
     return ETM_EINVAL;
-  if (W <= 0 || nb <= 0 || D <= 0 || H <= 0 || L <= 0 || hid <= 0 || A <= 0 || stage_W < W || D % H != 0) return ETM_EINVAL;
-  if (host_flag && !(box ? (const void *)box->host_actions : (const void *)host_actions)) return ETM_EINVAL;
-  if (box && (box->bx.A != A || A > ETM_MAX_BOX)) return ETM_EUNSUPPORTED;
-  if (action_mask && box) return ETM_EINVAL;
-  if (const int rc = etm_action_mask_check(action_mask, A)) return rc;
-  if (wkv && (!step_l || !slot_l || !bank)) return ETM_EINVAL;
-  if (h_splits < 0 || h_splits > RF_MAXSPLIT || (h_splits > 0 && !h_bias)) return ETM_EINVAL;
-  const int P = etm_rollout_trxl_team(H);
-  if (group) {
-    if (!etm_rollout_trxl_group_supported(D, H, L, hid, A, nb, W, gtrxl) || (wkv && P != H)) return ETM_EUNSUPPORTED;
-    if (scratch_bytes < etm_rollout_trxl_group_scratch_bytes(nb)) return ETM_EWORKSPACE;
+  if (p.W <= 0 || p.nb <= 0 || p.D <= 0 || p.H <= 0 || p.L <= 0 || p.hid <= 0 || p.A <= 0 || p.stage_W < p.W || p.D % p.H != 0) return ETM_EINVAL;
+  if (p.host_flag && !(c.box ? (const void *)p.box.host_actions : (const void *)p.host_actions)) return ETM_EINVAL;
+  if (const int rc = etm_action_mask_check(p.am, p.A)) return rc;
+  if (p.wkv && (!p.step_l || !p.slot_l || !p.bank)) return ETM_EINVAL;
+  if (p.h_splits < 0 || p.h_splits > RF_MAXSPLIT || (p.h_splits > 0 && !p.h_bias)) return ETM_EINVAL;
+  p.P = etm_rollout_trxl_team(p.H);
+  if (c.group) {
+    if (!etm_rollout_trxl_group_supported(p.D, p.H, p.L, p.hid, p.A, p.nb, p.W, p.gtrxl) || (p.wkv && p.P != p.H)) return ETM_EUNSUPPORTED;
+    if (c.scratch_bytes < etm_rollout_trxl_group_scratch_bytes(p.nb)) return ETM_EWORKSPACE;
   } else {
-    if (!etm_rollout_trxl_supported(D, H, L, hid, A, nb) || etm_rollout_trxl_grid(W, H) > 256) return ETM_EUNSUPPORTED;   // all teams resident
-    if (scratch_bytes < etm_rollout_trxl_scratch_bytes(W, D, H, nb)) return ETM_EWORKSPACE;
+    if (!etm_rollout_trxl_supported(p.D, p.H, p.L, p.hid, p.A, p.nb) || etm_rollout_trxl_grid(p.W, p.H) > 256) return ETM_EUNSUPPORTED;   // all teams resident
+    if (c.scratch_bytes < etm_rollout_trxl_scratch_bytes(p.W, p.D, p.H, p.nb)) return ETM_EWORKSPACE;
   }
-  RfParams p{};
-  if (const int rc = etm_branches_make(branch_sizes, n_branches, A, &p.br)) return rc;
-  if (box) p.box = *box;                               // (RfParams{}: box.bx.A == 0 selects the categorical instantiations)
-  p.ss = (const long long *)ss; p.mask_table = mask_table; p.index_table = (const long long *)index_table; p.st_mask = st_mask;
-  p.st_idx = (long long *)st_idx; p.latch = (long long *)latch; p.t_row = (long long *)t_row; p.mask_t = mask_t; p.win_t = (long long *)win_t;
-  p.kv_init = kv_init; p.T = T; p.am = (const long long *)action_mask; p.st_means = means ? st_means : nullptr;
-  p.st_logps = logps ? st_logps : nullptr;
-  p.h_in = h_in; p.h_bias = h_bias; p.h_splits = h_splits; p.wemb_t = wemb_t; p.bemb = bemb; p.nb = nb;
-  for (int b = 0; b < nb; ++b) {
-    const float *const *q = reinterpret_cast<const float *const *>(blocks) + RF_BLOCK_PTRS * b;
+  if (const int rc = etm_branches_make(c.branch_sizes, c.n_branches, p.A, &p.br)) return rc;
+  for (int b = 0; b < p.nb; ++b) {
+    const float *const *q = reinterpret_cast<const float *const *>(c.blocks) + RF_BLOCK_PTRS * b;
     for (int k = 0; k < 9; ++k) if (!q[k]) return ETM_EINVAL;
-    if (gtrxl) for (int k = 9; k < 17; ++k) if (!q[k]) return ETM_EINVAL;
+    if (p.gtrxl) for (int k = 9; k < 17; ++k) if (!q[k]) return ETM_EINVAL;
     if ((q[17] == nullptr) != (q[18] == nullptr)) return ETM_EINVAL;
     p.blk[b] = RfBlock{q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8],
                        RfGate{q[9], q[10], q[11], q[12]}, RfGate{q[13], q[14], q[15], q[16]}, q[17], q[18]};
   }
-  p.pre_ln = pre_ln; p.gtrxl = gtrxl; p.merge_gate = etm_rollout_trxl_gate_merged(D, H);
-  p.kv = kv; p.kv_w_stride = kv_worker_stride; p.kv_row_stride = kv_row_stride;
-  p.win = (const long long *)win; p.mask = mask; p.items = items; p.wh_t = wh_t; p.bh = bh; p.wp = wp; p.bp = bp; p.wv = wv; p.bv = bv;
-  p.uniforms = uniforms; p.forced = (const long long *)forced; p.t_dev = (long long *)t_dev; p.actions = (long long *)actions;
-  p.st_actions = (long long *)st_actions; p.st_logp = st_logp; p.st_values = st_values; p.host_actions = (long long *)host_actions;
-  p.host_flag = (long long *)host_flag; p.sync_counter = (int *)sync_counter;
-  p.n_slots = 6 * nb + 2;
-  p.wkv = wkv; p.pos = pos; p.step_l = (const long long *)step_l; p.slot_l = (const long long *)slot_l; p.kv_out = kv; p.bank = bank;
-  p.bank_slot_stride = bank_slot_stride; p.bank_row_stride = bank_row_stride; p.bank_block_stride = bank_block_stride;
-  p.ctl = (long long *)scratch;
-  p.xbuf = reinterpret_cast<float *>((char *)scratch + 64);
-  p.W = W; p.D = D; p.H = H; p.L = L; p.hid = hid; p.A = A; p.stage_W = stage_W; p.P = P;
-  p.eps = ln_eps; p.sqrt_d = (float)sqrt((double)D);
-  hipStream_t st = (hipStream_t)stream;
-  EtmProfScope prof(ETM_K_ROLLOUT_FUSED, st);
-  if (group) return etm_rf_launch_group(p, st);        // csrc/rollout_group.hip: weights once per group and step (gated layouts)
+  // what the kernels take besides the entry's arguments
+  p.merge_gate = etm_rollout_trxl_gate_merged(p.D, p.H);
+  p.n_slots = 6 * p.nb + 2;
+  p.ctl = (long long *)c.scratch;
+  p.xbuf = reinterpret_cast<float *>((char *)c.scratch + 64);
+  p.sqrt_d = (float)sqrt((double)p.D);
+  EtmProfScope prof(ETM_K_ROLLOUT_FUSED, c.stream);
+  if (c.group) return etm_rf_launch_group(p, c.stream);        // csrc/rollout_group.hip: weights once per group and step (gated layouts)
   p.map_mode = g_rf_placement;
-  const dim3 grid((unsigned)etm_rollout_trxl_grid(W, H)), block(RF_T);
-  // rows per thread of the per-block product slices: 20 registers x 4 are enough at D = 384, 32 at D = 512
-  const bool small = rf_rows(D, H) == 20;
-  const bool gen = pre_ln || gtrxl, box_k = p.box.bx.A > 0;
-#define RF_LAUNCH(GR_, LM_)                                                                                      \
-  do {                                                                                                           \
-    if (box_k && p.st_means) {                                                                                   \
-      if (gen) hipLaunchKernelGGL((rollout_trxl_gaussian_means_kernel<GR_, LM_, true>), grid, block, 0, st, p);  \
-      else hipLaunchKernelGGL((rollout_trxl_gaussian_means_kernel<GR_, LM_, false>), grid, block, 0, st, p);     \
-    } else if (box_k) {                                                                                          \
-      if (gen) hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, true, true>), grid, block, 0, st, p);           \
-      else hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, false, true>), grid, block, 0, st, p);              \
-    } else if (p.st_logps && p.am) {                                                                             \
-      if (gen) hipLaunchKernelGGL((rollout_trxl_logps_kernel<GR_, LM_, true, true>), grid, block, 0, st, p);     \
-      else hipLaunchKernelGGL((rollout_trxl_logps_kernel<GR_, LM_, false, true>), grid, block, 0, st, p);        \
-    } else if (p.st_logps) {                                                                                     \
-      if (gen) hipLaunchKernelGGL((rollout_trxl_logps_kernel<GR_, LM_, true, false>), grid, block, 0, st, p);    \
-      else hipLaunchKernelGGL((rollout_trxl_logps_kernel<GR_, LM_, false, false>), grid, block, 0, st, p);       \
-    } else if (p.am) {                                                                                           \
-      if (gen) hipLaunchKernelGGL((rollout_trxl_masked_kernel<GR_, LM_, true>), grid, block, 0, st, p);          \
-      else hipLaunchKernelGGL((rollout_trxl_masked_kernel<GR_, LM_, false>), grid, block, 0, st, p);             \
-    } else if (gen) hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, true, false>), grid, block, 0, st, p);     \
-    else hipLaunchKernelGGL((rollout_trxl_kernel<GR_, LM_, false, false>), grid, block, 0, st, p);               \
-  } while (0)
-  if (L <= 64) {
-    if (small) RF_LAUNCH(20, 64);
-    else RF_LAUNCH(32, 64);
-  } else {
-    if (small) RF_LAUNCH(20, 128);
-    else RF_LAUNCH(32, 128);
-  }
-#undef RF_LAUNCH
+  const int variant = c.box ? (p.st_means ? RF_BOX_MEANS : RF_BOX) : p.st_logps ? (p.am ? RF_LOGPS_MASKED : RF_LOGPS) : p.am ? RF_MASKED : RF_PLAIN;
+  // (rows per thread of the per-block product slices: 20 registers x 4 are enough at D = 384, 32 at D = 512)
+  const RfKernel kern = rf_kernels[rf_rows(p.D, p.H) == 20 ? 0 : 1][p.L <= 64 ? 0 : 1][p.pre_ln || p.gtrxl ? 1 : 0][variant];
+  hipLaunchKernelGGL(kern, dim3((unsigned)etm_rollout_trxl_grid(p.W, p.H)), dim3(RF_T), 0, c.stream, p);
   return etm_launch_status();
 }
+}  // namespace
 
-extern "C" int etm_rollout_trxl(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
-                                int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
-                                const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
-                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
-                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
-                                float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
-                                const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
-                                int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
-                                int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
-                                int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W, void *stream) {
-  return rollout_trxl_impl(0, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
-                          actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
-                          slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
-                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, nullptr, 1, nullptr, nullptr, stream);
+// The C signatures are fixed (include/etm_hip.h), so the shared head and middle of the 12 argument lists are spelled once here and
+// once in RF_FILL, which also opens the record `c`; the draw arguments of a categorical (T = int64_t) or Box (T = float) policy lie
+// between them, behind `uniforms` or `log_std, normals`.
+#define RF_HEAD_ARGS                                                                                                                      \
+  const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv, int64_t kv_worker_stride,     \
+      int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items, const float *wh_t, const float *bh, const float *wp,  \
+      const float *bp, const float *wv, const float *bv
+#define RF_DRAW_ARGS(T) const T *forced, int64_t *t_dev, T *actions, T *st_actions, float *st_logp, float *st_values, T *host_actions
+#define RF_MIDDLE_ARGS                                                                                                                    \
+  int64_t *host_flag, int32_t *sync_counter, float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos,     \
+      const int64_t *step_l, const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride,                      \
+      int64_t bank_block_stride, const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table,                        \
+      const int64_t *index_table, uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,    \
+      const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid
+#define RF_FILL(form)                                                                                                                     \
+  RfCall c{};                                                                                                                             \
+  c.group = form; c.blocks = blocks; c.scratch = scratch; c.scratch_bytes = scratch_bytes; c.n_branches = 1; c.stream = (hipStream_t)stream; \
+  c.p.h_in = h_in; c.p.wemb_t = wemb_t; c.p.bemb = bemb; c.p.nb = nb; c.p.kv = c.p.kv_out = kv; c.p.kv_w_stride = kv_worker_stride;                   \
+  c.p.kv_row_stride = kv_row_stride; c.p.win = (const long long *)win; c.p.mask = mask; c.p.items = items; c.p.wh_t = wh_t; c.p.bh = bh; \
+  c.p.wp = wp; c.p.bp = bp; c.p.wv = wv; c.p.bv = bv;                                                                                     \
+  c.p.t_dev = (long long *)t_dev; c.p.st_logp = st_logp; c.p.st_values = st_values;                                                       \
+  c.p.host_flag = (long long *)host_flag; c.p.sync_counter = (int *)sync_counter; c.p.eps = ln_eps; c.p.wkv = wkv; c.p.pos = pos;        \
+  c.p.step_l = (const long long *)step_l; c.p.slot_l = (const long long *)slot_l; c.p.bank = bank;                                       \
+  c.p.bank_slot_stride = bank_slot_stride; c.p.bank_row_stride = bank_row_stride; c.p.bank_block_stride = bank_block_stride;             \
+  c.p.h_bias = h_bias; c.p.h_splits = h_splits; c.p.ss = (const long long *)ss; c.p.mask_table = mask_table;                             \
+  c.p.index_table = (const long long *)index_table; c.p.st_mask = st_mask; c.p.st_idx = (long long *)st_idx;                             \
+  c.p.latch = (long long *)latch; c.p.t_row = (long long *)t_row; c.p.mask_t = mask_t; c.p.win_t = (long long *)win_t;                   \
+  c.p.kv_init = kv_init; c.p.T = T; c.p.pre_ln = pre_ln; c.p.gtrxl = gtrxl; c.p.W = W; c.p.D = D; c.p.H = H; c.p.L = L; c.p.hid = hid;   \
+  c.p.stage_W = stage_W
+#define RF_FILL_CATEGORICAL                                                                                                               \
+  c.p.uniforms = uniforms; c.p.forced = (const long long *)forced; c.p.actions = (long long *)actions;                                   \
+  c.p.st_actions = (long long *)st_actions; c.p.host_actions = (long long *)host_actions
+#define RF_FILL_BRANCHES c.branch_sizes = branch_sizes; c.n_branches = n_branches; c.p.A = etm_branches_total(branch_sizes, n_branches)
+#define RF_FILL_BOX                                                                                                                       \
+  c.box = true; c.low = low; c.high = high; c.p.A = A; c.p.box.log_std = log_std; c.p.box.normals = normals; c.p.box.forced = forced;    \
+  c.p.box.actions = actions; c.p.box.st_actions = st_actions; c.p.box.host_actions = host_actions
+
+#define RF_ARGS RF_HEAD_ARGS, const float *uniforms, RF_DRAW_ARGS(int64_t), RF_MIDDLE_ARGS, int A, int stage_W, void *stream
+extern "C" int etm_rollout_trxl(RF_ARGS) {
+  RF_FILL(0); RF_FILL_CATEGORICAL; c.p.A = A;
+  return rollout_trxl_run(c);
 }
 // The group form (csrc/rollout_group.hip): same arguments, other matrix packings (see there) and scratch size
 // (etm_rollout_trxl_group_scratch_bytes); W <= 8 workers, GRU-gated blocks -- etm_rollout_trxl_group_supported.
-extern "C" int etm_rollout_trxl_group(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
-                                int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
-                                const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
-                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
-                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
-                                float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
-                                const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
-                                int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
-                                int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
-                                int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W, void *stream) {
-  return rollout_trxl_impl(1, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
-                          actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
-                          slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
-                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, nullptr, 1, nullptr, nullptr, stream);
+extern "C" int etm_rollout_trxl_group(RF_ARGS) {
+  RF_FILL(1); RF_FILL_CATEGORICAL; c.p.A = A;
+  return rollout_trxl_run(c);
 }
+#undef RF_ARGS
 
 // MultiDiscrete policies: the same two launches with the action branches given by their sizes (wp / bp = the branches' heads
 // concatenated, A = the sum of the sizes); uniforms, forced, st_actions and st_logp are [S, stage_W, B], actions and host_actions [W, B].
-extern "C" int etm_rollout_trxl_branched(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
-                                int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
-                                const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
-                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
-                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
-                                float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
-                                const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
-                                int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
-                                int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
-                                int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int stage_W, const int32_t *branch_sizes,
-                                int n_branches, void *stream) {
-  return rollout_trxl_impl(0, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
-                          actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
-                          slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
-                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, etm_branches_total(branch_sizes, n_branches), stage_W,
-                          branch_sizes, n_branches, nullptr, nullptr, stream);
+#define RF_BRANCHED_ARGS                                                                                                                  \
+  RF_HEAD_ARGS, const float *uniforms, RF_DRAW_ARGS(int64_t), RF_MIDDLE_ARGS, int stage_W, const int32_t *branch_sizes, int n_branches
+extern "C" int etm_rollout_trxl_branched(RF_BRANCHED_ARGS, void *stream) {
+  RF_FILL(0); RF_FILL_CATEGORICAL; RF_FILL_BRANCHES;
+  return rollout_trxl_run(c);
 }
-extern "C" int etm_rollout_trxl_group_branched(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
-                                int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
-                                const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
-                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
-                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
-                                float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
-                                const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
-                                int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
-                                int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
-                                int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int stage_W, const int32_t *branch_sizes,
-                                int n_branches, void *stream) {
-  return rollout_trxl_impl(1, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
-                          actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
-                          slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
-                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, etm_branches_total(branch_sizes, n_branches), stage_W,
-                          branch_sizes, n_branches, nullptr, nullptr, stream);
+extern "C" int etm_rollout_trxl_group_branched(RF_BRANCHED_ARGS, void *stream) {
+  RF_FILL(1); RF_FILL_CATEGORICAL; RF_FILL_BRANCHES;
+  return rollout_trxl_run(c);
 }
 // Invalid-action masks: the two branched launches (a Discrete policy is one branch, n_branches = 1) with action_mask [W] int64, the
 // words of this group's workers for this step (bit j = column j of the concatenated policy head is allowed; every branch has a valid
 // action -- the host's duty).  Device or pinned host memory: the sampling workgroup reads its word in place at the start of the launch,
 // where it fetches the step's uniforms.  ETM_EINVAL: NULL or misaligned mask; ETM_EUNSUPPORTED: more than 63 columns.
-extern "C" int etm_rollout_trxl_branched_masked(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
-                                int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
-                                const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
-                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
-                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
-                                float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
-                                const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
-                                int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
-                                int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
-                                int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int stage_W, const int32_t *branch_sizes,
-                                int n_branches, const int64_t *action_mask, void *stream) {
-  if (!action_mask) return ETM_EINVAL;
-  return rollout_trxl_impl(0, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
-                          actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
-                          slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
-                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, etm_branches_total(branch_sizes, n_branches), stage_W,
-                          branch_sizes, n_branches, nullptr, action_mask, stream);
+extern "C" int etm_rollout_trxl_branched_masked(RF_BRANCHED_ARGS, const int64_t *action_mask, void *stream) {
+  RF_FILL(0); RF_FILL_CATEGORICAL; RF_FILL_BRANCHES;
+  c.p.am = (const long long *)action_mask; c.need_mask = true;
+  return rollout_trxl_run(c);
 }
-extern "C" int etm_rollout_trxl_group_branched_masked(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
-                                int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
-                                const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
-                                const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
-                                float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
-                                float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,
-                                const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
-                                int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,
-                                int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T,
-                                int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int stage_W, const int32_t *branch_sizes,
-                                int n_branches, const int64_t *action_mask, void *stream) {
-  if (!action_mask) return ETM_EINVAL;
-  return rollout_trxl_impl(1, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced, t_dev,
-                          actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos, step_l,
-                          slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask, st_idx,
-                          latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, etm_branches_total(branch_sizes, n_branches), stage_W,
-                          branch_sizes, n_branches, nullptr, action_mask, stream);
+extern "C" int etm_rollout_trxl_group_branched_masked(RF_BRANCHED_ARGS, const int64_t *action_mask, void *stream) {
+  RF_FILL(1); RF_FILL_CATEGORICAL; RF_FILL_BRANCHES;
+  c.p.am = (const long long *)action_mask; c.need_mask = true;
+  return rollout_trxl_run(c);
 }
 // The exact categorical KL (`exact_kl: true`): the two masked launches with action_mask optional (NULL: no masks) and st_logps
 // [S, stage_W, sum(sizes)] (at this group's first worker, as st_actions) before the stream: every column's log-prob lg[j] - lse of
 // the row -- sampled, greedy or forced action alike; -inf for a masked-out column; the st_logp entry's bits at the taken action --,
 // stored by the sampling thread as it draws.  Every other output is the twin's, bit for bit.  ETM_EINVAL: NULL or 4-byte-misaligned st_logps.
-#define RF_LOGPS_ARGS                                                                                                                       \
-  const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv, int64_t kv_worker_stride,       \
-      int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items, const float *wh_t, const float *bh, const float *wp,    \
-      const float *bp, const float *wv, const float *bv, const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions,   \
-      int64_t *st_actions, float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,             \
-      float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos, const int64_t *step_l,                       \
-      const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride,                    \
-      const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table, uint8_t *st_mask,       \
-      int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t, const float *kv_init, int T, int pre_ln,           \
-      int gtrxl, int W, int D, int H, int L, int hid, int stage_W, const int32_t *branch_sizes, int n_branches,                            \
-      const int64_t *action_mask, float *st_logps, void *stream
-#define RF_LOGPS_PASS                                                                                                                       \
-  h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, uniforms, forced,      \
-      t_dev, actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, pos,     \
-      step_l, slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table, st_mask,  \
-      st_idx, latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, etm_branches_total(branch_sizes, n_branches),       \
-      stage_W, branch_sizes, n_branches, nullptr, action_mask, stream, false, nullptr, true, st_logps
-extern "C" int etm_rollout_trxl_branched_logps(RF_LOGPS_ARGS) { return rollout_trxl_impl(0, RF_LOGPS_PASS); }
-extern "C" int etm_rollout_trxl_group_branched_logps(RF_LOGPS_ARGS) { return rollout_trxl_impl(1, RF_LOGPS_PASS); }
-#undef RF_LOGPS_ARGS
-#undef RF_LOGPS_PASS
+extern "C" int etm_rollout_trxl_branched_logps(RF_BRANCHED_ARGS, const int64_t *action_mask, float *st_logps, void *stream) {
+  RF_FILL(0); RF_FILL_CATEGORICAL; RF_FILL_BRANCHES;
+  c.p.am = (const long long *)action_mask; c.p.st_logps = st_logps; c.need_logps = true;
+  return rollout_trxl_run(c);
+}
+extern "C" int etm_rollout_trxl_group_branched_logps(RF_BRANCHED_ARGS, const int64_t *action_mask, float *st_logps, void *stream) {
+  RF_FILL(1); RF_FILL_CATEGORICAL; RF_FILL_BRANCHES;
+  c.p.am = (const long long *)action_mask; c.p.st_logps = st_logps; c.need_logps = true;
+  return rollout_trxl_run(c);
+}
+#undef RF_BRANCHED_ARGS
 extern "C" int etm_rollout_trxl_supported_branched(int D, int H, int L, int hid, const int32_t *branch_sizes, int n_branches, int nb) {
   const int A = etm_branches_total(branch_sizes, n_branches);
   return A > 0 && etm_rollout_trxl_supported(D, H, L, hid, A, nb);
@@ -466,59 +403,37 @@ extern "C" int etm_rollout_trxl_group_supported_branched(int D, int H, int L, in
 // Box policies (diagonal Gaussian, A <= 8 dimensions): the same two launches with the A means as the policy head (wp [A, hid], bp [A]),
 // the draw of etm_sample_gaussian (normals / forced / st_actions [S, stage_W, A], NaN forced = "sample"; actions / host_actions [W, A]
 // receive the actions clipped to [low, high], HOST arrays of A floats or NULL = unbounded) and log_std [A] on the device.
-static int rollout_trxl_gaussian_impl(int group, const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb,
-                                      float *kv, int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask,
-                                      float *items, const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv,
-                                      const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev,
-                                      float *actions, float *st_actions, float *st_logp, float *st_values, float *host_actions,
-                                      int64_t *host_flag, int32_t *sync_counter, float ln_eps, void *scratch, int64_t scratch_bytes,
-                                      const float *wkv, const float *pos, const int64_t *step_l, const int64_t *slot_l, float *bank,
-                                      int64_t bank_slot_stride, int64_t bank_row_stride, int64_t bank_block_stride, const float *h_bias,
-                                      int h_splits, const int64_t *ss, const uint8_t *mask_table, const int64_t *index_table,
-                                      uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,
-                                      const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A,
-                                      int stage_W, const float *low, const float *high, void *stream, bool means = false,
-                                      float *st_means = nullptr) {
-  RfBox box{};
-  if (const int rc = etm_box_make(low, high, A, &box.bx)) return rc;
-  box.log_std = log_std; box.normals = normals; box.forced = forced;
-  box.actions = actions; box.st_actions = st_actions; box.host_actions = host_actions;
-  return rollout_trxl_impl(group, h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv,
-                           nullptr, nullptr, t_dev, nullptr, nullptr, st_logp, st_values, nullptr, host_flag, sync_counter, ln_eps, scratch,
-                           scratch_bytes, wkv, pos, step_l, slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits,
-                           ss, mask_table, index_table, st_mask, st_idx, latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid,
-                           A, stage_W, nullptr, 1, &box, nullptr, stream, means, st_means);
-}
-#define RF_GAUSSIAN_ARGS RF_GAUSSIAN_ARGS_HEAD, void *stream
-#define RF_GAUSSIAN_ARGS_HEAD                                                                                                              \
-  const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv, int64_t kv_worker_stride,      \
-      int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items, const float *wh_t, const float *bh, const float *wp,   \
-      const float *bp, const float *wv, const float *bv, const float *log_std, const float *normals, const float *forced, int64_t *t_dev, \
-      float *actions, float *st_actions, float *st_logp, float *st_values, float *host_actions, int64_t *host_flag,                       \
-      int32_t *sync_counter, float ln_eps, void *scratch, int64_t scratch_bytes, const float *wkv, const float *pos,                      \
-      const int64_t *step_l, const int64_t *slot_l, float *bank, int64_t bank_slot_stride, int64_t bank_row_stride,                       \
-      int64_t bank_block_stride, const float *h_bias, int h_splits, const int64_t *ss, const uint8_t *mask_table,                        \
-      const int64_t *index_table, uint8_t *st_mask, int64_t *st_idx, int64_t *latch, int64_t *t_row, uint8_t *mask_t, int64_t *win_t,    \
-      const float *kv_init, int T, int pre_ln, int gtrxl, int W, int D, int H, int L, int hid, int A, int stage_W, const float *low,     \
+#define RF_GAUSSIAN_ARGS                                                                                                                  \
+  RF_HEAD_ARGS, const float *log_std, const float *normals, RF_DRAW_ARGS(float), RF_MIDDLE_ARGS, int A, int stage_W, const float *low,   \
       const float *high
-#define RF_GAUSSIAN_PASS                                                                                                                   \
-  h_in, wemb_t, bemb, blocks, nb, kv, kv_worker_stride, kv_row_stride, win, mask, items, wh_t, bh, wp, bp, wv, bv, log_std, normals,     \
-      forced, t_dev, actions, st_actions, st_logp, st_values, host_actions, host_flag, sync_counter, ln_eps, scratch, scratch_bytes, wkv, \
-      pos, step_l, slot_l, bank, bank_slot_stride, bank_row_stride, bank_block_stride, h_bias, h_splits, ss, mask_table, index_table,    \
-      st_mask, st_idx, latch, t_row, mask_t, win_t, kv_init, T, pre_ln, gtrxl, W, D, H, L, hid, A, stage_W, low, high, stream
-extern "C" int etm_rollout_trxl_gaussian(RF_GAUSSIAN_ARGS) { return rollout_trxl_gaussian_impl(0, RF_GAUSSIAN_PASS); }
-extern "C" int etm_rollout_trxl_group_gaussian(RF_GAUSSIAN_ARGS) { return rollout_trxl_gaussian_impl(1, RF_GAUSSIAN_PASS); }
+extern "C" int etm_rollout_trxl_gaussian(RF_GAUSSIAN_ARGS, void *stream) {
+  RF_FILL(0); RF_FILL_BOX;
+  return rollout_trxl_run(c);
+}
+extern "C" int etm_rollout_trxl_group_gaussian(RF_GAUSSIAN_ARGS, void *stream) {
+  RF_FILL(1); RF_FILL_BOX;
+  return rollout_trxl_run(c);
+}
 // The same two entries with the policy's means staged as well: st_means [S, stage_W, A] next to st_actions (at this group's first
 // worker, as st_actions), forced action or not.  ETM_EINVAL: NULL or 4-byte-misaligned st_means.
-extern "C" int etm_rollout_trxl_gaussian_means(RF_GAUSSIAN_ARGS_HEAD, float *st_means, void *stream) {
-  return rollout_trxl_gaussian_impl(0, RF_GAUSSIAN_PASS, true, st_means);
+extern "C" int etm_rollout_trxl_gaussian_means(RF_GAUSSIAN_ARGS, float *st_means, void *stream) {
+  RF_FILL(0); RF_FILL_BOX;
+  c.p.st_means = st_means; c.need_means = true;
+  return rollout_trxl_run(c);
 }
-extern "C" int etm_rollout_trxl_group_gaussian_means(RF_GAUSSIAN_ARGS_HEAD, float *st_means, void *stream) {
-  return rollout_trxl_gaussian_impl(1, RF_GAUSSIAN_PASS, true, st_means);
+extern "C" int etm_rollout_trxl_group_gaussian_means(RF_GAUSSIAN_ARGS, float *st_means, void *stream) {
+  RF_FILL(1); RF_FILL_BOX;
+  c.p.st_means = st_means; c.need_means = true;
+  return rollout_trxl_run(c);
 }
-#undef RF_GAUSSIAN_ARGS_HEAD
 #undef RF_GAUSSIAN_ARGS
-#undef RF_GAUSSIAN_PASS
+#undef RF_FILL_BOX
+#undef RF_FILL_BRANCHES
+#undef RF_FILL_CATEGORICAL
+#undef RF_FILL
+#undef RF_MIDDLE_ARGS
+#undef RF_DRAW_ARGS
+#undef RF_HEAD_ARGS
 extern "C" int etm_rollout_trxl_supported_gaussian(int D, int H, int L, int hid, int A, int nb) {
   return A > 0 && A <= ETM_MAX_BOX && etm_rollout_trxl_supported(D, H, L, hid, A, nb);
 }

@@ -72,25 +72,7 @@ SIGNATURES = {
     "etm_rollout_trxl_supported": (_I, [_I, _I, _I, _I, _I, _I]),
     "etm_rollout_trxl_gate_merged": (_I, [_I, _I]),
     "etm_rollout_trxl_scratch_bytes": (_L, [_I, _I, _I, _I]),
-    "etm_rollout_trxl": (_I, [_P, _P, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F,
-                              _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I,
-                              _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "etm_rollout_trxl_group": (_I, [_P, _P, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F,
-                                    _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I,
-                                    _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "etm_rollout_trxl_branched": (_I, [_P, _P, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F,
-                                       _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I,
-                                       _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
-    "etm_rollout_trxl_group_branched": (_I, [_P, _P, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F,
-                                             _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I,
-                                             _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "etm_rollout_trxl_group_supported": (_I, [_I] * 8),
-    "etm_rollout_trxl_gaussian": (_I, [_P, _P, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                       _P, _F, _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                       _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "etm_rollout_trxl_group_gaussian": (_I, [_P, _P, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                             _P, _P, _F, _P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                             _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "etm_rollout_trxl_supported_branched": (_I, [_I, _I, _I, _I, _P, _I, _I]),
     "etm_rollout_trxl_supported_gaussian": (_I, [_I] * 6),
     "etm_rollout_trxl_group_supported_gaussian": (_I, [_I] * 8),
@@ -191,6 +173,15 @@ SIGNATURES = {
     "etm_profile_collect": (_I, [_P, _P]),
     "etm_ppo_loss": (_I, [_P, _P, _L, _P, _L, _P, _P, _P, _P, _D, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _L, _P, _I, _I, _P]),
 }
+# the step kernel (etm_rollout_trxl*, worker and group form alike): the shared head (h_in ... bv) and middle (host_flag ... hid) of its
+# argument lists; between them lie the draw arguments up to host_actions -- uniforms + 7 pointers (categorical) or log_std, normals + 7
+# (Box) --, behind them (A, stage_W), (stage_W, branch_sizes, n_branches) or (A, stage_W, low, high), and the stream
+_STEP_HEAD = [_P, _P, _P, _P, _I, _P, _L, _L] + [_P] * 9
+_STEP_MIDDLE = [_P, _P, _F, _P, _L] + [_P] * 5 + [_L] * 3 + [_P, _I] + [_P] * 10 + [_I] * 8
+for _name in ("etm_rollout_trxl", "etm_rollout_trxl_group"):
+    SIGNATURES[_name] = (_I, _STEP_HEAD + [_P] * 8 + _STEP_MIDDLE + [_I, _I, _P])
+    SIGNATURES[_name + "_branched"] = (_I, _STEP_HEAD + [_P] * 8 + _STEP_MIDDLE + [_I, _P, _I, _P])
+    SIGNATURES[_name + "_gaussian"] = (_I, _STEP_HEAD + [_P] * 9 + _STEP_MIDDLE + [_I, _I, _P, _P, _P])
 # invalid-action masks (ABI 58): the masked twins take the arguments of their entry with the mask word array in front of the stream
 for _name, _extra in (("etm_rollout_sample_branched", [_P]), ("etm_rollout_policy_branched", [_P]), ("etm_rollout_trxl_branched", [_P]),
                       ("etm_rollout_trxl_group_branched", [_P]), ("etm_heads_loss", [_P]), ("etm_heads_loss_branched", [_P]),

@@ -832,19 +832,144 @@ def _mask_words(action_mask, rows, total, what, device=True):
     return action_mask
 
 
-def _sizes_or_single(branches, A):
-    """Branch sizes for the masked entries, which take a Discrete policy as one branch."""
-    sizes = _branch_sizes(branches)
-    return (int(A),) if sizes is None else sizes
+def _box_bounds(low, high, A):
+    """HOST float arrays of the A bounds of a Box (None: unbounded on that side) for the kernels' launch-time bound table."""
+    import numpy as np
+    arr = lambda b: None if b is None else (ctypes.c_float * A)(*[float(x) for x in np.broadcast_to(np.asarray(b, dtype=np.float32), (A,))])
+    return arr(low), arr(high)
 
 
-def _check_logps_table(st_logps, st_values, A):
-    """The log-probs' staging table of the ``*_logps`` entries lies next to the other staging tables: float32 [S, W_total, A] (A = all
-    branches' columns together), contiguous, on their device."""
-    if (st_logps.dtype != torch.float32 or tuple(st_logps.shape) != (*st_values.shape[:2], A) or not st_logps.is_contiguous()
-            or st_logps.device != st_values.device):
-        raise ValueError(f"st_logps: need a contiguous float32 [{st_values.shape[0]}, {st_values.shape[1]}, {A}] table on the staging "
-                         f"tables' device, got {tuple(st_logps.shape)} {st_logps.dtype}")
+@dataclasses.dataclass(frozen=True, eq=False)
+class _DrawCall:
+    """The draw at the end of a rollout step -- sample the action, stage the step's rows -- as the 24 etm_rollout_sample* / _policy* /
+    _trxl* entries take it; ``_draw_call`` makes it and validates it once.  The variant of the C entry follows from what is set:
+    ``box`` -> *_gaussian (``st_means`` on top -> *_gaussian_means); else ``st_logps`` -> *_branched_logps (the mask optional),
+    ``action_mask`` alone -> *_branched_masked, ``sizes`` alone -> *_branched, nothing -> the single-branch entry."""
+    W: int
+    A: int                              # columns of the policy head: all branches' actions, or a Box's dimensions
+    draws: torch.Tensor                 # the pre-drawn uniforms [S, W_total(, B)], or a Box's normals [S, W_total, A]
+    forced: torch.Tensor                # (optional) the table of forced actions, shaped like ``draws``
+    t_dev: torch.Tensor
+    actions: torch.Tensor
+    st_actions: torch.Tensor
+    st_logp: torch.Tensor
+    st_values: torch.Tensor
+    w_off: int = 0                      # the group's first worker: where its slice of the [S, W_total, ...] tables starts
+    sizes: tuple = None                 # categorical: the branch table (a Discrete policy under a mask or with st_logps is one branch)
+    box: tuple = None                   # Box: (log_std, low, high)
+    action_mask: torch.Tensor = None
+    st_logps: torch.Tensor = None
+    st_means: torch.Tensor = None
+
+    @property
+    def suffix(self):
+        """Behind etm_rollout_sample / _policy / _trxl / _trxl_group -- the scheme lib.py derives the signatures by."""
+        if self.box is not None:
+            return "_gaussian" + ("_means" if self.st_means is not None else "")
+        return "_branched" + ("_logps" if self.st_logps is not None else "_masked" if self.action_mask is not None else "") if self.sizes else ""
+
+    @property
+    def cols(self):
+        """Entries per (step, worker) of ``draws`` / ``forced`` / ``st_actions``: a Box's dimensions, or one per branch."""
+        return self.A if self.box is not None else len(self.sizes) if self.sizes else 1
+
+    def _at(self, table, cols):
+        return None if table is None else table.data_ptr() + self.w_off * cols * table.element_size()
+
+    def draw_args(self):
+        """(log_std,) draws, forced, t_dev, actions, st_actions, st_logp, st_values -- the tables from the group's first worker on.
+        (A categorical policy stages one log-prob per branch, a Box policy the joint one.)"""
+        lead = [] if self.box is None else [_ptr(self.box[0])]
+        return lead + [self._at(self.draws, self.cols), self._at(self.forced, self.cols), _ptr(self.t_dev), _ptr(self.actions),
+                       self._at(self.st_actions, self.cols), self._at(self.st_logp, 1 if self.box is not None else self.cols),
+                       self._at(self.st_values, 1)]
+
+    @property
+    def a_arg(self):
+        """The entries with a branch table take no A."""
+        return [] if self.sizes else [self.A]
+
+    @property
+    def bounds(self):
+        return [] if self.box is None else list(_box_bounds(self.box[1], self.box[2], self.A))
+
+    def tail(self):
+        """The arguments behind the shape integers (behind ``stage_W``, where there is one), in the order of ``suffix``."""
+        if self.box is not None:
+            return [] if self.st_means is None else [self._at(self.st_means, self.A)]
+        t = list(_branch_table(self.sizes)) if self.sizes else []
+        if self.action_mask is not None or self.st_logps is not None:
+            t.append(_ptr(self.action_mask))
+        return t + ([] if self.st_logps is None else [self._at(self.st_logps, self.A)])
+
+
+def _draw_call(what, W, A, tables, w_off=0, branches=None, box=None, action_mask=None, st_logps=None, st_means=None):
+    """The record of the draw of the op ``what`` over ``W`` workers and ``A`` policy-head columns, its operands checked.  ``tables``:
+    (draws, forced, t_dev, actions, st_actions, st_logp, st_values), the first seven fields of the record."""
+    draws, forced, _, actions, st_actions, _, st_values = tables
+    if st_means is not None and box is None:
+        raise ValueError(f"{what}: st_means belongs to a Box policy")
+    if st_logps is not None and box is not None:
+        raise ValueError(f"{what}: st_logps belongs to a categorical policy")
+    if action_mask is not None and box is not None:
+        raise ValueError(f"{what}: a Box policy has no action mask")
+    sizes = None
+    if box is None:
+        sizes = _branch_sizes(branches)
+        if sizes is None and (action_mask is not None or st_logps is not None):
+            sizes = (int(A),)              # the masked / logps entries take a Discrete policy as one branch
+    c = _DrawCall(W, A, *tables, w_off, sizes, box, action_mask, st_logps, st_means)
+    if sizes is not None and sum(sizes) != A:
+        raise ValueError(f"{what}: branches {sizes} do not add up to the {A} " + ("logit columns" if what == "rollout_sample"
+                                                                                  else "rows of the policy head"))
+    if st_logps is not None:
+        # next to the other staging tables: float32 [S, W_total, A] (A = all branches' columns together), contiguous, on their device
+        if (st_logps.dtype != torch.float32 or tuple(st_logps.shape) != (*st_values.shape[:2], A) or not st_logps.is_contiguous()
+                or st_logps.device != st_values.device):
+            raise ValueError(f"st_logps: need a contiguous float32 [{st_values.shape[0]}, {st_values.shape[1]}, {A}] table on the staging "
+                             f"tables' device, got {tuple(st_logps.shape)} {st_logps.dtype}")
+    if action_mask is not None:
+        _mask_words(action_mask, W, A, what, device=False)
+    if box is not None:
+        # the float tables of a Box draw hold A entries per (step, worker): the kernels index them so
+        for name, t in (("normals", draws), ("forced", forced), ("st_actions", st_actions)):
+            if t is not None and (t.dim() != 3 or t.shape[2] != A or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError(f"{name}: need a contiguous float32 [S, W, {A}] table, got {tuple(t.shape)} {t.dtype}")
+        if actions.dtype != torch.float32 or tuple(actions.shape) != (W, A) or not actions.is_contiguous():
+            raise ValueError(f"actions: need a contiguous float32 [{W}, {A}] tensor, got {tuple(actions.shape)} {actions.dtype}")
+        if box[0].numel() != A:
+            raise ValueError(f"log_std: need {A} entries, got {box[0].numel()}")
+    if st_means is not None:
+        # next to st_actions: same shape, float32, contiguous
+        if (st_means.dtype != torch.float32 or st_means.shape != st_actions.shape or not st_means.is_contiguous()
+                or st_means.device != st_actions.device):
+            raise ValueError(f"st_means: need a contiguous float32 table of st_actions' shape {tuple(st_actions.shape)} on its device, "
+                             f"got {tuple(st_means.shape)} {st_means.dtype}")
+    return c
+
+
+_policy_sync = {}
+
+
+def _hand_over(host_actions, host_flag, t_dev):
+    """host_actions, host_flag (pinned, optional) and the arrival counter of the launch's workgroups, one per step counter."""
+    sync = _policy_sync.get(t_dev.data_ptr())
+    if sync is None:
+        sync = _policy_sync[t_dev.data_ptr()] = torch.zeros(1, dtype=torch.int32, device=t_dev.device)
+    return [_ptr(host_actions), _ptr(host_flag), _ptr(sync)]
+
+
+def _launch_draw(stem, call, *args):
+    name = "etm_rollout_" + stem + call.suffix
+    _lib.check(getattr(_lib.load(), name)(*args, _stream()), name)
+
+
+def _sample(head, value, name, tables, **policy):
+    """The sampling launch on the policy head's outputs ``head`` [W, A]: the logits, or a Box policy's means."""
+    W, A = head.shape
+    call = _draw_call("rollout_sample", W, A, tables, **policy)
+    head, value = _f32c(head, name), _f32c(value, "value")
+    _launch_draw("sample", call, _ptr(head), _ptr(value), *call.draw_args(), *call.bounds, W, *call.a_arg, *call.tail())
 
 
 def rollout_sample(logits, value, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values, branches=None, action_mask=None,
@@ -858,70 +983,8 @@ def rollout_sample(logits, value, uniforms, forced, t_dev, actions, st_actions, 
     ``st_logps`` (optional, float32 [S, W, sum]): every column's log-prob of the row is staged too -- the policy's distribution,
     sampled, greedy or forced action alike; -inf at a masked-out column (etm_rollout_sample_branched_logps, masks or not); None is
     exactly the call without."""
-    lib = _lib.load()
-    W, A = logits.shape
-    logits, value = _f32c(logits, "logits"), _f32c(value, "value")
-    if st_logps is not None:
-        sizes = _sizes_or_single(branches, A)
-        if sum(sizes) != A:
-            raise ValueError(f"rollout_sample: branches {sizes} do not add up to the {A} logit columns")
-        tab, nbr = _branch_table(sizes)
-        _check_logps_table(st_logps, st_values, A)
-        am = 0 if action_mask is None else _mask_words(action_mask, W, A, "rollout_sample", device=False).data_ptr()
-        _lib.check(lib.etm_rollout_sample_branched_logps(_ptr(logits), _ptr(value), _ptr(uniforms), _ptr(forced), _ptr(t_dev), _ptr(actions),
-                                                         _ptr(st_actions), _ptr(st_logp), _ptr(st_values), W, tab, nbr, am,
-                                                         _ptr(st_logps), _stream()), "etm_rollout_sample_branched_logps")
-        return
-    if action_mask is not None:
-        sizes = _sizes_or_single(branches, A)
-        if sum(sizes) != A:
-            raise ValueError(f"rollout_sample: branches {sizes} do not add up to the {A} logit columns")
-        tab, nbr = _branch_table(sizes)
-        am = _mask_words(action_mask, W, A, "rollout_sample", device=False)
-        _lib.check(lib.etm_rollout_sample_branched_masked(_ptr(logits), _ptr(value), _ptr(uniforms), _ptr(forced), _ptr(t_dev), _ptr(actions),
-                                                          _ptr(st_actions), _ptr(st_logp), _ptr(st_values), W, tab, nbr, am.data_ptr(),
-                                                          _stream()), "etm_rollout_sample_branched_masked")
-        return
-    sizes = _branch_sizes(branches)
-    if sizes is None:
-        _lib.check(lib.etm_rollout_sample(_ptr(logits), _ptr(value), _ptr(uniforms), _ptr(forced), _ptr(t_dev), _ptr(actions),
-                                          _ptr(st_actions), _ptr(st_logp), _ptr(st_values), W, A, _stream()), "etm_rollout_sample")
-        return
-    if sum(sizes) != A:
-        raise ValueError(f"rollout_sample: branches {sizes} do not add up to the {A} logit columns")
-    tab, nbr = _branch_table(sizes)
-    _lib.check(lib.etm_rollout_sample_branched(_ptr(logits), _ptr(value), _ptr(uniforms), _ptr(forced), _ptr(t_dev), _ptr(actions),
-                                               _ptr(st_actions), _ptr(st_logp), _ptr(st_values), W, tab, nbr, _stream()),
-               "etm_rollout_sample_branched")
-
-
-_policy_sync = {}
-
-
-def _box_bounds(low, high, A):
-    """HOST float arrays of the A bounds of a Box (None: unbounded on that side) for the kernels' launch-time bound table."""
-    import numpy as np
-    arr = lambda b: None if b is None else (ctypes.c_float * A)(*[float(x) for x in np.broadcast_to(np.asarray(b, dtype=np.float32), (A,))])
-    return arr(low), arr(high)
-
-
-def _check_box_tables(A, W, log_std, normals, forced, actions, st_actions):
-    """The float tables of a Box draw must hold A entries per (step, worker): the kernels index them so."""
-    for name, t in (("normals", normals), ("forced", forced), ("st_actions", st_actions)):
-        if t is not None and (t.dim() != 3 or t.shape[2] != A or t.dtype != torch.float32 or not t.is_contiguous()):
-            raise ValueError(f"{name}: need a contiguous float32 [S, W, {A}] table, got {tuple(t.shape)} {t.dtype}")
-    if actions.dtype != torch.float32 or tuple(actions.shape) != (W, A) or not actions.is_contiguous():
-        raise ValueError(f"actions: need a contiguous float32 [{W}, {A}] tensor, got {tuple(actions.shape)} {actions.dtype}")
-    if log_std.numel() != A:
-        raise ValueError(f"log_std: need {A} entries, got {log_std.numel()}")
-
-
-def _check_means_table(st_means, st_actions):
-    """The means' staging table of the ``*_gaussian_means`` entries lies next to ``st_actions``: same shape, float32, contiguous."""
-    if (st_means.dtype != torch.float32 or st_means.shape != st_actions.shape or not st_means.is_contiguous()
-            or st_means.device != st_actions.device):
-        raise ValueError(f"st_means: need a contiguous float32 table of st_actions' shape {tuple(st_actions.shape)} on its device, "
-                         f"got {tuple(st_means.shape)} {st_means.dtype}")
+    _sample(logits, value, "logits", (uniforms, forced, t_dev, actions, st_actions, st_logp, st_values), branches=branches,
+            action_mask=action_mask, st_logps=st_logps)
 
 
 def rollout_sample_gaussian(mean, value, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values, low=None, high=None,
@@ -930,57 +993,19 @@ def rollout_sample_gaussian(mean, value, log_std, normals, forced, t_dev, action
     x = mean + exp(log_std) normals[t] (or ``forced[t]`` where it is not NaN), ``st_actions`` [S, W, A] = x, ``st_logp`` [S, W(, 1)]
     = log p(x), ``actions`` [W, A] = clip(x, low, high).  ``st_means`` (optional, float32 [S, W, A]): the means are staged too,
     forced action or not (etm_rollout_sample_gaussian_means); None is exactly the call without."""
-    lib = _lib.load()
-    W, A = mean.shape
-    mean, value = _f32c(mean, "mean"), _f32c(value, "value")
-    _check_box_tables(A, W, log_std, normals, forced, actions, st_actions)
-    lo, hi = _box_bounds(low, high, A)
-    if st_means is not None:
-        _check_means_table(st_means, st_actions)
-        _lib.check(lib.etm_rollout_sample_gaussian_means(_ptr(mean), _ptr(value), _ptr(log_std), _ptr(normals), _ptr(forced), _ptr(t_dev),
-                                                         _ptr(actions), _ptr(st_actions), _ptr(st_logp), _ptr(st_values), lo, hi, W, A,
-                                                         _ptr(st_means), _stream()),
-                   "etm_rollout_sample_gaussian_means")
-        return
-    _lib.check(lib.etm_rollout_sample_gaussian(_ptr(mean), _ptr(value), _ptr(log_std), _ptr(normals), _ptr(forced), _ptr(t_dev), _ptr(actions),
-                                               _ptr(st_actions), _ptr(st_logp), _ptr(st_values), lo, hi, W, A, _stream()),
-               "etm_rollout_sample_gaussian")
+    _sample(mean, value, "mean", (normals, forced, t_dev, actions, st_actions, st_logp, st_values), box=(log_std, low, high), st_means=st_means)
 
 
-def rollout_policy_gaussian(h2, mean_head, value_head, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values,
-                            low=None, high=None, host_actions=None, host_flag=None, h_bias=None, w_off=0, st_means=None):
-    """``rollout_policy`` for a Box policy (etm_rollout_policy_gaussian): the heads, the draw of ``rollout_sample_gaussian`` and the
-    hand-over of the clipped float actions (``host_actions``: pinned float32 [W, A]) in one launch.  ``st_means``: as in
-    ``rollout_sample_gaussian`` ([S, W_total, A], this group's slice taken as for ``st_actions``; etm_rollout_policy_gaussian_means)."""
-    lib = _lib.load()
-    W, A = h2.shape[0], mean_head.weight.shape[0]
-    hid = h2.shape[1] // 2
-    h2 = _f32c(h2, "h2")
-    ha = 0 if host_actions is None else host_actions.data_ptr()
-    hf = 0 if host_flag is None else host_flag.data_ptr()
-    sync = _policy_sync.get(t_dev.data_ptr())
-    if sync is None:
-        sync = _policy_sync[t_dev.data_ptr()] = torch.zeros(1, dtype=torch.int32, device=h2.device)
-    stage_w = st_values.shape[1]
-    _check_box_tables(A, W, log_std, normals, forced, actions, st_actions)
-    off = lambda t: None if t is None else t.data_ptr() + w_off * A * t.element_size()      # [S, W_total, A] tables
-    lo, hi = _box_bounds(low, high, A)
-    if st_means is not None:
-        _check_means_table(st_means, st_actions)
-        _lib.check(lib.etm_rollout_policy_gaussian_means(_ptr(h2), _ptr(h_bias), _ptr(mean_head.weight), _ptr(mean_head.bias),
-                                                         _ptr(value_head.weight), _ptr(value_head.bias), _ptr(log_std), off(normals),
-                                                         off(forced), _ptr(t_dev), _ptr(actions), off(st_actions),
-                                                         st_logp.data_ptr() + w_off * st_logp.element_size(),
-                                                         st_values.data_ptr() + w_off * st_values.element_size(), ha, hf, _ptr(sync), lo, hi,
-                                                         W, A, hid, stage_w, off(st_means), _stream()),
-                   "etm_rollout_policy_gaussian_means")
-        return
-    _lib.check(lib.etm_rollout_policy_gaussian(_ptr(h2), _ptr(h_bias), _ptr(mean_head.weight), _ptr(mean_head.bias), _ptr(value_head.weight),
-                                               _ptr(value_head.bias), _ptr(log_std), off(normals), off(forced), _ptr(t_dev), _ptr(actions),
-                                               off(st_actions), st_logp.data_ptr() + w_off * st_logp.element_size(),
-                                               st_values.data_ptr() + w_off * st_values.element_size(), ha, hf, _ptr(sync), lo, hi, W, A,
-                                               hid, stage_w, _stream()),
-               "etm_rollout_policy_gaussian")
+def _policy(h2, name, policy_head, value_head, tables, host_actions, host_flag, h_bias, w_off, **policy):
+    """The heads + sampling launch on the hidden heads' outputs ``h2`` [W, 2 hid].  Worker groups: h2 / actions / forced /
+    host_actions cover this group's W workers; the draws and the staging arrays are [S, W_total(, B)] and are addressed from the
+    group's first worker ``w_off``."""
+    W, A = h2.shape[0], policy_head.weight.shape[0]
+    call = _draw_call("rollout_policy", W, A, tables, w_off, **policy)
+    h2 = _f32c(h2, name)
+    _launch_draw("policy", call, _ptr(h2), _ptr(h_bias), _ptr(policy_head.weight), _ptr(policy_head.bias), _ptr(value_head.weight),
+                 _ptr(value_head.bias), *call.draw_args(), *_hand_over(host_actions, host_flag, call.t_dev), *call.bounds, W, *call.a_arg,
+                 h2.shape[1] // 2, call.st_values.shape[1], *call.tail())
 
 
 def rollout_policy(h2, policy_head, value_head, uniforms, forced, t_dev, actions, st_actions, st_logp, st_values,
@@ -992,79 +1017,39 @@ def rollout_policy(h2, policy_head, value_head, uniforms, forced, t_dev, actions
     ``policy_head`` is then the branches' heads concatenated ([sum, hid]) and the tables are as in ``rollout_sample``.
     ``action_mask`` (optional): int64 [W] words of THIS group's workers, device or pinned host memory (read in place), as in
     ``rollout_sample`` (etm_rollout_policy_branched_masked)."""
+    _policy(h2, "h", policy_head, value_head, (uniforms, forced, t_dev, actions, st_actions, st_logp, st_values), host_actions, host_flag,
+            h_bias, w_off, branches=branches, action_mask=action_mask, st_logps=st_logps)
+
+
+def rollout_policy_gaussian(h2, mean_head, value_head, log_std, normals, forced, t_dev, actions, st_actions, st_logp, st_values,
+                            low=None, high=None, host_actions=None, host_flag=None, h_bias=None, w_off=0, st_means=None):
+    """``rollout_policy`` for a Box policy (etm_rollout_policy_gaussian): the heads, the draw of ``rollout_sample_gaussian`` and the
+    hand-over of the clipped float actions (``host_actions``: pinned float32 [W, A]) in one launch.  ``st_means``: as in
+    ``rollout_sample_gaussian`` ([S, W_total, A], this group's slice taken as for ``st_actions``; etm_rollout_policy_gaussian_means)."""
+    _policy(h2, "h2", mean_head, value_head, (normals, forced, t_dev, actions, st_actions, st_logp, st_values), host_actions, host_flag,
+            h_bias, w_off, box=(log_std, low, high), st_means=st_means)
+
+
+def _supported_entry(stem, A, gaussian):
+    """The *_supported entry of a policy kind and its action arguments: A dimensions of a Box policy, the number of actions, or the
+    branch table of a MultiDiscrete policy."""
     lib = _lib.load()
-    W, A = h2.shape[0], policy_head.weight.shape[0]
-    hid = h2.shape[1] // 2
-    h2 = _f32c(h2, "h")
-    ha = 0 if host_actions is None else host_actions.data_ptr()
-    hf = 0 if host_flag is None else host_flag.data_ptr()
-    sync = _policy_sync.get(t_dev.data_ptr())       # arrival counter of the launch's workgroups, one per step counter
-    if sync is None:
-        sync = _policy_sync[t_dev.data_ptr()] = torch.zeros(1, dtype=torch.int32, device=h2.device)
-    # worker groups: h2 / actions / forced / host_actions cover this group's W workers; uniforms and the staging arrays are
-    # [S, W_total(, B)] and are addressed from the group's first worker ``w_off``
-    stage_w = st_values.shape[1]
-    sizes = _branch_sizes(branches)
-    nb_ = 1 if sizes is None else len(sizes)
-    off = lambda t: None if t is None else t.data_ptr() + w_off * nb_ * t.element_size()
-    if st_logps is not None:
-        sizes1 = _sizes_or_single(branches, A)
-        if sum(sizes1) != A:
-            raise ValueError(f"rollout_policy: branches {sizes1} do not add up to the {A} rows of the policy head")
-        tab, nbr = _branch_table(sizes1)
-        _check_logps_table(st_logps, st_values, A)
-        am = 0 if action_mask is None else _mask_words(action_mask, W, A, "rollout_policy", device=False).data_ptr()
-        _lib.check(lib.etm_rollout_policy_branched_logps(_ptr(h2), _ptr(h_bias), _ptr(policy_head.weight), _ptr(policy_head.bias),
-                                                         _ptr(value_head.weight), _ptr(value_head.bias), off(uniforms), off(forced),
-                                                         _ptr(t_dev), _ptr(actions), off(st_actions), off(st_logp),
-                                                         st_values.data_ptr() + w_off * st_values.element_size(), ha, hf, _ptr(sync), W,
-                                                         hid, stage_w, tab, nbr, am,
-                                                         st_logps.data_ptr() + w_off * A * st_logps.element_size(), _stream()),
-                   "etm_rollout_policy_branched_logps")
-        return
-    if action_mask is not None:
-        tab, nbr = _branch_table(_sizes_or_single(branches, A))
-        am = _mask_words(action_mask, W, A, "rollout_policy", device=False)
-        _lib.check(lib.etm_rollout_policy_branched_masked(_ptr(h2), _ptr(h_bias), _ptr(policy_head.weight), _ptr(policy_head.bias),
-                                                          _ptr(value_head.weight), _ptr(value_head.bias), off(uniforms), off(forced),
-                                                          _ptr(t_dev), _ptr(actions), off(st_actions), off(st_logp),
-                                                          st_values.data_ptr() + w_off * st_values.element_size(), ha, hf, _ptr(sync), W,
-                                                          hid, stage_w, tab, nbr, am.data_ptr(), _stream()),
-                   "etm_rollout_policy_branched_masked")
-        return
+    if gaussian:
+        return getattr(lib, stem + "_gaussian"), (int(A),)
+    sizes = _branch_sizes(A)
     if sizes is None:
-        _lib.check(lib.etm_rollout_policy(_ptr(h2), _ptr(h_bias), _ptr(policy_head.weight), _ptr(policy_head.bias), _ptr(value_head.weight),
-                                          _ptr(value_head.bias), off(uniforms), off(forced), _ptr(t_dev), _ptr(actions), off(st_actions),
-                                          off(st_logp), off(st_values), ha, hf, _ptr(sync), W, A, hid, stage_w, _stream()),
-                   "etm_rollout_policy")
-        return
-    if sum(sizes) != A:
-        raise ValueError(f"rollout_policy: branches {sizes} do not add up to the {A} rows of the policy head")
-    tab, nbr = _branch_table(sizes)
-    _lib.check(lib.etm_rollout_policy_branched(_ptr(h2), _ptr(h_bias), _ptr(policy_head.weight), _ptr(policy_head.bias),
-                                               _ptr(value_head.weight), _ptr(value_head.bias), off(uniforms), off(forced), _ptr(t_dev),
-                                               _ptr(actions), off(st_actions), off(st_logp), st_values.data_ptr() + w_off * st_values.element_size(),
-                                               ha, hf, _ptr(sync), W, hid, stage_w, tab, nbr, _stream()),
-               "etm_rollout_policy_branched")
+        return getattr(lib, stem), (A if isinstance(A, int) else int(tuple(A)[0]),)
+    return getattr(lib, stem + "_branched"), _branch_table(sizes)
 
 
 def rollout_trxl_group_ok(fused_group, W, L, hid, A, gaussian=False):
     """Does the group form of the step kernel (etm_rollout_trxl_group, csrc/rollout_group.hip) take a worker group of W workers of
     this model?  ``fused_group``: ``ActorCriticModel._rfg`` (None: the model has no group packings).  ``A``: the number of actions,
-    or the branch sizes of a MultiDiscrete policy."""
+    or the branch sizes of a MultiDiscrete policy; ``gaussian``: A dimensions of a Box policy."""
     if fused_group is None:
         return False
-    lib = _lib.load()
-    if gaussian:               # Box policy of A dimensions (etm_rollout_trxl_group_supported_gaussian)
-        return bool(lib.etm_rollout_trxl_group_supported_gaussian(fused_group["D"], fused_group["H"], L, hid, int(A), fused_group["nb"], W,
-                                                                  fused_group["gtrxl"]))
-    sizes = _branch_sizes(A)
-    if sizes is None:
-        a = A if isinstance(A, int) else int(tuple(A)[0])
-        return bool(lib.etm_rollout_trxl_group_supported(fused_group["D"], fused_group["H"], L, hid, a, fused_group["nb"], W, fused_group["gtrxl"]))
-    tab, nbr = _branch_table(sizes)
-    return bool(lib.etm_rollout_trxl_group_supported_branched(fused_group["D"], fused_group["H"], L, hid, tab, nbr, fused_group["nb"], W,
-                                                              fused_group["gtrxl"]))
+    entry, a = _supported_entry("etm_rollout_trxl_group_supported", A, gaussian)
+    return bool(entry(fused_group["D"], fused_group["H"], L, hid, *a, fused_group["nb"], W, fused_group["gtrxl"]))
 
 
 def rollout_trxl_scratch(W, D, H, nb, device, group=False):
@@ -1089,14 +1074,8 @@ def rollout_trxl_supported(D, H, L, hid, A, nb, gaussian=False):
     """Does ``rollout_trxl`` handle these shapes (etm_rollout_trxl_supported)?  ``A``: the number of actions, or the branch sizes
     of a MultiDiscrete policy (etm_rollout_trxl_supported_branched); ``gaussian``: A dimensions of a Box policy
     (etm_rollout_trxl_supported_gaussian)."""
-    lib = _lib.load()
-    if gaussian:
-        return bool(lib.etm_rollout_trxl_supported_gaussian(D, H, L, hid, int(A), nb))
-    sizes = _branch_sizes(A)
-    if sizes is None:
-        return bool(lib.etm_rollout_trxl_supported(D, H, L, hid, A if isinstance(A, int) else int(tuple(A)[0]), nb))
-    tab, nbr = _branch_table(sizes)
-    return bool(lib.etm_rollout_trxl_supported_branched(D, H, L, hid, tab, nbr, nb))
+    entry, a = _supported_entry("etm_rollout_trxl_supported", A, gaussian)
+    return bool(entry(D, H, L, hid, *a, nb))
 
 
 def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head, uniforms, forced, t_dev, actions, st_actions, st_logp,
@@ -1104,7 +1083,8 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
                  action_mask=None, st_means=None, st_logps=None):
     """Transformer + hidden / output heads + sampling of one rollout step of a worker group in one launch (etm_rollout_trxl).
     ``fused``: the transposed fixed-address weight copies of ``ActorCriticModel.refresh_rollout_weights`` (dict with the host
-    pointer table ``blocks``); ``kv`` the group's K | V cache [W, T, blocks, 2D]; ``scratch`` from ``rollout_trxl_scratch``; the
+    pointer table ``blocks``; with the group packings, ``ActorCriticModel._rfg`` with "group": True, it selects the group form of the
+    kernel: same arguments); ``kv`` the group's K | V cache [W, T, blocks, 2D]; ``scratch`` from ``rollout_trxl_scratch``; the
     staging arguments as in ``rollout_policy``.  ``window`` = (ss, mask_table, index_table, st_mask, st_idx, latch, t_row, kv_init):
     the launch does the step's window lookup (and the cache reset of workers at episode step 0) itself -- no ``rollout_window``
     in front of it.  ``tail`` = (wkv [blocks, D, 2D], pos [T, D] or None, step_l [W], slot_l [W],
@@ -1119,101 +1099,33 @@ def rollout_trxl(h_in, fused, kv, win_t, mask_t, items, policy_head, value_head,
     (etm_rollout_trxl_gaussian_means / _group_gaussian_means).
     ``st_logps`` (optional, categorical policies only): the log-probs' staging table as in ``rollout_policy``
     (etm_rollout_trxl_branched_logps / _group_branched_logps, masks or not)."""
-    lib = _lib.load()
-    if st_means is not None and box is None:
-        raise ValueError("rollout_trxl: st_means belongs to a Box policy")
-    if st_logps is not None and box is not None:
-        raise ValueError("rollout_trxl: st_logps belongs to a categorical policy")
+    h_splits = 0 if h_bias is None else h_in.shape[0]          # with h_bias, h_in = [splits, W, D] slice sums of rollout_hidden_partial
+    W, D = h_in.shape[-2:]
+    L = win_t.shape[1]
+    A, hid = policy_head.weight.shape
+    call = _draw_call("rollout_trxl", W, A, (uniforms, forced, t_dev, actions, st_actions, st_logp, st_values), w_off, branches, box,
+                      action_mask, st_logps, st_means)
     h_in = _f32c(h_in, "h_in")
-    h_splits = 0
-    if h_bias is not None:        # h_in = [splits, W, D] slice sums of rollout_hidden_partial
-        h_splits = h_in.shape[0]
-        h_in_shape = h_in.shape[1:]
-    else:
-        h_in_shape = h_in.shape
-    w_args = (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+    w_args = [0] * 11
     if window is not None:        # (ss [2, W], mask_table, index_table, st_mask, st_idx, latch [2, W], t_row, kv_init or None)
         ss, mask_table, index_table, st_mask, st_idx, latch, t_row, kv_init = window
-        Lw = win_t.shape[1]
-        w_args = (_ptr(ss), _ptr(mask_table), _ptr(index_table), st_mask.data_ptr() + w_off * Lw * st_mask.element_size(),
-                  st_idx.data_ptr() + w_off * Lw * st_idx.element_size(), _ptr(latch), _ptr(t_row), _ptr(mask_t), _ptr(win_t),
-                  0 if kv_init is None else _ptr(kv_init), index_table.shape[0])
-    t_args = (0, 0, 0, 0, 0, 0, 0, 0)
+        w_args = [_ptr(ss), _ptr(mask_table), _ptr(index_table), st_mask.data_ptr() + w_off * L * st_mask.element_size(),
+                  st_idx.data_ptr() + w_off * L * st_idx.element_size(), _ptr(latch), _ptr(t_row), _ptr(mask_t), _ptr(win_t),
+                  _ptr(kv_init), index_table.shape[0]]
+    t_args = [0] * 8
     if tail is not None:
         wkv, pos, step_l, slot_l, bank = tail
         if not (wkv.is_contiguous() and bank.stride(3) == 1 and (pos is None or pos.is_contiguous())):
             raise ValueError("rollout_trxl tail: wkv / pos contiguous and a bank with contiguous feature rows expected")
         # bank [slots, T, blocks, D] by STRIDES: the episode bank is block-major in memory (buffer.py), upstream's layout as a view
-        t_args = (_ptr(wkv), 0 if pos is None else _ptr(pos), _ptr(step_l), _ptr(slot_l), _ptr(bank), bank.stride(0), bank.stride(1),
-                  bank.stride(2))
-    W, D = h_in_shape
-    L = win_t.shape[1]
-    A, hid = policy_head.weight.shape
-    sync = _policy_sync.get(t_dev.data_ptr())
-    if sync is None:
-        sync = _policy_sync[t_dev.data_ptr()] = torch.zeros(1, dtype=torch.int32, device=h_in.device)
-    stage_w = st_values.shape[1]
-    sizes = _branch_sizes(branches)
-    nb_ = 1 if sizes is None else len(sizes)
-    off = lambda t: None if t is None else t.data_ptr() + w_off * nb_ * t.element_size()
-    ha = 0 if host_actions is None else host_actions.data_ptr()
-    hf = 0 if host_flag is None else host_flag.data_ptr()
-    args = (_ptr(h_in), _ptr(fused["emb_t"]), _ptr(fused["emb_b"]), fused["blocks"], fused["nb"], _ptr(kv), kv.stride(0),
-            kv.stride(1), _ptr(win_t), _ptr(mask_t), _ptr(items), _ptr(fused["heads_t"]), _ptr(fused["heads_b"]),
-            _ptr(policy_head.weight), _ptr(policy_head.bias), _ptr(value_head.weight), _ptr(value_head.bias),
-            off(uniforms), off(forced), _ptr(t_dev), _ptr(actions), off(st_actions), off(st_logp),
-            st_values.data_ptr() + w_off * st_values.element_size(), ha, hf, _ptr(sync), float(fused["eps"]), _ptr(scratch),
-            scratch.numel() * 8, *t_args, 0 if h_bias is None else _ptr(h_bias), h_splits, *w_args, int(fused.get("pre_ln", 0)),
-            int(fused.get("gtrxl", 0)), W, D, fused["H"], L, hid)
-    # ``fused`` with the group packings (ActorCriticModel._rfg, "group": True) selects the group form of the kernel: same arguments
-    group = bool(fused.get("group"))
-    if st_logps is not None:
-        sizes1 = _sizes_or_single(branches, A)
-        if sum(sizes1) != A:
-            raise ValueError(f"rollout_trxl: branches {sizes1} do not add up to the {A} rows of the policy head")
-        tab, nbr = _branch_table(sizes1)
-        _check_logps_table(st_logps, st_values, A)
-        am = 0 if action_mask is None else _mask_words(action_mask, W, A, "rollout_trxl", device=False).data_ptr()
-        entry, name = ((lib.etm_rollout_trxl_group_branched_logps, "etm_rollout_trxl_group_branched_logps") if group
-                       else (lib.etm_rollout_trxl_branched_logps, "etm_rollout_trxl_branched_logps"))
-        _lib.check(entry(*args, stage_w, tab, nbr, am, st_logps.data_ptr() + w_off * A * st_logps.element_size(), _stream()), name)
-        return
-    if action_mask is not None:
-        if box is not None:
-            raise ValueError("rollout_trxl: a Box policy has no action mask")
-        tab, nbr = _branch_table(_sizes_or_single(branches, A))
-        am = _mask_words(action_mask, W, A, "rollout_trxl", device=False)
-        entry, name = ((lib.etm_rollout_trxl_group_branched_masked, "etm_rollout_trxl_group_branched_masked") if group
-                       else (lib.etm_rollout_trxl_branched_masked, "etm_rollout_trxl_branched_masked"))
-        _lib.check(entry(*args, stage_w, tab, nbr, am.data_ptr(), _stream()), name)
-        return
-    if box is not None:
-        log_std, low, high = box
-        _check_box_tables(A, W, log_std, uniforms, forced, actions, st_actions)
-        offa = lambda t: None if t is None else t.data_ptr() + w_off * A * t.element_size()      # [S, W_total, A] tables
-        lo, hi = _box_bounds(low, high, A)
-        gargs = args[:17] + (_ptr(log_std), offa(uniforms), offa(forced), _ptr(t_dev), _ptr(actions), offa(st_actions),
-                             st_logp.data_ptr() + w_off * st_logp.element_size()) + args[23:]
-        if st_means is not None:
-            _check_means_table(st_means, st_actions)
-            entry, name = ((lib.etm_rollout_trxl_group_gaussian_means, "etm_rollout_trxl_group_gaussian_means") if group
-                           else (lib.etm_rollout_trxl_gaussian_means, "etm_rollout_trxl_gaussian_means"))
-            _lib.check(entry(*gargs, A, stage_w, lo, hi, offa(st_means), _stream()), name)
-            return
-        entry, name = ((lib.etm_rollout_trxl_group_gaussian, "etm_rollout_trxl_group_gaussian") if group
-                       else (lib.etm_rollout_trxl_gaussian, "etm_rollout_trxl_gaussian"))
-        _lib.check(entry(*gargs, A, stage_w, lo, hi, _stream()), name)
-        return
-    if sizes is None:
-        entry, name = (lib.etm_rollout_trxl_group, "etm_rollout_trxl_group") if group else (lib.etm_rollout_trxl, "etm_rollout_trxl")
-        _lib.check(entry(*args, A, stage_w, _stream()), name)
-        return
-    if sum(sizes) != A:
-        raise ValueError(f"rollout_trxl: branches {sizes} do not add up to the {A} rows of the policy head")
-    tab, nbr = _branch_table(sizes)
-    entry, name = ((lib.etm_rollout_trxl_group_branched, "etm_rollout_trxl_group_branched") if group
-                   else (lib.etm_rollout_trxl_branched, "etm_rollout_trxl_branched"))
-    _lib.check(entry(*args, stage_w, tab, nbr, _stream()), name)
+        t_args = [_ptr(wkv), _ptr(pos), _ptr(step_l), _ptr(slot_l), _ptr(bank), bank.stride(0), bank.stride(1), bank.stride(2)]
+    _launch_draw("trxl_group" if fused.get("group") else "trxl", call,
+                 _ptr(h_in), _ptr(fused["emb_t"]), _ptr(fused["emb_b"]), fused["blocks"], fused["nb"], _ptr(kv), kv.stride(0), kv.stride(1),
+                 _ptr(win_t), _ptr(mask_t), _ptr(items), _ptr(fused["heads_t"]), _ptr(fused["heads_b"]), _ptr(policy_head.weight),
+                 _ptr(policy_head.bias), _ptr(value_head.weight), _ptr(value_head.bias), *call.draw_args(),
+                 *_hand_over(host_actions, host_flag, t_dev), float(fused["eps"]), _ptr(scratch), scratch.numel() * 8, *t_args, _ptr(h_bias),
+                 h_splits, *w_args, int(fused.get("pre_ln", 0)), int(fused.get("gtrxl", 0)), W, D, fused["H"], L, hid,
+                 *call.a_arg, st_values.shape[1], *call.bounds, *call.tail())
 
 
 def gather_rows(fields, idx):

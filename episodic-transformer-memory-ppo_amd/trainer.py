@@ -1207,20 +1207,26 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             g.ss_dev.copy_(g.ss_pin, non_blocking=True)      # (streamed mode: uploaded with the observation rows)
             if g.am_pin is not None and not self._mask_in_place:
                 g.am_dev.copy_(g.am_pin, non_blocking=True)  # (the words' device twin: likewise)
-        branches = self.action_space_shape       # (one entry: Discrete; the kernels then take their single-branch entries)
         policy_head = m.rollout_policy_head()
-        # Box: the Gaussian forms of the sampling kernels -- normals in place of the uniforms, float forced / action tables
-        box = None if self.box is None else (m.policy_log_std, self.box.low, self.box.high)
-        draws = self._uniforms if box is None else self._normals
-        means = {"st_means": st["means"]} if self._kl_analytic else {}      # (kl_estimator: analytic; else exactly the calls of ever)
-        logps = {"st_logps": st["logps"]} if self._kl_exact_cat else {}     # (exact_kl, categorical; likewise)
         mask_t, win_t = g.mask_t, g.win_t
         # streamed + pipelined mode: the (step, slot) block is read from pinned host memory (see rollout_plan.plan_rollout)
         ss_src = g.ss_pin if stream_obs and g.stream is not None else g.ss_dev
         # action_masks: the words are read in place from pinned memory (or take the block's road); None without the key: the entries without masks
         am_src = None if g.am_pin is None else (g.am_pin if self._mask_in_place or (stream_obs and g.stream is not None) else g.am_dev)
         fused_step, rf, hidden = self._choose_step_form(g, obs_index is not None)
-        flag_pin = g.flag_pin if host_flag else None
+        # The draw's operands, once per call, for whichever op the step's form selects.  The policy part: a Box policy's (log_std, low,
+        # high) -- the Gaussian forms of the sampling kernels: normals in place of the uniforms, float forced / action tables -- and, with
+        # kl_estimator: analytic, the means' table; or the branches (one entry: Discrete; the kernels then take their single-branch
+        # entries), the mask words and, with exact_kl, the log-probs' table.  Without those keys exactly the calls of ever.
+        box = None if self.box is None else (m.policy_log_std, self.box.low, self.box.high)
+        if box is not None:
+            policy = {"st_means": st["means"]} if self._kl_analytic else {}
+        else:
+            policy = dict(branches=self.action_space_shape, action_mask=am_src, **({"st_logps": st["logps"]} if self._kl_exact_cat else {}))
+        # the staging part: the pre-drawn table, the forced actions, the step counter, the actions and the step's rows of the buffer
+        staging = (self._uniforms if box is None else self._normals, self._forced_tab, g.t_dev, g.act_dev, st["actions"], st["log_probs"],
+                   st["values"])
+        hand_over = dict(host_actions=g.act_pin, host_flag=g.flag_pin if host_flag else None, w_off=g.lo)
         if fused_step:
             # post-LN blocks without gates: the transformer, the heads and the sampling are ONE launch -- one workgroup per
             # worker walks the whole chain as matrix-vector products over the L2-resident weights (csrc/rollout_fused.hip);
@@ -1230,12 +1236,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             # ... and, after the action hand-over, the memory-bank write and the K | V projection of the new items (the tail;
             # pre-LN: the kernel applies norm_kv)
             tail = (self._kv_w_blocked, m.transformer._pos(), g.step_l, g.slot_l, buf.bank) if g.tail_in_kernel else None
-            ops.rollout_trxl(h_in, rf, g.kv, win_t, mask_t, g.item, policy_head, m.value,
-                             draws, self._forced_tab, g.t_dev, g.act_dev, st["actions"], st["log_probs"], st["values"],
-                             g.rf_scratch, host_actions=g.act_pin, host_flag=flag_pin, w_off=g.lo,
-                             tail=tail, h_bias=h_bias, branches=branches, box=box,
-                             window=(ss_src, self._mask_table, self._index_table, st["memory_mask"], st["memory_indices"],
-                                     g.ss_latch, g.t_row, self._kv_init), action_mask=am_src, **means, **logps)
+            ops.rollout_trxl(h_in, rf, g.kv, win_t, mask_t, g.item, policy_head, m.value, *staging, g.rf_scratch, tail=tail, h_bias=h_bias,
+                             box=box, window=(ss_src, self._mask_table, self._index_table, st["memory_mask"], st["memory_indices"],
+                                              g.ss_latch, g.t_row, self._kv_init), **hand_over, **policy)
             return g.item
         # window lookup + staging; the same launch records the staging row of this step for the tail (t_dev is incremented by
         # the sampling kernel) and resets the K/V cache of workers at episode step 0 (they start from the projection of an
@@ -1253,14 +1256,10 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             # host_flag_actions, the flag) says the launch is done
             h2, item = m.forward_hidden_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, raw=True, obs_rows=rows, **pk)
             if box is not None:
-                ops.rollout_policy_gaussian(h2, policy_head, m.value, box[0], draws, self._forced_tab, g.t_dev, g.act_dev,
-                                            st["actions"], st["log_probs"], st["values"], low=box[1], high=box[2],
-                                            host_actions=g.act_pin, host_flag=flag_pin, h_bias=m._b_heads, w_off=g.lo, **means)
+                ops.rollout_policy_gaussian(h2, policy_head, m.value, box[0], *staging, low=box[1], high=box[2], h_bias=m._b_heads,
+                                            **hand_over, **policy)
             else:
-                ops.rollout_policy(h2, policy_head, m.value, self._uniforms, self._forced_tab, g.t_dev,
-                                   g.act_dev, st["actions"], st["log_probs"], st["values"],
-                                   host_actions=g.act_pin, host_flag=flag_pin, h_bias=m._b_heads, w_off=g.lo, branches=branches,
-                                   action_mask=am_src, **logps)
+                ops.rollout_policy(h2, policy_head, m.value, *staging, h_bias=m._b_heads, **hand_over, **policy)
         else:
             if kv_spec is not None:
                 logits, value, item = m.forward_logits_cached(obs, kv_spec, items_out=g.item, obs_index=obs_index, obs_rows=rows, **pk)
@@ -1274,11 +1273,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             # one launch (several branches: their logits side by side)
             lg = logits[0] if len(logits) == 1 else torch.cat(logits, dim=1)
             if box is not None:       # (the means; host actions clipped to the bounds)
-                ops.rollout_sample_gaussian(lg, value, box[0], draws, self._forced_tab, g.t_dev, g.act_dev, st["actions"], st["log_probs"],
-                                            st["values"], low=box[1], high=box[2], **means)
+                ops.rollout_sample_gaussian(lg, value, box[0], *staging, low=box[1], high=box[2], **policy)
             else:
-                ops.rollout_sample(lg, value, self._uniforms, self._forced_tab, g.t_dev, g.act_dev,
-                                   st["actions"], st["log_probs"], st["values"], branches=branches, action_mask=am_src, **logps)
+                ops.rollout_sample(lg, value, *staging, **policy)
             g.act_pin.copy_(g.act_dev, non_blocking=True)
         if item.data_ptr() != g.item.data_ptr():
             g.item.copy_(item)

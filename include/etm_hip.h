@@ -232,6 +232,12 @@ int etm_rollout_window(const int64_t *step, const uint8_t *mask_table, const int
                        uint8_t *mask_t, int64_t *win_t, uint8_t *st_mask, int64_t *st_idx,
                        int64_t *t_row, int64_t *latch, float *reset_dst, const float *reset_init, int64_t reset_row_elems,
                        int W, int L, int stage_W, void *stream);
+/* REFUSALS of the six etm_rollout_sample* entries, in the order in which they win (a refused call launches nothing):
+ *   categorical: a NULL mandatory action_mask (*_masked); a NULL or 4-byte-misaligned st_logps (*_logps); a NULL mandatory pointer
+ *   (all but forced), W <= 0 or A <= 0 -- a branch table that is NULL, holds a size <= 0 or has more than 16 entries makes A = 0 --:
+ *   ETM_EINVAL; an action_mask that is not 8-byte aligned: ETM_EINVAL, then one over more than 63 columns: ETM_EUNSUPPORTED.
+ *   Gaussian: a NULL mandatory pointer (all but forced, low, high) or W <= 0; a NULL or misaligned st_means (*_means): ETM_EINVAL;
+ *   the Box table: A <= 0 ETM_EINVAL, A > 8 ETM_EUNSUPPORTED, a low above its high ETM_EINVAL. */
 int etm_rollout_sample(const float *logits, const float *value, const float *uniforms, const int64_t *forced, int64_t *t_dev,
                        int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W, int A, void *stream);
 /* MultiDiscrete (ABI 48): logits [W, sum sizes] hold the B = n_branches branches' segments side by side (branch b: columns
@@ -246,7 +252,7 @@ int etm_rollout_sample_branched(const float *logits, const float *value, const f
  * caller's duty: a word with an empty branch must not reach the device).  Per branch the logit of an invalid action reads as -inf in
  * front of the same sampling arithmetic: the draw (sampled, greedy) is the unmasked draw on the branch compacted to its valid
  * actions, the staged log-prob is l_a - lse over the valid actions; a forced action is taken as it is.  A Discrete policy is one
- * branch (n_branches = 1).  sum sizes <= 63 (else ETM_EUNSUPPORTED); ETM_EINVAL for a NULL or misaligned (8 bytes) action_mask. */
+ * branch (n_branches = 1).  sum sizes <= 63.  Refusals: see above. */
 int etm_rollout_sample_branched_masked(const float *logits, const float *value, const float *uniforms, const int64_t *forced,
                                        int64_t *t_dev, int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W,
                                        const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, void *stream);
@@ -255,8 +261,8 @@ int etm_rollout_sample_branched_masked(const float *logits, const float *value, 
  * st_logps before the stream: [S, W, sum sizes] (or [S, stage_W, sum sizes] at this group's first worker) next to st_actions.  It
  * receives l_j - lse of every column of every branch of the row -- the policy's distribution whether the action was sampled, taken
  * greedily (u < 0) or forced; exactly -inf for a masked-out column; at the taken action the st_logp entry's bits (the same expression
- * with the same lse).  Every other output is the twin's, bit for bit.  A Discrete policy is one branch.  ETM_EINVAL: NULL or
- * 4-byte-misaligned st_logps. */
+ * with the same lse).  Every other output is the twin's, bit for bit.  A Discrete policy is one branch.  Refusals: the family's
+ * comment of each entry. */
 int etm_rollout_sample_branched_logps(const float *logits, const float *value, const float *uniforms, const int64_t *forced,
                                       int64_t *t_dev, int64_t *actions, int64_t *st_actions, float *st_logp, float *st_values, int W,
                                       const int32_t *branch_sizes, int n_branches, const int64_t *action_mask, float *st_logps,
@@ -271,7 +277,7 @@ int etm_rollout_sample_gaussian(const float *mean, const float *value, const flo
 /* The exact Gaussian KL (ABI 61; `kl_estimator: analytic`): the *_gaussian_means form of each of the four Gaussian sampling entries
  * takes its twin's arguments and st_means before the stream -- [S, W, A] (or [S, stage_W, A] at this group's first worker) next to
  * st_actions -- and stores the policy's mean of every dimension there as well, forced action or not; every other output is the twin's,
- * bit for bit.  ETM_EINVAL: NULL or 4-byte-misaligned st_means. */
+ * bit for bit.  Refusals: the family's comment of each entry. */
 int etm_rollout_sample_gaussian_means(const float *mean, const float *value, const float *log_std, const float *normals, const float *forced,
                                       int64_t *t_dev, float *actions, float *st_actions, float *st_logp, float *st_values, const float *low,
                                       const float *high, int W, int A, float *st_means, void *stream);
@@ -620,7 +626,14 @@ int etm_rollout_heads(const float *h, const float *wp, const float *bp, const fl
  * system-scope fence the new step counter (*t_dev after the increment) is stored to *host_flag, so the host can spin on
  * the flag instead of waiting for an event.  sync_counter: one device int32, zero before the first call (the workgroups of a
  * launch count themselves in; the last one advances *t_dev and resets the counter).  forced: as in etm_rollout_sample, a
- * time-major table [S, stage_W] already offset to the group's first worker. */
+ * time-major table [S, stage_W] already offset to the group's first worker.
+ * REFUSALS of the six etm_rollout_policy* entries, in the order in which they win (a refused call launches nothing):
+ *   categorical: a NULL mandatory action_mask (*_masked); a NULL or 4-byte-misaligned st_logps (*_logps); a NULL mandatory pointer
+ *   (all but h_bias, forced, host_actions, host_flag), W, A or hid <= 0 (a bad branch table makes A = 0, as for etm_rollout_sample*),
+ *   stage_W < W; host_flag without host_actions: ETM_EINVAL; an action_mask that is not 8-byte aligned: ETM_EINVAL, then one over more
+ *   than 63 columns: ETM_EUNSUPPORTED.
+ *   Gaussian: a NULL or misaligned st_means (*_means); a NULL mandatory pointer (as above, and not low, high), W or hid <= 0,
+ *   stage_W < W; host_flag without host_actions: ETM_EINVAL; then the Box table as for etm_rollout_sample_gaussian. */
 int etm_rollout_policy(const float *h, const float *h_bias, const float *wp, const float *bp, const float *wv, const float *bv,
                        const float *uniforms, const int64_t *forced, int64_t *t_dev, int64_t *actions, int64_t *st_actions,
                        float *st_logp, float *st_values, int64_t *host_actions, int64_t *host_flag, int32_t *sync_counter,
@@ -689,7 +702,24 @@ int etm_rollout_policy_gaussian_means(const float *h, const float *h_bias, const
  *           followed by its D / P columns of Wv^T -- the cache columns member m reads are written by member m only; pos [T, D] or NULL;
  *           transformer.py:236-237 for the one new row) -- the memory-bank write and K | V projection of trainer.py:174.
  * Shape support: etm_rollout_trxl_supported(D, H, L, hid, A, nb) == 1 (D % (4 P) == 0, D <= 512, D / P <= 128, 2 hid / P <= 256,
- * H <= 8, L <= 128, nb <= 8, A < 64) and at most 256 workgroups (etm_rollout_trxl_grid(W, H)); ETM_EUNSUPPORTED otherwise. */
+ * H <= 8, L <= 128, nb <= 8, A < 64) and at most 256 workgroups (etm_rollout_trxl_grid(W, H)); ETM_EUNSUPPORTED otherwise.
+ * REFUSALS of the twelve etm_rollout_trxl* / etm_rollout_trxl_group* entries, in the order in which they win (a refused call launches
+ * nothing and writes nothing):
+ *    1. a NULL mandatory action_mask (*_masked): ETM_EINVAL; the Box table of the Gaussian entries: A <= 0 ETM_EINVAL, A > 8
+ *       ETM_EUNSUPPORTED, a low above its high ETM_EINVAL;
+ *    2. a NULL or 4-byte-misaligned st_means (*_means) or st_logps (*_logps): ETM_EINVAL;
+ *    3. ss without mask_table, index_table, st_mask, st_idx, latch, mask_t, win_t or with T <= 0; no ss and no win or no mask: ETM_EINVAL;
+ *    4. a NULL mandatory pointer -- h_in, wemb_t, bemb, blocks, kv, items, wh_t, bh, wp, bp, wv, bv, uniforms (Gaussian: log_std,
+ *       normals), actions, st_actions, t_dev, st_logp, st_values, sync_counter, scratch: ETM_EINVAL;
+ *    5. W, nb, D, H, L, hid or A <= 0 (a branch table that is NULL, holds a size <= 0 or has more than 16 entries makes A = 0),
+ *       stage_W < W, D % H != 0: ETM_EINVAL;
+ *    6. host_flag without host_actions: ETM_EINVAL;
+ *    7. an action_mask that is not 8-byte aligned: ETM_EINVAL, then one over more than 63 columns: ETM_EUNSUPPORTED;
+ *    8. wkv without step_l, slot_l or bank: ETM_EINVAL;   9. h_splits < 0, > 64, or > 0 without h_bias: ETM_EINVAL;
+ *   10. a shape outside the form's predicate (the worker form: or more than 256 workgroups; the group form: or a tail with
+ *       etm_rollout_trxl_team(H) != H): ETM_EUNSUPPORTED;   11. scratch_bytes below the form's scratch size: ETM_EWORKSPACE;
+ *   12. per block: a NULL among the first 9 pointers, with gtrxl != 0 among pointers 9 .. 16, or one of the two norm_kv pointers
+ *       without the other: ETM_EINVAL. */
 int etm_rollout_trxl_team(int H);
 /* Workgroup placement of the step kernel (process-wide; results do not depend on it): 0 (default) = the P members of a worker's
  * team on one XCD, 1 = XCD x hosts member x % P of an 8 / P-th of the workers, so that an XCD only ever reads one member's slice of
@@ -768,7 +798,7 @@ int etm_rollout_trxl_group_branched(const float *h_in, const float *wemb_t, cons
 /* Invalid-action masks (ABI 58): the two branched step launches with action_mask [W] int64 before the stream, the words of this
  * group's workers for this step in the layout of etm_rollout_sample_branched_masked (a Discrete policy is one branch).  Device or
  * pinned host memory: the sampling workgroup reads its words in place at the start of the launch, where the (step, slot) block is
- * read, so a read over the host link is hidden under the transformer.  Everything else as without masks. */
+ * read, so a read over the host link is hidden under the transformer.  Everything else as without masks; refusals: the list above. */
 int etm_rollout_trxl_branched_masked(const float *h_in, const float *wemb_t, const float *bemb, const void *const *blocks, int nb, float *kv,
                               int64_t kv_worker_stride, int64_t kv_row_stride, const int64_t *win, const uint8_t *mask, float *items,
                               const float *wh_t, const float *bh, const float *wp, const float *bp, const float *wv, const float *bv,
