@@ -251,6 +251,10 @@ SIGNATURES["etm_spot_room_supported"] = (_I, [_I, _I, _I, _I])
 SIGNATURES["etm_spot_room_state_bytes"] = (_L, [_I])
 SIGNATURES["etm_spot_room_reset"] = (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P])
 SIGNATURES["etm_spot_room_step"] = (_I, [_P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P])
+# attention statistics (csrc/attn_stats.hip; the ABI stays at 61): att [N, H, L] and the window mask -> sums per head, added to a table
+ATTN_STATS_WORDS = 264
+SIGNATURES["etm_attn_stats_workspace_bytes"] = (_L, [_I, _I, _I])
+SIGNATURES["etm_attn_stats"] = (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P])
 del _twin
 del _name, _extra, _res, _args
 

@@ -2152,6 +2152,55 @@ def obs_normalize(x, mean, rstd, clip, index=None, out=None):
     return out
 
 
+ATTN_STATS_WORDS = _lib.ATTN_STATS_WORDS
+
+
+def attn_stats(att, mask, table_rows, workspace):
+    """Add the statistics of the attention probabilities ``att`` [N, H, L] (float32, contiguous, as ``mha`` returns them) under the
+    window mask ``mask`` [N, L] (uint8, non-zero = valid: ``WindowSpec.mask``) to ``table_rows`` [H, 264] float64, IN PLACE
+    (etm_attn_stats; the words are listed in include/etm_hip.h).  ``workspace``: a uint8 device tensor of at least
+    etm_attn_stats_workspace_bytes(N, H, L) bytes, owned by the caller.  Two launches, capturable, deterministic."""
+    lib = _lib.load()
+    _need_dev(att, mask, table_rows, workspace)
+    if att.dtype != torch.float32 or att.dim() != 3 or not att.is_contiguous() or att.numel() == 0:
+        raise TypeError("attn_stats: att must be a non-empty contiguous float32 tensor [N, H, L]")
+    N, H, L = att.shape
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (N, L) or not mask.is_contiguous():
+        raise TypeError(f"attn_stats: mask must be a contiguous uint8 tensor [{N}, {L}]")
+    _f64c(table_rows, "attn_stats: table_rows", (H, ATTN_STATS_WORDS))
+    ws_bytes = lib.etm_attn_stats_workspace_bytes(N, H, L)
+    if ws_bytes <= 0:
+        raise ValueError(f"attn_stats: N = {N}, H = {H}, L = {L} (the kernel takes N >= 1, 1 <= H <= 32, 1 <= L <= 128)")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < ws_bytes:
+        raise TypeError(f"attn_stats: workspace must be a contiguous uint8 tensor of at least {ws_bytes} bytes")
+    _lib.check(lib.etm_attn_stats(_ptr(att), _ptr(mask), _ptr(table_rows), _ptr(workspace), workspace.numel(), N, H, L, _stream()),
+               "etm_attn_stats")
+    return table_rows
+
+
+class AttentionStatistics:
+    """Owner of the accumulator of ``attn_stats`` for a model: ``table`` [blocks, heads, 264] float64 and one workspace sized for
+    ``mbs``, the largest batch a pass will hand over -- both allocated once, so a captured graph can hold their addresses.
+    A forward pass hands ``table[block]`` and ``workspace`` to ``attn_stats``; ``reset()`` zeroes the table; ``read()`` returns it as
+    numpy (one device-to-host copy)."""
+
+    def __init__(self, blocks, heads, mbs, L, device):
+        lib = _lib.load()
+        self.blocks, self.heads, self.mbs, self.L = int(blocks), int(heads), int(mbs), int(L)
+        nbytes = lib.etm_attn_stats_workspace_bytes(self.mbs, self.heads, self.L)
+        if self.blocks < 1 or nbytes <= 0:
+            raise ValueError(f"AttentionStatistics: blocks = {blocks}, heads = {heads}, mbs = {mbs}, L = {L} (the kernel takes "
+                             "1 to 32 heads, a window of 1 to 128 entries and at least one sample)")
+        self.table = torch.zeros((self.blocks, self.heads, ATTN_STATS_WORDS), dtype=torch.float64, device=device)
+        self.workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+    def reset(self):
+        self.table.zero_()
+
+    def read(self):
+        return self.table.cpu().numpy()
+
+
 def return_scale_workspace(W, device):
     """A workspace of etm_return_scale for ``W`` workers, owned by the caller; its first float is the scale after a call."""
     return torch.zeros(int(_lib.load().etm_return_scale_workspace_bytes(int(W))), dtype=torch.uint8, device=device)

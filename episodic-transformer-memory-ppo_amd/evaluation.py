@@ -74,6 +74,7 @@ def evaluation_config(config: dict, n_workers: int, worker_steps: int) -> dict:
     cfg.pop("kl_estimator", None)                 # (no update ever reads a KL here: no means are staged, the sampling entries of ever)
     cfg.pop("exact_kl", None)                     # (likewise: no log-prob rows are staged either)
     cfg.pop("kl_penalty", None)                   # (likewise: it implies exact_kl, and no loss is ever formed here)
+    cfg.pop("attention_statistics", None)         # (only grad-enabled passes are counted, and none ever runs here)
     if cfg["environment"].get("type") != "Synthetic":
         cfg["environment"]["vectorize"] = "serial"
     return cfg

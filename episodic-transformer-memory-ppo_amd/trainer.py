@@ -53,7 +53,7 @@ from etm.optim import AdaptiveLr, FlatAdamW, KlGate
 from model import ActorCriticModel, IndexedObservations, PreviousStep
 from utils import (adaptive_lr_section, exact_kl_section, kl_estimator_section, kl_penalty_section, kl_penalty_step, normalization_section,
                    obs_reconstruction_coef, obs_reconstruction_section, polynomial_decay, process_episode_info, target_kl_rows,
-                   target_kl_section, previous_step_input_section)
+                   target_kl_section, previous_step_input_section, attention_statistics_section, attention_statistics_summary)
 from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
 from checkpoint import check_checkpoint_config, segment_first_worker_id
 from trainer_parts import _CheckpointResume, _DataParallelStep, _NativeRolloutDrive, _RunOutputs
@@ -327,6 +327,19 @@ def check_kl_penalty_config(config, world: int = 1):
     return out
 
 
+def check_attention_statistics_config(config, world: int = 1) -> bool:
+    """The optional key ``attention_statistics`` (utils.attention_statistics_section) -> False (absent or ``false``: nothing is
+    allocated, launched or changed) or True: every grad-enabled forward pass of an update adds its attention probabilities to a
+    per-block, per-head table (etm_attn_stats), read once per update into ``last_attention_statistics``.  Refused, each before
+    anything is built and each with what to do instead: a value that is no bool; the key in a data-parallel run (``world`` > 1):
+    every rank sees its own minibatches, and merging the ranks' tables is not built."""
+    on = attention_statistics_section(config)
+    if on and world > 1:
+        raise ValueError("attention_statistics: true in a data-parallel run: every rank would count the attention of its own minibatches "
+                         "only (merging the tables over the ranks is not built); remove the key, or train on one device")
+    return on
+
+
 def time_major(table, src):
     """The host table ``src`` [W, S(, B)] in the layout and type of the fixed-address device table ``table`` [S, W(, B)]."""
     x = torch.as_tensor(np.asarray(src), dtype=table.dtype)
@@ -380,6 +393,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         check_exact_kl_config(config, check_box_policy(config) is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
         pen_cfg = check_kl_penalty_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         obs_reconstruction_section(config, world=1 if dp is None else int(getattr(dp, "world", 1)))      # (the value; the observation's shape below)
+        attn_stats_on = check_attention_statistics_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
         # training state that a checkpoint carries over (trainer_parts._CheckpointResume): completed updates, the training segment (the
         # number of resumes so far; its environments' worker ids start at segment_first_worker_id), the last episodes' infos
         self.update_index, self.segment, self._episode_infos = 0, 0, deque(maxlen=100)
@@ -557,6 +571,16 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if self.dp is not None:
             self.dp.flat = self.flat_grads
         self._build_grad_groups()
+        # attention_statistics: the table every grad-enabled forward_window of the update adds to (ops.AttentionStatistics: fixed
+        # addresses, so the captured step holds them), zeroed at the start of every update and read once behind its read-back; the
+        # workspace takes any batch up to the whole buffer.  Not trainer state, not in the checkpoint.  ``last_attention_statistics``:
+        # utils.attention_statistics_summary of the last update's table -- its ``rows`` say how many rows were counted: every pass that
+        # was launched counts, also those of an update ``target_kl`` stopped (None without the key: nothing is allocated)
+        self._attn_stats, self.last_attention_statistics = None, None
+        if attn_stats_on:
+            t_ = config["transformer"]
+            self._attn_stats = ops.AttentionStatistics(t_["num_blocks"], t_["num_heads"], self.buffer.batch_size, t_["memory_length"], device)
+            self.model.transformer.attn_stats = self._attn_stats
         # target_kl: the gate of the KL early stop (etm/optim.py: KlGate), reset at the start of every update; not trainer state, not in
         # the checkpoint.  ``last_kl_stop``: what the last update's gate said (None without the key: nothing is allocated)
         self._kl_cfg, self._kl_gate, self.last_kl_stop = kl_cfg, None, None
@@ -1523,6 +1547,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             gate.reset()
         if self._adapt is not None:
             self._adapt.reset()
+        if self._attn_stats is not None:
+            self._attn_stats.reset()
         host_stop = False
         for epoch in range(self.config["epochs"]):
             if gate is not None and gate.host_word is not None and epoch > 0 and not host_stop:
@@ -1583,6 +1609,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             # (behind the phase's read-back: the table is complete, the copy waits for nothing) the float32 of the float64 mean
             losses = self._recon_tab[:min(rows, self._recon_tab.numel())].cpu().numpy()
             self.last_obs_reconstruction = {"loss": float(np.float32(losses.astype(np.float64).mean())), "coef": float(self._recon_coef_host)}
+        if self._attn_stats is not None:       # (behind the read-back too)
+            self.last_attention_statistics = attention_statistics_summary(self._attn_stats.read(), self.memory_length)
         self._bank_pos = self._row_stats = None
         self._mb_stats3 = self._epoch_stats3 = None
         grad_info = {}

@@ -221,6 +221,11 @@ class _RunOutputs:
             self.writer.add_scalar("other/obs_reconstruction_coef", self.last_obs_reconstruction["coef"], update)
         if self.last_valid_action_share is not None:     # (action_masks: mean share of allowed actions in the rollout's words)
             self.writer.add_scalar("other/valid_action_share", self.last_valid_action_share, update)
+        if self.last_attention_statistics is not None:   # (attention_statistics: per block and head, where the update's attention landed)
+            st = self.last_attention_statistics
+            for b, h in np.ndindex(st["rows"].shape):
+                for key in ("normalised_entropy", "mean_age", "max_prob"):
+                    self.writer.add_scalar(f"attention/b{b}h{h}_{key}", float(st[key][b, h]), update)
         if self.buffer.return_norm is not None:          # (the scale the last rollout's rewards were multiplied with)
             self.writer.add_scalar("training/return_scale", float(self.buffer.return_scale.item()), update)
         if self.model.obs_norm is not None:              # (the spread of the frozen table the next rollout runs on)

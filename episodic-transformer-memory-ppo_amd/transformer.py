@@ -219,6 +219,9 @@ class Transformer(nn.Module):
         self.embed_dim = config["embed_dim"]
         self.num_heads = config["num_heads"]
         self.max_episode_steps = max_episode_steps
+        # attention_statistics: an ops.AttentionStatistics the trainer hangs here; every grad-enabled forward_window then adds each
+        # block's attention probabilities to its table (None: nothing is launched)
+        self.attn_stats = None
         self.activation = nn.ReLU()
         self.linear_embedding = nn.Linear(input_dim, self.embed_dim)
         nn.init.orthogonal_(self.linear_embedding.weight, math.sqrt(2))
@@ -274,13 +277,16 @@ class Transformer(nn.Module):
             items = []
             h_res = None
             last = len(self.transformer_blocks) - 1
+            observe = self.attn_stats if torch.is_grad_enabled() else None
             for i, blk in enumerate(self.transformer_blocks):
                 if want_items:
                     items.append(h.detach())
                 if i < last:       # the state forked for the next block's two consumers (fused post-LN training path; None otherwise)
-                    h, _, h_res = blk.forward_window(h, spec, i, pos, h_res=h_res, fork=True)
+                    h, att, h_res = blk.forward_window(h, spec, i, pos, h_res=h_res, fork=True)
                 else:
-                    h, _ = blk.forward_window(h, spec, i, pos, h_res=h_res)
+                    h, att = blk.forward_window(h, spec, i, pos, h_res=h_res)
+                if observe is not None:
+                    ops.attn_stats(att, spec.mask, observe.table[i], observe.workspace)
         finally:
             # a gate that did not consume its packed operands (eager path at D > 1024, an exception above) must not find a pointer into
             # the shared buffer in a later, non-window forward()

@@ -259,6 +259,45 @@ def exact_kl_section(config: dict) -> bool:
     return bool(value)
 
 
+def attention_statistics_section(config: dict) -> bool:
+    """The optional key ``attention_statistics`` -> False (absent or ``false``: nothing is allocated, launched or changed) or True
+    (every grad-enabled forward pass of an update adds its attention probabilities to a per-block, per-head table).  A value that is
+    no bool is refused."""
+    value = config.get("attention_statistics", False)
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"attention_statistics must be true or false, got {value!r}; write `attention_statistics: true` to record where "
+                         "the policy's attention lands in its memory window, or remove the key")
+    return bool(value)
+
+
+ATTENTION_STATISTICS_WORDS = 264      # doubles per head of the table (include/etm_hip.h: etm_attn_stats)
+
+
+def attention_statistics_summary(table, memory_length: int) -> dict:
+    """The accumulator of etm_attn_stats, ``table`` [blocks, heads, 264] float64, as a dict of numpy arrays (a pure host function):
+    ``rows``, ``empty``, ``irregular`` [B, H]: the counted rows (a prefix mask with at least one valid entry), the rows without a
+    valid entry and the rows whose mask was no prefix; ``entropy`` (nats), ``max_prob``, ``mean_age`` [B, H]: means over the counted
+    rows; ``normalised_entropy`` [B, H]: the mean of entropy / ln v over the rows with v >= 2 valid entries -- each NaN where its
+    count is 0; ``age_hist``, ``index_hist`` [B, H, L]: the attention mass by age (``age_hist[..., a - 1]``: age a, 1 = the newest
+    stored step) and by window entry, each divided by its total mass (NaN without mass).  ``mean_age`` is the age histogram's mean.
+    Words beyond ``memory_length`` are padding and are not read."""
+    table = np.asarray(table, dtype=np.float64)
+    L = int(memory_length)
+    if table.ndim != 3 or table.shape[2] != ATTENTION_STATISTICS_WORDS or not 1 <= L <= 128:
+        raise ValueError(f"attention_statistics_summary: a table [blocks, heads, {ATTENTION_STATISTICS_WORDS}] and 1 <= memory_length "
+                         f"<= 128 are needed, got {table.shape} and {memory_length}")
+    rows, rows2 = table[:, :, 0], table[:, :, 1]
+    age, index = table[:, :, 8: 8 + L], table[:, :, 136: 136 + L]
+    age_mass, index_mass = age.sum(axis=2), index.sum(axis=2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per_row = lambda x, n: np.where(n > 0, x / n, np.nan)
+        return {"rows": rows.copy(), "empty": table[:, :, 2].copy(), "irregular": table[:, :, 3].copy(),
+                "entropy": per_row(table[:, :, 4], rows), "normalised_entropy": per_row(table[:, :, 5], rows2),
+                "max_prob": per_row(table[:, :, 6], rows),
+                "mean_age": per_row((age * np.arange(1, L + 1, dtype=np.float64)).sum(axis=2), age_mass),
+                "age_hist": per_row(age, age_mass[:, :, None]), "index_hist": per_row(index, index_mass[:, :, None])}
+
+
 def categorical_kl(old_logps, logits, sizes, mask_words=None, dtype=np.float64):
     """Exact KL(old || new) of categorical policies, the mean over the N samples AND the B branches (the convention of the k3 column it
     replaces; the joint KL of a sample's branches is B times it), in numpy ``dtype`` -- the one host definition of what the categorical

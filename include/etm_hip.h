@@ -1102,6 +1102,28 @@ int etm_spot_room_step(void *state, const int64_t *actions, int64_t act_stride, 
                        uint8_t *flags, float *returns, int32_t *lengths, int64_t *masks, int64_t *done_word, int64_t done_value, int W,
                        int G, int P, int N, int light_steps, int spot_period, int health, int max_steps, int64_t stream0, void *stream);
 
+/* Attention statistics (csrc/attn_stats.hip; added with the ABI left at 61 -- no signature above changes): where the attention
+ * probabilities att [N, H, L] of a training pass (the tensor every training attention kernel writes, contiguous) land in the memory
+ * window, per head, ADDED to table [H, ETM_ATTN_STATS_WORDS] doubles.  mask [N, L] bytes, non-zero = valid (WindowSpec.mask); v = the
+ * number of valid entries of mask[n].  A row (n, h) counts when the mask is a prefix (entries 0 .. v - 1 set, no others) and
+ * v >= 1; v = 0 is an empty row (its att is the uniform 1 / L a fully masked softmax leaves), any other mask an irregular row: both
+ * are counted as such and add nothing else.  The age of entry l is v - l: the newest stored step has age 1.  Words of a head:
+ *   0 counted rows; 1 counted rows with v >= 2; 2 empty rows; 3 irregular rows;
+ *   4 sum over counted rows of the entropy -sum_l p ln p (valid entries with p > 0, nats; fp32 logf, products and row sum);
+ *   5 sum over rows with v >= 2 of entropy / ln v; 6 sum over counted rows of max_l p over valid entries; 7 reserved (unchanged);
+ *   8 .. 135 age[a - 1] = sum over counted rows of p at age a; 136 .. 263 index[l] = the same at window entry l (words beyond L
+ *   receive + 0).  Sums across rows are double.
+ * Two launches on `stream` (per-workgroup partials in the workspace, then one thread per word adds the partials in index order to
+ * table), no atomics, nothing allocated: graph-capturable; the partial layout is a function of (N, H, L) alone, two calls on equal
+ * inputs give equal bits, and words of table outside the H heads are not touched.  Nothing is booked in the per-kernel profile.
+ *   etm_attn_stats_workspace_bytes: bytes of workspace a call needs (0 for arguments the call refuses).
+ * ETM_EINVAL, with nothing launched: a NULL att, mask, table or workspace; N < 1; H outside 1 .. 32; L outside 1 .. 128; table or
+ * workspace not 8-byte aligned; workspace_bytes below etm_attn_stats_workspace_bytes(N, H, L). */
+#define ETM_ATTN_STATS_WORDS 264
+int64_t etm_attn_stats_workspace_bytes(int N, int H, int L);
+int etm_attn_stats(const float *att, const uint8_t *mask, double *table, void *workspace, int64_t workspace_bytes, int N, int H, int L,
+                   void *stream);
+
 /* Monitored gradient norms of the module groups (model.py:128-151) from the flat gradient arena in two launches:
  * out[g] = sqrt(sum_s member[g][s] * ||flat[seg_start[s] .. seg_start[s] + seg_len[s])||^2).  Segments: runs of <= 4096 floats, each
  * inside one parameter tensor (device arrays seg_start int64 [n_segs], seg_len int32 [n_segs]); member [n_groups, n_segs] float
