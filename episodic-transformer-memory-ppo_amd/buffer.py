@@ -40,7 +40,8 @@ import numpy as np
 import torch
 
 from etm import ops
-from utils import exact_kl_section, kl_estimator_section, kl_penalty_section, normalization_section, previous_step_input_section
+from run_settings import kl_plumbing
+from utils import normalization_section, previous_step_input_section
 
 
 class Buffer:
@@ -92,9 +93,8 @@ class Buffer:
         # parameter moves during the update --, taken by ``prepare_batch_dict`` from ``log_std_source`` (the trainer sets it: the
         # model's policy_log_std); None without the key
         self.means = self.old_log_std = self.log_std_source = None
-        exact = exact_kl_section(config)      # (exact_kl: true on a Box policy is exactly kl_estimator: analytic)
-        exact = exact or kl_penalty_section(config) is not None      # (kl_penalty implies the exact KL's fields, for every policy kind)
-        if kl_estimator_section(config) == "analytic" or (exact and continuous):
+        kl_analytic, kl_exact_cat = kl_plumbing(config, continuous)      # (the rule the trainer stages by)
+        if kl_analytic:
             if not continuous:
                 raise ValueError("kl_estimator: analytic needs a Box (continuous) policy; remove the key")
             self.means = torch.zeros((W, S, B), dtype=torch.float32, device=dev)
@@ -102,7 +102,7 @@ class Buffer:
         # the exact categorical KL (exact_kl: true, Discrete / MultiDiscrete policies, masked or not): the rollout's log-probs of every
         # column of every branch [W, S, sum A_b] next to ``actions``, a member of ``samples_flat``; None without the key
         self.old_logps = None
-        if exact and not continuous:
+        if kl_exact_cat:
             self.old_logps = torch.zeros((W, S, sum(int(a) for a in action_space_shape)), dtype=torch.float32, device=dev)
 
         # previous_step_input (absent upstream): what the model is fed of step t - 1 at every sample -- ``prev_actions`` [W, S, B] int64

@@ -17,6 +17,7 @@ import time
 
 import torch
 
+from run_settings import KL_KEYS, check_evaluation_config
 from trainer import PPOTrainer
 from utils import process_episode_info
 
@@ -71,9 +72,8 @@ def evaluation_config(config: dict, n_workers: int, worker_steps: int) -> dict:
     cfg.pop("episode_bank_capacity", None)        # (sized for the training batch; the default never fills)
     cfg.pop("bootstrap_truncated", None)          # (no GAE target is ever used here; the rollout still strips the two info keys)
     cfg.pop("normalize_rewards", None)            # (likewise; normalize_observations stays: the model reads its table)
-    cfg.pop("kl_estimator", None)                 # (no update ever reads a KL here: no means are staged, the sampling entries of ever)
-    cfg.pop("exact_kl", None)                     # (likewise: no log-prob rows are staged either)
-    cfg.pop("kl_penalty", None)                   # (likewise: it implies exact_kl, and no loss is ever formed here)
+    for key in KL_KEYS:                           # (kl_estimator, exact_kl, kl_penalty: no update ever reads a KL and no loss is ever formed
+        cfg.pop(key, None)                        # here: neither means nor log-prob rows are staged, the sampling entries of ever)
     cfg.pop("attention_statistics", None)         # (only grad-enabled passes are counted, and none ever runs here)
     if cfg["environment"].get("type") != "Synthetic":
         cfg["environment"]["vectorize"] = "serial"
@@ -191,5 +191,4 @@ class Evaluator:
 
 def evaluation_defaults(config: dict) -> dict:
     """The ``evaluation`` section of ``config`` with the defaults filled in (also when the section is absent)."""
-    from trainer import check_evaluation_config
     return check_evaluation_config(config) or check_evaluation_config(dict(config, evaluation={}))

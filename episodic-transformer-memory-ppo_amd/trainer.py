@@ -44,18 +44,21 @@ def default_rollout_groups(num_workers: int, min_group: int) -> int:
 
 from buffer import Buffer
 from environments import action_space_kind, branch_bit_masks, empty_mask_branches, valid_action_share
-from environments.device_types import check_device_env_config, is_byte_only
 from environments.vec_env import make_vec_env
 from etm import lib as etm_lib
 from etm import ops
 from etm.ops import WindowSpec
 from etm.optim import AdaptiveLr, FlatAdamW, KlGate
 from model import ActorCriticModel, IndexedObservations, PreviousStep
-from utils import (adaptive_lr_section, exact_kl_section, kl_estimator_section, kl_penalty_section, kl_penalty_step, normalization_section,
-                   obs_reconstruction_coef, obs_reconstruction_section, polynomial_decay, process_episode_info, target_kl_rows,
-                   target_kl_section, previous_step_input_section, attention_statistics_section, attention_statistics_summary)
+from utils import kl_penalty_step, obs_reconstruction_coef, polynomial_decay, process_episode_info, target_kl_rows, attention_statistics_summary
 from rollout_plan import RolloutPlan, WorkerGroup, plan_rollout
-from checkpoint import check_checkpoint_config, segment_first_worker_id
+from checkpoint import segment_first_worker_id
+# the optional keys: their checks, the order in which they refuse and what they come to live in run_settings.py; the names stay
+# importable from here (tests, tools)
+from run_settings import (RunSettings, world_of, check_kernel_shapes, check_box_policy, check_byte_observation_transport,      # noqa: F401
+                          check_truncation_transport, check_action_mask_config, check_evaluation_config, check_normalization_config,
+                          check_target_kl_config, check_adaptive_lr_config, check_kl_estimator_config, check_exact_kl_config,
+                          check_kl_penalty_config, check_attention_statistics_config)
 from trainer_parts import _CheckpointResume, _DataParallelStep, _NativeRolloutDrive, _RunOutputs
 
 
@@ -91,255 +94,6 @@ def build_window_tables(memory_length: int, max_episode_length: int):
     return mask, indices
 
 
-def check_kernel_shapes(tcfg: dict):
-    """Fail early (before any environment or buffer is built) if the transformer shape is outside what the gfx950
-    kernels are built for; there is no fallback path."""
-    d, h, mem = tcfg["embed_dim"], tcfg["num_heads"], tcfg["memory_length"]
-    if d % h != 0:
-        raise ValueError("Embedding dimension needs to be divisible by the number of heads")
-    hd = d // h
-    problems = []
-    if d % 32 != 0 or d > 1024:
-        problems.append(f"embed_dim={d} (need a multiple of 32, <= 1024)")
-    if hd % 32 != 0 or hd > 128:
-        problems.append(f"head_dim={hd} (need 32, 64, 96 or 128)")
-    if mem > 128:
-        problems.append(f"memory_length={mem} (need <= 128)")
-    if not problems and ops.attention_supported(d, h, mem, ln=tcfg.get("layer_norm") == "pre",
-                                                pos_grad=tcfg.get("positional_encoding") == "learned") is None:
-        problems.append(f"attention backward at embed_dim={d}, num_heads={h}, memory_length={mem}, layer_norm="
-                        f"{tcfg.get('layer_norm')}, positional_encoding={tcfg.get('positional_encoding')} (LDS: see DESIGN.md section 6)")
-    if problems:
-        raise ValueError("transformer shape not supported by the MI355X kernels: " + "; ".join(problems))
-
-
-def check_box_policy(config: dict, A=None):
-    """Fail early for a Box (continuous) policy the fused kernels do not take: A = ``environment.continuous_actions`` (or the
-    dimension of the environment's Box) must lie in 1..8 and ``hidden_layer_size`` inside the Gaussian heads + loss kernel's
-    predicate (etm_heads_loss_supported_gaussian); there is no torch-autograd fallback.  None when the config is not a Box."""
-    if A is None:
-        A = config.get("environment", {}).get("continuous_actions")
-        if A is None:
-            return None
-    A, hid = int(A), int(config["hidden_layer_size"])
-    if not 1 <= A <= 8:
-        raise ValueError(f"Box action space of {A} dimensions: the fused Gaussian heads + loss kernel takes 1 to 8")
-    if not etm_lib.load().etm_heads_loss_supported_gaussian(1, hid, A):
-        raise ValueError(f"Box action space with hidden_layer_size={hid}: the fused Gaussian heads + loss kernel needs a multiple of 64, "
-                         "at most 512")
-    return A
-
-
-def check_byte_observation_transport(config, env=None):
-    """``worker_processes: true`` with ``observation_dtype: uint8`` is refused, before any environment or process is created: the
-    workers' shared segment types its observation rows as float32 (environments/shm_env.py)."""
-    env_cfg = config["environment"]
-    as_bytes = str(env_cfg.get("observation_dtype", "float32")) == "uint8" or is_byte_only(env_cfg.get("type"))      # (types with no float form)
-    if env is None and config.get("worker_processes", False) and as_bytes:
-        raise ValueError("worker_processes: true does not carry uint8 observations (the shared segment's rows are float32): "
-                         "set worker_processes: false (in-process environments keep the bytes), or let the environment emit float32")
-
-
-def check_truncation_transport(config, env=None):
-    """``worker_processes: true`` with ``bootstrap_truncated: true`` is refused, before any environment or process is created: the
-    workers' shared segment has no row for a final observation (environments/shm_env.py; a worker resets in place)."""
-    if env is None and config.get("worker_processes", False) and config.get("bootstrap_truncated", False):
-        raise ValueError("worker_processes: true does not carry bootstrap_truncated: true (the shared segment has no row for a final "
-                         "observation): set worker_processes: false (in-process environments hand it over in their info), or leave "
-                         "bootstrap_truncated off")
-
-
-def check_action_mask_config(config, env=None, action_space_shape=None, box=False):
-    """The optional key ``action_masks: true`` (invalid-action masking: one 64-bit word per worker and step, bit j = column j of the
-    concatenated policy head is allowed).  -> whether it is on; absent or false: nothing is allocated, no launch is added or exchanged.
-    Refused, each before anything is built from it: a Box policy (``environment.continuous_actions``, or ``box`` once the environment
-    is known); more than 63 actions over all branches (``action_space_shape``, or a Synthetic environment's ``num_actions``);
-    ``worker_processes: true`` without a supplied ``env`` (the workers' shared segment has no row for a mask word, as for
-    ``bootstrap_truncated``); an environment front-end without ``action_masks`` (``env``, once it exists).  Data-parallel runs need
-    nothing: the masks are per-rank data."""
-    if not config.get("action_masks", False):
-        return False
-    from environments import MAX_MASKED_ACTIONS
-    env_cfg = config.get("environment", {})
-    if box or env_cfg.get("continuous_actions") is not None:
-        raise ValueError("action_masks: true with a Box (continuous) action space: a Gaussian policy has no invalid actions to mask; "
-                         "remove the key (the environment's bounds already clip the actions)")
-    shape = action_space_shape
-    if shape is None and env_cfg.get("type") == "Synthetic" and "num_actions" in env_cfg:
-        n = env_cfg["num_actions"]
-        shape = tuple(n) if isinstance(n, (list, tuple)) else (int(n),)
-    if shape is not None and sum(int(a) for a in shape) > MAX_MASKED_ACTIONS:
-        raise ValueError(f"action_masks: true with {sum(int(a) for a in shape)} actions over all branches: a step's mask is one 64-bit word "
-                         f"per worker and takes at most {MAX_MASKED_ACTIONS}; remove the key, or reduce the action space")
-    if env is None and config.get("worker_processes", False):
-        raise ValueError("worker_processes: true does not carry action_masks: true (the shared segment has no row for a mask word): "
-                         "set worker_processes: false (in-process environments hand the words over each step), or remove the key")
-    if env is not None and not callable(getattr(env, "action_masks", None)):
-        raise ValueError(f"action_masks: true, but the environment front-end {type(env).__name__} has no action_masks(): let the "
-                         "environments offer action_masks() (environments/vec_env.py: the VecEnv protocol; a Synthetic environment needs "
-                         "environment.action_mask_p), or remove the key")
-    return True
-
-
-def check_evaluation_config(config, world: int = 1):
-    """The optional ``evaluation`` section (interval, episodes_per_worker, n_workers, deterministic, seed, worker_steps) -> a dict with
-    the defaults filled in, or None when the section is absent (never evaluate, allocate nothing).  ``evaluation.interval`` in a
-    data-parallel run (``world`` > 1) is refused, before any environment is built: every rank would have to take part in the same
-    evaluation -- evaluate the checkpoint with evaluate.py instead."""
-    ev = config.get("evaluation")
-    if ev is None:
-        return None
-    known = ("interval", "episodes_per_worker", "n_workers", "deterministic", "seed", "worker_steps")
-    unknown = sorted(set(ev) - set(known))
-    if unknown:
-        raise ValueError(f"evaluation: unknown keys {unknown} (known: {list(known)})")
-    out = dict(interval=int(ev.get("interval", 0) or 0), episodes_per_worker=int(ev.get("episodes_per_worker", 1)),
-               n_workers=int(ev.get("n_workers", config["n_workers"])), deterministic=bool(ev.get("deterministic", True)),
-               seed=int(ev.get("seed", 100000)), worker_steps=ev.get("worker_steps"))
-    if out["interval"] < 0 or out["episodes_per_worker"] < 1 or out["n_workers"] < 1:
-        raise ValueError("evaluation: interval >= 0, episodes_per_worker >= 1 and n_workers >= 1 are required")
-    if out["interval"] > 0 and world > 1:
-        raise ValueError("evaluation.interval in a data-parallel run: periodic evaluation runs on one rank's device only; "
-                         "evaluate the checkpoint with evaluate.py instead")
-    return out
-
-
-def check_normalization_config(config, world: int = 1, observation_shape=None, observation_dtype=None):
-    """The optional keys ``normalize_observations`` and ``normalize_rewards`` (each ``true`` or {clip, epsilon}) -> {"observations":
-    section or None, "rewards": section or None} with the defaults filled in.  Refused, each before anything is allocated: unknown
-    sub-keys, ``clip <= 0`` or ``epsilon <= 0`` (utils.normalization_section); either key in a data-parallel run (``world`` > 1: the
-    ranks' statistics would have to be merged, which this build does not do); ``normalize_observations`` with image or uint8
-    observations (``observation_shape`` / ``observation_dtype``, once the environment is known) or with more features than the
-    statistics kernel takes."""
-    out = {"observations": normalization_section(config, "normalize_observations"), "rewards": normalization_section(config, "normalize_rewards")}
-    on = [k for k, key in (("normalize_observations", "observations"), ("normalize_rewards", "rewards")) if out[key] is not None]
-    if on and world > 1:
-        raise ValueError(f"{' / '.join(on)} in a data-parallel run: every rank would keep statistics of its own workers only (merging "
-                         "them over the ranks is not built); remove the key(s), or train on one device")
-    if out["observations"] is not None and observation_shape is not None:
-        if len(tuple(observation_shape)) != 1 or observation_dtype == torch.uint8:
-            raise ValueError(f"normalize_observations with image / uint8 observations of shape {tuple(observation_shape)}: they are already "
-                             "in [0, 1] (byte k = k / 255); remove the key -- it is for float32 vector observations")
-        if not ops.obs_stats_supported(int(observation_shape[0])):
-            raise ValueError(f"normalize_observations with {int(observation_shape[0])} features: the statistics kernel takes 1 to 1024; "
-                             "remove the key or reduce the observation")
-    return out
-
-
-def check_target_kl_config(config, world: int = 1):
-    """The optional key ``target_kl`` (a number or {value, factor, host_check}; utils.target_kl_section) -> {"value", "factor",
-    "host_check", "limit"} or None when the key is absent (nothing is allocated, no launch is added or exchanged).  Refused, each before
-    anything is allocated: a value or factor that is no finite number > 0, unknown sub-keys, a ``host_check`` other than "epoch" /
-    "none"; the key in a data-parallel run (``world`` > 1): every rank sees the KL of its own minibatch, and agreeing on one is not
-    built."""
-    out = target_kl_section(config)
-    if out is not None and world > 1:
-        raise ValueError("target_kl in a data-parallel run: every rank would stop on the KL of its own minibatch and the replicas would "
-                         "part (agreeing on one KL over the ranks is not built); remove the key, or train on one device")
-    return out
-
-
-def check_adaptive_lr_config(config, world: int = 1):
-    """The optional key ``adaptive_lr`` (a number: the desired KL, or {desired_kl, factor, low, high, min, max};
-    utils.adaptive_lr_section) -> the rule with its float32 constants, or None when the key is absent (nothing is allocated, no launch
-    is added or exchanged).  Refused, each before anything is allocated and each with what to do instead: values outside their ranges
-    and unknown sub-keys (utils.adaptive_lr_section); a start value float32(learning_rate_schedule.initial) outside [min, max]; a
-    ``learning_rate_schedule`` that decays (final != initial): two schedules would compete for one number; the key in a data-parallel
-    run (``world`` > 1): every rank sees the KL of its own minibatch, and agreeing on one is not built."""
-    out = adaptive_lr_section(config)
-    if out is None:
-        return None
-    if world > 1:
-        raise ValueError("adaptive_lr in a data-parallel run: every rank would move its learning rate on the KL of its own minibatch and "
-                         "the replicas would part (agreeing on one KL over the ranks is not built); remove the key, or train on one device")
-    sched = config["learning_rate_schedule"]
-    if sched["final"] != sched["initial"]:
-        raise ValueError(f"adaptive_lr with a decaying learning_rate_schedule (initial {sched['initial']!r}, final {sched['final']!r}): the "
-                         "two schedules compete for one learning rate; set learning_rate_schedule.final to initial (it is the start value "
-                         "only), or remove the key adaptive_lr")
-    start = float(np.float32(sched["initial"]))
-    if not out["min"] <= start <= out["max"]:
-        raise ValueError(f"adaptive_lr: the start value float32(learning_rate_schedule.initial) = {start!r} lies outside [min, max] = "
-                         f"[{out['min']!r}, {out['max']!r}]; move initial into the range, or widen adaptive_lr.min / adaptive_lr.max")
-    return out
-
-
-def check_kl_estimator_config(config, box: bool = False, world: int = 1):
-    """The optional key ``kl_estimator`` (utils.kl_estimator_section) -> "k3" (absent: nothing is allocated, no launch is added or
-    exchanged) or "analytic": the statistic ``kl`` -- what ``other/kl`` shows and what ``target_kl`` and ``adaptive_lr`` decide on -- is
-    the exact KL of the rollout's and the current Gaussian of a Box policy instead of the sample estimate.  Refused, each before
-    anything is built and each with what to do instead: a value other than ``k3`` / ``analytic``; ``analytic`` without a Box policy
-    (``box``: a categorical policy's exact KL would need every old logit stored); ``analytic`` in a data-parallel run (``world`` > 1),
-    as for the other KL keys."""
-    kind = kl_estimator_section(config)
-    if kind != "analytic":
-        return kind
-    if not box:
-        raise ValueError("kl_estimator: analytic without a Box (continuous) action space: the exact KL is built for diagonal Gaussian "
-                         "policies only (a categorical policy's would need every old logit stored); categorical policies keep k3: "
-                         "remove the key, or replace it with `exact_kl: true` (the exact KL of every policy kind)")
-    if world > 1:
-        raise ValueError("kl_estimator: analytic in a data-parallel run: every rank would see the KL of its own minibatch (agreeing on one "
-                         "KL over the ranks is not built); remove the key, or train on one device")
-    return kind
-
-
-def check_exact_kl_config(config, box: bool = False, world: int = 1) -> bool:
-    """The optional key ``exact_kl`` (utils.exact_kl_section) -> False (absent or ``false``: nothing is allocated, no launch is added
-    or exchanged) or True: the statistic ``kl`` -- what ``other/kl`` shows and what ``target_kl`` and ``adaptive_lr`` decide on -- is the
-    exact KL(old || new) of the rollout's and the current policy for EVERY policy kind.  For a Box policy (``box``) that is exactly
-    ``kl_estimator: analytic``; for Discrete and MultiDiscrete policies, masked or not, the four categorical sampling sites stage
-    every column's log-prob and the loss kernels reduce ``utils.categorical_kl``.  Refused, each before anything is built and each
-    with what to do instead: a value that is no bool; ``exact_kl: true`` next to an explicit ``kl_estimator: k3`` (they contradict
-    each other); the key in a data-parallel run (``world`` > 1), as for the other KL keys."""
-    on = exact_kl_section(config)
-    if not on:
-        return False
-    if "kl_estimator" in config and kl_estimator_section(config) == "k3":
-        raise ValueError("exact_kl: true next to kl_estimator: k3: the two keys contradict each other (k3 is the sample estimate); "
-                         "remove kl_estimator for the exact KL, or remove exact_kl to keep the sample estimate")
-    if world > 1:
-        raise ValueError("exact_kl: true in a data-parallel run: every rank would see the KL of its own minibatch (agreeing on one "
-                         "KL over the ranks is not built); remove the key, or train on one device")
-    return True
-
-
-def check_kl_penalty_config(config, world: int = 1):
-    """The optional key ``kl_penalty`` (a number: a fixed coefficient, or {coef, target, high, low, up, down, min, max};
-    utils.kl_penalty_section) -> the section with its float32 constants, or None when the key is absent (nothing is allocated, no launch
-    is added or exchanged).  With the key the loss is L + coef * KL(old || new), the exact KL that ``exact_kl: true`` reports -- the key
-    implies that plumbing for every policy kind -- and with ``target`` the coefficient adapts once per update (utils.kl_penalty_step).
-    Refused, each before anything is built and each with what to do instead: what utils.kl_penalty_section refuses; an explicit
-    ``exact_kl: false`` or ``kl_estimator: k3`` next to the key (they contradict it); the key in a data-parallel run (``world`` > 1),
-    as for the other KL keys."""
-    out = kl_penalty_section(config)
-    if out is None:
-        return None
-    if "exact_kl" in config and not exact_kl_section(config):
-        raise ValueError("kl_penalty next to exact_kl: false: the two keys contradict each other (the penalty is a term in the exact KL "
-                         "and switches its plumbing on); remove exact_kl, or remove kl_penalty to train without the penalty")
-    if "kl_estimator" in config and kl_estimator_section(config) == "k3":
-        raise ValueError("kl_penalty next to kl_estimator: k3: the two keys contradict each other (the penalty is a term in the exact KL, "
-                         "k3 is the sample estimate); remove kl_estimator, or remove kl_penalty to train without the penalty")
-    if world > 1:
-        raise ValueError("kl_penalty in a data-parallel run: every rank would penalise and adapt on the KL of its own minibatches "
-                         "(agreeing on one KL over the ranks is not built); remove the key, or train on one device")
-    return out
-
-
-def check_attention_statistics_config(config, world: int = 1) -> bool:
-    """The optional key ``attention_statistics`` (utils.attention_statistics_section) -> False (absent or ``false``: nothing is
-    allocated, launched or changed) or True: every grad-enabled forward pass of an update adds its attention probabilities to a
-    per-block, per-head table (etm_attn_stats), read once per update into ``last_attention_statistics``.  Refused, each before
-    anything is built and each with what to do instead: a value that is no bool; the key in a data-parallel run (``world`` > 1):
-    every rank sees its own minibatches, and merging the ranks' tables is not built."""
-    on = attention_statistics_section(config)
-    if on and world > 1:
-        raise ValueError("attention_statistics: true in a data-parallel run: every rank would count the attention of its own minibatches "
-                         "only (merging the tables over the ranks is not built); remove the key, or train on one device")
-    return on
-
-
 def time_major(table, src):
     """The host table ``src`` [W, S(, B)] in the layout and type of the fixed-address device table ``table`` [S, W(, B)]."""
     x = torch.as_tensor(np.asarray(src), dtype=table.dtype)
@@ -351,7 +105,25 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
                  first_worker_id: int = 0, tensorboard: bool = True, resume: str = None) -> None:
         """``resume``: the path of a training checkpoint (``save_checkpoint``) to continue from: the file is read and verified first,
         the environments are built with the worker ids of the next training segment, and the state is loaded in place once everything
-        exists (``load_checkpoint`` without a second restart) -- also with ``worker_processes: true``."""
+        exists (``load_checkpoint`` without a second restart) -- also with ``worker_processes: true``.
+
+        Seven stages; within and across them every statement that allocates device or pinned memory, draws from a generator, creates a
+        stream or an event or touches the environment keeps its place in the order (keyed runs stay bit-equal, the allocator sees the
+        same requests)."""
+        resumed, first_worker_id = self._init_settings(config, run_id, device, env, dp, first_worker_id, tensorboard, resume)
+        self._init_environment(env, first_worker_id)
+        self._init_learner()
+        self._init_pinned_staging(resumed, first_worker_id)
+        self._init_step_operands()
+        self._init_kv_cache_and_replays()
+        self._init_worker_groups_and_tables()
+        if resumed is not None:
+            self._load_state(resumed, str(resume), restart=False)
+
+    def _init_settings(self, config, run_id, device, env, dp, first_worker_id, tensorboard, resume):
+        """Stage 1: the device, the library, the optional keys (``self.settings``: run_settings.RunSettings, stage one -- every refusal
+        the config alone gives, in the order stated there) and the state a checkpoint carries over.  -> (the verified checkpoint or
+        None, the first worker id of this training segment)."""
         if device is None:
             device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
         device = torch.device(device)
@@ -373,27 +145,8 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         self.cr_schedule = config["clip_range_schedule"]
         t = config["transformer"]
         self.memory_length, self.num_blocks, self.embed_dim = t["memory_length"], t["num_blocks"], t["embed_dim"]
-        check_kernel_shapes(t)
-        check_box_policy(config)
-        check_byte_observation_transport(config, env)
-        check_truncation_transport(config, env)
-        if env is None:       # environment.device: true (a device-resident type) against the transports and the world size
-            check_device_env_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
-        check_action_mask_config(config, env)
-        # previous_step_input: the value itself and the transport, before any environment or process is created (the shared segment of
-        # the worker processes has no row for the last reward); the action space is looked at below
-        previous_step_input_section(config, worker_processes=bool(env is None and config.get("worker_processes", False)))
-        check_evaluation_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
-        check_normalization_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
-        check_checkpoint_config(config, 1 if dp is None else int(getattr(dp, "world", 1)), resume=resume is not None)
-        kl_cfg = check_target_kl_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
-        adapt_cfg = check_adaptive_lr_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
-        # (a supplied environment says what the policy is once it is looked at, below; else the config does, before anything is built)
-        check_kl_estimator_config(config, env is not None or check_box_policy(config) is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
-        check_exact_kl_config(config, check_box_policy(config) is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
-        pen_cfg = check_kl_penalty_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
-        obs_reconstruction_section(config, world=1 if dp is None else int(getattr(dp, "world", 1)))      # (the value; the observation's shape below)
-        attn_stats_on = check_attention_statistics_config(config, 1 if dp is None else int(getattr(dp, "world", 1)))
+        self._world = world_of(dp)
+        self.settings = RunSettings.before_environment(config, self._world, env, resume is not None)
         # training state that a checkpoint carries over (trainer_parts._CheckpointResume): completed updates, the training segment (the
         # number of resumes so far; its environments' worker ids start at segment_first_worker_id), the last episodes' infos
         self.update_index, self.segment, self._episode_infos = 0, 0, deque(maxlen=100)
@@ -404,7 +157,12 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             self.segment = int(resumed["segment"]) + 1
             first_worker_id = segment_first_worker_id(first_worker_id, self.segment)
         self.writer = _make_writer(run_id) if tensorboard else _NullWriter()
+        return resumed, first_worker_id
 
+    def _init_environment(self, env, first_worker_id):
+        """Stage 2: the worker groups' number, the host CPU plan, the environments (``env``: a supplied front-end or None) and, with what
+        they say about observations and actions, stage two of the settings -- the refusals that need the environment."""
+        config = self.config
         # environments (batched front-end over the upstream per-worker protocol)
         # rollout_groups (default "auto": 2): the workers are stepped as that many groups in a software
         # pipeline -- while the host steps one group's environments the device runs the other groups' forward passes (small step
@@ -432,7 +190,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # the threads that write a step's observation rows: the copier's (frame ring) or the generator pool's (pool: 0, fresh draws)
         row_threads = ("gen_threads" if int(env_cfg.get("pool", 64)) == 0 else "copy_threads") if env_cfg.get("type") == "Synthetic" else None
         self._host_plan = hostcpu.plan_host_threads(copy_threads=int(env_cfg.get(row_threads, 1)) if row_threads else 1,
-                                                    worker_processes=bool(env is None and config.get("worker_processes", False)),
+                                                    worker_processes=self.settings.worker_processes,
                                                     num_envs=self.num_workers, envs_per_process=int(config.get("envs_per_process", 1)),
                                                     groups=n_groups, quiet=not config.get("host_cpu_plan", True))
         if not config.get("host_cpu_plan", True):
@@ -451,7 +209,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # HIP-registered segment (environments/shm_env.py): they take their actions straight from the device and step concurrently;
         # the per-step host loop is then the native driver of the kernel library (etm_rollout_drive) -- see _sample_training_data
         self._shm_env = None
-        if env is None and config.get("worker_processes", False):
+        if self.settings.worker_processes:
             from environments.shm_env import ShmVecEnv
             self._shm_env = ShmVecEnv(env_cfg, self.num_workers, first_worker_id, groups=n_groups,
                                       envs_per_proc=self._host_plan["envs_per_process"], steps_per_rollout=config["worker_steps"],
@@ -461,17 +219,12 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         self._env_cfg, self._env_groups = env_cfg, n_groups      # (the evaluator rebuilds its environments from these)
         self._evaluator = None            # evaluation.Evaluator, allocated by the first evaluate()
         self._draw_generator = None       # the rollout's draws come from torch's generator of the device (None) or from this one
-        W = self.num_workers
         obs_shape = tuple(self.env.observation_space_shape)
         self.observation_space = type("Space", (), {"shape": obs_shape})()
         # uint8 image observations stay bytes from the environment's row to the first encoder layer's loads (byte k stands for
         # float32(k) / float32(255)): the environment says so (``observation_dtype``, or else ``observation_space.dtype``)
         from environments import observation_dtype as _observation_dtype
         self.observation_dtype = torch.uint8 if _observation_dtype(self.env) == np.uint8 else torch.float32
-        if self.observation_dtype == torch.uint8:
-            if len(obs_shape) < 2:
-                raise ValueError("uint8 observations are images (byte k = k / 255); a vector observation must be float32")
-        check_normalization_config(config, 1 if dp is None else int(getattr(dp, "world", 1)), obs_shape, self.observation_dtype)
         # one branch per action dimension, from the environment (environments.action_space_shape: Discrete(n) -> (n,), MultiDiscrete
         # -> nvec); Discrete is upstream's single branch (trainer.py:47)
         self.action_space_shape = tuple(int(a) for a in getattr(self.env, "action_space_shape", None) or (self.env.num_actions,))
@@ -481,36 +234,37 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if kind is None and hasattr(self.env, "action_space"):
             kind = action_space_kind(self.env.action_space)
         self.box = kind if kind is not None and kind.is_box else None
-        if self.box is not None:
-            check_box_policy(config, self.box.shape[0])
         self.max_episode_length = self.env.max_episode_steps
-        # action_masks: the environment's front-end, the width of the policy head and the kind of policy are known now
-        self._masked = check_action_mask_config(config, self.env, self.action_space_shape, self.box is not None)
+        # the environment's front-end, the observations, the width of the policy head and the kind of policy are known now
+        s = self.settings = self.settings.with_environment(self.env, obs_shape, self.observation_dtype, self.action_space_shape, self.box)
+        # action_masks
+        self._masked = s.masked
         self.last_valid_action_share = None       # mean share of allowed actions in the last rollout's words (None without the key)
-        # previous_step_input: {"action", "reward"} or None (the kind of policy and the table's rows are known now)
-        self._prev_cfg = previous_step_input_section(config, self.action_space_shape, box=self.box is not None)
-        # kl_estimator: the kind of policy is known now.  "analytic": the four Gaussian sampling sites stage the means, the buffer
-        # carries them and a snapshot of the log-std, the Gaussian heads + loss kernel reduces the exact KL into stats[4]
-        self._kl_analytic = check_kl_estimator_config(config, self.box is not None, 1 if dp is None else int(getattr(dp, "world", 1))) == "analytic"
-        # exact_kl: a Box policy takes exactly that path; a categorical one (masked or not) stages every column's log-prob at the four
-        # categorical sampling sites, the buffer carries the rows, the categorical loss kernels reduce the exact KL into stats[4]
-        exact = check_exact_kl_config(config, self.box is not None, 1 if dp is None else int(getattr(dp, "world", 1)))
-        # kl_penalty implies the exact KL's plumbing (the penalty is coef times the very number that column 4 then holds).  The
-        # coefficient lives in ONE device float32 at a fixed address: the loss kernels read it in place, in eager steps and in captured
-        # graphs alike; the host writes it between updates only (_adapt_kl_penalty).  ``last_kl_penalty``: what the last update used and
-        # decided (None without the key: nothing is allocated)
-        exact = exact or pen_cfg is not None
-        self._kl_pen, self._kl_coef, self.last_kl_penalty = pen_cfg, None, None
-        if pen_cfg is not None:
-            self._kl_coef = torch.full((1,), pen_cfg["coef"], dtype=torch.float32, device=device)
-        self._kl_analytic = self._kl_analytic or (exact and self.box is not None)
-        self._kl_exact_cat = exact and self.box is None
-        # obs_reconstruction: the schedule of the auxiliary loss's coefficient, or None.  The coefficient lives in ONE device float32 at a
-        # fixed address that the fused last layer + loss kernel reads in place, in eager steps and captured graphs alike; the host writes
-        # it once per update, outside every graph (_train_epochs).  Every step files its (unscaled) reconstruction loss in a device table
-        # of its own under a device counter; the eight statistics columns are untouched.  ``last_obs_reconstruction``: {"loss", "coef"} of
-        # the last update (None without the key: nothing is allocated)
-        self._recon = obs_reconstruction_section(config, obs_shape, 1 if dp is None else int(getattr(dp, "world", 1)))
+        # previous_step_input: {"action", "reward"} or None
+        self._prev_cfg = s.prev
+        # kl_estimator "analytic": the four Gaussian sampling sites stage the means, the buffer carries them and a snapshot of the
+        # log-std, the Gaussian heads + loss kernel reduces the exact KL into stats[4].  exact_kl: a Box policy takes exactly that path; a
+        # categorical one (masked or not) stages every column's log-prob at the four categorical sampling sites, the buffer carries the
+        # rows, the categorical loss kernels reduce the exact KL into stats[4].  kl_penalty implies the exact KL's plumbing (the penalty is
+        # coef times the very number that column 4 then holds).  (run_settings.kl_plumbing)
+        self._kl_analytic, self._kl_exact_cat = s.kl_analytic, s.kl_exact_cat
+        # obs_reconstruction: the schedule of the auxiliary loss's coefficient, or None
+        self._recon = s.recon
+
+    def _init_learner(self):
+        """Stage 3: the per-feature device words, the buffer, the model, the optimiser and what hangs on them."""
+        config, device, dp, s = self.config, self.device, self.dp, self.settings
+        # kl_penalty: the coefficient lives in ONE device float32 at a fixed address: the loss kernels read it in place, in eager steps and
+        # in captured graphs alike; the host writes it between updates only (_adapt_kl_penalty).  ``last_kl_penalty``: what the last
+        # update used and decided (None without the key: nothing is allocated)
+        self._kl_pen, self._kl_coef, self.last_kl_penalty = s.kl_penalty, None, None
+        if self._kl_pen is not None:
+            self._kl_coef = torch.full((1,), self._kl_pen["coef"], dtype=torch.float32, device=device)
+        # obs_reconstruction: the coefficient lives in ONE device float32 at a fixed address that the fused last layer + loss kernel reads
+        # in place, in eager steps and captured graphs alike; the host writes it once per update, outside every graph (_train_epochs).
+        # Every step files its (unscaled) reconstruction loss in a device table of its own under a device counter; the eight statistics
+        # columns are untouched.  ``last_obs_reconstruction``: {"loss", "coef"} of the last update (None without the key: nothing is
+        # allocated)
         self._recon_coef = self._recon_tab = self._recon_row = self.last_obs_reconstruction = None
         if self._recon is not None:
             self._recon_coef_host = obs_reconstruction_coef(self._recon, 0)
@@ -577,12 +331,13 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # utils.attention_statistics_summary of the last update's table -- its ``rows`` say how many rows were counted: every pass that
         # was launched counts, also those of an update ``target_kl`` stopped (None without the key: nothing is allocated)
         self._attn_stats, self.last_attention_statistics = None, None
-        if attn_stats_on:
+        if s.attention_statistics:
             t_ = config["transformer"]
             self._attn_stats = ops.AttentionStatistics(t_["num_blocks"], t_["num_heads"], self.buffer.batch_size, t_["memory_length"], device)
             self.model.transformer.attn_stats = self._attn_stats
         # target_kl: the gate of the KL early stop (etm/optim.py: KlGate), reset at the start of every update; not trainer state, not in
         # the checkpoint.  ``last_kl_stop``: what the last update's gate said (None without the key: nothing is allocated)
+        kl_cfg = s.target_kl
         self._kl_cfg, self._kl_gate, self.last_kl_stop = kl_cfg, None, None
         if kl_cfg is not None:
             self._kl_gate = KlGate(kl_cfg["limit"], device, host_word=kl_cfg["host_check"] == "epoch")
@@ -592,10 +347,14 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         # the optimiser's state; the two counters are per update.  ``last_adaptive_lr``: the rate and the counters after the last update
         # (None without the key: nothing is allocated)
         self._adapt, self.last_adaptive_lr = None, None
-        if adapt_cfg is not None:
-            self._adapt = AdaptiveLr(adapt_cfg, device)
+        if s.adaptive_lr is not None:
+            self._adapt = AdaptiveLr(s.adaptive_lr, device)
             self.optimizer.attach_adaptive(self._adapt)
 
+    def _init_pinned_staging(self, resumed, first_worker_id):
+        """Stage 4: the pinned blocks the host and the device hand observations, actions, (step, slot), mask words and rewards over in,
+        and the environments' first observations in them."""
+        device, W, obs_shape, box = self.device, self.num_workers, self.observation_space.shape, self.box is not None
         # host <-> device staging (pinned)
         if self._shm_env is not None:
             # observation rows and action words live in the workers' shared segment, registered with the HIP runtime: the copy
@@ -645,6 +404,10 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         if self._masked:
             self._take_action_masks(self.env, 0, W, "reset")
 
+    def _init_step_operands(self):
+        """Stage 5: the fixed-address operands of the rollout step, the time-major staging of its outputs, the draw tables and the
+        upload stream."""
+        config, device, W, obs_shape, box = self.config, self.device, self.num_workers, self.observation_space.shape, self.box is not None
         # fixed-address operands of the rollout step (HIP-graph friendly) and time-major staging of the step outputs
         S, L, B = config["worker_steps"], self.memory_length, self._action_width
         self._obs_dev = torch.zeros((W,) + obs_shape, dtype=self.observation_dtype, device=device)
@@ -681,6 +444,10 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         self._plan = None            # the form of the captured step (rollout_plan.RolloutPlan), decided when it is captured
         self._stage_host = None      # host view of the staging array (direct observation rows)
         self._stage_read = torch.cuda.Event()      # (direct rows) the update's copy out of the staging array has run
+
+    def _init_kv_cache_and_replays(self):
+        """Stage 6: the rollout's K|V cache and the replays (cache refresh, last value, bootstrap pass) with their operands."""
+        config, device, W, L, B = self.config, self.device, self.num_workers, self.memory_length, self._action_width
         # rollout K/V cache (weights are frozen while sampling): per worker [T, blocks, 2D] projections of its episode
         self._use_kv_cache = bool(config.get("kv_cache_rollout", True))
         T, nb, D = self.max_episode_length, self.num_blocks, self.embed_dim
@@ -706,6 +473,9 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
             if self._prev_cfg is not None:
                 bs.pa, bs.pr = torch.zeros((W, B), dtype=torch.int64, device=device), torch.zeros(W, dtype=torch.float32, device=device)
 
+    def _init_worker_groups_and_tables(self):
+        """Stage 7: the worker groups over everything above, and the window tables."""
+        device, W = self.device, self.num_workers
         # worker groups: the full-width group (eager path, single-group graph path) aliases the buffers above; the pipelined
         # groups own what cannot be a contiguous slice of them.  WorkerGroup reads from this object, so all of these exist by now:
         # device, box, _action_width, num_blocks, embed_dim, num_workers, obs / _obs_pin / _act_pin, _ss_pin / _ss_dev, _obs_dev,
@@ -721,8 +491,6 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
         self._mask_table = mask.bool().contiguous().to(device)
         self._index_table = indices.contiguous().to(device)
         self.last_update_timing = {}
-        if resumed is not None:
-            self._load_state(resumed, str(resume), restart=False)
 
     def _take_action_masks(self, env, lo, hi, step):
         """``action_masks: true``: the words of the observations ``env`` (workers [lo, hi)) returned last -> the pinned block the next
@@ -781,8 +549,7 @@ class PPOTrainer(_DataParallelStep, _NativeRolloutDrive, _RunOutputs, _Checkpoin
     def run_training(self) -> None:
         print("Step 6: Starting training using " + str(self.device))
         episode_infos = self._episode_infos
-        ckpt_every = check_checkpoint_config(self.config, 1 if self.dp is None else int(getattr(self.dp, "world", 1)))
-        ev_cfg = check_evaluation_config(self.config, 1 if self.dp is None else int(getattr(self.dp, "world", 1)))
+        ckpt_every, ev_cfg = self.settings.checkpoint_interval, self.settings.evaluation
         ev_every = ev_cfg["interval"] if ev_cfg is not None else 0
         for update in range(self.update_index, self.config["updates"]):       # (a resumed run starts at the stored index)
             lr, beta, clip = self.schedules(update)

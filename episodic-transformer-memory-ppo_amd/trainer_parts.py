@@ -434,7 +434,7 @@ class _CheckpointResume:
             raise ValueError("load_checkpoint on a live trainer with worker_processes: true: the worker processes' environments cannot "
                              "be restarted in place; build the trainer with PPOTrainer(..., resume=path) (train.py --resume PATH)")
         import checkpoint as ck
-        ck.check_checkpoint_config(self.config, 1 if self.dp is None else int(getattr(self.dp, "world", 1)), resume=True)
+        ck.check_checkpoint_config(self.config, self._world, resume=True)
         self._load_state(self._read_verified(path), str(path), restart=True)
 
     def _load_state(self, state, what, restart):

@@ -76,10 +76,25 @@ def test_evaluation_section_defaults_and_refusals():
 
 def test_trainer_checks_evaluation_before_building_environments():
     """The constructor asks check_evaluation_config with the data-parallel world before it creates the writer or any environment."""
+    import types
+
+    import torch
     import trainer
-    src = inspect.getsource(trainer.PPOTrainer.__init__)
-    assert 0 < src.index("check_evaluation_config(") < src.index("_make_writer(") < src.index("make_vec_env(")
-    assert src.index("check_evaluation_config(") < src.index("ShmVecEnv(")
+    from environments import shm_env
+    built = []
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(trainer, "_make_writer", lambda *a, **k: built.append("writer"))
+        mp.setattr(trainer, "make_vec_env", lambda *a, **k: built.append("make_vec_env"))
+        mp.setattr(shm_env, "ShmVecEnv", lambda *a, **k: built.append("ShmVecEnv"))
+        for worker_processes in (False, True):
+            cfg = _base_config(evaluation=dict(interval=1), worker_processes=worker_processes, hidden_layer_size=64,
+                               transformer=dict(num_blocks=2, embed_dim=64, num_heads=2, memory_length=8, positional_encoding="relative",
+                                                layer_norm="post", gtrxl=False, gtrxl_bias=0.0),
+                               **{k: dict(initial=1e-3, final=1e-3, power=1.0, max_decay_steps=10)
+                                  for k in ("learning_rate_schedule", "beta_schedule", "clip_range_schedule")})
+            with pytest.raises(ValueError, match="evaluation.interval in a data-parallel run"):
+                trainer.PPOTrainer(cfg, device=torch.device("cuda", 0), dp=types.SimpleNamespace(world=2, rank=0))      # (no device is touched)
+    assert built == []
 
 
 def test_uniforms_with_deterministic_is_a_value_error():
